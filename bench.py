@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""bench.py — ICP iterations/s (+ occupancy cells ray-cast/s) on N MI355X GPUs.
+"""bench.py — ICP iterations/s (with --full, also occupancy cells ray-cast/s and more) on N MI355X GPUs.
 
 A *step* is one pass of the hot path over one batch of synthetic 2 048-beam scan
 pairs resident in HBM: per pair exactly what the reference's ``ICP()`` call does
@@ -7,13 +7,20 @@ pairs resident in HBM: per pair exactly what the reference's ``ICP()`` call does
 with the config.yaml parameters of BASELINE config 2), ``--pairs-per-gpu`` pairs
 per GPU (the batched loop-closure shape of config 5), followed by the all_gather
 of the result records.  The main line is weak scaling (every rank owns its own
-pairs); BASELINE config 5 as written — 512 candidate pairs in all — rides on the
-same line as ``config5_512`` (one GPU) / ``strong_512`` (N GPUs, 512/N pairs each).
+pairs); with ``--full``, BASELINE config 5 as written — 512 candidate pairs in all —
+rides on the same line as ``config5_512`` (one GPU) / ``strong_512`` (N GPUs, 512/N pairs each).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
     python bench.py --gpus 8 --steps 20 --warmup 3      # starts 8 child ranks itself (torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
            --master-port 29500 bench.py --gpus 8 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full                  # + every other leg (see below)
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR      # + the last step's results as DIR/*.npy
+
+A plain run measures the main line only: set-up, ``--warmup`` untimed steps, ``--steps`` timed steps, the result line.
+``--full`` adds the other legs: BASELINE config 5 (512 pairs, with and without the rotation search), single-pair
+latency, pipelined batches, the exhaustive NN kernel, the submap, the host API, ray casting, the pose graph and the CPU
+baselines (``--no-cpu-baseline``, ``--no-raycast`` and ``--no-extras`` trim that set).
 
 Rank 0 prints ONE JSON line.
 """
@@ -33,6 +40,8 @@ for p in (REPO, os.path.join(REPO, "iterative-closest-point-avmi_amd")):
 HBM_PEAK_GBS = 8000.0            # MI355X HBM3E spec (MI355X_MICROARCH.md; 6 290 GB/s measured copy)
 FP64_VALU_PEAK_TOPS = 39.3       # 78.6 TFLOP/s vector FP64 counts an FMA as 2; the NN loop issues plain ops
 ICP_KW = dict(error_threshold=1e-10, max_iterations=150, voxel_size=0.04, method="point_to_line", normal_k=12)
+DUMP_MAX_PAIRS = (64 * 10**6 - 8 * 1024) // 88   # --dump-outputs: 80 B of fields + 8 B of index per pair, under 64 MB
+                                                # with room for the headers of its 7 .npy files (128 B each)
 
 
 def free_port():
@@ -155,9 +164,10 @@ class Leg:
     """One timed leg of the hot path: a resident IcpBatch of B pairs per rank, K steps, barrier + synchronize on both
     sides, MAX over ranks; every step = voxel x2 + prepare + fused ICP + (world > 1) the all_gather of the results."""
 
-    def __init__(self, torch, dist, IcpBatch, gather_results, synth, B, rank, world, red_dev, seed0):
+    def __init__(self, torch, dist, IcpBatch, gather_results, synth, B, rank, world, red_dev, seed0, pairs=None):
         self.torch, self.dist, self.gather, self.B, self.rank, self.world, self.red_dev = torch, dist, gather_results, B, rank, world, red_dev
-        self.srcs, self.tgts = synth.loop_closure_batch(B, seed0=seed0 + 100003 * rank)
+        # pairs: the (srcs, tgts) of synth.loop_closure_batch(B, seed0 + 100003 * rank), when built beforehand (make_pairs)
+        self.srcs, self.tgts = pairs or synth.loop_closure_batch(B, seed0=seed0 + 100003 * rank)
         self.batch = IcpBatch(self.srcs + self.tgts, np.arange(B), np.arange(B, 2 * B), **ICP_KW)
         self.n_total = B * world
 
@@ -187,6 +197,7 @@ class Leg:
             elapsed = float(tmax.item())
         from icpmi import _lib
         res = out.cpu().numpy()                               # all pairs of all ranks (gathered) or the local batch
+        self.last = res[:self.n_total]
         self.iters_per_step = float(res[:self.n_total, _lib.RES_ITERS].sum())
         settled = res[:self.n_total, _lib.RES_STATUS] == _lib.ST_CONVERGED
         self.settled_pairs = int(settled.sum())
@@ -230,6 +241,70 @@ class Leg:
         return r
 
 
+def pairs_chunk(job):
+    """Pairs lo..hi-1 of icpmi.synth.loop_closure_batch(n, seed0) with its default candidate poses: every pair draws
+    from seeds of its own (pose: seed0 + i; source scan: seed0 + 7919 (i + 1); target scan: seed0 + i), so a range of
+    pairs is built alone, bit for bit as in the whole batch (tests/test_host_cpu.py::test_bench_pairs_equal_synth)."""
+    from icpmi import synth
+    lo, hi, seed0 = job
+    base, max_offset, max_yaw_deg = (0.5, -0.3, 0.1), 0.6, 6.0
+    srcs, tgts = [], []
+    for i in range(lo, hi):
+        rng = np.random.default_rng(seed0 + i)
+        while True:
+            d = rng.uniform(0.0, max_offset)
+            a = rng.uniform(-np.pi, np.pi)
+            th = np.deg2rad(rng.uniform(-max_yaw_deg, max_yaw_deg))
+            pose_t = (base[0] + d * np.cos(a), base[1] + d * np.sin(a), base[2] + th)
+            if synth._free_pose(pose_t[0], pose_t[1]):
+                break
+        srcs.append(synth.scan(base, seed0 + 7919 * (i + 1)))
+        tgts.append(synth.scan(pose_t, seed0 + i))
+    return srcs, tgts
+
+
+def make_pairs(n, seed0, workers):
+    """synth.loop_closure_batch(n, seed0) built by `workers` spawned processes (ranges of pairs, in order).  Called before
+    this process imports torch: the ~32 k scans of the default batch take half a minute on one core."""
+    if workers <= 1 or n < 256:
+        return pairs_chunk((0, n, seed0))
+    import multiprocessing
+    from concurrent.futures import ProcessPoolExecutor
+    edges = np.linspace(0, n, 4 * workers + 1).astype(int)
+    jobs = [(int(lo), int(hi), seed0) for lo, hi in zip(edges[:-1], edges[1:]) if hi > lo]
+    srcs, tgts = [], []
+    with ProcessPoolExecutor(workers, mp_context=multiprocessing.get_context("spawn")) as ex:
+        for s, t in ex.map(pairs_chunk, jobs):
+            srcs += s
+            tgts += t
+    return srcs, tgts
+
+
+def pair_workers():
+    """Processes for make_pairs: this process's CPUs, at most 16, shared by the ranks on this node."""
+    try:
+        cpus = len(os.sched_getaffinity(0))
+    except AttributeError:
+        cpus = os.cpu_count() or 1
+    return max(1, min(cpus, 16) // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1"))))
+
+
+def dump_outputs(d, res, dim=2):
+    """--dump-outputs: the result records of the last timed step (every pair of every rank, in pair order), as a caller
+    of IcpBatch.unpack receives them, one float64 .npy per field (80 B per pair: 16 384 pairs ~1.3 MB).  Beyond
+    DUMP_MAX_PAIRS pairs (64 MB in all) a fixed, seeded sample of the pairs is written, their indices as `pair_index`."""
+    from icpmi.batch import unpack_results
+    arrays = {}
+    if len(res) > DUMP_MAX_PAIRS:
+        keep = np.sort(np.random.default_rng(0).choice(len(res), DUMP_MAX_PAIRS, replace=False))
+        res, arrays["pair_index"] = res[keep], keep
+    R, t, err, info = unpack_results(res, dim)
+    os.makedirs(d, exist_ok=True)
+    arrays.update({"R": R, "t": t, "error": err, "delta": info["delta"], "iterations": info["iters"], "status": info["status"]})
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -240,15 +315,35 @@ def main():
                          "CUs idle at the end of a launch, so throughput grows with the batch")
     ap.add_argument("--pairs-total", type=int, default=0,
                     help="strong scaling as the MAIN line: this many pairs in all, split over the GPUs (BASELINE config 5 "
-                         "uses 512; the default line carries that case as config5_512 / strong_512 anyway)")
-    ap.add_argument("--raycast-scans", type=int, default=200)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-raycast", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the main line (no single-pair, submap, ... legs)")
+                         "uses 512; the --full line carries that case as config5_512 / strong_512 anyway)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the main line (config 5, single pair, submap, ray casting, pose graph, "
+                         "CPU baselines, ...); a plain run times the main line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the result records of the last step (all pairs) as DIR/<name>.npy")
+    ap.add_argument("--raycast-scans", type=int, default=200, help="(--full) scans of the ray-casting legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) without the CPU baselines")
+    ap.add_argument("--no-raycast", action="store_true", help="(--full) without the ray-casting legs")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) only the main line (no single-pair, submap, ... legs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
+
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if world != args.gpus:
+        raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
+    B = args.pairs_per_gpu
+    if args.pairs_total:
+        if args.pairs_total % world:
+            raise SystemExit("--pairs-total must be a multiple of the number of GPUs")
+        B = args.pairs_total // world
+    # the main line's scan pairs, built on the host before torch (and the GPU) is brought up in this process
+    pairs = make_pairs(B, 1000 + 100003 * rank, pair_workers())
 
     import torch
     import torch.distributed as dist
@@ -257,11 +352,6 @@ def main():
     from icpmi.batch import IcpBatch
     from icpmi.dist import gather_results
 
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    if world != args.gpus:
-        raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X; there is no CPU fallback")
     # ICPMI_BENCH_REHEARSE=1: every rank on cuda:0 with gloo (collectives staged through the host) — only to
@@ -281,13 +371,8 @@ def main():
             dist.init_process_group("nccl", device_id=dev)
 
     # ── main line: distinct pairs per rank, inputs resident in HBM before timing ──
-    B = args.pairs_per_gpu
-    if args.pairs_total:
-        if args.pairs_total % world:
-            raise SystemExit("--pairs-total must be a multiple of the number of GPUs")
-        B = args.pairs_total // world
-    mk = lambda b, seed0: Leg(torch, dist, IcpBatch, gather_results, synth, b, rank, world, red_dev, seed0)
-    leg = mk(B, 1000).run(args.steps, args.warmup)
+    mk = lambda b, seed0, pairs=None: Leg(torch, dist, IcpBatch, gather_results, synth, b, rank, world, red_dev, seed0, pairs)
+    leg = mk(B, 1000, pairs).run(args.steps, args.warmup)
     roofline = leg.roofline()
     srcs, tgts = leg.srcs, leg.tgts
 
@@ -298,12 +383,12 @@ def main():
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": {"workload": "config 2 scan pairs (2048-beam room scans, point_to_line ICP, voxel 0.04, "
                                    "normal_k 12, thr 1e-10) batched as in config 5; throughput batch of "
-                                   f"{B} resident pairs per GPU (config 5 itself, 512 pairs: see config5_512 / strong_512 and "
+                                   f"{B} resident pairs per GPU (config 5 itself, 512 pairs: with --full, see config5_512 / strong_512 and "
                                    "config5_run_icp_pair_512)",
                        "candidate_poses": "target pose = source pose + (d cos a, d sin a, yaw): d ~ U(0, 0.6 m), a ~ U(-pi, pi), "
                                           "yaw ~ U(-6, 6 deg) — offsets ICP converges from without pre-alignment "
                                           "(icpmi.synth.loop_closure_batch defaults); SURVEY 8d's 3 m / 20 deg candidates are "
-                                          "the config5_run_icp_pair_512 leg, which pre-aligns as the reference does",
+                                          "the config5_run_icp_pair_512 leg of --full, which pre-aligns as the reference does",
                        "pairs_per_gpu": B, "pairs_total": leg.n_total,
                        "mean_points_after_voxel": [round(float(leg.N.mean()), 1), round(float(leg.M.mean()), 1)],
                        "iterations_per_step": leg.iters_per_step, "parallelism": f"pairs sharded over {world} GPU(s)",
@@ -322,9 +407,12 @@ def main():
                               "status": "multi-rank RCCL path: exercised by gloo world-2 CPU tests and a world-of-one RCCL run on "
                                         "one GPU (tests); no multi-GPU run had been recorded when this bench was written"}
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, leg.last)
+
     # ── BASELINE config 5 as written: 512 candidate pairs in all (one GPU: one batch; N GPUs: 512/N pairs each +
     #    the all_gather) — strong scaling, same K steps, same barriers ──
-    if not args.pairs_total and 512 % world == 0 and not (args.no_extras and world == 1):
+    if args.full and not args.pairs_total and 512 % world == 0 and not (args.no_extras and world == 1):
         c5 = mk(512 // world, 5000).run(args.steps, args.warmup)
         r5 = c5.roofline()
         obj = {"workload": "BASELINE config 5: 512 candidate scan pairs in all, point_to_line ICP as config 2 (ICP only; "
@@ -343,7 +431,7 @@ def main():
         if world > 1:
             line["weak"] = {"pairs_per_gpu": B, "value": line["value"], "ms_per_step": line["ms_per_step"]}
 
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         # single-pair latency (config 2 exactly as the reference calls it, one pair)
         one = IcpBatch([srcs[0], tgts[0]], [0], [1], **ICP_KW)
         lat = timed(torch, one.run)
@@ -359,7 +447,7 @@ def main():
         line["pose_graph"] = bench_pose_graph(torch, not args.no_cpu_baseline)
         if not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(srcs, tgts)
-    if world > 1 and not args.no_raycast:
+    if args.full and world > 1 and not args.no_raycast:
         line["map_replay_sharded"] = bench_replay_sharded(torch, dist, synth, args.raycast_scans, rank, world, dev, red_dev)
     if rehearse:
         line["data"] = "synthetic (REHEARSAL: all ranks share cuda:0 over gloo; not a scaling measurement)"

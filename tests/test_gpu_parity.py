@@ -1677,3 +1677,33 @@ def test_packed_walks_on_exact_ties_and_lattices(uicp, method):
         # a batch of the same pair 80 times: the packed walk is taken when >= 16 lanes of a wave search — they all do here
         R, tt, err, info = batch.icp_batch([s] * 80, [t] * 80, 1e-12, 25, vox, None, None, method, 8)
         assert (info["iters"] == io["iters"]).all() and max(rot_err(R[i], tt[i], Ro, to) for i in range(80)) < FRO_TOL, name
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` (a plain run: the main line only) writes what its timed path computed in the last
+    step: the records of its seeded pairs, equal bit for bit to one IcpBatch run of the same pairs in this process."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    from icpmi import synth
+    from icpmi.batch import IcpBatch
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--pairs-per-gpu", "300", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["config"]["pairs_per_gpu"] == 300
+    assert "config5_512" not in line and "cpu_baseline" not in line                  # the extra legs are --full only
+    srcs, tgts = synth.loop_closure_batch(300, seed0=1000)
+    b = IcpBatch(srcs + tgts, np.arange(300), np.arange(300, 600), **bench.ICP_KW)
+    b.run()
+    R, t, err, info = b.unpack()
+    want = {"R": R, "t": t, "error": err, "delta": info["delta"], "iterations": info["iters"], "status": info["status"]}
+    assert sorted(f for f in os.listdir(out)) == sorted(k + ".npy" for k in want)
+    for k, v in want.items():
+        got = np.load(out / (k + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, np.asarray(v, dtype=np.float64)), k
+    assert float(np.load(out / "iterations.npy").sum()) == line["config"]["iterations_per_step"]

@@ -345,6 +345,62 @@ def test_bench_refuses_stale_pmc_traffic(tmp_path, monkeypatch):
     assert os.path.basename(bench.latest_profile("pmc_traffic.json")).startswith("r")
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs writes the last step's result records field by field as float64 .npy, every pair in pair order;
+    past DUMP_MAX_PAIRS, the same seeded sample of pairs every time, with its indices."""
+    import importlib.util
+    from icpmi import _lib
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.DUMP_MAX_PAIRS * 88 <= 64 * 2**20
+    B = 10
+    res = np.zeros((B, _lib.RES_DOUBLES))
+    res[:, _lib.RES_R:_lib.RES_R + 4] = np.arange(4 * B).reshape(B, 4)
+    res[:, _lib.RES_T:_lib.RES_T + 2] = -np.arange(2 * B).reshape(B, 2)
+    res[:, _lib.RES_ERR], res[:, _lib.RES_DELTA] = np.arange(B) * 1e-3, np.arange(B) * 1e-6
+    res[:, _lib.RES_ITERS], res[:, _lib.RES_STATUS] = np.arange(B) + 1, np.arange(B) % 4 + 1
+    bench.dump_outputs(str(tmp_path / "all"), res)
+    got = {f[:-4]: np.load(tmp_path / "all" / f) for f in os.listdir(tmp_path / "all")}
+    assert sorted(got) == ["R", "delta", "error", "iterations", "status", "t"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["R"], np.arange(4 * B).reshape(B, 2, 2)) and np.array_equal(got["t"][:, 1], -np.arange(1, 2 * B, 2))
+    assert np.array_equal(got["iterations"], np.arange(B) + 1) and np.array_equal(got["error"], np.arange(B) * 1e-3)
+    assert np.array_equal(got["delta"], np.arange(B) * 1e-6) and np.array_equal(got["status"], np.arange(B) % 4 + 1)
+    monkeypatch.setattr(bench, "DUMP_MAX_PAIRS", 4)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), res)
+    idx = np.load(tmp_path / "s1" / "pair_index.npy")
+    assert len(idx) == 4 and np.array_equal(idx, np.load(tmp_path / "s2" / "pair_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "iterations.npy"), idx + 1)
+    assert np.array_equal(np.load(tmp_path / "s1" / "status.npy"), idx % 4 + 1)
+
+
+def test_bench_pairs_equal_synth():
+    """The bench builds its scan pairs in ranges, in spawned processes: the same arrays, bit for bit and in the same
+    order, as icpmi.synth.loop_closure_batch makes in one call (the inputs of the measured path do not change)."""
+    from icpmi import synth
+    import bench
+    for seed0 in (1000, 1000 + 100003):
+        want = synth.loop_closure_batch(40, seed0=seed0)
+        a, b = bench.pairs_chunk((0, 17, seed0)), bench.pairs_chunk((17, 40, seed0))
+        got = (a[0] + b[0], a[1] + b[1])
+        assert all(len(g) == 40 and all(np.array_equal(x, y) and x.dtype == y.dtype for x, y in zip(g, w))
+                   for g, w in zip(got, want))
+    code = ("import sys, numpy as np\n"
+            f"sys.path[:0] = [{REPO!r}, {PKG!r}]\n"
+            "import bench\n"
+            "from icpmi import synth\n"
+            "if __name__ == '__main__':\n"
+            "    got = bench.make_pairs(300, 1000, 3)\n"
+            "    want = synth.loop_closure_batch(300, seed0=1000)\n"
+            "    assert all(len(g) == 300 and all(np.array_equal(x, y) for x, y in zip(g, w)) for g, w in zip(got, want))\n"
+            "    assert 'torch' not in sys.modules\n"
+            "    print('PAIRS_EQUAL')\n")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "PAIRS_EQUAL" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
 def test_arange_rows_is_numpys_arange():
     """icpmi.prealign.arange_rows tabulates np.arange(lo[k], hi[k], step) for every k at once (the fine grids that can
     follow each coarse winner of a rotation search, features.py:227-229): the same numbers and lengths bit for bit."""

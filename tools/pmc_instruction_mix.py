@@ -5,7 +5,7 @@
 
 pass A: SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_BRANCH SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES
 pass B: SQ_THREAD_CYCLES_VALU SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_WAVES
-(each with --kernel-trace only, on `python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline`).
+(each with --kernel-trace only, on `python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline`).
 """
 import csv
 import json
@@ -30,7 +30,7 @@ def main(a_csv, b_csv, keep):
     import os
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import bench
-    out = {"how": "rocprofv3 --kernel-trace --pmc <6 SQ counters> (two passes) -- python3 bench.py --steps 3 --warmup 1 "
+    out = {"how": "rocprofv3 --kernel-trace --pmc <6 SQ counters> (two passes) -- python3 bench.py --full --steps 3 --warmup 1 "
                   "--no-cpu-baseline; values per dispatch, averaged over the dispatches of a kernel at one grid size; "
                   "instruction counters count wave-level instructions.  derived.valu_issue_frac = SQ_ACTIVE_INST_VALU "
                   "(quad-cycles in which a SIMD issued a vector instruction, summed over the chip) x 4 / (1024 SIMDs x "

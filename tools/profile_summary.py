@@ -57,7 +57,7 @@ def pmc(fetch_csv, write_csv):
     except OSError:
         commit = ""
     out = {"how": "rocprofv3 --kernel-trace --pmc FETCH_SIZE (pass 1) / --pmc WRITE_SIZE (pass 2) -- python3 bench.py "
-                  "--steps 5 --warmup 1 --no-cpu-baseline; counters are KiB per dispatch, averaged over the "
+                  "--full --steps 5 --warmup 1 --no-cpu-baseline; counters are KiB per dispatch, averaged over the "
                   "dispatches of a kernel at one grid size; FETCH_SIZE doubled for 16-B-per-lane coalesced reads as "
                   "MI355X_MICROARCH.md (HBM) prescribes; WRITE_SIZE as read",
            "csrc_sha256": bench.csrc_signature(), "summarised_at_commit": commit,
