@@ -123,6 +123,15 @@ class GpuBackend:
         R, t, err, info = prealign.run_icp_pair_batch(source, targets, icp_cfg, feat_cfg)
         return R, t, err, info["iters"]
 
+    @staticmethod
+    def run_icp_pairs_first_accepted(source, targets, feat_cfg, icp_cfg, error_accept):
+        """The same, stopping after the first candidate in order whose error is below error_accept (slam.py:582-597: the
+        later ones are never computed) -> (R, t, err, iterations, first accepted index or -1).  Candidates after it may
+        come back unfinished (status 5); every one up to it is the full run's."""
+        R, t, err, info = prealign.run_icp_pair_batch(source, targets, icp_cfg, feat_cfg, error_accept=error_accept,
+                                                      stop_after_first_accepted=True)
+        return R, t, err, info["iters"], info["first_accepted"]
+
 
 def run(n_scans=60, log_path=None, verbose=True, imu_path=None, loop=False, use_submap=True, lc_error_threshold=0.05,
         backend=None, max_candidates=5):
@@ -198,10 +207,15 @@ def run(n_scans=60, log_path=None, verbose=True, imu_path=None, loop=False, use_
         if i >= 30 and i % 10 == 0:
             cands = [k for k, (_, pk) in enumerate(history[:-20]) if np.linalg.norm(pk[:2, 2] - pose[:2, 2]) < 3.0][:max_candidates]
             if cands:
-                R, t, err, its = be.run_icp_pairs(cur, [history[k][0] for k in cands],
-                                                  dict(rotation_voxel_size=0.15, angle_step_coarse=1.5, angle_step_fine=0.1), icp_kw)
-                ok = np.flatnonzero(np.asarray(err) < lc_error_threshold)
-                first = int(ok[0]) if len(ok) else -1
+                feat_kw = dict(rotation_voxel_size=0.15, angle_step_coarse=1.5, angle_step_fine=0.1)
+                if hasattr(be, "run_icp_pairs_first_accepted"):      # the candidates after the accepted one may stop early
+                    R, t, err, its, first = be.run_icp_pairs_first_accepted(cur, [history[k][0] for k in cands], feat_kw,
+                                                                            icp_kw, lc_error_threshold)
+                else:
+                    R, t, err, its = be.run_icp_pairs(cur, [history[k][0] for k in cands], feat_kw, icp_kw)
+                    ok = np.flatnonzero(np.asarray(err) < lc_error_threshold)
+                    first = int(ok[0]) if len(ok) else -1
+                # (argmin below only when nothing is accepted: then nothing was skipped either)
                 shown = first if first >= 0 else int(np.argmin(err))
                 closures.append((i, cands[shown], float(err[shown]), int(its[shown])))
                 if first >= 0:                                               # slam.py:582-620

@@ -52,6 +52,7 @@ extern "C" {
 #define ICPMI_ST_MAXITER 2        /* icp.py:222-223                               */
 #define ICPMI_ST_FEW_INLIERS 3    /* icp.py:186-187 `break`                       */
 #define ICPMI_ST_EMPTY 4          /* a cloud of the pair is empty after filtering */
+#define ICPMI_ST_SKIPPED 5        /* icpmi_icp_batch_gated: a candidate after the first accepted one was left unfinished */
 
 /* One ICP result = 16 float64: R row-major in [0, dim*dim), t in [9, 9+dim),
  * then error, last |prev_error - error|, iterations executed, status.
@@ -176,6 +177,28 @@ int icpmi_icp_batch(const double* pts, const int32_t* off_dev, const int32_t* cn
                     int32_t n_pairs, int32_t max_src_n, int32_t max_tgt_n, int32_t total_rows,
                     const icpmi_icp_params* params_host, const double* init, double* results,
                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* The loop-closure gate of slam.py:582-597: the candidates are tried in order and the first whose error is below
+ * the gate is taken (`break  # one closure per scan is enough`), so the ones after it are never computed.  Same call
+ * as icpmi_icp_batch (same results), plus: pair b is candidate index_base + b * index_stride (index_base >= 0,
+ * index_stride >= 1: a rank of a sharded run passes its rank and the world size); it is ELIGIBLE when
+ * search_records == NULL or slot 11 of its rotation-search record (stride 16, icpmi_rotation_search_batch) is below 2
+ * (ok, or too few points: the ICP starts from the identity as the reference's does; 2 = capacity: the caller redoes
+ * the candidate, 3 = no fine grid), and ACCEPTED when it is eligible, not skipped and its error is < error_accept
+ * (NaN: never).  A candidate whose index is above that of an accepted one may stop early with status
+ * ICPMI_ST_SKIPPED: its record then holds the totals of the steps it applied, `iterations` is their count, and
+ * error / delta are those of the last step whose error was taken (the step before, for a candidate stopped between
+ * the launches of a two-stage run).  Every other record — every candidate up to the first accepted one included —
+ * is bit for bit the record icpmi_icp_batch writes; skipping is allowed, never required (the exhaustive kernel
+ * never skips).  first_accepted_dev (device, one int32): on completion the lowest accepted candidate index, -1 when
+ * none; it also serves as the gate word during the call.  error_accept <= 0 accepts nothing and skips nothing. */
+int icpmi_icp_batch_gated(const double* pts, const int32_t* off_dev, const int32_t* cnt_dev,
+                          const double* normals, const void* prepared,
+                          const int32_t* pair_src, const int32_t* pair_tgt,
+                          int32_t n_pairs, int32_t max_src_n, int32_t max_tgt_n, int32_t total_rows,
+                          const icpmi_icp_params* params_host, const double* init, double* results,
+                          void* workspace, size_t workspace_bytes, double error_accept, const double* search_records,
+                          int32_t index_base, int32_t index_stride, int32_t* first_accepted_dev, void* stream);
 
 /* ---- prepared targets: axis choice + sort (+ normals) for the sweep search ----
  * For every selected cloud (<= 4096 rows): pick the projection axis (x, y, x+y

@@ -37,6 +37,20 @@ struct SideLock {
     SideLock& operator=(const SideLock&) = delete;
 };
 
+// Gate of icpmi_icp_batch_gated (icp.hip): pair b has the gate index base + b * stride; a pair whose index is above the
+// value of *hint it reads may stop (ICPMI_ST_SKIPPED); a finished, eligible pair with err < accept lowers *hint to its
+// index.  Eligible: search == nullptr, or slot 11 of its rotation-search record (stride 16) below 2 (ok, or too few
+// points: the ICP then starts from the identity, as the reference's does).
+struct IcpGate {
+    int32_t* hint;
+    const double* search;
+    double accept;
+    int base, stride;
+};
+__device__ __forceinline__ bool gate_eligible(const double* search, int b) {
+    return !search || search[(size_t)b * 16 + 11] < 2.0;
+}
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (ICPMI_WAVE - 1); }
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
 

@@ -314,8 +314,37 @@ extern "C" size_t icpmi_icp_workspace_bytes(int32_t n_pairs, int32_t max_src_n, 
 namespace icpmi {
 int launch_icp2(const double* pts, const int32_t* off, const int32_t* cnt, const int32_t* ps, const int32_t* pt,
                 int n_pairs, int max_src_n, int max_tgt_n, int total_rows, const icpmi_icp_params* p, const double* init,
-                double* results, const void* prepared, void* workspace, size_t workspace_bytes, hipStream_t st);   // icp2.hip
+                double* results, const void* prepared, void* workspace, size_t workspace_bytes, const IcpGate* gate,
+                hipStream_t st);   // icp2.hip
+
+// The answer of icpmi_icp_batch_gated, from the records alone (not from the gate word the kernels lowered): the lowest
+// candidate index that is eligible, not skipped and below the gate, -1 when none.  Right whatever kernel ran a pair —
+// the exhaustive one here never skips — and whether or not a pair saw the gate in time.
+constexpr int FA_THREADS = 256;
+__global__ __launch_bounds__(FA_THREADS) void icp_first_accepted_kernel(const double* results, int n_pairs, IcpGate g,
+                                                                        int32_t* out) {
+    __shared__ int best;
+    if (threadIdx.x == 0) best = 0x7fffffff;
+    __syncthreads();
+    int m = 0x7fffffff;
+    for (int b = threadIdx.x; b < n_pairs; b += FA_THREADS) {           // the lowest b of each thread is its first hit
+        const double* r = results + (size_t)b * ICPMI_RES_DOUBLES;
+        if (r[ICPMI_RES_STATUS] != (double)ICPMI_ST_SKIPPED && r[ICPMI_RES_ERR] < g.accept && gate_eligible(g.search, b)) {
+            m = g.base + b * g.stride;
+            break;
+        }
+    }
+    atomicMin(&best, m);
+    __syncthreads();
+    if (threadIdx.x == 0) *out = best == 0x7fffffff ? -1 : best;
 }
+
+static int icp_batch(const double* pts, const int32_t* off_dev, const int32_t* cnt_dev, const double* normals,
+                     const void* prepared, const int32_t* pair_src, const int32_t* pair_tgt, int32_t n_pairs,
+                     int32_t max_src_n, int32_t max_tgt_n, int32_t total_rows, const icpmi_icp_params* p,
+                     const double* init, double* results, void* workspace, size_t workspace_bytes, const IcpGate* gate,
+                     hipStream_t st);
+}  // namespace icpmi
 
 extern "C" int icpmi_icp_batch(const double* pts, const int32_t* off_dev, const int32_t* cnt_dev,
                                const double* normals, const void* prepared,
@@ -323,17 +352,49 @@ extern "C" int icpmi_icp_batch(const double* pts, const int32_t* off_dev, const 
                                int32_t n_pairs, int32_t max_src_n, int32_t max_tgt_n, int32_t total_rows,
                                const icpmi_icp_params* p, const double* init, double* results,
                                void* workspace, size_t workspace_bytes, void* stream) {
+    return icpmi::icp_batch(pts, off_dev, cnt_dev, normals, prepared, pair_src, pair_tgt, n_pairs, max_src_n, max_tgt_n,
+                            total_rows, p, init, results, workspace, workspace_bytes, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int icpmi_icp_batch_gated(const double* pts, const int32_t* off_dev, const int32_t* cnt_dev,
+                                     const double* normals, const void* prepared,
+                                     const int32_t* pair_src, const int32_t* pair_tgt,
+                                     int32_t n_pairs, int32_t max_src_n, int32_t max_tgt_n, int32_t total_rows,
+                                     const icpmi_icp_params* p, const double* init, double* results,
+                                     void* workspace, size_t workspace_bytes, double error_accept,
+                                     const double* search_records, int32_t index_base, int32_t index_stride,
+                                     int32_t* first_accepted_dev, void* stream) {
     using namespace icpmi;
+    if (!first_accepted_dev || index_base < 0 || index_stride < 1) return ICPMI_ERR_ARG;
+    if (n_pairs > 0 && (int64_t)index_base + (int64_t)(n_pairs - 1) * index_stride >= 0x7fffffff) return ICPMI_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    // the gate word starts above every index; only a finished, accepted candidate lowers it (icp2.hip)
+    if (hipMemsetD32Async((hipDeviceptr_t)first_accepted_dev, 0x7fffffff, 1, st) != hipSuccess) return ICPMI_ERR_HIP;
+    const IcpGate g{first_accepted_dev, search_records, error_accept, index_base, index_stride};
+    const int rc = icp_batch(pts, off_dev, cnt_dev, normals, prepared, pair_src, pair_tgt, n_pairs, max_src_n, max_tgt_n,
+                             total_rows, p, init, results, workspace, workspace_bytes, &g, st);
+    if (rc != ICPMI_OK) return rc;
+    icp_first_accepted_kernel<<<1, FA_THREADS, 0, st>>>(results, n_pairs, g, first_accepted_dev);
+    ICPMI_LAUNCH_CHECK();
+    return ICPMI_OK;
+}
+
+namespace icpmi {
+static int icp_batch(const double* pts, const int32_t* off_dev, const int32_t* cnt_dev, const double* normals,
+                     const void* prepared, const int32_t* pair_src, const int32_t* pair_tgt, int32_t n_pairs,
+                     int32_t max_src_n, int32_t max_tgt_n, int32_t total_rows, const icpmi_icp_params* p,
+                     const double* init, double* results, void* workspace, size_t workspace_bytes, const IcpGate* gate,
+                     hipStream_t st) {
     if (!pts || !off_dev || !pair_src || !pair_tgt || !p || !results) return ICPMI_ERR_ARG;
     if (n_pairs < 0 || max_src_n < 0 || max_tgt_n < 0 || (p->dim != 2 && p->dim != 3)) return ICPMI_ERR_ARG;
     if (p->method != ICPMI_POINT_TO_POINT && p->method != ICPMI_POINT_TO_LINE) return ICPMI_ERR_ARG;
     if (p->has_init && !init) return ICPMI_ERR_ARG;
     if (n_pairs == 0) return ICPMI_OK;
-    hipStream_t st = (hipStream_t)stream;
     // fast path: prepared (axis-sorted) targets, everything on chip
     if (prepared && p->dim == 2 && max_src_n <= 4096)
         return launch_icp2(pts, off_dev, cnt_dev, pair_src, pair_tgt, n_pairs, max_src_n, max_tgt_n, total_rows, p, init,
-                           results, prepared, workspace, workspace_bytes, st);
+                           results, prepared, workspace, workspace_bytes, gate, st);
+    // (the exhaustive kernel ignores the gate: every candidate runs to its end, which the gate allows)
     if (p->method == ICPMI_POINT_TO_LINE && p->dim == 2 && !normals) return ICPMI_ERR_ARG;
     if (!workspace || workspace_bytes < icpmi_icp_workspace_bytes(n_pairs, max_src_n, p->dim)) return ICPMI_ERR_WORKSPACE;
     const size_t rows = (size_t)n_pairs * (size_t)max_src_n;
@@ -351,3 +412,4 @@ extern "C" int icpmi_icp_batch(const double* pts, const int32_t* off_dev, const 
     ICPMI_LAUNCH_CHECK();
     return ICPMI_OK;
 }
+}  // namespace icpmi

@@ -82,6 +82,10 @@ struct Icp2Args {
     int32_t* far_list;        // nullptr: never
     int32_t* far_count;
     double far_d2;            // +inf: never
+    // Stop after the first accepted candidate (icpmi_icp_batch_gated; gate.hint == nullptr: ungated).  The lead lane
+    // reads the hint at the top of an iteration and the lead wave tests it where it decides CTRL_STOP; parked pairs test
+    // it once before they stage anything; a pair's final record lowers it (common.hpp, IcpGate).
+    IcpGate gate;
 };
 constexpr int ICP2_FAR_THREADS = 1024, ICP2_FAR_SMAX = 2, ICP2_FAR_POINTS = 2048;   // the continuation's shape: most source rows, target points
 constexpr int ICP2_ST_PARKED = 100;     // internal status between the two stages
@@ -214,6 +218,15 @@ __device__ __forceinline__ int finish_step(double* ctrl, int it, double err_sum,
     return stop ? FIN_STOP : (far ? FIN_FAR : FIN_GO);
 }
 
+// The gate (Icp2Args::gate), where the lead wave decides CTRL_STOP: a pair that goes on although a candidate before it
+// has been accepted stops as SKIPPED instead — its record then holds the totals of the `it` iterations whose error
+// finish_step has just taken.  gate_seen: what lane 0 loaded at the top of the iteration.
+__device__ __forceinline__ int gate_stop(double* ctrl, const int32_t* hint, int gate_seen, int gate_index, bool writer, int fin) {
+    if (fin == FIN_STOP || !hint || __builtin_amdgcn_readfirstlane(gate_seen) >= gate_index) return fin;
+    if (writer) ctrl[CTRL_STATUS] = (double)ICPMI_ST_SKIPPED;
+    return FIN_STOP;
+}
+
 // R_total = R R_total, t_total = t_total R^T + t: icp.py:210-211
 __device__ __forceinline__ void accumulate_step(double* ctrl, const double (&r)[4], const double (&t)[2]) {
     const double rt0 = ctrl[CTRL_RT], rt1 = ctrl[CTRL_RT + 1], rt2 = ctrl[CTRL_RT + 2], rt3 = ctrl[CTRL_RT + 3];
@@ -252,6 +265,21 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
     if (a.skip_over ? (N > THREADS * ICP2_SMAX || (TGT_LDS && M > a.lds_points)) : (a.n_lo >= 0 && N <= a.n_lo && M <= a.m_lo)) {
         if (a.skip_over && a.wide_list && threadIdx.x == 0) a.wide_list[atomicAdd(a.wide_count, 1)] = b;
         return;
+    }
+    const int gate_index = a.gate.base + b * a.gate.stride;
+    if (RESUME && a.gate.hint) {
+        // a parked pair tests the gate once, before it stages anything: skipped, its record keeps the totals the first
+        // stage left there (one step more than the iterations whose error it holds)
+        __shared__ int gate_skip;
+        if (tid == 0) {
+            gate_skip = __hip_atomic_load(a.gate.hint, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < gate_index;
+            if (gate_skip) {
+                res[ICPMI_RES_ITERS] += 1.0;
+                res[ICPMI_RES_STATUS] = (double)ICPMI_ST_SKIPPED;
+            }
+        }
+        __syncthreads();
+        if (gate_skip) return;
     }
 
     // two instantiations, each sees ONE address space behind these pointers
@@ -409,6 +437,10 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
         const int it_end = RESUME ? a.max_iterations : min(a.max_iterations, a.it_limit);
         for (int it = RESUME ? a.it_begin : 0; it < it_end; ++it) {
             DIAG_T(c0);
+            // the gate, loaded by one lane now and tested after the search (gate_stop): a cross-XCD load is a large part
+            // of a tail iteration; agent scope, so that no stale copy in this CU's L1 hides a lower value
+            int gate_seen = 0x7fffffff;
+            if (a.gate.hint && tid == 0) gate_seen = __hip_atomic_load(a.gate.hint, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             // ── correspondences: exact sweep search in LDS, icp.py:179 ───────
             // A row whose net displacement since its last search is inside its budget keeps one of its two
             // candidates (two distances); the others search.
@@ -601,7 +633,8 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
                 DIAG_SET(c2);
                 if (lead) {
                     combine_totals<11>(redA, NWAVES, acc);
-                    const int fin = finish_step(ctrl, it, acc[10], acc[9], N, has_corr, need, a.error_threshold, tid == 0, far_err);
+                    const int fin = gate_stop(ctrl, a.gate.hint, gate_seen, gate_index, tid == 0,
+                                              finish_step(ctrl, it, acc[10], acc[9], N, has_corr, need, a.error_threshold, tid == 0, far_err));
                     const bool stop = fin == FIN_STOP;
                     if (!stop) {
                         double A[3][3] = {{acc[0], acc[1], acc[2]}, {acc[1], acc[3], acc[4]}, {acc[2], acc[4], acc[5]}};
@@ -648,7 +681,8 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
                 DIAG_SET(c2);
                 if (lead) {
                     combine_totals<6>(redA, NWAVES, m);
-                    const int fin = finish_step(ctrl, it, m[5], m[4], N, has_corr, need, a.error_threshold, tid == 0, far_err);
+                    const int fin = gate_stop(ctrl, a.gate.hint, gate_seen, gate_index, tid == 0,
+                                              finish_step(ctrl, it, m[5], m[4], N, has_corr, need, a.error_threshold, tid == 0, far_err));
                     if (tid == 0) {
                         ctrl[CTRL_STOP] = (double)fin;
                         ctrl[CTRL_MP] = m[0] / m[4]; ctrl[CTRL_MP + 1] = m[1] / m[4];
@@ -756,6 +790,12 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
         res[ICPMI_RES_DELTA] = ctrl[CTRL_DELTA];
         res[ICPMI_RES_ITERS] = ctrl[CTRL_ITERS];
         res[ICPMI_RES_STATUS] = ctrl[CTRL_STATUS];
+        if (a.gate.hint) {                                  // a finished, eligible, accepted pair lowers the gate (NaN: never)
+            const double st = ctrl[CTRL_STATUS];
+            if (st != (double)ICP2_ST_PARKED && st != (double)ICPMI_ST_SKIPPED && ctrl[CTRL_ERR] < a.gate.accept &&
+                gate_eligible(a.gate.search, b))
+                atomicMin(a.gate.hint, gate_index);
+        }
     }
 }
 
@@ -807,8 +847,10 @@ __global__ __launch_bounds__(ICP2_FAR_THREADS, 4) void icp2_far_kernel(Icp2Args 
 // host side: called by icpmi_icp_batch (icp.hip) when a prepared buffer is given and everything fits
 int launch_icp2(const double* pts, const int32_t* off, const int32_t* cnt, const int32_t* ps, const int32_t* pt,
                 int n_pairs, int max_src_n, int max_tgt_n, int total_rows, const icpmi_icp_params* p, const double* init,
-                double* results, const void* prepared, void* workspace, size_t workspace_bytes, hipStream_t st) {
+                double* results, const void* prepared, void* workspace, size_t workspace_bytes, const IcpGate* gate,
+                hipStream_t st) {
     Icp2Args a;
+    a.gate = gate ? *gate : IcpGate{nullptr, nullptr, 0.0, 0, 1};
     a.it_begin = 0; a.it_limit = 0x7fffffff; a.resume = 0;
     a.st_xy = nullptr; a.st_pos = nullptr; a.list = nullptr; a.list_count = nullptr; a.st_stride = 0;
     a.wide_list = nullptr; a.wide_count = nullptr;

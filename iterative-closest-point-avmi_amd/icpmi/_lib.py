@@ -12,7 +12,7 @@ CSRC = os.path.join(_PKG, "csrc")
 LIB_PATH = os.path.join(_PKG, "lib", "libicpmi.so")
 
 OK = 0
-ST_CONVERGED, ST_MAXITER, ST_FEW_INLIERS, ST_EMPTY = 1, 2, 3, 4
+ST_CONVERGED, ST_MAXITER, ST_FEW_INLIERS, ST_EMPTY, ST_SKIPPED = 1, 2, 3, 4, 5
 RES_DOUBLES, RES_R, RES_T, RES_ERR, RES_DELTA, RES_ITERS, RES_STATUS = 16, 0, 9, 12, 13, 14, 15
 POINT_TO_POINT, POINT_TO_LINE = 0, 1
 
@@ -57,6 +57,9 @@ _SIGS = {
     "icpmi_icp_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "icpmi_icp_batch": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 4 + [C.POINTER(IcpParams), C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "icpmi_icp_batch_gated": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 4 + [C.POINTER(IcpParams), C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p, C.c_int32,
+                                        C.c_int32, C.c_void_p, C.c_void_p]),
     "icpmi_prepared_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "icpmi_prepare_targets": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p, C.c_size_t,
                                         C.c_void_p]),

@@ -261,6 +261,22 @@ class IcpBatch:
             self.icp_ws = torch.empty(L.icpmi_icp_workspace_bytes(self.B, self.max_src_n, self.dim),
                                       dtype=torch.uint8, device=dev)
         self.results = torch.zeros((max(self.B, 1), _lib.RES_DOUBLES), dtype=torch.float64, device=dev)
+        self.gate = None
+        self.first_accepted_dev = None
+
+    def set_gate(self, error_accept, search_records=None, index_base=0, index_stride=1):
+        """Stop after the first accepted pair (slam.py:582-597; include/icpmi.h, icpmi_icp_batch_gated): from now on
+        ``run()`` lets pairs after the first one with err < error_accept (and, with ``search_records``, a rotation-search
+        status below 2) stop early with status ST_SKIPPED, and leaves that pair's index in ``first_accepted_dev``
+        (device int32, -1: none).  Every record up to it equals the ungated run's bit for bit.  None: ungated again."""
+        if error_accept is None:
+            self.gate = None
+            return
+        if index_base < 0 or index_stride < 1:
+            raise ValueError("index_base must be >= 0 and index_stride >= 1")
+        self.gate = (float(error_accept), search_records, int(index_base), int(index_stride))
+        if self.first_accepted_dev is None:
+            self.first_accepted_dev = torch.full((1,), -1, dtype=torch.int32, device=self.results.device)
 
     def run(self, events=None):
         """Enqueue voxel filter -> normals -> fused ICP on the current stream; returns the device result tensor.
@@ -286,11 +302,16 @@ class IcpBatch:
                                            self.nrm_ws.numel(), st), "estimate_normals_2d")
         if events is not None:
             events[0].record()
-        check(L.icpmi_icp_batch(_ptr(self.vox.pts), _ptr(self.vox.off), _ptr(self.vox.cnt), _ptr(self.normals),
-                                _ptr(self.prepared), _ptr(self.pair_src), _ptr(self.pair_tgt), self.B,
-                                self.max_src_n, self.max_tgt_n, self.raw.total_rows,
-                                C.byref(self.params), _ptr(self.init), _ptr(self.results), _ptr(self.icp_ws),
-                                self.icp_ws.numel() if self.icp_ws is not None else 0, st), "ICP")
+        args = (_ptr(self.vox.pts), _ptr(self.vox.off), _ptr(self.vox.cnt), _ptr(self.normals), _ptr(self.prepared),
+                _ptr(self.pair_src), _ptr(self.pair_tgt), self.B, self.max_src_n, self.max_tgt_n, self.raw.total_rows,
+                C.byref(self.params), _ptr(self.init), _ptr(self.results), _ptr(self.icp_ws),
+                self.icp_ws.numel() if self.icp_ws is not None else 0)
+        if self.gate is None:
+            check(L.icpmi_icp_batch(*args, st), "ICP")
+        else:
+            accept, search, base, stride = self.gate
+            check(L.icpmi_icp_batch_gated(*args, accept, _ptr(search), base, stride, _ptr(self.first_accepted_dev), st),
+                  "ICP (gated)")
         if events is not None:
             events[1].record()
         return self.results

@@ -67,6 +67,17 @@ def first_accepted(results, error_accept):
     return int(ok[0]) if len(ok) else -1
 
 
+def first_accepted_gated(results, error_accept, search_status_slot=None):
+    """first_accepted on the records of a gated run (icpmi_icp_batch_gated): a skipped candidate (status 5) holds the
+    error of an unfinished ICP and never counts, nor does one whose rotation search fell outside the on-chip capacity
+    (``search_status_slot``: the slot that carries that status, 2) before its owner redid it."""
+    ok = (results[:, _lib.RES_ERR] < error_accept) & (results[:, _lib.RES_STATUS] != float(_lib.ST_SKIPPED))
+    if search_status_slot is not None:
+        ok &= results[:, search_status_slot] < 2.0
+    idx = torch.nonzero(ok)
+    return int(idx[0]) if len(idx) else -1
+
+
 def icp_batch_sharded(sources, targets, error_threshold, max_iterations, voxel_size, R_init=None, t_init=None,
                       method="point_to_point", normal_k=10, max_corr_dist=None, group=None, solver=None):
     """Register sources[i] onto targets[i] across all ranks of the process group.
@@ -113,12 +124,24 @@ class RunIcpPairSharded:
     whose error is below the gate.  The candidates stay resident: ``run()`` may be repeated.
 
     ``solver(source, target_list) -> [k, RES_DOUBLES] tensor`` replaces the local GPU batch (the CPU tests inject the
-    oracle there).  Slot 8 of a gathered record (unused by 2-D results) carries the status of the pair's rotation search, so
+    oracle there); with ``stop_after_first_accepted`` it is called as ``solver(source, target_list, gate)``, gate =
+    dict(error_accept, index_base, index_stride).
+
+    ``stop_after_first_accepted`` (needs ``error_accept``): every rank gates its own candidates (icpmi_icp_batch_gated
+    with index_base = rank, index_stride = world, so the gate speaks in global candidate numbers) and the ones after the
+    first it accepts may stop early, status 5.  No rank skips a candidate below its own first accepted one, so the first
+    gathered candidate that is accepted and not skipped is the one the ungated run would find, and every record up to it
+    is the ungated run's bit for bit.  Slot 8 of a gathered record (unused by 2-D results) carries the status of the pair's rotation search, so
     that every rank knows which candidates fell outside the on-chip search's capacity: their owners redo them through the
     single-pair entries (same numbers) and the records are gathered once more — all ranks take part, none has to be told."""
     SEARCH_STATUS = 8
 
-    def __init__(self, source, targets, icp_cfg=None, feat_cfg=None, group=None, max_rows_hint=0, solver=None):
+    def __init__(self, source, targets, icp_cfg=None, feat_cfg=None, group=None, max_rows_hint=0, solver=None,
+                 stop_after_first_accepted=False, error_accept=None):
+        if stop_after_first_accepted and error_accept is None:
+            raise ValueError("stop_after_first_accepted needs a gate: error_accept")
+        self.stop = bool(stop_after_first_accepted)
+        self.error_accept = None if error_accept is None else float(error_accept)
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -139,11 +162,16 @@ class RunIcpPairSharded:
                                          voxel_size=c.get("voxel_size", 0.06), method=c.get("method", "point_to_line"),
                                          normal_k=c.get("normal_k", 10), rotation_voxel_size=f.get("rotation_voxel_size", 0.3),
                                          angle_step_coarse=f.get("angle_step_coarse", 2.0), angle_step_fine=f.get("angle_step_fine", 0.2),
-                                         max_rows_hint=max_rows_hint)
+                                         max_rows_hint=max_rows_hint, stop_after_first_accepted=self.stop,
+                                         error_accept=self.error_accept if self.stop else None,
+                                         index_base=self.rank, index_stride=self.world)
 
     def _local(self, events=None):
         k = len(self.mine)
         if self.solver is not None:
+            if self.stop:
+                return self.solver(self.source, self.targets,
+                                   dict(error_accept=self.error_accept, index_base=self.rank, index_stride=self.world))
             return self.solver(self.source, self.targets)
         if k == 0:
             return torch.zeros((0, _lib.RES_DOUBLES), dtype=torch.float64, device=torch.device("cuda", torch.cuda.current_device()))
@@ -179,9 +207,17 @@ class RunIcpPairSharded:
         host[:, self.SEARCH_STATUS] = 0.0
         return unpack_results(host, 2)
 
-    def first_accepted(self, error_accept):
-        """slam.py:582-597 on the gathered records: index of the first candidate with error < error_accept, or -1."""
-        return first_accepted(self.gathered, error_accept)
+    def first_accepted(self, error_accept=None):
+        """slam.py:582-597 on the gathered records: index of the first candidate with error < error_accept, or -1.  A gated
+        run answers for its own gate (error_accept may be left out); candidates outside the on-chip search's capacity are
+        redone first (``results()``: every rank takes part, all of them see the same gathered records)."""
+        if not self.stop:
+            return first_accepted(self.gathered, error_accept)
+        if error_accept is not None and float(error_accept) != self.error_accept:
+            raise ValueError("a gated run answers for its own gate only")
+        if self.solver is None and bool((self.gathered[:, self.SEARCH_STATUS] == 2.0).any()):
+            self.results()
+        return first_accepted_gated(self.gathered, self.error_accept, self.SEARCH_STATUS)
 
 
 def _pack_results(R, t, err, info):
@@ -196,15 +232,21 @@ def _pack_results(R, t, err, info):
     return res
 
 
-def run_icp_pair_batch_sharded(source, targets, icp_cfg=None, feat_cfg=None, error_accept=None, group=None, solver=None):
+def run_icp_pair_batch_sharded(source, targets, icp_cfg=None, feat_cfg=None, error_accept=None, group=None, solver=None,
+                               stop_after_first_accepted=False):
     """``_run_icp_pair(source, targets[i], icp_cfg, feat_cfg, "rotation_search")`` for every candidate i (slam.py:575-579),
     the candidates sharded over the ranks of the process group -> (R [n,2,2], t [n,2], err [n], info) on every rank, with
     ``info["first_accepted"]`` = the candidate slam.py:582-597 would accept (first with err < error_accept; -1: none) when
-    a gate is given.  Same configuration keys and defaults as the reference."""
-    job = RunIcpPairSharded(source, targets, icp_cfg, feat_cfg, group=group, solver=solver)
+    a gate is given.  Same configuration keys and defaults as the reference.  ``stop_after_first_accepted`` (needs
+    ``error_accept``) lets the candidates after the accepted one stop early (RunIcpPairSharded; their status is 5)."""
+    job = RunIcpPairSharded(source, targets, icp_cfg, feat_cfg, group=group, solver=solver,
+                            stop_after_first_accepted=stop_after_first_accepted,
+                            error_accept=error_accept if stop_after_first_accepted else None)
     job.run()
     R, t, err, info = job.results()
-    if error_accept is not None:
+    if stop_after_first_accepted:
+        info["first_accepted"] = job.first_accepted()
+    elif error_accept is not None:
         ok = np.flatnonzero(err < error_accept)
         info["first_accepted"] = int(ok[0]) if len(ok) else -1
     return R, t, err, info

@@ -188,11 +188,21 @@ def _pair_lists(sources, targets):
 class RunIcpPairBatch:
     """``_run_icp_pair`` (slam.py:53-98, alignment_method "rotation_search") for a batch of pairs resident in HBM:
     ``run()`` = rotation search of every pair, then ICP of every pair from its own R_init / t_init — one stream, no host
-    round trip; returns the (B, 16) ICP result tensor (icpmi.batch.unpack_results)."""
+    round trip; returns the (B, 16) ICP result tensor (icpmi.batch.unpack_results).
+
+    The pairs are loop-closure candidates in the caller's order.  ``error_accept``: the gate of slam.py:582-597 (the first
+    candidate with err < error_accept is taken); ``unpack()`` then reports it as ``info["first_accepted"]``.  With
+    ``stop_after_first_accepted`` the candidates after it may stop early, as the reference never computes them
+    (icpmi_icp_batch_gated): their status is ST_SKIPPED (5); every candidate up to the accepted one is the full run's
+    bit for bit.  ``index_base`` / ``index_stride``: the candidate number of pair b is index_base + b * index_stride
+    (a rank of a sharded run, icpmi.dist)."""
 
     def __init__(self, clouds, pair_src, pair_tgt, error_threshold=1e-7, max_iterations=100, voxel_size=0.06,
                  method="point_to_line", normal_k=10, rotation_voxel_size=0.3, angle_step_coarse=2.0, angle_step_fine=0.2,
-                 max_corr_dist=None, max_rows_hint=0):
+                 max_corr_dist=None, max_rows_hint=0, stop_after_first_accepted=False, error_accept=None,
+                 index_base=0, index_stride=1):
+        if stop_after_first_accepted and error_accept is None:
+            raise ValueError("stop_after_first_accepted needs a gate: error_accept")
         raw = clouds if isinstance(clouds, CloudSet) else CloudSet.from_numpy(clouds)
         B = len(pair_src)
         self.icp = IcpBatch(raw, pair_src, pair_tgt, error_threshold, max_iterations, voxel_size,
@@ -200,6 +210,14 @@ class RunIcpPairBatch:
         self.search = RotationSearchBatch(raw, pair_src, pair_tgt, rotation_voxel_size, angle_step_coarse, angle_step_fine,
                                           init=self.icp.init, max_rows_hint=max_rows_hint)
         self.B = B
+        self.error_accept = None if error_accept is None else float(error_accept)
+        self.stop = bool(stop_after_first_accepted)
+        self.index_base, self.index_stride = int(index_base), int(index_stride)
+        if self.stop:
+            self.icp.set_gate(self.error_accept, self.search.records, self.index_base, self.index_stride)
+        # a pair can fall outside the on-chip search (status 2) only with a capacity hint, a raw cloud above the search's
+        # 2 048 rows or more angles than it tabulates (csrc/rotsearch.hip): only then may first_accepted() need the host
+        self.capacity_possible = self.search.too_many_angles or max_rows_hint > 0 or raw.max_n > 2048
 
     def run(self, events=None):
         if self.search.too_many_angles:
@@ -207,45 +225,91 @@ class RunIcpPairBatch:
             # single-pair entry, as pairs beyond the capacity hint are — same numbers
             self.search.records.zero_()
             self.search.records[:, 11] = ST_CAPACITY
+            if self.stop:
+                self.icp.first_accepted_dev.fill_(-1)  # no candidate ran on the device: unpack() redoes them in order
             if events is not None:
                 events[0].record(); events[1].record()
             return self.icp.results
         self.search.run()
         return self.icp.run(events=events)
 
+    def first_accepted(self):
+        """Index (in candidate numbers) of the candidate slam.py:582-597 accepts after the last gated ``run()``, -1 when
+        none: a 4-byte read of the device's answer — unless a candidate fell outside the on-chip search (status 2), which
+        only ``unpack()`` can settle (it redoes such candidates on the host)."""
+        if not self.stop:
+            raise ValueError("first_accepted() needs stop_after_first_accepted=True")
+        first = int(self.icp.first_accepted_dev.item())
+        if self.capacity_possible:
+            st = self.search.records[:self.B, 11]
+            lim = self.B if first < 0 else (first - self.index_base) // self.index_stride
+            if bool((st[:lim] == ST_CAPACITY).any()) or bool((st == ST_NO_FINE).any()):
+                return self.unpack()[3]["first_accepted"]
+        return first
+
+    def _redo(self, i, R0, t0, clouds):
+        """The ICP of pair i through the single-pair entry, from the single-pair search's start -> its 16-double record."""
+        from .batch import icp_pair
+        p = self.icp.params
+        Ri, ti, ei, info = icp_pair(clouds[self.icp.pair_src_host[i]], clouds[self.icp.pair_tgt_host[i]],
+                                    p.error_threshold, p.max_iterations, self.icp.voxel_size, R0[i], t0[i],
+                                    "point_to_line" if self.icp.use_p2l else "point_to_point", self.icp.normal_k,
+                                    None if p.max_corr_dist < 0 else p.max_corr_dist)
+        r = np.zeros(16)
+        r[0:4] = Ri[0].reshape(4); r[9:11] = ti[0]; r[12] = ei[0]
+        r[13] = info["delta"][0]; r[14] = info["iters"][0]; r[15] = info["status"][0]
+        return r
+
     def unpack(self):
         """(R, t, err, info) of the ICPs; pairs whose search fell outside the on-chip capacity (status 2) are redone
-        with the single-pair search's result as their start."""
+        with the single-pair search's result as their start.  With a gate, info["first_accepted"] is the candidate
+        slam.py:582-597 accepts (-1: none); with stop_after_first_accepted, a status-2 candidate after it is not redone
+        but reported SKIPPED (identity, err inf, 0 iterations), and info["status"] is 5 for every skipped candidate."""
         rec = self.search.records.cpu().numpy()[:self.B]
         res = self.icp.results.cpu().numpy()[:self.B].copy()
         if (rec[:, 11].astype(np.int64) == ST_NO_FINE).any():
             raise ValueError("attempt to get argmin of an empty sequence")          # features.py:231: np.argmin of an empty fine grid
         over = np.flatnonzero(rec[:, 11].astype(np.int64) == ST_CAPACITY)
+        first = -1
+        if self.stop:
+            # the device's answer never counts a status-2 candidate (its device ICP started from the wrong pose): the
+            # ones before it are redone in order, and the first of them that is accepted comes first
+            first = int(self.icp.first_accepted_dev.item())
         if len(over):
-            from .batch import icp_pair
             R0, t0, _, _ = self.search.results()
             clouds = self.search.raw.to_numpy()
-            p = self.icp.params
             for i in over:
-                Ri, ti, ei, info = icp_pair(clouds[self.icp.pair_src_host[i]], clouds[self.icp.pair_tgt_host[i]],
-                                            p.error_threshold, p.max_iterations, self.icp.voxel_size, R0[i], t0[i],
-                                            "point_to_line" if self.icp.use_p2l else "point_to_point", self.icp.normal_k,
-                                            None if p.max_corr_dist < 0 else p.max_corr_dist)
-                res[i, :] = 0.0
-                res[i, 0:4] = Ri[0].reshape(4); res[i, 9:11] = ti[0]; res[i, 12] = ei[0]
-                res[i, 13] = info["delta"][0]; res[i, 14] = info["iters"][0]; res[i, 15] = info["status"][0]
-        return unpack_results(res, 2)
+                idx = self.index_base + int(i) * self.index_stride
+                if self.stop and 0 <= first < idx:
+                    res[i, :] = 0.0
+                    res[i, 0] = res[i, 3] = 1.0
+                    res[i, 12] = res[i, 13] = np.inf
+                    res[i, 15] = _lib.ST_SKIPPED
+                    continue
+                res[i, :] = self._redo(i, R0, t0, clouds)
+                if self.stop and res[i, 12] < self.error_accept:
+                    first = idx
+        R, t, err, info = unpack_results(res, 2)
+        if self.error_accept is not None:
+            if not self.stop:                                                  # the full run: first in order below the gate
+                ok = np.flatnonzero(err < self.error_accept)
+                first = self.index_base + int(ok[0]) * self.index_stride if len(ok) else -1
+            info["first_accepted"] = first
+        return R, t, err, info
 
 
-def run_icp_pair_batch(sources, targets, icp_cfg=None, feat_cfg=None):
+def run_icp_pair_batch(sources, targets, icp_cfg=None, feat_cfg=None, error_accept=None, stop_after_first_accepted=False):
     """``_run_icp_pair(sources[i], targets[i], icp_cfg, feat_cfg, "rotation_search")`` for every i (slam.py:53-98, same
-    configuration keys and defaults) -> (R [B,2,2], t [B,2], err [B], info)."""
+    configuration keys and defaults) -> (R [B,2,2], t [B,2], err [B], info).  With ``error_accept``,
+    ``info["first_accepted"]`` is the candidate slam.py:582-597 accepts (-1: none); ``stop_after_first_accepted`` lets
+    the candidates after it stop early (status 5, RunIcpPairBatch)."""
     icp_cfg, feat_cfg = icp_cfg or {}, feat_cfg or {}
     clouds, ps, pt = _pair_lists(sources, targets)
     b = RunIcpPairBatch(clouds, ps, pt,
                         error_threshold=icp_cfg.get("error_threshold", 1e-7), max_iterations=icp_cfg.get("max_iterations", 100),
                         voxel_size=icp_cfg.get("voxel_size", 0.06), method=icp_cfg.get("method", "point_to_line"),
                         normal_k=icp_cfg.get("normal_k", 10), rotation_voxel_size=feat_cfg.get("rotation_voxel_size", 0.3),
-                        angle_step_coarse=feat_cfg.get("angle_step_coarse", 2.0), angle_step_fine=feat_cfg.get("angle_step_fine", 0.2))
+                        angle_step_coarse=feat_cfg.get("angle_step_coarse", 2.0), angle_step_fine=feat_cfg.get("angle_step_fine", 0.2),
+                        stop_after_first_accepted=stop_after_first_accepted, error_accept=error_accept)
     b.run()
     return b.unpack()
