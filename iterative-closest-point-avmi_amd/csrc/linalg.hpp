@@ -85,8 +85,45 @@ __device__ __forceinline__ void kabsch2(const double (&W)[4], double (&r)[4]) {
     }
 }
 
+// Rank-1 W = s u1 v1^T: every rotation with r u1 = v1 is optimal.  Completes
+// both bases deterministically: u2 = unit(u1 x e_k), e_k the axis of the
+// smallest |component| of u1; v2 = u2 carried by the minimal rotation u1 -> v1
+// (a half turn about u2 when u1 ~ -v1), re-orthogonalised against v1; u3, v3
+// by cross products.  Both bases are right-handed, so r = V U^T is a proper
+// rotation, and r = I when u1 = v1.  oracle/icp_oracle.c repeats this
+// operation for operation.
+__device__ inline void complete_rank1(double (&U)[9], double (&V)[9]) {
+    const double ux = U[0], uy = U[3], uz = U[6];
+    const double vx = V[0], vy = V[3], vz = V[6];
+    const double ax = fabs(ux), ay = fabs(uy), az = fabs(uz);
+    double ex = 0.0, ey = 0.0, ez = 0.0;
+    if (ax <= ay && ax <= az) ex = 1.0; else if (ay <= az) ey = 1.0; else ez = 1.0;
+    double px = uy * ez - uz * ey, py = uz * ex - ux * ez, pz = ux * ey - uy * ex;
+    double n = sqrt(px * px + py * py + pz * pz);
+    px = px / n; py = py / n; pz = pz / n;                               // u2
+    const double c = ux * vx + uy * vy + uz * vz;
+    double qx = px, qy = py, qz = pz;                                    // half turn about u2
+    if (1.0 + c > 1e-6) {                                                // Rodrigues with w = u1 x v1
+        const double wx = uy * vz - uz * vy, wy = uz * vx - ux * vz, wz = ux * vy - uy * vx;
+        const double f = (wx * px + wy * py + wz * pz) / (1.0 + c);
+        qx = c * px + (wy * pz - wz * py) + f * wx;
+        qy = c * py + (wz * px - wx * pz) + f * wy;
+        qz = c * pz + (wx * py - wy * px) + f * wz;
+    }
+    const double d = qx * vx + qy * vy + qz * vz;
+    qx = qx - d * vx; qy = qy - d * vy; qz = qz - d * vz;
+    n = sqrt(qx * qx + qy * qy + qz * qz);
+    qx = qx / n; qy = qy / n; qz = qz / n;                               // v2
+    U[1] = px; U[4] = py; U[7] = pz;
+    U[2] = uy * pz - uz * py; U[5] = uz * px - ux * pz; U[8] = ux * py - uy * px;
+    V[1] = qx; V[4] = qy; V[7] = qz;
+    V[2] = vy * qz - vz * qy; V[5] = vz * qx - vx * qz; V[8] = vx * qy - vy * qx;
+}
+
 // 3x3 case: one-sided Jacobi SVD W = U S V^T (columns sorted by descending
 // singular value), r = V U^T, reflection fixed on the last column of V.
+// Rank-deficient W: rank 0 gives r = I, rank 1 completes U and V
+// (complete_rank1), rank 2 completes U with a cross product.
 __device__ inline void kabsch3(const double (&W)[9], double (&r)[9]) {
     double A[9], V[9];
     for (int i = 0; i < 9; ++i) { A[i] = W[i]; V[i] = (i % 4 == 0) ? 1.0 : 0.0; }
@@ -122,7 +159,14 @@ __device__ inline void kabsch3(const double (&W)[9], double (&r)[9]) {
         S[jj] = sv[j];
         for (int i = 0; i < 3; ++i) { Vs[i * 3 + jj] = V[i * 3 + j]; U[i * 3 + jj] = sv[j] > 0 ? A[i * 3 + j] / sv[j] : 0.0; }
     }
-    if (S[0] > 0 && S[1] > 0 && !(S[2] > 0)) {       // rank 2: complete U with the cross product
+    // Numerical rank as np.linalg.matrix_rank counts it: sigma <= 3 eps sigma_1 is zero.  Such a column is noise
+    // and need not come out orthogonal (its squared norm can underflow and stall the sweeps), so it is rebuilt.
+    const double tiny = 3.0 * 2.220446049250313e-16 * S[0];
+    if (!(S[0] > 0)) {                               // rank 0 (W = 0): r = I
+        for (int i = 0; i < 9; ++i) { U[i] = (i % 4 == 0) ? 1.0 : 0.0; Vs[i] = U[i]; }
+    } else if (!(S[1] > tiny)) {                     // rank 1
+        complete_rank1(U, Vs);
+    } else if (!(S[2] > tiny)) {                     // rank 2: complete U with the cross product
         U[2] = U[3] * U[7] - U[6] * U[4];
         U[5] = U[6] * U[1] - U[0] * U[7];
         U[8] = U[0] * U[4] - U[3] * U[1];

@@ -314,7 +314,43 @@ void orc_p2l_solve_2d(const double* src, int K, const double* tgt, const double*
 /* ------------------------------------------------------------------------- */
 /* point-to-point step — reference icp.py:196-207                             */
 /* ------------------------------------------------------------------------- */
-/* One-sided Jacobi SVD of a 3x3 (dim<=3) matrix W = U diag(s) V^T, s descending. */
+/* Rank-1 W = s u1 v1^T: every rotation with r u1 = v1 is optimal.  Complete both
+ * bases deterministically: u2 = unit(u1 x e_k), e_k the axis of the smallest
+ * |component| of u1; v2 = u2 carried by the minimal rotation u1 -> v1 (a half turn
+ * about u2 when u1 ~ -v1), re-orthogonalised against v1; u3, v3 by cross products.
+ * Both bases are right-handed, so r = V U^T is a proper rotation, and r = I when
+ * u1 = v1.  Same operations as complete_rank1 in csrc/linalg.hpp. */
+static void complete_rank1(double* U, double* V) {
+    double ux = U[0], uy = U[3], uz = U[6];
+    double vx = V[0], vy = V[3], vz = V[6];
+    double ax = fabs(ux), ay = fabs(uy), az = fabs(uz);
+    double ex = 0.0, ey = 0.0, ez = 0.0;
+    if (ax <= ay && ax <= az) ex = 1.0; else if (ay <= az) ey = 1.0; else ez = 1.0;
+    double px = uy * ez - uz * ey, py = uz * ex - ux * ez, pz = ux * ey - uy * ex;
+    double n = sqrt(px * px + py * py + pz * pz);
+    px = px / n; py = py / n; pz = pz / n;                               /* u2 */
+    double c = ux * vx + uy * vy + uz * vz;
+    double qx = px, qy = py, qz = pz;                                    /* half turn about u2 */
+    if (1.0 + c > 1e-6) {                                                /* Rodrigues with w = u1 x v1 */
+        double wx = uy * vz - uz * vy, wy = uz * vx - ux * vz, wz = ux * vy - uy * vx;
+        double f = (wx * px + wy * py + wz * pz) / (1.0 + c);
+        qx = c * px + (wy * pz - wz * py) + f * wx;
+        qy = c * py + (wz * px - wx * pz) + f * wy;
+        qz = c * pz + (wx * py - wy * px) + f * wz;
+    }
+    double d = qx * vx + qy * vy + qz * vz;
+    qx = qx - d * vx; qy = qy - d * vy; qz = qz - d * vz;
+    n = sqrt(qx * qx + qy * qy + qz * qz);
+    qx = qx / n; qy = qy / n; qz = qz / n;                               /* v2 */
+    U[1] = px; U[4] = py; U[7] = pz;
+    U[2] = uy * pz - uz * py; U[5] = uz * px - ux * pz; U[8] = ux * py - uy * px;
+    V[1] = qx; V[4] = qy; V[7] = qz;
+    V[2] = vy * qz - vz * qy; V[5] = vz * qx - vx * qz; V[8] = vx * qy - vy * qx;
+}
+
+/* One-sided Jacobi SVD of a 3x3 (dim<=3) matrix W = U diag(s) V^T, s descending.
+ * U and V always come back orthonormal: W = 0 gives U = V = I (so r = I), a rank-1
+ * W is completed by complete_rank1, a rank-2 one by a cross product (numerical rank). */
 static void svd_jacobi(int d, const double* W, double* U, double* S, double* V) {
     double A[9], Vm[9];
     for (int i = 0; i < d * d; ++i) A[i] = W[i];
@@ -345,10 +381,16 @@ static void svd_jacobi(int d, const double* W, double* U, double* S, double* V) 
         int j = ord[jj]; S[jj] = sv[j];
         for (int i = 0; i < d; ++i) { V[i * d + jj] = Vm[i * d + j]; U[i * d + jj] = sv[j] > 0 ? A[i * d + j] / sv[j] : 0.0; }
     }
-    /* complete U to an orthonormal basis when W is rank deficient */
-    if (d == 3) {
-        int rank = (S[0] > 0) + (S[1] > 0) + (S[2] > 0);
-        if (rank == 2) {
+    /* complete U (and V) to orthonormal bases when W is rank deficient */
+    if (!(S[0] > 0)) {
+        for (int i = 0; i < d; ++i) for (int j = 0; j < d; ++j) { U[i * d + j] = (i == j); V[i * d + j] = (i == j); }
+    } else if (d == 3) {
+        /* numerical rank as np.linalg.matrix_rank counts it: sigma <= 3 eps sigma_1 is zero (such a column is
+         * noise and need not come out orthogonal: its squared norm can underflow and stall the sweeps) */
+        double tiny = 3.0 * 2.220446049250313e-16 * S[0];
+        int rank = 1 + (S[1] > tiny) + (S[2] > tiny);
+        if (rank == 1) complete_rank1(U, V);
+        else if (rank == 2) {
             U[0 * 3 + 2] = U[1 * 3 + 0] * U[2 * 3 + 1] - U[2 * 3 + 0] * U[1 * 3 + 1];
             U[1 * 3 + 2] = U[2 * 3 + 0] * U[0 * 3 + 1] - U[0 * 3 + 0] * U[2 * 3 + 1];
             U[2 * 3 + 2] = U[0 * 3 + 0] * U[1 * 3 + 1] - U[1 * 3 + 0] * U[0 * 3 + 1];
@@ -373,7 +415,7 @@ void orc_p2p_step(const double* P, const double* Q, int K, int dim, double* r, d
     for (int i = 0; i < K; ++i)
         for (int a = 0; a < dim; ++a) for (int b = 0; b < dim; ++b)
             W[a * dim + b] += (P[(size_t)i * dim + a] - mp[a]) * (Q[(size_t)i * dim + b] - mq[b]);
-    double U[9], S[3], V[9];
+    double U[9], S[3] = {0, 0, 0}, V[9];
     svd_jacobi(dim, W, U, S, V);
     for (int a = 0; a < dim; ++a) for (int b = 0; b < dim; ++b) {
         double s = 0; for (int c = 0; c < dim; ++c) s += V[a * dim + c] * U[b * dim + c];

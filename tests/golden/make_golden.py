@@ -506,6 +506,59 @@ def gold_run_icp_pair():
          icp_cfg=np.array([1e-10, 150, 0.04, 12]), feat_cfg=np.array([0.15, 1.5, 0.1]), **out)
 
 
+# ── 14. 3-D ICP (icp.py:132-223 on (n, 3) clouds) and the legacy odometry run_icp (icp.py:225-250) ─────────────
+def sha256(a):
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(a, dtype=np.float64).tobytes()).hexdigest()
+
+
+def _errors_after(src, tgt, kw, k):
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf):
+        return ref_icp.ICP(src, tgt, **dict(kw, max_iterations=k))[2]
+
+
+def _margin(src, tgt, kw, iters):
+    """Relative distance of the last two |prev - err| to error_threshold: the convergence test is not borderline."""
+    thr = kw["error_threshold"]
+    e = [float("inf") if k <= 0 else float(_errors_after(src, tgt, kw, k)) for k in (iters - 2, iters - 1, iters)]
+    last, before = abs(e[1] - e[2]), abs(e[0] - e[1])
+    return min((thr - last) / thr, (before - thr) / thr)
+
+
+def gold_icp3d():
+    teapot = np.loadtxt(os.path.join(REF, "teapot.csv"), delimiter=",")
+    cases = synth.icp3d_cases(teapot)
+    out = {}
+    for name, (src, tgt, kw) in cases.items():
+        R, t, e, it, conv = run_icp(src, tgt, **kw)
+        if conv:
+            m = _margin(src, tgt, kw, it)
+            assert m > 1e-6, (name, m)
+            out[f"{name}__margin"] = np.float64(m)
+        out[f"{name}__R"], out[f"{name}__t"] = R, t
+        out[f"{name}__err"], out[f"{name}__iters"], out[f"{name}__conv"] = np.float64(e), np.int64(it), np.int64(conv)
+        out[f"{name}__src_sha"], out[f"{name}__tgt_sha"] = np.array(sha256(src)), np.array(sha256(tgt))
+        print(f"  {name:16s} N={len(ref_icp.voxel_downsample(src, kw['voxel_size'])):5d} "
+              f"M={len(ref_icp.voxel_downsample(tgt, kw['voxel_size'])):5d} iters={it} err={e:.3e}")
+    # legacy odometry with its defaults (voxel 0.5, 100 iterations, 1e-5)
+    stream = synth.odometry3d_stream()
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf):
+        pose, traj = ref_icp.run_icp(iter(stream))
+    txt = buf.getvalue()
+    errs = [float(x) for x in re.findall(r"Scan:\s+\d+ Error:\s+(\S+)", txt)]
+    iters = [int(x) + 1 for x in re.findall(r"converged: iter=(\d+)", txt)]
+    assert len(errs) == len(iters) == len(stream) - 1, txt
+    for k in range(1, len(stream)):
+        m = _margin(stream[k - 1][1], stream[k][1], dict(error_threshold=1e-5, voxel_size=0.5), iters[k - 1])
+        assert m > 1e-6, (k, m)
+    out["odo__pose"], out["odo__traj"] = pose, np.array(traj)
+    out["odo__errs"], out["odo__iters"] = np.array(errs), np.array(iters, dtype=np.int64)
+    out["odo__sha"] = np.array([sha256(p) for _, p in stream])
+    save("icp3d", names=np.array(list(cases)), **out)
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:                      # python make_golden.py gold_submap_rotation ...
         for name in sys.argv[1:]:
@@ -524,3 +577,4 @@ if __name__ == "__main__":
     gold_pose_graph()
     gold_icp_limit()
     gold_run_icp_pair()
+    gold_icp3d()

@@ -332,3 +332,129 @@ def test_run_icp_pair_rotation_search_then_icp():
         assert abs(err - float(z[f"p{i}__err"])) <= 1e-9 * max(1.0, err), i
         seen.add((info["iters"] == 150, err < 0.08))
     assert seen == {(False, True), (False, False), (True, True), (True, False)}       # every regime is in the fixture
+
+
+# ── 3-D ICP (golden: make_golden.py gold_icp3d) ─────────────────────────────────────────────────────────────────────
+def _sha256(a):
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(a, dtype=np.float64).tobytes()).hexdigest()
+
+
+def icp3d_cases():
+    """name -> (source, target, kwargs, golden) for every case of icp3d.npz; the inputs are regenerated by
+    icpmi.synth and must hash to what the fixture was made from."""
+    from icpmi import synth
+    z = load_golden("icp3d")
+    cases = synth.icp3d_cases(load_golden("icp")["teapot"])
+    assert list(cases) == [str(n) for n in z["names"]]
+    for name, (s, t, kw) in cases.items():
+        assert _sha256(s) == str(z[f"{name}__src_sha"]) and _sha256(t) == str(z[f"{name}__tgt_sha"]), name
+    return {name: (s, t, kw, z) for name, (s, t, kw) in cases.items()}
+
+
+def odometry3d_stream():
+    from icpmi import synth
+    z = load_golden("icp3d")
+    stream = synth.odometry3d_stream()
+    assert [_sha256(p) for _, p in stream] == [str(h) for h in z["odo__sha"]]
+    return stream, z
+
+
+def assert_proper_rotation(R, tol=1e-12):
+    R = np.asarray(R)
+    assert np.abs(R.T @ R - np.eye(R.shape[0])).max() <= tol, R
+    assert abs(np.linalg.det(R) - 1.0) <= tol, R
+
+
+def assert_rank_deficient_case(R, t, err, iters, s, kw, z, name):
+    """W has rank <= 1: the rotation about the line is free, so demand a proper rotation that moves the source where
+    the reference's does, the same error and the same iteration count."""
+    assert_proper_rotation(R)
+    src = oracle.voxel_downsample(s, kw["voxel_size"])
+    Rr, tr = z[f"{name}__R"], z[f"{name}__t"]
+    assert np.abs((src @ R.T + t) - (src @ Rr.T + tr)).max() <= 1e-9, name
+    assert abs(err - float(z[f"{name}__err"])) <= 1e-11 * max(1.0, abs(err)), name
+    assert iters == int(z[f"{name}__iters"]), name
+
+
+def test_icp3d_golden_inputs_and_margins():
+    from icpmi import synth
+    cases = icp3d_cases()
+    assert len(cases) >= 20
+    for name, (s, t, kw, z) in cases.items():
+        if int(z[f"{name}__conv"]):
+            assert float(z[f"{name}__margin"]) > 1e-6, name          # convergence test is not borderline
+    assert set(synth.ICP3D_RANK_DEFICIENT) < set(cases)
+
+
+@pytest.mark.parametrize("name", [
+    "lat_n1200_m2048", "lat_n1800_m6000", "lat_n2348_m2048", "lat_n2848_m2049", "lat_n3900_m1500", "lat_n5396_m6000",
+    "tile_near_tie", "teapot_init", "teapot_Ronly", "teapot_corr", "teapot_break0", "teapot_maxit5", "breakN",
+    "planar_z0", "tilted_plane", "mirrored", "cube", "tetrahedron", "sphere", "line_x", "line_general",
+    "single_point"])
+def test_icp3d_matches_reference(name):
+    from icpmi import synth
+    s, t, kw, z = icp3d_cases()[name]
+    R, tt, err, info = oracle.icp(s, t, kdtree=True, **kw)
+    if name in synth.ICP3D_RANK_DEFICIENT:
+        assert_rank_deficient_case(R, tt, err, info["iters"], s, kw, z, name)
+        if name in ("line_x", "single_point"):                          # u1 = v1 / W = 0: the reference's R is I
+            assert rot_err(R, tt, z[f"{name}__R"], z[f"{name}__t"]) < 1e-9
+            assert np.abs(R - np.eye(3)).max() <= 1e-15
+        return
+    assert_proper_rotation(R)
+    assert rot_err(R, tt, z[f"{name}__R"], z[f"{name}__t"]) < 1e-9, name
+    ref = float(z[f"{name}__err"])
+    assert (np.isinf(err) and np.isinf(ref)) or abs(err - ref) <= 1e-12 * max(1.0, abs(err)), name
+    if int(z[f"{name}__conv"]):
+        assert info["status"] == oracle.CONVERGED and info["iters"] == int(z[f"{name}__iters"]), name
+    else:
+        assert info["status"] in (oracle.MAXITER, oracle.FEW_INLIERS), name
+    if name == "teapot_break0":
+        assert info["status"] == oracle.FEW_INLIERS and info["iters"] == 0
+    if name == "breakN":
+        assert info["status"] == oracle.FEW_INLIERS and info["iters"] == 1
+    if name == "teapot_maxit5":
+        assert info["status"] == oracle.MAXITER and info["iters"] == 5
+
+
+def test_p2p_step_rank_deficient_returns_proper_rotations():
+    """W = 0 and rank-1 W: what np.linalg.svd plus the det fix gives where that is unique (R = I), else any proper
+    rotation that maps u1 onto v1 (icp.py:202-206)."""
+    R, t = oracle.p2p_step(np.array([[0.3, -0.2, 0.5]]), np.array([[1.0, 2.0, 3.0]]))              # rank 0
+    assert np.array_equal(R, np.eye(3)) and np.allclose(t, [0.7, 2.2, 2.5], atol=1e-15)
+    R, t = oracle.p2p_step(np.array([[0.3, -0.2]]), np.array([[1.0, 2.0]]))                        # rank 0, 2-D
+    assert np.array_equal(R, np.eye(2))
+    P = np.array([[0.0, 0, 0], [2, 0, 0]])
+    R, t = oracle.p2p_step(P, P + [0.5, 0, 0])                                                     # W = diag(2, 0, 0)
+    assert np.array_equal(R, np.eye(3)) and np.array_equal(t, [0.5, 0, 0])
+    R, t = oracle.p2p_step(P, P[::-1] + [0.5, 0, 0])                                               # u1 = -v1
+    assert_proper_rotation(R)
+    assert np.allclose(R @ [1, 0, 0], [-1, 0, 0], atol=1e-15)
+    rng = np.random.default_rng(5)
+    for _ in range(50):                                                                            # general lines
+        d, e = rng.normal(size=3), rng.normal(size=3)
+        d, e = d / np.linalg.norm(d), e / np.linalg.norm(e)
+        a = rng.uniform(-2, 2, size=9)
+        sgn = rng.choice([-1.0, 1.0])
+        R, t = oracle.p2p_step(a[:, None] * d, sgn * a[:, None] * e)
+        assert_proper_rotation(R)
+        assert np.abs(R @ d - sgn * e).max() < 1e-12
+
+
+def test_run_icp3d_odometry_matches_reference():
+    """icp.py:225-250 on the oracle's ICP: the 4x4 pose chain of the reference's run_icp."""
+    stream, z = odometry3d_stream()
+    pose, traj, errs, iters = np.eye(4), [], [], []
+    for k in range(1, len(stream)):
+        r, t, err, info = oracle.icp(stream[k - 1][1], stream[k][1], 1e-5, 100, 0.5)
+        Rn = pose[:3, :3] @ r.T
+        pose[:3, :3] = Rn
+        pose[:3, 3] = pose[:3, 3] - Rn @ t
+        traj.append(pose.copy())
+        errs.append(err)
+        iters.append(info["iters"])
+    assert np.abs(pose - z["odo__pose"]).max() < 1e-8
+    assert np.abs(np.array(traj) - z["odo__traj"]).max() < 1e-8
+    assert np.allclose(errs, z["odo__errs"], rtol=1e-11, atol=0)
+    assert iters == list(z["odo__iters"])
