@@ -82,14 +82,13 @@ const char* icpmi_strerror(int code);
  * read from the environment variable ICPMI_<NAME> ONCE, when the library first
  * looks at an option, and icpmi_set_option overrides it afterwards (value NULL
  * unsets).  Names (with or without the ICPMI_ prefix): ICP2_SIDE (0: no side
- * streams), ICP2_SHAPE ("TxS": workgroup shape of the fused ICP), ICP2_FILTER
- * (0: no float32 filter), ICP2_STAGES (1: one launch, 2: two stages also for
+ * streams), ICP2_STAGES (1: one launch, 2: two stages also for
  * point_to_point), ICP2_FAR (mean squared error in m^2 of a pair's first step
  * above which it finishes on the kernel for far queries; default 1, 0: never),
  * POLAR (0 never / 2 always the bearing order), PREP_KNN
  * (grid | sweep), RAYCAST (atomic | tiles | owner: the pass of the occupancy
- * update), RT_WGS (resident workgroups of the tile pass), RS_BATCH (full: the
- * batched rotation search scores every angle; projection: no bearing order).
+ * update), RS_BATCH (full: the batched rotation search scores every angle;
+ * projection: no bearing order).
  * Unknown names: ICPMI_ERR_ARG.  Must not race with running calls.
  * icpmi_shutdown synchronises and destroys the side streams and events the
  * library made (they are made again on demand); call it before unloading. */

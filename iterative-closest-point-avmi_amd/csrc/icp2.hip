@@ -20,23 +20,10 @@
 //
 // Pairs that do not fit (more than 4 rows per thread, target larger than the
 // LDS copy, 3-D) run on the exhaustive kernel of icp.hip.
-#include <cstdio>
 #include <cstdlib>
 
 #include "linalg.hpp"
 #include "sweep.hpp"
-
-// -DICPMI_DIAG: diagnostic build; thread 0 accumulates s_memtime cycles per phase
-// and stores them in the unused R slots 4..8 of its result record.  Never shipped.
-#ifdef ICPMI_DIAG
-#define DIAG_T(var) const unsigned long long var = __builtin_readcyclecounter()
-#define DIAG_SET(var) var = __builtin_readcyclecounter()
-#define DIAG_ADD(acc, a, b) acc += (double)((b) - (a))
-#else
-#define DIAG_T(var)
-#define DIAG_SET(var)
-#define DIAG_ADD(acc, a, b)
-#endif
 
 namespace icpmi {
 
@@ -155,15 +142,6 @@ constexpr int CTRL_R = 0, CTRL_T = 4, CTRL_STOP = 6, CTRL_MP = 8, CTRL_MQ = 10;
 constexpr int CTRL_RT = 12, CTRL_TT = 16, CTRL_ERR = 18, CTRL_PREV = 19, CTRL_DELTA = 20, CTRL_ITERS = 21, CTRL_STATUS = 22,
               CTRL_DOUBLES = 24;
 
-#ifndef ICP2_PK
-#define ICP2_PK 1               // searches of the filter instantiations by the packed float32 walk (sweep.hpp, round 4); 0: the round-2 walks
-#endif
-#ifndef ICP2_FAR_PK
-#define ICP2_FAR_PK 0           // 1: the far continuation's searches by the packed walk and scan too (sweep.hpp) — exact (its tests pass on it) and
-                                // slower there: 4.05 against 3.74 ms for the ICP half of the 3 m / 20 degree candidates.  The continuation has already
-                                // packed its searching rows into few lanes, and a scan that offers every image of a block it enters issues more than
-                                // one that evaluates the few images inside the threshold exactly.
-#endif
 #ifndef ICP2_STAGE1_ITERS
 #define ICP2_STAGE1_ITERS 12    // iterations of the first stage of a large batch (launch_icp2)
 #endif
@@ -431,12 +409,8 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
         // runs iterations 2 .. max_iterations - 1 (the test rides on the convergence test of iteration 1: no arithmetic of its own)
         const double far_err = !RESUME && a.max_iterations > 2 && N <= ICP2_FAR_THREADS * ICP2_FAR_SMAX && M <= ICP2_FAR_POINTS
                                    ? a.far_d2 : __builtin_inf();
-#ifdef ICPMI_DIAG
-        double dg_nn = 0, dg_red = 0, dg_lead = 0, dg_apply = 0;
-#endif
         const int it_end = RESUME ? a.max_iterations : min(a.max_iterations, a.it_limit);
         for (int it = RESUME ? a.it_begin : 0; it < it_end; ++it) {
-            DIAG_T(c0);
             // the gate, loaded by one lane now and tested after the search (gate_stop): a cross-XCD load is a large part
             // of a tail iteration; agent scope, so that no stale copy in this CU's L1 hides a lower value
             int gate_seen = 0x7fffffff;
@@ -507,7 +481,7 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
                     if (srch[s]) {
                         double d2s;
                         if constexpr (FILT) {
-                            if (ICP2_PK && __popcll(__ballot(true)) >= ICP2_PK_MIN)
+                            if (__popcll(__ballot(true)) >= ICP2_PK_MIN)
                                 pos[s] = sweepf_nn_pk(lds_sq, sxy, filt, M, dir, uabs, px[s], py[s], pos[s], it < ICP2_PLAIN_CENTRED);
                             else pos[s] = sweepf_nn(lds_sq, sxy, filt, M, dir, uabs, px[s], py[s], pos[s], it < ICP2_PLAIN_CENTRED, d2s);
                         }
@@ -538,13 +512,7 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
                     __builtin_amdgcn_wave_barrier();
                     for (int j = tid & (ICPMI_WAVE - 1); j < nq; j += ICPMI_WAVE) {
                         const FarSlot e = far_q[j];
-#ifdef ICPMI_DIAG
-                        const Top2 r = sweepf_top2_far(lds_sq, sxy, lds_tree, tree_leaves, filt, M, dir, uabs, e.in.x, e.in.y, e.in.seed, &res[11]);
-#elif ICP2_FAR_PK
-                        const Top2 r = sweepf_top2_far_pk(lds_sq, sxy, lds_tree, tree_leaves, filt, M, dir, uabs, e.in.x, e.in.y, e.in.seed);
-#else
                         const Top2 r = sweepf_top2_far(lds_sq, sxy, lds_tree, tree_leaves, filt, M, dir, uabs, e.in.x, e.in.y, e.in.seed);
-#endif
                         FarSlot o;
                         o.out.s1 = r.s1; o.out.s3 = r.s3; o.out.p1 = r.p1; o.out.p2 = r.p2;
                         far_q[j] = o;
@@ -566,7 +534,7 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
                         else if constexpr (FILT) {
                             // the packed walk costs a wave the same whether one lane searches or all do; the branching walk
                             // is cheap while few do (its exact path is then rarely entered): chosen per wave by the count
-                            if (ICP2_PK && __popcll(__ballot(true)) >= ICP2_PK_MIN)
+                            if (__popcll(__ballot(true)) >= ICP2_PK_MIN)
                                 t2 = sweepf_top2_pk(lds_sq, sxy, filt, M, dir, uabs, px[s], py[s], pos[s], centred);
                             else t2 = sweepf_top2(lds_sq, sxy, filt, M, dir, uabs, px[s], py[s], pos[s], centred);
                         }
@@ -588,18 +556,8 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
                         bf = bf - fabsf(bf) * 1e-6f;
                         budget[s] = t2.s3 < __builtin_inf() ? bf : __builtin_inff();
                         ax[s] = (float)px[s]; ay[s] = (float)py[s];
-#ifdef ICPMI_DIAG
-                        atomicAdd(&res[8], 1.0);             // diag: number of searches run by this pair
-#endif
                     }
             }
-#ifdef ICPMI_DIAG
-            __syncthreads();          // diag only: charge the slowest wave's search to the search phase
-#endif
-            DIAG_T(c1);
-#ifdef ICPMI_DIAG
-            unsigned long long c2 = 0;
-#endif
             // rows that take part in the solve: all valid rows, or those within max_corr_dist of their match
             // (icp.py:184-185: nn_dists**2 < max_corr_dist**2, the distance squared again after its root)
             bool in[ICP2_SMAX];
@@ -630,7 +588,6 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
                 acc[10] = e_part;
                 wave_totals<11>(redA, acc);
                 __syncthreads();
-                DIAG_SET(c2);
                 if (lead) {
                     combine_totals<11>(redA, NWAVES, acc);
                     const int fin = gate_stop(ctrl, a.gate.hint, gate_seen, gate_index, tid == 0,
@@ -678,7 +635,6 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
                 m[5] = e_part;
                 wave_totals<6>(redA, m);
                 __syncthreads();
-                DIAG_SET(c2);
                 if (lead) {
                     combine_totals<6>(redA, NWAVES, m);
                     const int fin = gate_stop(ctrl, a.gate.hint, gate_seen, gate_index, tid == 0,
@@ -719,7 +675,6 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
                 }
                 __syncthreads();
             }
-            DIAG_T(c3);
             if (ctrl[CTRL_STOP] == (double)FIN_STOP) { stopped = true; break; }
             // ── apply to ALL rows; squared residual against this search's matches, icp.py:212-215 ─
             const double r0 = ctrl[CTRL_R], r1 = ctrl[CTRL_R + 1], r2 = ctrl[CTRL_R + 2], r3 = ctrl[CTRL_R + 3];
@@ -740,11 +695,6 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
                 e_part += se;
             }
             if (!RESUME && it == 1 && ctrl[CTRL_STOP] == (double)FIN_FAR) break;
-            DIAG_T(c4);
-#ifdef ICPMI_DIAG
-            DIAG_ADD(dg_nn, c0, c1); DIAG_ADD(dg_red, c1, c2); DIAG_ADD(dg_lead, c2, c3); DIAG_ADD(dg_apply, c3, c4);
-            if (tid == 0) { res[4] = dg_nn; res[5] = dg_red; res[6] = dg_lead; res[7] = dg_apply; }
-#endif
         }
         const bool far_parked = !RESUME && !stopped && ctrl[CTRL_STOP] == (double)FIN_FAR;      // left after iteration 1
         if (!RESUME && !stopped && (far_parked || it_end < a.max_iterations)) {
@@ -780,10 +730,8 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
         }
     }
     if (tid == 0) {
-#ifndef ICPMI_DIAG
 #pragma unroll
         for (int i = 0; i < ICPMI_RES_DOUBLES; ++i) res[i] = 0.0;
-#endif
         res[0] = ctrl[CTRL_RT]; res[1] = ctrl[CTRL_RT + 1]; res[2] = ctrl[CTRL_RT + 2]; res[3] = ctrl[CTRL_RT + 3];
         res[ICPMI_RES_T] = ctrl[CTRL_TT]; res[ICPMI_RES_T + 1] = ctrl[CTRL_TT + 1];
         res[ICPMI_RES_ERR] = ctrl[CTRL_ERR];
@@ -865,15 +813,6 @@ int launch_icp2(const double* pts, const int32_t* off, const int32_t* cnt, const
     a.error_threshold = p->error_threshold; a.max_corr_dist = p->max_corr_dist;
     a.max_iterations = p->max_iterations; a.method = p->method; a.has_init = p->has_init;
     const bool in_lds = max_tgt_n <= 4096;
-    // Workgroup shape by source size (rows per thread bounded by the instantiation).  option ICP2_SHAPE = "TxS"
-    // (threads x rows per thread, one of the instantiations below) overrides the choice for experiments;
-    // option ICP2_FILTER = 0 turns the single-precision filter off.
-    int T = 0, SM = 0;
-    if (const char* env = option("ICP2_SHAPE")) {
-        if (sscanf(env, "%dx%d", &T, &SM) != 2) { T = 0; SM = 0; }
-    }
-    const char* fenv = option("ICP2_FILTER");
-    const bool want_filter = !(fenv && fenv[0] == '0');
 #define ICPMI_ICP2_GO(TT, SS)                                                                                                    \
     do {                                                                                                                         \
         if (!in_lds) ICPMI_ICP2_GO2(TT, SS, false, false);                                                                      \
@@ -909,20 +848,20 @@ int launch_icp2(const double* pts, const int32_t* off, const int32_t* cnt, const
     a.n_lo = -1; a.m_lo = 0; a.skip_over = 0;
     int T2 = 0, SM2 = 0;                // second launch for the pairs the first shape cannot hold
     const bool many = n_pairs >= 1024;
-    if (T == 0) {
-        // A voxel-filtered 2 048-beam scan keeps ~1 400 rows: 768 threads x 2 rows, two workgroups per CU (6 waves per
-        // SIMD at 80 registers; 512 x 3 at 4 waves per SIMD is 5 % slower) — one pair's serial solve and barrier waits
-        // overlap the other's search.  Clouds that keep more than 1 536 rows go to a second launch (1 024 threads).
-        // With few pairs (less than two per CU) 1 024 threads x 2 rows finish a pair soonest.
-        if (max_src_n <= 1024) { T = 512; SM = 2; }
-        else if (many) { T = 768; SM = 2; }
-        else if (max_src_n <= 2048) { T = 1024; SM = 2; }
-        else { T = 1024; SM = 4; }
-    }
+    // Workgroup shape by source size (rows per thread bounded by the instantiation).
+    // A voxel-filtered 2 048-beam scan keeps ~1 400 rows: 768 threads x 2 rows, two workgroups per CU (6 waves per
+    // SIMD at 80 registers; 512 x 3 at 4 waves per SIMD is 5 % slower) — one pair's serial solve and barrier waits
+    // overlap the other's search.  Clouds that keep more than 1 536 rows go to a second launch (1 024 threads).
+    // With few pairs (less than two per CU) 1 024 threads x 2 rows finish a pair soonest.
+    int T, SM;
+    if (max_src_n <= 1024) { T = 512; SM = 2; }
+    else if (many) { T = 768; SM = 2; }
+    else if (max_src_n <= 2048) { T = 1024; SM = 2; }
+    else { T = 1024; SM = 4; }
     // LDS copy of the target: 36 B per point, 48 B with the float32 images of the filter.  Two workgroups of the
     // 512-thread shapes share a CU only up to 1 536 filter points (2 x 73.7 KB): larger targets, like larger
     // sources, are left to the second launch.  The filter needs <= 2 048 points (96 KB, one workgroup per CU).
-    int cap1 = ((T == 512 || T == 768) && many && in_lds && want_filter && max_tgt_n > 1536) ? 1536 : max_tgt_n;
+    int cap1 = ((T == 512 || T == 768) && many && in_lds && max_tgt_n > 1536) ? 1536 : max_tgt_n;
     if (T * SM < max_src_n || cap1 < max_tgt_n) { T2 = 1024; SM2 = max_src_n <= 2048 ? 2 : 4; a.skip_over = 1; }
     // Two stages for a large batch (see Icp2Args): needs the caller's workspace for the parked state.  Below ~1 000 pairs
     // every long pair starts within the first two rounds anyway and the stages only add their own cost (512 pairs: 0.70
@@ -948,7 +887,7 @@ int launch_icp2(const double* pts, const int32_t* off, const int32_t* cnt, const
     // sent over and the 16 384-pair batch takes 5.7 instead of 5.05 ms; 0 = never)
     double far_d2 = 1.0;
     if (const char* e = option("ICP2_FAR")) far_d2 = atof(e);
-    const bool far_ok = have_ws && in_lds && want_filter && far_d2 > 0.0 && p->max_iterations > 2;
+    const bool far_ok = have_ws && in_lds && far_d2 > 0.0 && p->max_iterations > 2;
     // the far continuation's LDS: the filter layout + the box hierarchy (2 B per point at most) + a slot per row of its shape
     // (every wave owns the stretch behind its own lanes, whatever the batch's source sizes).  Asked for BEFORE the first
     // launch: without it (another ARCH than gfx950's 160 KB) no pair is parked for a kernel that could not start.
@@ -988,11 +927,9 @@ int launch_icp2(const double* pts, const int32_t* off, const int32_t* cnt, const
         while (cap < cap1) cap <<= 1;
         if (cap1 > 1024 && cap1 <= 1536) cap = 1536;
         a.lds_points = cap;
-        const bool filter = in_lds && want_filter && cap <= 2048;
+        const bool filter = in_lds && cap <= 2048;
         const size_t lds = in_lds ? (filter ? (size_t)cap * 48 + 32 : (size_t)cap * 36) : 0;
         if (T == 512 && SM == 2) ICPMI_ICP2_GO(512, 2);
-        else if (T == 512 && SM == 3) ICPMI_ICP2_GO(512, 3);
-        else if (T == 512 && SM == 4) ICPMI_ICP2_GO(512, 4);
         else if (T == 768 && SM == 2) ICPMI_ICP2_GO(768, 2);
         else if (T == 1024 && SM == 2) ICPMI_ICP2_GO(1024, 2);
         else if (T == 1024 && SM == 4) ICPMI_ICP2_GO(1024, 4);
@@ -1011,11 +948,3 @@ int launch_icp2(const double* pts, const int32_t* off, const int32_t* cnt, const
 }
 
 }  // namespace icpmi
-
-#ifdef ICPMI_DIAG
-extern "C" int icpmi_diag_read(unsigned long long* out16) {   // diagnostic build only: read and clear the phase counters of sweep.hpp
-    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(icpmi::icpmi_dbg), 16 * sizeof(unsigned long long)) != hipSuccess) return 1;
-    unsigned long long z[16] = {0};
-    return hipMemcpyToSymbol(HIP_SYMBOL(icpmi::icpmi_dbg), z, sizeof(z)) == hipSuccess ? 0 : 1;
-}
-#endif

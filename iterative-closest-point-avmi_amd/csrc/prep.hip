@@ -9,9 +9,6 @@
 
 namespace icpmi {
 
-#ifndef PREP_POLAR32
-#define PREP_POLAR32 1          // bearing order by a 32-bit (fixed-point float32 bearing | row) sort; 0: float64 atan2, 64-bit network
-#endif
 #ifndef PREP_AXIS_STEP
 #define PREP_AXIS_STEP 4        // large batches estimate the search axis on every PREP_AXIS_STEP-th point
 #endif
@@ -63,13 +60,13 @@ __device__ __forceinline__ void prep_sort_polar32(const double* __restrict__ P, 
 template <int E>
 __device__ __forceinline__ void prep_sort_regs(const double* __restrict__ P, int M, int dir, uint64_t* by_row, uint64_t* keys,
                                                uint32_t* rows) {
-    if (PREP_POLAR32 && dir == SWEEP_POLAR) { prep_sort_polar32<E>(P, M, keys, rows); return; }
+    if (dir == SWEEP_POLAR) { prep_sort_polar32<E>(P, M, keys, rows); return; }
     constexpr uint64_t ROW_MASK = 0x7ff;                               // rows below 2 048
     uint64_t v[E];
 #pragma unroll
     for (int e = 0; e < E; ++e) {
         const int i = (int)threadIdx.x * E + e;
-        const uint64_t k = i < M ? f64_sortable(dir == SWEEP_POLAR ? polar_key(P[2 * i], P[2 * i + 1]) : proj(dir, P[2 * i], P[2 * i + 1])) : ~0ull;
+        const uint64_t k = i < M ? f64_sortable(proj(dir, P[2 * i], P[2 * i + 1])) : ~0ull;
         by_row[i] = k;
         v[e] = i < M ? ((k & ~ROW_MASK) | (uint64_t)i) : ~0ull;
     }
@@ -384,10 +381,9 @@ extern "C" int icpmi_prepare_targets_ex(const double* pts, const int32_t* off_de
     // selected cloud has at most 2 048 rows — the fused ICP launch picks ONE instantiation for the whole batch from the
     // same max_n, and the ones for larger targets (no float32 images) cannot walk a bearing order: a batch that mixes
     // scans with one rolling submap therefore sorts everything along projections.  Option "POLAR": 0 never, 2 always
-    // (tests); the filter being off (option "ICP2_FILTER" = 0) also turns it off.
+    // (tests).
     int polar = allow_polar && max_n <= 2048 ? 1 : 0;
     if (const char* env = option("POLAR")) polar = polar ? (env[0] == '0' ? 0 : (env[0] == '2' ? 2 : 1)) : 0;
-    if (const char* env = option("ICP2_FILTER")) polar = env[0] == '0' ? 0 : polar;
     int split = 256 / n_sel;                 // a workgroup for every CU when the batch is small
     split = split < 1 ? 1 : (split > 16 ? 16 : split);
     // k-NN search of the normals: grid for few clouds that will be sorted along a projection (a wall across the sweep axis

@@ -622,12 +622,7 @@ constexpr int RO_NEAR = RO_N0 + 8 * RO_N1;                       // 64 + 128 wor
 
 __global__ __launch_bounds__(RO_THREADS) void ray_owner_kernel(GridDesc g, const double* __restrict__ origin,
                                                               const double* __restrict__ hits, int nb, FinArgs f,
-                                                              int tiles_x, int tiles_y, unsigned long long* dbg) {
-#ifdef RO_X_TIMES        // diagnostic build: cycles per phase of every workgroup into the workspace (tools/time_livescan.py)
-    const unsigned long long tt0 = __builtin_readcyclecounter();
-    unsigned long long t_sel = 0, t_walk = 0;
-    if (threadIdx.x == 0) { dbg[4 * blockIdx.x] = 0; dbg[4 * blockIdx.x + 1] = 0; dbg[4 * blockIdx.x + 2] = 0; dbg[4 * blockIdx.x + 3] = 1; }
-#endif
+                                                              int tiles_x, int tiles_y) {
     __shared__ uint32_t cnt[RT_TILE * RT_TILE];
     __shared__ int4 seg[2 * RO_THREADS];                             // this chunk's beams: hit cell, step range inside the rectangle
     __shared__ uint16_t items[2 * RO_THREADS / ICPMI_WAVE * (RT_TILE / RO_STEPS)];   // (wave of beams << 8 | block of RO_STEPS steps)
@@ -691,9 +686,6 @@ __global__ __launch_bounds__(RO_THREADS) void ray_owner_kernel(GridDesc g, const
     const double owx = origin[0], owy = origin[1];
     const double rinv = 1.0 / g.res;
     for (int base = 0; base < nb; base += PER_CHUNK * RO_THREADS) {  // uniform trip count
-#ifdef RO_X_TIMES
-        const unsigned long long ta = __builtin_readcyclecounter();
-#endif
         const int par = (base / (PER_CHUNK * RO_THREADS)) & 1;
 #pragma unroll
         for (int j = 0; j < PER_CHUNK; ++j) {                        // a wave's 64 beams are neighbours
@@ -748,13 +740,8 @@ __global__ __launch_bounds__(RO_THREADS) void ray_owner_kernel(GridDesc g, const
             if (in < nb) { hwx[j] = hits[2 * (size_t)in]; hwy[j] = hits[2 * (size_t)in + 1]; }
         }
         __syncthreads();
-#ifdef RO_X_TIMES
-        const unsigned long long tb = __builtin_readcyclecounter();
-        t_sel += tb - ta;
-#endif
         const int total = n_items[par];
         if (tid == 0) n_items[par ^ 1] = 0;                          // nobody touches it between this barrier and the next
-#ifndef RO_X_NOWALK
         for (int it = wave_id(); it < total; it += RO_THREADS / ICPMI_WAVE) {       // free cells, mapping.py:135-139
             const int e = items[it];
             const int4 sg = seg[(e >> 8) * ICPMI_WAVE + lane];
@@ -791,14 +778,9 @@ __global__ __launch_bounds__(RO_THREADS) void ray_owner_kernel(GridDesc g, const
                 }
             }
         }
-#endif
         __syncthreads();                                             // seg and items are written again by the next chunk
-#ifdef RO_X_TIMES
-        t_walk += __builtin_readcyclecounter() - tb;
-#endif
     }
     // this rectangle's cells: H hit adds, then M miss adds, then the clip (mapping.py:129,139,141)
-#ifndef RO_X_NOFIN
 #pragma unroll
     for (int j = 0; j < FIN; ++j) {
         const int c = j * RO_THREADS + tid;
@@ -806,14 +788,6 @@ __global__ __launch_bounds__(RO_THREADS) void ray_owner_kernel(GridDesc g, const
         const uint32_t v = cnt[c];
         if (v) f.log_odds[(size_t)(y0 + c / w) * g.nx + (x0 + c % w)] = apply_counts(old[j], v >> 16, v & 0xffffu, f.l_hit, f.l_miss, f.lo32, f.hi32, true);
     }
-#endif
-#ifdef RO_X_TIMES
-    __syncthreads();
-    if (tid == 0) {
-        const unsigned long long te = __builtin_readcyclecounter();
-        dbg[4 * blockIdx.x] = t_sel; dbg[4 * blockIdx.x + 1] = t_walk; dbg[4 * blockIdx.x + 2] = te - tt0; dbg[4 * blockIdx.x + 3] = 2 + (unsigned long long)(w * h);
-    }
-#endif
 }
 
 __global__ void world_to_grid_kernel(const double* __restrict__ w, long long n, double mn, double res, long long* __restrict__ out) {
@@ -951,7 +925,7 @@ extern "C" int icpmi_grid_update_scans_box(float* log_odds, void* counts_ws, int
         // passes with counters are the cheaper way)
         if (nb1 > 0 && nb1 <= 65535 && tx * ty <= 320) {
             ray_owner_kernel<<<RO_NEAR + (int)(tx * ty) * (RT_TILE / RO_FAR) * (RT_TILE / RO_FAR), RO_THREADS, 0, st>>>(g, origins + 2 * (size_t)s1, hits + 2 * (size_t)hit_off_host[s1], nb1,
-                                                                               fin, (int)tx, (int)ty, (unsigned long long*)counts_ws);
+                                                                               fin, (int)tx, (int)ty);
             ICPMI_LAUNCH_CHECK();
             return ICPMI_OK;
         }
@@ -959,8 +933,7 @@ extern "C" int icpmi_grid_update_scans_box(float* log_odds, void* counts_ws, int
     TileArgs ta{};
     ScanBox* box_sets = (ScanBox*)((unsigned char*)counts_ws + capacity * sizeof(uint32_t) + 256);
     ta.tiles_x = (wx1 - wx0 + RT_TILE - 1) / RT_TILE; ta.tiles_y = (wy1 - wy0 + RT_TILE - 1) / RT_TILE;
-    const char* wg_env = option("RT_WGS");
-    const int rt_wgs = wg_env && atoi(wg_env) > 0 ? atoi(wg_env) : 1536;      // resident workgroups of the tile pass (6 per CU)
+    constexpr int rt_wgs = 1536;     // resident workgroups of the tile pass (6 per CU)
     bool pending = false;            // a counted group whose finalisation rides on the next launch
     int64_t q = 0;                   // index of the next group (counter-grid set q&1, box slot q%3)
     int clip_all = full_clip;

@@ -366,9 +366,6 @@ typedef float rsb_v2f __attribute__((ext_vector_type(2)));
 
 // rounds of a row's walk before the box hierarchy takes over (sweep.hpp: sweepf_nn_far): most coarse angles the bounds
 // cannot exclude put the rows decimetres to metres off, the fine grid lies about the winner
-#ifndef RSB_PK
-#define RSB_PK 1                // the rows' searches by the packed float32 walk / scan (sweep.hpp, round 4); 0: the round-3 searches
-#endif
 #ifndef RSB_COARSE_ROUNDS
 #define RSB_COARSE_ROUNDS 6
 #endif
@@ -390,11 +387,7 @@ __device__ __forceinline__ double rsb_score_angle(const double2* src_c, int n, c
             const double2 p = src_c[i];
             const double qx = (p.x * c + p.y * -s) + shx, qy = (p.x * s + p.y * c) + shy;   // src_c @ R.T + mu_t, features.py:216
             double d2;
-#if RSB_PK
             (void)sweepf_nn_far_pk(sq, sxy, tree, leaves, filt, m, dir, uabs, qx, qy, d2, walk_rounds);
-#else
-            (void)sweepf_nn_far(sq, sxy, tree, leaves, filt, m, dir, uabs, qx, qy, d2, walk_rounds);
-#endif
             const double d = sqrt(d2);                                  // KDTree distance ...
             acc += d * d;                                               // ... squared, features.py:218
         }
@@ -442,13 +435,6 @@ __global__ __launch_bounds__(RSB_THREADS, 4) void rotation_search_batch_kernel(R
     float4* sq = reinterpret_cast<float4*>(dyn + (size_t)a.cap * 32) + 1;      // one padding entry at either end
     float4* tree = reinterpret_cast<float4*>(dyn + (size_t)a.cap * 48 + 32);   // box hierarchy over blocks of 16 sorted positions (sweep.hpp: far queries)
 
-#ifdef RSB_X_TIMES          // diagnostic build: cycles per phase in the record (tools/time_prealign.py RSB_TIMES=1)
-#define RSB_T(k) tph[k] = __builtin_readcyclecounter()
-    unsigned long long tph[8];
-#else
-#define RSB_T(k)
-#endif
-    RSB_T(0);
     // ── 1. stage the pair ────────────────────────────────────────────────────
     if (tid == 0) { rt_bits = 0; rho_bits = 0; n_evals = 0; best_score = __builtin_inf(); }
     const double2* gx = a.g_sxy + a.off[tc];
@@ -490,7 +476,6 @@ __global__ __launch_bounds__(RSB_THREADS, 4) void rotation_search_batch_kernel(R
     const double2 c_lo = sxy[0], c_hi = sxy[m - 1];
     const double uabs = fmax(fabs(proj(dir, c_lo.x, c_lo.y)), fabs(proj(dir, c_hi.x, c_hi.y)));
 
-    RSB_T(1);
     // ── 2. distance field: lower bounds on the distance to the target, in the frame of the float32 images ─────
     // The rotated source lies in the disc of radius rho about mu_t; the grid covers the square around it.
     const float H = __int_as_float(rho_bits) * 1.00001f + 1e-3f;       // half side
@@ -530,7 +515,6 @@ __global__ __launch_bounds__(RSB_THREADS, 4) void rotation_search_batch_kernel(R
     }
     __syncthreads();
 
-    RSB_T(2);
     // ── 3. lower bound of every coarse score: a wave per angle, one look-up per row ──────────────
     const int n_coarse = a.n_coarse;
     if (a.prune) {
@@ -560,7 +544,6 @@ __global__ __launch_bounds__(RSB_THREADS, 4) void rotation_search_batch_kernel(R
     } else
         for (int k = tid; k < n_coarse; k += RSB_THREADS) lb[k] = -__builtin_inff();
     __syncthreads();
-    RSB_T(3);
     // ── 4. order by bound (rank by counting), then exact scores in that order ─────────────
     for (int i = tid; i < RSB_MAX_ANGLES; i += RSB_THREADS) scores[i] = __builtin_inf();      // (the field's memory: see above)
     for (int k = tid; k < n_coarse; k += RSB_THREADS) {
@@ -570,7 +553,6 @@ __global__ __launch_bounds__(RSB_THREADS, 4) void rotation_search_batch_kernel(R
         order[rank] = (short)k;
     }
     __syncthreads();
-    RSB_T(4);
     const bool prune = a.prune != 0;
     // (items are dealt to the waves round-robin — no work counter: a counter bumped by lane 0 and broadcast with
     // readfirstlane inside this loop was jump-threaded by the compiler into a per-lane loop whose other 63 lanes read item 0
@@ -594,7 +576,6 @@ __global__ __launch_bounds__(RSB_THREADS, 4) void rotation_search_batch_kernel(R
     const int coarse_evals = n_evals;
     const int nf = a.max_fine > 0 ? min(a.fine_cnt[kbest], a.max_fine) : 0;
     __syncthreads();
-    RSB_T(5);
     // ── 5. the fine grid around the winner, features.py:227-232 ───────────────
     for (int i = tid; i < RSB_MAX_ANGLES; i += RSB_THREADS) scores[i] = __builtin_inf();
     if (tid == 0) { best_score = __builtin_inf(); n_evals = 0; }
@@ -612,7 +593,6 @@ __global__ __launch_bounds__(RSB_THREADS, 4) void rotation_search_batch_kernel(R
     __syncthreads();
     first_argmin_init(sh_arg);
     const int jbest = nf > 0 ? first_argmin(scores, nf, sh_arg) : 0;
-    RSB_T(6);
     if (tid == 0) {
         for (int i = 0; i < RSB_REC_DOUBLES; ++i) rec[i] = 0.0;
         rec[RSREC_NS] = (double)n; rec[RSREC_NT] = (double)m;
@@ -621,9 +601,6 @@ __global__ __launch_bounds__(RSB_THREADS, 4) void rotation_search_batch_kernel(R
         rec[RSREC_FSCORE] = nf > 0 ? scores[jbest] : __builtin_nan("");
         rec[RSBREC_STATUS] = (double)(nf > 0 ? RSB_ST_OK : RSB_ST_NO_FINE);
         rec[RSBREC_EVALS] = (double)coarse_evals; rec[RSBREC_FEVALS] = (double)n_evals;
-#ifdef RSB_X_TIMES
-        for (int k = 0; k < 6; ++k) rec[k] = (double)(tph[k + 1] - tph[k]);      // stage, field, bounds, order, coarse, fine
-#endif
         if (init) {
             if (nf > 0) {
                 // R = [[ca, -sa], [sa, ca]], t = mu_t - R @ mu_s (features.py:235-237).  The 2 x 2 by 2 product is a BLAS

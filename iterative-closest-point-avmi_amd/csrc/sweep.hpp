@@ -130,147 +130,6 @@ struct Top2 {
     double s1, s2, s3;
 };
 
-#ifdef ICPMI_SWEEP_V1
-// `seed` >= 0 is a position whose distance seeds the top-two list (the previous
-// match).  CENTRED = true starts the walk at the query's own projection (binary
-// search) and skips the seed when the walk meets it: right after a large step the
-// previous match lies many positions away from the query's place, and walking
-// there from the seed would cost as much as an unseeded search.  CENTRED = false
-// walks outwards from the seed itself (no binary search: cheapest when the row
-// has barely moved).  Any seed and either start give the same answer.
-__device__ __forceinline__ Top2 sweep_top2(const double2* sxy, const int32_t* sorig, int m, int dir, double uabs,
-                                           double qx, double qy, int seed, bool CENTRED) {
-    const double uq = proj(dir, qx, qy);
-    Top2 t;
-    t.p1 = 0; t.p2 = -1;
-    t.s1 = t.s2 = t.s3 = __builtin_inf();
-    int r1 = 0x7fffffff, r2 = 0x7fffffff;
-    double thr = __builtin_inf();
-    int lo, hi;
-    const bool seeded = seed >= 0 && seed < m;
-    if (seeded) {
-        const double2 c = sxy[seed];
-        const double dx = qx - c.x, dy = qy - c.y;
-        double s = 0.0;
-        s += dx * dx;
-        s += dy * dy;
-        t.s1 = s; t.p1 = seed; r1 = sorig[seed];
-    }
-    if (seeded && !CENTRED) { lo = seed - 1; hi = seed + 1; }
-    else {
-        hi = sweep_lower_bound(sxy, m, dir, uq);
-        lo = hi - 1;
-    }
-    const int skip = seeded && CENTRED ? seed : -1;
-    while (lo >= 0 || hi < m) {
-#pragma unroll
-        for (int side = 0; side < 2; ++side) {
-            const bool right = side == 0;
-            if (right ? hi < m : lo >= 0) {
-                const int i = right ? hi : lo;
-                const double2 c = sxy[i];
-                const double du = right ? proj(dir, c.x, c.y) - uq : uq - proj(dir, c.x, c.y);
-                if (du > thr) { if (right) hi = m; else lo = -1; }      // everything further out is farther than the third
-                else {
-                    if (i != skip) {
-                        const double dx = qx - c.x, dy = qy - c.y;
-                        double s = 0.0;
-                        s += dx * dx;
-                        s += dy * dy;
-                        if (s <= t.s2) {                             // enters the top two (or ties with the second)
-                            const int row = sorig[i];
-                            if (s < t.s1 || (s == t.s1 && row < r1)) {
-                                t.s3 = t.s2; t.s2 = t.s1; t.p2 = t.p1; r2 = r1;
-                                t.s1 = s; t.p1 = i; r1 = row;
-                            } else if (s < t.s2 || row < r2) {
-                                t.s3 = t.s2; t.s2 = s; t.p2 = i; r2 = row;
-                            } else t.s3 = s;                         // tie with the second, lost on the row
-                            thr = prune_width(dir, t.s3, uq, uabs);
-                        } else if (s < t.s3) {
-                            t.s3 = s;
-                            thr = prune_width(dir, t.s3, uq, uabs);
-                        }
-                    }
-                    if (right) ++hi; else --lo;
-                }
-            }
-        }
-    }
-    return t;
-}
-
-// 1-NN of (qx, qy) in the sorted cloud.  Returns the sorted position; d2 is the
-// squared distance; ties go to the lowest original row (sorig).  `seed` >= 0 is a
-// position whose distance seeds the bound (the previous iteration's match); the
-// walk starts at the query's own projection (CENTRED: binary search; meeting the
-// seed again is harmless, it ties with itself) or at the seed.  Same answer for
-// any seed and either start.
-__device__ __forceinline__ int sweep_nn(const double2* sxy, const int32_t* sorig, int m, int dir, double uabs,
-                                        double qx, double qy, int seed, bool CENTRED, double& d2_out) {
-    const double uq = proj(dir, qx, qy);
-    double best = __builtin_inf(), thr = __builtin_inf();
-    int bpos = 0, brow = 0x7fffffff;
-    int lo, hi;
-    const bool seeded = seed >= 0 && seed < m;
-    if (seeded) {
-        const double2 c = sxy[seed];
-        const double dx = qx - c.x, dy = qy - c.y;
-        double s = 0.0;
-        s += dx * dx;
-        s += dy * dy;
-        best = s; bpos = seed; brow = sorig[seed];
-        thr = prune_width(dir, best, uq, uabs);
-    }
-    if (seeded && !CENTRED) { lo = seed - 1; hi = seed + 1; }
-    else {
-        hi = sweep_lower_bound(sxy, m, dir, uq);
-        lo = hi - 1;
-    }
-    while (lo >= 0 || hi < m) {
-        if (hi < m) {
-            const double2 c = sxy[hi];
-            const double du = proj(dir, c.x, c.y) - uq;
-            if (du > thr) hi = m;                               // everything further right is farther still
-            else {
-                const double dx = qx - c.x, dy = qy - c.y;
-                double s = 0.0;
-                s += dx * dx;
-                s += dy * dy;
-                if (s <= best) {
-                    const int row = sorig[hi];
-                    if (s < best || row < brow) {
-                        if (s < best) thr = prune_width(dir, s, uq, uabs);
-                        best = s; bpos = hi; brow = row;
-                    }
-                }
-                ++hi;
-            }
-        }
-        if (lo >= 0) {
-            const double2 c = sxy[lo];
-            const double du = uq - proj(dir, c.x, c.y);
-            if (du > thr) lo = -1;
-            else {
-                const double dx = qx - c.x, dy = qy - c.y;
-                double s = 0.0;
-                s += dx * dx;
-                s += dy * dy;
-                if (s <= best) {
-                    const int row = sorig[lo];
-                    if (s < best || row < brow) {
-                        if (s < best) thr = prune_width(dir, s, uq, uabs);
-                        best = s; bpos = lo; brow = row;
-                    }
-                }
-                --lo;
-            }
-        }
-    }
-    d2_out = best;
-    return bpos;
-}
-
-#else
 // ── batched, predicated walks (the searches of the fused ICP kernel) ─────────────────────────────────
 // One loop round takes ONE candidate from each open side; both are loaded before either is used and the
 // next pair is fetched while the current one is evaluated, so a round waits for LDS once instead of twice
@@ -860,14 +719,6 @@ constexpr int SWEEP_BLOCK = 16;
 #ifndef SWEEP_FAR_ROUNDS
 #define SWEEP_FAR_ROUNDS 24
 #endif
-#ifdef ICPMI_DIAG
-static __device__ unsigned long long icpmi_dbg[16];      // diagnostic build: cycles of the phases of sweepf_top2_far (per lane-call, summed)
-#define DBG_T(v) const unsigned long long v = __builtin_readcyclecounter()
-#define DBG_ADD(k, a, b) atomicAdd(&icpmi_dbg[k], (b) - (a))
-#else
-#define DBG_T(v)
-#define DBG_ADD(k, a, b)
-#endif
 
 // leaves of the tree over m points (a power of two, at least 2); the tree takes 2 * leaves entries of 16 B
 __host__ __device__ __forceinline__ int sweepf_tree_leaves(int m) {
@@ -1074,7 +925,9 @@ __device__ __forceinline__ int sweepf_nn_far_pk(const float4* sq, const double2*
     const int h0 = sweepf_lower_bound(sq, m, fq.u);
     const bool done = fq.polar ? sweep_pk_walk<3, 0, true>(sq, fq, h0 - 1, h0, m, -1, L, max_rounds)
                                : sweep_pk_walk<3, 0, false>(sq, fq, h0 - 1, h0, m, -1, L, max_rounds);
-    if (!done) {                                                       // the scan's own list (see sweepf_top2_far_pk): no word twice
+    if (!done) {
+        // a word offered twice would fill two places of the list and bound the window too tightly: so the scan keeps a
+        // list of its own — everything the walk has met within its bound is met again, the walk only lends its threshold
         SweepPkList<3> S;
         sweep_pk_far_scan<3, 0>(sq, tree, leaves, m, fq, S, fq.threshold(fq.dist_bound(L.m[0])));
         L = S;
@@ -1123,8 +976,7 @@ __device__ __forceinline__ void top2_offer(Top2& t, const float4* sq, double s, 
 #define SWEEP_FAR_ROUNDS_TOP2 3
 #endif
 __device__ __forceinline__ Top2 sweepf_top2_far(const float4* sq, const double2* sxy, const float4* tree, int leaves, const SweepF& f, int m, int dir,
-                                                double uabs, double qx, double qy, int seed, double* diag = nullptr) {
-    DBG_T(d0);
+                                                double uabs, double qx, double qy, int seed) {
     const SweepFQuery fq(f, dir, uabs, qx, qy);
     Top2 t;
     t.p1 = 0; t.p2 = -1;
@@ -1138,7 +990,6 @@ __device__ __forceinline__ Top2 sweepf_top2_far(const float4* sq, const double2*
     const int skip = seeded ? seed : -1;                               // the seed is in the list already
     int rounds = 0;
     bool far = false;
-    DBG_T(d1);
 #pragma unroll 1
     for (int pass = 0; pass < 2; ++pass) {
         while (w.more()) {
@@ -1157,47 +1008,14 @@ __device__ __forceinline__ Top2 sweepf_top2_far(const float4* sq, const double2*
         }
         if (far || !fq.polar || !w.wrap(m)) break;
     }
-    DBG_T(d2);
-    DBG_ADD(0, d0, d1); DBG_ADD(1, d1, d2); DBG_ADD(5, 0ull, 1ull);
     if (far) {
-#ifdef ICPMI_DIAG
-        if (diag) atomicAdd(diag, 4294967296.0);
-#endif
         sweepf_far_scan(sq, tree, leaves, m, fq, T, [&](int i) {
             if (i == t.p2 || (i == t.p1 && t.s1 < __builtin_inf())) return;
             top2_offer(t, sq, sweep_d2(qx, qy, sxy[i]), i, sweepf_row(sq[i]));
             fq.bounds(t.s3, W, T);
         });
-        DBG_T(d4);
-        DBG_ADD(3, d2, d4); DBG_ADD(6, 0ull, 1ull);
     }
     return t;
 }
-
-// sweepf_top2_far by the packed walk and scan (the far continuation's searches).  A word offered twice would stand for two
-// of the three nearest and bound the window by the SECOND distance: so the scan keeps a list of its own — everything
-// the walk has met within its bound is met again, the walk only lends its threshold.
-__device__ __forceinline__ Top2 sweepf_top2_far_pk(const float4* sq, const double2* sxy, const float4* tree, int leaves, const SweepF& f, int m, int dir,
-                                                   double uabs, double qx, double qy, int seed) {
-    const SweepPkQuery fq(f, dir, uabs, qx, qy);
-    SweepPkList<4> L;
-    const bool seeded = seed >= 0 && seed < m;
-    const bool from_seed = seeded && !(fq.polar && fabsf(sq[seed].z - fq.u) > 3.0f);
-    const int h0 = from_seed ? seed + 1 : sweepf_lower_bound(sq, m, fq.u);
-    const bool done = fq.polar ? sweep_pk_walk<4, 2, true>(sq, fq, h0 - 1, h0, m, -1, L, SWEEP_FAR_ROUNDS_TOP2)
-                               : sweep_pk_walk<4, 2, false>(sq, fq, h0 - 1, h0, m, -1, L, SWEEP_FAR_ROUNDS_TOP2);
-    if (!done) {
-        SweepPkList<4> S;
-        sweep_pk_far_scan<4, 2>(sq, tree, leaves, m, fq, S, fq.threshold(fq.dist_bound(L.m[2])));
-        L = S;
-    }
-    const float T = fq.threshold(fq.dist_bound(L.m[2]));
-    const bool a4 = L.m[3] != SWEEP_PK_NONE && !(sweep_pk_floor(L.m[3]) > T);
-    if (a4 || fq.bad || L.m[0] == SWEEP_PK_NONE) return sweepf_top2_far(sq, sxy, tree, leaves, f, m, dir, uabs, qx, qy, seed);
-    return sweep_pk_top2_exact(sq, sxy, qx, qy, L.m[0], L.m[1], L.m[2]);
-}
-
-#endif
-
 
 }  // namespace icpmi

@@ -18,13 +18,6 @@
 
 #include "sort.hpp"
 
-#ifndef VOX_REGS
-#define VOX_REGS 1              // 0: the round-3 path (sorted words unpacked to LDS, voxel_finish) for the usual shape too
-#endif
-#ifndef VOX_STOP_AFTER
-#define VOX_STOP_AFTER 0        // diagnostic variants only: leave the small kernel after a phase (1 bounds, 2 keys, 3 sort)
-#endif
-
 namespace icpmi {
 
 constexpr int VOX_THREADS = 1024;   // upper bound; the launcher picks 512 for large batches (loops use blockDim.x)
@@ -280,7 +273,7 @@ __global__ __launch_bounds__(VOX_THREADS) void voxel_small_kernel(
     uint64_t* keys = reinterpret_cast<uint64_t*>(dyn);
     uint32_t* rows = reinterpret_cast<uint32_t*>(dyn + (size_t)npad * sizeof(uint64_t));
 
-    if (VOX_REGS && VOX_STOP_AFTER == 0 && (npad == 4 * (int)blockDim.x || npad == 2 * (int)blockDim.x) && (blockDim.x == 512 || blockDim.x == 1024)) {
+    if ((npad == 4 * (int)blockDim.x || npad == 2 * (int)blockDim.x) && (blockDim.x == 512 || blockDim.x == 1024)) {
         uint32_t* sorted = reinterpret_cast<uint32_t*>(dyn);             // npad + 1 words
         bool done;
         if (blockDim.x == 512) {
@@ -295,9 +288,6 @@ __global__ __launch_bounds__(VOX_THREADS) void voxel_small_kernel(
     }
     double mn[3], mx[3], ext[3];
     cloud_bounds<DIM>(P, n, mn, mx, dscratch);
-#if VOX_STOP_AFTER == 1
-    if (threadIdx.x == 0) out_cnt[c] = (int)mn[0]; return;
-#endif
     if (!key_extents<DIM>(mn, mx, voxel, ext)) { if (threadIdx.x == 0) out_cnt[c] = -1; return; }
     // (key, row) sorts as ONE integer key << row_bits | row when that fits: the sort is bound by LDS traffic,
     // and a 2 048-beam scan in a room needs ~18 + 11 bits
@@ -323,14 +313,8 @@ __global__ __launch_bounds__(VOX_THREADS) void voxel_small_kernel(
                 uint32_t v[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = packed((int)threadIdx.x * 4 + e);
-#if VOX_STOP_AFTER == 2
-                if (threadIdx.x == 0) out_cnt[c] = (int)(v[0] + v[1] + v[2] + v[3]); return;
-#endif
                 if (blockDim.x == 512) bitonic_sort_regs_fixed<uint32_t, 4, 512>(v, scratch);
                 else bitonic_sort_regs_fixed<uint32_t, 4, 1024>(v, scratch);
-#if VOX_STOP_AFTER == 3
-                if (threadIdx.x == 0) out_cnt[c] = (int)(v[0] + v[1] + v[2] + v[3]); return;
-#endif
                 __syncthreads();                                            // scratch reads of the last LDS stage are done
 #pragma unroll
                 for (int e = 0; e < 4; ++e) unpack((int)threadIdx.x * 4 + e, v[e]);

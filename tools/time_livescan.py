@@ -29,17 +29,6 @@ g.reset()
 print("timed() after reset:", bench.timed(torch, lambda: g._apply(d_org, d_hits, off, box=box)) * 1e6, "us")
 print(f"per call: wall {wall / reps * 1e6:.2f} us, device (events) {e0.elapsed_time(e1) / reps * 1e3:.2f} us, host enqueue {t_host / reps * 1e6:.2f} us; box {box}")
 
-if os.environ.get("RO_TIMES"):          # diagnostic library (-DRO_X_TIMES): cycles per phase of every workgroup
-    g._ws.zero_(); torch.cuda.synchronize()
-    g._apply(d_org, d_hits, off, box=box); torch.cuda.synchronize()
-    d = g._ws[:8 * 4 * 1024].view(torch.int64).cpu().numpy().reshape(-1, 4)
-    d = d[d[:, 3] >= 2]
-    o = np.argsort(-d[:, 2])
-    print("workgroups that worked:", len(d), "slowest (select, walk, total cycles, cells+2):")
-    print(d[o[:12]])
-    print("median total", np.median(d[:, 2]), "median select", np.median(d[:, 0]), "median walk", np.median(d[:, 1]))
-    g._ws.zero_()
-
 # ... and the call slam.py:557 makes (NumPy origin and hits in), with the share of its host steps
 g.reset()
 print("host API update_scan (NumPy in):", bench.timed(torch, lambda: g.update_scan(org[0], hits[0])) * 1e6, "us per call")

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Diagnostic: time of batches made ONLY of pairs that run all 150 iterations (the limit-cycling pairs of the bench batch),
 N pairs at a time: N = 256 is one workgroup per CU, 512 two per CU, ... — what a tail iteration costs alone and shared.
-usage: [ICPMI_ICP2_SHAPE=768x2] time_tail.py N [N ...]"""
+usage: time_tail.py N [N ...]"""
 import os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "iterative-closest-point-avmi_amd"))
