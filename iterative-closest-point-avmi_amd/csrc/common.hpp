@@ -51,6 +51,26 @@ __device__ __forceinline__ bool gate_eligible(const double* search, int b) {
     return !search || search[(size_t)b * 16 + 11] < 2.0;
 }
 
+// ── carving a caller's buffer (host) ─────────────────────────────────────────
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Bump pointer over a caller's buffer.  take<T>(bytes) is the current position, and moves on by `bytes` rounded up to
+// 256; packed<T>(bytes) moves on by exactly `bytes` (the layouts that keep no gaps).  Every layout is described ONCE, by a
+// struct whose first member is a Carve and whose pointers are initialised from it, in the order they are declared (which
+// is the order of the layout).  Over a null base it only counts (every pointer is nullptr): that is the layout's *_bytes
+// query; over the caller's buffer it yields the pointers the launcher uses.
+struct Carve {
+    unsigned char* base;
+    size_t off = 0;
+    Carve(void* b) : base((unsigned char*)b) {}
+    template <class T> T* packed(size_t bytes) {
+        T* p = base ? (T*)(base + off) : nullptr;
+        off += bytes;
+        return p;
+    }
+    template <class T> T* take(size_t bytes) { return packed<T>(align256(bytes)); }
+};
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (ICPMI_WAVE - 1); }
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
 

@@ -303,12 +303,23 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_fused_kernel(IcpArgs a) {
     }
 }
 
+// workspace of the exhaustive kernel: transformed source rows | squared distances | matched rows, max_src_n of each per pair,
+// no gap between them
+struct IcpWs {
+    Carve c;
+    int32_t n_pairs, max_src_n, dim;
+    size_t rows = (size_t)n_pairs * (size_t)max_src_n;
+    double* P = c.packed<double>(rows * dim * sizeof(double));
+    double* D2 = c.packed<double>(rows * sizeof(double));
+    int32_t* Idx = c.packed<int32_t>(rows * sizeof(int32_t));
+    size_t bytes = c.off + 256;
+};
+
 }  // namespace icpmi
 
 extern "C" size_t icpmi_icp_workspace_bytes(int32_t n_pairs, int32_t max_src_n, int32_t dim) {
     if (n_pairs < 0 || max_src_n < 0 || (dim != 2 && dim != 3)) return 0;
-    const size_t rows = (size_t)n_pairs * (size_t)max_src_n;
-    return rows * dim * sizeof(double) + rows * sizeof(double) + rows * sizeof(int32_t) + 256;
+    return icpmi::IcpWs{nullptr, n_pairs, max_src_n, dim}.bytes;
 }
 
 namespace icpmi {
@@ -396,14 +407,12 @@ static int icp_batch(const double* pts, const int32_t* off_dev, const int32_t* c
                            results, prepared, workspace, workspace_bytes, gate, st);
     // (the exhaustive kernel ignores the gate: every candidate runs to its end, which the gate allows)
     if (p->method == ICPMI_POINT_TO_LINE && p->dim == 2 && !normals) return ICPMI_ERR_ARG;
-    if (!workspace || workspace_bytes < icpmi_icp_workspace_bytes(n_pairs, max_src_n, p->dim)) return ICPMI_ERR_WORKSPACE;
-    const size_t rows = (size_t)n_pairs * (size_t)max_src_n;
+    const IcpWs w{workspace, n_pairs, max_src_n, p->dim};
+    if (!workspace || workspace_bytes < w.bytes) return ICPMI_ERR_WORKSPACE;
     IcpArgs a;
     a.pts = pts; a.off = off_dev; a.cnt = cnt_dev; a.normals = normals;
     a.pair_src = pair_src; a.pair_tgt = pair_tgt; a.init = init; a.results = results;
-    a.wsP = (double*)workspace;
-    a.wsD2 = a.wsP + rows * p->dim;
-    a.wsIdx = (int32_t*)(a.wsD2 + rows);
+    a.wsP = w.P; a.wsD2 = w.D2; a.wsIdx = w.Idx;
     a.max_src_n = max_src_n;
     a.error_threshold = p->error_threshold; a.max_corr_dist = p->max_corr_dist;
     a.max_iterations = p->max_iterations; a.method = p->method; a.has_init = p->has_init;

@@ -23,6 +23,7 @@
 #include <cstdlib>
 
 #include "linalg.hpp"
+#include "prep_common.hpp"
 #include "sweep.hpp"
 
 namespace icpmi {
@@ -792,6 +793,20 @@ __global__ __launch_bounds__(ICP2_FAR_THREADS, 4) void icp2_far_kernel(Icp2Args 
     }
 }
 
+// The parked state of the stages (see Icp2Args), in the caller's workspace: transformed rows | sweep positions (max_src_n of
+// each per pair) | the three lists of pairs (second stage, wide, far) | their three counters, no gap between them.
+struct Icp2Ws {
+    Carve c;
+    int n_pairs, max_src_n;
+    size_t st_rows = (size_t)n_pairs * (size_t)max_src_n;
+    double2* st_xy = c.packed<double2>(st_rows * 16);
+    int32_t* st_pos = c.packed<int32_t>(st_rows * 4);
+    int32_t *list = c.packed<int32_t>((size_t)n_pairs * 4), *wide_list = c.packed<int32_t>((size_t)n_pairs * 4);
+    int32_t* far_list = c.packed<int32_t>((size_t)n_pairs * 4);
+    int32_t* list_count = c.packed<int32_t>(64);                   // [0 .. 2]: second stage, wide, far
+    size_t bytes = c.off;
+};
+
 // host side: called by icpmi_icp_batch (icp.hip) when a prepared buffer is given and everything fits
 int launch_icp2(const double* pts, const int32_t* off, const int32_t* cnt, const int32_t* ps, const int32_t* pt,
                 int n_pairs, int max_src_n, int max_tgt_n, int total_rows, const icpmi_icp_params* p, const double* init,
@@ -803,13 +818,9 @@ int launch_icp2(const double* pts, const int32_t* off, const int32_t* cnt, const
     a.st_xy = nullptr; a.st_pos = nullptr; a.list = nullptr; a.list_count = nullptr; a.st_stride = 0;
     a.wide_list = nullptr; a.wide_count = nullptr;
     a.far_list = nullptr; a.far_count = nullptr; a.far_d2 = __builtin_inf();
-    const unsigned char* b = (const unsigned char*)prepared;
+    const PreparedView v(prepared, total_rows);
     a.pts = pts; a.off = off; a.cnt = cnt; a.pair_src = ps; a.pair_tgt = pt; a.init = init; a.results = results;
-    a.g_sxy = (const double2*)b;
-    a.g_snrm = (const double2*)(b + (size_t)total_rows * 16);
-    a.g_sorig = (const int32_t*)(b + (size_t)total_rows * 32);
-    a.g_skey = (const float*)(b + (size_t)total_rows * 36);
-    a.g_dir = (const int32_t*)(b + (size_t)total_rows * 40);
+    a.g_sxy = v.sxy; a.g_snrm = v.snrm; a.g_sorig = v.sorig; a.g_skey = v.skey; a.g_dir = v.dir;
     a.error_threshold = p->error_threshold; a.max_corr_dist = p->max_corr_dist;
     a.max_iterations = p->max_iterations; a.method = p->method; a.has_init = p->has_init;
     const bool in_lds = max_tgt_n <= 4096;
@@ -870,11 +881,10 @@ int launch_icp2(const double* pts, const int32_t* off, const int32_t* cnt, const
     // option ICP2_STAGES = 1 keeps one launch (experiments, and the test that both give the same bits).
     constexpr int STAGE1_ITERATIONS = ICP2_STAGE1_ITERS;                   // measured 6.12 / 5.42 / 5.36 / 5.38 / 5.39 ms at 8 / 10 / 12 / 14 / 16
     const char* senv = option("ICP2_STAGES");
-    const size_t st_rows = (size_t)n_pairs * (size_t)max_src_n;
-    const size_t st_bytes = st_rows * 20 + (size_t)n_pairs * 12 + 64;
+    const Icp2Ws w{workspace, n_pairs, max_src_n};
     // point-to-line only: its pairs either settle within ~10 iterations or circle to the limit; point-to-point pairs all
     // take 25-40 and would all be parked (ICP2_STAGES = 2 forces the stages for them too: tests)
-    const bool have_ws = workspace && workspace_bytes >= st_bytes;
+    const bool have_ws = workspace && workspace_bytes >= w.bytes;
     const bool two_stage = many && have_ws && p->max_iterations >= 2 * STAGE1_ITERATIONS &&
                            !(senv && senv[0] == '1') && (p->method == ICPMI_POINT_TO_LINE || (senv && senv[0] == '2'));
     // second-stage workgroups: an eighth of the pairs, one parked pair each (about one pair in twelve is parked; the others
@@ -896,15 +906,9 @@ int launch_icp2(const double* pts, const int32_t* off, const int32_t* cnt, const
     const size_t far_lds = (size_t)far_cap * 50 + 32 + sizeof(FarSlot) * (size_t)(ICP2_FAR_THREADS * ICP2_FAR_SMAX);
     const bool far_go = far_ok && dyn_lds((const void*)icp2_far_kernel, far_lds) == hipSuccess;
     if (have_ws && (two_stage || T2 || far_go)) {
-        unsigned char* w = (unsigned char*)workspace;
-        a.st_xy = (double2*)w;
-        a.st_pos = (int32_t*)(w + st_rows * 16);
-        a.list = (int32_t*)(w + st_rows * 20);
-        a.wide_list = a.list + n_pairs;
-        a.far_list = a.wide_list + n_pairs;
-        a.list_count = a.far_list + n_pairs;
-        a.wide_count = a.list_count + 1;
-        a.far_count = a.list_count + 2;
+        a.st_xy = w.st_xy; a.st_pos = w.st_pos;
+        a.list = w.list; a.wide_list = w.wide_list; a.far_list = w.far_list;
+        a.list_count = w.list_count; a.wide_count = w.list_count + 1; a.far_count = w.list_count + 2;
         a.st_stride = max_src_n;
         if (!T2) { a.wide_list = nullptr; a.wide_count = nullptr; }
         if (far_go) a.far_d2 = far_d2;

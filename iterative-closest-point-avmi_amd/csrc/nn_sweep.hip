@@ -8,6 +8,7 @@
 // outwards until the projection gap exceeds the second-best distance.  Also
 // returns that second-best squared distance (what the fused ICP kernel uses to
 // keep matches between iterations).
+#include "prep_common.hpp"
 #include "sweep.hpp"
 
 namespace icpmi {
@@ -64,10 +65,7 @@ extern "C" int icpmi_nn_prepared_batch(const double* pts, const int32_t* off_dev
     if (n_pairs < 0 || max_src_n < 0 || max_tgt_n < 0 || out_stride < max_src_n) return ICPMI_ERR_ARG;
     if (max_tgt_n > 4096) return ICPMI_ERR_UNSUPPORTED;
     if (n_pairs == 0 || max_src_n == 0) return ICPMI_OK;
-    const unsigned char* b = (const unsigned char*)prepared;
-    const double2* g_sxy = (const double2*)b;
-    const int32_t* g_sorig = (const int32_t*)(b + (size_t)total_rows * 32);
-    const int32_t* g_dir = (const int32_t*)(b + (size_t)total_rows * 40);
+    const PreparedView v(prepared, total_rows);
     int cap = 64;
     while (cap < max_tgt_n) cap <<= 1;
     const size_t lds = (size_t)cap * 20;
@@ -76,7 +74,7 @@ extern "C" int icpmi_nn_prepared_batch(const double* pts, const int32_t* off_dev
         const int np = n_pairs - p0 < 65535 ? n_pairs - p0 : 65535;
         dim3 grid((max_src_n + NNS_THREADS - 1) / NNS_THREADS, np);
         nn_sweep_kernel<<<grid, NNS_THREADS, lds, (hipStream_t)stream>>>(
-            pts, off_dev, cnt_dev, pair_src + p0, pair_tgt + p0, g_sxy, g_sorig, g_dir, out_idx + (size_t)p0 * out_stride,
+            pts, off_dev, cnt_dev, pair_src + p0, pair_tgt + p0, v.sxy, v.sorig, v.dir, out_idx + (size_t)p0 * out_stride,
             out_dist + (size_t)p0 * out_stride, out_second_sq ? out_second_sq + (size_t)p0 * out_stride : nullptr, out_stride, cap);
         ICPMI_LAUNCH_CHECK();
     }

@@ -137,11 +137,20 @@ __global__ __launch_bounds__(NRM_THREADS) void normals_kernel(
         normals_cloud(gkeys + 2 * (size_t)off[c], grows + 2 * (size_t)off[c], npad, M, k, P, O);
 }
 
+// workspace of the clouds that do not fit in LDS: sort keys | rows (2 per point of each), no gap between them
+struct NormalsWs {
+    Carve c;
+    int32_t total_rows;
+    uint64_t* gkeys = c.packed<uint64_t>((size_t)total_rows * 2 * 8);
+    uint32_t* grows = c.packed<uint32_t>((size_t)total_rows * 2 * 4);
+    size_t bytes = c.off + 512;
+};
+
 }  // namespace icpmi
 
 extern "C" size_t icpmi_normals_workspace_bytes(int32_t total_rows, int32_t max_n) {
     if (max_n <= icpmi::NRM_LDS_MAX) return 256;
-    return 256 + (size_t)total_rows * 2 * 12 + 256;
+    return icpmi::NormalsWs{nullptr, total_rows}.bytes;
 }
 
 extern "C" int icpmi_normals_2d_batch(const double* pts, const int32_t* off_dev, const int32_t* cnt_dev,
@@ -155,16 +164,11 @@ extern "C" int icpmi_normals_2d_batch(const double* pts, const int32_t* off_dev,
     int npad = 64;
     while (npad < max_n) npad <<= 1;
     const int lds_points = npad < NRM_LDS_MAX ? npad : NRM_LDS_MAX;
-    uint64_t* gkeys = nullptr;
-    uint32_t* grows = nullptr;
-    if (npad > NRM_LDS_MAX) {
-        if (!workspace || workspace_bytes < icpmi_normals_workspace_bytes(total_rows, max_n)) return ICPMI_ERR_WORKSPACE;
-        gkeys = (uint64_t*)workspace;
-        grows = (uint32_t*)((unsigned char*)workspace + (size_t)total_rows * 2 * 8);
-    }
+    const NormalsWs w{npad > NRM_LDS_MAX ? workspace : nullptr, total_rows};
+    if (npad > NRM_LDS_MAX && (!workspace || workspace_bytes < w.bytes)) return ICPMI_ERR_WORKSPACE;
     const size_t lds = (size_t)lds_points * 12;
     if (dyn_lds((const void*)normals_kernel, lds) != hipSuccess) return ICPMI_ERR_HIP;
-    normals_kernel<<<n_sel, NRM_THREADS, lds, (hipStream_t)stream>>>(pts, off_dev, cnt_dev, cloud_ids, k, out_normals, gkeys, grows, lds_points);
+    normals_kernel<<<n_sel, NRM_THREADS, lds, (hipStream_t)stream>>>(pts, off_dev, cnt_dev, cloud_ids, k, out_normals, w.gkeys, w.grows, lds_points);
     ICPMI_LAUNCH_CHECK();
     return ICPMI_OK;
 }

@@ -490,22 +490,27 @@ static bool pg_plan(const int32_t* ij, int n, int m, PgPlan& p) {
     return true;
 }
 
-static size_t pg_align(size_t b) { return (b + 255) / 256 * 256; }
-
-static size_t pg_bytes(int n, int m, int k, int dense) {
-    const size_t N3 = 3 * (size_t)n, K = 3 * (size_t)k;
-    size_t b = 0;
-    b += pg_align((size_t)m * 2 * 4);                        // ei, ej
-    b += pg_align(((size_t)n + 1) * 4) + pg_align(((size_t)2 * m + 1) * 4) + pg_align((size_t)(m + 1) * 4) + pg_align((size_t)(k + 1) * 4);
-    b += 6 * pg_align(9 * (size_t)n * 8);                    // D U L Dinv G + b (oversized)
-    b += pg_align(N3 * (1 + K) * 8);                         // X
-    b += pg_align(18 * (size_t)(k + 1) * 8);                 // AB
-    b += pg_align((K * K + 1) * 8) + 2 * pg_align((K + 1) * 8);
-    b += pg_align(N3 * 8);                                   // dx
-    b += pg_align((size_t)(m + 1) * 8);                      // per-edge errors
-    if (dense) b += pg_align(N3 * N3 * 8);
-    return b + 256;
-}
+// the workspace: the plan's index arrays, then the arrays of PgArgs
+struct PgWs {
+    Carve c;
+    int n, m, k, dense;
+    size_t N3 = 3 * (size_t)n, K = 3 * (size_t)k, blocks = 9 * (size_t)n * 8;
+    int32_t* ei = c.take<int32_t>((size_t)m * 2 * 4);            // ei, ej
+    int32_t* ej = ei ? ei + m : nullptr;
+    int32_t* csr_ptr = c.take<int32_t>(((size_t)n + 1) * 4);
+    int32_t* csr_edge = c.take<int32_t>(((size_t)2 * m + 1) * 4);
+    int32_t* loop_slot = c.take<int32_t>((size_t)(m + 1) * 4);
+    int32_t* loop_edge = c.take<int32_t>((size_t)(k + 1) * 4);
+    double *D = c.take<double>(blocks), *U = c.take<double>(blocks), *L = c.take<double>(blocks);     // D U L Dinv G + b (oversized)
+    double *Dinv = c.take<double>(blocks), *G = c.take<double>(blocks), *b = c.take<double>(blocks);
+    double* X = c.take<double>(N3 * (1 + K) * 8);
+    double* AB = c.take<double>(18 * (size_t)(k + 1) * 8);
+    double *M = c.take<double>((K * K + 1) * 8), *g = c.take<double>((K + 1) * 8), *y = c.take<double>((K + 1) * 8);
+    double* dx = c.take<double>(N3 * 8);
+    double* edge_err = c.take<double>((size_t)(m + 1) * 8);      // per-edge errors (no kernel uses them: kept for the size)
+    double* Hd = dense ? c.take<double>(N3 * N3 * 8) : nullptr;
+    size_t bytes = c.off + 256;
+};
 
 }  // namespace icpmi
 
@@ -513,7 +518,7 @@ extern "C" size_t icpmi_pose_graph_workspace_bytes(const int32_t* edges_ij_host,
     if (n_nodes < 0 || n_edges < 0 || (n_edges > 0 && !edges_ij_host)) return 0;
     icpmi::PgPlan p;
     if (!icpmi::pg_plan(edges_ij_host, n_nodes, n_edges, p)) return 0;
-    return icpmi::pg_bytes(n_nodes, n_edges, p.k, p.dense);
+    return icpmi::PgWs{nullptr, n_nodes, n_edges, p.k, p.dense}.bytes;
 }
 
 extern "C" int icpmi_pose_graph_optimize(double* nodes, const int32_t* edges_ij_host, const double* edges_z,
@@ -533,37 +538,23 @@ extern "C" int icpmi_pose_graph_optimize(double* nodes, const int32_t* edges_ij_
     if (fix_node < 0 || fix_node >= n_nodes) return ICPMI_ERR_ARG;
     PgPlan p;
     if (!pg_plan(edges_ij_host, n_nodes, n_edges, p)) return ICPMI_ERR_ARG;
-    if (!workspace || workspace_bytes < pg_bytes(n_nodes, n_edges, p.k, p.dense)) return ICPMI_ERR_WORKSPACE;
     const int n = n_nodes, m = n_edges, k = p.k;
-    const size_t N3 = 3 * (size_t)n, K = 3 * (size_t)k;
-    unsigned char* w = (unsigned char*)workspace;
-    auto take = [&](size_t bytes) { unsigned char* r = w; w += pg_align(bytes); return r; };
-    int32_t* d_ei = (int32_t*)take((size_t)m * 2 * 4);
-    int32_t* d_ej = d_ei + m;
-    int32_t* d_ptr = (int32_t*)take(((size_t)n + 1) * 4);
-    int32_t* d_edge = (int32_t*)take(((size_t)2 * m + 1) * 4);
-    int32_t* d_slot = (int32_t*)take((size_t)(m + 1) * 4);
-    int32_t* d_loop = (int32_t*)take((size_t)(k + 1) * 4);
+    const PgWs w{workspace, n, m, k, p.dense};
+    if (!workspace || workspace_bytes < w.bytes) return ICPMI_ERR_WORKSPACE;
     PgArgs a{};
-    a.D = (double*)take(9 * (size_t)n * 8); a.U = (double*)take(9 * (size_t)n * 8); a.L = (double*)take(9 * (size_t)n * 8);
-    a.Dinv = (double*)take(9 * (size_t)n * 8); a.G = (double*)take(9 * (size_t)n * 8); a.b = (double*)take(9 * (size_t)n * 8);
-    a.X = (double*)take(N3 * (1 + K) * 8);
-    a.AB = (double*)take(18 * (size_t)(k + 1) * 8);
-    a.M = (double*)take((K * K + 1) * 8); a.g = (double*)take((K + 1) * 8); a.y = (double*)take((K + 1) * 8);
-    a.dx = (double*)take(N3 * 8);
-    take((size_t)(m + 1) * 8);
-    a.Hd = p.dense ? (double*)take(N3 * N3 * 8) : nullptr;
+    a.D = w.D; a.U = w.U; a.L = w.L; a.Dinv = w.Dinv; a.G = w.G; a.b = w.b;
+    a.X = w.X; a.AB = w.AB; a.M = w.M; a.g = w.g; a.y = w.y; a.dx = w.dx; a.Hd = w.Hd;
     std::vector<int32_t> sep(2 * (size_t)m);
     for (int q = 0; q < m; ++q) { sep[q] = edges_ij_host[2 * q]; sep[m + q] = edges_ij_host[2 * q + 1]; }
     // pageable host memory: the runtime stages these copies before returning, so the vectors may go out of scope
-    if (hipMemcpyAsync(d_ei, sep.data(), sep.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
-    if (hipMemcpyAsync(d_ptr, p.csr_ptr.data(), p.csr_ptr.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
-    if (!p.csr_edge.empty() && hipMemcpyAsync(d_edge, p.csr_edge.data(), p.csr_edge.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
-    if (hipMemcpyAsync(d_slot, p.loop_slot.data(), p.loop_slot.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
-    if (k > 0 && hipMemcpyAsync(d_loop, p.loop_edge.data(), (size_t)k * 4, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
+    if (hipMemcpyAsync(w.ei, sep.data(), sep.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
+    if (hipMemcpyAsync(w.csr_ptr, p.csr_ptr.data(), p.csr_ptr.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
+    if (!p.csr_edge.empty() && hipMemcpyAsync(w.csr_edge, p.csr_edge.data(), p.csr_edge.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
+    if (hipMemcpyAsync(w.loop_slot, p.loop_slot.data(), p.loop_slot.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
+    if (k > 0 && hipMemcpyAsync(w.loop_edge, p.loop_edge.data(), (size_t)k * 4, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
     if (hipStreamSynchronize(st) != hipSuccess) return ICPMI_ERR_HIP;        // the staging vectors die with this call
-    a.nodes = nodes; a.ei = d_ei; a.ej = d_ej; a.z = edges_z; a.omega = edges_omega;
-    a.csr_ptr = d_ptr; a.csr_edge = d_edge; a.loop_slot = d_slot; a.loop_edge = d_loop;
+    a.nodes = nodes; a.ei = w.ei; a.ej = w.ej; a.z = edges_z; a.omega = edges_omega;
+    a.csr_ptr = w.csr_ptr; a.csr_edge = w.csr_edge; a.loop_slot = w.loop_slot; a.loop_edge = w.loop_edge;
     a.n = n; a.m = m; a.k = k; a.dense = p.dense; a.n_iter = n_iterations; a.fix = fix_node; a.eps = convergence_eps;
     a.info = info;
     pose_graph_kernel<<<1, PG_THREADS, 0, st>>>(a);

@@ -310,16 +310,12 @@ int prep_big_cloud(const double* P, const int32_t* cnt_c, int n_cap, int normal_
                    int32_t* o_sorig, int32_t* dir_c, double* o_rows, void* scratch, size_t scratch_bytes, hipStream_t st);
 }
 
-// layout of a prepared-target buffer: sorted xy | sorted normals | sorted->row map | float32 bearings (bearing order) |
-// axis per cloud | scratch for
-// the sort of clouds above 4096 rows (max_n = rows of the largest cloud that will be prepared)
-static size_t prepared_core_bytes(int32_t total_rows, int32_t n_clouds) {
-    return (((size_t)total_rows * (16 + 16 + 4 + 4) + (size_t)n_clouds * 4) + 255) / 256 * 256 + 256;
-}
-
+// the buffer (PreparedView, prep_common.hpp) + the scratch for the sort of clouds above 4096 rows (max_n = rows of the
+// largest cloud that will be prepared)
 extern "C" size_t icpmi_prepared_bytes(int32_t total_rows, int32_t n_clouds, int32_t max_n) {
     if (total_rows < 0 || n_clouds < 0 || max_n < 0) return 0;
-    return prepared_core_bytes(total_rows, n_clouds) + (max_n > icpmi::PREP_MAX_POINTS ? icpmi::prep_big_scratch_bytes(max_n) : 0);
+    return icpmi::PreparedView(nullptr, total_rows, n_clouds).core_bytes +
+           (max_n > icpmi::PREP_MAX_POINTS ? icpmi::prep_big_scratch_bytes(max_n) : 0);
 }
 
 extern "C" int icpmi_prepare_targets(const double* pts, const int32_t* off_dev, const int32_t* off_host,
@@ -344,17 +340,12 @@ extern "C" int icpmi_prepare_targets_ex(const double* pts, const int32_t* off_de
     if (cloud_ids && max_n > PREP_MAX_POINTS && !cloud_ids_host) return ICPMI_ERR_ARG;
     if (n_sel == 0 || max_n == 0) return ICPMI_OK;
     hipStream_t st = (hipStream_t)stream;
-    unsigned char* b = (unsigned char*)prepared;
-    double2* g_sxy = (double2*)b;
-    double2* g_snrm = (double2*)(b + (size_t)total_rows * 16);
-    int32_t* g_sorig = (int32_t*)(b + (size_t)total_rows * 32);
-    float* g_skey = (float*)(b + (size_t)total_rows * 36);
-    int32_t* g_dir = (int32_t*)(b + (size_t)total_rows * 40);
+    const PreparedView v(prepared, total_rows, n_clouds);
     // clouds above the LDS capacity: one by one through global memory (prep_big.hip)
     int small_max = max_n;
     if (max_n > PREP_MAX_POINTS) {
-        void* scratch = b + prepared_core_bytes(total_rows, n_clouds);
-        const size_t scratch_bytes = prepared_bytes - prepared_core_bytes(total_rows, n_clouds);
+        void* scratch = (unsigned char*)prepared + v.core_bytes;
+        const size_t scratch_bytes = prepared_bytes - v.core_bytes;
         small_max = 0;
         for (int i = 0; i < n_sel; ++i) {
             const int c = cloud_ids ? cloud_ids_host[i] : i;
@@ -362,8 +353,8 @@ extern "C" int icpmi_prepare_targets_ex(const double* pts, const int32_t* off_de
             const int n = off_host[c + 1] - off_host[c];
             if (n <= PREP_MAX_POINTS) { small_max = n > small_max ? n : small_max; continue; }
             const size_t o = (size_t)off_host[c];
-            const int rc = prep_big_cloud(pts + o * 2, cnt_dev ? cnt_dev + c : nullptr, n, normal_k > 31 ? -1 : normal_k, g_sxy + o, g_snrm + o,
-                                          g_sorig + o, g_dir + c, out_normals ? out_normals + o * 2 : nullptr, scratch,
+            const int rc = prep_big_cloud(pts + o * 2, cnt_dev ? cnt_dev + c : nullptr, n, normal_k > 31 ? -1 : normal_k, v.sxy + o, v.snrm + o,
+                                          v.sorig + o, v.dir + c, out_normals ? out_normals + o * 2 : nullptr, scratch,
                                           scratch_bytes, st);
             if (rc != ICPMI_OK) return rc;
         }
@@ -400,7 +391,7 @@ extern "C" int icpmi_prepare_targets_ex(const double* pts, const int32_t* off_de
         if (dyn_lds((const void*)prep_targets_kernel<KKV, G>,                                                           \
                                 (int)lds) != hipSuccess) return ICPMI_ERR_HIP;                                          \
         prep_targets_kernel<KKV, G><<<n_sel * (KKV > 0 ? split : 1), PREP_THREADS, lds, st>>>(                          \
-            pts, off_dev, cnt_dev, cloud_ids, normal_k, g_sxy, g_snrm, g_sorig, g_skey, g_dir, out_normals, lds_points, \
+            pts, off_dev, cnt_dev, cloud_ids, normal_k, v.sxy, v.snrm, v.sorig, v.skey, v.dir, out_normals, lds_points, \
             KKV > 0 ? split : 1, polar);                                                                                \
     } while (0)
 #define ICPMI_PREP_GO(KKV)                                                                                              \
@@ -417,8 +408,8 @@ extern "C" int icpmi_prepare_targets_ex(const double* pts, const int32_t* off_de
         if (dyn_lds((const void*)normals_anyk_kernel, lds_k) != hipSuccess) return ICPMI_ERR_HIP;
         int per_cloud = 2048 / n_sel;
         per_cloud = per_cloud < 1 ? 1 : (per_cloud > 256 ? 256 : per_cloud);
-        normals_anyk_kernel<<<dim3(per_cloud, n_sel), ANYK_THREADS, lds_k, st>>>(off_dev, cnt_dev, cloud_ids, normal_k, g_sxy, g_snrm, g_sorig,
-                                                                                  g_dir, out_normals, sel_cap);
+        normals_anyk_kernel<<<dim3(per_cloud, n_sel), ANYK_THREADS, lds_k, st>>>(off_dev, cnt_dev, cloud_ids, normal_k, v.sxy, v.snrm, v.sorig,
+                                                                                  v.dir, out_normals, sel_cap);
         ICPMI_LAUNCH_CHECK();
         return ICPMI_OK;
     }

@@ -54,35 +54,30 @@ __global__ __launch_bounds__(256) void big_normals_kernel(
     prep_normals<KK>(sxy, sorig, M, s0, min(M, s0 + 256), *dir_c, kk, o_snrm, o_rows);
 }
 
-static size_t align256b(size_t x) { return (x + 255) & ~(size_t)255; }
+size_t radix_temp_bytes(int n);                              // voxel.hip: the same sort of (uint64 key, uint32 row) pairs
 
-static size_t big_radix_temp(int n) {
-    size_t bytes = 0;
-    uint64_t* k = nullptr;
-    uint32_t* v = nullptr;
-    (void)rocprim::radix_sort_pairs(nullptr, bytes, k, k, v, v, (size_t)n, 0, 64, (hipStream_t)0, false);
-    return bytes;
-}
+// scratch of one large cloud: keys, twice | rows, twice | temporary storage of the sort
+struct PrepBigWs {
+    Carve c;
+    int n;
+    uint64_t *k0 = c.take<uint64_t>((size_t)n * 8), *k1 = c.take<uint64_t>((size_t)n * 8);
+    uint32_t *r0 = c.take<uint32_t>((size_t)n * 4), *r1 = c.take<uint32_t>((size_t)n * 4);
+    size_t temp_bytes = radix_temp_bytes(n);
+    void* temp = c.take<void>(temp_bytes);
+    size_t bytes = c.off + 256;
+};
 
-size_t prep_big_scratch_bytes(int n) {
-    return 2 * align256b((size_t)n * 8) + 2 * align256b((size_t)n * 4) + align256b(big_radix_temp(n)) + 256;
-}
+size_t prep_big_scratch_bytes(int n) { return PrepBigWs{nullptr, n}.bytes; }
 
 // one cloud; P = its first row, cnt_c = its device-side row count (or null), outputs already offset to the cloud
 int prep_big_cloud(const double* P, const int32_t* cnt_c, int n_cap, int normal_k, double2* o_sxy, double2* o_snrm,
                    int32_t* o_sorig, int32_t* dir_c, double* o_rows, void* scratch, size_t scratch_bytes, hipStream_t st) {
-    if (scratch_bytes < prep_big_scratch_bytes(n_cap)) return ICPMI_ERR_WORKSPACE;
-    unsigned char* b = (unsigned char*)scratch;
-    size_t o = 0;
-    uint64_t* k0 = (uint64_t*)(b + o); o += align256b((size_t)n_cap * 8);
-    uint64_t* k1 = (uint64_t*)(b + o); o += align256b((size_t)n_cap * 8);
-    uint32_t* r0 = (uint32_t*)(b + o); o += align256b((size_t)n_cap * 4);
-    uint32_t* r1 = (uint32_t*)(b + o); o += align256b((size_t)n_cap * 4);
-    size_t tb = big_radix_temp(n_cap);
-    big_axis_keys_kernel<<<1, BIG_THREADS, 0, st>>>(P, cnt_c, n_cap, dir_c, k0, r0);
-    if (rocprim::radix_sort_pairs(b + o, tb, k0, k1, r0, r1, (size_t)n_cap, 0, 64, st, false) != hipSuccess) return ICPMI_ERR_HIP;
+    PrepBigWs w{scratch, n_cap};         // (rocprim takes the size by reference)
+    if (scratch_bytes < w.bytes) return ICPMI_ERR_WORKSPACE;
+    big_axis_keys_kernel<<<1, BIG_THREADS, 0, st>>>(P, cnt_c, n_cap, dir_c, w.k0, w.r0);
+    if (rocprim::radix_sort_pairs(w.temp, w.temp_bytes, w.k0, w.k1, w.r0, w.r1, (size_t)n_cap, 0, 64, st, false) != hipSuccess) return ICPMI_ERR_HIP;
     const int blocks = (n_cap + 255) / 256;
-    big_gather_kernel<<<blocks, 256, 0, st>>>(P, cnt_c, n_cap, r1, o_sxy, o_sorig);
+    big_gather_kernel<<<blocks, 256, 0, st>>>(P, cnt_c, n_cap, w.r1, o_sxy, o_sorig);
     if (normal_k >= 0) {
         if (normal_k + 1 <= 8) big_normals_kernel<8><<<blocks, 256, 0, st>>>(cnt_c, n_cap, dir_c, normal_k, o_sxy, o_sorig, o_snrm, o_rows);
         else if (normal_k + 1 <= 13) big_normals_kernel<13><<<blocks, 256, 0, st>>>(cnt_c, n_cap, dir_c, normal_k, o_sxy, o_sorig, o_snrm, o_rows);

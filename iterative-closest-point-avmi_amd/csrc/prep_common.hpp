@@ -6,6 +6,28 @@
 
 namespace icpmi {
 
+// A prepared-target buffer, the one statement of its format: sorted xy | sorted normals | sorted->row map | float32
+// bearing keys (bearing order) | axis per cloud, with no gaps between the arrays; `core_bytes` on, the scratch for the sort
+// of clouds above 4096 rows.  The writer (prep.hip) and every reader take their pointers from here (a reader keeps
+// them in pointers to const).
+struct PreparedView {
+    double2 *sxy, *snrm;
+    int32_t* sorig;
+    float* skey;
+    int32_t* dir;
+    size_t core_bytes;
+    PreparedView(const void* prepared, int32_t total_rows, int32_t n_clouds = 0) {   // (n_clouds: for core_bytes alone)
+        unsigned char* const b = (unsigned char*)prepared;
+        const auto at = [b](size_t o) { return b ? b + o : nullptr; };      // a null base: the size alone
+        sxy = (double2*)b;
+        snrm = (double2*)at((size_t)total_rows * 16);
+        sorig = (int32_t*)at((size_t)total_rows * 32);
+        skey = (float*)at((size_t)total_rows * 36);
+        dir = (int32_t*)at((size_t)total_rows * 40);
+        core_bytes = align256((size_t)total_rows * 40 + (size_t)n_clouds * 4) + 256;
+    }
+};
+
 constexpr int PREP_BINS = 64;
 
 // Search axis of a cloud: ranges of the four projections x, y, x+y, x-y, a 64-bin histogram per axis, and

@@ -814,6 +814,19 @@ __global__ void bresenham_cells_kernel(const int32_t* __restrict__ segs, const l
     }
 }
 
+// The counter workspace (sized below): the counters | three bounding-box slots | two sets of scan boxes, no gap but the
+// 256 bytes that hold the slots.
+struct GridWs {
+    Carve c;
+    int32_t ny, nx;
+    size_t capacity = 4 * (size_t)ny * (size_t)nx;                 // counters
+    uint32_t* counters = c.packed<uint32_t>(capacity * sizeof(uint32_t));
+    BBox* slots = c.packed<BBox>(256);                             // [3]
+    ScanBox* box_sets[2] = {c.packed<ScanBox>((size_t)RC_GROUP_MAX * RT_BOXES * sizeof(ScanBox)),     // by group parity
+                            c.packed<ScanBox>((size_t)RC_GROUP_MAX * RT_BOXES * sizeof(ScanBox))};
+    size_t bytes = c.off;
+};
+
 }  // namespace icpmi
 
 // Counter workspace: room for FOUR grids of uint32 counters (+ three bounding-box slots), whatever the group size.
@@ -824,7 +837,7 @@ __global__ void bresenham_cells_kernel(const int32_t* __restrict__ segs, const l
 // + the cell boxes of the scans of a group, two sets (tile path).
 extern "C" size_t icpmi_grid_workspace_bytes(int32_t ny, int32_t nx) {
     if (ny <= 0 || nx <= 0) return 0;
-    return 4 * (size_t)ny * (size_t)nx * sizeof(uint32_t) + 256 + 2 * (size_t)icpmi::RC_GROUP_MAX * icpmi::RT_BOXES * sizeof(icpmi::ScanBox);
+    return icpmi::GridWs{nullptr, ny, nx}.bytes;
 }
 
 extern "C" int icpmi_world_to_grid(const double* w, int64_t n, double min_w, double resolution, int64_t* out, void* stream) {
@@ -883,11 +896,10 @@ extern "C" int icpmi_grid_update_scans_box(float* log_odds, void* counts_ws, int
     const bool empty_window = wx0 >= wx1 || wy0 >= wy1;             // no cell of the band can be touched (a full clip still runs)
     if (empty_window) { wx0 = 0; wx1 = 1; wy0 = row_begin; wy1 = row_begin + 1; }
     const size_t cells = (size_t)(wx1 - wx0) * (size_t)(wy1 - wy0);                 // counters per scan
-    const size_t capacity = 4 * (size_t)ny * (size_t)nx;
-    int group_max = (int)(capacity / (2 * cells));                                  // >= 2: the window is at most the grid
+    const GridWs ws{counts_ws, ny, nx};
+    int group_max = (int)(ws.capacity / (2 * cells));                               // >= 2: the window is at most the grid
     group_max = group_max > RC_GROUP_MAX ? RC_GROUP_MAX : group_max;
-    uint32_t* set2[2] = {(uint32_t*)counts_ws, (uint32_t*)counts_ws + (size_t)group_max * cells};
-    BBox* slots = (BBox*)((unsigned char*)counts_ws + capacity * sizeof(uint32_t));
+    uint32_t* set2[2] = {ws.counters, ws.counters + (size_t)group_max * cells};
     // every call starts with empty boxes and ends with empty counter grids (each finalise pass zeroes what it
     // reads), so calls are independent of each other; scan_seq is no longer needed and ignored
     (void)scan_seq;
@@ -895,7 +907,7 @@ extern "C" int icpmi_grid_update_scans_box(float* log_odds, void* counts_ws, int
     for (int t = 0; t < n_scans; ++t) live_scans += hit_off_host[t + 1] > hit_off_host[t] ? 1 : 0;
     // one scan with a box from the caller (the live update): the finalise pass walks that box, no slot to clear first
     const bool window_is_box = live_scans == 1 && box_host && !empty_window;
-    if (!window_is_box && hipMemsetAsync(slots, 0, 3 * sizeof(BBox), st) != hipSuccess) return ICPMI_ERR_HIP;
+    if (!window_is_box && hipMemsetAsync(ws.slots, 0, 3 * sizeof(BBox), st) != hipSuccess) return ICPMI_ERR_HIP;
     GridDesc g{nx, ny, min_x, min_y, resolution, wx0, wx1, wy0, wy1, wx0, wy0, wx1 - wx0, row_begin, row_end};
     if (empty_window) { g.wx1 = g.wx0; }                              // nothing is counted; the finalise pass only clips
     FinArgs fin{};
@@ -931,7 +943,6 @@ extern "C" int icpmi_grid_update_scans_box(float* log_odds, void* counts_ws, int
         }
     }
     TileArgs ta{};
-    ScanBox* box_sets = (ScanBox*)((unsigned char*)counts_ws + capacity * sizeof(uint32_t) + 256);
     ta.tiles_x = (wx1 - wx0 + RT_TILE - 1) / RT_TILE; ta.tiles_y = (wy1 - wy0 + RT_TILE - 1) / RT_TILE;
     constexpr int rt_wgs = 1536;     // resident workgroups of the tile pass (6 per CU)
     bool pending = false;            // a counted group whose finalisation rides on the next launch
@@ -973,7 +984,7 @@ extern "C" int icpmi_grid_update_scans_box(float* log_odds, void* counts_ws, int
         if (nb0 == 0) { ++s; continue; }                        // mapping.py:113-114: silent no-op, no clip
         if (!hits) return ICPMI_ERR_ARG;
         uint32_t* counts = set2[q & 1];
-        BBox* cur = slots + (q % 3);
+        BBox* cur = ws.slots + (q % 3);
         if (nb0 <= 65535) {
             // a group: the following scans too, while they fit a 16-bit counter (empty scans are skipped over)
             int t = s;
@@ -985,7 +996,7 @@ extern "C" int icpmi_grid_update_scans_box(float* log_odds, void* counts_ws, int
             if (tiles_ok) {
                 ta.boxes = nullptr;
                 if (live_scans > 1) {                               // several scans share the window: each one's own box
-                    ScanBox* boxes = box_sets + (size_t)(q & 1) * RC_GROUP_MAX * RT_BOXES;
+                    ScanBox* boxes = ws.box_sets[q & 1];
                     if (!boxes_ready) ray_scan_boxes_kernel<<<grp.n, RT_THREADS, 0, st>>>(g, origins, hits, grp, boxes);
                     ta.boxes = boxes;
                     const int r = build_group(t, nxt, nxt_end);     // the boxes of the group after this one ride on this launch
@@ -997,11 +1008,11 @@ extern "C" int icpmi_grid_update_scans_box(float* log_odds, void* counts_ws, int
                 const int n_fin = pending ? RC_FIN_BLOCKS : 0;
                 if (!have_nxt) nxt.n = 0;
                 ray_tile_step_kernel<<<n_tiles + n_fin + nxt.n, RT_THREADS, 0, st>>>(g, origins, hits, grp, counts, cells, cur, ta, n_items, n_tiles, n_fin,
-                                                                                     fin, nxt, box_sets + (size_t)((q + 1) & 1) * RC_GROUP_MAX * RT_BOXES);
+                                                                                     fin, nxt, ws.box_sets[(q + 1) & 1]);
             } else if (pending) ray_step_kernel<<<blocks + RC_FIN_BLOCKS, RC_THREADS, 0, st>>>(g, origins, hits, grp, counts, cells, cur, blocks, fin);
             else ray_count_group_kernel<<<blocks, RC_THREADS, 0, st>>>(g, origins, hits, grp, counts, cells, cur);
             // this group's finalisation: reads its own grids and slot, frees the slot two groups ahead
-            fin.counts = counts; fin.n_grids = grp.n; fin.bbox = cur; fin.other = slots + ((q + 2) % 3);
+            fin.counts = counts; fin.n_grids = grp.n; fin.bbox = cur; fin.other = ws.slots + ((q + 2) % 3);
             fin.count_kind = 0; fin.clip = 1; fin.full_clip = clip_all;
             pending = true;
             s = t;
@@ -1017,7 +1028,7 @@ extern "C" int icpmi_grid_update_scans_box(float* log_odds, void* counts_ws, int
             w.other = nullptr; w.count_kind = 1; w.clip = 0;
             ray_finalize_kernel<<<RC_FIN_BLOCKS, RC_THREADS, 0, st>>>(g, w);
             ray_count_kernel<<<blocks, RC_THREADS, 0, st>>>(g, o, h, nb0, counts, cur, RC_DO_MISS);
-            w.other = slots + ((q + 2) % 3); w.count_kind = 2; w.clip = 1; w.full_clip = clip_all;
+            w.other = ws.slots + ((q + 2) % 3); w.count_kind = 2; w.clip = 1; w.full_clip = clip_all;
             ray_finalize_kernel<<<RC_FIN_BLOCKS, RC_THREADS, 0, st>>>(g, w);
             ++s;
         }

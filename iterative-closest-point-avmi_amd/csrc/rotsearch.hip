@@ -9,6 +9,7 @@
 // points after the coarse voxel filter), `sqrt(d2)` squared again as
 // `np.mean(dists ** 2)` does, fixed-tree workgroup sum.
 #include "nn.hpp"
+#include "prep_common.hpp"
 #include "sweep.hpp"
 
 namespace icpmi {
@@ -647,6 +648,49 @@ __global__ __launch_bounds__(RSB_MEAN_WAVES* ICPMI_WAVE) void rsb_means_kernel(c
     if (lane < 2) means[2 * c + lane] = s / (double)n;
 }
 
+// ── the workspaces of the entry points below ──
+// single search: offsets (3 int32) | counts (2 int32) | voxel-filtered copy | coarse + fine scores | voxel scratch
+// Its head, which icpmi_rotation_refine reads again: the counts 16 bytes in, the filtered copy 256 bytes in.
+struct RsHead {
+    Carve c;
+    int32_t n_src, n_tgt;
+    int32_t* off = c.take<int32_t>(256);
+    int32_t* cnt = off ? off + 4 : nullptr;
+    double* vox = c.take<double>(((size_t)n_src + n_tgt + 1) * 16);
+};
+struct RsWs : RsHead {
+    int32_t n_coarse, max_fine;
+    double* sc_coarse = c.take<double>(((size_t)n_coarse + max_fine + 1) * 8);
+    double* sc_fine = sc_coarse ? sc_coarse + n_coarse : nullptr;
+    size_t vws_bytes = icpmi_voxel_workspace_bytes(n_src > n_tgt ? n_src : n_tgt);
+    void* vws = c.take<void>(vws_bytes);
+    size_t bytes = c.off;
+};
+
+// batch search: filtered clouds | counts | means | prepared targets | voxel scratch
+struct RsbWs {
+    Carve c;
+    int32_t total_rows, n_clouds, max_n;
+    double* vox = c.take<double>((size_t)total_rows * 16);
+    int32_t* cnt = c.take<int32_t>((size_t)n_clouds * 4);
+    double* means = c.take<double>((size_t)n_clouds * 16);
+    size_t prepared_bytes = align256(icpmi_prepared_bytes(total_rows, n_clouds, max_n));
+    void* prepared = c.take<void>(prepared_bytes);
+    size_t vws_bytes = icpmi_voxel_workspace_bytes(max_n);
+    void* vws = c.take<void>(vws_bytes);
+    size_t bytes = c.off + 256;
+};
+
+// scratch of the refinement: rotated rows | squared distances | matched rows (n_src of each)
+struct RsRefineWs {
+    Carve c;
+    int32_t n_src;
+    double2* rot = c.take<double2>((size_t)n_src * 16);
+    double* dsq = c.take<double>((size_t)n_src * 8);
+    int32_t* idx = c.take<int32_t>((size_t)n_src * 4);
+    size_t bytes = c.off + 256;
+};
+
 }  // namespace icpmi
 
 extern "C" int icpmi_rotation_scores(const double* src_c, int32_t n_src, const double* tgt, int32_t n_tgt,
@@ -660,14 +704,9 @@ extern "C" int icpmi_rotation_scores(const double* src_c, int32_t n_src, const d
     return ICPMI_OK;
 }
 
-// workspace: offsets (3 int32) | counts (2 int32) | voxel-filtered copy | coarse + fine scores | voxel scratch
-static size_t rs_align(size_t x) { return (x + 255) / 256 * 256; }
-
 extern "C" size_t icpmi_rotation_search_workspace_bytes(int32_t n_src, int32_t n_tgt, int32_t n_coarse, int32_t max_fine) {
     if (n_src < 0 || n_tgt < 0 || n_coarse < 0 || max_fine < 0) return 0;
-    const int mx = n_src > n_tgt ? n_src : n_tgt;
-    return 256 + rs_align(((size_t)n_src + n_tgt + 1) * 16) + rs_align(((size_t)n_coarse + max_fine + 1) * 8) +
-           rs_align(icpmi_voxel_workspace_bytes(mx));
+    return icpmi::RsWs{{nullptr, n_src, n_tgt}, n_coarse, max_fine}.bytes;
 }
 
 extern "C" int icpmi_rotation_search(const double* pts, int32_t n_src, int32_t n_tgt, double voxel_size,
@@ -679,40 +718,28 @@ extern "C" int icpmi_rotation_search(const double* pts, int32_t n_src, int32_t n
     if (!pts || !coarse_cs || !out_record || !workspace || n_src <= 0 || n_tgt <= 0 || n_coarse <= 0 || max_fine < 0) return ICPMI_ERR_ARG;
     if (max_fine > 0 && (!fine_cs || !fine_cnt)) return ICPMI_ERR_ARG;
     if (!(voxel_size > 0.0)) return ICPMI_ERR_ARG;
-    if (workspace_bytes < icpmi_rotation_search_workspace_bytes(n_src, n_tgt, n_coarse, max_fine)) return ICPMI_ERR_WORKSPACE;
+    const RsWs w{{workspace, n_src, n_tgt}, n_coarse, max_fine};
+    if (workspace_bytes < w.bytes) return ICPMI_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    unsigned char* w = (unsigned char*)workspace;
-    int32_t* off = (int32_t*)w;
-    int32_t* cnt = off + 4;
-    double* vox = (double*)(w + 256);
-    double* sc_coarse = (double*)(w + 256 + rs_align(((size_t)n_src + n_tgt + 1) * 16));
-    double* sc_fine = sc_coarse + n_coarse;
-    void* vws = (unsigned char*)sc_coarse + rs_align(((size_t)n_coarse + max_fine + 1) * 8);
-    const int mx = n_src > n_tgt ? n_src : n_tgt;
-    rs_offsets_kernel<<<1, 1, 0, st>>>(off, n_src, n_tgt);
+    rs_offsets_kernel<<<1, 1, 0, st>>>(w.off, n_src, n_tgt);
     const int32_t off_host[3] = {0, n_src, n_src + n_tgt};                  // read before the call returns
-    int rc = icpmi_voxel_downsample_batch(pts, off, off_host, 2, 2, voxel_size, vox, cnt, vws, icpmi_voxel_workspace_bytes(mx), stream);
+    int rc = icpmi_voxel_downsample_batch(pts, w.off, off_host, 2, 2, voxel_size, w.vox, w.cnt, w.vws, w.vws_bytes, stream);
     if (rc != ICPMI_OK) return rc;
-    rs_means_kernel<<<1, 2 * ICPMI_WAVE, 0, st>>>(vox, off, cnt, centred, shift_x, shift_y, out_record);
-    rotation_scores_state_kernel<<<n_coarse, RS_THREADS, 0, st>>>(vox, off, cnt, out_record, coarse_cs, nullptr, 0, nullptr, 0, sc_coarse);
+    rs_means_kernel<<<1, 2 * ICPMI_WAVE, 0, st>>>(w.vox, w.off, w.cnt, centred, shift_x, shift_y, out_record);
+    rotation_scores_state_kernel<<<n_coarse, RS_THREADS, 0, st>>>(w.vox, w.off, w.cnt, out_record, coarse_cs, nullptr, 0, nullptr, 0, w.sc_coarse);
     if (max_fine > 0)
-        rotation_scores_state_kernel<<<max_fine, RS_THREADS, 0, st>>>(vox, off, cnt, out_record, fine_cs, fine_cnt, max_fine, sc_coarse,
-                                                                      n_coarse, sc_fine);
-    rs_finish_kernel<<<1, 64, 0, st>>>(sc_coarse, n_coarse, sc_fine, max_fine > 0 ? fine_cnt : nullptr, out_record);
+        rotation_scores_state_kernel<<<max_fine, RS_THREADS, 0, st>>>(w.vox, w.off, w.cnt, out_record, fine_cs, fine_cnt, max_fine, w.sc_coarse,
+                                                                      n_coarse, w.sc_fine);
+    rs_finish_kernel<<<1, 64, 0, st>>>(w.sc_coarse, n_coarse, w.sc_fine, max_fine > 0 ? fine_cnt : nullptr, out_record);
     ICPMI_LAUNCH_CHECK();
     return ICPMI_OK;
 }
 
 
-// workspace of the batch search: filtered clouds | counts | means | prepared targets | voxel scratch
-static size_t rsb_prepared_at(int32_t total_rows, int32_t n_clouds) {
-    return rs_align((size_t)total_rows * 16) + rs_align((size_t)n_clouds * 4) + rs_align((size_t)n_clouds * 16);
-}
 
 extern "C" size_t icpmi_rotation_search_batch_workspace_bytes(int32_t total_rows, int32_t n_clouds, int32_t max_n) {
     if (total_rows < 0 || n_clouds < 0 || max_n < 0) return 0;
-    return rsb_prepared_at(total_rows, n_clouds) + rs_align(icpmi_prepared_bytes(total_rows, n_clouds, max_n)) +
-           rs_align(icpmi_voxel_workspace_bytes(max_n)) + 256;
+    return icpmi::RsbWs{nullptr, total_rows, n_clouds, max_n}.bytes;
 }
 
 extern "C" int icpmi_rotation_search_batch(const double* pts, const int32_t* off_dev, const int32_t* off_host, int32_t n_clouds,
@@ -737,32 +764,24 @@ extern "C" int icpmi_rotation_search_batch(const double* pts, const int32_t* off
     }
     const int total_rows = off_host[n_clouds];
     if (max_n > 4096) return ICPMI_ERR_UNSUPPORTED;                      // single-pair entry (icpmi_rotation_search) for larger clouds
-    if (workspace_bytes < icpmi_rotation_search_batch_workspace_bytes(total_rows, n_clouds, max_n)) return ICPMI_ERR_WORKSPACE;
+    const RsbWs w{workspace, total_rows, n_clouds, max_n};
+    if (workspace_bytes < w.bytes) return ICPMI_ERR_WORKSPACE;
+    const PreparedView v(w.prepared, total_rows, n_clouds);
     hipStream_t st = (hipStream_t)stream;
-    unsigned char* w = (unsigned char*)workspace;
-    double* vox = (double*)w;
-    int32_t* cnt = (int32_t*)(w + rs_align((size_t)total_rows * 16));
-    double* means = (double*)((unsigned char*)cnt + rs_align((size_t)n_clouds * 4));
-    unsigned char* prepared = w + rsb_prepared_at(total_rows, n_clouds);
-    const size_t prepared_bytes = rs_align(icpmi_prepared_bytes(total_rows, n_clouds, max_n));
-    void* vws = prepared + prepared_bytes;
-    int rc = icpmi_voxel_downsample_batch(pts, off_dev, off_host, n_clouds, 2, voxel_size, vox, cnt, vws, icpmi_voxel_workspace_bytes(max_n), stream);
+    int rc = icpmi_voxel_downsample_batch(pts, off_dev, off_host, n_clouds, 2, voxel_size, w.vox, w.cnt, w.vws, w.vws_bytes, stream);
     if (rc != ICPMI_OK) return rc;
-    rsb_means_kernel<<<(n_clouds + RSB_MEAN_WAVES - 1) / RSB_MEAN_WAVES, RSB_MEAN_WAVES * ICPMI_WAVE, 0, st>>>(vox, off_dev, cnt, n_clouds, means);
+    rsb_means_kernel<<<(n_clouds + RSB_MEAN_WAVES - 1) / RSB_MEAN_WAVES, RSB_MEAN_WAVES * ICPMI_WAVE, 0, st>>>(w.vox, off_dev, w.cnt, n_clouds, w.means);
     // search order of the targets: a projection or, for scans in their sensor frame, the bearing (the library's estimate; any
     // order is exact for any query — RS_BATCH = "projection" keeps to the projections)
     const char* oe = option("RS_BATCH");
     // a pair whose target is not among tgt_ids must report "no order" (status 2), not search whatever the workspace held
-    if (hipMemsetAsync(prepared + (size_t)total_rows * 40, 0xFF, (size_t)n_clouds * sizeof(int32_t), st) != hipSuccess) return ICPMI_ERR_HIP;
-    rc = icpmi_prepare_targets_ex(vox, off_dev, off_host, cnt, tgt_ids, nullptr, tgt_ids ? n_tgt_ids : n_clouds, n_clouds, total_rows, max_n, -1,
-                                  nullptr, prepared, prepared_bytes, oe && oe[0] == 'p' ? 0 : 1, stream);
+    if (hipMemsetAsync(v.dir, 0xFF, (size_t)n_clouds * sizeof(int32_t), st) != hipSuccess) return ICPMI_ERR_HIP;
+    rc = icpmi_prepare_targets_ex(w.vox, off_dev, off_host, w.cnt, tgt_ids, nullptr, tgt_ids ? n_tgt_ids : n_clouds, n_clouds, total_rows, max_n, -1,
+                                  nullptr, w.prepared, w.prepared_bytes, oe && oe[0] == 'p' ? 0 : 1, stream);
     if (rc != ICPMI_OK) return rc;
     RsbArgs a;
-    a.vox = vox; a.off = off_dev; a.cnt = cnt; a.means = means; a.pair_src = pair_src; a.pair_tgt = pair_tgt;
-    a.g_sxy = (const double2*)prepared;
-    a.g_sorig = (const int32_t*)(prepared + (size_t)total_rows * 32);
-    a.g_skey = (const float*)(prepared + (size_t)total_rows * 36);
-    a.g_dir = (const int32_t*)(prepared + (size_t)total_rows * 40);
+    a.vox = w.vox; a.off = off_dev; a.cnt = w.cnt; a.means = w.means; a.pair_src = pair_src; a.pair_tgt = pair_tgt;
+    a.g_sxy = v.sxy; a.g_sorig = v.sorig; a.g_skey = v.skey; a.g_dir = v.dir;
     a.coarse_cs = coarse_cs; a.n_coarse = n_coarse; a.fine_cs = fine_cs; a.fine_cnt = fine_cnt; a.max_fine = max_fine;
     a.records = out_records; a.init = out_init;
     // rows the on-chip copies hold: the largest raw cloud (the filter only removes rows), at most 2 048; the caller's hint
@@ -783,10 +802,10 @@ extern "C" int icpmi_rotation_search_batch(const double* pts, const int32_t* off
 }
 
 
-// scratch of the refinement: rotated rows | squared distances | matched rows (n_src of each)
+
 extern "C" size_t icpmi_rotation_refine_workspace_bytes(int32_t n_src) {
     if (n_src < 0) return 0;
-    return rs_align((size_t)n_src * 16) + rs_align((size_t)n_src * 8) + rs_align((size_t)n_src * 4) + 256;
+    return icpmi::RsRefineWs{nullptr, n_src}.bytes;
 }
 
 extern "C" int icpmi_rotation_refine(const void* search_workspace, int32_t n_src, int32_t n_tgt, const double* record,
@@ -796,19 +815,13 @@ extern "C" int icpmi_rotation_refine(const void* search_workspace, int32_t n_src
     if (!search_workspace || !record || !coarse_cs || !out4 || !scratch || n_src <= 0 || n_tgt <= 0 || max_fine < 0) return ICPMI_ERR_ARG;
     if (max_fine > 0 && !fine_cs) return ICPMI_ERR_ARG;
     if (n_src > RSR_MAX_ROWS) return ICPMI_ERR_UNSUPPORTED;             // (raw rows: the filtered count is at most that)
-    if (scratch_bytes < icpmi_rotation_refine_workspace_bytes(n_src)) return ICPMI_ERR_WORKSPACE;
+    const RsRefineWs s{scratch, n_src};
+    if (scratch_bytes < s.bytes) return ICPMI_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const unsigned char* w = (const unsigned char*)search_workspace;
-    const int32_t* off = (const int32_t*)w;
-    const int32_t* cnt = off + 4;
-    const double* vox = (const double*)(w + 256);
-    unsigned char* s = (unsigned char*)scratch;
-    double2* rot = (double2*)s;
-    double* dsq = (double*)(s + rs_align((size_t)n_src * 16));
-    int32_t* idx = (int32_t*)((unsigned char*)dsq + rs_align((size_t)n_src * 8));
-    rs_refine_match_kernel<<<(n_src + RS_THREADS - 1) / RS_THREADS, RS_THREADS, 0, st>>>(vox, off, cnt, record, coarse_cs, fine_cs, max_fine,
-                                                                                          pred_x, pred_y, rot, dsq, idx);
-    rs_refine_finish_kernel<<<1, RSR_THREADS, 0, st>>>(vox, off, cnt, rot, dsq, idx, pred_x, pred_y, out4);
+    const RsHead w{const_cast<void*>(search_workspace), n_src, n_tgt};    // read only: the kernels take pointers to const
+    rs_refine_match_kernel<<<(n_src + RS_THREADS - 1) / RS_THREADS, RS_THREADS, 0, st>>>(w.vox, w.off, w.cnt, record, coarse_cs, fine_cs, max_fine,
+                                                                                          pred_x, pred_y, s.rot, s.dsq, s.idx);
+    rs_refine_finish_kernel<<<1, RSR_THREADS, 0, st>>>(w.vox, w.off, w.cnt, s.rot, s.dsq, s.idx, pred_x, pred_y, out4);
     ICPMI_LAUNCH_CHECK();
     return ICPMI_OK;
 }

@@ -448,9 +448,7 @@ __global__ void vox_means_kernel(const uint64_t* __restrict__ keys, const uint32
     for (int d = 0; d < DIM; ++d) O[(size_t)vid[r] * DIM + d] = s[d] / c;
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static size_t radix_temp_bytes(int n) {
+size_t radix_temp_bytes(int n) {                             // (also prep_big.hip)
     size_t bytes = 0;
     uint64_t* k = nullptr;
     uint32_t* v = nullptr;
@@ -465,33 +463,33 @@ static size_t scan_temp_bytes(int n) {
     return bytes;
 }
 
-static size_t voxel_big_bytes(int n) {
-    const size_t t1 = radix_temp_bytes(n), t2 = scan_temp_bytes(n);
-    return 256 + 2 * align256((size_t)n * 8) + 4 * align256((size_t)n * 4) + align256(t1 > t2 ? t1 : t2) + 256;
-}
+// workspace of one large cloud: bounds | keys, twice | rows, twice | voxel heads | voxel ids | temporary storage of the
+// sort and of the scan (one after the other in the same bytes)
+struct VoxBigWs {
+    Carve c;
+    int n;
+    size_t radix_bytes = radix_temp_bytes(n), scan_bytes = scan_temp_bytes(n);
+    VoxBounds* h = c.take<VoxBounds>(256);
+    uint64_t *k0 = c.take<uint64_t>((size_t)n * 8), *k1 = c.take<uint64_t>((size_t)n * 8);
+    uint32_t *r0 = c.take<uint32_t>((size_t)n * 4), *r1 = c.take<uint32_t>((size_t)n * 4);
+    uint32_t *heads = c.take<uint32_t>((size_t)n * 4), *vid = c.take<uint32_t>((size_t)n * 4);
+    void* temp = c.take<void>(radix_bytes > scan_bytes ? radix_bytes : scan_bytes);
+    size_t bytes = c.off + 256;
+};
 
 template <int DIM>
 static int voxel_big(const double* P, int n, double voxel, double* O, int32_t* out_cnt, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (ws_bytes < voxel_big_bytes(n)) return ICPMI_ERR_WORKSPACE;
-    unsigned char* base = (unsigned char*)ws;
-    size_t o = 0;
-    VoxBounds* h = (VoxBounds*)(base + o); o += 256;
-    uint64_t* k0 = (uint64_t*)(base + o); o += align256((size_t)n * 8);
-    uint64_t* k1 = (uint64_t*)(base + o); o += align256((size_t)n * 8);
-    uint32_t* r0 = (uint32_t*)(base + o); o += align256((size_t)n * 4);
-    uint32_t* r1 = (uint32_t*)(base + o); o += align256((size_t)n * 4);
-    uint32_t* heads = (uint32_t*)(base + o); o += align256((size_t)n * 4);
-    uint32_t* vid = (uint32_t*)(base + o); o += align256((size_t)n * 4);
-    size_t tb = radix_temp_bytes(n), sb = scan_temp_bytes(n);
+    VoxBigWs w{ws, n};                   // (rocprim takes the sizes by reference)
+    if (ws_bytes < w.bytes) return ICPMI_ERR_WORKSPACE;
     const int blocks = (n + 255) / 256;
-    vox_bounds_init_kernel<<<1, 64, 0, st>>>(h);
+    vox_bounds_init_kernel<<<1, 64, 0, st>>>(w.h);
     // few workgroups: every wave ends with 2*DIM atomics on the same words, and those serialise
-    vox_bounds_kernel<DIM><<<blocks < 64 ? blocks : 64, 256, 0, st>>>(P, n, h);
-    vox_keys_kernel<DIM><<<blocks, 256, 0, st>>>(P, n, voxel, h, k0, r0);
-    if (rocprim::radix_sort_pairs(base + o, tb, k0, k1, r0, r1, (size_t)n, 0, 64, st, false) != hipSuccess) return ICPMI_ERR_HIP;
-    vox_heads_kernel<<<blocks, 256, 0, st>>>(k1, n, heads);
-    if (rocprim::exclusive_scan(base + o, sb, heads, vid, 0u, (size_t)n, rocprim::plus<uint32_t>(), st, false) != hipSuccess) return ICPMI_ERR_HIP;
-    vox_means_kernel<DIM><<<blocks, 256, 0, st>>>(k1, r1, heads, vid, n, voxel, h, P, O, out_cnt);
+    vox_bounds_kernel<DIM><<<blocks < 64 ? blocks : 64, 256, 0, st>>>(P, n, w.h);
+    vox_keys_kernel<DIM><<<blocks, 256, 0, st>>>(P, n, voxel, w.h, w.k0, w.r0);
+    if (rocprim::radix_sort_pairs(w.temp, w.radix_bytes, w.k0, w.k1, w.r0, w.r1, (size_t)n, 0, 64, st, false) != hipSuccess) return ICPMI_ERR_HIP;
+    vox_heads_kernel<<<blocks, 256, 0, st>>>(w.k1, n, w.heads);
+    if (rocprim::exclusive_scan(w.temp, w.scan_bytes, w.heads, w.vid, 0u, (size_t)n, rocprim::plus<uint32_t>(), st, false) != hipSuccess) return ICPMI_ERR_HIP;
+    vox_means_kernel<DIM><<<blocks, 256, 0, st>>>(w.k1, w.r1, w.heads, w.vid, n, voxel, w.h, P, O, out_cnt);
     ICPMI_LAUNCH_CHECK();
     return ICPMI_OK;
 }
@@ -501,7 +499,7 @@ static int voxel_big(const double* P, int n, double voxel, double* O, int32_t* o
 extern "C" size_t icpmi_voxel_workspace_bytes(int32_t max_n) {
     using namespace icpmi;
     if (max_n <= VOX_SMALL_MAX) return 256;
-    return voxel_big_bytes(max_n);
+    return VoxBigWs{nullptr, max_n}.bytes;
 }
 
 extern "C" int icpmi_voxel_downsample_batch(const double* pts, const int32_t* off_dev, const int32_t* off_host,

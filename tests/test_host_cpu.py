@@ -42,6 +42,49 @@ def test_library_builds_and_exports_header_symbols():
     assert lib.icpmi_icp_workspace_bytes(2, 100, 2) == 2 * 100 * (16 + 8 + 4) + 256
     assert lib.icpmi_voxel_workspace_bytes(2048) == 256
     assert lib.icpmi_voxel_workspace_bytes(100000) > 100000 * 24
+    # every size query against literal values: a layout is described once (a struct that walks icpmi::Carve) and its size
+    # must not move when the description is edited — callers, utilities/features.py among them, index into these buffers
+    import torch
+    on_gpu = torch.cuda.is_available()
+    for name, table in SIZE_TABLE.items():
+        for args, want in table:
+            if isinstance(want, tuple):
+                want = want[1 if on_gpu else 0]
+            assert getattr(lib, name)(*args) == want, (name, args)
+    import numpy as np
+    chain = [(i, i + 1) for i in range(49)]
+    for edges, n, want in ((chain, 50, 29184),                                              # sparse plan, no loop edge
+                           (chain + [(0, 49), (10, 30), (5, 45)], 50, 40960),               # sparse plan, k = 3
+                           ([e for e in chain if e[0] != 20] + [(0, 49)], 50, 209408),      # a gap in the chain: dense plan
+                           ([(0, 7)], 5, 0), ([], 5, 8192), ([], -1, 0)):
+        ij = np.ascontiguousarray(np.array(edges, dtype=np.int32).reshape(-1, 2))
+        assert lib.icpmi_pose_graph_workspace_bytes(ij.ctypes.data if len(edges) else None, n, len(edges)) == want, (edges, n)
+    assert lib.icpmi_pose_graph_workspace_bytes(None, 5, 3) == 0
+
+
+# (arguments, bytes) of the host-only size queries; zero-sized inputs keep their fixed parts; negative ones give 0 where the
+# query checks them.  A pair of values: the layout holds rocprim's temporary storage (clouds above 8192 rows in the voxel
+# filter, above 4096 in the prepare path), whose size rocprim picks for the device it finds — (without a GPU, on gfx950).
+SIZE_TABLE = {
+    "icpmi_voxel_workspace_bytes": [((0,), 256), ((-1,), 256), ((2048,), 256), ((2049,), 256), ((4096,), 256), ((8192,), 256),
+                                    ((8193,), (264192, 362752)), ((100000,), (3201024, 4401152))],
+    "icpmi_prepared_bytes": [((0, 0, 0), 256), ((-1, 1, 1), 0), ((1, -1, 1), 0), ((1, 1, -1), 0), ((100, 1, 0), 4352),
+                             ((1000, 3, 500), 40448), ((8192, 2, 4096), 328192), ((8193, 2, 4097), (427776, 477184)),
+                             ((12000, 3, 10000), (721408, 841472))],
+    "icpmi_icp_workspace_bytes": [((2, 100, 2), 5856), ((2, 100, 3), 7456), ((7, 333, 3), 84172), ((16384, 1400, 2), 642253056),
+                                  ((0, 0, 2), 256), ((0, 100, 3), 256), ((-1, 100, 2), 0), ((2, -1, 2), 0), ((2, 100, 4), 0),
+                                  ((2, 100, 1), 0)],
+    "icpmi_normals_workspace_bytes": [((1000, 8192), 256), ((0, 0), 256), ((0, 9000), 512), ((20000, 8193), 480512),
+                                      ((100000, 20000), 2400512)],
+    "icpmi_rotation_search_workspace_bytes": [((1400, 1500, 72, 40), 48128), ((10000, 9000, 360, 64), (629504, 749568)), ((1, 1, 1, 0), 1024),
+                                              ((0, 0, 0, 0), 1024), ((-1, 10, 10, 10), 0), ((10, -1, 10, 10), 0),
+                                              ((10, 10, -1, 10), 0), ((10, 10, 10, -1), 0)],
+    "icpmi_rotation_search_batch_workspace_bytes": [((20000, 16, 2048), 1121536), ((4096, 1, 4096), 230912), ((333, 7, 100), 20224),
+                                                    ((0, 0, 0), 768), ((-1, 1, 1), 0), ((1, -1, 1), 0), ((1, 1, -1), 0)],
+    "icpmi_rotation_refine_workspace_bytes": [((1,), 1024), ((1400,), 39680), ((4096,), 114944), ((0,), 256), ((-1,), 0)],
+    "icpmi_grid_workspace_bytes": [((10, 20), 20864), ((480, 320), 2475264), ((4000, 4000), 256017664), ((0, 10), 0), ((10, 0), 0),
+                                   ((-1, 10), 0), ((10, -5), 0)],
+}
 
 
 def test_two_hip_runtimes_in_one_process_are_named():
