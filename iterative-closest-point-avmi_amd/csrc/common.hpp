@@ -51,6 +51,13 @@ __device__ __forceinline__ bool gate_eligible(const double* search, int b) {
     return !search || search[(size_t)b * 16 + 11] < 2.0;
 }
 
+// The fused 2-D ICP on prepared targets (icp2.hip), called by icpmi_icp_batch (icp.hip) when a prepared buffer is given and
+// everything fits.
+int launch_icp2(const double* pts, const int32_t* off, const int32_t* cnt, const int32_t* ps, const int32_t* pt,
+                int n_pairs, int max_src_n, int max_tgt_n, int total_rows, const icpmi_icp_params* p, const double* init,
+                double* results, const void* prepared, void* workspace, size_t workspace_bytes, const IcpGate* gate,
+                hipStream_t st);
+
 // ── carving a caller's buffer (host) ─────────────────────────────────────────
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 

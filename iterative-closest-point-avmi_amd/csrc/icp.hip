@@ -323,11 +323,6 @@ extern "C" size_t icpmi_icp_workspace_bytes(int32_t n_pairs, int32_t max_src_n, 
 }
 
 namespace icpmi {
-int launch_icp2(const double* pts, const int32_t* off, const int32_t* cnt, const int32_t* ps, const int32_t* pt,
-                int n_pairs, int max_src_n, int max_tgt_n, int total_rows, const icpmi_icp_params* p, const double* init,
-                double* results, const void* prepared, void* workspace, size_t workspace_bytes, const IcpGate* gate,
-                hipStream_t st);   // icp2.hip
-
 // The answer of icpmi_icp_batch_gated, from the records alone (not from the gate word the kernels lowered): the lowest
 // candidate index that is eligible, not skipped and below the gate, -1 when none.  Right whatever kernel ran a pair —
 // the exhaustive one here never skips — and whether or not a pair saw the gate in time.

@@ -807,57 +807,50 @@ struct Icp2Ws {
     size_t bytes = c.off;
 };
 
-// host side: called by icpmi_icp_batch (icp.hip) when a prepared buffer is given and everything fits
-int launch_icp2(const double* pts, const int32_t* off, const int32_t* cnt, const int32_t* ps, const int32_t* pt,
-                int n_pairs, int max_src_n, int max_tgt_n, int total_rows, const icpmi_icp_params* p, const double* init,
-                double* results, const void* prepared, void* workspace, size_t workspace_bytes, const IcpGate* gate,
-                hipStream_t st) {
-    Icp2Args a;
-    a.gate = gate ? *gate : IcpGate{nullptr, nullptr, 0.0, 0, 1};
-    a.it_begin = 0; a.it_limit = 0x7fffffff; a.resume = 0;
-    a.st_xy = nullptr; a.st_pos = nullptr; a.list = nullptr; a.list_count = nullptr; a.st_stride = 0;
-    a.wide_list = nullptr; a.wide_count = nullptr;
-    a.far_list = nullptr; a.far_count = nullptr; a.far_d2 = __builtin_inf();
-    const PreparedView v(prepared, total_rows);
-    a.pts = pts; a.off = off; a.cnt = cnt; a.pair_src = ps; a.pair_tgt = pt; a.init = init; a.results = results;
-    a.g_sxy = v.sxy; a.g_snrm = v.snrm; a.g_sorig = v.sorig; a.g_skey = v.skey; a.g_dir = v.dir;
-    a.error_threshold = p->error_threshold; a.max_corr_dist = p->max_corr_dist;
-    a.max_iterations = p->max_iterations; a.method = p->method; a.has_init = p->has_init;
+// ── host side ────────────────────────────────────────────────────────────────────────────────────────
+// What a call starts is decided first and as a whole (plan_icp2: a function of its arguments, no HIP call), then issued
+// (launch_icp2).
+
+// One launch: the instantiation, its LDS, and the part of the batch it takes.
+struct Icp2Shape {
+    int threads, smax;        // THREADS x ICP2_SMAX
+    bool in_lds, filter;      // TGT_LDS, FILT
+    int lds_points;           // capacity of the LDS copy (points)
+    size_t lds;               // dynamic LDS of the launch (bytes)
+    int n_lo, m_lo;           // Icp2Args: only the pairs whose source has more than n_lo rows or whose target more than m_lo
+    int skip_over;            // Icp2Args: leave the pairs this shape cannot hold to the launch for wide clouds
+};
+struct Icp2Plan {
+    Icp2Shape first;          // every pair of the batch (but the ones it leaves to `wide`)
+    bool has_wide;            // a launch for the pairs the first shape cannot hold
+    Icp2Shape wide;
+    bool two_stage;           // `first` stops after stage1_iterations and a second stage continues the parked pairs
+    int stage1_iterations, stage2_grid, wide_grid;
+    bool far_wanted;          // the far continuation may run (if the device grants its LDS)
+    Icp2Shape far;
+    double far_d2;
+    bool needs_lists;         // the parked state and the lists of the workspace are used (whether or not `far` runs)
+};
+constexpr int ICP2_NO_LIMIT = 0x7fffffff;               // it_limit of a launch that runs a pair to its end
+
+// `points` target points at most in LDS (when the targets are staged there at all), for `threads` x `smax` source rows
+static Icp2Shape icp2_shape(int threads, int smax, int points, bool in_lds) {
+    int cap = 64;
+    while (cap < points) cap <<= 1;
+    if (points > 1024 && points <= 1536) cap = 1536;
+    // The filter needs <= 2 048 points (96 KB, one workgroup per CU).
+    const bool filter = in_lds && cap <= 2048;
+    // LDS copy of the target: 36 B per point, 48 B with the float32 images of the filter.
+    const size_t lds = in_lds ? (filter ? (size_t)cap * 48 + 32 : (size_t)cap * 36) : 0;
+    return {threads, smax, in_lds, filter, cap, lds, -1, 0, 0};
+}
+
+// stages_opt, far_opt: the options ICP2_STAGES and ICP2_FAR (nullptr: not set); have_ws: the caller gave a workspace that
+// holds the parked state (Icp2Ws)
+static Icp2Plan plan_icp2(int n_pairs, int max_src_n, int max_tgt_n, const icpmi_icp_params& p, bool have_ws,
+                          const char* stages_opt, const char* far_opt) {
+    Icp2Plan plan{};
     const bool in_lds = max_tgt_n <= 4096;
-#define ICPMI_ICP2_GO(TT, SS)                                                                                                    \
-    do {                                                                                                                         \
-        if (!in_lds) ICPMI_ICP2_GO2(TT, SS, false, false);                                                                      \
-        else if (filter) ICPMI_ICP2_GO2(TT, SS, true, true);                                                                    \
-        else ICPMI_ICP2_GO2(TT, SS, true, false);                                                                               \
-    } while (0)
-#define ICPMI_ICP2_GO2(TT, SS, L, F)                                                                                             \
-    do {                                                                                                                         \
-        if (dyn_lds((const void*)icp2_fused_kernel<TT, SS, L, F>, lds) != hipSuccess) return ICPMI_ERR_HIP;                      \
-        if (pass == 1 && a.wide_list) {                     /* the listed pairs: few workgroups walking the list */              \
-            if (dyn_lds((const void*)icp2_wide_kernel<TT, SS, L, F>, lds) != hipSuccess) return ICPMI_ERR_HIP;                   \
-            hipStream_t ws = st;                            /* beside the second stage when the side stream is there */          \
-            if (forked && hipStreamWaitEvent(side->stream[0], side->fork, 0) == hipSuccess) ws = side->stream[0];                 \
-            icp2_wide_kernel<TT, SS, L, F><<<wide_grid, TT, lds, ws>>>(a);                                                       \
-            if (ws != st && (hipEventRecord(side->join[0], ws) != hipSuccess ||                                                  \
-                             hipStreamWaitEvent(st, side->join[0], 0) != hipSuccess)) {                                          \
-                (void)hipStreamSynchronize(ws);             /* never return with a launch the caller cannot order against */     \
-                return ICPMI_ERR_HIP;                                                                                            \
-            }                                                                                                                    \
-        } else icp2_fused_kernel<TT, SS, L, F><<<n_pairs, TT, lds, st>>>(a);                                                      \
-        if (two_stage && pass == 0 && a.wide_list && side) forked = hipEventRecord(side->fork, st) == hipSuccess;                \
-        if (two_stage && pass == 0) {                       /* the parked pairs, all started together */                         \
-            Icp2Args c = a;                                                                                                      \
-            c.resume = 1; c.it_begin = a.it_limit; c.it_limit = 0x7fffffff;                                                      \
-            if (dyn_lds((const void*)icp2_resume_kernel<TT, SS, L, F>, lds) != hipSuccess) return ICPMI_ERR_HIP;                 \
-            icp2_resume_kernel<TT, SS, L, F><<<stage2_grid, TT, lds, st>>>(c);                                                   \
-            if (stage2_grid < n_pairs) {                    /* more parked pairs than workgroups: the rest of the list */         \
-                if (dyn_lds((const void*)icp2_resume_rest_kernel<TT, SS, L, F>, lds) != hipSuccess) return ICPMI_ERR_HIP;        \
-                icp2_resume_rest_kernel<TT, SS, L, F><<<256, TT, lds, st>>>(c, stage2_grid);                                     \
-            }                                                                                                                    \
-        }                                                                                                                        \
-    } while (0)
-    a.n_lo = -1; a.m_lo = 0; a.skip_over = 0;
-    int T2 = 0, SM2 = 0;                // second launch for the pairs the first shape cannot hold
     const bool many = n_pairs >= 1024;
     // Workgroup shape by source size (rows per thread bounded by the instantiation).
     // A voxel-filtered 2 048-beam scan keeps ~1 400 rows: 768 threads x 2 rows, two workgroups per CU (6 waves per
@@ -869,84 +862,157 @@ int launch_icp2(const double* pts, const int32_t* off, const int32_t* cnt, const
     else if (many) { T = 768; SM = 2; }
     else if (max_src_n <= 2048) { T = 1024; SM = 2; }
     else { T = 1024; SM = 4; }
-    // LDS copy of the target: 36 B per point, 48 B with the float32 images of the filter.  Two workgroups of the
-    // 512-thread shapes share a CU only up to 1 536 filter points (2 x 73.7 KB): larger targets, like larger
-    // sources, are left to the second launch.  The filter needs <= 2 048 points (96 KB, one workgroup per CU).
-    int cap1 = ((T == 512 || T == 768) && many && in_lds && max_tgt_n > 1536) ? 1536 : max_tgt_n;
-    if (T * SM < max_src_n || cap1 < max_tgt_n) { T2 = 1024; SM2 = max_src_n <= 2048 ? 2 : 4; a.skip_over = 1; }
+    // Two workgroups of the 512-thread shapes share a CU only up to 1 536 filter points (2 x 73.7 KB): larger targets,
+    // like larger sources, are left to the second launch.
+    const int cap1 = ((T == 512 || T == 768) && many && in_lds && max_tgt_n > 1536) ? 1536 : max_tgt_n;
+    plan.first = icp2_shape(T, SM, cap1, in_lds);
+    // second launch for the pairs the first shape cannot hold
+    plan.has_wide = T * SM < max_src_n || cap1 < max_tgt_n;
+    if (plan.has_wide) {
+        plan.first.skip_over = 1;
+        plan.wide = icp2_shape(1024, max_src_n <= 2048 ? 2 : 4, max_tgt_n, in_lds);
+        plan.wide.n_lo = T * SM; plan.wide.m_lo = cap1;
+    }
     // Two stages for a large batch (see Icp2Args): needs the caller's workspace for the parked state.  Below ~1 000 pairs
     // every long pair starts within the first two rounds anyway and the stages only add their own cost (512 pairs: 0.70
     // against 0.65 ms).  About one pair
     // in thirteen of a loop-closure batch runs to the iteration limit; 12 iterations settle the others.
     // option ICP2_STAGES = 1 keeps one launch (experiments, and the test that both give the same bits).
-    constexpr int STAGE1_ITERATIONS = ICP2_STAGE1_ITERS;                   // measured 6.12 / 5.42 / 5.36 / 5.38 / 5.39 ms at 8 / 10 / 12 / 14 / 16
-    const char* senv = option("ICP2_STAGES");
-    const Icp2Ws w{workspace, n_pairs, max_src_n};
+    plan.stage1_iterations = ICP2_STAGE1_ITERS;                            // measured 6.12 / 5.42 / 5.36 / 5.38 / 5.39 ms at 8 / 10 / 12 / 14 / 16
     // point-to-line only: its pairs either settle within ~10 iterations or circle to the limit; point-to-point pairs all
     // take 25-40 and would all be parked (ICP2_STAGES = 2 forces the stages for them too: tests)
-    const bool have_ws = workspace && workspace_bytes >= w.bytes;
-    const bool two_stage = many && have_ws && p->max_iterations >= 2 * STAGE1_ITERATIONS &&
-                           !(senv && senv[0] == '1') && (p->method == ICPMI_POINT_TO_LINE || (senv && senv[0] == '2'));
+    plan.two_stage = many && have_ws && p.max_iterations >= 2 * plan.stage1_iterations &&
+                     !(stages_opt && stages_opt[0] == '1') &&
+                     (p.method == ICPMI_POINT_TO_LINE || (stages_opt && stages_opt[0] == '2'));
     // second-stage workgroups: an eighth of the pairs, one parked pair each (about one pair in twelve is parked; the others
     // leave at once), then 256 workgroups that walk whatever the list holds beyond that
-    const int stage2_grid = n_pairs / 8 > 256 ? n_pairs / 8 : 256;
+    plan.stage2_grid = n_pairs / 8 > 256 ? n_pairs / 8 : 256;
     // the launch for wide clouds: a thirty-second (a launch of 4 096 workgroups that find an empty list still takes 100 us)
-    const int wide_grid = n_pairs < 256 ? n_pairs : (n_pairs / 32 > 256 ? n_pairs / 32 : 256);
+    plan.wide_grid = n_pairs < 256 ? n_pairs : (n_pairs / 32 > 256 ? n_pairs / 32 : 256);
     // option ICP2_FAR = the mean squared error (m^2) of the first step above which a pair goes to the far continuation
     // (default 1: one metre rms — the candidates ICP converges from by itself stay below it: with 0.5 some of them are
     // sent over and the 16 384-pair batch takes 5.7 instead of 5.05 ms; 0 = never)
-    double far_d2 = 1.0;
-    if (const char* e = option("ICP2_FAR")) far_d2 = atof(e);
-    const bool far_ok = have_ws && in_lds && far_d2 > 0.0 && p->max_iterations > 2;
+    plan.far_d2 = far_opt ? atof(far_opt) : 1.0;
+    plan.far_wanted = have_ws && in_lds && plan.far_d2 > 0.0 && p.max_iterations > 2;
     // the far continuation's LDS: the filter layout + the box hierarchy (2 B per point at most) + a slot per row of its shape
-    // (every wave owns the stretch behind its own lanes, whatever the batch's source sizes).  Asked for BEFORE the first
-    // launch: without it (another ARCH than gfx950's 160 KB) no pair is parked for a kernel that could not start.
+    // (every wave owns the stretch behind its own lanes, whatever the batch's source sizes).
     int far_cap = 64;
     while (far_cap < max_tgt_n && far_cap < ICP2_FAR_POINTS) far_cap <<= 1;
-    const size_t far_lds = (size_t)far_cap * 50 + 32 + sizeof(FarSlot) * (size_t)(ICP2_FAR_THREADS * ICP2_FAR_SMAX);
-    const bool far_go = far_ok && dyn_lds((const void*)icp2_far_kernel, far_lds) == hipSuccess;
-    if (have_ws && (two_stage || T2 || far_go)) {
-        a.st_xy = w.st_xy; a.st_pos = w.st_pos;
-        a.list = w.list; a.wide_list = w.wide_list; a.far_list = w.far_list;
-        a.list_count = w.list_count; a.wide_count = w.list_count + 1; a.far_count = w.list_count + 2;
-        a.st_stride = max_src_n;
-        if (!T2) { a.wide_list = nullptr; a.wide_count = nullptr; }
-        if (far_go) a.far_d2 = far_d2;
-        else { a.far_list = nullptr; a.far_count = nullptr; }
-        if (hipMemsetAsync(a.list_count, 0, 3 * sizeof(int32_t), st) != hipSuccess) return ICPMI_ERR_HIP;
+    plan.far = {ICP2_FAR_THREADS, ICP2_FAR_SMAX, true, true, far_cap,
+                (size_t)far_cap * 50 + 32 + sizeof(FarSlot) * (size_t)(ICP2_FAR_THREADS * ICP2_FAR_SMAX), -1, 0, 0};
+    plan.needs_lists = have_ws && (plan.two_stage || plan.has_wide);
+    return plan;
+}
+
+// The four kernels of a shape.
+struct Icp2Kernels {
+    void (*fused)(Icp2Args);
+    void (*wide)(Icp2Args);
+    void (*resume)(Icp2Args);
+    void (*resume_rest)(Icp2Args, int);
+};
+template <int T, int S, bool L, bool F>
+constexpr Icp2Kernels icp2_kernels() {
+    return {icp2_fused_kernel<T, S, L, F>, icp2_wide_kernel<T, S, L, F>, icp2_resume_kernel<T, S, L, F>,
+            icp2_resume_rest_kernel<T, S, L, F>};
+}
+template <int T, int S>
+static Icp2Kernels icp2_kernels_of(const Icp2Shape& s) {
+    if (!s.in_lds) return icp2_kernels<T, S, false, false>();
+    if (s.filter) return icp2_kernels<T, S, true, true>();
+    return icp2_kernels<T, S, true, false>();
+}
+// every instantiation there is; fused == nullptr: none for this shape
+static Icp2Kernels icp2_kernels_of(const Icp2Shape& s) {
+    if (s.threads == 512 && s.smax == 2) return icp2_kernels_of<512, 2>(s);
+    if (s.threads == 768 && s.smax == 2) return icp2_kernels_of<768, 2>(s);
+    if (s.threads == 1024 && s.smax == 2) return icp2_kernels_of<1024, 2>(s);
+    if (s.threads == 1024 && s.smax == 4) return icp2_kernels_of<1024, 4>(s);
+    return {nullptr, nullptr, nullptr, nullptr};
+}
+
+// the arguments of one launch: the shape's part of the batch and LDS capacity, iterations [it_begin, it_limit)
+static Icp2Args icp2_args(const Icp2Args& base, const Icp2Shape& s, int it_begin, int it_limit, int resume) {
+    Icp2Args a = base;
+    a.lds_points = s.lds_points; a.n_lo = s.n_lo; a.m_lo = s.m_lo; a.skip_over = s.skip_over;
+    a.it_begin = it_begin; a.it_limit = it_limit; a.resume = resume;
+    return a;
+}
+
+// called by icpmi_icp_batch (icp.hip) when a prepared buffer is given and everything fits
+int launch_icp2(const double* pts, const int32_t* off, const int32_t* cnt, const int32_t* ps, const int32_t* pt,
+                int n_pairs, int max_src_n, int max_tgt_n, int total_rows, const icpmi_icp_params* p, const double* init,
+                double* results, const void* prepared, void* workspace, size_t workspace_bytes, const IcpGate* gate,
+                hipStream_t st) {
+    const Icp2Ws w{workspace, n_pairs, max_src_n};
+    const bool have_ws = workspace && workspace_bytes >= w.bytes;
+    const Icp2Plan plan = plan_icp2(n_pairs, max_src_n, max_tgt_n, *p, have_ws, option("ICP2_STAGES"), option("ICP2_FAR"));
+    const Icp2Kernels k1 = icp2_kernels_of(plan.first), k2 = icp2_kernels_of(plan.wide);
+    if (!k1.fused || (plan.has_wide && !k2.fused)) return ICPMI_ERR_ARG;
+    Icp2Args base;
+    base.gate = gate ? *gate : IcpGate{nullptr, nullptr, 0.0, 0, 1};
+    base.st_xy = nullptr; base.st_pos = nullptr; base.list = nullptr; base.list_count = nullptr; base.st_stride = 0;
+    base.wide_list = nullptr; base.wide_count = nullptr;
+    base.far_list = nullptr; base.far_count = nullptr; base.far_d2 = __builtin_inf();
+    const PreparedView v(prepared, total_rows);
+    base.pts = pts; base.off = off; base.cnt = cnt; base.pair_src = ps; base.pair_tgt = pt; base.init = init; base.results = results;
+    base.g_sxy = v.sxy; base.g_snrm = v.snrm; base.g_sorig = v.sorig; base.g_skey = v.skey; base.g_dir = v.dir;
+    base.error_threshold = p->error_threshold; base.max_corr_dist = p->max_corr_dist;
+    base.max_iterations = p->max_iterations; base.method = p->method; base.has_init = p->has_init;
+    // The far continuation's LDS is asked for BEFORE the first launch: without it (another ARCH than gfx950's 160 KB) no
+    // pair is parked for a kernel that could not start.
+    const bool far_go = plan.far_wanted && dyn_lds((const void*)icp2_far_kernel, plan.far.lds) == hipSuccess;
+    if (plan.needs_lists || far_go) {
+        base.st_xy = w.st_xy; base.st_pos = w.st_pos; base.st_stride = max_src_n;
+        base.list = w.list; base.list_count = w.list_count;
+        if (plan.has_wide) { base.wide_list = w.wide_list; base.wide_count = w.list_count + 1; }
+        if (far_go) { base.far_list = w.far_list; base.far_count = w.list_count + 2; base.far_d2 = plan.far_d2; }
+        if (hipMemsetAsync(w.list_count, 0, 3 * sizeof(int32_t), st) != hipSuccess) return ICPMI_ERR_HIP;
     }
-    // The launch for wide clouds (a handful of pairs, ~0.1 ms at a few per cent of the chip) only needs the first stage's
-    // list: it runs on a side stream beside the second stage and joins the caller's stream afterwards.
     // (state.hip: the library's side streams, one set per device; the lock is held for the fork / launch / join sequence)
     SideLock side_lock;
     Side* const side = side_lock.side;
+
+    // first launch: every pair, to its end or (two stages) to the end of the first stage
+    const Icp2Shape& s1 = plan.first;
+    if (dyn_lds((const void*)k1.fused, s1.lds) != hipSuccess) return ICPMI_ERR_HIP;
+    k1.fused<<<n_pairs, s1.threads, s1.lds, st>>>(
+        icp2_args(base, s1, 0, plan.two_stage ? plan.stage1_iterations : ICP2_NO_LIMIT, 0));
     bool forked = false;
-    for (int pass = 0; pass < 2; ++pass) {
-        a.it_limit = two_stage && pass == 0 ? STAGE1_ITERATIONS : 0x7fffffff;
-        if (pass == 1) {
-            if (!T2) break;
-            a.n_lo = T * SM; a.m_lo = cap1; a.skip_over = 0; T = T2; SM = SM2; cap1 = max_tgt_n;
+    if (plan.two_stage) {
+        // The launch for wide clouds (a handful of pairs, ~0.1 ms at a few per cent of the chip) only needs the first stage's
+        // list: it runs on a side stream beside the second stage and joins the caller's stream afterwards.
+        if (base.wide_list && side) forked = hipEventRecord(side->fork, st) == hipSuccess;
+        // second stage: the parked pairs, all started together
+        const Icp2Args second = icp2_args(base, s1, plan.stage1_iterations, ICP2_NO_LIMIT, 1);
+        if (dyn_lds((const void*)k1.resume, s1.lds) != hipSuccess) return ICPMI_ERR_HIP;
+        k1.resume<<<plan.stage2_grid, s1.threads, s1.lds, st>>>(second);
+        if (plan.stage2_grid < n_pairs) {                   // more parked pairs than workgroups: the rest of the list
+            if (dyn_lds((const void*)k1.resume_rest, s1.lds) != hipSuccess) return ICPMI_ERR_HIP;
+            k1.resume_rest<<<256, s1.threads, s1.lds, st>>>(second, plan.stage2_grid);
         }
-        int cap = 64;
-        while (cap < cap1) cap <<= 1;
-        if (cap1 > 1024 && cap1 <= 1536) cap = 1536;
-        a.lds_points = cap;
-        const bool filter = in_lds && cap <= 2048;
-        const size_t lds = in_lds ? (filter ? (size_t)cap * 48 + 32 : (size_t)cap * 36) : 0;
-        if (T == 512 && SM == 2) ICPMI_ICP2_GO(512, 2);
-        else if (T == 768 && SM == 2) ICPMI_ICP2_GO(768, 2);
-        else if (T == 1024 && SM == 2) ICPMI_ICP2_GO(1024, 2);
-        else if (T == 1024 && SM == 4) ICPMI_ICP2_GO(1024, 4);
-        else return ICPMI_ERR_ARG;
     }
-#undef ICPMI_ICP2_GO
-#undef ICPMI_ICP2_GO2
-    if (a.far_list) {                                       // after every first launch (the wide one has joined the stream)
-        Icp2Args c = a;
-        c.resume = 1; c.it_begin = 2; c.it_limit = 0x7fffffff; c.skip_over = 0; c.n_lo = -1; c.m_lo = 0;
-        c.lds_points = far_cap;
-        icp2_far_kernel<<<n_pairs < 256 ? n_pairs : 256, ICP2_FAR_THREADS, far_lds, st>>>(c);
+    if (plan.has_wide) {
+        const Icp2Shape& s2 = plan.wide;
+        const Icp2Args wide = icp2_args(base, s2, 0, ICP2_NO_LIMIT, 0);
+        if (base.wide_list) {                               // the listed pairs: few workgroups walking the list
+            if (dyn_lds((const void*)k2.wide, s2.lds) != hipSuccess) return ICPMI_ERR_HIP;
+            hipStream_t ws = st;                            // beside the second stage when the side stream is there
+            if (forked && hipStreamWaitEvent(side->stream[0], side->fork, 0) == hipSuccess) ws = side->stream[0];
+            k2.wide<<<plan.wide_grid, s2.threads, s2.lds, ws>>>(wide);
+            if (ws != st && (hipEventRecord(side->join[0], ws) != hipSuccess ||
+                             hipStreamWaitEvent(st, side->join[0], 0) != hipSuccess)) {
+                (void)hipStreamSynchronize(ws);             // never return with a launch the caller cannot order against
+                return ICPMI_ERR_HIP;
+            }
+        } else {                                            // no workspace, no list: a workgroup per pair of the batch looks
+            if (dyn_lds((const void*)k2.fused, s2.lds) != hipSuccess) return ICPMI_ERR_HIP;
+            k2.fused<<<n_pairs, s2.threads, s2.lds, st>>>(wide);
+        }
     }
+    if (base.far_list)                                      // after every first launch (the wide one has joined the stream)
+        icp2_far_kernel<<<n_pairs < 256 ? n_pairs : 256, plan.far.threads, plan.far.lds, st>>>(
+            icp2_args(base, plan.far, 2, ICP2_NO_LIMIT, 1));
     ICPMI_LAUNCH_CHECK();
     return ICPMI_OK;
 }

@@ -302,13 +302,33 @@ __global__ __launch_bounds__(ANYK_THREADS) void normals_anyk_kernel(
     }
 }
 
-}  // namespace icpmi
-
-namespace icpmi {
-size_t prep_big_scratch_bytes(int n);                                                                  // prep_big.hip
-int prep_big_cloud(const double* P, const int32_t* cnt_c, int n_cap, int normal_k, double2* o_sxy, double2* o_snrm,
-                   int32_t* o_sorig, int32_t* dir_c, double* o_rows, void* scratch, size_t scratch_bytes, hipStream_t st);
+// The instantiation of prep_targets_kernel for normals from `normal_k` neighbours, and its list capacity kk.
+using PrepKernel = void (*)(const double*, const int32_t*, const int32_t*, const int32_t*, int, double2*, double2*, int32_t*,
+                            float*, int32_t*, double*, int, int, int);
+struct PrepChoice {
+    PrepKernel kernel;
+    int kk;                   // 0: sort only
+    bool grid;
+};
+template <int KK>
+static PrepChoice prep_choice_of(bool use_grid) {
+    if (use_grid && KK > 0) return {prep_targets_kernel<KK, true>, KK, true};       // the grid serves the k-NN search alone
+    return {prep_targets_kernel<KK, false>, KK, false};
 }
+static PrepChoice prep_choice(int normal_k, bool use_grid) {
+    // beyond 31 neighbours: sort only, then the any-k kernel on the sorted copy
+    if (normal_k > 31) return {prep_targets_kernel<0, false>, 0, false};
+    // list capacity = k + 1 exactly for the usual k (5, 10 = reference default, 12 = config.yaml), else the next size up
+    if (normal_k < 0) return prep_choice_of<0>(use_grid);
+    if (normal_k + 1 <= 6) return prep_choice_of<6>(use_grid);
+    if (normal_k + 1 <= 8) return prep_choice_of<8>(use_grid);
+    if (normal_k + 1 <= 11) return prep_choice_of<11>(use_grid);
+    if (normal_k + 1 <= 13) return prep_choice_of<13>(use_grid);
+    if (normal_k + 1 <= 16) return prep_choice_of<16>(use_grid);
+    return prep_choice_of<32>(use_grid);
+}
+
+}  // namespace icpmi
 
 // the buffer (PreparedView, prep_common.hpp) + the scratch for the sort of clouds above 4096 rows (max_n = rows of the
 // largest cloud that will be prepared)
@@ -385,21 +405,15 @@ extern "C" int icpmi_prepare_targets_ex(const double* pts, const int32_t* off_de
     // (tests run both on the same inputs)
     int use_grid = split > 1 && !polar;
     if (const char* env = option("PREP_KNN")) use_grid = env[0] == 'g' ? 1 : (env[0] == 's' ? 0 : use_grid);
-#define ICPMI_PREP_GO2(KKV, G)                                                                                          \
-    do {                                                                                                                \
-        const size_t lds = G ? lds_sep : lds_alias;                                                                     \
-        if (dyn_lds((const void*)prep_targets_kernel<KKV, G>,                                                           \
-                                (int)lds) != hipSuccess) return ICPMI_ERR_HIP;                                          \
-        prep_targets_kernel<KKV, G><<<n_sel * (KKV > 0 ? split : 1), PREP_THREADS, lds, st>>>(                          \
-            pts, off_dev, cnt_dev, cloud_ids, normal_k, v.sxy, v.snrm, v.sorig, v.skey, v.dir, out_normals, lds_points, \
-            KKV > 0 ? split : 1, polar);                                                                                \
-    } while (0)
-#define ICPMI_PREP_GO(KKV)                                                                                              \
-    do { if (use_grid && KKV > 0) ICPMI_PREP_GO2(KKV, true); else ICPMI_PREP_GO2(KKV, false); } while (0)
-    // list capacity = k + 1 exactly for the usual k (5, 10 = reference default, 12 = config.yaml), else the next size up;
-    // beyond 31 neighbours: sort only, then the any-k kernel on the sorted copy
+    const PrepChoice pc = prep_choice(normal_k, use_grid);
+    if (small_max > 0) {
+        const size_t lds = pc.grid ? lds_sep : lds_alias;
+        const int parts = pc.kk > 0 ? split : 1;
+        if (dyn_lds((const void*)pc.kernel, lds) != hipSuccess) return ICPMI_ERR_HIP;
+        pc.kernel<<<n_sel * parts, PREP_THREADS, lds, st>>>(pts, off_dev, cnt_dev, cloud_ids, normal_k, v.sxy, v.snrm, v.sorig, v.skey,
+                                                            v.dir, out_normals, lds_points, parts, polar);
+    }
     if (normal_k > 31) {
-        if (small_max > 0) { ICPMI_PREP_GO2(0, false); }
         ICPMI_LAUNCH_CHECK();
         // the list of a query: k + 1 positions, at most the largest cloud
         const int kcap = normal_k + 1 < max_n ? normal_k + 1 : max_n;
@@ -410,18 +424,7 @@ extern "C" int icpmi_prepare_targets_ex(const double* pts, const int32_t* off_de
         per_cloud = per_cloud < 1 ? 1 : (per_cloud > 256 ? 256 : per_cloud);
         normals_anyk_kernel<<<dim3(per_cloud, n_sel), ANYK_THREADS, lds_k, st>>>(off_dev, cnt_dev, cloud_ids, normal_k, v.sxy, v.snrm, v.sorig,
                                                                                   v.dir, out_normals, sel_cap);
-        ICPMI_LAUNCH_CHECK();
-        return ICPMI_OK;
     }
-    if (normal_k < 0) ICPMI_PREP_GO(0);
-    else if (normal_k + 1 <= 6) ICPMI_PREP_GO(6);
-    else if (normal_k + 1 <= 8) ICPMI_PREP_GO(8);
-    else if (normal_k + 1 <= 11) ICPMI_PREP_GO(11);
-    else if (normal_k + 1 <= 13) ICPMI_PREP_GO(13);
-    else if (normal_k + 1 <= 16) ICPMI_PREP_GO(16);
-    else ICPMI_PREP_GO(32);
-#undef ICPMI_PREP_GO2
-#undef ICPMI_PREP_GO
     ICPMI_LAUNCH_CHECK();
     return ICPMI_OK;
 }

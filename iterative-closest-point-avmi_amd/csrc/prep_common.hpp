@@ -28,6 +28,11 @@ struct PreparedView {
     }
 };
 
+// prep_big.hip, called by prep.hip for every cloud above its LDS capacity: the scratch a cloud of n rows needs, and one cloud
+size_t prep_big_scratch_bytes(int n);
+int prep_big_cloud(const double* P, const int32_t* cnt_c, int n_cap, int normal_k, double2* o_sxy, double2* o_snrm,
+                   int32_t* o_sorig, int32_t* dir_c, double* o_rows, void* scratch, size_t scratch_bytes, hipStream_t st);
+
 constexpr int PREP_BINS = 64;
 
 // Search axis of a cloud: ranges of the four projections x, y, x+y, x-y, a 64-bin histogram per axis, and
