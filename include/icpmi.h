@@ -316,6 +316,86 @@ int icpmi_rotation_search_batch(const double* pts, const int32_t* off_dev, const
                                 int32_t max_rows_hint, double* out_records, double* out_init,
                                 void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- feature-based pre-alignment, utilities/features.py:35-160, 247-315 ------------------------------------------
+ * The five stages of feature_based_alignment, each on a cloud set of 2-D clouds (pts / off_dev / cnt_dev as above;
+ * cloud_ids[n_sel]: the clouds to process, NULL = clouds 0..n_sel-1), one workgroup per cloud or per pair with the cloud
+ * in LDS: at most 2048 valid rows per cloud (a larger cloud is left alone: no output, 0 keypoints), k <= 31, at most 256
+ * keypoints per cloud.  Per-cloud tables are indexed by the cloud's number in the set.
+ *
+ * compute_curvature, features.py:35-54.  out_curvature: one double per row (row layout of pts).  The k+1 nearest rows
+ * (k clamped to n-1, the lower row on equal distances), np.cov of them, eigenvalues in closed form,
+ * ev[0] / (ev[-1] + 1e-10); fewer than 3 neighbours: 0.  The neighbours are summed in ascending row order (the reference
+ * sums them in distance order: equal to its own rounding), so rows with one neighbour set get one value bit for bit. */
+int icpmi_feature_curvature_batch(const double* pts, const int32_t* off_dev, const int32_t* cnt_dev,
+                                  const int32_t* cloud_ids, int32_t n_sel, int32_t k, double* out_curvature,
+                                  void* stream);
+
+/* extract_keypoints, features.py:57-71.  The candidates of a cloud are walked in `order` (int32 per row, row layout:
+ * order[off[c] + i] = i-th candidate row of cloud c — the drop-in passes np.argsort(-curvatures)) or, with order == NULL,
+ * by descending `curvature` (row layout) with ties by ascending row; a candidate is kept when no kept point is closer
+ * than min_dist (sqrt(dx*dx + dy*dy) < min_dist, the reference's comparison bit for bit), until top_n are kept.
+ * out_kp[c * kp_stride + s]: row of the s-th keypoint of cloud c; out_kp_cnt[c]: their number.  top_n <= kp_stride. */
+int icpmi_feature_keypoints_batch(const double* pts, const int32_t* off_dev, const int32_t* cnt_dev,
+                                  const int32_t* cloud_ids, int32_t n_sel, const double* curvature,
+                                  const int32_t* order, int32_t top_n, double min_dist, int32_t* out_kp,
+                                  int32_t* out_kp_cnt, int32_t kp_stride, void* stream);
+
+/* compute_descriptors, features.py:76-87.  out_desc[(c * kp_stride + s) * 32 + q]: distance from keypoint s of cloud c
+ * to its (q+1)-th nearest other row, ascending, q < out_desc_len[c] = min(k, n-1) (the rest of the 32 is zero): exact
+ * neighbour distances with IEEE sqrt, as KDTree.query returns them. */
+int icpmi_feature_descriptors_batch(const double* pts, const int32_t* off_dev, const int32_t* cnt_dev,
+                                    const int32_t* cloud_ids, int32_t n_sel, const int32_t* kp, const int32_t* kp_cnt,
+                                    int32_t kp_stride, int32_t k, double* out_desc, int32_t* out_desc_len, void* stream);
+
+/* match_descriptors, features.py:92-106, for every pair (pair_src[b], pair_tgt[b]) of clouds: squared descriptor
+ * distances by direct differences, the two smallest per source keypoint (the lower index on ties), D0 < ratio_sq * D1
+ * (ratio_sq = ratio ** 2 from the caller, as the reference forms it).  out_matches[(b * kp_stride + m) * 2]: source and
+ * target keypoint of match m, in source-keypoint order; out_match_cnt[b].  No source descriptors, fewer than 2 target
+ * descriptors or descriptors of different lengths: no matches. */
+int icpmi_feature_match_batch(const double* desc, const int32_t* desc_len, const int32_t* kp_cnt, int32_t kp_stride,
+                              const int32_t* pair_src, const int32_t* pair_tgt, int32_t n_pairs, double ratio_sq,
+                              int32_t* out_matches, int32_t* out_match_cnt, void* stream);
+
+/* ransac_align, features.py:125-160 (with _rigid_from_points, features.py:111-122), for every pair.  The hypotheses are
+ * an INPUT: hyp_idx (int32 [n_iter][2], the index pairs np.random.choice(n, 2, replace=False) drew) or hyp_u (double
+ * [n_iter][2] uniform in [0, 1), mapped on the device to i = floor(u0 * n), j = floor(u1 * (n - 1)), j += (j >= i), n
+ * the pair's match count) — exactly one of the two; pair b reads from element b * hyp_pair_stride on (0: one table for
+ * all).  Per hypothesis: two-point rigid fit in closed form (both matches on one target keypoint, W = 0: R = I as the
+ * reference's SVD gives), error of every match, inliers err < inlier_thresh; the first hypothesis with the largest
+ * count wins, a count of 0 never replaces the identity; then the refit on the inliers of the best when there are at
+ * least 2.  A hypothesis with an index outside [0, n) or two equal indices counts 0.
+ * out_records [n_pairs][16]: slots 4 matches, 5 inliers, 6..9 R row-major, 10..11 t, 12 status (0, or 4: fewer than 2
+ * matches — identity, zeros, 0), 13 index of the winning hypothesis (-1: none); the other slots 0.
+ * out_counts (optional) [n_pairs][n_iter]: inliers of every hypothesis. */
+int icpmi_feature_ransac_batch(const double* pts, const int32_t* off_dev, const int32_t* cnt_dev, const int32_t* kp,
+                               const int32_t* kp_cnt, int32_t kp_stride, const int32_t* pair_src, const int32_t* pair_tgt,
+                               int32_t n_pairs, const int32_t* matches, const int32_t* match_cnt, const int32_t* hyp_idx,
+                               const double* hyp_u, int32_t n_iter, int32_t hyp_pair_stride, double inlier_thresh,
+                               double* out_records, int32_t* out_counts, void* stream);
+
+/* feature_based_alignment, features.py:247-315, as _run_icp_pair calls it (slam.py:68-88), for every pair of a batch:
+ * voxel filter of every cloud at voxel_size, then the five stages above (candidate order: descending curvature, ties by
+ * ascending row) — one chain of launches on `stream`, nothing returns to the host.  pts / off_dev / off_host: RAW 2-D
+ * clouds.  init_in (optional) [n_pairs][6], R row-major then t: the source of pair b is transformed by it before the
+ * filter (slam.py:69-71; pair_src_host, the host mirror of pair_src, is then required).  init_out (optional)
+ * [n_pairs][6]: R_feat @ R_init, t_init @ R_feat.T + t_feat when the pair has at least min_inliers inliers, else init_in
+ * (the identity without one) (slam.py:83-88) — the `init` of icpmi_icp_batch.
+ * out_records [n_pairs][16]: 0, 1 filtered rows of source and target; 2, 3 their keypoints; 4 matches; 5 inliers; 6..9 R;
+ * 10, 11 t; 12 status; 13 winning hypothesis.  Status: 0 aligned; 1 a filtered cloud has fewer than 10 rows
+ * (features.py:281-282); 2 a filtered cloud exceeds the 2048 rows the kernels hold on chip (not aligned: the caller falls
+ * back); 3 fewer than 2 keypoints (features.py:290-291); 4 fewer than 2 matches (features.py:299-300); 5 the two
+ * clouds' descriptors differ in length (k_descriptor > rows - 1 of one of them: NumPy raises in the reference).  Every
+ * status but 0 leaves identity, zeros, 0 inliers. */
+size_t icpmi_feature_align_batch_workspace_bytes(int32_t total_rows, int32_t n_clouds, int32_t max_n, int32_t n_pairs,
+                                                 int32_t top_n, int32_t with_init);
+int icpmi_feature_align_batch(const double* pts, const int32_t* off_dev, const int32_t* off_host, int32_t n_clouds,
+                              const int32_t* pair_src, const int32_t* pair_src_host, const int32_t* pair_tgt,
+                              int32_t n_pairs, double voxel_size, int32_t k_curvature, int32_t top_n, double min_kp_dist,
+                              int32_t k_descriptor, double ratio_sq, const int32_t* hyp_idx, const double* hyp_u,
+                              int32_t n_iter, int32_t hyp_pair_stride, double inlier_thresh, int32_t min_inliers,
+                              const double* init_in, double* init_out, double* out_records,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- OccupancyGrid2D, utilities/mapping.py ---------------------------------
  * world -> cell index, mapping.py:57-60,94-98: floor((w - min) / res), float64
  * IEEE division, result as int64. */

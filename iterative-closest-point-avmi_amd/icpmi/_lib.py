@@ -80,6 +80,19 @@ _SIGS = {
     "icpmi_rotation_search_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                               C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                               C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "icpmi_feature_curvature_batch": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "icpmi_feature_keypoints_batch": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double,
+                                                C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "icpmi_feature_descriptors_batch": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "icpmi_feature_match_batch": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "icpmi_feature_ransac_batch": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 +
+                                   [C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "icpmi_feature_align_batch_workspace_bytes": (C.c_size_t, [C.c_int32] * 6),
+    "icpmi_feature_align_batch": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_double, C.c_int32,
+                                            C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_int32,
+                                            C.c_int32, C.c_double, C.c_int32] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
     "icpmi_world_to_grid": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "icpmi_bresenham_cells": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "icpmi_grid_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),

@@ -23,6 +23,7 @@ from .batch import CloudSet, IcpBatch, _ptr, _stream, require_gpu, unpack_result
 REC_DOUBLES = 16
 ST_OK, ST_FEW, ST_CAPACITY, ST_NO_FINE = 0, 1, 2, 3
 RSB_MAX_ANGLES = 1024          # angles per sweep the batched kernel tabulates (csrc/rotsearch.hip)
+ALIGNMENT_METHODS = ("rotation_search", "features", "both")      # slam.py:60, 68
 
 
 def arange_rows(lo, hi, step):
@@ -164,6 +165,86 @@ class RotationSearchBatch:
                 features.VERBOSE = keep
         return R, tt, score, rec
 
+FEAT_ST_OK, FEAT_ST_FEW_ROWS, FEAT_ST_CAPACITY, FEAT_ST_FEW_KP, FEAT_ST_FEW_MATCHES, FEAT_ST_DESC_LEN = 0, 1, 2, 3, 4, 5
+FEAT_DEFAULTS = dict(voxel_size=0.2, k_curvature=10, top_n=100, min_kp_dist=0.3, k_descriptor=30, ratio_threshold=0.8,
+                     ransac_iterations=1000, inlier_threshold=0.5, min_inliers=3)            # slam.py:72-83
+
+
+class FeatureAlignBatch:
+    """feature_based_alignment (features.py:247-315) of every pair of a cloud set, resident on the device.
+
+    ``run()`` enqueues the chain of ``icpmi_feature_align_batch`` on the current stream — voxel filter at the feature voxel
+    size, curvature, keypoints, descriptors, matching, RANSAC — and returns the (B, 16) record tensor (include/icpmi.h).
+    ``init_in`` ([B, 6] device tensor: R row major, t): the start every source is transformed by first (slam.py:69-71);
+    ``init_out`` then receives the start of the ICP that follows (slam.py:83-88) and may be the same tensor.
+
+    The candidate order of the keypoints is the device's rule (descending curvature, ties by ascending row): the
+    reference's order among equal curvatures is an accident of NumPy's unstable sort, which a batch cannot reproduce.
+    The RANSAC hypotheses are an input, one table for every pair: ``hypotheses`` ((n_iter, 2) integers, used as they are;
+    a row that names a match the pair does not have counts no inliers) or ``rng`` (a ``numpy.random.Generator``): the match
+    count of a pair is only known on the device, so ``rng.random((n_iter, 2))`` is drawn once and the kernel maps a row
+    (u0, u1) to the matches i = floor(u0 * n), j = floor(u1 * (n - 1)), j += (j >= i) — two distinct matches, every
+    pair of them equally likely, as ``np.random.choice(n, 2, replace=False)`` gives.  Neither: ``rng`` seeded with 0.
+
+    A pair the kernels could not align — status 2, a filtered cloud above the 2 048 rows they hold on chip, or status 5,
+    descriptors of different lengths (NumPy raises there in the reference) — has no feature start: identity, zeros, 0
+    inliers in its record and ``init_out`` left as ``init_in``, as for the reference's own early returns; the status in
+    slot 12 says which."""
+
+    def __init__(self, clouds, pair_src, pair_tgt, feat_cfg=None, hypotheses=None, rng=None, init_in=None, init_out=None, like=None):
+        require_gpu()
+        L = _lib.lib()
+        self.raw = clouds if isinstance(clouds, CloudSet) else CloudSet.from_numpy(clouds)
+        if self.raw.dim != 2:
+            raise ValueError("feature_based_alignment is 2-D")
+        dev = self.raw.pts.device
+        cfg = dict(FEAT_DEFAULTS)
+        cfg.update({k: v for k, v in (feat_cfg or {}).items() if k in FEAT_DEFAULTS})
+        self.cfg = cfg
+        if not cfg["voxel_size"] > 0:
+            raise ValueError("voxel_size must be positive")
+        self.pair_src_host = np.ascontiguousarray(pair_src, dtype=np.int32)
+        self.pair_tgt_host = np.ascontiguousarray(pair_tgt, dtype=np.int32)
+        self.B = len(self.pair_src_host)
+        if len(self.pair_tgt_host) != self.B:
+            raise ValueError("pair_src and pair_tgt differ in length")
+        self.pair_src = torch.from_numpy(self.pair_src_host).to(dev)
+        self.pair_tgt = torch.from_numpy(self.pair_tgt_host).to(dev)
+        self.n_iter = int(cfg["ransac_iterations"])
+        self.hyp_idx = self.hyp_u = None
+        if like is not None:                               # another batch's hypothesis table (a pair redone on its own)
+            self.n_iter, self.hyp_idx, self.hyp_u = like.n_iter, like.hyp_idx, like.hyp_u
+        elif hypotheses is not None:
+            h = np.ascontiguousarray(hypotheses, dtype=np.int32)
+            if h.shape != (self.n_iter, 2):
+                raise ValueError(f"hypotheses must have shape ({self.n_iter}, 2), got {h.shape}")
+            self.hyp_idx = torch.from_numpy(h).to(dev) if self.n_iter else None
+        elif self.n_iter:
+            rng = rng if rng is not None else np.random.default_rng(0)
+            self.hyp_u = torch.from_numpy(rng.random((self.n_iter, 2))).to(dev)
+        self.init_in, self.init_out = init_in, init_out
+        self.records = torch.zeros((max(self.B, 1), REC_DOUBLES), dtype=torch.float64, device=dev)
+        need = L.icpmi_feature_align_batch_workspace_bytes(self.raw.total_rows, self.raw.n_clouds, self.raw.max_n, self.B,
+                                                           int(cfg["top_n"]), 1 if init_in is not None else 0)
+        self.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+
+    def run(self):
+        c = self.cfg
+        check(_lib.lib().icpmi_feature_align_batch(
+            _ptr(self.raw.pts), _ptr(self.raw.off), self.raw.off_host.ctypes.data_as(C.c_void_p), self.raw.n_clouds,
+            _ptr(self.pair_src), self.pair_src_host.ctypes.data_as(C.c_void_p), _ptr(self.pair_tgt), self.B,
+            float(c["voxel_size"]), int(c["k_curvature"]), int(c["top_n"]), float(c["min_kp_dist"]), int(c["k_descriptor"]),
+            float(c["ratio_threshold"] ** 2), _ptr(self.hyp_idx), _ptr(self.hyp_u), self.n_iter, 0, float(c["inlier_threshold"]),
+            int(c["min_inliers"]), _ptr(self.init_in), _ptr(self.init_out), _ptr(self.records), _ptr(self.ws), self.ws.numel(),
+            _stream()), "feature_based_alignment (batch)")
+        return self.records
+
+    def results(self, records=None):
+        """-> (R [B,2,2], t [B,2], n_inliers [B], records [B,16]) on the host (synchronises); records[:, 12] is the status."""
+        rec = (self.records if records is None else records).cpu().numpy()[:self.B]
+        return rec[:, 6:10].reshape(-1, 2, 2).copy(), rec[:, 10:12].copy(), rec[:, 5].astype(np.int64), rec
+
+
 def rotation_search_batch(sources, targets, voxel_size=0.3, angle_step_coarse=2.0, angle_step_fine=0.2):
     """rotation_search(sources[i], targets[i]) for every i in one chain of launches -> (R [B,2,2], t [B,2], score [B]).
     ``sources`` may be one array shared by every pair (the loop-closure shape, slam.py:576-579)."""
@@ -186,9 +267,12 @@ def _pair_lists(sources, targets):
 
 
 class RunIcpPairBatch:
-    """``_run_icp_pair`` (slam.py:53-98, alignment_method "rotation_search") for a batch of pairs resident in HBM:
-    ``run()`` = rotation search of every pair, then ICP of every pair from its own R_init / t_init — one stream, no host
-    round trip; returns the (B, 16) ICP result tensor (icpmi.batch.unpack_results).
+    """``_run_icp_pair`` (slam.py:53-98) for a batch of pairs resident in HBM: ``run()`` = the pre-alignment of every pair
+    — rotation search (``alignment_method`` "rotation_search", the default), feature alignment ("features") or the search
+    followed by the feature alignment from its result ("both") — then ICP of every pair from its own R_init / t_init:
+    one stream, no host round trip; returns the (B, 16) ICP result tensor (icpmi.batch.unpack_results).  With a feature
+    alignment, ``unpack()`` adds ``info["feature_records"]`` (FeatureAlignBatch; slot 12: status — a pair the feature
+    kernels could not align simply has no feature start).
 
     The pairs are loop-closure candidates in the caller's order.  ``error_accept``: the gate of slam.py:582-597 (the first
     candidate with err < error_accept is taken); ``unpack()`` then reports it as ``info["first_accepted"]``.  With
@@ -200,26 +284,41 @@ class RunIcpPairBatch:
     def __init__(self, clouds, pair_src, pair_tgt, error_threshold=1e-7, max_iterations=100, voxel_size=0.06,
                  method="point_to_line", normal_k=10, rotation_voxel_size=0.3, angle_step_coarse=2.0, angle_step_fine=0.2,
                  max_corr_dist=None, max_rows_hint=0, stop_after_first_accepted=False, error_accept=None,
-                 index_base=0, index_stride=1):
+                 index_base=0, index_stride=1, alignment_method="rotation_search", feat_cfg=None, hypotheses=None, rng=None):
+        if alignment_method not in ALIGNMENT_METHODS:
+            raise ValueError(f"alignment_method must be one of {ALIGNMENT_METHODS}, got {alignment_method!r}")
         if stop_after_first_accepted and error_accept is None:
             raise ValueError("stop_after_first_accepted needs a gate: error_accept")
         raw = clouds if isinstance(clouds, CloudSet) else CloudSet.from_numpy(clouds)
         B = len(pair_src)
         self.icp = IcpBatch(raw, pair_src, pair_tgt, error_threshold, max_iterations, voxel_size,
                             np.tile(np.eye(2), (B, 1, 1)), np.zeros((B, 2)), method, normal_k, max_corr_dist)
-        self.search = RotationSearchBatch(raw, pair_src, pair_tgt, rotation_voxel_size, angle_step_coarse, angle_step_fine,
-                                          init=self.icp.init, max_rows_hint=max_rows_hint)
         self.B = B
+        self.alignment_method = alignment_method
+        self.use_search = alignment_method in ("rotation_search", "both")           # slam.py:60
+        self.search = None
+        if self.use_search:
+            self.search = RotationSearchBatch(raw, pair_src, pair_tgt, rotation_voxel_size, angle_step_coarse, angle_step_fine,
+                                              init=self.icp.init, max_rows_hint=max_rows_hint)
+        # slam.py:68-88: the feature alignment starts from the search's result ("both") or from the raw source, and leaves
+        # the start of the ICP where the search would have: in the ICP's own init tensor
+        self.features = None
+        if alignment_method in ("features", "both"):
+            self.features = FeatureAlignBatch(raw, pair_src, pair_tgt, feat_cfg, hypotheses, rng,
+                                              init_in=self.icp.init if self.use_search else None, init_out=self.icp.init)
         self.error_accept = None if error_accept is None else float(error_accept)
         self.stop = bool(stop_after_first_accepted)
         self.index_base, self.index_stride = int(index_base), int(index_stride)
         if self.stop:
-            self.icp.set_gate(self.error_accept, self.search.records, self.index_base, self.index_stride)
+            self.icp.set_gate(self.error_accept, self.search.records if self.use_search else None, self.index_base, self.index_stride)
         # a pair can fall outside the on-chip search (status 2) only with a capacity hint, a raw cloud above the search's
         # 2 048 rows or more angles than it tabulates (csrc/rotsearch.hip): only then may first_accepted() need the host
-        self.capacity_possible = self.search.too_many_angles or max_rows_hint > 0 or raw.max_n > 2048
+        self.capacity_possible = self.use_search and (self.search.too_many_angles or max_rows_hint > 0 or raw.max_n > 2048)
 
     def run(self, events=None):
+        if not self.use_search:                            # "features": no search
+            self.features.run()
+            return self.icp.run(events=events)
         if self.search.too_many_angles:
             # more angles than the batched kernel tabulates (a step below ~0.36 degrees): every pair is searched by the
             # single-pair entry, as pairs beyond the capacity hint are — same numbers
@@ -231,6 +330,8 @@ class RunIcpPairBatch:
                 events[0].record(); events[1].record()
             return self.icp.results
         self.search.run()
+        if self.features is not None:
+            self.features.run()
         return self.icp.run(events=events)
 
     def first_accepted(self):
@@ -248,11 +349,20 @@ class RunIcpPairBatch:
         return first
 
     def _redo(self, i, R0, t0, clouds):
-        """The ICP of pair i through the single-pair entry, from the single-pair search's start -> its 16-double record."""
+        """The ICP of pair i through the single-pair entry, from the single-pair search's start — with "both", carried on
+        by the pair's own feature alignment (same configuration, same hypothesis table) -> its 16-double record."""
         from .batch import icp_pair
         p = self.icp.params
+        Rs, ts = R0[i], t0[i]
+        if self.features is not None:
+            start = torch.from_numpy(np.concatenate([Rs.reshape(4), ts])[None, :].copy()).to(self.icp.results.device)
+            one = FeatureAlignBatch([clouds[self.icp.pair_src_host[i]], clouds[self.icp.pair_tgt_host[i]]], [0], [1],
+                                    self.features.cfg, init_in=start, init_out=start, like=self.features)
+            self.redone_feature_records[int(i)] = one.run().cpu().numpy()[0]
+            v = start.cpu().numpy()[0]
+            Rs, ts = v[:4].reshape(2, 2), v[4:]
         Ri, ti, ei, info = icp_pair(clouds[self.icp.pair_src_host[i]], clouds[self.icp.pair_tgt_host[i]],
-                                    p.error_threshold, p.max_iterations, self.icp.voxel_size, R0[i], t0[i],
+                                    p.error_threshold, p.max_iterations, self.icp.voxel_size, Rs, ts,
                                     "point_to_line" if self.icp.use_p2l else "point_to_point", self.icp.normal_k,
                                     None if p.max_corr_dist < 0 else p.max_corr_dist)
         r = np.zeros(16)
@@ -262,11 +372,12 @@ class RunIcpPairBatch:
 
     def unpack(self):
         """(R, t, err, info) of the ICPs; pairs whose search fell outside the on-chip capacity (status 2) are redone
-        with the single-pair search's result as their start.  With a gate, info["first_accepted"] is the candidate
+        with the single-pair search's result as their start (and, with "both", their own feature alignment from it).  With a gate, info["first_accepted"] is the candidate
         slam.py:582-597 accepts (-1: none); with stop_after_first_accepted, a status-2 candidate after it is not redone
         but reported SKIPPED (identity, err inf, 0 iterations), and info["status"] is 5 for every skipped candidate."""
-        rec = self.search.records.cpu().numpy()[:self.B]
+        rec = self.search.records.cpu().numpy()[:self.B] if self.use_search else np.zeros((self.B, REC_DOUBLES))
         res = self.icp.results.cpu().numpy()[:self.B].copy()
+        self.redone_feature_records = {}
         if (rec[:, 11].astype(np.int64) == ST_NO_FINE).any():
             raise ValueError("attempt to get argmin of an empty sequence")          # features.py:231: np.argmin of an empty fine grid
         over = np.flatnonzero(rec[:, 11].astype(np.int64) == ST_CAPACITY)
@@ -290,6 +401,10 @@ class RunIcpPairBatch:
                 if self.stop and res[i, 12] < self.error_accept:
                     first = idx
         R, t, err, info = unpack_results(res, 2)
+        if self.features is not None:
+            info["feature_records"] = self.features.records.cpu().numpy()[:self.B].copy()
+            for i, r in self.redone_feature_records.items():
+                info["feature_records"][i] = r
         if self.error_accept is not None:
             if not self.stop:                                                  # the full run: first in order below the gate
                 ok = np.flatnonzero(err < self.error_accept)
@@ -298,11 +413,16 @@ class RunIcpPairBatch:
         return R, t, err, info
 
 
-def run_icp_pair_batch(sources, targets, icp_cfg=None, feat_cfg=None, error_accept=None, stop_after_first_accepted=False):
-    """``_run_icp_pair(sources[i], targets[i], icp_cfg, feat_cfg, "rotation_search")`` for every i (slam.py:53-98, same
+def run_icp_pair_batch(sources, targets, icp_cfg=None, feat_cfg=None, error_accept=None, stop_after_first_accepted=False,
+                       alignment_method="rotation_search", hypotheses=None, rng=None):
+    """``_run_icp_pair(sources[i], targets[i], icp_cfg, feat_cfg, alignment_method)`` for every i (slam.py:53-98, same
     configuration keys and defaults) -> (R [B,2,2], t [B,2], err [B], info).  With ``error_accept``,
     ``info["first_accepted"]`` is the candidate slam.py:582-597 accepts (-1: none); ``stop_after_first_accepted`` lets
-    the candidates after it stop early (status 5, RunIcpPairBatch)."""
+    the candidates after it stop early (status 5, RunIcpPairBatch).  ``alignment_method``: "rotation_search" (the
+    default: exactly the launches of before), "features" or "both" (FeatureAlignBatch, with its ``hypotheses`` / ``rng``;
+    ``info["feature_records"]`` then holds its records)."""
+    if alignment_method not in ALIGNMENT_METHODS:
+        raise ValueError(f"alignment_method must be one of {ALIGNMENT_METHODS}, got {alignment_method!r}")
     icp_cfg, feat_cfg = icp_cfg or {}, feat_cfg or {}
     clouds, ps, pt = _pair_lists(sources, targets)
     b = RunIcpPairBatch(clouds, ps, pt,
@@ -310,6 +430,7 @@ def run_icp_pair_batch(sources, targets, icp_cfg=None, feat_cfg=None, error_acce
                         voxel_size=icp_cfg.get("voxel_size", 0.06), method=icp_cfg.get("method", "point_to_line"),
                         normal_k=icp_cfg.get("normal_k", 10), rotation_voxel_size=feat_cfg.get("rotation_voxel_size", 0.3),
                         angle_step_coarse=feat_cfg.get("angle_step_coarse", 2.0), angle_step_fine=feat_cfg.get("angle_step_fine", 0.2),
-                        stop_after_first_accepted=stop_after_first_accepted, error_accept=error_accept)
+                        stop_after_first_accepted=stop_after_first_accepted, error_accept=error_accept,
+                        alignment_method=alignment_method, feat_cfg=feat_cfg, hypotheses=hypotheses, rng=rng)
     b.run()
     return b.unpack()
