@@ -27,13 +27,11 @@ namespace icpmi {
 constexpr int RC_THREADS = 256;
 #ifndef ICPMI_RC_STEPS
 #define ICPMI_RC_STEPS 16
-#define ICPMI_RC_SLOTS 16
-#define ICPMI_RC_FIN_BLOCKS 1024
 #endif
 constexpr int RC_STEPS = ICPMI_RC_STEPS;   // Bresenham steps per chunk
-constexpr int RC_SLOTS = ICPMI_RC_SLOTS;   // chunk slots per 64-beam group (grid-stride over longer rays)
+constexpr int RC_SLOTS = 16;               // chunk slots per 64-beam group (grid-stride over longer rays)
 constexpr int RC_COORD_MAX = 1 << 29; // cell coordinates are clamped to +-2^29
-constexpr int RC_FIN_BLOCKS = ICPMI_RC_FIN_BLOCKS;
+constexpr int RC_FIN_BLOCKS = 1024;
 
 struct GridDesc {
     int nx, ny;
@@ -52,6 +50,36 @@ struct BBox {
     uint32_t x1p;      // x1 + 1
     uint32_t y1p;      // y1 + 1
 };
+struct ScanBox { int x0, y0, x1, y1; };           // inclusive; x1 < x0: nothing to touch
+
+__device__ __forceinline__ BBox box_of(const GridDesc& g, int x0, int y0, int x1, int y1) {
+    return BBox{(uint32_t)(g.nx - x0), (uint32_t)(g.ny - y0), (uint32_t)(x1 + 1), (uint32_t)(y1 + 1)};
+}
+__device__ __forceinline__ ScanBox box_rect(const GridDesc& g, const BBox& b) {
+    if (b.inv_x0 == 0) return ScanBox{0, 0, -1, -1};
+    return ScanBox{g.nx - (int)b.inv_x0, g.ny - (int)b.inv_y0, (int)b.x1p - 1, (int)b.y1p - 1};
+}
+// what a beam can touch, cut to the window (Bresenham stays inside the rectangle spanned by its end points); all zero: nothing
+__device__ __forceinline__ BBox beam_box(const GridDesc& g, bool valid, int ox, int oy, int hx, int hy) {
+    const int x0 = max(g.wx0, min(ox, hx)), x1 = min(g.wx1 - 1, max(ox, hx));
+    const int y0 = max(g.wy0, min(oy, hy)), y1 = min(g.wy1 - 1, max(oy, hy));
+    return valid && x0 <= x1 && y0 <= y1 ? box_of(g, x0, y0, x1, y1) : BBox{0u, 0u, 0u, 0u};
+}
+// the union of the wave's boxes, in every lane
+__device__ __forceinline__ BBox box_wave_union(BBox b) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        b.inv_x0 = max(b.inv_x0, (uint32_t)__shfl_xor((int)b.inv_x0, o, ICPMI_WAVE));
+        b.inv_y0 = max(b.inv_y0, (uint32_t)__shfl_xor((int)b.inv_y0, o, ICPMI_WAVE));
+        b.x1p = max(b.x1p, (uint32_t)__shfl_xor((int)b.x1p, o, ICPMI_WAVE));
+        b.y1p = max(b.y1p, (uint32_t)__shfl_xor((int)b.y1p, o, ICPMI_WAVE));
+    }
+    return b;
+}
+__device__ __forceinline__ void box_grow(BBox* slot, const BBox& b) {
+    atomicMax(&slot->inv_x0, b.inv_x0); atomicMax(&slot->inv_y0, b.inv_y0);
+    atomicMax(&slot->x1p, b.x1p); atomicMax(&slot->y1p, b.y1p);
+}
 
 __device__ __forceinline__ bool world_to_cell(double w, double mn, double res, int& out) {
     const double f = floor((w - mn) / res);          // mapping.py:58-59,96-97
@@ -71,6 +99,9 @@ __device__ __forceinline__ bool world_to_cell_fast(double w, double mn, double r
 
 __device__ __forceinline__ bool world_to_cell_q(double w, double mn, double res, int& out) {   // same index, the division only near an integer
     return world_to_cell_fast(w, mn, res, 1.0 / res, out);
+}
+__device__ __forceinline__ bool origin_cell(const GridDesc& g, const double* __restrict__ origin, int& ox, int& oy) {
+    return world_to_cell(origin[0], g.min_x, g.res, ox) && world_to_cell(origin[1], g.min_y, g.res, oy);
 }
 
 // Walker over the cells of one ray.
@@ -137,6 +168,46 @@ struct Ray {
     }
 };
 
+// The steps [klo, khi) of the beam (ox, oy) -> (hx, hy) that lie in the cells [x0, x1) x [y0, y1); left as they are (the
+// caller's empty range) when there are none.
+__device__ __forceinline__ void cut_beam(int ox, int oy, int hx, int hy, int x0, int y0, int x1, int y1, int& klo, int& khi) {
+    // Bresenham stays inside the rectangle of its end points ...
+    bool cross = !(max(ox, hx) < x0 || min(ox, hx) >= x1 || max(oy, hy) < y0 || min(oy, hy) >= y1);
+    if (cross) {
+        // ... and within one cell of the straight line: a rectangle (grown by a cell) whose corners all lie
+        // strictly on one side of the line cannot be touched
+        const long long dx = hx - ox, dy = hy - oy;
+        const long long cxa = x0 - 1 - ox, cxb = x1 - ox, cya = y0 - 1 - oy, cyb = y1 - oy;
+        const long long c0 = dx * cya - dy * cxa, c1 = dx * cya - dy * cxb, c2 = dx * cyb - dy * cxa, c3 = dx * cyb - dy * cxb;
+        cross = !((c0 > 0 && c1 > 0 && c2 > 0 && c3 > 0) || (c0 < 0 && c1 < 0 && c2 < 0 && c3 < 0));
+    }
+    if (cross) {
+        Ray ray;
+        ray.init(ox, oy, hx, hy);
+        if (ray.xmajor) { ray.clip_major(x0, x1, klo, khi); ray.clip_minor(y0, y1, klo, khi); }
+        else { ray.clip_major(y0, y1, klo, khi); ray.clip_minor(x0, x1, klo, khi); }
+    }
+}
+
+// One count for this lane's cell (negative: none), runs of equal cells in adjacent lanes merged into one atomic each;
+// `prev` is the cell of the lane below (__shfl_up by one).
+template <class Cell>
+__device__ __forceinline__ void add_runs(uint32_t* counts, Cell cell, Cell prev, int lane) {
+    const bool leader = lane == 0 || cell != prev;
+    const unsigned long long lead = __ballot(leader);
+    if (leader && cell >= 0) {
+        const unsigned long long above = lane == 63 ? 0ull : (lead >> (lane + 1));
+        const int run = above ? __ffsll((long long)above) : 64 - lane;
+        atomicAdd(&counts[cell], (uint32_t)run);
+    }
+}
+
+__device__ __forceinline__ float clamp32(float v, float lo32, float hi32) {     // np.clip on float32, mapping.py:141
+    if (v < lo32) v = lo32;
+    if (v > hi32) v = hi32;
+    return v;
+}
+
 // mode bits
 constexpr int RC_DO_HITS = 1, RC_DO_MISS = 2, RC_PACKED = 4;
 
@@ -163,24 +234,9 @@ __device__ __forceinline__ void ray_count_body(
         const bool hit_in = valid && hx >= g.wx0 && hx < g.wx1 && hy >= g.wy0 && hy < g.wy1;
         if ((mode & RC_DO_HITS) && hit_in)
             atomicAdd(&counts[counter_index(g, hx, hy)], (mode & RC_PACKED) ? 0x10000u : 1u);
-        // bounding box of everything this beam can touch: Bresenham stays inside
-        // the rectangle spanned by its end points
-        int bx0 = max(g.wx0, min(ox, hx)), bx1 = min(g.wx1 - 1, max(ox, hx));
-        int by0 = max(g.wy0, min(oy, hy)), by1 = min(g.wy1 - 1, max(oy, hy));
-        const bool any = valid && bx0 <= bx1 && by0 <= by1;
-        uint32_t a = any ? (uint32_t)(g.nx - bx0) : 0u, b = any ? (uint32_t)(g.ny - by0) : 0u;
-        uint32_t c = any ? (uint32_t)(bx1 + 1) : 0u, d = any ? (uint32_t)(by1 + 1) : 0u;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            a = max(a, (uint32_t)__shfl_xor((int)a, o, ICPMI_WAVE));
-            b = max(b, (uint32_t)__shfl_xor((int)b, o, ICPMI_WAVE));
-            c = max(c, (uint32_t)__shfl_xor((int)c, o, ICPMI_WAVE));
-            d = max(d, (uint32_t)__shfl_xor((int)d, o, ICPMI_WAVE));
-        }
-        if (lane == 0 && a) {
-            atomicMax(&bbox->inv_x0, a); atomicMax(&bbox->inv_y0, b);
-            atomicMax(&bbox->x1p, c); atomicMax(&bbox->y1p, d);
-        }
+        // bounding box of everything the wave's beams can touch
+        const BBox b = box_wave_union(beam_box(g, valid, ox, oy, hx, hy));
+        if (lane == 0 && b.inv_x0) box_grow(bbox, b);
     }
     if (!(mode & RC_DO_MISS)) return;
 
@@ -213,15 +269,7 @@ __device__ __forceinline__ void ray_count_body(
                 }
                 ray.step();
             }
-            // merge runs of equal cells in adjacent lanes into one atomic
-            const long long prev = __shfl_up(cellid, 1, ICPMI_WAVE);
-            const bool leader = lane == 0 || cellid != prev;
-            const unsigned long long lead = __ballot(leader);
-            if (leader && cellid >= 0) {
-                const unsigned long long above = lane == 63 ? 0ull : (lead >> (lane + 1));
-                const int run = above ? __ffsll((long long)above) : 64 - lane;
-                atomicAdd(&counts[cellid], (uint32_t)run);
-            }
+            add_runs(counts, cellid, __shfl_up(cellid, 1, ICPMI_WAVE), lane);
         }
     }
 }
@@ -249,11 +297,7 @@ __device__ __forceinline__ float apply_counts(float v0, uint32_t H, uint32_t M, 
         if (nv == v) break;
         v = nv;
     }
-    if (clip) {                                    // np.clip on float32, mapping.py:141
-        if (v < lo32) v = lo32;
-        if (v > hi32) v = hi32;
-    }
-    return v;
+    return clip ? clamp32(v, lo32, hi32) : v;
 }
 
 // A group of consecutive scans counted in ONE launch, each into its own counter grid (cells are independent and
@@ -294,16 +338,11 @@ __device__ __forceinline__ void ray_finalize_body(const GridDesc& g, const FinAr
     const double l_hit = f.l_hit, l_miss = f.l_miss;
     const float lo32 = f.lo32, hi32 = f.hi32;
     const int count_kind = f.count_kind, clip = f.clip, full_clip = f.full_clip;
-    int x0, y0, x1, y1;
-    const BBox bb = *bbox;
-    if (full_clip) { x0 = 0; y0 = g.ry0; x1 = g.nx - 1; y1 = g.ry1 - 1; }        // the whole band, also outside the counted window
-    else if (f.use_window) { x0 = g.wx0; y0 = g.wy0; x1 = g.wx1 - 1; y1 = g.wy1 - 1; }
-    else {
-        if (bb.inv_x0 == 0) { x0 = 0; y0 = 0; x1 = -1; y1 = -1; }
-        else { x0 = g.nx - (int)bb.inv_x0; y0 = g.ny - (int)bb.inv_y0; x1 = (int)bb.x1p - 1; y1 = (int)bb.y1p - 1; }   // inside the band by construction
-    }
-    for (int y = y0 + block; y <= y1; y += nblocks)
-        for (int x = x0 + threadIdx.x; x <= x1; x += RC_THREADS) {
+    ScanBox r = box_rect(g, *bbox);                                            // the counted box: inside the band by construction
+    if (full_clip) r = ScanBox{0, g.ry0, g.nx - 1, g.ry1 - 1};                 // the whole band, also outside the counted window
+    else if (f.use_window) r = ScanBox{g.wx0, g.wy0, g.wx1 - 1, g.wy1 - 1};
+    for (int y = r.y0 + block; y <= r.y1; y += nblocks)
+        for (int x = r.x0 + threadIdx.x; x <= r.x1; x += RC_THREADS) {
             const size_t c = (size_t)y * g.nx + x;
             const bool counted = x >= g.wx0 && x < g.wx1 && y >= g.wy0 && y < g.wy1;      // only a whole-band clip walks beyond the window
             const size_t cc = counted ? counter_index(g, x, y) : 0;
@@ -324,18 +363,14 @@ __device__ __forceinline__ void ray_finalize_body(const GridDesc& g, const FinAr
                         const uint32_t M = count_kind == 0 ? cn[s] & 0xffffu : (count_kind == 2 ? cn[s] : 0u);
                         v = apply_counts(v, H, M, l_hit, l_miss, lo32, hi32, clip != 0);
                     } else if (s == 0 && full_clip && clip) {        // untouched by the first scan, but its clip is whole-grid
-                        v = v < lo32 ? lo32 : v;
-                        v = v > hi32 ? hi32 : v;
+                        v = clamp32(v, lo32, hi32);
                     }
                 log_odds[c] = v;
             } else if (full_clip && clip) {
-                float v = log_odds[c];
-                if (v < lo32) v = lo32;
-                if (v > hi32) v = hi32;
-                log_odds[c] = v;
+                log_odds[c] = clamp32(log_odds[c], lo32, hi32);
             }
         }
-    if (other && block == 0 && threadIdx.x == 0) { other->inv_x0 = 0; other->inv_y0 = 0; other->x1p = 0; other->y1p = 0; }
+    if (other && block == 0 && threadIdx.x == 0) *other = BBox{0u, 0u, 0u, 0u};
 }
 
 __global__ __launch_bounds__(RC_THREADS) void ray_count_kernel(
@@ -392,8 +427,6 @@ constexpr int RT_FAR = 4, RT_CHUNKS = 16;           // workgroups per (scan, til
 __host__ __device__ constexpr int rt_blocks_per_scan(int n_tiles) { return n_tiles * RT_FAR + 9 * (RT_CHUNKS - RT_FAR); }
 constexpr int RT_STEPS = 16, RT_BLOCKS = RT_TILE / RT_STEPS;   // a thread walks blocks of 16 steps
 
-struct ScanBox { int x0, y0, x1, y1; };           // inclusive; x1 < x0: nothing to touch
-
 // beams of a scan are cut into RT_CHUNKS parts of rt_part(nb) consecutive beams (whole waves)
 __host__ __device__ constexpr int rt_part(int nb) { return ((nb + RT_CHUNKS - 1) / RT_CHUNKS + ICPMI_WAVE - 1) & ~(ICPMI_WAVE - 1); }
 
@@ -406,43 +439,24 @@ constexpr int RT_BOXES = 1 + RT_CHUNKS;           // per scan: the box of the sc
 __device__ __forceinline__ void ray_scan_boxes_body(const GridDesc& g, const double* __restrict__ origins,
                                                     const double* __restrict__ hits, const ScanGroup& grp,
                                                     ScanBox* __restrict__ boxes, int s) {
-    __shared__ uint32_t bb[RT_BOXES][4];
+    __shared__ BBox bb[RT_BOXES];
     const int tid = threadIdx.x;
     const int nb = grp.nb[s], part = rt_part(nb);
     const double* h = hits + 2 * (size_t)grp.hit_row[s];
     const double* origin = origins + 2 * (size_t)grp.origin_row[s];
-    if (tid < RT_BOXES * 4) (&bb[0][0])[tid] = 0u;
+    if (tid < RT_BOXES * 4) (&bb[0].inv_x0)[tid] = 0u;
     int ox = 0, oy = 0;
-    const bool ok = world_to_cell(origin[0], g.min_x, g.res, ox) && world_to_cell(origin[1], g.min_y, g.res, oy);
+    const bool ok = origin_cell(g, origin, ox, oy);
     __syncthreads();
     for (int base = 0; ok && base < nb; base += RT_THREADS) {           // a wave's 64 beams belong to one part
         const int i = base + tid;
-        uint32_t a = 0, b = 0, c = 0, d = 0;
         int hx = 0, hy = 0;
-        if (i < nb && world_to_cell_q(h[2 * (size_t)i], g.min_x, g.res, hx) && world_to_cell_q(h[2 * (size_t)i + 1], g.min_y, g.res, hy)) {
-            const int bx0 = max(g.wx0, min(ox, hx)), bx1 = min(g.wx1 - 1, max(ox, hx));
-            const int by0 = max(g.wy0, min(oy, hy)), by1 = min(g.wy1 - 1, max(oy, hy));
-            if (bx0 <= bx1 && by0 <= by1) { a = (uint32_t)(g.nx - bx0); b = (uint32_t)(g.ny - by0); c = (uint32_t)(bx1 + 1); d = (uint32_t)(by1 + 1); }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            a = max(a, (uint32_t)__shfl_xor((int)a, o, ICPMI_WAVE));
-            b = max(b, (uint32_t)__shfl_xor((int)b, o, ICPMI_WAVE));
-            c = max(c, (uint32_t)__shfl_xor((int)c, o, ICPMI_WAVE));
-            d = max(d, (uint32_t)__shfl_xor((int)d, o, ICPMI_WAVE));
-        }
-        if (lane_id() == 0 && a) {
-            const int p = 1 + i / part;
-            atomicMax(&bb[0][0], a); atomicMax(&bb[0][1], b); atomicMax(&bb[0][2], c); atomicMax(&bb[0][3], d);
-            atomicMax(&bb[p][0], a); atomicMax(&bb[p][1], b); atomicMax(&bb[p][2], c); atomicMax(&bb[p][3], d);
-        }
+        const bool valid = i < nb && world_to_cell_q(h[2 * (size_t)i], g.min_x, g.res, hx) && world_to_cell_q(h[2 * (size_t)i + 1], g.min_y, g.res, hy);
+        const BBox b = box_wave_union(beam_box(g, valid, ox, oy, hx, hy));
+        if (lane_id() == 0 && b.inv_x0) { box_grow(&bb[0], b); box_grow(&bb[1 + i / part], b); }
     }
     __syncthreads();
-    if (tid < RT_BOXES) {
-        ScanBox r{0, 0, -1, -1};
-        if (bb[tid][0]) r = ScanBox{g.nx - (int)bb[tid][0], g.ny - (int)bb[tid][1], (int)bb[tid][2] - 1, (int)bb[tid][3] - 1};
-        boxes[(size_t)s * RT_BOXES + tid] = r;
-    }
+    if (tid < RT_BOXES) boxes[(size_t)s * RT_BOXES + tid] = box_rect(g, bb[tid]);
 }
 
 __global__ __launch_bounds__(RT_THREADS) void ray_scan_boxes_kernel(GridDesc g, const double* __restrict__ origins,
@@ -469,7 +483,7 @@ __device__ __forceinline__ void ray_tile_body(const GridDesc& g, const double* _
     const int tid = threadIdx.x;
     const double* origin = origins + 2 * (size_t)grp.origin_row[s];
     int ox = 0, oy = 0;
-    const bool ok = world_to_cell(origin[0], g.min_x, g.res, ox) && world_to_cell(origin[1], g.min_y, g.res, oy);
+    const bool ok = origin_cell(g, origin, ox, oy);
     // Every tile has RT_FAR workgroups, each with a quarter of the beams.  The 3 x 3 tiles around the origin see every
     // beam at full length: their beams are cut into RT_CHUNKS parts, and the extra workgroups come after the regular ones.
     const int otx = (ox - g.wx0) >> 6, oty = (oy - g.wy0) >> 6;            // arithmetic shift: floor, also left of the window
@@ -490,15 +504,9 @@ __device__ __forceinline__ void ray_tile_body(const GridDesc& g, const double* _
     const int x1 = min(x0 + RT_TILE, g.wx1), y1 = min(y0 + RT_TILE, g.wy1);
     if (ta.boxes) {
         const ScanBox sb = ta.boxes[(size_t)s * RT_BOXES];
-        if (first && tid == 0 && sb.x1 >= sb.x0) {                       // the group's box for the finalise pass
-            atomicMax(&bbox->inv_x0, (uint32_t)(g.nx - sb.x0)); atomicMax(&bbox->inv_y0, (uint32_t)(g.ny - sb.y0));
-            atomicMax(&bbox->x1p, (uint32_t)(sb.x1 + 1)); atomicMax(&bbox->y1p, (uint32_t)(sb.y1 + 1));
-        }
+        if (first && tid == 0 && sb.x1 >= sb.x0) box_grow(bbox, box_of(g, sb.x0, sb.y0, sb.x1, sb.y1));   // the group's box for the finalise pass
         if (sb.x1 < x0 || sb.x0 >= x1 || sb.y1 < y0 || sb.y0 >= y1) return;              // uniform: the scan does not reach this tile
-    } else if (first && tid == 0) {                                     // a single scan: the caller's box is the scan's
-        atomicMax(&bbox->inv_x0, (uint32_t)(g.nx - g.wx0)); atomicMax(&bbox->inv_y0, (uint32_t)(g.ny - g.wy0));
-        atomicMax(&bbox->x1p, (uint32_t)g.wx1); atomicMax(&bbox->y1p, (uint32_t)g.wy1);
-    }
+    } else if (first && tid == 0) box_grow(bbox, box_of(g, g.wx0, g.wy0, g.wx1 - 1, g.wy1 - 1));   // a single scan: the caller's box is the scan's
     const double* h = hits + 2 * (size_t)grp.hit_row[s];
     // a near workgroup takes one part of the beams, a far one four
     const int nb = grp.nb[s], part = rt_part(nb);
@@ -519,22 +527,7 @@ __device__ __forceinline__ void ray_tile_body(const GridDesc& g, const double* _
         bool hit_in = false;
         if (i < b1 && world_to_cell_q(h[2 * (size_t)i], g.min_x, g.res, hx) && world_to_cell_q(h[2 * (size_t)i + 1], g.min_y, g.res, hy)) {
             hit_in = hx >= x0 && hx < x1 && hy >= y0 && hy < y1;
-            // Bresenham stays inside the rectangle of its end points ...
-            bool cross = !(max(ox, hx) < x0 || min(ox, hx) >= x1 || max(oy, hy) < y0 || min(oy, hy) >= y1);
-            if (cross) {
-                // ... and within one cell of the straight line: a tile (grown by a cell) whose corners all lie
-                // strictly on one side of the line cannot be touched
-                const long long dx = hx - ox, dy = hy - oy;
-                const long long cxa = x0 - 1 - ox, cxb = x1 - ox, cya = y0 - 1 - oy, cyb = y1 - oy;
-                const long long c0 = dx * cya - dy * cxa, c1 = dx * cya - dy * cxb, c2 = dx * cyb - dy * cxa, c3 = dx * cyb - dy * cxb;
-                cross = !((c0 > 0 && c1 > 0 && c2 > 0 && c3 > 0) || (c0 < 0 && c1 < 0 && c2 < 0 && c3 < 0));
-            }
-            if (cross) {
-                Ray ray;
-                ray.init(ox, oy, hx, hy);
-                if (ray.xmajor) { ray.clip_major(x0, x1, klo, khi); ray.clip_minor(y0, y1, klo, khi); }
-                else { ray.clip_major(y0, y1, klo, khi); ray.clip_minor(x0, x1, klo, khi); }
-            }
+            cut_beam(ox, oy, hx, hy, x0, y0, x1, y1, klo, khi);
         }
         if (!__syncthreads_or(hit_in || khi > klo)) continue;            // nothing of this pass touches the tile
         if (!dirty) {
@@ -639,7 +632,7 @@ __global__ __launch_bounds__(RO_THREADS) void ray_owner_kernel(GridDesc g, const
         hwx[j] = i < nb ? hits[2 * (size_t)i] : 0.0; hwy[j] = i < nb ? hits[2 * (size_t)i + 1] : 0.0;
     }
     int ox = 0, oy = 0;
-    if (!(world_to_cell(origin[0], g.min_x, g.res, ox) && world_to_cell(origin[1], g.min_y, g.res, oy))) return;   // mapping.py: int() raises
+    if (!origin_cell(g, origin, ox, oy)) return;                     // mapping.py: int() raises
     const int otx = (ox - g.wx0) >> 6, oty = (oy - g.wy0) >> 6;      // arithmetic shift: floor, also left of the window
     // the rectangle this workgroup owns (uniform)
     int x0, y0, x1, y1;
@@ -704,22 +697,7 @@ __global__ __launch_bounds__(RO_THREADS) void ray_owner_kernel(GridDesc g, const
             }
             if (maybe && world_to_cell_fast(hwx[j], g.min_x, g.res, rinv, hx) && world_to_cell_fast(hwy[j], g.min_y, g.res, rinv, hy)) {
                 if (hx >= x0 && hx < x1 && hy >= y0 && hy < y1) atomicAdd(&cnt[(hy - y0) * w + (hx - x0)], 0x10000u);   // mapping.py:124-129
-                // Bresenham stays inside the rectangle of its end points ...
-                bool cross = !(max(ox, hx) < x0 || min(ox, hx) >= x1 || max(oy, hy) < y0 || min(oy, hy) >= y1);
-                if (cross) {
-                    // ... and within one cell of the straight line: a rectangle (grown by a cell) whose corners all lie
-                    // strictly on one side of the line cannot be touched
-                    const long long dx = hx - ox, dy = hy - oy;
-                    const long long cxa = x0 - 1 - ox, cxb = x1 - ox, cya = y0 - 1 - oy, cyb = y1 - oy;
-                    const long long c0 = dx * cya - dy * cxa, c1 = dx * cya - dy * cxb, c2 = dx * cyb - dy * cxa, c3 = dx * cyb - dy * cxb;
-                    cross = !((c0 > 0 && c1 > 0 && c2 > 0 && c3 > 0) || (c0 < 0 && c1 < 0 && c2 < 0 && c3 < 0));
-                }
-                if (cross) {
-                    Ray ray;
-                    ray.init(ox, oy, hx, hy);
-                    if (ray.xmajor) { ray.clip_major(x0, x1, klo, khi); ray.clip_minor(y0, y1, klo, khi); }
-                    else { ray.clip_major(y0, y1, klo, khi); ray.clip_minor(x0, x1, klo, khi); }
-                }
+                cut_beam(ox, oy, hx, hy, x0, y0, x1, y1, klo, khi);
             }
             // The walk is shared out as (64 neighbouring beams, block of RO_STEPS steps) items: a far tile is crossed by two
             // or three waves' worth of beams for up to 64 steps each, and a step is a chain of dependent LDS operations
@@ -768,15 +746,7 @@ __global__ __launch_bounds__(RO_THREADS) void ray_owner_kernel(GridDesc g, const
 #pragma unroll
             for (int q = 0; q < RO_STEPS; ++q) prev[q] = __shfl_up(cid[q], 1, ICPMI_WAVE);
 #pragma unroll
-            for (int q = 0; q < RO_STEPS; ++q) {
-                const bool leader = lane == 0 || cid[q] != prev[q];
-                const unsigned long long lead = __ballot(leader);
-                if (leader && cid[q] >= 0) {
-                    const unsigned long long above = lane == 63 ? 0ull : (lead >> (lane + 1));
-                    const int run = above ? __ffsll((long long)above) : 64 - lane;
-                    atomicAdd(&cnt[cid[q]], (uint32_t)run);
-                }
-            }
+            for (int q = 0; q < RO_STEPS; ++q) add_runs(cnt, cid[q], prev[q], lane);
         }
         __syncthreads();                                             // seg and items are written again by the next chunk
     }
@@ -816,16 +786,128 @@ __global__ void bresenham_cells_kernel(const int32_t* __restrict__ segs, const l
 
 // The counter workspace (sized below): the counters | three bounding-box slots | two sets of scan boxes, no gap but the
 // 256 bytes that hold the slots.
+constexpr size_t grid_counters(int32_t ny, int32_t nx) { return 4 * (size_t)ny * (size_t)nx; }
 struct GridWs {
     Carve c;
     int32_t ny, nx;
-    size_t capacity = 4 * (size_t)ny * (size_t)nx;                 // counters
+    size_t capacity = grid_counters(ny, nx);
     uint32_t* counters = c.packed<uint32_t>(capacity * sizeof(uint32_t));
     BBox* slots = c.packed<BBox>(256);                             // [3]
     ScanBox* box_sets[2] = {c.packed<ScanBox>((size_t)RC_GROUP_MAX * RT_BOXES * sizeof(ScanBox)),     // by group parity
                             c.packed<ScanBox>((size_t)RC_GROUP_MAX * RT_BOXES * sizeof(ScanBox))};
     size_t bytes = c.off;
 };
+
+// ── host side of update_scan: what a call starts is decided first and as a whole (plan_raycast: a function of its
+// arguments, no HIP call), then issued (icpmi_grid_update_scans_box) ──────────────────────────────────────────────
+// The RAYCAST option by its first letter; `other` (any other value) only keeps the owner pass off.
+enum class RcOption { unset, atomic, tiles, owner, other };
+static RcOption parse_rc_option(const char* v) {
+    if (!v) return RcOption::unset;
+    return v[0] == 'a' ? RcOption::atomic : v[0] == 't' ? RcOption::tiles : v[0] == 'o' ? RcOption::owner : RcOption::other;
+}
+
+// the live update in one launch | tile counters in LDS | an atomic per (wave, cell); the last two pipelined over groups
+enum class RcPass { owner, tiles, atomic };
+
+struct RaycastPlan {
+    int wx0, wx1, wy0, wy1;       // the window: grid (band) cut to the caller's box; one counter region per scan of a group covers it
+    bool empty_window;            // no cell of the band can be touched (a full clip still runs): one cell, nothing counted in it
+    size_t cells;                 // counters per scan
+    int group_max, live_scans;    // scans per group at most (two sets fit the workspace); scans with beams
+    bool window_is_box;           // one scan with a box from the caller (the live update): the finalise pass walks that box
+    int tiles_x, tiles_y;         // 64 x 64 tiles of the window
+    RcPass pass;
+    int owner_scan, owner_beams, owner_grid;   // owner pass: the scan, its beams, the workgroups of the launch
+};
+constexpr int RC_WIDE = 65535;    // beams a 16-bit counter holds
+
+static RaycastPlan plan_raycast(int ny, int nx, int row_begin, int row_end, const int32_t* box, const int32_t* hit_off,
+                                int n_scans, bool full_clip, bool have_hits, RcOption opt) {
+    RaycastPlan p{};
+    p.wx0 = box && box[0] > 0 ? box[0] : 0; p.wy0 = box && box[1] > row_begin ? box[1] : row_begin;
+    p.wx1 = box && box[2] + 1 < nx ? box[2] + 1 : nx; p.wy1 = box && box[3] + 1 < row_end ? box[3] + 1 : row_end;
+    p.empty_window = p.wx0 >= p.wx1 || p.wy0 >= p.wy1;
+    if (p.empty_window) { p.wx0 = 0; p.wx1 = 1; p.wy0 = row_begin; p.wy1 = row_begin + 1; }
+    p.cells = (size_t)(p.wx1 - p.wx0) * (size_t)(p.wy1 - p.wy0);
+    const size_t fit = grid_counters(ny, nx) / (2 * p.cells);                       // >= 2: the window is at most the grid
+    p.group_max = fit > (size_t)RC_GROUP_MAX ? RC_GROUP_MAX : (int)fit;
+    for (int t = 0; t < n_scans; ++t) p.live_scans += hit_off[t + 1] > hit_off[t] ? 1 : 0;
+    p.window_is_box = p.live_scans == 1 && box && !p.empty_window;
+    p.tiles_x = (p.wx1 - p.wx0 + RT_TILE - 1) / RT_TILE; p.tiles_y = (p.wy1 - p.wy0 + RT_TILE - 1) / RT_TILE;
+    const long long tiles = (long long)p.tiles_x * p.tiles_y;
+    p.pass = RcPass::atomic;
+    // The tile pass needs the caller's box (the tiles of the window are enumerated; a scan's own box, found on the device,
+    // sends the other tiles home at once); without one the window is the whole grid and the atomic pass runs.  So it does
+    // for a single scan that the owner pass cannot take (two short launches, 21 us against 32) and for a replay whose box is
+    // far larger than a scan's reach: every scan would start four workgroups per tile just to find that it does not get
+    // there (~1 000 tiles: even).  RAYCAST = atomic / tiles force either (experiments, and the parity tests).
+    if (box && !p.empty_window && have_hits && opt != RcOption::atomic &&
+        ((p.live_scans > 1 && tiles <= 768) || opt == RcOption::tiles)) p.pass = RcPass::tiles;
+    // The live update: the owner pass (RAYCAST = owner says the same; atomic / tiles keep the passes above).  It needs no
+    // clip of cells the scan does not touch (full_clip) and 16-bit counts, and every workgroup looks at every beam: beyond
+    // a few hundred tiles the two passes with counters are the cheaper way.
+    if (p.window_is_box && !full_clip && have_hits && (opt == RcOption::unset || opt == RcOption::owner)) {
+        int s = 0;
+        while (hit_off[s + 1] == hit_off[s]) ++s;
+        const int nb = hit_off[s + 1] - hit_off[s];
+        if (nb > 0 && nb <= RC_WIDE && tiles <= 320) {
+            p.pass = RcPass::owner; p.owner_scan = s; p.owner_beams = nb;
+            p.owner_grid = RO_NEAR + (int)tiles * (RT_TILE / RO_FAR) * (RT_TILE / RO_FAR);
+        }
+    }
+    return p;
+}
+
+// counting workgroups of a scan of nb beams (ray_count_body: RC_SLOTS waves per 64 beams)
+static int count_blocks(int nb) {
+    const long waves = (long)((nb + ICPMI_WAVE - 1) / ICPMI_WAVE) * RC_SLOTS;
+    return (int)((waves * ICPMI_WAVE + RC_THREADS - 1) / RC_THREADS);
+}
+
+// The group that starts at the first scan with beams at or after `from`, and goes on while the scans fit a 16-bit counter
+// (scans without beams are skipped: mapping.py:113-114, a silent no-op without a clip).  BUILT: end = one past its last
+// scan; NONE: the replay ends (end = n_scans) or scan `end` is too wide for a group; BAD: a negative beam count.
+enum { RC_GROUP_BAD = -1, RC_GROUP_NONE = 0, RC_GROUP_BUILT = 1 };
+static int build_group(const int32_t* hit_off, int n_scans, int group_max, int from, ScanGroup& gq, int& end) {
+    gq = ScanGroup{};
+    for (end = from; end < n_scans && gq.n < group_max; ++end) {
+        const int nb = hit_off[end + 1] - hit_off[end];
+        if (nb < 0) return RC_GROUP_BAD;
+        if (nb == 0) continue;
+        if (nb > RC_WIDE) break;
+        gq.nb[gq.n] = nb; gq.origin_row[gq.n] = end; gq.hit_row[gq.n] = hit_off[end];
+        gq.first_block[gq.n + 1] = gq.first_block[gq.n] + count_blocks(nb);
+        ++gq.n;
+    }
+    return gq.n > 0 ? RC_GROUP_BUILT : RC_GROUP_NONE;
+}
+
+// What the q-th group (or wide scan) of a call works on: counter grids and scan boxes alternate between two sets, the
+// bounding-box slots between three (a finalise pass frees the slot two groups ahead).
+struct RcSlots { uint32_t* counts; BBox *box, *box_to_free; ScanBox *boxes, *next_boxes; };
+static RcSlots rc_slots(const GridWs& ws, const RaycastPlan& p, int64_t q) {
+    return {ws.counters + (size_t)(q & 1) * p.group_max * p.cells, ws.slots + q % 3, ws.slots + (q + 2) % 3,
+            ws.box_sets[q & 1], ws.box_sets[(q + 1) & 1]};
+}
+
+// The finalise pass over n_grids counter grids; `last`: the scans are complete after it (it clips and frees a slot), which
+// only the hits-only round of a wide scan is not.  `base`: what every pass of a call shares.
+static FinArgs fin_args(FinArgs base, const RcSlots& at, int n_grids, int count_kind, bool last, int clip_all) {
+    base.counts = at.counts; base.n_grids = n_grids; base.bbox = at.box; base.count_kind = count_kind;
+    base.other = last ? at.box_to_free : nullptr; base.clip = last ? 1 : 0; base.full_clip = last ? clip_all : 0;
+    return base;
+}
+
+// A scan of more beams than a 16-bit counter holds: hits and misses in two rounds, no pipelining
+static void launch_wide_scan(const GridDesc& g, const double* origin, const double* hits, int nb, const RcSlots& at,
+                             const FinArgs& base, int clip_all, hipStream_t st) {
+    const int blocks = count_blocks(nb);
+    ray_count_kernel<<<blocks, RC_THREADS, 0, st>>>(g, origin, hits, nb, at.counts, at.box, RC_DO_HITS);
+    ray_finalize_kernel<<<RC_FIN_BLOCKS, RC_THREADS, 0, st>>>(g, fin_args(base, at, 1, 1, false, clip_all));
+    ray_count_kernel<<<blocks, RC_THREADS, 0, st>>>(g, origin, hits, nb, at.counts, at.box, RC_DO_MISS);
+    ray_finalize_kernel<<<RC_FIN_BLOCKS, RC_THREADS, 0, st>>>(g, fin_args(base, at, 1, 2, true, clip_all));
+}
 
 }  // namespace icpmi
 
@@ -887,153 +969,68 @@ extern "C" int icpmi_grid_update_scans_box(float* log_odds, void* counts_ws, int
     if (row_begin == row_end) return ICPMI_OK;                  // an empty band: nothing to write
     if (ny > RC_COORD_MAX || nx > RC_COORD_MAX || !(resolution > 0.0)) return ICPMI_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    // the window: grid (band) cut to the caller's box; one counter region per scan of a group covers it
-    int wx0 = 0, wx1 = nx, wy0 = row_begin, wy1 = row_end;
-    if (box_host) {
-        wx0 = box_host[0] > wx0 ? box_host[0] : wx0; wy0 = box_host[1] > wy0 ? box_host[1] : wy0;
-        wx1 = box_host[2] + 1 < wx1 ? box_host[2] + 1 : wx1; wy1 = box_host[3] + 1 < wy1 ? box_host[3] + 1 : wy1;
-    }
-    const bool empty_window = wx0 >= wx1 || wy0 >= wy1;             // no cell of the band can be touched (a full clip still runs)
-    if (empty_window) { wx0 = 0; wx1 = 1; wy0 = row_begin; wy1 = row_begin + 1; }
-    const size_t cells = (size_t)(wx1 - wx0) * (size_t)(wy1 - wy0);                 // counters per scan
+    (void)scan_seq;   // ignored: a call starts with empty boxes and ends with empty counter grids (a finalise pass zeroes what it reads)
+    const RaycastPlan plan = plan_raycast(ny, nx, row_begin, row_end, box_host, hit_off_host, n_scans, full_clip != 0,
+                                          hits != nullptr, parse_rc_option(option("RAYCAST")));
     const GridWs ws{counts_ws, ny, nx};
-    int group_max = (int)(ws.capacity / (2 * cells));                               // >= 2: the window is at most the grid
-    group_max = group_max > RC_GROUP_MAX ? RC_GROUP_MAX : group_max;
-    uint32_t* set2[2] = {ws.counters, ws.counters + (size_t)group_max * cells};
-    // every call starts with empty boxes and ends with empty counter grids (each finalise pass zeroes what it
-    // reads), so calls are independent of each other; scan_seq is no longer needed and ignored
-    (void)scan_seq;
-    int live_scans = 0;
-    for (int t = 0; t < n_scans; ++t) live_scans += hit_off_host[t + 1] > hit_off_host[t] ? 1 : 0;
-    // one scan with a box from the caller (the live update): the finalise pass walks that box, no slot to clear first
-    const bool window_is_box = live_scans == 1 && box_host && !empty_window;
-    if (!window_is_box && hipMemsetAsync(ws.slots, 0, 3 * sizeof(BBox), st) != hipSuccess) return ICPMI_ERR_HIP;
-    GridDesc g{nx, ny, min_x, min_y, resolution, wx0, wx1, wy0, wy1, wx0, wy0, wx1 - wx0, row_begin, row_end};
-    if (empty_window) { g.wx1 = g.wx0; }                              // nothing is counted; the finalise pass only clips
-    FinArgs fin{};
-    fin.log_odds = log_odds; fin.l_hit = l_hit; fin.l_miss = l_miss; fin.lo32 = (float)lo; fin.hi32 = (float)hi;
-    fin.grid_stride = cells; fin.n_grids = 1; fin.use_window = window_is_box ? 1 : 0;
-    // The tile path needs the caller's box (the tiles of the window are enumerated; a scan's own box, found on the
-    // device, sends the other tiles home at once).  Without a box (a direct caller of the plain entry points, or
-    // non-finite coordinates) the window is the whole grid and the per-beam atomic pass runs instead.
-    // ICPMI_RAYCAST=atomic forces the latter (experiments, and the parity tests of both passes).
-    // A single scan (the live update) also takes the atomic pass: two short launches, 21 us against 32.
-    const char* rc_env = option("RAYCAST");
-    // ... and so does a replay whose box is far larger than a scan's reach (a long trajectory in one call): every scan
-    // would start four workgroups per tile of the box just to find that it does not get there (~1 000 tiles: even).
-    const long long window_tiles = (long long)((wx1 - wx0 + 63) / 64) * ((wy1 - wy0 + 63) / 64);
-    const bool forced_tiles = rc_env && rc_env[0] == 't';
-    const bool tiles_ok = box_host && !empty_window && !(rc_env && rc_env[0] == 'a') && hits &&
-                          ((live_scans > 1 && window_tiles <= 768) || forced_tiles);
-    // One live scan with a box from the caller: the owner pass, a single launch (RAYCAST = owner forces it for any single
-    // scan with a box, atomic / tiles keep the passes above: the parity tests run all three).  It needs no clip of cells
-    // the scan does not touch (full_clip) and 16-bit counts.
-    if (live_scans == 1 && box_host && !empty_window && !full_clip && hits && (!rc_env || rc_env[0] == 'o')) {
-        int s1 = 0;
-        while (hit_off_host[s1 + 1] == hit_off_host[s1]) ++s1;
-        const int nb1 = hit_off_host[s1 + 1] - hit_off_host[s1];
-        const long long tx = (wx1 - wx0 + RT_TILE - 1) / RT_TILE, ty = (wy1 - wy0 + RT_TILE - 1) / RT_TILE;
-        // (every workgroup looks at every beam: beyond a few hundred tiles — a box far larger than a lidar's reach — the two
-        // passes with counters are the cheaper way)
-        if (nb1 > 0 && nb1 <= 65535 && tx * ty <= 320) {
-            ray_owner_kernel<<<RO_NEAR + (int)(tx * ty) * (RT_TILE / RO_FAR) * (RT_TILE / RO_FAR), RO_THREADS, 0, st>>>(g, origins + 2 * (size_t)s1, hits + 2 * (size_t)hit_off_host[s1], nb1,
-                                                                               fin, (int)tx, (int)ty);
-            ICPMI_LAUNCH_CHECK();
-            return ICPMI_OK;
-        }
+    if (!plan.window_is_box && hipMemsetAsync(ws.slots, 0, 3 * sizeof(BBox), st) != hipSuccess) return ICPMI_ERR_HIP;
+    GridDesc g{nx, ny, min_x, min_y, resolution, plan.wx0, plan.wx1, plan.wy0, plan.wy1,
+               plan.wx0, plan.wy0, plan.wx1 - plan.wx0, row_begin, row_end};
+    if (plan.empty_window) g.wx1 = g.wx0;                       // nothing is counted; the finalise pass only clips
+    FinArgs base{};
+    base.log_odds = log_odds; base.l_hit = l_hit; base.l_miss = l_miss; base.lo32 = (float)lo; base.hi32 = (float)hi;
+    base.grid_stride = plan.cells; base.n_grids = 1; base.use_window = plan.window_is_box ? 1 : 0;
+    if (plan.pass == RcPass::owner) {
+        const int s1 = plan.owner_scan;
+        ray_owner_kernel<<<plan.owner_grid, RO_THREADS, 0, st>>>(g, origins + 2 * (size_t)s1, hits + 2 * (size_t)hit_off_host[s1],
+                                                                 plan.owner_beams, base, plan.tiles_x, plan.tiles_y);
+        ICPMI_LAUNCH_CHECK();
+        return ICPMI_OK;
     }
-    TileArgs ta{};
-    ta.tiles_x = (wx1 - wx0 + RT_TILE - 1) / RT_TILE; ta.tiles_y = (wy1 - wy0 + RT_TILE - 1) / RT_TILE;
+    // The replay: the launch that counts group q also finalises group q - 1 (`fin`, from the other set of counter grids)
+    // and, on the tile pass, finds the scan boxes of group q + 1 (`nxt`, built one round ahead for that).
     constexpr int rt_wgs = 1536;     // resident workgroups of the tile pass (6 per CU)
-    bool pending = false;            // a counted group whose finalisation rides on the next launch
-    int64_t q = 0;                   // index of the next group (counter-grid set q&1, box slot q%3)
-    int clip_all = full_clip;
-    auto blocks_of = [](int nb) {
-        const long waves = (long)((nb + ICPMI_WAVE - 1) / ICPMI_WAVE) * RC_SLOTS;
-        return (int)((waves * ICPMI_WAVE + RC_THREADS - 1) / RC_THREADS);
-    };
-    // the group that starts at the first non-empty scan at or after `from`: 1 = built (end = one past its last scan),
-    // 0 = none (the replay ends, or a scan too wide for a group comes first), -1 = bad offsets
-    auto build_group = [&](int from, ScanGroup& gq, int& end) {
-        gq = ScanGroup{};
-        int t = from;
-        while (t < n_scans && hit_off_host[t + 1] == hit_off_host[t]) ++t;
-        end = t;
-        if (t >= n_scans) return 0;
-        while (t < n_scans && gq.n < group_max) {
-            const int nb = hit_off_host[t + 1] - hit_off_host[t];
-            if (nb < 0) return -1;
-            if (nb > 65535) break;
-            if (nb > 0) {
-                gq.nb[gq.n] = nb; gq.origin_row[gq.n] = t; gq.hit_row[gq.n] = hit_off_host[t];
-                gq.first_block[gq.n + 1] = gq.first_block[gq.n] + blocks_of(nb);
-                ++gq.n;
-            }
-            ++t;
-        }
-        end = t;
-        return gq.n > 0 ? 1 : 0;
-    };
     ScanGroup grp{}, nxt{};
-    bool have_nxt = false;
-    int nxt_end = 0;
-    int s = 0;
-    while (s < n_scans) {
-        const int nb0 = hit_off_host[s + 1] - hit_off_host[s];
-        if (nb0 < 0) return ICPMI_ERR_ARG;
-        if (nb0 == 0) { ++s; continue; }                        // mapping.py:113-114: silent no-op, no clip
+    int end = 0, nxt_end = 0;
+    bool have_nxt = false, pending = false;   // pending: a counted group whose finalisation rides on the next launch
+    FinArgs fin = base;
+    int clip_all = full_clip, s = 0;
+    for (int64_t q = 0;; ++q) {
+        const bool boxes_ready = have_nxt;
+        int r = RC_GROUP_BUILT;
+        if (have_nxt) { grp = nxt; end = nxt_end; have_nxt = false; }
+        else r = build_group(hit_off_host, n_scans, plan.group_max, s, grp, end);
+        if (r == RC_GROUP_BAD) return ICPMI_ERR_ARG;
+        if (r == RC_GROUP_NONE && end >= n_scans) break;
         if (!hits) return ICPMI_ERR_ARG;
-        uint32_t* counts = set2[q & 1];
-        BBox* cur = ws.slots + (q % 3);
-        if (nb0 <= 65535) {
-            // a group: the following scans too, while they fit a 16-bit counter (empty scans are skipped over)
-            int t = s;
-            bool boxes_ready = false;
-            if (have_nxt && nxt.origin_row[0] == s) { grp = nxt; t = nxt_end; boxes_ready = true; }
-            else if (build_group(s, grp, t) < 0) return ICPMI_ERR_ARG;
-            have_nxt = false;
-            const int blocks = grp.first_block[grp.n];
-            if (tiles_ok) {
-                ta.boxes = nullptr;
-                if (live_scans > 1) {                               // several scans share the window: each one's own box
-                    ScanBox* boxes = ws.box_sets[q & 1];
-                    if (!boxes_ready) ray_scan_boxes_kernel<<<grp.n, RT_THREADS, 0, st>>>(g, origins, hits, grp, boxes);
-                    ta.boxes = boxes;
-                    const int r = build_group(t, nxt, nxt_end);     // the boxes of the group after this one ride on this launch
-                    if (r < 0) return ICPMI_ERR_ARG;
-                    have_nxt = r > 0;
-                }
-                const int n_items = grp.n * rt_blocks_per_scan(ta.tiles_x * ta.tiles_y);
-                const int n_tiles = n_items < rt_wgs ? n_items : rt_wgs;
-                const int n_fin = pending ? RC_FIN_BLOCKS : 0;
-                if (!have_nxt) nxt.n = 0;
-                ray_tile_step_kernel<<<n_tiles + n_fin + nxt.n, RT_THREADS, 0, st>>>(g, origins, hits, grp, counts, cells, cur, ta, n_items, n_tiles, n_fin,
-                                                                                     fin, nxt, ws.box_sets[(q + 1) & 1]);
-            } else if (pending) ray_step_kernel<<<blocks + RC_FIN_BLOCKS, RC_THREADS, 0, st>>>(g, origins, hits, grp, counts, cells, cur, blocks, fin);
-            else ray_count_group_kernel<<<blocks, RC_THREADS, 0, st>>>(g, origins, hits, grp, counts, cells, cur);
-            // this group's finalisation: reads its own grids and slot, frees the slot two groups ahead
-            fin.counts = counts; fin.n_grids = grp.n; fin.bbox = cur; fin.other = ws.slots + ((q + 2) % 3);
-            fin.count_kind = 0; fin.clip = 1; fin.full_clip = clip_all;
-            pending = true;
-            s = t;
-        } else {
-            // more beams than a 16-bit counter holds: hits and misses in two rounds, no pipelining
+        const RcSlots at = rc_slots(ws, plan, q);
+        if (r == RC_GROUP_NONE) {                               // scan `end` is too wide for a group
             if (pending) { ray_finalize_kernel<<<RC_FIN_BLOCKS, RC_THREADS, 0, st>>>(g, fin); pending = false; }
-            const double* h = hits + 2 * (size_t)hit_off_host[s];
-            const double* o = origins + 2 * (size_t)s;
-            const int blocks = blocks_of(nb0);
-            FinArgs w = fin;
-            w.counts = counts; w.n_grids = 1; w.bbox = cur; w.full_clip = 0;
-            ray_count_kernel<<<blocks, RC_THREADS, 0, st>>>(g, o, h, nb0, counts, cur, RC_DO_HITS);
-            w.other = nullptr; w.count_kind = 1; w.clip = 0;
-            ray_finalize_kernel<<<RC_FIN_BLOCKS, RC_THREADS, 0, st>>>(g, w);
-            ray_count_kernel<<<blocks, RC_THREADS, 0, st>>>(g, o, h, nb0, counts, cur, RC_DO_MISS);
-            w.other = ws.slots + ((q + 2) % 3); w.count_kind = 2; w.clip = 1; w.full_clip = clip_all;
-            ray_finalize_kernel<<<RC_FIN_BLOCKS, RC_THREADS, 0, st>>>(g, w);
-            ++s;
+            launch_wide_scan(g, origins + 2 * (size_t)end, hits + 2 * (size_t)hit_off_host[end],
+                             hit_off_host[end + 1] - hit_off_host[end], at, base, clip_all, st);
+            s = end + 1;
+        } else {
+            const int blocks = grp.first_block[grp.n];
+            if (plan.pass == RcPass::tiles) {
+                TileArgs ta{nullptr, plan.tiles_x, plan.tiles_y};
+                if (plan.live_scans > 1) {                      // several scans share the window: each one's own box
+                    if (!boxes_ready) ray_scan_boxes_kernel<<<grp.n, RT_THREADS, 0, st>>>(g, origins, hits, grp, at.boxes);
+                    ta.boxes = at.boxes;
+                    const int rn = build_group(hit_off_host, n_scans, plan.group_max, end, nxt, nxt_end);
+                    if (rn == RC_GROUP_BAD) return ICPMI_ERR_ARG;
+                    have_nxt = rn == RC_GROUP_BUILT;            // (nxt.n is 0 otherwise)
+                }
+                const int n_items = grp.n * rt_blocks_per_scan(plan.tiles_x * plan.tiles_y);
+                const int n_count = n_items < rt_wgs ? n_items : rt_wgs, n_fin = pending ? RC_FIN_BLOCKS : 0;
+                ray_tile_step_kernel<<<n_count + n_fin + nxt.n, RT_THREADS, 0, st>>>(g, origins, hits, grp, at.counts, plan.cells, at.box, ta,
+                                                                                     n_items, n_count, n_fin, fin, nxt, at.next_boxes);
+            } else if (pending) ray_step_kernel<<<blocks + RC_FIN_BLOCKS, RC_THREADS, 0, st>>>(g, origins, hits, grp, at.counts, plan.cells,
+                                                                                               at.box, blocks, fin);
+            else ray_count_group_kernel<<<blocks, RC_THREADS, 0, st>>>(g, origins, hits, grp, at.counts, plan.cells, at.box);
+            fin = fin_args(base, at, grp.n, 0, true, clip_all);
+            pending = true; s = end;
         }
         clip_all = 0;                                           // every cell is inside [lo, hi] after one clipped scan
-        ++q;
         ICPMI_LAUNCH_CHECK();
     }
     if (pending) ray_finalize_kernel<<<RC_FIN_BLOCKS, RC_THREADS, 0, st>>>(g, fin);
