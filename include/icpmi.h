@@ -181,9 +181,10 @@ int icpmi_icp_batch(const double* pts, const int32_t* off_dev, const int32_t* cn
  * the gate is taken (`break  # one closure per scan is enough`), so the ones after it are never computed.  Same call
  * as icpmi_icp_batch (same results), plus: pair b is candidate index_base + b * index_stride (index_base >= 0,
  * index_stride >= 1: a rank of a sharded run passes its rank and the world size); it is ELIGIBLE when
- * search_records == NULL or slot 11 of its rotation-search record (stride 16, icpmi_rotation_search_batch) is below 2
- * (ok, or too few points: the ICP starts from the identity as the reference's does; 2 = capacity: the caller redoes
- * the candidate, 3 = no fine grid), and ACCEPTED when it is eligible, not skipped and its error is < error_accept
+ * search_records == NULL or the status of its rotation-search record (slot ICPMI_RSBREC_STATUS, stride
+ * ICPMI_RSBREC_DOUBLES, icpmi_rotation_search_batch) is below ICPMI_RSB_ST_CAPACITY (ok, or too few points: the ICP
+ * starts from the identity as the reference's does; ICPMI_RSB_ST_CAPACITY: the caller redoes the candidate,
+ * ICPMI_RSB_ST_NO_FINE: no fine grid), and ACCEPTED when it is eligible, not skipped and its error is < error_accept
  * (NaN: never).  A candidate whose index is above that of an accepted one may stop early with status
  * ICPMI_ST_SKIPPED: its record then holds the totals of the steps it applied, `iterations` is their count, and
  * error / delta are those of the last step whose error was taken (the step before, for a candidate stopped between
@@ -263,10 +264,23 @@ int icpmi_rotation_scores(const double* src_c, int32_t n_src, const double* tgt,
  * the caller's (the reference's own NumPy expressions), so the chosen angle is the reference's bit for bit.
  * centred != 0: the source is centred on its mean and shifted to the target's mean (features.py:205-216);
  * else the rows are rotated as they are and shifted by (shift_x, shift_y) (slam.py:138-143).
- * out_record (device, 12 doubles): voxel counts of source and target, mean of the source (2), shift (2), winning
- * coarse index, its score, length of its fine grid, winning fine index, its score, reserved.  np.argmin semantics
- * (first minimum; first NaN if any).  The voxel-filtered clouds stay in the workspace (256 bytes in: source rows,
- * then target rows, counts as int32 at byte 16) for a following icpmi_nn_batch-style refinement. */
+ * out_record (device, ICPMI_RSREC_DOUBLES doubles, slots ICPMI_RSREC_*): voxel counts of source and target, mean of
+ * the source (2), shift (2), winning coarse index, its score, length of its fine grid, winning fine index, its score,
+ * reserved.  np.argmin semantics (first minimum; first NaN if any).  The voxel-filtered clouds stay in the workspace
+ * (ICPMI_RS_WS_CLOUDS bytes in: source rows, then target rows — n_src rows further on; counts as int32 at byte
+ * ICPMI_RS_WS_COUNTS) for a following icpmi_nn_batch-style refinement. */
+#define ICPMI_RSREC_DOUBLES 12
+#define ICPMI_RSREC_NS 0          /* rows of the filtered source                  */
+#define ICPMI_RSREC_NT 1          /* rows of the filtered target                  */
+#define ICPMI_RSREC_MUS 2         /* mean of the source (2; zeros when not centred) */
+#define ICPMI_RSREC_MUT 4         /* shift (2): mean of the target, or the caller's */
+#define ICPMI_RSREC_K 6           /* winning coarse index                         */
+#define ICPMI_RSREC_CSCORE 7      /* its score                                    */
+#define ICPMI_RSREC_NF 8          /* length of its fine grid                      */
+#define ICPMI_RSREC_J 9           /* winning fine index                           */
+#define ICPMI_RSREC_FSCORE 10     /* its score                                    */
+#define ICPMI_RS_WS_COUNTS 16     /* byte offsets into the search workspace       */
+#define ICPMI_RS_WS_CLOUDS 256
 size_t icpmi_rotation_search_workspace_bytes(int32_t n_src, int32_t n_tgt, int32_t n_coarse, int32_t max_fine);
 int icpmi_rotation_search(const double* pts, int32_t n_src, int32_t n_tgt, double voxel_size,
                           const double* coarse_cs, int32_t n_coarse,
@@ -279,8 +293,9 @@ int icpmi_rotation_search(const double* pts, int32_t n_src, int32_t n_tgt, doubl
  * source rotated by the winning angle (NumPy's own (n, 2) @ (2, 2) arithmetic) and placed at (pred_x, pred_y), its
  * nearest target rows, np.percentile(d^2, 80) with linear interpolation, and the mean of (matched - rotated) over the
  * rows at or below it — out4 (device): refined t (2; the predicted position when fewer than 5 rows qualify, slam.py:
- * 175-181), the inlier count, the percentile.  n_src / n_tgt: the RAW row counts passed to the search; n_src <= 2048
- * (ICPMI_ERR_UNSUPPORTED above: refine on the host from the filtered clouds). */
+ * 175-181), the inlier count, the percentile.  n_src / n_tgt: the RAW row counts passed to the search; n_src <=
+ * ICPMI_RSR_MAX_ROWS (ICPMI_ERR_UNSUPPORTED above: refine on the host from the filtered clouds). */
+#define ICPMI_RSR_MAX_ROWS 2048
 size_t icpmi_rotation_refine_workspace_bytes(int32_t n_src);
 int icpmi_rotation_refine(const void* search_workspace, int32_t n_src, int32_t n_tgt, const double* record,
                           const double* coarse_cs, const double* fine_cs, int32_t max_fine,
@@ -293,20 +308,33 @@ int icpmi_rotation_refine(const void* search_workspace, int32_t n_src, int32_t n
  * put in search order; NULL = every cloud).  One chain of launches: voxel filter of every cloud at voxel_size, the
  * means of the filtered clouds, the search order of the targets, then ONE workgroup per pair for both sweeps.  Angle
  * grids as in icpmi_rotation_search (coarse_cs; fine_cs / fine_cnt / max_fine: one fine grid per coarse winner; the
- * caller's NumPy cos / sin; at most 1024 coarse angles and 1024 per fine grid).
+ * caller's NumPy cos / sin; at most ICPMI_RSB_MAX_ANGLES coarse angles and as many per fine grid).
  * Only the arg-min of the coarse scores matters to the reference (features.py:223), so a workgroup bounds every
  * coarse score from below with a distance field of its target (one look-up per row), scores angles exactly — same
  * float64 nearest-neighbour distances as icpmi_rotation_search — in order of that bound, and stops at the first angle
  * whose bound exceeds the best exact score: np.argmin over the scored angles (first minimum) is np.argmin over all.
- * out_records [n_pairs][16]: slots 0..10 as icpmi_rotation_search's record (filtered counts, mean of the source (2),
- * mean of the target (2), winning coarse index, its score, length of its fine grid, winning fine index, its score);
- * 11 status — 0 searched; 1 a filtered cloud has fewer than 5 points (features.py:203-204: identity, zeros, inf);
- * 2 a filtered cloud exceeds the on-chip capacity (not searched: use icpmi_rotation_search); 3 the winner's fine grid
- * is empty (np.argmin raises in the reference); 12, 13 coarse / fine angles scored exactly (diagnostic).
+ * out_records [n_pairs][ICPMI_RSBREC_DOUBLES]: the ICPMI_RSREC_* slots as icpmi_rotation_search's record (filtered
+ * counts, mean of the source (2), mean of the target (2), winning coarse index, its score, length of its fine grid,
+ * winning fine index, its score); ICPMI_RSBREC_STATUS — ICPMI_RSB_ST_OK searched; _FEW a filtered cloud has fewer
+ * than 5 points (features.py:203-204: identity, zeros, inf); _CAPACITY a filtered cloud exceeds the on-chip capacity
+ * (not searched: use icpmi_rotation_search); _NO_FINE the winner's fine grid is empty (np.argmin raises in the
+ * reference); ICPMI_RSBREC_EVALS, _FEVALS coarse / fine angles scored exactly (diagnostic).
  * out_init (optional) [n_pairs][6]: R row-major then t = mu_t - R mu_s (features.py:235-237) — the `init` argument of
- * icpmi_icp_batch, so pre-alignment and ICP chain on one stream with no host round trip; identity for status != 0.
+ * icpmi_icp_batch, so pre-alignment and ICP chain on one stream with no host round trip; identity for a status other
+ * than ICPMI_RSB_ST_OK.
  * max_rows_hint: an upper bound the caller expects for the FILTERED clouds (0: none).  The on-chip copies are sized
- * by min(largest raw cloud, 2048, hint); up to 1024 rows two workgroups share a CU.  A pair beyond it gets status 2. */
+ * by min(largest raw cloud, ICPMI_RSB_MAX_ROWS, hint); up to 1024 rows two workgroups share a CU.  A pair beyond it
+ * gets ICPMI_RSB_ST_CAPACITY. */
+#define ICPMI_RSBREC_DOUBLES 16
+#define ICPMI_RSBREC_STATUS 11
+#define ICPMI_RSBREC_EVALS 12
+#define ICPMI_RSBREC_FEVALS 13
+#define ICPMI_RSB_ST_OK 0
+#define ICPMI_RSB_ST_FEW 1
+#define ICPMI_RSB_ST_CAPACITY 2
+#define ICPMI_RSB_ST_NO_FINE 3
+#define ICPMI_RSB_MAX_ANGLES 1024 /* coarse angles, and angles per fine grid      */
+#define ICPMI_RSB_MAX_ROWS 2048   /* rows of a filtered cloud a workgroup holds   */
 size_t icpmi_rotation_search_batch_workspace_bytes(int32_t total_rows, int32_t n_clouds, int32_t max_n);
 int icpmi_rotation_search_batch(const double* pts, const int32_t* off_dev, const int32_t* off_host, int32_t n_clouds,
                                 const int32_t* tgt_ids, int32_t n_tgt_ids,
@@ -319,9 +347,31 @@ int icpmi_rotation_search_batch(const double* pts, const int32_t* off_dev, const
 /* ---- feature-based pre-alignment, utilities/features.py:35-160, 247-315 ------------------------------------------
  * The five stages of feature_based_alignment, each on a cloud set of 2-D clouds (pts / off_dev / cnt_dev as above;
  * cloud_ids[n_sel]: the clouds to process, NULL = clouds 0..n_sel-1), one workgroup per cloud or per pair with the cloud
- * in LDS: at most 2048 valid rows per cloud (a larger cloud is left alone: no output, 0 keypoints), k <= 31, at most 256
- * keypoints per cloud.  Per-cloud tables are indexed by the cloud's number in the set.
- *
+ * in LDS: at most ICPMI_FT_MAX_ROWS valid rows per cloud (a larger cloud is left alone: no output, 0 keypoints), k <= 31,
+ * at most ICPMI_FT_MAX_KP keypoints per cloud.  Per-cloud tables are indexed by the cloud's number in the set.
+ * A pair's record is ICPMI_FTREC_DOUBLES doubles with the slots ICPMI_FTREC_* and a status ICPMI_FT_ST_*. */
+#define ICPMI_FT_MAX_ROWS 2048
+#define ICPMI_FT_MAX_KP 256
+#define ICPMI_FT_DESC_STRIDE 32   /* doubles per descriptor row (k <= 31)         */
+#define ICPMI_FTREC_DOUBLES 16
+#define ICPMI_FTREC_NS 0          /* rows of the filtered source                  */
+#define ICPMI_FTREC_NT 1          /* rows of the filtered target                  */
+#define ICPMI_FTREC_KPS 2         /* keypoints of the source                      */
+#define ICPMI_FTREC_KPT 3         /* keypoints of the target                      */
+#define ICPMI_FTREC_MATCHES 4
+#define ICPMI_FTREC_INLIERS 5
+#define ICPMI_FTREC_R 6           /* R row-major (4)                              */
+#define ICPMI_FTREC_T 10          /* t (2)                                        */
+#define ICPMI_FTREC_STATUS 12
+#define ICPMI_FTREC_BEST 13       /* index of the winning hypothesis (-1: none)   */
+#define ICPMI_FT_ST_OK 0          /* aligned                                      */
+#define ICPMI_FT_ST_FEW_ROWS 1    /* a filtered cloud has fewer than 10 rows, features.py:281-282 */
+#define ICPMI_FT_ST_CAPACITY 2    /* a filtered cloud exceeds ICPMI_FT_MAX_ROWS (not aligned: the caller falls back) */
+#define ICPMI_FT_ST_FEW_KP 3      /* fewer than 2 keypoints, features.py:290-291  */
+#define ICPMI_FT_ST_FEW_MATCHES 4 /* fewer than 2 matches, features.py:299-300    */
+#define ICPMI_FT_ST_DESC_LEN 5    /* the two clouds' descriptors differ in length (NumPy raises in the reference) */
+
+/*
  * compute_curvature, features.py:35-54.  out_curvature: one double per row (row layout of pts).  The k+1 nearest rows
  * (k clamped to n-1, the lower row on equal distances), np.cov of them, eigenvalues in closed form,
  * ev[0] / (ev[-1] + 1e-10); fewer than 3 neighbours: 0.  The neighbours are summed in ascending row order (the reference
@@ -340,8 +390,9 @@ int icpmi_feature_keypoints_batch(const double* pts, const int32_t* off_dev, con
                                   const int32_t* order, int32_t top_n, double min_dist, int32_t* out_kp,
                                   int32_t* out_kp_cnt, int32_t kp_stride, void* stream);
 
-/* compute_descriptors, features.py:76-87.  out_desc[(c * kp_stride + s) * 32 + q]: distance from keypoint s of cloud c
- * to its (q+1)-th nearest other row, ascending, q < out_desc_len[c] = min(k, n-1) (the rest of the 32 is zero): exact
+/* compute_descriptors, features.py:76-87.  out_desc[(c * kp_stride + s) * ICPMI_FT_DESC_STRIDE + q]: distance from
+ * keypoint s of cloud c to its (q+1)-th nearest other row, ascending, q < out_desc_len[c] = min(k, n-1) (the rest of
+ * the row is zero): exact
  * neighbour distances with IEEE sqrt, as KDTree.query returns them. */
 int icpmi_feature_descriptors_batch(const double* pts, const int32_t* off_dev, const int32_t* cnt_dev,
                                     const int32_t* cloud_ids, int32_t n_sel, const int32_t* kp, const int32_t* kp_cnt,
@@ -364,8 +415,8 @@ int icpmi_feature_match_batch(const double* desc, const int32_t* desc_len, const
  * reference's SVD gives), error of every match, inliers err < inlier_thresh; the first hypothesis with the largest
  * count wins, a count of 0 never replaces the identity; then the refit on the inliers of the best when there are at
  * least 2.  A hypothesis with an index outside [0, n) or two equal indices counts 0.
- * out_records [n_pairs][16]: slots 4 matches, 5 inliers, 6..9 R row-major, 10..11 t, 12 status (0, or 4: fewer than 2
- * matches — identity, zeros, 0), 13 index of the winning hypothesis (-1: none); the other slots 0.
+ * out_records [n_pairs][ICPMI_FTREC_DOUBLES]: ICPMI_FTREC_MATCHES, _INLIERS, _R (row-major), _T, _STATUS (ICPMI_FT_ST_OK,
+ * or ICPMI_FT_ST_FEW_MATCHES: fewer than 2 matches — identity, zeros, 0), _BEST (-1: none); the other slots 0.
  * out_counts (optional) [n_pairs][n_iter]: inliers of every hypothesis. */
 int icpmi_feature_ransac_batch(const double* pts, const int32_t* off_dev, const int32_t* cnt_dev, const int32_t* kp,
                                const int32_t* kp_cnt, int32_t kp_stride, const int32_t* pair_src, const int32_t* pair_tgt,
@@ -380,12 +431,9 @@ int icpmi_feature_ransac_batch(const double* pts, const int32_t* off_dev, const 
  * filter (slam.py:69-71; pair_src_host, the host mirror of pair_src, is then required).  init_out (optional)
  * [n_pairs][6]: R_feat @ R_init, t_init @ R_feat.T + t_feat when the pair has at least min_inliers inliers, else init_in
  * (the identity without one) (slam.py:83-88) — the `init` of icpmi_icp_batch.
- * out_records [n_pairs][16]: 0, 1 filtered rows of source and target; 2, 3 their keypoints; 4 matches; 5 inliers; 6..9 R;
- * 10, 11 t; 12 status; 13 winning hypothesis.  Status: 0 aligned; 1 a filtered cloud has fewer than 10 rows
- * (features.py:281-282); 2 a filtered cloud exceeds the 2048 rows the kernels hold on chip (not aligned: the caller falls
- * back); 3 fewer than 2 keypoints (features.py:290-291); 4 fewer than 2 matches (features.py:299-300); 5 the two
- * clouds' descriptors differ in length (k_descriptor > rows - 1 of one of them: NumPy raises in the reference).  Every
- * status but 0 leaves identity, zeros, 0 inliers. */
+ * out_records [n_pairs][ICPMI_FTREC_DOUBLES]: every ICPMI_FTREC_* slot (filtered rows of source and target, their
+ * keypoints, matches, inliers, R, t, status, winning hypothesis).  Status ICPMI_FT_ST_*, listed above (_DESC_LEN:
+ * k_descriptor > rows - 1 of one of the clouds).  Every status but ICPMI_FT_ST_OK leaves identity, zeros, 0 inliers. */
 size_t icpmi_feature_align_batch_workspace_bytes(int32_t total_rows, int32_t n_clouds, int32_t max_n, int32_t n_pairs,
                                                  int32_t top_n, int32_t with_init);
 int icpmi_feature_align_batch(const double* pts, const int32_t* off_dev, const int32_t* off_host, int32_t n_clouds,

@@ -39,8 +39,8 @@ struct SideLock {
 
 // Gate of icpmi_icp_batch_gated (icp.hip): pair b has the gate index base + b * stride; a pair whose index is above the
 // value of *hint it reads may stop (ICPMI_ST_SKIPPED); a finished, eligible pair with err < accept lowers *hint to its
-// index.  Eligible: search == nullptr, or slot 11 of its rotation-search record (stride 16) below 2 (ok, or too few
-// points: the ICP then starts from the identity, as the reference's does).
+// index.  Eligible: search == nullptr, or the status of its rotation-search record (ICPMI_RSBREC_STATUS) below
+// ICPMI_RSB_ST_CAPACITY (ok, or too few points: the ICP then starts from the identity, as the reference's does).
 struct IcpGate {
     int32_t* hint;
     const double* search;
@@ -48,7 +48,7 @@ struct IcpGate {
     int base, stride;
 };
 __device__ __forceinline__ bool gate_eligible(const double* search, int b) {
-    return !search || search[(size_t)b * 16 + 11] < 2.0;
+    return !search || search[(size_t)b * ICPMI_RSBREC_DOUBLES + ICPMI_RSBREC_STATUS] < (double)ICPMI_RSB_ST_CAPACITY;
 }
 
 // The fused 2-D ICP on prepared targets (icp2.hip), called by icpmi_icp_batch (icp.hip) when a prepared buffer is given and
@@ -60,6 +60,18 @@ int launch_icp2(const double* pts, const int32_t* off, const int32_t* cnt, const
 
 // ── carving a caller's buffer (host) ─────────────────────────────────────────
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Rows of the clouds of a set, from the host mirror of its offsets: false when a cloud has a negative row count.
+inline bool cloud_rows(const int32_t* off_host, int n_clouds, int& max_n, int& total_rows) {
+    max_n = 0;
+    for (int c = 0; c < n_clouds; ++c) {
+        const int rows = off_host[c + 1] - off_host[c];
+        if (rows < 0) return false;
+        max_n = rows > max_n ? rows : max_n;
+    }
+    total_rows = off_host[n_clouds];
+    return true;
+}
 
 // Bump pointer over a caller's buffer.  take<T>(bytes) is the current position, and moves on by `bytes` rounded up to
 // 256; packed<T>(bytes) moves on by exactly `bytes` (the layouts that keep no gaps).  Every layout is described ONCE, by a
@@ -127,6 +139,19 @@ __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, ICPMI_WAVE));
     return v;
+}
+
+// (value, index) pairs: the other pair replaces this one when its value is better — `better` is a strict order, `<` for
+// an arg-min, `>` for an arg-max — or equal with the lower index: the FIRST of equal values wins, as np.argmin's scan.
+template <class T, class Better>
+__device__ __forceinline__ void take_first_best(T& v, int& i, T ov, int oi, Better better) {
+    if (better(ov, v) || (ov == v && oi < i)) { v = ov; i = oi; }
+}
+// ... over the wave (butterfly): every lane gets the wave's pair
+template <class T, class Better>
+__device__ __forceinline__ void wave_first_best(T& v, int& i, Better better) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) take_first_best(v, i, __shfl_xor(v, o, ICPMI_WAVE), __shfl_xor(i, o, ICPMI_WAVE), better);
 }
 
 // Workgroup-wide sum of NV doubles per thread; the result is in every thread.

@@ -22,16 +22,12 @@
 
 namespace icpmi {
 
-constexpr int FT_MAX_ROWS = 2048;       // rows of a cloud the stage kernels hold in LDS
-constexpr int FT_MAX_KP = 256;          // keypoints per cloud (top_n), matches per pair
-constexpr int FT_DESC_STRIDE = 32;      // doubles per descriptor row (k <= 31)
+constexpr int FT_MAX_ROWS = ICPMI_FT_MAX_ROWS;          // rows of a cloud the stage kernels hold in LDS
+constexpr int FT_MAX_KP = ICPMI_FT_MAX_KP;              // keypoints per cloud (top_n), matches per pair
+constexpr int FT_DESC_STRIDE = ICPMI_FT_DESC_STRIDE;    // doubles per descriptor row (k <= 31)
 constexpr int FT_MAX_K = 31;
 constexpr int FT_THREADS = 256;
-constexpr int FT_REC_DOUBLES = 16;
-// record slots (include/icpmi.h, icpmi_feature_align_batch)
-constexpr int FTREC_NS = 0, FTREC_NT = 1, FTREC_KPS = 2, FTREC_KPT = 3, FTREC_MATCHES = 4, FTREC_INLIERS = 5, FTREC_R = 6,
-              FTREC_T = 10, FTREC_STATUS = 12, FTREC_BEST = 13;
-constexpr int FT_ST_OK = 0, FT_ST_FEW_ROWS = 1, FT_ST_CAPACITY = 2, FT_ST_FEW_KP = 3, FT_ST_FEW_MATCHES = 4, FT_ST_DESC_LEN = 5;
+// (record slots and statuses: ICPMI_FTREC_*, ICPMI_FT_ST_*, include/icpmi.h)
 
 // the cloud of a workgroup: its rows in LDS, and the identity map the (distance, row) lists break ties with
 struct FtCloud {
@@ -310,7 +306,7 @@ __global__ __launch_bounds__(FT_THREADS) void ft_ransac_kernel(const double* __r
     __shared__ int red_cnt[FT_THREADS / ICPMI_WAVE], red_idx[FT_THREADS / ICPMI_WAVE], bad;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int sc = pair_src[b], tc = pair_tgt[b];
-    double* rec = records + (size_t)b * FT_REC_DOUBLES;
+    double* rec = records + (size_t)b * ICPMI_FTREC_DOUBLES;
     int32_t* counts = out_counts ? out_counts + (size_t)b * n_iter : nullptr;
     int n = min(min(match_cnt[b], kp_stride), FT_MAX_KP);
     if (tid == 0) bad = 0;
@@ -335,9 +331,9 @@ __global__ __launch_bounds__(FT_THREADS) void ft_ransac_kernel(const double* __r
     if (n < 2) {                                                    // features.py:130-131 (uniform per workgroup)
         for (int h = tid; counts && h < n_iter; h += FT_THREADS) counts[h] = 0;
         if (tid == 0) {
-            for (int q = 0; q < FT_REC_DOUBLES; ++q) rec[q] = 0.0;
-            rec[FTREC_MATCHES] = (double)n; rec[FTREC_R] = 1.0; rec[FTREC_R + 3] = 1.0;
-            rec[FTREC_STATUS] = (double)FT_ST_FEW_MATCHES; rec[FTREC_BEST] = -1.0;
+            for (int q = 0; q < ICPMI_FTREC_DOUBLES; ++q) rec[q] = 0.0;
+            rec[ICPMI_FTREC_MATCHES] = (double)n; rec[ICPMI_FTREC_R] = 1.0; rec[ICPMI_FTREC_R + 3] = 1.0;
+            rec[ICPMI_FTREC_STATUS] = (double)ICPMI_FT_ST_FEW_MATCHES; rec[ICPMI_FTREC_BEST] = -1.0;
         }
         return;
     }
@@ -353,17 +349,13 @@ __global__ __launch_bounds__(FT_THREADS) void ft_ransac_kernel(const double* __r
         if (c > bc) { bc = c; bh = h; }                             // ascending h per thread: the first of equal counts stays
     }
     // the first hypothesis with the largest count, features.py:148 (strict >)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const int oc = __shfl_xor(bc, o, ICPMI_WAVE), oh = __shfl_xor(bh, o, ICPMI_WAVE);
-        if (oc > bc || (oc == bc && oh < bh)) { bc = oc; bh = oh; }
-    }
+    const auto more = [](int a, int b) { return a > b; };
+    wave_first_best(bc, bh, more);
     if (lane_id() == 0) { red_cnt[wave_id()] = bc; red_idx[wave_id()] = bh; }
     __syncthreads();
     if (wave_id() != 0) return;                                     // the refit is one wave's work
     bc = red_cnt[0]; bh = red_idx[0];
-    for (int w = 1; w < FT_THREADS / ICPMI_WAVE; ++w)
-        if (red_cnt[w] > bc || (red_cnt[w] == bc && red_idx[w] < bh)) { bc = red_cnt[w]; bh = red_idx[w]; }
+    for (int w = 1; w < FT_THREADS / ICPMI_WAVE; ++w) take_first_best(bc, bh, red_cnt[w], red_idx[w], more);
     FtRigid g;
     g.r[0] = 1.0; g.r[1] = 0.0; g.r[2] = 0.0; g.r[3] = 1.0; g.tx = 0.0; g.ty = 0.0;
     int inl = 0;
@@ -395,11 +387,11 @@ __global__ __launch_bounds__(FT_THREADS) void ft_ransac_kernel(const double* __r
         }
     }
     if (lane_id() == 0) {
-        for (int q = 0; q < FT_REC_DOUBLES; ++q) rec[q] = 0.0;
-        rec[FTREC_MATCHES] = (double)n; rec[FTREC_INLIERS] = (double)inl;
-        rec[FTREC_R] = g.r[0]; rec[FTREC_R + 1] = g.r[1]; rec[FTREC_R + 2] = g.r[2]; rec[FTREC_R + 3] = g.r[3];
-        rec[FTREC_T] = g.tx; rec[FTREC_T + 1] = g.ty;
-        rec[FTREC_STATUS] = (double)FT_ST_OK; rec[FTREC_BEST] = bc > 0 ? (double)bh : -1.0;
+        for (int q = 0; q < ICPMI_FTREC_DOUBLES; ++q) rec[q] = 0.0;
+        rec[ICPMI_FTREC_MATCHES] = (double)n; rec[ICPMI_FTREC_INLIERS] = (double)inl;
+        rec[ICPMI_FTREC_R] = g.r[0]; rec[ICPMI_FTREC_R + 1] = g.r[1]; rec[ICPMI_FTREC_R + 2] = g.r[2]; rec[ICPMI_FTREC_R + 3] = g.r[3];
+        rec[ICPMI_FTREC_T] = g.tx; rec[ICPMI_FTREC_T + 1] = g.ty;
+        rec[ICPMI_FTREC_STATUS] = (double)ICPMI_FT_ST_OK; rec[ICPMI_FTREC_BEST] = bc > 0 ? (double)bh : -1.0;
     }
 }
 
@@ -455,29 +447,29 @@ __global__ void ft_finish_kernel(const int32_t* __restrict__ work_off, const int
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= n_pairs) return;
     const int sc = work_src[b], tc = pair_tgt[b];
-    double* rec = records + (size_t)b * FT_REC_DOUBLES;
+    double* rec = records + (size_t)b * ICPMI_FTREC_DOUBLES;
     const int ns = cnt[sc], nt = cnt[tc];
-    int status = (int)rec[FTREC_STATUS];                            // the RANSAC kernel's: ok, or fewer than 2 matches
-    if (ns > FT_MAX_ROWS || nt > FT_MAX_ROWS || ns < 0 || nt < 0) status = FT_ST_CAPACITY;
-    else if (ns < 10 || nt < 10) status = FT_ST_FEW_ROWS;           // features.py:281-282
-    else if (kp_cnt[sc] < 2 || kp_cnt[tc] < 2) status = FT_ST_FEW_KP;   // features.py:290-291
-    else if (desc_len[sc] != desc_len[tc]) status = FT_ST_DESC_LEN;
-    rec[FTREC_NS] = (double)ns; rec[FTREC_NT] = (double)nt;
-    const bool looked = status != FT_ST_CAPACITY && status != FT_ST_FEW_ROWS;      // else the reference never extracts keypoints
-    rec[FTREC_KPS] = looked ? (double)kp_cnt[sc] : 0.0; rec[FTREC_KPT] = looked ? (double)kp_cnt[tc] : 0.0;
-    if (status != FT_ST_OK) {                                       // identity, zeros, 0 inliers
-        if (status != FT_ST_FEW_MATCHES) rec[FTREC_MATCHES] = 0.0;
-        rec[FTREC_INLIERS] = 0.0; rec[FTREC_R] = 1.0; rec[FTREC_R + 1] = 0.0; rec[FTREC_R + 2] = 0.0; rec[FTREC_R + 3] = 1.0;
-        rec[FTREC_T] = 0.0; rec[FTREC_T + 1] = 0.0; rec[FTREC_BEST] = -1.0;
+    int status = (int)rec[ICPMI_FTREC_STATUS];                            // the RANSAC kernel's: ok, or fewer than 2 matches
+    if (ns > FT_MAX_ROWS || nt > FT_MAX_ROWS || ns < 0 || nt < 0) status = ICPMI_FT_ST_CAPACITY;
+    else if (ns < 10 || nt < 10) status = ICPMI_FT_ST_FEW_ROWS;           // features.py:281-282
+    else if (kp_cnt[sc] < 2 || kp_cnt[tc] < 2) status = ICPMI_FT_ST_FEW_KP;   // features.py:290-291
+    else if (desc_len[sc] != desc_len[tc]) status = ICPMI_FT_ST_DESC_LEN;
+    rec[ICPMI_FTREC_NS] = (double)ns; rec[ICPMI_FTREC_NT] = (double)nt;
+    const bool looked = status != ICPMI_FT_ST_CAPACITY && status != ICPMI_FT_ST_FEW_ROWS;      // else the reference never extracts keypoints
+    rec[ICPMI_FTREC_KPS] = looked ? (double)kp_cnt[sc] : 0.0; rec[ICPMI_FTREC_KPT] = looked ? (double)kp_cnt[tc] : 0.0;
+    if (status != ICPMI_FT_ST_OK) {                                       // identity, zeros, 0 inliers
+        if (status != ICPMI_FT_ST_FEW_MATCHES) rec[ICPMI_FTREC_MATCHES] = 0.0;
+        rec[ICPMI_FTREC_INLIERS] = 0.0; rec[ICPMI_FTREC_R] = 1.0; rec[ICPMI_FTREC_R + 1] = 0.0; rec[ICPMI_FTREC_R + 2] = 0.0; rec[ICPMI_FTREC_R + 3] = 1.0;
+        rec[ICPMI_FTREC_T] = 0.0; rec[ICPMI_FTREC_T + 1] = 0.0; rec[ICPMI_FTREC_BEST] = -1.0;
     }
-    rec[FTREC_STATUS] = (double)status;
+    rec[ICPMI_FTREC_STATUS] = (double)status;
     if (!init_out) return;
     double o[6] = {1.0, 0.0, 0.0, 1.0, 0.0, 0.0};
     if (init_in)
         for (int q = 0; q < 6; ++q) o[q] = init_in[(size_t)b * 6 + q];
-    if (status == FT_ST_OK && (int)rec[FTREC_INLIERS] >= min_inliers) {
-        const double f0 = rec[FTREC_R], f1 = rec[FTREC_R + 1], f2 = rec[FTREC_R + 2], f3 = rec[FTREC_R + 3];
-        const double tx = rec[FTREC_T], ty = rec[FTREC_T + 1];
+    if (status == ICPMI_FT_ST_OK && (int)rec[ICPMI_FTREC_INLIERS] >= min_inliers) {
+        const double f0 = rec[ICPMI_FTREC_R], f1 = rec[ICPMI_FTREC_R + 1], f2 = rec[ICPMI_FTREC_R + 2], f3 = rec[ICPMI_FTREC_R + 3];
+        const double tx = rec[ICPMI_FTREC_T], ty = rec[ICPMI_FTREC_T + 1];
         if (init_in) {                                              // R_feat @ R_init, t_init @ R_feat.T + t_feat (slam.py:85-86)
             const double i0 = o[0], i1 = o[1], i2 = o[2], i3 = o[3], ix = o[4], iy = o[5];
             o[0] = __builtin_fma(f1, i2, f0 * i0); o[1] = __builtin_fma(f1, i3, f0 * i1);
@@ -628,13 +620,8 @@ extern "C" int icpmi_feature_align_batch(const double* pts, const int32_t* off_d
     if (!(voxel_size > 0.0)) return ICPMI_ERR_ARG;
     if (k_curvature > FT_MAX_K || k_descriptor > FT_MAX_K || top_n > FT_MAX_KP) return ICPMI_ERR_UNSUPPORTED;
     if (n_pairs == 0) return ICPMI_OK;
-    int max_n = 0;
-    for (int c = 0; c < n_clouds; ++c) {
-        const int rows = off_host[c + 1] - off_host[c];
-        if (rows < 0) return ICPMI_ERR_ARG;
-        max_n = rows > max_n ? rows : max_n;
-    }
-    const int total_rows = off_host[n_clouds];
+    int max_n, total_rows;
+    if (!cloud_rows(off_host, n_clouds, max_n, total_rows)) return ICPMI_ERR_ARG;
     const FtPlan plan = plan_features(n_clouds, n_pairs, top_n, init_in != nullptr);
     const FtWs w{workspace, total_rows, n_clouds, max_n, n_pairs, plan.kp_stride, plan.with_init ? 1 : 0};
     if (workspace_bytes < w.bytes) return ICPMI_ERR_WORKSPACE;

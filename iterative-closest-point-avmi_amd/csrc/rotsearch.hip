@@ -18,29 +18,36 @@ constexpr int RS_THREADS = 256;
 constexpr int RS_TILE_DOUBLES = 4096;                         // 32 KiB: 2048 target points per tile
 constexpr int RS_TILE_POINTS = (RS_TILE_DOUBLES / 2) / NN_CHUNK * NN_CHUNK;
 
-__global__ __launch_bounds__(RS_THREADS) void rotation_scores_kernel(
-    const double* __restrict__ src_c, int n, const double* __restrict__ tgt, int m,
-    const double* __restrict__ cs, double shift_x, double shift_y, double* __restrict__ scores) {
-    __shared__ __attribute__((aligned(16))) double tile[RS_TILE_DOUBLES];
-    __shared__ double red[block_sum_doubles<1>()];
-    block_sum_init(red, block_sum_doubles<1>());
-    const int a = blockIdx.x;
-    const double c = cs[2 * a], s = cs[2 * a + 1];            // R = [[c, -s], [s, c]], features.py:214-215
+// nearest target of the query p over the m rows of tgt, a tile at a time (every thread of the workgroup calls it: two
+// barriers per tile): best = squared distance, bestj = row, the lowest on ties
+__device__ __forceinline__ void rs_nearest_tiled(const double* __restrict__ tgt, int m, double* tile, const double (&p)[1][2],
+                                                 double (&best)[1], int (&bestj)[1]) {
+    best[0] = __builtin_inf();
+    bestj[0] = 0;
+    for (int t0 = 0; t0 < m; t0 += RS_TILE_POINTS) {
+        const int cnt = min(RS_TILE_POINTS, m - t0);
+        __syncthreads();
+        const int padded = stage_targets<2>(tgt + (size_t)t0 * 2, cnt, tile);
+        __syncthreads();
+        nn_scan_tile<2, 1>(tile, padded, t0, p, best, bestj);
+    }
+}
+
+// score of one angle by a workgroup of RS_THREADS (the value is in every thread): the n rows of src less (mux, muy) —
+// +0.0 for rows that are centred already: x - 0.0 is x bit for bit, -0.0 and NaN included — rotated by (c, s), shifted,
+// each to its nearest of the m targets
+__device__ __forceinline__ double rs_score_angle(const double* __restrict__ src, double mux, double muy, double c, double s,
+                                                 double shift_x, double shift_y, int n, const double* __restrict__ tgt, int m,
+                                                 double* tile, double* red) {
     double acc[1] = {0.0};
     for (int first = 0; first < n; first += RS_THREADS) {     // uniform trip count
         const int i = first + threadIdx.x;
         const int ii = i < n ? i : n - 1;
-        const double x = src_c[2 * ii], y = src_c[2 * ii + 1];
-        double p[1][2] = {{(x * c + y * -s) + shift_x, (x * s + y * c) + shift_y}};   // src_c @ R.T + shift, features.py:216
-        double best[1] = {__builtin_inf()};
-        int bestj[1] = {0};
-        for (int t0 = 0; t0 < m; t0 += RS_TILE_POINTS) {
-            const int cnt = min(RS_TILE_POINTS, m - t0);
-            __syncthreads();
-            const int padded = stage_targets<2>(tgt + (size_t)t0 * 2, cnt, tile);
-            __syncthreads();
-            nn_scan_tile<2, 1>(tile, padded, t0, p, best, bestj);
-        }
+        const double x = src[2 * ii] - mux, y = src[2 * ii + 1] - muy;               // src - mu_s, features.py:207
+        const double p[1][2] = {{(x * c + y * -s) + shift_x, (x * s + y * c) + shift_y}};   // src_c @ R.T + shift, features.py:216
+        double best[1];
+        int bestj[1];
+        rs_nearest_tiled(tgt, m, tile, p, best, bestj);
         if (i < n) {
             const double d = sqrt(best[0]);                   // KDTree distance ...
             acc[0] += d * d;                                  // ... squared, features.py:218
@@ -48,18 +55,28 @@ __global__ __launch_bounds__(RS_THREADS) void rotation_scores_kernel(
     }
     __syncthreads();
     block_sum<1, RS_THREADS / ICPMI_WAVE>(acc, red);
-    if (threadIdx.x == 0) scores[a] = acc[0] / (double)n;
+    return acc[0] / (double)n;
+}
+
+__global__ __launch_bounds__(RS_THREADS) void rotation_scores_kernel(
+    const double* __restrict__ src_c, int n, const double* __restrict__ tgt, int m,
+    const double* __restrict__ cs, double shift_x, double shift_y, double* __restrict__ scores) {
+    __shared__ __attribute__((aligned(16))) double tile[RS_TILE_DOUBLES];
+    __shared__ double red[block_sum_doubles<1>()];
+    block_sum_init(red, block_sum_doubles<1>());
+    const int a = blockIdx.x;                                 // R = [[c, -s], [s, c]], features.py:214-215
+    const double score = rs_score_angle(src_c, 0.0, 0.0, cs[2 * a], cs[2 * a + 1], shift_x, shift_y, n, tgt, m, tile, red);
+    if (threadIdx.x == 0) scores[a] = score;
 }
 
 
 // ── the whole search on the device (icpmi_rotation_search) ───────────────────────────────────────────
 // What the drop-in `rotation_search` used to do with five host round trips (two voxel filters, their means, the
-// coarse sweep, its arg-min, the fine sweep) as one chain of launches; only a 12-double record returns.
+// coarse sweep, its arg-min, the fine sweep) as one chain of launches; only the record returns.
 // The angle grids stay the caller's: cos / sin of every coarse angle and of every fine grid that can follow
 // (one row per coarse winner) are computed with the reference's own NumPy calls and cached on the device, so
 // the chosen angle — hence R and t — is the reference's bit for bit.
-constexpr int RSREC_NS = 0, RSREC_NT = 1, RSREC_MUS = 2, RSREC_MUT = 4, RSREC_K = 6, RSREC_CSCORE = 7, RSREC_NF = 8,
-              RSREC_J = 9, RSREC_FSCORE = 10, RSREC_DOUBLES = 12;
+// (record slots: ICPMI_RSREC_*, include/icpmi.h)
 
 __global__ void rs_offsets_kernel(int32_t* off, int n_src, int n_tgt) {
     off[0] = 0; off[1] = n_src; off[2] = n_src + n_tgt;
@@ -67,24 +84,21 @@ __global__ void rs_offsets_kernel(int32_t* off, int n_src, int n_tgt) {
 
 // np.mean(cloud, axis=0) of a C-contiguous (n, 2) array adds the rows one after the other (the reduction runs
 // along the slow axis: no pairwise summation) and divides by n: one lane per (cloud, column).
-// Two waves, one per cloud: the wave copies 256 rows at a time into LDS with coalesced loads (the chain of
-// dependent adds then never waits for HBM) and its lanes 0 and 1 add the two columns in row order.
+// A wave per cloud: it copies 256 rows at a time into LDS with coalesced loads (the chain of dependent adds then never
+// waits for HBM) and its lanes 0 and 1 add the two columns in row order.
 constexpr int RS_MEAN_ROWS = 256;
-__global__ __launch_bounds__(2 * ICPMI_WAVE) void rs_means_kernel(const double* __restrict__ vox, const int32_t* __restrict__ off,
-                                                                 const int32_t* __restrict__ cnt, int centred, double shift_x,
-                                                                 double shift_y, double* __restrict__ rec) {
-    __shared__ double2 rows[2][RS_MEAN_ROWS];
-    const int c = wave_id(), lane = lane_id(), n = cnt[c];
-    const double2* p = reinterpret_cast<const double2*>(vox + (size_t)off[c] * 2);
+// in-order sum of column `lane` (lanes 0 and 1; the other lanes get 0) of the n rows at p, through the wave's buffer
+__device__ __forceinline__ double rs_column_sum(const double2* __restrict__ p, int n, double2* rows) {
+    const int lane = lane_id();
     double s = 0.0;
     for (int i0 = 0; i0 < n; i0 += RS_MEAN_ROWS) {                       // wave-uniform trip count
         const int m = min(RS_MEAN_ROWS, n - i0);
-        for (int i = lane; i < m; i += ICPMI_WAVE) rows[c][i] = p[i0 + i];
+        for (int i = lane; i < m; i += ICPMI_WAVE) rows[i] = p[i0 + i];
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         if (lane < 2) {
-            const double* col = reinterpret_cast<const double*>(rows[c]) + lane;
+            const double* col = reinterpret_cast<const double*>(rows) + lane;
             int i = 0;
             for (; i + 8 <= m; i += 8) {
                 const double v0 = col[2 * i], v1 = col[2 * i + 2], v2 = col[2 * i + 4], v3 = col[2 * i + 6];
@@ -95,12 +109,22 @@ __global__ __launch_bounds__(2 * ICPMI_WAVE) void rs_means_kernel(const double* 
         }
         __builtin_amdgcn_wave_barrier();                                 // the rows are read before the next copy overwrites them
     }
+    return s;
+}
+
+// the single search: two waves, source and target
+__global__ __launch_bounds__(2 * ICPMI_WAVE) void rs_means_kernel(const double* __restrict__ vox, const int32_t* __restrict__ off,
+                                                                 const int32_t* __restrict__ cnt, int centred, double shift_x,
+                                                                 double shift_y, double* __restrict__ rec) {
+    __shared__ double2 rows[2][RS_MEAN_ROWS];
+    const int c = wave_id(), lane = lane_id(), n = cnt[c];
+    const double s = rs_column_sum(reinterpret_cast<const double2*>(vox + (size_t)off[c] * 2), n, rows[c]);
     if (lane < 2) {
         const int d = lane;
         const double m = s / (double)n;
-        if (c == 0) rec[RSREC_MUS + d] = centred ? m : 0.0;
-        else rec[RSREC_MUT + d] = centred ? m : (d == 0 ? shift_x : shift_y);
-        if (d == 0) rec[c == 0 ? RSREC_NS : RSREC_NT] = (double)n;
+        if (c == 0) rec[ICPMI_RSREC_MUS + d] = centred ? m : 0.0;
+        else rec[ICPMI_RSREC_MUT + d] = centred ? m : (d == 0 ? shift_x : shift_y);
+        if (d == 0) rec[c == 0 ? ICPMI_RSREC_NS : ICPMI_RSREC_NT] = (double)n;
     }
 }
 
@@ -117,13 +141,10 @@ __device__ __forceinline__ int first_argmin(const double* __restrict__ v, int n,
         if (x != x) bn = min(bn, i);
         else if (x < bv) { bv = x; bi = i; }                 // ascending i: the first of equal values stays
     }
+    const auto less = [](double a, double b) { return a < b; };
+    wave_first_best(bv, bi, less);
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(bv, o, ICPMI_WAVE);
-        const int oi = __shfl_xor(bi, o, ICPMI_WAVE), on = __shfl_xor(bn, o, ICPMI_WAVE);
-        if (ov < bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        bn = min(bn, on);
-    }
+    for (int o = 32; o > 0; o >>= 1) bn = min(bn, __shfl_xor(bn, o, ICPMI_WAVE));
     double* shv = reinterpret_cast<double*>(sh);             // value per wave (2 ints each), then indices
     const int waves = (blockDim.x + ICPMI_WAVE - 1) / ICPMI_WAVE;
     int* shi = sh + 2 * 16;
@@ -134,8 +155,7 @@ __device__ __forceinline__ int first_argmin(const double* __restrict__ v, int n,
     else {
         double gv = __builtin_inf();
         int gi = big;
-        for (int w = 0; w < waves; ++w)
-            if (shv[w] < gv || (shv[w] == gv && shi[w] < gi)) { gv = shv[w]; gi = shi[w]; }
+        for (int w = 0; w < waves; ++w) take_first_best(gv, gi, shv[w], shi[w], less);
         best = gi == big ? 0 : gi;                           // nothing below +inf: index 0, as the serial scan
     }
     __syncthreads();                                         // sh may be used again
@@ -167,31 +187,9 @@ __global__ __launch_bounds__(RS_THREADS) void rotation_scores_state_kernel(
     if (n <= 0 || m <= 0) { if (threadIdx.x == 0) scores[a] = __builtin_nan(""); return; }
     const double* src = vox + (size_t)off[0] * 2;
     const double* tgt = vox + (size_t)off[1] * 2;
-    const double mux = rec[RSREC_MUS], muy = rec[RSREC_MUS + 1], shift_x = rec[RSREC_MUT], shift_y = rec[RSREC_MUT + 1];
-    const double c = cs[2 * a], s = cs[2 * a + 1];            // R = [[c, -s], [s, c]], features.py:214-215
-    double acc[1] = {0.0};
-    for (int first = 0; first < n; first += RS_THREADS) {     // uniform trip count
-        const int i = first + threadIdx.x;
-        const int ii = i < n ? i : n - 1;
-        const double x = src[2 * ii] - mux, y = src[2 * ii + 1] - muy;              // src - mu_s, features.py:207
-        double p[1][2] = {{(x * c + y * -s) + shift_x, (x * s + y * c) + shift_y}};   // src_c @ R.T + shift, features.py:216
-        double best[1] = {__builtin_inf()};
-        int bestj[1] = {0};
-        for (int t0 = 0; t0 < m; t0 += RS_TILE_POINTS) {
-            const int cntp = min(RS_TILE_POINTS, m - t0);
-            __syncthreads();
-            const int padded = stage_targets<2>(tgt + (size_t)t0 * 2, cntp, tile);
-            __syncthreads();
-            nn_scan_tile<2, 1>(tile, padded, t0, p, best, bestj);
-        }
-        if (i < n) {
-            const double d = sqrt(best[0]);                   // KDTree distance ...
-            acc[0] += d * d;                                  // ... squared, features.py:218
-        }
-    }
-    __syncthreads();
-    block_sum<1, RS_THREADS / ICPMI_WAVE>(acc, red);
-    if (threadIdx.x == 0) scores[a] = acc[0] / (double)n;
+    const double score = rs_score_angle(src, rec[ICPMI_RSREC_MUS], rec[ICPMI_RSREC_MUS + 1], cs[2 * a], cs[2 * a + 1],   // R = [[c, -s], [s, c]], features.py:214-215
+                                        rec[ICPMI_RSREC_MUT], rec[ICPMI_RSREC_MUT + 1], n, tgt, m, tile, red);
+    if (threadIdx.x == 0) scores[a] = score;
 }
 
 __global__ void rs_finish_kernel(const double* __restrict__ coarse, int n_coarse, const double* __restrict__ fine,
@@ -203,8 +201,8 @@ __global__ void rs_finish_kernel(const double* __restrict__ coarse, int n_coarse
     first_argmin_init(sh);
     const int j = nf > 0 ? first_argmin(fine, nf, sh) : 0;
     if (threadIdx.x == 0) {
-        rec[RSREC_K] = (double)k; rec[RSREC_CSCORE] = coarse[k];
-        rec[RSREC_NF] = (double)nf; rec[RSREC_J] = (double)j; rec[RSREC_FSCORE] = nf > 0 ? fine[j] : __builtin_nan("");
+        rec[ICPMI_RSREC_K] = (double)k; rec[ICPMI_RSREC_CSCORE] = coarse[k];
+        rec[ICPMI_RSREC_NF] = (double)nf; rec[ICPMI_RSREC_J] = (double)j; rec[ICPMI_RSREC_FSCORE] = nf > 0 ? fine[j] : __builtin_nan("");
     }
 }
 
@@ -217,12 +215,12 @@ __global__ void rs_finish_kernel(const double* __restrict__ coarse, int n_coarse
 // a BLAS gemm whose element is fma(y, R[c][1], x * R[c][0]) (OpenBLAS, FMA kernels; checked on random inputs in the
 // build container) — the distances the k-d tree's (direct differences, IEEE sqrt), squared again; the percentile
 // numpy's _lerp on the (n - 1) * 0.8-th order statistic; the mean a row-by-row sum divided by the count.
-constexpr int RSR_MAX_ROWS = 2048;            // rows the finishing workgroup holds in LDS
+constexpr int RSR_MAX_ROWS = ICPMI_RSR_MAX_ROWS;   // rows the finishing workgroup holds in LDS
 constexpr int RSR_THREADS = 1024;
 
 __device__ __forceinline__ void rsr_best_cs(const double* __restrict__ rec, const double* __restrict__ coarse_cs,
                                             const double* __restrict__ fine_cs, int max_fine, double& ca, double& sa) {
-    const int k = (int)rec[RSREC_K], nf = (int)rec[RSREC_NF], j = (int)rec[RSREC_J];
+    const int k = (int)rec[ICPMI_RSREC_K], nf = (int)rec[ICPMI_RSREC_NF], j = (int)rec[ICPMI_RSREC_J];
     const double* cs = nf > 0 ? fine_cs + ((size_t)k * max_fine + j) * 2 : coarse_cs + (size_t)k * 2;   // slam.py:157-159
     ca = cs[0]; sa = cs[1];
 }
@@ -243,16 +241,10 @@ __global__ __launch_bounds__(RS_THREADS) void rs_refine_match_kernel(
     const int i = first + threadIdx.x, ii = i < n ? i : n - 1;
     const double x = src[2 * ii], y = src[2 * ii + 1];
     const double rx = __builtin_fma(y, -sa, x * ca), ry = __builtin_fma(y, ca, x * sa);   // src @ R_best.T, slam.py:168
-    double p[1][2] = {{rx + pred_x, ry + pred_y}};                 // placed, slam.py:169
-    double best[1] = {__builtin_inf()};
-    int bestj[1] = {0};
-    for (int t0 = 0; t0 < m; t0 += RS_TILE_POINTS) {
-        const int c = min(RS_TILE_POINTS, m - t0);
-        __syncthreads();
-        const int padded = stage_targets<2>(tgt + (size_t)t0 * 2, c, tile);
-        __syncthreads();
-        nn_scan_tile<2, 1>(tile, padded, t0, p, best, bestj);
-    }
+    const double p[1][2] = {{rx + pred_x, ry + pred_y}};           // placed, slam.py:169
+    double best[1];
+    int bestj[1];
+    rs_nearest_tiled(tgt, m, tile, p, best, bestj);
     if (i < n) {
         const double d = sqrt(best[0]);
         rot[i] = make_double2(rx, ry); dsq[i] = d * d; idx[i] = bestj[0];    // slam.py:170-171
@@ -336,10 +328,8 @@ __global__ __launch_bounds__(RSR_THREADS) void rs_refine_finish_kernel(
 constexpr int RSB_THREADS = 512;
 constexpr int RSB_WAVES = RSB_THREADS / ICPMI_WAVE;
 constexpr int RSB_W = 64;                        // field cells per side
-constexpr int RSB_MAX_ANGLES = 1024;             // coarse angles / fine angles per grid at most
-constexpr int RSB_REC_DOUBLES = 16;
-constexpr int RSBREC_STATUS = 11, RSBREC_EVALS = 12, RSBREC_FEVALS = 13;
-constexpr int RSB_ST_OK = 0, RSB_ST_FEW = 1, RSB_ST_CAPACITY = 2, RSB_ST_NO_FINE = 3;
+constexpr int RSB_MAX_ANGLES = ICPMI_RSB_MAX_ANGLES;   // coarse angles / fine angles per grid at most
+// (record slots and statuses: ICPMI_RSREC_*, ICPMI_RSBREC_*, ICPMI_RSB_ST_*, include/icpmi.h)
 
 struct RsbArgs {
     const double* vox;            // voxel-filtered clouds (cloud set layout)
@@ -400,6 +390,18 @@ __device__ __forceinline__ double rsb_score_angle(const double2* src_c, int n, c
     return wave_sum(acc) / (double)n;
 }
 
+// the head of a pair's record: everything zero, then the counts, the means and the status
+__device__ __forceinline__ void rsb_write_head(double* rec, int n, int m, double musx, double musy, double mutx, double muty, int status) {
+    for (int i = 0; i < ICPMI_RSBREC_DOUBLES; ++i) rec[i] = 0.0;
+    rec[ICPMI_RSREC_NS] = (double)n; rec[ICPMI_RSREC_NT] = (double)m;
+    rec[ICPMI_RSREC_MUS] = musx; rec[ICPMI_RSREC_MUS + 1] = musy; rec[ICPMI_RSREC_MUT] = mutx; rec[ICPMI_RSREC_MUT + 1] = muty;
+    rec[ICPMI_RSBREC_STATUS] = (double)status;
+}
+// the start of the ICP of a pair that was not searched, or has no fine grid: the identity
+__device__ __forceinline__ void rsb_identity_start(double* init) {
+    if (init) { init[0] = 1.0; init[1] = 0.0; init[2] = 0.0; init[3] = 1.0; init[4] = 0.0; init[5] = 0.0; }
+}
+
 __global__ __launch_bounds__(RSB_THREADS, 4) void rotation_search_batch_kernel(RsbArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     __shared__ __attribute__((aligned(16))) float field[RSB_W * RSB_W];
@@ -414,20 +416,18 @@ __global__ __launch_bounds__(RSB_THREADS, 4) void rotation_search_batch_kernel(R
     const int b = blockIdx.x, tid = threadIdx.x;
     const int sc = a.pair_src[b], tc = a.pair_tgt[b];
     const int n = a.cnt[sc], m = a.cnt[tc];
-    double* rec = a.records + (size_t)b * RSB_REC_DOUBLES;
+    double* rec = a.records + (size_t)b * ICPMI_RSBREC_DOUBLES;
     double* init = a.init ? a.init + (size_t)b * 6 : nullptr;
     const double musx = a.means[2 * sc], musy = a.means[2 * sc + 1], mutx = a.means[2 * tc], muty = a.means[2 * tc + 1];
     const int dir = a.g_dir[tc];
-    int status = RSB_ST_OK;
-    if (n < 5 || m < 5) status = RSB_ST_FEW;                           // features.py:203-204: identity, zeros, inf
-    else if (n > a.cap || m > a.cap || dir < 0 || dir > SWEEP_POLAR) status = RSB_ST_CAPACITY;
-    if (status != RSB_ST_OK) {                                         // uniform per workgroup, before any barrier
+    int status = ICPMI_RSB_ST_OK;
+    if (n < 5 || m < 5) status = ICPMI_RSB_ST_FEW;                           // features.py:203-204: identity, zeros, inf
+    else if (n > a.cap || m > a.cap || dir < 0 || dir > SWEEP_POLAR) status = ICPMI_RSB_ST_CAPACITY;
+    if (status != ICPMI_RSB_ST_OK) {                                         // uniform per workgroup, before any barrier
         if (tid == 0) {
-            for (int i = 0; i < RSB_REC_DOUBLES; ++i) rec[i] = 0.0;
-            rec[RSREC_NS] = (double)n; rec[RSREC_NT] = (double)m;
-            rec[RSREC_MUS] = musx; rec[RSREC_MUS + 1] = musy; rec[RSREC_MUT] = mutx; rec[RSREC_MUT + 1] = muty;
-            rec[RSREC_CSCORE] = __builtin_inf(); rec[RSREC_FSCORE] = __builtin_inf(); rec[RSBREC_STATUS] = (double)status;
-            if (init) { init[0] = 1.0; init[1] = 0.0; init[2] = 0.0; init[3] = 1.0; init[4] = 0.0; init[5] = 0.0; }
+            rsb_write_head(rec, n, m, musx, musy, mutx, muty, status);
+            rec[ICPMI_RSREC_CSCORE] = __builtin_inf(); rec[ICPMI_RSREC_FSCORE] = __builtin_inf();
+            rsb_identity_start(init);
         }
         return;
     }
@@ -555,21 +555,25 @@ __global__ __launch_bounds__(RSB_THREADS, 4) void rotation_search_batch_kernel(R
     }
     __syncthreads();
     const bool prune = a.prune != 0;
-    // (items are dealt to the waves round-robin — no work counter: a counter bumped by lane 0 and broadcast with
-    // readfirstlane inside this loop was jump-threaded by the compiler into a per-lane loop whose other 63 lanes read item 0
-    // for ever)
-    for (int item = wave_id(); item < n_coarse; item += RSB_WAVES) {
-        const int k = order[item];
-        if ((double)lb[k] > *(volatile double*)&best_score) break;              // bounds ascend: nothing further on can win
-        const double sc_k = rsb_score_angle(src_c, n, sq, sxy, filt, m, dir, uabs, a.coarse_cs[2 * k], a.coarse_cs[2 * k + 1], mutx, muty,
-                                            &best_score, prune, tree, leaves, RSB_COARSE_ROUNDS);
-        if (lane_id() == 0) {
-            scores[k] = sc_k;
-            atomicAdd(&n_evals, 1);
-            if (sc_k < __builtin_inf())                                  // non-negative doubles order like their bits
-                atomicMin(reinterpret_cast<unsigned long long*>(&best_score), (unsigned long long)__double_as_longlong(sc_k));
+    // Exact scores of n_items angles of `cs`, dealt to the waves round-robin; `through` (the coarse pass): item i is angle
+    // through[i], and a wave stops at the first whose bound exceeds the best exact score — bounds ascend: nothing further
+    // on can win.  (No work counter: a counter bumped by lane 0 and broadcast with readfirstlane inside this loop was
+    // jump-threaded by the compiler into a per-lane loop whose other 63 lanes read item 0 for ever.)
+    const auto score_exactly = [&](int n_items, const short* through, const double* cs, int walk_rounds) __attribute__((always_inline)) {
+        for (int item = wave_id(); item < n_items; item += RSB_WAVES) {
+            const int k = through ? through[item] : item;
+            if (through && (double)lb[k] > *(volatile double*)&best_score) break;
+            const double sc_k = rsb_score_angle(src_c, n, sq, sxy, filt, m, dir, uabs, cs[2 * k], cs[2 * k + 1], mutx, muty, &best_score, prune,
+                                                tree, leaves, walk_rounds);
+            if (lane_id() == 0) {
+                scores[k] = sc_k;
+                atomicAdd(&n_evals, 1);
+                if (sc_k < __builtin_inf())                                  // non-negative doubles order like their bits
+                    atomicMin(reinterpret_cast<unsigned long long*>(&best_score), (unsigned long long)__double_as_longlong(sc_k));
+            }
         }
-    }
+    };
+    score_exactly(n_coarse, order, a.coarse_cs, RSB_COARSE_ROUNDS);
     __syncthreads();
     first_argmin_init(sh_arg);
     const int kbest = first_argmin(scores, n_coarse, sh_arg);
@@ -582,26 +586,15 @@ __global__ __launch_bounds__(RSB_THREADS, 4) void rotation_search_batch_kernel(R
     if (tid == 0) { best_score = __builtin_inf(); n_evals = 0; }
     __syncthreads();
     const double* fcs = a.fine_cs + (size_t)kbest * a.max_fine * 2;
-    for (int j = wave_id(); j < nf; j += RSB_WAVES) {
-        const double sc_j = rsb_score_angle(src_c, n, sq, sxy, filt, m, dir, uabs, fcs[2 * j], fcs[2 * j + 1], mutx, muty, &best_score, prune, tree, leaves, RSB_FINE_ROUNDS);
-        if (lane_id() == 0) {
-            scores[j] = sc_j;
-            atomicAdd(&n_evals, 1);
-            if (sc_j < __builtin_inf())
-                atomicMin(reinterpret_cast<unsigned long long*>(&best_score), (unsigned long long)__double_as_longlong(sc_j));
-        }
-    }
+    score_exactly(nf, nullptr, fcs, RSB_FINE_ROUNDS);
     __syncthreads();
     first_argmin_init(sh_arg);
     const int jbest = nf > 0 ? first_argmin(scores, nf, sh_arg) : 0;
     if (tid == 0) {
-        for (int i = 0; i < RSB_REC_DOUBLES; ++i) rec[i] = 0.0;
-        rec[RSREC_NS] = (double)n; rec[RSREC_NT] = (double)m;
-        rec[RSREC_MUS] = musx; rec[RSREC_MUS + 1] = musy; rec[RSREC_MUT] = mutx; rec[RSREC_MUT + 1] = muty;
-        rec[RSREC_K] = (double)kbest; rec[RSREC_CSCORE] = cscore; rec[RSREC_NF] = (double)nf; rec[RSREC_J] = (double)jbest;
-        rec[RSREC_FSCORE] = nf > 0 ? scores[jbest] : __builtin_nan("");
-        rec[RSBREC_STATUS] = (double)(nf > 0 ? RSB_ST_OK : RSB_ST_NO_FINE);
-        rec[RSBREC_EVALS] = (double)coarse_evals; rec[RSBREC_FEVALS] = (double)n_evals;
+        rsb_write_head(rec, n, m, musx, musy, mutx, muty, nf > 0 ? ICPMI_RSB_ST_OK : ICPMI_RSB_ST_NO_FINE);
+        rec[ICPMI_RSREC_K] = (double)kbest; rec[ICPMI_RSREC_CSCORE] = cscore; rec[ICPMI_RSREC_NF] = (double)nf; rec[ICPMI_RSREC_J] = (double)jbest;
+        rec[ICPMI_RSREC_FSCORE] = nf > 0 ? scores[jbest] : __builtin_nan("");
+        rec[ICPMI_RSBREC_EVALS] = (double)coarse_evals; rec[ICPMI_RSBREC_FEVALS] = (double)n_evals;
         if (init) {
             if (nf > 0) {
                 // R = [[ca, -sa], [sa, ca]], t = mu_t - R @ mu_s (features.py:235-237).  The 2 x 2 by 2 product is a BLAS
@@ -610,7 +603,7 @@ __global__ __launch_bounds__(RSB_THREADS, 4) void rotation_search_batch_kernel(R
                 const double ca = fcs[2 * jbest], sa = fcs[2 * jbest + 1];
                 const double y0 = __builtin_fma(ca, musx, -sa * musy), y1 = __builtin_fma(sa, musx, ca * musy);
                 init[0] = ca; init[1] = -sa; init[2] = sa; init[3] = ca; init[4] = mutx - y0; init[5] = muty - y1;
-            } else { init[0] = 1.0; init[1] = 0.0; init[2] = 0.0; init[3] = 1.0; init[4] = 0.0; init[5] = 0.0; }
+            } else rsb_identity_start(init);
         }
     }
 }
@@ -625,37 +618,19 @@ __global__ __launch_bounds__(RSB_MEAN_WAVES* ICPMI_WAVE) void rsb_means_kernel(c
     const int c = blockIdx.x * RSB_MEAN_WAVES + w;
     if (c >= n_clouds) return;                                          // whole waves leave: no workgroup barrier below
     const int n = cnt[c];
-    const double2* p = reinterpret_cast<const double2*>(vox) + off[c];
-    double s = 0.0;
-    for (int i0 = 0; i0 < n; i0 += RS_MEAN_ROWS) {                       // wave-uniform trip count
-        const int mm = min(RS_MEAN_ROWS, n - i0);
-        for (int i = lane; i < mm; i += ICPMI_WAVE) rows[w][i] = p[i0 + i];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (lane < 2) {
-            const double* col = reinterpret_cast<const double*>(rows[w]) + lane;
-            int i = 0;
-            for (; i + 8 <= mm; i += 8) {
-                const double v0 = col[2 * i], v1 = col[2 * i + 2], v2 = col[2 * i + 4], v3 = col[2 * i + 6];
-                const double v4 = col[2 * i + 8], v5 = col[2 * i + 10], v6 = col[2 * i + 12], v7 = col[2 * i + 14];
-                s += v0; s += v1; s += v2; s += v3; s += v4; s += v5; s += v6; s += v7;
-            }
-            for (; i < mm; ++i) s += col[2 * i];
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
+    const double s = rs_column_sum(reinterpret_cast<const double2*>(vox) + off[c], n, rows[w]);
     if (lane < 2) means[2 * c + lane] = s / (double)n;
 }
 
 // ── the workspaces of the entry points below ──
 // single search: offsets (3 int32) | counts (2 int32) | voxel-filtered copy | coarse + fine scores | voxel scratch
-// Its head, which icpmi_rotation_refine reads again: the counts 16 bytes in, the filtered copy 256 bytes in.
+// Its head, which icpmi_rotation_refine and the callers read again: the counts ICPMI_RS_WS_COUNTS bytes in, the filtered copy
+// ICPMI_RS_WS_CLOUDS bytes in.
 struct RsHead {
     Carve c;
     int32_t n_src, n_tgt;
-    int32_t* off = c.take<int32_t>(256);
-    int32_t* cnt = off ? off + 4 : nullptr;
+    int32_t* off = c.take<int32_t>(ICPMI_RS_WS_CLOUDS);
+    int32_t* cnt = off ? off + ICPMI_RS_WS_COUNTS / 4 : nullptr;
     double* vox = c.take<double>(((size_t)n_src + n_tgt + 1) * 16);
 };
 struct RsWs : RsHead {
@@ -680,6 +655,44 @@ struct RsbWs {
     void* vws = c.take<void>(vws_bytes);
     size_t bytes = c.off + 256;
 };
+
+// What a batch call starts, decided as a whole from its arguments (no HIP call).  RS_BATCH, parsed once: "full" scores
+// every angle exactly, "projection" keeps the targets' search order to the projections.
+enum class RsBatchOption { unset, full, projection, other };
+static RsBatchOption parse_rs_batch_option(const char* v) {
+    if (!v) return RsBatchOption::unset;
+    return v[0] == 'f' ? RsBatchOption::full : v[0] == 'p' ? RsBatchOption::projection : RsBatchOption::other;
+}
+struct RsbPlan {
+    int rc;                   // ICPMI_OK, or why nothing is launched
+    int max_n, total_rows;    // rows of the largest raw cloud, of all of them
+    int cap;                  // rows of a cloud the on-chip copies hold
+    size_t lds;               // dynamic LDS of the search kernel
+    int means_grid;
+    int allow_polar;          // the targets may be put in bearing order
+    int prune;                // 0: score every angle
+};
+static RsbPlan plan_rotation_search_batch(const int32_t* off_host, int n_clouds, int max_rows_hint, RsBatchOption opt) {
+    RsbPlan p{};
+    p.rc = ICPMI_ERR_ARG;
+    if (!cloud_rows(off_host, n_clouds, p.max_n, p.total_rows)) return p;
+    p.rc = ICPMI_ERR_UNSUPPORTED;
+    if (p.max_n > 4096) return p;                                        // single-pair entry (icpmi_rotation_search) for larger clouds
+    p.rc = ICPMI_OK;
+    // rows the on-chip copies hold: the largest raw cloud (the filter only removes rows), at most ICPMI_RSB_MAX_ROWS; the
+    // caller's hint (an upper bound it expects for the FILTERED clouds) lowers it so that two workgroups share a CU — a pair
+    // with a larger filtered cloud reports ICPMI_RSB_ST_CAPACITY and is left to the single-pair entry
+    p.cap = p.max_n < ICPMI_RSB_MAX_ROWS ? p.max_n : ICPMI_RSB_MAX_ROWS;
+    if (max_rows_hint > 0 && max_rows_hint < p.cap) p.cap = max_rows_hint;
+    p.cap = (p.cap + 63) / 64 * 64;
+    p.lds = (size_t)p.cap * 48 + 32 + 32 * (size_t)sweepf_tree_leaves(p.cap);
+    p.means_grid = (n_clouds + RSB_MEAN_WAVES - 1) / RSB_MEAN_WAVES;
+    // search order of the targets: a projection or, for scans in their sensor frame, the bearing (the library's estimate;
+    // any order is exact for any query)
+    p.allow_polar = opt == RsBatchOption::projection ? 0 : 1;
+    p.prune = opt == RsBatchOption::full ? 0 : 1;
+    return p;
+}
 
 // scratch of the refinement: rotated rows | squared distances | matched rows (n_src of each)
 struct RsRefineWs {
@@ -756,52 +769,27 @@ extern "C" int icpmi_rotation_search_batch(const double* pts, const int32_t* off
     if (!(voxel_size > 0.0)) return ICPMI_ERR_ARG;
     if (n_coarse > RSB_MAX_ANGLES || max_fine > RSB_MAX_ANGLES) return ICPMI_ERR_UNSUPPORTED;
     if (n_pairs == 0) return ICPMI_OK;
-    int max_n = 0;
-    for (int c = 0; c < n_clouds; ++c) {
-        const int nrow = off_host[c + 1] - off_host[c];
-        if (nrow < 0) return ICPMI_ERR_ARG;
-        max_n = nrow > max_n ? nrow : max_n;
-    }
-    const int total_rows = off_host[n_clouds];
-    if (max_n > 4096) return ICPMI_ERR_UNSUPPORTED;                      // single-pair entry (icpmi_rotation_search) for larger clouds
-    const RsbWs w{workspace, total_rows, n_clouds, max_n};
+    const RsbPlan plan = plan_rotation_search_batch(off_host, n_clouds, max_rows_hint, parse_rs_batch_option(option("RS_BATCH")));
+    if (plan.rc != ICPMI_OK) return plan.rc;
+    const RsbWs w{workspace, plan.total_rows, n_clouds, plan.max_n};
     if (workspace_bytes < w.bytes) return ICPMI_ERR_WORKSPACE;
-    const PreparedView v(w.prepared, total_rows, n_clouds);
+    const PreparedView v(w.prepared, plan.total_rows, n_clouds);
     hipStream_t st = (hipStream_t)stream;
     int rc = icpmi_voxel_downsample_batch(pts, off_dev, off_host, n_clouds, 2, voxel_size, w.vox, w.cnt, w.vws, w.vws_bytes, stream);
     if (rc != ICPMI_OK) return rc;
-    rsb_means_kernel<<<(n_clouds + RSB_MEAN_WAVES - 1) / RSB_MEAN_WAVES, RSB_MEAN_WAVES * ICPMI_WAVE, 0, st>>>(w.vox, off_dev, w.cnt, n_clouds, w.means);
-    // search order of the targets: a projection or, for scans in their sensor frame, the bearing (the library's estimate; any
-    // order is exact for any query — RS_BATCH = "projection" keeps to the projections)
-    const char* oe = option("RS_BATCH");
-    // a pair whose target is not among tgt_ids must report "no order" (status 2), not search whatever the workspace held
+    rsb_means_kernel<<<plan.means_grid, RSB_MEAN_WAVES * ICPMI_WAVE, 0, st>>>(w.vox, off_dev, w.cnt, n_clouds, w.means);
+    // a pair whose target is not among tgt_ids must report "no order" (ICPMI_RSB_ST_CAPACITY), not search whatever the workspace held
     if (hipMemsetAsync(v.dir, 0xFF, (size_t)n_clouds * sizeof(int32_t), st) != hipSuccess) return ICPMI_ERR_HIP;
-    rc = icpmi_prepare_targets_ex(w.vox, off_dev, off_host, w.cnt, tgt_ids, nullptr, tgt_ids ? n_tgt_ids : n_clouds, n_clouds, total_rows, max_n, -1,
-                                  nullptr, w.prepared, w.prepared_bytes, oe && oe[0] == 'p' ? 0 : 1, stream);
+    rc = icpmi_prepare_targets_ex(w.vox, off_dev, off_host, w.cnt, tgt_ids, nullptr, tgt_ids ? n_tgt_ids : n_clouds, n_clouds, plan.total_rows,
+                                  plan.max_n, -1, nullptr, w.prepared, w.prepared_bytes, plan.allow_polar, stream);
     if (rc != ICPMI_OK) return rc;
-    RsbArgs a;
-    a.vox = w.vox; a.off = off_dev; a.cnt = w.cnt; a.means = w.means; a.pair_src = pair_src; a.pair_tgt = pair_tgt;
-    a.g_sxy = v.sxy; a.g_sorig = v.sorig; a.g_skey = v.skey; a.g_dir = v.dir;
-    a.coarse_cs = coarse_cs; a.n_coarse = n_coarse; a.fine_cs = fine_cs; a.fine_cnt = fine_cnt; a.max_fine = max_fine;
-    a.records = out_records; a.init = out_init;
-    // rows the on-chip copies hold: the largest raw cloud (the filter only removes rows), at most 2 048; the caller's hint
-    // (an upper bound it expects for the FILTERED clouds) lowers it so that two workgroups share a CU — a pair with a
-    // larger filtered cloud reports RSB_ST_CAPACITY and is left to the single-pair entry
-    int cap = max_n < 2048 ? max_n : 2048;
-    if (max_rows_hint > 0 && max_rows_hint < cap) cap = max_rows_hint;
-    cap = (cap + 63) / 64 * 64;
-    a.cap = cap;
-    const char* e = option("RS_BATCH");
-    a.prune = e && e[0] == 'f' ? 0 : 1;                                 // "full": every angle scored exactly
-    const size_t lds = (size_t)cap * 48 + 32 + 32 * (size_t)sweepf_tree_leaves(cap);
-    if (dyn_lds((const void*)rotation_search_batch_kernel, lds) != hipSuccess)
-        return ICPMI_ERR_HIP;
-    rotation_search_batch_kernel<<<n_pairs, RSB_THREADS, lds, st>>>(a);
+    const RsbArgs a{w.vox, off_dev, w.cnt, w.means, pair_src, pair_tgt, v.sxy, v.sorig, v.skey, v.dir, coarse_cs, n_coarse,
+                    fine_cs, fine_cnt, max_fine, out_records, out_init, plan.cap, plan.prune};
+    if (dyn_lds((const void*)rotation_search_batch_kernel, plan.lds) != hipSuccess) return ICPMI_ERR_HIP;
+    rotation_search_batch_kernel<<<n_pairs, RSB_THREADS, plan.lds, st>>>(a);
     ICPMI_LAUNCH_CHECK();
     return ICPMI_OK;
 }
-
-
 
 extern "C" size_t icpmi_rotation_refine_workspace_bytes(int32_t n_src) {
     if (n_src < 0) return 0;

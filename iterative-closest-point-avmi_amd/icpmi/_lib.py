@@ -15,6 +15,19 @@ OK = 0
 ST_CONVERGED, ST_MAXITER, ST_FEW_INLIERS, ST_EMPTY, ST_SKIPPED = 1, 2, 3, 4, 5
 RES_DOUBLES, RES_R, RES_T, RES_ERR, RES_DELTA, RES_ITERS, RES_STATUS = 16, 0, 9, 12, 13, 14, 15
 POINT_TO_POINT, POINT_TO_LINE = 0, 1
+# the record of icpmi_rotation_search (RSREC_*; the workspace offsets its callers read the filtered clouds at), what
+# icpmi_rotation_search_batch adds to it (RSBREC_*, RSB_*), icpmi_rotation_refine's capacity, and the record, statuses and
+# capacities of the feature alignment (FTREC_*, FT_*): include/icpmi.h's ICPMI_* names (tests/test_host_cpu.py compares)
+RSREC_DOUBLES, RSREC_NS, RSREC_NT, RSREC_MUS, RSREC_MUT, RSREC_K, RSREC_CSCORE, RSREC_NF, RSREC_J, RSREC_FSCORE = 12, 0, 1, 2, 4, 6, 7, 8, 9, 10
+RS_WS_COUNTS, RS_WS_CLOUDS = 16, 256
+RSR_MAX_ROWS = 2048
+RSBREC_DOUBLES, RSBREC_STATUS, RSBREC_EVALS, RSBREC_FEVALS = 16, 11, 12, 13
+RSB_ST_OK, RSB_ST_FEW, RSB_ST_CAPACITY, RSB_ST_NO_FINE = 0, 1, 2, 3
+RSB_MAX_ANGLES, RSB_MAX_ROWS = 1024, 2048
+FT_MAX_ROWS, FT_MAX_KP, FT_DESC_STRIDE = 2048, 256, 32
+FTREC_DOUBLES, FTREC_NS, FTREC_NT, FTREC_KPS, FTREC_KPT, FTREC_MATCHES, FTREC_INLIERS, FTREC_R, FTREC_T, FTREC_STATUS, FTREC_BEST = (
+    16, 0, 1, 2, 3, 4, 5, 6, 10, 12, 13)
+FT_ST_OK, FT_ST_FEW_ROWS, FT_ST_CAPACITY, FT_ST_FEW_KP, FT_ST_FEW_MATCHES, FT_ST_DESC_LEN = 0, 1, 2, 3, 4, 5
 
 
 class IcpParams(C.Structure):

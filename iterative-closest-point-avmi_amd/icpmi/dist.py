@@ -179,7 +179,7 @@ class RunIcpPairSharded:
             events[0].record()
         self.batch.search.run()
         res = self.batch.icp.run(events=None if events is None else (events[1], events[2]))[:k]
-        res[:, self.SEARCH_STATUS] = self.batch.search.records[:k, 11]          # device-side copy: rides on the gather
+        res[:, self.SEARCH_STATUS] = self.batch.search.records[:k, _lib.RSBREC_STATUS]          # device-side copy: rides on the gather
         return res
 
     def run(self, events=None, force_collective=False):

@@ -20,9 +20,10 @@ from . import _lib
 from ._lib import check
 from .batch import CloudSet, IcpBatch, _ptr, _stream, require_gpu, unpack_results
 
-REC_DOUBLES = 16
-ST_OK, ST_FEW, ST_CAPACITY, ST_NO_FINE = 0, 1, 2, 3
-RSB_MAX_ANGLES = 1024          # angles per sweep the batched kernel tabulates (csrc/rotsearch.hip)
+# the records' layout, statuses and capacities are include/icpmi.h's, mirrored once in _lib; the names users import stay
+REC_DOUBLES = _lib.RSBREC_DOUBLES                                # (the feature record has the same stride)
+ST_OK, ST_FEW, ST_CAPACITY, ST_NO_FINE = _lib.RSB_ST_OK, _lib.RSB_ST_FEW, _lib.RSB_ST_CAPACITY, _lib.RSB_ST_NO_FINE
+RSB_MAX_ANGLES = _lib.RSB_MAX_ANGLES                             # angles per sweep the batched kernel tabulates
 ALIGNMENT_METHODS = ("rotation_search", "features", "both")      # slam.py:60, 68
 
 
@@ -48,6 +49,29 @@ def arange_rows(lo, hi, step):
     return vals, n
 
 
+def device_angle_tables(dev, coarse, fine, fine_n):
+    """cos / sin of the coarse angles [K, 2] and of every fine grid [K, L, 2] (features.py:214 uses np.cos / np.sin) and the
+    grids' lengths (int32), on the device."""
+    cs = np.ascontiguousarray(np.stack([np.cos(coarse), np.sin(coarse)], axis=1))
+    fcs = np.ascontiguousarray(np.stack([np.cos(fine), np.sin(fine)], axis=2)) if fine.size else np.zeros((len(coarse), 0, 2))
+    return (torch.from_numpy(cs).to(dev), torch.from_numpy(fcs).to(dev),
+            torch.from_numpy(np.ascontiguousarray(fine_n, dtype=np.int32)).to(dev))
+
+
+def winning_angle(coarse, fine, rec, coarse_without_fine=False):
+    """The angle a search record names (one record, or [B, .] records -> [B] angles): entry RSREC_J of the fine grid of the
+    winning coarse angle RSREC_K (features.py:231-232).  A winner whose fine grid is empty: np.argmin raises in
+    rotation_search (features.py:231); with ``coarse_without_fine`` the coarse angle stands (slam.py:157-159)."""
+    rec = np.asarray(rec)
+    k, j = rec[..., _lib.RSREC_K].astype(np.int64), rec[..., _lib.RSREC_J].astype(np.int64)
+    has_fine = rec[..., _lib.RSREC_NF] > 0
+    if has_fine.all():
+        return fine[k, j]
+    if not coarse_without_fine:
+        raise ValueError("attempt to get argmin of an empty sequence")          # np.argmin(scores_fine) on an empty grid
+    return np.where(has_fine, fine[k, j], coarse[k]) if has_fine.any() else coarse[k]
+
+
 class AngleTables:
     """Coarse angles of features.py:221 and, for every coarse angle that can win, the fine grid of features.py:227-229,
     with cos / sin of all of them on the device (features.py:214 uses np.cos / np.sin).  One per (device, steps)."""
@@ -66,12 +90,7 @@ class AngleTables:
         hi = self.coarse + np.deg2rad(angle_step_coarse)
         self.fine, self.fine_n = arange_rows(lo, hi, np.deg2rad(angle_step_fine))
         self.max_fine = int(self.fine.shape[1]) if self.fine.ndim == 2 else 0
-        cs = np.ascontiguousarray(np.stack([np.cos(self.coarse), np.sin(self.coarse)], axis=1))
-        fcs = (np.ascontiguousarray(np.stack([np.cos(self.fine), np.sin(self.fine)], axis=2)) if self.fine.size
-               else np.zeros((len(self.coarse), 0, 2)))
-        self.d_cs = torch.from_numpy(cs).to(dev)
-        self.d_fcs = torch.from_numpy(fcs).to(dev)
-        self.d_fn = torch.from_numpy(np.ascontiguousarray(self.fine_n, dtype=np.int32)).to(dev)
+        self.d_cs, self.d_fcs, self.d_fn = device_angle_tables(dev, self.coarse, self.fine, self.fine_n)
 
     @property
     def device_table(self):
@@ -118,7 +137,7 @@ class RotationSearchBatch:
         mf = t.max_fine
         if self.too_many_angles:                   # icpmi_rotation_search_batch would answer ICPMI_ERR_UNSUPPORTED
             self.records.zero_()
-            self.records[:, 11] = ST_CAPACITY      # results() searches such pairs one by one: same numbers
+            self.records[:, _lib.RSBREC_STATUS] = ST_CAPACITY      # results() searches such pairs one by one: same numbers
             return self.records
         check(_lib.lib().icpmi_rotation_search_batch(
             _ptr(self.raw.pts), _ptr(self.raw.off), self.raw.off_host.ctypes.data_as(C.c_void_p), self.raw.n_clouds,
@@ -130,27 +149,26 @@ class RotationSearchBatch:
 
     def results(self, records=None):
         """-> (R [B,2,2], t [B,2], score [B], records [B,16]) on the host (synchronises).  Pairs the on-chip search could
-        not hold (status 2: a filtered cloud above the capacity hint) are searched one by one through the single-pair
+        not hold (ST_CAPACITY: a filtered cloud above the capacity hint) are searched one by one through the single-pair
         entry — same numbers."""
         rec = (self.records if records is None else records).cpu().numpy()[:self.B]
         t = self.tables
         R = np.tile(np.eye(2), (self.B, 1, 1))
         tt = np.zeros((self.B, 2))
         score = np.full(self.B, np.inf)
-        status = rec[:, 11].astype(np.int64)
+        status = rec[:, _lib.RSBREC_STATUS].astype(np.int64)
         if (status == ST_NO_FINE).any():
             raise ValueError("attempt to get argmin of an empty sequence")          # np.argmin(scores_fine) on an empty grid
         ok = np.flatnonzero(status == ST_OK)
         if len(ok):
-            k = rec[ok, 6].astype(np.int64)
-            j = rec[ok, 9].astype(np.int64)
-            ang = t.fine[k, j]
+            ang = winning_angle(t.coarse, t.fine, rec[ok])
             ca, sa = np.cos(ang), np.sin(ang)
+            mu_s, mu_t = rec[:, _lib.RSREC_MUS:_lib.RSREC_MUS + 2], rec[:, _lib.RSREC_MUT:_lib.RSREC_MUT + 2]
             for q, i in enumerate(ok):                                              # features.py:235-237, NumPy's own matmul
                 Ri = np.array([[ca[q], -sa[q]], [sa[q], ca[q]]])
                 R[i] = Ri
-                tt[i] = rec[i, 4:6] - Ri @ rec[i, 2:4]
-            score[ok] = rec[ok, 10]
+                tt[i] = mu_t[i] - Ri @ mu_s[i]
+            score[ok] = rec[ok, _lib.RSREC_FSCORE]
         over = np.flatnonzero(status == ST_CAPACITY)
         if len(over):
             from utilities import features
@@ -165,7 +183,8 @@ class RotationSearchBatch:
                 features.VERBOSE = keep
         return R, tt, score, rec
 
-FEAT_ST_OK, FEAT_ST_FEW_ROWS, FEAT_ST_CAPACITY, FEAT_ST_FEW_KP, FEAT_ST_FEW_MATCHES, FEAT_ST_DESC_LEN = 0, 1, 2, 3, 4, 5
+FEAT_ST_OK, FEAT_ST_FEW_ROWS, FEAT_ST_CAPACITY, FEAT_ST_FEW_KP, FEAT_ST_FEW_MATCHES, FEAT_ST_DESC_LEN = (
+    _lib.FT_ST_OK, _lib.FT_ST_FEW_ROWS, _lib.FT_ST_CAPACITY, _lib.FT_ST_FEW_KP, _lib.FT_ST_FEW_MATCHES, _lib.FT_ST_DESC_LEN)
 FEAT_DEFAULTS = dict(voxel_size=0.2, k_curvature=10, top_n=100, min_kp_dist=0.3, k_descriptor=30, ratio_threshold=0.8,
                      ransac_iterations=1000, inlier_threshold=0.5, min_inliers=3)            # slam.py:72-83
 
@@ -186,10 +205,10 @@ class FeatureAlignBatch:
     (u0, u1) to the matches i = floor(u0 * n), j = floor(u1 * (n - 1)), j += (j >= i) — two distinct matches, every
     pair of them equally likely, as ``np.random.choice(n, 2, replace=False)`` gives.  Neither: ``rng`` seeded with 0.
 
-    A pair the kernels could not align — status 2, a filtered cloud above the 2 048 rows they hold on chip, or status 5,
-    descriptors of different lengths (NumPy raises there in the reference) — has no feature start: identity, zeros, 0
-    inliers in its record and ``init_out`` left as ``init_in``, as for the reference's own early returns; the status in
-    slot 12 says which."""
+    A pair the kernels could not align — FEAT_ST_CAPACITY, a filtered cloud above the 2 048 rows they hold on chip, or
+    FEAT_ST_DESC_LEN, descriptors of different lengths (NumPy raises there in the reference) — has no feature start:
+    identity, zeros, 0 inliers in its record and ``init_out`` left as ``init_in``, as for the reference's own early returns;
+    the status in slot ``_lib.FTREC_STATUS`` says which."""
 
     def __init__(self, clouds, pair_src, pair_tgt, feat_cfg=None, hypotheses=None, rng=None, init_in=None, init_out=None, like=None):
         require_gpu()
@@ -223,7 +242,7 @@ class FeatureAlignBatch:
             rng = rng if rng is not None else np.random.default_rng(0)
             self.hyp_u = torch.from_numpy(rng.random((self.n_iter, 2))).to(dev)
         self.init_in, self.init_out = init_in, init_out
-        self.records = torch.zeros((max(self.B, 1), REC_DOUBLES), dtype=torch.float64, device=dev)
+        self.records = torch.zeros((max(self.B, 1), _lib.FTREC_DOUBLES), dtype=torch.float64, device=dev)
         need = L.icpmi_feature_align_batch_workspace_bytes(self.raw.total_rows, self.raw.n_clouds, self.raw.max_n, self.B,
                                                            int(cfg["top_n"]), 1 if init_in is not None else 0)
         self.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
@@ -240,9 +259,11 @@ class FeatureAlignBatch:
         return self.records
 
     def results(self, records=None):
-        """-> (R [B,2,2], t [B,2], n_inliers [B], records [B,16]) on the host (synchronises); records[:, 12] is the status."""
+        """-> (R [B,2,2], t [B,2], n_inliers [B], records [B,16]) on the host (synchronises); slot ``_lib.FTREC_STATUS`` of a
+        record is the status."""
         rec = (self.records if records is None else records).cpu().numpy()[:self.B]
-        return rec[:, 6:10].reshape(-1, 2, 2).copy(), rec[:, 10:12].copy(), rec[:, 5].astype(np.int64), rec
+        R, t = rec[:, _lib.FTREC_R:_lib.FTREC_R + 4], rec[:, _lib.FTREC_T:_lib.FTREC_T + 2]
+        return R.reshape(-1, 2, 2).copy(), t.copy(), rec[:, _lib.FTREC_INLIERS].astype(np.int64), rec
 
 
 def rotation_search_batch(sources, targets, voxel_size=0.3, angle_step_coarse=2.0, angle_step_fine=0.2):
@@ -271,7 +292,7 @@ class RunIcpPairBatch:
     — rotation search (``alignment_method`` "rotation_search", the default), feature alignment ("features") or the search
     followed by the feature alignment from its result ("both") — then ICP of every pair from its own R_init / t_init:
     one stream, no host round trip; returns the (B, 16) ICP result tensor (icpmi.batch.unpack_results).  With a feature
-    alignment, ``unpack()`` adds ``info["feature_records"]`` (FeatureAlignBatch; slot 12: status — a pair the feature
+    alignment, ``unpack()`` adds ``info["feature_records"]`` (FeatureAlignBatch; slot FTREC_STATUS: status — a pair the feature
     kernels could not align simply has no feature start).
 
     The pairs are loop-closure candidates in the caller's order.  ``error_accept``: the gate of slam.py:582-597 (the first
@@ -311,9 +332,10 @@ class RunIcpPairBatch:
         self.index_base, self.index_stride = int(index_base), int(index_stride)
         if self.stop:
             self.icp.set_gate(self.error_accept, self.search.records if self.use_search else None, self.index_base, self.index_stride)
-        # a pair can fall outside the on-chip search (status 2) only with a capacity hint, a raw cloud above the search's
-        # 2 048 rows or more angles than it tabulates (csrc/rotsearch.hip): only then may first_accepted() need the host
-        self.capacity_possible = self.use_search and (self.search.too_many_angles or max_rows_hint > 0 or raw.max_n > 2048)
+        # a pair can fall outside the on-chip search (ST_CAPACITY) only with a capacity hint, a raw cloud above the rows the
+        # search holds or more angles than it tabulates: only then may first_accepted() need the host
+        self.capacity_possible = self.use_search and (self.search.too_many_angles or max_rows_hint > 0 or
+                                                      raw.max_n > _lib.RSB_MAX_ROWS)
 
     def run(self, events=None):
         if not self.use_search:                            # "features": no search
@@ -323,7 +345,7 @@ class RunIcpPairBatch:
             # more angles than the batched kernel tabulates (a step below ~0.36 degrees): every pair is searched by the
             # single-pair entry, as pairs beyond the capacity hint are — same numbers
             self.search.records.zero_()
-            self.search.records[:, 11] = ST_CAPACITY
+            self.search.records[:, _lib.RSBREC_STATUS] = ST_CAPACITY
             if self.stop:
                 self.icp.first_accepted_dev.fill_(-1)  # no candidate ran on the device: unpack() redoes them in order
             if events is not None:
@@ -342,7 +364,7 @@ class RunIcpPairBatch:
             raise ValueError("first_accepted() needs stop_after_first_accepted=True")
         first = int(self.icp.first_accepted_dev.item())
         if self.capacity_possible:
-            st = self.search.records[:self.B, 11]
+            st = self.search.records[:self.B, _lib.RSBREC_STATUS]
             lim = self.B if first < 0 else (first - self.index_base) // self.index_stride
             if bool((st[:lim] == ST_CAPACITY).any()) or bool((st == ST_NO_FINE).any()):
                 return self.unpack()[3]["first_accepted"]
@@ -365,9 +387,9 @@ class RunIcpPairBatch:
                                     p.error_threshold, p.max_iterations, self.icp.voxel_size, Rs, ts,
                                     "point_to_line" if self.icp.use_p2l else "point_to_point", self.icp.normal_k,
                                     None if p.max_corr_dist < 0 else p.max_corr_dist)
-        r = np.zeros(16)
-        r[0:4] = Ri[0].reshape(4); r[9:11] = ti[0]; r[12] = ei[0]
-        r[13] = info["delta"][0]; r[14] = info["iters"][0]; r[15] = info["status"][0]
+        r = np.zeros(_lib.RES_DOUBLES)
+        r[_lib.RES_R:_lib.RES_R + 4] = Ri[0].reshape(4); r[_lib.RES_T:_lib.RES_T + 2] = ti[0]; r[_lib.RES_ERR] = ei[0]
+        r[_lib.RES_DELTA] = info["delta"][0]; r[_lib.RES_ITERS] = info["iters"][0]; r[_lib.RES_STATUS] = info["status"][0]
         return r
 
     def unpack(self):
@@ -378,9 +400,10 @@ class RunIcpPairBatch:
         rec = self.search.records.cpu().numpy()[:self.B] if self.use_search else np.zeros((self.B, REC_DOUBLES))
         res = self.icp.results.cpu().numpy()[:self.B].copy()
         self.redone_feature_records = {}
-        if (rec[:, 11].astype(np.int64) == ST_NO_FINE).any():
+        status = rec[:, _lib.RSBREC_STATUS].astype(np.int64)
+        if (status == ST_NO_FINE).any():
             raise ValueError("attempt to get argmin of an empty sequence")          # features.py:231: np.argmin of an empty fine grid
-        over = np.flatnonzero(rec[:, 11].astype(np.int64) == ST_CAPACITY)
+        over = np.flatnonzero(status == ST_CAPACITY)
         first = -1
         if self.stop:
             # the device's answer never counts a status-2 candidate (its device ICP started from the wrong pose): the
@@ -393,12 +416,12 @@ class RunIcpPairBatch:
                 idx = self.index_base + int(i) * self.index_stride
                 if self.stop and 0 <= first < idx:
                     res[i, :] = 0.0
-                    res[i, 0] = res[i, 3] = 1.0
-                    res[i, 12] = res[i, 13] = np.inf
-                    res[i, 15] = _lib.ST_SKIPPED
+                    res[i, _lib.RES_R] = res[i, _lib.RES_R + 3] = 1.0
+                    res[i, _lib.RES_ERR] = res[i, _lib.RES_DELTA] = np.inf
+                    res[i, _lib.RES_STATUS] = _lib.ST_SKIPPED
                     continue
                 res[i, :] = self._redo(i, R0, t0, clouds)
-                if self.stop and res[i, 12] < self.error_accept:
+                if self.stop and res[i, _lib.RES_ERR] < self.error_accept:
                     first = idx
         R, t, err, info = unpack_results(res, 2)
         if self.features is not None:

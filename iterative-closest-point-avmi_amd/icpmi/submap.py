@@ -18,6 +18,7 @@ the same kernels; both take the submap as a NumPy array or as the device tensor
 import numpy as np
 import torch
 
+from . import _lib
 from . import batch as _b
 
 VERBOSE = True      # the reference prints a line for corrections above one degree
@@ -145,7 +146,7 @@ def submap_rotation_search(source_local, submap_global, predicted_pose, angle_ra
     back 16 doubles.  The angle grids are the reference's NumPy expressions (every fine grid that can follow a coarse
     winner is tabulated up front); R and t are the reference's bit for bit.
     """
-    from utilities.features import _SearchContext, arange_rows
+    from utilities.features import _SearchContext, arange_rows, winning_angle
     _b.require_gpu()
     predicted_pose = np.asarray(predicted_pose, dtype=np.float64)
     src_in, tgt_in = _device_rows(source_local), _device_rows(submap_global)
@@ -168,49 +169,38 @@ def submap_rotation_search(source_local, submap_global, predicted_pose, angle_ra
     dtab = ctx.device_table(angles, fine, fine_n)
     max_fine = int(fine.shape[1])
     ws = ctx.workspace(ns, nt, len(angles), max_fine)
-    _b._lib.check(_b._lib.lib().icpmi_rotation_search(_b._ptr(ctx.pts), ns, nt, float(voxel_size), _b._ptr(dtab[0]), len(angles),
-                                                      _b._ptr(dtab[1]) if max_fine else None, _b._ptr(dtab[2]) if max_fine else None,
-                                                      max_fine, 0, float(pred_t[0]), float(pred_t[1]), _b._ptr(ctx.rec), _b._ptr(ws),
-                                                      ws.numel(), _b._stream()), "submap_rotation_search")
-    L = _b._lib.lib()
-    on_device = ns <= 2048                                                    # the refinement's finishing workgroup holds the rows in LDS
+    L = _lib.lib()
+    _lib.check(L.icpmi_rotation_search(_b._ptr(ctx.pts), ns, nt, float(voxel_size), _b._ptr(dtab[0]), len(angles),
+                                       _b._ptr(dtab[1]) if max_fine else None, _b._ptr(dtab[2]) if max_fine else None,
+                                       max_fine, 0, float(pred_t[0]), float(pred_t[1]), _b._ptr(ctx.rec), _b._ptr(ws),
+                                       ws.numel(), _b._stream()), "submap_rotation_search")
+    on_device = ns <= _lib.RSR_MAX_ROWS                                       # the refinement's finishing workgroup holds the rows in LDS
     if on_device:
         # translation: one nearest-neighbour centroid step over the closest 80 %, slam.py:161-181, still on the device
         need = L.icpmi_rotation_refine_workspace_bytes(ns)
         if getattr(ctx, "ref_ws", None) is None or ctx.ref_ws.numel() < need:
             ctx.ref_ws = torch.empty(2 * need, dtype=torch.uint8, device=ctx.dev)
             ctx.ref_out = torch.zeros(4, dtype=torch.float64, device=ctx.dev)
-        _b._lib.check(L.icpmi_rotation_refine(_b._ptr(ws), ns, nt, _b._ptr(ctx.rec), _b._ptr(dtab[0]),
-                                              _b._ptr(dtab[1]) if max_fine else None, max_fine, float(pred_t[0]), float(pred_t[1]),
-                                              _b._ptr(ctx.ref_out), _b._ptr(ctx.ref_ws), ctx.ref_ws.numel(), _b._stream()),
-                      "submap_rotation_search (refinement)")
+        _lib.check(L.icpmi_rotation_refine(_b._ptr(ws), ns, nt, _b._ptr(ctx.rec), _b._ptr(dtab[0]),
+                                           _b._ptr(dtab[1]) if max_fine else None, max_fine, float(pred_t[0]), float(pred_t[1]),
+                                           _b._ptr(ctx.ref_out), _b._ptr(ctx.ref_ws), ctx.ref_ws.numel(), _b._stream()),
+                   "submap_rotation_search (refinement)")
         both = torch.cat([ctx.rec, ctx.ref_out]).cpu().numpy()                # one read-back
-        rec, ref = both[:12], both[12:]
+        rec, ref = both[:_lib.RSREC_DOUBLES], both[_lib.RSREC_DOUBLES:]
     else:
         rec = ctx.rec.cpu().numpy()
-    if rec[0] < 5 or rec[1] < 5:                                              # slam.py:128-129
+    if rec[_lib.RSREC_NS] < 5 or rec[_lib.RSREC_NT] < 5:                      # slam.py:128-129
         return predicted_pose[:2, :2], predicted_pose[:2, 2]
-    if on_device:
-        k = int(rec[6])
-        best_angle = angles[k]
-        if int(rec[8]) > 0:                                                   # slam.py:157-159
-            best_angle = fine[k, int(rec[9])]
-        correction = np.degrees(best_angle - pred_theta)
-        if abs(correction) > 1.0 and VERBOSE:
-            print(f"  Submap rotation correction: {correction:+.1f}°")
-        ca, sa = np.cos(best_angle), np.sin(best_angle)
-        return np.array([[ca, -sa], [sa, ca]]), ref[:2].copy()
-    src_d, tgt_d = ctx.filtered_clouds(ns, nt, rec)
-    src = src_d.cpu().numpy()
-    k = int(rec[6])
-    best_angle = angles[k]
-    if int(rec[8]) > 0:                                                       # slam.py:157-159
-        best_angle = fine[k, int(rec[9])]
+    best_angle = winning_angle(angles, fine, rec, coarse_without_fine=True)   # slam.py:157-159
     correction = np.degrees(best_angle - pred_theta)
     if abs(correction) > 1.0 and VERBOSE:
         print(f"  Submap rotation correction: {correction:+.1f}°")
     ca, sa = np.cos(best_angle), np.sin(best_angle)
     R_best = np.array([[ca, -sa], [sa, ca]])
+    if on_device:
+        return R_best, ref[:2].copy()
+    src_d, tgt_d = ctx.filtered_clouds(ns, nt, rec)
+    src = src_d.cpu().numpy()
     # translation: one nearest-neighbour centroid step, slam.py:168-181
     rotated_src = src @ R_best.T
     placed = rotated_src + pred_t

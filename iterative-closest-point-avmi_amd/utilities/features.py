@@ -25,8 +25,8 @@ import torch
 
 from icpmi import _lib
 from icpmi import batch as _b
-from icpmi.prealign import (AngleTables, FeatureAlignBatch, arange_rows, rotation_search_batch,  # noqa: F401
-                            run_icp_pair_batch)
+from icpmi.prealign import (AngleTables, FeatureAlignBatch, arange_rows, device_angle_tables,  # noqa: F401
+                            rotation_search_batch, run_icp_pair_batch, winning_angle)
 
 VERBOSE = True      # the reference prints one line per search
 
@@ -76,8 +76,8 @@ class _SearchContext:
         self.dev = dev
         self.cap = 0
         self.tables = {}
-        self.rec = torch.zeros(12, dtype=torch.float64, device=dev)
-        self.rec_host = torch.zeros(12, dtype=torch.float64).pin_memory()
+        self.rec = torch.zeros(_lib.RSREC_DOUBLES, dtype=torch.float64, device=dev)
+        self.rec_host = torch.zeros(_lib.RSREC_DOUBLES, dtype=torch.float64).pin_memory()
         self.ws = None
 
     def upload(self, src, tgt):
@@ -100,14 +100,10 @@ class _SearchContext:
         return self.ws
 
     def device_table(self, coarse, fine, fine_n):
-        """cos / sin of the coarse angles and of every fine grid (features.py:214 uses np.cos / np.sin) on the device."""
-        cs = np.ascontiguousarray(np.stack([np.cos(coarse), np.sin(coarse)], axis=1))
-        fcs = np.ascontiguousarray(np.stack([np.cos(fine), np.sin(fine)], axis=2)) if fine.size else np.zeros((len(coarse), 0, 2))
-        return (torch.from_numpy(cs).to(self.dev), torch.from_numpy(fcs).to(self.dev),
-                torch.from_numpy(np.ascontiguousarray(fine_n, dtype=np.int32)).to(self.dev))
+        return device_angle_tables(self.dev, coarse, fine, fine_n)
 
     def run(self, src, tgt, voxel_size, coarse, fine, fine_n, dtab, centred, shift):
-        """-> the 12-double record on the host (one synchronisation), see include/icpmi.h icpmi_rotation_search."""
+        """-> the record on the host (one synchronisation; slots _lib.RSREC_*, include/icpmi.h icpmi_rotation_search)."""
         d_cs, d_fcs, d_fn = dtab
         pts = self.upload(src, tgt)
         max_fine = int(fine.shape[1]) if fine.ndim == 2 else 0
@@ -122,8 +118,8 @@ class _SearchContext:
 
     def filtered_clouds(self, n_src, n_tgt, rec):
         """Views of the voxel-filtered source and target the last run left in the workspace (device, no copy)."""
-        v = self.ws[256:256 + (n_src + n_tgt) * 16].view(torch.float64).reshape(-1, 2)
-        return v[:int(rec[0])], v[n_src:n_src + int(rec[1])]
+        v = self.ws[_lib.RS_WS_CLOUDS:_lib.RS_WS_CLOUDS + (n_src + n_tgt) * 16].view(torch.float64).reshape(-1, 2)
+        return v[:int(rec[_lib.RSREC_NS])], v[n_src:n_src + int(rec[_lib.RSREC_NT])]
 
 
 def _as_rows(a, name):
@@ -140,20 +136,17 @@ def rotation_search(source, target, voxel_size=0.3, angle_step_coarse=2.0, angle
     """Brute-force rotation search — features.py:165-242.  Returns (R (2,2), t (2,), score).
 
     One chain of launches on the device (voxel filters, means, coarse sweep, arg-min, fine sweep, arg-min) and one
-    12-double read-back; the angle grids, their cos / sin and the final R, t are the reference's NumPy expressions."""
+    read-back of the record; the angle grids, their cos / sin and the final R, t are the reference's NumPy expressions."""
     src, tgt = _as_rows(source, "source"), _as_rows(target, "target")
     ctx = _SearchContext.get()
     tab = AngleTables.get(ctx.dev, angle_step_coarse, angle_step_fine)            # features.py:221, 227-229 for every possible winner
     angles_coarse, fine, fine_n, dtab = tab.coarse, tab.fine, tab.fine_n, tab.device_table
     rec = ctx.run(src, tgt, voxel_size, angles_coarse, fine, fine_n, dtab, True, (0.0, 0.0))
-    if rec[0] < 5 or rec[1] < 5:                                               # features.py:203-204
+    if rec[_lib.RSREC_NS] < 5 or rec[_lib.RSREC_NT] < 5:                       # features.py:203-204
         return np.eye(2), np.zeros(2), float("inf")
-    k = int(rec[6])
-    if int(rec[8]) <= 0:
-        raise ValueError("attempt to get argmin of an empty sequence")         # np.argmin(scores_fine) on an empty grid
-    best_angle = fine[k, int(rec[9])]
-    best_score = np.float64(rec[10])
-    mu_s, mu_t = rec[2:4].copy(), rec[4:6].copy()
+    best_angle = winning_angle(angles_coarse, fine, rec)                       # (raises as np.argmin on an empty fine grid)
+    best_score = np.float64(rec[_lib.RSREC_FSCORE])
+    mu_s, mu_t = rec[_lib.RSREC_MUS:_lib.RSREC_MUS + 2].copy(), rec[_lib.RSREC_MUT:_lib.RSREC_MUT + 2].copy()
     ca, sa = np.cos(best_angle), np.sin(best_angle)
     R = np.array([[ca, -sa], [sa, ca]])
     t = mu_t - R @ mu_s
@@ -164,7 +157,7 @@ def rotation_search(source, target, voxel_size=0.3, angle_step_coarse=2.0, angle
 
 
 # ── feature-based pre-alignment, features.py:22-160, 247-315 ─────────────────────────────────────────
-FEAT_MAX_ROWS, FEAT_MAX_KP, FEAT_DESC_STRIDE = 2048, 256, 32          # csrc/features.hip
+FEAT_MAX_ROWS, FEAT_MAX_KP, FEAT_DESC_STRIDE = _lib.FT_MAX_ROWS, _lib.FT_MAX_KP, _lib.FT_DESC_STRIDE
 
 
 def _pairwise_sq(a, b):
@@ -320,7 +313,7 @@ def ransac_align(kp_s, kp_t, matches, n_iter=1000, inlier_thresh=0.5):
     kp[1, :len(kp_t)] = np.arange(len(kp_t))
     mm = np.zeros((stride, 2), dtype=np.int32)
     mm[:n] = m
-    rec = torch.zeros((1, 16), dtype=torch.float64, device=dev)
+    rec = torch.zeros((1, _lib.FTREC_DOUBLES), dtype=torch.float64, device=dev)
     d_kp, d_kc, d_ps, d_pt = _i32(kp, dev), _i32([len(kp_s), len(kp_t)], dev), _i32([0], dev), _i32([1], dev)
     d_m, d_mc, d_hyp = _i32(mm, dev), _i32([n], dev), _i32(hyp, dev)
     _lib.check(_lib.lib().icpmi_feature_ransac_batch(
@@ -329,7 +322,7 @@ def ransac_align(kp_s, kp_t, matches, n_iter=1000, inlier_thresh=0.5):
         None, _b._stream()),
         "ransac_align")
     r = rec.cpu().numpy()[0]
-    return r[6:10].reshape(2, 2).copy(), r[10:12].copy(), int(r[5])
+    return r[_lib.FTREC_R:_lib.FTREC_R + 4].reshape(2, 2).copy(), r[_lib.FTREC_T:_lib.FTREC_T + 2].copy(), int(r[_lib.FTREC_INLIERS])
 
 
 def feature_based_alignment(source, target, voxel_size=0.2, k_curvature=10, top_n=100, min_kp_dist=0.3, k_descriptor=30,

@@ -769,6 +769,51 @@ def test_rotation_scores_against_oracle(uicp):
         assert int(np.argmin(got)) == int(np.argmin(ref))
 
 
+def _jittered_lattice(n, seed, spacing=0.5):
+    """n points on a square lattice, each moved by at most a tenth of the spacing: two of them differ by at least 0.4 along
+    an axis, so a voxel filter at 0.3 keeps every one (as its own voxel's mean: the point itself)."""
+    w = int(np.ceil(np.sqrt(n)))
+    i = np.arange(n)
+    return (np.stack([i % w, i // w], axis=1) + np.random.default_rng(seed).uniform(-0.1, 0.1, (n, 2))) * spacing
+
+
+@pytest.mark.parametrize("n_src", [5, 256, 257, 600])          # a lone partial trip of the row loop, an exact one, a tail of one, several
+def test_single_search_and_standalone_scores_run_one_loop(uicp, n_src):
+    """The sweeps of icpmi_rotation_search and icpmi_rotation_scores are ONE scoring loop (csrc/rotsearch.hip:
+    rs_score_angle): scored by the stand-alone entry on the filtered clouds the search left behind, centred on the
+    record's means, the winning coarse and fine angles get the record's scores bit for bit; both agree with the oracle to
+    the bound of test_rotation_scores_against_oracle; the record's means are np.mean(axis=0) of the filtered clouds bit for
+    bit.  Targets of 5 rows and of one below, at and one above the tile of the nearest-target walk (RS_TILE_POINTS)."""
+    from icpmi import _lib
+    from icpmi.prealign import arange_rows
+    from utilities import features
+    tile = 2048                                                   # RS_TILE_POINTS
+    coarse = np.deg2rad(np.arange(-180, 180, 45.0))              # eight coarse angles, six fine ones around each
+    fine, fine_n = arange_rows(coarse - np.deg2rad(45.0), coarse + np.deg2rad(45.0), np.deg2rad(15.0))
+    ctx = features._SearchContext.get()
+    dtab = ctx.device_table(coarse, fine, fine_n)
+    th = np.deg2rad(20.0)
+    R = np.array([[np.cos(th), -np.sin(th)], [np.sin(th), np.cos(th)]])
+    src = _jittered_lattice(n_src, 100 + n_src) @ R.T + (3.0, 2.0)
+    for n_tgt in (5, tile - 1, tile, tile + 1):
+        tgt = _jittered_lattice(n_tgt, 200 + n_tgt)
+        rec = ctx.run(src, tgt, 0.3, coarse, fine, fine_n, dtab, True, (0.0, 0.0))
+        assert (rec[_lib.RSREC_NS], rec[_lib.RSREC_NT]) == (n_src, n_tgt)                  # the filter kept every row
+        fs, ft = (c.cpu().numpy() for c in ctx.filtered_clouds(n_src, n_tgt, rec))
+        mu_s, mu_t = rec[_lib.RSREC_MUS:_lib.RSREC_MUS + 2], rec[_lib.RSREC_MUT:_lib.RSREC_MUT + 2]
+        assert np.array_equal(mu_s, np.mean(fs, axis=0)) and np.array_equal(mu_t, np.mean(ft, axis=0))
+        k, nf, j = int(rec[_lib.RSREC_K]), int(rec[_lib.RSREC_NF]), int(rec[_lib.RSREC_J])
+        assert nf == fine_n[k] == 6
+        for angles, win, slot in ((coarse, k, _lib.RSREC_CSCORE), (fine[k, :nf], j, _lib.RSREC_FSCORE)):
+            got = features.rotation_scores(fs - mu_s, ft, angles, mu_t)
+            ref = oracle.rotation_scores(fs - mu_s, ft, angles, mu_t)
+            print(f"n_src {n_src} n_tgt {n_tgt} slot {slot}: record {rec[slot]!r} stand-alone {got[win]!r} oracle {ref[win]!r} "
+                  f"max |got - ref| {np.abs(got - ref).max():.3e}")
+            assert got[win] == rec[slot] and win == int(np.argmin(got))                    # bit for bit: one loop, one order
+            assert np.abs(got - ref).max() <= 1e-13 * max(1.0, ref.max())
+            assert abs(rec[slot] - ref[win]) <= 1e-13 * max(1.0, ref.max())
+
+
 # ── submap rotation search + scan-to-submap attempt (SURVEY §8f rank 1, slam.py:111-225) ──
 @pytest.mark.parametrize("case", ["cfg", "default", "imu_narrow", "far_off"])
 def test_submap_rotation_search_golden(uicp, case, capsys):

@@ -87,6 +87,52 @@ SIZE_TABLE = {
 }
 
 
+def test_record_layouts_are_named_once_in_the_header():
+    """include/icpmi.h names the slots, statuses and capacities of the rotation-search and feature records; icpmi._lib
+    mirrors every one of them (ICPMI_<NAME> -> _lib.<NAME>) and the names prealign / utilities.features exported before are
+    aliases of them."""
+    from icpmi import _lib, prealign
+    from utilities import features
+    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    defines = {n: int(v) for n, v in re.findall(r"^#define ICPMI_(\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", txt, flags=re.M)}
+    families = ("RSREC_", "RS_WS_", "RSR_", "RSBREC_", "RSB_", "FTREC_", "FT_")
+    named = {n for n in defines if n.startswith(families)}
+    assert len(named) == 43     # search: 10 + 4 slots, 4 statuses, 2 offsets, 3 capacities; features: 11 slots, 6 statuses, 3 capacities
+    for n in named:
+        assert getattr(_lib, n) == defines[n], n
+    for n, v in defines.items():                              # and whatever else the binding mirrors (RES_*, ST_*, ERR_*) agrees
+        assert getattr(_lib, n, v) == v, n
+    assert _lib.RES_DOUBLES == defines["RES_DOUBLES"] and _lib.ERR_HIP == defines["ERR_HIP"] == -3
+    assert [defines[n] for n in ("RSBREC_STATUS", "RSBREC_DOUBLES", "FTREC_STATUS", "FTREC_DOUBLES", "RSREC_DOUBLES")] == [11, 16, 12, 16, 12]
+    assert (prealign.ST_OK, prealign.ST_FEW, prealign.ST_CAPACITY, prealign.ST_NO_FINE) == tuple(
+        defines[n] for n in ("RSB_ST_OK", "RSB_ST_FEW", "RSB_ST_CAPACITY", "RSB_ST_NO_FINE")) == (0, 1, 2, 3)
+    assert prealign.REC_DOUBLES == defines["RSBREC_DOUBLES"] == defines["FTREC_DOUBLES"]
+    assert prealign.RSB_MAX_ANGLES == defines["RSB_MAX_ANGLES"] == 1024
+    feat = ("OK", "FEW_ROWS", "CAPACITY", "FEW_KP", "FEW_MATCHES", "DESC_LEN")
+    assert [getattr(prealign, "FEAT_ST_" + n) for n in feat] == [defines["FT_ST_" + n] for n in feat] == list(range(6))
+    assert (features.FEAT_MAX_ROWS, features.FEAT_MAX_KP, features.FEAT_DESC_STRIDE) == (
+        defines["FT_MAX_ROWS"], defines["FT_MAX_KP"], defines["FT_DESC_STRIDE"]) == (2048, 256, 32)
+
+
+def test_winning_angle_of_a_search_record():
+    """icpmi.prealign.winning_angle: the fine angle a record names, for one record and for a batch of them; a winner
+    without a fine grid raises as np.argmin does (features.py:231) or, for the submap search, falls back to the coarse
+    angle (slam.py:157-159)."""
+    from icpmi import _lib
+    from icpmi.prealign import winning_angle
+    coarse = np.array([0.1, 0.2, 0.3])
+    fine = np.arange(12.0).reshape(3, 4)
+    rec = np.zeros((3, _lib.RSBREC_DOUBLES))
+    rec[:, _lib.RSREC_K], rec[:, _lib.RSREC_NF], rec[:, _lib.RSREC_J] = (2, 0, 1), (4, 3, 0), (3, 1, 0)
+    assert np.array_equal(winning_angle(coarse, fine, rec[:2]), [11.0, 1.0])
+    assert winning_angle(coarse, fine, rec[0]) == 11.0 and winning_angle(coarse, fine, rec[0], coarse_without_fine=True) == 11.0
+    with pytest.raises(ValueError, match="argmin of an empty sequence"):
+        winning_angle(coarse, fine, rec[2])
+    assert winning_angle(coarse, fine, rec[2], coarse_without_fine=True) == 0.2
+    assert winning_angle(coarse, np.zeros((3, 0)), rec[2], coarse_without_fine=True) == 0.2
+    assert np.array_equal(winning_angle(coarse, fine, rec, coarse_without_fine=True), [11.0, 1.0, 0.2])
+
+
 def test_two_hip_runtimes_in_one_process_are_named():
     """libicpmi.so loaded BEFORE torch maps /opt/rocm's libamdhip64 and torch then maps its own — every
     launch would fail with a bare ICPMI_ERR_HIP.  icpmi_runtime_check names the two copies; the Python loader raises with
