@@ -14,7 +14,9 @@ end to end on a synthetic drive:
     loop closure:   every candidate goes through _run_icp_pair (rotation    slam.py:566-620, 53-98
                     search, then ICP from its result) — all candidates in
                     ONE batch, nothing returning to the host between the
-                    search and the ICP (icpmi.prealign) — and, as in
+                    search and the ICP, against past scans that were
+                    filtered and put in search order once, when they were
+                    appended (icpmi.history.ScanHistory) — and, as in
                     the reference, the FIRST candidate in order whose error
                     is below the gate is accepted: it adds a pose-graph
                     edge, the graph is optimised, poses are rewritten, the
@@ -29,6 +31,7 @@ It also writes and re-reads the drive in the reference's wire formats: lidar lin
 `timestamp_us;qx;qy;qz;qw` (services/imu_service.py:1-38).
 
     python examples/slam_loop.py [n_scans] [--imu] [--loop]      (--loop: a closed circuit, 1.2 laps)
+                                 [--reference-candidates]        (candidates by slam.py:230-268's rule)
 """
 import os
 import sys
@@ -40,6 +43,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "iterative-closest-point-avmi_amd"))
 
 from icpmi import batch, prealign, synth  # noqa: E402
+from icpmi.history import ScanHistory, find_loop_candidates  # noqa: E402
 from icpmi.submap import RollingSubmap  # noqa: E402
 from utilities import features  # noqa: E402
 from utilities import icp as uicp  # noqa: E402
@@ -132,9 +136,24 @@ class GpuBackend:
                                                       stop_after_first_accepted=True)
         return R, t, err, info["iters"], info["first_accepted"]
 
+    History = ScanHistory
+
+    @staticmethod
+    def match_history_first_accepted(hist, source_id, cand_ids, feat_cfg, icp_cfg, error_accept):
+        """The same against scans resident in ``hist`` (a ``History`` with the voxel sizes and normal_k of the two
+        configurations), by id: nothing is uploaded, filtered or put in search order again.  Same records bit for bit."""
+        m = hist.match(source_id, cand_ids, error_threshold=icp_cfg["error_threshold"], max_iterations=icp_cfg["max_iterations"],
+                       method=icp_cfg["method"], angle_step_coarse=feat_cfg["angle_step_coarse"],
+                       angle_step_fine=feat_cfg["angle_step_fine"], error_accept=error_accept, stop_after_first_accepted=True)
+        m.run()
+        R, t, err, info = m.unpack()
+        return R, t, err, info["iters"], info["first_accepted"]
+
 
 def run(n_scans=60, log_path=None, verbose=True, imu_path=None, loop=False, use_submap=True, lc_error_threshold=0.05,
-        backend=None, max_candidates=5):
+        backend=None, max_candidates=5, reference_candidates=False):
+    """reference_candidates: pick the loop-closure candidates with ``find_loop_candidates`` (slam.py:230-268: a cumulative
+    travel gate, nearest first) instead of this harness' short rule (the first ``max_candidates`` old scans within 3 m)."""
     from icpmi import submap as submap_mod
     uicp.VERBOSE = features.VERBOSE = submap_mod.VERBOSE = upg.VERBOSE = False
     be = backend or GpuBackend
@@ -156,6 +175,10 @@ def run(n_scans=60, log_path=None, verbose=True, imu_path=None, loop=False, use_
     submap = be.Submap(window=40, voxel_size=0.04)
     history, mapper, timing = [], None, {"s2s": 0.0, "submap": 0.0, "map": 0.0, "loop": 0.0}
     closures, rejected, accepted = [], [], []
+    feat_kw = dict(rotation_voxel_size=0.15, angle_step_coarse=1.5, angle_step_fine=0.1)
+    # the past scans, prepared once on the device (a backend without a History matches the arrays, batch by batch)
+    resident = be.History(voxel_size=icp_kw["voxel_size"], normal_k=icp_kw["normal_k"],
+                          rotation_voxel_size=feat_kw["rotation_voxel_size"]) if hasattr(be, "History") else None
     graph = be.Graph()
     prev = None
     for i, cur in enumerate(scans):
@@ -195,7 +218,9 @@ def run(n_scans=60, log_path=None, verbose=True, imu_path=None, loop=False, use_
         mapper.update_scan(pose[:2, 2], world)
         timing["map"] += time.perf_counter() - t0
         submap.push(world)
-        history.append((cur, pose.copy()))
+        history.append((cur, pose.copy()))                                    # slam.py:554
+        if resident is not None:
+            resident.add(cur)
         node = graph.add_node(pose_matrix_to_vec(pose))                      # slam.py:543-549: node + odometry edge
         if node > 0:
             odo_err = err if err <= 0.15 else 0.15
@@ -205,10 +230,15 @@ def run(n_scans=60, log_path=None, verbose=True, imu_path=None, loop=False, use_
         # chained on the device — and the FIRST whose error is below the gate wins (slam.py:582-597)
         t0 = time.perf_counter()
         if i >= 30 and i % 10 == 0:
-            cands = [k for k, (_, pk) in enumerate(history[:-20]) if np.linalg.norm(pk[:2, 2] - pose[:2, 2]) < 3.0][:max_candidates]
+            if reference_candidates:
+                cands = [k for k, _ in find_loop_candidates(pose, [pk for _, pk in history], i, 3.0, 20, max_candidates)]
+            else:
+                cands = [k for k, (_, pk) in enumerate(history[:-20]) if np.linalg.norm(pk[:2, 2] - pose[:2, 2]) < 3.0][:max_candidates]
             if cands:
-                feat_kw = dict(rotation_voxel_size=0.15, angle_step_coarse=1.5, angle_step_fine=0.1)
-                if hasattr(be, "run_icp_pairs_first_accepted"):      # the candidates after the accepted one may stop early
+                if resident is not None:                             # the current scan is the last one added
+                    R, t, err, its, first = be.match_history_first_accepted(resident, len(history) - 1, cands, feat_kw, icp_kw,
+                                                                            lc_error_threshold)
+                elif hasattr(be, "run_icp_pairs_first_accepted"):      # the candidates after the accepted one may stop early
                     R, t, err, its, first = be.run_icp_pairs_first_accepted(cur, [history[k][0] for k in cands], feat_kw,
                                                                             icp_kw, lc_error_threshold)
                 else:
@@ -255,4 +285,4 @@ if __name__ == "__main__":
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     run(int(args[0]) if args else 60, log_path="/tmp/icpmi_demo_lidar.csv",
         imu_path="/tmp/icpmi_demo_imu.csv" if "--imu" in sys.argv else None, loop="--loop" in sys.argv,
-        use_submap="--no-submap" not in sys.argv)
+        use_submap="--no-submap" not in sys.argv, reference_candidates="--reference-candidates" in sys.argv)

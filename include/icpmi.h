@@ -344,6 +344,61 @@ int icpmi_rotation_search_batch(const double* pts, const int32_t* off_dev, const
                                 int32_t max_rows_hint, double* out_records, double* out_init,
                                 void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- resident scan history: the loop-closure candidates of slam.py:566-597 are PAST scans (slam.py:554 appends one per
+ * scan to scan_history; pose-graph optimisation moves their poses, slam.py:606-607, never their points), so everything
+ * _run_icp_pair (slam.py:53-98) derives from a target alone is computed once, when the scan enters the history --------
+ * The state is the caller's memory, named by this struct (host).  pts / off_dev: a cloud set of scan_capacity RAW 2-D
+ * clouds packed back to back (the filter takes a cloud's rows from its offsets), a cloud not added yet having zero rows:
+ * off[c] = rows in use for every c at or above the number of scans.  ids[c] = c (device).  Per row of row_capacity:
+ * the raw rows, the two filtered copies (16 B each) and the two prepared buffers (icpmi_prepared_bytes(row_capacity,
+ * scan_capacity, 0) bytes each, about 40 B a row); per cloud: the two counts and the mean (rs_means [scan_capacity][2]).
+ * Both prepared buffers are laid out for (row_capacity, scan_capacity) — never for the rows in use, which change with
+ * every scan — and start out from icpmi_prepared_relayout.  voxel_ws: icpmi_voxel_workspace_bytes(4096) bytes. */
+typedef struct icpmi_history {
+    const double* pts;        /* raw clouds                                                   */
+    const int32_t* off_dev;   /* [scan_capacity + 1]                                          */
+    const int32_t* ids;       /* [scan_capacity], ids[c] = c                                  */
+    double* icp_vox;          /* filtered at icp_voxel (icp.py:149-150), cloud set layout     */
+    int32_t* icp_cnt;
+    void* icp_prepared;       /* icpmi_prepare_targets_ex of them, allow_polar, normal_k      */
+    double* rs_vox;           /* filtered at rs_voxel (features.py:198-199)                   */
+    int32_t* rs_cnt;
+    double* rs_means;         /* np.mean(axis=0) of each (features.py:205-206)                */
+    void* rs_prepared;        /* search order of them, no normals                             */
+    void* voxel_ws;
+    size_t prepared_bytes;    /* of each prepared buffer                                      */
+    size_t voxel_ws_bytes;
+    double icp_voxel;
+    double rs_voxel;
+    int32_t scan_capacity;
+    int32_t row_capacity;
+    int32_t normal_k;         /* < 0: no normals (a point_to_point history)                   */
+    int32_t allow_polar;      /* of the ICP's prepared buffer; 0 once a scan has more than 2048 rows */
+} icpmi_history;
+
+/* Processes the clouds [first, first + n_new) and leaves every other cloud's state as it is: voxel filter at icp_voxel,
+ * icpmi_prepare_targets_ex of them into icp_prepared (prepare != 0), voxel filter at rs_voxel, their means, their search
+ * order into rs_prepared (prepare != 0) — the steps ICP (icp.py:149-173) and rotation_search (features.py:198-211) take
+ * per call, by the same kernels.  prepare == 0: a cloud that is only ever a SOURCE (the current scan staged behind the
+ * last one).  off_host mirrors off_dev.  A cloud above 4096 rows: ICPMI_ERR_UNSUPPORTED. */
+int icpmi_history_add(const icpmi_history* h, const int32_t* off_host, int32_t first, int32_t n_new, int32_t prepare,
+                      void* stream);
+
+/* The second half of icpmi_rotation_search_batch on the resident state: same arguments from pair_src on, same records,
+ * out_init and statuses (features.py:213-242).  max_n: rows of the largest RAW cloud any pair names (sizes the on-chip
+ * copies).  A pair whose target was never added reports ICPMI_RSB_ST_CAPACITY. */
+int icpmi_history_search(const icpmi_history* h, const int32_t* pair_src, const int32_t* pair_tgt, int32_t n_pairs,
+                         int32_t max_n, const double* coarse_cs, int32_t n_coarse, const double* fine_cs,
+                         const int32_t* fine_cnt, int32_t max_fine, int32_t max_rows_hint, double* out_records,
+                         double* out_init, void* stream);
+
+/* Copies the first rows_used rows and clouds_used clouds of a prepared buffer laid out for (src_rows, src_clouds) into
+ * one laid out for (dst_rows, dst_clouds) >= them, and marks every further cloud of dst "no order" (what
+ * icpmi_history_search reports as ICPMI_RSB_ST_CAPACITY).  src == NULL with nothing in use: a fresh buffer.  No
+ * reference counterpart: scan_history is a Python list (slam.py:554). */
+int icpmi_prepared_relayout(const void* src, int32_t src_rows, int32_t src_clouds, int32_t rows_used, int32_t clouds_used,
+                            void* dst, size_t dst_bytes, int32_t dst_rows, int32_t dst_clouds, void* stream);
+
 /* ---- feature-based pre-alignment, utilities/features.py:35-160, 247-315 ------------------------------------------
  * The five stages of feature_based_alignment, each on a cloud set of 2-D clouds (pts / off_dev / cnt_dev as above;
  * cloud_ids[n_sel]: the clouds to process, NULL = clouds 0..n_sel-1), one workgroup per cloud or per pair with the cloud

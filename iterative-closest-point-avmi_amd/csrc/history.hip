@@ -1,0 +1,83 @@
+// history.hip — a resident, append-only set of prepared scans for loop-closure matching.
+//
+// Reference slam.py:566-597: the candidates of a loop closure are past scans (scan_history, appended at slam.py:554), and
+// each is matched by _run_icp_pair (slam.py:53-98), which filters the target twice (features.py:198-199, icp.py:149-150),
+// takes its mean (features.py:206) and builds two k-d trees of it (features.py:211, icp.py:173) — every time, although a
+// past scan never changes (pose-graph optimisation moves its pose, slam.py:606-607).  Here those steps run once, when the
+// scan is added, and a query is the search kernel and the ICP kernels on the state they left.
+//
+// No kernel of its own: the filter (voxel.hip), the prepare kernels (prep.hip) and both halves of the rotation search
+// (rotsearch.hip) are the batch path's, run on a range of clouds; growing is device-to-device copies.
+//
+// Two things a history must get right, both because its clouds are a prefix of a larger allocation:
+//  - a prepared buffer's arrays are carved from a row count (PreparedView).  That count is the history's row CAPACITY,
+//    fixed until a relayout — with the rows in use, every array would move at every add;
+//  - the filter takes a cloud's rows from off[c + 1] - off[c], so the raw clouds lie back to back and the clouds not
+//    added yet have zero rows (off[c] = rows in use).
+#include "prep_common.hpp"
+#include "rotsearch.hpp"
+
+namespace icpmi {
+
+constexpr int HISTORY_MAX_ROWS = 4096;      // the on-chip path of every kernel involved (prep.hip: PREP_MAX_POINTS)
+
+static bool history_complete(const icpmi_history* h) {
+    return h && h->pts && h->off_dev && h->ids && h->icp_vox && h->icp_cnt && h->icp_prepared && h->rs_vox && h->rs_cnt &&
+           h->rs_means && h->rs_prepared && h->scan_capacity > 0 && h->row_capacity > 0 &&
+           h->prepared_bytes >= icpmi_prepared_bytes(h->row_capacity, h->scan_capacity, 0);
+}
+
+}  // namespace icpmi
+
+extern "C" int icpmi_history_add(const icpmi_history* h, const int32_t* off_host, int32_t first, int32_t n_new, int32_t prepare,
+                                 void* stream) {
+    using namespace icpmi;
+    if (!history_complete(h) || !off_host || first < 0 || n_new < 0 || first > h->scan_capacity - n_new) return ICPMI_ERR_ARG;
+    if (!(h->icp_voxel > 0.0) || !(h->rs_voxel > 0.0)) return ICPMI_ERR_ARG;
+    if (n_new == 0) return ICPMI_OK;
+    int max_n, end_row;
+    if (off_host[first] < 0 || !cloud_rows(off_host + first, n_new, max_n, end_row)) return ICPMI_ERR_ARG;
+    if (end_row > h->row_capacity) return ICPMI_ERR_ARG;
+    if (max_n > HISTORY_MAX_ROWS) return ICPMI_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    const int32_t* ids = h->ids + first;
+    // ICP: filter, then search order and normals (IcpBatch.run's two launches, for this range)
+    int rc = icpmi_voxel_downsample_batch(h->pts, h->off_dev + first, off_host + first, n_new, 2, h->icp_voxel, h->icp_vox,
+                                          h->icp_cnt + first, h->voxel_ws, h->voxel_ws_bytes, stream);
+    if (rc != ICPMI_OK) return rc;
+    if (prepare) {
+        rc = icpmi_prepare_targets_ex(h->icp_vox, h->off_dev, off_host, h->icp_cnt, ids, nullptr, n_new, h->scan_capacity,
+                                      h->row_capacity, max_n, h->normal_k < 0 ? -1 : h->normal_k, nullptr, h->icp_prepared,
+                                      h->prepared_bytes, h->allow_polar, stream);
+        if (rc != ICPMI_OK) return rc;
+    }
+    // rotation search: filter, means, search order (the first half of icpmi_rotation_search_batch, for this range)
+    rc = rsb_filter_means(h->pts, h->off_dev, off_host, first, n_new, h->rs_voxel, h->rs_vox, h->rs_cnt, h->rs_means, h->voxel_ws,
+                          h->voxel_ws_bytes, st);
+    if (rc != ICPMI_OK || !prepare) return rc;
+    return icpmi_prepare_targets_ex(h->rs_vox, h->off_dev, off_host, h->rs_cnt, ids, nullptr, n_new, h->scan_capacity, h->row_capacity,
+                                    max_n, -1, nullptr, h->rs_prepared, h->prepared_bytes, rsb_allow_polar(), stream);
+}
+
+extern "C" int icpmi_history_search(const icpmi_history* h, const int32_t* pair_src, const int32_t* pair_tgt, int32_t n_pairs,
+                                    int32_t max_n, const double* coarse_cs, int32_t n_coarse, const double* fine_cs,
+                                    const int32_t* fine_cnt, int32_t max_fine, int32_t max_rows_hint, double* out_records,
+                                    double* out_init, void* stream) {
+    using namespace icpmi;
+    if (!history_complete(h)) return ICPMI_ERR_ARG;
+    const RsbState s{h->rs_vox, h->off_dev, h->rs_cnt, h->rs_means, h->rs_prepared, h->row_capacity};
+    return rsb_search(s, max_n, max_rows_hint, pair_src, pair_tgt, n_pairs, coarse_cs, n_coarse, fine_cs, fine_cnt, max_fine,
+                      out_records, out_init, (hipStream_t)stream);
+}
+
+extern "C" int icpmi_prepared_relayout(const void* src, int32_t src_rows, int32_t src_clouds, int32_t rows_used, int32_t clouds_used,
+                                       void* dst, size_t dst_bytes, int32_t dst_rows, int32_t dst_clouds, void* stream) {
+    using namespace icpmi;
+    if (!dst || rows_used < 0 || clouds_used < 0 || dst_rows < rows_used || dst_clouds < clouds_used) return ICPMI_ERR_ARG;
+    if (src ? (src_rows < rows_used || src_clouds < clouds_used) : (rows_used > 0 || clouds_used > 0)) return ICPMI_ERR_ARG;
+    if (dst_bytes < icpmi_prepared_bytes(dst_rows, dst_clouds, 0)) return ICPMI_ERR_WORKSPACE;
+    const PreparedView from(src, src ? src_rows : 0), to(dst, dst_rows);
+    if (prepared_relayout(from, to, (size_t)rows_used, (size_t)clouds_used, (size_t)dst_clouds, (hipStream_t)stream) != hipSuccess)
+        return ICPMI_ERR_HIP;
+    return ICPMI_OK;
+}

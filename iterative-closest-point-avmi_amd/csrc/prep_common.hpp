@@ -28,6 +28,22 @@ struct PreparedView {
     }
 };
 
+// The first `rows` rows and `clouds` clouds of one prepared buffer into another laid out for more of either (a history that
+// grows): a copy per array, and "no order" (0xFF words, which every reader refuses) for the clouds of dst behind them.
+inline hipError_t prepared_relayout(const PreparedView& src, const PreparedView& dst, size_t rows, size_t clouds, size_t dst_clouds,
+                                    hipStream_t st) {
+    const auto copy = [st](void* d, const void* s, size_t bytes) {
+        return bytes ? hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToDevice, st) : hipSuccess;
+    };
+    hipError_t e = copy(dst.sxy, src.sxy, rows * sizeof(double2));
+    if (e == hipSuccess) e = copy(dst.snrm, src.snrm, rows * sizeof(double2));
+    if (e == hipSuccess) e = copy(dst.sorig, src.sorig, rows * sizeof(int32_t));
+    if (e == hipSuccess) e = copy(dst.skey, src.skey, rows * sizeof(float));
+    if (e == hipSuccess) e = copy(dst.dir, src.dir, clouds * sizeof(int32_t));
+    if (e == hipSuccess && dst_clouds > clouds) e = hipMemsetAsync(dst.dir + clouds, 0xFF, (dst_clouds - clouds) * sizeof(int32_t), st);
+    return e;
+}
+
 // prep_big.hip, called by prep.hip for every cloud above its LDS capacity: the scratch a cloud of n rows needs, and one cloud
 size_t prep_big_scratch_bytes(int n);
 int prep_big_cloud(const double* P, const int32_t* cnt_c, int n_cap, int normal_k, double2* o_sxy, double2* o_snrm,

@@ -10,6 +10,7 @@
 // `np.mean(dists ** 2)` does, fixed-tree workgroup sum.
 #include "nn.hpp"
 #include "prep_common.hpp"
+#include "rotsearch.hpp"
 #include "sweep.hpp"
 
 namespace icpmi {
@@ -608,15 +609,15 @@ __global__ __launch_bounds__(RSB_THREADS, 4) void rotation_search_batch_kernel(R
     }
 }
 
-// np.mean(cloud, axis=0) of every filtered cloud (see rs_means_kernel): a wave per cloud
+// np.mean(cloud, axis=0) of the filtered clouds [first, first + n_clouds) (see rs_means_kernel): a wave per cloud
 constexpr int RSB_MEAN_WAVES = 4;
 __global__ __launch_bounds__(RSB_MEAN_WAVES* ICPMI_WAVE) void rsb_means_kernel(const double* __restrict__ vox, const int32_t* __restrict__ off,
-                                                                                const int32_t* __restrict__ cnt, int n_clouds,
+                                                                                const int32_t* __restrict__ cnt, int first, int n_clouds,
                                                                                 double* __restrict__ means) {
     __shared__ double2 rows[RSB_MEAN_WAVES][RS_MEAN_ROWS];
     const int w = wave_id(), lane = lane_id();
-    const int c = blockIdx.x * RSB_MEAN_WAVES + w;
-    if (c >= n_clouds) return;                                          // whole waves leave: no workgroup barrier below
+    const int c = first + blockIdx.x * RSB_MEAN_WAVES + w;
+    if (c >= first + n_clouds) return;                                          // whole waves leave: no workgroup barrier below
     const int n = cnt[c];
     const double s = rs_column_sum(reinterpret_cast<const double2*>(vox) + off[c], n, rows[w]);
     if (lane < 2) means[2 * c + lane] = s / (double)n;
@@ -668,14 +669,13 @@ struct RsbPlan {
     int max_n, total_rows;    // rows of the largest raw cloud, of all of them
     int cap;                  // rows of a cloud the on-chip copies hold
     size_t lds;               // dynamic LDS of the search kernel
-    int means_grid;
     int allow_polar;          // the targets may be put in bearing order
     int prune;                // 0: score every angle
 };
-static RsbPlan plan_rotation_search_batch(const int32_t* off_host, int n_clouds, int max_rows_hint, RsBatchOption opt) {
+// (max_n, total_rows: rows of the largest raw cloud a pair can name, and the row count the state is laid out for)
+static RsbPlan plan_rotation_search(int max_n, int total_rows, int max_rows_hint, RsBatchOption opt) {
     RsbPlan p{};
-    p.rc = ICPMI_ERR_ARG;
-    if (!cloud_rows(off_host, n_clouds, p.max_n, p.total_rows)) return p;
+    p.max_n = max_n; p.total_rows = total_rows;
     p.rc = ICPMI_ERR_UNSUPPORTED;
     if (p.max_n > 4096) return p;                                        // single-pair entry (icpmi_rotation_search) for larger clouds
     p.rc = ICPMI_OK;
@@ -686,12 +686,55 @@ static RsbPlan plan_rotation_search_batch(const int32_t* off_host, int n_clouds,
     if (max_rows_hint > 0 && max_rows_hint < p.cap) p.cap = max_rows_hint;
     p.cap = (p.cap + 63) / 64 * 64;
     p.lds = (size_t)p.cap * 48 + 32 + 32 * (size_t)sweepf_tree_leaves(p.cap);
-    p.means_grid = (n_clouds + RSB_MEAN_WAVES - 1) / RSB_MEAN_WAVES;
     // search order of the targets: a projection or, for scans in their sensor frame, the bearing (the library's estimate;
     // any order is exact for any query)
     p.allow_polar = opt == RsBatchOption::projection ? 0 : 1;
     p.prune = opt == RsBatchOption::full ? 0 : 1;
     return p;
+}
+static RsbPlan plan_rotation_search_batch(const int32_t* off_host, int n_clouds, int max_rows_hint, RsBatchOption opt) {
+    int max_n, total_rows;
+    if (!cloud_rows(off_host, n_clouds, max_n, total_rows)) { RsbPlan p{}; p.rc = ICPMI_ERR_ARG; return p; }
+    return plan_rotation_search(max_n, total_rows, max_rows_hint, opt);
+}
+
+int rsb_filter_means(const double* pts, const int32_t* off_dev, const int32_t* off_host, int first, int n, double voxel,
+                     double* vox, int32_t* cnt, double* means, void* vws, size_t vws_bytes, hipStream_t st) {
+    if (n <= 0) return ICPMI_OK;
+    // the filter takes a cloud's rows from its offsets and writes them where they were: a range is the same call on the
+    // tail of the offsets
+    const int rc = icpmi_voxel_downsample_batch(pts, off_dev + first, off_host + first, n, 2, voxel, vox, cnt + first, vws, vws_bytes, st);
+    if (rc != ICPMI_OK) return rc;
+    rsb_means_kernel<<<(n + RSB_MEAN_WAVES - 1) / RSB_MEAN_WAVES, RSB_MEAN_WAVES * ICPMI_WAVE, 0, st>>>(vox, off_dev, cnt, first, n, means);
+    ICPMI_LAUNCH_CHECK();
+    return ICPMI_OK;
+}
+
+int rsb_allow_polar() { return parse_rs_batch_option(option("RS_BATCH")) == RsBatchOption::projection ? 0 : 1; }
+
+static int rsb_launch_search(const RsbPlan& plan, const RsbState& s, const int32_t* pair_src, const int32_t* pair_tgt, int n_pairs,
+                             const double* coarse_cs, int n_coarse, const double* fine_cs, const int32_t* fine_cnt, int max_fine,
+                             double* out_records, double* out_init, hipStream_t st) {
+    const PreparedView v(s.prepared, s.layout_rows);
+    const RsbArgs a{s.vox, s.off, s.cnt, s.means, pair_src, pair_tgt, v.sxy, v.sorig, v.skey, v.dir, coarse_cs, n_coarse,
+                    fine_cs, fine_cnt, max_fine, out_records, out_init, plan.cap, plan.prune};
+    if (dyn_lds((const void*)rotation_search_batch_kernel, plan.lds) != hipSuccess) return ICPMI_ERR_HIP;
+    rotation_search_batch_kernel<<<n_pairs, RSB_THREADS, plan.lds, st>>>(a);
+    ICPMI_LAUNCH_CHECK();
+    return ICPMI_OK;
+}
+
+int rsb_search(const RsbState& s, int max_n, int max_rows_hint, const int32_t* pair_src, const int32_t* pair_tgt, int n_pairs,
+               const double* coarse_cs, int n_coarse, const double* fine_cs, const int32_t* fine_cnt, int max_fine,
+               double* out_records, double* out_init, hipStream_t st) {
+    if (!pair_src || !pair_tgt || !coarse_cs || !out_records) return ICPMI_ERR_ARG;
+    if (n_pairs < 0 || n_coarse <= 0 || max_fine < 0 || max_rows_hint < 0 || max_n < 0) return ICPMI_ERR_ARG;
+    if (max_fine > 0 && (!fine_cs || !fine_cnt)) return ICPMI_ERR_ARG;
+    if (n_coarse > RSB_MAX_ANGLES || max_fine > RSB_MAX_ANGLES) return ICPMI_ERR_UNSUPPORTED;
+    if (n_pairs == 0) return ICPMI_OK;
+    const RsbPlan plan = plan_rotation_search(max_n, s.layout_rows, max_rows_hint, parse_rs_batch_option(option("RS_BATCH")));
+    if (plan.rc != ICPMI_OK) return plan.rc;
+    return rsb_launch_search(plan, s, pair_src, pair_tgt, n_pairs, coarse_cs, n_coarse, fine_cs, fine_cnt, max_fine, out_records, out_init, st);
 }
 
 // scratch of the refinement: rotated rows | squared distances | matched rows (n_src of each)
@@ -775,20 +818,15 @@ extern "C" int icpmi_rotation_search_batch(const double* pts, const int32_t* off
     if (workspace_bytes < w.bytes) return ICPMI_ERR_WORKSPACE;
     const PreparedView v(w.prepared, plan.total_rows, n_clouds);
     hipStream_t st = (hipStream_t)stream;
-    int rc = icpmi_voxel_downsample_batch(pts, off_dev, off_host, n_clouds, 2, voxel_size, w.vox, w.cnt, w.vws, w.vws_bytes, stream);
+    int rc = rsb_filter_means(pts, off_dev, off_host, 0, n_clouds, voxel_size, w.vox, w.cnt, w.means, w.vws, w.vws_bytes, st);
     if (rc != ICPMI_OK) return rc;
-    rsb_means_kernel<<<plan.means_grid, RSB_MEAN_WAVES * ICPMI_WAVE, 0, st>>>(w.vox, off_dev, w.cnt, n_clouds, w.means);
     // a pair whose target is not among tgt_ids must report "no order" (ICPMI_RSB_ST_CAPACITY), not search whatever the workspace held
     if (hipMemsetAsync(v.dir, 0xFF, (size_t)n_clouds * sizeof(int32_t), st) != hipSuccess) return ICPMI_ERR_HIP;
     rc = icpmi_prepare_targets_ex(w.vox, off_dev, off_host, w.cnt, tgt_ids, nullptr, tgt_ids ? n_tgt_ids : n_clouds, n_clouds, plan.total_rows,
                                   plan.max_n, -1, nullptr, w.prepared, w.prepared_bytes, plan.allow_polar, stream);
     if (rc != ICPMI_OK) return rc;
-    const RsbArgs a{w.vox, off_dev, w.cnt, w.means, pair_src, pair_tgt, v.sxy, v.sorig, v.skey, v.dir, coarse_cs, n_coarse,
-                    fine_cs, fine_cnt, max_fine, out_records, out_init, plan.cap, plan.prune};
-    if (dyn_lds((const void*)rotation_search_batch_kernel, plan.lds) != hipSuccess) return ICPMI_ERR_HIP;
-    rotation_search_batch_kernel<<<n_pairs, RSB_THREADS, plan.lds, st>>>(a);
-    ICPMI_LAUNCH_CHECK();
-    return ICPMI_OK;
+    return rsb_launch_search(plan, RsbState{w.vox, off_dev, w.cnt, w.means, w.prepared, plan.total_rows}, pair_src, pair_tgt, n_pairs,
+                             coarse_cs, n_coarse, fine_cs, fine_cnt, max_fine, out_records, out_init, st);
 }
 
 extern "C" size_t icpmi_rotation_refine_workspace_bytes(int32_t n_src) {

@@ -2,9 +2,20 @@
 
 Host side of libicpmi.so: ``icpmi.batch`` (batched scan-pair ICP on one GPU),
 ``icpmi.dist`` (the same batch sharded over the GPUs of a node), ``icpmi.synth``
-(synthetic scans).  The drop-in modules with the reference's own names live in
+(synthetic scans), ``icpmi.history`` (``ScanHistory``: past scans kept prepared on the
+device for loop-closure matching).  The drop-in modules with the reference's own names live in
 the sibling package ``utilities`` (``utilities.icp``, ``utilities.mapping``).
 """
 from ._lib import IcpmiError, build, lib  # noqa: F401
 
 __version__ = "0.1"
+
+
+def __getattr__(name):
+    # icpmi.ScanHistory / icpmi.find_loop_candidates: icpmi.history's, imported on first use (that module needs torch;
+    # `import icpmi` alone — the build, the scan generator in spawned processes — must not)
+    if name in ("ScanHistory", "find_loop_candidates", "history"):
+        import importlib
+        history = importlib.import_module(".history", __name__)
+        return history if name == "history" else getattr(history, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -36,6 +36,15 @@ class IcpParams(C.Structure):
                 ("has_init", C.c_int32), ("dim", C.c_int32)]
 
 
+class History(C.Structure):
+    """icpmi_history (include/icpmi.h): the device buffers of a resident scan history."""
+    _fields_ = [("pts", C.c_void_p), ("off_dev", C.c_void_p), ("ids", C.c_void_p), ("icp_vox", C.c_void_p), ("icp_cnt", C.c_void_p),
+                ("icp_prepared", C.c_void_p), ("rs_vox", C.c_void_p), ("rs_cnt", C.c_void_p), ("rs_means", C.c_void_p),
+                ("rs_prepared", C.c_void_p), ("voxel_ws", C.c_void_p), ("prepared_bytes", C.c_size_t), ("voxel_ws_bytes", C.c_size_t),
+                ("icp_voxel", C.c_double), ("rs_voxel", C.c_double), ("scan_capacity", C.c_int32), ("row_capacity", C.c_int32),
+                ("normal_k", C.c_int32), ("allow_polar", C.c_int32)]
+
+
 class IcpmiError(RuntimeError):
     pass
 
@@ -93,6 +102,11 @@ _SIGS = {
     "icpmi_rotation_search_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                               C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                               C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "icpmi_history_add": (C.c_int, [C.POINTER(History), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "icpmi_history_search": (C.c_int, [C.POINTER(History), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "icpmi_prepared_relayout": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32,
+                                          C.c_int32, C.c_void_p]),
     "icpmi_feature_curvature_batch": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "icpmi_feature_keypoints_batch": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double,
                                                 C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),

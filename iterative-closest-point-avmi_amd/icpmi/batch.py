@@ -264,6 +264,11 @@ class IcpBatch:
         self.gate = None
         self.first_accepted_dev = None
 
+    @property
+    def layout_rows(self):
+        """The row count ``prepared`` is laid out for: the set's rows (a resident history: its row capacity)."""
+        return self.raw.total_rows
+
     def set_gate(self, error_accept, search_records=None, index_base=0, index_stride=1):
         """Stop after the first accepted pair (slam.py:582-597; include/icpmi.h, icpmi_icp_batch_gated): from now on
         ``run()`` lets pairs after the first one with err < error_accept (and, with ``search_records``, a rotation-search
@@ -282,6 +287,11 @@ class IcpBatch:
         """Enqueue voxel filter -> normals -> fused ICP on the current stream; returns the device result tensor.
 
         events: optional (start, end) torch.cuda.Event pair recorded around the fused ICP launch only."""
+        self.prepare()
+        return self.launch_icp(events)
+
+    def prepare(self):
+        """The per-cloud half of ``run()``: voxel filter of every cloud, search order (and normals) of the targets."""
         L = _lib.lib()
         st = _stream()
         voxel_downsample_set(self.raw, self.voxel_size, out=self.vox, workspace=self.vox_ws)
@@ -300,10 +310,15 @@ class IcpBatch:
                                            _ptr(self.tgt_ids_dev), len(self.tgt_ids), self.raw.total_rows,
                                            self.max_tgt_n, self.normal_k, _ptr(self.normals), _ptr(self.nrm_ws),
                                            self.nrm_ws.numel(), st), "estimate_normals_2d")
+
+    def launch_icp(self, events=None):
+        """The per-pair half of ``run()``: the fused ICP on the filtered clouds and prepared targets -> the result tensor."""
+        L = _lib.lib()
+        st = _stream()
         if events is not None:
             events[0].record()
         args = (_ptr(self.vox.pts), _ptr(self.vox.off), _ptr(self.vox.cnt), _ptr(self.normals), _ptr(self.prepared),
-                _ptr(self.pair_src), _ptr(self.pair_tgt), self.B, self.max_src_n, self.max_tgt_n, self.raw.total_rows,
+                _ptr(self.pair_src), _ptr(self.pair_tgt), self.B, self.max_src_n, self.max_tgt_n, self.layout_rows,
                 C.byref(self.params), _ptr(self.init), _ptr(self.results), _ptr(self.icp_ws),
                 self.icp_ws.numel() if self.icp_ws is not None else 0)
         if self.gate is None:

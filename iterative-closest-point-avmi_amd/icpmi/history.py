@@ -1,0 +1,355 @@
+"""A scan history that stays prepared on the device, for loop-closure matching.
+
+The reference picks its loop-closure candidates from ``scan_history`` (slam.py:566-574, ``_find_loop_candidates``,
+slam.py:230-268) and runs ``_run_icp_pair(points, scan_history[idx][0], ...)`` on each (slam.py:575-579).  A past scan
+never changes — pose-graph optimisation moves its pose, not its points (slam.py:606-607) — yet every ``_run_icp_pair``
+filters it twice, takes its mean and builds two k-d trees of it.  ``ScanHistory`` does that work once, when the scan is
+appended (slam.py:554), and a query is the rotation-search kernel and the ICP kernels on what it left:
+
+    hist = ScanHistory(voxel_size=0.06, normal_k=10, rotation_voxel_size=0.3)
+    sid = hist.add(points)                                     # slam.py:554
+    cands = find_loop_candidates(pose, poses, sid, 3.0, 50, 5) # slam.py:566-574
+    m = hist.match(sid, [k for k, _ in cands], error_accept=0.05, stop_after_first_accepted=True)
+    m.run(); first = m.first_accepted()                        # slam.py:575-597
+
+``match`` returns a ``RunIcpPairBatch`` whose clouds are the resident ones: ``run()`` / ``unpack()`` / ``first_accepted()``
+are that class's own code, and its records are the batch path's bit for bit (same kernels on the same filtered rows).
+
+torch is used for device memory and streams only; the device work is include/icpmi.h's ``icpmi_history_*``.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import IcpParams, check
+from .batch import PREP_MAX_POINTS, CloudSet, IcpBatch, _ptr, _stream, require_gpu
+from .prealign import AngleTables, REC_DOUBLES, RSB_MAX_ANGLES, RotationSearchBatch, RunIcpPairBatch
+
+
+def find_loop_candidates(current_pose, poses, current_idx, distance_threshold, min_interval, max_candidates,
+                         min_cumulative_travel=10.0):
+    """``_find_loop_candidates`` (slam.py:230-268) -> [(idx, dist), ...]: the scans at least ``min_interval`` scans old,
+    closer than ``distance_threshold`` to the current position and at least ``min_cumulative_travel`` of driven path away
+    (a robot standing still has not come back), nearest first (equal distances in scan order), at most ``max_candidates``.
+
+    poses: a sequence of 3 x 3 pose matrices or an (n, 2) array of positions; current_pose: a 3 x 3 matrix or a position.
+    Host only and vectorised: the poses live in the pose graph on the host, and there are thousands of them at most."""
+    cur = np.asarray(current_pose, dtype=np.float64)
+    cur = cur[:2, 2] if cur.ndim == 2 else cur[:2]
+    P = np.asarray(poses, dtype=np.float64)
+    if P.ndim == 3:
+        P = P[:, :2, 2]
+    P = P.reshape(-1, 2)
+    n = len(P)
+    if n == 0:
+        return []
+    step = np.diff(P, axis=0)
+    cum = np.zeros(n)
+    np.cumsum(np.sqrt(step[:, 0] ** 2 + step[:, 1] ** 2), out=cum[1:])        # slam.py:247-251, summed in scan order
+    d = cur[None, :] - P
+    dist = np.sqrt(d[:, 0] ** 2 + d[:, 1] ** 2)                                # slam.py:258
+    travel = cum[current_idx] - cum if current_idx < n else np.zeros(n)        # slam.py:263
+    # the reference's three `continue`s, negated as it writes them (a NaN fails none of them)
+    keep = ~(current_idx - np.arange(n) < min_interval) & ~(dist >= distance_threshold) & ~(travel < min_cumulative_travel)
+    idx = np.flatnonzero(keep)
+    idx = idx[np.argsort(dist[idx], kind="stable")][:max_candidates]
+    return [(int(k), float(dist[k])) for k in idx]
+
+
+class _ResidentIcp(IcpBatch):
+    """``IcpBatch`` over a history's filtered clouds and prepared targets: ``run()`` is the ICP launch alone."""
+
+    def __init__(self, hist, pair_src, pair_tgt, error_threshold, max_iterations, method, max_corr_dist, R_init, t_init):
+        L = _lib.lib()
+        dev = hist.device
+        if method not in ("point_to_point", "point_to_line"):
+            raise ValueError(f"method must be 'point_to_point' or 'point_to_line', got {method!r}")
+        if method == "point_to_line" and hist.normal_k is None:
+            raise ValueError("this history holds no normals (normal_k=None): point_to_point only")
+        self.history = hist
+        self.raw, self.vox, self.dim = hist.raw, hist.vox, 2
+        self.pair_src_host = np.ascontiguousarray(pair_src, dtype=np.int32)
+        self.pair_tgt_host = np.ascontiguousarray(pair_tgt, dtype=np.int32)
+        self.B = len(self.pair_src_host)
+        self.pair_src = torch.from_numpy(self.pair_src_host).to(dev)
+        self.pair_tgt = torch.from_numpy(self.pair_tgt_host).to(dev)
+        self.voxel_size = hist.voxel_size
+        self.normal_k = -1 if hist.normal_k is None else hist.normal_k
+        self.use_p2l = method == "point_to_line"
+        have_init = R_init is not None and t_init is not None                    # icp.py:153
+        self.params = IcpParams(float(error_threshold), -1.0 if max_corr_dist is None else float(max_corr_dist),
+                                int(max_iterations), _lib.POINT_TO_LINE if self.use_p2l else _lib.POINT_TO_POINT,
+                                1 if have_init else 0, 2)
+        self.init = None
+        if have_init:
+            R = np.broadcast_to(np.asarray(R_init, dtype=np.float64), (self.B, 2, 2)).reshape(self.B, 4)
+            t = np.broadcast_to(np.asarray(t_init, dtype=np.float64), (self.B, 2))
+            self.init = torch.from_numpy(np.ascontiguousarray(np.concatenate([R, t], axis=1))).to(dev)
+        sizes = hist.sizes()
+        self.max_src_n = int(sizes[self.pair_src_host].max()) if self.B else 0
+        self.max_tgt_n = int(sizes[self.pair_tgt_host].max()) if self.B else 0
+        self.normals, self.prepared, self.fast = None, hist.icp_prepared, True
+        self.icp_ws = torch.empty(L.icpmi_icp_workspace_bytes(self.B, self.max_src_n, 2), dtype=torch.uint8, device=dev)
+        self.results = torch.zeros((max(self.B, 1), _lib.RES_DOUBLES), dtype=torch.float64, device=dev)
+        self.gate = None
+        self.first_accepted_dev = None
+
+    @property
+    def layout_rows(self):
+        return self.history.row_capacity
+
+    def prepare(self):
+        raise _lib.IcpmiError("a resident batch is prepared when its scans are added")
+
+    def run(self, events=None):
+        return self.launch_icp(events)
+
+
+class _ResidentSearch(RotationSearchBatch):
+    """``RotationSearchBatch`` over a history's search state: ``run()`` is ``icpmi_history_search``."""
+
+    def __init__(self, hist, pair_src, pair_tgt, angle_step_coarse, angle_step_fine, init, max_rows_hint):
+        dev = hist.device
+        self.history = hist
+        self.raw = hist.raw
+        self.pair_src_host = np.ascontiguousarray(pair_src, dtype=np.int32)
+        self.pair_tgt_host = np.ascontiguousarray(pair_tgt, dtype=np.int32)
+        self.B = len(self.pair_src_host)
+        self.pair_src = torch.from_numpy(self.pair_src_host).to(dev)
+        self.pair_tgt = torch.from_numpy(self.pair_tgt_host).to(dev)
+        self.voxel_size = hist.rotation_voxel_size
+        self.steps = (angle_step_coarse, angle_step_fine)
+        self.tables = AngleTables.get(dev, angle_step_coarse, angle_step_fine)
+        self.max_rows_hint = int(max_rows_hint)
+        self.too_many_angles = len(self.tables.coarse) > RSB_MAX_ANGLES or self.tables.max_fine > RSB_MAX_ANGLES
+        self.records = torch.zeros((max(self.B, 1), REC_DOUBLES), dtype=torch.float64, device=dev)
+        self.init = init
+        sizes = hist.sizes()
+        self.max_n = int(max(sizes[self.pair_src_host].max(), sizes[self.pair_tgt_host].max())) if self.B else 0
+
+    def run(self):
+        t = self.tables
+        mf = t.max_fine
+        check(_lib.lib().icpmi_history_search(
+            C.byref(self.history.state), _ptr(self.pair_src), _ptr(self.pair_tgt), self.B, self.max_n, _ptr(t.d_cs), len(t.coarse),
+            _ptr(t.d_fcs) if mf else None, _ptr(t.d_fn) if mf else None, mf, self.max_rows_hint, _ptr(self.records),
+            _ptr(self.init), _stream()), "rotation_search (history)")
+        return self.records
+
+
+class HistoryMatch(RunIcpPairBatch):
+    """What ``ScanHistory.match`` returns: ``RunIcpPairBatch`` (its ``run`` / ``unpack`` / ``first_accepted``) with the
+    history's resident clouds behind it.  Valid while the history keeps its buffers: ``run()`` raises once the history has
+    grown, or — for a source that was an array — once another scan or source has been staged over it."""
+
+    def __init__(self, hist, source_id, candidates, staged, error_threshold, max_iterations, method, max_corr_dist,
+                 angle_step_coarse, angle_step_fine, max_rows_hint, error_accept, stop_after_first_accepted, index_base,
+                 index_stride):
+        if stop_after_first_accepted and error_accept is None:
+            raise ValueError("stop_after_first_accepted needs a gate: error_accept")
+        B = len(candidates)
+        ps = np.full(B, source_id, dtype=np.int32)
+        self.history = hist
+        self.layout_generation = hist.layout_generation
+        self.stage_generation = hist.stage_generation if staged else None
+        self.icp = _ResidentIcp(hist, ps, candidates, error_threshold, max_iterations, method, max_corr_dist,
+                                np.tile(np.eye(2), (B, 1, 1)), np.zeros((B, 2)))
+        self.B = B
+        self.alignment_method, self.use_search, self.features = "rotation_search", True, None
+        self.search = _ResidentSearch(hist, ps, candidates, angle_step_coarse, angle_step_fine, self.icp.init, max_rows_hint)
+        self._set_gate(error_accept, stop_after_first_accepted, index_base, index_stride, max_rows_hint, self.search.max_n)
+
+    def run(self, events=None):
+        h = self.history
+        if h.layout_generation != self.layout_generation:
+            raise _lib.IcpmiError("the history has grown since this match was made: call match() again")
+        if self.stage_generation is not None and h.stage_generation != self.stage_generation:
+            raise _lib.IcpmiError("the staged source of this match has been overwritten: call match() again")
+        return super().run(events)
+
+
+class ScanHistory:
+    """An append-only set of 2-D scans (at most 4096 rows each: the on-chip kernels) resident on one device, each filtered
+    at the ICP voxel size and at the rotation search's, with its mean and both search orders (and normals from ``normal_k``
+    neighbours; ``None``: a point_to_point-only history) — everything ``_run_icp_pair`` (slam.py:53-98) derives from a
+    target alone, computed once by ``add``.
+
+    The buffers hold ``scan_capacity`` scans and ``row_capacity`` raw rows (128 bytes of device memory per row); either
+    doubles when it is exceeded (new buffers, device-to-device copies), and results do not depend on that."""
+
+    def __init__(self, voxel_size=0.06, normal_k=10, rotation_voxel_size=0.3, scan_capacity=256, row_capacity=None, device=None):
+        require_gpu()
+        if not voxel_size > 0 or not rotation_voxel_size > 0:
+            raise ValueError("voxel sizes must be positive")
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.voxel_size, self.rotation_voxel_size = float(voxel_size), float(rotation_voxel_size)
+        self.normal_k = None if normal_k is None else int(normal_k)
+        self.n_scans = self.rows_used = 0
+        self.allow_polar = True            # until a scan above 2048 rows arrives (the ICP kernels for such targets walk projections)
+        self.layout_generation = self.stage_generation = 0
+        self.scan_capacity = self.row_capacity = 0
+        scan_capacity = max(int(scan_capacity), 1)
+        self._allocate(scan_capacity, max(int(row_capacity), 1) if row_capacity is not None else 1024 * scan_capacity)
+
+    # ── buffers ──────────────────────────────────────────────────────────────
+    def _allocate(self, S, R):
+        """Buffers for S scans and R rows, holding what the current ones hold."""
+        L = _lib.lib()
+        dev, n, rows = self.device, self.n_scans, self.rows_used
+        old = self.__dict__.copy() if self.scan_capacity else None
+        f64 = dict(dtype=torch.float64, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        off_host = np.full(S + 1, rows, dtype=np.int32)
+        if old:
+            off_host[:n + 1] = old["raw"].off_host[:n + 1]
+        self.raw = CloudSet(torch.empty((R, 2), **f64), off_host)
+        self.vox = CloudSet(torch.empty((R, 2), **f64), off_host, cnt=torch.zeros(S, **i32), off=self.raw.off)
+        self.rs_vox = CloudSet(torch.empty((R, 2), **f64), off_host, cnt=torch.zeros(S, **i32), off=self.raw.off)
+        self.rs_means = torch.zeros((S, 2), **f64)
+        self.ids = torch.arange(S, **i32)
+        nbytes = L.icpmi_prepared_bytes(R, S, 0)
+        self.icp_prepared = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.rs_prepared = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.voxel_ws = torch.empty(L.icpmi_voxel_workspace_bytes(PREP_MAX_POINTS), dtype=torch.uint8, device=dev)
+        for name in ("icp_prepared", "rs_prepared"):
+            check(L.icpmi_prepared_relayout(_ptr(old[name]) if old else None, self.row_capacity, self.scan_capacity, rows, n,
+                                            _ptr(getattr(self, name)), nbytes, R, S, _stream()), "prepared_relayout")
+        if old:
+            for new, was in ((self.raw.pts, old["raw"].pts), (self.vox.pts, old["vox"].pts), (self.rs_vox.pts, old["rs_vox"].pts)):
+                new[:rows].copy_(was[:rows])
+            for new, was in ((self.vox.cnt, old["vox"].cnt), (self.rs_vox.cnt, old["rs_vox"].cnt), (self.rs_means, old["rs_means"])):
+                new[:n].copy_(was[:n])
+        self.scan_capacity, self.row_capacity = S, R
+        self.state = _lib.History(self.raw.pts.data_ptr(), self.raw.off.data_ptr(), self.ids.data_ptr(), self.vox.pts.data_ptr(),
+                                  self.vox.cnt.data_ptr(), self.icp_prepared.data_ptr(), self.rs_vox.pts.data_ptr(),
+                                  self.rs_vox.cnt.data_ptr(), self.rs_means.data_ptr(), self.rs_prepared.data_ptr(),
+                                  self.voxel_ws.data_ptr(), nbytes, self.voxel_ws.numel(), self.voxel_size, self.rotation_voxel_size,
+                                  S, R, -1 if self.normal_k is None else self.normal_k, 1 if self.allow_polar else 0)
+        self.layout_generation += 1
+
+    def _reserve(self, scans, rows):
+        S, R = self.scan_capacity, self.row_capacity
+        while S < scans:
+            S *= 2
+        while R < rows:
+            R *= 2
+        if R >= 2 ** 31:
+            raise ValueError("history too large for 32-bit row offsets")
+        if (S, R) != (self.scan_capacity, self.row_capacity):
+            self._allocate(S, R)
+
+    def _place(self, arrs, first, prepare):
+        """Upload the clouds behind the rows in use as clouds first, first + 1, ... and process that range."""
+        rows = self.rows_used
+        ends = rows + np.cumsum([len(a) for a in arrs])
+        self._reserve(first + len(arrs), int(ends[-1]))
+        host = np.concatenate(arrs, axis=0)
+        if len(host):
+            self.raw.pts[rows:int(ends[-1])].copy_(torch.from_numpy(host))
+        k = len(arrs)
+        off = self.raw.off_host                                  # shared by the three cloud sets; clouds behind: zero rows
+        off[first + 1:first + 1 + k] = ends
+        off[first + 1 + k:] = ends[-1]
+        self.raw.off[first + 1:first + 1 + k].copy_(torch.from_numpy(off[first + 1:first + 1 + k]))
+        self.raw.off[first + 1 + k:].fill_(int(ends[-1]))
+        self._process(first, k, prepare)
+        self.stage_generation += 1
+        return int(ends[-1])
+
+    def _process(self, first, n, prepare):
+        check(_lib.lib().icpmi_history_add(C.byref(self.state), self.raw.off_host.ctypes.data_as(C.c_void_p), first, n,
+                                           1 if prepare else 0, _stream()), "history_add")
+
+    @staticmethod
+    def _clouds(clouds):
+        arrs = [np.ascontiguousarray(c, dtype=np.float64) for c in clouds]
+        for a in arrs:
+            if a.ndim != 2 or a.shape[1] != 2:
+                raise ValueError("a scan must be an (n, 2) array")
+            if len(a) > PREP_MAX_POINTS:
+                raise ValueError(f"a scan of {len(a)} rows: the resident history holds scans of at most {PREP_MAX_POINTS} rows "
+                                 "(the on-chip kernels); match larger clouds with RunIcpPairBatch")
+        return arrs
+
+    # ── the public interface ─────────────────────────────────────────────────
+    def __len__(self):
+        return self.n_scans
+
+    def sizes(self):
+        """Raw row count of every cloud slot (host; the scans, then a staged source, then zeros)."""
+        return np.diff(self.raw.off_host)
+
+    def counts(self):
+        """Rows of every scan after the ICP's voxel filter (synchronises)."""
+        return self.vox.cnt[:self.n_scans].cpu().numpy()
+
+    def search_counts(self):
+        """Rows of every scan after the rotation search's voxel filter (synchronises)."""
+        return self.rs_vox.cnt[:self.n_scans].cpu().numpy()
+
+    def add(self, points):
+        """Append one scan (slam.py:554) -> its id."""
+        return self.add_many([points])[0]
+
+    def add_many(self, clouds):
+        """Append scans: one upload and one ``icpmi_history_add`` for the whole range -> their ids."""
+        arrs = self._clouds(clouds)
+        if not arrs:
+            return []
+        first = self.n_scans
+        redo = self.allow_polar and max(len(a) for a in arrs) > 2048 and first > 0
+        if max(len(a) for a in arrs) > 2048:
+            self.allow_polar = False
+            self.state.allow_polar = 0
+        self.rows_used = self._place(arrs, first, prepare=True)
+        self.n_scans = first + len(arrs)
+        if redo:
+            # a target above 2048 rows makes the ICP launch walk projections for every target of its batch: the earlier
+            # scans, in bearing order until now, are put in order again (once in a history's life; their raw rows are here)
+            self._process(0, first, True)
+        return list(range(first, self.n_scans))
+
+    def match(self, source, candidates, *, error_threshold=1e-7, max_iterations=100, method="point_to_line", max_corr_dist=None,
+              angle_step_coarse=2.0, angle_step_fine=0.2, max_rows_hint=0, error_accept=None, stop_after_first_accepted=False,
+              alignment_method="rotation_search", index_base=0, index_stride=1):
+        """``_run_icp_pair(source, scan k, ...)`` for every k of ``candidates`` (slam.py:575-579), in that order (repeats
+        allowed) -> a ``HistoryMatch``.  ``source``: a scan id — the current scan is appended before its candidates are
+        matched, slam.py:554 — or an (n, 2) array, which is staged behind the last scan, filtered and given its means for
+        this match only and is not added.  Voxel sizes and ``normal_k`` are the history's; the other arguments are
+        ``RunIcpPairBatch``'s.  ``index_base`` / ``index_stride``: the candidate number of pair b is index_base + b *
+        index_stride, as there — what a form sharded over ranks (icpmi.dist) would pass; sharding itself is not built.
+
+        ``alignment_method`` other than "rotation_search" is not resident: use ``RunIcpPairBatch``."""
+        if alignment_method != "rotation_search":
+            raise ValueError(f"alignment_method {alignment_method!r} is not resident in a ScanHistory (only 'rotation_search' is): "
+                             "use RunIcpPairBatch for 'features' and 'both'")
+        cands = np.asarray(candidates)
+        if cands.ndim != 1 or (len(cands) and not np.issubdtype(cands.dtype, np.integer)):
+            raise ValueError("candidates must be a 1-D sequence of scan ids")
+        if len(cands) and (cands.min() < 0 or cands.max() >= self.n_scans):
+            raise ValueError(f"candidate ids must lie in [0, {self.n_scans}): got {int(cands.min())}..{int(cands.max())}")
+        cands = np.ascontiguousarray(cands, dtype=np.int32)
+        staged = not isinstance(source, (int, np.integer))
+        if staged:
+            arr = self._clouds([source])
+            self._place(arr, self.n_scans, prepare=False)        # cloud n_scans, for this match: rows_used stays
+            source = self.n_scans
+        elif not 0 <= source < self.n_scans:
+            raise ValueError(f"source id must lie in [0, {self.n_scans}): got {source}")
+        return HistoryMatch(self, int(source), cands, staged, error_threshold, max_iterations, method, max_corr_dist,
+                            angle_step_coarse, angle_step_fine, max_rows_hint, error_accept, stop_after_first_accepted,
+                            index_base, index_stride)
+
+    def icp(self, source_id, target_id, R_init=None, t_init=None, error_threshold=1e-7, max_iterations=100,
+            method="point_to_line", max_corr_dist=None):
+        """``ICP(scan source_id, scan target_id, ...)`` (icp.py:132-223) against the resident prepared target — the
+        scan-to-scan step of slam.py:471 with the previous scan already prepared -> (R, t, err, info) like ``icp_pair``
+        (synchronises)."""
+        for k in (source_id, target_id):
+            if not 0 <= k < self.n_scans:
+                raise ValueError(f"scan ids must lie in [0, {self.n_scans}): got {k}")
+        b = _ResidentIcp(self, [source_id], [target_id], error_threshold, max_iterations, method, max_corr_dist, R_init, t_init)
+        b.run()
+        return b.unpack()

@@ -327,6 +327,10 @@ class RunIcpPairBatch:
         if alignment_method in ("features", "both"):
             self.features = FeatureAlignBatch(raw, pair_src, pair_tgt, feat_cfg, hypotheses, rng,
                                               init_in=self.icp.init if self.use_search else None, init_out=self.icp.init)
+        self._set_gate(error_accept, stop_after_first_accepted, index_base, index_stride, max_rows_hint, raw.max_n)
+
+    def _set_gate(self, error_accept, stop_after_first_accepted, index_base, index_stride, max_rows_hint, max_raw_n):
+        """The gate of slam.py:582-597 over ``self.icp`` / ``self.search`` (max_raw_n: rows of the largest raw cloud of a pair)."""
         self.error_accept = None if error_accept is None else float(error_accept)
         self.stop = bool(stop_after_first_accepted)
         self.index_base, self.index_stride = int(index_base), int(index_stride)
@@ -335,7 +339,7 @@ class RunIcpPairBatch:
         # a pair can fall outside the on-chip search (ST_CAPACITY) only with a capacity hint, a raw cloud above the rows the
         # search holds or more angles than it tabulates: only then may first_accepted() need the host
         self.capacity_possible = self.use_search and (self.search.too_many_angles or max_rows_hint > 0 or
-                                                      raw.max_n > _lib.RSB_MAX_ROWS)
+                                                      max_raw_n > _lib.RSB_MAX_ROWS)
 
     def run(self, events=None):
         if not self.use_search:                            # "features": no search
