@@ -21,7 +21,8 @@ end to end on a synthetic drive:
                     is below the gate is accepted: it adds a pose-graph
                     edge, the graph is optimised, poses are rewritten, the
                     submap buffer and the occupancy grid are rebuilt
-                    (replay of all scans)
+                    (replay of all scans) — from the resident history by
+                    scan id and pose, the scans transformed on the device
 
 The geometry behind the loop is a `backend` (rotation_search, ICP, run_icp_pairs, Submap, Grid, Graph): the MI355X
 drop-ins by default; the tests inject the CPU oracle there to check the whole composition scan by scan.
@@ -258,10 +259,16 @@ def run(n_scans=60, log_path=None, verbose=True, imu_path=None, loop=False, use_
                     graph.optimize(n_iterations=20, fix_node=0)
                     history = [(pts, pose_vec_to_matrix(v)) for (pts, _), v in zip(history, graph.nodes)]
                     pose = history[-1][1].copy()
-                    worlds = [pts @ T[:2, :2].T + T[:2, 2] for pts, T in history]
-                    submap.reset(worlds[-submap.window:])
-                    mapper.reset()                                            # _rebuild_map, slam.py:271-277
-                    mapper.update_scans(np.array([T[:2, 2] for _, T in history]), worlds)
+                    if resident is not None and hasattr(submap, "reset_from_history") and hasattr(mapper, "rebuild_from_history"):
+                        # the raw rows are resident: ids and poses go down, the world rows never visit the host
+                        moved = [T for _, T in history]
+                        submap.reset_from_history(resident, moved)            # slam.py:612-615
+                        mapper.rebuild_from_history(resident, moved)          # _rebuild_map, slam.py:271-277
+                    else:
+                        worlds = [pts @ T[:2, :2].T + T[:2, 2] for pts, T in history]
+                        submap.reset(worlds[-submap.window:])
+                        mapper.reset()                                        # _rebuild_map, slam.py:271-277
+                        mapper.update_scans(np.array([T[:2, 2] for _, T in history]), worlds)
                     accepted.append((i, cands[best], float(np.linalg.norm(pose[:2, 2] - before)), dict(graph.last_info)))
         timing["loop"] += time.perf_counter() - t0
         prev = cur

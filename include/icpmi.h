@@ -392,6 +392,17 @@ int icpmi_history_search(const icpmi_history* h, const int32_t* pair_src, const 
                          const int32_t* fine_cnt, int32_t max_fine, int32_t max_rows_hint, double* out_records,
                          double* out_init, void* stream);
 
+/* transform_points_2d (slam.py:46-50) of resident raw rows, for the rebuilds that follow an accepted closure: the map
+ * replay of _rebuild_map (slam.py:271-277) and the submap buffer of slam.py:612-615 take scan ids and poses, and the world
+ * rows never visit the host.  Rows [out_off[k], out_off[k + 1]) of out_rows are the raw rows of scan ids[k] (h->pts at
+ * off_dev[ids[k]] .. off_dev[ids[k] + 1]) under poses[k] = {R row-major, t}, six doubles, the layout of `init` above.  ids,
+ * poses, out_off [n_ids + 1] and out_rows are device memory; scans may repeat and come in any order; only pts, off_dev and
+ * scan_capacity of h are used.  Bit for bit what NumPy's `points @ T[:2, :2].T + T[:2, 2]` gives: a scan of two or more rows
+ * is a gemm there, fma(y, R[c][1], x * R[c][0]) + t[c]; a scan of exactly ONE row is a gemv, fma(x, R[c][0], y * R[c][1]) +
+ * t[c].  n_ids == 0: no launch, ICPMI_OK.  One launch, no workspace. */
+int icpmi_history_world_rows(const icpmi_history* h, const int32_t* ids, int32_t n_ids, const double* poses,
+                             const int32_t* out_off, double* out_rows, void* stream);
+
 /* Copies the first rows_used rows and clouds_used clouds of a prepared buffer laid out for (src_rows, src_clouds) into
  * one laid out for (dst_rows, dst_clouds) >= them, and marks every further cloud of dst "no order" (what
  * icpmi_history_search reports as ICPMI_RSB_ST_CAPACITY).  src == NULL with nothing in use: a fresh buffer.  No

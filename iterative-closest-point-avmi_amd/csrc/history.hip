@@ -6,8 +6,14 @@
 // past scan never changes (pose-graph optimisation moves its pose, slam.py:606-607).  Here those steps run once, when the
 // scan is added, and a query is the search kernel and the ICP kernels on the state they left.
 //
-// No kernel of its own: the filter (voxel.hip), the prepare kernels (prep.hip) and both halves of the rotation search
-// (rotsearch.hip) are the batch path's, run on a range of clouds; growing is device-to-device copies.
+// Adding and matching have no kernel of their own: the filter (voxel.hip), the prepare kernels (prep.hip) and both halves
+// of the rotation search (rotsearch.hip) are the batch path's, run on a range of clouds; growing is device-to-device copies.
+//
+// One kernel lives here: history_world_rows_kernel, transform_points_2d (slam.py:46-50) of resident raw rows.  After an
+// accepted closure the reference moves every pose (slam.py:606-607), transforms every past scan again on the host and
+// replays it into the map (_rebuild_map, slam.py:271-277) and into the submap buffer (slam.py:612-615).  The rows are
+// already here; what changed is six doubles per scan, so the rebuild takes scan ids and poses and the world rows never
+// visit the host.
 //
 // Two things a history must get right, both because its clouds are a prefix of a larger allocation:
 //  - a prepared buffer's arrays are carved from a row count (PreparedView).  That count is the history's row CAPACITY,
@@ -20,6 +26,56 @@
 namespace icpmi {
 
 constexpr int HISTORY_MAX_ROWS = 4096;      // the on-chip path of every kernel involved (prep.hip: PREP_MAX_POINTS)
+
+// ── world rows ──────────────────────────────────────────────────────────────────────────────────────────────────────
+// points @ T[:2, :2].T + T[:2, 2] as NumPy rounds it.  The product is BLAS: a scan of two or more rows goes to gemm, whose
+// element is fma(y, R[c][1], x * R[c][0]) (ft_transform_kernel of features.hip has the same form); a scan of exactly one
+// row goes to gemv, which accumulates the other way round, fma(x, R[c][0], y * R[c][1]).  Both are written out; the file is
+// compiled with -ffp-contract=off, so nothing else fuses.
+//
+// One thread per row, double2 in and double2 out (both streams coalesced), a workgroup per (scan of the list, chunk of
+// WR_THREADS of its rows).  The host knows no row count here (the offsets are the device's), so every scan gets the chunks
+// of the largest scan a history holds and a workgroup past its scan's rows leaves at once.  Scan id, offsets and the pose
+// depend on the workgroup alone: scalar loads, once.
+constexpr int WR_THREADS = 256;
+constexpr int WR_CHUNKS = HISTORY_MAX_ROWS / WR_THREADS;
+static_assert(WR_CHUNKS * WR_THREADS == HISTORY_MAX_ROWS, "the chunks of a scan cover the largest scan exactly");
+
+__global__ __launch_bounds__(WR_THREADS) void history_world_rows_kernel(const double2* __restrict__ pts, const int32_t* __restrict__ off,
+                                                                        int scan_capacity, const int32_t* __restrict__ ids,
+                                                                        const double* __restrict__ poses,
+                                                                        const int32_t* __restrict__ out_off, double2* __restrict__ out) {
+    const int k = blockIdx.x / WR_CHUNKS;
+    const int first = (blockIdx.x % WR_CHUNKS) * WR_THREADS;
+    const int id = ids[k];
+    if (id < 0 || id >= scan_capacity) return;                  // (the callers refuse such an id; never read past the offsets)
+    const int begin = off[id];
+    const int n = off[id + 1] - begin;
+    const int out_begin = out_off[k];
+    const int room = out_off[k + 1] - out_begin;
+    const int rows = n < room ? n : room;                       // equal for a well-formed call
+    if (begin < 0 || out_begin < 0 || first >= rows) return;
+    const double* r = poses + (size_t)k * 6;
+    const double r00 = r[0], r01 = r[1], r10 = r[2], r11 = r[3], tx = r[4], ty = r[5];
+    const int i = first + (int)threadIdx.x;
+    if (i >= rows) return;
+    const double2 p = pts[(size_t)begin + i];
+    double2 w;
+    if (n == 1) w = make_double2(__builtin_fma(p.x, r00, p.y * r01) + tx, __builtin_fma(p.x, r10, p.y * r11) + ty);     // gemv
+    else w = make_double2(__builtin_fma(p.y, r01, p.x * r00) + tx, __builtin_fma(p.y, r11, p.x * r10) + ty);            // gemm
+    out[(size_t)out_begin + i] = w;
+}
+
+struct WorldRowsPlan {
+    int rc;                   // ICPMI_OK, or why nothing is launched
+    unsigned grid, block;     // grid == 0: nothing to do
+};
+static WorldRowsPlan plan_world_rows(int n_ids) {
+    WorldRowsPlan p{ICPMI_OK, 0, WR_THREADS};
+    if (n_ids < 0 || n_ids > INT32_MAX / WR_CHUNKS) { p.rc = ICPMI_ERR_ARG; return p; }
+    p.grid = (unsigned)n_ids * WR_CHUNKS;
+    return p;
+}
 
 static bool history_complete(const icpmi_history* h) {
     return h && h->pts && h->off_dev && h->ids && h->icp_vox && h->icp_cnt && h->icp_prepared && h->rs_vox && h->rs_cnt &&
@@ -68,6 +124,19 @@ extern "C" int icpmi_history_search(const icpmi_history* h, const int32_t* pair_
     const RsbState s{h->rs_vox, h->off_dev, h->rs_cnt, h->rs_means, h->rs_prepared, h->row_capacity};
     return rsb_search(s, max_n, max_rows_hint, pair_src, pair_tgt, n_pairs, coarse_cs, n_coarse, fine_cs, fine_cnt, max_fine,
                       out_records, out_init, (hipStream_t)stream);
+}
+
+extern "C" int icpmi_history_world_rows(const icpmi_history* h, const int32_t* ids, int32_t n_ids, const double* poses,
+                                        const int32_t* out_off, double* out_rows, void* stream) {
+    using namespace icpmi;
+    if (!h || !h->pts || !h->off_dev || h->scan_capacity <= 0) return ICPMI_ERR_ARG;
+    const WorldRowsPlan plan = plan_world_rows(n_ids);
+    if (plan.rc != ICPMI_OK || plan.grid == 0) return plan.rc;
+    if (!ids || !poses || !out_off || !out_rows) return ICPMI_ERR_ARG;
+    history_world_rows_kernel<<<plan.grid, plan.block, 0, (hipStream_t)stream>>>(
+        reinterpret_cast<const double2*>(h->pts), h->off_dev, h->scan_capacity, ids, poses, out_off, reinterpret_cast<double2*>(out_rows));
+    ICPMI_LAUNCH_CHECK();
+    return ICPMI_OK;
 }
 
 extern "C" int icpmi_prepared_relayout(const void* src, int32_t src_rows, int32_t src_clouds, int32_t rows_used, int32_t clouds_used,

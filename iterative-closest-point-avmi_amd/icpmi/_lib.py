@@ -105,6 +105,7 @@ _SIGS = {
     "icpmi_history_add": (C.c_int, [C.POINTER(History), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "icpmi_history_search": (C.c_int, [C.POINTER(History), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                        C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "icpmi_history_world_rows": (C.c_int, [C.POINTER(History), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "icpmi_prepared_relayout": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32,
                                           C.c_int32, C.c_void_p]),
     "icpmi_feature_curvature_batch": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -12,6 +12,11 @@ appended (slam.py:554), and a query is the rotation-search kernel and the ICP ke
     m = hist.match(sid, [k for k, _ in cands], error_accept=0.05, stop_after_first_accepted=True)
     m.run(); first = m.first_accepted()                        # slam.py:575-597
 
+After an accepted closure every pose has moved and the reference transforms every past scan again on the host to rebuild
+the map and the submap buffer (slam.py:271-277, 612-615).  The raw rows are here, so ``world_rows(poses, ids)`` is one
+launch of ``icpmi_history_world_rows`` — NumPy's ``points @ T[:2, :2].T + T[:2, 2]`` bit for bit — and
+``OccupancyGrid2D.rebuild_from_history`` / ``RollingSubmap.reset_from_history`` take the history and the poses.
+
 ``match`` returns a ``RunIcpPairBatch`` whose clouds are the resident ones: ``run()`` / ``unpack()`` / ``first_accepted()``
 are that class's own code, and its records are the batch path's bit for bit (same kernels on the same filtered rows).
 
@@ -56,6 +61,25 @@ def find_loop_candidates(current_pose, poses, current_idx, distance_threshold, m
     idx = np.flatnonzero(keep)
     idx = idx[np.argsort(dist[idx], kind="stable")][:max_candidates]
     return [(int(k), float(dist[k])) for k in idx]
+
+
+def scan_reach(points):
+    """The largest row norm of an (n, 2) array, 0.0 for no rows; NaN or inf as soon as one coordinate is (``hypot``: no
+    overflow or underflow on the way, so a finite reach is the norm to within an ulp)."""
+    a = np.asarray(points, dtype=np.float64).reshape(-1, 2)
+    if len(a) == 0:
+        return 0.0
+    return float(np.hypot(a[:, 0], a[:, 1]).max())               # (max propagates a NaN)
+
+
+def pose_rows(poses, n):
+    """n pose matrices (3 x 3 each: ``PoseGraph2D.get_poses_as_matrices()``) -> (n, 6) float64 rows {R row-major, t}."""
+    P = np.asarray(poses, dtype=np.float64)
+    if n == 0 and P.size == 0:
+        return np.zeros((0, 6))
+    if P.shape != (n, 3, 3):
+        raise ValueError(f"poses must be {n} matrices of 3 x 3 (one per scan id): got shape {P.shape}")
+    return np.ascontiguousarray(np.concatenate([P[:, :2, :2].reshape(n, 4), P[:, :2, 2]], axis=1))
 
 
 class _ResidentIcp(IcpBatch):
@@ -187,6 +211,7 @@ class ScanHistory:
         self.voxel_size, self.rotation_voxel_size = float(voxel_size), float(rotation_voxel_size)
         self.normal_k = None if normal_k is None else int(normal_k)
         self.n_scans = self.rows_used = 0
+        self.reach = np.zeros(0)           # host: the largest row norm of every scan (non-finite if a coordinate is)
         self.allow_polar = True            # until a scan above 2048 rows arrives (the ICP kernels for such targets walk projections)
         self.layout_generation = self.stage_generation = 0
         self.scan_capacity = self.row_capacity = 0
@@ -305,6 +330,7 @@ class ScanHistory:
             self.state.allow_polar = 0
         self.rows_used = self._place(arrs, first, prepare=True)
         self.n_scans = first + len(arrs)
+        self.reach = np.concatenate([self.reach, [scan_reach(a) for a in arrs]])
         if redo:
             # a target above 2048 rows makes the ICP launch walk projections for every target of its batch: the earlier
             # scans, in bearing order until now, are put in order again (once in a history's life; their raw rows are here)
@@ -341,6 +367,45 @@ class ScanHistory:
         return HistoryMatch(self, int(source), cands, staged, error_threshold, max_iterations, method, max_corr_dist,
                             angle_step_coarse, angle_step_fine, max_rows_hint, error_accept, stop_after_first_accepted,
                             index_base, index_stride)
+
+    # ── world rows: transform_points_2d (slam.py:46-50) of resident scans ─────
+    def world_row_args(self, poses, ids=None):
+        """The host side of ``world_rows``, checked: (ids int32 [n], poses (n, 6), out offsets int32 [n + 1]).  ``ids=None``:
+        every scan in order.  Only [0, len(self)) is addressable — a staged source is not a scan of the history."""
+        if ids is None:
+            ids = np.arange(self.n_scans, dtype=np.int32)
+        else:
+            ids = np.asarray(ids)
+            if ids.ndim != 1 or (len(ids) and not np.issubdtype(ids.dtype, np.integer)):
+                raise ValueError("ids must be a 1-D sequence of scan ids")
+            if len(ids) and (ids.min() < 0 or ids.max() >= self.n_scans):
+                raise ValueError(f"scan ids must lie in [0, {self.n_scans}): got {int(ids.min())}..{int(ids.max())}")
+            ids = np.ascontiguousarray(ids, dtype=np.int32)
+        pose6 = pose_rows(poses, len(ids))
+        ends = np.cumsum(self.sizes()[ids], dtype=np.int64)
+        if len(ends) and ends[-1] >= 2 ** 31:
+            raise ValueError("too many rows for 32-bit row offsets: transform the list in parts")
+        off = np.zeros(len(ids) + 1, dtype=np.int32)
+        off[1:] = ends
+        return ids, pose6, off
+
+    def world_rows_into(self, out, ids_dev, poses_dev, off_dev, n):
+        """One ``icpmi_history_world_rows`` launch on the current stream: scan ids_dev[k] under poses_dev[k] into rows
+        [off_dev[k], off_dev[k + 1]) of ``out`` — device tensors as ``world_row_args`` lays them out; ``out`` holds at
+        least off_dev[n] rows."""
+        check(_lib.lib().icpmi_history_world_rows(C.byref(self.state), _ptr(ids_dev), n, _ptr(poses_dev), _ptr(off_dev), _ptr(out),
+                                                  _stream()), "history_world_rows")
+
+    def world_rows(self, poses, ids=None):
+        """``points @ T[:2, :2].T + T[:2, 2]`` (slam.py:46-50), NumPy's result bit for bit, of scan ids[k] under poses[k] (3 x 3
+        matrices, one per id; ids may repeat, in any order) -> (rows: a new (sum n, 2) float64 device tensor, offsets: host
+        int32 [len(ids) + 1]).  Three small uploads and one launch; the history is not written."""
+        ids, pose6, off = self.world_row_args(poses, ids)
+        rows = torch.empty((int(off[-1]), 2), dtype=torch.float64, device=self.device)
+        if len(ids):
+            dev = [torch.from_numpy(a).to(self.device) for a in (ids, pose6, off)]
+            self.world_rows_into(rows, dev[0], dev[1], dev[2], len(ids))
+        return rows, off
 
     def icp(self, source_id, target_id, R_init=None, t_init=None, error_threshold=1e-7, max_iterations=100,
             method="point_to_line", max_corr_dist=None):

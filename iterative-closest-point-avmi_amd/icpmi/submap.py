@@ -60,6 +60,20 @@ class RollingSubmap:
         self._scans = [self._to_dev(s) for s in list(scans)[-self.window:]]
         self._built = None
 
+    def reset_from_history(self, history, poses, ids=None):
+        """``reset`` from scans resident in an ``icpmi.ScanHistory``: the buffer becomes the world rows of the last
+        ``window`` of ``ids`` (``None``: every scan in order) at their ``poses`` (3 x 3 matrices, one per id) — what
+        ``reset([pts @ T[:2, :2].T + T[:2, 2] ...])`` holds, bit for bit, from one launch and no upload of points.  The rows
+        are a tensor of this buffer's own (``world_rows`` allocates it), not a view of anything reused.  -> self"""
+        if history.device != self._dev:
+            raise ValueError(f"the history lives on {history.device}, the submap on {self._dev}")
+        ids, _, _ = history.world_row_args(poses, ids)                  # the whole list is checked, then its tail is used
+        tail = slice(max(len(ids) - self.window, 0), len(ids))
+        rows, off = history.world_rows(np.asarray(poses, dtype=np.float64)[tail], ids[tail])
+        self._scans = [rows[int(off[k]):int(off[k + 1])] for k in range(len(off) - 1)]
+        self._built = None
+        return self
+
     @property
     def points_in(self):
         return int(sum(s.shape[0] for s in self._scans))

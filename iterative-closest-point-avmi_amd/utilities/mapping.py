@@ -44,6 +44,7 @@ class OccupancyGrid2D:
         self._full_clip = not (self.log_odds_min <= 0.0 <= self.log_odds_max)
         self._stages = None                # pinned staging rows of update_scan (NumPy in)
         self._call = None                  # converted constant arguments of the update call (see _apply)
+        self._replay_scratch = None        # world rows of one piece of replay_history
         self.cell_updates = 0              # not tracked on the device; see update_scans()
 
     # ── the grid as the reference exposes it ─────────────────────────────────
@@ -183,6 +184,56 @@ class OccupancyGrid2D:
 
     _REPLAY_PIECE = 64
 
+    def replay_history(self, history, poses, ids=None, rows=None):
+        """``update_scans`` of scans resident in an ``icpmi.ScanHistory``, by id: scan ids[k] (``None``: every scan in
+        order) at poses[k] (3 x 3 matrices).  Origins are the poses' translations, hits the scans' world rows — transformed
+        on the device (``icpmi_history_world_rows``: NumPy's ``pts @ T[:2, :2].T + T[:2, 2]`` bit for bit), so the cells are
+        those of the host replay and nothing but ids, poses and offsets is uploaded.  ``rows`` as in ``update_scans``.
+
+        Pieces of ``_REPLAY_PIECE`` scans as there, each one transform launch into a scratch of the largest piece's size
+        (reused: everything runs on one stream) and one ``_apply``; a piece's cell box comes from the host
+        (``reach_cell_box``), with no read-back."""
+        self._replay(self._replay_args(history, poses, ids), rows)
+
+    def _replay_args(self, history, poses, ids):
+        if history.device != self._dev:
+            raise ValueError(f"the history lives on {history.device}, the grid on {self._dev}")
+        return (history,) + history.world_row_args(poses, ids)
+
+    def _replay(self, args, rows):
+        history, ids, pose6, off = args
+        S = len(ids)
+        if S == 0:
+            return
+        org = torch.from_numpy(np.ascontiguousarray(pose6[:, 4:6])).to(self._dev)
+        if off[-1] == 0:                                           # no beam at all: what update_scans does with that
+            self._apply(org, None, off, rows, None)
+            return
+        P = self._REPLAY_PIECE
+        starts = range(0, S, P)
+        piece_off = [off[c0:min(S, c0 + P) + 1] - off[c0] for c0 in starts]       # each piece's offsets into the scratch
+        need = max(int(o[-1]) for o in piece_off)
+        if self._replay_scratch is None or self._replay_scratch.shape[0] < need:
+            self._replay_scratch = torch.empty((need, 2), dtype=torch.float64, device=self._dev)
+        scratch = self._replay_scratch
+        ids_d, pose_d = torch.from_numpy(ids).to(self._dev), torch.from_numpy(pose6).to(self._dev)
+        off_d = torch.from_numpy(np.concatenate(piece_off)).to(self._dev)
+        reach = history.reach[ids]
+        at = 0
+        for c0, o in zip(starts, piece_off):
+            k = len(o) - 1
+            if o[-1] > 0:
+                history.world_rows_into(scratch, ids_d[c0:c0 + k], pose_d[c0:c0 + k], off_d[at:at + k + 1], k)
+                self._apply(org[c0:c0 + k], scratch[:int(o[-1])], o, rows,
+                            reach_cell_box(self, pose6[c0:c0 + k], reach[c0:c0 + k]))
+            at += k + 1
+
+    def rebuild_from_history(self, history, poses):
+        """``_rebuild_map`` (slam.py:271-277) from a resident history: ``reset()`` and the replay of every scan at its pose."""
+        args = self._replay_args(history, poses, None)             # refused before anything is zeroed
+        self.reset()
+        self._replay(args, None)
+
     @staticmethod
     def _box_tiles(box):
         """Tiles of 64 x 64 cells a cell box spans."""
@@ -287,6 +338,32 @@ def _minmax_rows(rows):
     with an inner loop of length two (90 us for a 2 048-beam scan), and the contiguous axis of the copy in 5."""
     t = np.ascontiguousarray(rows.T)
     return t.min(axis=1), t.max(axis=1)
+
+
+def reach_cell_box(grid, poses, reach):
+    """Inclusive cell bounds (host int32[4], through ``grid._box_of``) that hold every ray of scans whose world rows exist on
+    the device only: scan s has the pose poses[s] = {R row-major, t} (six doubles) and no raw row longer than reach[s]
+    (``ScanHistory.reach``).  A superset of the exact box of origins and world rows; ``None`` (no promise: the caller reads
+    the bounds back from the device) when a reach or a pose is not finite.  ``grid``: anything with min_x, min_y and
+    resolution.  Host arithmetic only.
+
+    A world coordinate is w = fl(fl(fma(y, b, fl(x a))) + t) with (a, b) a row of R, exactly x a + y b + t but for three
+    roundings.  |x a + y b| <= |(a, b)| |(x, y)| <= F r, with F the Frobenius norm of R and r the reach.  With u = 2^-53,
+    the product and the fma put at most (1 + u)^2 on that, and the last addition at most u |w| <= u (|t| + F r (1 + u)^2)
+    more, so |w - t| <= F r (1 + 4u) + 2u |t|.  F and r are themselves computed here: two nested hypots, the reach's hypot
+    and their product are each within an ulp or two, under 8u relative together, and t -+ d below rounds once more,
+    u (|t| + d).  Where an intermediate is subnormal a rounding is absolute, at most 2^-1074 each.  The margin taken,
+    d = F r (1 + 2^-40) + 2^-40 |t| + 1e-300, covers all of that some thousand times over and is a relative 1e-12 of the
+    distances involved: it moves a cell bound only for a coordinate that close to a cell edge."""
+    P = np.asarray(poses, dtype=np.float64).reshape(-1, 6)
+    r = np.asarray(reach, dtype=np.float64).reshape(-1)
+    if len(P) == 0 or len(P) != len(r) or not (np.isfinite(P).all() and np.isfinite(r).all()):
+        return None
+    F = np.hypot(np.hypot(P[:, 0], P[:, 1]), np.hypot(P[:, 2], P[:, 3]))
+    eps = 2.0 ** -40
+    t = P[:, 4:6]
+    d = ((F * r) * (1.0 + eps))[:, None] + eps * np.abs(t) + 1e-300
+    return OccupancyGrid2D._box_of(grid, (t - d).min(axis=0), (t + d).max(axis=0))
 
 
 def bresenham_cells(segments):
