@@ -91,6 +91,83 @@ class CloudSet:
         return [host[self.off_host[c]:self.off_host[c] + cnt[c]].copy() for c in range(self.n_clouds)]
 
 
+class PairList:
+    """The pairs of a batch: the cloud index of the source and of the target of every pair, int32, on the host
+    (``src_host`` / ``tgt_host``) and — after ``to(device)`` — on the device (``src`` / ``tgt``).  The parts of one job
+    (ICP, rotation search, feature alignment) share one."""
+
+    def __init__(self, pair_src, pair_tgt):
+        self.src_host = np.ascontiguousarray(pair_src, dtype=np.int32)
+        self.tgt_host = np.ascontiguousarray(pair_tgt, dtype=np.int32)
+        self.B = len(self.src_host)
+        if len(self.tgt_host) != self.B:
+            raise ValueError("pair_src and pair_tgt differ in length")
+        self.src = self.tgt = None
+
+    @classmethod
+    def of(cls, pair_src, pair_tgt=None):
+        """``pair_src`` itself when it is a PairList already (``pair_tgt`` is not looked at), else a new one."""
+        return pair_src if isinstance(pair_src, cls) else cls(pair_src, pair_tgt)
+
+    def to(self, dev):
+        """Upload the two lists (once) -> self."""
+        if self.src is None:
+            self.src = torch.from_numpy(self.src_host).to(dev)
+            self.tgt = torch.from_numpy(self.tgt_host).to(dev)
+        elif self.src.device != dev:
+            raise ValueError(f"this pair list lives on {self.src.device}, not on {dev}")
+        return self
+
+
+class _Paired:
+    """The names under which every batch object shows its ``pairs`` (a PairList)."""
+    pair_src_host = property(lambda self: self.pairs.src_host)
+    pair_tgt_host = property(lambda self: self.pairs.tgt_host)
+    pair_src = property(lambda self: self.pairs.src)
+    pair_tgt = property(lambda self: self.pairs.tgt)
+    B = property(lambda self: self.pairs.B)
+
+
+def pair_lists(sources, targets):
+    """(clouds, pair_src, pair_tgt) for sources[i] -> targets[i]; ``sources`` may be one array shared by every pair (the
+    loop-closure shape, slam.py:576-579), which is then stored once."""
+    targets = list(targets)
+    B = len(targets)
+    if isinstance(sources, np.ndarray) and sources.ndim == 2:
+        return [sources] + targets, np.zeros(B, dtype=np.int32), np.arange(1, B + 1, dtype=np.int32)
+    sources = list(sources)
+    if len(sources) != B:
+        raise ValueError("sources and targets differ in length")
+    return sources + targets, np.arange(B, dtype=np.int32), np.arange(B, 2 * B, dtype=np.int32)
+
+
+ICP_METHODS = ("point_to_point", "point_to_line")
+
+
+def icp_params(error_threshold, max_corr_dist, max_iterations, method, have_init, dim, strict=False):
+    """The ICP problem record of include/icpmi.h with the reference's rules: point_to_line is 2-D only (icp.py:162) and
+    ``max_corr_dist=None`` keeps every correspondence (-1).  A method string that is neither of ``ICP_METHODS`` is
+    point_to_point, as the reference's else-branch (icp.py:196) — or, with ``strict``, a ValueError."""
+    if method not in ICP_METHODS:
+        if strict:
+            raise ValueError(f"method must be 'point_to_point' or 'point_to_line', got {method!r}")
+        method = "point_to_point"
+    use_p2l = method == "point_to_line" and dim == 2
+    return IcpParams(float(error_threshold), -1.0 if max_corr_dist is None else float(max_corr_dist), int(max_iterations),
+                     _lib.POINT_TO_LINE if use_p2l else _lib.POINT_TO_POINT, 1 if have_init else 0, int(dim))
+
+
+def init_rows(R_init, t_init, B, dim):
+    """The start of every pair as [B, d*d + d] float64 rows {R row major, t}: one (d, d) / (d,) start for all pairs or one
+    per pair.  None unless both are given: R_init is used only together with t_init (icp.py:153)."""
+    if R_init is None or t_init is None:
+        return None
+    d = dim
+    R = np.broadcast_to(np.asarray(R_init, dtype=np.float64), (B, d, d)).reshape(B, d * d)
+    t = np.broadcast_to(np.asarray(t_init, dtype=np.float64), (B, d))
+    return np.ascontiguousarray(np.concatenate([R, t], axis=1))
+
+
 def voxel_downsample_set(cs, voxel_size, out=None, workspace=None):
     """voxel_downsample (reference icp.py:117-129) of every cloud of the set."""
     L = _lib.lib()
@@ -146,13 +223,12 @@ def normals_set(cs, k, cloud_ids=None, out=None, workspace=None):
 def nn_set(cs, pair_src, pair_tgt):
     """1-NN of every row of cloud pair_src[b] in cloud pair_tgt[b] -> (dist, idx) device tensors [B, stride]."""
     L = _lib.lib()
-    ps = torch.as_tensor(np.ascontiguousarray(pair_src, dtype=np.int32), device=cs.pts.device)
-    pt = torch.as_tensor(np.ascontiguousarray(pair_tgt, dtype=np.int32), device=cs.pts.device)
-    B = len(pair_src)
-    stride = max(int(np.diff(cs.off_host)[np.asarray(pair_src)].max()) if B else 0, 1)
+    p = PairList(pair_src, pair_tgt).to(cs.pts.device)
+    B = p.B
+    stride = max(int(np.diff(cs.off_host)[p.src_host].max()) if B else 0, 1)
     idx = torch.empty((max(B, 1), stride), dtype=torch.int32, device=cs.pts.device)
     dist = torch.empty((max(B, 1), stride), dtype=torch.float64, device=cs.pts.device)
-    check(L.icpmi_nn_batch(_ptr(cs.pts), _ptr(cs.off), _ptr(cs.cnt), _ptr(ps), _ptr(pt), B, stride, cs.dim,
+    check(L.icpmi_nn_batch(_ptr(cs.pts), _ptr(cs.off), _ptr(cs.cnt), _ptr(p.src), _ptr(p.tgt), B, stride, cs.dim,
                            _ptr(idx), _ptr(dist), stride, _stream()), "nn")
     return dist, idx
 
@@ -164,105 +240,100 @@ def nn_set_sweep(cs, pair_src, pair_tgt, return_second=False):
     if cs.dim != 2:
         raise ValueError("the sweep search is 2-D only")
     dev = cs.pts.device
-    pair_src = np.ascontiguousarray(pair_src, dtype=np.int32)
-    pair_tgt = np.ascontiguousarray(pair_tgt, dtype=np.int32)
-    B = len(pair_src)
+    p = PairList(pair_src, pair_tgt)
+    B = p.B
     sizes = np.diff(cs.off_host)
-    tgt_ids = np.unique(pair_tgt)
+    tgt_ids = np.unique(p.tgt_host)
     max_tgt = int(sizes[tgt_ids].max()) if B else 0
     if max_tgt > PREP_MAX_POINTS:
         raise ValueError(f"target clouds above {PREP_MAX_POINTS} rows need the exhaustive search (nn_set)")
-    stride = max(int(sizes[pair_src].max()) if B else 0, 1)
+    stride = max(int(sizes[p.src_host].max()) if B else 0, 1)
     prepared = torch.empty(L.icpmi_prepared_bytes(cs.total_rows, cs.n_clouds, max_tgt), dtype=torch.uint8, device=dev)
     ids = torch.from_numpy(tgt_ids.astype(np.int32)).to(dev)
     check(L.icpmi_prepare_targets(_ptr(cs.pts), _ptr(cs.off), None, _ptr(cs.cnt), _ptr(ids), None, len(tgt_ids),
                                   cs.n_clouds, cs.total_rows, max_tgt, -1, None, _ptr(prepared), prepared.numel(),
                                   _stream()), "prepare_targets")
-    ps, pt = torch.from_numpy(pair_src).to(dev), torch.from_numpy(pair_tgt).to(dev)
+    p.to(dev)
     idx = torch.empty((max(B, 1), stride), dtype=torch.int32, device=dev)
     dist = torch.empty((max(B, 1), stride), dtype=torch.float64, device=dev)
     second = torch.empty((max(B, 1), stride), dtype=torch.float64, device=dev) if return_second else None
-    check(L.icpmi_nn_prepared_batch(_ptr(cs.pts), _ptr(cs.off), _ptr(cs.cnt), _ptr(prepared), _ptr(ps), _ptr(pt), B,
+    check(L.icpmi_nn_prepared_batch(_ptr(cs.pts), _ptr(cs.off), _ptr(cs.cnt), _ptr(prepared), _ptr(p.src), _ptr(p.tgt), B,
                                     stride, max_tgt, cs.total_rows, _ptr(idx), _ptr(dist), _ptr(second), stride,
                                     _stream()), "nn (sweep)")
     return (dist, idx, second) if return_second else (dist, idx)
 
 
-class IcpBatch:
+class IcpBatch(_Paired):
     """A batch of scan pairs resident in HBM, ready to be registered repeatedly.
 
     clouds: list of arrays; pair_src/pair_tgt: cloud indices per pair (a source
-    shared by many pairs is stored once).  ``run()`` performs exactly what the
+    shared by many pairs is stored once), or a ``PairList`` as pair_src.  ``run()`` performs exactly what the
     reference's ``ICP()`` does per pair — voxel filter of source and target,
     target normals for point_to_line, the ICP loop — and leaves a
     (B, 16) float64 result tensor on the device.
     """
+    strict_method = False       # a method string the reference does not know: point_to_point (icp_params)
 
     def __init__(self, clouds, pair_src, pair_tgt, error_threshold, max_iterations, voxel_size,
                  R_init=None, t_init=None, method="point_to_point", normal_k=10, max_corr_dist=None,
                  force_exhaustive=False):
         require_gpu()
-        L = _lib.lib()
-        self.raw = clouds if isinstance(clouds, CloudSet) else CloudSet.from_numpy(clouds)
-        dev = self.raw.pts.device
-        self.dim = self.raw.dim
-        self.pair_src_host = np.ascontiguousarray(pair_src, dtype=np.int32)
-        self.pair_tgt_host = np.ascontiguousarray(pair_tgt, dtype=np.int32)
-        self.B = len(self.pair_src_host)
-        if len(self.pair_tgt_host) != self.B:
-            raise ValueError("pair_src and pair_tgt differ in length")
-        self.pair_src = torch.from_numpy(self.pair_src_host).to(dev)
-        self.pair_tgt = torch.from_numpy(self.pair_tgt_host).to(dev)
-        self.voxel_size = float(voxel_size)
-        self.normal_k = int(normal_k)
-        use_p2l = method == "point_to_line" and self.dim == 2          # icp.py:162
-        if method not in ("point_to_point", "point_to_line"):
-            use_p2l = False                                             # any other string: icp.py:196 else-branch
-        have_init = R_init is not None and t_init is not None          # icp.py:153
-        self.params = IcpParams(float(error_threshold), -1.0 if max_corr_dist is None else float(max_corr_dist),
-                                int(max_iterations), _lib.POINT_TO_LINE if use_p2l else _lib.POINT_TO_POINT,
-                                1 if have_init else 0, self.dim)
-        self.use_p2l = use_p2l
-        self.init = None
-        if have_init:
-            d = self.dim
-            R = np.broadcast_to(np.asarray(R_init, dtype=np.float64), (self.B, d, d)).reshape(self.B, d * d)
-            t = np.broadcast_to(np.asarray(t_init, dtype=np.float64), (self.B, d))
-            self.init = torch.from_numpy(np.ascontiguousarray(np.concatenate([R, t], axis=1))).to(dev)
-        sizes = np.diff(self.raw.off_host)
-        self.max_src_n = int(sizes[self.pair_src_host].max()) if self.B else 0
-        self.tgt_ids = np.unique(self.pair_tgt_host)
-        # persistent device buffers: nothing is allocated inside run()
-        self.vox = CloudSet(torch.empty_like(self.raw.pts), self.raw.off_host,
-                            cnt=torch.zeros(max(self.raw.n_clouds, 1), dtype=torch.int32, device=dev), off=self.raw.off)
-        self.vox_ws = torch.empty(L.icpmi_voxel_workspace_bytes(self.raw.max_n), dtype=torch.uint8, device=dev)
-        self.normals = None
-        self.tgt_ids_dev = torch.from_numpy(self.tgt_ids.astype(np.int32)).to(dev)
-        self.max_tgt_n = int(sizes[self.tgt_ids].max()) if len(self.tgt_ids) else 0
-        # fast path: 2-D, every cloud small enough for the on-chip kernels
-        # (targets above PREP_MAX_POINTS rows — a rolling submap — are sorted through global memory and searched via L2)
-        self.fast = self.dim == 2 and self.max_src_n <= PREP_MAX_POINTS and not force_exhaustive
-        self.prepared = None
-        self.icp_ws = None
-        if self.fast:
-            self.prepared = torch.empty(L.icpmi_prepared_bytes(self.raw.total_rows, self.raw.n_clouds, self.max_tgt_n),
-                                        dtype=torch.uint8, device=dev)
-            self.tgt_ids_host = np.ascontiguousarray(self.tgt_ids, dtype=np.int32)
-            # parked pairs (csrc/icp2.hip): a large batch runs in two stages — the pairs still running after 12
-            # iterations are continued together by a second launch — and pairs that start metres from their target
-            # are continued by the kernel for far queries
-            self.icp_ws = torch.empty(L.icpmi_icp_workspace_bytes(self.B, self.max_src_n, self.dim),
-                                      dtype=torch.uint8, device=dev)
-        else:
-            if use_p2l:
-                self.normals = torch.zeros((max(self.raw.total_rows, 1), 2), dtype=torch.float64, device=dev)
-                self.nrm_ws = torch.empty(L.icpmi_normals_workspace_bytes(self.raw.total_rows, self.max_tgt_n),
-                                          dtype=torch.uint8, device=dev)
-            self.icp_ws = torch.empty(L.icpmi_icp_workspace_bytes(self.B, self.max_src_n, self.dim),
-                                      dtype=torch.uint8, device=dev)
+        raw = clouds if isinstance(clouds, CloudSet) else CloudSet.from_numpy(clouds)
+        self._init_common(raw, pair_src, pair_tgt, error_threshold, max_iterations, voxel_size, R_init, t_init, method,
+                          normal_k, max_corr_dist)
+        self._init_buffers(force_exhaustive)
+
+    def _init_common(self, raw, pair_src, pair_tgt, error_threshold, max_iterations, voxel_size, R_init, t_init, method,
+                     normal_k, max_corr_dist):
+        """What every variant needs: the pairs, the problem, the start of every pair, the ICP workspace, the results and
+        the gate state.  The clouds' own buffers are ``_init_buffers``' (a resident variant points at a history's)."""
+        self.raw, self.dim = raw, raw.dim
+        dev = raw.pts.device
+        self.pairs = PairList.of(pair_src, pair_tgt)
+        rows = init_rows(R_init, t_init, self.B, self.dim)
+        self.set_problem(error_threshold, max_iterations, voxel_size, method, normal_k, max_corr_dist, rows is not None)
+        self.pairs.to(dev)
+        self.init = None if rows is None else torch.from_numpy(rows).to(dev)
+        # parked pairs (csrc/icp2.hip): a large batch runs in two stages — the pairs still running after 12
+        # iterations are continued together by a second launch — and pairs that start metres from their target
+        # are continued by the kernel for far queries
+        self.icp_ws = torch.empty(_lib.lib().icpmi_icp_workspace_bytes(self.B, self.max_src_n, self.dim),
+                                  dtype=torch.uint8, device=dev)
         self.results = torch.zeros((max(self.B, 1), _lib.RES_DOUBLES), dtype=torch.float64, device=dev)
         self.gate = None
         self.first_accepted_dev = None
+
+    def set_problem(self, error_threshold, max_iterations, voxel_size, method, normal_k, max_corr_dist, have_init):
+        """Aim the batch at the clouds now in ``raw`` (their row counts) with these ICP arguments; buffers stay as they
+        are, so a cached batch (``PairContext``) may only be re-aimed at clouds within the capacity it was built for."""
+        self.voxel_size, self.normal_k = float(voxel_size), int(normal_k)
+        self.params = icp_params(error_threshold, max_corr_dist, max_iterations, method, have_init, self.dim,
+                                 strict=self.strict_method)
+        self.use_p2l = self.params.method == _lib.POINT_TO_LINE
+        sizes = np.diff(self.raw.off_host)
+        self.max_src_n = int(sizes[self.pair_src_host].max()) if self.B else 0
+        self.max_tgt_n = int(sizes[self.pair_tgt_host].max()) if self.B else 0
+
+    def _init_buffers(self, force_exhaustive):
+        """The buffers a batch owns for its clouds (persistent: nothing is allocated inside run())."""
+        L = _lib.lib()
+        dev = self.raw.pts.device
+        self.tgt_ids = np.unique(self.pair_tgt_host)          # (sorted, contiguous, int32 as the pair list)
+        self.vox = CloudSet(torch.empty_like(self.raw.pts), self.raw.off_host,
+                            cnt=torch.zeros(max(self.raw.n_clouds, 1), dtype=torch.int32, device=dev), off=self.raw.off)
+        self.vox_ws = torch.empty(L.icpmi_voxel_workspace_bytes(self.raw.max_n), dtype=torch.uint8, device=dev)
+        self.tgt_ids_dev = torch.from_numpy(self.tgt_ids).to(dev)
+        # fast path: 2-D, every cloud small enough for the on-chip kernels
+        # (targets above PREP_MAX_POINTS rows — a rolling submap — are sorted through global memory and searched via L2)
+        self.fast = self.dim == 2 and self.max_src_n <= PREP_MAX_POINTS and not force_exhaustive
+        self.prepared = self.normals = None
+        if self.fast:
+            self.prepared = torch.empty(L.icpmi_prepared_bytes(self.raw.total_rows, self.raw.n_clouds, self.max_tgt_n),
+                                        dtype=torch.uint8, device=dev)
+        elif self.use_p2l:
+            self.normals = torch.zeros((max(self.raw.total_rows, 1), 2), dtype=torch.float64, device=dev)
+            self.nrm_ws = torch.empty(L.icpmi_normals_workspace_bytes(self.raw.total_rows, self.max_tgt_n),
+                                      dtype=torch.uint8, device=dev)
 
     @property
     def layout_rows(self):
@@ -299,7 +370,7 @@ class IcpBatch:
             # allow_polar: the sort order (a projection, or the bearing about the frame origin) is the library's choice
             check(L.icpmi_prepare_targets_ex(_ptr(self.vox.pts), _ptr(self.vox.off),
                                              self.raw.off_host.ctypes.data_as(C.c_void_p), _ptr(self.vox.cnt),
-                                             _ptr(self.tgt_ids_dev), self.tgt_ids_host.ctypes.data_as(C.c_void_p),
+                                             _ptr(self.tgt_ids_dev), self.tgt_ids.ctypes.data_as(C.c_void_p),
                                              len(self.tgt_ids), self.raw.n_clouds, self.raw.total_rows, self.max_tgt_n,
                                              self.normal_k if self.use_p2l else -1, None, _ptr(self.prepared),
                                              self.prepared.numel(), 1, st), "prepare_targets")
@@ -345,6 +416,19 @@ def unpack_results(res, dim):
     info = dict(iters=res[:, _lib.RES_ITERS].astype(np.int64), status=res[:, _lib.RES_STATUS].astype(np.int64),
                 delta=res[:, _lib.RES_DELTA].copy())
     return R, t, err, info
+
+
+def pack_results(R, t, err, info):
+    """The inverse of ``unpack_results``: [B, RES_DOUBLES] records."""
+    res = np.zeros((len(err), _lib.RES_DOUBLES))
+    d = R.shape[1]
+    res[:, _lib.RES_R:_lib.RES_R + d * d] = R.reshape(len(err), d * d)
+    res[:, _lib.RES_T:_lib.RES_T + d] = t
+    res[:, _lib.RES_ERR] = err
+    res[:, _lib.RES_DELTA] = info["delta"]
+    res[:, _lib.RES_ITERS] = info["iters"]
+    res[:, _lib.RES_STATUS] = info["status"]
+    return res
 
 
 class PairContext:
@@ -399,17 +483,10 @@ class PairContext:
         b.raw.off_host[:] = (0, ns, ns + nt)
         self.off_stage.numpy()[:] = b.raw.off_host
         b.raw.off.copy_(self.off_stage, non_blocking=True)
-        b.max_src_n, b.max_tgt_n = ns, nt
-        b.voxel_size, b.normal_k = float(voxel_size), int(normal_k)
-        use_p2l = method == "point_to_line"
-        have_init = R_init is not None and t_init is not None                    # icp.py:153
-        b.use_p2l = use_p2l
-        b.params = IcpParams(float(error_threshold), -1.0 if max_corr_dist is None else float(max_corr_dist),
-                             int(max_iterations), _lib.POINT_TO_LINE if use_p2l else _lib.POINT_TO_POINT,
-                             1 if have_init else 0, 2)
-        if have_init:
-            self.init_stage.numpy()[0, :4] = np.asarray(R_init, dtype=np.float64).reshape(4)
-            self.init_stage.numpy()[0, 4:] = np.asarray(t_init, dtype=np.float64).reshape(2)
+        rows = init_rows(R_init, t_init, 1, 2)
+        b.set_problem(error_threshold, max_iterations, voxel_size, method, normal_k, max_corr_dist, rows is not None)
+        if rows is not None:
+            self.init_stage.numpy()[:] = rows
             b.init.copy_(self.init_stage, non_blocking=True)
         res = b.run()
         self.res_host.copy_(res[:1], non_blocking=True)
@@ -421,7 +498,7 @@ def icp_pair(source, target, error_threshold, max_iterations, voxel_size, R_init
              method="point_to_point", normal_k=10, max_corr_dist=None):
     """One registration with the semantics of the reference ``ICP`` -> (R, t, err, info) like ``icp_batch``."""
     d = source.shape[1]
-    if d == 2 and len(source) <= PREP_MAX_POINTS and len(target) <= PREP_MAX_POINTS and method in ("point_to_point", "point_to_line"):
+    if d == 2 and len(source) <= PREP_MAX_POINTS and len(target) <= PREP_MAX_POINTS and method in ICP_METHODS:
         res = PairContext.get().solve(source, target, error_threshold, max_iterations, voxel_size, R_init, t_init, method,
                                       normal_k, max_corr_dist)
         return unpack_results(res[None, :], 2)
@@ -436,19 +513,7 @@ def icp_batch(sources, targets, error_threshold, max_iterations, voxel_size, R_i
     ``sources`` may be one array shared by every pair (the loop-closure shape,
     slam.py:576-579).  Returns (R [B,d,d], t [B,d], err [B], info).
     """
-    targets = list(targets)
-    B = len(targets)
-    if isinstance(sources, np.ndarray) and sources.ndim == 2:
-        clouds = [sources] + targets
-        ps = np.zeros(B, dtype=np.int32)
-        pt = np.arange(1, B + 1, dtype=np.int32)
-    else:
-        sources = list(sources)
-        if len(sources) != B:
-            raise ValueError("sources and targets differ in length")
-        clouds = sources + targets
-        ps = np.arange(B, dtype=np.int32)
-        pt = np.arange(B, 2 * B, dtype=np.int32)
+    clouds, ps, pt = pair_lists(sources, targets)
     batch = IcpBatch(clouds, ps, pt, error_threshold, max_iterations, voxel_size, R_init, t_init,
                      method, normal_k, max_corr_dist, force_exhaustive)
     batch.run()

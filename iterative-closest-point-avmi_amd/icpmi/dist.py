@@ -13,6 +13,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
+from .batch import IcpBatch, pack_results as _pack_results, pair_lists, unpack_results
 
 
 def _all_gather_into(out, inp, group=None):
@@ -105,14 +106,9 @@ def icp_batch_sharded(sources, targets, error_threshold, max_iterations, voxel_s
     elif len(mine) == 0:
         local = torch.zeros((0, _lib.RES_DOUBLES), dtype=torch.float64, device=torch.device("cuda", torch.cuda.current_device()))
     else:
-        from .batch import IcpBatch
-        k = len(mine)
-        if shared:
-            clouds, ps, pt = [sources] + tgt, np.zeros(k, dtype=np.int32), np.arange(1, k + 1, dtype=np.int32)
-        else:
-            clouds, ps, pt = src + tgt, np.arange(k, dtype=np.int32), np.arange(k, 2 * k, dtype=np.int32)
+        clouds, ps, pt = pair_lists(sources if shared else src, tgt)
         b = IcpBatch(clouds, ps, pt, error_threshold, max_iterations, voxel_size, Ri, ti, method, normal_k, max_corr_dist)
-        local = b.run()[:k]
+        local = b.run()[:len(mine)]
     return gather_results(local, n, rank, world, group)
 
 
@@ -155,9 +151,8 @@ class RunIcpPairSharded:
         self.gathered = None
         if solver is None and len(self.mine):
             from .prealign import RunIcpPairBatch
-            k = len(self.mine)
             c, f = self.icp_cfg, self.feat_cfg
-            self.batch = RunIcpPairBatch([source] + self.targets, np.zeros(k, dtype=np.int32), np.arange(1, k + 1, dtype=np.int32),
+            self.batch = RunIcpPairBatch(*pair_lists(np.asarray(source), self.targets),
                                          error_threshold=c.get("error_threshold", 1e-7), max_iterations=c.get("max_iterations", 100),
                                          voxel_size=c.get("voxel_size", 0.06), method=c.get("method", "point_to_line"),
                                          normal_k=c.get("normal_k", 10), rotation_voxel_size=f.get("rotation_voxel_size", 0.3),
@@ -192,7 +187,6 @@ class RunIcpPairSharded:
     def results(self):
         """(R [n,2,2], t [n,2], err [n], info) of the last run on the host (synchronises); candidates whose rotation search
         fell outside the on-chip capacity are redone by their owners and gathered again."""
-        from .batch import unpack_results
         res = self.gathered
         over = torch.nonzero(res[:, self.SEARCH_STATUS] == 2.0).reshape(-1).cpu().numpy() if self.solver is None else np.empty(0, dtype=np.int64)
         if len(over):
@@ -218,18 +212,6 @@ class RunIcpPairSharded:
         if self.solver is None and bool((self.gathered[:, self.SEARCH_STATUS] == 2.0).any()):
             self.results()
         return first_accepted_gated(self.gathered, self.error_accept, self.SEARCH_STATUS)
-
-
-def _pack_results(R, t, err, info):
-    res = np.zeros((len(err), _lib.RES_DOUBLES))
-    d = R.shape[1]
-    res[:, _lib.RES_R:_lib.RES_R + d * d] = R.reshape(len(err), d * d)
-    res[:, _lib.RES_T:_lib.RES_T + d] = t
-    res[:, _lib.RES_ERR] = err
-    res[:, _lib.RES_DELTA] = info["delta"]
-    res[:, _lib.RES_ITERS] = info["iters"]
-    res[:, _lib.RES_STATUS] = info["status"]
-    return res
 
 
 def run_icp_pair_batch_sharded(source, targets, icp_cfg=None, feat_cfg=None, error_accept=None, group=None, solver=None,

@@ -28,9 +28,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import IcpParams, check
-from .batch import PREP_MAX_POINTS, CloudSet, IcpBatch, _ptr, _stream, require_gpu
-from .prealign import AngleTables, REC_DOUBLES, RSB_MAX_ANGLES, RotationSearchBatch, RunIcpPairBatch
+from ._lib import check
+from .batch import PREP_MAX_POINTS, CloudSet, IcpBatch, PairList, _ptr, _stream, require_gpu
+from .prealign import RotationSearchBatch, RunIcpPairBatch, _gate_given
 
 
 def find_loop_candidates(current_pose, poses, current_idx, distance_threshold, min_interval, max_candidates,
@@ -82,43 +82,30 @@ def pose_rows(poses, n):
     return np.ascontiguousarray(np.concatenate([P[:, :2, :2].reshape(n, 4), P[:, :2, 2]], axis=1))
 
 
+def _scan_ids(ids, what, n_scans, one=False):
+    """``ids`` as a contiguous int32 array, checked: a 1-D sequence of integers, every one in [0, n_scans) (repeats and
+    an empty list are fine).  what: (the argument's name, its entries' name) for the messages.  ``one``: a single id,
+    not a sequence -> that id as an int."""
+    name, entries = what
+    a = np.asarray([int(ids)] if one else ids)
+    if a.ndim != 1 or (len(a) and not np.issubdtype(a.dtype, np.integer)):
+        raise ValueError(f"{name} must be a 1-D sequence of scan ids")
+    if len(a) and (a.min() < 0 or a.max() >= n_scans):
+        raise ValueError(f"{entries} must lie in [0, {n_scans}): got " + (f"{ids}" if one else f"{int(a.min())}..{int(a.max())}"))
+    return int(a[0]) if one else np.ascontiguousarray(a, dtype=np.int32)
+
+
 class _ResidentIcp(IcpBatch):
     """``IcpBatch`` over a history's filtered clouds and prepared targets: ``run()`` is the ICP launch alone."""
+    strict_method = True        # nothing here is the reference's call: an unknown method string is refused
 
     def __init__(self, hist, pair_src, pair_tgt, error_threshold, max_iterations, method, max_corr_dist, R_init, t_init):
-        L = _lib.lib()
-        dev = hist.device
-        if method not in ("point_to_point", "point_to_line"):
-            raise ValueError(f"method must be 'point_to_point' or 'point_to_line', got {method!r}")
         if method == "point_to_line" and hist.normal_k is None:
             raise ValueError("this history holds no normals (normal_k=None): point_to_point only")
         self.history = hist
-        self.raw, self.vox, self.dim = hist.raw, hist.vox, 2
-        self.pair_src_host = np.ascontiguousarray(pair_src, dtype=np.int32)
-        self.pair_tgt_host = np.ascontiguousarray(pair_tgt, dtype=np.int32)
-        self.B = len(self.pair_src_host)
-        self.pair_src = torch.from_numpy(self.pair_src_host).to(dev)
-        self.pair_tgt = torch.from_numpy(self.pair_tgt_host).to(dev)
-        self.voxel_size = hist.voxel_size
-        self.normal_k = -1 if hist.normal_k is None else hist.normal_k
-        self.use_p2l = method == "point_to_line"
-        have_init = R_init is not None and t_init is not None                    # icp.py:153
-        self.params = IcpParams(float(error_threshold), -1.0 if max_corr_dist is None else float(max_corr_dist),
-                                int(max_iterations), _lib.POINT_TO_LINE if self.use_p2l else _lib.POINT_TO_POINT,
-                                1 if have_init else 0, 2)
-        self.init = None
-        if have_init:
-            R = np.broadcast_to(np.asarray(R_init, dtype=np.float64), (self.B, 2, 2)).reshape(self.B, 4)
-            t = np.broadcast_to(np.asarray(t_init, dtype=np.float64), (self.B, 2))
-            self.init = torch.from_numpy(np.ascontiguousarray(np.concatenate([R, t], axis=1))).to(dev)
-        sizes = hist.sizes()
-        self.max_src_n = int(sizes[self.pair_src_host].max()) if self.B else 0
-        self.max_tgt_n = int(sizes[self.pair_tgt_host].max()) if self.B else 0
-        self.normals, self.prepared, self.fast = None, hist.icp_prepared, True
-        self.icp_ws = torch.empty(L.icpmi_icp_workspace_bytes(self.B, self.max_src_n, 2), dtype=torch.uint8, device=dev)
-        self.results = torch.zeros((max(self.B, 1), _lib.RES_DOUBLES), dtype=torch.float64, device=dev)
-        self.gate = None
-        self.first_accepted_dev = None
+        self._init_common(hist.raw, pair_src, pair_tgt, error_threshold, max_iterations, hist.voxel_size, R_init, t_init, method,
+                          -1 if hist.normal_k is None else hist.normal_k, max_corr_dist)
+        self.vox, self.normals, self.prepared, self.fast = hist.vox, None, hist.icp_prepared, True
 
     @property
     def layout_rows(self):
@@ -135,25 +122,15 @@ class _ResidentSearch(RotationSearchBatch):
     """``RotationSearchBatch`` over a history's search state: ``run()`` is ``icpmi_history_search``."""
 
     def __init__(self, hist, pair_src, pair_tgt, angle_step_coarse, angle_step_fine, init, max_rows_hint):
-        dev = hist.device
         self.history = hist
-        self.raw = hist.raw
-        self.pair_src_host = np.ascontiguousarray(pair_src, dtype=np.int32)
-        self.pair_tgt_host = np.ascontiguousarray(pair_tgt, dtype=np.int32)
-        self.B = len(self.pair_src_host)
-        self.pair_src = torch.from_numpy(self.pair_src_host).to(dev)
-        self.pair_tgt = torch.from_numpy(self.pair_tgt_host).to(dev)
-        self.voxel_size = hist.rotation_voxel_size
-        self.steps = (angle_step_coarse, angle_step_fine)
-        self.tables = AngleTables.get(dev, angle_step_coarse, angle_step_fine)
-        self.max_rows_hint = int(max_rows_hint)
-        self.too_many_angles = len(self.tables.coarse) > RSB_MAX_ANGLES or self.tables.max_fine > RSB_MAX_ANGLES
-        self.records = torch.zeros((max(self.B, 1), REC_DOUBLES), dtype=torch.float64, device=dev)
-        self.init = init
+        self._init_common(hist.raw, pair_src, pair_tgt, hist.rotation_voxel_size, angle_step_coarse, angle_step_fine, init,
+                          max_rows_hint)
         sizes = hist.sizes()
         self.max_n = int(max(sizes[self.pair_src_host].max(), sizes[self.pair_tgt_host].max())) if self.B else 0
 
     def run(self):
+        if self.too_many_angles:
+            return self.mark_over_capacity()
         t = self.tables
         mf = t.max_fine
         check(_lib.lib().icpmi_history_search(
@@ -171,19 +148,17 @@ class HistoryMatch(RunIcpPairBatch):
     def __init__(self, hist, source_id, candidates, staged, error_threshold, max_iterations, method, max_corr_dist,
                  angle_step_coarse, angle_step_fine, max_rows_hint, error_accept, stop_after_first_accepted, index_base,
                  index_stride):
-        if stop_after_first_accepted and error_accept is None:
-            raise ValueError("stop_after_first_accepted needs a gate: error_accept")
+        _gate_given(stop_after_first_accepted, error_accept)
         B = len(candidates)
-        ps = np.full(B, source_id, dtype=np.int32)
+        pairs = PairList(np.full(B, source_id, dtype=np.int32), candidates)
         self.history = hist
         self.layout_generation = hist.layout_generation
         self.stage_generation = hist.stage_generation if staged else None
-        self.icp = _ResidentIcp(hist, ps, candidates, error_threshold, max_iterations, method, max_corr_dist,
-                                np.tile(np.eye(2), (B, 1, 1)), np.zeros((B, 2)))
-        self.B = B
-        self.alignment_method, self.use_search, self.features = "rotation_search", True, None
-        self.search = _ResidentSearch(hist, ps, candidates, angle_step_coarse, angle_step_fine, self.icp.init, max_rows_hint)
-        self._set_gate(error_accept, stop_after_first_accepted, index_base, index_stride, max_rows_hint, self.search.max_n)
+        icp = _ResidentIcp(hist, pairs, None, error_threshold, max_iterations, method, max_corr_dist,
+                           np.tile(np.eye(2), (B, 1, 1)), np.zeros((B, 2)))
+        search = _ResidentSearch(hist, pairs, None, angle_step_coarse, angle_step_fine, icp.init, max_rows_hint)
+        self._init_parts("rotation_search", icp, search, None, error_accept, stop_after_first_accepted, index_base,
+                         index_stride, max_rows_hint, search.max_n)
 
     def run(self, events=None):
         h = self.history
@@ -351,19 +326,14 @@ class ScanHistory:
         if alignment_method != "rotation_search":
             raise ValueError(f"alignment_method {alignment_method!r} is not resident in a ScanHistory (only 'rotation_search' is): "
                              "use RunIcpPairBatch for 'features' and 'both'")
-        cands = np.asarray(candidates)
-        if cands.ndim != 1 or (len(cands) and not np.issubdtype(cands.dtype, np.integer)):
-            raise ValueError("candidates must be a 1-D sequence of scan ids")
-        if len(cands) and (cands.min() < 0 or cands.max() >= self.n_scans):
-            raise ValueError(f"candidate ids must lie in [0, {self.n_scans}): got {int(cands.min())}..{int(cands.max())}")
-        cands = np.ascontiguousarray(cands, dtype=np.int32)
+        cands = _scan_ids(candidates, ("candidates", "candidate ids"), self.n_scans)
         staged = not isinstance(source, (int, np.integer))
         if staged:
             arr = self._clouds([source])
             self._place(arr, self.n_scans, prepare=False)        # cloud n_scans, for this match: rows_used stays
             source = self.n_scans
-        elif not 0 <= source < self.n_scans:
-            raise ValueError(f"source id must lie in [0, {self.n_scans}): got {source}")
+        else:
+            source = _scan_ids(source, ("source", "source id"), self.n_scans, one=True)
         return HistoryMatch(self, int(source), cands, staged, error_threshold, max_iterations, method, max_corr_dist,
                             angle_step_coarse, angle_step_fine, max_rows_hint, error_accept, stop_after_first_accepted,
                             index_base, index_stride)
@@ -375,12 +345,7 @@ class ScanHistory:
         if ids is None:
             ids = np.arange(self.n_scans, dtype=np.int32)
         else:
-            ids = np.asarray(ids)
-            if ids.ndim != 1 or (len(ids) and not np.issubdtype(ids.dtype, np.integer)):
-                raise ValueError("ids must be a 1-D sequence of scan ids")
-            if len(ids) and (ids.min() < 0 or ids.max() >= self.n_scans):
-                raise ValueError(f"scan ids must lie in [0, {self.n_scans}): got {int(ids.min())}..{int(ids.max())}")
-            ids = np.ascontiguousarray(ids, dtype=np.int32)
+            ids = _scan_ids(ids, ("ids", "scan ids"), self.n_scans)
         pose6 = pose_rows(poses, len(ids))
         ends = np.cumsum(self.sizes()[ids], dtype=np.int64)
         if len(ends) and ends[-1] >= 2 ** 31:
@@ -412,9 +377,7 @@ class ScanHistory:
         """``ICP(scan source_id, scan target_id, ...)`` (icp.py:132-223) against the resident prepared target — the
         scan-to-scan step of slam.py:471 with the previous scan already prepared -> (R, t, err, info) like ``icp_pair``
         (synchronises)."""
-        for k in (source_id, target_id):
-            if not 0 <= k < self.n_scans:
-                raise ValueError(f"scan ids must lie in [0, {self.n_scans}): got {k}")
+        source_id, target_id = (_scan_ids(k, ("ids", "scan ids"), self.n_scans, one=True) for k in (source_id, target_id))
         b = _ResidentIcp(self, [source_id], [target_id], error_threshold, max_iterations, method, max_corr_dist, R_init, t_init)
         b.run()
         return b.unpack()

@@ -18,7 +18,8 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .batch import CloudSet, IcpBatch, _ptr, _stream, require_gpu, unpack_results
+from .batch import (CloudSet, IcpBatch, PairList, _Paired, _ptr, _stream, icp_pair, pack_results, pair_lists, require_gpu,
+                    unpack_results)
 
 # the records' layout, statuses and capacities are include/icpmi.h's, mirrored once in _lib; the names users import stay
 REC_DOUBLES = _lib.RSBREC_DOUBLES                                # (the feature record has the same stride)
@@ -97,7 +98,7 @@ class AngleTables:
         return self.d_cs, self.d_fcs, self.d_fn
 
 
-class RotationSearchBatch:
+class RotationSearchBatch(_Paired):
     """rotation_search (features.py:165-242) of every pair of a cloud set, resident on the device.
 
     ``run()`` enqueues the chain on the current stream and returns the (B, 16) record tensor; ``init`` ([B, 6]: R row
@@ -107,38 +108,43 @@ class RotationSearchBatch:
     def __init__(self, clouds, pair_src, pair_tgt, voxel_size=0.3, angle_step_coarse=2.0, angle_step_fine=0.2,
                  init=None, max_rows_hint=0):
         require_gpu()
-        L = _lib.lib()
-        self.raw = clouds if isinstance(clouds, CloudSet) else CloudSet.from_numpy(clouds)
-        if self.raw.dim != 2:
-            raise ValueError("rotation_search is 2-D")
-        dev = self.raw.pts.device
-        self.pair_src_host = np.ascontiguousarray(pair_src, dtype=np.int32)
-        self.pair_tgt_host = np.ascontiguousarray(pair_tgt, dtype=np.int32)
-        self.B = len(self.pair_src_host)
-        if len(self.pair_tgt_host) != self.B:
-            raise ValueError("pair_src and pair_tgt differ in length")
-        self.pair_src = torch.from_numpy(self.pair_src_host).to(dev)
-        self.pair_tgt = torch.from_numpy(self.pair_tgt_host).to(dev)
+        raw = clouds if isinstance(clouds, CloudSet) else CloudSet.from_numpy(clouds)
+        self._init_common(raw, pair_src, pair_tgt, voxel_size, angle_step_coarse, angle_step_fine, init, max_rows_hint)
+        dev = raw.pts.device
         self.tgt_ids = torch.from_numpy(np.unique(self.pair_tgt_host).astype(np.int32)).to(dev)
-        self.voxel_size = float(voxel_size)
-        if not self.voxel_size > 0:
+        need = _lib.lib().icpmi_rotation_search_batch_workspace_bytes(raw.total_rows, raw.n_clouds, raw.max_n)
+        self.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+
+    def _init_common(self, raw, pair_src, pair_tgt, voxel_size, angle_step_coarse, angle_step_fine, init, max_rows_hint):
+        """What every variant needs: the pairs, the angle tables, the records and where the starts go.  The filtered
+        clouds and their search order are the workspace's (a resident variant: a history's)."""
+        if raw.dim != 2:
+            raise ValueError("rotation_search is 2-D")
+        if not voxel_size > 0:
             raise ValueError("voxel_size must be positive")
+        dev = raw.pts.device
+        self.raw, self.voxel_size = raw, float(voxel_size)
+        self.pairs = PairList.of(pair_src, pair_tgt).to(dev)
         self.steps = (angle_step_coarse, angle_step_fine)
         self.tables = AngleTables.get(dev, angle_step_coarse, angle_step_fine)
         self.max_rows_hint = int(max_rows_hint)
         self.too_many_angles = len(self.tables.coarse) > RSB_MAX_ANGLES or self.tables.max_fine > RSB_MAX_ANGLES
         self.records = torch.zeros((max(self.B, 1), REC_DOUBLES), dtype=torch.float64, device=dev)
         self.init = init if init is not None else torch.zeros((max(self.B, 1), 6), dtype=torch.float64, device=dev)
-        need = L.icpmi_rotation_search_batch_workspace_bytes(self.raw.total_rows, self.raw.n_clouds, self.raw.max_n)
-        self.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+
+    def mark_over_capacity(self):
+        """More angles than the batched kernel tabulates (a step below ~0.36 degrees; icpmi_rotation_search_batch would
+        answer ICPMI_ERR_UNSUPPORTED): every record becomes ST_CAPACITY, and such pairs are searched one by one through
+        the single-pair entry when the results are read — same numbers."""
+        self.records.zero_()
+        self.records[:, _lib.RSBREC_STATUS] = ST_CAPACITY
+        return self.records
 
     def run(self):
+        if self.too_many_angles:
+            return self.mark_over_capacity()
         t = self.tables
         mf = t.max_fine
-        if self.too_many_angles:                   # icpmi_rotation_search_batch would answer ICPMI_ERR_UNSUPPORTED
-            self.records.zero_()
-            self.records[:, _lib.RSBREC_STATUS] = ST_CAPACITY      # results() searches such pairs one by one: same numbers
-            return self.records
         check(_lib.lib().icpmi_rotation_search_batch(
             _ptr(self.raw.pts), _ptr(self.raw.off), self.raw.off_host.ctypes.data_as(C.c_void_p), self.raw.n_clouds,
             _ptr(self.tgt_ids), len(self.tgt_ids), _ptr(self.pair_src), _ptr(self.pair_tgt), self.B, self.voxel_size,
@@ -147,18 +153,24 @@ class RotationSearchBatch:
             "rotation_search (batch)")
         return self.records
 
+    def host_records(self, records=None):
+        """The records of the last run on the host (synchronises); raises as np.argmin(scores_fine) does in the reference
+        (features.py:231) when a winning coarse angle has an empty fine grid."""
+        rec = (self.records if records is None else records).cpu().numpy()[:self.B]
+        if (rec[:, _lib.RSBREC_STATUS].astype(np.int64) == ST_NO_FINE).any():
+            raise ValueError("attempt to get argmin of an empty sequence")
+        return rec
+
     def results(self, records=None):
         """-> (R [B,2,2], t [B,2], score [B], records [B,16]) on the host (synchronises).  Pairs the on-chip search could
         not hold (ST_CAPACITY: a filtered cloud above the capacity hint) are searched one by one through the single-pair
         entry — same numbers."""
-        rec = (self.records if records is None else records).cpu().numpy()[:self.B]
+        rec = self.host_records(records)
         t = self.tables
         R = np.tile(np.eye(2), (self.B, 1, 1))
         tt = np.zeros((self.B, 2))
         score = np.full(self.B, np.inf)
         status = rec[:, _lib.RSBREC_STATUS].astype(np.int64)
-        if (status == ST_NO_FINE).any():
-            raise ValueError("attempt to get argmin of an empty sequence")          # np.argmin(scores_fine) on an empty grid
         ok = np.flatnonzero(status == ST_OK)
         if len(ok):
             ang = winning_angle(t.coarse, t.fine, rec[ok])
@@ -189,7 +201,7 @@ FEAT_DEFAULTS = dict(voxel_size=0.2, k_curvature=10, top_n=100, min_kp_dist=0.3,
                      ransac_iterations=1000, inlier_threshold=0.5, min_inliers=3)            # slam.py:72-83
 
 
-class FeatureAlignBatch:
+class FeatureAlignBatch(_Paired):
     """feature_based_alignment (features.py:247-315) of every pair of a cloud set, resident on the device.
 
     ``run()`` enqueues the chain of ``icpmi_feature_align_batch`` on the current stream — voxel filter at the feature voxel
@@ -222,13 +234,7 @@ class FeatureAlignBatch:
         self.cfg = cfg
         if not cfg["voxel_size"] > 0:
             raise ValueError("voxel_size must be positive")
-        self.pair_src_host = np.ascontiguousarray(pair_src, dtype=np.int32)
-        self.pair_tgt_host = np.ascontiguousarray(pair_tgt, dtype=np.int32)
-        self.B = len(self.pair_src_host)
-        if len(self.pair_tgt_host) != self.B:
-            raise ValueError("pair_src and pair_tgt differ in length")
-        self.pair_src = torch.from_numpy(self.pair_src_host).to(dev)
-        self.pair_tgt = torch.from_numpy(self.pair_tgt_host).to(dev)
+        self.pairs = PairList.of(pair_src, pair_tgt).to(dev)
         self.n_iter = int(cfg["ransac_iterations"])
         self.hyp_idx = self.hyp_u = None
         if like is not None:                               # another batch's hypothesis table (a pair redone on its own)
@@ -269,25 +275,19 @@ class FeatureAlignBatch:
 def rotation_search_batch(sources, targets, voxel_size=0.3, angle_step_coarse=2.0, angle_step_fine=0.2):
     """rotation_search(sources[i], targets[i]) for every i in one chain of launches -> (R [B,2,2], t [B,2], score [B]).
     ``sources`` may be one array shared by every pair (the loop-closure shape, slam.py:576-579)."""
-    clouds, ps, pt = _pair_lists(sources, targets)
+    clouds, ps, pt = pair_lists(sources, targets)
     b = RotationSearchBatch(clouds, ps, pt, voxel_size, angle_step_coarse, angle_step_fine)
     b.run()
     R, t, score, _ = b.results()
     return R, t, score
 
 
-def _pair_lists(sources, targets):
-    targets = list(targets)
-    B = len(targets)
-    if isinstance(sources, np.ndarray) and sources.ndim == 2:
-        return [sources] + targets, np.zeros(B, dtype=np.int32), np.arange(1, B + 1, dtype=np.int32)
-    sources = list(sources)
-    if len(sources) != B:
-        raise ValueError("sources and targets differ in length")
-    return sources + targets, np.arange(B, dtype=np.int32), np.arange(B, 2 * B, dtype=np.int32)
+def _gate_given(stop_after_first_accepted, error_accept):
+    if stop_after_first_accepted and error_accept is None:
+        raise ValueError("stop_after_first_accepted needs a gate: error_accept")
 
 
-class RunIcpPairBatch:
+class RunIcpPairBatch(_Paired):
     """``_run_icp_pair`` (slam.py:53-98) for a batch of pairs resident in HBM: ``run()`` = the pre-alignment of every pair
     — rotation search (``alignment_method`` "rotation_search", the default), feature alignment ("features") or the search
     followed by the feature alignment from its result ("both") — then ICP of every pair from its own R_init / t_init:
@@ -308,29 +308,32 @@ class RunIcpPairBatch:
                  index_base=0, index_stride=1, alignment_method="rotation_search", feat_cfg=None, hypotheses=None, rng=None):
         if alignment_method not in ALIGNMENT_METHODS:
             raise ValueError(f"alignment_method must be one of {ALIGNMENT_METHODS}, got {alignment_method!r}")
-        if stop_after_first_accepted and error_accept is None:
-            raise ValueError("stop_after_first_accepted needs a gate: error_accept")
+        _gate_given(stop_after_first_accepted, error_accept)
         raw = clouds if isinstance(clouds, CloudSet) else CloudSet.from_numpy(clouds)
-        B = len(pair_src)
-        self.icp = IcpBatch(raw, pair_src, pair_tgt, error_threshold, max_iterations, voxel_size,
-                            np.tile(np.eye(2), (B, 1, 1)), np.zeros((B, 2)), method, normal_k, max_corr_dist)
-        self.B = B
-        self.alignment_method = alignment_method
-        self.use_search = alignment_method in ("rotation_search", "both")           # slam.py:60
-        self.search = None
-        if self.use_search:
-            self.search = RotationSearchBatch(raw, pair_src, pair_tgt, rotation_voxel_size, angle_step_coarse, angle_step_fine,
-                                              init=self.icp.init, max_rows_hint=max_rows_hint)
+        pairs = PairList.of(pair_src, pair_tgt)                 # one pair list, uploaded once, for every part
+        B = pairs.B
+        icp = IcpBatch(raw, pairs, None, error_threshold, max_iterations, voxel_size,
+                       np.tile(np.eye(2), (B, 1, 1)), np.zeros((B, 2)), method, normal_k, max_corr_dist)
+        search = features = None
+        if alignment_method in ("rotation_search", "both"):                         # slam.py:60
+            search = RotationSearchBatch(raw, pairs, None, rotation_voxel_size, angle_step_coarse, angle_step_fine,
+                                         init=icp.init, max_rows_hint=max_rows_hint)
         # slam.py:68-88: the feature alignment starts from the search's result ("both") or from the raw source, and leaves
         # the start of the ICP where the search would have: in the ICP's own init tensor
-        self.features = None
         if alignment_method in ("features", "both"):
-            self.features = FeatureAlignBatch(raw, pair_src, pair_tgt, feat_cfg, hypotheses, rng,
-                                              init_in=self.icp.init if self.use_search else None, init_out=self.icp.init)
-        self._set_gate(error_accept, stop_after_first_accepted, index_base, index_stride, max_rows_hint, raw.max_n)
+            features = FeatureAlignBatch(raw, pairs, None, feat_cfg, hypotheses, rng,
+                                         init_in=icp.init if search is not None else None, init_out=icp.init)
+        self._init_parts(alignment_method, icp, search, features, error_accept, stop_after_first_accepted, index_base,
+                         index_stride, max_rows_hint, raw.max_n)
 
-    def _set_gate(self, error_accept, stop_after_first_accepted, index_base, index_stride, max_rows_hint, max_raw_n):
-        """The gate of slam.py:582-597 over ``self.icp`` / ``self.search`` (max_raw_n: rows of the largest raw cloud of a pair)."""
+    def _init_parts(self, alignment_method, icp, search, features, error_accept, stop_after_first_accepted, index_base,
+                    index_stride, max_rows_hint, max_raw_n):
+        """The job over parts already built — ``icp``, ``search`` (None: no search) and ``features`` (None: none) over one
+        pair list, the search writing its starts into ``icp.init`` — and the gate of slam.py:582-597 over them
+        (max_raw_n: rows of the largest raw cloud of a pair)."""
+        self.icp, self.search, self.features = icp, search, features
+        self.pairs = icp.pairs
+        self.alignment_method, self.use_search = alignment_method, search is not None
         self.error_accept = None if error_accept is None else float(error_accept)
         self.stop = bool(stop_after_first_accepted)
         self.index_base, self.index_stride = int(index_base), int(index_stride)
@@ -346,10 +349,7 @@ class RunIcpPairBatch:
             self.features.run()
             return self.icp.run(events=events)
         if self.search.too_many_angles:
-            # more angles than the batched kernel tabulates (a step below ~0.36 degrees): every pair is searched by the
-            # single-pair entry, as pairs beyond the capacity hint are — same numbers
-            self.search.records.zero_()
-            self.search.records[:, _lib.RSBREC_STATUS] = ST_CAPACITY
+            self.search.mark_over_capacity()
             if self.stop:
                 self.icp.first_accepted_dev.fill_(-1)  # no candidate ran on the device: unpack() redoes them in order
             if events is not None:
@@ -377,7 +377,6 @@ class RunIcpPairBatch:
     def _redo(self, i, R0, t0, clouds):
         """The ICP of pair i through the single-pair entry, from the single-pair search's start — with "both", carried on
         by the pair's own feature alignment (same configuration, same hypothesis table) -> its 16-double record."""
-        from .batch import icp_pair
         p = self.icp.params
         Rs, ts = R0[i], t0[i]
         if self.features is not None:
@@ -387,27 +386,20 @@ class RunIcpPairBatch:
             self.redone_feature_records[int(i)] = one.run().cpu().numpy()[0]
             v = start.cpu().numpy()[0]
             Rs, ts = v[:4].reshape(2, 2), v[4:]
-        Ri, ti, ei, info = icp_pair(clouds[self.icp.pair_src_host[i]], clouds[self.icp.pair_tgt_host[i]],
-                                    p.error_threshold, p.max_iterations, self.icp.voxel_size, Rs, ts,
-                                    "point_to_line" if self.icp.use_p2l else "point_to_point", self.icp.normal_k,
-                                    None if p.max_corr_dist < 0 else p.max_corr_dist)
-        r = np.zeros(_lib.RES_DOUBLES)
-        r[_lib.RES_R:_lib.RES_R + 4] = Ri[0].reshape(4); r[_lib.RES_T:_lib.RES_T + 2] = ti[0]; r[_lib.RES_ERR] = ei[0]
-        r[_lib.RES_DELTA] = info["delta"][0]; r[_lib.RES_ITERS] = info["iters"][0]; r[_lib.RES_STATUS] = info["status"][0]
-        return r
+        return pack_results(*icp_pair(clouds[self.icp.pair_src_host[i]], clouds[self.icp.pair_tgt_host[i]],
+                                      p.error_threshold, p.max_iterations, self.icp.voxel_size, Rs, ts,
+                                      "point_to_line" if self.icp.use_p2l else "point_to_point", self.icp.normal_k,
+                                      None if p.max_corr_dist < 0 else p.max_corr_dist))[0]
 
     def unpack(self):
         """(R, t, err, info) of the ICPs; pairs whose search fell outside the on-chip capacity (status 2) are redone
         with the single-pair search's result as their start (and, with "both", their own feature alignment from it).  With a gate, info["first_accepted"] is the candidate
         slam.py:582-597 accepts (-1: none); with stop_after_first_accepted, a status-2 candidate after it is not redone
         but reported SKIPPED (identity, err inf, 0 iterations), and info["status"] is 5 for every skipped candidate."""
-        rec = self.search.records.cpu().numpy()[:self.B] if self.use_search else np.zeros((self.B, REC_DOUBLES))
+        rec = self.search.host_records() if self.use_search else np.zeros((self.B, REC_DOUBLES))
         res = self.icp.results.cpu().numpy()[:self.B].copy()
         self.redone_feature_records = {}
-        status = rec[:, _lib.RSBREC_STATUS].astype(np.int64)
-        if (status == ST_NO_FINE).any():
-            raise ValueError("attempt to get argmin of an empty sequence")          # features.py:231: np.argmin of an empty fine grid
-        over = np.flatnonzero(status == ST_CAPACITY)
+        over = np.flatnonzero(rec[:, _lib.RSBREC_STATUS].astype(np.int64) == ST_CAPACITY)
         first = -1
         if self.stop:
             # the device's answer never counts a status-2 candidate (its device ICP started from the wrong pose): the
@@ -448,10 +440,8 @@ def run_icp_pair_batch(sources, targets, icp_cfg=None, feat_cfg=None, error_acce
     the candidates after it stop early (status 5, RunIcpPairBatch).  ``alignment_method``: "rotation_search" (the
     default: exactly the launches of before), "features" or "both" (FeatureAlignBatch, with its ``hypotheses`` / ``rng``;
     ``info["feature_records"]`` then holds its records)."""
-    if alignment_method not in ALIGNMENT_METHODS:
-        raise ValueError(f"alignment_method must be one of {ALIGNMENT_METHODS}, got {alignment_method!r}")
     icp_cfg, feat_cfg = icp_cfg or {}, feat_cfg or {}
-    clouds, ps, pt = _pair_lists(sources, targets)
+    clouds, ps, pt = pair_lists(sources, targets)
     b = RunIcpPairBatch(clouds, ps, pt,
                         error_threshold=icp_cfg.get("error_threshold", 1e-7), max_iterations=icp_cfg.get("max_iterations", 100),
                         voxel_size=icp_cfg.get("voxel_size", 0.06), method=icp_cfg.get("method", "point_to_line"),

@@ -39,25 +39,16 @@ class RollingSubmap:
     def __len__(self):
         return len(self._scans)
 
-    def _to_dev(self, pts):
-        if isinstance(pts, torch.Tensor):
-            t = pts.to(self._dev, torch.float64)
-        else:
-            t = torch.from_numpy(np.ascontiguousarray(pts, dtype=np.float64)).to(self._dev)
-        if t.dim() != 2 or t.shape[1] != 2:
-            raise ValueError("scans must have shape (n, 2)")
-        return t.contiguous()
-
     def push(self, global_points):
         """slam.py:559-562: append the scan (global frame); drop the oldest beyond the window."""
-        self._scans.append(self._to_dev(global_points))
+        self._scans.append(_device_rows(global_points, self._dev))
         if len(self._scans) > self.window:
             self._scans.pop(0)
         self._built = None
 
     def reset(self, scans=()):
         """slam.py:612-615: rebuild the buffer from (the tail of) a list of global-frame scans."""
-        self._scans = [self._to_dev(s) for s in list(scans)[-self.window:]]
+        self._scans = [_device_rows(s, self._dev) for s in list(scans)[-self.window:]]
         self._built = None
 
     def reset_from_history(self, history, poses, ids=None):
@@ -105,13 +96,8 @@ class RollingSubmap:
         sub, _ = self.build()
         if sub.shape[0] == 0:
             raise ValueError("the submap is empty")
-        src = self._to_dev(source_local)
-        pts = torch.cat([src, sub], dim=0)
-        cs = _b.CloudSet(pts, np.array([0, src.shape[0], src.shape[0] + sub.shape[0]], dtype=np.int32))
-        b = _b.IcpBatch(cs, [0], [1], error_threshold, max_iterations, voxel_size, R_init, t_init, method, normal_k,
-                        max_corr_dist)
-        b.run()
-        R, t, err, info = b.unpack()
+        R, t, err, info = _two_cloud_icp(_device_rows(source_local, self._dev), sub, error_threshold, max_iterations, voxel_size,
+                                         R_init, t_init, method, normal_k, max_corr_dist)
         return R[0], t[0], err[0], {k: v[0] for k, v in info.items()}
 
     def rotation_search(self, source_local, predicted_pose, **kw):
@@ -128,8 +114,9 @@ class RollingSubmap:
 
 
 # ── slam.py:111-225 ──────────────────────────────────────────────────────────
-def _device_rows(points):
-    dev = torch.device("cuda", torch.cuda.current_device())
+def _device_rows(points, dev=None):
+    """An (n, 2) array or tensor as a contiguous float64 tensor on ``dev`` (None: the current device)."""
+    dev = dev if dev is not None else torch.device("cuda", torch.cuda.current_device())
     if isinstance(points, torch.Tensor):
         t = points.to(dev, torch.float64)
     else:
@@ -137,6 +124,16 @@ def _device_rows(points):
     if t.dim() != 2 or t.shape[1] != 2:
         raise ValueError("points must have shape (n, 2)")
     return t.contiguous()
+
+
+def _two_cloud_icp(src_d, tgt_d, *icp_args):
+    """ICP of one device cloud onto another, neither visiting the host: ``IcpBatch`` over the two as one set (``icp_args``:
+    its arguments from error_threshold on) -> ``unpack()`` of the one pair."""
+    n = src_d.shape[0]
+    cs = _b.CloudSet(torch.cat([src_d, tgt_d], dim=0), np.array([0, n, n + tgt_d.shape[0]], dtype=np.int32))
+    b = _b.IcpBatch(cs, [0], [1], *icp_args)
+    b.run()
+    return b.unpack()
 
 
 def _voxel_rows(points_dev, voxel_size):
@@ -248,11 +245,7 @@ def attempt_submap_icp(source, submap, predicted, imu_yaw, imu_narrow, sub_rot_r
         angle_range, angle_step = sub_rot_range, sub_rot_step
     R_init, t_init = submap_rotation_search(source, submap, pred, angle_range=angle_range, angle_step=angle_step,
                                             fine_step=sub_rot_fine, voxel_size=sub_rot_voxel)
-    src_d, sub_d = _device_rows(source), _device_rows(submap)
-    pts = torch.cat([src_d, sub_d], dim=0)
-    cs = _b.CloudSet(pts, np.array([0, len(src_d), len(src_d) + len(sub_d)], dtype=np.int32))
-    b = _b.IcpBatch(cs, [0], [1], icp_cfg.get("error_threshold", 1e-7), icp_cfg.get("max_iterations", 100),
-                    icp_cfg.get("voxel_size", 0.06), R_init, t_init, "point_to_point", 10, sub_corr_dist)
-    b.run()
-    R, t, err, info = b.unpack()
+    R, t, err, info = _two_cloud_icp(_device_rows(source), _device_rows(submap), icp_cfg.get("error_threshold", 1e-7),
+                                     icp_cfg.get("max_iterations", 100), icp_cfg.get("voxel_size", 0.06), R_init, t_init,
+                                     "point_to_point", 10, sub_corr_dist)
     return R[0], t[0], _uicp._report(err[0], info, 0, icp_cfg.get("max_iterations", 100))

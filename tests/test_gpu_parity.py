@@ -1244,6 +1244,45 @@ def test_pair_context_keeps_the_sweep_path_above_4096_rows_in_all(uicp):
     assert uicp.last_icp_info["iterations"] == io["iters"] and rot_err(R, t, Ro, to) < FRO_TOL
 
 
+def test_pair_context_re_aimed_call_after_call_equals_fresh_batches(uicp):
+    """Six ``icp_pair`` calls in a row through one ``PairContext``, each re-aiming the cached batch (IcpBatch.set_problem):
+    other methods, with and without a start, with a correspondence limit, a small pair after a larger one (stale row counts
+    would show), a source that makes the context grow, and the first call again.  The 16-double record of every call is that
+    of a fresh ``IcpBatch`` over the same two clouds and arguments, bit for bit."""
+    import torch
+    from icpmi import batch, synth
+    a, b = synth.scan((0.0, 0.0, 0.0), 41), synth.scan((0.15, -0.08, np.deg2rad(3.0)), 42)
+    a300, b300, a64, b64 = a[::6][:300], b[::6][:300], a[::32][:64], b[::32][:64]
+    big = synth.scan((0.05, 0.02, np.deg2rad(1.0)), 43, n_beams=2100)
+    assert (len(a300), len(b300), len(a64), len(b64), len(big)) == (300, 300, 64, 64, 2100)
+    th = np.deg2rad(2.0)
+    R0, t0 = np.array([[np.cos(th), -np.sin(th)], [np.sin(th), np.cos(th)]]), np.array([0.1, -0.05])
+    calls = [(a300, b300, R0, t0, "point_to_line", 10, None),
+             (a300, b300, None, None, "point_to_point", 10, None),
+             (a300, b300, None, None, "point_to_line", 8, 0.5),
+             (a64, b64, R0, None, "point_to_line", 10, None),            # (half a start is no start, icp.py:153)
+             (big, b300, None, None, "point_to_line", 10, None),
+             (a300, b300, R0, t0, "point_to_line", 10, None)]
+    batch.PairContext._per_device.pop(torch.device("cuda", torch.cuda.current_device()), None)
+    ctx = batch.PairContext.get()                                         # a new context: 2 048 rows a side until it grows
+    got, caps = [], []
+    for src, tgt, Ri, ti, method, k, corr in calls:
+        out = batch.icp_pair(src, tgt, 1e-10, 60, 0.04, Ri, ti, method, k, corr)
+        assert batch.PairContext.get() is ctx
+        rec = ctx.res_host.numpy()[0].copy()
+        for x, y in zip(out[:3], batch.unpack_results(rec[None, :], 2)[:3]):
+            assert np.array_equal(x, y, equal_nan=True)
+        got.append(rec)
+        caps.append(ctx.cap_s)
+    assert caps == [2048, 2048, 2048, 2048, 4096, 4096]                   # call 5 went through _grow
+    for i, (src, tgt, Ri, ti, method, k, corr) in enumerate(calls):
+        fresh = batch.IcpBatch([src, tgt], [0], [1], 1e-10, 60, 0.04, Ri, ti, method, k, corr)
+        want = fresh.run().cpu().numpy()[0]
+        assert want.shape == (16,) and np.array_equal(got[i], want), (i, got[i], want)
+        assert want[15] in (1, 2) and want[14] >= 2, (i, want)           # a real registration, not an early refusal
+    assert np.array_equal(got[5], got[0])
+
+
 def test_library_options_and_shutdown(uicp):
     """icpmi_set_option / icpmi_shutdown (include/icpmi.h, "library state"): unknown names are refused, a set option
     takes effect without touching the environment, shutdown destroys the side streams and later calls make them again."""

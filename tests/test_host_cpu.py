@@ -521,7 +521,7 @@ def test_candidate_poses_stay_out_of_obstacles():
 
 
 def test_pair_lists_of_the_batched_run_icp_pair():
-    from icpmi.prealign import _pair_lists
+    from icpmi.batch import pair_lists as _pair_lists
     a, b, c = np.zeros((5, 2)), np.ones((6, 2)), np.ones((7, 2))
     clouds, ps, pt = _pair_lists(a, [b, c])                              # one source shared by every pair (slam.py:576-579)
     assert len(clouds) == 3 and list(ps) == [0, 0] and list(pt) == [1, 2]
@@ -529,6 +529,97 @@ def test_pair_lists_of_the_batched_run_icp_pair():
     assert len(clouds) == 4 and list(ps) == [0, 1] and list(pt) == [2, 3]
     with pytest.raises(ValueError):
         _pair_lists([a], [b, c])
+
+
+def test_pair_list_refuses_lists_of_different_lengths():
+    """icpmi.batch.PairList, its host half (no device): int32 copies, the number of pairs, the one length check."""
+    from icpmi.batch import PairList
+    p = PairList([0, 0, 1], (3, 4, 5))
+    assert p.B == 3 and p.src_host.dtype == p.tgt_host.dtype == np.int32 and p.src is None and p.tgt is None
+    assert list(p.src_host) == [0, 0, 1] and list(p.tgt_host) == [3, 4, 5]
+    assert PairList.of(p) is p and PairList.of([1], [2]).B == 1 and PairList([], []).B == 0
+    for ps, pt in (([0, 1], [2]), ([0], [1, 2]), ([], [0])):
+        with pytest.raises(ValueError, match="pair_src and pair_tgt differ in length"):
+            PairList(ps, pt)
+
+
+def test_icp_params_builder():
+    """icpmi.batch.icp_params: the reference's rules for the ICP problem record (icp.py:153, 162, 196), once."""
+    from icpmi import _lib
+    from icpmi.batch import icp_params, init_rows
+    p = icp_params(1e-7, 0.5, 100, "point_to_line", True, 2)
+    assert (p.error_threshold, p.max_corr_dist, p.max_iterations, p.method, p.has_init, p.dim) == (1e-7, 0.5, 100, _lib.POINT_TO_LINE, 1, 2)
+    assert icp_params(1e-7, None, 100, "point_to_line", False, 3).method == _lib.POINT_TO_POINT       # 3-D: icp.py:162
+    assert icp_params(1e-7, None, 100, "point_to_point", False, 2).method == _lib.POINT_TO_POINT
+    assert icp_params(1e-7, None, 100, "plane", False, 2).method == _lib.POINT_TO_POINT                # IcpBatch: icp.py:196 else-branch
+    for dim in (2, 3):
+        with pytest.raises(ValueError, match="method must be 'point_to_point' or 'point_to_line', got 'plane'"):
+            icp_params(1e-7, None, 100, "plane", False, dim, strict=True)                              # the history's policy
+    assert icp_params(1e-7, None, 100, "point_to_line", False, 2, strict=True).method == _lib.POINT_TO_LINE
+    assert icp_params(1e-7, None, 100, "point_to_point", False, 2).max_corr_dist == -1.0
+    # an init counts only when both halves are given (icp.py:153)
+    R, t = np.eye(2), np.zeros(2)
+    for Ri, ti, want in ((R, t, 1), (R, None, 0), (None, t, 0), (None, None, 0)):
+        rows = init_rows(Ri, ti, 1, 2)
+        assert (rows is not None) == bool(want)
+        assert icp_params(1e-7, None, 100, "point_to_point", rows is not None, 2).has_init == want
+
+
+def test_init_rows_builder():
+    """icpmi.batch.init_rows against the expression IcpBatch.__init__ held before: one start broadcast to every pair, one
+    start per pair, and the 3-D case."""
+    from icpmi.batch import init_rows
+    rng = np.random.default_rng(3)
+
+    def before(R_init, t_init, B, d):
+        R = np.broadcast_to(np.asarray(R_init, dtype=np.float64), (B, d, d)).reshape(B, d * d)
+        t = np.broadcast_to(np.asarray(t_init, dtype=np.float64), (B, d))
+        return np.ascontiguousarray(np.concatenate([R, t], axis=1))
+
+    for shape_R, shape_t, B, d in (((2, 2), (2,), 3, 2), ((3, 2, 2), (3, 2), 3, 2), ((3, 3), (3,), 3, 3), ((3, 3), (3,), 1, 3)):
+        R, t = rng.normal(size=shape_R), rng.normal(size=shape_t)
+        got = init_rows(R, t, B, d)
+        assert got.shape == (B, d * d + d) and got.dtype == np.float64 and got.flags.c_contiguous
+        assert np.array_equal(got, before(R, t, B, d))
+    got = init_rows(R := rng.normal(size=(2, 2)), t := rng.normal(size=2), 3, 2)
+    assert all(np.array_equal(row, np.concatenate([R.ravel(), t])) for row in got)               # R row major, then t
+    per = init_rows(Rs := rng.normal(size=(3, 2, 2)), ts := rng.normal(size=(3, 2)), 3, 2)
+    assert all(np.array_equal(per[b], np.concatenate([Rs[b].ravel(), ts[b]])) for b in range(3))
+    with pytest.raises(ValueError):
+        init_rows(np.eye(2), np.zeros(2), 3, 3)                                                 # a 2-D start for 3-D pairs
+
+
+def test_scan_ids_validator():
+    """icpmi.history._scan_ids: the one check of scan ids behind ScanHistory.match, world_row_args and icp, with the messages
+    each of them raised before."""
+    from icpmi.history import _scan_ids
+    cand, ids = ("candidates", "candidate ids"), ("ids", "scan ids")
+    for what, m1, m2 in ((cand, "candidates must be a 1-D sequence of scan ids", "candidate ids must lie in [0, 7): got "),
+                         (ids, "ids must be a 1-D sequence of scan ids", "scan ids must lie in [0, 7): got ")):
+        for bad in ([[0, 1], [2, 3]], [0.0, 1.0], [0.5], 3):                                      # 2-D, floats, a scalar
+            with pytest.raises(ValueError) as e:
+                _scan_ids(bad, what, 7)
+            assert str(e.value) == m1
+        for bad, got in (([0, -1, 3], "-1..3"), ([7], "7..7"), ([0, 12], "0..12"), (np.array([-2, 9]), "-2..9")):
+            with pytest.raises(ValueError) as e:
+                _scan_ids(bad, what, 7)
+            assert str(e.value) == m2 + got
+        out = _scan_ids([], what, 7)                                                               # an empty list is fine
+        assert out.shape == (0,) and out.dtype == np.int32
+        out = _scan_ids([6, 0, 6, 6, 3], what, 7)                                                  # and so are repeats
+        assert out.dtype == np.int32 and out.flags.c_contiguous and list(out) == [6, 0, 6, 6, 3]
+        assert list(_scan_ids(np.array([1, 2], dtype=np.int64), what, 7)) == [1, 2]
+        with pytest.raises(ValueError, match="got 0..0"):
+            _scan_ids([0], what, 0)                                                                # an empty history has no ids
+    # one id, not a sequence (ScanHistory.icp, the source of ScanHistory.match)
+    assert _scan_ids(6, ids, 7, one=True) == 6 and _scan_ids(np.int32(0), ids, 7, one=True) == 0
+    for bad in (7, -1):
+        with pytest.raises(ValueError) as e:
+            _scan_ids(bad, ids, 7, one=True)
+        assert str(e.value) == f"scan ids must lie in [0, 7): got {bad}"
+    with pytest.raises(ValueError) as e:
+        _scan_ids(9, ("source", "source id"), 7, one=True)
+    assert str(e.value) == "source id must lie in [0, 7): got 9"
 
 
 def test_cell_box_of_a_scan_matches_the_array_expression():
