@@ -140,20 +140,25 @@ class GpuBackend:
     History = ScanHistory
 
     @staticmethod
-    def match_history_first_accepted(hist, source_id, cand_ids, feat_cfg, icp_cfg, error_accept):
+    def match_history_first_accepted(hist, source_id, cand_ids, feat_cfg, icp_cfg, error_accept, alignment_method="rotation_search"):
         """The same against scans resident in ``hist`` (a ``History`` with the voxel sizes and normal_k of the two
-        configurations), by id: nothing is uploaded, filtered or put in search order again.  Same records bit for bit."""
+        configurations), by id: nothing is uploaded, filtered or put in search order again.  Same records bit for bit.
+        ``alignment_method`` "features" / "both": the history was built with a ``feat_cfg`` and holds every scan's keypoints
+        and descriptors too."""
         m = hist.match(source_id, cand_ids, error_threshold=icp_cfg["error_threshold"], max_iterations=icp_cfg["max_iterations"],
                        method=icp_cfg["method"], angle_step_coarse=feat_cfg["angle_step_coarse"],
-                       angle_step_fine=feat_cfg["angle_step_fine"], error_accept=error_accept, stop_after_first_accepted=True)
+                       angle_step_fine=feat_cfg["angle_step_fine"], error_accept=error_accept, stop_after_first_accepted=True,
+                       alignment_method=alignment_method)
         m.run()
         R, t, err, info = m.unpack()
         return R, t, err, info["iters"], info["first_accepted"]
 
 
 def run(n_scans=60, log_path=None, verbose=True, imu_path=None, loop=False, use_submap=True, lc_error_threshold=0.05,
-        backend=None, max_candidates=5, reference_candidates=False):
-    """reference_candidates: pick the loop-closure candidates with ``find_loop_candidates`` (slam.py:230-268: a cumulative
+        backend=None, max_candidates=5, reference_candidates=False, alignment_method="rotation_search"):
+    """alignment_method: the pre-alignment of the loop-closure matches (slam.py:60, 68: "rotation_search", "features" or
+    "both"); other than the default, the resident history keeps the per-scan features as well.
+    reference_candidates: pick the loop-closure candidates with ``find_loop_candidates`` (slam.py:230-268: a cumulative
     travel gate, nearest first) instead of this harness' short rule (the first ``max_candidates`` old scans within 3 m)."""
     from icpmi import submap as submap_mod
     uicp.VERBOSE = features.VERBOSE = submap_mod.VERBOSE = upg.VERBOSE = False
@@ -178,8 +183,10 @@ def run(n_scans=60, log_path=None, verbose=True, imu_path=None, loop=False, use_
     closures, rejected, accepted = [], [], []
     feat_kw = dict(rotation_voxel_size=0.15, angle_step_coarse=1.5, angle_step_fine=0.1)
     # the past scans, prepared once on the device (a backend without a History matches the arrays, batch by batch)
+    match_kw = {} if alignment_method == "rotation_search" else dict(alignment_method=alignment_method)
+    hist_kw = {} if alignment_method == "rotation_search" else dict(feat_cfg={})        # (the reference's feature defaults)
     resident = be.History(voxel_size=icp_kw["voxel_size"], normal_k=icp_kw["normal_k"],
-                          rotation_voxel_size=feat_kw["rotation_voxel_size"]) if hasattr(be, "History") else None
+                          rotation_voxel_size=feat_kw["rotation_voxel_size"], **hist_kw) if hasattr(be, "History") else None
     graph = be.Graph()
     prev = None
     for i, cur in enumerate(scans):
@@ -238,7 +245,7 @@ def run(n_scans=60, log_path=None, verbose=True, imu_path=None, loop=False, use_
             if cands:
                 if resident is not None:                             # the current scan is the last one added
                     R, t, err, its, first = be.match_history_first_accepted(resident, len(history) - 1, cands, feat_kw, icp_kw,
-                                                                            lc_error_threshold)
+                                                                            lc_error_threshold, **match_kw)
                 elif hasattr(be, "run_icp_pairs_first_accepted"):      # the candidates after the accepted one may stop early
                     R, t, err, its, first = be.run_icp_pairs_first_accepted(cur, [history[k][0] for k in cands], feat_kw,
                                                                             icp_kw, lc_error_threshold)

@@ -510,6 +510,62 @@ int icpmi_feature_align_batch(const double* pts, const int32_t* off_dev, const i
                               const double* init_in, double* init_out, double* out_records,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- resident features: the feature start of _run_icp_pair (slam.py:68-88) against past scans ------------------------
+ * Filtering a cloud at the feature voxel size, compute_curvature, extract_keypoints and compute_descriptors are functions
+ * of ONE cloud, and a past scan never changes: a history keeps their results in a feature store and a query runs
+ * matching, RANSAC and the record only.  The store is the caller's memory, named by this struct (host), laid out over the
+ * history's own cloud set — the same off_dev and ids, the history's scan_capacity and row_capacity, addressed by those
+ * capacities and never by the rows or scans in use:
+ *   per row of row_capacity    vox (16 B) and the curvature scratch curv (8 B): 24 B a raw row;
+ *   per scan of scan_capacity  cnt, kp_cnt, desc_len (4 B each), kp [kp_stride] (4 B each) and
+ *                              desc [kp_stride][ICPMI_FT_DESC_STRIDE] (256 B a keypoint slot): 12 + 260 * kp_stride bytes,
+ *                              27 052 B a scan at the reference's top_n of 100 (kp_stride 104).
+ * The cloud-side configuration the tables were computed with is part of the store; kp_stride is top_n rounded up to 8 (at
+ * least 8), the stride of icpmi_feature_align_batch's own tables. */
+typedef struct icpmi_feature_store {
+    double* vox;              /* filtered at voxel_size (features.py:262-263), cloud set layout */
+    double* curv;             /* [row_capacity] curvature of every filtered row (scratch)       */
+    int32_t* cnt;             /* [scan_capacity] filtered rows                                  */
+    int32_t* kp;              /* [scan_capacity][kp_stride]                                     */
+    int32_t* kp_cnt;          /* [scan_capacity]                                                */
+    double* desc;             /* [scan_capacity][kp_stride][ICPMI_FT_DESC_STRIDE]               */
+    int32_t* desc_len;        /* [scan_capacity]                                                */
+    double voxel_size;
+    double min_kp_dist;
+    int32_t k_curvature;
+    int32_t top_n;
+    int32_t k_descriptor;
+    int32_t kp_stride;
+} icpmi_feature_store;
+
+/* Processes the clouds [first, first + n_new) of the history into the store and leaves every other cloud's state as it is:
+ * voxel filter at the store's voxel size (on the tail of the offsets, as icpmi_history_add), curvature, keypoints by the
+ * device order rule, descriptors — the launches of icpmi_feature_align_batch's first half, for this range.  Uses pts,
+ * off_dev, ids, the voxel workspace and the capacities of h; off_host mirrors off_dev.  Refused on the host, before any
+ * launch: a null pointer or a range beyond a capacity (ICPMI_ERR_ARG); k > 31, top_n > ICPMI_FT_MAX_KP or top_n > kp_stride
+ * (ICPMI_ERR_UNSUPPORTED).  A scan whose filtered cloud exceeds ICPMI_FT_MAX_ROWS is left without features (0 keypoints):
+ * its pairs report ICPMI_FT_ST_CAPACITY. */
+int icpmi_history_features_add(const icpmi_history* h, const icpmi_feature_store* store, const int32_t* off_host, int32_t first,
+                               int32_t n_new, void* stream);
+
+/* The pair half of icpmi_feature_align_batch on the resident state: same arguments from pair_src on, same records,
+ * init_out and statuses.  Sources and targets are clouds of the history (a staged source included).  max_n: rows of the
+ * largest RAW source any pair names.
+ * init_in == NULL ("features"): matching, RANSAC and the record straight on the store's tables; the workspace holds the
+ * matches and their counts only, and off_host / pair_src_host are not read.
+ * init_in != NULL ("both"): a work set of one transformed copy of its source per pair (h->pts rows @ R_init.T + t_init,
+ * the gemm form fma(y, R[c][1], x * R[c][0]) + t[c] for every row count) is filtered and given curvature, keypoints and
+ * descriptors in the workspace; the pair stages then take sources from it and targets from the store.  off_host (the
+ * history's offsets) and pair_src_host are then required; a source beyond the capacities or above max_n rows:
+ * ICPMI_ERR_ARG.  n_pairs == 0: no launch, ICPMI_OK. */
+size_t icpmi_history_feature_align_workspace_bytes(int32_t n_pairs, int32_t max_n, int32_t top_n, int32_t with_init);
+int icpmi_history_feature_align(const icpmi_history* h, const icpmi_feature_store* store, const int32_t* off_host,
+                                const int32_t* pair_src, const int32_t* pair_src_host, const int32_t* pair_tgt,
+                                int32_t n_pairs, int32_t max_n, double ratio_sq, const int32_t* hyp_idx, const double* hyp_u,
+                                int32_t n_iter, int32_t hyp_pair_stride, double inlier_thresh, int32_t min_inliers,
+                                const double* init_in, double* init_out, double* out_records, void* workspace,
+                                size_t workspace_bytes, void* stream);
+
 /* ---- OccupancyGrid2D, utilities/mapping.py ---------------------------------
  * world -> cell index, mapping.py:57-60,94-98: floor((w - min) / res), float64
  * IEEE division, result as int64. */

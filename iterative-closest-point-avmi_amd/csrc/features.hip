@@ -5,7 +5,9 @@
 // pair with the cloud staged in LDS and an exhaustive float64 neighbour scan (the lists of prep_common.hpp, ordered by
 // (distance, row) as icpmi_normals_2d_batch orders them).  The stages are separate kernels: the single-stage entry
 // points and the chain (icpmi_feature_align_batch) launch the SAME kernels, so the chain is the composition of the
-// stages by construction.
+// stages by construction.  The three pair stages (matching, RANSAC, the record) read a source side and a target side
+// (FtSide): the batch passes one set of tables twice, the resident chain of a scan history (icpmi_history_feature_align,
+// at the end of this file) takes its targets — and without a start per pair its sources — from the history's feature store.
 //
 // What is pinned to the reference's numbers, stage by stage ("feature alignment"):
 //   curvature     to the reference's own sensitivity to summation order: np.cov sums the neighbours in per-point distance
@@ -209,30 +211,44 @@ __global__ __launch_bounds__(FT_THREADS) void ft_descriptors_kernel(const double
     if (threadIdx.x == 0) out_desc_len[f.c] = kk - 1;
 }
 
+// ── one side of a pair ───────────────────────────────────────────────────────────────────────────────
+// The pair stages read a source cloud and a target cloud.  Each comes from a set of per-cloud tables — filtered points,
+// offsets, counts, keypoints, descriptors — described once here.  A batch whose clouds are all of one set passes that set
+// as both sides; a resident history with a start per pair takes its sources from a work set and its targets from the
+// store.  Both sides share kp_stride.
+struct FtSide {
+    const double* __restrict__ pts;
+    const int32_t* __restrict__ off;
+    const int32_t* __restrict__ cnt;          // nullptr: every cloud is full (off[c + 1] - off[c] rows)
+    const int32_t* __restrict__ kp;
+    const int32_t* __restrict__ kp_cnt;
+    const double* __restrict__ desc;
+    const int32_t* __restrict__ desc_len;
+};
+
 // ── 4. match_descriptors, features.py:92-106 ────────────────────────────────────────────────────────
 // A thread per source keypoint: squared descriptor distance to every target keypoint by direct differences, the two
 // smallest (the lower index on ties), Lowe's test D0 < ratio^2 * D1.  The matches leave in source-keypoint order.
-__global__ __launch_bounds__(FT_MAX_KP) void ft_match_kernel(const double* __restrict__ desc, const int32_t* __restrict__ desc_len,
-                                                            const int32_t* __restrict__ kp_cnt, int kp_stride,
+__global__ __launch_bounds__(FT_MAX_KP) void ft_match_kernel(const FtSide src, const FtSide tgt, int kp_stride,
                                                             const int32_t* __restrict__ pair_src, const int32_t* __restrict__ pair_tgt,
                                                             double ratio_sq, int32_t* __restrict__ out_matches,
                                                             int32_t* __restrict__ out_match_cnt) {
     __shared__ int wave_tot[FT_MAX_KP / ICPMI_WAVE];
     const int b = blockIdx.x, i = threadIdx.x;
     const int sc = pair_src[b], tc = pair_tgt[b];
-    const int ns = min(min(kp_cnt[sc], kp_stride), FT_MAX_KP), nt = min(min(kp_cnt[tc], kp_stride), FT_MAX_KP);
-    const int len = desc_len[sc];
+    const int ns = min(min(src.kp_cnt[sc], kp_stride), FT_MAX_KP), nt = min(min(tgt.kp_cnt[tc], kp_stride), FT_MAX_KP);
+    const int len = src.desc_len[sc];
     // features.py:97; descriptors of different lengths cannot be compared (NumPy raises; the chain reports status 5)
-    const bool any = ns > 0 && nt >= 2 && len == desc_len[tc] && len > 0 && len <= FT_MAX_K;
+    const bool any = ns > 0 && nt >= 2 && len == tgt.desc_len[tc] && len > 0 && len <= FT_MAX_K;
     bool ok = false;
     int j0 = 0;
     if (any && i < ns) {
-        const double* a_row = desc + ((size_t)sc * kp_stride + i) * FT_DESC_STRIDE;
+        const double* a_row = src.desc + ((size_t)sc * kp_stride + i) * FT_DESC_STRIDE;
         double a[FT_MAX_K];
 #pragma unroll
         for (int q = 0; q < FT_MAX_K; ++q) a[q] = q < len ? a_row[q] : 0.0;
         double best0 = __builtin_inf(), best1 = __builtin_inf();
-        const double* t_rows = desc + (size_t)tc * kp_stride * FT_DESC_STRIDE;
+        const double* t_rows = tgt.desc + (size_t)tc * kp_stride * FT_DESC_STRIDE;
         for (int j = 0; j < nt; ++j) {
             const double* b_row = t_rows + (size_t)j * FT_DESC_STRIDE;
             double D = 0.0;
@@ -294,9 +310,7 @@ __device__ __forceinline__ bool ft_hypothesis(const int32_t* __restrict__ hyp_id
     return i >= 0 && j >= 0 && i < n && j < n && i != j;            // anything else counts no inliers
 }
 
-__global__ __launch_bounds__(FT_THREADS) void ft_ransac_kernel(const double* __restrict__ pts, const int32_t* __restrict__ off,
-                                                               const int32_t* __restrict__ cnt, const int32_t* __restrict__ kp,
-                                                               const int32_t* __restrict__ kp_cnt, int kp_stride,
+__global__ __launch_bounds__(FT_THREADS) void ft_ransac_kernel(const FtSide src, const FtSide tgt, int kp_stride,
                                                                const int32_t* __restrict__ pair_src, const int32_t* __restrict__ pair_tgt,
                                                                const int32_t* __restrict__ matches, const int32_t* __restrict__ match_cnt,
                                                                const int32_t* __restrict__ hyp_idx, const double* __restrict__ hyp_u,
@@ -312,16 +326,17 @@ __global__ __launch_bounds__(FT_THREADS) void ft_ransac_kernel(const double* __r
     if (tid == 0) bad = 0;
     __syncthreads();
     {   // the matched keypoints' coordinates, features.py:133-134
-        const int ns_kp = min(kp_cnt[sc], kp_stride), nt_kp = min(kp_cnt[tc], kp_stride);
-        const int rows_s = min(cnt ? cnt[sc] : off[sc + 1] - off[sc], off[sc + 1] - off[sc]);
-        const int rows_t = min(cnt ? cnt[tc] : off[tc + 1] - off[tc], off[tc + 1] - off[tc]);
-        const double2* Ps = reinterpret_cast<const double2*>(pts) + off[sc];
-        const double2* Pt = reinterpret_cast<const double2*>(pts) + off[tc];
+        const int ns_kp = min(src.kp_cnt[sc], kp_stride), nt_kp = min(tgt.kp_cnt[tc], kp_stride);
+        const int cap_s = src.off[sc + 1] - src.off[sc], cap_t = tgt.off[tc + 1] - tgt.off[tc];
+        const int rows_s = min(src.cnt ? src.cnt[sc] : cap_s, cap_s);
+        const int rows_t = min(tgt.cnt ? tgt.cnt[tc] : cap_t, cap_t);
+        const double2* Ps = reinterpret_cast<const double2*>(src.pts) + src.off[sc];
+        const double2* Pt = reinterpret_cast<const double2*>(tgt.pts) + tgt.off[tc];
         for (int m = tid; m < n; m += FT_THREADS) {
             const int ms = matches[((size_t)b * kp_stride + m) * 2], mt = matches[((size_t)b * kp_stride + m) * 2 + 1];
             int rs = -1, rt = -1;
-            if (ms >= 0 && ms < ns_kp) rs = kp[(size_t)sc * kp_stride + ms];
-            if (mt >= 0 && mt < nt_kp) rt = kp[(size_t)tc * kp_stride + mt];
+            if (ms >= 0 && ms < ns_kp) rs = src.kp[(size_t)sc * kp_stride + ms];
+            if (mt >= 0 && mt < nt_kp) rt = tgt.kp[(size_t)tc * kp_stride + mt];
             if (rs < 0 || rs >= rows_s || rt < 0 || rt >= rows_t) { atomicOr(&bad, 1); continue; }
             S[m] = Ps[rs]; D[m] = Pt[rt];
         }
@@ -421,16 +436,19 @@ __global__ void ft_work_offsets_kernel(const int32_t* __restrict__ off, int n_cl
     }
 }
 
-// copy b of the work set = rows of cloud pair_src[b] @ R_init.T + t_init.  NumPy's (n, 2) @ (2, 2) is a BLAS gemm whose
-// element is fma(y, R[c][1], x * R[c][0]) (rotsearch.hip, the refinement, has the same product)
-__global__ __launch_bounds__(FT_THREADS) void ft_transform_kernel(double* __restrict__ work_pts, const int32_t* __restrict__ work_off,
-                                                                  int n_clouds, const int32_t* __restrict__ pair_src,
+// copy b of the work set (its cloud first_copy + b) = rows of cloud pair_src[b] of the raw set @ R_init.T + t_init.  NumPy's
+// (n, 2) @ (2, 2) is a BLAS gemm whose element is fma(y, R[c][1], x * R[c][0]) (rotsearch.hip, the refinement, has the
+// same product) — for every row count: the source is transformed as the (n, 2) array it is
+__global__ __launch_bounds__(FT_THREADS) void ft_transform_kernel(const double* __restrict__ raw_pts, const int32_t* __restrict__ raw_off,
+                                                                  double* __restrict__ work_pts, const int32_t* __restrict__ work_off,
+                                                                  int first_copy, const int32_t* __restrict__ pair_src,
                                                                   const double* __restrict__ init) {
     const int b = blockIdx.x;
     const int sc = pair_src[b];
-    const int rows = work_off[sc + 1] - work_off[sc];
-    const double2* src = reinterpret_cast<const double2*>(work_pts) + work_off[sc];
-    double2* dst = reinterpret_cast<double2*>(work_pts) + work_off[n_clouds + b];
+    const int room = work_off[first_copy + b + 1] - work_off[first_copy + b];
+    const int rows = min(raw_off[sc + 1] - raw_off[sc], room);      // equal for a well-formed call
+    const double2* src = reinterpret_cast<const double2*>(raw_pts) + raw_off[sc];
+    double2* dst = reinterpret_cast<double2*>(work_pts) + work_off[first_copy + b];
     const double* r = init + (size_t)b * 6;
     for (int i = threadIdx.x; i < rows; i += FT_THREADS) {
         const double2 p = src[i];
@@ -440,23 +458,22 @@ __global__ __launch_bounds__(FT_THREADS) void ft_transform_kernel(double* __rest
 
 // the record of a pair, with the early returns of features.py:281-300 in the reference's order, and the start of the ICP
 // that follows (slam.py:83-88)
-__global__ void ft_finish_kernel(const int32_t* __restrict__ work_off, const int32_t* __restrict__ cnt, const int32_t* __restrict__ kp_cnt,
-                                 const int32_t* __restrict__ desc_len, const int32_t* __restrict__ work_src,
+__global__ void ft_finish_kernel(const FtSide src, const FtSide tgt, const int32_t* __restrict__ work_src,
                                  const int32_t* __restrict__ pair_tgt, int n_pairs, int min_inliers, const double* __restrict__ init_in,
                                  double* __restrict__ init_out, double* __restrict__ records) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= n_pairs) return;
     const int sc = work_src[b], tc = pair_tgt[b];
     double* rec = records + (size_t)b * ICPMI_FTREC_DOUBLES;
-    const int ns = cnt[sc], nt = cnt[tc];
+    const int ns = src.cnt[sc], nt = tgt.cnt[tc];
     int status = (int)rec[ICPMI_FTREC_STATUS];                            // the RANSAC kernel's: ok, or fewer than 2 matches
     if (ns > FT_MAX_ROWS || nt > FT_MAX_ROWS || ns < 0 || nt < 0) status = ICPMI_FT_ST_CAPACITY;
     else if (ns < 10 || nt < 10) status = ICPMI_FT_ST_FEW_ROWS;           // features.py:281-282
-    else if (kp_cnt[sc] < 2 || kp_cnt[tc] < 2) status = ICPMI_FT_ST_FEW_KP;   // features.py:290-291
-    else if (desc_len[sc] != desc_len[tc]) status = ICPMI_FT_ST_DESC_LEN;
+    else if (src.kp_cnt[sc] < 2 || tgt.kp_cnt[tc] < 2) status = ICPMI_FT_ST_FEW_KP;   // features.py:290-291
+    else if (src.desc_len[sc] != tgt.desc_len[tc]) status = ICPMI_FT_ST_DESC_LEN;
     rec[ICPMI_FTREC_NS] = (double)ns; rec[ICPMI_FTREC_NT] = (double)nt;
     const bool looked = status != ICPMI_FT_ST_CAPACITY && status != ICPMI_FT_ST_FEW_ROWS;      // else the reference never extracts keypoints
-    rec[ICPMI_FTREC_KPS] = looked ? (double)kp_cnt[sc] : 0.0; rec[ICPMI_FTREC_KPT] = looked ? (double)kp_cnt[tc] : 0.0;
+    rec[ICPMI_FTREC_KPS] = looked ? (double)src.kp_cnt[sc] : 0.0; rec[ICPMI_FTREC_KPT] = looked ? (double)tgt.kp_cnt[tc] : 0.0;
     if (status != ICPMI_FT_ST_OK) {                                       // identity, zeros, 0 inliers
         if (status != ICPMI_FT_ST_FEW_MATCHES) rec[ICPMI_FTREC_MATCHES] = 0.0;
         rec[ICPMI_FTREC_INLIERS] = 0.0; rec[ICPMI_FTREC_R] = 1.0; rec[ICPMI_FTREC_R + 1] = 0.0; rec[ICPMI_FTREC_R + 2] = 0.0; rec[ICPMI_FTREC_R + 3] = 1.0;
@@ -529,6 +546,81 @@ static FtPlan plan_features(int n_clouds, int n_pairs, int top_n, bool with_init
 
 static bool ft_stage_args_ok(const void* pts, const void* off, int n_sel) { return pts && off && n_sel >= 0; }
 
+// the pair stages over two sides (the callers have checked their arguments; n_pairs > 0)
+static int ft_launch_match(const FtSide& src, const FtSide& tgt, int kp_stride, const int32_t* pair_src, const int32_t* pair_tgt, int n_pairs,
+                           double ratio_sq, int32_t* out_matches, int32_t* out_match_cnt, hipStream_t st) {
+    ft_match_kernel<<<n_pairs, FT_MAX_KP, 0, st>>>(src, tgt, kp_stride, pair_src, pair_tgt, ratio_sq, out_matches, out_match_cnt);
+    ICPMI_LAUNCH_CHECK();
+    return ICPMI_OK;
+}
+static int ft_launch_ransac(const FtSide& src, const FtSide& tgt, int kp_stride, const int32_t* pair_src, const int32_t* pair_tgt, int n_pairs,
+                            const int32_t* matches, const int32_t* match_cnt, const int32_t* hyp_idx, const double* hyp_u, int n_iter,
+                            int hyp_pair_stride, double inlier_thresh, double* out_records, int32_t* out_counts, hipStream_t st) {
+    ft_ransac_kernel<<<n_pairs, FT_THREADS, 0, st>>>(src, tgt, kp_stride, pair_src, pair_tgt, matches, match_cnt, hyp_idx, hyp_u, n_iter,
+                                                     hyp_pair_stride, inlier_thresh, out_records, out_counts);
+    ICPMI_LAUNCH_CHECK();
+    return ICPMI_OK;
+}
+
+// matching, RANSAC and the record of every pair: the second half of both chains
+struct FtPairArgs {
+    const int32_t* pair_src;      // the source of pair b in the source side's tables
+    const int32_t* pair_tgt;
+    int n_pairs;
+    double ratio_sq;
+    const int32_t* hyp_idx;
+    const double* hyp_u;
+    int n_iter, hyp_pair_stride;
+    double inlier_thresh;
+    int min_inliers;
+    const double* init_in;
+    double* init_out;
+    double* out_records;
+};
+static int ft_pair_stages(const FtPlan& plan, const FtSide& src, const FtSide& tgt, const FtPairArgs& a, int32_t* matches, int32_t* match_cnt,
+                          hipStream_t st) {
+    int rc = ft_launch_match(src, tgt, plan.kp_stride, a.pair_src, a.pair_tgt, a.n_pairs, a.ratio_sq, matches, match_cnt, st);
+    if (rc != ICPMI_OK) return rc;
+    rc = ft_launch_ransac(src, tgt, plan.kp_stride, a.pair_src, a.pair_tgt, a.n_pairs, matches, match_cnt, a.hyp_idx, a.hyp_u, a.n_iter,
+                          a.hyp_pair_stride, a.inlier_thresh, a.out_records, nullptr, st);
+    if (rc != ICPMI_OK) return rc;
+    ft_finish_kernel<<<plan.finish_grid, FT_THREADS, 0, st>>>(src, tgt, a.pair_src, a.pair_tgt, a.n_pairs, a.min_inliers, a.init_in, a.init_out,
+                                                             a.out_records);
+    ICPMI_LAUNCH_CHECK();
+    return ICPMI_OK;
+}
+
+// ── the resident chain's workspace (icpmi_history_feature_align), described once ──
+// matches | their counts — and, with a start per pair, the work set: one transformed copy of its source per pair (capacity
+// max_n rows each), their filtered copies, offsets, counts, the identity pair list into the set, curvature, keypoints,
+// descriptors, voxel scratch.  Without a start the sources are clouds of the store and only the first two exist.
+struct FtHistWs {
+    Carve c;
+    int32_t n_pairs, max_n, kp_stride, with_init;
+    size_t work_clouds = with_init ? (size_t)n_pairs : 0;
+    size_t work_rows = work_clouds * (size_t)max_n;
+    int32_t* matches = c.take<int32_t>((size_t)n_pairs * kp_stride * 8);
+    int32_t* match_cnt = c.take<int32_t>((size_t)n_pairs * 4);
+    double* work_pts = c.take<double>(work_rows * 16);
+    double* vox = c.take<double>(work_rows * 16);
+    int32_t* work_off = c.take<int32_t>(with_init ? (work_clouds + 1) * 4 : 0);
+    int32_t* cnt = c.take<int32_t>(work_clouds * 4);
+    int32_t* work_src = c.take<int32_t>(work_clouds * 4);
+    double* curv = c.take<double>(work_rows * 8);
+    int32_t* kp = c.take<int32_t>(work_clouds * kp_stride * 4);
+    int32_t* kp_cnt = c.take<int32_t>(work_clouds * 4);
+    double* desc = c.take<double>(work_clouds * kp_stride * FT_DESC_STRIDE * 8);
+    int32_t* desc_len = c.take<int32_t>(work_clouds * 4);
+    size_t vws_bytes = with_init ? icpmi_voxel_workspace_bytes(max_n) : 0;
+    void* vws = c.take<void>(vws_bytes);
+    size_t bytes = c.off + 256;
+};
+
+static bool ft_store_complete(const icpmi_feature_store* s) {
+    return s && s->vox && s->curv && s->cnt && s->kp && s->kp_cnt && s->desc && s->desc_len && s->voxel_size > 0.0 && s->kp_stride > 0 &&
+           s->k_curvature >= 0 && s->k_descriptor >= 0;
+}
+
 }  // namespace icpmi
 
 extern "C" int icpmi_feature_curvature_batch(const double* pts, const int32_t* off_dev, const int32_t* cnt_dev,
@@ -577,10 +669,8 @@ extern "C" int icpmi_feature_match_batch(const double* desc, const int32_t* desc
     if (!desc || !desc_len || !kp_cnt || !pair_src || !pair_tgt || !out_matches || !out_match_cnt || kp_stride <= 0 || n_pairs < 0)
         return ICPMI_ERR_ARG;
     if (n_pairs == 0) return ICPMI_OK;
-    ft_match_kernel<<<n_pairs, FT_MAX_KP, 0, (hipStream_t)stream>>>(desc, desc_len, kp_cnt, kp_stride, pair_src, pair_tgt, ratio_sq, out_matches,
-                                                                    out_match_cnt);
-    ICPMI_LAUNCH_CHECK();
-    return ICPMI_OK;
+    const FtSide side{nullptr, nullptr, nullptr, nullptr, kp_cnt, desc, desc_len};
+    return ft_launch_match(side, side, kp_stride, pair_src, pair_tgt, n_pairs, ratio_sq, out_matches, out_match_cnt, (hipStream_t)stream);
 }
 
 extern "C" int icpmi_feature_ransac_batch(const double* pts, const int32_t* off_dev, const int32_t* cnt_dev, const int32_t* kp,
@@ -592,11 +682,9 @@ extern "C" int icpmi_feature_ransac_batch(const double* pts, const int32_t* off_
     if (!pts || !off_dev || !kp || !kp_cnt || !pair_src || !pair_tgt || !matches || !match_cnt || !out_records) return ICPMI_ERR_ARG;
     if (kp_stride <= 0 || n_pairs < 0 || n_iter < 0 || hyp_pair_stride < 0 || (n_iter > 0 && !hyp_idx == !hyp_u)) return ICPMI_ERR_ARG;
     if (n_pairs == 0) return ICPMI_OK;
-    ft_ransac_kernel<<<n_pairs, FT_THREADS, 0, (hipStream_t)stream>>>(pts, off_dev, cnt_dev, kp, kp_cnt, kp_stride, pair_src, pair_tgt, matches,
-                                                                      match_cnt, hyp_idx, hyp_u, n_iter, hyp_pair_stride, inlier_thresh,
-                                                                      out_records, out_counts);
-    ICPMI_LAUNCH_CHECK();
-    return ICPMI_OK;
+    const FtSide side{pts, off_dev, cnt_dev, kp, kp_cnt, nullptr, nullptr};
+    return ft_launch_ransac(side, side, kp_stride, pair_src, pair_tgt, n_pairs, matches, match_cnt, hyp_idx, hyp_u, n_iter, hyp_pair_stride,
+                            inlier_thresh, out_records, out_counts, (hipStream_t)stream);
 }
 
 extern "C" size_t icpmi_feature_align_batch_workspace_bytes(int32_t total_rows, int32_t n_clouds, int32_t max_n, int32_t n_pairs,
@@ -642,7 +730,7 @@ extern "C" int icpmi_feature_align_batch(const double* pts, const int32_t* off_d
         work_off_host_p = work_off_host.data();
         if (hipMemcpyAsync(w.work_pts, pts, (size_t)total_rows * 16, hipMemcpyDeviceToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
         ft_work_offsets_kernel<<<1, 1024, 0, st>>>(off_dev, n_clouds, pair_src, n_pairs, w.work_off, w.work_src);
-        ft_transform_kernel<<<plan.pair_grid, FT_THREADS, 0, st>>>(w.work_pts, w.work_off, n_clouds, pair_src, init_in);
+        ft_transform_kernel<<<plan.pair_grid, FT_THREADS, 0, st>>>(pts, off_dev, w.work_pts, w.work_off, n_clouds, pair_src, init_in);
         ICPMI_LAUNCH_CHECK();
         work_pts = w.work_pts; work_off = w.work_off; work_src = w.work_src;
     }
@@ -657,14 +745,67 @@ extern "C" int icpmi_feature_align_batch(const double* pts, const int32_t* off_d
     rc = icpmi_feature_descriptors_batch(w.vox, work_off, w.cnt, nullptr, plan.work_clouds, w.kp, w.kp_cnt, plan.kp_stride, k_descriptor, w.desc,
                                          w.desc_len, stream);
     if (rc != ICPMI_OK) return rc;
-    rc = icpmi_feature_match_batch(w.desc, w.desc_len, w.kp_cnt, plan.kp_stride, work_src, pair_tgt, n_pairs, ratio_sq, w.matches, w.match_cnt,
-                                   stream);
-    if (rc != ICPMI_OK) return rc;
-    rc = icpmi_feature_ransac_batch(w.vox, work_off, w.cnt, w.kp, w.kp_cnt, plan.kp_stride, work_src, pair_tgt, n_pairs, w.matches, w.match_cnt,
-                                    hyp_idx, hyp_u, n_iter, hyp_pair_stride, inlier_thresh, out_records, nullptr, stream);
-    if (rc != ICPMI_OK) return rc;
-    ft_finish_kernel<<<plan.finish_grid, FT_THREADS, 0, st>>>(work_off, w.cnt, w.kp_cnt, w.desc_len, work_src, pair_tgt, n_pairs, min_inliers,
-                                                             init_in, init_out, out_records);
+    const FtSide side{w.vox, work_off, w.cnt, w.kp, w.kp_cnt, w.desc, w.desc_len};      // sources and targets: clouds of the one work set
+    const FtPairArgs a{work_src, pair_tgt, n_pairs, ratio_sq, hyp_idx, hyp_u, n_iter, hyp_pair_stride, inlier_thresh, min_inliers,
+                       init_in, init_out, out_records};
+    return ft_pair_stages(plan, side, side, a, w.matches, w.match_cnt, st);
+}
+
+// ── the resident chain: the pair half of icpmi_feature_align_batch on a history's feature store ──────────────────────
+extern "C" size_t icpmi_history_feature_align_workspace_bytes(int32_t n_pairs, int32_t max_n, int32_t top_n, int32_t with_init) {
+    if (n_pairs < 0 || max_n < 0) return 0;
+    return icpmi::FtHistWs{nullptr, n_pairs, max_n, icpmi::ft_kp_stride(top_n), with_init ? 1 : 0}.bytes;
+}
+
+extern "C" int icpmi_history_feature_align(const icpmi_history* h, const icpmi_feature_store* s, const int32_t* off_host,
+                                           const int32_t* pair_src, const int32_t* pair_src_host, const int32_t* pair_tgt,
+                                           int32_t n_pairs, int32_t max_n, double ratio_sq, const int32_t* hyp_idx, const double* hyp_u,
+                                           int32_t n_iter, int32_t hyp_pair_stride, double inlier_thresh, int32_t min_inliers,
+                                           const double* init_in, double* init_out, double* out_records, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    using namespace icpmi;
+    if (!h || !h->pts || !h->off_dev || !h->ids || h->scan_capacity <= 0 || h->row_capacity <= 0 || !ft_store_complete(s)) return ICPMI_ERR_ARG;
+    if (n_pairs < 0 || max_n < 0 || n_iter < 0 || hyp_pair_stride < 0) return ICPMI_ERR_ARG;
+    if (s->k_curvature > FT_MAX_K || s->k_descriptor > FT_MAX_K || s->top_n > FT_MAX_KP || s->top_n > s->kp_stride) return ICPMI_ERR_UNSUPPORTED;
+    if (n_pairs == 0) return ICPMI_OK;
+    if (!pair_src || !pair_tgt || !out_records || !workspace) return ICPMI_ERR_ARG;
+    if (n_iter > 0 && !hyp_idx == !hyp_u) return ICPMI_ERR_ARG;
+    if (init_in && (!pair_src_host || !off_host)) return ICPMI_ERR_ARG;
+    if (s->kp_stride != ft_kp_stride(s->top_n)) return ICPMI_ERR_ARG;              // the work set's tables share the store's stride
+    const FtPlan plan = plan_features(0, n_pairs, s->top_n, init_in != nullptr);
+    const FtHistWs w{workspace, n_pairs, max_n, plan.kp_stride, plan.with_init ? 1 : 0};
+    if (workspace_bytes < w.bytes) return ICPMI_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const FtSide store{s->vox, h->off_dev, s->cnt, s->kp, s->kp_cnt, s->desc, s->desc_len};
+    FtPairArgs a{pair_src, pair_tgt, n_pairs, ratio_sq, hyp_idx, hyp_u, n_iter, hyp_pair_stride, inlier_thresh, min_inliers,
+                 init_in, init_out, out_records};
+    if (!plan.with_init) return ft_pair_stages(plan, store, store, a, w.matches, w.match_cnt, st);
+    // a start per pair: the work set is one transformed copy of its source per pair, laid out by ft_work_offsets_kernel's
+    // rule with no clouds in front (the history's first offset is 0), and goes through the four per-cloud stages here
+    if (off_host[0] != 0) return ICPMI_ERR_ARG;
+    std::vector<int32_t> work_off_host(1, 0);
+    for (int b = 0; b < n_pairs; ++b) {
+        const int sc = pair_src_host[b];
+        if (sc < 0 || sc >= h->scan_capacity) return ICPMI_ERR_ARG;
+        const int rows = off_host[sc + 1] - off_host[sc];
+        if (rows < 0 || rows > max_n || off_host[sc + 1] > h->row_capacity) return ICPMI_ERR_ARG;
+        work_off_host.push_back(work_off_host.back() + rows);
+    }
+    ft_work_offsets_kernel<<<1, 1024, 0, st>>>(h->off_dev, 0, pair_src, n_pairs, w.work_off, w.work_src);
+    ft_transform_kernel<<<plan.pair_grid, FT_THREADS, 0, st>>>(h->pts, h->off_dev, w.work_pts, w.work_off, 0, pair_src, init_in);
     ICPMI_LAUNCH_CHECK();
-    return ICPMI_OK;
+    int rc = icpmi_voxel_downsample_batch(w.work_pts, w.work_off, work_off_host.data(), plan.work_clouds, 2, s->voxel_size, w.vox, w.cnt,
+                                          w.vws, w.vws_bytes, stream);
+    if (rc != ICPMI_OK) return rc;
+    rc = icpmi_feature_curvature_batch(w.vox, w.work_off, w.cnt, nullptr, plan.work_clouds, s->k_curvature, w.curv, stream);
+    if (rc != ICPMI_OK) return rc;
+    rc = icpmi_feature_keypoints_batch(w.vox, w.work_off, w.cnt, nullptr, plan.work_clouds, w.curv, nullptr, s->top_n, s->min_kp_dist, w.kp,
+                                       w.kp_cnt, plan.kp_stride, stream);
+    if (rc != ICPMI_OK) return rc;
+    rc = icpmi_feature_descriptors_batch(w.vox, w.work_off, w.cnt, nullptr, plan.work_clouds, w.kp, w.kp_cnt, plan.kp_stride, s->k_descriptor,
+                                         w.desc, w.desc_len, stream);
+    if (rc != ICPMI_OK) return rc;
+    const FtSide work{w.vox, w.work_off, w.cnt, w.kp, w.kp_cnt, w.desc, w.desc_len};
+    a.pair_src = w.work_src;
+    return ft_pair_stages(plan, work, store, a, w.matches, w.match_cnt, st);
 }

@@ -45,6 +45,13 @@ class History(C.Structure):
                 ("normal_k", C.c_int32), ("allow_polar", C.c_int32)]
 
 
+class FeatureStore(C.Structure):
+    """icpmi_feature_store (include/icpmi.h): a history's per-cloud feature tables and the configuration they were made with."""
+    _fields_ = [("vox", C.c_void_p), ("curv", C.c_void_p), ("cnt", C.c_void_p), ("kp", C.c_void_p), ("kp_cnt", C.c_void_p),
+                ("desc", C.c_void_p), ("desc_len", C.c_void_p), ("voxel_size", C.c_double), ("min_kp_dist", C.c_double),
+                ("k_curvature", C.c_int32), ("top_n", C.c_int32), ("k_descriptor", C.c_int32), ("kp_stride", C.c_int32)]
+
+
 class IcpmiError(RuntimeError):
     pass
 
@@ -106,6 +113,11 @@ _SIGS = {
     "icpmi_history_search": (C.c_int, [C.POINTER(History), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                        C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "icpmi_history_world_rows": (C.c_int, [C.POINTER(History), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "icpmi_history_features_add": (C.c_int, [C.POINTER(History), C.POINTER(FeatureStore), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "icpmi_history_feature_align_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "icpmi_history_feature_align": (C.c_int, [C.POINTER(History), C.POINTER(FeatureStore)] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32,
+                                              C.c_double, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32] +
+                                    [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
     "icpmi_prepared_relayout": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32,
                                           C.c_int32, C.c_void_p]),
     "icpmi_feature_curvature_batch": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -30,7 +30,8 @@ import torch
 from . import _lib
 from ._lib import check
 from .batch import PREP_MAX_POINTS, CloudSet, IcpBatch, PairList, _ptr, _stream, require_gpu
-from .prealign import RotationSearchBatch, RunIcpPairBatch, _gate_given
+from .prealign import (ALIGNMENT_METHODS, FEAT_CLOUD_KEYS, FEAT_DEFAULTS, FeatureAlignBatch, RotationSearchBatch, RunIcpPairBatch,
+                       _gate_given)
 
 
 def find_loop_candidates(current_pose, poses, current_idx, distance_threshold, min_interval, max_candidates,
@@ -140,6 +141,30 @@ class _ResidentSearch(RotationSearchBatch):
         return self.records
 
 
+class _ResidentFeatures(FeatureAlignBatch):
+    """``FeatureAlignBatch`` over a history's feature store: ``run()`` is ``icpmi_history_feature_align`` — matching, RANSAC
+    and the record on the tables the scans got when they were added (with a start per pair, after the per-cloud stages of
+    the transformed sources, which are per pair by nature)."""
+
+    def __init__(self, hist, pair_src, pair_tgt, cfg, hypotheses, rng, init_in, init_out):
+        self.history = hist
+        self._init_common(hist.raw, pair_src, pair_tgt, cfg, hypotheses, rng, init_in, init_out)
+        self.max_n = int(hist.sizes()[self.pair_src_host].max()) if self.B else 0
+        need = _lib.lib().icpmi_history_feature_align_workspace_bytes(self.B, self.max_n, int(self.cfg["top_n"]),
+                                                                      1 if init_in is not None else 0)
+        self.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=hist.device)
+
+    def run(self):
+        c, h = self.cfg, self.history
+        check(_lib.lib().icpmi_history_feature_align(
+            C.byref(h.state), C.byref(h.store), h.raw.off_host.ctypes.data_as(C.c_void_p), _ptr(self.pair_src),
+            self.pair_src_host.ctypes.data_as(C.c_void_p), _ptr(self.pair_tgt), self.B, self.max_n, float(c["ratio_threshold"] ** 2),
+            _ptr(self.hyp_idx), _ptr(self.hyp_u), self.n_iter, 0, float(c["inlier_threshold"]), int(c["min_inliers"]),
+            _ptr(self.init_in), _ptr(self.init_out), _ptr(self.records), _ptr(self.ws), self.ws.numel(), _stream()),
+            "feature_based_alignment (history)")
+        return self.records
+
+
 class HistoryMatch(RunIcpPairBatch):
     """What ``ScanHistory.match`` returns: ``RunIcpPairBatch`` (its ``run`` / ``unpack`` / ``first_accepted``) with the
     history's resident clouds behind it.  Valid while the history keeps its buffers: ``run()`` raises once the history has
@@ -147,7 +172,7 @@ class HistoryMatch(RunIcpPairBatch):
 
     def __init__(self, hist, source_id, candidates, staged, error_threshold, max_iterations, method, max_corr_dist,
                  angle_step_coarse, angle_step_fine, max_rows_hint, error_accept, stop_after_first_accepted, index_base,
-                 index_stride):
+                 index_stride, alignment_method="rotation_search", feat_cfg=None, hypotheses=None, rng=None):
         _gate_given(stop_after_first_accepted, error_accept)
         B = len(candidates)
         pairs = PairList(np.full(B, source_id, dtype=np.int32), candidates)
@@ -156,9 +181,16 @@ class HistoryMatch(RunIcpPairBatch):
         self.stage_generation = hist.stage_generation if staged else None
         icp = _ResidentIcp(hist, pairs, None, error_threshold, max_iterations, method, max_corr_dist,
                            np.tile(np.eye(2), (B, 1, 1)), np.zeros((B, 2)))
-        search = _ResidentSearch(hist, pairs, None, angle_step_coarse, angle_step_fine, icp.init, max_rows_hint)
-        self._init_parts("rotation_search", icp, search, None, error_accept, stop_after_first_accepted, index_base,
-                         index_stride, max_rows_hint, search.max_n)
+        search = features = None
+        if alignment_method in ("rotation_search", "both"):                         # slam.py:60
+            search = _ResidentSearch(hist, pairs, None, angle_step_coarse, angle_step_fine, icp.init, max_rows_hint)
+        if alignment_method in ("features", "both"):                                # slam.py:68-88, as RunIcpPairBatch wires it
+            features = _ResidentFeatures(hist, pairs, None, feat_cfg, hypotheses, rng,
+                                         init_in=icp.init if search is not None else None, init_out=icp.init)
+        sizes = hist.sizes()
+        max_raw_n = int(max(sizes[pairs.src_host].max(), sizes[pairs.tgt_host].max())) if B else 0
+        self._init_parts(alignment_method, icp, search, features, error_accept, stop_after_first_accepted, index_base,
+                         index_stride, max_rows_hint, max_raw_n)
 
     def run(self, events=None):
         h = self.history
@@ -176,12 +208,28 @@ class ScanHistory:
     target alone, computed once by ``add``.
 
     The buffers hold ``scan_capacity`` scans and ``row_capacity`` raw rows (128 bytes of device memory per row); either
-    doubles when it is exceeded (new buffers, device-to-device copies), and results do not depend on that."""
+    doubles when it is exceeded (new buffers, device-to-device copies), and results do not depend on that.
 
-    def __init__(self, voxel_size=0.06, normal_k=10, rotation_voxel_size=0.3, scan_capacity=256, row_capacity=None, device=None):
+    ``feat_cfg`` (a dict, possibly empty): the history also keeps what ``feature_based_alignment`` (features.py:247-315)
+    derives from a cloud alone — the filter at the feature voxel size, curvature, keypoints, descriptors — so that
+    ``match(alignment_method="features" / "both")`` is resident too.  Its cloud-side keys (``FEAT_CLOUD_KEYS``) over
+    ``FEAT_DEFAULTS`` fix that store: 24 more bytes per row and 12 + 260 * kp_stride bytes per scan (27 052 at the
+    reference's ``top_n`` of 100).  ``None``: no store, and ``match`` refuses those two methods."""
+
+    def __init__(self, voxel_size=0.06, normal_k=10, rotation_voxel_size=0.3, scan_capacity=256, row_capacity=None, device=None,
+                 feat_cfg=None):
         require_gpu()
         if not voxel_size > 0 or not rotation_voxel_size > 0:
             raise ValueError("voxel sizes must be positive")
+        self.feat_cfg = self.store = None
+        if feat_cfg is not None:
+            self.feat_cfg = {k: feat_cfg.get(k, FEAT_DEFAULTS[k]) for k in FEAT_CLOUD_KEYS}
+            c = self.feat_cfg
+            if not c["voxel_size"] > 0:
+                raise ValueError("voxel sizes must be positive")
+            if max(int(c["k_curvature"]), int(c["k_descriptor"])) > 31 or int(c["top_n"]) > _lib.FT_MAX_KP:
+                raise ValueError(f"resident features hold k <= 31 neighbours and top_n <= {_lib.FT_MAX_KP} keypoints")
+            self.kp_stride = 8 if int(c["top_n"]) <= 0 else (int(c["top_n"]) + 7) // 8 * 8
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.voxel_size, self.rotation_voxel_size = float(voxel_size), float(rotation_voxel_size)
         self.normal_k = None if normal_k is None else int(normal_k)
@@ -216,17 +264,35 @@ class ScanHistory:
         for name in ("icp_prepared", "rs_prepared"):
             check(L.icpmi_prepared_relayout(_ptr(old[name]) if old else None, self.row_capacity, self.scan_capacity, rows, n,
                                             _ptr(getattr(self, name)), nbytes, R, S, _stream()), "prepared_relayout")
+        per_row = [("raw", None), ("vox", None), ("rs_vox", None)]
+        per_scan = [("vox", "cnt"), ("rs_vox", "cnt"), ("rs_means", None)]
+        if self.feat_cfg is not None:
+            # the feature store: tables per row or per scan, so growing is plain prefix copies (curvature is scratch of an add)
+            K = self.kp_stride
+            self.ft_vox = CloudSet(torch.empty((R, 2), **f64), off_host, cnt=torch.zeros(S, **i32), off=self.raw.off)
+            self.ft_curv = torch.empty(R, **f64)
+            self.ft_kp, self.ft_kp_cnt = torch.zeros((S, K), **i32), torch.zeros(S, **i32)
+            self.ft_desc, self.ft_desc_len = torch.zeros((S, K, _lib.FT_DESC_STRIDE), **f64), torch.zeros(S, **i32)
+            per_row += [("ft_vox", None)]
+            per_scan += [("ft_vox", "cnt"), ("ft_kp", None), ("ft_kp_cnt", None), ("ft_desc", None), ("ft_desc_len", None)]
         if old:
-            for new, was in ((self.raw.pts, old["raw"].pts), (self.vox.pts, old["vox"].pts), (self.rs_vox.pts, old["rs_vox"].pts)):
-                new[:rows].copy_(was[:rows])
-            for new, was in ((self.vox.cnt, old["vox"].cnt), (self.rs_vox.cnt, old["rs_vox"].cnt), (self.rs_means, old["rs_means"])):
-                new[:n].copy_(was[:n])
+            pick = lambda d, name, part: getattr(d[name], part or "pts") if isinstance(d[name], CloudSet) else d[name]   # noqa: E731
+            for name, part in per_row:
+                pick(self.__dict__, name, part)[:rows].copy_(pick(old, name, part)[:rows])
+            for name, part in per_scan:
+                pick(self.__dict__, name, part)[:n].copy_(pick(old, name, part)[:n])
         self.scan_capacity, self.row_capacity = S, R
         self.state = _lib.History(self.raw.pts.data_ptr(), self.raw.off.data_ptr(), self.ids.data_ptr(), self.vox.pts.data_ptr(),
                                   self.vox.cnt.data_ptr(), self.icp_prepared.data_ptr(), self.rs_vox.pts.data_ptr(),
                                   self.rs_vox.cnt.data_ptr(), self.rs_means.data_ptr(), self.rs_prepared.data_ptr(),
                                   self.voxel_ws.data_ptr(), nbytes, self.voxel_ws.numel(), self.voxel_size, self.rotation_voxel_size,
                                   S, R, -1 if self.normal_k is None else self.normal_k, 1 if self.allow_polar else 0)
+        if self.feat_cfg is not None:
+            c = self.feat_cfg
+            self.store = _lib.FeatureStore(self.ft_vox.pts.data_ptr(), self.ft_curv.data_ptr(), self.ft_vox.cnt.data_ptr(),
+                                           self.ft_kp.data_ptr(), self.ft_kp_cnt.data_ptr(), self.ft_desc.data_ptr(),
+                                           self.ft_desc_len.data_ptr(), float(c["voxel_size"]), float(c["min_kp_dist"]),
+                                           int(c["k_curvature"]), int(c["top_n"]), int(c["k_descriptor"]), self.kp_stride)
         self.layout_generation += 1
 
     def _reserve(self, scans, rows):
@@ -240,8 +306,9 @@ class ScanHistory:
         if (S, R) != (self.scan_capacity, self.row_capacity):
             self._allocate(S, R)
 
-    def _place(self, arrs, first, prepare):
-        """Upload the clouds behind the rows in use as clouds first, first + 1, ... and process that range."""
+    def _place(self, arrs, first, prepare, features=True):
+        """Upload the clouds behind the rows in use as clouds first, first + 1, ... and process that range (``features``: into
+        the feature store too, when the history has one)."""
         rows = self.rows_used
         ends = rows + np.cumsum([len(a) for a in arrs])
         self._reserve(first + len(arrs), int(ends[-1]))
@@ -254,13 +321,16 @@ class ScanHistory:
         off[first + 1 + k:] = ends[-1]
         self.raw.off[first + 1:first + 1 + k].copy_(torch.from_numpy(off[first + 1:first + 1 + k]))
         self.raw.off[first + 1 + k:].fill_(int(ends[-1]))
-        self._process(first, k, prepare)
+        self._process(first, k, prepare, features)
         self.stage_generation += 1
         return int(ends[-1])
 
-    def _process(self, first, n, prepare):
-        check(_lib.lib().icpmi_history_add(C.byref(self.state), self.raw.off_host.ctypes.data_as(C.c_void_p), first, n,
-                                           1 if prepare else 0, _stream()), "history_add")
+    def _process(self, first, n, prepare, features=True):
+        off_host = self.raw.off_host.ctypes.data_as(C.c_void_p)
+        check(_lib.lib().icpmi_history_add(C.byref(self.state), off_host, first, n, 1 if prepare else 0, _stream()), "history_add")
+        if features and self.store is not None:
+            check(_lib.lib().icpmi_history_features_add(C.byref(self.state), C.byref(self.store), off_host, first, n, _stream()),
+                  "history_features_add")
 
     @staticmethod
     def _clouds(clouds):
@@ -289,6 +359,12 @@ class ScanHistory:
         """Rows of every scan after the rotation search's voxel filter (synchronises)."""
         return self.rs_vox.cnt[:self.n_scans].cpu().numpy()
 
+    def feature_counts(self):
+        """(rows after the feature voxel filter, keypoints) of every scan (synchronises); needs a feature store."""
+        if self.store is None:
+            raise ValueError("this history keeps no features (feat_cfg=None)")
+        return self.ft_vox.cnt[:self.n_scans].cpu().numpy(), self.ft_kp_cnt[:self.n_scans].cpu().numpy()
+
     def add(self, points):
         """Append one scan (slam.py:554) -> its id."""
         return self.add_many([points])[0]
@@ -309,12 +385,13 @@ class ScanHistory:
         if redo:
             # a target above 2048 rows makes the ICP launch walk projections for every target of its batch: the earlier
             # scans, in bearing order until now, are put in order again (once in a history's life; their raw rows are here)
-            self._process(0, first, True)
+            # (their features do not depend on the search order: the store is left alone)
+            self._process(0, first, True, features=False)
         return list(range(first, self.n_scans))
 
     def match(self, source, candidates, *, error_threshold=1e-7, max_iterations=100, method="point_to_line", max_corr_dist=None,
               angle_step_coarse=2.0, angle_step_fine=0.2, max_rows_hint=0, error_accept=None, stop_after_first_accepted=False,
-              alignment_method="rotation_search", index_base=0, index_stride=1):
+              alignment_method="rotation_search", index_base=0, index_stride=1, feat_cfg=None, hypotheses=None, rng=None):
         """``_run_icp_pair(source, scan k, ...)`` for every k of ``candidates`` (slam.py:575-579), in that order (repeats
         allowed) -> a ``HistoryMatch``.  ``source``: a scan id — the current scan is appended before its candidates are
         matched, slam.py:554 — or an (n, 2) array, which is staged behind the last scan, filtered and given its means for
@@ -322,21 +399,36 @@ class ScanHistory:
         ``RunIcpPairBatch``'s.  ``index_base`` / ``index_stride``: the candidate number of pair b is index_base + b *
         index_stride, as there — what a form sharded over ranks (icpmi.dist) would pass; sharding itself is not built.
 
-        ``alignment_method`` other than "rotation_search" is not resident: use ``RunIcpPairBatch``."""
-        if alignment_method != "rotation_search":
+        ``alignment_method`` "features" / "both" need a history built with ``feat_cfg``: the cloud-side keys are the
+        history's (one given here that differs is refused), the pair-side keys (``ratio_threshold``, ``ransac_iterations``,
+        ``inlier_threshold``, ``min_inliers``) come from ``feat_cfg`` here over ``FEAT_DEFAULTS``; ``hypotheses`` / ``rng``
+        as ``FeatureAlignBatch`` takes them.  Without a feature store only "rotation_search" is resident."""
+        if alignment_method != "rotation_search" and self.store is None:
             raise ValueError(f"alignment_method {alignment_method!r} is not resident in a ScanHistory (only 'rotation_search' is): "
                              "use RunIcpPairBatch for 'features' and 'both'")
+        if alignment_method not in ALIGNMENT_METHODS:
+            raise ValueError(f"alignment_method must be one of {ALIGNMENT_METHODS}, got {alignment_method!r}")
+        cfg = None
+        if alignment_method != "rotation_search":
+            cfg = dict(feat_cfg or {})
+            for k in FEAT_CLOUD_KEYS:
+                if k in cfg and cfg[k] != self.feat_cfg[k]:
+                    raise ValueError(f"feat_cfg[{k!r}] = {cfg[k]!r} differs from the history's {self.feat_cfg[k]!r}: the resident "
+                                     "features were computed with the history's")
+            cfg.update(self.feat_cfg)
         cands = _scan_ids(candidates, ("candidates", "candidate ids"), self.n_scans)
         staged = not isinstance(source, (int, np.integer))
         if staged:
             arr = self._clouds([source])
-            self._place(arr, self.n_scans, prepare=False)        # cloud n_scans, for this match: rows_used stays
+            # cloud n_scans, for this match: rows_used stays.  Its own features serve "features" alone ("both" computes
+            # them of the transformed copies)
+            self._place(arr, self.n_scans, prepare=False, features=alignment_method == "features")
             source = self.n_scans
         else:
             source = _scan_ids(source, ("source", "source id"), self.n_scans, one=True)
         return HistoryMatch(self, int(source), cands, staged, error_threshold, max_iterations, method, max_corr_dist,
                             angle_step_coarse, angle_step_fine, max_rows_hint, error_accept, stop_after_first_accepted,
-                            index_base, index_stride)
+                            index_base, index_stride, alignment_method, cfg, hypotheses, rng)
 
     # ── world rows: transform_points_2d (slam.py:46-50) of resident scans ─────
     def world_row_args(self, poses, ids=None):

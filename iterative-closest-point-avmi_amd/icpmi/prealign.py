@@ -199,6 +199,8 @@ FEAT_ST_OK, FEAT_ST_FEW_ROWS, FEAT_ST_CAPACITY, FEAT_ST_FEW_KP, FEAT_ST_FEW_MATC
     _lib.FT_ST_OK, _lib.FT_ST_FEW_ROWS, _lib.FT_ST_CAPACITY, _lib.FT_ST_FEW_KP, _lib.FT_ST_FEW_MATCHES, _lib.FT_ST_DESC_LEN)
 FEAT_DEFAULTS = dict(voxel_size=0.2, k_curvature=10, top_n=100, min_kp_dist=0.3, k_descriptor=30, ratio_threshold=0.8,
                      ransac_iterations=1000, inlier_threshold=0.5, min_inliers=3)            # slam.py:72-83
+# the keys a cloud's own tables depend on (what a resident history computes once per scan); the others are per pair
+FEAT_CLOUD_KEYS = ("voxel_size", "k_curvature", "top_n", "min_kp_dist", "k_descriptor")
 
 
 class FeatureAlignBatch(_Paired):
@@ -224,11 +226,19 @@ class FeatureAlignBatch(_Paired):
 
     def __init__(self, clouds, pair_src, pair_tgt, feat_cfg=None, hypotheses=None, rng=None, init_in=None, init_out=None, like=None):
         require_gpu()
-        L = _lib.lib()
-        self.raw = clouds if isinstance(clouds, CloudSet) else CloudSet.from_numpy(clouds)
-        if self.raw.dim != 2:
+        raw = clouds if isinstance(clouds, CloudSet) else CloudSet.from_numpy(clouds)
+        self._init_common(raw, pair_src, pair_tgt, feat_cfg, hypotheses, rng, init_in, init_out, like)
+        need = _lib.lib().icpmi_feature_align_batch_workspace_bytes(raw.total_rows, raw.n_clouds, raw.max_n, self.B,
+                                                                    int(self.cfg["top_n"]), 1 if init_in is not None else 0)
+        self.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=raw.pts.device)
+
+    def _init_common(self, raw, pair_src, pair_tgt, feat_cfg, hypotheses, rng, init_in, init_out, like=None):
+        """What every variant needs: the configuration, the pairs, the hypothesis table, the records and where the starts
+        come from and go.  The per-cloud tables are the workspace's (a resident variant: a history's feature store)."""
+        if raw.dim != 2:
             raise ValueError("feature_based_alignment is 2-D")
-        dev = self.raw.pts.device
+        self.raw = raw
+        dev = raw.pts.device
         cfg = dict(FEAT_DEFAULTS)
         cfg.update({k: v for k, v in (feat_cfg or {}).items() if k in FEAT_DEFAULTS})
         self.cfg = cfg
@@ -249,9 +259,6 @@ class FeatureAlignBatch(_Paired):
             self.hyp_u = torch.from_numpy(rng.random((self.n_iter, 2))).to(dev)
         self.init_in, self.init_out = init_in, init_out
         self.records = torch.zeros((max(self.B, 1), _lib.FTREC_DOUBLES), dtype=torch.float64, device=dev)
-        need = L.icpmi_feature_align_batch_workspace_bytes(self.raw.total_rows, self.raw.n_clouds, self.raw.max_n, self.B,
-                                                           int(cfg["top_n"]), 1 if init_in is not None else 0)
-        self.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
 
     def run(self):
         c = self.cfg
