@@ -33,6 +33,9 @@ It also writes and re-reads the drive in the reference's wire formats: lidar lin
 
     python examples/slam_loop.py [n_scans] [--imu] [--loop]      (--loop: a closed circuit, 1.2 laps)
                                  [--reference-candidates]        (candidates by slam.py:230-268's rule)
+                                 [--edge-information icp]        (pose-graph edges weighted by the matcher's own
+                                                                  information matrix instead of slam.py:548, 592's
+                                                                  isotropic one)
 """
 import os
 import sys
@@ -43,7 +46,7 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "iterative-closest-point-avmi_amd"))
 
-from icpmi import batch, prealign, synth  # noqa: E402
+from icpmi import batch, information, prealign, synth  # noqa: E402
 from icpmi.history import ScanHistory, find_loop_candidates  # noqa: E402
 from icpmi.submap import RollingSubmap  # noqa: E402
 from utilities import features  # noqa: E402
@@ -139,6 +142,25 @@ class GpuBackend:
 
     History = ScanHistory
 
+    icp_information = staticmethod(information.icp_information)
+
+    @staticmethod
+    def match_history_information(hist, source_id, cand_ids, feat_cfg, icp_cfg, error_accept, alignment_method="rotation_search"):
+        """``match_history_first_accepted`` and, for the accepted candidate, the information record of its registration
+        (``HistoryMatch.information([first])``, unpacked; None when nothing is accepted) as a sixth value."""
+        m = hist.match(source_id, cand_ids, error_threshold=icp_cfg["error_threshold"], max_iterations=icp_cfg["max_iterations"],
+                       method=icp_cfg["method"], angle_step_coarse=feat_cfg["angle_step_coarse"],
+                       angle_step_fine=feat_cfg["angle_step_fine"], error_accept=error_accept, stop_after_first_accepted=True,
+                       alignment_method=alignment_method)
+        m.run()
+        R, t, err, info = m.unpack()
+        first = info["first_accepted"]
+        rec = None
+        if first >= 0:
+            rec = information.unpack_information(m.information([first]).cpu().numpy()[0])
+            rec["method"] = icp_cfg["method"]
+        return R, t, err, info["iters"], first, rec
+
     @staticmethod
     def match_history_first_accepted(hist, source_id, cand_ids, feat_cfg, icp_cfg, error_accept, alignment_method="rotation_search"):
         """The same against scans resident in ``hist`` (a ``History`` with the voxel sizes and normal_k of the two
@@ -154,15 +176,42 @@ class GpuBackend:
         return R, t, err, info["iters"], info["first_accepted"]
 
 
+EDGE_INFORMATION = ("isotropic", "icp")
+
+
+def edge_omega(info, R, scale=1.0):
+    """The pose-graph information of a registration from its information record (icpmi.information): ``scale`` *
+    edge_information(H, R, sigma2) with sigma2 the residual variance, floored at the 1e-6 of slam.py:548, 592; None when the
+    record cannot give one (too few inliers, an empty cloud): the caller keeps the isotropic weight."""
+    if info is None or info["status"] != 0:
+        return None
+    try:
+        sigma2 = max(information.residual_variance(info), 1e-6)
+    except ValueError:
+        return None
+    return scale * information.edge_information(info["H"], R, sigma2)
+
+
 def run(n_scans=60, log_path=None, verbose=True, imu_path=None, loop=False, use_submap=True, lc_error_threshold=0.05,
-        backend=None, max_candidates=5, reference_candidates=False, alignment_method="rotation_search"):
-    """alignment_method: the pre-alignment of the loop-closure matches (slam.py:60, 68: "rotation_search", "features" or
+        backend=None, max_candidates=5, reference_candidates=False, alignment_method="rotation_search",
+        edge_information="isotropic"):
+    """edge_information: "isotropic" weights the pose-graph edges as the reference does (slam.py:548, 592); "icp" takes the
+    information matrix of each accepted registration instead (icpmi.information: the odometry edge from ``icp_information``
+    at the scan-to-scan result, the closure edge from the resident match's ``information([first])``, times the 10.0 of
+    slam.py:592) and reports the smallest relative eigenvalue of each closure's constraint spectrum; it needs a backend
+    with ``icp_information``, ``History`` and ``match_history_information``.
+    alignment_method: the pre-alignment of the loop-closure matches (slam.py:60, 68: "rotation_search", "features" or
     "both"); other than the default, the resident history keeps the per-scan features as well.
     reference_candidates: pick the loop-closure candidates with ``find_loop_candidates`` (slam.py:230-268: a cumulative
     travel gate, nearest first) instead of this harness' short rule (the first ``max_candidates`` old scans within 3 m)."""
     from icpmi import submap as submap_mod
     uicp.VERBOSE = features.VERBOSE = submap_mod.VERBOSE = upg.VERBOSE = False
     be = backend or GpuBackend
+    if edge_information not in EDGE_INFORMATION:
+        raise ValueError(f"edge_information must be one of {EDGE_INFORMATION}, got {edge_information!r}")
+    use_info = edge_information == "icp"
+    if use_info and not all(hasattr(be, name) for name in ("icp_information", "History", "match_history_information")):
+        raise ValueError("edge_information='icp' needs a backend with icp_information, History and match_history_information")
     segs = synth.maze_segments()
     truth = synth.loop_trajectory(n_scans) if loop else synth.trajectory(n_scans, step=0.18)
     scans = [synth.scan(p, 9000 + i, segs=segs) for i, p in enumerate(truth)]
@@ -180,7 +229,7 @@ def run(n_scans=60, log_path=None, verbose=True, imu_path=None, loop=False, use_
     pose = pose_matrix(*truth[0])                       # start at the true pose; everything after is estimated
     submap = be.Submap(window=40, voxel_size=0.04)
     history, mapper, timing = [], None, {"s2s": 0.0, "submap": 0.0, "map": 0.0, "loop": 0.0}
-    closures, rejected, accepted = [], [], []
+    closures, rejected, accepted, spectra = [], [], [], []
     feat_kw = dict(rotation_voxel_size=0.15, angle_step_coarse=1.5, angle_step_fine=0.1)
     # the past scans, prepared once on the device (a backend without a History matches the arrays, batch by batch)
     match_kw = {} if alignment_method == "rotation_search" else dict(alignment_method=alignment_method)
@@ -190,6 +239,7 @@ def run(n_scans=60, log_path=None, verbose=True, imu_path=None, loop=False, use_
     graph = be.Graph()
     prev = None
     for i, cur in enumerate(scans):
+        odo_omega = None
         if prev is not None:
             t0 = time.perf_counter()
             # ICP(prev -> cur) maps the previous scan into the current sensor frame (slam.py:481-483)
@@ -206,6 +256,9 @@ def run(n_scans=60, log_path=None, verbose=True, imu_path=None, loop=False, use_
                 T_inv[:2, :2] = r.T
                 T_inv[:2, 2] = -r.T @ t
                 pose = pose @ T_inv                                           # slam.py:38-43
+                if use_info:                                                  # the odometry edge's own information (its z is T^-1)
+                    odo_omega = edge_omega(be.icp_information(prev, cur, r, t, icp_kw["voxel_size"], method=icp_kw["method"],
+                                                              normal_k=icp_kw["normal_k"]), r)
             else:
                 rejected.append(i)                                            # keep the pose; the submap step may still fix it
             timing["s2s"] += time.perf_counter() - t0
@@ -232,7 +285,8 @@ def run(n_scans=60, log_path=None, verbose=True, imu_path=None, loop=False, use_
         node = graph.add_node(pose_matrix_to_vec(pose))                      # slam.py:543-549: node + odometry edge
         if node > 0:
             odo_err = err if err <= 0.15 else 0.15
-            graph.add_edge(node - 1, node, relative_transform_vec(history[-2][1], pose), np.eye(3) / max(odo_err, 1e-6))
+            graph.add_edge(node - 1, node, relative_transform_vec(history[-2][1], pose),
+                           np.eye(3) / max(odo_err, 1e-6) if odo_omega is None else odo_omega)
         # loop closure candidates: old scans near the current position (slam.py:230-268), tried in order; each is
         # pre-aligned and registered as _run_icp_pair does (slam.py:53-98) — all of them in one batch, searches and ICPs
         # chained on the device — and the FIRST whose error is below the gate wins (slam.py:582-597)
@@ -243,7 +297,11 @@ def run(n_scans=60, log_path=None, verbose=True, imu_path=None, loop=False, use_
             else:
                 cands = [k for k, (_, pk) in enumerate(history[:-20]) if np.linalg.norm(pk[:2, 2] - pose[:2, 2]) < 3.0][:max_candidates]
             if cands:
-                if resident is not None:                             # the current scan is the last one added
+                lc_info = None
+                if use_info:                                         # the same match, and the accepted candidate's information
+                    R, t, err, its, first, lc_info = be.match_history_information(resident, len(history) - 1, cands, feat_kw, icp_kw,
+                                                                                 lc_error_threshold, **match_kw)
+                elif resident is not None:                           # the current scan is the last one added
                     R, t, err, its, first = be.match_history_first_accepted(resident, len(history) - 1, cands, feat_kw, icp_kw,
                                                                             lc_error_threshold, **match_kw)
                 elif hasattr(be, "run_icp_pairs_first_accepted"):      # the candidates after the accepted one may stop early
@@ -260,8 +318,12 @@ def run(n_scans=60, log_path=None, verbose=True, imu_path=None, loop=False, use_
                     best = first
                     T_lc = np.eye(3)
                     T_lc[:2, :2], T_lc[:2, 2] = R[best], t[best]              # cur -> candidate frame, so z = T_lc^-1
+                    lc_omega = edge_omega(lc_info, R[best], 10.0)             # None: isotropic, slam.py:592
+                    if lc_info is not None:
+                        lam = information.constraint_spectrum(lc_info["H"])[0]
+                        spectra.append((i, cands[best], float(lam[0] / lam[-1])))
                     graph.add_edge(node, cands[best], pose_matrix_to_vec(np.linalg.inv(T_lc)),
-                                   np.eye(3) * 10.0 / max(float(err[best]), 1e-6))
+                                   np.eye(3) * 10.0 / max(float(err[best]), 1e-6) if lc_omega is None else lc_omega)
                     before = pose[:2, 2].copy()
                     graph.optimize(n_iterations=20, fix_node=0)
                     history = [(pts, pose_vec_to_matrix(v)) for (pts, _), v in zip(history, graph.nodes)]
@@ -291,12 +353,24 @@ def run(n_scans=60, log_path=None, verbose=True, imu_path=None, loop=False, use_
         if accepted:
             print("closures accepted (scan, matched scan, pose moved by [m], iterations): "
                   + ", ".join(f"({a}, {b}, {d:.3f}, {inf['iterations']})" for a, b, d, inf in accepted))
+        if spectra:
+            print("closure constraint spectra (scan, matched scan, smallest / largest eigenvalue of the scaled Hessian): "
+                  + ", ".join(f"({a}, {b}, {r:.2e})" for a, b, r in spectra))
     return dict(drift=drift, occupied=occupied, free=free, closures=closures, rejected=rejected, timing=timing,
-                accepted=accepted, graph=graph, mapper=mapper, history=history)
+                accepted=accepted, graph=graph, mapper=mapper, history=history, spectra=spectra)
 
 
 if __name__ == "__main__":
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    argv = sys.argv[1:]
+    edge_info = "isotropic"
+    for k, a in enumerate(argv):
+        if a == "--edge-information" and k + 1 < len(argv):
+            edge_info = argv.pop(k + 1)
+            break
+        if a.startswith("--edge-information="):
+            edge_info = a.split("=", 1)[1]
+    args = [a for a in argv if not a.startswith("--")]
     run(int(args[0]) if args else 60, log_path="/tmp/icpmi_demo_lidar.csv",
         imu_path="/tmp/icpmi_demo_imu.csv" if "--imu" in sys.argv else None, loop="--loop" in sys.argv,
-        use_submap="--no-submap" not in sys.argv, reference_candidates="--reference-candidates" in sys.argv)
+        use_submap="--no-submap" not in sys.argv, reference_candidates="--reference-candidates" in sys.argv,
+        edge_information=edge_info)

@@ -200,6 +200,47 @@ int icpmi_icp_batch_gated(const double* pts, const int32_t* off_dev, const int32
                           void* workspace, size_t workspace_bytes, double error_accept, const double* search_records,
                           int32_t index_base, int32_t index_stride, int32_t* first_accepted_dev, void* stream);
 
+/* ---- information matrix of an ICP result: the normal equations of _point_to_line_solve_2d, icp.py:92-104 (ATA, ATb),
+ * evaluated once at a given transform; matching and rejection as icp.py:179, 184-186 --------------------------------
+ * The reference weights its pose-graph edges isotropically (slam.py:548, 592); the Gauss-Newton Hessian of the last
+ * ICP step says how well each direction of [theta, tx, ty] is constrained.  A pass of its own, after the ICP: the fused
+ * kernels are not touched.  2-D rows only (the entry takes no `dim`); a method other than the two below:
+ * ICPMI_ERR_UNSUPPORTED.
+ * For pair b, S the valid rows of cloud pair_src[b], Q and N the valid rows of cloud pair_tgt[b] and their normals
+ * (`normals`: row layout of pts; required for ICPMI_POINT_TO_LINE, NULL: ICPMI_ERR_ARG; not read for
+ * ICPMI_POINT_TO_POINT), transforms[b] = {R row-major (4), t (2)}:
+ *   moved row   p' = ((R00 * sx + R01 * sy) + tx, (R10 * sx + R11 * sy) + ty) — float64, evaluated exactly as written:
+ *               two products, their sum, then the translation, every operation rounded on its own (no fused
+ *               multiply-add);
+ *   match       j = the exact nearest row of Q to p', d2 = dx * dx + dy * dy, lowest index on ties (icpmi_nn_batch);
+ *   inlier      max_corr_dist < 0 (None), or dist * dist < max_corr_dist * max_corr_dist with dist = sqrt(d2);
+ *   point_to_line, per inlier, n = N[j], q = Q[j]:  c = ny * p'x - nx * p'y, A row = [c, nx, ny],
+ *               b = -(nx * (p'x - qx) + ny * (p'y - qy));
+ *   point_to_point, per inlier, two rows:  [-p'y, 1, 0 | -(p'x - qx)] and [p'x, 0, 1 | -(p'y - qy)];
+ *   H = sum A^T A, g = sum A^T b, sse = sum b * b over those rows.
+ * out [n_pairs][ICPMI_INFO_DOUBLES], slots ICPMI_INFO_*: H's upper triangle (theta-theta, theta-x, theta-y, xx, xy, yy),
+ * g (theta, x, y), sse, inliers, source rows, status; the rest zero.  Status 0: ok; ICPMI_ST_FEW_INLIERS: a gate is
+ * given and inliers < max(3, rows / 10) (icp.py:186; the sums over the inliers are still written); ICPMI_ST_EMPTY: a
+ * cloud of the pair has no rows (every other slot zero).
+ * One workgroup of ICPMI_INFO_THREADS threads per pair: thread l takes the source rows l, l + ICPMI_INFO_THREADS, ...
+ * (any number of them: max_src_n, their upper bound, sizes nothing and is only checked to be >= 0), the target passes
+ * through LDS ICPMI_INFO_TILE_ROWS rows at a time (any number of them), and the partial sums meet in one fixed tree —
+ * no atomics — so a record is the same bits run after run and in whatever batch its pair is computed.  The search is
+ * exhaustive: rows(S) * rows(Q) distance evaluations by one workgroup.  No workspace. */
+#define ICPMI_INFO_DOUBLES 16
+#define ICPMI_INFO_H 0            /* 6: theta-theta, theta-x, theta-y, xx, xy, yy */
+#define ICPMI_INFO_G 6            /* 3: theta, x, y                               */
+#define ICPMI_INFO_SSE 9
+#define ICPMI_INFO_INLIERS 10
+#define ICPMI_INFO_ROWS 11
+#define ICPMI_INFO_STATUS 12
+#define ICPMI_INFO_THREADS 512
+#define ICPMI_INFO_TILE_ROWS 2048
+int icpmi_icp_information_batch(const double* pts, const int32_t* off_dev, const int32_t* cnt_dev,
+                                const double* normals, const int32_t* pair_src, const int32_t* pair_tgt,
+                                int32_t n_pairs, int32_t max_src_n, const double* transforms,
+                                int32_t method, double max_corr_dist, double* out, void* stream);
+
 /* ---- prepared targets: axis choice + sort (+ normals) for the sweep search ----
  * For every selected cloud (<= 4096 rows): pick the projection axis (x, y, x+y
  * or x-y) with the smallest expected search window, sort the cloud along it and

@@ -28,6 +28,11 @@ FT_MAX_ROWS, FT_MAX_KP, FT_DESC_STRIDE = 2048, 256, 32
 FTREC_DOUBLES, FTREC_NS, FTREC_NT, FTREC_KPS, FTREC_KPT, FTREC_MATCHES, FTREC_INLIERS, FTREC_R, FTREC_T, FTREC_STATUS, FTREC_BEST = (
     16, 0, 1, 2, 3, 4, 5, 6, 10, 12, 13)
 FT_ST_OK, FT_ST_FEW_ROWS, FT_ST_CAPACITY, FT_ST_FEW_KP, FT_ST_FEW_MATCHES, FT_ST_DESC_LEN = 0, 1, 2, 3, 4, 5
+# the record of icpmi_icp_information_batch (INFO_*: H's upper triangle, g, sse, inliers, source rows, status) and the
+# two sizes its kernel is built on (threads of a workgroup, target rows of an LDS tile)
+INFO_DOUBLES, INFO_H, INFO_G, INFO_SSE, INFO_INLIERS, INFO_ROWS, INFO_STATUS = 16, 0, 6, 9, 10, 11, 12
+INFO_THREADS, INFO_TILE_ROWS = 512, 2048
+INFO_SLOTS = ("H_tt", "H_tx", "H_ty", "H_xx", "H_xy", "H_yy", "g_t", "g_x", "g_y", "sse", "inliers", "rows", "status")
 
 
 class IcpParams(C.Structure):
@@ -89,6 +94,8 @@ _SIGS = {
     "icpmi_icp_batch_gated": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 4 + [C.POINTER(IcpParams), C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p, C.c_int32,
                                         C.c_int32, C.c_void_p, C.c_void_p]),
+    "icpmi_icp_information_batch": (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double,
+                                              C.c_void_p, C.c_void_p]),
     "icpmi_prepared_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "icpmi_prepare_targets": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p, C.c_size_t,
                                         C.c_void_p]),

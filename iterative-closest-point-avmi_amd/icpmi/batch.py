@@ -302,6 +302,7 @@ class IcpBatch(_Paired):
         self.results = torch.zeros((max(self.B, 1), _lib.RES_DOUBLES), dtype=torch.float64, device=dev)
         self.gate = None
         self.first_accepted_dev = None
+        self.info_normals = None          # row-order normals of the targets information() was asked about (made on first use)
 
     def set_problem(self, error_threshold, max_iterations, voxel_size, method, normal_k, max_corr_dist, have_init):
         """Aim the batch at the clouds now in ``raw`` (their row counts) with these ICP arguments; buffers stay as they
@@ -401,6 +402,13 @@ class IcpBatch(_Paired):
         if events is not None:
             events[1].record()
         return self.results
+
+    def information(self, pairs=None, results=None):
+        """The Gauss-Newton information records (icpmi.information; include/icpmi.h, icpmi_icp_information_batch) of the pairs
+        ``pairs`` (indices into the pair list; None: all) at the transforms in ``results`` (None: those of the last ``run()``),
+        with the batch's method and ``max_corr_dist`` -> a device (len(pairs), 16) tensor; does not synchronise.  2-D only."""
+        from .information import batch_information
+        return batch_information(self, pairs, results)
 
     def unpack(self, results=None):
         """(R [B,d,d], t [B,d], err [B], info) on the host (synchronises)."""

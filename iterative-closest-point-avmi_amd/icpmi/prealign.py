@@ -367,6 +367,14 @@ class RunIcpPairBatch(_Paired):
             self.features.run()
         return self.icp.run(events=events)
 
+    def information(self, pairs=None):
+        """``IcpBatch.information`` of the ICP part: the information records of the pairs ``pairs`` (indices b into the pair
+        list — the pair of candidate number c is b = (c - index_base) / index_stride; None: all) at the transforms of the last ``run()`` -> a
+        device (len(pairs), 16) tensor.  Typically asked for the ``first_accepted()`` pair alone.  A record with status
+        ST_SKIPPED is answered at the transform it holds (the steps the candidate had applied when it stopped), and a pair
+        ``unpack()`` redoes on the host (search status 2) at the device's, not the redone, transform."""
+        return self.icp.information(pairs)
+
     def first_accepted(self):
         """Index (in candidate numbers) of the candidate slam.py:582-597 accepts after the last gated ``run()``, -1 when
         none: a 4-byte read of the device's answer — unless a candidate fell outside the on-chip search (status 2), which
