@@ -61,13 +61,17 @@ int launch_icp2(const double* pts, const int32_t* off, const int32_t* cnt, const
 // ── carving a caller's buffer (host) ─────────────────────────────────────────
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// Rows of the clouds of a set, from the host mirror of its offsets: false when a cloud has a negative row count.
-inline bool cloud_rows(const int32_t* off_host, int n_clouds, int& max_n, int& total_rows) {
+// Rows of the clouds of a set, from the host mirror of its offsets: false when a cloud has a negative row count.  With a
+// `limit` (and a counter), max_n is the largest cloud at or below it and *n_above counts the clouds above it.
+inline bool cloud_rows(const int32_t* off_host, int n_clouds, int& max_n, int& total_rows, int limit = 0x7fffffff,
+                       int* n_above = nullptr) {
     max_n = 0;
+    if (n_above) *n_above = 0;
     for (int c = 0; c < n_clouds; ++c) {
         const int rows = off_host[c + 1] - off_host[c];
         if (rows < 0) return false;
-        max_n = rows > max_n ? rows : max_n;
+        if (rows > limit) ++*n_above;
+        else max_n = rows > max_n ? rows : max_n;
     }
     total_rows = off_host[n_clouds];
     return true;

@@ -141,8 +141,7 @@ __global__ __launch_bounds__(ICPMI_WAVE) void ft_keypoints_kernel(const double* 
         for (int i = threadIdx.x; i < n; i += ICPMI_WAVE) rows[i] = (uint32_t)order[f.first + i];
         __syncthreads();
     } else {
-        int npad = 64;
-        while (npad < n) npad <<= 1;
+        const int npad = sort_npad(n);
         for (int i = threadIdx.x; i < npad; i += ICPMI_WAVE) {
             keys[i] = i < n ? f64_sortable(-curv[f.first + i]) : ~0ull;       // ascending -curvature = descending curvature
             rows[i] = i < n ? (uint32_t)i : 0xffffffffu;

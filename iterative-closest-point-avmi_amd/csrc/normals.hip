@@ -128,11 +128,11 @@ __global__ __launch_bounds__(NRM_THREADS) void normals_kernel(
     if (M <= 0) return;
     const double* P = pts + (size_t)off[c] * 2;
     double* O = out_normals + (size_t)off[c] * 2;
-    int npad = 64;
-    while (npad < M) npad <<= 1;
+    const int npad = sort_npad(M);
+    const PairSortLds lds(npad);
     // two instantiations so that each sees one address space (LDS or global)
     if (npad <= lds_points)
-        normals_cloud(reinterpret_cast<uint64_t*>(dyn), reinterpret_cast<uint32_t*>(dyn + (size_t)npad * sizeof(uint64_t)), npad, M, k, P, O);
+        normals_cloud(lds.keys(dyn), lds.rows(dyn), npad, M, k, P, O);
     else
         normals_cloud(gkeys + 2 * (size_t)off[c], grows + 2 * (size_t)off[c], npad, M, k, P, O);
 }
@@ -161,12 +161,11 @@ extern "C" int icpmi_normals_2d_batch(const double* pts, const int32_t* off_dev,
     if (!pts || !off_dev || !out_normals || n_sel < 0 || total_rows < 0 || max_n < 0 || k < 0) return ICPMI_ERR_ARG;
     if (k > 31) return ICPMI_ERR_UNSUPPORTED;
     if (n_sel == 0 || max_n == 0) return ICPMI_OK;
-    int npad = 64;
-    while (npad < max_n) npad <<= 1;
+    const int npad = sort_npad(max_n);
     const int lds_points = npad < NRM_LDS_MAX ? npad : NRM_LDS_MAX;
     const NormalsWs w{npad > NRM_LDS_MAX ? workspace : nullptr, total_rows};
     if (npad > NRM_LDS_MAX && (!workspace || workspace_bytes < w.bytes)) return ICPMI_ERR_WORKSPACE;
-    const size_t lds = (size_t)lds_points * 12;
+    const size_t lds = PairSortLds(lds_points).bytes;
     if (dyn_lds((const void*)normals_kernel, lds) != hipSuccess) return ICPMI_ERR_HIP;
     normals_kernel<<<n_sel, NRM_THREADS, lds, (hipStream_t)stream>>>(pts, off_dev, cnt_dev, cloud_ids, k, out_normals, w.gkeys, w.grows, lds_points);
     ICPMI_LAUNCH_CHECK();

@@ -5,6 +5,8 @@
 // fused ICP kernel, and — for point_to_line — estimate_normals_2d (reference
 // utilities/icp.py:51-76) by an outward sweep from every point's own sorted
 // position, which is an exact k-NN search (see sweep.hpp).
+#include <vector>
+
 #include "prep_common.hpp"
 
 namespace icpmi {
@@ -17,7 +19,36 @@ namespace icpmi {
 #endif
 constexpr int PREP_THREADS = 512;
 constexpr int PREP_MAXW = PREP_THREADS / ICPMI_WAVE;
-constexpr int PREP_MAX_POINTS = 4096;   // sorted copy (20 B/pt) + sort scratch (12 B/pt) stay in LDS
+constexpr int PREP_MAX_POINTS = 4096;   // sorted copy + sort scratch stay in LDS (PrepLds)
+
+// Dynamic LDS of prep_targets_kernel, stated once: the kernel takes its pointers from here (lds_points from the launch, npad
+// from its own cloud), the launcher its size (npad of the largest cloud).  The sorted copy of lds_points rows: xy |
+// original row | float32 bearing (bearing order only).  The sort scratch of the cloud's npad slots: behind the copy when the
+// grid is built there afterwards (GRID), otherwise ON the copy (the sorted rows pass through registers) — 40 KB instead of
+// 64 KB for ~1 500 points, so that the k-NN loops of three workgroups instead of two share a CU.  Up to 4 * PREP_THREADS
+// slots the network runs on registers (at least a slot per thread) and the scratch is keys by row | sorted keys | their
+// rows; beyond, the pair sort's keys | rows alone.  The grid's cell ends and positions by cell then take the scratch's place.
+struct PrepLds {
+    size_t sorig_at, sth_at;              // the sorted copy: sxy at 0
+    size_t by_row_at, keys_at;            // the sort scratch: keys by row (register sort), then `pairs` = sorted keys | their rows
+    size_t cell_end_at, cell_pts_at;      // the grid, in the scratch's place afterwards
+    size_t bytes;
+    bool reg_sort;
+    int nsort, cells_cap;                 // slots of the sort; cells of the grid
+    PairSortLds pairs;
+    __host__ __device__ PrepLds(int lds_points, int npad, bool grid)
+        : reg_sort(npad <= 4 * PREP_THREADS), nsort(reg_sort && npad < PREP_THREADS ? PREP_THREADS : npad),
+          cells_cap(2 * npad < 4096 ? 2 * npad : 4096), pairs(nsort) {
+        const size_t copy_bytes = (size_t)lds_points * 24;
+        sorig_at = (size_t)lds_points * 16;
+        sth_at = (size_t)lds_points * 20;
+        by_row_at = cell_end_at = grid ? copy_bytes : 0;
+        keys_at = by_row_at + (reg_sort ? (size_t)nsort * sizeof(uint64_t) : 0);
+        cell_pts_at = cell_end_at + (size_t)cells_cap * sizeof(uint32_t);
+        bytes = keys_at + pairs.bytes > copy_bytes ? keys_at + pairs.bytes : copy_bytes;
+    }
+    template <class T> static __device__ T* at(unsigned char* dyn, size_t o) { return reinterpret_cast<T*>(dyn + o); }
+};
 
 // KK = capacity of the per-query neighbour list (0: no normals); GRID: k-NN through a grid instead of the sweep
 // Sort of up to E * PREP_THREADS rows by (key, row) on registers; leaves keys[i] / rows[i] = full sortable key and row of
@@ -116,30 +147,23 @@ __global__ __launch_bounds__(PREP_THREADS, (KK <= 13 ? ICPMI_PREP_WPS : (KK <= 1
     if (off[c + 1] - off[c] > PREP_MAX_POINTS) return;          // prepared through global memory (prep_big.hip)
     if (M <= 0 || M > lds_points) { if (threadIdx.x == 0) g_dir[c] = -1; return; }
     const double* P = pts + (size_t)off[c] * 2;
-    int npad = 64;
-    while (npad < M) npad <<= 1;
-    double2* sxy = reinterpret_cast<double2*>(dyn);                                   // lds_points * 16 B
-    int32_t* sorig = reinterpret_cast<int32_t*>(dyn + (size_t)lds_points * 16);       // lds_points * 4 B
-    float* sth = reinterpret_cast<float*>(dyn + (size_t)lds_points * 20);             // lds_points * 4 B: float32 bearings (polar order)
-    // sort scratch (20 B per padded slot, 12 for 4 096 slots): behind the sorted copy when the grid needs it afterwards,
-    // otherwise ON the sorted copy (the sorted rows pass through registers) — 40 KB instead of 64 KB for ~1 500 points, so
-    // that the k-NN loops of three workgroups instead of two share a CU
-    const size_t scratch_at = GRID ? (size_t)lds_points * 24 : 0;
-    const bool reg_sort = npad <= 4 * PREP_THREADS;                                    // the network on registers (below)
-    const int nsort = reg_sort ? max(npad, PREP_THREADS) : npad;
-    uint64_t* by_row = reinterpret_cast<uint64_t*>(dyn + scratch_at);                  // reg_sort: keys by row, nsort * 8 B
-    uint64_t* keys = reinterpret_cast<uint64_t*>(dyn + scratch_at + (reg_sort ? (size_t)nsort * 8 : 0));     // sorted keys, 8 B per slot
-    uint32_t* rows = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(keys) + (size_t)nsort * 8); // their rows
+    const int npad = sort_npad(M);
+    const PrepLds lds(lds_points, npad, GRID);
+    double2* sxy = lds.at<double2>(dyn, 0);
+    int32_t* sorig = lds.at<int32_t>(dyn, lds.sorig_at);
+    float* sth = lds.at<float>(dyn, lds.sth_at);
+    uint64_t *by_row = lds.at<uint64_t>(dyn, lds.by_row_at), *keys = lds.pairs.keys(dyn + lds.keys_at);
+    uint32_t* rows = lds.pairs.rows(dyn + lds.keys_at);
 
     double bounds[4];
     const int dir = choose_axis<PREP_THREADS>(P, M, dsc, hist, bounds, polar, (!GRID && M >= 512) ? PREP_AXIS_STEP : 1);   // bounds: the grid's
     // ── sort along the chosen axis (or by bearing) ───────────────────────────
-    if (reg_sort) {
+    if (lds.reg_sort) {
         // (key, row) as ONE 64-bit element: the key's low 11 bits give way to the row, the network runs on registers
         // (sort.hpp: thread t owns slots t E .. t E + E - 1), and the rare neighbours whose keys agree in the 53 bits
         // that are left are put right afterwards from the full keys — the order is exactly the pair sort's.
-        if (nsort == PREP_THREADS) prep_sort_regs<1>(P, M, dir, by_row, keys, rows);
-        else if (nsort == 2 * PREP_THREADS) prep_sort_regs<2>(P, M, dir, by_row, keys, rows);
+        if (lds.nsort == PREP_THREADS) prep_sort_regs<1>(P, M, dir, by_row, keys, rows);
+        else if (lds.nsort == 2 * PREP_THREADS) prep_sort_regs<2>(P, M, dir, by_row, keys, rows);
         else prep_sort_regs<4>(P, M, dir, by_row, keys, rows);
     } else {
         for (int i = threadIdx.x; i < npad; i += PREP_THREADS) {
@@ -185,10 +209,8 @@ __global__ __launch_bounds__(PREP_THREADS, (KK <= 13 ? ICPMI_PREP_WPS : (KK <= 1
             // grid bounds that far better than a 1-D window (a wall across the sweep axis puts hundreds of
             // points in it).  Built in the LDS the sort has released: cell ends (4 B per cell), then positions
             // by cell.  Same neighbours, same order.
-            const int cells_cap = min(4096, 2 * npad);
-            uint32_t* cell_end = reinterpret_cast<uint32_t*>(dyn + scratch_at);
-            uint16_t* cell_pts = reinterpret_cast<uint16_t*>(cell_end + cells_cap);
-            const PrepGrid grid = prep_grid_build(sxy, M, bounds, kk, cell_end, cell_pts, cells_cap, hist);
+            const PrepGrid grid = prep_grid_build(sxy, M, bounds, kk, lds.at<uint32_t>(dyn, lds.cell_end_at), lds.at<uint16_t>(dyn, lds.cell_pts_at),
+                                                   lds.cells_cap, hist);
             prep_normals_grid<KK>(sxy, sorig, M, min(M, part * per), min(M, (part + 1) * per), kk, grid, o_snrm, o_rows);
         } else {
             // Many clouds: every CU is busy, the sum of the work counts, and the sweep has less of it per candidate.
@@ -328,6 +350,80 @@ static PrepChoice prep_choice(int normal_k, bool use_grid) {
     return prep_choice_of<32>(use_grid);
 }
 
+// What a call starts, decided as a whole from its arguments and the host mirrors (no HIP call).  need_bytes: what
+// icpmi_prepared_bytes asks for these arguments; polar_opt, knn_opt: the options POLAR and PREP_KNN, read once by the caller.
+struct PrepPlan {
+    int rc;                   // ICPMI_OK, or why nothing is launched
+    std::vector<int32_t> big; // selected clouds above PREP_MAX_POINTS rows, prepared one by one (prep_big.hip) in front of the launches
+    int sel_rc;               // ICPMI_ERR_ARG: the selection names a cloud outside the set — returned after the large clouds in front of it
+    int small_max, lds_points;    // rows of the largest cloud of the main launch, and of its sorted copy in LDS (rounded to 64)
+    PrepChoice pc;
+    int polar, split, parts;
+    unsigned grid;            // main launch (0: none): workgroups,
+    size_t lds;               // ... their dynamic LDS (PrepLds)
+    int sel_cap, per_cloud;   // any-k launch behind it (per_cloud 0: none): list capacity of a query, workgroups per cloud,
+    size_t lds_k;             // ... their dynamic LDS
+};
+static PrepPlan plan_prepare(const int32_t* off_host, const int32_t* cloud_ids, const int32_t* cloud_ids_host, int n_sel,
+                             int n_clouds, int max_n, int normal_k, size_t prepared_bytes, size_t need_bytes, int allow_polar,
+                             const char* polar_opt, const char* knn_opt) {
+    PrepPlan p{};
+    const auto fail = [&p](int rc) { p.rc = rc; return p; };
+    if (normal_k > 31 && (size_t)(normal_k + 1) * 4 * (ANYK_THREADS / ICPMI_WAVE) > 96 * 1024) return fail(ICPMI_ERR_UNSUPPORTED);   // k beyond 6 143
+    if (prepared_bytes < need_bytes) return fail(ICPMI_ERR_WORKSPACE);
+    if (max_n > PREP_MAX_POINTS && !off_host) return fail(ICPMI_ERR_ARG);       // sizes are needed on the host to route big clouds
+    if (cloud_ids && max_n > PREP_MAX_POINTS && !cloud_ids_host) return fail(ICPMI_ERR_ARG);
+    if (n_sel == 0 || max_n == 0) return p;
+    // clouds above the LDS capacity go one by one through global memory (prep_big.hip)
+    p.small_max = max_n;
+    if (max_n > PREP_MAX_POINTS) {
+        p.small_max = 0;
+        for (int i = 0; i < n_sel; ++i) {
+            const int c = cloud_ids ? cloud_ids_host[i] : i;
+            if (c < 0 || c >= n_clouds) { p.sel_rc = ICPMI_ERR_ARG; return p; }
+            const int n = off_host[c + 1] - off_host[c];
+            if (n > PREP_MAX_POINTS) p.big.push_back(c);
+            else p.small_max = n > p.small_max ? n : p.small_max;
+        }
+        if (p.small_max == 0 && normal_k <= 31) return p;
+    }
+    // sorted copy sized to the largest cloud (rounded to 64) — with ~1 500-point clouds 53 KB instead of 64 KB: three
+    // workgroups per CU instead of two
+    p.lds_points = (p.small_max + 63) / 64 * 64;
+    // bearing order (sweep.hpp, SWEEP_POLAR) only where every consumer understands it: on request, and only when EVERY
+    // selected cloud has at most 2 048 rows — the fused ICP launch picks ONE instantiation for the whole batch from the
+    // same max_n, and the ones for larger targets (no float32 images) cannot walk a bearing order: a batch that mixes
+    // scans with one rolling submap therefore sorts everything along projections.  Option "POLAR": 0 never, 2 always
+    // (tests).
+    p.polar = allow_polar && max_n <= 2048 ? 1 : 0;
+    if (polar_opt) p.polar = p.polar ? (polar_opt[0] == '0' ? 0 : (polar_opt[0] == '2' ? 2 : 1)) : 0;
+    p.split = 256 / n_sel;                 // a workgroup for every CU when the batch is small
+    p.split = p.split < 1 ? 1 : (p.split > 16 ? 16 : p.split);
+    // k-NN search of the normals: grid for few clouds that will be sorted along a projection (a wall across the sweep axis
+    // puts hundreds of points into a window, and a small launch lasts as long as its longest search), sweep otherwise —
+    // in bearing order a scan's windows are short everywhere (round 4, one 2 048-beam scan, k = 12: sweep 0.037 ms, grid
+    // 0.076; 64 scans: 0.050 / 0.115).  Where the bearing order is allowed the device may still pick a projection for a
+    // cloud that is no scan: the sweep is then slower, never wrong.  Option PREP_KNN = grid | sweep forces one of the two
+    // (tests run both on the same inputs)
+    int use_grid = p.split > 1 && !p.polar;
+    if (knn_opt) use_grid = knn_opt[0] == 'g' ? 1 : (knn_opt[0] == 's' ? 0 : use_grid);
+    p.pc = prep_choice(normal_k, use_grid);
+    p.parts = p.pc.kk > 0 ? p.split : 1;
+    if (p.small_max > 0) {
+        p.grid = (unsigned)(n_sel * p.parts);
+        p.lds = PrepLds(p.lds_points, sort_npad(p.small_max), p.pc.grid).bytes;
+    }
+    if (normal_k > 31) {
+        // the list of a query: k + 1 positions, at most the largest cloud
+        const int kcap = normal_k + 1 < max_n ? normal_k + 1 : max_n;
+        p.sel_cap = (kcap + 63) / 64 * 64;
+        p.lds_k = (size_t)p.sel_cap * 4 * (ANYK_THREADS / ICPMI_WAVE);
+        p.per_cloud = 2048 / n_sel;
+        p.per_cloud = p.per_cloud < 1 ? 1 : (p.per_cloud > 256 ? 256 : p.per_cloud);
+    }
+    return p;
+}
+
 }  // namespace icpmi
 
 // the buffer (PreparedView, prep_common.hpp) + the scratch for the sort of clouds above 4096 rows (max_n = rows of the
@@ -354,76 +450,31 @@ extern "C" int icpmi_prepare_targets_ex(const double* pts, const int32_t* off_de
                                         int32_t allow_polar, void* stream) {
     using namespace icpmi;
     if (!pts || !off_dev || !prepared || n_sel < 0 || n_clouds < 0 || total_rows < 0 || max_n < 0) return ICPMI_ERR_ARG;
-    if (normal_k > 31 && (size_t)(normal_k + 1) * 4 * (ANYK_THREADS / ICPMI_WAVE) > 96 * 1024) return ICPMI_ERR_UNSUPPORTED;   // k beyond 6 143
-    if (prepared_bytes < icpmi_prepared_bytes(total_rows, n_clouds, max_n)) return ICPMI_ERR_WORKSPACE;
-    if (max_n > PREP_MAX_POINTS && !off_host) return ICPMI_ERR_ARG;       // sizes are needed on the host to route big clouds
-    if (cloud_ids && max_n > PREP_MAX_POINTS && !cloud_ids_host) return ICPMI_ERR_ARG;
-    if (n_sel == 0 || max_n == 0) return ICPMI_OK;
+    const PrepPlan plan = plan_prepare(off_host, cloud_ids, cloud_ids_host, n_sel, n_clouds, max_n, normal_k, prepared_bytes,
+                                       icpmi_prepared_bytes(total_rows, n_clouds, max_n), allow_polar, option("POLAR"), option("PREP_KNN"));
+    if (plan.rc != ICPMI_OK) return plan.rc;
     hipStream_t st = (hipStream_t)stream;
     const PreparedView v(prepared, total_rows, n_clouds);
-    // clouds above the LDS capacity: one by one through global memory (prep_big.hip)
-    int small_max = max_n;
-    if (max_n > PREP_MAX_POINTS) {
-        void* scratch = (unsigned char*)prepared + v.core_bytes;
-        const size_t scratch_bytes = prepared_bytes - v.core_bytes;
-        small_max = 0;
-        for (int i = 0; i < n_sel; ++i) {
-            const int c = cloud_ids ? cloud_ids_host[i] : i;
-            if (c < 0 || c >= n_clouds) return ICPMI_ERR_ARG;
-            const int n = off_host[c + 1] - off_host[c];
-            if (n <= PREP_MAX_POINTS) { small_max = n > small_max ? n : small_max; continue; }
-            const size_t o = (size_t)off_host[c];
-            const int rc = prep_big_cloud(pts + o * 2, cnt_dev ? cnt_dev + c : nullptr, n, normal_k > 31 ? -1 : normal_k, v.sxy + o, v.snrm + o,
-                                          v.sorig + o, v.dir + c, out_normals ? out_normals + o * 2 : nullptr, scratch,
-                                          scratch_bytes, st);
-            if (rc != ICPMI_OK) return rc;
-        }
-        if (small_max == 0 && normal_k <= 31) return ICPMI_OK;
+    void* scratch = (unsigned char*)prepared + v.core_bytes;
+    for (const int32_t c : plan.big) {
+        const size_t o = (size_t)off_host[c];
+        const int rc = prep_big_cloud(pts + o * 2, cnt_dev ? cnt_dev + c : nullptr, off_host[c + 1] - off_host[c], normal_k > 31 ? -1 : normal_k,
+                                      v.sxy + o, v.snrm + o, v.sorig + o, v.dir + c, out_normals ? out_normals + o * 2 : nullptr, scratch,
+                                      prepared_bytes - v.core_bytes, st);
+        if (rc != ICPMI_OK) return rc;
     }
-    int npad = 64;
-    while (npad < small_max) npad <<= 1;
-    // sorted copy: 20 B per point, sized to the largest cloud (rounded to 64); sort scratch: 12 B per padded slot.
-    // With ~1 500-point clouds this is 53 KB instead of 64 KB: three workgroups per CU instead of two.
-    const int lds_points = (small_max + 63) / 64 * 64;
-    const size_t sort_bytes = npad <= 4 * PREP_THREADS ? (size_t)(npad > PREP_THREADS ? npad : PREP_THREADS) * 20 : (size_t)npad * 12;
-    const size_t lds_sep = (size_t)lds_points * 24 + sort_bytes;                            // grid instantiation
-    const size_t lds_alias = (size_t)lds_points * 24 > sort_bytes ? (size_t)lds_points * 24 : sort_bytes;
-    // bearing order (sweep.hpp, SWEEP_POLAR) only where every consumer understands it: on request, and only when EVERY
-    // selected cloud has at most 2 048 rows — the fused ICP launch picks ONE instantiation for the whole batch from the
-    // same max_n, and the ones for larger targets (no float32 images) cannot walk a bearing order: a batch that mixes
-    // scans with one rolling submap therefore sorts everything along projections.  Option "POLAR": 0 never, 2 always
-    // (tests).
-    int polar = allow_polar && max_n <= 2048 ? 1 : 0;
-    if (const char* env = option("POLAR")) polar = polar ? (env[0] == '0' ? 0 : (env[0] == '2' ? 2 : 1)) : 0;
-    int split = 256 / n_sel;                 // a workgroup for every CU when the batch is small
-    split = split < 1 ? 1 : (split > 16 ? 16 : split);
-    // k-NN search of the normals: grid for few clouds that will be sorted along a projection (a wall across the sweep axis
-    // puts hundreds of points into a window, and a small launch lasts as long as its longest search), sweep otherwise —
-    // in bearing order a scan's windows are short everywhere (round 4, one 2 048-beam scan, k = 12: sweep 0.037 ms, grid
-    // 0.076; 64 scans: 0.050 / 0.115).  Where the bearing order is allowed the device may still pick a projection for a
-    // cloud that is no scan: the sweep is then slower, never wrong.  Option PREP_KNN = grid | sweep forces one of the two
-    // (tests run both on the same inputs)
-    int use_grid = split > 1 && !polar;
-    if (const char* env = option("PREP_KNN")) use_grid = env[0] == 'g' ? 1 : (env[0] == 's' ? 0 : use_grid);
-    const PrepChoice pc = prep_choice(normal_k, use_grid);
-    if (small_max > 0) {
-        const size_t lds = pc.grid ? lds_sep : lds_alias;
-        const int parts = pc.kk > 0 ? split : 1;
-        if (dyn_lds((const void*)pc.kernel, lds) != hipSuccess) return ICPMI_ERR_HIP;
-        pc.kernel<<<n_sel * parts, PREP_THREADS, lds, st>>>(pts, off_dev, cnt_dev, cloud_ids, normal_k, v.sxy, v.snrm, v.sorig, v.skey,
-                                                            v.dir, out_normals, lds_points, parts, polar);
+    if (plan.sel_rc != ICPMI_OK) return plan.sel_rc;
+    if (!plan.grid && !plan.per_cloud) return ICPMI_OK;
+    if (plan.grid) {
+        if (dyn_lds((const void*)plan.pc.kernel, plan.lds) != hipSuccess) return ICPMI_ERR_HIP;
+        plan.pc.kernel<<<plan.grid, PREP_THREADS, plan.lds, st>>>(pts, off_dev, cnt_dev, cloud_ids, normal_k, v.sxy, v.snrm, v.sorig, v.skey,
+                                                                  v.dir, out_normals, plan.lds_points, plan.parts, plan.polar);
     }
-    if (normal_k > 31) {
+    if (plan.per_cloud) {
         ICPMI_LAUNCH_CHECK();
-        // the list of a query: k + 1 positions, at most the largest cloud
-        const int kcap = normal_k + 1 < max_n ? normal_k + 1 : max_n;
-        const int sel_cap = (kcap + 63) / 64 * 64;
-        const size_t lds_k = (size_t)sel_cap * 4 * (ANYK_THREADS / ICPMI_WAVE);
-        if (dyn_lds((const void*)normals_anyk_kernel, lds_k) != hipSuccess) return ICPMI_ERR_HIP;
-        int per_cloud = 2048 / n_sel;
-        per_cloud = per_cloud < 1 ? 1 : (per_cloud > 256 ? 256 : per_cloud);
-        normals_anyk_kernel<<<dim3(per_cloud, n_sel), ANYK_THREADS, lds_k, st>>>(off_dev, cnt_dev, cloud_ids, normal_k, v.sxy, v.snrm, v.sorig,
-                                                                                  v.dir, out_normals, sel_cap);
+        if (dyn_lds((const void*)normals_anyk_kernel, plan.lds_k) != hipSuccess) return ICPMI_ERR_HIP;
+        normals_anyk_kernel<<<dim3(plan.per_cloud, n_sel), ANYK_THREADS, plan.lds_k, st>>>(off_dev, cnt_dev, cloud_ids, normal_k, v.sxy, v.snrm,
+                                                                                           v.sorig, v.dir, out_normals, plan.sel_cap);
     }
     ICPMI_LAUNCH_CHECK();
     return ICPMI_OK;

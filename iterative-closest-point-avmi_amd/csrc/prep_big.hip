@@ -54,8 +54,6 @@ __global__ __launch_bounds__(256) void big_normals_kernel(
     prep_normals<KK>(sxy, sorig, M, s0, min(M, s0 + 256), *dir_c, kk, o_snrm, o_rows);
 }
 
-size_t radix_temp_bytes(int n);                              // voxel.hip: the same sort of (uint64 key, uint32 row) pairs
-
 // scratch of one large cloud: keys, twice | rows, twice | temporary storage of the sort
 struct PrepBigWs {
     Carve c;

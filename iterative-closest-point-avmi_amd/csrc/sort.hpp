@@ -4,6 +4,22 @@
 
 namespace icpmi {
 
+// Slots of a sort of n elements: the smallest power of two >= max(n, 64).
+__host__ __device__ __forceinline__ int sort_npad(int n) { int npad = 64; while (npad < n) npad <<= 1; return npad; }
+
+// LDS area of a (key, row) pair sort, stated once: npad uint64 keys, then npad uint32 rows — 12 B per slot.  The kernel
+// takes its pointers from here (over the area's first byte), the launcher its size.
+struct PairSortLds {
+    size_t rows_at, bytes;
+    __host__ __device__ explicit PairSortLds(int npad)
+        : rows_at((size_t)npad * sizeof(uint64_t)), bytes((size_t)npad * (sizeof(uint64_t) + sizeof(uint32_t))) {}
+    __device__ uint64_t* keys(unsigned char* base) const { return reinterpret_cast<uint64_t*>(base); }
+    __device__ uint32_t* rows(unsigned char* base) const { return reinterpret_cast<uint32_t*>(base + rows_at); }
+};
+
+// temporary storage of rocPRIM's radix sort of n (uint64 key, uint32 row) pairs (voxel.hip; prep_big.hip sorts the same pairs)
+size_t radix_temp_bytes(int n);
+
 // Sorts npad (power of two) pairs ascending by (key, row).  Rows are unique, so
 // the order is total and equals a stable sort by key.  Pad with key = ~0,
 // row = ~0.  Ends with a barrier.
@@ -39,67 +55,20 @@ __device__ __forceinline__ void bitonic_sort_packed(T* v, int npad) {
         }
 }
 
-// The same network with the elements in REGISTERS: thread t owns elements t*E .. t*E + E-1 (npad = E * blockDim.x).
-// Strides below E are compare-exchanges between a thread's own registers, strides below 64 E exchange with a lane of
-// the same wave (one cross-lane move per element, no index arithmetic, no barrier), only the few strides beyond that
-// go through LDS.  The sorts of the voxel filter and of the prepare kernel are bound by their vector instructions,
-// and this form needs about half of them (2 048 elements on 512 threads: 21 + 39 of the 66 stages never touch
-// LDS).  v: packed values (key << row_bits | row), all ones = padding; lds: npad elements of scratch.
-template <typename T, int E>
-__device__ __forceinline__ void bitonic_sort_regs(T (&v)[E], T* lds) {
-    const int npad = E * (int)blockDim.x;
-    const int base = (int)threadIdx.x * E, lane = lane_id();
-    for (int k = 2; k <= npad; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            if (j < E) {
-#pragma unroll
-                for (int e = 0; e < E; ++e)
-                    if ((e & j) == 0 && (e | j) < E) {
-                        const bool asc = ((base + e) & k) == 0;
-                        const T a = v[e], b = v[e | j];
-                        const bool sw = (a > b) == asc;
-                        v[e] = sw ? b : a;
-                        v[e | j] = sw ? a : b;
-                    }
-            } else if (j < E * ICPMI_WAVE) {
-                const int m = j / E;                                    // partner lane = lane ^ m
-                const bool lower = (lane & m) == 0;
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    const T o = __shfl_xor(v[e], m, ICPMI_WAVE);
-                    const bool asc = ((base + e) & k) == 0;
-                    const bool keep_min = asc == lower;
-                    const T lo = v[e] < o ? v[e] : o, hi = v[e] < o ? o : v[e];
-                    v[e] = keep_min ? lo : hi;
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < E; ++e) lds[base + e] = v[e];
-                __syncthreads();
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    const int i = base + e;
-                    const T o = lds[i ^ j];
-                    const bool keep_min = ((i & k) == 0) == ((i & j) == 0);
-                    const T lo = v[e] < o ? v[e] : o, hi = v[e] < o ? o : v[e];
-                    v[e] = keep_min ? lo : hi;
-                }
-                __syncthreads();
-            }
-        }
-}
-
 // ── the register network, every stage fixed at compile time (round 4) ────────────────────────────────
-// bitonic_sort_regs above walks (k, j) in run-time loops: every stage recomputes partner lanes, directions and LDS
-// addresses and goes through ds_bpermute — measured (round 4): the sort is half of the voxel filter (0.70 of 1.41 ms for
-// 32 768 scans) at ~18 vector instructions per element and stage.  Here the network is the FLIP form of the bitonic sort
-// (level k: one stage against the mirror image inside each k-block, i <-> i ^ (k - 1), then strides k/4 .. 1 as i <-> i ^ j;
-// every compare-exchange puts the minimum at the lower index: no direction bit), unrolled by templates, so that each stage
-// is: its partner through the cheapest cross-lane move that reaches it — a DPP quad permutation or row (half) mirror /
-// rotation, ds_swizzle inside 32 lanes, ds_bpermute across the halves of the wave (addresses computed once) —, one
-// v_min, one v_max, one select on a lane mask that is a constant of the stage.  Strides inside a thread are plain
-// min / max pairs; the strides that cross waves (6 of the 66 stages of 2 048 elements on 512 threads) go through LDS as
-// before.  Same result as any sorting network on distinct elements (the packed values are distinct: the row is part of them).
+// The network with the elements in REGISTERS: thread t owns elements t*E .. t*E + E-1 (NPAD = E * THREADS).  Strides below E
+// are compare-exchanges between a thread's own registers, strides below 64 E exchange with a lane of the same wave (one
+// cross-lane move per element, no barrier), only the few strides beyond that go through LDS.  The sorts of the voxel filter
+// and of the prepare kernel are bound by their vector instructions, and this form needs about half of them (2 048 elements
+// on 512 threads: 21 + 39 of the 66 stages never touch LDS).  The network is the FLIP form of the bitonic sort (level k:
+// one stage against the mirror image inside each k-block, i <-> i ^ (k - 1), then strides k/4 .. 1 as i <-> i ^ j; every
+// compare-exchange puts the minimum at the lower index: no direction bit), unrolled by templates (walked in run-time loops
+// it took ~18 vector instructions per element and stage, DESIGN K5), so that each stage is: its partner through the
+// cheapest cross-lane move that reaches it — a DPP quad permutation or row (half) mirror / rotation, ds_swizzle inside 32
+// lanes, ds_bpermute across the halves of the wave (addresses computed once) —, one v_min, one v_max, one select on a lane
+// mask that is a constant of the stage.  Strides inside a thread are plain min / max pairs; the strides that cross waves
+// (6 of the 66 stages of 2 048 elements on 512 threads) go through LDS.  Same result as any sorting network on distinct
+// elements (the packed values are distinct: the row is part of them).
 template <int CTRL>
 __device__ __forceinline__ uint32_t sort_dpp(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);

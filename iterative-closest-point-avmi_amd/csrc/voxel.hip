@@ -24,15 +24,37 @@ constexpr int VOX_THREADS = 1024;   // upper bound; the launcher picks 512 for l
 constexpr int VOX_MAXW = VOX_THREADS / ICPMI_WAVE;
 constexpr int VOX_SMALL_MAX = 8192;
 
-__device__ __forceinline__ uint64_t vox_key(const double* p, int dim, const double* mn, const double* ext, double voxel) {
+template <int DIM>
+__device__ __forceinline__ uint64_t vox_key(const double* p, const double* mn, const double* ext, double voxel) {
     // floor((p - min) / voxel).astype(int), linearised so that integer order ==
     // lexicographic order of the per-axis keys
     uint64_t k = 0;
-    for (int d = 0; d < dim; ++d) {
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) {
         const int64_t kd = (int64_t)floor((p[d] - mn[d]) / voxel);
         k = k * (uint64_t)ext[d] + (uint64_t)kd;
     }
     return k;
+}
+
+// Per-thread min / max per axis -> the workgroup's, in every thread: wave reduction, one slot per wave and bound in
+// `scratch` (6 * VOX_MAXW doubles of LDS), ONE barrier, the wave slots combined (NW of them; 0: as many as the workgroup
+// has).  The caller orders earlier uses of `scratch` before the call.
+template <int DIM, int NW>
+__device__ __forceinline__ void bounds_combine(double (&mn)[3], double (&mx)[3], double* scratch) {
+    const int nw = NW ? NW : blockDim.x / ICPMI_WAVE;
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) { mn[d] = wave_min(mn[d]); mx[d] = wave_max(mx[d]); }
+    if (lane_id() == 0)
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) { scratch[d * VOX_MAXW + wave_id()] = mn[d]; scratch[(3 + d) * VOX_MAXW + wave_id()] = mx[d]; }
+    __syncthreads();
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) {
+        double a = __builtin_inf(), b = -__builtin_inf();
+        for (int k = 0; k < nw; ++k) { a = fmin(a, scratch[d * VOX_MAXW + k]); b = fmax(b, scratch[(3 + d) * VOX_MAXW + k]); }
+        mn[d] = a; mx[d] = b;
+    }
 }
 
 // min / max over the rows of one cloud, result in every thread
@@ -46,20 +68,8 @@ __device__ __forceinline__ void cloud_bounds(const double* pts, int n, double (&
             mn[d] = fmin(mn[d], v);
             mx[d] = fmax(mx[d], v);
         }
-    const int w = wave_id(), l = lane_id(), nw = blockDim.x / ICPMI_WAVE;
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) { mn[d] = wave_min(mn[d]); mx[d] = wave_max(mx[d]); }
-    __syncthreads();
-    if (l == 0)
-#pragma unroll
-        for (int d = 0; d < DIM; ++d) { scratch[d * VOX_MAXW + w] = mn[d]; scratch[(3 + d) * VOX_MAXW + w] = mx[d]; }
-    __syncthreads();
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) {
-        double a = __builtin_inf(), b = -__builtin_inf();
-        for (int k = 0; k < nw; ++k) { a = fmin(a, scratch[d * VOX_MAXW + k]); b = fmax(b, scratch[(3 + d) * VOX_MAXW + k]); }
-        mn[d] = a; mx[d] = b;
-    }
+    __syncthreads();                                          // whoever used `scratch` before is done with it
+    bounds_combine<DIM, 0>(mn, mx, scratch);
 }
 
 // key extents; returns false when the linear key would not fit in 63 bits
@@ -76,6 +86,18 @@ __device__ __forceinline__ bool key_extents(const double (&mn)[3], const double 
         prod *= e;
     }
     return ok && prod < 9.0e18;
+}
+
+// (key, row) as ONE integer key << row_bits | row: row_bits = bits of a row below npad; returns the bound of the packed values
+// (keys are below the product of the extents).  Below 4e9 they sort as 32-bit words, below 9e18 as 64-bit ones, else as pairs.
+template <int DIM>
+__device__ __forceinline__ double vox_packed_range(const double (&ext)[3], int npad, int& row_bits) {
+    row_bits = 6;
+    while ((1 << row_bits) < npad) ++row_bits;
+    double cells = 1.0;
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) cells *= ext[d];
+    return cells * (double)npad;
 }
 
 // Exclusive prefix sum of one int per thread over the workgroup; `total` gets
@@ -97,6 +119,26 @@ __device__ __forceinline__ int block_exscan(int v, int* scratch, int& total) {
     return base + inc - v;
 }
 
+// Mean of the voxel whose run of equal keys starts at sorted position r: the sum over its rows in order (rows ascending ==
+// input order, as np.bincount adds them), divided by their count.
+template <int DIM>
+__device__ __forceinline__ void run_mean(const uint64_t* keys, const uint32_t* rows, int r, int n,
+                                         const double* __restrict__ pts, double* __restrict__ mean) {
+    const uint64_t k = keys[r];
+    double s[DIM];
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) s[d] = 0.0;
+    int q = r;
+    for (; q < n && keys[q] == k; ++q) {
+        const double* p = pts + (size_t)rows[q] * DIM;
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) s[d] += p[d];
+    }
+    const double c = (double)(q - r);
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) mean[d] = s[d] / c;
+}
+
 // After the sort: voxel boundaries, voxel ids, in-order sums, means.
 // keys/rows are sorted by (key, row); thread t owns sorted positions
 // [t*ipt, (t+1)*ipt).  Works on LDS or global arrays (generic pointers).
@@ -112,19 +154,7 @@ __device__ __forceinline__ void voxel_finish(const uint64_t* keys, const uint32_
     int vid = block_exscan(heads, iscratch, total);
     for (int r = lo; r < hi; ++r) {
         if (!(r == 0 || keys[r] != keys[r - 1])) continue;
-        const uint64_t k = keys[r];
-        double s[DIM];
-#pragma unroll
-        for (int d = 0; d < DIM; ++d) s[d] = 0.0;
-        int q = r;
-        for (; q < n && keys[q] == k; ++q) {                 // rows ascending == input order
-            const double* p = pts + (size_t)rows[q] * DIM;
-#pragma unroll
-            for (int d = 0; d < DIM; ++d) s[d] += p[d];
-        }
-        const double c = (double)(q - r);
-#pragma unroll
-        for (int d = 0; d < DIM; ++d) out[(size_t)vid * DIM + d] = s[d] / c;
+        run_mean<DIM>(keys, rows, r, n, pts, out + (size_t)vid * DIM);
         ++vid;
     }
     if (threadIdx.x == 0) *out_cnt = total;
@@ -150,7 +180,6 @@ template <int DIM, int E, int THREADS>
 __device__ __forceinline__ bool voxel_small_regs(const double* __restrict__ P, double* __restrict__ O, int n, double voxel,
                                                  uint32_t* sorted, double* dscratch, int* iscratch, int32_t* out_cnt) {
     constexpr uint32_t PAD = 0xffffffffu;
-    constexpr int NW = THREADS / ICPMI_WAVE;
     const int tid = (int)threadIdx.x;
     // the thread's rows e THREADS + t (coalesced; any start order sorts the same) stay in registers from the bounds to the keys
     double raw[E][DIM];
@@ -166,26 +195,10 @@ __device__ __forceinline__ bool voxel_small_regs(const double* __restrict__ P, d
             if (i < n) { mn[d] = fmin(mn[d], raw[e][d]); mx[d] = fmax(mx[d], raw[e][d]); }
         }
     }
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) { mn[d] = wave_min(mn[d]); mx[d] = wave_max(mx[d]); }
-    if (lane_id() == 0)
-#pragma unroll
-        for (int d = 0; d < DIM; ++d) { dscratch[d * VOX_MAXW + wave_id()] = mn[d]; dscratch[(3 + d) * VOX_MAXW + wave_id()] = mx[d]; }
-    __syncthreads();
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) {
-        double a = __builtin_inf(), b = -__builtin_inf();
-#pragma unroll
-        for (int k = 0; k < NW; ++k) { a = fmin(a, dscratch[d * VOX_MAXW + k]); b = fmax(b, dscratch[(3 + d) * VOX_MAXW + k]); }
-        mn[d] = a; mx[d] = b;
-    }
+    bounds_combine<DIM, THREADS / ICPMI_WAVE>(mn, mx, dscratch);    // (dscratch is untouched so far: no barrier in front)
     if (!key_extents<DIM>(mn, mx, voxel, extd)) { if (tid == 0) *out_cnt = -1; return true; }
-    int row_bits = 6;
-    while ((1 << row_bits) < E * THREADS) ++row_bits;
-    double cells = 1.0;
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) cells *= extd[d];
-    if (!(cells * (double)(E * THREADS) < 4.0e9)) return false;     // (uniform: every thread holds the same bounds)
+    int row_bits;
+    if (!(vox_packed_range<DIM>(extd, E * THREADS, row_bits) < 4.0e9)) return false;     // (uniform: every thread holds the same bounds)
     const uint32_t ext[3] = {(uint32_t)extd[0], (uint32_t)extd[1], (uint32_t)extd[2]};
     const uint32_t row_mask = (1u << row_bits) - 1u;
     uint32_t v[E];
@@ -254,6 +267,24 @@ __device__ __forceinline__ bool voxel_small_regs(const double* __restrict__ P, d
     return true;
 }
 
+// The packed fallbacks: key << row_bits | row of every slot into `pk` (all ones = padding), sorted there as words of type
+// T, unpacked into keys / rows (pk may be either of them: a slot is read before it is written, by the same thread).
+template <typename T, int DIM>
+__device__ __forceinline__ void sort_packed_keys(T* pk, uint64_t* keys, uint32_t* rows, int n, int npad, int row_bits,
+                                                 const double* __restrict__ P, const double (&mn)[3], const double (&ext)[3], double voxel) {
+    constexpr T PAD = ~(T)0;
+    for (int i = threadIdx.x; i < npad; i += blockDim.x)
+        pk[i] = i < n ? (T)(vox_key<DIM>(P + (size_t)i * DIM, mn, ext, voxel) << row_bits) | (T)i : PAD;
+    __syncthreads();
+    bitonic_sort_packed<T>(pk, npad);
+    for (int i = threadIdx.x; i < npad; i += blockDim.x) {
+        const T v = pk[i];
+        keys[i] = v == PAD ? ~0ull : (uint64_t)(v >> row_bits);
+        rows[i] = v == PAD ? 0xffffffffu : (uint32_t)(v & (((T)1 << row_bits) - (T)1));
+    }
+    __syncthreads();
+}
+
 // ── small path: one workgroup per cloud, everything in LDS ─────────────────
 template <int DIM>
 __global__ __launch_bounds__(VOX_THREADS) void voxel_small_kernel(
@@ -268,13 +299,14 @@ __global__ __launch_bounds__(VOX_THREADS) void voxel_small_kernel(
     if (n <= 0) { if (threadIdx.x == 0) out_cnt[c] = 0; return; }
     const double* P = pts + (size_t)off[c] * DIM;
     double* O = out_pts + (size_t)off[c] * DIM;
-    int npad = 64;
-    while (npad < n) npad <<= 1;
-    uint64_t* keys = reinterpret_cast<uint64_t*>(dyn);
-    uint32_t* rows = reinterpret_cast<uint32_t*>(dyn + (size_t)npad * sizeof(uint64_t));
+    const int npad = sort_npad(n);
+    const PairSortLds lds(npad);
+    uint64_t* keys = lds.keys(dyn);
+    uint32_t* rows = lds.rows(dyn);
 
     if ((npad == 4 * (int)blockDim.x || npad == 2 * (int)blockDim.x) && (blockDim.x == 512 || blockDim.x == 1024)) {
-        uint32_t* sorted = reinterpret_cast<uint32_t*>(dyn);             // npad + 1 words
+        // the usual shape (a 2 048-beam scan on 512 or 1 024 threads): the network runs on registers (sort.hpp)
+        uint32_t* sorted = reinterpret_cast<uint32_t*>(keys);            // npad + 1 words, in the key array
         bool done;
         if (blockDim.x == 512) {
             if (npad == 2048) done = voxel_small_regs<DIM, 4, 512>(P, O, n, voxel, sorted, dscratch, iscratch, out_cnt + c);
@@ -283,7 +315,7 @@ __global__ __launch_bounds__(VOX_THREADS) void voxel_small_kernel(
             if (npad == 4096) done = voxel_small_regs<DIM, 4, 1024>(P, O, n, voxel, sorted, dscratch, iscratch, out_cnt + c);
             else done = voxel_small_regs<DIM, 2, 1024>(P, O, n, voxel, sorted, dscratch, iscratch, out_cnt + c);
         }
-        if (done) return;
+        if (done) return;                                                // else: key and row need more than 32 bits
         __syncthreads();                                                 // dscratch is written again below
     }
     double mn[3], mx[3], ext[3];
@@ -291,70 +323,15 @@ __global__ __launch_bounds__(VOX_THREADS) void voxel_small_kernel(
     if (!key_extents<DIM>(mn, mx, voxel, ext)) { if (threadIdx.x == 0) out_cnt[c] = -1; return; }
     // (key, row) sorts as ONE integer key << row_bits | row when that fits: the sort is bound by LDS traffic,
     // and a 2 048-beam scan in a room needs ~18 + 11 bits
-    int row_bits = 6;
-    while ((1 << row_bits) < npad) ++row_bits;
-    double cells = 1.0;
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) cells *= ext[d];                      // keys are below this product
-    const double packed_range = cells * (double)npad;                   // packed values are below this
+    int row_bits;
+    const double packed_range = vox_packed_range<DIM>(ext, npad, row_bits);
     if (packed_range < 4.0e9) {
-        uint32_t* pk = rows;                                             // sorted in the row array, unpacked in place
-        if (npad == 4 * (int)blockDim.x || npad == 2 * (int)blockDim.x) {
-            // the usual shape (a 2 048-beam scan on 512 or 1 024 threads): the network runs on registers (sort.hpp)
-            auto packed = [&](int i) {
-                return i < n ? (uint32_t)(vox_key(P + (size_t)i * DIM, DIM, mn, ext, voxel) << row_bits) | (uint32_t)i : 0xffffffffu;
-            };
-            auto unpack = [&](int i, uint32_t v) {
-                keys[i] = v == 0xffffffffu ? ~0ull : (uint64_t)(v >> row_bits);
-                rows[i] = v == 0xffffffffu ? 0xffffffffu : (v & ((1u << row_bits) - 1u));
-            };
-            uint32_t* scratch = reinterpret_cast<uint32_t*>(keys);          // the key array is free until the unpacking
-            if (npad == 4 * (int)blockDim.x) {
-                uint32_t v[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = packed((int)threadIdx.x * 4 + e);
-                if (blockDim.x == 512) bitonic_sort_regs_fixed<uint32_t, 4, 512>(v, scratch);
-                else bitonic_sort_regs_fixed<uint32_t, 4, 1024>(v, scratch);
-                __syncthreads();                                            // scratch reads of the last LDS stage are done
-#pragma unroll
-                for (int e = 0; e < 4; ++e) unpack((int)threadIdx.x * 4 + e, v[e]);
-            } else {
-                uint32_t v[2];
-#pragma unroll
-                for (int e = 0; e < 2; ++e) v[e] = packed((int)threadIdx.x * 2 + e);
-                if (blockDim.x == 512) bitonic_sort_regs_fixed<uint32_t, 2, 512>(v, scratch);
-                else bitonic_sort_regs_fixed<uint32_t, 2, 1024>(v, scratch);
-                __syncthreads();
-#pragma unroll
-                for (int e = 0; e < 2; ++e) unpack((int)threadIdx.x * 2 + e, v[e]);
-            }
-            __syncthreads();
-        } else {
-        for (int i = threadIdx.x; i < npad; i += blockDim.x)
-            pk[i] = i < n ? (uint32_t)(vox_key(P + (size_t)i * DIM, DIM, mn, ext, voxel) << row_bits) | (uint32_t)i : 0xffffffffu;
-        __syncthreads();
-        bitonic_sort_packed<uint32_t>(pk, npad);
-        for (int i = threadIdx.x; i < npad; i += blockDim.x) {
-            const uint32_t v = pk[i];
-            keys[i] = v == 0xffffffffu ? ~0ull : (uint64_t)(v >> row_bits);
-            rows[i] = v == 0xffffffffu ? 0xffffffffu : (v & ((1u << row_bits) - 1u));
-        }
-        __syncthreads();
-        }
+        sort_packed_keys<uint32_t, DIM>(rows, keys, rows, n, npad, row_bits, P, mn, ext, voxel);   // in the row array, unpacked in place
     } else if (packed_range < 9.0e18) {
-        for (int i = threadIdx.x; i < npad; i += blockDim.x)
-            keys[i] = i < n ? (vox_key(P + (size_t)i * DIM, DIM, mn, ext, voxel) << row_bits) | (uint64_t)i : ~0ull;
-        __syncthreads();
-        bitonic_sort_packed<uint64_t>(keys, npad);
-        for (int i = threadIdx.x; i < npad; i += blockDim.x) {
-            const uint64_t v = keys[i];
-            keys[i] = v == ~0ull ? ~0ull : (v >> row_bits);
-            rows[i] = v == ~0ull ? 0xffffffffu : (uint32_t)(v & ((1ull << row_bits) - 1ull));
-        }
-        __syncthreads();
+        sort_packed_keys<uint64_t, DIM>(keys, keys, rows, n, npad, row_bits, P, mn, ext, voxel);   // in the key array
     } else {
         for (int i = threadIdx.x; i < npad; i += blockDim.x) {
-            keys[i] = i < n ? vox_key(P + (size_t)i * DIM, DIM, mn, ext, voxel) : ~0ull;
+            keys[i] = i < n ? vox_key<DIM>(P + (size_t)i * DIM, mn, ext, voxel) : ~0ull;
             rows[i] = i < n ? (uint32_t)i : 0xffffffffu;
         }
         __syncthreads();
@@ -411,7 +388,7 @@ __global__ void vox_keys_kernel(const double* __restrict__ P, int n, double voxe
     if (i >= n) return;
     double mn[3], ext[3];
     const bool ok = vox_header<DIM>(b, voxel, mn, ext);
-    keys[i] = ok ? vox_key(P + (size_t)i * DIM, DIM, mn, ext, voxel) : 0ull;
+    keys[i] = ok ? vox_key<DIM>(P + (size_t)i * DIM, mn, ext, voxel) : 0ull;
     rows[i] = (uint32_t)i;
 }
 
@@ -433,22 +410,10 @@ __global__ void vox_means_kernel(const uint64_t* __restrict__ keys, const uint32
     const bool ok = vox_header<DIM>(b, voxel, mn, ext);
     if (r == n - 1) *out_cnt = ok ? (int32_t)(vid[r] + heads[r]) : -1;
     if (!ok || !heads[r]) return;
-    const uint64_t k = keys[r];
-    double s[DIM];
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) s[d] = 0.0;
-    int q = r;
-    for (; q < n && keys[q] == k; ++q) {                     // rows ascending == input order
-        const double* p = P + (size_t)rows[q] * DIM;
-#pragma unroll
-        for (int d = 0; d < DIM; ++d) s[d] += p[d];
-    }
-    const double c = (double)(q - r);
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) O[(size_t)vid[r] * DIM + d] = s[d] / c;
+    run_mean<DIM>(keys, rows, r, n, P, O + (size_t)vid[r] * DIM);
 }
 
-size_t radix_temp_bytes(int n) {                             // (also prep_big.hip)
+size_t radix_temp_bytes(int n) {                             // (sort.hpp; also prep_big.hip)
     size_t bytes = 0;
     uint64_t* k = nullptr;
     uint32_t* v = nullptr;
@@ -494,6 +459,46 @@ static int voxel_big(const double* P, int n, double voxel, double* O, int32_t* o
     return ICPMI_OK;
 }
 
+// What a batch call starts, decided from its arguments and the host mirror of the offsets (no HIP call).
+struct VoxPlan {
+    int rc;            // ICPMI_OK, or why nothing is launched
+    int threads;       // of the one launch of voxel_small_kernel over the whole set; 0: no cloud has at most VOX_SMALL_MAX rows
+    size_t lds;        // ... with the pair-sort area of the largest such cloud
+    int n_big;         // clouds above VOX_SMALL_MAX rows: one by one through voxel_big
+};
+static VoxPlan plan_voxel(const int32_t* off_host, int n_clouds, int dim, double voxel_size) {
+    VoxPlan p{ICPMI_ERR_ARG, 0, 0, 0};
+    if (n_clouds < 0 || (dim != 2 && dim != 3) || !(voxel_size > 0.0)) return p;
+    int max_small = 0, total_rows;
+    if (n_clouds > 0 && !cloud_rows(off_host, n_clouds, max_small, total_rows, VOX_SMALL_MAX, &p.n_big)) return p;
+    p.rc = ICPMI_OK;
+    // The kernel is a chain of latency-bound phases (two passes over the points, 66 sort stages, a gather): with
+    // many clouds, four 512-thread workgroups per CU overlap them better than two of 1 024 (2.17 -> 1.55 ms for
+    // 32 768 clouds); a lone cloud finishes sooner with 1 024 threads.
+    p.threads = p.n_big == n_clouds ? 0 : (n_clouds > 256 ? 512 : VOX_THREADS);
+    p.lds = PairSortLds(sort_npad(max_small)).bytes;
+    return p;
+}
+
+template <int DIM>
+static int voxel_launch(const VoxPlan& plan, const double* pts, const int32_t* off_dev, const int32_t* off_host, int n_clouds,
+                        double voxel, double* out_pts, int32_t* out_cnt, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    if (plan.threads) {
+        if (dyn_lds((const void*)voxel_small_kernel<DIM>, plan.lds) != hipSuccess) return ICPMI_ERR_HIP;
+        voxel_small_kernel<DIM><<<n_clouds, plan.threads, plan.lds, st>>>(pts, off_dev, voxel, out_pts, out_cnt);
+        ICPMI_LAUNCH_CHECK();
+    }
+    for (int c = 0; c < n_clouds && plan.n_big > 0; ++c) {
+        const int n = off_host[c + 1] - off_host[c];
+        if (n <= VOX_SMALL_MAX) continue;
+        if (!workspace) return ICPMI_ERR_WORKSPACE;
+        const size_t o = (size_t)off_host[c] * DIM;
+        const int rc = voxel_big<DIM>(pts + o, n, voxel, out_pts + o, out_cnt + c, workspace, workspace_bytes, st);
+        if (rc != ICPMI_OK) return rc;
+    }
+    return ICPMI_OK;
+}
+
 }  // namespace icpmi
 
 extern "C" size_t icpmi_voxel_workspace_bytes(int32_t max_n) {
@@ -508,41 +513,8 @@ extern "C" int icpmi_voxel_downsample_batch(const double* pts, const int32_t* of
                                             size_t workspace_bytes, void* stream) {
     using namespace icpmi;
     if (!pts || !off_dev || !off_host || !out_pts || !out_cnt) return ICPMI_ERR_ARG;
-    if (n_clouds < 0 || (dim != 2 && dim != 3) || !(voxel_size > 0.0)) return ICPMI_ERR_ARG;
-    if (n_clouds == 0) return ICPMI_OK;
-    hipStream_t st = (hipStream_t)stream;
-    int max_small = 0, n_big = 0;
-    for (int c = 0; c < n_clouds; ++c) {
-        const int n = off_host[c + 1] - off_host[c];
-        if (n < 0) return ICPMI_ERR_ARG;
-        if (n <= VOX_SMALL_MAX) max_small = n > max_small ? n : max_small; else ++n_big;
-    }
-    if (n_big < n_clouds) {
-        int npad = 64;
-        while (npad < max_small) npad <<= 1;
-        const size_t lds = (size_t)npad * 12;
-        // The kernel is a chain of latency-bound phases (two passes over the points, 66 sort stages, a gather): with
-        // many clouds, four 512-thread workgroups per CU overlap them better than two of 1 024 (2.17 -> 1.55 ms for
-        // 32 768 clouds); a lone cloud finishes sooner with 1 024 threads.
-        const int vox_threads = n_clouds > 256 ? 512 : VOX_THREADS;
-        if (dim == 2) {
-            if (dyn_lds((const void*)voxel_small_kernel<2>, lds) != hipSuccess) return ICPMI_ERR_HIP;
-            voxel_small_kernel<2><<<n_clouds, vox_threads, lds, st>>>(pts, off_dev, voxel_size, out_pts, out_cnt);
-        } else {
-            if (dyn_lds((const void*)voxel_small_kernel<3>, lds) != hipSuccess) return ICPMI_ERR_HIP;
-            voxel_small_kernel<3><<<n_clouds, vox_threads, lds, st>>>(pts, off_dev, voxel_size, out_pts, out_cnt);
-        }
-        ICPMI_LAUNCH_CHECK();
-    }
-    for (int c = 0; c < n_clouds && n_big > 0; ++c) {
-        const int n = off_host[c + 1] - off_host[c];
-        if (n <= VOX_SMALL_MAX) continue;
-        if (!workspace) return ICPMI_ERR_WORKSPACE;
-        const double* P = pts + (size_t)off_host[c] * dim;
-        double* O = out_pts + (size_t)off_host[c] * dim;
-        const int rc = dim == 2 ? voxel_big<2>(P, n, voxel_size, O, out_cnt + c, workspace, workspace_bytes, st)
-                                : voxel_big<3>(P, n, voxel_size, O, out_cnt + c, workspace, workspace_bytes, st);
-        if (rc != ICPMI_OK) return rc;
-    }
-    return ICPMI_OK;
+    const VoxPlan plan = plan_voxel(off_host, n_clouds, dim, voxel_size);
+    if (plan.rc != ICPMI_OK) return plan.rc;
+    return dim == 2 ? voxel_launch<2>(plan, pts, off_dev, off_host, n_clouds, voxel_size, out_pts, out_cnt, workspace, workspace_bytes, (hipStream_t)stream)
+                    : voxel_launch<3>(plan, pts, off_dev, off_host, n_clouds, voxel_size, out_pts, out_cnt, workspace, workspace_bytes, (hipStream_t)stream);
 }
