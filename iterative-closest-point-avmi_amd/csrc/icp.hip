@@ -183,14 +183,8 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_fused_kernel(IcpArgs a) {
                     block_sum<10, ICP_MAXW>(acc, redA);
                     if (has_corr && acc[9] < (double)need) { status = ICPMI_ST_FEW_INLIERS; break; }
                     double A[3][3] = {{acc[0], acc[1], acc[2]}, {acc[1], acc[3], acc[4]}, {acc[2], acc[4], acc[5]}};
-                    double rhs[3] = {acc[6], acc[7], acc[8]}, x[3];
-                    if (solve3(A, rhs, x)) {
-                        double st, ct;
-                        sincos_step(x[0], st, ct);                                  // icp.py:110-114
-                        r[0] = ct; r[1] = -st; r[2] = st; r[3] = ct; t[0] = x[1]; t[1] = x[2];
-                    } else {
-                        r[0] = 1.0; r[1] = 0.0; r[2] = 0.0; r[3] = 1.0; t[0] = 0.0; t[1] = 0.0;
-                    }
+                    double rhs[3] = {acc[6], acc[7], acc[8]};
+                    p2l_step_from_solution(A, rhs, r, t);                           // icp.py:106-114
                 }
             } else {
                 // ── point-to-point: centroids, then centred cross-covariance ─

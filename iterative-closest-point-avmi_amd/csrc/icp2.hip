@@ -55,25 +55,25 @@ struct Icp2Args {
     // together, instead of the last of them finishing alone at the end of one long launch.
     int it_begin, it_limit;   // iterations [it_begin, min(it_limit, max_iterations)) run here
     int resume;               // 1: the pairs are list[0 .. *list_count), their state comes from st_*
-    double2* st_xy;           // [pair][st_stride]: moving source rows of a parked pair
-    int32_t* st_pos;          //                    and the position of each row's match in the sorted target
-    int32_t* list;
-    int32_t* list_count;
-    int st_stride;
-    int32_t* wide_list;       // pairs the first launch leaves to the wider shape (when the caller gave a workspace): the second
-    int32_t* wide_count;      // launch walks this list instead of starting a workgroup per pair of the batch just to look
+    double2* st_xy = nullptr; // [pair][st_stride]: moving source rows of a parked pair
+    int32_t* st_pos = nullptr; //                   and the position of each row's match in the sorted target
+    int32_t* list = nullptr;
+    int32_t* list_count = nullptr;
+    int st_stride = 0;
+    int32_t* wide_list = nullptr;    // pairs the first launch leaves to the wider shape (when the caller gave a workspace): the second
+    int32_t* wide_count = nullptr;   // launch walks this list instead of starting a workgroup per pair of the batch just to look
     // Pairs that start FAR from their target (a candidate whose pre-alignment is wrong: every row metres from the nearest
     // wall) walk most of the sorted target in every search.  A first launch that finds the mean squared error of step 0
     // (the convergence test of iteration 1 has it anyway) above far_d2 parks the pair after iteration 1 (same state as
     // above) on far_list, and icp2_far_kernel continues it with searches that give up long walks for a box hierarchy
     // (sweep.hpp).  Same matches, same arithmetic: the pair's result does not depend on which kernel finished it.
-    int32_t* far_list;        // nullptr: never
-    int32_t* far_count;
-    double far_d2;            // +inf: never
+    int32_t* far_list = nullptr;     // nullptr: never
+    int32_t* far_count = nullptr;
+    double far_d2 = __builtin_inf(); // +inf: never
     // Stop after the first accepted candidate (icpmi_icp_batch_gated; gate.hint == nullptr: ungated).  The lead lane
     // reads the hint at the top of an iteration and the lead wave tests it where it decides CTRL_STOP; parked pairs test
     // it once before they stage anything; a pair's final record lowers it (common.hpp, IcpGate).
-    IcpGate gate;
+    IcpGate gate = {nullptr, nullptr, 0.0, 0, 1};
 };
 constexpr int ICP2_FAR_THREADS = 1024, ICP2_FAR_SMAX = 2, ICP2_FAR_POINTS = 2048;   // the continuation's shape: most source rows, target points
 constexpr int ICP2_ST_PARKED = 100;     // internal status between the two stages
@@ -159,10 +159,6 @@ constexpr int CTRL_RT = 12, CTRL_TT = 16, CTRL_ERR = 18, CTRL_PREV = 19, CTRL_DE
 #ifndef ICP2_PLAIN_CENTRED
 #define ICP2_PLAIN_CENTRED ICP2_PLAIN_ITERS     // plain iterations that start at the row's own projection
 #endif
-// THREADS x ICP2_SMAX = most source rows a pair may have on this instantiation
-// TGT_LDS: the prepared target is staged in LDS (<= 4096 points); otherwise it is read in place, through L2
-// FILT (with TGT_LDS): the LDS copy carries a float32 image per point instead of the row map (48 B instead of
-// 36 B per point) and the searches judge every candidate on it first (sweep.hpp, "single-precision filter")
 // A value every lane of the wave holds alike, moved to scalar registers (it stays live across the whole search).
 __device__ __forceinline__ double wave_uniform(double v) {
     const long long b = __double_as_longlong(v);
@@ -173,22 +169,53 @@ __device__ __forceinline__ float wave_uniform(float v) {
     return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }
 
-// Finish step it-1 (icp.py:215-220: mean squared error of the step, its change, convergence) and test the inlier
-// count of step it (icp.py:186).  Every lane of the lead wave evaluates the same values; the writer lane stores.
-// Returns FIN_STOP when the pair is done, FIN_FAR when step 0 left a mean squared error above far_err (the pair goes to the
-// far continuation after this iteration, launch_icp2), else FIN_GO.
+// far continuation: a searching row's query on its way to the lane that runs the search, and the answer on its way back
+union FarSlot {
+    struct { double x, y; int seed, pad; } in;
+    struct { double s1, s3; int p1, p2; } out;
+};
+static_assert(sizeof(FarSlot) == 24, "24 B per row");
+
+// ── the dynamic LDS of a launch, stated once: kernel, icp2_shape and plan_icp2 read it here ─────────────────────────
+// sorted points | normals | row map (4 B per point) or, filter, float32 images (16 B per point, one padding entry at either end)
+// | far: box hierarchy over blocks of 16 images (sweep.hpp; 2 B per point at most) | far: a FarSlot per row of the shape, each
+// wave its own stretch.  Byte offsets, not pointers (a layout that holds pointers cost the prepare kernel 6 %).
+struct Icp2Lds {
+    size_t xy, nrm, orig, sq, tree, slots, bytes;
+    __host__ __device__ constexpr Icp2Lds(int lds_points, bool filter, bool far = false, int far_rows = 0)
+        : xy(0), nrm((size_t)lds_points * 16), orig((size_t)lds_points * 32), sq(orig + 16),
+          tree(sq + (size_t)lds_points * 16 + 16), slots(tree + (size_t)lds_points * 2),
+          bytes(far ? slots + sizeof(FarSlot) * (size_t)far_rows : (filter ? tree : orig + (size_t)lds_points * 4)) {}
+};
+constexpr bool icp2_lds_pinned(size_t c) {               // the layout this file has always had, at capacity c
+    const Icp2Lds p((int)c, false), f((int)c, true), r((int)c, true, true, ICP2_FAR_THREADS * ICP2_FAR_SMAX);
+    return p.bytes == c * 36 && f.bytes == c * 48 + 32 && r.bytes == c * 50 + 32 + 24 * 1024 * 2 && f.xy == 0 && f.nrm == c * 16 &&
+           p.orig == c * 32 && f.sq == c * 32 + 16 && r.tree == c * 48 + 32 && r.slots == c * 50 + 32;
+}
+static_assert(icp2_lds_pinned(64) && icp2_lds_pinned(1536) && icp2_lds_pinned(2048) && icp2_lds_pinned(4096), "sizes and offsets of the areas");
+// The error of a step (icp.py:215-220: mean squared error, its change, convergence), taken by the lead wave: every lane
+// evaluates the same values, the writer lane stores.  `it`: the iterations the error belongs to.
+__device__ __forceinline__ bool step_error(double* ctrl, double err_sum, int N, double error_threshold, int it, bool writer, double& err) {
+    err = err_sum / (double)N;
+    const double delta = fabs(ctrl[CTRL_PREV] - err);
+    const bool stop = delta < error_threshold;
+    if (writer) {
+        ctrl[CTRL_ERR] = err; ctrl[CTRL_DELTA] = delta; ctrl[CTRL_PREV] = err; ctrl[CTRL_ITERS] = (double)it;
+        if (stop) ctrl[CTRL_STATUS] = (double)ICPMI_ST_CONVERGED;
+    }
+    return stop;
+}
+// Finish step it-1 (step_error) and test the inlier count of step it (icp.py:186), in every lane of the lead wave: FIN_STOP
+// when the pair is done, FIN_FAR when step 0 left a mean squared error above far_err (the pair goes to the far continuation
+// after this iteration, launch_icp2), else FIN_GO.
 constexpr int FIN_GO = 0, FIN_STOP = 1, FIN_FAR = 2;
 __device__ __forceinline__ int finish_step(double* ctrl, int it, double err_sum, double inliers, int N, bool has_corr,
                                            int need, double error_threshold, bool writer, double far_err) {
     bool stop = false, far = false;
     if (it > 0) {
-        const double err = err_sum / (double)N, delta = fabs(ctrl[CTRL_PREV] - err);
-        stop = delta < error_threshold;
+        double err;
+        stop = step_error(ctrl, err_sum, N, error_threshold, it, writer, err);
         far = it == 1 && err > far_err;
-        if (writer) {
-            ctrl[CTRL_ERR] = err; ctrl[CTRL_DELTA] = delta; ctrl[CTRL_PREV] = err; ctrl[CTRL_ITERS] = (double)it;
-            if (stop) ctrl[CTRL_STATUS] = (double)ICPMI_ST_CONVERGED;
-        }
     }
     if (!stop && has_corr && inliers < (double)need) {
         stop = true;
@@ -196,7 +223,6 @@ __device__ __forceinline__ int finish_step(double* ctrl, int it, double err_sum,
     }
     return stop ? FIN_STOP : (far ? FIN_FAR : FIN_GO);
 }
-
 // The gate (Icp2Args::gate), where the lead wave decides CTRL_STOP: a pair that goes on although a candidate before it
 // has been accepted stops as SKIPPED instead — its record then holds the totals of the `it` iterations whose error
 // finish_step has just taken.  gate_seen: what lane 0 loaded at the top of the iteration.
@@ -205,23 +231,81 @@ __device__ __forceinline__ int gate_stop(double* ctrl, const int32_t* hint, int 
     if (writer) ctrl[CTRL_STATUS] = (double)ICPMI_ST_SKIPPED;
     return FIN_STOP;
 }
-
-// R_total = R R_total, t_total = t_total R^T + t: icp.py:210-211
-__device__ __forceinline__ void accumulate_step(double* ctrl, const double (&r)[4], const double (&t)[2]) {
+// The writer lane publishes a step: into the totals (R_total = R R_total, t_total = t_total R^T + t: icp.py:210-211), out to the rows.
+__device__ __forceinline__ void publish_step(double* ctrl, const double (&r)[4], const double (&t)[2]) {
     const double rt0 = ctrl[CTRL_RT], rt1 = ctrl[CTRL_RT + 1], rt2 = ctrl[CTRL_RT + 2], rt3 = ctrl[CTRL_RT + 3];
     const double tt0 = ctrl[CTRL_TT], tt1 = ctrl[CTRL_TT + 1];
     ctrl[CTRL_RT] = r[0] * rt0 + r[1] * rt2; ctrl[CTRL_RT + 1] = r[0] * rt1 + r[1] * rt3;
     ctrl[CTRL_RT + 2] = r[2] * rt0 + r[3] * rt2; ctrl[CTRL_RT + 3] = r[2] * rt1 + r[3] * rt3;
     ctrl[CTRL_TT] = (tt0 * r[0] + tt1 * r[1]) + t[0]; ctrl[CTRL_TT + 1] = (tt0 * r[2] + tt1 * r[3]) + t[1];
+    ctrl[CTRL_R] = r[0]; ctrl[CTRL_R + 1] = r[1]; ctrl[CTRL_R + 2] = r[2]; ctrl[CTRL_R + 3] = r[3];
+    ctrl[CTRL_T] = t[0]; ctrl[CTRL_T + 1] = t[1];
+}
+// Totals <-> result record (thread 0).  A parked pair's totals travel through its record.
+__device__ __forceinline__ void load_totals(double* ctrl, const double* res) {
+    ctrl[CTRL_RT] = res[0]; ctrl[CTRL_RT + 1] = res[1]; ctrl[CTRL_RT + 2] = res[2]; ctrl[CTRL_RT + 3] = res[3];
+    ctrl[CTRL_TT] = res[ICPMI_RES_T]; ctrl[CTRL_TT + 1] = res[ICPMI_RES_T + 1];
+    ctrl[CTRL_ERR] = res[ICPMI_RES_ERR]; ctrl[CTRL_PREV] = res[ICPMI_RES_ERR]; ctrl[CTRL_DELTA] = res[ICPMI_RES_DELTA]; ctrl[CTRL_ITERS] = res[ICPMI_RES_ITERS];
+}
+// ... and the final record of a pair; a finished, eligible, accepted pair lowers the gate (NaN: never)
+__device__ __forceinline__ void store_record(double* res, const double* ctrl, const IcpGate& gate, int gate_index, int b) {
+#pragma unroll
+    for (int i = 0; i < ICPMI_RES_DOUBLES; ++i) res[i] = 0.0;
+    res[0] = ctrl[CTRL_RT]; res[1] = ctrl[CTRL_RT + 1]; res[2] = ctrl[CTRL_RT + 2]; res[3] = ctrl[CTRL_RT + 3];
+    res[ICPMI_RES_T] = ctrl[CTRL_TT]; res[ICPMI_RES_T + 1] = ctrl[CTRL_TT + 1];
+    res[ICPMI_RES_ERR] = ctrl[CTRL_ERR]; res[ICPMI_RES_DELTA] = ctrl[CTRL_DELTA];
+    res[ICPMI_RES_ITERS] = ctrl[CTRL_ITERS]; res[ICPMI_RES_STATUS] = ctrl[CTRL_STATUS];
+    const double st = ctrl[CTRL_STATUS];
+    if (gate.hint && st != (double)ICP2_ST_PARKED && st != (double)ICPMI_ST_SKIPPED && ctrl[CTRL_ERR] < gate.accept && gate_eligible(gate.search, b))
+        atomicMin(gate.hint, gate_index);
+}
+// ── the rules of a row, each written once ────────────────────────────────────────────────────────────
+// squared residual of a row at (x, y) against its match q: one term of the error of a step, icp.py:215
+__device__ __forceinline__ double row_residual(const double2 q, double x, double y) {
+    const double ex = q.x - x, ey = q.y - y;
+    double se = 0.0;
+    se += ex * ex; se += ey * ey;
+    return se;
+}
+// squared distances of a row to its two kept candidates (positions pa, pb)
+__device__ __forceinline__ void kept_pair_d2(const double2* sxy, double px, double py, int pa, int pb, double& q2, double& w2) {
+    const double2 c = sxy[pa], e = sxy[pb];
+    const double dx = px - c.x, dy = py - c.y;
+    const double ex = px - e.x, ey = py - e.y;
+    q2 = 0.0; w2 = 0.0;
+    q2 += dx * dx; q2 += dy * dy;
+    w2 += ex * ex; w2 += ey * ey;
+}
+// the correspondence gate, icp.py:184-185: nn_dists**2 < max_corr_dist**2 — the search's squared distance, bit for bit, squared again after its root
+__device__ __forceinline__ bool within_gate(double dx, double dy, double max_corr_sq) {
+    double s2 = 0.0;
+    s2 += dx * dx; s2 += dy * dy;
+    const double dist = sqrt(s2);
+    return dist * dist < max_corr_sq;
+}
+// The movement budget a top-two search leaves its row (icp2_pair).
+template <bool FAR>
+__device__ __forceinline__ float budget_of(const Top2& t2, double px, double py) {
+    float bf;
+    if constexpr (FAR) {
+        const double d1 = sqrt(t2.s1), d3 = sqrt(t2.s3);   // the far continuation keeps d3 itself (see the keep test) ...
+        bf = (float)(d3 - 1e-13 * (d3 + d1) - 1.3e-7 * (fabs(px) + fabs(py)));   // ... minus the rounding of the single-precision anchor; rounded down
+    } else {
+        // (d3 - d1) / 2 minus the rounding of the single-precision anchor, from float32 roots rounded the safe way —
+        // d3 down, d1 up (conversion 2^-24, v_sqrt_f32 one ulp: 1.2e-7 in all, 3e-7 taken) —: two float64 roots were a
+        // tenth of a top-two search; the budget only has to be a lower bound (round 4)
+        const float r3 = __builtin_amdgcn_sqrtf((float)t2.s3) * 0.9999997f;
+        const float r1 = __builtin_amdgcn_sqrtf((float)t2.s1) * 1.0000003f + 1e-30f;
+        bf = (r3 - r1) * 0.4999999f - 1.3e-7f * (fabsf((float)px) + fabsf((float)py));
+    }
+    bf = bf - fabsf(bf) * 1e-6f;
+    return t2.s3 < __builtin_inf() ? bf : __builtin_inff();
 }
 
-// far continuation: a searching row's query on its way to the lane that runs the search, and the answer on its way back
-union FarSlot {
-    struct { double x, y; int seed, pad; } in;
-    struct { double s1, s3; int p1, p2; } out;
-};
-static_assert(sizeof(FarSlot) == 24, "24 B per row");
-
+// THREADS x ICP2_SMAX = most source rows a pair may have on this instantiation
+// TGT_LDS: the prepared target is staged in LDS (<= 4096 points); otherwise it is read in place, through L2
+// FILT (with TGT_LDS): the LDS copy carries a float32 image per point instead of the row map (48 B instead of
+// 36 B per point) and the searches judge every candidate on it first (sweep.hpp, "single-precision filter")
 template <int THREADS, int ICP2_SMAX, bool TGT_LDS, bool FILT, bool RESUME, bool FAR = false>
 __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
@@ -260,12 +344,12 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
         __syncthreads();
         if (gate_skip) return;
     }
-
     // two instantiations, each sees ONE address space behind these pointers
-    double2* lds_xy = reinterpret_cast<double2*>(dyn);
-    double2* lds_nrm = reinterpret_cast<double2*>(dyn + (size_t)a.lds_points * 16);
-    int32_t* lds_orig = reinterpret_cast<int32_t*>(dyn + (size_t)a.lds_points * 32);      // !FILT: row map (4 B per point)
-    float4* lds_sq = reinterpret_cast<float4*>(dyn + (size_t)a.lds_points * 32) + 1;     //  FILT: float32 images (16 B per point), one padding entry at either end
+    const Icp2Lds lds(a.lds_points, FILT, FAR, THREADS * ICP2_SMAX);
+    double2* lds_xy = reinterpret_cast<double2*>(dyn + lds.xy);
+    double2* lds_nrm = reinterpret_cast<double2*>(dyn + lds.nrm);
+    int32_t* lds_orig = reinterpret_cast<int32_t*>(dyn + lds.orig);    // !FILT: row map
+    float4* lds_sq = reinterpret_cast<float4*>(dyn + lds.sq);          //  FILT: float32 images
     // (no block boxes here: the far scan of sweep.hpp costs this kernel 11 registers — spills at six waves per SIMD — and
     // 35 % of its time on pairs that start close, to halve the time of pairs that start metres away; measured, round 3)
     const double2* sxy = TGT_LDS ? lds_xy : a.g_sxy + a.off[tc];
@@ -273,26 +357,19 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
     const int32_t* sorig = TGT_LDS ? lds_orig : a.g_sorig + a.off[tc];
     static_assert(TGT_LDS || !FILT, "the filter images live in LDS");
     static_assert(!FAR || (FILT && RESUME), "the far continuation: filter images, parked state");
-    float4* lds_tree = reinterpret_cast<float4*>(dyn + (size_t)a.lds_points * 48 + 32);    // FAR: box hierarchy over blocks of 16 images (sweep.hpp)
-    const int tree_leaves = sweepf_tree_leaves(M);
-    // FAR: ICP2_SMAX slots per lane, each wave its own stretch (behind the largest tree: 2 * lds_points bytes)
-    FarSlot* far_q = reinterpret_cast<FarSlot*>(dyn + (size_t)a.lds_points * 50 + 32) + (size_t)(threadIdx.x / ICPMI_WAVE) * (ICPMI_WAVE * ICP2_SMAX);
+    float4* lds_tree = reinterpret_cast<float4*>(dyn + lds.tree);      // FAR: box hierarchy over blocks of 16 images (sweep.hpp) ...
+    const int tree_leaves = sweepf_tree_leaves(M);                     // ... and ICP2_SMAX slots per lane, each wave its own stretch
+    FarSlot* far_q = reinterpret_cast<FarSlot*>(dyn + lds.slots) + (size_t)(threadIdx.x / ICPMI_WAVE) * (ICPMI_WAVE * ICP2_SMAX);
     __shared__ int rt_bits;                                      // max(|x - ox|, |y - oy|) over the target, float32 bits
     if (FILT && tid == 0) rt_bits = 0;
-
     if (tid == 0) {
-        if (RESUME) {                                       // the totals the first stage left in the result record
-            ctrl[CTRL_RT] = res[0]; ctrl[CTRL_RT + 1] = res[1]; ctrl[CTRL_RT + 2] = res[2]; ctrl[CTRL_RT + 3] = res[3];
-            ctrl[CTRL_TT] = res[ICPMI_RES_T]; ctrl[CTRL_TT + 1] = res[ICPMI_RES_T + 1];
-            ctrl[CTRL_ERR] = res[ICPMI_RES_ERR]; ctrl[CTRL_PREV] = res[ICPMI_RES_ERR]; ctrl[CTRL_DELTA] = res[ICPMI_RES_DELTA];
-            ctrl[CTRL_ITERS] = res[ICPMI_RES_ITERS];
-        } else {
-            const double* in = a.init + (size_t)b * 6;      // icp.py:153-156
+        if (RESUME) load_totals(ctrl, res);                 // the totals the first stage left in the result record
+        else {                                              // a fresh pair: identity or the caller's initial guess (icp.py:153-156)
+            const double* in = a.init + (size_t)b * 6;
             ctrl[CTRL_RT] = a.has_init ? in[0] : 1.0; ctrl[CTRL_RT + 1] = a.has_init ? in[1] : 0.0;
             ctrl[CTRL_RT + 2] = a.has_init ? in[2] : 0.0; ctrl[CTRL_RT + 3] = a.has_init ? in[3] : 1.0;
             ctrl[CTRL_TT] = a.has_init ? in[4] : 0.0; ctrl[CTRL_TT + 1] = a.has_init ? in[5] : 0.0;
-            ctrl[CTRL_ERR] = __builtin_inf(); ctrl[CTRL_PREV] = __builtin_inf(); ctrl[CTRL_DELTA] = __builtin_inf();
-            ctrl[CTRL_ITERS] = 0.0;
+            ctrl[CTRL_ERR] = __builtin_inf(); ctrl[CTRL_PREV] = __builtin_inf(); ctrl[CTRL_DELTA] = __builtin_inf(); ctrl[CTRL_ITERS] = 0.0;
         }
         ctrl[CTRL_STATUS] = (double)ICPMI_ST_MAXITER;
     }
@@ -397,12 +474,7 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
 #pragma unroll
             for (int s = 0; s < ICP2_SMAX; ++s) {
                 if (!(s < S && s * THREADS + tid < N)) continue;
-                const double2 q = sxy[pos[s]];
-                const double ex = q.x - px[s], ey = q.y - py[s];
-                double se = 0.0;
-                se += ex * ex;
-                se += ey * ey;
-                e_part += se;
+                e_part += row_residual(sxy[pos[s]], px[s], py[s]);
             }
         }
         bool stopped = false;
@@ -417,8 +489,10 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
             int gate_seen = 0x7fffffff;
             if (a.gate.hint && tid == 0) gate_seen = __hip_atomic_load(a.gate.hint, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             // ── correspondences: exact sweep search in LDS, icp.py:179 ───────
-            // A row whose net displacement since its last search is inside its budget keeps one of its two
-            // candidates (two distances); the others search.
+            // (This phase, the searches and the apply loop as named local lambdas, with a row_valid lambda for the row test below, leave
+            // every kernel's registers, scratch and occupancy as they are and cost time all the same: 16 384 pairs 4.624 -> 4.651 ms, 512
+            // pairs 0.637 -> 0.651, step 7.298 -> 7.336, each outside the parent's spread.  row_valid as a function: 4 B of scratch in one kernel.)
+            // A row whose net displacement since its last search is inside its budget keeps one of its two candidates; the others search.
             bool srch[ICP2_SMAX];
 #pragma unroll
             for (int s = 0; s < ICP2_SMAX; ++s) {
@@ -437,14 +511,8 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
                     within = false;
                     if (valid && budget[s] > 0.0f) {
                         const int pa = pos[s], pb = pos2[s] >= 0 ? pos2[s] : pos[s];
-                        const double2 c = sxy[pa], e = sxy[pb];
-                        const double dx = px[s] - c.x, dy = py[s] - c.y;
-                        const double ex = px[s] - e.x, ey = py[s] - e.y;
-                        double q2 = 0.0, w2 = 0.0;
-                        q2 += dx * dx;
-                        q2 += dy * dy;
-                        w2 += ex * ex;
-                        w2 += ey * ey;
+                        double q2, w2;
+                        kept_pair_d2(sxy, px[s], py[s], pa, pb, q2, w2);
                         const double g = (double)budget[s] - (fabs(px[s] - (double)ax[s]) + fabs(py[s] - (double)ay[s])) * 1.000000001;
                         within = g > 0.0 && fmin(q2, w2) * 1.000000000001 < g * g * 0.999999999999;
                     }
@@ -456,14 +524,8 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
                     // straight-line: a missing second candidate stands in as the first (never better), and only an
                     // exact tie of the two distances takes a branch (to compare the rows)
                     const int pa = pos[s], pb = pos2[s] >= 0 ? pos2[s] : pos[s];
-                    const double2 c = sxy[pa], e = sxy[pb];
-                    const double dx = px[s] - c.x, dy = py[s] - c.y;
-                    const double ex = px[s] - e.x, ey = py[s] - e.y;
-                    double q2 = 0.0, w2 = 0.0;
-                    q2 += dx * dx;
-                    q2 += dy * dy;
-                    w2 += ex * ex;
-                    w2 += ey * ey;
+                    double q2, w2;
+                    kept_pair_d2(sxy, px[s], py[s], pa, pb, q2, w2);
                     bool second_wins = w2 < q2;
                     if (w2 == q2 && pb != pa) {
                         if constexpr (FILT) second_wins = sweepf_row(lds_sq[pb]) < sweepf_row(lds_sq[pa]);
@@ -541,26 +603,11 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
                         }
                         else t2 = sweep_top2(sxy, sorig, M, dir, uabs, px[s], py[s], pos[s], centred);
                         pos[s] = t2.p1; pos2[s] = t2.p2;
-                        float bf;
-                        if constexpr (FAR) {
-                            const double d1 = sqrt(t2.s1), d3 = sqrt(t2.s3);
-                            // minus the rounding of the single-precision anchor; rounded down                  (see the test above)
-                            bf = (float)(d3 - 1e-13 * (d3 + d1) - 1.3e-7 * (fabs(px[s]) + fabs(py[s])));
-                        } else {
-                            // (d3 - d1) / 2 minus the rounding of the single-precision anchor, from float32 roots rounded the safe way —
-                            // d3 down, d1 up (conversion 2^-24, v_sqrt_f32 one ulp: 1.2e-7 in all, 3e-7 taken) —: two float64 roots were a
-                            // tenth of a top-two search; the budget only has to be a lower bound (round 4)
-                            const float r3 = __builtin_amdgcn_sqrtf((float)t2.s3) * 0.9999997f;
-                            const float r1 = __builtin_amdgcn_sqrtf((float)t2.s1) * 1.0000003f + 1e-30f;
-                            bf = (r3 - r1) * 0.4999999f - 1.3e-7f * (fabsf((float)px[s]) + fabsf((float)py[s]));
-                        }
-                        bf = bf - fabsf(bf) * 1e-6f;
-                        budget[s] = t2.s3 < __builtin_inf() ? bf : __builtin_inff();
+                        budget[s] = budget_of<FAR>(t2, px[s], py[s]);
                         ax[s] = (float)px[s]; ay[s] = (float)py[s];
                     }
             }
-            // rows that take part in the solve: all valid rows, or those within max_corr_dist of their match
-            // (icp.py:184-185: nn_dists**2 < max_corr_dist**2, the distance squared again after its root)
+            // rows that take part in the solve: all valid rows, or those within max_corr_dist of their match (within_gate)
             bool in[ICP2_SMAX];
 #pragma unroll
             for (int s = 0; s < ICP2_SMAX; ++s) in[s] = s < S && s * THREADS + tid < N;
@@ -572,13 +619,7 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
                     if (!in[s]) continue;
                     const double2 q = sxy[pos[s]], nm = snrm[pos[s]];
                     const double dx = px[s] - q.x, dy = py[s] - q.y;
-                    if (has_corr) {                                   // the search's squared distance, recomputed bit for bit
-                        double s2 = 0.0;
-                        s2 += dx * dx;
-                        s2 += dy * dy;
-                        const double dist = sqrt(s2);
-                        if (!(dist * dist < max_corr_sq)) continue;
-                    }
+                    if (has_corr && !within_gate(dx, dy, max_corr_sq)) continue;
                     const double c = nm.y * px[s] - nm.x * py[s];
                     const double bi = -(nm.x * dx + nm.y * dy);
                     acc[0] += c * c;       acc[1] += c * nm.x;    acc[2] += c * nm.y;
@@ -596,8 +637,9 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
                     const bool stop = fin == FIN_STOP;
                     if (!stop) {
                         double A[3][3] = {{acc[0], acc[1], acc[2]}, {acc[1], acc[3], acc[4]}, {acc[2], acc[4], acc[5]}};
-                        double rhs[3] = {acc[6], acc[7], acc[8]}, x[3];
-                        double r[4], t[2];
+                        // (Written out: through linalg.hpp's p2l_step_from_solution, or with this solve as a phase of its own, the code
+                        // of all 49 kernels moves — 4-6 VGPRs fewer, 16 384 pairs 4.61 -> 4.67 ms, 512 pairs 0.636 -> 0.660.)
+                        double rhs[3] = {acc[6], acc[7], acc[8]}, x[3], r[4], t[2];
                         if (solve3(A, rhs, x)) {
                             double st, ct;
                             sincos_step(x[0], st, ct);                             // icp.py:110-114
@@ -605,12 +647,7 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
                         } else {
                             r[0] = 1.0; r[1] = 0.0; r[2] = 0.0; r[3] = 1.0; t[0] = 0.0; t[1] = 0.0;
                         }
-                        // accumulate totals, icp.py:210-211
-                        if (tid == 0) {
-                            accumulate_step(ctrl, r, t);
-                            ctrl[CTRL_R] = r[0]; ctrl[CTRL_R + 1] = r[1]; ctrl[CTRL_R + 2] = r[2]; ctrl[CTRL_R + 3] = r[3];
-                            ctrl[CTRL_T] = t[0]; ctrl[CTRL_T + 1] = t[1];
-                        }
+                        if (tid == 0) publish_step(ctrl, r, t);                    // accumulate totals, icp.py:210-211
                     }
                     if (tid == 0) ctrl[CTRL_STOP] = (double)fin;
                 }
@@ -622,13 +659,8 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
                 for (int s = 0; s < ICP2_SMAX; ++s) {
                     if (!in[s]) continue;
                     const double2 q = sxy[pos[s]];
-                    if (has_corr) {                                   // the search's squared distance, recomputed bit for bit
-                        const double dx = px[s] - q.x, dy = py[s] - q.y;
-                        double s2 = 0.0;
-                        s2 += dx * dx;
-                        s2 += dy * dy;
-                        const double dist = sqrt(s2);
-                        in[s] = dist * dist < max_corr_sq;
+                    if (has_corr) {
+                        in[s] = within_gate(px[s] - q.x, py[s] - q.y, max_corr_sq);
                         if (!in[s]) continue;
                     }
                     m[0] += px[s]; m[1] += py[s]; m[2] += q.x; m[3] += q.y; m[4] += 1.0;
@@ -668,11 +700,7 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
                     s0 += r[0] * mpx; s0 += r[1] * mpy;
                     s1 += r[2] * mpx; s1 += r[3] * mpy;
                     t[0] = mqx - s0; t[1] = mqy - s1;                              // icp.py:207
-                    if (tid == 0) {
-                        accumulate_step(ctrl, r, t);
-                        ctrl[CTRL_R] = r[0]; ctrl[CTRL_R + 1] = r[1]; ctrl[CTRL_R + 2] = r[2]; ctrl[CTRL_R + 3] = r[3];
-                        ctrl[CTRL_T] = t[0]; ctrl[CTRL_T + 1] = t[1];
-                    }
+                    if (tid == 0) publish_step(ctrl, r, t);
                 }
                 __syncthreads();
             }
@@ -689,11 +717,7 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
                 nx += px[s] * r0; nx += py[s] * r1; nx += t0;
                 ny += px[s] * r2; ny += py[s] * r3; ny += t1;
                 px[s] = nx; py[s] = ny;
-                const double ex = q.x - nx, ey = q.y - ny;
-                double se = 0.0;
-                se += ex * ex;
-                se += ey * ey;
-                e_part += se;
+                e_part += row_residual(q, nx, ny);
             }
             if (!RESUME && it == 1 && ctrl[CTRL_STOP] == (double)FIN_FAR) break;
         }
@@ -721,31 +745,12 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
             __syncthreads();
             if (lead) {
                 combine_totals<1>(redA, NWAVES, e);
-                if (tid == 0) {
-                    const double err = e[0] / (double)N, delta = fabs(ctrl[CTRL_PREV] - err);
-                    ctrl[CTRL_ERR] = err; ctrl[CTRL_DELTA] = delta;
-                    ctrl[CTRL_ITERS] = (double)a.max_iterations;
-                    if (delta < a.error_threshold) ctrl[CTRL_STATUS] = (double)ICPMI_ST_CONVERGED;
-                }
+                double err;
+                if (tid == 0) step_error(ctrl, e[0], N, a.error_threshold, a.max_iterations, true, err);
             }
         }
     }
-    if (tid == 0) {
-#pragma unroll
-        for (int i = 0; i < ICPMI_RES_DOUBLES; ++i) res[i] = 0.0;
-        res[0] = ctrl[CTRL_RT]; res[1] = ctrl[CTRL_RT + 1]; res[2] = ctrl[CTRL_RT + 2]; res[3] = ctrl[CTRL_RT + 3];
-        res[ICPMI_RES_T] = ctrl[CTRL_TT]; res[ICPMI_RES_T + 1] = ctrl[CTRL_TT + 1];
-        res[ICPMI_RES_ERR] = ctrl[CTRL_ERR];
-        res[ICPMI_RES_DELTA] = ctrl[CTRL_DELTA];
-        res[ICPMI_RES_ITERS] = ctrl[CTRL_ITERS];
-        res[ICPMI_RES_STATUS] = ctrl[CTRL_STATUS];
-        if (a.gate.hint) {                                  // a finished, eligible, accepted pair lowers the gate (NaN: never)
-            const double st = ctrl[CTRL_STATUS];
-            if (st != (double)ICP2_ST_PARKED && st != (double)ICPMI_ST_SKIPPED && ctrl[CTRL_ERR] < a.gate.accept &&
-                gate_eligible(a.gate.search, b))
-                atomicMin(a.gate.hint, gate_index);
-        }
-    }
+    if (tid == 0) store_record(res, ctrl, a.gate, gate_index, b);
 }
 
 template <int THREADS, int ICP2_SMAX, bool TGT_LDS, bool FILT>
@@ -795,7 +800,7 @@ __global__ __launch_bounds__(ICP2_FAR_THREADS, 4) void icp2_far_kernel(Icp2Args 
 
 // The parked state of the stages (see Icp2Args), in the caller's workspace: transformed rows | sweep positions (max_src_n of
 // each per pair) | the three lists of pairs (second stage, wide, far) | their three counters, no gap between them.
-struct Icp2Ws {
+struct Icp2Ws {                 // (tests/test_icp2_layout_gpu.py reads the far counter at its offset here: keep the two together)
     Carve c;
     int n_pairs, max_src_n;
     size_t st_rows = (size_t)n_pairs * (size_t)max_src_n;
@@ -840,9 +845,7 @@ static Icp2Shape icp2_shape(int threads, int smax, int points, bool in_lds) {
     if (points > 1024 && points <= 1536) cap = 1536;
     // The filter needs <= 2 048 points (96 KB, one workgroup per CU).
     const bool filter = in_lds && cap <= 2048;
-    // LDS copy of the target: 36 B per point, 48 B with the float32 images of the filter.
-    const size_t lds = in_lds ? (filter ? (size_t)cap * 48 + 32 : (size_t)cap * 36) : 0;
-    return {threads, smax, in_lds, filter, cap, lds, -1, 0, 0};
+    return {threads, smax, in_lds, filter, cap, in_lds ? Icp2Lds(cap, filter).bytes : 0, -1, 0, 0};
 }
 
 // stages_opt, far_opt: the options ICP2_STAGES and ICP2_FAR (nullptr: not set); have_ws: the caller gave a workspace that
@@ -894,12 +897,11 @@ static Icp2Plan plan_icp2(int n_pairs, int max_src_n, int max_tgt_n, const icpmi
     // sent over and the 16 384-pair batch takes 5.7 instead of 5.05 ms; 0 = never)
     plan.far_d2 = far_opt ? atof(far_opt) : 1.0;
     plan.far_wanted = have_ws && in_lds && plan.far_d2 > 0.0 && p.max_iterations > 2;
-    // the far continuation's LDS: the filter layout + the box hierarchy (2 B per point at most) + a slot per row of its shape
-    // (every wave owns the stretch behind its own lanes, whatever the batch's source sizes).
+    // the far continuation's LDS (Icp2Lds): every wave owns the slots behind its own lanes, whatever the batch's source sizes
     int far_cap = 64;
     while (far_cap < max_tgt_n && far_cap < ICP2_FAR_POINTS) far_cap <<= 1;
     plan.far = {ICP2_FAR_THREADS, ICP2_FAR_SMAX, true, true, far_cap,
-                (size_t)far_cap * 50 + 32 + sizeof(FarSlot) * (size_t)(ICP2_FAR_THREADS * ICP2_FAR_SMAX), -1, 0, 0};
+                Icp2Lds(far_cap, true, true, ICP2_FAR_THREADS * ICP2_FAR_SMAX).bytes, -1, 0, 0};
     plan.needs_lists = have_ws && (plan.two_stage || plan.has_wide);
     return plan;
 }
@@ -949,11 +951,8 @@ int launch_icp2(const double* pts, const int32_t* off, const int32_t* cnt, const
     const Icp2Plan plan = plan_icp2(n_pairs, max_src_n, max_tgt_n, *p, have_ws, option("ICP2_STAGES"), option("ICP2_FAR"));
     const Icp2Kernels k1 = icp2_kernels_of(plan.first), k2 = icp2_kernels_of(plan.wide);
     if (!k1.fused || (plan.has_wide && !k2.fused)) return ICPMI_ERR_ARG;
-    Icp2Args base;
-    base.gate = gate ? *gate : IcpGate{nullptr, nullptr, 0.0, 0, 1};
-    base.st_xy = nullptr; base.st_pos = nullptr; base.list = nullptr; base.list_count = nullptr; base.st_stride = 0;
-    base.wide_list = nullptr; base.wide_count = nullptr;
-    base.far_list = nullptr; base.far_count = nullptr; base.far_d2 = __builtin_inf();
+    Icp2Args base;                                          // the parked state, the lists and the gate: none unless set below
+    if (gate) base.gate = *gate;
     const PreparedView v(prepared, total_rows);
     base.pts = pts; base.off = off; base.cnt = cnt; base.pair_src = ps; base.pair_tgt = pt; base.init = init; base.results = results;
     base.g_sxy = v.sxy; base.g_snrm = v.snrm; base.g_sorig = v.sorig; base.g_skey = v.skey; base.g_dir = v.dir;

@@ -71,6 +71,18 @@ __device__ __forceinline__ void sincos_step(double x, double& s, double& c) {
     }
 }
 
+// The point-to-line step from A x = rhs (icp.py:106-114): r rotates by x[0], t = (x[1], x[2]); identity when the solve fails.
+__device__ __forceinline__ void p2l_step_from_solution(double (&A)[3][3], double (&rhs)[3], double (&r)[4], double (&t)[2]) {
+    double x[3];
+    if (solve3(A, rhs, x)) {
+        double st, ct;
+        sincos_step(x[0], st, ct);
+        r[0] = ct; r[1] = -st; r[2] = st; r[3] = ct; t[0] = x[1]; t[1] = x[2];
+    } else {
+        r[0] = 1.0; r[1] = 0.0; r[2] = 0.0; r[3] = 1.0; t[0] = 0.0; t[1] = 0.0;
+    }
+}
+
 // Optimal proper rotation for the 2x2 cross-covariance W = sum pc qc^T: what
 // r = V U^T with the det<0 fix evaluates to (reference icp.py:202-206).
 // tr(R W) = c (W00+W11) + s (W01-W10) is maximal at (c, s) parallel to those.
