@@ -74,6 +74,12 @@ struct Icp2Args {
     // reads the hint at the top of an iteration and the lead wave tests it where it decides CTRL_STOP; parked pairs test
     // it once before they stage anything; a pair's final record lowers it (common.hpp, IcpGate).
     IcpGate gate = {nullptr, nullptr, 0.0, 0, 1};
+    // The far continuation (far_list above).  "Same arithmetic" includes the order of the sums over the rows: a thread adds
+    // up its own rows, then the waves are added in order.  The continuation therefore gives a pair's rows to its threads as
+    // the launch that parked the pair did: row n to thread n % far_row_threads (the threads beyond stay without rows) when
+    // the pair was the first launch's (at most far_row_n source rows and far_row_m target rows), as its own shape does when
+    // it was the wide launch's.  (Behind everything else: the other kernels' arguments stay where they were.)
+    int far_row_threads = 0, far_row_n = 0, far_row_m = 0;
 };
 constexpr int ICP2_FAR_THREADS = 1024, ICP2_FAR_SMAX = 2, ICP2_FAR_POINTS = 2048;   // the continuation's shape: most source rows, target points
 constexpr int ICP2_ST_PARKED = 100;     // internal status between the two stages
@@ -322,6 +328,9 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
     const double* src = a.pts + (size_t)a.off[sc] * 2;
     double* res = a.results + (size_t)b * ICPMI_RES_DOUBLES;
     const int dir = a.g_dir[tc];
+    // RT: threads that hold rows, row n = s * RT + tid (the far continuation: as in the launch that parked the pair, Icp2Args)
+    const int RT = FAR && N <= a.far_row_n && M <= a.far_row_m ? a.far_row_threads : THREADS;
+    const bool row_lane = !FAR || tid < RT;
     // The voxel filter leaves the row counts on the device, so the launcher sizes the rows per thread for the usual
     // case and sends the (rare) larger clouds to a second launch of a wider shape: each pair is registered by
     // exactly one of the two (uniform per workgroup, before any barrier).
@@ -374,7 +383,7 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
         ctrl[CTRL_STATUS] = (double)ICPMI_ST_MAXITER;
     }
 
-    if (N <= 0 || M <= 0 || dir < 0 || (TGT_LDS && M > a.lds_points) || N > THREADS * ICP2_SMAX || (!FILT && dir >= SWEEP_POLAR)) {
+    if (N <= 0 || M <= 0 || dir < 0 || (TGT_LDS && M > a.lds_points) || N > RT * ICP2_SMAX || (!FILT && dir >= SWEEP_POLAR)) {
         if (tid == 0) ctrl[CTRL_STATUS] = (double)ICPMI_ST_EMPTY;   // the launcher only sends pairs that fit
     } else {
         const bool use_p2l = a.method == ICPMI_POINT_TO_LINE;
@@ -412,7 +421,7 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
             __syncthreads();                                     // rt_bits = 0 is visible, the images are complete
             atomicMax(&rt_bits, __float_as_int(rmax));           // non-negative floats order like their bits
         }
-        // moving source rows in registers: row n = s*THREADS + tid
+        // moving source rows in registers: row n = s*RT + tid
         double px[ICP2_SMAX], py[ICP2_SMAX];
         int pos[ICP2_SMAX];
         // Movement budget of each row's match.  A search returns the two nearest
@@ -432,10 +441,10 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
         int pos2[ICP2_SMAX];
 #pragma unroll
         for (int s = 0; s < ICP2_SMAX; ++s) { ax[s] = 0.0f; ay[s] = 0.0f; budget[s] = -1.0f; pos2[s] = -1; }
-        const int S = (N + THREADS - 1) / THREADS;
+        const int S = row_lane ? (N + RT - 1) / RT : 0;
 #pragma unroll
         for (int s = 0; s < ICP2_SMAX; ++s) {
-            const int n = s * THREADS + tid;
+            const int n = row_lane ? s * RT + tid : N;
             px[s] = 0.0; py[s] = 0.0; pos[s] = -1;                       // -1: no previous match yet
             if (n < N && RESUME) {
                 const double2 v = a.st_xy[(size_t)b * a.st_stride + n];
@@ -473,7 +482,7 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
             // apply loop below, term by term
 #pragma unroll
             for (int s = 0; s < ICP2_SMAX; ++s) {
-                if (!(s < S && s * THREADS + tid < N)) continue;
+                if (!(s < S && s * RT + tid < N)) continue;
                 e_part += row_residual(sxy[pos[s]], px[s], py[s]);
             }
         }
@@ -496,7 +505,7 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
             bool srch[ICP2_SMAX];
 #pragma unroll
             for (int s = 0; s < ICP2_SMAX; ++s) {
-                const bool valid = s < S && s * THREADS + tid < N;
+                const bool valid = s < S && s * RT + tid < N;
                 // |dx| + |dy| >= the distance between the row and its anchor
                 // (Tried in round 3: testing delta + dq < d3 with the CURRENT distance dq to the better kept candidate — about
                 // twice as generous, 0.7 % instead of 2 % of the rows of a limit cycle search — costs 8 registers (a spill at
@@ -610,7 +619,7 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
             // rows that take part in the solve: all valid rows, or those within max_corr_dist of their match (within_gate)
             bool in[ICP2_SMAX];
 #pragma unroll
-            for (int s = 0; s < ICP2_SMAX; ++s) in[s] = s < S && s * THREADS + tid < N;
+            for (int s = 0; s < ICP2_SMAX; ++s) in[s] = s < S && s * RT + tid < N;
             if (use_p2l) {
                 // ── point-to-line normal equations, icp.py:88-104, + carried error ─
                 double acc[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -711,7 +720,7 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
             e_part = 0.0;
 #pragma unroll
             for (int s = 0; s < ICP2_SMAX; ++s) {
-                if (!(s < S && s * THREADS + tid < N)) continue;
+                if (!(s < S && s * RT + tid < N)) continue;
                 const double2 q = sxy[pos[s]];
                 double nx = 0.0, ny = 0.0;
                 nx += px[s] * r0; nx += py[s] * r1; nx += t0;
@@ -726,7 +735,7 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
             // parked for the second stage: rows and matches as they are, totals through the result record
 #pragma unroll
             for (int s = 0; s < ICP2_SMAX; ++s) {
-                const int n = s * THREADS + tid;
+                const int n = s * RT + tid;
                 if (s < S && n < N) {
                     a.st_xy[(size_t)b * a.st_stride + n] = make_double2(px[s], py[s]);
                     a.st_pos[(size_t)b * a.st_stride + n] = pos[s];
@@ -1009,9 +1018,11 @@ int launch_icp2(const double* pts, const int32_t* off, const int32_t* cnt, const
             k2.fused<<<n_pairs, s2.threads, s2.lds, st>>>(wide);
         }
     }
-    if (base.far_list)                                      // after every first launch (the wide one has joined the stream)
-        icp2_far_kernel<<<n_pairs < 256 ? n_pairs : 256, plan.far.threads, plan.far.lds, st>>>(
-            icp2_args(base, plan.far, 2, ICP2_NO_LIMIT, 1));
+    if (base.far_list) {                                    // after every first launch (the wide one has joined the stream)
+        Icp2Args far = icp2_args(base, plan.far, 2, ICP2_NO_LIMIT, 1);
+        far.far_row_threads = s1.threads; far.far_row_n = s1.threads * s1.smax; far.far_row_m = s1.lds_points;
+        icp2_far_kernel<<<n_pairs < 256 ? n_pairs : 256, plan.far.threads, plan.far.lds, st>>>(far);
+    }
     ICPMI_LAUNCH_CHECK();
     return ICPMI_OK;
 }

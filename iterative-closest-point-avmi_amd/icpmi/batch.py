@@ -341,6 +341,16 @@ class IcpBatch(_Paired):
         """The row count ``prepared`` is laid out for: the set's rows (a resident history: its row capacity)."""
         return self.raw.total_rows
 
+    def direction_words(self):
+        """The sort order the last ``prepare()`` chose for every target cloud (``tgt_ids`` order): the int32 words behind the
+        row arrays of ``prepared`` (csrc/prep_common.hpp, PreparedView) — 0..3 the projections x, y, x + y, x - y, 4 the
+        bearing (csrc/sweep.hpp).  Read-only, on the host (synchronises); fast path only."""
+        if self.prepared is None:
+            raise IcpmiError("no prepared targets: this batch takes the exhaustive kernels")
+        at = self.layout_rows * 40
+        words = self.prepared[at:at + 4 * self.raw.n_clouds].view(torch.int32)
+        return words.cpu().numpy()[self.tgt_ids].copy()
+
     def set_gate(self, error_accept, search_records=None, index_base=0, index_stride=1):
         """Stop after the first accepted pair (slam.py:582-597; include/icpmi.h, icpmi_icp_batch_gated): from now on
         ``run()`` lets pairs after the first one with err < error_accept (and, with ``search_records``, a rotation-search
