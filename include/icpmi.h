@@ -359,7 +359,11 @@ int icpmi_rotation_refine(const void* search_workspace, int32_t n_src, int32_t n
  * winning fine index, its score); ICPMI_RSBREC_STATUS — ICPMI_RSB_ST_OK searched; _FEW a filtered cloud has fewer
  * than 5 points (features.py:203-204: identity, zeros, inf); _CAPACITY a filtered cloud exceeds the on-chip capacity
  * (not searched: use icpmi_rotation_search); _NO_FINE the winner's fine grid is empty (np.argmin raises in the
- * reference); ICPMI_RSBREC_EVALS, _FEVALS coarse / fine angles scored exactly (diagnostic).
+ * reference); ICPMI_RSBREC_EVALS the coarse angles scored exactly, counted as a schedule-free number: those
+ * whose bound does not exceed the winning score (every run scores these), and at least one per wave of the workgroup (8,
+ * or all the coarse angles if fewer: a wave's first angle is scored before any result exists); a run may score a few
+ * more, depending on when its waves see each other's results, and those are not counted, so that a record is the same
+ * bits run after run — ICPMI_RSBREC_FEVALS the fine angles scored (diagnostic).
  * out_init (optional) [n_pairs][6]: R row-major then t = mu_t - R mu_s (features.py:235-237) — the `init` argument of
  * icpmi_icp_batch, so pre-alignment and ICP chain on one stream with no host round trip; identity for a status other
  * than ICPMI_RSB_ST_OK.
@@ -679,6 +683,72 @@ int icpmi_grid_update_scans_box(float* log_odds, void* counts, int32_t ny, int32
                                 int32_t n_scans, double l_hit, double l_miss, double lo, double hi,
                                 int64_t scan_seq, int32_t full_clip, int32_t row_begin, int32_t row_end,
                                 const int32_t* box_host, void* stream);
+
+/* ---- correlative scan-to-map matching: the grid of utilities/mapping.py read back as a target -----------------------
+ * The reference registers a scan against a cloud only (slam.py:53-98, 111-183).  These entries score a scan against the
+ * occupancy grid itself over a window of rotations and whole-cell shifts.  After the cells are formed everything is
+ * integer, so the result does not depend on how the work is split or on the order of the integer atomics.
+ *
+ * icpmi_grid_score_field: field[iy][ix] = clip(rint(log_odds[iy][ix] * 2^shift_bits), -32767, 32767) as int16 — the
+ * product in float32 (a power of two: exact), rint half to even, NaN -> 0, +-inf and anything beyond the clamp saturate.
+ * shift_bits in [0, ICPMI_GM_MAX_SHIFT_BITS] is the caller's choice (the Python layer takes the largest one with
+ * max(|log_odds_min|, |log_odds_max|) * 2^shift_bits <= 32767: 12 for the default +-5).  Both pointers 16-byte aligned
+ * (vector loads and stores); ny * nx == 0: no launch, ICPMI_OK.
+ *
+ * icpmi_grid_match_batch: pair b names cloud pair_cloud[b] of the set (pts, off_dev, cnt_dev: 2-D rows; cnt_dev NULL =
+ * every cloud full), a translation pair_t[2b .. 2b+1] and n_angles rotations cos_sin[(b * n_angles + a) * 2 .. + 1] =
+ * (cos, sin) — the caller's own doubles.  With W = window and S = 2W + 1, for angle a and source row (x, y), float64,
+ * evaluated exactly as written, every operation rounded on its own (no fused multiply-add):
+ *   wx = (c * x - s * y) + tx,  wy = (s * x + c * y) + ty,
+ *   cx = floor((wx - min_x) / resolution),  cy = floor((wy - min_y) / resolution)   (IEEE divide, mapping.py:94-98);
+ * a row whose wx or wy is not finite, or whose cx or cy lies outside [-2^29, 2^29], has no cell and adds nothing.
+ *   score[b][a][j][i] = sum over the rows with a cell of field[cy + j - W][cx + i - W],
+ * a cell outside [0, ny) x [0, nx) counting 0, as unknown space does.  int32: at most ICPMI_GM_MAX_ROWS rows of at most
+ * 32767 each cannot overflow.  The winner is the first maximum of score[b] over (a, j, i) in C order (np.argmax); the
+ * host forms the pose from it: translation (tx + (i - W) * resolution, ty + (j - W) * resolution), rotation the
+ * caller's (cos, sin) at a.
+ * out_records [n_pairs][ICPMI_GMREC_INTS] int32, slots ICPMI_GMREC_*: status, rows with a cell at the winning angle,
+ * the winner's flat index (a * S + j) * S + i, a, j, i, its score, and the score of the centre candidate
+ * (centre_angle, W, W) — 0 when centre_angle < 0.  Status ICPMI_GM_ST_OK; ICPMI_GM_ST_EMPTY: no row has a cell at any
+ * angle (every score 0, index 0); ICPMI_GM_ST_CAPACITY: the cloud's device count is negative (the voxel filter's
+ * overflow mark) or exceeds the cloud's own rows or ICPMI_GM_MAX_ROWS (not read: every score 0).
+ * out_scores (optional): receives the whole volume [n_pairs][n_angles][S][S] int32 (it is then accumulated there
+ * instead of in the workspace).  workspace: icpmi_grid_match_workspace_bytes(n_pairs, n_angles, window) bytes (0 for a
+ * negative argument); the call zeroes what it accumulates into, so a workspace is reusable as it is.
+ * Every refusal is decided on the host before any launch.  off_host mirrors off_dev and pair_cloud_host mirrors
+ * pair_cloud (both required: they size the launch); a pair's cloud outside [0, n_clouds), a null pointer, a grid with
+ * ny * nx >= 2^31, a non-positive or non-finite resolution, centre_angle >= n_angles, n_angles < 1: ICPMI_ERR_ARG;
+ * window > ICPMI_GM_MAX_WINDOW, n_angles > ICPMI_GM_MAX_ANGLES or a pair's cloud above ICPMI_GM_MAX_ROWS rows by
+ * off_host: ICPMI_ERR_UNSUPPORTED; a short workspace: ICPMI_ERR_WORKSPACE.  n_pairs == 0: no launch, ICPMI_OK.
+ * Launches: two memsets, one scoring launch — a workgroup of ICPMI_GM_THREADS threads per (pair, angle, chunk of
+ * ICPMI_GM_CHUNK_ROWS rows), ending in one int32 atomicAdd per shift — and one arg-max workgroup per pair. */
+#define ICPMI_GM_MAX_WINDOW 31
+#define ICPMI_GM_MAX_ANGLES 1024
+#define ICPMI_GM_MAX_ROWS 65535
+#define ICPMI_GM_MAX_SHIFT_BITS 14
+#define ICPMI_GM_THREADS 256
+#define ICPMI_GM_CHUNK_ROWS 256
+#define ICPMI_GM_ST_OK 0
+#define ICPMI_GM_ST_EMPTY 1
+#define ICPMI_GM_ST_CAPACITY 2
+#define ICPMI_GMREC_INTS 8
+#define ICPMI_GMREC_STATUS 0
+#define ICPMI_GMREC_ROWS 1
+#define ICPMI_GMREC_INDEX 2
+#define ICPMI_GMREC_A 3
+#define ICPMI_GMREC_J 4
+#define ICPMI_GMREC_I 5
+#define ICPMI_GMREC_SCORE 6
+#define ICPMI_GMREC_CENTRE 7
+int icpmi_grid_score_field(const float* log_odds, int32_t ny, int32_t nx, int32_t shift_bits, int16_t* field,
+                           void* stream);
+size_t icpmi_grid_match_workspace_bytes(int32_t n_pairs, int32_t n_angles, int32_t window);
+int icpmi_grid_match_batch(const int16_t* field, int32_t ny, int32_t nx, double min_x, double min_y, double resolution,
+                           const double* pts, const int32_t* off_dev, const int32_t* off_host, const int32_t* cnt_dev,
+                           int32_t n_clouds, const int32_t* pair_cloud, const int32_t* pair_cloud_host,
+                           int32_t n_pairs, const double* pair_t, const double* cos_sin, int32_t n_angles,
+                           int32_t window, int32_t centre_angle, int32_t* out_records, int32_t* out_scores,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* ── pose graph: PoseGraph2D.optimize, utilities/pose_graph.py:83-134 ──────────
  * Gauss-Newton on SE(2) over n_nodes poses [x, y, theta] (nodes: device, updated

@@ -412,7 +412,7 @@ __global__ __launch_bounds__(RSB_THREADS, 4) void rotation_search_batch_kernel(R
     double* scores = reinterpret_cast<double*>(field);
     short* order = reinterpret_cast<short*>(field + 2 * RSB_MAX_ANGLES);
     __shared__ double best_score;
-    __shared__ int rt_bits, rho_bits, n_evals;
+    __shared__ int rt_bits, rho_bits, n_evals, n_needed;
     __shared__ __attribute__((aligned(8))) int sh_arg[RS_ARGMIN_INTS];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int sc = a.pair_src[b], tc = a.pair_tgt[b];
@@ -438,7 +438,7 @@ __global__ __launch_bounds__(RSB_THREADS, 4) void rotation_search_batch_kernel(R
     float4* tree = reinterpret_cast<float4*>(dyn + (size_t)a.cap * 48 + 32);   // box hierarchy over blocks of 16 sorted positions (sweep.hpp: far queries)
 
     // ── 1. stage the pair ────────────────────────────────────────────────────
-    if (tid == 0) { rt_bits = 0; rho_bits = 0; n_evals = 0; best_score = __builtin_inf(); }
+    if (tid == 0) { rt_bits = 0; rho_bits = 0; n_evals = 0; n_needed = 0; best_score = __builtin_inf(); }
     const double2* gx = a.g_sxy + a.off[tc];
     const int32_t* go = a.g_sorig + a.off[tc];
     const float* gk = a.g_skey + a.off[tc];
@@ -579,7 +579,13 @@ __global__ __launch_bounds__(RSB_THREADS, 4) void rotation_search_batch_kernel(R
     first_argmin_init(sh_arg);
     const int kbest = first_argmin(scores, n_coarse, sh_arg);
     const double cscore = scores[kbest];
-    const int coarse_evals = n_evals;
+    // The coarse angles the record counts: those whose bound does not exceed the winning score — every schedule scores
+    // exactly these (a wave stops only at a bound above the best score SO FAR, which is never below the final one) — and at
+    // least the first angle of each wave, scored before any result exists (at write time, below).  How many more a run
+    // scores depends on when its waves saw each other's results, so n_evals itself is not the same number run after run
+    // (seen: 14 or 15 for one pair) and a record is.
+    for (int k = tid; k < n_coarse; k += RSB_THREADS)
+        if ((double)lb[k] <= cscore) atomicAdd(&n_needed, 1);
     const int nf = a.max_fine > 0 ? min(a.fine_cnt[kbest], a.max_fine) : 0;
     __syncthreads();
     // ── 5. the fine grid around the winner, features.py:227-232 ───────────────
@@ -595,7 +601,7 @@ __global__ __launch_bounds__(RSB_THREADS, 4) void rotation_search_batch_kernel(R
         rsb_write_head(rec, n, m, musx, musy, mutx, muty, nf > 0 ? ICPMI_RSB_ST_OK : ICPMI_RSB_ST_NO_FINE);
         rec[ICPMI_RSREC_K] = (double)kbest; rec[ICPMI_RSREC_CSCORE] = cscore; rec[ICPMI_RSREC_NF] = (double)nf; rec[ICPMI_RSREC_J] = (double)jbest;
         rec[ICPMI_RSREC_FSCORE] = nf > 0 ? scores[jbest] : __builtin_nan("");
-        rec[ICPMI_RSBREC_EVALS] = (double)coarse_evals; rec[ICPMI_RSBREC_FEVALS] = (double)n_evals;
+        rec[ICPMI_RSBREC_EVALS] = (double)max(n_needed, min(n_coarse, RSB_WAVES)); rec[ICPMI_RSBREC_FEVALS] = (double)n_evals;
         if (init) {
             if (nf > 0) {
                 // R = [[ca, -sa], [sa, ca]], t = mu_t - R @ mu_s (features.py:235-237).  The 2 x 2 by 2 product is a BLAS

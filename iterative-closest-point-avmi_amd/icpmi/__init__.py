@@ -4,7 +4,7 @@ Host side of libicpmi.so: ``icpmi.batch`` (batched scan-pair ICP on one GPU),
 ``icpmi.dist`` (the same batch sharded over the GPUs of a node), ``icpmi.synth``
 (synthetic scans), ``icpmi.history`` (``ScanHistory``: past scans kept prepared on the
 device for loop-closure matching), ``icpmi.information`` (the information matrix of an ICP result and the pose-graph
-edge it gives).  The drop-in modules with the reference's own names live in
+edge it gives), ``icpmi.gridmatch`` (correlative scan-to-map matching against the occupancy grid).  The drop-in modules with the reference's own names live in
 the sibling package ``utilities`` (``utilities.icp``, ``utilities.mapping``).
 """
 from ._lib import IcpmiError, build, lib  # noqa: F401

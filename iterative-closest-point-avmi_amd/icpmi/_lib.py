@@ -32,6 +32,10 @@ FT_ST_OK, FT_ST_FEW_ROWS, FT_ST_CAPACITY, FT_ST_FEW_KP, FT_ST_FEW_MATCHES, FT_ST
 # two sizes its kernel is built on (threads of a workgroup, target rows of an LDS tile)
 INFO_DOUBLES, INFO_H, INFO_G, INFO_SSE, INFO_INLIERS, INFO_ROWS, INFO_STATUS = 16, 0, 6, 9, 10, 11, 12
 INFO_THREADS, INFO_TILE_ROWS = 512, 2048
+# icpmi_grid_match_batch (GM_*: capacities, the two sizes its kernels are built on, statuses) and its int32 record (GMREC_*)
+GM_MAX_WINDOW, GM_MAX_ANGLES, GM_MAX_ROWS, GM_MAX_SHIFT_BITS, GM_THREADS, GM_CHUNK_ROWS = 31, 1024, 65535, 14, 256, 256
+GM_ST_OK, GM_ST_EMPTY, GM_ST_CAPACITY = 0, 1, 2
+GMREC_INTS, GMREC_STATUS, GMREC_ROWS, GMREC_INDEX, GMREC_A, GMREC_J, GMREC_I, GMREC_SCORE, GMREC_CENTRE = 8, 0, 1, 2, 3, 4, 5, 6, 7
 INFO_SLOTS = ("H_tt", "H_tx", "H_ty", "H_xx", "H_xy", "H_yy", "g_t", "g_x", "g_y", "sse", "inliers", "rows", "status")
 
 
@@ -154,6 +158,11 @@ _SIGS = {
                                               C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double,
                                               C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int32, C.c_int32,
                                               C.c_int32, C.c_void_p, C.c_void_p]),
+    "icpmi_grid_score_field": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "icpmi_grid_match_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "icpmi_grid_match_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double] + [C.c_void_p] * 4 +
+                               [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "icpmi_pose_graph_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
     "icpmi_pose_graph_optimize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                             C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_size_t,

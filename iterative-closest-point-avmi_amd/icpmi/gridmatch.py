@@ -1,0 +1,138 @@
+"""Correlative scan-to-map matching: clouds scored against the occupancy grid itself over a window of rotations and
+whole-cell shifts (``icpmi_grid_score_field``, ``icpmi_grid_match_batch``; the contract is include/icpmi.h's).
+
+The reference registers a scan against a cloud only (slam.py:53-98, 111-183); this reads the map ``utilities.mapping``
+builds.  The log-odds are quantised to int16 and a candidate's score is the integer sum of the field under the scan's
+cells, so a result is the same bits whatever the launch looks like — and equal to a NumPy restatement of the contract.
+The angles' cos / sin are computed here on the host with NumPy (as ``prealign.AngleTables`` does), and the pose of the
+winner is formed on the host from the record: R from that cos / sin, t = predicted + whole cells.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check
+from .batch import CloudSet, _ptr, _stream, require_gpu
+
+ST_OK, ST_EMPTY, ST_CAPACITY = _lib.GM_ST_OK, _lib.GM_ST_EMPTY, _lib.GM_ST_CAPACITY
+MAX_WINDOW, MAX_ANGLES, MAX_ROWS = _lib.GM_MAX_WINDOW, _lib.GM_MAX_ANGLES, _lib.GM_MAX_ROWS
+
+
+def shift_bits(log_odds_min, log_odds_max):
+    """The largest k in [0, GM_MAX_SHIFT_BITS] with max(|log_odds_min|, |log_odds_max|) * 2^k <= 32767 (0 when none is)."""
+    m = max(abs(float(log_odds_min)), abs(float(log_odds_max)))
+    for k in range(_lib.GM_MAX_SHIFT_BITS, 0, -1):
+        if m * 2.0 ** k <= 32767.0:
+            return k
+    return 0
+
+
+def score_field(log_odds, k, out=None):
+    """``icpmi_grid_score_field`` of a float32 (ny, nx) device tensor -> the int16 (ny, nx) field (``out`` when given)."""
+    ny, nx = log_odds.shape
+    if log_odds.dtype != torch.float32 or not log_odds.is_contiguous():
+        raise ValueError("log_odds must be a contiguous float32 (ny, nx) device tensor")
+    if out is None:
+        out = torch.empty((ny, nx), dtype=torch.int16, device=log_odds.device)
+    check(_lib.lib().icpmi_grid_score_field(_ptr(log_odds), ny, nx, int(k), _ptr(out), _stream()), "grid_score_field")
+    return out
+
+
+def angle_grid(theta, angular_window, angular_step):
+    """theta + np.deg2rad(np.arange(-range, range + step, step)), the expression of slam.py:146-148, for every theta
+    -> (angles [B, A], index of the offset nearest to zero)."""
+    offsets = np.deg2rad(np.arange(-angular_window, angular_window + angular_step, angular_step))
+    if len(offsets) == 0:
+        raise ValueError("the angle grid is empty: angular_window and angular_step must be positive")
+    theta = np.asarray(theta, dtype=np.float64).reshape(-1)
+    return theta[:, None] + offsets[None, :], int(np.argmin(np.abs(offsets)))
+
+
+class GridMatchBatch:
+    """Pair b: cloud ``pair_clouds[b]`` of ``cloud_set`` scored against ``grid`` at the translation ``translations[b]``
+    under the rotations ``angle_rows[b]`` (radians, [B, A]) and every shift of whole cells within ``window``.
+
+    ``grid``: anything with ``device_log_odds`` (float32 (ny, nx) device tensor), ``min_x``, ``min_y``, ``resolution``,
+    ``log_odds_min`` and ``log_odds_max`` — a ``utilities.mapping.OccupancyGrid2D``.  ``field``: a ``(tensor, k)`` an earlier
+    ``score_field`` returned, to score against the map as it was then; ``None``: the field is rebuilt by every ``run()``.
+    ``run()`` enqueues the launches on the current stream and returns the (B, 8) int32 record tensor, without a
+    synchronisation; ``want_scores``: ``scores`` then holds the full (B, A, S, S) int32 volume.  ``unpack()`` reads the
+    records back and forms the poses."""
+
+    def __init__(self, grid, cloud_set, pair_clouds, translations, angle_rows, window, centre_angle=-1, field=None, want_scores=False):
+        require_gpu()
+        if cloud_set.dim != 2:
+            raise ValueError("grid matching is 2-D")
+        self.grid, self.cs, self.field = grid, cloud_set, field
+        dev = cloud_set.pts.device
+        self.pair_host = np.ascontiguousarray(pair_clouds, dtype=np.int32).reshape(-1)
+        self.B = B = len(self.pair_host)
+        self.t_host = np.ascontiguousarray(np.asarray(translations, dtype=np.float64).reshape(B, 2))
+        self.angles = np.ascontiguousarray(np.asarray(angle_rows, dtype=np.float64).reshape(B, -1))
+        self.A, self.W, self.centre_angle = self.angles.shape[1], int(window), int(centre_angle)
+        self.S = 2 * self.W + 1
+        if not 0 <= self.W <= MAX_WINDOW:
+            raise ValueError(f"window must lie in [0, {MAX_WINDOW}] cells, got {self.W}")
+        if not 1 <= self.A <= MAX_ANGLES:
+            raise ValueError(f"between 1 and {MAX_ANGLES} angles per pair, got {self.A}")
+        if self.centre_angle >= self.A:
+            raise ValueError("centre_angle must be negative (none) or an index into the angle rows")
+        if B and (self.pair_host.min() < 0 or self.pair_host.max() >= cloud_set.n_clouds):
+            raise ValueError("pair_clouds must index the cloud set")
+        if B and int(np.diff(cloud_set.off_host)[self.pair_host].max()) > MAX_ROWS:
+            raise ValueError(f"a cloud above {MAX_ROWS} rows cannot be scored (int32 sums): filter it first")
+        self.cos_sin_host = np.ascontiguousarray(np.stack([np.cos(self.angles), np.sin(self.angles)], axis=2))
+        self.pair = torch.from_numpy(self.pair_host).to(dev)
+        self.t = torch.from_numpy(self.t_host).to(dev)
+        self.cos_sin = torch.from_numpy(self.cos_sin_host).to(dev)
+        self.k = shift_bits(grid.log_odds_min, grid.log_odds_max) if field is None else int(field[1])
+        self.records = torch.zeros((max(B, 1), _lib.GMREC_INTS), dtype=torch.int32, device=dev)
+        self.scores = torch.zeros((max(B, 1), self.A, self.S, self.S), dtype=torch.int32, device=dev) if want_scores else None
+        need = _lib.lib().icpmi_grid_match_workspace_bytes(B, self.A, self.W)
+        self.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        self._field_buf = None
+
+    def run(self):
+        g = self.grid
+        lo = g.device_log_odds
+        if self.field is not None:
+            fld = self.field[0]
+            if tuple(fld.shape) != tuple(lo.shape) or fld.dtype != torch.int16:
+                raise ValueError("field must be the int16 (ny, nx) tensor score_field() returned for this grid")
+        else:
+            fld = self._field_buf = score_field(lo, self.k, self._field_buf)
+        ny, nx = lo.shape
+        cs = self.cs
+        check(_lib.lib().icpmi_grid_match_batch(
+            _ptr(fld), ny, nx, float(g.min_x), float(g.min_y), float(g.resolution), _ptr(cs.pts), _ptr(cs.off),
+            cs.off_host.ctypes.data_as(C.c_void_p), _ptr(cs.cnt), cs.n_clouds, _ptr(self.pair),
+            self.pair_host.ctypes.data_as(C.c_void_p), self.B, _ptr(self.t), _ptr(self.cos_sin), self.A, self.W,
+            self.centre_angle, _ptr(self.records), _ptr(self.scores), _ptr(self.ws), self.ws.numel(), _stream()), "grid_match")
+        return self.records
+
+    def unpack(self, records=None):
+        """-> (R [B,2,2], t [B,2], score [B] int, info) on the host (synchronises).  t = translation + ((i - W), (j - W)) *
+        resolution, R from the caller's cos / sin at a.  info: ``status``, ``rows``, ``index``, ``a``, ``j``, ``i``,
+        ``centre_score``, ``shift_bits``, ``angle`` and ``mean_log_odds`` = score / (rows * 2^k), the mean log-odds under the
+        hits (0 where no row was scored)."""
+        rec = (self.records if records is None else records).cpu().numpy()[:self.B].astype(np.int64)
+        col = lambda s: rec[:, s].copy()                       # noqa: E731
+        a, j, i, score, rows = (col(s) for s in (_lib.GMREC_A, _lib.GMREC_J, _lib.GMREC_I, _lib.GMREC_SCORE, _lib.GMREC_ROWS))
+        b = np.arange(self.B)
+        co, si = self.cos_sin_host[b, a, 0], self.cos_sin_host[b, a, 1]
+        R = np.stack([np.stack([co, -si], axis=1), np.stack([si, co], axis=1)], axis=1)
+        res = float(self.grid.resolution)
+        t = np.stack([self.t_host[:, 0] + (i - self.W) * res, self.t_host[:, 1] + (j - self.W) * res], axis=1)
+        info = {"status": col(_lib.GMREC_STATUS), "rows": rows, "index": col(_lib.GMREC_INDEX), "a": a, "j": j, "i": i,
+                "centre_score": col(_lib.GMREC_CENTRE), "shift_bits": self.k, "angle": self.angles[b, a],
+                "mean_log_odds": np.where(rows > 0, score / (np.maximum(rows, 1) * 2.0 ** self.k), 0.0)}
+        return R, t, score, info
+
+
+def cloud_set_of(clouds, voxel_size=None):
+    """The clouds as a device ``CloudSet`` (one as it is), through the voxel filter of icp.py:117-129 when a size is given."""
+    from .batch import voxel_downsample_set
+    cs = clouds if isinstance(clouds, CloudSet) else CloudSet.from_numpy(clouds)
+    return voxel_downsample_set(cs, voxel_size) if voxel_size is not None else cs

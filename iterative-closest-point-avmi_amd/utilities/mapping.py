@@ -299,6 +299,92 @@ class OccupancyGrid2D:
         self._host = None
         self._full_clip = not (self.log_odds_min <= 0.0 <= self.log_odds_max)
 
+    # ── reading the map: correlative scan-to-map matching (icpmi.gridmatch; no counterpart in the reference) ─────────
+    def score_field(self):
+        """-> (field, k): the log-odds as the matcher reads them, an int16 (ny, nx) device tensor
+        clip(rint(log_odds * 2^k), -32767, 32767), and k = ``icpmi.gridmatch.shift_bits`` of the clamps (12 for +-5).
+        Built anew at every call — there is no cache, so no update has to invalidate one.  The matching methods build one
+        per call too, unless one is passed back as ``field=``: they then score against the map as it was when that field
+        was made, whatever has been applied since."""
+        from icpmi import gridmatch
+        k = gridmatch.shift_bits(self.log_odds_min, self.log_odds_max)
+        return gridmatch.score_field(self._grid, k), k
+
+    @staticmethod
+    def _xytheta(poses, n=None):
+        """Predicted poses as (n, 3) rows [x, y, theta]: given as such, or as a stack of 3 x 3 matrices (theta as
+        slam.py:131-132)."""
+        p = np.asarray(poses, dtype=np.float64)
+        if p.ndim == 3 and p.shape[1:] == (3, 3):
+            p = np.stack([p[:, 0, 2], p[:, 1, 2], np.arctan2(p[:, 1, 0], p[:, 0, 0])], axis=1)
+        elif p.ndim > 2 or p.size % 3:
+            raise ValueError("poses must be rows [x, y, theta] or a stack of 3 x 3 matrices")
+        p = p.reshape(-1, 3)
+        if n is not None and len(p) != n:
+            raise ValueError(f"{n} scans but {len(p)} predicted poses")
+        return p
+
+    def _match_set(self, cs, pair_clouds, poses, linear_window, angular_window, angular_step, field, want_scores=False):
+        from icpmi import gridmatch
+        if cs.pts.device != self._dev:
+            raise ValueError(f"the clouds live on {cs.pts.device}, the grid on {self._dev}")
+        xyt = self._xytheta(poses, len(pair_clouds))
+        if angular_step is None:                                   # score_poses: the pose itself and nothing around it
+            angles, centre, W = xyt[:, 2:3], 0, 0
+        else:
+            angles, centre = gridmatch.angle_grid(xyt[:, 2], angular_window, angular_step)
+            W = int(round(linear_window / self.resolution))
+        job = gridmatch.GridMatchBatch(self, cs, pair_clouds, xyt[:, :2], angles, W, centre, field=field, want_scores=want_scores)
+        job.run()
+        return job
+
+    def match_scans(self, clouds, predicted_poses, linear_window=0.6, angular_window=12.0, angular_step=1.0, voxel_size=None,
+                    field=None):
+        """Localise every scan of ``clouds`` (sensor frame, (n, 2) arrays or a device ``CloudSet``) in this map around its
+        predicted pose ([x, y, theta] or a 3 x 3 matrix): the pose among theta + np.deg2rad(np.arange(-angular_window,
+        angular_window + angular_step, angular_step)) (slam.py:146-148's expression) and shifts of whole cells up to
+        W = int(round(linear_window / resolution)) each way that puts the scan's hits on the largest sum of log-odds.
+        ``voxel_size``: the scans pass through ``voxel_downsample`` first.  One chain of launches for all scans.
+        -> (R [B,2,2], t [B,2], score [B], info) as ``icpmi.gridmatch.GridMatchBatch.unpack`` forms them."""
+        from icpmi import gridmatch
+        cs = gridmatch.cloud_set_of(clouds, voxel_size)
+        return self._match_set(cs, np.arange(cs.n_clouds), predicted_poses, linear_window, angular_window, angular_step, field).unpack()
+
+    def match_scan(self, points_local, predicted_pose, linear_window=0.6, angular_window=12.0, angular_step=1.0, voxel_size=None,
+                   field=None):
+        """``match_scans`` of one scan -> (R (2,2), t (2,), score, info) with scalar entries in ``info``."""
+        R, t, score, info = self.match_scans([points_local], [predicted_pose], linear_window, angular_window, angular_step,
+                                             voxel_size, field)
+        return R[0], t[0], int(score[0]), {k: (v[0] if isinstance(v, np.ndarray) else v) for k, v in info.items()}
+
+    def score_poses(self, points_local, poses, field=None):
+        """The score of one scan at every pose of ``poses`` ((P, 3) rows [x, y, theta] or 3 x 3 matrices): the same kernel
+        with one angle and no shifts per pose (pass one matrix as a stack of one) — weights for a particle filter, or a check of a loop closure before its edge
+        goes into the graph -> (score [P], info)."""
+        from icpmi import gridmatch
+        cs = gridmatch.cloud_set_of([points_local])
+        xyt = self._xytheta(poses)
+        _, _, score, info = self._match_set(cs, np.zeros(len(xyt), dtype=np.int32), xyt, 0.0, 0.0, None, field).unpack()
+        return score, info
+
+    def match_history(self, history, ids, predicted_poses, linear_window=0.6, angular_window=12.0, angular_step=1.0, voxel_size=None,
+                      field=None):
+        """``match_scans`` of scans resident in an ``icpmi.ScanHistory``, by id: the raw rows are read where they are and no
+        scan is uploaded.  ``voxel_size``: the history's own filtered copies where it is one of the history's voxel sizes;
+        any other size filters every resident scan first."""
+        from icpmi import history as _h
+        from icpmi.batch import voxel_downsample_set
+        ids = _h._scan_ids(ids, ("ids", "scan ids"), history.n_scans)
+        if voxel_size is None:
+            cs = history.raw
+        elif float(voxel_size) == history.voxel_size:
+            cs = history.vox
+        elif float(voxel_size) == history.rotation_voxel_size:
+            cs = history.rs_vox
+        else:
+            cs = voxel_downsample_set(history.raw, voxel_size)
+        return self._match_set(cs, ids, predicted_poses, linear_window, angular_window, angular_step, field).unpack()
+
     # ── probability / display, mapping.py:150-166 (NumPy on the host copy) ───
     def to_probability(self):
         return 1.0 / (1.0 + np.exp(-self.log_odds))

@@ -1,0 +1,99 @@
+#!/usr/bin/env python3
+"""Correlative scan-to-map matching (icpmi.gridmatch.GridMatchBatch behind OccupancyGrid2D.match_scan / match_history /
+score_poses) on bench.py's config-4 grid (2 242 x 2 402 cells at 0.05 m, 32 scans applied), one process on one GPU, device
+events around run(), the variants alternating:
+
+  (a) one 1 430-row scan, 25 angles x 13^2 shifts (W = 6), the field rebuilt by every run — what match_scan enqueues;
+  (k) the same with the field kept (field=): scoring and arg-max alone;
+  (f) the field alone (icpmi_grid_score_field of the whole grid);
+  (b) 512 resident 2 048-beam scans of a ScanHistory by id, 25 angles x 13^2 shifts each, field kept;
+  (c) 4 096 poses of the 1 430-row scan through the score_poses shape (one angle, no shifts), field kept.
+
+A sample is BLOCK runs back to back between two events, divided by BLOCK; SAMPLES samples per variant after a warm-up of
+each.  (a) is sampled twice, as a1 and a2, in the same alternation: |median a1 - median a2| is the run-to-run spread a
+difference has to exceed.  There is no earlier capability to compare a time against: the numbers stand on their own.
+
+usage: time_gridmatch.py [samples] [block]   (prints one JSON line)"""
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "iterative-closest-point-avmi_amd"))
+sys.path.insert(0, REPO)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from icpmi import ScanHistory, synth  # noqa: E402
+from icpmi.batch import CloudSet  # noqa: E402
+from icpmi.gridmatch import GridMatchBatch, angle_grid  # noqa: E402
+
+SAMPLES = int(sys.argv[1]) if len(sys.argv) > 1 else 15
+BLOCK = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+N_HIST, N_POSES, ROWS, W = 512, 4096, 1430, 6
+
+
+def sample(fn, block=BLOCK):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(block):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / block
+
+
+def stats(v):
+    q1, med, q3 = np.percentile(v, [25, 50, 75])
+    return {"median_ms": round(float(med), 4), "q1_ms": round(float(q1), 4), "q3_ms": round(float(q3), 4),
+            "min_ms": round(float(np.min(v)), 4), "max_ms": round(float(np.max(v)), 4), "samples": len(v)}
+
+
+assert torch.cuda.is_available(), "time_gridmatch.py measures on the GPU: there is nothing to time without one"
+import bench  # noqa: E402
+grid, org, hits, _ = bench.raycast_workload(synth, 32)
+grid.update_scans(org, hits)
+field = grid.score_field()
+
+rng = np.random.default_rng(0)
+true = (0.5, -0.1, np.deg2rad(14.0))
+full = synth.scan(true, 4242)
+scan = full[np.linspace(0, len(full) - 1, ROWS).astype(np.int64)]
+pred = (true[0] + 0.12, true[1] - 0.08, true[2] + np.deg2rad(3.0))
+angles, centre = angle_grid([pred[2]], 12.0, 1.0)
+one = CloudSet.from_numpy([scan])
+a = GridMatchBatch(grid, one, [0], [pred[:2]], angles, W, centre)
+k = GridMatchBatch(grid, one, [0], [pred[:2]], angles, W, centre, field=field)
+
+poses = [(0.3 + 0.02 * (i % 32) + rng.uniform(-0.1, 0.1), -0.2 + 0.01 * (i % 32) + rng.uniform(-0.1, 0.1),
+          np.deg2rad(10.0 + 0.5 * (i % 32) + rng.uniform(-3.0, 3.0))) for i in range(N_HIST)]
+hist = ScanHistory(scan_capacity=N_HIST, row_capacity=N_HIST * 2048)
+ids = hist.add_many([synth.scan(p, 6000 + i) for i, p in enumerate(poses)])
+P = np.array(poses)
+hangles, hcentre = angle_grid(P[:, 2] + np.deg2rad(2.0), 12.0, 1.0)
+b = GridMatchBatch(grid, hist.raw, ids, P[:, :2] + 0.1, hangles, W, hcentre, field=field)
+
+hyp = np.array(true) + rng.uniform(-1.0, 1.0, size=(N_POSES, 3)) * np.array([0.5, 0.5, 0.2])
+c = GridMatchBatch(grid, one, np.zeros(N_POSES, dtype=np.int32), hyp[:, :2], hyp[:, 2:3], 0, 0, field=field)
+
+variants = {"a1": a.run, "k": k.run, "f": grid.score_field, "b": b.run, "c": c.run, "a2": a.run}
+for fn in variants.values():
+    sample(fn, 3)
+# what the runs found, once: the single scan's error against its true pose, the batch's statuses
+_, t, score, info = a.unpack()
+found = {"err_m": [round(float(abs(t[0, i] - true[i])), 4) for i in (0, 1)], "err_deg": round(float(np.rad2deg(abs(info["angle"][0] - true[2]))), 3),
+         "score": int(score[0]), "centre_score": int(info["centre_score"][0]), "equal_with_field_kept": bool(np.array_equal(a.records.cpu().numpy(), k.records.cpu().numpy())),
+         "history_status_ok": int((b.unpack()[3]["status"] == 0).sum()), "poses_status_ok": int((c.unpack()[3]["status"] == 0).sum())}
+times = {name: [] for name in variants}
+for _ in range(SAMPLES):
+    for name, fn in variants.items():
+        times[name].append(sample(fn))
+both = np.array(times["a1"] + times["a2"])
+out = {"grid": [grid.ny, grid.nx], "resolution": grid.resolution, "block": BLOCK, "found": found,
+       "a_one_scan_25x13x13_field_rebuilt": stats(both), "a1": stats(times["a1"]), "a2": stats(times["a2"]),
+       "a_spread_ms": round(abs(float(np.median(times["a1"]) - np.median(times["a2"]))), 4),
+       "k_one_scan_field_kept": stats(times["k"]), "f_field_alone": stats(times["f"]),
+       f"b_{N_HIST}_history_scans_25x13x13": stats(times["b"]), f"c_{N_POSES}_poses": stats(times["c"]),
+       "b_candidates_per_s": round(N_HIST * 25 * 169 * 1e3 / float(np.median(times["b"]))),
+       "c_poses_per_s": round(N_POSES * 1e3 / float(np.median(times["c"])))}
+print(json.dumps(out))
