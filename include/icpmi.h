@@ -750,6 +750,56 @@ int icpmi_grid_match_batch(const int16_t* field, int32_t ny, int32_t nx, double 
                            int32_t window, int32_t centre_angle, int32_t* out_records, int32_t* out_scores,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the same search over a wide window: bounded blocks, the exhaustive winner ---------------------------------------
+ * icpmi_grid_search_batch returns what icpmi_grid_match_batch would over a window of up to ICPMI_GMW_MAX_WINDOW cells,
+ * without forming the volume.  Fields, cells, scores, clouds, cnt_dev, the statuses and the record's first eight int32 are
+ * icpmi_grid_match_batch's, unchanged; n_angles may go up to ICPMI_GMW_MAX_ANGLES, and n_angles * S^2 >= 2^31 (S = 2W + 1)
+ * is refused.  The winner is the first maximum over (a, j, i) in C order of the full exhaustive volume.
+ *
+ * icpmi_grid_bound_field: with D = block in {4, 8, 16} and q~ the int16 field extended by 0 outside the grid,
+ *   M(y, x) = max over 0 <= dy, dx < D of q~(y + dy, x + dx)   for y in [-(D - 1), ny), x in [-(D - 1), nx),
+ * stored as out[y + D - 1][x + D - 1], int16 of shape (ny + D - 1, nx + D - 1); M is 0 outside that domain.  Both pointers
+ * 16-byte aligned; ny * nx == 0: no launch, ICPMI_OK; (ny + D - 1) * (nx + D - 1) >= 2^31 or another block: ICPMI_ERR_ARG.
+ *
+ * Blocks: NB = ceil(S / D) per axis; block (a, J, I) holds the shifts j in [J * D, min((J + 1) * D, S)) and i likewise.
+ *   U[b][a][J][I] = sum over the rows with a cell at angle a of M(cy + J * D - W, cx + I * D - W),
+ * int32, no smaller than any score of the block.  The search, all on the caller's stream without a host synchronisation:
+ * (1) U for every block; (2) for each angle the first block in C order of maximal U is scored exactly, and best0[b] is the
+ * largest exact score over these n_angles seed blocks; (3) every block with U >= best0 survives (>=: a block whose bound
+ * equals best0 may hold an equal score at a lower index) and is scored exactly, shifts with j >= S or i >= S ignored;
+ * (4) the winner is the largest exact score, on equal scores the lower flat index a * S^2 + j * S + i.  Every flat index that
+ * attains the true maximum m lies in a block with U >= m >= best0, which survives: the record equals the exhaustive one.
+ * out_records [n_pairs][ICPMI_GMW_REC_INTS] int32: slots 0-7 are ICPMI_GMREC_* (slot 7, the exact score of (centre_angle,
+ * W, W), is always evaluated, pruned or not; 0 when centre_angle < 0); ICPMI_GMW_REC_BLOCKS: n_angles * NB^2;
+ * ICPMI_GMW_REC_SURVIVORS: blocks with U >= best0; ICPMI_GMW_REC_SEED: best0; ICPMI_GMW_REC_MAX_BOUND: the largest U.  All
+ * twelve are functions of the inputs alone.  An EMPTY or CAPACITY pair has every U and score 0: every block survives, index 0.
+ * bound: icpmi_grid_bound_field's output for `field` and `block`.  out_bounds (optional): receives U, [n_pairs][n_angles]
+ * [NB][NB] int32 (accumulated there instead of in the workspace).  workspace: icpmi_grid_search_workspace_bytes(n_pairs,
+ * n_angles, window, block) bytes (0 for a negative argument or another block) — two int32 per block, and per (pair, angle)
+ * and per pair a few words; the call zeroes what it accumulates into, so a workspace is reusable as it is.
+ * Refusals, on the host before any launch, are icpmi_grid_match_batch's, with: a block outside {4, 8, 16}: ICPMI_ERR_ARG;
+ * window > ICPMI_GMW_MAX_WINDOW, n_angles > ICPMI_GMW_MAX_ANGLES, n_angles * S^2 >= 2^31 or n_pairs * n_angles * NB^2 >=
+ * 2^31: ICPMI_ERR_UNSUPPORTED.  Launches: two memsets; the bound pass (gm_score_kernel's walk over M, lanes owning blocks);
+ * one arg-max workgroup per (pair, angle); the seeds' exact scores, one workgroup per seed block over all rows of its cloud,
+ * merged by one 64-bit atomicMax on (score + 2^31) << 32 | (0xFFFFFFFF - flat); a compaction of the survivors; their exact
+ * scores by a fixed grid of at most ICPMI_GMW_SCORE_GROUPS workgroups striding over the device-side count; the records. */
+#define ICPMI_GMW_MAX_WINDOW 255
+#define ICPMI_GMW_MAX_ANGLES 16384
+#define ICPMI_GMW_SCORE_GROUPS 2048
+#define ICPMI_GMW_REC_INTS 12
+#define ICPMI_GMW_REC_BLOCKS 8
+#define ICPMI_GMW_REC_SURVIVORS 9
+#define ICPMI_GMW_REC_SEED 10
+#define ICPMI_GMW_REC_MAX_BOUND 11
+int icpmi_grid_bound_field(const int16_t* field, int32_t ny, int32_t nx, int32_t block, int16_t* out, void* stream);
+size_t icpmi_grid_search_workspace_bytes(int32_t n_pairs, int32_t n_angles, int32_t window, int32_t block);
+int icpmi_grid_search_batch(const int16_t* field, const int16_t* bound, int32_t ny, int32_t nx, double min_x, double min_y,
+                            double resolution, const double* pts, const int32_t* off_dev, const int32_t* off_host,
+                            const int32_t* cnt_dev, int32_t n_clouds, const int32_t* pair_cloud,
+                            const int32_t* pair_cloud_host, int32_t n_pairs, const double* pair_t, const double* cos_sin,
+                            int32_t n_angles, int32_t window, int32_t block, int32_t centre_angle, int32_t* out_records,
+                            int32_t* out_bounds, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ── pose graph: PoseGraph2D.optimize, utilities/pose_graph.py:83-134 ──────────
  * Gauss-Newton on SE(2) over n_nodes poses [x, y, theta] (nodes: device, updated
  * in place) and n_edges constraints (i, j, z_ij [3], Omega [3][3] row-major).

@@ -4,20 +4,13 @@
 // of a (2W + 1)^2 window the sum of the field under the scan's cells.  Cells are formed once in float64 exactly as
 // world_to_grid does (mapping.py:94-98); everything after that is integer, so any split of the rows over workgroups and any
 // order of the integer atomics gives the same bits.
-#include "common.hpp"
+#include "gridmatch.hpp"
 
 namespace icpmi {
 
-constexpr int GM_THREADS = ICPMI_GM_THREADS;
-constexpr int GM_WAVES = GM_THREADS / ICPMI_WAVE;
-constexpr int GM_CHUNK = ICPMI_GM_CHUNK_ROWS;              // source rows of one workgroup
 constexpr int GM_MAX_NS = 16;                              // shifts a lane owns, at most
-constexpr int GM_CELL_MAX = 1 << 29;                       // a row whose cell lies beyond +-2^29 is not scored
-constexpr int GM_FAR = 1 << 30;                            // an offset no cell reaches the grid with (nx, ny <= 2^29)
 constexpr int GM_FIELD_VEC = 8;                            // cells a thread of the field kernel converts
-static_assert(GM_CHUNK == GM_THREADS, "a thread forms one cell of the chunk");
 static_assert((2 * ICPMI_GM_MAX_WINDOW + 1) * (2 * ICPMI_GM_MAX_WINDOW + 1) <= GM_MAX_NS * GM_THREADS, "every shift has an owner");
-static_assert((long long)ICPMI_GM_MAX_ROWS * 32767 < (1ll << 31), "a score is an int32");
 static_assert(ICPMI_GMREC_CENTRE + 1 == ICPMI_GMREC_INTS, "the record is eight int32");
 
 // ── the score field ──────────────────────────────────────────────────────────
@@ -44,56 +37,13 @@ __global__ __launch_bounds__(GM_THREADS) void gm_field_kernel(const float* __res
 }
 
 // ── scoring ──────────────────────────────────────────────────────────────────
-struct GmArgs {
-    const short* field;
-    int ny, nx;
-    double min_x, min_y, res;
-    const double* pts;
-    const int32_t* off;
-    const int32_t* cnt;
-    const int32_t* pair_cloud;
-    const double* pair_t;
-    const double* cos_sin;
-    int n_angles, window, centre_angle, n_chunks;
-    int32_t* valid;          // [n_pairs][n_angles]: rows with a cell, per angle
-    int32_t* volume;         // [n_pairs][n_angles][S][S]
-    int32_t* records;
-};
-
-// rows of a pair's cloud: the device count where the set has one; -1 for a count that is negative (the voxel filter's
-// overflow mark) or beyond the cloud's own rows or ICPMI_GM_MAX_ROWS — such a cloud is not read (ICPMI_GM_ST_CAPACITY)
-__device__ __forceinline__ int gm_rows(const GmArgs& a, int c) {
-    const int cap = a.off[c + 1] - a.off[c];
-    const int n = a.cnt ? a.cnt[c] : cap;
-    return n < 0 || n > cap || n > ICPMI_GM_MAX_ROWS ? -1 : n;
-}
-
-// floor((w - mn) / res), the IEEE divide of world_to_grid_kernel; false for a non-finite w or a cell beyond +-2^29
-__device__ __forceinline__ bool gm_cell(double w, double mn, double res, int& out) {
-    if (!(fabs(w) < __builtin_inf())) return false;
-    const double f = floor((w - mn) / res);
-    if (!(fabs(f) <= (double)GM_CELL_MAX)) return false;
-    out = (int)f;
-    return true;
-}
-
-// The workgroup's static LDS: the chunk's cells (only rows whose window reaches the grid; the slots behind them, one past the
-// chunk included, hold a cell that fails every bounds test), how many there are, how many rows had a cell at all, and —
-// where several lanes share a shift — the shifts' sums.
-struct GmLds {
-    int2 cells[GM_CHUNK + 1];
-    int acc[GM_THREADS];
-    int kept, valid;
-};
-
-// One workgroup per (pair, angle, chunk of GM_CHUNK rows).  Phase 1: thread r forms the cell of row r of the chunk in float64.
-// Phase 2, NS > 1 (S^2 > GM_THREADS): lane t owns the shifts t, t + GM_THREADS, ... with their sums in registers and walks
-// every kept cell, the cell read as an LDS broadcast; lanes with consecutive i read consecutive int16 of a grid row.
-// NS == 1 (S^2 <= GM_THREADS): G = GM_THREADS / S^2 groups of lanes share the rows (group g takes rows g, g + G, ...), lane
-// t owning shift t mod S^2, and the groups meet in LDS integer adds.  The walk is branch-free — a load that fails the bounds
-// test reads cell 0 of the field and adds 0 — so the loads of U cells (4, 2 or 1) times NS shifts are in flight together instead
-// of one at a time.  Either way the workgroup ends with ONE int32 atomicAdd per shift into the volume (zeroed on the stream
-// before the launch).  No workgroup waits for another.
+// One workgroup per (pair, angle, chunk of GM_CHUNK rows).  Phase 1 (gm_form_cells): thread r forms the cell of row r of the
+// chunk in float64.  Phase 2 (gm_accumulate over the S^2 shifts, rows of S, step 1 from -W), NS > 1 (S^2 > GM_THREADS): lane t
+// owns the shifts t, t + GM_THREADS, ... with their sums in registers and walks every kept cell, the cell read as an LDS
+// broadcast; lanes with consecutive i read consecutive int16 of a grid row.  NS == 1 (S^2 <= GM_THREADS): G = GM_THREADS /
+// S^2 groups of lanes share the rows (group g takes rows g, g + G, ...), lane t owning shift t mod S^2, and the groups meet
+// in LDS integer adds.  The walk is branch-free (gm_walk).  Either way the workgroup ends with ONE int32 atomicAdd per shift
+// into the volume (zeroed on the stream before the launch).  No workgroup waits for another.
 template <int NS>
 __global__ __launch_bounds__(GM_THREADS) void gm_score_kernel(GmArgs a) {
     __shared__ GmLds lds;
@@ -106,73 +56,12 @@ __global__ __launch_bounds__(GM_THREADS) void gm_score_kernel(GmArgs a) {
     const int base = chunk * GM_CHUNK;
     if (base >= N) return;                                     // uniform per workgroup, before any barrier
     const int W = a.window, S = 2 * W + 1, S2 = S * S;
-    if (tid == 0) { lds.kept = 0; lds.valid = 0; }
     if (NS == 1) lds.acc[tid] = 0;
-    __syncthreads();
-
-    const int row = base + tid;
-    if (row < N) {
-        const double* p = a.pts + ((size_t)a.off[c] + row) * 2;
-        const double* cs = a.cos_sin + ((size_t)b * a.n_angles + ang) * 2;
-        const double x = p[0], y = p[1], co = cs[0], si = cs[1];
-        const double wx = (co * x - si * y) + a.pair_t[2 * b];         // as include/icpmi.h states it (no contraction)
-        const double wy = (si * x + co * y) + a.pair_t[2 * b + 1];
-        int cx, cy;
-        if (gm_cell(wx, a.min_x, a.res, cx) && gm_cell(wy, a.min_y, a.res, cy)) {
-            atomicAdd(&lds.valid, 1);
-            // a row whose whole window misses the grid adds 0 to every candidate: dropped here
-            if (cx + W >= 0 && cx - W < a.nx && cy + W >= 0 && cy - W < a.ny) lds.cells[atomicAdd(&lds.kept, 1)] = make_int2(cx, cy);
-        }
-    }
-    __syncthreads();
-    const int kept = lds.kept;
+    // a row whose whole window misses the grid adds 0 to every candidate: dropped in phase 1
+    const int kept = gm_form_cells(lds, a, b, ang, c, N, base, GmReach{-W, W, -W, W, a.nx, a.ny});
     if (tid == 0 && lds.valid) atomicAdd(a.valid + (size_t)b * a.n_angles + ang, lds.valid);
     if (kept == 0) return;                                     // uniform
-    const int2 far = make_int2(GM_FAR, GM_FAR);
-    if (tid >= kept) lds.cells[tid] = far;                     // what the unrolled walk reads behind the kept cells
-    if (tid == 0) lds.cells[GM_CHUNK] = far;
-    __syncthreads();
-
-    const int G = NS == 1 ? GM_THREADS / S2 : 1;               // lane groups that share the rows
-    const int g = NS == 1 ? tid / S2 : 0;
-    int dx[NS], dy[NS], acc[NS];
-#pragma unroll
-    for (int k = 0; k < NS; ++k) {
-        const int s = NS == 1 ? tid - g * S2 : tid + k * GM_THREADS;
-        const bool owns = NS == 1 ? g < G : s < S2;
-        dx[k] = owns ? s % S - W : GM_FAR;                     // a lane without a shift fails every bounds test
-        dy[k] = owns ? s / S - W : GM_FAR;
-        acc[k] = 0;
-    }
-    const unsigned nx = (unsigned)a.nx, ny = (unsigned)a.ny;
-    constexpr int U = NS == 1 ? 4 : (NS <= 4 ? 2 : 1);         // cells per step: U * NS loads in flight
-    for (int r = NS == 1 && g >= G ? kept : g; r < kept; r += G * U) {         // (a lane without a shift walks nothing)
-        int2 cell[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) cell[u] = lds.cells[min(r + u * G, GM_CHUNK)];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-#pragma unroll
-            for (int k = 0; k < NS; ++k) {                     // unsigned sums: far + far wraps to 2^31, still out of bounds
-                const unsigned x = (unsigned)cell[u].x + (unsigned)dx[k], y = (unsigned)cell[u].y + (unsigned)dy[k];
-                const bool in = x < nx && y < ny;
-                const int v = a.field[in ? y * nx + x : 0u];
-                acc[k] += in ? v : 0;
-            }
-        }
-    }
-    int32_t* vol = a.volume + ((size_t)b * a.n_angles + ang) * S2;
-    if (NS == 1) {
-        if (g < G && acc[0]) atomicAdd(&lds.acc[tid - g * S2], acc[0]);
-        __syncthreads();
-        if (tid < S2 && lds.acc[tid]) atomicAdd(vol + tid, lds.acc[tid]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < NS; ++k) {
-            const int s = tid + k * GM_THREADS;
-            if (s < S2 && acc[k]) atomicAdd(vol + s, acc[k]);
-        }
-    }
+    gm_accumulate<NS>(lds, a.field, a.nx, a.ny, kept, S2, S, 1, -W, 0, a.volume + ((size_t)b * a.n_angles + ang) * S2);
 }
 
 // ── arg-max and record ───────────────────────────────────────────────────────

@@ -36,6 +36,9 @@ INFO_THREADS, INFO_TILE_ROWS = 512, 2048
 GM_MAX_WINDOW, GM_MAX_ANGLES, GM_MAX_ROWS, GM_MAX_SHIFT_BITS, GM_THREADS, GM_CHUNK_ROWS = 31, 1024, 65535, 14, 256, 256
 GM_ST_OK, GM_ST_EMPTY, GM_ST_CAPACITY = 0, 1, 2
 GMREC_INTS, GMREC_STATUS, GMREC_ROWS, GMREC_INDEX, GMREC_A, GMREC_J, GMREC_I, GMREC_SCORE, GMREC_CENTRE = 8, 0, 1, 2, 3, 4, 5, 6, 7
+# icpmi_grid_search_batch (GMW_*: its capacities, its planned survivor grid, and the four slots its record adds to GMREC_*)
+GMW_MAX_WINDOW, GMW_MAX_ANGLES, GMW_SCORE_GROUPS = 255, 16384, 2048
+GMW_REC_INTS, GMW_REC_BLOCKS, GMW_REC_SURVIVORS, GMW_REC_SEED, GMW_REC_MAX_BOUND = 12, 8, 9, 10, 11
 INFO_SLOTS = ("H_tt", "H_tx", "H_ty", "H_xx", "H_xy", "H_yy", "g_t", "g_x", "g_y", "sse", "inliers", "rows", "status")
 
 
@@ -163,6 +166,11 @@ _SIGS = {
     "icpmi_grid_match_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double] + [C.c_void_p] * 4 +
                                [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "icpmi_grid_bound_field": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "icpmi_grid_search_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "icpmi_grid_search_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double] + [C.c_void_p] * 4 +
+                                [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "icpmi_pose_graph_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
     "icpmi_pose_graph_optimize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                             C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_size_t,

@@ -1,5 +1,7 @@
 """Correlative scan-to-map matching: clouds scored against the occupancy grid itself over a window of rotations and
-whole-cell shifts (``icpmi_grid_score_field``, ``icpmi_grid_match_batch``; the contract is include/icpmi.h's).
+whole-cell shifts (``icpmi_grid_score_field``, ``icpmi_grid_match_batch``; the contract is include/icpmi.h's), and the same
+search over a wide window (``icpmi_grid_bound_field``, ``icpmi_grid_search_batch``): blocks of shifts bounded from above by
+a max-pooled field, pruned against a seed score, the exhaustive winner returned.
 
 The reference registers a scan against a cloud only (slam.py:53-98, 111-183); this reads the map ``utilities.mapping``
 builds.  The log-odds are quantised to int16 and a candidate's score is the integer sum of the field under the scan's
@@ -18,6 +20,7 @@ from .batch import CloudSet, _ptr, _stream, require_gpu
 
 ST_OK, ST_EMPTY, ST_CAPACITY = _lib.GM_ST_OK, _lib.GM_ST_EMPTY, _lib.GM_ST_CAPACITY
 MAX_WINDOW, MAX_ANGLES, MAX_ROWS = _lib.GM_MAX_WINDOW, _lib.GM_MAX_ANGLES, _lib.GM_MAX_ROWS
+WIDE_MAX_WINDOW, WIDE_MAX_ANGLES, BLOCKS = _lib.GMW_MAX_WINDOW, _lib.GMW_MAX_ANGLES, (4, 8, 16)
 
 
 def shift_bits(log_odds_min, log_odds_max):
@@ -37,6 +40,21 @@ def score_field(log_odds, k, out=None):
     if out is None:
         out = torch.empty((ny, nx), dtype=torch.int16, device=log_odds.device)
     check(_lib.lib().icpmi_grid_score_field(_ptr(log_odds), ny, nx, int(k), _ptr(out), _stream()), "grid_score_field")
+    return out
+
+
+def bound_field(field, block=8, out=None):
+    """``icpmi_grid_bound_field`` of an int16 (ny, nx) device field -> the int16 (ny + block - 1, nx + block - 1) bound field:
+    entry [y + block - 1, x + block - 1] is the largest field value in rows [y, y + block) and columns [x, x + block), cells
+    outside the grid counting 0."""
+    if block not in BLOCKS:
+        raise ValueError(f"block must be one of {BLOCKS}, got {block}")
+    if field.dtype != torch.int16 or field.dim() != 2 or not field.is_contiguous():
+        raise ValueError("field must be a contiguous int16 (ny, nx) device tensor")
+    ny, nx = field.shape
+    if out is None:
+        out = torch.empty((ny + block - 1, nx + block - 1), dtype=torch.int16, device=field.device)
+    check(_lib.lib().icpmi_grid_bound_field(_ptr(field), ny, nx, int(block), _ptr(out), _stream()), "grid_bound_field")
     return out
 
 
@@ -62,6 +80,15 @@ class GridMatchBatch:
     records back and forms the poses."""
 
     def __init__(self, grid, cloud_set, pair_clouds, translations, angle_rows, window, centre_angle=-1, field=None, want_scores=False):
+        self._setup(grid, cloud_set, pair_clouds, translations, angle_rows, window, centre_angle, field, MAX_WINDOW, MAX_ANGLES)
+        B, dev = self.B, cloud_set.pts.device
+        self.records = torch.zeros((max(B, 1), _lib.GMREC_INTS), dtype=torch.int32, device=dev)
+        self.scores = torch.zeros((max(B, 1), self.A, self.S, self.S), dtype=torch.int32, device=dev) if want_scores else None
+        need = _lib.lib().icpmi_grid_match_workspace_bytes(B, self.A, self.W)
+        self.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+
+    def _setup(self, grid, cloud_set, pair_clouds, translations, angle_rows, window, centre_angle, field, max_window, max_angles):
+        """The pairs, their angles and the refusals the two searches share; everything but the outputs and the workspace."""
         require_gpu()
         if cloud_set.dim != 2:
             raise ValueError("grid matching is 2-D")
@@ -73,10 +100,10 @@ class GridMatchBatch:
         self.angles = np.ascontiguousarray(np.asarray(angle_rows, dtype=np.float64).reshape(B, -1))
         self.A, self.W, self.centre_angle = self.angles.shape[1], int(window), int(centre_angle)
         self.S = 2 * self.W + 1
-        if not 0 <= self.W <= MAX_WINDOW:
-            raise ValueError(f"window must lie in [0, {MAX_WINDOW}] cells, got {self.W}")
-        if not 1 <= self.A <= MAX_ANGLES:
-            raise ValueError(f"between 1 and {MAX_ANGLES} angles per pair, got {self.A}")
+        if not 0 <= self.W <= max_window:
+            raise ValueError(f"window must lie in [0, {max_window}] cells, got {self.W}")
+        if not 1 <= self.A <= max_angles:
+            raise ValueError(f"between 1 and {max_angles} angles per pair, got {self.A}")
         if self.centre_angle >= self.A:
             raise ValueError("centre_angle must be negative (none) or an index into the angle rows")
         if B and (self.pair_host.min() < 0 or self.pair_host.max() >= cloud_set.n_clouds):
@@ -88,22 +115,23 @@ class GridMatchBatch:
         self.t = torch.from_numpy(self.t_host).to(dev)
         self.cos_sin = torch.from_numpy(self.cos_sin_host).to(dev)
         self.k = shift_bits(grid.log_odds_min, grid.log_odds_max) if field is None else int(field[1])
-        self.records = torch.zeros((max(B, 1), _lib.GMREC_INTS), dtype=torch.int32, device=dev)
-        self.scores = torch.zeros((max(B, 1), self.A, self.S, self.S), dtype=torch.int32, device=dev) if want_scores else None
-        need = _lib.lib().icpmi_grid_match_workspace_bytes(B, self.A, self.W)
-        self.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
         self._field_buf = None
 
-    def run(self):
-        g = self.grid
-        lo = g.device_log_odds
+    def _field(self):
+        """The field a run scores against: the caller's, or the grid's log-odds quantised now."""
+        lo = self.grid.device_log_odds
         if self.field is not None:
             fld = self.field[0]
             if tuple(fld.shape) != tuple(lo.shape) or fld.dtype != torch.int16:
                 raise ValueError("field must be the int16 (ny, nx) tensor score_field() returned for this grid")
-        else:
-            fld = self._field_buf = score_field(lo, self.k, self._field_buf)
-        ny, nx = lo.shape
+            return fld
+        self._field_buf = score_field(lo, self.k, self._field_buf)
+        return self._field_buf
+
+    def run(self):
+        g = self.grid
+        fld = self._field()
+        ny, nx = fld.shape
         cs = self.cs
         check(_lib.lib().icpmi_grid_match_batch(
             _ptr(fld), ny, nx, float(g.min_x), float(g.min_y), float(g.resolution), _ptr(cs.pts), _ptr(cs.off),
@@ -128,6 +156,63 @@ class GridMatchBatch:
         info = {"status": col(_lib.GMREC_STATUS), "rows": rows, "index": col(_lib.GMREC_INDEX), "a": a, "j": j, "i": i,
                 "centre_score": col(_lib.GMREC_CENTRE), "shift_bits": self.k, "angle": self.angles[b, a],
                 "mean_log_odds": np.where(rows > 0, score / (np.maximum(rows, 1) * 2.0 ** self.k), 0.0)}
+        return R, t, score, info
+
+
+class GridSearchBatch(GridMatchBatch):
+    """``GridMatchBatch`` over a window of up to ``WIDE_MAX_WINDOW`` cells: the shifts are cut into blocks of ``block`` x
+    ``block``, every block gets an upper bound from the bound field, and only the blocks whose bound reaches a seed score
+    are scored — the record's first eight slots are those of the exhaustive search all the same.
+
+    ``bounds``: a tensor an earlier ``bound_field(field, block)`` returned, handed back like ``field=`` (no cache: without it
+    the bound field is rebuilt by every ``run()``).  ``run()`` returns the (B, 12) int32 record tensor; ``want_bounds``:
+    ``bounds_volume`` then holds the (B, A, NB, NB) int32 upper bounds of the blocks."""
+
+    def __init__(self, grid, cloud_set, pair_clouds, translations, angle_rows, window, centre_angle=-1, block=8, field=None, bounds=None,
+                 want_bounds=False):
+        self._setup(grid, cloud_set, pair_clouds, translations, angle_rows, window, centre_angle, field, WIDE_MAX_WINDOW, WIDE_MAX_ANGLES)
+        if block not in BLOCKS:
+            raise ValueError(f"block must be one of {BLOCKS}, got {block}")
+        if self.A * self.S * self.S >= 2 ** 31:
+            raise ValueError(f"{self.A} angles x {self.S}^2 shifts do not fit an int32 index")
+        self.block, self.bounds = int(block), bounds
+        self.NB = NB = -(-self.S // self.block)
+        if self.B * self.A * NB * NB >= 2 ** 31:
+            raise ValueError(f"{self.B} pairs x {self.A} angles x {NB}^2 blocks do not fit an int32 index")
+        ny, nx = grid.device_log_odds.shape
+        if bounds is not None and (tuple(bounds.shape) != (ny + block - 1, nx + block - 1) or bounds.dtype != torch.int16):
+            raise ValueError(f"bounds must be the int16 ({ny + block - 1}, {nx + block - 1}) tensor bound_field() returned for this grid and block")
+        dev = cloud_set.pts.device
+        self.records = torch.zeros((max(self.B, 1), _lib.GMW_REC_INTS), dtype=torch.int32, device=dev)
+        self.bounds_volume = torch.zeros((max(self.B, 1), self.A, NB, NB), dtype=torch.int32, device=dev) if want_bounds else None
+        need = _lib.lib().icpmi_grid_search_workspace_bytes(self.B, self.A, self.W, self.block)
+        self.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        self._bound_buf = None
+
+    def run(self):
+        g = self.grid
+        fld = self._field()
+        if self.bounds is not None:
+            bnd = self.bounds
+        else:
+            bnd = self._bound_buf = bound_field(fld, self.block, self._bound_buf)
+        ny, nx = fld.shape
+        cs = self.cs
+        check(_lib.lib().icpmi_grid_search_batch(
+            _ptr(fld), _ptr(bnd), ny, nx, float(g.min_x), float(g.min_y), float(g.resolution), _ptr(cs.pts), _ptr(cs.off),
+            cs.off_host.ctypes.data_as(C.c_void_p), _ptr(cs.cnt), cs.n_clouds, _ptr(self.pair),
+            self.pair_host.ctypes.data_as(C.c_void_p), self.B, _ptr(self.t), _ptr(self.cos_sin), self.A, self.W, self.block,
+            self.centre_angle, _ptr(self.records), _ptr(self.bounds_volume), _ptr(self.ws), self.ws.numel(), _stream()), "grid_search")
+        return self.records
+
+    def unpack(self, records=None):
+        """``GridMatchBatch.unpack`` with, in ``info``: ``blocks`` (A * NB^2), ``survivors`` (the blocks scored exactly),
+        ``seed_score`` (the score they had to reach) and ``max_bound`` (the largest upper bound of a block)."""
+        R, t, score, info = super().unpack(records)
+        rec = (self.records if records is None else records).cpu().numpy()[:self.B].astype(np.int64)
+        for key, slot in (("blocks", _lib.GMW_REC_BLOCKS), ("survivors", _lib.GMW_REC_SURVIVORS), ("seed_score", _lib.GMW_REC_SEED),
+                          ("max_bound", _lib.GMW_REC_MAX_BOUND)):
+            info[key] = rec[:, slot].copy()
         return R, t, score, info
 
 

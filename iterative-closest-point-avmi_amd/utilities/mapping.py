@@ -385,6 +385,63 @@ class OccupancyGrid2D:
             cs = voxel_downsample_set(history.raw, voxel_size)
         return self._match_set(cs, ids, predicted_poses, linear_window, angular_window, angular_step, field).unpack()
 
+    # ── the same search over a wide window (icpmi.gridmatch.GridSearchBatch): metres and the full circle ─────────────
+    def bound_field(self, field=None, block=8):
+        """-> the bound field of ``field`` (a ``(tensor, k)`` of ``score_field()``; None: of the map as it is now) for blocks of
+        ``block`` x ``block`` shifts: what the ``search_*`` methods prune with.  Built anew at every call, like the field; a
+        caller who keeps one passes it back as ``bounds=`` together with the ``field=`` it was made from."""
+        from icpmi import gridmatch
+        return gridmatch.bound_field((self.score_field() if field is None else field)[0], block)
+
+    def _search_set(self, cs, pair_clouds, poses, linear_window, angular_window, angular_step, block, field, bounds):
+        from icpmi import gridmatch
+        if cs.pts.device != self._dev:
+            raise ValueError(f"the clouds live on {cs.pts.device}, the grid on {self._dev}")
+        if bounds is not None and field is None:
+            raise ValueError("bounds= belongs to the field it was made from: pass that field= too")
+        xyt = self._xytheta(poses, len(pair_clouds))
+        angles, centre = gridmatch.angle_grid(xyt[:, 2], angular_window, angular_step)
+        W = int(round(linear_window / self.resolution))
+        job = gridmatch.GridSearchBatch(self, cs, pair_clouds, xyt[:, :2], angles, W, centre, block=block, field=field, bounds=bounds)
+        job.run()
+        return job
+
+    def search_scans(self, clouds, predicted_poses, linear_window=5.0, angular_window=180.0, angular_step=1.0, voxel_size=None,
+                     block=8, field=None, bounds=None):
+        """``match_scans`` over a wide window — localising in a saved or rebuilt map, recovering when ICP and the submap both
+        reject, checking a loop closure: the same arguments, angle grid and result (the first maximum of the exhaustive
+        search, bit for bit), up to ``icpmi.gridmatch.WIDE_MAX_WINDOW`` cells each way.  The shifts are cut into blocks of
+        ``block`` x ``block`` (4, 8 or 16); only blocks whose upper bound reaches a seed score are scored.  ``info`` adds
+        ``blocks``, ``survivors``, ``seed_score`` and ``max_bound``.  ``bounds``: a ``bound_field(field, block)`` kept by the
+        caller, with the ``field`` it was made from."""
+        from icpmi import gridmatch
+        cs = gridmatch.cloud_set_of(clouds, voxel_size)
+        return self._search_set(cs, np.arange(cs.n_clouds), predicted_poses, linear_window, angular_window, angular_step, block, field,
+                                bounds).unpack()
+
+    def search_scan(self, points_local, predicted_pose, linear_window=5.0, angular_window=180.0, angular_step=1.0, voxel_size=None,
+                    block=8, field=None, bounds=None):
+        """``search_scans`` of one scan -> (R (2,2), t (2,), score, info) with scalar entries in ``info``."""
+        R, t, score, info = self.search_scans([points_local], [predicted_pose], linear_window, angular_window, angular_step,
+                                              voxel_size, block, field, bounds)
+        return R[0], t[0], int(score[0]), {k: (v[0] if isinstance(v, np.ndarray) else v) for k, v in info.items()}
+
+    def search_history(self, history, ids, predicted_poses, linear_window=5.0, angular_window=180.0, angular_step=1.0, voxel_size=None,
+                       block=8, field=None, bounds=None):
+        """``search_scans`` of scans resident in an ``icpmi.ScanHistory``, by id, with ``match_history``'s choice of rows."""
+        from icpmi import history as _h
+        from icpmi.batch import voxel_downsample_set
+        ids = _h._scan_ids(ids, ("ids", "scan ids"), history.n_scans)
+        if voxel_size is None:
+            cs = history.raw
+        elif float(voxel_size) == history.voxel_size:
+            cs = history.vox
+        elif float(voxel_size) == history.rotation_voxel_size:
+            cs = history.rs_vox
+        else:
+            cs = voxel_downsample_set(history.raw, voxel_size)
+        return self._search_set(cs, ids, predicted_poses, linear_window, angular_window, angular_step, block, field, bounds).unpack()
+
     # ── probability / display, mapping.py:150-166 (NumPy on the host copy) ───
     def to_probability(self):
         return 1.0 / (1.0 + np.exp(-self.log_odds))
