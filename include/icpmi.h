@@ -807,21 +807,47 @@ int icpmi_grid_search_batch(const int16_t* field, const int16_t* bound, int32_t 
  * builds its gather lists from them); edges_z / edges_omega: device.
  * All iterations run in one launch.  Graphs whose consecutive nodes are all
  * joined by an edge (the odometry chain slam.py:543-549 builds) are solved as
- * block-tridiagonal + low-rank; any other graph through the dense 3n x 3n
- * matrix, as the reference does.  fix_node is held by the 1e10 diagonal of
- * pose_graph.py:107-112.
+ * block-tridiagonal + low-rank (the split); any other graph through the dense
+ * 3n x 3n matrix, as the reference does.  fix_node is held by the 1e10 diagonal
+ * of pose_graph.py:107-112.
+ * The split inverts the chain part T on its own, so a chain edge with (almost)
+ * no information would cost it digits that a solve of the whole system keeps.
+ * The call reads the information matrices back and treats a chain edge as weak
+ * when the Gershgorin lower bound of its symmetric part is below S / (3 n), S
+ * the largest row sum of |Omega| in the graph: such an edge enters T as S I and
+ * its remainder Omega - S I joins the closures (same sum, T as stiff there as
+ * anywhere).  That needs room: size the workspace with
+ * icpmi_pose_graph_weighted_workspace_bytes (edges_omega_host: the same
+ * matrices on the host); with the plain size query a graph that has weak chain
+ * edges ends at once with status 4.  Status 4 also ends a launch where a block
+ * of T is exactly singular or the closure system has an exactly zero pivot.
  * info (device, 10 doubles): iterations run, status (0 nothing to do: fewer
  * than two nodes or no edges; 1 converged: step norm < convergence_eps; 2
- * iteration limit; 3 singular system: the nodes keep the values of the previous
- * iteration, pose_graph.py:117-119), norm of the last step; then the time spent
- * per phase in microseconds, summed over the iterations (assembly, chain
- * factorisation, chain sweeps, closure system, its solve, update of dx, apply).
- * workspace: icpmi_pose_graph_workspace_bytes(edges_ij_host, n_nodes, n_edges). */
+ * iteration limit; 3 singular system, reported by the dense elimination only
+ * (an exactly zero pivot, LAPACK's error): the nodes keep the values of the
+ * previous iteration, pose_graph.py:117-119; 4 split step refused: the nodes
+ * keep the values of the previous iteration and `iterations run` counts the
+ * applied ones — continue with icpmi_pose_graph_optimize_dense for the
+ * remaining iterations, as PoseGraph2D.optimize does), norm of the last step;
+ * then the time spent per phase in microseconds, summed over the iterations
+ * (assembly, chain factorisation, chain sweeps, closure system, its solve,
+ * update of dx, apply).
+ * icpmi_pose_graph_optimize_dense: the same call with the dense path forced;
+ * it never returns status 4.
+ * workspace: icpmi_pose_graph_workspace_bytes(edges_ij_host, n_nodes, n_edges),
+ * icpmi_pose_graph_dense_workspace_bytes(...) for the dense call. */
 size_t icpmi_pose_graph_workspace_bytes(const int32_t* edges_ij_host, int32_t n_nodes, int32_t n_edges);
+size_t icpmi_pose_graph_weighted_workspace_bytes(const int32_t* edges_ij_host, const double* edges_omega_host,
+                                                 int32_t n_nodes, int32_t n_edges);
 int icpmi_pose_graph_optimize(double* nodes, const int32_t* edges_ij_host, const double* edges_z,
                               const double* edges_omega, int32_t n_nodes, int32_t n_edges,
                               int32_t n_iterations, int32_t fix_node, double convergence_eps,
                               double* info, void* workspace, size_t workspace_bytes, void* stream);
+size_t icpmi_pose_graph_dense_workspace_bytes(const int32_t* edges_ij_host, int32_t n_nodes, int32_t n_edges);
+int icpmi_pose_graph_optimize_dense(double* nodes, const int32_t* edges_ij_host, const double* edges_z,
+                                    const double* edges_omega, int32_t n_nodes, int32_t n_edges,
+                                    int32_t n_iterations, int32_t fix_node, double convergence_eps,
+                                    double* info, void* workspace, size_t workspace_bytes, void* stream);
 
 /* total_error, pose_graph.py:189-194: sum over edges of e^T Omega e, in edge
  * order.  Everything on the device; scratch: n_edges doubles; out: 1 double. */

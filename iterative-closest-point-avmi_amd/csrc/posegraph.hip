@@ -17,6 +17,15 @@
 // takes the general path: the same dense matrix as the reference, eliminated
 // with partial pivoting by the workgroup in global memory.
 //
+// The split is only as good as T.  The host plan (pg_plan) reads the information
+// matrices and gives every weak chain edge a twin among the closures, so that T
+// stays as stiff as the whole system; a graph with a chain edge that carries no
+// information at all along some direction is not split.  Where a block of T or
+// the closure system still turns out exactly singular, the launch ends with
+// status PG_REFUSED and the poses of the previous iteration, and the caller
+// continues from there on the dense path.  Only the dense elimination, like the
+// reference's LAPACK call, ever reports a singular system.
+//
 // Every sum has a fixed order (per-node gathers in edge order, fixed reduction
 // trees): results are reproducible run to run.
 #include "common.hpp"
@@ -50,7 +59,7 @@ struct PgArgs {
     double* info;                  // [0] iterations run, [1] status, [2] last step norm
 };
 
-enum { PG_NOTHING = 0, PG_CONVERGED = 1, PG_MAXITER = 2, PG_SINGULAR = 3 };
+enum { PG_NOTHING = 0, PG_CONVERGED = 1, PG_MAXITER = 2, PG_SINGULAR = 3, PG_REFUSED = 4 };
 
 // ── 3x3 helpers (row-major, fully unrolled) ─────────────────────────────────
 struct M3 { double a[9]; };
@@ -279,7 +288,7 @@ __global__ __launch_bounds__(PG_THREADS) void pose_graph_kernel(PgArgs g) {
         __syncthreads();
         PG_MARK(0);
 
-        bool singular = false;
+        bool singular = false, refused = false;
         if (g.dense) {
             singular = !block_lu_solve(g.Hd, N3, g.dx, s_val, s_idx);
         } else {
@@ -352,8 +361,8 @@ __global__ __launch_bounds__(PG_THREADS) void pose_graph_kernel(PgArgs g) {
                 m3_store(g.D, inv);
             }
             __syncthreads();
-            singular = s_flag != 0;
-            if (!singular) {
+            refused = s_flag != 0;                                                       // a block of T is exactly singular
+            if (!refused) {
                 for (int col = tid; col < ncols; col += PG_THREADS) {
                     double r[3], x[3];
                     for (int c = 0; c < 3; ++c) r[c] = g.X[(size_t)c * ncols + col];
@@ -401,10 +410,10 @@ __global__ __launch_bounds__(PG_THREADS) void pose_graph_kernel(PgArgs g) {
                     }
                     __syncthreads();
                     PG_MARK(3);
-                    singular = !block_lu_solve(g.M, K, g.g, s_val, s_idx);
+                    refused = !block_lu_solve(g.M, K, g.g, s_val, s_idx);
                     PG_MARK(4);
                 }
-                if (!singular) {
+                if (!refused) {
                     // dx = Y[:, 0] - Y[:, 1:] y: one wave per row, lanes along the row (coalesced), fixed-tree sum
                     const int l16 = tid & 15;
                     for (int t0 = 0; t0 < N3; t0 += PG_THREADS / 16) {                   // 16 lanes per row, uniform trip count
@@ -420,6 +429,7 @@ __global__ __launch_bounds__(PG_THREADS) void pose_graph_kernel(PgArgs g) {
         __syncthreads();
         PG_MARK(5);
         if (singular) { status = PG_SINGULAR; iters = it; break; }           // pose_graph.py:117-119: nodes keep their values
+        if (refused) { status = PG_REFUSED; iters = it; break; }             // nodes keep their values; the caller goes on densely
         // ── apply the update, pose_graph.py:121-129 ──────────────────────────────
         double ss = 0.0;
         for (int v = tid; v < n; v += PG_THREADS) {
@@ -460,40 +470,93 @@ __global__ __launch_bounds__(PG_THREADS) void pose_graph_error_kernel(const doub
 }
 
 struct PgPlan {
-    int k = 0, dense = 0;
+    int k = 0, dense = 0, m2 = 0;                  // m2: edges after the weak chain edges got their twins
+    bool null_edge = false;                        // a chain edge without information along some direction: no split
+    double stiff = 0.0;                            // the information a weak chain edge carries inside T (times I)
+    std::vector<int32_t> ij, weak;                 // [m2][2] the edge list with the twins appended; ids of the weak chain edges
     std::vector<int32_t> csr_ptr, csr_edge, loop_slot, loop_edge;
 };
 
 // Classify the edges (host side: the edge list is a few KB of integers the caller holds on the host anyway).
-static bool pg_plan(const int32_t* ij, int n, int m, PgPlan& p) {
-    p.csr_ptr.assign(n + 1, 0);
-    p.loop_slot.assign(m, -1);
+//
+// With the information matrices at hand (omega: [m][9] on the host, or null) the chain edges too weak for T are found
+// here.  The split inverts T without the closures, and what it loses against a solve of the whole system grows with
+// S / lambda, S the largest information in the graph and lambda the smallest of a chain edge: T^-1 r grows with
+// 1 / lambda, the step does not, and the difference of the two cancels that many digits (measured: the step error is
+// proportional to 1 / eps for Omega = diag(eps, 1e4, 1e4)).  A step may be off by 3n times what a stable solve of the
+// whole system leaves, so a chain edge counts as weak when lambda < S / (3n), lambda the smallest eigenvalue of the
+// symmetric part.  A weak edge (i, j, z, Omega) is split in two that sum to it: (i, j, z, S I) stays in the chain, so T
+// is as stiff there as anywhere, and its twin (i, j, z, Omega - S I) goes with the closures, whose system is eliminated
+// with pivoting.  An edge with an eigenvalue that is zero to rounding (|lambda| <= 64 u max |lambda|: the closed form
+// below is good to a few u of the largest) may leave the whole system exactly singular, which only the dense elimination
+// can tell as the reference's LAPACK call does: such a graph is not split at all.
+static void pg_sym_eigenvalues(const double* o, double* e) {                 // symmetric part of a 3 x 3, closed form
+    const double a00 = o[0], a11 = o[4], a22 = o[8], a01 = 0.5 * (o[1] + o[3]), a02 = 0.5 * (o[2] + o[6]), a12 = 0.5 * (o[5] + o[7]);
+    const double p1 = a01 * a01 + a02 * a02 + a12 * a12;
+    if (p1 == 0.0) { e[0] = a00; e[1] = a11; e[2] = a22; return; }
+    const double q = (a00 + a11 + a22) / 3.0;
+    const double p2 = (a00 - q) * (a00 - q) + (a11 - q) * (a11 - q) + (a22 - q) * (a22 - q) + 2.0 * p1;
+    const double p = sqrt(p2 / 6.0);
+    const double b00 = (a00 - q) / p, b11 = (a11 - q) / p, b22 = (a22 - q) / p, b01 = a01 / p, b02 = a02 / p, b12 = a12 / p;
+    double r = 0.5 * (b00 * (b11 * b22 - b12 * b12) - b01 * (b01 * b22 - b12 * b02) + b02 * (b01 * b12 - b11 * b02));
+    r = r < -1.0 ? -1.0 : (r > 1.0 ? 1.0 : r);
+    const double phi = acos(r) / 3.0;
+    e[0] = q + 2.0 * p * cos(phi);
+    e[2] = q + 2.0 * p * cos(phi + 2.0943951023931953);
+    e[1] = 3.0 * q - e[0] - e[2];
+}
+
+static bool pg_plan(const int32_t* ij, const double* omega, int n, int m, bool force_dense, PgPlan& p) {
+    p.dense = force_dense;
     std::vector<char> linked(n > 1 ? n - 1 : 0, 0);
     for (int q = 0; q < m; ++q) {
         const int i = ij[2 * q], j = ij[2 * q + 1];
         if (i < 0 || i >= n || j < 0 || j >= n) return false;
+        if (i - j == 1 || j - i == 1) linked[i < j ? i : j] = 1;
+    }
+    for (char c : linked) if (!c) p.dense = 1;               // a gap in the chain: T would be singular
+    p.ij.assign(ij, ij + 2 * (size_t)m);
+    if (!p.dense && omega) {
+        for (size_t t = 0; t < 9 * (size_t)m; t += 3) {
+            const double row = (fabs(omega[t]) + fabs(omega[t + 1])) + fabs(omega[t + 2]);
+            if (row > p.stiff) p.stiff = row;
+        }
+        for (int q = 0; q < m; ++q) {
+            const int i = ij[2 * q], j = ij[2 * q + 1];
+            if (i - j != 1 && j - i != 1) continue;
+            double e[3];
+            pg_sym_eigenvalues(omega + 9 * (size_t)q, e);
+            const double lo = fmin(fmin(e[0], e[1]), e[2]);
+            const double amin = fmin(fmin(fabs(e[0]), fabs(e[1])), fabs(e[2])), amax = fmax(fmax(fabs(e[0]), fabs(e[1])), fabs(e[2]));
+            if (!(amin > 64 * 0x1p-53 * amax)) p.null_edge = true;           // all zero and NaN included
+            else if (!(lo >= p.stiff / (3.0 * n))) { p.weak.push_back(q); p.ij.push_back(i); p.ij.push_back(j); }
+        }
+        if (p.null_edge) { p.weak.clear(); p.ij.resize(2 * (size_t)m); }
+    }
+    const int m2 = p.m2 = m + (int)p.weak.size();
+    p.csr_ptr.assign(n + 1, 0);
+    p.loop_slot.assign(m2, -1);
+    for (int q = 0; q < m2; ++q) {
+        const int i = p.ij[2 * q], j = p.ij[2 * q + 1];
         ++p.csr_ptr[i + 1];
         if (j != i) ++p.csr_ptr[j + 1];
-        if (i - j == 1 || j - i == 1) linked[i < j ? i : j] = 1;
-        else { p.loop_slot[q] = p.k++; p.loop_edge.push_back(q); }
+        if (!p.dense && (q >= m || (i - j != 1 && j - i != 1))) { p.loop_slot[q] = p.k++; p.loop_edge.push_back(q); }
     }
     for (int v = 0; v < n; ++v) p.csr_ptr[v + 1] += p.csr_ptr[v];
     p.csr_edge.resize(p.csr_ptr[n]);
     std::vector<int32_t> fill(p.csr_ptr.begin(), p.csr_ptr.end() - 1);
-    for (int q = 0; q < m; ++q) {
-        const int i = ij[2 * q], j = ij[2 * q + 1];
+    for (int q = 0; q < m2; ++q) {
+        const int i = p.ij[2 * q], j = p.ij[2 * q + 1];
         p.csr_edge[fill[i]++] = q;
         if (j != i) p.csr_edge[fill[j]++] = q;
     }
-    for (char c : linked) if (!c) p.dense = 1;               // a gap in the chain: T would be singular
-    if (p.dense) { p.k = 0; p.loop_edge.clear(); std::fill(p.loop_slot.begin(), p.loop_slot.end(), -1); }
     return true;
 }
 
-// the workspace: the plan's index arrays, then the arrays of PgArgs
+// the workspace: the plan's index arrays, then the arrays of PgArgs (m: edges with the twins, w: twins)
 struct PgWs {
     Carve c;
-    int n, m, k, dense;
+    int n, m, k, dense, w;
     size_t N3 = 3 * (size_t)n, K = 3 * (size_t)k, blocks = 9 * (size_t)n * 8;
     int32_t* ei = c.take<int32_t>((size_t)m * 2 * 4);            // ei, ej
     int32_t* ej = ei ? ei + m : nullptr;
@@ -509,23 +572,23 @@ struct PgWs {
     double* dx = c.take<double>(N3 * 8);
     double* edge_err = c.take<double>((size_t)(m + 1) * 8);      // per-edge errors (no kernel uses them: kept for the size)
     double* Hd = dense ? c.take<double>(N3 * N3 * 8) : nullptr;
+    double* omega = w ? c.take<double>((size_t)m * 9 * 8) : nullptr;     // the caller's z and Omega with the twins' rows: only
+    double* z = w ? c.take<double>((size_t)m * 3 * 8) : nullptr;         // where there are twins
     size_t bytes = c.off + 256;
 };
 
-}  // namespace icpmi
-
-extern "C" size_t icpmi_pose_graph_workspace_bytes(const int32_t* edges_ij_host, int32_t n_nodes, int32_t n_edges) {
+static size_t pg_workspace_bytes(const int32_t* edges_ij_host, const double* omega_host, int32_t n_nodes, int32_t n_edges,
+                                 bool force_dense) {
     if (n_nodes < 0 || n_edges < 0 || (n_edges > 0 && !edges_ij_host)) return 0;
-    icpmi::PgPlan p;
-    if (!icpmi::pg_plan(edges_ij_host, n_nodes, n_edges, p)) return 0;
-    return icpmi::PgWs{nullptr, n_nodes, n_edges, p.k, p.dense}.bytes;
+    PgPlan p;
+    if (!pg_plan(edges_ij_host, omega_host, n_nodes, n_edges, force_dense, p)) return 0;
+    return PgWs{nullptr, n_nodes, p.m2, p.k, p.dense, (int)p.weak.size()}.bytes;
 }
 
-extern "C" int icpmi_pose_graph_optimize(double* nodes, const int32_t* edges_ij_host, const double* edges_z,
-                                         const double* edges_omega, int32_t n_nodes, int32_t n_edges,
-                                         int32_t n_iterations, int32_t fix_node, double convergence_eps,
-                                         double* info, void* workspace, size_t workspace_bytes, void* stream) {
-    using namespace icpmi;
+static int pg_optimize(double* nodes, const int32_t* edges_ij_host, const double* edges_z,
+                       const double* edges_omega, int32_t n_nodes, int32_t n_edges,
+                       int32_t n_iterations, int32_t fix_node, double convergence_eps,
+                       double* info, void* workspace, size_t workspace_bytes, void* stream, bool force_dense) {
     if (!nodes || !info || n_nodes < 0 || n_edges < 0 || n_iterations < 0) return ICPMI_ERR_ARG;
     if (n_edges > 0 && (!edges_ij_host || !edges_z || !edges_omega)) return ICPMI_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -536,16 +599,51 @@ extern "C" int icpmi_pose_graph_optimize(double* nodes, const int32_t* edges_ij_
         return ICPMI_OK;
     }
     if (fix_node < 0 || fix_node >= n_nodes) return ICPMI_ERR_ARG;
+    const int n = n_nodes, m = n_edges;
+    std::vector<double> om, zz;                                              // the information matrices, to find the weak chain edges
+    if (!force_dense) {
+        om.resize(9 * (size_t)m);
+        if (hipMemcpyAsync(om.data(), edges_omega, om.size() * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return ICPMI_ERR_HIP;
+        if (hipStreamSynchronize(st) != hipSuccess) return ICPMI_ERR_HIP;
+    }
     PgPlan p;
-    if (!pg_plan(edges_ij_host, n_nodes, n_edges, p)) return ICPMI_ERR_ARG;
-    const int n = n_nodes, m = n_edges, k = p.k;
-    const PgWs w{workspace, n, m, k, p.dense};
-    if (!workspace || workspace_bytes < w.bytes) return ICPMI_ERR_WORKSPACE;
+    if (!pg_plan(edges_ij_host, force_dense ? nullptr : om.data(), n, m, force_dense, p)) return ICPMI_ERR_ARG;
+    const int k = p.k, m2 = p.m2, nw = (int)p.weak.size();
+    const PgWs w{workspace, n, m2, k, p.dense, nw};
+    if (!workspace || workspace_bytes < w.bytes || p.null_edge) {
+        if (!workspace || (!nw && !p.null_edge)) return ICPMI_ERR_WORKSPACE;
+        // a chain edge with a null direction, or a workspace sized without the information matrices
+        // (icpmi_pose_graph_workspace_bytes) and so without room for the twins: the split is refused before its
+        // first iteration and the caller continues on the dense path
+        const double refused[10] = {0.0, (double)PG_REFUSED, 0.0};
+        if (hipMemcpyAsync(info, refused, sizeof(refused), hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
+        if (hipStreamSynchronize(st) != hipSuccess) return ICPMI_ERR_HIP;
+        return ICPMI_OK;
+    }
     PgArgs a{};
     a.D = w.D; a.U = w.U; a.L = w.L; a.Dinv = w.Dinv; a.G = w.G; a.b = w.b;
     a.X = w.X; a.AB = w.AB; a.M = w.M; a.g = w.g; a.y = w.y; a.dx = w.dx; a.Hd = w.Hd;
-    std::vector<int32_t> sep(2 * (size_t)m);
-    for (int q = 0; q < m; ++q) { sep[q] = edges_ij_host[2 * q]; sep[m + q] = edges_ij_host[2 * q + 1]; }
+    a.z = edges_z; a.omega = edges_omega;
+    if (nw) {
+        zz.resize(3 * (size_t)m2);
+        if (hipMemcpyAsync(zz.data(), edges_z, 3 * (size_t)m * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return ICPMI_ERR_HIP;
+        if (hipStreamSynchronize(st) != hipSuccess) return ICPMI_ERR_HIP;
+        om.resize(9 * (size_t)m2);
+        for (int t = 0; t < nw; ++t) {
+            const size_t q = (size_t)p.weak[t], q2 = (size_t)m + t;
+            for (int c = 0; c < 3; ++c) zz[3 * q2 + c] = zz[3 * q + c];
+            for (int c = 0; c < 9; ++c) {
+                const double stiff = c % 4 == 0 ? p.stiff : 0.0;
+                om[9 * q2 + c] = om[9 * q + c] - stiff;
+                om[9 * q + c] = stiff;
+            }
+        }
+        if (hipMemcpyAsync(w.omega, om.data(), om.size() * 8, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
+        if (hipMemcpyAsync(w.z, zz.data(), zz.size() * 8, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
+        a.z = w.z; a.omega = w.omega;
+    }
+    std::vector<int32_t> sep(2 * (size_t)m2);
+    for (int q = 0; q < m2; ++q) { sep[q] = p.ij[2 * q]; sep[m2 + q] = p.ij[2 * q + 1]; }
     // pageable host memory: the runtime stages these copies before returning, so the vectors may go out of scope
     if (hipMemcpyAsync(w.ei, sep.data(), sep.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
     if (hipMemcpyAsync(w.csr_ptr, p.csr_ptr.data(), p.csr_ptr.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
@@ -553,13 +651,41 @@ extern "C" int icpmi_pose_graph_optimize(double* nodes, const int32_t* edges_ij_
     if (hipMemcpyAsync(w.loop_slot, p.loop_slot.data(), p.loop_slot.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
     if (k > 0 && hipMemcpyAsync(w.loop_edge, p.loop_edge.data(), (size_t)k * 4, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
     if (hipStreamSynchronize(st) != hipSuccess) return ICPMI_ERR_HIP;        // the staging vectors die with this call
-    a.nodes = nodes; a.ei = w.ei; a.ej = w.ej; a.z = edges_z; a.omega = edges_omega;
+    a.nodes = nodes; a.ei = w.ei; a.ej = w.ej;
     a.csr_ptr = w.csr_ptr; a.csr_edge = w.csr_edge; a.loop_slot = w.loop_slot; a.loop_edge = w.loop_edge;
-    a.n = n; a.m = m; a.k = k; a.dense = p.dense; a.n_iter = n_iterations; a.fix = fix_node; a.eps = convergence_eps;
+    a.n = n; a.m = m2; a.k = k; a.dense = p.dense; a.n_iter = n_iterations; a.fix = fix_node; a.eps = convergence_eps;
     a.info = info;
     pose_graph_kernel<<<1, PG_THREADS, 0, st>>>(a);
     ICPMI_LAUNCH_CHECK();
     return ICPMI_OK;
+}
+
+}  // namespace icpmi
+
+extern "C" size_t icpmi_pose_graph_workspace_bytes(const int32_t* edges_ij_host, int32_t n_nodes, int32_t n_edges) {
+    return icpmi::pg_workspace_bytes(edges_ij_host, nullptr, n_nodes, n_edges, false);
+}
+extern "C" size_t icpmi_pose_graph_weighted_workspace_bytes(const int32_t* edges_ij_host, const double* edges_omega_host,
+                                                            int32_t n_nodes, int32_t n_edges) {
+    return icpmi::pg_workspace_bytes(edges_ij_host, edges_omega_host, n_nodes, n_edges, false);
+}
+extern "C" size_t icpmi_pose_graph_dense_workspace_bytes(const int32_t* edges_ij_host, int32_t n_nodes, int32_t n_edges) {
+    return icpmi::pg_workspace_bytes(edges_ij_host, nullptr, n_nodes, n_edges, true);
+}
+
+extern "C" int icpmi_pose_graph_optimize(double* nodes, const int32_t* edges_ij_host, const double* edges_z,
+                                         const double* edges_omega, int32_t n_nodes, int32_t n_edges,
+                                         int32_t n_iterations, int32_t fix_node, double convergence_eps,
+                                         double* info, void* workspace, size_t workspace_bytes, void* stream) {
+    return icpmi::pg_optimize(nodes, edges_ij_host, edges_z, edges_omega, n_nodes, n_edges, n_iterations, fix_node,
+                              convergence_eps, info, workspace, workspace_bytes, stream, false);
+}
+extern "C" int icpmi_pose_graph_optimize_dense(double* nodes, const int32_t* edges_ij_host, const double* edges_z,
+                                               const double* edges_omega, int32_t n_nodes, int32_t n_edges,
+                                               int32_t n_iterations, int32_t fix_node, double convergence_eps,
+                                               double* info, void* workspace, size_t workspace_bytes, void* stream) {
+    return icpmi::pg_optimize(nodes, edges_ij_host, edges_z, edges_omega, n_nodes, n_edges, n_iterations, fix_node,
+                              convergence_eps, info, workspace, workspace_bytes, stream, true);
 }
 
 extern "C" int icpmi_pose_graph_error(const double* nodes, const int32_t* edges_i, const int32_t* edges_j, const double* edges_z,

@@ -20,6 +20,7 @@ from icpmi import batch as _b
 VERBOSE = True      # the reference prints one line per optimisation
 
 NOTHING_TO_DO, CONVERGED, MAX_ITERATIONS, SINGULAR = 0, 1, 2, 3
+_SPLIT_REFUSED = 4   # device status only: the chain part of the split is exactly singular, go on with the dense matrix
 
 
 def normalize_angle(a):
@@ -94,19 +95,34 @@ class PoseGraph2D:
         fix = fix_node + n if fix_node < 0 else fix_node
         d_nodes = torch.from_numpy(np.ascontiguousarray(np.array(self.nodes, dtype=np.float64).reshape(n, 3))).to(dev)
         d_z, d_om = torch.from_numpy(z).to(dev), torch.from_numpy(om).to(dev)
-        info = torch.zeros(10, dtype=torch.float64, device=dev)
+        d_info = torch.zeros(10, dtype=torch.float64, device=dev)
         ijp = ij.ctypes.data_as(C.c_void_p)
-        need = L.icpmi_pose_graph_workspace_bytes(ijp, n, m)
-        ws = torch.empty(max(int(need), 256), dtype=torch.uint8, device=dev)
-        _lib.check(L.icpmi_pose_graph_optimize(_b._ptr(d_nodes), ijp, _b._ptr(d_z), _b._ptr(d_om), n, m,
-                                               int(n_iterations), int(fix), float(convergence_eps), _b._ptr(info),
-                                               _b._ptr(ws), ws.numel(), _b._stream()), "PoseGraph2D.optimize")
+
+        def launch(size_query, entry, iterations):
+            ws = torch.empty(max(int(size_query(ijp, n, m)), 256), dtype=torch.uint8, device=dev)
+            _lib.check(entry(_b._ptr(d_nodes), ijp, _b._ptr(d_z), _b._ptr(d_om), n, m, iterations, int(fix),
+                             float(convergence_eps), _b._ptr(d_info), _b._ptr(ws), ws.numel(), _b._stream()),
+                       "PoseGraph2D.optimize")
+            return d_info.cpu().numpy()
+
+        omp = om.ctypes.data_as(C.c_void_p)                 # with the information matrices: room for the twins of weak chain edges
+        info = launch(lambda *a: L.icpmi_pose_graph_weighted_workspace_bytes(a[0], omp, *a[1:]),
+                      L.icpmi_pose_graph_optimize, int(n_iterations))
+        split_refused_at = None
+        if int(info[1]) == _SPLIT_REFUSED:
+            # the chain part of the split turned out exactly singular: the remaining iterations take the dense matrix
+            split_refused_at, first = int(info[0]), info
+            info = launch(L.icpmi_pose_graph_dense_workspace_bytes, L.icpmi_pose_graph_optimize_dense,
+                          int(n_iterations) - split_refused_at)
+            info[0] += first[0]
+            info[3:10] += first[3:10]
+            if int(info[0]) == split_refused_at:
+                info[2] = first[2]                           # singular at once: the last step applied is the split's
         out = d_nodes.cpu().numpy()
-        info = info.cpu().numpy()
         iters, status, step = int(info[0]), int(info[1]), info[2]
         for k in range(n):                                   # in place, like pose_graph.py:122-125
             self.nodes[k][:] = out[k]
-        self.last_info = dict(iterations=iters, status=status, step_norm=float(step),
+        self.last_info = dict(iterations=iters, status=status, step_norm=float(step), split_refused_at=split_refused_at,
                               phase_us=dict(zip(("assemble", "chain_lu", "chain_sweeps", "closure_system",
                                                  "closure_solve", "dx", "apply"), info[3:10].tolist())))
         if VERBOSE:
