@@ -800,6 +800,55 @@ int icpmi_grid_search_batch(const int16_t* field, const int16_t* bound, int32_t 
                             int32_t n_angles, int32_t window, int32_t block, int32_t centre_angle, int32_t* out_records,
                             int32_t* out_bounds, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- moments of a match: the sub-cell pose and the covariance the score volume holds ---------------------------------
+ * icpmi_grid_match_batch returns the first maximum of an integer volume: one whole cell, one whole angle step, and no
+ * word on how well the map constrained it.  icpmi_grid_match_moments reads that volume once more and leaves the weighted
+ * moments of the candidates about the winner (Olson's covariance of a correlative match), in integers: twelve int64 per
+ * pair that do not depend on how the candidates are split or in which order they are added.
+ *
+ * volume: device, [n_pairs][n_angles][S][S] int32 contiguous, S = 2 * window + 1 — what icpmi_grid_match_batch leaves in
+ * out_scores.  records: device, [n_pairs][ICPMI_GMREC_INTS] int32 as icpmi_grid_match_batch wrote them earlier on the same
+ * stream (nothing synchronises); slots A, J, I lie inside the volume.  moments: device, [n_pairs][ICPMI_GMOM_INTS] int64,
+ * 8-byte aligned; the call zeroes it itself (a memset), so a buffer is reusable as it is.
+ *
+ * Per pair, in int64: (a*, j*, i*, best, rows) = slots A, J, I, SCORE, ROWS of its record, h = max(1, rows * half_step),
+ * and for every candidate (a, j, i) with score s
+ *   d = max(0, best - s),  u = floor(8 * d / h),  e = u >> 3,  f = u & 7,  w = e > 20 ? 0 : T[f] >> e,
+ *   T = {1048576, 961548, 881744, 808563, 741455, 679917, 623487, 571740} = rint(2^20 * 2^(-f / 8))
+ * (fractional parts .43 .80 .63 .20 .42 .02 .12: none near a tie).  A candidate h below the best counts half, in eight
+ * sub-steps per halving; half_step is the score drop per scored row, in field units (2^shift_bits per unit of log-odds),
+ * that halves the weight — scaled by the rows at the winning angle, so the setting does not depend on the cloud's size.
+ * With da = a - a*, dj = j - j*, di = i - i* the slots ICPMI_GMOM_* are: W = sum w; A, J, I = sum w * da, w * dj, w * di;
+ * AA, AJ, AI, JJ, JI, II = sum w * da^2, w * da * dj, w * da * di, w * dj^2, w * dj * di, w * di^2; SUPPORT = the number of
+ * candidates with w > 0; EDGE = sum w over the candidates on a face of the volume (a in {0, n_angles - 1} when
+ * n_angles > 1, or j or i in {0, S - 1} when S > 1): a large share of W there says the window cut the distribution.
+ * Headroom: at the capacities (1 024 angles, window 31, every score equal, the winner at index 0) the largest slot is
+ * AA = 1 487 384 306 207 686 656 < 2^61, and 8 * d <= 2^35: no sum overflows.
+ * A pair whose record says ICPMI_GM_ST_CAPACITY gets twelve zeros.  ICPMI_GM_ST_EMPTY goes through the rule: every score
+ * is 0, the winner index 0, every weight 2^20 — the uniform distribution of "no information".
+ * Refusals, on the host before anything is enqueued: n_pairs == 0: ICPMI_OK, nothing done; a null volume, records or
+ * moments, n_pairs < 0, n_angles < 1, window < 0, half_step outside [1, ICPMI_GMOM_MAX_HALF_STEP] or moments not 8-byte
+ * aligned: ICPMI_ERR_ARG; window > ICPMI_GM_MAX_WINDOW or n_angles > ICPMI_GM_MAX_ANGLES: ICPMI_ERR_UNSUPPORTED.
+ * Launches: one memset and gm_moments_kernel — workgroups of ICPMI_GM_THREADS threads over (chunk of candidates, pair),
+ * each ending in one 64-bit integer atomicAdd per non-zero slot. */
+#define ICPMI_GMOM_INTS 12
+#define ICPMI_GMOM_W 0
+#define ICPMI_GMOM_A 1
+#define ICPMI_GMOM_J 2
+#define ICPMI_GMOM_I 3
+#define ICPMI_GMOM_AA 4
+#define ICPMI_GMOM_AJ 5
+#define ICPMI_GMOM_AI 6
+#define ICPMI_GMOM_JJ 7
+#define ICPMI_GMOM_JI 8
+#define ICPMI_GMOM_II 9
+#define ICPMI_GMOM_SUPPORT 10
+#define ICPMI_GMOM_EDGE 11
+#define ICPMI_GMOM_WEIGHT_BITS 20
+#define ICPMI_GMOM_MAX_HALF_STEP 32767
+int icpmi_grid_match_moments(const int32_t* volume, const int32_t* records, int32_t n_pairs, int32_t n_angles,
+                             int32_t window, int32_t half_step, int64_t* moments, void* stream);
+
 /* ── pose graph: PoseGraph2D.optimize, utilities/pose_graph.py:83-134 ──────────
  * Gauss-Newton on SE(2) over n_nodes poses [x, y, theta] (nodes: device, updated
  * in place) and n_edges constraints (i, j, z_ij [3], Omega [3][3] row-major).

@@ -134,6 +134,11 @@ __device__ __forceinline__ int wave_sum(int v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, ICPMI_WAVE);
     return v;
 }
+__device__ __forceinline__ long long wave_sum(long long v) {     // the two halves shuffled apart, one 64-bit add per step
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, ICPMI_WAVE);
+    return v;
+}
 __device__ __forceinline__ double wave_min(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, ICPMI_WAVE));

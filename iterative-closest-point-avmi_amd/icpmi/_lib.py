@@ -39,6 +39,10 @@ GMREC_INTS, GMREC_STATUS, GMREC_ROWS, GMREC_INDEX, GMREC_A, GMREC_J, GMREC_I, GM
 # icpmi_grid_search_batch (GMW_*: its capacities, its planned survivor grid, and the four slots its record adds to GMREC_*)
 GMW_MAX_WINDOW, GMW_MAX_ANGLES, GMW_SCORE_GROUPS = 255, 16384, 2048
 GMW_REC_INTS, GMW_REC_BLOCKS, GMW_REC_SURVIVORS, GMW_REC_SEED, GMW_REC_MAX_BOUND = 12, 8, 9, 10, 11
+# icpmi_grid_match_moments (GMOM_*: the twelve int64 slots of a pair's moments, the weight's bits, the largest half_step)
+GMOM_INTS, GMOM_W, GMOM_A, GMOM_J, GMOM_I, GMOM_AA, GMOM_AJ, GMOM_AI, GMOM_JJ, GMOM_JI, GMOM_II, GMOM_SUPPORT, GMOM_EDGE = (
+    12, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11)
+GMOM_WEIGHT_BITS, GMOM_MAX_HALF_STEP = 20, 32767
 INFO_SLOTS = ("H_tt", "H_tx", "H_ty", "H_xx", "H_xy", "H_yy", "g_t", "g_x", "g_y", "sse", "inliers", "rows", "status")
 
 
@@ -171,6 +175,7 @@ _SIGS = {
     "icpmi_grid_search_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double] + [C.c_void_p] * 4 +
                                 [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "icpmi_grid_match_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "icpmi_pose_graph_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
     "icpmi_pose_graph_optimize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                             C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_size_t,

@@ -1,7 +1,9 @@
 """Correlative scan-to-map matching: clouds scored against the occupancy grid itself over a window of rotations and
 whole-cell shifts (``icpmi_grid_score_field``, ``icpmi_grid_match_batch``; the contract is include/icpmi.h's), and the same
 search over a wide window (``icpmi_grid_bound_field``, ``icpmi_grid_search_batch``): blocks of shifts bounded from above by
-a max-pooled field, pruned against a seed score, the exhaustive winner returned.
+a max-pooled field, pruned against a seed score, the exhaustive winner returned.  ``icpmi_grid_match_moments`` reads the
+volume of a match once more: the integer-weighted moments of the candidates about the winner, from which
+``gaussian_of_moments`` forms a sub-cell pose and a covariance on the host.
 
 The reference registers a scan against a cloud only (slam.py:53-98, 111-183); this reads the map ``utilities.mapping``
 builds.  The log-odds are quantised to int16 and a candidate's score is the integer sum of the field under the scan's
@@ -68,6 +70,69 @@ def angle_grid(theta, angular_window, angular_step):
     return theta[:, None] + offsets[None, :], int(np.argmin(np.abs(offsets)))
 
 
+def half_step(half_log_odds, k):
+    """``half_log_odds`` — the drop of the mean log-odds under a scan's hits that halves a candidate's weight — in the field
+    units of shift ``k``: int(np.rint(half_log_odds * 2^k)), the ``half_step`` of ``icpmi_grid_match_moments``.  ValueError
+    unless it lies in [1, GMOM_MAX_HALF_STEP]."""
+    h = int(np.rint(float(half_log_odds) * 2.0 ** int(k)))
+    if not 1 <= h <= _lib.GMOM_MAX_HALF_STEP:
+        raise ValueError(f"half_log_odds {half_log_odds} at shift {k} is a half_step of {h}, outside [1, {_lib.GMOM_MAX_HALF_STEP}]")
+    return h
+
+
+def match_moments(volume, records, n_pairs, n_angles, window, half_step, out=None):
+    """``icpmi_grid_match_moments`` of a match's (B, A, S, S) int32 device volume and its (B, 8) int32 device records, as
+    ``GridMatchBatch.run()`` left them on the current stream -> the (B, GMOM_INTS) int64 device tensor of moments (``out``
+    when given).  Enqueues and does not synchronise."""
+    S = 2 * int(window) + 1
+    for name, ten, cols in (("volume", volume, n_angles * S * S), ("records", records, _lib.GMREC_INTS)):
+        if ten.dtype != torch.int32 or not ten.is_contiguous() or ten.numel() < n_pairs * cols:
+            raise ValueError(f"{name} must be a contiguous int32 device tensor of at least {n_pairs} x {cols} values")
+    if out is None:
+        out = torch.empty((max(n_pairs, 1), _lib.GMOM_INTS), dtype=torch.int64, device=volume.device)
+    elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() < n_pairs * _lib.GMOM_INTS:
+        raise ValueError(f"out must be a contiguous int64 device tensor of at least {n_pairs} x {_lib.GMOM_INTS} values")
+    check(_lib.lib().icpmi_grid_match_moments(_ptr(volume), _ptr(records), int(n_pairs), int(n_angles), int(window), int(half_step),
+                                              _ptr(out), _stream()), "grid_match_moments")
+    return out
+
+
+def gaussian_of_moments(moments, resolution, angular_step):
+    """The Gaussian a (B, GMOM_INTS) integer array of moments describes, in NumPy on the host -> a dict:
+
+    ``offset`` (B, 3): (resolution * mu_I, resolution * mu_J, angular_step * mu_A), the weighted mean of the candidates
+    relative to the winner, mu_X = M_X / M_W; ``covariance`` (B, 3, 3), symmetric, of the pose's own parameters (t_x, t_y,
+    theta) with world = R(theta) p + t: the index-unit central moments (M_XY M_W - M_X M_Y) / M_W^2 — the numerator formed
+    exactly in Python integers, one float64 division — plus 1/12 on the diagonal (a candidate is a bin one cell or one step
+    wide, so a single surviving candidate does not claim zero variance), reordered to [x, y, theta] = [I, J, A] and scaled by
+    diag(resolution, resolution, angular_step); ``support`` (B,), the candidates with a non-zero weight; ``edge_weight``
+    (B,), the share of the weight on the faces of the volume — near 1 the window cut the distribution off.
+
+    ``angular_step``: radians, one value or one per pair.  A search over one angle has no step: pass 0, and the theta row
+    and column of the covariance and the theta offset are zero.  A pair with M_W = 0 (``ST_CAPACITY``: nothing was read) gets
+    NaN offset, covariance and edge_weight."""
+    M = np.asarray(moments).reshape(-1, _lib.GMOM_INTS)
+    B = len(M)
+    res = float(resolution)
+    steps = np.broadcast_to(np.asarray(angular_step, dtype=np.float64), (B,))
+    first = (_lib.GMOM_I, _lib.GMOM_J, _lib.GMOM_A)                                   # [x, y, theta] = [I, J, A]
+    second = ((_lib.GMOM_II, _lib.GMOM_JI, _lib.GMOM_AI), (_lib.GMOM_JI, _lib.GMOM_JJ, _lib.GMOM_AJ), (_lib.GMOM_AI, _lib.GMOM_AJ, _lib.GMOM_AA))
+    offset, cov, edge = np.full((B, 3), np.nan), np.full((B, 3, 3), np.nan), np.full(B, np.nan)
+    for b in range(B):
+        m = [int(v) for v in M[b]]
+        W = m[_lib.GMOM_W]
+        if W == 0:
+            continue
+        D = (res, res, float(steps[b]))
+        for p in range(3):
+            offset[b, p] = D[p] * (float(m[first[p]]) / float(W))
+            for q in range(p, 3):
+                central = float(m[second[p][q]] * W - m[first[p]] * m[first[q]]) / float(W * W)
+                cov[b, p, q] = cov[b, q, p] = (D[p] * D[q]) * (central + (1.0 / 12.0 if p == q else 0.0))
+        edge[b] = float(m[_lib.GMOM_EDGE]) / float(W)
+    return {"offset": offset, "covariance": cov, "support": M[:, _lib.GMOM_SUPPORT].astype(np.int64), "edge_weight": edge}
+
+
 class GridMatchBatch:
     """Pair b: cloud ``pair_clouds[b]`` of ``cloud_set`` scored against ``grid`` at the translation ``translations[b]``
     under the rotations ``angle_rows[b]`` (radians, [B, A]) and every shift of whole cells within ``window``.
@@ -77,11 +142,25 @@ class GridMatchBatch:
     ``score_field`` returned, to score against the map as it was then; ``None``: the field is rebuilt by every ``run()``.
     ``run()`` enqueues the launches on the current stream and returns the (B, 8) int32 record tensor, without a
     synchronisation; ``want_scores``: ``scores`` then holds the full (B, A, S, S) int32 volume.  ``unpack()`` reads the
-    records back and forms the poses."""
+    records back and forms the poses.
 
-    def __init__(self, grid, cloud_set, pair_clouds, translations, angle_rows, window, centre_angle=-1, field=None, want_scores=False):
+    ``half_log_odds`` (None: off): ``run()`` also enqueues ``match_moments`` of the volume into ``moments``, with
+    ``half_step(half_log_odds, k)``, and ``unpack()`` adds the sub-cell pose and its covariance to ``info``.  The volume is
+    then kept as with ``want_scores``, and every angle row must be evenly spaced (its step scales the theta moments)."""
+
+    def __init__(self, grid, cloud_set, pair_clouds, translations, angle_rows, window, centre_angle=-1, field=None, want_scores=False,
+                 half_log_odds=None):
         self._setup(grid, cloud_set, pair_clouds, translations, angle_rows, window, centre_angle, field, MAX_WINDOW, MAX_ANGLES)
         B, dev = self.B, cloud_set.pts.device
+        self.half_step = self.moments = None
+        if half_log_odds is not None:
+            self.half_step = half_step(half_log_odds, self.k)
+            gaps = np.diff(self.angles, axis=1)
+            if self.A > 1 and not all(np.allclose(g, g.mean()) for g in gaps):
+                raise ValueError("half_log_odds needs evenly spaced angle rows: the step scales the moments in theta")
+            self.angular_step = (self.angles[:, -1] - self.angles[:, 0]) / (self.A - 1) if self.A > 1 else np.zeros(B)
+            self.moments = torch.zeros((max(B, 1), _lib.GMOM_INTS), dtype=torch.int64, device=dev)
+            want_scores = True
         self.records = torch.zeros((max(B, 1), _lib.GMREC_INTS), dtype=torch.int32, device=dev)
         self.scores = torch.zeros((max(B, 1), self.A, self.S, self.S), dtype=torch.int32, device=dev) if want_scores else None
         need = _lib.lib().icpmi_grid_match_workspace_bytes(B, self.A, self.W)
@@ -138,13 +217,18 @@ class GridMatchBatch:
             cs.off_host.ctypes.data_as(C.c_void_p), _ptr(cs.cnt), cs.n_clouds, _ptr(self.pair),
             self.pair_host.ctypes.data_as(C.c_void_p), self.B, _ptr(self.t), _ptr(self.cos_sin), self.A, self.W,
             self.centre_angle, _ptr(self.records), _ptr(self.scores), _ptr(self.ws), self.ws.numel(), _stream()), "grid_match")
+        if self.moments is not None:
+            match_moments(self.scores, self.records, self.B, self.A, self.W, self.half_step, out=self.moments)
         return self.records
 
     def unpack(self, records=None):
         """-> (R [B,2,2], t [B,2], score [B] int, info) on the host (synchronises).  t = translation + ((i - W), (j - W)) *
         resolution, R from the caller's cos / sin at a.  info: ``status``, ``rows``, ``index``, ``a``, ``j``, ``i``,
         ``centre_score``, ``shift_bits``, ``angle`` and ``mean_log_odds`` = score / (rows * 2^k), the mean log-odds under the
-        hits (0 where no row was scored)."""
+        hits (0 where no row was scored).  With ``half_log_odds`` (R, t, score stay the whole-cell winner) also ``moments``
+        (B, GMOM_INTS) int64, ``gaussian_of_moments``' ``offset``, ``covariance``, ``support`` and ``edge_weight``, and the
+        refined pose: ``t_refined`` = t + offset[:, :2], ``angle_refined`` = angle + offset[:, 2], ``R_refined`` from NumPy's cos
+        and sin of it."""
         rec = (self.records if records is None else records).cpu().numpy()[:self.B].astype(np.int64)
         col = lambda s: rec[:, s].copy()                       # noqa: E731
         a, j, i, score, rows = (col(s) for s in (_lib.GMREC_A, _lib.GMREC_J, _lib.GMREC_I, _lib.GMREC_SCORE, _lib.GMREC_ROWS))
@@ -156,6 +240,12 @@ class GridMatchBatch:
         info = {"status": col(_lib.GMREC_STATUS), "rows": rows, "index": col(_lib.GMREC_INDEX), "a": a, "j": j, "i": i,
                 "centre_score": col(_lib.GMREC_CENTRE), "shift_bits": self.k, "angle": self.angles[b, a],
                 "mean_log_odds": np.where(rows > 0, score / (np.maximum(rows, 1) * 2.0 ** self.k), 0.0)}
+        if self.moments is not None:
+            info["moments"] = self.moments.cpu().numpy()[:self.B]
+            info.update(gaussian_of_moments(info["moments"], res, self.angular_step))
+            info["t_refined"], info["angle_refined"] = t + info["offset"][:, :2], info["angle"] + info["offset"][:, 2]
+            co, si = np.cos(info["angle_refined"]), np.sin(info["angle_refined"])
+            info["R_refined"] = np.stack([np.stack([co, -si], axis=1), np.stack([si, co], axis=1)], axis=1)
         return R, t, score, info
 
 
@@ -166,10 +256,15 @@ class GridSearchBatch(GridMatchBatch):
 
     ``bounds``: a tensor an earlier ``bound_field(field, block)`` returned, handed back like ``field=`` (no cache: without it
     the bound field is rebuilt by every ``run()``).  ``run()`` returns the (B, 12) int32 record tensor; ``want_bounds``:
-    ``bounds_volume`` then holds the (B, A, NB, NB) int32 upper bounds of the blocks."""
+    ``bounds_volume`` then holds the (B, A, NB, NB) int32 upper bounds of the blocks.  ``half_log_odds`` is refused: this
+    search forms no volume to take moments of."""
 
     def __init__(self, grid, cloud_set, pair_clouds, translations, angle_rows, window, centre_angle=-1, block=8, field=None, bounds=None,
-                 want_bounds=False):
+                 want_bounds=False, half_log_odds=None):
+        if half_log_odds is not None:
+            raise ValueError("the wide search forms no score volume, so it has no moments: run GridMatchBatch (match_scans) with "
+                             "half_log_odds around the wide search's winner")
+        self.half_step = self.moments = None
         self._setup(grid, cloud_set, pair_clouds, translations, angle_rows, window, centre_angle, field, WIDE_MAX_WINDOW, WIDE_MAX_ANGLES)
         if block not in BLOCKS:
             raise ValueError(f"block must be one of {BLOCKS}, got {block}")

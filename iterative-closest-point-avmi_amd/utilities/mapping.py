@@ -324,7 +324,7 @@ class OccupancyGrid2D:
             raise ValueError(f"{n} scans but {len(p)} predicted poses")
         return p
 
-    def _match_set(self, cs, pair_clouds, poses, linear_window, angular_window, angular_step, field, want_scores=False):
+    def _match_set(self, cs, pair_clouds, poses, linear_window, angular_window, angular_step, field, want_scores=False, half_log_odds=None):
         from icpmi import gridmatch
         if cs.pts.device != self._dev:
             raise ValueError(f"the clouds live on {cs.pts.device}, the grid on {self._dev}")
@@ -334,27 +334,32 @@ class OccupancyGrid2D:
         else:
             angles, centre = gridmatch.angle_grid(xyt[:, 2], angular_window, angular_step)
             W = int(round(linear_window / self.resolution))
-        job = gridmatch.GridMatchBatch(self, cs, pair_clouds, xyt[:, :2], angles, W, centre, field=field, want_scores=want_scores)
+        job = gridmatch.GridMatchBatch(self, cs, pair_clouds, xyt[:, :2], angles, W, centre, field=field, want_scores=want_scores,
+                                       half_log_odds=half_log_odds)
         job.run()
         return job
 
     def match_scans(self, clouds, predicted_poses, linear_window=0.6, angular_window=12.0, angular_step=1.0, voxel_size=None,
-                    field=None):
+                    field=None, half_log_odds=None):
         """Localise every scan of ``clouds`` (sensor frame, (n, 2) arrays or a device ``CloudSet``) in this map around its
         predicted pose ([x, y, theta] or a 3 x 3 matrix): the pose among theta + np.deg2rad(np.arange(-angular_window,
         angular_window + angular_step, angular_step)) (slam.py:146-148's expression) and shifts of whole cells up to
         W = int(round(linear_window / resolution)) each way that puts the scan's hits on the largest sum of log-odds.
         ``voxel_size``: the scans pass through ``voxel_downsample`` first.  One chain of launches for all scans.
+        ``half_log_odds`` (None: off): the drop of the mean log-odds under the hits that halves a candidate's weight; ``info``
+        then carries the moments of the score volume about the winner, the sub-cell pose (``t_refined``, ``angle_refined``,
+        ``R_refined``) and its ``covariance``, with ``edge_weight`` to show a distribution the window cut off.
         -> (R [B,2,2], t [B,2], score [B], info) as ``icpmi.gridmatch.GridMatchBatch.unpack`` forms them."""
         from icpmi import gridmatch
         cs = gridmatch.cloud_set_of(clouds, voxel_size)
-        return self._match_set(cs, np.arange(cs.n_clouds), predicted_poses, linear_window, angular_window, angular_step, field).unpack()
+        return self._match_set(cs, np.arange(cs.n_clouds), predicted_poses, linear_window, angular_window, angular_step, field,
+                               half_log_odds=half_log_odds).unpack()
 
     def match_scan(self, points_local, predicted_pose, linear_window=0.6, angular_window=12.0, angular_step=1.0, voxel_size=None,
-                   field=None):
+                   field=None, half_log_odds=None):
         """``match_scans`` of one scan -> (R (2,2), t (2,), score, info) with scalar entries in ``info``."""
         R, t, score, info = self.match_scans([points_local], [predicted_pose], linear_window, angular_window, angular_step,
-                                             voxel_size, field)
+                                             voxel_size, field, half_log_odds)
         return R[0], t[0], int(score[0]), {k: (v[0] if isinstance(v, np.ndarray) else v) for k, v in info.items()}
 
     def score_poses(self, points_local, poses, field=None):
@@ -368,7 +373,7 @@ class OccupancyGrid2D:
         return score, info
 
     def match_history(self, history, ids, predicted_poses, linear_window=0.6, angular_window=12.0, angular_step=1.0, voxel_size=None,
-                      field=None):
+                      field=None, half_log_odds=None):
         """``match_scans`` of scans resident in an ``icpmi.ScanHistory``, by id: the raw rows are read where they are and no
         scan is uploaded.  ``voxel_size``: the history's own filtered copies where it is one of the history's voxel sizes;
         any other size filters every resident scan first."""
@@ -383,7 +388,8 @@ class OccupancyGrid2D:
             cs = history.rs_vox
         else:
             cs = voxel_downsample_set(history.raw, voxel_size)
-        return self._match_set(cs, ids, predicted_poses, linear_window, angular_window, angular_step, field).unpack()
+        return self._match_set(cs, ids, predicted_poses, linear_window, angular_window, angular_step, field,
+                               half_log_odds=half_log_odds).unpack()
 
     # ── the same search over a wide window (icpmi.gridmatch.GridSearchBatch): metres and the full circle ─────────────
     def bound_field(self, field=None, block=8):
