@@ -321,8 +321,11 @@ __global__ __launch_bounds__(RSR_THREADS) void rs_refine_finish_kernel(
 //      is np.argmin over all.  The nearest-neighbour distances are the exact ones; their SUM is taken in this kernel's own
 //      fixed order (a lane per row with stride 64, then a wave tree; the single-pair kernel strides by 256 and NumPy's
 //      mean sums pairwise), so a score agrees with the other two to rounding (1e-13 in the tests) and the arg-min is
-//      theirs unless two angles tie to within that rounding — which the goldens, the 512-pair comparisons and the
-//      symmetric clouds of the tests have not produced, and which no fixture pins;
+//      theirs unless two angles tie to within that rounding.  Pinned (tests/test_rotation_bound_gpu.py): between two
+//      angles whose scores differ by 1e-9 relative and more the lower one wins in either table order — no bound hides it,
+//      on walls, specks, turned and distant frames and at the row counts where the loops below change — with the same
+//      bits as scoring every angle; exact ties go to the first entry.  Not pinned: the winner between scores that differ
+//      by less than the rounding of a float64 sum;
 //   5. scores the fine grid around the winner (features.py:227-232) the same way and writes the record and, for the
 //      ICP that follows, R_init / t_init (device memory: no host round trip between pre-alignment and ICP).
 // Typically 8-20 of 240 coarse angles are scored exactly, each by searches of ~10 candidates.
