@@ -862,29 +862,44 @@ int icpmi_grid_match_moments(const int32_t* volume, const int32_t* records, int3
  * The split inverts the chain part T on its own, so a chain edge with (almost)
  * no information would cost it digits that a solve of the whole system keeps.
  * The call reads the information matrices back and treats a chain edge as weak
- * when the Gershgorin lower bound of its symmetric part is below S / (3 n), S
- * the largest row sum of |Omega| in the graph: such an edge enters T as S I and
- * its remainder Omega - S I joins the closures (same sum, T as stiff there as
- * anywhere).  That needs room: size the workspace with
+ * when the smallest eigenvalue of its symmetric part (closed form) is below
+ * S / (3 n), S the largest row sum of |Omega| in the graph: such an edge enters
+ * T as S I and its remainder Omega - S I joins the closures (same sum, T as
+ * stiff there as anywhere).  That needs room: size the workspace with
  * icpmi_pose_graph_weighted_workspace_bytes (edges_omega_host: the same
  * matrices on the host); with the plain size query a graph that has weak chain
- * edges ends at once with status 4.  Status 4 also ends a launch where a block
- * of T is exactly singular or the closure system has an exactly zero pivot.
- * info (device, 10 doubles): iterations run, status (0 nothing to do: fewer
- * than two nodes or no edges; 1 converged: step norm < convergence_eps; 2
- * iteration limit; 3 singular system, reported by the dense elimination only
- * (an exactly zero pivot, LAPACK's error): the nodes keep the values of the
- * previous iteration, pose_graph.py:117-119; 4 split step refused: the nodes
- * keep the values of the previous iteration and `iterations run` counts the
- * applied ones — continue with icpmi_pose_graph_optimize_dense for the
- * remaining iterations, as PoseGraph2D.optimize does), norm of the last step;
- * then the time spent per phase in microseconds, summed over the iterations
- * (assembly, chain factorisation, chain sweeps, closure system, its solve,
- * update of dx, apply).
+ * edges ends at once with ICPMI_PG_ST_REFUSED.  That status also ends a launch
+ * where a block of T is exactly singular or the closure system has an exactly
+ * zero pivot.
+ * info (device, ICPMI_PGINFO_DOUBLES doubles), slots ICPMI_PGINFO_*:
+ * ITERATIONS run; STATUS, one of ICPMI_PG_ST_* (NOTHING to do: fewer than two
+ * nodes or no edges; CONVERGED: step norm < convergence_eps; MAXITER: iteration
+ * limit; SINGULAR system, reported by the dense elimination only (an exactly
+ * zero pivot, LAPACK's error): the nodes keep the values of the previous
+ * iteration, pose_graph.py:117-119; REFUSED split step: the nodes keep the
+ * values of the previous iteration and ITERATIONS counts the applied ones —
+ * continue with icpmi_pose_graph_optimize_dense for the remaining iterations,
+ * as PoseGraph2D.optimize does); STEP, the norm of the last step; then from
+ * PHASE_US on the ICPMI_PGINFO_PHASES device clocks in microseconds, summed over
+ * the iterations: assembly; the closure columns W; the chain solve (cyclic
+ * reduction of T, which is its factorisation, and the back substitution, on all
+ * columns); the closure system; its solve; dx; apply.  On the dense path the
+ * four clocks between assembly and dx stay 0 and the whole elimination is in dx.
  * icpmi_pose_graph_optimize_dense: the same call with the dense path forced;
- * it never returns status 4.
+ * it never returns ICPMI_PG_ST_REFUSED.
  * workspace: icpmi_pose_graph_workspace_bytes(edges_ij_host, n_nodes, n_edges),
  * icpmi_pose_graph_dense_workspace_bytes(...) for the dense call. */
+#define ICPMI_PG_ST_NOTHING 0
+#define ICPMI_PG_ST_CONVERGED 1
+#define ICPMI_PG_ST_MAXITER 2
+#define ICPMI_PG_ST_SINGULAR 3
+#define ICPMI_PG_ST_REFUSED 4
+#define ICPMI_PGINFO_DOUBLES 10
+#define ICPMI_PGINFO_ITERATIONS 0
+#define ICPMI_PGINFO_STATUS 1
+#define ICPMI_PGINFO_STEP 2
+#define ICPMI_PGINFO_PHASE_US 3
+#define ICPMI_PGINFO_PHASES 7
 size_t icpmi_pose_graph_workspace_bytes(const int32_t* edges_ij_host, int32_t n_nodes, int32_t n_edges);
 size_t icpmi_pose_graph_weighted_workspace_bytes(const int32_t* edges_ij_host, const double* edges_omega_host,
                                                  int32_t n_nodes, int32_t n_edges);

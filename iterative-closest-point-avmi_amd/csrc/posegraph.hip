@@ -17,14 +17,23 @@
 // takes the general path: the same dense matrix as the reference, eliminated
 // with partial pivoting by the workgroup in global memory.
 //
+// An iteration of pose_graph_kernel is its phases in this order (PgPhase names their clocks):
+//     assemble; then either the dense solve, or closure columns -> chain solve (reduce, back-substitute) ->
+//     closure system -> closure solve -> dx; then apply.
+// Each is a function called once, but for two that stay as they were because the measured time depends on it: the
+// chain solve is written out in the kernel (as a function, of the same text, it runs 4 % slower at 2 000 and 4 000
+// nodes), and the assembly is one node loop that branches on the path where it stores (split into a chain and a
+// dense loop over a shared gather, dx ran 4 to 9 % slower).  With 256 VGPRs in use and over a hundred SGPRs spilled,
+// the allocation of the whole kernel moves with the shape of any of its parts.
+//
 // The split is only as good as T.  The host plan (pg_plan) reads the information
 // matrices and gives every weak chain edge a twin among the closures, so that T
 // stays as stiff as the whole system; a graph with a chain edge that carries no
 // information at all along some direction is not split.  Where a block of T or
 // the closure system still turns out exactly singular, the launch ends with
-// status PG_REFUSED and the poses of the previous iteration, and the caller
-// continues from there on the dense path.  Only the dense elimination, like the
-// reference's LAPACK call, ever reports a singular system.
+// status ICPMI_PG_ST_REFUSED and the poses of the previous iteration, and the
+// caller continues from there on the dense path.  Only the dense elimination,
+// like the reference's LAPACK call, ever reports a singular system.
 //
 // Every sum has a fixed order (per-node gathers in edge order, fixed reduction
 // trees): results are reproducible run to run.
@@ -37,29 +46,56 @@ constexpr int PG_THREADS = 512;                    // one workgroup, 2 waves per
 constexpr double PG_PI = 3.141592653589793;        // np.pi
 constexpr double PG_2PI = 6.283185307179586;       // 2 * np.pi
 
-struct PgArgs {
-    double* nodes;                 // [n][3] x, y, theta — updated in place
-    const int32_t* ei;             // [m]
-    const int32_t* ej;             // [m]
-    const double* z;               // [m][3]
-    const double* omega;           // [m][9]
-    const int32_t* csr_ptr;        // [n+1] incident edges of every node ...
-    const int32_t* csr_edge;       // ... in edge order
-    const int32_t* loop_slot;      // [m] index among the non-chain edges, -1 for a chain edge
-    const int32_t* loop_edge;      // [k] edge ids of the non-chain edges
-    int n, m, k, dense, n_iter, fix;
-    double eps;
-    double *D, *U, *L, *b;         // block tridiagonal T per node: D[v] = H[v][v], U[v] = H[v][v+s], L[v] = H[v][v-s] (s = level stride)
-    double *Dinv, *G;              // per even node of a level: L[e] * inv(D[e-s]) and U[e] * inv(D[e+s])
-    double* X;                     // [3n][1 + 3k] right-hand sides -> solutions (column 0 = r = -b, then W)
-    double* AB;                    // [k][18] Jacobians of the non-chain edges
-    double *M, *g, *y;             // [3k][3k], [3k], [3k]
-    double* dx;                    // [3n]
-    double* Hd;                    // [3n][3n], dense path only
-    double* info;                  // [0] iterations run, [1] status, [2] last step norm
+// The device arrays, listed ONCE: the plan's index arrays, then what the kernel works in (m: edges with the twins,
+// w: twins).  Over a null base it only counts (the *_workspace_bytes queries); over the caller's workspace it is the
+// pointer block the kernel gets by value, inside PgArgs.  The + 1 keep zero-sized arrays distinct.
+struct PgWs {
+    Carve c;
+    int n, m, k, dense, w;
+    // rows of the system, closure unknowns, columns of X: int like the kernel's indices (the workspace of a graph
+    // near 2^31 / 3 rows would not fit any device); every product of two of them is taken in size_t
+    int N3 = 3 * n, K = 3 * k, ncols = 1 + K;
+    size_t blocks = 9 * (size_t)n * 8;
+    int32_t* ei = c.take<int32_t>((size_t)m * 2 * 4);            // [m] ei, then [m] ej
+    int32_t* ej = ei ? ei + m : nullptr;
+    int32_t* csr_ptr = c.take<int32_t>(((size_t)n + 1) * 4);     // [n+1] incident edges of every node ...
+    int32_t* csr_edge = c.take<int32_t>(((size_t)2 * m + 1) * 4);        // ... in edge order
+    int32_t* loop_slot = c.take<int32_t>((size_t)(m + 1) * 4);   // [m] index among the non-chain edges, -1 for a chain edge
+    int32_t* loop_edge = c.take<int32_t>((size_t)(k + 1) * 4);   // [k] edge ids of the non-chain edges
+    // block tridiagonal T per node: D[v] = H[v][v], U[v] = H[v][v+s], L[v] = H[v][v-s] (s = level stride)
+    double *D = c.take<double>(blocks), *U = c.take<double>(blocks), *L = c.take<double>(blocks);
+    // per even node of a level: L[e] * inv(D[e-s]) and U[e] * inv(D[e+s])
+    double *Dinv = c.take<double>(blocks), *G = c.take<double>(blocks);
+    double* X = c.take<double>((size_t)N3 * ncols * 8);                // [3n][1 + 3k] right-hand sides -> solutions (column 0 = r = -b, then W)
+    double* AB = c.take<double>(18 * (size_t)(k + 1) * 8);       // [k][18] Jacobians of the non-chain edges
+    double *M = c.take<double>(((size_t)K * K + 1) * 8), *g = c.take<double>(((size_t)K + 1) * 8);       // [3k][3k], [3k] -> y
+    double* dx = c.take<double>((size_t)N3 * 8);                         // [3n]
+    double* Hd = dense ? c.take<double>((size_t)N3 * N3 * 8) : nullptr;  // [3n][3n], dense path only
+    double* tw_omega = w ? c.take<double>((size_t)m * 9 * 8) : nullptr;  // the caller's Omega and z with the twins' rows:
+    double* tw_z = w ? c.take<double>((size_t)m * 3 * 8) : nullptr;      // only where there are twins
+    size_t bytes = c.off + 256;
 };
 
-enum { PG_NOTHING = 0, PG_CONVERGED = 1, PG_MAXITER = 2, PG_SINGULAR = 3, PG_REFUSED = 4 };
+struct PgArgs : PgWs {
+    double* nodes;                 // [n][3] x, y, theta — updated in place
+    const double* z;               // [m][3]    the caller's arrays, or tw_z / tw_omega
+    const double* omega;           // [m][9]
+    int n_iter, fix;
+    double eps;
+    double* info;                  // [ICPMI_PGINFO_DOUBLES]
+};
+
+// the phases of an iteration, in the order of their clocks in info[ICPMI_PGINFO_PHASE_US + .]
+enum PgPhase { PG_ASSEMBLE, PG_CLOSURE_COLUMNS, PG_CHAIN_SOLVE, PG_CLOSURE_SYSTEM, PG_CLOSURE_SOLVE, PG_DX, PG_APPLY, PG_PHASES };
+static_assert(PG_PHASES == ICPMI_PGINFO_PHASES && ICPMI_PGINFO_PHASE_US + PG_PHASES == ICPMI_PGINFO_DOUBLES, "info record");
+
+// phase clocks: thread 0, the 100 MHz wall clock; mark(p) books the time since the last mark to phase p
+struct PgClock {
+    long long acc[PG_PHASES] = {0, 0, 0, 0, 0, 0, 0}, last = wall_clock64();
+    __device__ __forceinline__ void mark(PgPhase p) {
+        if (threadIdx.x == 0) { const long long now = wall_clock64(); acc[p] += now - last; last = now; }
+    }
+};
 
 // ── 3x3 helpers (row-major, fully unrolled) ─────────────────────────────────
 struct M3 { double a[9]; };
@@ -128,21 +164,6 @@ __device__ __forceinline__ void pg_linearise(const double* xi, const double* xj,
 }
 
 // ── workgroup-wide helpers ───────────────────────────────────────────────────
-// argmax of |v| with the lowest index among equals; every thread gets the result
-__device__ __forceinline__ void block_argmax(double v, int idx, double* s_val, int* s_idx, double& out_v, int& out_i) {
-    s_val[threadIdx.x] = v; s_idx[threadIdx.x] = idx;
-    __syncthreads();
-    for (int o = PG_THREADS / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            const double a = s_val[threadIdx.x], b = s_val[threadIdx.x + o];
-            const int ia = s_idx[threadIdx.x], ib = s_idx[threadIdx.x + o];
-            if (b > a || (b == a && ib < ia)) { s_val[threadIdx.x] = b; s_idx[threadIdx.x] = ib; }
-        }
-        __syncthreads();
-    }
-    out_v = s_val[0]; out_i = s_idx[0];
-    __syncthreads();
-}
 __device__ __forceinline__ double block_total(double v, double* s_val) {
     s_val[threadIdx.x] = v;
     __syncthreads();
@@ -168,12 +189,7 @@ __device__ bool block_lu_solve(double* a, int N, double* rhs, double* s_val, int
                 const double v = fabs(a[(size_t)r * N + p]);
                 if (v > best) { best = v; bi = r; }
             }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const double ob = __shfl_xor(best, o, ICPMI_WAVE);
-                const int oi = __shfl_xor(bi, o, ICPMI_WAVE);
-                if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-            }
+            wave_first_best(best, bi, [](double x, double y) { return x > y; });      // the lowest row among equal |a|
             if (lane_id() == 0) { s_val[0] = best; s_idx[0] = bi; }
         }
         __syncthreads();
@@ -211,106 +227,157 @@ __device__ bool block_lu_solve(double* a, int N, double* rhs, double* s_val, int
     return true;
 }
 
+// ── assemble: linearise every edge and gather per node (pose_graph.py:96-105) ──
+// One loop for both paths (see the head of the file): what a node gathers is the same, where it is stored differs.
+__device__ __forceinline__ void pg_assemble(const PgArgs& g) {
+    const int tid = threadIdx.x, n = g.n, ncols = g.ncols, N3 = g.N3, f = g.fix;
+    for (int v = tid; v < n; v += PG_THREADS) {
+        M3 D = m3_zero(), U = m3_zero(), L = m3_zero();
+        double b[3] = {0.0, 0.0, 0.0};
+        for (int t = g.csr_ptr[v]; t < g.csr_ptr[v + 1]; ++t) {
+            const int q = g.csr_edge[t];
+            const int i = g.ei[q], j = g.ej[q];
+            double e[3], tmp[3], Oe[3];
+            M3 A, B;
+            pg_linearise(g.nodes + 3 * i, g.nodes + 3 * j, g.z + 3 * q, e, A, B);
+            const M3 Om = m3_load(g.omega + 9 * (size_t)q);
+            const M3 OA = m3_mul(Om, A), OB = m3_mul(Om, B);
+            m3_vec(Om, e, Oe);
+            const bool in_T = g.dense || g.loop_slot[q] < 0;
+            if (i == v) {
+                m3_tvec(A, Oe, tmp); b[0] += tmp[0]; b[1] += tmp[1]; b[2] += tmp[2];
+                if (in_T) m3_add(D, m3_tmul(A, OA));
+            }
+            if (j == v) {
+                m3_tvec(B, Oe, tmp); b[0] += tmp[0]; b[1] += tmp[1]; b[2] += tmp[2];
+                if (in_T) m3_add(D, m3_tmul(B, OB));
+            }
+            if (g.dense) {
+                if (i == v && j != f && v != f) {                    // H[i][j] += A^T O B (row block owned by this thread)
+                    const M3 c = m3_tmul(A, OB);
+                    for (int r = 0; r < 3; ++r) for (int cc = 0; cc < 3; ++cc) g.Hd[(size_t)(3 * v + r) * N3 + 3 * j + cc] += c.a[3 * r + cc];
+                }
+                if (j == v && i != f && v != f) {                    // H[j][i] += B^T O A
+                    const M3 c = m3_tmul(B, OA);
+                    for (int r = 0; r < 3; ++r) for (int cc = 0; cc < 3; ++cc) g.Hd[(size_t)(3 * v + r) * N3 + 3 * i + cc] += c.a[3 * r + cc];
+                }
+            } else if (in_T && v == min(i, j) && i != j) {
+                if (i == v) { m3_add(U, m3_tmul(A, OB)); m3_add(L, m3_tmul(B, OA)); }
+                else { m3_add(U, m3_tmul(B, OA)); m3_add(L, m3_tmul(A, OB)); }
+            }
+        }
+        if (v == f) {                                                // anchor, pose_graph.py:107-112
+            D = m3_zero(); D.a[0] = D.a[4] = D.a[8] = 1e10;
+            U = m3_zero(); L = m3_zero();
+            b[0] = b[1] = b[2] = 0.0;
+        }
+        if (v + 1 == f) { U = m3_zero(); L = m3_zero(); }
+        if (g.dense) {
+            if (v == f) { for (int r = 0; r < 3; ++r) g.Hd[(size_t)(3 * v + r) * N3 + 3 * v + r] = 1e10; }
+            else for (int r = 0; r < 3; ++r) for (int cc = 0; cc < 3; ++cc) g.Hd[(size_t)(3 * v + r) * N3 + 3 * v + cc] += D.a[3 * r + cc];
+            for (int c = 0; c < 3; ++c) g.dx[3 * v + c] = -b[c];
+        } else {
+            // per node: D[v] = H[v][v], U[v] = H[v][v+1] (zero for the last node), L[v] = H[v][v-1] (zero for node 0)
+            m3_store(g.D + 9 * (size_t)v, D); m3_store(g.U + 9 * (size_t)v, U);
+            if (v + 1 < n) m3_store(g.L + 9 * (size_t)(v + 1), L);
+            if (v == 0) m3_store(g.L, m3_zero());
+            for (int c = 0; c < 3; ++c) g.X[(size_t)(3 * v + c) * ncols] = -b[c];           // column 0: r = -b
+        }
+    }
+    __syncthreads();
+}
+
+// ── closure columns: right-hand sides 1..3k of X, the Jacobian columns W of the non-chain edges ──
+__device__ __forceinline__ void pg_closure_columns(const PgArgs& g) {
+    const int K = g.K, ncols = g.ncols, f = g.fix;
+    for (size_t t = threadIdx.x; t < (size_t)g.N3 * (size_t)K; t += PG_THREADS) g.X[(t / K) * ncols + 1 + (t % K)] = 0.0;
+    __syncthreads();
+    for (int q = threadIdx.x; q < g.k; q += PG_THREADS) {
+        const int eq = g.loop_edge[q], i = g.ei[eq], j = g.ej[eq];
+        double e[3];
+        M3 A, B;
+        pg_linearise(g.nodes + 3 * i, g.nodes + 3 * j, g.z + 3 * eq, e, A, B);     // the Jacobians alone: no Omega here
+        m3_store(g.AB + 18 * (size_t)q, A); m3_store(g.AB + 18 * (size_t)q + 9, B);
+        for (int a = 0; a < 3; ++a)
+            for (int c = 0; c < 3; ++c) {                        // W_e = [A^T ; B^T]: rows of node i / j, column 3q + a
+                if (i != f) g.X[(size_t)(3 * i + c) * ncols + 1 + 3 * q + a] += A.a[3 * a + c];
+                if (j != f) g.X[(size_t)(3 * j + c) * ncols + 1 + 3 * q + a] += B.a[3 * a + c];
+            }
+    }
+    __syncthreads();
+}
+
+// ── closure system: M = I + C W^T Y, g = C W^T T^-1 r ─────────────────────────
+__device__ __forceinline__ void pg_closure_system(const PgArgs& g) {
+    const int K = g.K, ncols = g.ncols, f = g.fix;
+    for (int t = threadIdx.x; t < K * (K + 1); t += PG_THREADS) {
+        const int r = t / (K + 1), c = t % (K + 1);                  // c == K: the right-hand side (column 0 of X)
+        const int q = r / 3, a = r % 3;
+        const int eq = g.loop_edge[q];
+        const int i = g.ei[eq], j = g.ej[eq];
+        const int col = c == K ? 0 : 1 + c;
+        const double* AB = g.AB + 18 * (size_t)q;
+        const double* Om = g.omega + 9 * (size_t)eq;
+        double acc = 0.0;
+        for (int bb = 0; bb < 3; ++bb) {
+            double s = 0.0;
+            for (int cc = 0; cc < 3; ++cc) {
+                if (i != f) s += AB[3 * bb + cc] * g.X[(size_t)(3 * i + cc) * ncols + col];
+                if (j != f) s += AB[9 + 3 * bb + cc] * g.X[(size_t)(3 * j + cc) * ncols + col];
+            }
+            acc += Om[3 * a + bb] * s;
+        }
+        if (c == K) g.g[r] = acc;
+        else g.M[(size_t)r * K + c] = acc + (r == c ? 1.0 : 0.0);
+    }
+    __syncthreads();
+}
+
+// ── dx = Y[:, 0] - Y[:, 1:] y (y in g.g): 16 lanes per row, lanes along the row (coalesced), fixed-tree sum ──
+__device__ __forceinline__ void pg_dx(const PgArgs& g) {
+    const int tid = threadIdx.x, l16 = tid & 15, K = g.K, ncols = g.ncols, N3 = g.N3;
+    for (int t0 = 0; t0 < N3; t0 += PG_THREADS / 16) {                           // uniform trip count
+        const int t = min(t0 + (tid >> 4), N3 - 1);
+        double part = 0.0;
+        for (int c = l16; c < K; c += 16) part += g.X[(size_t)t * ncols + 1 + c] * g.g[c];
+        const double tot = row_sum(part);
+        if (l16 == 0 && t0 + (tid >> 4) < N3) g.dx[t] = g.X[(size_t)t * ncols] - tot;
+    }
+}
+
+// ── apply the update, pose_graph.py:121-129; returns the norm of the step ─────
+__device__ __forceinline__ double pg_apply(const PgArgs& g, double* s_val) {
+    double ss = 0.0;
+    for (int v = threadIdx.x; v < g.n; v += PG_THREADS) {
+        const double d0 = g.dx[3 * v], d1 = g.dx[3 * v + 1], d2 = g.dx[3 * v + 2];
+        g.nodes[3 * v] += d0;
+        g.nodes[3 * v + 1] += d1;
+        g.nodes[3 * v + 2] = pg_wrap(g.nodes[3 * v + 2] + d2);
+        ss += (d0 * d0 + d1 * d1) + d2 * d2;
+    }
+    return sqrt(block_total(ss, s_val));
+}
+
 __global__ __launch_bounds__(PG_THREADS) void pose_graph_kernel(PgArgs g) {
     __shared__ double s_val[PG_THREADS];
     __shared__ int s_idx[PG_THREADS];
-    __shared__ int s_flag;
-    const int tid = threadIdx.x;
-    const int n = g.n, k = g.k, K = 3 * g.k, ncols = 1 + 3 * g.k, N3 = 3 * g.n, f = g.fix;
-    int status = PG_MAXITER, iters = g.n_iter;
+    __shared__ int s_flag;                                        // a block of T turned out exactly singular
+    int status = ICPMI_PG_ST_MAXITER, iters = g.n_iter;
     double step = 0.0;
-    // phase clocks (thread 0, 100 MHz wall clock): assemble, chain LU + W, sweeps, closure system, its solve, dx, update
-    long long t_acc[7] = {0, 0, 0, 0, 0, 0, 0}, t_last = wall_clock64();
-#define PG_MARK(i)                                                                      \
-    do {                                                                                \
-        if (tid == 0) { const long long now = wall_clock64(); t_acc[i] += now - t_last; t_last = now; } \
-    } while (0)
-
+    PgClock clock;
+    const int tid = threadIdx.x, n = g.n, ncols = g.ncols;
     for (int it = 0; it < g.n_iter; ++it) {
-        if (tid == 0) s_flag = 0;
-        if (g.dense)
-            for (size_t t = tid; t < (size_t)N3 * N3; t += PG_THREADS) g.Hd[t] = 0.0;
+        if (threadIdx.x == 0) s_flag = 0;
+        if (g.dense) for (size_t t = threadIdx.x; t < (size_t)g.N3 * g.N3; t += PG_THREADS) g.Hd[t] = 0.0;
         __syncthreads();
-        // ── linearise every edge and gather per node (pose_graph.py:96-105) ──────
-        for (int v = tid; v < n; v += PG_THREADS) {
-            M3 D = m3_zero(), U = m3_zero(), L = m3_zero();
-            double b[3] = {0.0, 0.0, 0.0};
-            for (int t = g.csr_ptr[v]; t < g.csr_ptr[v + 1]; ++t) {
-                const int q = g.csr_edge[t];
-                const int i = g.ei[q], j = g.ej[q];
-                double e[3], tmp[3], Oe[3];
-                M3 A, B;
-                pg_linearise(g.nodes + 3 * i, g.nodes + 3 * j, g.z + 3 * q, e, A, B);
-                const M3 Om = m3_load(g.omega + 9 * (size_t)q);
-                const M3 OA = m3_mul(Om, A), OB = m3_mul(Om, B);
-                m3_vec(Om, e, Oe);
-                const bool in_T = g.dense || g.loop_slot[q] < 0;
-                if (i == v) {
-                    m3_tvec(A, Oe, tmp); b[0] += tmp[0]; b[1] += tmp[1]; b[2] += tmp[2];
-                    if (in_T) m3_add(D, m3_tmul(A, OA));
-                }
-                if (j == v) {
-                    m3_tvec(B, Oe, tmp); b[0] += tmp[0]; b[1] += tmp[1]; b[2] += tmp[2];
-                    if (in_T) m3_add(D, m3_tmul(B, OB));
-                }
-                if (g.dense) {
-                    if (i == v && j != f && v != f) {                    // H[i][j] += A^T O B (row block owned by this thread)
-                        const M3 c = m3_tmul(A, OB);
-                        for (int r = 0; r < 3; ++r) for (int cc = 0; cc < 3; ++cc) g.Hd[(size_t)(3 * v + r) * N3 + 3 * j + cc] += c.a[3 * r + cc];
-                    }
-                    if (j == v && i != f && v != f) {                    // H[j][i] += B^T O A
-                        const M3 c = m3_tmul(B, OA);
-                        for (int r = 0; r < 3; ++r) for (int cc = 0; cc < 3; ++cc) g.Hd[(size_t)(3 * v + r) * N3 + 3 * i + cc] += c.a[3 * r + cc];
-                    }
-                } else if (in_T && v == min(i, j) && i != j) {
-                    if (i == v) { m3_add(U, m3_tmul(A, OB)); m3_add(L, m3_tmul(B, OA)); }
-                    else { m3_add(U, m3_tmul(B, OA)); m3_add(L, m3_tmul(A, OB)); }
-                }
-            }
-            if (v == f) {                                                // anchor, pose_graph.py:107-112
-                D = m3_zero(); D.a[0] = D.a[4] = D.a[8] = 1e10;
-                U = m3_zero(); L = m3_zero();
-                b[0] = b[1] = b[2] = 0.0;
-            }
-            if (v + 1 == f) { U = m3_zero(); L = m3_zero(); }
-            if (g.dense) {
-                if (v == f) { for (int r = 0; r < 3; ++r) g.Hd[(size_t)(3 * v + r) * N3 + 3 * v + r] = 1e10; }
-                else for (int r = 0; r < 3; ++r) for (int cc = 0; cc < 3; ++cc) g.Hd[(size_t)(3 * v + r) * N3 + 3 * v + cc] += D.a[3 * r + cc];
-                for (int c = 0; c < 3; ++c) g.dx[3 * v + c] = -b[c];
-            } else {
-                // per node: D[v] = H[v][v], U[v] = H[v][v+1] (zero for the last node), L[v] = H[v][v-1] (zero for node 0)
-                m3_store(g.D + 9 * (size_t)v, D); m3_store(g.U + 9 * (size_t)v, U);
-                if (v + 1 < n) m3_store(g.L + 9 * (size_t)(v + 1), L);
-                if (v == 0) m3_store(g.L, m3_zero());
-                for (int c = 0; c < 3; ++c) g.X[(size_t)(3 * v + c) * ncols] = -b[c];           // column 0: r = -b
-            }
-        }
-        __syncthreads();
-        PG_MARK(0);
-
         bool singular = false, refused = false;
-        if (g.dense) {
-            singular = !block_lu_solve(g.Hd, N3, g.dx, s_val, s_idx);
-        } else {
-            // ── right-hand sides 1..3k: the Jacobian columns W of the non-chain edges ──
-            for (size_t t = tid; t < (size_t)N3 * (size_t)K; t += PG_THREADS) g.X[(t / K) * ncols + 1 + (t % K)] = 0.0;
-            __syncthreads();
-            for (int q = tid; q < k; q += PG_THREADS) {
-                const int eq = g.loop_edge[q];
-                const int i = g.ei[eq], j = g.ej[eq];
-                double e[3];
-                M3 A, B;
-                pg_linearise(g.nodes + 3 * i, g.nodes + 3 * j, g.z + 3 * eq, e, A, B);
-                m3_store(g.AB + 18 * (size_t)q, A); m3_store(g.AB + 18 * (size_t)q + 9, B);
-                for (int a = 0; a < 3; ++a)
-                    for (int c = 0; c < 3; ++c) {                        // W_e = [A^T ; B^T]: rows of node i / j, column 3q + a
-                        if (i != f) g.X[(size_t)(3 * i + c) * ncols + 1 + 3 * q + a] += A.a[3 * a + c];
-                        if (j != f) g.X[(size_t)(3 * j + c) * ncols + 1 + 3 * q + a] += B.a[3 * a + c];
-                    }
-            }
-            __syncthreads();
-            PG_MARK(1);
-            // ── T^-1 on every column by block cyclic reduction along the chain ───────
+        pg_assemble(g);
+        clock.mark(PG_ASSEMBLE);
+        if (g.dense) singular = !block_lu_solve(g.Hd, g.N3, g.dx, s_val, s_idx);
+        else {
+            pg_closure_columns(g);
+            clock.mark(PG_CLOSURE_COLUMNS);
+            // ── chain solve: T^-1 on every column of X by block cyclic reduction along the chain ──
             // Level with stride s: the nodes that are odd multiples of s are eliminated into their neighbours at
             // distance s (which then couple at distance 2s); log2(n) levels, every level parallel over nodes and
             // columns.  An eliminated node keeps its inverted diagonal block and its two couplings for the way back.
@@ -370,7 +437,8 @@ __global__ __launch_bounds__(PG_THREADS) void pose_graph_kernel(PgArgs g) {
                     for (int c = 0; c < 3; ++c) g.X[(size_t)c * ncols + col] = x[c];
                 }
                 __syncthreads();
-                for (s >>= 1; s >= 1; s >>= 1) {                                         // back: the odd nodes of every level
+                // back-substitute: node 0 above, then the odd nodes of every level from the top stride down; X becomes T^-1 [r W]
+                for (s >>= 1; s >= 1; s >>= 1) {
                     const int n_odd = (n - s + 2 * s - 1) / (2 * s);                     // nodes s, 3s, 5s, ... below n
                     for (int t = tid; t < n_odd * ncols; t += PG_THREADS) {
                         const int i = s * (2 * (t / ncols) + 1), col = t % ncols, a = i - s, b = i + s;
@@ -385,69 +453,28 @@ __global__ __launch_bounds__(PG_THREADS) void pose_graph_kernel(PgArgs g) {
                     }
                     __syncthreads();
                 }
-                PG_MARK(2);
-                if (k > 0) {
-                    // ── (I + C W^T Y) y = C W^T T^-1 r ───────────────────────────────────
-                    for (int t = tid; t < K * (K + 1); t += PG_THREADS) {
-                        const int r = t / (K + 1), c = t % (K + 1);                  // c == K: the right-hand side (column 0 of X)
-                        const int q = r / 3, a = r % 3;
-                        const int eq = g.loop_edge[q];
-                        const int i = g.ei[eq], j = g.ej[eq];
-                        const int col = c == K ? 0 : 1 + c;
-                        const double* AB = g.AB + 18 * (size_t)q;
-                        const double* Om = g.omega + 9 * (size_t)eq;
-                        double acc = 0.0;
-                        for (int bb = 0; bb < 3; ++bb) {
-                            double s = 0.0;
-                            for (int cc = 0; cc < 3; ++cc) {
-                                if (i != f) s += AB[3 * bb + cc] * g.X[(size_t)(3 * i + cc) * ncols + col];
-                                if (j != f) s += AB[9 + 3 * bb + cc] * g.X[(size_t)(3 * j + cc) * ncols + col];
-                            }
-                            acc += Om[3 * a + bb] * s;
-                        }
-                        if (c == K) g.g[r] = acc;
-                        else g.M[(size_t)r * K + c] = acc + (r == c ? 1.0 : 0.0);
-                    }
-                    __syncthreads();
-                    PG_MARK(3);
-                    refused = !block_lu_solve(g.M, K, g.g, s_val, s_idx);
-                    PG_MARK(4);
+                clock.mark(PG_CHAIN_SOLVE);
+                if (g.k > 0) {
+                    pg_closure_system(g);
+                    clock.mark(PG_CLOSURE_SYSTEM);
+                    refused = !block_lu_solve(g.M, g.K, g.g, s_val, s_idx);           // y, in place of g
+                    clock.mark(PG_CLOSURE_SOLVE);
                 }
-                if (!refused) {
-                    // dx = Y[:, 0] - Y[:, 1:] y: one wave per row, lanes along the row (coalesced), fixed-tree sum
-                    const int l16 = tid & 15;
-                    for (int t0 = 0; t0 < N3; t0 += PG_THREADS / 16) {                   // 16 lanes per row, uniform trip count
-                        const int t = min(t0 + (tid >> 4), N3 - 1);
-                        double part = 0.0;
-                        for (int c = l16; c < K; c += 16) part += g.X[(size_t)t * ncols + 1 + c] * g.g[c];
-                        const double tot = row_sum(part);
-                        if (l16 == 0 && t0 + (tid >> 4) < N3) g.dx[t] = g.X[(size_t)t * ncols] - tot;
-                    }
-                }
+                if (!refused) pg_dx(g);
             }
         }
         __syncthreads();
-        PG_MARK(5);
-        if (singular) { status = PG_SINGULAR; iters = it; break; }           // pose_graph.py:117-119: nodes keep their values
-        if (refused) { status = PG_REFUSED; iters = it; break; }             // nodes keep their values; the caller goes on densely
-        // ── apply the update, pose_graph.py:121-129 ──────────────────────────────
-        double ss = 0.0;
-        for (int v = tid; v < n; v += PG_THREADS) {
-            const double d0 = g.dx[3 * v], d1 = g.dx[3 * v + 1], d2 = g.dx[3 * v + 2];
-            g.nodes[3 * v] += d0;
-            g.nodes[3 * v + 1] += d1;
-            g.nodes[3 * v + 2] = pg_wrap(g.nodes[3 * v + 2] + d2);
-            ss += (d0 * d0 + d1 * d1) + d2 * d2;
-        }
-        step = sqrt(block_total(ss, s_val));
-        PG_MARK(6);
-        if (step < g.eps) { status = PG_CONVERGED; iters = it + 1; break; }
+        clock.mark(PG_DX);                                       // on the dense path: the whole elimination
+        if (singular) { status = ICPMI_PG_ST_SINGULAR; iters = it; break; }      // pose_graph.py:117-119: nodes keep their values
+        if (refused) { status = ICPMI_PG_ST_REFUSED; iters = it; break; }        // nodes keep their values; the caller goes on densely
+        step = pg_apply(g, s_val);
+        clock.mark(PG_APPLY);
+        if (step < g.eps) { status = ICPMI_PG_ST_CONVERGED; iters = it + 1; break; }
     }
-    if (tid == 0) {
-        g.info[0] = (double)iters; g.info[1] = (double)status; g.info[2] = step;
-        for (int i = 0; i < 7; ++i) g.info[3 + i] = (double)t_acc[i] * 0.01;      // microseconds per phase, all iterations
+    if (threadIdx.x == 0) {
+        g.info[ICPMI_PGINFO_ITERATIONS] = (double)iters; g.info[ICPMI_PGINFO_STATUS] = (double)status; g.info[ICPMI_PGINFO_STEP] = step;
+        for (int i = 0; i < PG_PHASES; ++i) g.info[ICPMI_PGINFO_PHASE_US + i] = (double)clock.acc[i] * 0.01;      // microseconds, all iterations
     }
-#undef PG_MARK
 }
 
 // total_error, pose_graph.py:189-194: e^T Omega e summed in edge order
@@ -469,12 +496,29 @@ __global__ __launch_bounds__(PG_THREADS) void pose_graph_error_kernel(const doub
     }
 }
 
+// ── the host plan: everything a launch needs, decided without a HIP call ─────
 struct PgPlan {
-    int k = 0, dense = 0, m2 = 0;                  // m2: edges after the weak chain edges got their twins
-    bool null_edge = false;                        // a chain edge without information along some direction: no split
-    double stiff = 0.0;                            // the information a weak chain edge carries inside T (times I)
-    std::vector<int32_t> ij, weak;                 // [m2][2] the edge list with the twins appended; ids of the weak chain edges
-    std::vector<int32_t> csr_ptr, csr_edge, loop_slot, loop_edge;
+    int rc = ICPMI_OK;                             // ICPMI_ERR_ARG: an edge names a node outside the graph
+    bool refused = false;                          // a chain edge without information along some direction: no split, no launch
+    int k = 0, dense = 0, m2 = 0, twins = 0;       // m2: edges after the weak chain edges got their twins
+    std::vector<int32_t> weak;                     // [twins] ids of the weak chain edges
+    double stiff = 0.0;                            // the information a weak chain edge keeps inside T (times I)
+    std::vector<int32_t> ei_ej, csr_ptr, csr_edge, loop_slot, loop_edge;     // ei_ej: [m2] ei, then [m2] ej, the twins appended
+    std::vector<double> z, omega;                  // [m2][3], [m2][9] with the twins' rows: add_twin_rows, only where there are twins
+    // the caller's Omega and z ([m][9], [m][3] on the host) with the twins' rows: the chain edge keeps S I, its twin gets the rest
+    void add_twin_rows(const double* omega_host, const double* z_host, int m) {
+        z.assign(z_host, z_host + 3 * (size_t)m); z.resize(3 * (size_t)m2);
+        omega.assign(omega_host, omega_host + 9 * (size_t)m); omega.resize(9 * (size_t)m2);
+        for (int t = 0; t < twins; ++t) {
+            const size_t q = (size_t)weak[t], q2 = (size_t)m + t;
+            for (int c = 0; c < 3; ++c) z[3 * q2 + c] = z[3 * q + c];
+            for (int c = 0; c < 9; ++c) {
+                const double s = c % 4 == 0 ? stiff : 0.0;
+                omega[9 * q2 + c] = omega[9 * q + c] - s;
+                omega[9 * q + c] = s;
+            }
+        }
+    }
 };
 
 // Classify the edges (host side: the edge list is a few KB of integers the caller holds on the host anyway).
@@ -490,6 +534,8 @@ struct PgPlan {
 // with pivoting.  An edge with an eigenvalue that is zero to rounding (|lambda| <= 64 u max |lambda|: the closed form
 // below is good to a few u of the largest) may leave the whole system exactly singular, which only the dense elimination
 // can tell as the reference's LAPACK call does: such a graph is not split at all.
+// The twins' rows of z and Omega need the caller's z on the host too: add_twin_rows completes a plan that has twins;
+// without them the plan already has every size and index list, which is all the size queries need.
 static void pg_sym_eigenvalues(const double* o, double* e) {                 // symmetric part of a 3 x 3, closed form
     const double a00 = o[0], a11 = o[4], a22 = o[8], a01 = 0.5 * (o[1] + o[3]), a02 = 0.5 * (o[2] + o[6]), a12 = 0.5 * (o[5] + o[7]);
     const double p1 = a01 * a01 + a02 * a02 + a12 * a12;
@@ -506,155 +552,106 @@ static void pg_sym_eigenvalues(const double* o, double* e) {                 // 
     e[1] = 3.0 * q - e[0] - e[2];
 }
 
-static bool pg_plan(const int32_t* ij, const double* omega, int n, int m, bool force_dense, PgPlan& p) {
+static PgPlan pg_plan(const int32_t* ij, const double* omega, int n, int m, bool force_dense) {
+    PgPlan p;
     p.dense = force_dense;
+    const auto chained = [&](int q) { return ij[2 * q] - ij[2 * q + 1] == 1 || ij[2 * q + 1] - ij[2 * q] == 1; };
     std::vector<char> linked(n > 1 ? n - 1 : 0, 0);
     for (int q = 0; q < m; ++q) {
         const int i = ij[2 * q], j = ij[2 * q + 1];
-        if (i < 0 || i >= n || j < 0 || j >= n) return false;
-        if (i - j == 1 || j - i == 1) linked[i < j ? i : j] = 1;
+        if (i < 0 || i >= n || j < 0 || j >= n) { p.rc = ICPMI_ERR_ARG; return p; }
+        if (chained(q)) linked[i < j ? i : j] = 1;
     }
     for (char c : linked) if (!c) p.dense = 1;               // a gap in the chain: T would be singular
-    p.ij.assign(ij, ij + 2 * (size_t)m);
     if (!p.dense && omega) {
-        for (size_t t = 0; t < 9 * (size_t)m; t += 3) {
-            const double row = (fabs(omega[t]) + fabs(omega[t + 1])) + fabs(omega[t + 2]);
-            if (row > p.stiff) p.stiff = row;
-        }
+        for (size_t t = 0; t < 9 * (size_t)m; t += 3) p.stiff = fmax(p.stiff, (fabs(omega[t]) + fabs(omega[t + 1])) + fabs(omega[t + 2]));
         for (int q = 0; q < m; ++q) {
-            const int i = ij[2 * q], j = ij[2 * q + 1];
-            if (i - j != 1 && j - i != 1) continue;
+            if (!chained(q)) continue;
             double e[3];
             pg_sym_eigenvalues(omega + 9 * (size_t)q, e);
             const double lo = fmin(fmin(e[0], e[1]), e[2]);
             const double amin = fmin(fmin(fabs(e[0]), fabs(e[1])), fabs(e[2])), amax = fmax(fmax(fabs(e[0]), fabs(e[1])), fabs(e[2]));
-            if (!(amin > 64 * 0x1p-53 * amax)) p.null_edge = true;           // all zero and NaN included
-            else if (!(lo >= p.stiff / (3.0 * n))) { p.weak.push_back(q); p.ij.push_back(i); p.ij.push_back(j); }
+            if (!(amin > 64 * 0x1p-53 * amax)) p.refused = true;             // all zero and NaN included
+            else if (!(lo >= p.stiff / (3.0 * n))) p.weak.push_back(q);
         }
-        if (p.null_edge) { p.weak.clear(); p.ij.resize(2 * (size_t)m); }
+        if (p.refused) p.weak.clear();
     }
-    const int m2 = p.m2 = m + (int)p.weak.size();
-    p.csr_ptr.assign(n + 1, 0);
-    p.loop_slot.assign(m2, -1);
+    p.twins = (int)p.weak.size();
+    const int m2 = p.m2 = m + p.twins;
+    p.ei_ej.resize(2 * (size_t)m2);
+    int32_t *ei = p.ei_ej.data(), *ej = ei + m2;
+    for (int q = 0; q < m2; ++q) { const int src = q < m ? q : p.weak[q - m]; ei[q] = ij[2 * src]; ej[q] = ij[2 * src + 1]; }
+    p.csr_ptr.assign(n + 1, 0); p.loop_slot.assign(m2, -1);
     for (int q = 0; q < m2; ++q) {
-        const int i = p.ij[2 * q], j = p.ij[2 * q + 1];
-        ++p.csr_ptr[i + 1];
-        if (j != i) ++p.csr_ptr[j + 1];
-        if (!p.dense && (q >= m || (i - j != 1 && j - i != 1))) { p.loop_slot[q] = p.k++; p.loop_edge.push_back(q); }
+        ++p.csr_ptr[ei[q] + 1];
+        if (ej[q] != ei[q]) ++p.csr_ptr[ej[q] + 1];
+        if (!p.dense && (q >= m || !chained(q))) { p.loop_slot[q] = p.k++; p.loop_edge.push_back(q); }
     }
     for (int v = 0; v < n; ++v) p.csr_ptr[v + 1] += p.csr_ptr[v];
     p.csr_edge.resize(p.csr_ptr[n]);
     std::vector<int32_t> fill(p.csr_ptr.begin(), p.csr_ptr.end() - 1);
     for (int q = 0; q < m2; ++q) {
-        const int i = p.ij[2 * q], j = p.ij[2 * q + 1];
-        p.csr_edge[fill[i]++] = q;
-        if (j != i) p.csr_edge[fill[j]++] = q;
+        p.csr_edge[fill[ei[q]]++] = q;
+        if (ej[q] != ei[q]) p.csr_edge[fill[ej[q]]++] = q;
     }
-    return true;
+    return p;
 }
-
-// the workspace: the plan's index arrays, then the arrays of PgArgs (m: edges with the twins, w: twins)
-struct PgWs {
-    Carve c;
-    int n, m, k, dense, w;
-    size_t N3 = 3 * (size_t)n, K = 3 * (size_t)k, blocks = 9 * (size_t)n * 8;
-    int32_t* ei = c.take<int32_t>((size_t)m * 2 * 4);            // ei, ej
-    int32_t* ej = ei ? ei + m : nullptr;
-    int32_t* csr_ptr = c.take<int32_t>(((size_t)n + 1) * 4);
-    int32_t* csr_edge = c.take<int32_t>(((size_t)2 * m + 1) * 4);
-    int32_t* loop_slot = c.take<int32_t>((size_t)(m + 1) * 4);
-    int32_t* loop_edge = c.take<int32_t>((size_t)(k + 1) * 4);
-    double *D = c.take<double>(blocks), *U = c.take<double>(blocks), *L = c.take<double>(blocks);     // D U L Dinv G + b (oversized)
-    double *Dinv = c.take<double>(blocks), *G = c.take<double>(blocks), *b = c.take<double>(blocks);
-    double* X = c.take<double>(N3 * (1 + K) * 8);
-    double* AB = c.take<double>(18 * (size_t)(k + 1) * 8);
-    double *M = c.take<double>((K * K + 1) * 8), *g = c.take<double>((K + 1) * 8), *y = c.take<double>((K + 1) * 8);
-    double* dx = c.take<double>(N3 * 8);
-    double* edge_err = c.take<double>((size_t)(m + 1) * 8);      // per-edge errors (no kernel uses them: kept for the size)
-    double* Hd = dense ? c.take<double>(N3 * N3 * 8) : nullptr;
-    double* omega = w ? c.take<double>((size_t)m * 9 * 8) : nullptr;     // the caller's z and Omega with the twins' rows: only
-    double* z = w ? c.take<double>((size_t)m * 3 * 8) : nullptr;         // where there are twins
-    size_t bytes = c.off + 256;
-};
-
-static size_t pg_workspace_bytes(const int32_t* edges_ij_host, const double* omega_host, int32_t n_nodes, int32_t n_edges,
-                                 bool force_dense) {
+static size_t pg_workspace_bytes(const int32_t* edges_ij_host, const double* omega_host, int32_t n_nodes, int32_t n_edges, bool force_dense) {
     if (n_nodes < 0 || n_edges < 0 || (n_edges > 0 && !edges_ij_host)) return 0;
-    PgPlan p;
-    if (!pg_plan(edges_ij_host, omega_host, n_nodes, n_edges, force_dense, p)) return 0;
-    return PgWs{nullptr, n_nodes, p.m2, p.k, p.dense, (int)p.weak.size()}.bytes;
+    const PgPlan p = pg_plan(edges_ij_host, omega_host, n_nodes, n_edges, force_dense);
+    return p.rc == ICPMI_OK ? PgWs{nullptr, n_nodes, p.m2, p.k, p.dense, p.twins}.bytes : 0;
 }
 
-static int pg_optimize(double* nodes, const int32_t* edges_ij_host, const double* edges_z,
-                       const double* edges_omega, int32_t n_nodes, int32_t n_edges,
-                       int32_t n_iterations, int32_t fix_node, double convergence_eps,
+// an info record without a launch: nothing to do, or the split refused before its first iteration
+static int pg_write_info(double* info, int status, hipStream_t st) {
+    double rec[ICPMI_PGINFO_DOUBLES] = {};
+    rec[ICPMI_PGINFO_STATUS] = (double)status;
+    if (hipMemcpyAsync(info, rec, sizeof(rec), hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
+    return hipStreamSynchronize(st) == hipSuccess ? ICPMI_OK : ICPMI_ERR_HIP;          // `rec` is on this stack frame
+}
+// host <-> device copies of whole vectors (nothing for an empty one); the caller synchronises
+template <class T> static bool pg_upload(T* dst, const std::vector<T>& v, hipStream_t st) {
+    return v.empty() || hipMemcpyAsync(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st) == hipSuccess;
+}
+static bool pg_read_back(std::vector<double>& v, const double* src, size_t count, hipStream_t st) {
+    v.resize(count);
+    return hipMemcpyAsync(v.data(), src, count * 8, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+}
+
+static int pg_optimize(double* nodes, const int32_t* edges_ij_host, const double* edges_z, const double* edges_omega,
+                       int32_t n_nodes, int32_t n_edges, int32_t n_iterations, int32_t fix_node, double convergence_eps,
                        double* info, void* workspace, size_t workspace_bytes, void* stream, bool force_dense) {
     if (!nodes || !info || n_nodes < 0 || n_edges < 0 || n_iterations < 0) return ICPMI_ERR_ARG;
     if (n_edges > 0 && (!edges_ij_host || !edges_z || !edges_omega)) return ICPMI_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (n_nodes < 2 || n_edges == 0 || n_iterations == 0) {                  // pose_graph.py:89-91: nothing to do
-        const double none[10] = {0.0, n_iterations == 0 && n_nodes >= 2 && n_edges > 0 ? (double)PG_MAXITER : (double)PG_NOTHING, 0.0};
-        if (hipMemcpyAsync(info, none, sizeof(none), hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
-        if (hipStreamSynchronize(st) != hipSuccess) return ICPMI_ERR_HIP;    // `none` is on this stack frame
-        return ICPMI_OK;
-    }
+    if (n_nodes < 2 || n_edges == 0) return pg_write_info(info, ICPMI_PG_ST_NOTHING, st);          // pose_graph.py:89-91
+    if (n_iterations == 0) return pg_write_info(info, ICPMI_PG_ST_MAXITER, st);
     if (fix_node < 0 || fix_node >= n_nodes) return ICPMI_ERR_ARG;
     const int n = n_nodes, m = n_edges;
-    std::vector<double> om, zz;                                              // the information matrices, to find the weak chain edges
-    if (!force_dense) {
-        om.resize(9 * (size_t)m);
-        if (hipMemcpyAsync(om.data(), edges_omega, om.size() * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return ICPMI_ERR_HIP;
-        if (hipStreamSynchronize(st) != hipSuccess) return ICPMI_ERR_HIP;
-    }
-    PgPlan p;
-    if (!pg_plan(edges_ij_host, force_dense ? nullptr : om.data(), n, m, force_dense, p)) return ICPMI_ERR_ARG;
-    const int k = p.k, m2 = p.m2, nw = (int)p.weak.size();
-    const PgWs w{workspace, n, m2, k, p.dense, nw};
-    if (!workspace || workspace_bytes < w.bytes || p.null_edge) {
-        if (!workspace || (!nw && !p.null_edge)) return ICPMI_ERR_WORKSPACE;
+    std::vector<double> om, zz;                              // the information matrices, to find the weak chain edges
+    if (!force_dense && !pg_read_back(om, edges_omega, 9 * (size_t)m, st)) return ICPMI_ERR_HIP;
+    PgPlan p = pg_plan(edges_ij_host, force_dense ? nullptr : om.data(), n, m, force_dense);
+    if (p.rc != ICPMI_OK) return p.rc;
+    const PgWs w{workspace, n, p.m2, p.k, p.dense, p.twins};
+    if (!workspace || workspace_bytes < w.bytes || p.refused) {
+        if (!workspace || (!p.twins && !p.refused)) return ICPMI_ERR_WORKSPACE;
         // a chain edge with a null direction, or a workspace sized without the information matrices
         // (icpmi_pose_graph_workspace_bytes) and so without room for the twins: the split is refused before its
         // first iteration and the caller continues on the dense path
-        const double refused[10] = {0.0, (double)PG_REFUSED, 0.0};
-        if (hipMemcpyAsync(info, refused, sizeof(refused), hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
-        if (hipStreamSynchronize(st) != hipSuccess) return ICPMI_ERR_HIP;
-        return ICPMI_OK;
+        return pg_write_info(info, ICPMI_PG_ST_REFUSED, st);
     }
-    PgArgs a{};
-    a.D = w.D; a.U = w.U; a.L = w.L; a.Dinv = w.Dinv; a.G = w.G; a.b = w.b;
-    a.X = w.X; a.AB = w.AB; a.M = w.M; a.g = w.g; a.y = w.y; a.dx = w.dx; a.Hd = w.Hd;
-    a.z = edges_z; a.omega = edges_omega;
-    if (nw) {
-        zz.resize(3 * (size_t)m2);
-        if (hipMemcpyAsync(zz.data(), edges_z, 3 * (size_t)m * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return ICPMI_ERR_HIP;
-        if (hipStreamSynchronize(st) != hipSuccess) return ICPMI_ERR_HIP;
-        om.resize(9 * (size_t)m2);
-        for (int t = 0; t < nw; ++t) {
-            const size_t q = (size_t)p.weak[t], q2 = (size_t)m + t;
-            for (int c = 0; c < 3; ++c) zz[3 * q2 + c] = zz[3 * q + c];
-            for (int c = 0; c < 9; ++c) {
-                const double stiff = c % 4 == 0 ? p.stiff : 0.0;
-                om[9 * q2 + c] = om[9 * q + c] - stiff;
-                om[9 * q + c] = stiff;
-            }
-        }
-        if (hipMemcpyAsync(w.omega, om.data(), om.size() * 8, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
-        if (hipMemcpyAsync(w.z, zz.data(), zz.size() * 8, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
-        a.z = w.z; a.omega = w.omega;
+    PgArgs a{w, nodes, edges_z, edges_omega, n_iterations, fix_node, convergence_eps, info};
+    if (p.twins) {                                           // the twins' rows are made of the caller's z
+        if (!pg_read_back(zz, edges_z, 3 * (size_t)m, st)) return ICPMI_ERR_HIP;
+        p.add_twin_rows(om.data(), zz.data(), m);
+        if (!pg_upload(w.tw_omega, p.omega, st) || !pg_upload(w.tw_z, p.z, st)) return ICPMI_ERR_HIP;
+        a.z = w.tw_z; a.omega = w.tw_omega;
     }
-    std::vector<int32_t> sep(2 * (size_t)m2);
-    for (int q = 0; q < m2; ++q) { sep[q] = p.ij[2 * q]; sep[m2 + q] = p.ij[2 * q + 1]; }
-    // pageable host memory: the runtime stages these copies before returning, so the vectors may go out of scope
-    if (hipMemcpyAsync(w.ei, sep.data(), sep.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
-    if (hipMemcpyAsync(w.csr_ptr, p.csr_ptr.data(), p.csr_ptr.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
-    if (!p.csr_edge.empty() && hipMemcpyAsync(w.csr_edge, p.csr_edge.data(), p.csr_edge.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
-    if (hipMemcpyAsync(w.loop_slot, p.loop_slot.data(), p.loop_slot.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
-    if (k > 0 && hipMemcpyAsync(w.loop_edge, p.loop_edge.data(), (size_t)k * 4, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
-    if (hipStreamSynchronize(st) != hipSuccess) return ICPMI_ERR_HIP;        // the staging vectors die with this call
-    a.nodes = nodes; a.ei = w.ei; a.ej = w.ej;
-    a.csr_ptr = w.csr_ptr; a.csr_edge = w.csr_edge; a.loop_slot = w.loop_slot; a.loop_edge = w.loop_edge;
-    a.n = n; a.m = m2; a.k = k; a.dense = p.dense; a.n_iter = n_iterations; a.fix = fix_node; a.eps = convergence_eps;
-    a.info = info;
+    // pageable host memory: the runtime stages these copies before returning; the plan lives until the synchronise anyway
+    if (!pg_upload(w.ei, p.ei_ej, st) || !pg_upload(w.csr_ptr, p.csr_ptr, st) || !pg_upload(w.csr_edge, p.csr_edge, st) ||
+        !pg_upload(w.loop_slot, p.loop_slot, st) || !pg_upload(w.loop_edge, p.loop_edge, st))
+        return ICPMI_ERR_HIP;
+    if (hipStreamSynchronize(st) != hipSuccess) return ICPMI_ERR_HIP;
     pose_graph_kernel<<<1, PG_THREADS, 0, st>>>(a);
     ICPMI_LAUNCH_CHECK();
     return ICPMI_OK;

@@ -43,6 +43,9 @@ GMW_REC_INTS, GMW_REC_BLOCKS, GMW_REC_SURVIVORS, GMW_REC_SEED, GMW_REC_MAX_BOUND
 GMOM_INTS, GMOM_W, GMOM_A, GMOM_J, GMOM_I, GMOM_AA, GMOM_AJ, GMOM_AI, GMOM_JJ, GMOM_JI, GMOM_II, GMOM_SUPPORT, GMOM_EDGE = (
     12, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11)
 GMOM_WEIGHT_BITS, GMOM_MAX_HALF_STEP = 20, 32767
+# icpmi_pose_graph_optimize: its statuses (PG_ST_*) and the slots of its info record (PGINFO_*: three values, then PHASES clocks)
+PG_ST_NOTHING, PG_ST_CONVERGED, PG_ST_MAXITER, PG_ST_SINGULAR, PG_ST_REFUSED = 0, 1, 2, 3, 4
+PGINFO_DOUBLES, PGINFO_ITERATIONS, PGINFO_STATUS, PGINFO_STEP, PGINFO_PHASE_US, PGINFO_PHASES = 10, 0, 1, 2, 3, 7
 INFO_SLOTS = ("H_tt", "H_tx", "H_ty", "H_xx", "H_xy", "H_yy", "g_t", "g_x", "g_y", "sse", "inliers", "rows", "status")
 
 

@@ -5,7 +5,13 @@ Gauss-Newton optimisation runs on the MI355X in one launch (csrc/posegraph.hip).
 Nodes are poses [x, y, theta]; edges are relative-pose measurements with 3x3
 information matrices.  After ``optimize()`` read ``nodes`` or
 ``get_poses_as_matrices()``.  ``last_info`` holds what the reference only
-prints: iterations run, status and the norm of the last step.  The private
+prints: iterations run, status and the norm of the last step, and in
+``phase_us`` the kernel's device clocks in microseconds, summed over the
+iterations, under ``PHASE_KEYS``.  Two keys are older than what they time:
+``chain_lu`` is the building of the closure columns W and ``chain_sweeps`` the
+whole chain solve (the cyclic reduction of T, which is its factorisation, and
+the back substitution).  On the dense path the four clocks between
+``assemble`` and ``dx`` stay 0 and the whole elimination is in ``dx``.  The private
 per-edge helper ``_error_and_jacobians`` (pose_graph.py:138-182) has no host
 counterpart here: edges are linearised inside the kernels.
 """
@@ -19,8 +25,11 @@ from icpmi import batch as _b
 
 VERBOSE = True      # the reference prints one line per optimisation
 
-NOTHING_TO_DO, CONVERGED, MAX_ITERATIONS, SINGULAR = 0, 1, 2, 3
-_SPLIT_REFUSED = 4   # device status only: the chain part of the split is exactly singular, go on with the dense matrix
+NOTHING_TO_DO, CONVERGED, MAX_ITERATIONS, SINGULAR = _lib.PG_ST_NOTHING, _lib.PG_ST_CONVERGED, _lib.PG_ST_MAXITER, _lib.PG_ST_SINGULAR
+_SPLIT_REFUSED = _lib.PG_ST_REFUSED   # device status only: the chain part of the split is exactly singular, go on with the dense matrix
+_ITERATIONS, _STATUS, _STEP = _lib.PGINFO_ITERATIONS, _lib.PGINFO_STATUS, _lib.PGINFO_STEP
+_PHASES = slice(_lib.PGINFO_PHASE_US, _lib.PGINFO_PHASE_US + _lib.PGINFO_PHASES)
+PHASE_KEYS = ("assemble", "chain_lu", "chain_sweeps", "closure_system", "closure_solve", "dx", "apply")    # in slot order
 
 
 def normalize_angle(a):
@@ -95,7 +104,7 @@ class PoseGraph2D:
         fix = fix_node + n if fix_node < 0 else fix_node
         d_nodes = torch.from_numpy(np.ascontiguousarray(np.array(self.nodes, dtype=np.float64).reshape(n, 3))).to(dev)
         d_z, d_om = torch.from_numpy(z).to(dev), torch.from_numpy(om).to(dev)
-        d_info = torch.zeros(10, dtype=torch.float64, device=dev)
+        d_info = torch.zeros(_lib.PGINFO_DOUBLES, dtype=torch.float64, device=dev)
         ijp = ij.ctypes.data_as(C.c_void_p)
 
         def launch(size_query, entry, iterations):
@@ -109,22 +118,21 @@ class PoseGraph2D:
         info = launch(lambda *a: L.icpmi_pose_graph_weighted_workspace_bytes(a[0], omp, *a[1:]),
                       L.icpmi_pose_graph_optimize, int(n_iterations))
         split_refused_at = None
-        if int(info[1]) == _SPLIT_REFUSED:
+        if int(info[_STATUS]) == _SPLIT_REFUSED:
             # the chain part of the split turned out exactly singular: the remaining iterations take the dense matrix
-            split_refused_at, first = int(info[0]), info
+            split_refused_at, first = int(info[_ITERATIONS]), info
             info = launch(L.icpmi_pose_graph_dense_workspace_bytes, L.icpmi_pose_graph_optimize_dense,
                           int(n_iterations) - split_refused_at)
-            info[0] += first[0]
-            info[3:10] += first[3:10]
-            if int(info[0]) == split_refused_at:
-                info[2] = first[2]                           # singular at once: the last step applied is the split's
+            info[_ITERATIONS] += first[_ITERATIONS]
+            info[_PHASES] += first[_PHASES]
+            if int(info[_ITERATIONS]) == split_refused_at:
+                info[_STEP] = first[_STEP]                         # singular at once: the last step applied is the split's
         out = d_nodes.cpu().numpy()
-        iters, status, step = int(info[0]), int(info[1]), info[2]
+        iters, status, step = int(info[_ITERATIONS]), int(info[_STATUS]), info[_STEP]
         for k in range(n):                                   # in place, like pose_graph.py:122-125
             self.nodes[k][:] = out[k]
         self.last_info = dict(iterations=iters, status=status, step_norm=float(step), split_refused_at=split_refused_at,
-                              phase_us=dict(zip(("assemble", "chain_lu", "chain_sweeps", "closure_system",
-                                                 "closure_solve", "dx", "apply"), info[3:10].tolist())))
+                              phase_us=dict(zip(PHASE_KEYS, info[_PHASES].tolist())))
         if VERBOSE:
             if status == SINGULAR:
                 print(f"  PoseGraph: singular H at iter {iters}, stopping")

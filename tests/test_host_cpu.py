@@ -51,15 +51,36 @@ def test_library_builds_and_exports_header_symbols():
             if isinstance(want, tuple):
                 want = want[1 if on_gpu else 0]
             assert getattr(lib, name)(*args) == want, (name, args)
-    import numpy as np
+    # The pose-graph workspace (PgWs in csrc/posegraph.hip), by hand.  a(x) = x rounded up to 256 bytes; n nodes, m edges
+    # (with the twins), k non-chain edges, w twins:
+    #   a(8m) + a(4(n+1)) + a(4(2m+1)) + a(4(m+1)) + a(4(k+1))       ei/ej, csr_ptr, csr_edge, loop_slot, loop_edge
+    #   + 5 a(72n) + a(24n(1+3k)) + a(144(k+1)) + a(8(9k^2+1)) + a(8(3k+1)) + a(24n)     D U L Dinv G, X, AB, M, g, dx
+    #   + [dense: a(72n^2)] + [w > 0: a(72m) + a(24m)] + 256
+    # n = 50, m = 49, k = 0: 512 + 256 + 512 + 256 + 256 + 19200 + 1280 + 256 + 256 + 256 + 1280 + 256 = 24576
+    # n = 50, m = 52, k = 3: 512 + 256 + 512 + 256 + 256 + 19200 + 12032 + 768 + 768 + 256 + 1280 + 256 = 36352
+    # n = 50, m = 49, k = 0, dense: 24576 + a(180000) = 24576 + 180224 = 204800
+    # n = 5, m = 0 (no chain either: dense, and a(0) = 0 for ei/ej): 9 x 256 + 5 x 512 + a(1800) + 256 = 7168
+    # (Three arrays no kernel used — a(72n) + a(8(3k+1)) + a(8(m+1)), 4608 bytes for the 50-node graphs and 1024 for
+    # n = 5 — were part of the layout before: 29184, 40960, 209408, 8192.)
     chain = [(i, i + 1) for i in range(49)]
-    for edges, n, want in ((chain, 50, 29184),                                              # sparse plan, no loop edge
-                           (chain + [(0, 49), (10, 30), (5, 45)], 50, 40960),               # sparse plan, k = 3
-                           ([e for e in chain if e[0] != 20] + [(0, 49)], 50, 209408),      # a gap in the chain: dense plan
-                           ([(0, 7)], 5, 0), ([], 5, 8192), ([], -1, 0)):
+    closures = [(0, 49), (10, 30), (5, 45)]
+    for edges, n, want in ((chain, 50, 24576),                                              # sparse plan, no loop edge
+                           (chain + closures, 50, 36352),                                   # sparse plan, k = 3
+                           ([e for e in chain if e[0] != 20] + [(0, 49)], 50, 204800),      # a gap in the chain: dense plan
+                           ([(0, 7)], 5, 0), ([], 5, 7168), ([], -1, 0)):
         ij = np.ascontiguousarray(np.array(edges, dtype=np.int32).reshape(-1, 2))
         assert lib.icpmi_pose_graph_workspace_bytes(ij.ctypes.data if len(edges) else None, n, len(edges)) == want, (edges, n)
     assert lib.icpmi_pose_graph_workspace_bytes(None, 5, 3) == 0
+    # With the information matrices (S = 1e4, a chain edge is weak below S / (3n) = 66.7).  One weak chain edge gets a twin
+    # among the closures: m = 53, k = 4, w = 1, the plain size of a graph with one more closure and one more edge row
+    # (512 + 256 + 512 + 256 + 256 + 19200 + 15616 + 768 + 1280 + 256 + 1280 + 256 = 40448) plus the two twin arrays
+    # (a(72 x 53) + a(24 x 53) = 3840 + 1280): 45568.  A chain edge of all zeros is a null edge: no twins, the plain 36352.
+    ij = np.ascontiguousarray(np.array(chain + closures, dtype=np.int32))
+    for weak, want in ((np.diag([1e-8, 1e4, 1e4]), 45568), (np.zeros((3, 3)), 36352), (None, 36352)):
+        om = np.ascontiguousarray(np.tile(1e4 * np.eye(3), (len(ij), 1, 1)))
+        if weak is not None:
+            om[20] = weak
+        assert lib.icpmi_pose_graph_weighted_workspace_bytes(ij.ctypes.data, om.ctypes.data, 50, len(ij)) == want, weak
 
 
 # (arguments, bytes) of the host-only size queries; zero-sized inputs keep their fixed parts; negative ones give 0 where the
@@ -88,18 +109,25 @@ SIZE_TABLE = {
 
 
 def test_record_layouts_are_named_once_in_the_header():
-    """include/icpmi.h names the slots, statuses and capacities of the rotation-search and feature records; icpmi._lib
-    mirrors every one of them (ICPMI_<NAME> -> _lib.<NAME>) and the names prealign / utilities.features exported before are
-    aliases of them."""
+    """include/icpmi.h names the slots, statuses and capacities of the rotation-search and feature records and of the
+    pose graph's info record; icpmi._lib mirrors every one of them (ICPMI_<NAME> -> _lib.<NAME>) and the names prealign /
+    utilities.features / utilities.pose_graph exported before are aliases of them."""
     from icpmi import _lib, prealign
-    from utilities import features
+    from utilities import features, pose_graph
     txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
     defines = {n: int(v) for n, v in re.findall(r"^#define ICPMI_(\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", txt, flags=re.M)}
-    families = ("RSREC_", "RS_WS_", "RSR_", "RSBREC_", "RSB_", "FTREC_", "FT_")
+    families = ("RSREC_", "RS_WS_", "RSR_", "RSBREC_", "RSB_", "FTREC_", "FT_", "PG_", "PGINFO_")
     named = {n for n in defines if n.startswith(families)}
-    assert len(named) == 43     # search: 10 + 4 slots, 4 statuses, 2 offsets, 3 capacities; features: 11 slots, 6 statuses, 3 capacities
+    # search: 10 + 4 slots, 4 statuses, 2 offsets, 3 capacities; features: 11 slots, 6 statuses, 3 capacities;
+    # pose graph: 5 statuses, the record's length, 4 slots, the number of phase clocks
+    assert len(named) == 43 + 11
     for n in named:
         assert getattr(_lib, n) == defines[n], n
+    pg = ("NOTHING", "CONVERGED", "MAXITER", "SINGULAR", "REFUSED")
+    assert [defines["PG_ST_" + n] for n in pg] == list(range(5))
+    assert (pose_graph.NOTHING_TO_DO, pose_graph.CONVERGED, pose_graph.MAX_ITERATIONS, pose_graph.SINGULAR) == (0, 1, 2, 3)
+    assert [defines["PGINFO_" + n] for n in ("ITERATIONS", "STATUS", "STEP", "PHASE_US", "PHASES", "DOUBLES")] == [0, 1, 2, 3, 7, 10]
+    assert len(pose_graph.PHASE_KEYS) == defines["PGINFO_PHASES"] == defines["PGINFO_DOUBLES"] - defines["PGINFO_PHASE_US"]
     for n, v in defines.items():                              # and whatever else the binding mirrors (RES_*, ST_*, ERR_*) agrees
         assert getattr(_lib, n, v) == v, n
     assert _lib.RES_DOUBLES == defines["RES_DOUBLES"] and _lib.ERR_HIP == defines["ERR_HIP"] == -3
