@@ -919,6 +919,61 @@ int icpmi_pose_graph_error(const double* nodes, const int32_t* edges_i, const in
                            const double* edges_z, const double* edges_omega, int32_t n_edges,
                            double* scratch, double* out, void* stream);
 
+/* ── pose graph: marginal covariances ──────────────────────────────────────────
+ * 3 x 3 blocks of H^-1, H exactly the matrix pose_graph.py:93-114 assembles at
+ * the current nodes: every edge's four blocks, the rows and columns of fix_node
+ * zeroed, 1e10 I on its diagonal block.  Block (v, w) is rows 3v..3v+2, columns
+ * 3w..3w+2; nothing is symmetrised, and information matrices that are not
+ * symmetric or not positive definite are accepted as optimize accepts them.  For
+ * symmetric positive definite information this is the covariance of the poses
+ * given the anchor.  No iteration is run; nodes are only read.
+ * Arguments as icpmi_pose_graph_optimize (edges_ij_host on the HOST, nodes /
+ * edges_z / edges_omega on the device), and:
+ * selected_host: n_selected node indices on the HOST (duplicates allowed).
+ * out_diagonal (device, or null): block (v, v) of every node, [n_nodes][9]
+ *   row-major.
+ * out_columns (device, or null): block (v, selected[a]) of every node v,
+ *   [n_selected][n_nodes][9]: every joint marginal of selected nodes.
+ * force_dense != 0: the dense path whatever the graph.
+ * Paths: the split of optimize on the same plan (chain, closures, twins of weak
+ * chain edges) through H^-1 = T^-1 - T^-1 W (I + C W^T T^-1 W)^-1 C W^T T^-1;
+ * its sweeps along the chain are serial in n_nodes, everything else is spread
+ * over the device.  A graph that optimize does not split, or force_dense, takes
+ * the dense matrix eliminated with partial pivoting: O(n_nodes^3) time like
+ * optimize's dense path, and for the diagonal all 3 n_nodes unit columns are
+ * solved, a second 3n x 3n array in the workspace.
+ * info (device, ICPMI_MARG_DOUBLES doubles), slots ICPMI_MARG_*: STATUS, one of
+ * ICPMI_PG_ST_* (CONVERGED: done; SINGULAR: an exactly zero pivot of the dense
+ * elimination, which alone reports it — the outputs are filled with NaN;
+ * REFUSED: a block of the split is exactly singular, or the plan does not split
+ * this graph (a chain edge without information along some direction, or twins
+ * without room because the workspace was sized without the information
+ * matrices) — nothing was written, repeat with force_dense; NOTHING: fewer than
+ * two nodes or no edges, nothing was written); PATH, ICPMI_MARG_PATH_*;
+ * CLOSURES and TWINS of the plan.
+ * Refused on the host before anything is enqueued: null nodes or info, both
+ * outputs null, n_selected < 0, a selected index, fix_node or an edge index
+ * outside the graph (ICPMI_ERR_ARG); a workspace below the size query's value
+ * (ICPMI_ERR_WORKSPACE).
+ * workspace: icpmi_pose_graph_marginals_workspace_bytes (edges_omega_host: the
+ * information matrices on the host, for the twins, or null; 0 for sizes below
+ * zero or an edge outside the graph). */
+#define ICPMI_MARG_DOUBLES 4
+#define ICPMI_MARG_STATUS 0
+#define ICPMI_MARG_PATH 1
+#define ICPMI_MARG_CLOSURES 2
+#define ICPMI_MARG_TWINS 3
+#define ICPMI_MARG_PATH_SPLIT 0
+#define ICPMI_MARG_PATH_DENSE 1
+size_t icpmi_pose_graph_marginals_workspace_bytes(const int32_t* edges_ij_host, const double* edges_omega_host,
+                                                  int32_t n_nodes, int32_t n_edges, int32_t n_selected,
+                                                  int32_t want_diagonal, int32_t force_dense);
+int icpmi_pose_graph_marginals(const double* nodes, const int32_t* edges_ij_host, const double* edges_z,
+                               const double* edges_omega, int32_t n_nodes, int32_t n_edges, int32_t fix_node,
+                               const int32_t* selected_host, int32_t n_selected, double* out_diagonal,
+                               double* out_columns, int32_t force_dense, double* info, void* workspace,
+                               size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,8 @@
 //
 // Every sum has a fixed order (per-node gathers in edge order, fixed reduction
 // trees): results are reproducible run to run.
+//
+// PoseGraph2D.marginals (blocks of H^-1 on the same plan, its own kernels and layout) follows pg_optimize below.
 #include "common.hpp"
 #include <vector>
 
@@ -657,7 +659,445 @@ static int pg_optimize(double* nodes, const int32_t* edges_ij_host, const double
     return ICPMI_OK;
 }
 
+// ═════════════════════════════════════════════════════════════════════════════
+// Marginals: 3 x 3 blocks of H^-1, H the matrix pose_graph.py:93-114 assembles at the current nodes (nothing is
+// iterated, the nodes are only read).  Two outputs, either may be left out:
+//     diagonal  block (v, v) of every node                      [n][9]
+//     columns   block (v, S[a]) of every node, S the selection  [s][n][9]
+// Split path, on the same plan as the optimiser (chain / closures, twins of weak chain edges), H = T + W C W^T:
+//     H^-1 = T^-1 - Y (I + C W^T Y)^-1 C W^T T^-1,      Y = T^-1 W.
+//   T = block LU along the chain: left Schur complements Sl[v] = D[v] - L[v] Sl[v-1]^-1 U[v-1], kept inverted.  The
+//   sweep is SERIAL in n (one thread); so are the two substitutions of a chain solve, which run one column per lane
+//   over the whole grid.  The transposed solve Z = T^-T W reuses the factors (the left Schur complements of T^T are
+//   the transposes of those of T).
+//   columns:  V = T^-1 E_S,  y = M^-1 (C W^T V),  block (v, S[a]) = V - Y y            (M = I + C W^T Y, pivoted LU)
+//   diagonal: G[v] = (T^-1)[v][v] by a second serial sweep, from the last node down, that only adds:
+//             G[n-1] = Sl[n-1]^-1,  G[v] = Sl[v]^-1 + (Sl[v]^-1 U[v]) G[v+1] (L[v+1] Sl[v]^-1);
+//             the correction of node v is the columns' own, with the node's three right-hand sides read off Z:
+//             C W^T T^-1 E_v = C Z_v^T,  y_v = M^-1 (C Z_v^T),  block (v, v) = G[v] - Y_v y_v.
+//             (Two forms that cost the same lose digits the bound does not allow, in NumPy float64 on the test graphs:
+//             inverting D - L Sl^-1 U - U Sr^-1 L cancels where the chain alone is loose, up to 14 times the bound;
+//             Y_v (M^-1 C) Z_v^T pays the full condition of M, up to 26 times.  This one stays below 0.4 of it there and
+//             below 0.71 on the device.)
+// Dense path (gap in the chain, other numbering, forced): the reference's dense matrix, eliminated with partial
+// pivoting in global memory, O(n^3) like the optimiser's dense path; the right-hand sides are the selected unit
+// columns, and ALL 3n of them for the diagonal.  Only this path reports a singular system (outputs: NaN).
+// Plain launches one after another on the caller's stream; a kernel that finds the refusal / singular flag set by an
+// earlier one returns at once.  The pivoted systems (M, or the dense H) are factorised by one workgroup and solved
+// one right-hand side per lane.  Every sum has a fixed order.
+// ═════════════════════════════════════════════════════════════════════════════
+constexpr int MG_THREADS = 256;                    // the grid-wide kernels
+enum MgFlag { MG_REFUSED, MG_SINGULAR, MG_FLAGS };
+
+// The device arrays of a marginals call, listed ONCE (as PgWs: counts over a null base, hands out pointers otherwise).
+// n nodes, m edges with the twins, k closures, w twins, s selected nodes, diag: the diagonal is wanted.
+struct MgWs {
+    Carve c;
+    int n, m, k, dense, w, s, diag;
+    int N3 = 3 * n, K = 3 * k;
+    int ncols = dense ? 0 : K + 3 * s + (diag ? K : 0);          // columns of X: Y = T^-1 W | V = T^-1 E_S | Z = T^-T W
+    int NL = dense ? N3 : K;                                     // order of the pivoted system: H, or M
+    int nrhs = 3 * s + (diag ? N3 : 0);                          // its right-hand sides: 3 per selected node, then (diagonal) 3 per node
+    size_t blocks = dense ? 0 : 9 * (size_t)n * 8;
+    int32_t* ei = c.take<int32_t>((size_t)m * 2 * 4);            // the plan's index arrays, as in PgWs
+    int32_t* ej = ei ? ei + m : nullptr;
+    int32_t* csr_ptr = c.take<int32_t>(((size_t)n + 1) * 4);
+    int32_t* csr_edge = c.take<int32_t>(((size_t)2 * m + 1) * 4);
+    int32_t* loop_slot = c.take<int32_t>((size_t)(m + 1) * 4);
+    int32_t* loop_edge = c.take<int32_t>((size_t)(k + 1) * 4);
+    int32_t* sel = c.take<int32_t>((size_t)(s + 1) * 4);         // [s] the selected nodes
+    int32_t* piv = c.take<int32_t>((size_t)(NL + 1) * 4);        // [NL] pivot rows of the elimination
+    int32_t* flag = c.take<int32_t>(MG_FLAGS * 4);               // MgFlag
+    double *D = c.take<double>(blocks), *U = c.take<double>(blocks), *L = c.take<double>(blocks);   // T, as in PgWs
+    double* Sl = c.take<double>(blocks);                         // [n][9] the left Schur complements, inverted
+    double* Td = c.take<double>(diag ? blocks : 0);              // [n][9] the diagonal blocks of T^-1
+    double* X = c.take<double>((size_t)N3 * ncols * 8);          // [3n][ncols] right-hand sides -> solutions
+    double* AB = c.take<double>(18 * (size_t)(k + 1) * 8);       // [k][18] Jacobians of the closures
+    double* A = c.take<double>(((size_t)NL * NL + 1) * 8);       // [NL][NL] M or H -> its LU factors
+    double* R = c.take<double>(((size_t)NL * nrhs + 1) * 8);     // [NL][nrhs] right-hand sides -> solutions
+    double* tw_omega = w ? c.take<double>((size_t)m * 9 * 8) : nullptr;
+    double* tw_z = w ? c.take<double>((size_t)m * 3 * 8) : nullptr;
+    size_t bytes = c.off + 256;
+};
+
+struct MgArgs : MgWs {
+    const double* nodes;           // [n][3], read only
+    const double* z;               // [m][3]    the caller's arrays, or tw_z / tw_omega
+    const double* omega;           // [m][9]
+    int fix;
+    double* out_diagonal;          // [n][9] or null
+    double* out_columns;           // [s][n][9] or null
+    double* info;                  // [ICPMI_MARG_DOUBLES]
+};
+
+// assemble: what pg_assemble gathers per node, without the gradient; one thread per node over the grid.  The dense
+// matrix g.A was zeroed before; a node writes its own three rows only.
+__global__ __launch_bounds__(MG_THREADS) void marg_assemble_kernel(MgArgs g) {
+    const int v = blockIdx.x * MG_THREADS + threadIdx.x, n = g.n, N3 = g.N3, f = g.fix;
+    if (v >= n) return;
+    M3 D = m3_zero(), U = m3_zero(), L = m3_zero();
+    for (int t = g.csr_ptr[v]; t < g.csr_ptr[v + 1]; ++t) {
+        const int q = g.csr_edge[t];
+        const int i = g.ei[q], j = g.ej[q];
+        double e[3];
+        M3 A, B;
+        pg_linearise(g.nodes + 3 * i, g.nodes + 3 * j, g.z + 3 * q, e, A, B);
+        const M3 Om = m3_load(g.omega + 9 * (size_t)q);
+        const M3 OA = m3_mul(Om, A), OB = m3_mul(Om, B);
+        const bool in_T = g.dense || g.loop_slot[q] < 0;
+        if (i == v && in_T) m3_add(D, m3_tmul(A, OA));
+        if (j == v && in_T) m3_add(D, m3_tmul(B, OB));
+        if (g.dense) {
+            if (i == v && j != f && v != f) {
+                const M3 c = m3_tmul(A, OB);
+                for (int r = 0; r < 3; ++r) for (int cc = 0; cc < 3; ++cc) g.A[(size_t)(3 * v + r) * N3 + 3 * j + cc] += c.a[3 * r + cc];
+            }
+            if (j == v && i != f && v != f) {
+                const M3 c = m3_tmul(B, OA);
+                for (int r = 0; r < 3; ++r) for (int cc = 0; cc < 3; ++cc) g.A[(size_t)(3 * v + r) * N3 + 3 * i + cc] += c.a[3 * r + cc];
+            }
+        } else if (in_T && v == min(i, j) && i != j) {
+            if (i == v) { m3_add(U, m3_tmul(A, OB)); m3_add(L, m3_tmul(B, OA)); }
+            else { m3_add(U, m3_tmul(B, OA)); m3_add(L, m3_tmul(A, OB)); }
+        }
+    }
+    if (v == f) { D = m3_zero(); D.a[0] = D.a[4] = D.a[8] = 1e10; U = m3_zero(); L = m3_zero(); }     // pose_graph.py:107-112
+    if (v + 1 == f) { U = m3_zero(); L = m3_zero(); }
+    if (g.dense) {
+        if (v == f) { for (int r = 0; r < 3; ++r) g.A[(size_t)(3 * v + r) * N3 + 3 * v + r] = 1e10; }
+        else for (int r = 0; r < 3; ++r) for (int cc = 0; cc < 3; ++cc) g.A[(size_t)(3 * v + r) * N3 + 3 * v + cc] += D.a[3 * r + cc];
+    } else {
+        m3_store(g.D + 9 * (size_t)v, D); m3_store(g.U + 9 * (size_t)v, U);       // U[v] = H[v][v+1], L[v] = H[v][v-1]
+        if (v + 1 < n) m3_store(g.L + 9 * (size_t)(v + 1), L);
+        if (v == 0) m3_store(g.L, m3_zero());
+    }
+}
+
+// the Jacobians of the closures (no Omega here), one thread per closure
+__global__ __launch_bounds__(MG_THREADS) void marg_closure_jacobians_kernel(MgArgs g) {
+    const int q = blockIdx.x * MG_THREADS + threadIdx.x;
+    if (q >= g.k) return;
+    const int eq = g.loop_edge[q], i = g.ei[eq], j = g.ej[eq];
+    double e[3];
+    M3 A, B;
+    pg_linearise(g.nodes + 3 * i, g.nodes + 3 * j, g.z + 3 * eq, e, A, B);
+    m3_store(g.AB + 18 * (size_t)q, A); m3_store(g.AB + 18 * (size_t)q + 9, B);
+}
+
+// Right-hand sides of the chain solves, every element on its own (a gather: nothing is accumulated across threads):
+// columns [0, K) and, for the diagonal, [K + 3s, K + 3s + K): W, whose column 3q + a holds row a of A_q at node i and
+// of B_q at node j (both for a self-edge), nothing at the anchor; columns [K, K + 3s): the unit columns of the selection.
+__global__ __launch_bounds__(MG_THREADS) void marg_chain_rhs_kernel(MgArgs g) {
+    const size_t t = (size_t)blockIdx.x * MG_THREADS + threadIdx.x;
+    if (t >= (size_t)g.N3 * g.ncols) return;
+    const int row = (int)(t / g.ncols), col = (int)(t % g.ncols), v = row / 3, c = row % 3, K = g.K;
+    double x = 0.0;
+    if (col >= K && col < K + 3 * g.s) x = (g.sel[(col - K) / 3] == v && (col - K) % 3 == c) ? 1.0 : 0.0;
+    else if (v != g.fix) {
+        const int w = col < K ? col : col - K - 3 * g.s, q = w / 3, a = w % 3;
+        const int eq = g.loop_edge[q];
+        if (g.ei[eq] == v) x += g.AB[18 * (size_t)q + 3 * a + c];
+        if (g.ej[eq] == v) x += g.AB[18 * (size_t)q + 9 + 3 * a + c];
+    }
+    g.X[t] = x;
+}
+
+// The factorisation of T, serial along the chain (one thread): the left Schur complements from node 0 up, kept
+// inverted; an exactly singular one refuses the split.  Then, for the diagonal, the blocks (T^-1)[v][v] from the last
+// node down.
+__global__ void marg_chain_factor_kernel(MgArgs g) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int n = g.n;
+    M3 S = m3_load(g.D), inv;
+    for (int v = 0; v < n; ++v) {
+        if (!m3_inv(S, inv)) { g.flag[MG_REFUSED] = 1; return; }
+        m3_store(g.Sl + 9 * (size_t)v, inv);
+        if (v + 1 < n) {
+            S = m3_load(g.D + 9 * (size_t)(v + 1));
+            m3_sub(S, m3_mul(m3_mul(m3_load(g.L + 9 * (size_t)(v + 1)), inv), m3_load(g.U + 9 * (size_t)v)));
+        }
+    }
+    if (!g.diag) return;
+    M3 G = inv;                                                  // Sl[n-1]^-1
+    m3_store(g.Td + 9 * (size_t)(n - 1), G);
+    for (int v = n - 2; v >= 0; --v) {
+        const M3 Si = m3_load(g.Sl + 9 * (size_t)v);
+        const M3 left = m3_mul(Si, m3_load(g.U + 9 * (size_t)v)), right = m3_mul(m3_load(g.L + 9 * (size_t)(v + 1)), Si);
+        G = m3_mul(m3_mul(left, G), right);
+        m3_add(G, Si);
+        m3_store(g.Td + 9 * (size_t)v, G);
+    }
+}
+
+// T^-1 (columns below K + 3s) or T^-T (the others) on the columns of X: one column per lane, serial along the chain.
+__global__ __launch_bounds__(ICPMI_WAVE) void marg_chain_solve_kernel(MgArgs g) {
+    const int col = blockIdx.x * ICPMI_WAVE + threadIdx.x, n = g.n, ncols = g.ncols;
+    if (col >= ncols || g.flag[MG_REFUSED]) return;
+    const bool tr = col >= g.K + 3 * g.s;
+    double y[3] = {0.0, 0.0, 0.0}, t1[3], t2[3];
+    for (int v = 0; v < n; ++v) {                                // forward: y[v] = r[v] - L[v] Sl[v-1]^-1 y[v-1]
+        double r[3];
+        for (int c = 0; c < 3; ++c) r[c] = g.X[(size_t)(3 * v + c) * ncols + col];
+        if (v > 0) {
+            if (tr) { m3_tvec(m3_load(g.Sl + 9 * (size_t)(v - 1)), y, t1); m3_tvec(m3_load(g.U + 9 * (size_t)(v - 1)), t1, t2); }
+            else { m3_vec(m3_load(g.Sl + 9 * (size_t)(v - 1)), y, t1); m3_vec(m3_load(g.L + 9 * (size_t)v), t1, t2); }
+            for (int c = 0; c < 3; ++c) r[c] -= t2[c];
+        }
+        for (int c = 0; c < 3; ++c) { y[c] = r[c]; g.X[(size_t)(3 * v + c) * ncols + col] = r[c]; }
+    }
+    double x[3] = {0.0, 0.0, 0.0};
+    for (int v = n - 1; v >= 0; --v) {                           // back: x[v] = Sl[v]^-1 (y[v] - U[v] x[v+1])
+        double r[3];
+        for (int c = 0; c < 3; ++c) r[c] = g.X[(size_t)(3 * v + c) * ncols + col];
+        if (v + 1 < n) {
+            if (tr) m3_tvec(m3_load(g.L + 9 * (size_t)(v + 1)), x, t1);
+            else m3_vec(m3_load(g.U + 9 * (size_t)v), x, t1);
+            for (int c = 0; c < 3; ++c) r[c] -= t1[c];
+        }
+        if (tr) m3_tvec(m3_load(g.Sl + 9 * (size_t)v), r, x);
+        else m3_vec(m3_load(g.Sl + 9 * (size_t)v), r, x);
+        for (int c = 0; c < 3; ++c) g.X[(size_t)(3 * v + c) * ncols + col] = x[c];
+    }
+}
+
+// The closure system, one element per thread: M = I + C W^T Y into A, then the right-hand sides into R: C W^T V (the
+// selection, three per selected node) and C Z_v^T (the diagonal, three per node).  The gathers are pg_closure_system's.
+__global__ __launch_bounds__(MG_THREADS) void marg_closure_system_kernel(MgArgs g) {
+    const int K = g.K, s3 = 3 * g.s, width = K + g.nrhs, f = g.fix;
+    const size_t t = (size_t)blockIdx.x * MG_THREADS + threadIdx.x;
+    if (t >= (size_t)K * width || g.flag[MG_REFUSED]) return;
+    const int r = (int)(t / width), c = (int)(t % width), q = r / 3, a = r % 3;
+    const int eq = g.loop_edge[q];
+    const double* Om = g.omega + 9 * (size_t)eq;
+    if (c >= K + s3) {                                           // row r of C Z_v^T, column c - K - s3 = 3v + component
+        const double* Zr = g.X + (size_t)(c - K - s3) * g.ncols + K + s3 + 3 * q;
+        g.R[(size_t)r * g.nrhs + (c - K)] = (Om[3 * a] * Zr[0] + Om[3 * a + 1] * Zr[1]) + Om[3 * a + 2] * Zr[2];
+        return;
+    }
+    const int i = g.ei[eq], j = g.ej[eq];                       // column c of X: Y below K, V from there
+    const double* AB = g.AB + 18 * (size_t)q;
+    double acc = 0.0;
+    for (int bb = 0; bb < 3; ++bb) {
+        double sum = 0.0;
+        for (int cc = 0; cc < 3; ++cc) {
+            if (i != f) sum += AB[3 * bb + cc] * g.X[(size_t)(3 * i + cc) * g.ncols + c];
+            if (j != f) sum += AB[9 + 3 * bb + cc] * g.X[(size_t)(3 * j + cc) * g.ncols + c];
+        }
+        acc += Om[3 * a + bb] * sum;
+    }
+    if (c < K) g.A[(size_t)r * K + c] = acc + (r == c ? 1.0 : 0.0);
+    else g.R[(size_t)r * g.nrhs + (c - K)] = acc;
+}
+
+// unit right-hand sides of the dense system: 3 per selected node, then (diagonal) the whole identity
+__global__ __launch_bounds__(MG_THREADS) void marg_dense_rhs_kernel(MgArgs g) {
+    const size_t t = (size_t)blockIdx.x * MG_THREADS + threadIdx.x;
+    if (t >= (size_t)g.N3 * g.nrhs) return;
+    const int row = (int)(t / g.nrhs), c = (int)(t % g.nrhs), s3 = 3 * g.s;
+    const int target = c < s3 ? 3 * g.sel[c / 3] + c % 3 : c - s3;
+    g.R[t] = row == target ? 1.0 : 0.0;
+}
+
+// P A = L U in place (a: N x N row-major in global memory) with partial pivoting, one workgroup: the multipliers stay
+// below the diagonal, whole rows are exchanged, piv[p] is the row exchanged with row p.  An exactly zero pivot column
+// raises flag[on_zero] (refused for the closure system, LAPACK's singular matrix for the dense one) and ends it.
+__global__ __launch_bounds__(PG_THREADS) void marg_lu_factor_kernel(double* a, int N, int32_t* piv, int32_t* flag, int on_zero) {
+    __shared__ double s_val;
+    __shared__ int s_idx;
+    if (flag[MG_REFUSED]) return;
+    const int tid = threadIdx.x;
+    const int tx = tid & 31, ty = tid >> 5;                       // update tile: 32 columns x (PG_THREADS / 32) rows
+    for (int p = 0; p < N; ++p) {
+        if (wave_id() == 0) {                                     // pivot search as in block_lu_solve: the lowest row among equal |a|
+            double best = -1.0; int bi = 0x7fffffff;
+            for (int r = p + lane_id(); r < N; r += ICPMI_WAVE) {
+                const double v = fabs(a[(size_t)r * N + p]);
+                if (v > best) { best = v; bi = r; }
+            }
+            wave_first_best(best, bi, [](double x, double y) { return x > y; });
+            if (lane_id() == 0) { s_val = best; s_idx = bi; }
+        }
+        __syncthreads();
+        const double pv = s_val;
+        const int pr = s_idx;
+        if (!(pv > 0.0)) { if (tid == 0) flag[on_zero] = 1; return; }        // uniform
+        if (tid == 0) piv[p] = pr;
+        if (pr != p)
+            for (int c = tid; c < N; c += PG_THREADS) {
+                const double t = a[(size_t)p * N + c];
+                a[(size_t)p * N + c] = a[(size_t)pr * N + c];
+                a[(size_t)pr * N + c] = t;
+            }
+        __syncthreads();
+        const double pivot = a[(size_t)p * N + p];
+        for (int r = p + 1 + tid; r < N; r += PG_THREADS) a[(size_t)r * N + p] = a[(size_t)r * N + p] / pivot;
+        __syncthreads();
+        for (int r = p + 1 + ty; r < N; r += PG_THREADS / 32) {
+            const double l = a[(size_t)r * N + p];
+            for (int c = p + 1 + tx; c < N; c += 32) a[(size_t)r * N + c] -= l * a[(size_t)p * N + c];
+        }
+        __syncthreads();
+    }
+}
+
+// the factors on the columns of R ([N][nrhs] row-major), one column per lane over the grid: row exchanges, L, U
+__global__ __launch_bounds__(ICPMI_WAVE) void marg_lu_solve_kernel(const double* a, int N, const int32_t* piv, double* R, int nrhs,
+                                                                   const int32_t* flag) {
+    const int col = blockIdx.x * ICPMI_WAVE + threadIdx.x;
+    if (col >= nrhs || flag[MG_REFUSED] || flag[MG_SINGULAR]) return;
+    for (int p = 0; p < N; ++p) {
+        const int pr = piv[p];
+        if (pr != p) { const double t = R[(size_t)p * nrhs + col]; R[(size_t)p * nrhs + col] = R[(size_t)pr * nrhs + col]; R[(size_t)pr * nrhs + col] = t; }
+    }
+    for (int r = 1; r < N; ++r) {
+        double acc = R[(size_t)r * nrhs + col];
+        for (int q = 0; q < r; ++q) acc -= a[(size_t)r * N + q] * R[(size_t)q * nrhs + col];
+        R[(size_t)r * nrhs + col] = acc;
+    }
+    for (int r = N - 1; r >= 0; --r) {
+        double acc = R[(size_t)r * nrhs + col];
+        for (int q = r + 1; q < N; ++q) acc -= a[(size_t)r * N + q] * R[(size_t)q * nrhs + col];
+        R[(size_t)r * nrhs + col] = acc / a[(size_t)r * N + r];
+    }
+}
+
+// both outputs of the split path, one entry per thread, the K products summed in column order:
+// block (v, S[a]) = V - Y_v y_a, then block (v, v) = G[v] - Y_v y_v
+__global__ __launch_bounds__(MG_THREADS) void marg_split_out_kernel(MgArgs g) {
+    const size_t t = (size_t)blockIdx.x * MG_THREADS + threadIdx.x, nc = g.out_columns ? (size_t)g.s * g.n * 9 : 0;
+    if (t >= nc + (g.out_diagonal ? (size_t)g.n * 9 : 0) || g.flag[MG_REFUSED]) return;
+    const size_t d = t < nc ? t : t - nc;
+    const int e = (int)(d % 9), v = (int)(d / 9 % g.n), K = g.K;
+    const int rhs = t < nc ? 3 * (int)(d / 9 / g.n) + e % 3 : 3 * g.s + 3 * v + e % 3;     // column of R
+    const double* Xr = g.X + (size_t)(3 * v + e / 3) * g.ncols;
+    double acc = 0.0;
+    for (int q = 0; q < K; ++q) acc += Xr[q] * g.R[(size_t)q * g.nrhs + rhs];
+    if (t < nc) g.out_columns[t] = Xr[K + rhs] - acc;
+    else g.out_diagonal[d] = g.Td[d] - acc;
+}
+
+// both outputs of the dense path, out of the solved unit columns; NaN after a singular elimination
+__global__ __launch_bounds__(MG_THREADS) void marg_dense_out_kernel(MgArgs g) {
+    const size_t t = (size_t)blockIdx.x * MG_THREADS + threadIdx.x, nc = g.out_columns ? (size_t)g.s * g.n * 9 : 0;
+    if (t >= nc + (g.out_diagonal ? (size_t)g.n * 9 : 0)) return;
+    const bool singular = g.flag[MG_SINGULAR] != 0;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const int s3 = 3 * g.s;
+    if (t < nc) {
+        const int e = (int)(t % 9), v = (int)(t / 9 % g.n), a = (int)(t / 9 / g.n);
+        g.out_columns[t] = singular ? nan : g.R[(size_t)(3 * v + e / 3) * g.nrhs + 3 * a + e % 3];
+    } else {
+        const size_t d = t - nc;
+        const int e = (int)(d % 9), v = (int)(d / 9);
+        g.out_diagonal[d] = singular ? nan : g.R[(size_t)(3 * v + e / 3) * g.nrhs + s3 + 3 * v + e % 3];
+    }
+}
+
+__global__ void marg_info_kernel(MgArgs g) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    g.info[ICPMI_MARG_STATUS] = (double)(g.flag[MG_SINGULAR] ? ICPMI_PG_ST_SINGULAR : g.flag[MG_REFUSED] ? ICPMI_PG_ST_REFUSED : ICPMI_PG_ST_CONVERGED);
+    g.info[ICPMI_MARG_PATH] = (double)(g.dense ? ICPMI_MARG_PATH_DENSE : ICPMI_MARG_PATH_SPLIT);
+    g.info[ICPMI_MARG_CLOSURES] = (double)g.k;
+    g.info[ICPMI_MARG_TWINS] = (double)g.w;
+}
+
+static int mg_write_info(double* info, int status, int dense, hipStream_t st) {
+    double rec[ICPMI_MARG_DOUBLES] = {};
+    rec[ICPMI_MARG_STATUS] = (double)status;
+    rec[ICPMI_MARG_PATH] = (double)(dense ? ICPMI_MARG_PATH_DENSE : ICPMI_MARG_PATH_SPLIT);
+    if (hipMemcpyAsync(info, rec, sizeof(rec), hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
+    return hipStreamSynchronize(st) == hipSuccess ? ICPMI_OK : ICPMI_ERR_HIP;
+}
+
+static size_t mg_workspace_bytes(const int32_t* edges_ij_host, const double* omega_host, int32_t n_nodes, int32_t n_edges,
+                                 int32_t n_selected, bool diag, bool force_dense) {
+    if (n_nodes < 0 || n_edges < 0 || n_selected < 0 || (n_edges > 0 && !edges_ij_host)) return 0;
+    if ((size_t)n_nodes > 0x7fffffffu / 9 || (size_t)n_selected > 0x7fffffffu / 9) return 0;      // int indices of the kernels
+    const PgPlan p = pg_plan(edges_ij_host, omega_host, n_nodes, n_edges, force_dense);
+    return p.rc == ICPMI_OK ? MgWs{nullptr, n_nodes, p.m2, p.k, p.dense, p.twins, n_selected, diag}.bytes : 0;
+}
+
+static inline unsigned mg_grid(size_t items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
+
+static int mg_marginals(const double* nodes, const int32_t* edges_ij_host, const double* edges_z, const double* edges_omega,
+                        int32_t n_nodes, int32_t n_edges, int32_t fix_node, const int32_t* selected_host, int32_t n_selected,
+                        double* out_diagonal, double* out_columns, bool force_dense, double* info, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    if (!nodes || !info || (!out_diagonal && !out_columns) || n_nodes < 0 || n_edges < 0 || n_selected < 0) return ICPMI_ERR_ARG;
+    if (n_edges > 0 && (!edges_ij_host || !edges_z || !edges_omega)) return ICPMI_ERR_ARG;
+    if (n_selected > 0 && !selected_host) return ICPMI_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_nodes < 2 || n_edges == 0) return mg_write_info(info, ICPMI_PG_ST_NOTHING, force_dense, st);      // as optimize
+    if (fix_node < 0 || fix_node >= n_nodes) return ICPMI_ERR_ARG;
+    for (int a = 0; a < n_selected; ++a) if (selected_host[a] < 0 || selected_host[a] >= n_nodes) return ICPMI_ERR_ARG;
+    const int n = n_nodes, m = n_edges, s = out_columns ? n_selected : 0, diag = out_diagonal != nullptr;
+    // everything the host can refuse comes before the first HIP call: the edge indices, and a workspace below what
+    // the graph needs even without twins
+    const size_t least = mg_workspace_bytes(edges_ij_host, nullptr, n, m, s, diag, force_dense);
+    if (least == 0) return ICPMI_ERR_ARG;
+    if (!workspace || workspace_bytes < least) return ICPMI_ERR_WORKSPACE;
+    std::vector<double> om, zz;
+    if (!force_dense && !pg_read_back(om, edges_omega, 9 * (size_t)m, st)) return ICPMI_ERR_HIP;
+    PgPlan p = pg_plan(edges_ij_host, force_dense ? nullptr : om.data(), n, m, force_dense);
+    if (p.rc != ICPMI_OK) return p.rc;
+    const MgWs w{workspace, n, p.m2, p.k, p.dense, p.twins, s, diag};
+    // a chain edge with a null direction, or a workspace sized without the information matrices: the caller repeats densely
+    if (p.refused || workspace_bytes < w.bytes) return mg_write_info(info, ICPMI_PG_ST_REFUSED, 0, st);
+    MgArgs a{w, nodes, edges_z, edges_omega, fix_node, out_diagonal, out_columns, info};
+    if (p.twins) {
+        if (!pg_read_back(zz, edges_z, 3 * (size_t)m, st)) return ICPMI_ERR_HIP;
+        p.add_twin_rows(om.data(), zz.data(), m);
+        if (!pg_upload(w.tw_omega, p.omega, st) || !pg_upload(w.tw_z, p.z, st)) return ICPMI_ERR_HIP;
+        a.z = w.tw_z; a.omega = w.tw_omega;
+    }
+    const std::vector<int32_t> sel(selected_host, selected_host + s);
+    if (!pg_upload(w.ei, p.ei_ej, st) || !pg_upload(w.csr_ptr, p.csr_ptr, st) || !pg_upload(w.csr_edge, p.csr_edge, st) ||
+        !pg_upload(w.loop_slot, p.loop_slot, st) || !pg_upload(w.loop_edge, p.loop_edge, st) || !pg_upload(w.sel, sel, st))
+        return ICPMI_ERR_HIP;
+    if (hipMemsetAsync(w.flag, 0, MG_FLAGS * 4, st) != hipSuccess) return ICPMI_ERR_HIP;
+    if (w.dense && hipMemsetAsync(w.A, 0, (size_t)w.NL * w.NL * 8, st) != hipSuccess) return ICPMI_ERR_HIP;
+    if (hipStreamSynchronize(st) != hipSuccess) return ICPMI_ERR_HIP;          // the plan's vectors are on this stack frame
+    const size_t outs = (size_t)s * n * 9;
+    marg_assemble_kernel<<<mg_grid(n, MG_THREADS), MG_THREADS, 0, st>>>(a);
+    if (w.dense) {
+        if (w.nrhs > 0) {
+            marg_dense_rhs_kernel<<<mg_grid((size_t)w.N3 * w.nrhs, MG_THREADS), MG_THREADS, 0, st>>>(a);
+            marg_lu_factor_kernel<<<1, PG_THREADS, 0, st>>>(w.A, w.NL, w.piv, w.flag, MG_SINGULAR);
+            marg_lu_solve_kernel<<<mg_grid(w.nrhs, ICPMI_WAVE), ICPMI_WAVE, 0, st>>>(w.A, w.NL, w.piv, w.R, w.nrhs, w.flag);
+            marg_dense_out_kernel<<<mg_grid(outs + (diag ? (size_t)n * 9 : 0), MG_THREADS), MG_THREADS, 0, st>>>(a);
+        }
+    } else {
+        if (w.k > 0) marg_closure_jacobians_kernel<<<mg_grid(w.k, MG_THREADS), MG_THREADS, 0, st>>>(a);
+        if (w.ncols > 0) marg_chain_rhs_kernel<<<mg_grid((size_t)w.N3 * w.ncols, MG_THREADS), MG_THREADS, 0, st>>>(a);
+        marg_chain_factor_kernel<<<1, ICPMI_WAVE, 0, st>>>(a);
+        if (w.ncols > 0) marg_chain_solve_kernel<<<mg_grid(w.ncols, ICPMI_WAVE), ICPMI_WAVE, 0, st>>>(a);
+        if (w.k > 0) {
+            marg_closure_system_kernel<<<mg_grid((size_t)w.K * (w.K + w.nrhs), MG_THREADS), MG_THREADS, 0, st>>>(a);
+            marg_lu_factor_kernel<<<1, PG_THREADS, 0, st>>>(w.A, w.NL, w.piv, w.flag, MG_REFUSED);
+            if (w.nrhs > 0) marg_lu_solve_kernel<<<mg_grid(w.nrhs, ICPMI_WAVE), ICPMI_WAVE, 0, st>>>(w.A, w.NL, w.piv, w.R, w.nrhs, w.flag);
+        }
+        marg_split_out_kernel<<<mg_grid(outs + (diag ? (size_t)n * 9 : 0), MG_THREADS), MG_THREADS, 0, st>>>(a);
+    }
+    marg_info_kernel<<<1, ICPMI_WAVE, 0, st>>>(a);
+    ICPMI_LAUNCH_CHECK();
+    return ICPMI_OK;
+}
+
 }  // namespace icpmi
+
+extern "C" size_t icpmi_pose_graph_marginals_workspace_bytes(const int32_t* edges_ij_host, const double* edges_omega_host,
+                                                             int32_t n_nodes, int32_t n_edges, int32_t n_selected,
+                                                             int32_t want_diagonal, int32_t force_dense) {
+    return icpmi::mg_workspace_bytes(edges_ij_host, edges_omega_host, n_nodes, n_edges, n_selected, want_diagonal != 0, force_dense != 0);
+}
+extern "C" int icpmi_pose_graph_marginals(const double* nodes, const int32_t* edges_ij_host, const double* edges_z,
+                                          const double* edges_omega, int32_t n_nodes, int32_t n_edges, int32_t fix_node,
+                                          const int32_t* selected_host, int32_t n_selected, double* out_diagonal,
+                                          double* out_columns, int32_t force_dense, double* info, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+    return icpmi::mg_marginals(nodes, edges_ij_host, edges_z, edges_omega, n_nodes, n_edges, fix_node, selected_host, n_selected,
+                               out_diagonal, out_columns, force_dense != 0, info, workspace, workspace_bytes, stream);
+}
 
 extern "C" size_t icpmi_pose_graph_workspace_bytes(const int32_t* edges_ij_host, int32_t n_nodes, int32_t n_edges) {
     return icpmi::pg_workspace_bytes(edges_ij_host, nullptr, n_nodes, n_edges, false);

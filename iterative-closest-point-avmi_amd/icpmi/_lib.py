@@ -46,6 +46,9 @@ GMOM_WEIGHT_BITS, GMOM_MAX_HALF_STEP = 20, 32767
 # icpmi_pose_graph_optimize: its statuses (PG_ST_*) and the slots of its info record (PGINFO_*: three values, then PHASES clocks)
 PG_ST_NOTHING, PG_ST_CONVERGED, PG_ST_MAXITER, PG_ST_SINGULAR, PG_ST_REFUSED = 0, 1, 2, 3, 4
 PGINFO_DOUBLES, PGINFO_ITERATIONS, PGINFO_STATUS, PGINFO_STEP, PGINFO_PHASE_US, PGINFO_PHASES = 10, 0, 1, 2, 3, 7
+# icpmi_pose_graph_marginals: the slots of its info record (its statuses are PG_ST_*) and the two paths
+MARG_DOUBLES, MARG_STATUS, MARG_PATH, MARG_CLOSURES, MARG_TWINS = 4, 0, 1, 2, 3
+MARG_PATH_SPLIT, MARG_PATH_DENSE = 0, 1
 INFO_SLOTS = ("H_tt", "H_tx", "H_ty", "H_xx", "H_xy", "H_yy", "g_t", "g_x", "g_y", "sse", "inliers", "rows", "status")
 
 
@@ -190,6 +193,10 @@ _SIGS = {
                                                   C.c_void_p]),
     "icpmi_pose_graph_error": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "icpmi_pose_graph_marginals_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_void_p] + [C.c_int32] * 5),
+    "icpmi_pose_graph_marginals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                             C.c_size_t, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -54,6 +54,54 @@ def relative_transform_vec(T_i, T_j):
     return pose_matrix_to_vec(np.linalg.inv(T_i) @ T_j)
 
 
+class Marginals:
+    """What ``PoseGraph2D.marginals`` returns: blocks of H^-1 (no counterpart in the reference).
+    ``diagonal``: (n, 3, 3) block (v, v) of every node, or None; ``nodes``: the selected nodes, negative indices resolved;
+    ``columns``: (s, n, 3, 3), ``columns[a, v]`` is block (v, nodes[a]), or None; ``status``; ``path``: "split" or "dense"."""
+
+    def __init__(self, poses, fix_node, nodes, diagonal, columns, status, path):
+        self.poses, self.fix_node, self.nodes = poses, fix_node, list(nodes)
+        self.diagonal, self.columns, self.status, self.path = diagonal, columns, status, path
+
+    def _node(self, v):
+        n = len(self.poses)
+        v = int(v)
+        v = v + n if v < 0 else v
+        if not 0 <= v < n:
+            raise IndexError("list index out of range")
+        return v
+
+    def block(self, v, w):
+        """Block (v, w) of H^-1: needs ``w`` among ``nodes``, or ``v == w`` and the diagonal."""
+        v, w = self._node(v), self._node(w)
+        if self.columns is not None and w in self.nodes:
+            return self.columns[self.nodes.index(w), v]
+        if v == w and self.diagonal is not None:
+            return self.diagonal[v]
+        raise KeyError(f"block ({v}, {w}) was not computed: pass nodes=[..., {w}] to marginals()")
+
+    def joint(self, i, j):
+        """The 6 x 6 joint marginal [[S_ii, S_ij], [S_ji, S_jj]] of two selected nodes."""
+        i, j = self._node(i), self._node(j)
+        if self.columns is None or i not in self.nodes or j not in self.nodes:
+            raise KeyError(f"joint({i}, {j}) needs both nodes among marginals(nodes=...)")
+        return np.block([[self.block(i, i), self.block(i, j)], [self.block(j, i), self.block(j, j)]])
+
+    def relative_jacobians(self, i, j):
+        """A = d z_ij / d x_i and B = d z_ij / d x_j at the poses the marginals were taken at (pose_graph.py:165-178)."""
+        xi, xj = self.poses[self._node(i)], self.poses[self._node(j)]
+        c, s = np.cos(xi[2]), np.sin(xi[2])
+        dx, dy = xj[0] - xi[0], xj[1] - xi[1]
+        A = np.array([[-c, -s, -s * dx + c * dy], [s, -c, -c * dx - s * dy], [0.0, 0.0, -1.0]])
+        B = np.array([[c, s, 0.0], [-s, c, 0.0], [0.0, 0.0, 1.0]])
+        return A, B
+
+    def relative(self, i, j):
+        """Covariance A S_ii A^T + A S_ij B^T + B S_ji A^T + B S_jj B^T of the predicted measurement z_ij (3 x 3)."""
+        J = np.hstack(self.relative_jacobians(i, j))
+        return J @ self.joint(i, j) @ J.T
+
+
 class PoseGraph2D:
     """pose_graph.py:42-194.  ``nodes`` is a list of (3,) arrays and ``edges`` a list of
     ``(i, j, z_ij, omega)`` tuples, as in the reference; both may be edited freely between calls."""
@@ -140,6 +188,59 @@ class PoseGraph2D:
                 print(f"  PoseGraph converged: iter={iters - 1}, ||Δx||={step:.2e}")
             elif status == MAX_ITERATIONS:
                 print(f"  PoseGraph max iterations: iter={n_iterations}, ||Δx||={step:.2e}")
+
+    def marginals(self, nodes=None, fix_node=0, diagonal=True, force_dense=False):
+        """3 x 3 blocks of the inverse of the matrix ``optimize`` factorises (pose_graph.py:93-114) at the current poses:
+        for symmetric positive definite information, the covariance of the poses given the pose at ``fix_node``.
+        ``diagonal``: the block of every node; ``nodes``: a list of node indices (negative ones count from the end,
+        repeats allowed) whose block columns are returned too, which holds every joint marginal among them.  Nothing is
+        iterated and ``self.nodes`` stay as they are.  ``force_dense``: the dense elimination whatever the graph (it is
+        taken anyway where the chain + closures split does not apply or is refused).  Returns a ``Marginals``, or None where ``optimize`` would return
+        at once (fewer than two nodes, no edges); raises ``np.linalg.LinAlgError`` where the reference's solve would."""
+        n = len(self.nodes)
+        if n < 2 or len(self.edges) == 0:
+            return None
+        sel = []
+        for v in ([] if nodes is None else nodes):
+            v = int(v)
+            v = v + n if v < 0 else v
+            if not 0 <= v < n:
+                raise IndexError("list index out of range")
+            sel.append(v)
+        if not sel and not diagonal:
+            raise ValueError("marginals: nothing asked for (diagonal=False and no nodes)")
+        _b.require_gpu()
+        L = _lib.lib()
+        dev = torch.device("cuda", torch.cuda.current_device())
+        ij, z, om = self._edge_arrays()
+        m, s = len(ij), len(sel)
+        fix = fix_node + n if fix_node < 0 else fix_node
+        poses = np.ascontiguousarray(np.array(self.nodes, dtype=np.float64).reshape(n, 3))
+        d_nodes = torch.from_numpy(poses).to(dev)
+        d_z, d_om = torch.from_numpy(z).to(dev), torch.from_numpy(om).to(dev)
+        d_info = torch.zeros(_lib.MARG_DOUBLES, dtype=torch.float64, device=dev)
+        d_diag = torch.empty((n, 3, 3), dtype=torch.float64, device=dev) if diagonal else None
+        d_cols = torch.empty((s, n, 3, 3), dtype=torch.float64, device=dev) if s else None
+        sel_host = np.ascontiguousarray(np.array(sel, dtype=np.int32))
+        ijp, omp, selp = (a.ctypes.data_as(C.c_void_p) for a in (ij, om, sel_host))
+
+        def launch(dense):
+            size = L.icpmi_pose_graph_marginals_workspace_bytes(ijp, omp, n, m, s, int(bool(diagonal)), int(dense))
+            ws = torch.empty(max(int(size), 256), dtype=torch.uint8, device=dev)
+            _lib.check(L.icpmi_pose_graph_marginals(_b._ptr(d_nodes), ijp, _b._ptr(d_z), _b._ptr(d_om), n, m, int(fix), selp, s,
+                                                    _b._ptr(d_diag) if diagonal else None, _b._ptr(d_cols) if s else None,
+                                                    int(dense), _b._ptr(d_info), _b._ptr(ws), ws.numel(), _b._stream()),
+                       "PoseGraph2D.marginals")
+            return d_info.cpu().numpy()
+
+        info = launch(bool(force_dense))
+        if int(info[_lib.MARG_STATUS]) == _SPLIT_REFUSED:          # as optimize: go on with the dense matrix
+            info = launch(True)
+        status = int(info[_lib.MARG_STATUS])
+        if status == SINGULAR:
+            raise np.linalg.LinAlgError("Singular matrix")
+        return Marginals(poses, fix, sel, d_diag.cpu().numpy() if diagonal else None, d_cols.cpu().numpy() if s else None,
+                         status, "dense" if int(info[_lib.MARG_PATH]) == _lib.MARG_PATH_DENSE else "split")
 
     def get_poses_as_matrices(self):
         return [pose_vec_to_matrix(v) for v in self.nodes]
