@@ -974,6 +974,70 @@ int icpmi_pose_graph_marginals(const double* nodes, const int32_t* edges_ij_host
                                double* out_columns, int32_t force_dense, double* info, void* workspace,
                                size_t workspace_bytes, void* stream);
 
+/* ── pose graph: robust edges (no counterpart in the reference) ────────────────
+ * icpmi_pose_graph_optimize (the Gauss-Newton of pose_graph.py:93-134) with a
+ * robust loss on the edges the caller masks.  chi2_q = e_q^T Omega_q e_q,
+ * evaluated as icpmi_pose_graph_error evaluates it, with the caller's Omega;
+ * c = delta^2;
+ *     F(x) = sum over unmasked edges of chi2_q + sum over masked edges of rho(chi2_q)
+ * kernel (ICPMI_ROB_KERNEL_*)   rho(s)                                  w(s) = rho'(s)
+ *   HUBER 0           s if s <= c, else 2 delta sqrt(s) - c   1 if s <= c, else delta / sqrt(s)
+ *   CAUCHY 1          c log1p(s / c)                          c / (c + s)
+ *   GEMAN_MCCLURE 2   c s / (c + s)                           (c / (c + s))^2
+ * Geman-McClure is the closed form of switchable constraints / dynamic
+ * covariance scaling (DCS) with Phi = c.  Every w is continuous in s, lies in
+ * (0, 1] for s >= 0 and is exactly 1.0 where the loss is quadratic (an unmasked
+ * edge, Huber up to c), so such a call computes bit for bit what
+ * icpmi_pose_graph_optimize computes.  log1p and sqrt are taken on the device
+ * in float64; Geman-McClure's rho is evaluated as (c / (c + s)) s.
+ * Evaluation order: iteratively re-weighted least squares inside Gauss-Newton.
+ * Every iteration starts with the phase `weights`: every edge of the caller's
+ * list is linearised at the current poses, chi2_q and w_q = rho'(chi2_q) are
+ * stored (an unmasked edge has w_q = 1); then H = sum w_q J^T Omega J and
+ * b = sum w_q J^T Omega e are assembled and solved as in
+ * icpmi_pose_graph_optimize, w_q Omega_q in the place of Omega_q.  After the
+ * last iteration one more weights pass runs, so that edge_chi2, edge_weight and
+ * COST_AFTER describe the poses that are returned.  COST_BEFORE is the cost at
+ * the input poses.  Both costs are summed in a fixed order.
+ * Path rule: the plan of icpmi_pose_graph_optimize on the caller's unweighted
+ * Omega (weights <= 1 on closures only make the weak-edge rule conservative).
+ * A masked edge between consecutive nodes cannot stay in the chain part T,
+ * whose stiffness its weight would move under the plan: a graph with one takes
+ * the dense path, as with dense != 0.  ICPMI_PG_ST_REFUSED and the dense
+ * continuation are those of icpmi_pose_graph_optimize: repeat the call with
+ * dense != 0 for the remaining iterations.
+ * edges_mask_host: uint8 [n_edges] on the HOST, non-zero = robust.
+ * edge_chi2, edge_weight: device, n_edges doubles each, the caller's edge order.
+ * info (device, ICPMI_ROB_DOUBLES doubles): the ICPMI_PGINFO_* record in its
+ * slots, then COST_BEFORE, COST_AFTER and WEIGHTS_US (the device clock of the
+ * weights phase in microseconds, all passes).
+ * n_iterations == 0 is evaluation only: chi2, weights and both costs (equal)
+ * at the given poses, status MAXITER, nothing moved.
+ * Refused on the host before anything is enqueued (ICPMI_ERR_ARG): an unknown
+ * kernel; delta not > 0, or NaN; a null mask with n_edges > 0; a null output;
+ * null nodes or info, negative sizes, null edge arrays with n_edges > 0,
+ * fix_node or an edge index outside the graph; and (ICPMI_ERR_WORKSPACE) a
+ * workspace below the size query's value.
+ * workspace: icpmi_pose_graph_robust_workspace_bytes (edges_omega_host: the
+ * information matrices on the host, for the twins, or null; 0 for sizes below
+ * zero, a missing list or an edge outside the graph). */
+#define ICPMI_ROB_KERNEL_HUBER 0
+#define ICPMI_ROB_KERNEL_CAUCHY 1
+#define ICPMI_ROB_KERNEL_GEMAN_MCCLURE 2
+#define ICPMI_ROB_DOUBLES 13
+#define ICPMI_ROB_COST_BEFORE 10
+#define ICPMI_ROB_COST_AFTER 11
+#define ICPMI_ROB_WEIGHTS_US 12
+size_t icpmi_pose_graph_robust_workspace_bytes(const int32_t* edges_ij_host, const double* edges_omega_host,
+                                               const uint8_t* edges_mask_host, int32_t n_nodes, int32_t n_edges,
+                                               int32_t dense);
+int icpmi_pose_graph_optimize_robust(double* nodes, const int32_t* edges_ij_host, const double* edges_z,
+                                     const double* edges_omega, const uint8_t* edges_mask_host, int32_t n_nodes,
+                                     int32_t n_edges, int32_t n_iterations, int32_t fix_node, double convergence_eps,
+                                     int32_t kernel, double delta, int32_t dense, double* edge_chi2,
+                                     double* edge_weight, double* info, void* workspace, size_t workspace_bytes,
+                                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

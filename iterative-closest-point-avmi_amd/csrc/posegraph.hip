@@ -17,11 +17,11 @@
 // takes the general path: the same dense matrix as the reference, eliminated
 // with partial pivoting by the workgroup in global memory.
 //
-// An iteration of pose_graph_kernel is its phases in this order (PgPhase names their clocks):
+// An iteration of pose_graph_kernel (pg_gauss_newton, inlined into it) is its phases in this order (PgPhase names their clocks):
 //     assemble; then either the dense solve, or closure columns -> chain solve (reduce, back-substitute) ->
 //     closure system -> closure solve -> dx; then apply.
 // Each is a function called once, but for two that stay as they were because the measured time depends on it: the
-// chain solve is written out in the kernel (as a function, of the same text, it runs 4 % slower at 2 000 and 4 000
+// chain solve is written out in the iteration loop (as a function, of the same text, it runs 4 % slower at 2 000 and 4 000
 // nodes), and the assembly is one node loop that branches on the path where it stores (split into a chain and a
 // dense loop over a shared gather, dx ran 4 to 9 % slower).  With 256 VGPRs in use and over a hundred SGPRs spilled,
 // the allocation of the whole kernel moves with the shape of any of its parts.
@@ -37,6 +37,12 @@
 //
 // Every sum has a fixed order (per-node gathers in edge order, fixed reduction
 // trees): results are reproducible run to run.
+//
+// pose_graph_robust_kernel (PoseGraph2D.optimize_robust: Huber, Cauchy or Geman-McClure on the edges the caller masks)
+// is the same iteration, pg_gauss_newton, under the other edge policy: a `weights` phase in front of every iteration
+// sets w_q = rho'(chi2_q) at the current poses, and the assembly and the closure system load w_q Omega_q where the
+// plain kernel loads Omega_q.  The two kernels share every phase's one copy; the plain one keeps the registers, scratch
+// and LDS it had (DESIGN.md has both resource reports).
 //
 // PoseGraph2D.marginals (blocks of H^-1 on the same plan, its own kernels and layout) follows pg_optimize below.
 #include "common.hpp"
@@ -87,15 +93,56 @@ struct PgArgs : PgWs {
     double* info;                  // [ICPMI_PGINFO_DOUBLES]
 };
 
+// The robust optimiser's device arrays: PgWs, then per edge of the plan (m: with the twins) its weight and its mask.
+struct PgRobWs : PgWs {
+    double* wgt = c.take<double>(((size_t)m + 1) * 8);           // [m] w_q of this iteration: 1.0 for an unmasked edge and for a twin
+    uint8_t* rob = c.take<uint8_t>((size_t)m + 1);               // [m] the caller's mask, 0 for the twins
+    size_t bytes = c.off + 256;                                  // of the whole layout (PgWs::bytes ends before wgt)
+};
+
+struct PgRobArgs : PgRobWs {
+    double* nodes;                 // as PgArgs
+    const double* z;
+    const double* omega;
+    int n_iter, fix;
+    double eps;
+    double* info;                  // [ICPMI_ROB_DOUBLES]
+    const double* omega0;          // [m0][9] the caller's Omega: chi2 is taken of the edge as given, also where it has a twin
+    int m0, kernel;                // the caller's edges; ICPMI_ROB_KERNEL_*
+    double delta;
+    double* edge_chi2;             // [m0] out
+    double* edge_weight;           // [m0] out
+};
+
+// How an edge's Omega enters H and b: weigh(g, q, x) is what a loaded entry x of Omega_q contributes with.
+struct PgPlainEdges {              // Omega_q as given
+    static constexpr bool weighted = false;
+    using Args = PgArgs;
+    static __device__ __forceinline__ double weigh(const PgArgs&, int, double x) { return x; }
+};
+struct PgWeightedEdges {           // w_q Omega_q, w_q from the weights phase: the loaded entries multiplied, nothing else
+    static constexpr bool weighted = true;
+    using Args = PgRobArgs;
+    static __device__ __forceinline__ double weigh(const PgRobArgs& g, int q, double x) { return x * g.wgt[q]; }
+};
+
 // the phases of an iteration, in the order of their clocks in info[ICPMI_PGINFO_PHASE_US + .]
 enum PgPhase { PG_ASSEMBLE, PG_CLOSURE_COLUMNS, PG_CHAIN_SOLVE, PG_CLOSURE_SYSTEM, PG_CLOSURE_SOLVE, PG_DX, PG_APPLY, PG_PHASES };
 static_assert(PG_PHASES == ICPMI_PGINFO_PHASES && ICPMI_PGINFO_PHASE_US + PG_PHASES == ICPMI_PGINFO_DOUBLES, "info record");
+// the robust kernel's record: the same ten slots, then its own three
+static_assert(ICPMI_ROB_COST_BEFORE == ICPMI_PGINFO_DOUBLES && ICPMI_ROB_COST_AFTER == ICPMI_PGINFO_DOUBLES + 1 &&
+              ICPMI_ROB_WEIGHTS_US == ICPMI_PGINFO_DOUBLES + 2 && ICPMI_ROB_DOUBLES == ICPMI_PGINFO_DOUBLES + 3, "robust info record");
 
 // phase clocks: thread 0, the 100 MHz wall clock; mark(p) books the time since the last mark to phase p
 struct PgClock {
     long long acc[PG_PHASES] = {0, 0, 0, 0, 0, 0, 0}, last = wall_clock64();
     __device__ __forceinline__ void mark(PgPhase p) {
         if (threadIdx.x == 0) { const long long now = wall_clock64(); acc[p] += now - last; last = now; }
+    }
+    __device__ __forceinline__ long long lap() {                  // the time since the last mark, for a clock kept elsewhere
+        long long d = 0;
+        if (threadIdx.x == 0) { const long long now = wall_clock64(); d = now - last; last = now; }
+        return d;
     }
 };
 
@@ -231,7 +278,12 @@ __device__ bool block_lu_solve(double* a, int N, double* rhs, double* s_val, int
 
 // ── assemble: linearise every edge and gather per node (pose_graph.py:96-105) ──
 // One loop for both paths (see the head of the file): what a node gathers is the same, where it is stored differs.
-__device__ __forceinline__ void pg_assemble(const PgArgs& g) {
+template <class E> __device__ __forceinline__ M3 pg_edge_omega(const typename E::Args& g, int q) {
+    M3 r = m3_load(g.omega + 9 * (size_t)q);
+    for (int i = 0; i < 9; ++i) r.a[i] = E::weigh(g, q, r.a[i]);
+    return r;
+}
+template <class E> __device__ __forceinline__ void pg_assemble(const typename E::Args& g) {
     const int tid = threadIdx.x, n = g.n, ncols = g.ncols, N3 = g.N3, f = g.fix;
     for (int v = tid; v < n; v += PG_THREADS) {
         M3 D = m3_zero(), U = m3_zero(), L = m3_zero();
@@ -242,7 +294,7 @@ __device__ __forceinline__ void pg_assemble(const PgArgs& g) {
             double e[3], tmp[3], Oe[3];
             M3 A, B;
             pg_linearise(g.nodes + 3 * i, g.nodes + 3 * j, g.z + 3 * q, e, A, B);
-            const M3 Om = m3_load(g.omega + 9 * (size_t)q);
+            const M3 Om = pg_edge_omega<E>(g, q);
             const M3 OA = m3_mul(Om, A), OB = m3_mul(Om, B);
             m3_vec(Om, e, Oe);
             const bool in_T = g.dense || g.loop_slot[q] < 0;
@@ -290,7 +342,7 @@ __device__ __forceinline__ void pg_assemble(const PgArgs& g) {
 }
 
 // ── closure columns: right-hand sides 1..3k of X, the Jacobian columns W of the non-chain edges ──
-__device__ __forceinline__ void pg_closure_columns(const PgArgs& g) {
+template <class G> __device__ __forceinline__ void pg_closure_columns(const G& g) {
     const int K = g.K, ncols = g.ncols, f = g.fix;
     for (size_t t = threadIdx.x; t < (size_t)g.N3 * (size_t)K; t += PG_THREADS) g.X[(t / K) * ncols + 1 + (t % K)] = 0.0;
     __syncthreads();
@@ -310,7 +362,7 @@ __device__ __forceinline__ void pg_closure_columns(const PgArgs& g) {
 }
 
 // ── closure system: M = I + C W^T Y, g = C W^T T^-1 r ─────────────────────────
-__device__ __forceinline__ void pg_closure_system(const PgArgs& g) {
+template <class E> __device__ __forceinline__ void pg_closure_system(const typename E::Args& g) {
     const int K = g.K, ncols = g.ncols, f = g.fix;
     for (int t = threadIdx.x; t < K * (K + 1); t += PG_THREADS) {
         const int r = t / (K + 1), c = t % (K + 1);                  // c == K: the right-hand side (column 0 of X)
@@ -327,7 +379,7 @@ __device__ __forceinline__ void pg_closure_system(const PgArgs& g) {
                 if (i != f) s += AB[3 * bb + cc] * g.X[(size_t)(3 * i + cc) * ncols + col];
                 if (j != f) s += AB[9 + 3 * bb + cc] * g.X[(size_t)(3 * j + cc) * ncols + col];
             }
-            acc += Om[3 * a + bb] * s;
+            acc += E::weigh(g, eq, Om[3 * a + bb]) * s;
         }
         if (c == K) g.g[r] = acc;
         else g.M[(size_t)r * K + c] = acc + (r == c ? 1.0 : 0.0);
@@ -336,7 +388,7 @@ __device__ __forceinline__ void pg_closure_system(const PgArgs& g) {
 }
 
 // ── dx = Y[:, 0] - Y[:, 1:] y (y in g.g): 16 lanes per row, lanes along the row (coalesced), fixed-tree sum ──
-__device__ __forceinline__ void pg_dx(const PgArgs& g) {
+template <class G> __device__ __forceinline__ void pg_dx(const G& g) {
     const int tid = threadIdx.x, l16 = tid & 15, K = g.K, ncols = g.ncols, N3 = g.N3;
     for (int t0 = 0; t0 < N3; t0 += PG_THREADS / 16) {                           // uniform trip count
         const int t = min(t0 + (tid >> 4), N3 - 1);
@@ -348,7 +400,7 @@ __device__ __forceinline__ void pg_dx(const PgArgs& g) {
 }
 
 // ── apply the update, pose_graph.py:121-129; returns the norm of the step ─────
-__device__ __forceinline__ double pg_apply(const PgArgs& g, double* s_val) {
+template <class G> __device__ __forceinline__ double pg_apply(const G& g, double* s_val) {
     double ss = 0.0;
     for (int v = threadIdx.x; v < g.n; v += PG_THREADS) {
         const double d0 = g.dx[3 * v], d1 = g.dx[3 * v + 1], d2 = g.dx[3 * v + 2];
@@ -360,20 +412,63 @@ __device__ __forceinline__ double pg_apply(const PgArgs& g, double* s_val) {
     return sqrt(block_total(ss, s_val));
 }
 
-__global__ __launch_bounds__(PG_THREADS) void pose_graph_kernel(PgArgs g) {
-    __shared__ double s_val[PG_THREADS];
-    __shared__ int s_idx[PG_THREADS];
-    __shared__ int s_flag;                                        // a block of T turned out exactly singular
+// ── weights (robust kernel only): chi2_q = e^T Omega e of every edge of the caller's list, evaluated as
+// pose_graph_error_kernel evaluates it with the caller's Omega, and on a masked edge w_q = rho'(chi2_q), c = delta^2:
+//     Huber           rho = s (s <= c), 2 delta sqrt(s) - c     w = 1 (s <= c), delta / sqrt(s)
+//     Cauchy          rho = c log1p(s / c)                      w = c / (c + s)
+//     Geman-McClure   rho = (c / (c + s)) s                     w = (c / (c + s))^2
+// Every other edge, and every twin, has rho = s and w = 1.0.  Returns the cost, sum of rho: per thread in edge order
+// (edges tid, tid + PG_THREADS, ...), then block_total's tree.
+__device__ __forceinline__ double pg_weights(const PgRobArgs& g, double* s_val) {
+    const double c = g.delta * g.delta;
+    double part = 0.0;
+    for (int q = threadIdx.x; q < g.m; q += PG_THREADS) {
+        double w = 1.0;
+        if (q < g.m0) {
+            double e[3], Oe[3];
+            M3 A, B;
+            pg_linearise(g.nodes + 3 * g.ei[q], g.nodes + 3 * g.ej[q], g.z + 3 * q, e, A, B);
+            m3_vec(m3_load(g.omega0 + 9 * (size_t)q), e, Oe);
+            const double s = (e[0] * Oe[0] + e[1] * Oe[1]) + e[2] * Oe[2];
+            double rho = s;
+            if (g.rob[q]) {
+                if (g.kernel == ICPMI_ROB_KERNEL_HUBER) {
+                    if (!(s <= c)) { const double r = sqrt(s); w = g.delta / r; rho = (2.0 * g.delta) * r - c; }
+                } else {
+                    const double t = c / (c + s);
+                    if (g.kernel == ICPMI_ROB_KERNEL_CAUCHY) { w = t; rho = c * log1p(s / c); }
+                    else { w = t * t; rho = t * s; }
+                }
+            }
+            g.edge_chi2[q] = s;
+            g.edge_weight[q] = w;
+            part += rho;
+        }
+        g.wgt[q] = w;
+    }
+    return block_total(part, s_val);
+}
+
+// ── the optimisation: every iteration of both kernels.  E: how an edge's Omega enters (PgPlainEdges, PgWeightedEdges) ──
+// s_val, s_idx, s_flag: the kernel's LDS (s_flag: a block of T turned out exactly singular)
+template <class E> __device__ __forceinline__ void pg_gauss_newton(const typename E::Args& g, double* s_val, int* s_idx, int& s_flag) {
     int status = ICPMI_PG_ST_MAXITER, iters = g.n_iter;
     double step = 0.0;
     PgClock clock;
+    [[maybe_unused]] double cost = 0.0, cost_before = 0.0;
+    [[maybe_unused]] long long weights_clock = 0;
     const int tid = threadIdx.x, n = g.n, ncols = g.ncols;
     for (int it = 0; it < g.n_iter; ++it) {
         if (threadIdx.x == 0) s_flag = 0;
         if (g.dense) for (size_t t = threadIdx.x; t < (size_t)g.N3 * g.N3; t += PG_THREADS) g.Hd[t] = 0.0;
         __syncthreads();
         bool singular = false, refused = false;
-        pg_assemble(g);
+        if constexpr (E::weighted) {
+            cost = pg_weights(g, s_val);
+            if (it == 0) cost_before = cost;
+            weights_clock += clock.lap();
+        }
+        pg_assemble<E>(g);
         clock.mark(PG_ASSEMBLE);
         if (g.dense) singular = !block_lu_solve(g.Hd, g.N3, g.dx, s_val, s_idx);
         else {
@@ -457,7 +552,7 @@ __global__ __launch_bounds__(PG_THREADS) void pose_graph_kernel(PgArgs g) {
                 }
                 clock.mark(PG_CHAIN_SOLVE);
                 if (g.k > 0) {
-                    pg_closure_system(g);
+                    pg_closure_system<E>(g);
                     clock.mark(PG_CLOSURE_SYSTEM);
                     refused = !block_lu_solve(g.M, g.K, g.g, s_val, s_idx);           // y, in place of g
                     clock.mark(PG_CLOSURE_SOLVE);
@@ -473,10 +568,32 @@ __global__ __launch_bounds__(PG_THREADS) void pose_graph_kernel(PgArgs g) {
         clock.mark(PG_APPLY);
         if (step < g.eps) { status = ICPMI_PG_ST_CONVERGED; iters = it + 1; break; }
     }
+    if constexpr (E::weighted) {                                 // chi2, weights and the cost of the poses that are returned
+        cost = pg_weights(g, s_val);
+        if (g.n_iter == 0) cost_before = cost;
+        weights_clock += clock.lap();
+    }
     if (threadIdx.x == 0) {
         g.info[ICPMI_PGINFO_ITERATIONS] = (double)iters; g.info[ICPMI_PGINFO_STATUS] = (double)status; g.info[ICPMI_PGINFO_STEP] = step;
         for (int i = 0; i < PG_PHASES; ++i) g.info[ICPMI_PGINFO_PHASE_US + i] = (double)clock.acc[i] * 0.01;      // microseconds, all iterations
+        if constexpr (E::weighted) {
+            g.info[ICPMI_ROB_COST_BEFORE] = cost_before; g.info[ICPMI_ROB_COST_AFTER] = cost;
+            g.info[ICPMI_ROB_WEIGHTS_US] = (double)weights_clock * 0.01;
+        }
     }
+}
+
+__global__ __launch_bounds__(PG_THREADS) void pose_graph_kernel(PgArgs g) {
+    __shared__ double s_val[PG_THREADS];
+    __shared__ int s_idx[PG_THREADS];
+    __shared__ int s_flag;
+    pg_gauss_newton<PgPlainEdges>(g, s_val, s_idx, s_flag);
+}
+__global__ __launch_bounds__(PG_THREADS) void pose_graph_robust_kernel(PgRobArgs g) {
+    __shared__ double s_val[PG_THREADS];
+    __shared__ int s_idx[PG_THREADS];
+    __shared__ int s_flag;
+    pg_gauss_newton<PgWeightedEdges>(g, s_val, s_idx, s_flag);
 }
 
 // total_error, pose_graph.py:189-194: e^T Omega e summed in edge order
@@ -655,6 +772,75 @@ static int pg_optimize(double* nodes, const int32_t* edges_ij_host, const double
         return ICPMI_ERR_HIP;
     if (hipStreamSynchronize(st) != hipSuccess) return ICPMI_ERR_HIP;
     pose_graph_kernel<<<1, PG_THREADS, 0, st>>>(a);
+    ICPMI_LAUNCH_CHECK();
+    return ICPMI_OK;
+}
+
+// ── the robust optimiser's host side ─────────────────────────────────────────
+// A masked chain edge cannot stay in T (its weight would move T's stiffness under the plan): such a graph is planned
+// dense, like force_dense.  The weak-edge rule stays on the caller's unweighted Omega.
+static bool pg_robust_dense(const int32_t* ij, const uint8_t* mask, int m, bool force_dense) {
+    for (int q = 0; q < m && !force_dense; ++q) {
+        const int d = ij[2 * q] - ij[2 * q + 1];
+        if (mask[q] && (d == 1 || d == -1)) force_dense = true;
+    }
+    return force_dense;
+}
+static size_t pg_robust_workspace_bytes(const int32_t* edges_ij_host, const double* omega_host, const uint8_t* mask_host,
+                                        int32_t n_nodes, int32_t n_edges, bool force_dense) {
+    if (n_nodes < 0 || n_edges < 0 || (n_edges > 0 && (!edges_ij_host || !mask_host))) return 0;
+    const PgPlan p = pg_plan(edges_ij_host, omega_host, n_nodes, n_edges, pg_robust_dense(edges_ij_host, mask_host, n_edges, force_dense));
+    return p.rc == ICPMI_OK ? PgRobWs{{nullptr, n_nodes, p.m2, p.k, p.dense, p.twins}}.bytes : 0;
+}
+static int pg_robust_write_info(double* info, int status, hipStream_t st) {
+    double rec[ICPMI_ROB_DOUBLES] = {};
+    rec[ICPMI_PGINFO_STATUS] = (double)status;
+    if (hipMemcpyAsync(info, rec, sizeof(rec), hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
+    return hipStreamSynchronize(st) == hipSuccess ? ICPMI_OK : ICPMI_ERR_HIP;
+}
+
+static int pg_optimize_robust(double* nodes, const int32_t* edges_ij_host, const double* edges_z, const double* edges_omega,
+                              const uint8_t* mask_host, int32_t n_nodes, int32_t n_edges, int32_t n_iterations, int32_t fix_node,
+                              double convergence_eps, int32_t kernel, double delta, bool force_dense, double* edge_chi2,
+                              double* edge_weight, double* info, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!nodes || !info || !edge_chi2 || !edge_weight || n_nodes < 0 || n_edges < 0 || n_iterations < 0) return ICPMI_ERR_ARG;
+    if (n_edges > 0 && (!edges_ij_host || !edges_z || !edges_omega || !mask_host)) return ICPMI_ERR_ARG;
+    if (kernel != ICPMI_ROB_KERNEL_HUBER && kernel != ICPMI_ROB_KERNEL_CAUCHY && kernel != ICPMI_ROB_KERNEL_GEMAN_MCCLURE) return ICPMI_ERR_ARG;
+    if (!(delta > 0.0)) return ICPMI_ERR_ARG;                // NaN included
+    hipStream_t st = (hipStream_t)stream;
+    const int n = n_nodes, m = n_edges;
+    if (n >= 2 && m > 0) {
+        // everything the host can refuse comes before the first HIP call: the anchor, the edge indices, and a workspace
+        // below what the graph needs even without twins
+        if (fix_node < 0 || fix_node >= n) return ICPMI_ERR_ARG;
+        const size_t least = pg_robust_workspace_bytes(edges_ij_host, nullptr, mask_host, n, m, force_dense);
+        if (least == 0) return ICPMI_ERR_ARG;
+        if (!workspace || workspace_bytes < least) return ICPMI_ERR_WORKSPACE;
+    }
+    if (n < 2 || m == 0) return pg_robust_write_info(info, ICPMI_PG_ST_NOTHING, st);
+    force_dense = pg_robust_dense(edges_ij_host, mask_host, m, force_dense);
+    std::vector<double> om, zz;
+    if (!force_dense && !pg_read_back(om, edges_omega, 9 * (size_t)m, st)) return ICPMI_ERR_HIP;
+    PgPlan p = pg_plan(edges_ij_host, force_dense ? nullptr : om.data(), n, m, force_dense);
+    if (p.rc != ICPMI_OK) return p.rc;
+    const PgRobWs w{{workspace, n, p.m2, p.k, p.dense, p.twins}};
+    // as pg_optimize: a chain edge with a null direction, or twins without room: the caller continues on the dense path
+    if (p.refused || workspace_bytes < w.bytes) return pg_robust_write_info(info, ICPMI_PG_ST_REFUSED, st);
+    PgRobArgs a{w, nodes, edges_z, edges_omega, n_iterations, fix_node, convergence_eps, info, edges_omega, m, kernel, delta,
+                edge_chi2, edge_weight};
+    if (p.twins) {
+        if (!pg_read_back(zz, edges_z, 3 * (size_t)m, st)) return ICPMI_ERR_HIP;
+        p.add_twin_rows(om.data(), zz.data(), m);
+        if (!pg_upload(w.tw_omega, p.omega, st) || !pg_upload(w.tw_z, p.z, st)) return ICPMI_ERR_HIP;
+        a.z = w.tw_z; a.omega = w.tw_omega;
+    }
+    std::vector<uint8_t> rob(mask_host, mask_host + m);
+    rob.resize(p.m2, 0);                                     // a twin is unmasked by construction
+    if (!pg_upload(w.ei, p.ei_ej, st) || !pg_upload(w.csr_ptr, p.csr_ptr, st) || !pg_upload(w.csr_edge, p.csr_edge, st) ||
+        !pg_upload(w.loop_slot, p.loop_slot, st) || !pg_upload(w.loop_edge, p.loop_edge, st) || !pg_upload(w.rob, rob, st))
+        return ICPMI_ERR_HIP;
+    if (hipStreamSynchronize(st) != hipSuccess) return ICPMI_ERR_HIP;          // the plan's vectors are on this stack frame
+    pose_graph_robust_kernel<<<1, PG_THREADS, 0, st>>>(a);
     ICPMI_LAUNCH_CHECK();
     return ICPMI_OK;
 }
@@ -1123,6 +1309,22 @@ extern "C" int icpmi_pose_graph_optimize_dense(double* nodes, const int32_t* edg
                                                double* info, void* workspace, size_t workspace_bytes, void* stream) {
     return icpmi::pg_optimize(nodes, edges_ij_host, edges_z, edges_omega, n_nodes, n_edges, n_iterations, fix_node,
                               convergence_eps, info, workspace, workspace_bytes, stream, true);
+}
+
+extern "C" size_t icpmi_pose_graph_robust_workspace_bytes(const int32_t* edges_ij_host, const double* edges_omega_host,
+                                                          const uint8_t* edges_mask_host, int32_t n_nodes, int32_t n_edges,
+                                                          int32_t dense) {
+    return icpmi::pg_robust_workspace_bytes(edges_ij_host, edges_omega_host, edges_mask_host, n_nodes, n_edges, dense != 0);
+}
+extern "C" int icpmi_pose_graph_optimize_robust(double* nodes, const int32_t* edges_ij_host, const double* edges_z,
+                                                const double* edges_omega, const uint8_t* edges_mask_host, int32_t n_nodes,
+                                                int32_t n_edges, int32_t n_iterations, int32_t fix_node, double convergence_eps,
+                                                int32_t kernel, double delta, int32_t dense, double* edge_chi2,
+                                                double* edge_weight, double* info, void* workspace, size_t workspace_bytes,
+                                                void* stream) {
+    return icpmi::pg_optimize_robust(nodes, edges_ij_host, edges_z, edges_omega, edges_mask_host, n_nodes, n_edges, n_iterations,
+                                     fix_node, convergence_eps, kernel, delta, dense != 0, edge_chi2, edge_weight, info, workspace,
+                                     workspace_bytes, stream);
 }
 
 extern "C" int icpmi_pose_graph_error(const double* nodes, const int32_t* edges_i, const int32_t* edges_j, const double* edges_z,

@@ -49,6 +49,9 @@ PGINFO_DOUBLES, PGINFO_ITERATIONS, PGINFO_STATUS, PGINFO_STEP, PGINFO_PHASE_US, 
 # icpmi_pose_graph_marginals: the slots of its info record (its statuses are PG_ST_*) and the two paths
 MARG_DOUBLES, MARG_STATUS, MARG_PATH, MARG_CLOSURES, MARG_TWINS = 4, 0, 1, 2, 3
 MARG_PATH_SPLIT, MARG_PATH_DENSE = 0, 1
+# icpmi_pose_graph_optimize_robust: its loss kernels and the three slots its info record adds to PGINFO_*
+ROB_KERNEL_HUBER, ROB_KERNEL_CAUCHY, ROB_KERNEL_GEMAN_MCCLURE = 0, 1, 2
+ROB_DOUBLES, ROB_COST_BEFORE, ROB_COST_AFTER, ROB_WEIGHTS_US = 13, 10, 11, 12
 INFO_SLOTS = ("H_tt", "H_tx", "H_ty", "H_xx", "H_xy", "H_yy", "g_t", "g_x", "g_y", "sse", "inliers", "rows", "status")
 
 
@@ -197,6 +200,9 @@ _SIGS = {
     "icpmi_pose_graph_marginals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                              C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                              C.c_size_t, C.c_void_p]),
+    "icpmi_pose_graph_robust_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "icpmi_pose_graph_optimize_robust": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_double, C.c_int32, C.c_double, C.c_int32] +
+                                         [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -30,6 +30,7 @@ _SPLIT_REFUSED = _lib.PG_ST_REFUSED   # device status only: the chain part of th
 _ITERATIONS, _STATUS, _STEP = _lib.PGINFO_ITERATIONS, _lib.PGINFO_STATUS, _lib.PGINFO_STEP
 _PHASES = slice(_lib.PGINFO_PHASE_US, _lib.PGINFO_PHASE_US + _lib.PGINFO_PHASES)
 PHASE_KEYS = ("assemble", "chain_lu", "chain_sweeps", "closure_system", "closure_solve", "dx", "apply")    # in slot order
+ROBUST_KERNELS = {"huber": _lib.ROB_KERNEL_HUBER, "cauchy": _lib.ROB_KERNEL_CAUCHY, "geman_mcclure": _lib.ROB_KERNEL_GEMAN_MCCLURE}
 
 
 def normalize_angle(a):
@@ -110,6 +111,7 @@ class PoseGraph2D:
         self.nodes = []
         self.edges = []
         self.last_info = {}
+        self.last_robust = {}
 
     def add_node(self, pose_vec):
         self.nodes.append(np.asarray(pose_vec, dtype=float).copy())
@@ -189,13 +191,126 @@ class PoseGraph2D:
             elif status == MAX_ITERATIONS:
                 print(f"  PoseGraph max iterations: iter={n_iterations}, ||Δx||={step:.2e}")
 
-    def marginals(self, nodes=None, fix_node=0, diagonal=True, force_dense=False):
+    # ── robust edges (no counterpart in the reference) ────────────────────
+    def _robust_mask(self, ij, edges):
+        """uint8 mask over the edge list: ``edges`` is an iterable of edge indices or a boolean mask; None = every edge that
+        does not join consecutive nodes (the loop closures)."""
+        m = len(ij)
+        if edges is None:
+            return np.ascontiguousarray((np.abs(ij[:, 0] - ij[:, 1]) != 1).astype(np.uint8))
+        e = np.asarray(list(edges) if not isinstance(edges, np.ndarray) else edges)
+        mask = np.zeros(m, dtype=np.uint8)
+        if e.dtype == np.bool_:
+            if e.shape != (m,):
+                raise ValueError(f"a boolean edge mask needs one entry per edge ({m}), got shape {e.shape}")
+            mask[e] = 1
+        elif e.size:
+            idx = e.astype(np.int64)
+            if e.ndim != 1 or np.any(idx != e) or np.any(idx < -m) or np.any(idx >= m):
+                raise IndexError("edge index out of range")
+            mask[idx] = 1
+        return mask
+
+    def _run_robust(self, what, n_iterations, fix_node, convergence_eps, kernel, delta, edges):
+        """The robust entry on the current graph, with the REFUSED -> dense continuation of ``optimize``.
+        -> (nodes (n, 3), info record, the first launch's record or None, chi2, weights, mask)."""
+        if kernel not in ROBUST_KERNELS:
+            raise ValueError(f"unknown robust kernel {kernel!r}: one of {sorted(ROBUST_KERNELS)}")
+        if not float(delta) > 0.0:
+            raise ValueError(f"delta must be > 0, got {delta!r}")
+        n = len(self.nodes)
+        _b.require_gpu()
+        L = _lib.lib()
+        dev = torch.device("cuda", torch.cuda.current_device())
+        ij, z, om = self._edge_arrays()
+        m = len(ij)
+        mask = self._robust_mask(ij, edges)
+        fix = fix_node + n if fix_node < 0 else fix_node
+        d_nodes = torch.from_numpy(np.ascontiguousarray(np.array(self.nodes, dtype=np.float64).reshape(n, 3))).to(dev)
+        d_z, d_om = torch.from_numpy(z).to(dev), torch.from_numpy(om).to(dev)
+        d_info = torch.zeros(_lib.ROB_DOUBLES, dtype=torch.float64, device=dev)
+        d_chi2, d_wgt = (torch.zeros(m, dtype=torch.float64, device=dev) for _ in range(2))
+        ijp, omp, maskp = (a.ctypes.data_as(C.c_void_p) for a in (ij, om, mask))
+
+        def launch(dense, iterations):
+            size = L.icpmi_pose_graph_robust_workspace_bytes(ijp, omp, maskp, n, m, int(dense))
+            ws = torch.empty(max(int(size), 256), dtype=torch.uint8, device=dev)
+            _lib.check(L.icpmi_pose_graph_optimize_robust(
+                _b._ptr(d_nodes), ijp, _b._ptr(d_z), _b._ptr(d_om), maskp, n, m, int(iterations), int(fix), float(convergence_eps),
+                ROBUST_KERNELS[kernel], float(delta), int(dense), _b._ptr(d_chi2), _b._ptr(d_wgt), _b._ptr(d_info), _b._ptr(ws),
+                ws.numel(), _b._stream()), what)
+            return d_info.cpu().numpy()
+
+        info, first = launch(False, n_iterations), None
+        if int(info[_STATUS]) == _SPLIT_REFUSED:                  # as optimize: the remaining iterations take the dense matrix
+            first = info
+            info = launch(True, int(n_iterations) - int(first[_ITERATIONS]))
+        return d_nodes.cpu().numpy(), info, first, d_chi2.cpu().numpy(), d_wgt.cpu().numpy(), mask.astype(bool)
+
+    def optimize_robust(self, n_iterations=20, fix_node=0, convergence_eps=1e-6, kernel="huber", delta=2.7955, edges=None):
+        """``optimize`` with a robust loss on some edges: Gauss-Newton on sum of chi2 over the plain edges plus sum of
+        rho(chi2) over the robust ones, chi2 = e^T Omega e, by re-weighting every robust edge's Omega with rho'(chi2) at the
+        start of every iteration.  ``kernel``: "huber", "cauchy" or "geman_mcclure" (include/icpmi.h has the table);
+        ``delta``: chi2 = delta^2 is where the loss leaves the quadratic — the default is sqrt(7.8147), the 95 % quantile of
+        chi-square with 3 degrees of freedom; ``edges``: indices or a boolean mask of the robust edges, None = every edge that
+        does not join consecutive nodes.  A robust edge between consecutive nodes sends the graph down the dense path.
+        Sets ``last_info`` as ``optimize`` does, plus ``cost_before`` / ``cost_after`` (the loss at the poses given and
+        returned), ``weights_us`` and ``path``; and ``last_robust`` = dict(chi2, weights, mask, kernel, delta), chi2 and
+        weights per edge at the returned poses."""
+        n = len(self.nodes)
+        if n < 2 or len(self.edges) == 0:
+            return
+        out, info, first, chi2, weights, mask = self._run_robust("PoseGraph2D.optimize_robust", int(n_iterations), fix_node,
+                                                                 convergence_eps, kernel, delta, edges)
+        split_refused_at = None
+        if first is not None:
+            split_refused_at = int(first[_ITERATIONS])
+            info[_ITERATIONS] += first[_ITERATIONS]
+            info[_PHASES] += first[_PHASES]
+            info[_lib.ROB_WEIGHTS_US] += first[_lib.ROB_WEIGHTS_US]
+            if split_refused_at > 0:
+                info[_lib.ROB_COST_BEFORE] = first[_lib.ROB_COST_BEFORE]     # of the poses given; refused at once, the dense launch has it
+            if int(info[_ITERATIONS]) == split_refused_at:
+                info[_STEP] = first[_STEP]
+        iters, status, step = int(info[_ITERATIONS]), int(info[_STATUS]), info[_STEP]
+        for k in range(n):
+            self.nodes[k][:] = out[k]
+        # the plan's path rule (pg_plan, csrc/posegraph.hip) restated: the split needs every pair of consecutive nodes joined
+        # by an edge, none of those edges robust; a refused split went on densely
+        ij = self._edge_arrays()[0]
+        chained = np.abs(ij[:, 0] - ij[:, 1]) == 1
+        dense = (first is not None or bool(mask[chained].any())
+                 or len(set(np.minimum(ij[chained, 0], ij[chained, 1]).tolist())) < n - 1)
+        self.last_info = dict(iterations=iters, status=status, step_norm=float(step), split_refused_at=split_refused_at,
+                              phase_us=dict(zip(PHASE_KEYS, info[_PHASES].tolist())),
+                              cost_before=float(info[_lib.ROB_COST_BEFORE]), cost_after=float(info[_lib.ROB_COST_AFTER]),
+                              weights_us=float(info[_lib.ROB_WEIGHTS_US]), path="dense" if dense else "split")
+        self.last_robust = dict(chi2=chi2, weights=weights, mask=mask, kernel=kernel, delta=float(delta))
+        if VERBOSE:
+            if status == SINGULAR:
+                print(f"  PoseGraph: singular H at iter {iters}, stopping")
+            elif status == CONVERGED:
+                print(f"  PoseGraph converged: iter={iters - 1}, ||Δx||={step:.2e}")
+            elif status == MAX_ITERATIONS:
+                print(f"  PoseGraph max iterations: iter={n_iterations}, ||Δx||={step:.2e}")
+
+    def robust_cost(self, kernel, delta, edges=None):
+        """(cost, chi2, weights) of the robust loss at the current poses (``optimize_robust`` names the arguments): the
+        evaluation-only call, nothing is moved.  (0.0, empty, empty) for a graph without edges."""
+        if len(self.nodes) < 2 or len(self.edges) == 0:
+            return 0.0, np.zeros(0), np.zeros(0)
+        _, info, _, chi2, weights, _ = self._run_robust("PoseGraph2D.robust_cost", 0, 0, 0.0, kernel, delta, edges)
+        return float(info[_lib.ROB_COST_AFTER]), chi2, weights
+
+    def marginals(self, nodes=None, fix_node=0, diagonal=True, force_dense=False, edge_weights=None):
         """3 x 3 blocks of the inverse of the matrix ``optimize`` factorises (pose_graph.py:93-114) at the current poses:
         for symmetric positive definite information, the covariance of the poses given the pose at ``fix_node``.
         ``diagonal``: the block of every node; ``nodes``: a list of node indices (negative ones count from the end,
         repeats allowed) whose block columns are returned too, which holds every joint marginal among them.  Nothing is
         iterated and ``self.nodes`` stay as they are.  ``force_dense``: the dense elimination whatever the graph (it is
-        taken anyway where the chain + closures split does not apply or is refused).  Returns a ``Marginals``, or None where ``optimize`` would return
+        taken anyway where the chain + closures split does not apply or is refused).  ``edge_weights``: one weight per edge
+        (``last_robust["weights"]``), every Omega is multiplied by its weight on the host before upload: the covariances at
+        a robust optimum.  Returns a ``Marginals``, or None where ``optimize`` would return
         at once (fewer than two nodes, no edges); raises ``np.linalg.LinAlgError`` where the reference's solve would."""
         n = len(self.nodes)
         if n < 2 or len(self.edges) == 0:
@@ -214,6 +329,11 @@ class PoseGraph2D:
         dev = torch.device("cuda", torch.cuda.current_device())
         ij, z, om = self._edge_arrays()
         m, s = len(ij), len(sel)
+        if edge_weights is not None:
+            w = np.asarray(edge_weights, dtype=np.float64)
+            if w.shape != (m,):
+                raise ValueError(f"edge_weights needs one weight per edge ({m}), got shape {w.shape}")
+            om = np.ascontiguousarray(om * w[:, None, None])
         fix = fix_node + n if fix_node < 0 else fix_node
         poses = np.ascontiguousarray(np.array(self.nodes, dtype=np.float64).reshape(n, 3))
         d_nodes = torch.from_numpy(poses).to(dev)
