@@ -849,6 +849,41 @@ int icpmi_grid_search_batch(const int16_t* field, const int16_t* bound, int32_t 
 int icpmi_grid_match_moments(const int32_t* volume, const int32_t* records, int32_t n_pairs, int32_t n_angles,
                              int32_t window, int32_t half_step, int64_t* moments, void* stream);
 
+/* ---- likelihood field: the exact truncated distance transform of the occupied cells, mapped to a score ---------------
+ * The matchers above read the raw field: a hit scores only where earlier hits raised that very cell.  This entry makes the
+ * field they read instead while a wall is one cell wide: every cell scored by its distance to the nearest occupied cell.
+ * The result is an int16 (ny, nx) field like icpmi_grid_score_field's, so every matching entry, icpmi_grid_bound_field and
+ * the moments take it unchanged.  All of it is integer: the outputs are functions of the inputs alone, to the bit.
+ *
+ * field: device, int16 [ny][nx], what icpmi_grid_score_field wrote.  A cell is occupied iff field[y][x] >= threshold (any
+ * int32); cells outside the grid are never occupied.  radius R in [0, ICPMI_LF_MAX_RADIUS], in cells.
+ * d2_out (device, int16 [ny][nx], optional): the smallest (y - y')^2 + (x - x')^2 over the occupied cells (y', x') where
+ * that is at most R^2, and the sentinel R^2 + 1 everywhere else — exact.  (Evaluated in two passes: g(y, x) = the
+ * distance along the column to the nearest occupied cell within R; then the minimum over |dx| <= R of dx^2 + g(y, x + dx)^2;
+ * whatever exceeds R^2 becomes the sentinel.  A cell within R^2 has |dx|, |dy| <= R, so the two windows lose nothing.)
+ * lf_out (device, int16 [ny][nx], optional): table[d2] where d2 <= R^2; beyond the radius min(field, 0) when keep_free != 0
+ * — the raw field's penalty for a hit in observed free space stays — and 0 otherwise.
+ * table: R^2 + 1 int16 on the HOST, indexed by the squared distance (the Python layer: a Gaussian of the distance with the
+ * map's clamp as its peak).  It is read and checked before anything is enqueued and copied into the workspace on the
+ * stream, so the caller may free it when the call returns.  A table that holds -32768 is refused: every matcher's int32
+ * score bound rests on |field| <= 32767.  NULL is allowed only when lf_out is NULL.
+ * workspace: device, icpmi_grid_likelihood_workspace_bytes(ny, nx, radius) bytes (the device copy of the table, 256-byte
+ * granules; 0 for a refused argument); may be NULL when lf_out is NULL.
+ * Refusals, on the host before anything is enqueued: ny <= 0 or nx <= 0, ny * nx >= 2^31, field NULL, both outputs NULL,
+ * lf_out without a table, a pointer that is not 16-byte aligned (vector loads and stores), a table that holds -32768:
+ * ICPMI_ERR_ARG; a radius outside [0, ICPMI_LF_MAX_RADIUS] or more than 65 535 tile rows: ICPMI_ERR_UNSUPPORTED; lf_out
+ * with a workspace that is NULL or short: ICPMI_ERR_WORKSPACE.
+ * Launches: one copy of the table (only with lf_out) and lf_field_kernel — a workgroup of ICPMI_GM_THREADS threads per tile
+ * of ICPMI_LF_TILE_Y x ICPMI_LF_TILE_X outputs.  It stages the occupancy of the tile and a halo of R as bits in LDS, runs
+ * both passes there and writes each output once: 2 bytes read and 2 or 4 written per cell, and the halo from L2. */
+#define ICPMI_LF_MAX_RADIUS 64
+#define ICPMI_LF_TILE_X 128
+#define ICPMI_LF_TILE_Y 64
+size_t icpmi_grid_likelihood_workspace_bytes(int32_t ny, int32_t nx, int32_t radius);
+int icpmi_grid_likelihood_field(const int16_t* field, int32_t ny, int32_t nx, int32_t threshold, int32_t radius,
+                                const int16_t* table, int32_t keep_free, int16_t* d2_out, int16_t* lf_out,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
 /* ── pose graph: PoseGraph2D.optimize, utilities/pose_graph.py:83-134 ──────────
  * Gauss-Newton on SE(2) over n_nodes poses [x, y, theta] (nodes: device, updated
  * in place) and n_edges constraints (i, j, z_ij [3], Omega [3][3] row-major).

@@ -3,7 +3,9 @@ whole-cell shifts (``icpmi_grid_score_field``, ``icpmi_grid_match_batch``; the c
 search over a wide window (``icpmi_grid_bound_field``, ``icpmi_grid_search_batch``): blocks of shifts bounded from above by
 a max-pooled field, pruned against a seed score, the exhaustive winner returned.  ``icpmi_grid_match_moments`` reads the
 volume of a match once more: the integer-weighted moments of the candidates about the winner, from which
-``gaussian_of_moments`` forms a sub-cell pose and a covariance on the host.
+``gaussian_of_moments`` forms a sub-cell pose and a covariance on the host.  ``icpmi_grid_likelihood_field`` makes the field
+the matchers read while the map's walls are one cell wide: the exact truncated distance to the nearest occupied cell
+(``distance_field``), mapped to a score through a table (``likelihood_table``, ``likelihood_field``).
 
 The reference registers a scan against a cloud only (slam.py:53-98, 111-183); this reads the map ``utilities.mapping``
 builds.  The log-odds are quantised to int16 and a candidate's score is the integer sum of the field under the scan's
@@ -23,6 +25,7 @@ from .batch import CloudSet, _ptr, _stream, require_gpu
 ST_OK, ST_EMPTY, ST_CAPACITY = _lib.GM_ST_OK, _lib.GM_ST_EMPTY, _lib.GM_ST_CAPACITY
 MAX_WINDOW, MAX_ANGLES, MAX_ROWS = _lib.GM_MAX_WINDOW, _lib.GM_MAX_ANGLES, _lib.GM_MAX_ROWS
 WIDE_MAX_WINDOW, WIDE_MAX_ANGLES, BLOCKS = _lib.GMW_MAX_WINDOW, _lib.GMW_MAX_ANGLES, (4, 8, 16)
+LF_MAX_RADIUS = _lib.LF_MAX_RADIUS
 
 
 def shift_bits(log_odds_min, log_odds_max):
@@ -57,6 +60,68 @@ def bound_field(field, block=8, out=None):
     if out is None:
         out = torch.empty((ny + block - 1, nx + block - 1), dtype=torch.int16, device=field.device)
     check(_lib.lib().icpmi_grid_bound_field(_ptr(field), ny, nx, int(block), _ptr(out), _stream()), "grid_bound_field")
+    return out
+
+
+def _int16_field(field, out, what):
+    if field.dtype != torch.int16 or field.dim() != 2 or not field.is_contiguous():
+        raise ValueError("field must be a contiguous int16 (ny, nx) device tensor")
+    if out is None:
+        return torch.empty_like(field)
+    if out.dtype != torch.int16 or out.shape != field.shape or not out.is_contiguous() or out.device != field.device:
+        raise ValueError(f"{what} must be a contiguous int16 tensor of the field's shape on its device")
+    return out
+
+
+def _radius(radius):
+    R = int(radius)
+    if R != radius or not 0 <= R <= LF_MAX_RADIUS:
+        raise ValueError(f"radius must be a whole number of cells in [0, {LF_MAX_RADIUS}], got {radius}")
+    return R
+
+
+def distance_field(field, threshold, radius, out=None):
+    """The exact squared distance, in cells, of every cell of an int16 (ny, nx) device field to the nearest occupied one —
+    a cell with ``field >= threshold`` — where that is at most radius^2, and radius^2 + 1 elsewhere
+    (``icpmi_grid_likelihood_field``'s ``d2_out``) -> an int16 (ny, nx) tensor (``out`` when given)."""
+    R = _radius(radius)
+    out = _int16_field(field, out, "out")
+    ny, nx = field.shape
+    check(_lib.lib().icpmi_grid_likelihood_field(_ptr(field), ny, nx, int(threshold), R, None, 0, _ptr(out), None, None, 0, _stream()),
+          "grid_likelihood_field")
+    return out
+
+
+def likelihood_table(peak, sigma_cells, radius):
+    """The int16 table of ``likelihood_field`` for a Gaussian of the distance: entry d2 — a SQUARED distance in cells — is
+    rint(peak * exp(-d2 / (2 sigma_cells^2))), clipped to +-32767, formed in float64 on the host; radius^2 + 1 entries."""
+    R = _radius(radius)
+    if not float(sigma_cells) > 0.0:
+        raise ValueError(f"sigma_cells must be positive, got {sigma_cells}")
+    return np.clip(np.rint(peak * np.exp(-np.arange(R * R + 1) / (2 * sigma_cells**2))), -32767, 32767).astype(np.int16)
+
+
+def likelihood_field(field, threshold, radius, table, keep_free=True, out=None, d2_out=None):
+    """``icpmi_grid_likelihood_field``: ``table[d2]`` wherever ``distance_field``'s d2 is within the radius; beyond it
+    min(field, 0) — the raw field's penalty for a hit in observed free space — with ``keep_free``, else 0.  ``table``: radius^2
+    + 1 int16 on the host (``likelihood_table``), none of them -32768.  ``d2_out``: an int16 tensor that receives the distance
+    field of the same launch.  -> the int16 (ny, nx) field (``out`` when given), which every matcher takes as
+    ``field=(tensor, k)`` and ``bound_field`` as its input."""
+    R = _radius(radius)
+    table = np.ascontiguousarray(table)
+    if table.dtype != np.int16 or table.shape != (R * R + 1,):
+        raise ValueError(f"table must hold radius^2 + 1 = {R * R + 1} int16, got {table.dtype} {table.shape}")
+    if int(table.min()) == -32768:
+        raise ValueError("the table holds -32768: the matchers' score bound needs |field| <= 32767")
+    out = _int16_field(field, out, "out")
+    if d2_out is not None:
+        d2_out = _int16_field(field, d2_out, "d2_out")
+    ny, nx = field.shape
+    L = _lib.lib()
+    ws = torch.empty(L.icpmi_grid_likelihood_workspace_bytes(ny, nx, R), dtype=torch.uint8, device=field.device)
+    check(L.icpmi_grid_likelihood_field(_ptr(field), ny, nx, int(threshold), R, table.ctypes.data_as(C.c_void_p), int(bool(keep_free)),
+                                        None if d2_out is None else _ptr(d2_out), _ptr(out), _ptr(ws), ws.numel(), _stream()),
+          "grid_likelihood_field")
     return out
 
 

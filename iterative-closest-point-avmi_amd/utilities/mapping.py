@@ -310,6 +310,40 @@ class OccupancyGrid2D:
         k = gridmatch.shift_bits(self.log_odds_min, self.log_odds_max)
         return gridmatch.score_field(self._grid, k), k
 
+    def _lf_radius(self, radius):
+        from icpmi import gridmatch
+        R = int(np.ceil(radius / self.resolution))
+        if not 0 <= R <= gridmatch.LF_MAX_RADIUS:
+            raise ValueError(f"a radius of {radius} m is {R} cells at {self.resolution} m; at most {gridmatch.LF_MAX_RADIUS} are supported")
+        return R
+
+    def distance_field(self, radius, occupied_log_odds=0.5, field=None):
+        """-> the squared distance, in cells, of every cell to the nearest occupied one — log-odds >= ``occupied_log_odds`` in
+        ``field`` (a ``(tensor, k)`` of ``score_field()``; None: the map as it is now) — exact where it is at most R^2,
+        R = int(np.ceil(radius / resolution)) for ``radius`` in metres, and R^2 + 1 elsewhere: an int16 (ny, nx) device tensor
+        (``icpmi.gridmatch.distance_field``).  Built anew at every call, like the field."""
+        from icpmi import gridmatch
+        q, k = self.score_field() if field is None else field
+        return gridmatch.distance_field(q, int(np.rint(occupied_log_odds * 2.0 ** k)), self._lf_radius(radius))
+
+    def likelihood_field(self, sigma=None, radius=None, occupied_log_odds=0.5, keep_free=True, field=None):
+        """-> (field, k): the map as a likelihood field, for ``field=`` of every matching method (and ``bound_field(field=...)``
+        for the wide search).  A cell scores rint(peak * exp(-d^2 / (2 sigma^2))) with d its exact distance to the nearest
+        occupied cell — log-odds >= ``occupied_log_odds`` — and peak = rint(log_odds_max * 2^k): a hit half a cell off a wall
+        one cell wide still scores.  ``sigma`` in metres (None: one cell); ``radius`` in metres (None: 3 sigma), R =
+        int(np.ceil(radius / resolution)) cells — the float quotient as it comes, so 6 * 0.05 m at 0.05 m is 7 cells and 0.3 m is
+        6: never fewer than asked for — ValueError above ``icpmi.gridmatch.LF_MAX_RADIUS``.  Beyond the radius a cell
+        keeps min(raw field, 0), the penalty of observed free space, with ``keep_free``; else 0.  ``field``: the raw
+        ``(tensor, k)`` of ``score_field()`` to start from (None: the map as it is now); k is that field's.
+        Built anew at every call — there is no cache, so no update has to invalidate one; a field passed to a matcher scores
+        against the map as it was when the field was made, whatever has been applied since."""
+        from icpmi import gridmatch
+        q, k = self.score_field() if field is None else field
+        sigma = self.resolution if sigma is None else float(sigma)
+        R = self._lf_radius(3.0 * sigma if radius is None else radius)
+        table = gridmatch.likelihood_table(np.rint(self.log_odds_max * 2.0 ** k), sigma / self.resolution, R)
+        return gridmatch.likelihood_field(q, int(np.rint(occupied_log_odds * 2.0 ** k)), R, table, keep_free), k
+
     @staticmethod
     def _xytheta(poses, n=None):
         """Predicted poses as (n, 3) rows [x, y, theta]: given as such, or as a stack of 3 x 3 matrices (theta as
