@@ -19,6 +19,7 @@ from ._lib import IcpmiError, IcpParams, check
 
 
 PREP_MAX_POINTS = 4096      # clouds up to this many rows take the sorted-sweep kernels (prep.hip, icp2.hip)
+VOXEL_KEY_RANGE_ERROR = "voxel key range does not fit in 64 bits"      # a count of -1 from the voxel filter, on the host
 
 
 def require_gpu():
@@ -85,9 +86,12 @@ class CloudSet:
         return self.cnt.cpu().numpy()
 
     def to_numpy(self):
-        """List of (cnt_c, dim) arrays (synchronises)."""
+        """List of (cnt_c, dim) arrays (synchronises).  A negative count is the voxel filter's "key range does not fit"
+        (csrc/voxel.hip): OverflowError, as from ``utilities.icp.voxel_downsample``."""
         host = self.pts.cpu().numpy()
         cnt = self.counts_host()
+        if (cnt[:self.n_clouds] < 0).any():
+            raise OverflowError(VOXEL_KEY_RANGE_ERROR)
         return [host[self.off_host[c]:self.off_host[c] + cnt[c]].copy() for c in range(self.n_clouds)]
 
 
@@ -166,6 +170,15 @@ def init_rows(R_init, t_init, B, dim):
     R = np.broadcast_to(np.asarray(R_init, dtype=np.float64), (B, d, d)).reshape(B, d * d)
     t = np.broadcast_to(np.asarray(t_init, dtype=np.float64), (B, d))
     return np.ascontiguousarray(np.concatenate([R, t], axis=1))
+
+
+def filtered_rows(out, c=0):
+    """Rows the voxel filter left in cloud ``c`` of its output set (synchronises); OverflowError for its count of -1 — as a
+    slice bound that count would silently drop the cloud's last row."""
+    n = int(out.cnt[c].item())
+    if n < 0:
+        raise OverflowError(VOXEL_KEY_RANGE_ERROR)
+    return n
 
 
 def voxel_downsample_set(cs, voxel_size, out=None, workspace=None):

@@ -81,7 +81,7 @@ class RollingSubmap:
                 self._ws = torch.empty(need, dtype=torch.uint8, device=self._dev)
             out = _b.voxel_downsample_set(cs, self.voxel_size, workspace=self._ws)
             self._built = out
-        m = int(self._built.cnt[0].item())
+        m = _b.filtered_rows(self._built)
         return self._built.pts[:m], self._built
 
     def build_numpy(self):
@@ -142,7 +142,7 @@ def _voxel_rows(points_dev, voxel_size):
     if n == 0:
         raise ValueError("zero-size array to reduction operation minimum which has no identity")   # np.min, icp.py:119
     out = _b.voxel_downsample_set(_b.CloudSet(points_dev, np.array([0, n], dtype=np.int32)), voxel_size)
-    return out.pts[: int(out.cnt[0].item())]
+    return out.pts[: _b.filtered_rows(out)]
 
 
 def submap_rotation_search(source_local, submap_global, predicted_pose, angle_range=60.0, angle_step=2.0,

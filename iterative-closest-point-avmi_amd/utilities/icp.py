@@ -97,10 +97,7 @@ def voxel_downsample(points, voxel_size):
     points = _as_points(points, "points")
     cs = _b.CloudSet.from_numpy([points])
     out = _b.voxel_downsample_set(cs, voxel_size)
-    n = int(out.cnt[0].item())
-    if n < 0:
-        raise OverflowError("voxel key range does not fit in 64 bits")
-    return out.pts[:n].cpu().numpy()
+    return out.pts[:_b.filtered_rows(out)].cpu().numpy()
 
 
 def ICP(source, target, error_threshold, max_iterations, voxel_size,

@@ -2,7 +2,12 @@
 LDS layout or their launch changes: the 512- and the 1 024-thread voxel launch on all three sort forms, the prepare kernel on
 both sides of every register-sort width, of its pair-sort fallback and of the hand-over to the global-memory path, and the
 return codes of the two entry points for calls that launch nothing.  Everything against the project's own oracle, bit for
-bit where no bound is stated."""
+bit where no bound is stated.
+
+The voxel clouds here are uniform: a voxel holds one point, or two at the largest voxel size, so these tests cross the switches
+between the sort forms but cannot see the order in which a run of equal keys is summed (a + b commutes).  Runs of three and
+more points on every one of these paths, keys on the rounding boundary of the divide and the clouds the filter refuses are
+tested in tests/test_voxel_edges_gpu.py."""
 import ctypes as C
 
 import numpy as np
