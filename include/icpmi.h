@@ -647,7 +647,13 @@ int icpmi_bresenham_cells(const int32_t* segs, const int64_t* cell_off, int32_t 
  * Every call leaves the workspace all zero again.
  * scan_seq: ignored (kept for binary compatibility; calls are independent).
  * full_clip != 0 clips every cell of the grid on the first scan (needed only
- * when cells may lie outside [lo, hi] beforehand). */
+ * when cells may lie outside [lo, hi] beforehand).
+ * Coordinates far from the grid (the same rule for this entry, _band and _box, and for every pass): the cell index of
+ * a coordinate is q = floor((w - min) / resolution), the IEEE quotient.  A scan whose origin has a q that is NaN or
+ * not below 1e300 in magnitude adds nothing; a beam whose hit has one is dropped, as a non-finite coordinate is (the
+ * reference raises on both).  Any other q beyond +-2^29 is replaced by +-2^29: the beam is the Bresenham line between
+ * the CLAMPED cells, which is not the direction of the world line, and its length is at most 2^30 cells.  The
+ * reference walks the unclamped line; the two agree for every coordinate within 2^29 cells of the grid's minimum. */
 size_t icpmi_grid_workspace_bytes(int32_t ny, int32_t nx);
 int icpmi_grid_update_scans(float* log_odds, void* counts, int32_t ny, int32_t nx,
                             double min_x, double min_y, double resolution,
@@ -662,7 +668,8 @@ int icpmi_grid_update_scans(float* log_odds, void* counts, int32_t ny, int32_t n
  * gathering the bands gives the same grid bit for bit.  log_odds and counts
  * are FULL-size (ny x nx) buffers; only rows of the band are read or written,
  * rays are clipped to the band analytically (no steps are walked outside it),
- * and full_clip clips the band only. */
+ * and full_clip clips the band only.  Coordinates beyond +-2^29 cells or with a
+ * quotient >= 1e300: as stated for icpmi_grid_update_scans. */
 int icpmi_grid_update_scans_band(float* log_odds, void* counts, int32_t ny, int32_t nx,
                                  double min_x, double min_y, double resolution,
                                  const double* origins, const double* hits, const int32_t* hit_off_host,
@@ -676,13 +683,38 @@ int icpmi_grid_update_scans_band(float* log_odds, void* counts, int32_t ny, int3
  * Counters are then kept for that box only, which is what lets 32 scans be counted per launch inside a workspace
  * of four grids (the Python class computes the box from the scans it is given), and a replay of several scans is
  * counted tile by tile in LDS instead of with one device atomic per beam and cell (same counts, ~1.4x the rate).
- * A ray cell outside the box is not counted: the box is a contract, not a clip the reference has. */
+ * A ray cell outside the box is not counted: the box is a contract, not a clip the reference has.
+ * Coordinates beyond +-2^29 cells or with a quotient >= 1e300: as stated for icpmi_grid_update_scans — the box holds the
+ * CLAMPED cells (so its bounds lie in [-2^29 - 1, 2^29 + 1]). */
 int icpmi_grid_update_scans_box(float* log_odds, void* counts, int32_t ny, int32_t nx,
                                 double min_x, double min_y, double resolution,
                                 const double* origins, const double* hits, const int32_t* hit_off_host,
                                 int32_t n_scans, double l_hit, double l_miss, double lo, double hi,
                                 int64_t scan_seq, int32_t full_clip, int32_t row_begin, int32_t row_end,
                                 const int32_t* box_host, void* stream);
+
+/* What icpmi_grid_update_scans_box starts for its HOST arguments (have_hits: whether `hits` is non-null), under the
+ * RAYCAST option as it stands — no HIP call, no launch, no device pointer.  The refusals are that entry's, in its
+ * order (ICPMI_ERR_ARG: a null out or hit_off_host, ny, nx <= 0 or > 2^29, n_scans < 0, a band outside [0, ny], a
+ * resolution that is not > 0, a negative beam count, beams without hits).  An empty band starts nothing: ICPMI_OK and
+ * a plan of zeros (ICPMI_RC_PASS_NONE).
+ *   pass        the counting pass of the scans that fit a 16-bit counter: one launch in which a workgroup owns a
+ *               rectangle of cells (OWNER), counters of a 64 x 64 tile in LDS (TILES), an atomic per (wave, cell) on
+ *               the scan's counter region (ATOMIC)
+ *   group_max   scans counted per launch at most;  tiles_x, tiles_y: 64 x 64 tiles of the window (grid or band cut to
+ *               the box);  live_scans: scans with beams
+ *   wide        1: a scan has more than 65 535 beams and goes through the two-round route (hits, then misses, on the
+ *               atomic counters) whatever `pass` says about the others */
+#define ICPMI_RC_PASS_NONE 0
+#define ICPMI_RC_PASS_OWNER 1
+#define ICPMI_RC_PASS_TILES 2
+#define ICPMI_RC_PASS_ATOMIC 3
+typedef struct icpmi_grid_plan {
+    int32_t pass, group_max, tiles_x, tiles_y, live_scans, wide;
+} icpmi_grid_plan;
+int icpmi_grid_update_plan(int32_t ny, int32_t nx, double resolution, const int32_t* hit_off_host, int32_t n_scans,
+                           int32_t have_hits, int32_t full_clip, int32_t row_begin, int32_t row_end,
+                           const int32_t* box_host, icpmi_grid_plan* out);
 
 /* ---- correlative scan-to-map matching: the grid of utilities/mapping.py read back as a target -----------------------
  * The reference registers a scan against a cloud only (slam.py:53-98, 111-183).  These entries score a scan against the

@@ -286,16 +286,21 @@ __device__ __forceinline__ float apply_counts(float v0, uint32_t H, uint32_t M, 
         if (exact + bound < (double)lo32) return lo32;
         if (exact - bound > (double)hi32) return hi32;
     }
+    // A fixed point ends a loop: further equal adds change nothing.  The add that finds it is kept — equal values can
+    // still differ in the sign of a zero (-0.0 + 0.0 is +0.0, and 0.0 + l is -0.0 for a negative l that underflows), and
+    // the value after it is a fixed point bit for bit.
     float v = v0;
     for (uint32_t i = 0; i < H; ++i) {
         const float nv = (float)((double)v + l_hit);
-        if (nv == v) break;                       // fixed point: further equal adds change nothing
+        const bool fixed = nv == v;
         v = nv;
+        if (fixed) break;
     }
     for (uint32_t i = 0; i < M; ++i) {
         const float nv = (float)((double)v + l_miss);
-        if (nv == v) break;
+        const bool fixed = nv == v;
         v = nv;
+        if (fixed) break;
     }
     return clip ? clamp32(v, lo32, hi32) : v;
 }
@@ -678,6 +683,12 @@ __global__ __launch_bounds__(RO_THREADS) void ray_owner_kernel(GridDesc g, const
     const double wya = g.min_y + ((double)y0 - 2.0) * g.res, wyb = g.min_y + ((double)y1 + 2.0) * g.res;
     const double owx = origin[0], owy = origin[1];
     const double rinv = 1.0 / g.res;
+    // The side-of-line test holds for the world line, and the beam is the line between the CLAMPED cells (world_to_cell): a
+    // beam with an end within four cells of the clamp or beyond it (or NaN) stays out of that test.  One comparison per beam:
+    // the length the test already forms, against what the origin leaves of the range (negative for an origin out of it); the
+    // end-point test before it stays — the clamp is monotone.
+    const double reach = (double)(RC_COORD_MAX - 4) * g.res;
+    const double line_max = reach - fmax(fabs(owx - g.min_x), fabs(owy - g.min_y));     // (a NaN beam length compares false)
     for (int base = 0; base < nb; base += PER_CHUNK * RO_THREADS) {  // uniform trip count
         const int par = (base / (PER_CHUNK * RO_THREADS)) & 1;
 #pragma unroll
@@ -689,7 +700,8 @@ __global__ __launch_bounds__(RO_THREADS) void ray_owner_kernel(GridDesc g, const
                 // (comparisons with NaN are false: such a beam goes on to the cell index, which refuses it)
                 maybe = !((owx < wxa && hwx[j] < wxa) || (owx > wxb && hwx[j] > wxb) || (owy < wya && hwy[j] < wya) || (owy > wyb && hwy[j] > wyb));
                 const double dxw = hwx[j] - owx, dyw = hwy[j] - owy;
-                if (maybe && fabs(dxw) + fabs(dyw) > 4.0 * g.res) {
+                const double len1 = fabs(dxw) + fabs(dyw);
+                if (maybe && len1 > 4.0 * g.res && len1 < line_max) {
                     const double c0 = dxw * (wya - owy) - dyw * (wxa - owx), c1 = dxw * (wya - owy) - dyw * (wxb - owx);
                     const double c2 = dxw * (wyb - owy) - dyw * (wxa - owx), c3 = dxw * (wyb - owy) - dyw * (wxb - owx);
                     maybe = !((c0 > 0 && c1 > 0 && c2 > 0 && c3 > 0) || (c0 < 0 && c1 < 0 && c2 < 0 && c3 < 0));
@@ -955,6 +967,32 @@ extern "C" int icpmi_grid_update_scans_band(float* log_odds, void* counts_ws, in
                                             void* stream) {
     return icpmi_grid_update_scans_box(log_odds, counts_ws, ny, nx, min_x, min_y, resolution, origins, hits, hit_off_host, n_scans,
                                        l_hit, l_miss, lo, hi, scan_seq, full_clip, row_begin, row_end, nullptr, stream);
+}
+
+// What icpmi_grid_update_scans_box would start for these host arguments, under the RAYCAST option as it stands: the same
+// refusals in the same order, then plan_raycast and build_group's checks of the beam counts.  No HIP call.
+extern "C" int icpmi_grid_update_plan(int32_t ny, int32_t nx, double resolution, const int32_t* hit_off_host, int32_t n_scans,
+                                      int32_t have_hits, int32_t full_clip, int32_t row_begin, int32_t row_end,
+                                      const int32_t* box_host, icpmi_grid_plan* out) {
+    using namespace icpmi;
+    if (!out || !hit_off_host || ny <= 0 || nx <= 0 || n_scans < 0) return ICPMI_ERR_ARG;
+    if (row_begin < 0 || row_end > ny || row_begin > row_end) return ICPMI_ERR_ARG;
+    if (ny > RC_COORD_MAX || nx > RC_COORD_MAX || !(resolution > 0.0)) return ICPMI_ERR_ARG;
+    *out = icpmi_grid_plan{};
+    if (row_begin == row_end) return ICPMI_OK;                  // an empty band: nothing is started (pass ICPMI_RC_PASS_NONE)
+    const RaycastPlan plan = plan_raycast(ny, nx, row_begin, row_end, box_host, hit_off_host, n_scans, full_clip != 0,
+                                          have_hits != 0, parse_rc_option(option("RAYCAST")));
+    int wide = 0;
+    for (int t = 0; t < n_scans; ++t) {
+        const int nb = hit_off_host[t + 1] - hit_off_host[t];
+        if (nb < 0) return ICPMI_ERR_ARG;
+        if (nb > 0 && !have_hits) return ICPMI_ERR_ARG;
+        wide |= nb > RC_WIDE ? 1 : 0;
+    }
+    out->pass = plan.pass == RcPass::owner ? ICPMI_RC_PASS_OWNER : plan.pass == RcPass::tiles ? ICPMI_RC_PASS_TILES : ICPMI_RC_PASS_ATOMIC;
+    out->group_max = plan.group_max; out->tiles_x = plan.tiles_x; out->tiles_y = plan.tiles_y;
+    out->live_scans = plan.live_scans; out->wide = wide;
+    return ICPMI_OK;
 }
 
 extern "C" int icpmi_grid_update_scans_box(float* log_odds, void* counts_ws, int32_t ny, int32_t nx,

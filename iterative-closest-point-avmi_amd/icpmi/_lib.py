@@ -54,6 +54,8 @@ MARG_PATH_SPLIT, MARG_PATH_DENSE = 0, 1
 # icpmi_pose_graph_optimize_robust: its loss kernels and the three slots its info record adds to PGINFO_*
 ROB_KERNEL_HUBER, ROB_KERNEL_CAUCHY, ROB_KERNEL_GEMAN_MCCLURE = 0, 1, 2
 ROB_DOUBLES, ROB_COST_BEFORE, ROB_COST_AFTER, ROB_WEIGHTS_US = 13, 10, 11, 12
+# icpmi_grid_update_plan: the counting pass of a ray-cast call
+RC_PASS_NONE, RC_PASS_OWNER, RC_PASS_TILES, RC_PASS_ATOMIC = 0, 1, 2, 3
 INFO_SLOTS = ("H_tt", "H_tx", "H_ty", "H_xx", "H_xy", "H_yy", "g_t", "g_x", "g_y", "sse", "inliers", "rows", "status")
 
 
@@ -77,6 +79,12 @@ class FeatureStore(C.Structure):
     _fields_ = [("vox", C.c_void_p), ("curv", C.c_void_p), ("cnt", C.c_void_p), ("kp", C.c_void_p), ("kp_cnt", C.c_void_p),
                 ("desc", C.c_void_p), ("desc_len", C.c_void_p), ("voxel_size", C.c_double), ("min_kp_dist", C.c_double),
                 ("k_curvature", C.c_int32), ("top_n", C.c_int32), ("k_descriptor", C.c_int32), ("kp_stride", C.c_int32)]
+
+
+class GridPlan(C.Structure):
+    """icpmi_grid_plan (include/icpmi.h): what one icpmi_grid_update_scans_box call starts, from its host arguments."""
+    _fields_ = [("pass_", C.c_int32), ("group_max", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32),
+                ("live_scans", C.c_int32), ("wide", C.c_int32)]
 
 
 class IcpmiError(RuntimeError):
@@ -176,6 +184,8 @@ _SIGS = {
                                               C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double,
                                               C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int32, C.c_int32,
                                               C.c_int32, C.c_void_p, C.c_void_p]),
+    "icpmi_grid_update_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_void_p, C.POINTER(GridPlan)]),
     "icpmi_grid_score_field": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "icpmi_grid_match_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
     "icpmi_grid_match_batch": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double] + [C.c_void_p] * 4 +

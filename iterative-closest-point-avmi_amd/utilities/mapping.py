@@ -255,8 +255,9 @@ class OccupancyGrid2D:
         if not (math.isfinite(x0) and math.isfinite(y0) and math.isfinite(x1) and math.isfinite(y1)):
             return None                                         # a NaN / inf coordinate somewhere: no promise
         res, lim = self.resolution, 2.0 ** 29
-        # same expression as the cell index, monotone in the coordinate
-        c = [min(max(math.floor((v - m) / res), -lim), lim) for v, m in ((x0, self.min_x), (y0, self.min_y), (x1, self.min_x), (y1, self.min_y))]
+        # same expression as the cell index, monotone in the coordinate; clamped before the floor, which refuses a quotient that
+        # overflowed to infinity (a finite coordinate near 1.8e308: the library drops that beam, the box only has to hold it)
+        c = [math.floor(min(max((v - m) / res, -lim), lim)) for v, m in ((x0, self.min_x), (y0, self.min_y), (x1, self.min_x), (y1, self.min_y))]
         return np.array([c[0] - 1, c[1] - 1, c[2] + 1, c[3] + 1], dtype=np.int32)
 
     def _apply(self, org, packed, off, rows=None, box=None):

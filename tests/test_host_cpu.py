@@ -672,3 +672,59 @@ def test_cell_box_of_a_scan_matches_the_array_expression():
         c = np.clip(np.floor((lo_hi - np.array([grid.min_x, grid.min_y])) / grid.resolution), -2.0 ** 29, 2.0 ** 29)
         want = np.array([c[0, 0] - 1, c[0, 1] - 1, c[1, 0] + 1, c[1, 1] + 1], dtype=np.int32)
         assert got.dtype == np.int32 and np.array_equal(got, want), trial
+
+
+def test_cell_box_holds_a_coordinate_whose_quotient_overflows():
+    """A finite coordinate near 1.8e308 has an infinite quotient: the library drops that beam, and the box — clamped before the
+    floor — is the clamp on that side (math.floor(inf) raised OverflowError out of update_scan)."""
+    import types
+    from utilities import mapping
+    grid = types.SimpleNamespace(min_x=0.0, min_y=0.0, resolution=0.05)
+    got = mapping.OccupancyGrid2D._box_of(grid, np.array([-1.7e308, 1.0]), np.array([2.0, 1e301]))
+    assert got.tolist() == [-2 ** 29 - 1, 19, 41, 2 ** 29 + 1]
+
+
+def test_grid_update_plan_rows():
+    """icpmi_grid_update_plan: the host-only view of what icpmi_grid_update_scans_box starts — its refusals, and the pass, group
+    size, tiles, live scans and wide flag for the default RAYCAST option, against literal values."""
+    import ctypes
+    import icpmi
+    from icpmi import _lib
+    icpmi.build()
+    lib = icpmi.lib()
+    ERR_ARG, NONE, OWNER, TILES, ATOMIC = -1, _lib.RC_PASS_NONE, _lib.RC_PASS_OWNER, _lib.RC_PASS_TILES, _lib.RC_PASS_ATOMIC
+    assert ctypes.sizeof(_lib.GridPlan) == 24 and _lib.GridPlan.wide.offset == 20
+
+    def call(ny=150, nx=200, res=0.05, off=(0, 2048), have_hits=1, full_clip=0, rows=None, box=(0, 0, 199, 149), out=True, n_scans=None):
+        o = np.array(off, dtype=np.int32) if off is not None else None
+        b = np.array(box, dtype=np.int32) if box is not None else None
+        plan = _lib.GridPlan(-7, -7, -7, -7, -7, -7)
+        r0, r1 = (0, ny) if rows is None else rows
+        code = lib.icpmi_grid_update_plan(ny, nx, res, o.ctypes.data if o is not None else None, len(off) - 1 if n_scans is None else n_scans,
+                                          have_hits, full_clip, r0, r1, b.ctypes.data if b is not None else None,
+                                          ctypes.byref(plan) if out else None)
+        return code, (plan.pass_, plan.group_max, plan.tiles_x, plan.tiles_y, plan.live_scans, plan.wide)
+
+    # refusals, in the order of icpmi_grid_update_scans_box
+    for kw in (dict(out=False), dict(off=None, n_scans=1), dict(ny=0), dict(nx=-1), dict(n_scans=-1), dict(rows=(-1, 10)), dict(rows=(0, 151)),
+               dict(rows=(9, 8)), dict(ny=2 ** 29 + 1, rows=(0, 1)), dict(res=0.0), dict(res=float("nan")), dict(off=(0, 10, 5)),
+               dict(have_hits=0)):
+        assert call(**kw)[0] == ERR_ARG, kw
+    # (pass, group_max, tiles_x, tiles_y, live_scans, wide)
+    rows = [(dict(), (OWNER, 2, 4, 3, 1, 0)),                                          # the live update
+            (dict(rows=(7, 7)), (NONE, 0, 0, 0, 0, 0)),                                 # an empty band starts nothing
+            (dict(full_clip=1), (ATOMIC, 2, 4, 3, 1, 0)),                               # the owner pass does no whole-grid clip
+            (dict(box=None), (ATOMIC, 2, 4, 3, 1, 0)),                                  # no promise about the rays
+            (dict(off=(0, 65535)), (OWNER, 2, 4, 3, 1, 0)), (dict(off=(0, 65536)), (ATOMIC, 2, 4, 3, 1, 1)),
+            (dict(off=(0, 100, 100, 300)), (TILES, 2, 4, 3, 2, 0)),                     # a replay with a box
+            (dict(off=(0, 100, 70000, 70100)), (TILES, 2, 4, 3, 3, 1)),
+            (dict(off=(0, 100, 300), box=(10, 20, 70, 40)), (TILES, 32, 1, 1, 2, 0)),   # a small box: 32 scans a group
+            (dict(off=(0, 100, 300), rows=(40, 97)), (TILES, 5, 4, 1, 2, 0)),           # a band: 200 x 57 cells
+            (dict(off=(0, 100, 300), box=(300, 0, 400, 10)), (ATOMIC, 32, 1, 1, 2, 0)),  # a box beside the grid: an empty window
+            (dict(off=(0, 0, 0)), (ATOMIC, 2, 4, 3, 0, 0)), (dict(off=(0, 0), have_hits=0), (ATOMIC, 2, 4, 3, 0, 0)),
+            (dict(ny=4000, nx=4000, box=(0, 0, 3999, 3999)), (ATOMIC, 2, 63, 63, 1, 0)),   # 3 969 tiles: too many for the owner pass
+            (dict(ny=1200, nx=1200, box=(0, 0, 1199, 1199)), (ATOMIC, 2, 19, 19, 1, 0)),   # 361 > 320
+            (dict(ny=1088, nx=1088, box=(0, 0, 1087, 1087)), (OWNER, 2, 17, 17, 1, 0))]    # 289 tiles
+    for kw, want in rows:
+        code, got = call(**kw)
+        assert code == 0 and got == want, (kw, got)
