@@ -916,6 +916,79 @@ int icpmi_grid_likelihood_field(const int16_t* field, int32_t ny, int32_t nx, in
                                 const int16_t* table, int32_t keep_free, int16_t* d2_out, int16_t* lf_out,
                                 void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the cast: the grid read back as ranges (no counterpart in the reference) ------------------------------------------
+ * icpmi_grid_update_scans writes along rays; these entries read along them: from a cell, towards a cell, where is the first
+ * wall, and is there unexplored space before it?  The cells of a ray are exactly the cells the update would lower, plus the
+ * end cell, so the map's writer and its reader agree cell for cell.  Behind the end cells everything is integer: a record
+ * is a function of the inputs alone, to the bit.
+ *
+ * Field and cells.  field: device, int16 [ny][nx] — icpmi_grid_score_field's, or any other such as a likelihood field.  A
+ * cell inside the grid is OCCUPIED iff field[y][x] >= occ_threshold (any int32; icpmi_grid_likelihood_field's rule) and
+ * UNKNOWN iff field[y][x] == 0.  A cell outside [0, ny) x [0, nx) is neither.
+ *
+ * Segments and steps.  A segment is (x0, y0, x1, y1) in cells, int32, each within +-2^29 (a value beyond is replaced by
+ * +-2^29, as icpmi_grid_update_scans clamps).  With dx = |x1 - x0|, dy = |y1 - y0| its steps are k = 0 .. K, K = max(dx, dy).
+ * Step k < K is the k-th cell of _bresenham, mapping.py:68-89 (icpmi_bresenham_cells); step K is the end cell (x1, y1), which
+ * that list leaves out.  In closed form, x the major axis when dx >= dy (y otherwise), sm and sn the signs of the deltas
+ * (-1 for a delta of 0), dmaj = K and dmin the other delta: step k lies at major = m0 + sm * k and minor = n0 + sn *
+ * floor((2 * k * dmin + dmaj - 1) / (2 * dmaj)); K = 0 has the one step (x0, y0).
+ *
+ * Record: four int32 per ray, slots ICPMI_GC_*, written as one 16-byte store: [k_hit, x_hit, y_hit, k_unknown].
+ * k_hit: the first step whose cell is occupied, (x_hit, y_hit) that cell; without one k_hit = ICPMI_GC_NONE and (x_hit,
+ * y_hit) = (x1, y1).  k_unknown: the first step BEFORE k_hit whose cell is unknown — without a hit, among all K + 1 steps —
+ * or ICPMI_GC_NONE.  A ray without cells (below): [ICPMI_GC_NO_CELLS, 0, 0, ICPMI_GC_NONE].
+ *
+ * icpmi_grid_occupancy_planes packs a field into the two bit planes the casts read: `planes` (device, 16-byte aligned,
+ * icpmi_grid_occupancy_planes_bytes(ny, nx) bytes; 0 for a refused grid) holds uint32 [ny][wpr] for "occupied", then, from
+ * the next multiple of 256 bytes on, the same for "unknown"; wpr = ceil(nx / 32), bit x & 31 of word x >> 5 of row y is cell
+ * (y, x), and the pad bits of a row's last word are clear in both.  A caller may keep planes across calls, as a field is
+ * kept: a cast against kept planes reads the map as it was when they were made, whatever has been applied since, and
+ * ignores `field` and `occ_threshold`.
+ *
+ * icpmi_grid_cast_segments: segs device, int32 [n][4], 16-byte aligned; out_records device, int32 [n][ICPMI_GC_INTS], 16-byte
+ * aligned.  planes: what icpmi_grid_occupancy_planes wrote for this ny, nx — or NULL, and the call packs `field` with
+ * occ_threshold into `workspace` (device, 16-byte aligned, icpmi_grid_occupancy_planes_bytes(ny, nx) bytes) first.
+ *
+ * icpmi_grid_cast_rays: ray (p, b) of n_poses x n_beams leaves pose p — poses[2p .. 2p+1] = (px, py), pose_cs[2p .. 2p+1] =
+ * (ct, st) = (cos, sin) of its heading — along beam b, beam_cs[2b .. 2b+1] = (ca, sa) = (cos, sin) of the bearing in the
+ * sensor frame: the caller's own doubles, as icpmi_grid_match_batch takes its cos_sin (all device).  Float64, evaluated
+ * exactly as written, every operation rounded on its own (no fused multiply-add):
+ *   c = ct * ca - st * sa,  s = st * ca + ct * sa,  ex = px + reach * c,  ey = py + reach * s      (reach in metres)
+ *   x0 = cell(px, min_x), y0 = cell(py, min_y), x1 = cell(ex, min_x), y1 = cell(ey, min_y),
+ *   cell(w, min) = floor((w - min) / resolution), the IEEE quotient (world_to_cell, mapping.py:57-59), clamped to +-2^29.
+ * A ray one of whose four quotients is NaN or not below 1e300 in magnitude — a pose or an end point that is not finite —
+ * has no cells.  out_records: device, int32 [n_poses][n_beams][ICPMI_GC_INTS].  field, planes, workspace: as above.
+ *
+ * Refusals, on the host before any launch: ny or nx negative or above 2^29, ny * nx >= 2^31, n, n_poses or n_beams
+ * negative, a resolution or reach that is not positive and finite, a null or misaligned pointer that the call would use:
+ * ICPMI_ERR_ARG; n >= 2^29 or n_poses * n_beams >= 2^29: ICPMI_ERR_UNSUPPORTED; planes NULL and a workspace that is NULL,
+ * misaligned or short (for icpmi_grid_occupancy_planes: planes_bytes short): ICPMI_ERR_WORKSPACE.  No ray: no launch,
+ * ICPMI_OK.  ny * nx == 0: nothing is packed (no planes launch; planes and workspace may be NULL) and every ray that has
+ * cells gets the record of "no hit".  There is no limit on a ray's length: only the steps inside the grid can matter, and
+ * their range is found in closed form.
+ * Launches: gc_planes_kernel (only when the call packs: a lane per word of a plane, 2 bytes read and 2 bits written per
+ * cell) and gc_cast_kernel — workgroups of ICPMI_GC_THREADS threads, one lane per ray, a wave 64 consecutive beams of one
+ * pose.  A lane cuts its steps to the grid, walks them bit by bit with the words of a few steps loaded together, and leaves
+ * at its hit. */
+#define ICPMI_GC_INTS 4
+#define ICPMI_GC_K_HIT 0
+#define ICPMI_GC_X_HIT 1
+#define ICPMI_GC_Y_HIT 2
+#define ICPMI_GC_K_UNKNOWN 3
+#define ICPMI_GC_NONE (-1)        /* k_hit: nothing occupied on the ray; k_unknown: nothing unknown before the hit */
+#define ICPMI_GC_NO_CELLS (-2)    /* k_hit of a ray whose pose or end point has no cell */
+#define ICPMI_GC_THREADS 256
+size_t icpmi_grid_occupancy_planes_bytes(int32_t ny, int32_t nx);
+int icpmi_grid_occupancy_planes(const int16_t* field, int32_t ny, int32_t nx, int32_t occ_threshold, void* planes,
+                                size_t planes_bytes, void* stream);
+int icpmi_grid_cast_segments(const int16_t* field, const void* planes, int32_t ny, int32_t nx, int32_t occ_threshold,
+                             const int32_t* segs, int32_t n, int32_t* out_records, void* workspace, size_t workspace_bytes,
+                             void* stream);
+int icpmi_grid_cast_rays(const int16_t* field, const void* planes, int32_t ny, int32_t nx, int32_t occ_threshold,
+                         double min_x, double min_y, double resolution, const double* poses, const double* pose_cs,
+                         int32_t n_poses, const double* beam_cs, int32_t n_beams, double reach, int32_t* out_records,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* ── pose graph: PoseGraph2D.optimize, utilities/pose_graph.py:83-134 ──────────
  * Gauss-Newton on SE(2) over n_nodes poses [x, y, theta] (nodes: device, updated
  * in place) and n_edges constraints (i, j, z_ij [3], Omega [3][3] row-major).

@@ -1,0 +1,283 @@
+// gridcast.hip — the occupancy grid read back as ranges (include/icpmi.h: icpmi_grid_occupancy_planes, icpmi_grid_cast_segments,
+// icpmi_grid_cast_rays): along a ray, the first occupied cell and the first unknown cell before it.  The ray's cells are those
+// raycast.hip lowers (raywalk.hpp: one walker for the writer and the reader), with the end cell as one more step.
+//   gc_planes_kernel  packs the int16 field into two bit planes, occupied and unknown, one bit per cell: 2 bytes read and 2
+//                     bits written per cell, so the casts read 1/16 of the field's bytes — planes that stay in L2 where the
+//                     field does not;
+//   gc_cast_kernel    one lane per ray, a wave = 64 consecutive beams of one pose.  A lane cuts its steps to the grid in closed
+//                     form and walks what is left bit by bit, GC_CHUNK steps at a time with their words loaded together.
+// Measured and not kept (DESIGN.md has the times): walking an x-major ray run by run — the steps between two changes of y
+// as masked words of one row, __ffs / __clz for the hit — and a second, transposed pair of planes so that y-major rays walk
+// runs too.  Both lost to the plain walk at 4 096 poses x 360 beams: at a cell of 0.05 m most runs are a cell or two long,
+// and the lanes of a wave spend them in different branches.
+// After the end cells are formed everything is integer: a record is a function of the inputs alone.
+#include "raywalk.hpp"
+
+namespace icpmi {
+
+constexpr int GC_THREADS = ICPMI_GC_THREADS;
+#ifndef ICPMI_GC_CHUNK
+#define ICPMI_GC_CHUNK 4                   // (make variant: 1, 8 and 16 were measured against it)
+#endif
+constexpr int GC_CHUNK = ICPMI_GC_CHUNK;   // steps of a walk whose words are loaded together
+
+// The planes of an (ny, nx) grid, described once (the host sizes the buffer with it, the kernels find their words):
+//   occ  uint32 [ny][wpr]   bit x & 31 of word x >> 5 of row y: cell (y, x) is occupied
+//   unk  uint32 [ny][wpr]   the same for "unknown"
+// Rows are padded to whole words and the pad bits are clear, so a masked word never shows a cell outside the grid.
+struct GcPlanes {
+    int wpr;
+    size_t words, occ, unk, bytes;
+    __host__ __device__ GcPlanes(int ny, int nx) {
+        wpr = (nx + 31) / 32;
+        words = (size_t)ny * wpr;
+        const auto a256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
+        occ = 0;
+        unk = a256(words * sizeof(uint32_t));
+        bytes = unk + a256(words * sizeof(uint32_t));
+    }
+};
+
+struct GcPlaneArgs {
+    const short* q;
+    unsigned char* planes;
+    int ny, nx, threshold;
+};
+
+// The 8 flat cells from lo (a multiple of 8) on: bit j of occ says q[lo + j] >= threshold, of unk q[lo + j] == 0.  A group
+// inside the array is one aligned 16-byte load (gridfield.hip's rule); the array's last, partial group goes cell by cell,
+// and a cell at or behind `total` has no bits.
+__device__ __forceinline__ void gc_group_bits(const short* __restrict__ q, long long lo, long long total, int threshold,
+                                              unsigned& occ, unsigned& unk) {
+    occ = unk = 0;
+    if (lo + 8 <= total) {
+        const uint4 v = *reinterpret_cast<const uint4*>(q + lo);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int c = (int)(short)((j & 1) ? w[j >> 1] >> 16 : w[j >> 1] & 0xffffu);
+            occ |= (unsigned)(c >= threshold) << j;
+            unk |= (unsigned)(c == 0) << j;
+        }
+    } else {
+        for (int j = 0; j < 8 && lo + j < total; ++j) {
+            const int c = q[lo + j];
+            occ |= (unsigned)(c >= threshold) << j;
+            unk |= (unsigned)(c == 0) << j;
+        }
+    }
+}
+
+// One lane per word of the planes: the 32 cells of row y from column 32 w on are 64 bytes of the field that start at any
+// int16, so the lane loads the (at most five) aligned groups of 8 that hold them, forms their bits as one 40-bit mask and
+// shifts the row's own cells down; what lies behind the row's end — the next row's cells, or nothing — is masked away.
+__global__ __launch_bounds__(GC_THREADS) void gc_planes_kernel(GcPlaneArgs a) {
+    const GcPlanes L(a.ny, a.nx);
+    const size_t t = (size_t)blockIdx.x * GC_THREADS + threadIdx.x;
+    if (t >= L.words) return;
+    const unsigned y = (unsigned)t / (unsigned)L.wpr, w = (unsigned)t - y * (unsigned)L.wpr;     // words < 2^31
+    const int x0 = (int)w * 32, n = min(32, a.nx - x0);
+    const long long total = (long long)a.ny * a.nx, f0 = (long long)y * a.nx + x0, lo = f0 & ~7ll;
+    const int s = (int)(f0 - lo);
+    unsigned long long occ = 0, unk = 0;
+#pragma unroll
+    for (int g = 0; g < 5; ++g) {
+        unsigned o = 0, u = 0;
+        if (g * 8 < s + n) gc_group_bits(a.q, lo + 8 * g, total, a.threshold, o, u);
+        occ |= (unsigned long long)o << (8 * g);
+        unk |= (unsigned long long)u << (8 * g);
+    }
+    const uint32_t mask = n == 32 ? ~0u : (1u << n) - 1u;
+    reinterpret_cast<uint32_t*>(a.planes + L.occ)[t] = (uint32_t)(occ >> s) & mask;
+    reinterpret_cast<uint32_t*>(a.planes + L.unk)[t] = (uint32_t)(unk >> s) & mask;
+}
+
+
+struct GcArgs {
+    const unsigned char* planes;
+    int ny, nx;
+    const int32_t* segs;      // [n_beams][4] cells: the segment entry (n_poses = 1); null: the ray entry
+    const double* poses;      // [n_poses][2]
+    const double* pose_cs;    // [n_poses][2]
+    const double* beam_cs;    // [n_beams][2]
+    double reach, min_x, min_y, res;
+    int n_poses, n_beams, wpp;   // wpp: waves per pose — a wave never spans two poses
+    int4* out;
+};
+
+// The record of the segment (x0, y0) -> (x1, y1) over the planes
+__device__ __forceinline__ int4 gc_walk(const unsigned char* __restrict__ planes, const GcPlanes& L, int ny, int nx,
+                                        int x0, int y0, int x1, int y1) {
+    Ray r;
+    r.init(x0, y0, x1, y1);
+    r.n = r.dmaj + 1;                                              // steps 0 .. K: the end cell is a step of the cast
+    // only the steps inside the grid can matter: a range [klo, khi), in closed form
+    int klo = 0, khi = 0;
+    if (r.xmajor) { r.clip_major(0, nx, klo, khi); r.clip_minor(0, ny, klo, khi); }
+    else { r.clip_major(0, ny, klo, khi); r.clip_minor(0, nx, klo, khi); }
+    int k_hit = ICPMI_GC_NONE, k_unk = ICPMI_GC_NONE, xh = x1, yh = y1;
+    if (klo >= khi) return make_int4(k_hit, xh, yh, k_unk);
+    if (r.dmaj > 0) r.seek(klo);                                   // (K = 0: the origin cell alone, offset 0)
+    const uint32_t* occ = reinterpret_cast<const uint32_t*>(planes + L.occ);
+    const uint32_t* unk = reinterpret_cast<const uint32_t*>(planes + L.unk);
+    // Bit by bit, GC_CHUNK steps at a time: their words are asked for together and looked at in order, so the chain of
+    // dependent loads of a ray is a GC_CHUNK-th of its steps (a step past the range repeats the chunk's first word, unused).
+    // A lane leaves at its hit; a wave when all of its lanes have.
+    for (int k0 = klo; k0 < khi && k_hit < 0; k0 += GC_CHUNK) {
+        int xs[GC_CHUNK], ys[GC_CHUNK];
+        uint32_t wi[GC_CHUNK], o[GC_CHUNK], u[GC_CHUNK];           // (ny * wpr < 2^31 words)
+        const bool want_unk = k_unk < 0;
+#pragma unroll
+        for (int j = 0; j < GC_CHUNK; ++j) {
+            r.cell(k0 + j, xs[j], ys[j]);
+            wi[j] = k0 + j < khi ? (uint32_t)ys[j] * (uint32_t)L.wpr + (uint32_t)(xs[j] >> 5) : wi[0];
+            r.step();
+        }
+#pragma unroll
+        for (int j = 0; j < GC_CHUNK; ++j) o[j] = occ[wi[j]];
+#pragma unroll
+        for (int j = 0; j < GC_CHUNK; ++j) u[j] = want_unk ? unk[wi[j]] : 0u;
+#pragma unroll
+        for (int j = 0; j < GC_CHUNK; ++j) {
+            const uint32_t bit = 1u << (xs[j] & 31);
+            const bool live = k0 + j < khi && k_hit < 0;
+            if (live && (o[j] & bit)) { k_hit = k0 + j; xh = xs[j]; yh = ys[j]; }
+            else if (live && k_unk < 0 && (u[j] & bit)) k_unk = k0 + j;          // (only BEFORE the hit: a hit ends `live`)
+        }
+    }
+    return make_int4(k_hit, xh, yh, k_unk);
+}
+
+__global__ __launch_bounds__(GC_THREADS) void gc_cast_kernel(GcArgs a) {
+    const unsigned gw = (unsigned)(((unsigned long long)blockIdx.x * GC_THREADS + threadIdx.x) >> 6);   // < 2^29 waves
+    const unsigned pose = gw / (unsigned)a.wpp;
+    const int beam = (int)(gw - pose * (unsigned)a.wpp) * ICPMI_WAVE + lane_id();
+    if (pose >= (unsigned)a.n_poses || beam >= a.n_beams) return;
+    const size_t ray = (size_t)pose * a.n_beams + beam;
+    int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+    bool cells = true;
+    if (a.segs) {
+        const int4 s = reinterpret_cast<const int4*>(a.segs)[ray];
+        const auto clamped = [](int v) { return min(max(v, -RC_COORD_MAX), RC_COORD_MAX); };
+        x0 = clamped(s.x); y0 = clamped(s.y); x1 = clamped(s.z); y1 = clamped(s.w);
+    } else {
+        // as include/icpmi.h states it: every operation rounded on its own (no contraction)
+        const double px = a.poses[2 * (size_t)pose], py = a.poses[2 * (size_t)pose + 1];
+        const double ct = a.pose_cs[2 * (size_t)pose], st = a.pose_cs[2 * (size_t)pose + 1];
+        const double ca = a.beam_cs[2 * (size_t)beam], sa = a.beam_cs[2 * (size_t)beam + 1];
+        const double c = ct * ca - st * sa, s = st * ca + ct * sa;
+        const double ex = px + a.reach * c, ey = py + a.reach * s;
+        const bool ox = world_to_cell(px, a.min_x, a.res, x0), oy = world_to_cell(py, a.min_y, a.res, y0);
+        const bool hx = world_to_cell(ex, a.min_x, a.res, x1), hy = world_to_cell(ey, a.min_y, a.res, y1);
+        cells = ox && oy && hx && hy;
+    }
+    int4 rec = make_int4(ICPMI_GC_NO_CELLS, 0, 0, ICPMI_GC_NONE);
+    if (cells) {
+        const GcPlanes L(a.ny, a.nx);
+        rec = gc_walk(a.planes, L, a.ny, a.nx, x0, y0, x1, y1);
+    }
+    a.out[ray] = rec;                                              // one 16-byte store
+}
+
+// ── host: the plan, the entries ──────────────────────────────────────────────
+// What a call starts, decided as a whole and without a HIP call
+struct GcPlan {
+    int rc;                   // ICPMI_OK, or why nothing is launched
+    unsigned plane_blocks;    // gc_planes_kernel: a lane per word of a plane; 0: nothing to pack
+    unsigned cast_blocks;     // gc_cast_kernel: whole waves per pose; 0: no ray
+    int wpp;
+    size_t plane_bytes;       // GcPlanes of the grid
+};
+static GcPlan plan_cast(int ny, int nx, long long n_poses, long long n_beams) {
+    GcPlan p{ICPMI_OK, 0, 0, 0, 0};
+    if (ny < 0 || nx < 0 || ny > RC_COORD_MAX || nx > RC_COORD_MAX || (long long)ny * nx >= (1ll << 31) || n_poses < 0 || n_beams < 0) {
+        p.rc = ICPMI_ERR_ARG;
+        return p;
+    }
+    if (n_poses * n_beams >= (1ll << 29)) { p.rc = ICPMI_ERR_UNSUPPORTED; return p; }
+    const GcPlanes L(ny, nx);
+    p.plane_bytes = L.bytes;
+    p.plane_blocks = (unsigned)((L.words + GC_THREADS - 1) / GC_THREADS);
+    p.wpp = (int)((n_beams + ICPMI_WAVE - 1) / ICPMI_WAVE);
+    p.cast_blocks = (unsigned)((n_poses * p.wpp * ICPMI_WAVE + GC_THREADS - 1) / GC_THREADS);
+    return p;
+}
+
+static bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
+
+static int launch_planes(const GcPlan& plan, const int16_t* field, int ny, int nx, int threshold, void* planes, hipStream_t st) {
+    if (!plan.plane_blocks) return ICPMI_OK;
+    const GcPlaneArgs a{(const short*)field, (unsigned char*)planes, ny, nx, threshold};
+    gc_planes_kernel<<<plan.plane_blocks, GC_THREADS, 0, st>>>(a);
+    ICPMI_LAUNCH_CHECK();
+    return ICPMI_OK;
+}
+
+// The part the two cast entries share: the planes are the caller's, or packed from the field into the workspace first
+static int cast(const GcPlan& plan, GcArgs a, const int16_t* field, const void* planes, int threshold, int32_t* out,
+                void* workspace, size_t workspace_bytes, hipStream_t st) {
+    if (!plan.cast_blocks) return ICPMI_OK;
+    if (!out || misaligned16(out)) return ICPMI_ERR_ARG;
+    if (!planes && plan.plane_blocks) {
+        if (!field || misaligned16(field)) return ICPMI_ERR_ARG;
+        if (!workspace || misaligned16(workspace) || workspace_bytes < plan.plane_bytes) return ICPMI_ERR_WORKSPACE;
+        const int rc = launch_planes(plan, field, a.ny, a.nx, threshold, workspace, st);
+        if (rc != ICPMI_OK) return rc;
+        planes = workspace;
+    }
+    if (planes && misaligned16(planes)) return ICPMI_ERR_ARG;
+    a.planes = (const unsigned char*)planes;                       // (null only for an empty grid: no step is inside it)
+    a.wpp = plan.wpp;
+    a.out = reinterpret_cast<int4*>(out);
+    gc_cast_kernel<<<plan.cast_blocks, GC_THREADS, 0, st>>>(a);
+    ICPMI_LAUNCH_CHECK();
+    return ICPMI_OK;
+}
+
+}  // namespace icpmi
+
+extern "C" size_t icpmi_grid_occupancy_planes_bytes(int32_t ny, int32_t nx) {
+    using namespace icpmi;
+    const GcPlan plan = plan_cast(ny, nx, 0, 0);
+    return plan.rc == ICPMI_OK ? plan.plane_bytes : 0;
+}
+
+extern "C" int icpmi_grid_occupancy_planes(const int16_t* field, int32_t ny, int32_t nx, int32_t occ_threshold, void* planes,
+                                           size_t planes_bytes, void* stream) {
+    using namespace icpmi;
+    const GcPlan plan = plan_cast(ny, nx, 0, 0);
+    if (plan.rc != ICPMI_OK) return plan.rc;
+    if (!plan.plane_blocks) return ICPMI_OK;
+    if (!field || !planes || misaligned16(field) || misaligned16(planes)) return ICPMI_ERR_ARG;
+    if (planes_bytes < plan.plane_bytes) return ICPMI_ERR_WORKSPACE;
+    return launch_planes(plan, field, ny, nx, occ_threshold, planes, (hipStream_t)stream);
+}
+
+extern "C" int icpmi_grid_cast_segments(const int16_t* field, const void* planes, int32_t ny, int32_t nx, int32_t occ_threshold,
+                                        const int32_t* segs, int32_t n, int32_t* out_records, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+    using namespace icpmi;
+    const GcPlan plan = plan_cast(ny, nx, 1, n);
+    if (plan.rc != ICPMI_OK) return plan.rc;
+    if (n > 0 && (!segs || misaligned16(segs))) return ICPMI_ERR_ARG;
+    GcArgs a{};
+    a.ny = ny; a.nx = nx; a.segs = segs; a.n_poses = 1; a.n_beams = n;
+    return cast(plan, a, field, planes, occ_threshold, out_records, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int icpmi_grid_cast_rays(const int16_t* field, const void* planes, int32_t ny, int32_t nx, int32_t occ_threshold,
+                                    double min_x, double min_y, double resolution, const double* poses, const double* pose_cs,
+                                    int32_t n_poses, const double* beam_cs, int32_t n_beams, double reach,
+                                    int32_t* out_records, void* workspace, size_t workspace_bytes, void* stream) {
+    using namespace icpmi;
+    const GcPlan plan = plan_cast(ny, nx, n_poses, n_beams);
+    if (plan.rc != ICPMI_OK) return plan.rc;
+    const double inf = __builtin_inf();
+    if (!(resolution > 0.0 && resolution < inf) || !(reach > 0.0 && reach < inf)) return ICPMI_ERR_ARG;
+    if (plan.cast_blocks && (!poses || !pose_cs || !beam_cs)) return ICPMI_ERR_ARG;
+    GcArgs a{};
+    a.ny = ny; a.nx = nx; a.poses = poses; a.pose_cs = pose_cs; a.beam_cs = beam_cs;
+    a.reach = reach; a.min_x = min_x; a.min_y = min_y; a.res = resolution;
+    a.n_poses = n_poses; a.n_beams = n_beams;
+    return cast(plan, a, field, planes, occ_threshold, out_records, workspace, workspace_bytes, (hipStream_t)stream);
+}

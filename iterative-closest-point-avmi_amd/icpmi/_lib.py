@@ -45,6 +45,8 @@ GMOM_INTS, GMOM_W, GMOM_A, GMOM_J, GMOM_I, GMOM_AA, GMOM_AJ, GMOM_AI, GMOM_JJ, G
 GMOM_WEIGHT_BITS, GMOM_MAX_HALF_STEP = 20, 32767
 # icpmi_grid_likelihood_field (LF_*: the largest radius in cells, the output tile of one workgroup)
 LF_MAX_RADIUS, LF_TILE_X, LF_TILE_Y = 64, 128, 64
+# icpmi_grid_cast_segments / icpmi_grid_cast_rays: the slots of a ray's int32 record and its two marks (GC_*)
+GC_INTS, GC_K_HIT, GC_X_HIT, GC_Y_HIT, GC_K_UNKNOWN, GC_NONE, GC_NO_CELLS, GC_THREADS = 4, 0, 1, 2, 3, -1, -2, 256
 # icpmi_pose_graph_optimize: its statuses (PG_ST_*) and the slots of its info record (PGINFO_*: three values, then PHASES clocks)
 PG_ST_NOTHING, PG_ST_CONVERGED, PG_ST_MAXITER, PG_ST_SINGULAR, PG_ST_REFUSED = 0, 1, 2, 3, 4
 PGINFO_DOUBLES, PGINFO_ITERATIONS, PGINFO_STATUS, PGINFO_STEP, PGINFO_PHASE_US, PGINFO_PHASES = 10, 0, 1, 2, 3, 7
@@ -200,6 +202,13 @@ _SIGS = {
     "icpmi_grid_likelihood_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
     "icpmi_grid_likelihood_field": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "icpmi_grid_occupancy_planes_bytes": (C.c_size_t, [C.c_int32] * 2),
+    "icpmi_grid_occupancy_planes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "icpmi_grid_cast_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                           C.c_void_p, C.c_size_t, C.c_void_p]),
+    "icpmi_grid_cast_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                       C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]),
     "icpmi_pose_graph_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
     "icpmi_pose_graph_optimize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                             C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_size_t,

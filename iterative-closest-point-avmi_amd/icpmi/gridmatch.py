@@ -5,7 +5,10 @@ a max-pooled field, pruned against a seed score, the exhaustive winner returned.
 volume of a match once more: the integer-weighted moments of the candidates about the winner, from which
 ``gaussian_of_moments`` forms a sub-cell pose and a covariance on the host.  ``icpmi_grid_likelihood_field`` makes the field
 the matchers read while the map's walls are one cell wide: the exact truncated distance to the nearest occupied cell
-(``distance_field``), mapped to a score through a table (``likelihood_table``, ``likelihood_field``).
+(``distance_field``), mapped to a score through a table (``likelihood_table``, ``likelihood_field``).  The cast reads the
+same field back as ranges (``icpmi_grid_occupancy_planes``, ``icpmi_grid_cast_segments``, ``icpmi_grid_cast_rays``:
+``occupancy_planes``, ``cast_segments``, ``cast_rays``): along the cells the map's update would lower, the first occupied
+cell and the first unknown cell before it.
 
 The reference registers a scan against a cloud only (slam.py:53-98, 111-183); this reads the map ``utilities.mapping``
 builds.  The log-odds are quantised to int16 and a candidate's score is the integer sum of the field under the scan's
@@ -123,6 +126,139 @@ def likelihood_field(field, threshold, radius, table, keep_free=True, out=None, 
                                         None if d2_out is None else _ptr(d2_out), _ptr(out), _ptr(ws), ws.numel(), _stream()),
           "grid_likelihood_field")
     return out
+
+
+class OccupancyPlanes:
+    """What ``occupancy_planes`` returns and the casts take instead of a field: ``buf``, the uint8 device buffer of the two
+    bit planes (occupied, unknown; include/icpmi.h has the layout), with the grid's ``ny``, ``nx`` and the ``threshold`` they
+    were packed with.  Kept by the caller, they show the map as it was when they were made."""
+
+    def __init__(self, buf, ny, nx, threshold):
+        self.buf, self.ny, self.nx, self.threshold = buf, int(ny), int(nx), int(threshold)
+
+
+def _cast_grid(ny, nx):
+    if max(ny, nx) > 2 ** 29 or ny * nx >= 2 ** 31:
+        raise ValueError(f"a grid of {ny} x {nx} cells cannot be cast: at most 2^29 per axis and fewer than 2^31 cells")
+
+
+def occupancy_planes(field, threshold):
+    """``icpmi_grid_occupancy_planes`` of an int16 (ny, nx) device field: one bit per cell for "occupied" — ``field >=
+    threshold`` — and one for "unknown" — ``field == 0`` -> ``OccupancyPlanes``, for ``cast_segments`` and ``cast_rays``."""
+    if not isinstance(field, torch.Tensor) or field.dtype != torch.int16 or field.dim() != 2 or not field.is_contiguous():
+        raise ValueError("field must be a contiguous int16 (ny, nx) device tensor")
+    ny, nx = field.shape
+    _cast_grid(ny, nx)
+    L = _lib.lib()
+    buf = torch.empty(L.icpmi_grid_occupancy_planes_bytes(ny, nx), dtype=torch.uint8, device=field.device)
+    check(L.icpmi_grid_occupancy_planes(_ptr(field), ny, nx, int(threshold), _ptr(buf), buf.numel(), _stream()), "grid_occupancy_planes")
+    return OccupancyPlanes(buf, ny, nx, threshold)
+
+
+def _cast_source(field_or_planes, threshold):
+    """-> (field, planes buffer, workspace, ny, nx, threshold, device) as the cast entries take them: kept planes as they
+    are, a field with a workspace the entry packs it into."""
+    if isinstance(field_or_planes, OccupancyPlanes):
+        p = field_or_planes
+        return None, p.buf, None, p.ny, p.nx, p.threshold, p.buf.device
+    f = field_or_planes
+    if not isinstance(f, torch.Tensor) or f.dtype != torch.int16 or f.dim() != 2 or not f.is_contiguous():
+        raise ValueError("the map must be a contiguous int16 (ny, nx) device field or the OccupancyPlanes of one")
+    ny, nx = f.shape
+    _cast_grid(ny, nx)
+    ws = torch.empty(_lib.lib().icpmi_grid_occupancy_planes_bytes(ny, nx), dtype=torch.uint8, device=f.device)
+    return f, None, ws, ny, nx, int(threshold), f.device
+
+
+def _cast_out(out, shape, dev):
+    if out is None:
+        return torch.empty(shape, dtype=torch.int32, device=dev)
+    if out.dtype != torch.int32 or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"out must be a contiguous int32 tensor of shape {tuple(shape)} on the map's device")
+    return out
+
+
+def _rows_f64(rows, cols, what, dev, n=None):
+    t = rows if isinstance(rows, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(rows, dtype=np.float64).reshape(-1, cols)))
+    if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != cols or (n is not None and t.shape[0] != n):
+        raise ValueError(f"{what} must be float64 rows of {cols}" + (f", {n} of them" if n is not None else ""))
+    return t.to(dev).contiguous()
+
+
+def cast_segments(field_or_planes, threshold, segs, out=None):
+    """``icpmi_grid_cast_segments``: the (n, 4) int32 cell segments (x0, y0, x1, y1), each coordinate within +-2^29, walked over
+    an int16 (ny, nx) device field (occupied: ``field >= threshold``) or over kept ``OccupancyPlanes`` (``threshold`` is then
+    the planes' own) -> the (n, GC_INTS) int32 device tensor of records [k_hit, x_hit, y_hit, k_unknown] (``out`` when given).
+    Enqueues and does not synchronise."""
+    field, planes, ws, ny, nx, thr, dev = _cast_source(field_or_planes, threshold)
+    if not isinstance(segs, torch.Tensor):
+        host = np.asarray(segs)
+        if host.dtype.kind not in "iu" or host.ndim != 2 or host.shape[1] != 4:
+            raise ValueError("segs must be (n, 4) integer rows (x0, y0, x1, y1)")
+        if host.size and np.abs(host.astype(np.int64)).max() > 2 ** 29:
+            raise ValueError("a segment's coordinates must lie within +-2^29 cells")
+        segs = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32))
+    if segs.dtype != torch.int32 or segs.dim() != 2 or segs.shape[1] != 4:
+        raise ValueError("segs must be (n, 4) int32 rows (x0, y0, x1, y1)")
+    n = segs.shape[0]
+    if n >= 2 ** 29:
+        raise ValueError(f"{n} segments: fewer than 2^29 fit one call")
+    segs = segs.to(dev).contiguous()
+    out = _cast_out(out, (n, _lib.GC_INTS), dev)
+    check(_lib.lib().icpmi_grid_cast_segments(_ptr(field), _ptr(planes), ny, nx, thr, _ptr(segs), n, _ptr(out), _ptr(ws),
+                                              0 if ws is None else ws.numel(), _stream()), "grid_cast_segments")
+    return out
+
+
+def cast_rays(field_or_planes, threshold, min_x, min_y, resolution, poses_xy, pose_cs, beam_cs, reach, out=None):
+    """``icpmi_grid_cast_rays``: from every pose — ``poses_xy`` (P, 2) in metres, ``pose_cs`` (P, 2) the (cos, sin) of its
+    heading — along every beam — ``beam_cs`` (A, 2), the (cos, sin) of its bearing in the sensor frame — to ``reach`` metres,
+    over the map as ``cast_segments`` takes it -> the (P, A, GC_INTS) int32 device tensor of records (``out`` when given).
+    The rows are the caller's own float64 (arrays or device tensors).  Enqueues and does not synchronise."""
+    field, planes, ws, ny, nx, thr, dev = _cast_source(field_or_planes, threshold)
+    for name, v in (("resolution", resolution), ("reach", reach)):
+        if not (np.isfinite(v) and v > 0.0):
+            raise ValueError(f"{name} must be positive and finite, got {v}")
+    xy = _rows_f64(poses_xy, 2, "poses_xy", dev)
+    P = xy.shape[0]
+    pcs, bcs = _rows_f64(pose_cs, 2, "pose_cs", dev, P), _rows_f64(beam_cs, 2, "beam_cs", dev)
+    A = bcs.shape[0]
+    if P * A >= 2 ** 29:
+        raise ValueError(f"{P} poses x {A} beams: fewer than 2^29 rays fit one call")
+    out = _cast_out(out, (P, A, _lib.GC_INTS), dev)
+    check(_lib.lib().icpmi_grid_cast_rays(_ptr(field), _ptr(planes), ny, nx, thr, float(min_x), float(min_y), float(resolution),
+                                          _ptr(xy), _ptr(pcs), P, _ptr(bcs), A, float(reach), _ptr(out), _ptr(ws),
+                                          0 if ws is None else ws.numel(), _stream()), "grid_cast_rays")
+    return out
+
+
+def ray_end_cells(min_x, min_y, resolution, poses_xy, pose_cs, beam_cs, reach):
+    """The origin and end cells ``icpmi_grid_cast_rays`` forms, in NumPy on the host with the same float64 operations ->
+    (segments (P, A, 4) int64 [x0, y0, x1, y1], clamped to +-2^29; has_cells (P, A) bool)."""
+    xy, pcs, bcs = (np.asarray(v, dtype=np.float64).reshape(-1, 2) for v in (poses_xy, pose_cs, beam_cs))
+    px, py, ct, st = xy[:, None, 0], xy[:, None, 1], pcs[:, None, 0], pcs[:, None, 1]
+    ca, sa = bcs[None, :, 0], bcs[None, :, 1]
+    with np.errstate(invalid="ignore", over="ignore"):
+        c, s = ct * ca - st * sa, st * ca + ct * sa
+        ex, ey = px + reach * c, py + reach * s
+        f = [np.floor((np.broadcast_to(w, ex.shape) - m) / resolution) for w, m in ((px, min_x), (py, min_y), (ex, min_x), (ey, min_y))]
+        ok = np.all([np.abs(v) < 1e300 for v in f], axis=0)
+        seg = np.stack([np.clip(np.where(ok, v, 0.0), -2.0 ** 29, 2.0 ** 29).astype(np.int64) for v in f], axis=-1)
+    return seg, ok
+
+
+def step_cells(segs, k):
+    """The cell of step ``k`` of every segment of ``segs`` (..., 4) — include/icpmi.h's closed form, in NumPy int64 ->
+    (x, y); ``k`` outside [0, K] gives the cell the formula gives."""
+    segs, k = np.asarray(segs, dtype=np.int64), np.asarray(k, dtype=np.int64)
+    x0, y0, x1, y1 = (segs[..., i] for i in range(4))
+    dx, dy = np.abs(x1 - x0), np.abs(y1 - y0)
+    sx, sy = np.where(x0 < x1, 1, -1), np.where(y0 < y1, 1, -1)
+    xmajor = dx >= dy
+    dmaj, dmin = np.where(xmajor, dx, dy), np.where(xmajor, dy, dx)
+    q = (2 * k * dmin + dmaj - 1) // np.maximum(2 * dmaj, 1)
+    q = np.where(dmaj > 0, q, 0)
+    return np.where(xmajor, x0 + sx * k, x0 + sx * q), np.where(xmajor, y0 + sy * q, y0 + sy * k)
 
 
 def angle_grid(theta, angular_window, angular_step):

@@ -407,6 +407,63 @@ class OccupancyGrid2D:
         _, _, score, info = self._match_set(cs, np.zeros(len(xyt), dtype=np.int32), xyt, 0.0, 0.0, None, field).unpack()
         return score, info
 
+    # ── the map read back as ranges (icpmi.gridmatch.cast_rays; no counterpart in the reference) ─────────────────────
+    def occupancy_planes(self, occupied_log_odds=0.5, field=None):
+        """-> (planes, k): the map as the two bit planes the cast reads — a cell is occupied where its log-odds are >=
+        ``occupied_log_odds`` in ``field`` (a ``(tensor, k)`` of ``score_field()`` or ``likelihood_field()``; None: the map as
+        it is now), unknown where its field value is 0 — for ``planes=`` of ``cast_scans``.  Built anew at every call; a cast
+        against kept planes reads the map as it was when they were made, whatever has been applied since."""
+        from icpmi import gridmatch
+        q, k = self.score_field() if field is None else field
+        return gridmatch.occupancy_planes(q, int(np.rint(occupied_log_odds * 2.0 ** k))), k
+
+    def cast_scans(self, poses, angles, max_range, occupied_log_odds=0.5, field=None, planes=None):
+        """The scan this map predicts at every pose of ``poses`` ((P, 3) rows [x, y, theta] or 3 x 3 matrices): along each
+        sensor-frame bearing of ``angles`` (radians, A of them) up to ``max_range`` metres, the first occupied cell — log-odds
+        >= ``occupied_log_odds`` — among exactly the cells ``update_scan`` would lower for a hit at that range, end cell
+        included, and the first unknown cell before it.  One launch for all P x A rays.  ``field``: a ``(tensor, k)`` to read
+        instead of the map as it is now; ``planes``: what ``occupancy_planes()`` returned (``occupied_log_odds`` is then the
+        planes' own).  -> (ranges (P, A) float64, info).  ``ranges``: the distance from the pose to the CENTRE of the hit cell,
+        hypot((x_hit + 0.5) * resolution + min_x - x, (y_hit + 0.5) * resolution + min_y - y); inf where nothing was hit, nan
+        where the ray has no cells (a pose or end point that is not finite).  info: ``k_hit`` (P, A) (the step of the hit; -1
+        none, -2 no cells), ``cells`` (P, A, 2) the hit cell (x, y) (the end cell without a hit), ``k_unknown`` (P, A) (-1: none),
+        ``unknown_range`` (the same distance to the first unknown cell, inf without one) and ``shift_bits``."""
+        from icpmi import gridmatch
+        if field is not None and planes is not None:
+            raise ValueError("pass field= or planes=, not both")
+        xyt = self._xytheta(poses)
+        ang = np.asarray(angles, dtype=np.float64).reshape(-1)
+        if planes is not None:
+            src, k = planes
+            if not isinstance(src, gridmatch.OccupancyPlanes) or (src.ny, src.nx) != (self.ny, self.nx):
+                raise ValueError("planes must be what occupancy_planes() returned for this grid")
+            threshold = src.threshold
+        else:
+            src, k = self.score_field() if field is None else field
+            if tuple(src.shape) != (self.ny, self.nx):
+                raise ValueError("field must be the int16 (ny, nx) tensor score_field() returned for this grid")
+            threshold = int(np.rint(occupied_log_odds * 2.0 ** k))
+        pose_cs = np.stack([np.cos(xyt[:, 2]), np.sin(xyt[:, 2])], axis=1)
+        beam_cs = np.stack([np.cos(ang), np.sin(ang)], axis=1)
+        rec = gridmatch.cast_rays(src, threshold, self.min_x, self.min_y, self.resolution, xyt[:, :2], pose_cs, beam_cs, max_range)
+        rec = rec.cpu().numpy().astype(np.int64)
+        k_hit, k_unknown = rec[..., _lib.GC_K_HIT], rec[..., _lib.GC_K_UNKNOWN]
+        cells = rec[..., _lib.GC_X_HIT:_lib.GC_Y_HIT + 1]
+        segs, _ = gridmatch.ray_end_cells(self.min_x, self.min_y, self.resolution, xyt[:, :2], pose_cs, beam_cs, float(max_range))
+        ux, uy = gridmatch.step_cells(segs, np.maximum(k_unknown, 0))
+        px, py = xyt[:, None, 0], xyt[:, None, 1]
+        centre = lambda cx, cy: np.hypot((cx + 0.5) * self.resolution + self.min_x - px, (cy + 0.5) * self.resolution + self.min_y - py)  # noqa: E731
+        with np.errstate(invalid="ignore", over="ignore"):
+            ranges = np.where(k_hit >= 0, centre(cells[..., 0], cells[..., 1]), np.where(k_hit == _lib.GC_NONE, np.inf, np.nan))
+            unknown_range = np.where(k_unknown >= 0, centre(ux, uy), np.inf)
+        return ranges, {"k_hit": k_hit, "cells": cells, "k_unknown": k_unknown, "unknown_range": unknown_range, "shift_bits": k}
+
+    def cast_scan(self, pose, angles, max_range, occupied_log_odds=0.5, field=None, planes=None):
+        """``cast_scans`` from one pose ([x, y, theta] or a 3 x 3 matrix) -> (ranges (A,), info) with (A, ...) entries."""
+        p = np.asarray(pose, dtype=np.float64)
+        ranges, info = self.cast_scans(p[None] if p.ndim == 2 else p.reshape(1, 3), angles, max_range, occupied_log_odds, field, planes)
+        return ranges[0], {k: (v[0] if isinstance(v, np.ndarray) else v) for k, v in info.items()}
+
     def match_history(self, history, ids, predicted_poses, linear_window=0.6, angular_window=12.0, angular_step=1.0, voxel_size=None,
                       field=None, half_log_odds=None):
         """``match_scans`` of scans resident in an ``icpmi.ScanHistory``, by id: the raw rows are read where they are and no
