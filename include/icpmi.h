@@ -989,6 +989,88 @@ int icpmi_grid_cast_rays(const int16_t* field, const void* planes, int32_t ny, i
                          int32_t n_poses, const double* beam_cs, int32_t n_beams, double reach, int32_t* out_records,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the check: measured scans held against the map along their beams (no counterpart in the reference) ----------------
+ * The matchers score the map under a scan's end points; the cast reads the map back as ranges.  icpmi_grid_check_batch asks
+ * what a loop-closure gate or a particle filter needs: does this scan, at this pose, contradict the free space and the
+ * walls the map already holds?  Every measured beam is walked from the pose's cell to the cell of its own hit — exactly the
+ * cells icpmi_grid_update_scans would touch for that beam — and classified; the classes are counted per pair on the device
+ * and eight integers per pair come back.  After the cells are formed everything is integer, and the counts are sums of int32
+ * atomics of at most ICPMI_GM_MAX_ROWS rows: a record is a function of the inputs alone, to the bit.
+ *
+ * The map: field + occ_threshold + workspace, or kept planes, exactly as icpmi_grid_cast_segments takes them (planes given:
+ * field, occ_threshold and workspace are ignored; planes NULL: the call packs `field` into `workspace` first).
+ * The scans: a cloud set and pairs exactly as icpmi_grid_match_batch takes them — pts (here 16-byte aligned: a row is one
+ * load), off_dev, off_host, cnt_dev (NULL = every cloud full), n_clouds, pair_cloud, pair_cloud_host, n_pairs, pair_t — and
+ * cos_sin [n_pairs][2], one rotation (cos, sin) per pair.  int32 tolerance >= 0, in steps.
+ *
+ * Cells of a row.  Row (x, y) of pair b has its end cell (cx, cy) by icpmi_grid_match_batch's expressions, float64, every
+ * operation rounded on its own:  wx = (c * x - s * y) + tx,  wy = (s * x + c * y) + ty,  cx = floor((wx - min_x) /
+ * resolution),  cy = floor((wy - min_y) / resolution).  The row has no cell if wx or wy is not finite or if cx or cy lies
+ * outside [-2^29, 2^29].  The origin cell (ox, oy) comes from (tx, ty) by the same rule; if the origin has no cell, no row of
+ * that pair has cells.
+ *
+ * Classes of a row.  Let [k_hit, ., ., k_unknown] be the cast's record of the segment (ox, oy) -> (cx, cy): steps 0 .. K, the
+ * end cell included, K = max(|cx - ox|, |cy - oy|).  A row with cells falls in exactly one class:
+ *   ICPMI_GK_CLASS_CONFIRMED   k_hit >= 0 and k_hit >= K - tolerance: the beam ends where the map has a wall;
+ *   ICPMI_GK_CLASS_VIOLATED    k_hit >= 0 and k_hit <  K - tolerance: it returned from behind something the map holds occupied;
+ *   ICPMI_GK_CLASS_IN_FREE     no hit, the end cell inside the grid with its unknown bit clear: a return from observed free space;
+ *   ICPMI_GK_CLASS_UNEXPLORED  no hit, the end cell outside the grid or unknown.
+ * (K <= 2^30 and tolerance <= 2^30: K - tolerance does not overflow.)  The tolerance exists because a noisy return lands a
+ * cell behind the first occupied layer of a mapped wall.
+ *
+ * out_records: device, int32 [n_pairs][ICPMI_GK_INTS], slots ICPMI_GK_REC_*: STATUS, ROWS (the rows with cells), the four
+ * class counts (slot ICPMI_GK_REC_CONFIRMED + class; they sum to ROWS), THROUGH_UNKNOWN (the rows with cells whose k_unknown
+ * >= 0) and a 0.  Status ICPMI_GK_ST_OK; ICPMI_GK_ST_EMPTY: no row has a cell; ICPMI_GK_ST_CAPACITY: icpmi_grid_match_batch's
+ * rule for cnt_dev (negative, beyond the cloud's own rows or beyond ICPMI_GM_MAX_ROWS) — nothing is read, every count 0.
+ * out_rows (optional, NULL: off): device, 16-byte aligned, int32 [n_pairs][row_stride][ICPMI_GK_ROW_INTS], one 16-byte
+ * store per row: [class, k_hit, K, k_unknown]; a row without cells is [ICPMI_GK_NO_CELLS, 0, 0, -1].  row_stride is the
+ * caller's, at least every named cloud's row count by off_host.  Rows at or behind a cloud's count are not written.
+ *
+ * Refusals, on the host before anything is enqueued.  n_pairs == 0: ICPMI_OK, nothing done.  ICPMI_ERR_ARG: n_pairs or
+ * n_clouds negative; off_host or pair_cloud_host NULL; a pair's cloud outside [0, n_clouds) or with a negative row count; a
+ * grid the casts refuse (ny or nx negative or above 2^29, ny * nx >= 2^31); a resolution that is not positive and finite,
+ * a min_x or min_y that is not finite; tolerance < 0 or > 2^30; pts, off_dev, pair_cloud, pair_t, cos_sin or out_records
+ * NULL; pts, out_rows or planes not 16-byte aligned; with out_rows, a row_stride below the largest named cloud; planes NULL
+ * on a grid with cells and field NULL or not 16-byte aligned.  ICPMI_ERR_UNSUPPORTED: a named cloud above
+ * ICPMI_GM_MAX_ROWS rows by off_host; the sum of the named clouds' rows reaching 2^29; n_pairs * ceil(largest named cloud
+ * / ICPMI_GK_CHUNK_ROWS) reaching 2^31.  ICPMI_ERR_WORKSPACE: planes NULL on a grid with cells and a workspace that is NULL,
+ * misaligned or below icpmi_grid_occupancy_planes_bytes(ny, nx).  ny * nx == 0: nothing is packed and no step is inside the
+ * grid — every row with cells is UNEXPLORED.
+ * Launches: one memset of the records; gc_planes_kernel (only when the call packs); gk_check_kernel — a workgroup of
+ * ICPMI_GK_THREADS threads per (pair, chunk of ICPMI_GK_CHUNK_ROWS rows), a lane per row, a wave 64 consecutive rows of one
+ * pair; ballots count the classes per wave, LDS per workgroup, one int32 atomicAdd per non-zero counter per workgroup —
+ * (only when a named cloud has rows); and gk_status_kernel, a lane per pair, which settles the status. */
+#define ICPMI_GK_THREADS 256
+#define ICPMI_GK_CHUNK_ROWS 256
+#define ICPMI_GK_MAX_TOLERANCE 1073741824
+#define ICPMI_GK_INTS 8
+#define ICPMI_GK_REC_STATUS 0
+#define ICPMI_GK_REC_ROWS 1
+#define ICPMI_GK_REC_CONFIRMED 2
+#define ICPMI_GK_REC_VIOLATED 3
+#define ICPMI_GK_REC_IN_FREE 4
+#define ICPMI_GK_REC_UNEXPLORED 5
+#define ICPMI_GK_REC_THROUGH_UNKNOWN 6
+#define ICPMI_GK_ST_OK 0
+#define ICPMI_GK_ST_EMPTY 1
+#define ICPMI_GK_ST_CAPACITY 2
+#define ICPMI_GK_CLASS_CONFIRMED 0
+#define ICPMI_GK_CLASS_VIOLATED 1
+#define ICPMI_GK_CLASS_IN_FREE 2
+#define ICPMI_GK_CLASS_UNEXPLORED 3
+#define ICPMI_GK_NO_CELLS (-2)    /* class of a row whose pose or end point has no cell */
+#define ICPMI_GK_ROW_INTS 4
+#define ICPMI_GK_ROW_CLASS 0
+#define ICPMI_GK_ROW_K_HIT 1
+#define ICPMI_GK_ROW_K 2
+#define ICPMI_GK_ROW_K_UNKNOWN 3
+int icpmi_grid_check_batch(const int16_t* field, const void* planes, int32_t ny, int32_t nx, int32_t occ_threshold,
+                           double min_x, double min_y, double resolution, const double* pts, const int32_t* off_dev,
+                           const int32_t* off_host, const int32_t* cnt_dev, int32_t n_clouds, const int32_t* pair_cloud,
+                           const int32_t* pair_cloud_host, int32_t n_pairs, const double* pair_t, const double* cos_sin,
+                           int32_t tolerance, int32_t* out_records, int32_t* out_rows, int32_t row_stride,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* ── pose graph: PoseGraph2D.optimize, utilities/pose_graph.py:83-134 ──────────
  * Gauss-Newton on SE(2) over n_nodes poses [x, y, theta] (nodes: device, updated
  * in place) and n_edges constraints (i, j, z_ij [3], Omega [3][3] row-major).

@@ -32,11 +32,12 @@ struct GmArgs {
 
 // rows of a pair's cloud: the device count where the set has one; -1 for a count that is negative (the voxel filter's
 // overflow mark) or beyond the cloud's own rows or ICPMI_GM_MAX_ROWS — such a cloud is not read (ICPMI_GM_ST_CAPACITY)
-__device__ __forceinline__ int gm_rows(const GmArgs& a, int c) {
-    const int cap = a.off[c + 1] - a.off[c];
-    const int n = a.cnt ? a.cnt[c] : cap;
+__device__ __forceinline__ int gm_rows(const int32_t* off, const int32_t* cnt, int c) {
+    const int cap = off[c + 1] - off[c];
+    const int n = cnt ? cnt[c] : cap;
     return n < 0 || n > cap || n > ICPMI_GM_MAX_ROWS ? -1 : n;
 }
+__device__ __forceinline__ int gm_rows(const GmArgs& a, int c) { return gm_rows(a.off, a.cnt, c); }
 
 // floor((w - mn) / res), the IEEE divide of world_to_grid_kernel; false for a non-finite w or a cell beyond +-2^29
 __device__ __forceinline__ bool gm_cell(double w, double mn, double res, int& out) {

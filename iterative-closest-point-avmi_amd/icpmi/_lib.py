@@ -47,6 +47,14 @@ GMOM_WEIGHT_BITS, GMOM_MAX_HALF_STEP = 20, 32767
 LF_MAX_RADIUS, LF_TILE_X, LF_TILE_Y = 64, 128, 64
 # icpmi_grid_cast_segments / icpmi_grid_cast_rays: the slots of a ray's int32 record and its two marks (GC_*)
 GC_INTS, GC_K_HIT, GC_X_HIT, GC_Y_HIT, GC_K_UNKNOWN, GC_NONE, GC_NO_CELLS, GC_THREADS = 4, 0, 1, 2, 3, -1, -2, 256
+# icpmi_grid_check_batch (GK_*: the two sizes its kernel is built on, the largest tolerance, the slots of a pair's int32 record,
+# its statuses, the classes of a row with the mark of a row without cells, and the slots of a row's record)
+GK_THREADS, GK_CHUNK_ROWS, GK_MAX_TOLERANCE = 256, 256, 2 ** 30
+GK_INTS, GK_REC_STATUS, GK_REC_ROWS, GK_REC_CONFIRMED, GK_REC_VIOLATED, GK_REC_IN_FREE, GK_REC_UNEXPLORED, GK_REC_THROUGH_UNKNOWN = (
+    8, 0, 1, 2, 3, 4, 5, 6)
+GK_ST_OK, GK_ST_EMPTY, GK_ST_CAPACITY = 0, 1, 2
+GK_CLASS_CONFIRMED, GK_CLASS_VIOLATED, GK_CLASS_IN_FREE, GK_CLASS_UNEXPLORED, GK_NO_CELLS = 0, 1, 2, 3, -2
+GK_ROW_INTS, GK_ROW_CLASS, GK_ROW_K_HIT, GK_ROW_K, GK_ROW_K_UNKNOWN = 4, 0, 1, 2, 3
 # icpmi_pose_graph_optimize: its statuses (PG_ST_*) and the slots of its info record (PGINFO_*: three values, then PHASES clocks)
 PG_ST_NOTHING, PG_ST_CONVERGED, PG_ST_MAXITER, PG_ST_SINGULAR, PG_ST_REFUSED = 0, 1, 2, 3, 4
 PGINFO_DOUBLES, PGINFO_ITERATIONS, PGINFO_STATUS, PGINFO_STEP, PGINFO_PHASE_US, PGINFO_PHASES = 10, 0, 1, 2, 3, 7
@@ -209,6 +217,9 @@ _SIGS = {
     "icpmi_grid_cast_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
                                        C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
                                        C.c_size_t, C.c_void_p]),
+    "icpmi_grid_check_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double] +
+                               [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "icpmi_pose_graph_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
     "icpmi_pose_graph_optimize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                             C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_size_t,

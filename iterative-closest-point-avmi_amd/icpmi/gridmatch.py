@@ -8,7 +8,9 @@ the matchers read while the map's walls are one cell wide: the exact truncated d
 (``distance_field``), mapped to a score through a table (``likelihood_table``, ``likelihood_field``).  The cast reads the
 same field back as ranges (``icpmi_grid_occupancy_planes``, ``icpmi_grid_cast_segments``, ``icpmi_grid_cast_rays``:
 ``occupancy_planes``, ``cast_segments``, ``cast_rays``): along the cells the map's update would lower, the first occupied
-cell and the first unknown cell before it.
+cell and the first unknown cell before it.  The check (``icpmi_grid_check_batch``: ``check_pairs``) walks measured beams over
+the same planes, from the pose to the cell of each row's own hit, and counts per pair the beams the map confirms, the beams
+that came back from behind a wall of the map, and the returns out of observed free or unexplored space.
 
 The reference registers a scan against a cloud only (slam.py:53-98, 111-183); this reads the map ``utilities.mapping``
 builds.  The log-odds are quantised to int16 and a candidate's score is the integer sum of the field under the scan's
@@ -230,6 +232,51 @@ def cast_rays(field_or_planes, threshold, min_x, min_y, resolution, poses_xy, po
                                           _ptr(xy), _ptr(pcs), P, _ptr(bcs), A, float(reach), _ptr(out), _ptr(ws),
                                           0 if ws is None else ws.numel(), _stream()), "grid_cast_rays")
     return out
+
+
+def check_pairs(field_or_planes, threshold, min_x, min_y, resolution, cloud_set, pair_clouds, translations, cos_sin, tolerance,
+                want_rows=False, out=None):
+    """``icpmi_grid_check_batch``: pair b holds cloud ``pair_clouds[b]`` of ``cloud_set`` (sensor frame, 2-D) at the
+    translation ``translations[b]`` and the rotation ``cos_sin[b]`` = (cos, sin) against the map as ``cast_segments`` takes it.
+    Every row's beam is walked from the pose's cell to the cell of its own hit and falls in one class (include/icpmi.h):
+    confirmed — the map has a wall within ``tolerance`` steps of the beam's end —, violated — the beam came back from behind
+    a wall of the map —, in free space or unexplored.  -> (records, rows): the (B, GK_INTS) int32 device tensor of records
+    [status, rows with cells, confirmed, violated, in_free, unexplored, through_unknown, 0] and, with ``want_rows``, the (B,
+    stride, GK_ROW_INTS) int32 device tensor of [class, k_hit, K, k_unknown] per row (else None) — stride the largest named
+    cloud; what lies at or behind a cloud's count is not written.  ``out``: a records tensor, or with ``want_rows`` the pair
+    (records, rows), to write into.  The rows are the caller's own float64 (arrays or device tensors).  Enqueues and does not
+    synchronise."""
+    field, planes, ws, ny, nx, thr, dev = _cast_source(field_or_planes, threshold)
+    cs = cloud_set
+    if cs.dim != 2:
+        raise ValueError("the check is 2-D")
+    if cs.pts.device != dev:
+        raise ValueError(f"the clouds live on {cs.pts.device}, the map on {dev}")
+    if not (np.isfinite(resolution) and resolution > 0.0) or not (np.isfinite(min_x) and np.isfinite(min_y)):
+        raise ValueError(f"resolution must be positive and finite and the map's corner finite, got {resolution}, ({min_x}, {min_y})")
+    tol = int(tolerance)
+    if tol != tolerance or not 0 <= tol <= _lib.GK_MAX_TOLERANCE:
+        raise ValueError(f"tolerance must be a whole number of steps in [0, 2^30], got {tolerance}")
+    pair_host = np.ascontiguousarray(pair_clouds, dtype=np.int32).reshape(-1)
+    B = len(pair_host)
+    if B and (pair_host.min() < 0 or pair_host.max() >= cs.n_clouds):
+        raise ValueError("pair_clouds must index the cloud set")
+    named = np.diff(cs.off_host).astype(np.int64)[pair_host]
+    if B and int(named.max()) > MAX_ROWS:
+        raise ValueError(f"a cloud above {MAX_ROWS} rows cannot be checked: filter it first")
+    if int(named.sum()) >= 2 ** 29:
+        raise ValueError(f"{int(named.sum())} rows: fewer than 2^29 fit one call")
+    stride = int(named.max()) if B else 0
+    t, rot = _rows_f64(translations, 2, "translations", dev, B), _rows_f64(cos_sin, 2, "cos_sin", dev, B)
+    rec_out, rows_out = (out if want_rows else (out, None)) if out is not None else (None, None)
+    records = _cast_out(rec_out, (B, _lib.GK_INTS), dev)
+    rows = _cast_out(rows_out, (B, stride, _lib.GK_ROW_INTS), dev) if want_rows else None
+    pair = torch.from_numpy(pair_host).to(dev)
+    check(_lib.lib().icpmi_grid_check_batch(
+        _ptr(field), _ptr(planes), ny, nx, thr, float(min_x), float(min_y), float(resolution), _ptr(cs.pts), _ptr(cs.off),
+        cs.off_host.ctypes.data_as(C.c_void_p), _ptr(cs.cnt), cs.n_clouds, _ptr(pair), pair_host.ctypes.data_as(C.c_void_p), B, _ptr(t),
+        _ptr(rot), tol, _ptr(records), _ptr(rows), stride, _ptr(ws), 0 if ws is None else ws.numel(), _stream()), "grid_check")
+    return records, rows
 
 
 def ray_end_cells(min_x, min_y, resolution, poses_xy, pose_cs, beam_cs, reach):

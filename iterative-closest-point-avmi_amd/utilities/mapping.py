@@ -417,6 +417,22 @@ class OccupancyGrid2D:
         q, k = self.score_field() if field is None else field
         return gridmatch.occupancy_planes(q, int(np.rint(occupied_log_odds * 2.0 ** k))), k
 
+    def _cast_map(self, occupied_log_odds, field, planes):
+        """-> (what the cast and the check read, k, the threshold): kept ``planes`` as they are, else ``field`` or the map as it
+        is now, with ``occupied_log_odds`` in that field's units."""
+        from icpmi import gridmatch
+        if field is not None and planes is not None:
+            raise ValueError("pass field= or planes=, not both")
+        if planes is not None:
+            src, k = planes
+            if not isinstance(src, gridmatch.OccupancyPlanes) or (src.ny, src.nx) != (self.ny, self.nx):
+                raise ValueError("planes must be what occupancy_planes() returned for this grid")
+            return src, k, src.threshold
+        src, k = self.score_field() if field is None else field
+        if tuple(src.shape) != (self.ny, self.nx):
+            raise ValueError("field must be the int16 (ny, nx) tensor score_field() returned for this grid")
+        return src, k, int(np.rint(occupied_log_odds * 2.0 ** k))
+
     def cast_scans(self, poses, angles, max_range, occupied_log_odds=0.5, field=None, planes=None):
         """The scan this map predicts at every pose of ``poses`` ((P, 3) rows [x, y, theta] or 3 x 3 matrices): along each
         sensor-frame bearing of ``angles`` (radians, A of them) up to ``max_range`` metres, the first occupied cell — log-odds
@@ -429,20 +445,9 @@ class OccupancyGrid2D:
         none, -2 no cells), ``cells`` (P, A, 2) the hit cell (x, y) (the end cell without a hit), ``k_unknown`` (P, A) (-1: none),
         ``unknown_range`` (the same distance to the first unknown cell, inf without one) and ``shift_bits``."""
         from icpmi import gridmatch
-        if field is not None and planes is not None:
-            raise ValueError("pass field= or planes=, not both")
+        src, k, threshold = self._cast_map(occupied_log_odds, field, planes)
         xyt = self._xytheta(poses)
         ang = np.asarray(angles, dtype=np.float64).reshape(-1)
-        if planes is not None:
-            src, k = planes
-            if not isinstance(src, gridmatch.OccupancyPlanes) or (src.ny, src.nx) != (self.ny, self.nx):
-                raise ValueError("planes must be what occupancy_planes() returned for this grid")
-            threshold = src.threshold
-        else:
-            src, k = self.score_field() if field is None else field
-            if tuple(src.shape) != (self.ny, self.nx):
-                raise ValueError("field must be the int16 (ny, nx) tensor score_field() returned for this grid")
-            threshold = int(np.rint(occupied_log_odds * 2.0 ** k))
         pose_cs = np.stack([np.cos(xyt[:, 2]), np.sin(xyt[:, 2])], axis=1)
         beam_cs = np.stack([np.cos(ang), np.sin(ang)], axis=1)
         rec = gridmatch.cast_rays(src, threshold, self.min_x, self.min_y, self.resolution, xyt[:, :2], pose_cs, beam_cs, max_range)
@@ -464,22 +469,109 @@ class OccupancyGrid2D:
         ranges, info = self.cast_scans(p[None] if p.ndim == 2 else p.reshape(1, 3), angles, max_range, occupied_log_odds, field, planes)
         return ranges[0], {k: (v[0] if isinstance(v, np.ndarray) else v) for k, v in info.items()}
 
+    # ── measured scans held against the map along their beams (icpmi.gridmatch.check_pairs; no counterpart in the reference) ──
+    def _check_set(self, cs, pair_clouds, poses, tolerance, occupied_log_odds, field, planes, want_rows):
+        from icpmi import gridmatch
+        src, k, threshold = self._cast_map(occupied_log_odds, field, planes)
+        if cs.pts.device != self._dev:
+            raise ValueError(f"the clouds live on {cs.pts.device}, the grid on {self._dev}")
+        pair_clouds = np.ascontiguousarray(pair_clouds, dtype=np.int32).reshape(-1)
+        xyt = self._xytheta(poses, len(pair_clouds))
+        cos_sin = np.stack([np.cos(xyt[:, 2]), np.sin(xyt[:, 2])], axis=1)
+        records, rows = gridmatch.check_pairs(src, threshold, self.min_x, self.min_y, self.resolution, cs, pair_clouds, xyt[:, :2], cos_sin,
+                                              tolerance, want_rows=want_rows)
+        rec = records.cpu().numpy().astype(np.int64)
+        info = {key: rec[:, slot].copy() for key, slot in (
+            ("status", _lib.GK_REC_STATUS), ("rows", _lib.GK_REC_ROWS), ("confirmed", _lib.GK_REC_CONFIRMED), ("violated", _lib.GK_REC_VIOLATED),
+            ("in_free", _lib.GK_REC_IN_FREE), ("unexplored", _lib.GK_REC_UNEXPLORED), ("through_unknown", _lib.GK_REC_THROUGH_UNKNOWN))}
+        some = np.maximum(info["rows"], 1)
+        info["violated_share"] = np.where(info["rows"] > 0, info["violated"] / some, 0.0)
+        info["in_free_share"] = np.where(info["rows"] > 0, info["in_free"] / some, 0.0)
+        info["shift_bits"] = k
+        if want_rows:
+            n = np.diff(cs.off_host).astype(np.int64)
+            if cs.cnt is not None:
+                n = np.minimum(n, cs.cnt.cpu().numpy().astype(np.int64))
+            n = np.where(info["status"] == _lib.GK_ST_CAPACITY, 0, n[pair_clouds])
+            host = rows.cpu().numpy()
+            info["classes"] = [host[b, :n[b]].copy() for b in range(len(pair_clouds))]
+        return info
+
+    def check_scans(self, clouds, poses, tolerance=2, occupied_log_odds=0.5, voxel_size=None, field=None, planes=None, want_rows=False):
+        """Does each scan of ``clouds`` (sensor frame, (n, 2) arrays or a device ``CloudSet``), held at its pose of ``poses``
+        ([x, y, theta] rows or 3 x 3 matrices), contradict the free space and the walls this map already holds?  Every
+        measured beam is walked from the pose's cell to the cell of its own hit — exactly the cells ``update_scan`` would
+        touch for it — and falls in one class: ``confirmed``, the map has an occupied cell (log-odds >= ``occupied_log_odds``)
+        within ``tolerance`` steps of the beam's end; ``violated``, the first occupied cell lies more than ``tolerance`` steps
+        before the end — the beam came back from behind a wall of the map, which is what a false loop closure between
+        similar rooms looks like —; ``in_free``, nothing occupied and the end in observed free space (something new, or
+        something that moved in); ``unexplored``, nothing occupied and the end in unknown space or off the grid.  A sum of
+        log-odds under the hits (``score_poses``) sees none of this.  One launch for all scans; only a few integers per scan
+        come back.  ``tolerance`` is in steps (cells along the beam's major axis); at 0 a true pose fails, because a noisy
+        return lands a cell behind the first occupied layer of a mapped wall.  A return just IN FRONT of a thin wall counts
+        as ``in_free``; the remedy is thicker walls: pass ``planes=occupancy_planes(lower_occupied_log_odds,
+        field=likelihood_field(...))`` — planes packed from a likelihood field with a lower ``occupied_log_odds`` hold every
+        cell near a wall occupied.  ``voxel_size``: the scans pass through ``voxel_downsample`` first.  ``field``: a
+        ``(tensor, k)`` to read instead of the map as it is now; ``planes``: what ``occupancy_planes()`` returned
+        (``occupied_log_odds`` is then the planes' own); both show the map as it was when they were made.
+        -> info: int64 arrays ``rows`` (the rows with cells), ``confirmed``, ``violated``, ``in_free``, ``unexplored`` (these
+        four sum to ``rows``), ``through_unknown`` (rows whose beam crossed an unknown cell before its hit or end) and
+        ``status`` (``icpmi._lib.GK_ST_*``); ``violated_share`` and ``in_free_share`` (count / rows, 0.0 where rows is 0);
+        ``shift_bits``.  With ``want_rows``, ``classes``: per scan an (n, 4) int32 array [class, k_hit, K, k_unknown] per row
+        (``icpmi._lib.GK_CLASS_*``; ``GK_NO_CELLS`` for a row without cells)."""
+        from icpmi import gridmatch
+        cs = gridmatch.cloud_set_of(clouds, voxel_size)
+        return self._check_set(cs, np.arange(cs.n_clouds), poses, tolerance, occupied_log_odds, field, planes, want_rows)
+
+    def check_scan(self, points_local, pose, tolerance=2, occupied_log_odds=0.5, voxel_size=None, field=None, planes=None, want_rows=False):
+        """``check_scans`` of one scan at one pose ([x, y, theta] or a 3 x 3 matrix) -> info with scalar entries (``classes``:
+        the one (n, 4) array).  Planes packed from a ``likelihood_field`` with a lower ``occupied_log_odds`` thicken the walls:
+        the remedy for returns just in front of a thin wall."""
+        p = np.asarray(pose, dtype=np.float64)
+        info = self.check_scans([points_local], p[None] if p.ndim == 2 else p.reshape(1, 3), tolerance, occupied_log_odds, voxel_size,
+                                field, planes, want_rows)
+        return {k: (v[0] if isinstance(v, (np.ndarray, list)) else v) for k, v in info.items()}
+
+    def check_poses(self, points_local, poses, tolerance=2, occupied_log_odds=0.5, field=None, planes=None, want_rows=False):
+        """``check_scans`` of ONE scan at every pose of ``poses`` ((P, 3) rows [x, y, theta] or 3 x 3 matrices), as
+        ``score_poses`` scores one: the scan is uploaded once and every hypothesis names it — a particle filter's free-space
+        test, or a gate on loop-closure candidates -> info with (P,) entries.  Planes packed from a ``likelihood_field`` with a
+        lower ``occupied_log_odds`` thicken the walls: the remedy for returns just in front of a thin wall."""
+        from icpmi import gridmatch
+        cs = gridmatch.cloud_set_of([points_local])
+        xyt = self._xytheta(poses)
+        return self._check_set(cs, np.zeros(len(xyt), dtype=np.int32), xyt, tolerance, occupied_log_odds, field, planes, want_rows)
+
+    def check_history(self, history, ids, poses, tolerance=2, occupied_log_odds=0.5, voxel_size=None, field=None, planes=None,
+                      want_rows=False):
+        """``check_scans`` of scans resident in an ``icpmi.ScanHistory``, by id: the rows are read where they are and no scan
+        is uploaded; ``voxel_size`` chooses them as in ``match_history``.  Planes packed from a ``likelihood_field`` with a
+        lower ``occupied_log_odds`` thicken the walls: the remedy for returns just in front of a thin wall."""
+        from icpmi import history as _h
+        ids = _h._scan_ids(ids, ("ids", "scan ids"), history.n_scans)
+        return self._check_set(self._history_rows(history, voxel_size), ids, poses, tolerance, occupied_log_odds, field, planes, want_rows)
+
+    @staticmethod
+    def _history_rows(history, voxel_size):
+        """The cloud set of a history's scans at ``voxel_size``: the raw rows (None), the history's own filtered copies where
+        it is one of the history's voxel sizes, any other size filters every resident scan first."""
+        from icpmi.batch import voxel_downsample_set
+        if voxel_size is None:
+            return history.raw
+        if float(voxel_size) == history.voxel_size:
+            return history.vox
+        if float(voxel_size) == history.rotation_voxel_size:
+            return history.rs_vox
+        return voxel_downsample_set(history.raw, voxel_size)
+
     def match_history(self, history, ids, predicted_poses, linear_window=0.6, angular_window=12.0, angular_step=1.0, voxel_size=None,
                       field=None, half_log_odds=None):
         """``match_scans`` of scans resident in an ``icpmi.ScanHistory``, by id: the raw rows are read where they are and no
         scan is uploaded.  ``voxel_size``: the history's own filtered copies where it is one of the history's voxel sizes;
         any other size filters every resident scan first."""
         from icpmi import history as _h
-        from icpmi.batch import voxel_downsample_set
         ids = _h._scan_ids(ids, ("ids", "scan ids"), history.n_scans)
-        if voxel_size is None:
-            cs = history.raw
-        elif float(voxel_size) == history.voxel_size:
-            cs = history.vox
-        elif float(voxel_size) == history.rotation_voxel_size:
-            cs = history.rs_vox
-        else:
-            cs = voxel_downsample_set(history.raw, voxel_size)
+        cs = self._history_rows(history, voxel_size)
         return self._match_set(cs, ids, predicted_poses, linear_window, angular_window, angular_step, field,
                                half_log_odds=half_log_odds).unpack()
 
@@ -528,16 +620,8 @@ class OccupancyGrid2D:
                        block=8, field=None, bounds=None):
         """``search_scans`` of scans resident in an ``icpmi.ScanHistory``, by id, with ``match_history``'s choice of rows."""
         from icpmi import history as _h
-        from icpmi.batch import voxel_downsample_set
         ids = _h._scan_ids(ids, ("ids", "scan ids"), history.n_scans)
-        if voxel_size is None:
-            cs = history.raw
-        elif float(voxel_size) == history.voxel_size:
-            cs = history.vox
-        elif float(voxel_size) == history.rotation_voxel_size:
-            cs = history.rs_vox
-        else:
-            cs = voxel_downsample_set(history.raw, voxel_size)
+        cs = self._history_rows(history, voxel_size)
         return self._search_set(cs, ids, predicted_poses, linear_window, angular_window, angular_step, block, field, bounds).unpack()
 
     # ── probability / display, mapping.py:150-166 (NumPy on the host copy) ───
