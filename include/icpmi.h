@@ -1071,6 +1071,83 @@ int icpmi_grid_check_batch(const int16_t* field, const void* planes, int32_t ny,
                            int32_t tolerance, int32_t* out_records, int32_t* out_rows, int32_t row_stride,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the beam model: measured scans scored against the ranges the map expects (no counterpart in the reference) --------
+ * The check sorts a beam into four classes with a hard tolerance; the cast hands the expected ranges to the host.
+ * icpmi_grid_beam_batch gives what a particle filter's measurement update, a ranking of loop-closure candidates and a sigma
+ * estimate from residuals read: one number per (scan, pose) that falls smoothly with the signed distance, along each beam,
+ * between where the map has its first wall and where the beam returned.  Every measured beam is walked from the pose's cell
+ * through the cell of its own hit to a far end `beyond` metres behind it; the difference in steps picks an entry of the
+ * caller's table, and the entries are summed per pair on the device.  After the cells are formed everything is integer and
+ * added with integer atomics: a record is a function of the inputs alone, to the bit.
+ *
+ * The map, the cloud set, the pairs, pair_t and cos_sin: exactly as icpmi_grid_check_batch takes them.  In place of its
+ * tolerance: beyond, float64 metres, finite and >= 0 — how far past its return a beam is walked; half_width H, 0 <= H <=
+ * ICPMI_GB_MAX_HALF_WIDTH; table, device, 16-byte aligned, int32 [2 H + 3].
+ *
+ * Cells of a row.  For row (x, y) of pair b, in float64 with every operation rounded on its own (sqrt the IEEE one):
+ *   r = sqrt(x * x + y * y),  s = (r + beyond) / r,  fx = x * s,  fy = y * s.
+ * Three cells by icpmi_grid_check_batch's expressions and rule: the origin o from (tx, ty), the hit h from (x, y) and the
+ * far end f from (fx, fy).  If any of the three has no cell — a coordinate that is not finite or a cell outside [-2^29,
+ * 2^29]; r = 0 among them, where s is not finite — the row has no cells.
+ *
+ * Index of a row.  Let [k_hit, ., ., k_unknown] be the cast's record of the segment o -> f, the end cell included, and k_z =
+ * |h_major - o_major| on the major axis OF THAT WALK (x where |fx_cell - ox| >= |fy_cell - oy|, else y): the step at which
+ * the beam returned.  The row's table index i is
+ *   clamp(k_hit - k_z, -H, H) + H   where k_hit >= 0: positive differences mean the beam came back short of the map's wall,
+ *                                   negative ones that it came back from behind it;
+ *   2 H + 1                         else, where h lies inside the grid with its unknown bit clear: a return out of observed
+ *                                   free space with no wall within `beyond`;
+ *   2 H + 2                         else: a return from unexplored space or from off the grid.
+ * Differences are in steps along the walk's major axis, as the check's tolerance is: a step is `resolution` metres along an
+ * axis and up to sqrt(2) * resolution along a diagonal, so the same table is up to sqrt(2) wider in metres on a diagonal.
+ * (k_hit and k_z lie in [-1, 2^30]: the difference does not overflow.)
+ *
+ * out_records: device, int32 [n_pairs][ICPMI_GB_INTS], slots ICPMI_GB_REC_*: STATUS, ROWS (the rows with cells), SCORE,
+ * EXPECTED (rows with k_hit >= 0), NOVEL (rows at index 2 H + 1), UNEXPLORED (rows at index 2 H + 2; the three sum to ROWS)
+ * and two 0.  SCORE is the sum over the rows with cells of clip(table[i], -ICPMI_GB_TABLE_CLIP, ICPMI_GB_TABLE_CLIP): the
+ * kernel clips while it stages the table, so ICPMI_GM_MAX_ROWS rows cannot overflow an int32.  Status ICPMI_GB_ST_OK /
+ * _EMPTY / _CAPACITY by icpmi_grid_check_batch's rules, the one for cnt_dev included.
+ * out_hist (optional, NULL: off): device, 16-byte aligned, int32 [n_pairs][2 H + 3]: the rows with cells per index (they sum
+ * to ROWS, and SCORE is their product with the clipped table); all 0 for a pair with CAPACITY.
+ * out_rows (optional, NULL: off): device, 16-byte aligned, int32 [n_pairs][row_stride][ICPMI_GB_ROW_INTS], one 16-byte
+ * store per row: [i, k_hit, k_z, k_unknown]; a row without cells is [ICPMI_GB_NO_CELLS, 0, 0, -1].  row_stride and what is
+ * written as for icpmi_grid_check_batch.
+ *
+ * Refusals, on the host before anything is enqueued: icpmi_grid_check_batch's for everything shared, in its order (n_pairs
+ * == 0: ICPMI_OK, nothing done, whatever else is passed).  In addition ICPMI_ERR_ARG for: half_width outside [0,
+ * ICPMI_GB_MAX_HALF_WIDTH]; beyond negative, NaN or infinite; table NULL or not 16-byte aligned; out_hist not 16-byte
+ * aligned.
+ * Launches: one memset of the records and one of the histograms when asked for; gc_planes_kernel (only when the call
+ * packs); gb_beam_kernel — a workgroup of ICPMI_GB_THREADS threads per (pair, chunk of ICPMI_GB_CHUNK_ROWS rows), a lane per
+ * row; the clipped table and the chunk's histogram in LDS, the score summed per wave, one int32 atomicAdd per non-zero slot
+ * and bin per workgroup — (only when a named cloud has rows); and gb_status_kernel, a lane per pair. */
+#define ICPMI_GB_THREADS 256
+#define ICPMI_GB_CHUNK_ROWS 256
+#define ICPMI_GB_MAX_HALF_WIDTH 127
+#define ICPMI_GB_TABLE_CLIP 32767
+#define ICPMI_GB_INTS 8
+#define ICPMI_GB_REC_STATUS 0
+#define ICPMI_GB_REC_ROWS 1
+#define ICPMI_GB_REC_SCORE 2
+#define ICPMI_GB_REC_EXPECTED 3
+#define ICPMI_GB_REC_NOVEL 4
+#define ICPMI_GB_REC_UNEXPLORED 5
+#define ICPMI_GB_ST_OK 0
+#define ICPMI_GB_ST_EMPTY 1
+#define ICPMI_GB_ST_CAPACITY 2
+#define ICPMI_GB_NO_CELLS (-2)    /* index of a row whose pose, hit or far end has no cell */
+#define ICPMI_GB_ROW_INTS 4
+#define ICPMI_GB_ROW_INDEX 0
+#define ICPMI_GB_ROW_K_HIT 1
+#define ICPMI_GB_ROW_K_Z 2
+#define ICPMI_GB_ROW_K_UNKNOWN 3
+int icpmi_grid_beam_batch(const int16_t* field, const void* planes, int32_t ny, int32_t nx, int32_t occ_threshold,
+                          double min_x, double min_y, double resolution, const double* pts, const int32_t* off_dev,
+                          const int32_t* off_host, const int32_t* cnt_dev, int32_t n_clouds, const int32_t* pair_cloud,
+                          const int32_t* pair_cloud_host, int32_t n_pairs, const double* pair_t, const double* cos_sin,
+                          double beyond, int32_t half_width, const int32_t* table, int32_t* out_records, int32_t* out_hist,
+                          int32_t* out_rows, int32_t row_stride, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ── pose graph: PoseGraph2D.optimize, utilities/pose_graph.py:83-134 ──────────
  * Gauss-Newton on SE(2) over n_nodes poses [x, y, theta] (nodes: device, updated
  * in place) and n_edges constraints (i, j, z_ij [3], Omega [3][3] row-major).

@@ -10,7 +10,7 @@
 //                     adds them per workgroup, one int32 atomicAdd per non-zero counter goes to the pair's record;
 //   gk_status_kernel  a lane per pair, after the counts: the record's status.
 // After the cells are formed everything is integer, and integer atomics commute: a record is a function of the inputs alone.
-#include "gridcast.hpp"
+#include "gridpairs.hpp"
 #include "gridmatch.hpp"
 
 namespace icpmi {
@@ -111,37 +111,15 @@ __global__ __launch_bounds__(GK_THREADS) void gk_status_kernel(GkArgs a) {
 }
 
 // ── host: the plan, the entry ────────────────────────────────────────────────
-// What a call starts, decided as a whole and without a HIP call.  The chunk never depends on the batch and the sums are
+// What a call starts, decided as a whole and without a HIP call: the plan of the pairs (gridpairs.hpp: the grid's GcPlan,
+// the (pair, chunk) grid, the status grid) and the bytes zeroed.  The chunk never depends on the batch and the sums are
 // integers: a pair's record does not depend on the batch it is computed in.
-struct GkPlan {
-    int rc;                   // ICPMI_OK, or why nothing is launched
-    GcPlan grid;              // the planes of the grid: what is packed when the call packs, and their size
-    unsigned check_grid;      // (pair, chunk) workgroups; 0: no named cloud has a row (the records are still written)
-    unsigned status_grid;     // gk_status_kernel: a lane per pair
-    int n_chunks, max_n;      // row chunks of, and rows of, the largest named cloud
+struct GkPlan : PairPlan {
     size_t record_bytes;      // what is zeroed before the launch
 };
 static GkPlan plan_check(int ny, int nx, int n_pairs, int n_clouds, const int32_t* off_host, const int32_t* pair_cloud_host) {
-    GkPlan p{ICPMI_OK, plan_cast(ny, nx, 0, 0), 0, 0, 0, 0, 0};
-    if (n_pairs < 0 || n_clouds < 0 || !off_host || !pair_cloud_host) { p.rc = ICPMI_ERR_ARG; return p; }
-    long long total = 0;
-    bool above = false;
-    for (int b = 0; b < n_pairs; ++b) {
-        const int c = pair_cloud_host[b];
-        if (c < 0 || c >= n_clouds) { p.rc = ICPMI_ERR_ARG; return p; }
-        const int rows = off_host[c + 1] - off_host[c];
-        if (rows < 0) { p.rc = ICPMI_ERR_ARG; return p; }
-        above |= rows > ICPMI_GM_MAX_ROWS;
-        p.max_n = rows > p.max_n ? rows : p.max_n;
-        total += rows;
-    }
-    if (p.grid.rc != ICPMI_OK) { p.rc = p.grid.rc; return p; }
-    p.n_chunks = (p.max_n + GK_CHUNK - 1) / GK_CHUNK;
-    const unsigned long long groups = (unsigned long long)n_pairs * p.n_chunks;
-    if (above || total >= (1ll << 29) || groups >= (1ull << 31)) { p.rc = ICPMI_ERR_UNSUPPORTED; return p; }
-    p.check_grid = (unsigned)groups;
-    p.status_grid = (unsigned)(((long long)n_pairs + GK_THREADS - 1) / GK_THREADS);
-    p.record_bytes = (size_t)n_pairs * ICPMI_GK_INTS * sizeof(int32_t);
+    GkPlan p{plan_pairs(ny, nx, n_pairs, n_clouds, off_host, pair_cloud_host, GK_CHUNK, GK_THREADS), 0};
+    if (p.rc == ICPMI_OK) p.record_bytes = (size_t)n_pairs * ICPMI_GK_INTS * sizeof(int32_t);
     return p;
 }
 
@@ -173,13 +151,13 @@ extern "C" int icpmi_grid_check_batch(const int16_t* field, const void* planes, 
     if (hipMemsetAsync(out_records, 0, plan.record_bytes, st) != hipSuccess) return ICPMI_ERR_HIP;
     GkArgs a{(const unsigned char*)planes, ny, nx, min_x, min_y, resolution, pts, off_dev, cnt_dev, pair_cloud, pair_t, cos_sin,
              tolerance, plan.n_chunks, n_pairs, row_stride, out_records, reinterpret_cast<int4*>(out_rows)};
-    if (plan.check_grid) {
+    if (plan.row_grid) {
         if (pack) {
             const int rc = launch_planes(plan.grid, field, ny, nx, occ_threshold, workspace, st);
             if (rc != ICPMI_OK) return rc;
             a.planes = (const unsigned char*)workspace;
         }
-        gk_check_kernel<<<plan.check_grid, GK_THREADS, 0, st>>>(a);
+        gk_check_kernel<<<plan.row_grid, GK_THREADS, 0, st>>>(a);
         ICPMI_LAUNCH_CHECK();
     }
     gk_status_kernel<<<plan.status_grid, GK_THREADS, 0, st>>>(a);

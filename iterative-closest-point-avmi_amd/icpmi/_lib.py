@@ -55,6 +55,12 @@ GK_INTS, GK_REC_STATUS, GK_REC_ROWS, GK_REC_CONFIRMED, GK_REC_VIOLATED, GK_REC_I
 GK_ST_OK, GK_ST_EMPTY, GK_ST_CAPACITY = 0, 1, 2
 GK_CLASS_CONFIRMED, GK_CLASS_VIOLATED, GK_CLASS_IN_FREE, GK_CLASS_UNEXPLORED, GK_NO_CELLS = 0, 1, 2, 3, -2
 GK_ROW_INTS, GK_ROW_CLASS, GK_ROW_K_HIT, GK_ROW_K, GK_ROW_K_UNKNOWN = 4, 0, 1, 2, 3
+# icpmi_grid_beam_batch (GB_*: the two sizes its kernel is built on, the widest table and the clip of its entries, the slots of
+# a pair's int32 record, its statuses, the index of a row without cells, and the slots of a row's record)
+GB_THREADS, GB_CHUNK_ROWS, GB_MAX_HALF_WIDTH, GB_TABLE_CLIP = 256, 256, 127, 32767
+GB_INTS, GB_REC_STATUS, GB_REC_ROWS, GB_REC_SCORE, GB_REC_EXPECTED, GB_REC_NOVEL, GB_REC_UNEXPLORED = 8, 0, 1, 2, 3, 4, 5
+GB_ST_OK, GB_ST_EMPTY, GB_ST_CAPACITY, GB_NO_CELLS = 0, 1, 2, -2
+GB_ROW_INTS, GB_ROW_INDEX, GB_ROW_K_HIT, GB_ROW_K_Z, GB_ROW_K_UNKNOWN = 4, 0, 1, 2, 3
 # icpmi_pose_graph_optimize: its statuses (PG_ST_*) and the slots of its info record (PGINFO_*: three values, then PHASES clocks)
 PG_ST_NOTHING, PG_ST_CONVERGED, PG_ST_MAXITER, PG_ST_SINGULAR, PG_ST_REFUSED = 0, 1, 2, 3, 4
 PGINFO_DOUBLES, PGINFO_ITERATIONS, PGINFO_STATUS, PGINFO_STEP, PGINFO_PHASE_US, PGINFO_PHASES = 10, 0, 1, 2, 3, 7
@@ -220,6 +226,9 @@ _SIGS = {
     "icpmi_grid_check_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double] +
                                [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                 C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "icpmi_grid_beam_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double] +
+                              [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_int32] +
+                              [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "icpmi_pose_graph_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
     "icpmi_pose_graph_optimize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                             C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_size_t,

@@ -10,7 +10,10 @@ same field back as ranges (``icpmi_grid_occupancy_planes``, ``icpmi_grid_cast_se
 ``occupancy_planes``, ``cast_segments``, ``cast_rays``): along the cells the map's update would lower, the first occupied
 cell and the first unknown cell before it.  The check (``icpmi_grid_check_batch``: ``check_pairs``) walks measured beams over
 the same planes, from the pose to the cell of each row's own hit, and counts per pair the beams the map confirms, the beams
-that came back from behind a wall of the map, and the returns out of observed free or unexplored space.
+that came back from behind a wall of the map, and the returns out of observed free or unexplored space.  The beam model
+(``icpmi_grid_beam_batch``: ``beam_pairs``, ``beam_table``, ``pose_weights``) walks each beam a little past its own hit and
+scores the signed steps between the map's first wall and the beam's return through a table: one number per pair that falls
+smoothly where the check counts classes.
 
 The reference registers a scan against a cloud only (slam.py:53-98, 111-183); this reads the map ``utilities.mapping``
 builds.  The log-odds are quantised to int16 and a candidate's score is the integer sum of the field under the scan's
@@ -277,6 +280,114 @@ def check_pairs(field_or_planes, threshold, min_x, min_y, resolution, cloud_set,
         cs.off_host.ctypes.data_as(C.c_void_p), _ptr(cs.cnt), cs.n_clouds, _ptr(pair), pair_host.ctypes.data_as(C.c_void_p), B, _ptr(t),
         _ptr(rot), tol, _ptr(records), _ptr(rows), stride, _ptr(ws), 0 if ws is None else ws.numel(), _stream()), "grid_check")
     return records, rows
+
+
+def beam_table(resolution, sigma, half_width, z_hit=0.8, z_short=0.1, z_rand=0.1, unexplored=None, scale=1024):
+    """The table ``beam_pairs`` reads, from the beam model's mixture: for a difference of d steps, d = -half_width ...
+    half_width, p(d) = z_hit * exp(-(d * resolution)^2 / (2 sigma^2)) + z_short * [d > 0] + z_rand — a Gaussian about the
+    map's wall, a floor for returns short of it (something in the way) and a floor for anything at all; the two tail entries
+    (a return out of observed free space with no wall near, a return from unexplored space) are z_short + z_rand, the
+    last one ``unexplored`` when that is given.  An entry is max(-32767, rint(scale * ln(p / max p))): 0 at the best
+    difference, negative elsewhere -> int32 [2 * half_width + 3].  ``resolution`` and ``sigma`` in metres; a step is a cell
+    along the beam's major axis, so on a diagonal the same table is up to sqrt(2) wider in metres."""
+    H = int(half_width)
+    if H != half_width or not 0 <= H <= _lib.GB_MAX_HALF_WIDTH:
+        raise ValueError(f"half_width must be a whole number in [0, {_lib.GB_MAX_HALF_WIDTH}], got {half_width}")
+    if not (np.isfinite(resolution) and resolution > 0.0 and np.isfinite(sigma) and sigma > 0.0 and np.isfinite(scale) and scale > 0.0):
+        raise ValueError(f"resolution, sigma and scale must be positive and finite, got {resolution}, {sigma}, {scale}")
+    tail = z_short + z_rand
+    weights = [z_hit, z_short, z_rand, tail if unexplored is None else unexplored]
+    if not all(np.isfinite(w) and w >= 0.0 for w in weights) or not z_hit + z_rand > 0.0:
+        raise ValueError("the mixture's weights must be finite and not negative, and z_hit + z_rand positive")
+    d = np.arange(-H, H + 1, dtype=np.float64)
+    p = z_hit * np.exp(-(d * resolution) ** 2 / (2.0 * float(sigma) ** 2)) + z_short * (d > 0) + z_rand
+    p = np.concatenate([p, [tail, weights[3]]])
+    with np.errstate(divide="ignore"):
+        return np.maximum(-float(_lib.GB_TABLE_CLIP), np.rint(scale * np.log(p / p.max()))).astype(np.int32)
+
+
+def pose_weights(score, temperature=1.0, scale=1024, status=None):
+    """Scores of ``beam_pairs`` (made with a table of that ``scale``) as normalised weights, in NumPy on the host:
+    w = softmax(score / (scale * temperature)), computed about the maximum, and the effective sample size ess = 1 / sum(w^2)
+    -> (w float64, ess).  ``temperature`` > 1 flattens the weights: the beams of a scan are not independent, and a filter
+    that multiplies hundreds of them as if they were collapses onto one particle.  ``status``: the records' statuses; a pose
+    whose status is not OK gets weight 0 (all of them: every weight 0 and ess 0.0)."""
+    s = np.asarray(score, dtype=np.float64).reshape(-1)
+    if not (np.isfinite(temperature) and temperature > 0.0 and np.isfinite(scale) and scale > 0.0):
+        raise ValueError(f"temperature and scale must be positive and finite, got {temperature}, {scale}")
+    keep = np.ones(len(s), dtype=bool) if status is None else np.asarray(status).reshape(-1) == _lib.GB_ST_OK
+    if len(keep) != len(s):
+        raise ValueError(f"{len(s)} scores but {len(keep)} statuses")
+    w = np.zeros(len(s))
+    if not keep.any():
+        return w, 0.0
+    z = s[keep] / (float(scale) * float(temperature))
+    e = np.exp(z - z.max())
+    w[keep] = e / e.sum()
+    return w, float(1.0 / np.sum(w * w))
+
+
+def beam_pairs(field_or_planes, threshold, min_x, min_y, resolution, cloud_set, pair_clouds, translations, cos_sin, table, half_width,
+               beyond, want_hist=False, want_rows=False, out=None):
+    """``icpmi_grid_beam_batch``: the beam model.  Pair b holds cloud ``pair_clouds[b]`` of ``cloud_set`` (sensor frame, 2-D)
+    at the translation ``translations[b]`` and the rotation ``cos_sin[b]`` = (cos, sin) against the map as ``cast_segments``
+    takes it.  Every row's beam is walked from the pose's cell through the cell of its own hit to a far end ``beyond`` metres
+    behind it; k_hit is the step of the map's first occupied cell on that walk and k_z the step at which the beam returned,
+    both on the walk's major axis.  The row adds ``table[i]`` (clipped to +-32767) to the pair's score, i =
+    clamp(k_hit - k_z, -H, H) + H where the map has a wall on the walk (positive differences: the beam came back short of
+    it; negative: from behind it), else 2H + 1 for a return out of observed free space and 2H + 2 for one from unexplored
+    space or off the grid; H = ``half_width``, ``table`` int32 [2H + 3] (``beam_table``; an array or a device tensor).
+    Differences are in steps along the major axis — cells along an axis, up to sqrt(2) cells in metres along a diagonal —
+    as the check's tolerance is.  -> (records, hist, rows): the (B, GB_INTS) int32 device tensor of records [status, rows
+    with cells, score, expected (rows with k_hit >= 0), novel (index 2H + 1), unexplored (index 2H + 2), 0, 0]; with
+    ``want_hist`` the (B, 2H + 3) int32 rows per index (else None); with ``want_rows`` the (B, stride, GB_ROW_INTS) int32
+    [i, k_hit, k_z, k_unknown] per row (else None) — stride the largest named cloud, a row without cells is [GB_NO_CELLS, 0,
+    0, -1], and what lies at or behind a cloud's count is not written.  ``out``: a records tensor, or the triple (records,
+    hist, rows) with None for what is not asked for, to write into.  The rows are the caller's own float64 (arrays or device
+    tensors).  Enqueues and does not synchronise."""
+    field, planes, ws, ny, nx, thr, dev = _cast_source(field_or_planes, threshold)
+    cs = cloud_set
+    if cs.dim != 2:
+        raise ValueError("the beam model is 2-D")
+    if cs.pts.device != dev:
+        raise ValueError(f"the clouds live on {cs.pts.device}, the map on {dev}")
+    if not (np.isfinite(resolution) and resolution > 0.0) or not (np.isfinite(min_x) and np.isfinite(min_y)):
+        raise ValueError(f"resolution must be positive and finite and the map's corner finite, got {resolution}, ({min_x}, {min_y})")
+    H = int(half_width)
+    if H != half_width or not 0 <= H <= _lib.GB_MAX_HALF_WIDTH:
+        raise ValueError(f"half_width must be a whole number in [0, {_lib.GB_MAX_HALF_WIDTH}], got {half_width}")
+    if not (np.isfinite(beyond) and beyond >= 0.0):
+        raise ValueError(f"beyond must be finite and not negative, got {beyond}")
+    if not isinstance(table, torch.Tensor):
+        host = np.asarray(table)
+        if host.dtype.kind not in "iu" or host.size and np.abs(host.astype(np.int64)).max() >= 2 ** 31:
+            raise ValueError("table must hold int32 entries")
+        table = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32))
+    if table.dtype != torch.int32 or tuple(table.shape) != (2 * H + 3,):
+        raise ValueError(f"table must be int32 [{2 * H + 3}] for a half width of {H}, got {table.dtype} {tuple(table.shape)}")
+    table = table.to(dev).contiguous()
+    pair_host = np.ascontiguousarray(pair_clouds, dtype=np.int32).reshape(-1)
+    B = len(pair_host)
+    if B and (pair_host.min() < 0 or pair_host.max() >= cs.n_clouds):
+        raise ValueError("pair_clouds must index the cloud set")
+    named = np.diff(cs.off_host).astype(np.int64)[pair_host]
+    if B and int(named.max()) > MAX_ROWS:
+        raise ValueError(f"a cloud above {MAX_ROWS} rows cannot be scored: filter it first")
+    if int(named.sum()) >= 2 ** 29:
+        raise ValueError(f"{int(named.sum())} rows: fewer than 2^29 fit one call")
+    stride = int(named.max()) if B else 0
+    t, rot = _rows_f64(translations, 2, "translations", dev, B), _rows_f64(cos_sin, 2, "cos_sin", dev, B)
+    rec_out, hist_out, rows_out = (out, None, None) if out is None or isinstance(out, torch.Tensor) else out
+    records = _cast_out(rec_out, (B, _lib.GB_INTS), dev)
+    hist = _cast_out(hist_out, (B, 2 * H + 3), dev) if want_hist else None
+    rows = _cast_out(rows_out, (B, stride, _lib.GB_ROW_INTS), dev) if want_rows else None
+    pair = torch.from_numpy(pair_host).to(dev)
+    check(_lib.lib().icpmi_grid_beam_batch(
+        _ptr(field), _ptr(planes), ny, nx, thr, float(min_x), float(min_y), float(resolution), _ptr(cs.pts), _ptr(cs.off),
+        cs.off_host.ctypes.data_as(C.c_void_p), _ptr(cs.cnt), cs.n_clouds, _ptr(pair), pair_host.ctypes.data_as(C.c_void_p), B, _ptr(t),
+        _ptr(rot), float(beyond), H, _ptr(table), _ptr(records), _ptr(hist), _ptr(rows), stride, _ptr(ws), 0 if ws is None else ws.numel(),
+        _stream()), "grid_beam")
+    return records, hist, rows
 
 
 def ray_end_cells(min_x, min_y, resolution, poses_xy, pose_cs, beam_cs, reach):

@@ -489,13 +489,19 @@ class OccupancyGrid2D:
         info["in_free_share"] = np.where(info["rows"] > 0, info["in_free"] / some, 0.0)
         info["shift_bits"] = k
         if want_rows:
-            n = np.diff(cs.off_host).astype(np.int64)
-            if cs.cnt is not None:
-                n = np.minimum(n, cs.cnt.cpu().numpy().astype(np.int64))
-            n = np.where(info["status"] == _lib.GK_ST_CAPACITY, 0, n[pair_clouds])
-            host = rows.cpu().numpy()
-            info["classes"] = [host[b, :n[b]].copy() for b in range(len(pair_clouds))]
+            info["classes"] = self._rows_per_pair(cs, pair_clouds, rows, info["status"] == _lib.GK_ST_CAPACITY)
         return info
+
+    @staticmethod
+    def _rows_per_pair(cs, pair_clouds, rows, refused):
+        """The rows' records of the check or the beam model, per pair, cut to the cloud's count (none where the count was
+        ``refused``: nothing was read)."""
+        n = np.diff(cs.off_host).astype(np.int64)
+        if cs.cnt is not None:
+            n = np.minimum(n, cs.cnt.cpu().numpy().astype(np.int64))
+        n = np.where(refused, 0, n[pair_clouds])
+        host = rows.cpu().numpy()
+        return [host[b, :n[b]].copy() for b in range(len(pair_clouds))]
 
     def check_scans(self, clouds, poses, tolerance=2, occupied_log_odds=0.5, voxel_size=None, field=None, planes=None, want_rows=False):
         """Does each scan of ``clouds`` (sensor frame, (n, 2) arrays or a device ``CloudSet``), held at its pose of ``poses``
@@ -550,6 +556,89 @@ class OccupancyGrid2D:
         from icpmi import history as _h
         ids = _h._scan_ids(ids, ("ids", "scan ids"), history.n_scans)
         return self._check_set(self._history_rows(history, voxel_size), ids, poses, tolerance, occupied_log_odds, field, planes, want_rows)
+
+    # ── the beam model: measured scans scored against the ranges the map expects (icpmi.gridmatch.beam_pairs) ───────────
+    def _beam_set(self, cs, pair_clouds, poses, sigma, half_width, beyond, table, occupied_log_odds, field, planes, want_histogram, want_rows):
+        from icpmi import gridmatch
+        src, k, threshold = self._cast_map(occupied_log_odds, field, planes)
+        if cs.pts.device != self._dev:
+            raise ValueError(f"the clouds live on {cs.pts.device}, the grid on {self._dev}")
+        pair_clouds = np.ascontiguousarray(pair_clouds, dtype=np.int32).reshape(-1)
+        xyt = self._xytheta(poses, len(pair_clouds))
+        cos_sin = np.stack([np.cos(xyt[:, 2]), np.sin(xyt[:, 2])], axis=1)
+        if table is None:
+            table = gridmatch.beam_table(self.resolution, self.resolution if sigma is None else sigma, half_width)
+        if beyond is None:
+            beyond = 1.5 * (int(half_width) + 2) * self.resolution
+        records, hist, rows = gridmatch.beam_pairs(src, threshold, self.min_x, self.min_y, self.resolution, cs, pair_clouds, xyt[:, :2], cos_sin,
+                                                   table, half_width, beyond, want_hist=want_histogram, want_rows=want_rows)
+        rec = records.cpu().numpy().astype(np.int64)
+        info = {key: rec[:, slot].copy() for key, slot in (
+            ("status", _lib.GB_REC_STATUS), ("rows", _lib.GB_REC_ROWS), ("score", _lib.GB_REC_SCORE), ("expected", _lib.GB_REC_EXPECTED),
+            ("novel", _lib.GB_REC_NOVEL), ("unexplored", _lib.GB_REC_UNEXPLORED))}
+        info["mean_score"] = np.where(info["rows"] > 0, info["score"] / np.maximum(info["rows"], 1), 0.0)
+        info["shift_bits"] = k
+        if want_histogram:
+            info["histogram"] = hist.cpu().numpy().astype(np.int64)
+        if want_rows:
+            info["classes"] = self._rows_per_pair(cs, pair_clouds, rows, info["status"] == _lib.GB_ST_CAPACITY)
+        return info
+
+    def beam_scans(self, clouds, poses, sigma=None, half_width=8, beyond=None, table=None, occupied_log_odds=0.5, voxel_size=None, field=None,
+                   planes=None, want_histogram=False, want_rows=False):
+        """The beam model: how well does each scan of ``clouds`` (sensor frame, (n, 2) arrays or a device ``CloudSet``), held at
+        its pose of ``poses`` ([x, y, theta] rows or 3 x 3 matrices), agree with the ranges this map expects?  Every measured
+        beam is walked from the pose's cell through the cell of its own hit to ``beyond`` metres behind it; the signed number
+        of steps d between the map's first occupied cell (log-odds >= ``occupied_log_odds``) and the step at which the beam
+        returned picks ``table[clamp(d, -H, H) + H]``, H = ``half_width``: d > 0, the beam came back short of the map's wall;
+        d < 0, from behind it.  A beam without a wall on its walk reads ``table[2H + 1]`` where it returned out of observed
+        free space and ``table[2H + 2]`` where it returned from unexplored space or off the grid.  The score of a scan is the
+        sum over its beams — a log-likelihood in units of 1 / 1024 with the default table, which falls smoothly where
+        ``check_scans`` counts four classes with a hard tolerance and ``score_poses`` cannot see the free space a beam
+        crossed; ``icpmi.gridmatch.pose_weights`` turns scores into a particle filter's weights.  One launch for all scans.
+        ``sigma``: the Gaussian's width in metres (None: one cell); ``beyond``: None for 1.5 * (half_width + 2) * resolution,
+        enough for H + 1 major steps past the return on any bearing; ``table``: int32 [2H + 3] to read instead of
+        ``icpmi.gridmatch.beam_table(resolution, sigma, half_width)``.  Differences are steps along a beam's major axis: a
+        cell along an axis, up to sqrt(2) cells in metres along a diagonal.  ``voxel_size``, ``field``, ``planes`` as for
+        ``check_scans``.
+        -> info: int64 arrays ``status`` (``icpmi._lib.GB_ST_*``), ``rows`` (the rows with cells), ``score``, ``expected`` (rows
+        with a wall of the map on their walk), ``novel`` (index 2H + 1), ``unexplored`` (index 2H + 2; the three sum to
+        ``rows``); ``mean_score`` (score / rows, 0.0 where rows is 0); ``shift_bits``.  With ``want_histogram``,
+        ``histogram`` (B, 2H + 3): the rows per index.  With ``want_rows``, ``classes``: per scan an (n, 4) int32 array [index,
+        k_hit, k_z, k_unknown] per row (``GB_NO_CELLS`` for a row without cells)."""
+        from icpmi import gridmatch
+        cs = gridmatch.cloud_set_of(clouds, voxel_size)
+        return self._beam_set(cs, np.arange(cs.n_clouds), poses, sigma, half_width, beyond, table, occupied_log_odds, field, planes,
+                              want_histogram, want_rows)
+
+    def beam_scan(self, points_local, pose, sigma=None, half_width=8, beyond=None, table=None, occupied_log_odds=0.5, voxel_size=None,
+                  field=None, planes=None, want_histogram=False, want_rows=False):
+        """``beam_scans`` of one scan at one pose ([x, y, theta] or a 3 x 3 matrix) -> info with scalar entries (``histogram``:
+        the one (2H + 3,) array; ``classes``: the one (n, 4) array)."""
+        p = np.asarray(pose, dtype=np.float64)
+        info = self.beam_scans([points_local], p[None] if p.ndim == 2 else p.reshape(1, 3), sigma, half_width, beyond, table,
+                               occupied_log_odds, voxel_size, field, planes, want_histogram, want_rows)
+        return {k: (v[0] if isinstance(v, (np.ndarray, list)) else v) for k, v in info.items()}
+
+    def beam_poses(self, points_local, poses, sigma=None, half_width=8, beyond=None, table=None, occupied_log_odds=0.5, field=None,
+                   planes=None, want_histogram=False, want_rows=False):
+        """``beam_scans`` of ONE scan at every pose of ``poses`` ((P, 3) rows [x, y, theta] or 3 x 3 matrices): the scan is
+        uploaded once and every hypothesis names it — a particle filter's measurement update (``icpmi.gridmatch.pose_weights``
+        of ``score`` and ``status``), or a ranking of loop-closure candidates -> info with (P,) entries."""
+        from icpmi import gridmatch
+        cs = gridmatch.cloud_set_of([points_local])
+        xyt = self._xytheta(poses)
+        return self._beam_set(cs, np.zeros(len(xyt), dtype=np.int32), xyt, sigma, half_width, beyond, table, occupied_log_odds, field,
+                              planes, want_histogram, want_rows)
+
+    def beam_history(self, history, ids, poses, sigma=None, half_width=8, beyond=None, table=None, occupied_log_odds=0.5, voxel_size=None,
+                     field=None, planes=None, want_histogram=False, want_rows=False):
+        """``beam_scans`` of scans resident in an ``icpmi.ScanHistory``, by id: the rows are read where they are and no scan
+        is uploaded; ``voxel_size`` chooses them as in ``match_history``."""
+        from icpmi import history as _h
+        ids = _h._scan_ids(ids, ("ids", "scan ids"), history.n_scans)
+        return self._beam_set(self._history_rows(history, voxel_size), ids, poses, sigma, half_width, beyond, table, occupied_log_odds,
+                              field, planes, want_histogram, want_rows)
 
     @staticmethod
     def _history_rows(history, voxel_size):
