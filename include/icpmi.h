@@ -1039,7 +1039,7 @@ int icpmi_grid_cast_rays(const int16_t* field, const void* planes, int32_t ny, i
  * Launches: one memset of the records; gc_planes_kernel (only when the call packs); gk_check_kernel — a workgroup of
  * ICPMI_GK_THREADS threads per (pair, chunk of ICPMI_GK_CHUNK_ROWS rows), a lane per row, a wave 64 consecutive rows of one
  * pair; ballots count the classes per wave, LDS per workgroup, one int32 atomicAdd per non-zero counter per workgroup —
- * (only when a named cloud has rows); and gk_status_kernel, a lane per pair, which settles the status. */
+ * (only when a named cloud has rows); and pair_status_kernel, a lane per pair, which settles the status. */
 #define ICPMI_GK_THREADS 256
 #define ICPMI_GK_CHUNK_ROWS 256
 #define ICPMI_GK_MAX_TOLERANCE 1073741824
@@ -1120,7 +1120,7 @@ int icpmi_grid_check_batch(const int16_t* field, const void* planes, int32_t ny,
  * Launches: one memset of the records and one of the histograms when asked for; gc_planes_kernel (only when the call
  * packs); gb_beam_kernel — a workgroup of ICPMI_GB_THREADS threads per (pair, chunk of ICPMI_GB_CHUNK_ROWS rows), a lane per
  * row; the clipped table and the chunk's histogram in LDS, the score summed per wave, one int32 atomicAdd per non-zero slot
- * and bin per workgroup — (only when a named cloud has rows); and gb_status_kernel, a lane per pair. */
+ * and bin per workgroup — (only when a named cloud has rows); and pair_status_kernel, a lane per pair. */
 #define ICPMI_GB_THREADS 256
 #define ICPMI_GB_CHUNK_ROWS 256
 #define ICPMI_GB_MAX_HALF_WIDTH 127

@@ -124,20 +124,18 @@ int launch_planes(const GcPlan& plan, const int16_t* field, int ny, int nx, int 
     return ICPMI_OK;
 }
 
-// The part the two cast entries share: the planes are the caller's, or packed from the field into the workspace first
+// The part the two cast entries share (where the planes come from is gridcast.hpp's resolve_planes)
 static int cast(const GcPlan& plan, GcArgs a, const int16_t* field, const void* planes, int threshold, int32_t* out,
                 void* workspace, size_t workspace_bytes, hipStream_t st) {
     if (!plan.cast_blocks) return ICPMI_OK;
     if (!out || misaligned16(out)) return ICPMI_ERR_ARG;
-    if (!planes && plan.plane_blocks) {
-        if (!field || misaligned16(field)) return ICPMI_ERR_ARG;
-        if (!workspace || misaligned16(workspace) || workspace_bytes < plan.plane_bytes) return ICPMI_ERR_WORKSPACE;
-        const int rc = launch_planes(plan, field, a.ny, a.nx, threshold, workspace, st);
+    const GcSource src = resolve_planes(plan, field, planes, workspace, workspace_bytes);
+    if (src.rc != ICPMI_OK) return src.rc;
+    if (src.pack) {
+        const int rc = launch_planes(plan, field, a.ny, a.nx, threshold, src.workspace, st);
         if (rc != ICPMI_OK) return rc;
-        planes = workspace;
     }
-    if (planes && misaligned16(planes)) return ICPMI_ERR_ARG;
-    a.planes = (const unsigned char*)planes;                       // (null only for an empty grid: no step is inside it)
+    a.planes = (const unsigned char*)src.planes;
     a.wpp = plan.wpp;
     a.out = reinterpret_cast<int4*>(out);
     gc_cast_kernel<<<plan.cast_blocks, GC_THREADS, 0, st>>>(a);

@@ -1,6 +1,7 @@
-// gridcast.hpp — what the kernels that read the occupancy planes share (gridcast.hip: the cast; gridcheck.hip: the check of
-// measured beams): the layout of the planes, the walk of one segment over them, the plan of the grid and the launch that
-// packs a field into planes.  Each exists once, so the cast and the check read the map through one copy.
+// gridcast.hpp — what the kernels that read the occupancy planes share (gridcast.hip: the cast; gridcheck.hip, gridbeam.hip:
+// the check and the beam model of measured beams): the layout of the planes, the walk of one segment over them, the read of
+// one cell's unknown bit, the plan of the grid, where a call's planes come from and the launch that packs a field into
+// planes.  Each exists once, so the three read the map through one copy.
 #pragma once
 #include "raywalk.hpp"
 
@@ -72,7 +73,14 @@ __device__ __forceinline__ int4 gc_walk(const unsigned char* __restrict__ planes
     return make_int4(k_hit, xh, yh, k_unk);
 }
 
-// ── host: the plan, the packing launch ───────────────────────────────────────
+// One more masked read: is cell (x, y) observed space — its unknown bit clear?  A cell outside the grid is not.
+__device__ __forceinline__ bool gc_observed(const unsigned char* __restrict__ planes, const GcPlanes& L, int ny, int nx, int x, int y) {
+    if ((unsigned)x >= (unsigned)nx || (unsigned)y >= (unsigned)ny) return false;
+    const uint32_t* unk = reinterpret_cast<const uint32_t*>(planes + L.unk);
+    return !(unk[(uint32_t)y * (uint32_t)L.wpr + (uint32_t)(x >> 5)] & (1u << (x & 31)));
+}
+
+// ── host: the plan, the source of the planes, the packing launch ─────────────
 // What a call starts, decided as a whole and without a HIP call
 struct GcPlan {
     int rc;                   // ICPMI_OK, or why nothing is launched
@@ -97,6 +105,23 @@ inline GcPlan plan_cast(int ny, int nx, long long n_poses, long long n_beams) {
 }
 
 inline bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
+
+// Where a call's planes come from: the caller's, or packed from the field into the workspace first.  Decided without a HIP
+// call, so that a caller enqueues nothing before every refusal has been made; launch_planes into `workspace` where `pack`.
+struct GcSource {
+    int rc;                   // ICPMI_OK, or the refusal
+    const void* planes;       // what the kernel reads (null only for an empty grid: no step is inside it)
+    bool pack;
+    void* workspace;
+};
+inline GcSource resolve_planes(const GcPlan& plan, const int16_t* field, const void* planes, void* workspace, size_t workspace_bytes) {
+    GcSource s{ICPMI_OK, planes, !planes && plan.plane_blocks, workspace};
+    if (planes && misaligned16(planes)) s.rc = ICPMI_ERR_ARG;
+    else if (s.pack && (!field || misaligned16(field))) s.rc = ICPMI_ERR_ARG;
+    else if (s.pack && (!workspace || misaligned16(workspace) || workspace_bytes < plan.plane_bytes)) s.rc = ICPMI_ERR_WORKSPACE;
+    if (s.pack) s.planes = workspace;
+    return s;
+}
 
 // gc_planes_kernel of `field` into `planes` (gridcast.hip): ICPMI_OK, at once where the plan has nothing to pack
 int launch_planes(const GcPlan& plan, const int16_t* field, int ny, int nx, int threshold, void* planes, hipStream_t st);

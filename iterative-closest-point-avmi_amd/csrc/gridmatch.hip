@@ -48,17 +48,13 @@ template <int NS>
 __global__ __launch_bounds__(GM_THREADS) void gm_score_kernel(GmArgs a) {
     __shared__ GmLds lds;
     const int tid = threadIdx.x;
-    const int chunk = blockIdx.x % a.n_chunks;
-    const int ang = (blockIdx.x / a.n_chunks) % a.n_angles;
-    const int b = blockIdx.x / (a.n_chunks * a.n_angles);
-    const int c = a.pair_cloud[b];
-    const int N = gm_rows(a, c);
-    const int base = chunk * GM_CHUNK;
-    if (base >= N) return;                                     // uniform per workgroup, before any barrier
+    const GmFrame f = gm_frame(a.pairs, blockIdx.x, a.n_chunks, a.n_angles);
+    if (f.base >= f.N) return;                                 // uniform per workgroup, before any barrier
+    const int b = f.b, ang = f.ang;
     const int W = a.window, S = 2 * W + 1, S2 = S * S;
     if (NS == 1) lds.acc[tid] = 0;
     // a row whose whole window misses the grid adds 0 to every candidate: dropped in phase 1
-    const int kept = gm_form_cells(lds, a, b, ang, c, N, base, GmReach{-W, W, -W, W, a.nx, a.ny});
+    const int kept = gm_form_cells(lds, a, b, ang, f.c, f.N, f.base, GmReach{-W, W, -W, W, a.nx, a.ny});
     if (tid == 0 && lds.valid) atomicAdd(a.valid + (size_t)b * a.n_angles + ang, lds.valid);
     if (kept == 0) return;                                     // uniform
     gm_accumulate<NS>(lds, a.field, a.nx, a.ny, kept, S2, S, 1, -W, 0, a.volume + ((size_t)b * a.n_angles + ang) * S2);
@@ -86,10 +82,9 @@ __global__ __launch_bounds__(GM_THREADS) void gm_argmax_kernel(GmArgs a) {
     any = __syncthreads_or(any);
     if (tid != 0) return;
     for (int w = 1; w < GM_WAVES; ++w) take_first_best(best, at, wave_v[w], wave_i[w], greater);
-    const int N = gm_rows(a, a.pair_cloud[b]);
     const int ang = at / S2, rem = at - ang * S2;
     int32_t* rec = a.records + (size_t)b * ICPMI_GMREC_INTS;
-    rec[ICPMI_GMREC_STATUS] = N < 0 ? ICPMI_GM_ST_CAPACITY : (any ? ICPMI_GM_ST_OK : ICPMI_GM_ST_EMPTY);
+    rec[ICPMI_GMREC_STATUS] = gm_status(gm_rows(a.pairs, a.pairs.pair_cloud[b]), any);
     rec[ICPMI_GMREC_ROWS] = valid[ang];
     rec[ICPMI_GMREC_INDEX] = at;
     rec[ICPMI_GMREC_A] = ang;
@@ -173,28 +168,19 @@ extern "C" int icpmi_grid_match_batch(const int16_t* field, int32_t ny, int32_t 
                                       void* workspace, size_t workspace_bytes, void* stream) {
     using namespace icpmi;
     if (n_pairs == 0) return ICPMI_OK;
-    if (n_pairs < 0 || n_clouds < 0 || !off_host || !pair_cloud_host) return ICPMI_ERR_ARG;
-    int max_n = 0;
-    for (int b = 0; b < n_pairs; ++b) {
-        const int c = pair_cloud_host[b];
-        if (c < 0 || c >= n_clouds) return ICPMI_ERR_ARG;
-        const int rows = off_host[c + 1] - off_host[c];
-        if (rows < 0) return ICPMI_ERR_ARG;
-        max_n = rows > max_n ? rows : max_n;
-    }
-    const GmPlan plan = plan_grid_match(n_pairs, max_n, n_angles, window);
+    const PairScan pairs = scan_pairs(n_pairs, n_clouds, off_host, pair_cloud_host);
+    if (pairs.rc != ICPMI_OK) return pairs.rc;
+    const GmPlan plan = plan_grid_match(n_pairs, pairs.max_n, n_angles, window);
     if (plan.rc != ICPMI_OK) return plan.rc;
     if (!field || !pts || !off_dev || !pair_cloud || !pair_t || !cos_sin || !out_records || !workspace) return ICPMI_ERR_ARG;
     if (ny < 1 || nx < 1 || ny > GM_CELL_MAX || nx > GM_CELL_MAX || (long long)ny * nx >= (1ll << 31)) return ICPMI_ERR_ARG;
-    if (!(resolution > 0.0) || !(fabs(resolution) < __builtin_inf()) || !(fabs(min_x) < __builtin_inf()) || !(fabs(min_y) < __builtin_inf()))
-        return ICPMI_ERR_ARG;
-    if (centre_angle >= n_angles) return ICPMI_ERR_ARG;
+    if (!world_ok(resolution, min_x, min_y) || centre_angle >= n_angles) return ICPMI_ERR_ARG;
     const int S = 2 * window + 1;
     const GmWs ws(workspace, (size_t)n_pairs, (size_t)n_angles, (size_t)S * S);
     if (workspace_bytes < ws.bytes()) return ICPMI_ERR_WORKSPACE;
 
     int32_t* volume = out_scores ? out_scores : ws.volume;
-    const GmArgs a{(const short*)field, ny, nx, min_x, min_y, resolution, pts, off_dev, cnt_dev, pair_cloud, pair_t, cos_sin,
+    const GmArgs a{(const short*)field, ny, nx, {min_x, min_y, resolution, pts, off_dev, cnt_dev, pair_cloud, pair_t, cos_sin},
                    n_angles, window, centre_angle, plan.n_chunks, ws.valid, volume, out_records};
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(ws.valid, 0, plan.valid_bytes, st) != hipSuccess) return ICPMI_ERR_HIP;

@@ -1,8 +1,9 @@
 // gridmatch.hpp — what the scan-to-map kernels share (gridmatch.hip: the exhaustive window; gridmatch_wide.hip: the pruned
-// wide window): the arguments, the rule for a cloud's rows, the cell of a row, the workgroup's LDS, phase 1 (the cells of a
-// chunk of rows) and the branch-free walk of a lane's shifts over those cells.  Each exists once.
+// wide window): the arguments, the cell of a row, the workgroup's LDS, phase 1 (the cells of a chunk of rows) and the
+// branch-free walk of a lane's shifts over those cells.  Each exists once.  The pair list, the rule for a cloud's rows and
+// the frame of a workgroup are gridpairs.hpp's; the check and the beam model form their cells with gm_cell too.
 #pragma once
-#include "common.hpp"
+#include "gridpairs.hpp"
 
 namespace icpmi {
 
@@ -11,33 +12,18 @@ constexpr int GM_WAVES = GM_THREADS / ICPMI_WAVE;
 constexpr int GM_CHUNK = ICPMI_GM_CHUNK_ROWS;              // source rows of one workgroup
 constexpr int GM_CELL_MAX = 1 << 29;                       // a row whose cell lies beyond +-2^29 is not scored
 constexpr int GM_FAR = 1 << 30;                            // an offset no cell reaches the grid with (nx, ny <= 2^29)
-static_assert(GM_CHUNK == GM_THREADS, "a thread forms one cell of the chunk");
+static_assert(GM_CHUNK == GM_THREADS && GM_CHUNK == PAIR_THREADS, "a thread forms one cell of the chunk; gm_frame's chunk");
 static_assert((long long)ICPMI_GM_MAX_ROWS * 32767 < (1ll << 31), "a score is an int32");
 
 struct GmArgs {
     const short* field;
     int ny, nx;
-    double min_x, min_y, res;
-    const double* pts;
-    const int32_t* off;
-    const int32_t* cnt;
-    const int32_t* pair_cloud;
-    const double* pair_t;
-    const double* cos_sin;
+    GmPairs pairs;           // cos_sin: [n_pairs][n_angles][2]
     int n_angles, window, centre_angle, n_chunks;
     int32_t* valid;          // [n_pairs][n_angles]: rows with a cell, per angle
     int32_t* volume;         // [n_pairs][n_angles][S][S]
     int32_t* records;
 };
-
-// rows of a pair's cloud: the device count where the set has one; -1 for a count that is negative (the voxel filter's
-// overflow mark) or beyond the cloud's own rows or ICPMI_GM_MAX_ROWS — such a cloud is not read (ICPMI_GM_ST_CAPACITY)
-__device__ __forceinline__ int gm_rows(const int32_t* off, const int32_t* cnt, int c) {
-    const int cap = off[c + 1] - off[c];
-    const int n = cnt ? cnt[c] : cap;
-    return n < 0 || n > cap || n > ICPMI_GM_MAX_ROWS ? -1 : n;
-}
-__device__ __forceinline__ int gm_rows(const GmArgs& a, int c) { return gm_rows(a.off, a.cnt, c); }
 
 // floor((w - mn) / res), the IEEE divide of world_to_grid_kernel; false for a non-finite w or a cell beyond +-2^29
 __device__ __forceinline__ bool gm_cell(double w, double mn, double res, int& out) {
@@ -68,18 +54,18 @@ struct GmReach {
 // is counted in lds.valid either way.  -> the kept cells (uniform); behind them lds.cells holds far cells, unless none is kept.
 // Ends in a barrier; the caller's earlier reads of lds.cells, lds.kept and lds.valid must lie behind one too.
 __device__ __forceinline__ int gm_form_cells(GmLds& lds, const GmArgs& a, int b, int ang, int c, int N, int base, const GmReach& reach) {
+    const GmPairs& pl = a.pairs;
     const int tid = threadIdx.x;
     if (tid == 0) { lds.kept = 0; lds.valid = 0; }
     __syncthreads();
     const int row = base + tid;
     if (row < N) {
-        const double* p = a.pts + ((size_t)a.off[c] + row) * 2;
-        const double* cs = a.cos_sin + ((size_t)b * a.n_angles + ang) * 2;
-        const double x = p[0], y = p[1], co = cs[0], si = cs[1];
-        const double wx = (co * x - si * y) + a.pair_t[2 * b];         // as include/icpmi.h states it (no contraction)
-        const double wy = (si * x + co * y) + a.pair_t[2 * b + 1];
+        const double* p = pl.pts + ((size_t)pl.off[c] + row) * 2;
+        const double* cs = pl.cos_sin + ((size_t)b * a.n_angles + ang) * 2;
+        double wx, wy;
+        gm_world(p[0], p[1], cs[0], cs[1], pl.pair_t[2 * b], pl.pair_t[2 * b + 1], wx, wy);
         int cx, cy;
-        if (gm_cell(wx, a.min_x, a.res, cx) && gm_cell(wy, a.min_y, a.res, cy)) {
+        if (gm_cell(wx, pl.min_x, pl.res, cx) && gm_cell(wy, pl.min_y, pl.res, cy)) {
             atomicAdd(&lds.valid, 1);
             if (cx + reach.hi_x >= 0 && cx + reach.lo_x < reach.nx && cy + reach.hi_y >= 0 && cy + reach.lo_y < reach.ny)
                 lds.cells[atomicAdd(&lds.kept, 1)] = make_int2(cx, cy);

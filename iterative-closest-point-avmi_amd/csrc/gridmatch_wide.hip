@@ -117,17 +117,13 @@ __global__ __launch_bounds__(GM_THREADS) void gmw_bound_kernel(GmwArgs w) {
     __shared__ GmLds lds;
     const GmArgs& a = w.g;
     const int tid = threadIdx.x;
-    const int chunk = blockIdx.x % a.n_chunks;
-    const int ang = (blockIdx.x / a.n_chunks) % a.n_angles;
-    const int b = blockIdx.x / (a.n_chunks * a.n_angles);
-    const int c = a.pair_cloud[b];
-    const int N = gm_rows(a, c);
-    const int base = chunk * GM_CHUNK;
-    if (base >= N) return;                                     // uniform per workgroup, before any barrier
+    const GmFrame f = gm_frame(a.pairs, blockIdx.x, a.n_chunks, a.n_angles);
+    if (f.base >= f.N) return;                                 // uniform per workgroup, before any barrier
+    const int b = f.b, ang = f.ang;
     const int nb2 = w.nb * w.nb, origin = w.D - 1 - a.window, nxo = a.nx + w.D - 1, nyo = a.ny + w.D - 1;
     if (NS == 1) lds.acc[tid] = 0;
     const int last = origin + (w.nb - 1) * w.D;
-    const int kept = gm_form_cells(lds, a, b, ang, c, N, base, GmReach{origin, last, origin, last, nxo, nyo});
+    const int kept = gm_form_cells(lds, a, b, ang, f.c, f.N, f.base, GmReach{origin, last, origin, last, nxo, nyo});
     if (tid == 0 && lds.valid) atomicAdd(a.valid + (size_t)b * a.n_angles + ang, lds.valid);
     if (kept == 0) return;                                     // uniform
     int32_t* out = w.U + ((size_t)b * a.n_angles + ang) * nb2;
@@ -172,8 +168,8 @@ __device__ __forceinline__ void gmw_score_block(GmLds& lds, int* wave_v, int* wa
     const int tid = threadIdx.x, g = tid / D2, s = tid - g * D2;
     const int W = a.window, S = 2 * W + 1, nb2 = w.nb * w.nb;
     const int ang = blk / nb2, rem = blk - ang * nb2, J = rem / w.nb, I = rem - J * w.nb;
-    const int c = a.pair_cloud[b];
-    const int N = gm_rows(a, c);
+    const int c = a.pairs.pair_cloud[b];
+    const int N = gm_rows(a.pairs, c);
     const int dx[1] = {I * D - W + s % D}, dy[1] = {J * D - W + s / D};
     int acc[1] = {0};
     lds.acc[tid] = 0;
@@ -266,10 +262,9 @@ __global__ __launch_bounds__(GMW_RECORD_THREADS) void gmw_record_kernel(GmwArgs 
     any = __syncthreads_or(any);
     if (threadIdx.x != 0) return;
     const GmwPair p = w.pair[b];
-    const int N = gm_rows(a, a.pair_cloud[b]);
     const int at = gmw_key_flat(p.best), ang = at / S2, rem = at - ang * S2;
     int32_t* rec = a.records + (size_t)b * ICPMI_GMW_REC_INTS;
-    rec[ICPMI_GMREC_STATUS] = N < 0 ? ICPMI_GM_ST_CAPACITY : (any ? ICPMI_GM_ST_OK : ICPMI_GM_ST_EMPTY);
+    rec[ICPMI_GMREC_STATUS] = gm_status(gm_rows(a.pairs, a.pairs.pair_cloud[b]), any);
     rec[ICPMI_GMREC_ROWS] = valid[ang];
     rec[ICPMI_GMREC_INDEX] = at;
     rec[ICPMI_GMREC_A] = ang;
@@ -379,26 +374,18 @@ extern "C" int icpmi_grid_search_batch(const int16_t* field, const int16_t* boun
                                        int32_t* out_bounds, void* workspace, size_t workspace_bytes, void* stream) {
     using namespace icpmi;
     if (n_pairs == 0) return ICPMI_OK;
-    if (n_pairs < 0 || n_clouds < 0 || !off_host || !pair_cloud_host) return ICPMI_ERR_ARG;
-    int max_n = 0;
-    for (int b = 0; b < n_pairs; ++b) {
-        const int c = pair_cloud_host[b];
-        if (c < 0 || c >= n_clouds) return ICPMI_ERR_ARG;
-        const int rows = off_host[c + 1] - off_host[c];
-        if (rows < 0) return ICPMI_ERR_ARG;
-        max_n = rows > max_n ? rows : max_n;
-    }
-    const GmwPlan plan = plan_grid_search(n_pairs, max_n, n_angles, window, block, centre_angle);
+    const PairScan pairs = scan_pairs(n_pairs, n_clouds, off_host, pair_cloud_host);
+    if (pairs.rc != ICPMI_OK) return pairs.rc;
+    const GmwPlan plan = plan_grid_search(n_pairs, pairs.max_n, n_angles, window, block, centre_angle);
     if (plan.rc != ICPMI_OK) return plan.rc;
     if (!field || !bound || !pts || !off_dev || !pair_cloud || !pair_t || !cos_sin || !out_records || !workspace) return ICPMI_ERR_ARG;
     if (ny < 1 || nx < 1 || ny > GM_CELL_MAX || nx > GM_CELL_MAX || (long long)(ny + block - 1) * (nx + block - 1) >= (1ll << 31)) return ICPMI_ERR_ARG;
-    if (!(resolution > 0.0) || !(fabs(resolution) < __builtin_inf()) || !(fabs(min_x) < __builtin_inf()) || !(fabs(min_y) < __builtin_inf()))
-        return ICPMI_ERR_ARG;
+    if (!world_ok(resolution, min_x, min_y)) return ICPMI_ERR_ARG;
     const GmwWs ws(workspace, (size_t)n_pairs, (size_t)n_angles, (size_t)plan.nb * plan.nb);
     if (workspace_bytes < ws.bytes()) return ICPMI_ERR_WORKSPACE;
 
     int32_t* U = out_bounds ? out_bounds : ws.U;
-    const GmwArgs w{GmArgs{(const short*)field, ny, nx, min_x, min_y, resolution, pts, off_dev, cnt_dev, pair_cloud, pair_t, cos_sin,
+    const GmwArgs w{GmArgs{(const short*)field, ny, nx, {min_x, min_y, resolution, pts, off_dev, cnt_dev, pair_cloud, pair_t, cos_sin},
                            n_angles, window, centre_angle, plan.n_chunks, ws.valid, nullptr, out_records},
                     (const short*)bound, n_pairs, block, plan.nb, U, ws.seeds, ws.list, ws.n_listed, ws.pair};
     hipStream_t st = (hipStream_t)stream;

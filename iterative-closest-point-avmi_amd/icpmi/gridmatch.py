@@ -237,6 +237,41 @@ def cast_rays(field_or_planes, threshold, min_x, min_y, resolution, poses_xy, po
     return out
 
 
+def _pair_list(cs, pair_clouds):
+    """The pair list every pair entry takes -> (pair_host int32 [B], the rows of each pair's cloud int64 [B], the device copy):
+    a 2-D cloud set, every pair naming one of its clouds, none of them above ``MAX_ROWS`` rows."""
+    if cs.dim != 2:
+        raise ValueError("pairs against the grid are 2-D")
+    pair_host = np.ascontiguousarray(pair_clouds, dtype=np.int32).reshape(-1)
+    if len(pair_host) and (pair_host.min() < 0 or pair_host.max() >= cs.n_clouds):
+        raise ValueError("pair_clouds must index the cloud set")
+    named = np.diff(cs.off_host).astype(np.int64)[pair_host]
+    if len(named) and int(named.max()) > MAX_ROWS:
+        raise ValueError(f"a cloud above {MAX_ROWS} rows cannot be scored (int32 sums): filter it first")
+    return pair_host, named, torch.from_numpy(pair_host).to(cs.pts.device)
+
+
+def _map_pairs(field_or_planes, threshold, min_x, min_y, resolution, cs, pair_clouds, translations, cos_sin):
+    """Pairs of a cloud set against a map, as ``check_pairs`` and ``beam_pairs`` take them -> (head, tail, keep, B, stride,
+    dev): the arguments their C entries begin with (``field`` ... ``cos_sin``) and end with (workspace, bytes, stream), the
+    arrays and tensors those point into (to be held until the call has returned), the pairs, the rows of the largest named
+    cloud and the map's device."""
+    field, planes, ws, ny, nx, thr, dev = _cast_source(field_or_planes, threshold)
+    if cs.pts.device != dev:
+        raise ValueError(f"the clouds live on {cs.pts.device}, the map on {dev}")
+    if not (np.isfinite(resolution) and resolution > 0.0) or not (np.isfinite(min_x) and np.isfinite(min_y)):
+        raise ValueError(f"resolution must be positive and finite and the map's corner finite, got {resolution}, ({min_x}, {min_y})")
+    pair_host, named, pair = _pair_list(cs, pair_clouds)
+    B = len(pair_host)
+    if int(named.sum()) >= 2 ** 29:
+        raise ValueError(f"{int(named.sum())} rows: fewer than 2^29 fit one call")
+    t, rot = _rows_f64(translations, 2, "translations", dev, B), _rows_f64(cos_sin, 2, "cos_sin", dev, B)
+    head = (_ptr(field), _ptr(planes), ny, nx, thr, float(min_x), float(min_y), float(resolution), _ptr(cs.pts), _ptr(cs.off),
+            cs.off_host.ctypes.data_as(C.c_void_p), _ptr(cs.cnt), cs.n_clouds, _ptr(pair), pair_host.ctypes.data_as(C.c_void_p), B, _ptr(t),
+            _ptr(rot))
+    return head, (_ptr(ws), 0 if ws is None else ws.numel(), _stream()), (pair_host, pair, t, rot, ws), B, int(named.max()) if B else 0, dev
+
+
 def check_pairs(field_or_planes, threshold, min_x, min_y, resolution, cloud_set, pair_clouds, translations, cos_sin, tolerance,
                 want_rows=False, out=None):
     """``icpmi_grid_check_batch``: pair b holds cloud ``pair_clouds[b]`` of ``cloud_set`` (sensor frame, 2-D) at the
@@ -249,36 +284,15 @@ def check_pairs(field_or_planes, threshold, min_x, min_y, resolution, cloud_set,
     cloud; what lies at or behind a cloud's count is not written.  ``out``: a records tensor, or with ``want_rows`` the pair
     (records, rows), to write into.  The rows are the caller's own float64 (arrays or device tensors).  Enqueues and does not
     synchronise."""
-    field, planes, ws, ny, nx, thr, dev = _cast_source(field_or_planes, threshold)
-    cs = cloud_set
-    if cs.dim != 2:
-        raise ValueError("the check is 2-D")
-    if cs.pts.device != dev:
-        raise ValueError(f"the clouds live on {cs.pts.device}, the map on {dev}")
-    if not (np.isfinite(resolution) and resolution > 0.0) or not (np.isfinite(min_x) and np.isfinite(min_y)):
-        raise ValueError(f"resolution must be positive and finite and the map's corner finite, got {resolution}, ({min_x}, {min_y})")
+    head, tail, _keep, B, stride, dev = _map_pairs(field_or_planes, threshold, min_x, min_y, resolution, cloud_set, pair_clouds, translations,
+                                                   cos_sin)       # (_keep: what head and tail point into)
     tol = int(tolerance)
     if tol != tolerance or not 0 <= tol <= _lib.GK_MAX_TOLERANCE:
         raise ValueError(f"tolerance must be a whole number of steps in [0, 2^30], got {tolerance}")
-    pair_host = np.ascontiguousarray(pair_clouds, dtype=np.int32).reshape(-1)
-    B = len(pair_host)
-    if B and (pair_host.min() < 0 or pair_host.max() >= cs.n_clouds):
-        raise ValueError("pair_clouds must index the cloud set")
-    named = np.diff(cs.off_host).astype(np.int64)[pair_host]
-    if B and int(named.max()) > MAX_ROWS:
-        raise ValueError(f"a cloud above {MAX_ROWS} rows cannot be checked: filter it first")
-    if int(named.sum()) >= 2 ** 29:
-        raise ValueError(f"{int(named.sum())} rows: fewer than 2^29 fit one call")
-    stride = int(named.max()) if B else 0
-    t, rot = _rows_f64(translations, 2, "translations", dev, B), _rows_f64(cos_sin, 2, "cos_sin", dev, B)
     rec_out, rows_out = (out if want_rows else (out, None)) if out is not None else (None, None)
     records = _cast_out(rec_out, (B, _lib.GK_INTS), dev)
     rows = _cast_out(rows_out, (B, stride, _lib.GK_ROW_INTS), dev) if want_rows else None
-    pair = torch.from_numpy(pair_host).to(dev)
-    check(_lib.lib().icpmi_grid_check_batch(
-        _ptr(field), _ptr(planes), ny, nx, thr, float(min_x), float(min_y), float(resolution), _ptr(cs.pts), _ptr(cs.off),
-        cs.off_host.ctypes.data_as(C.c_void_p), _ptr(cs.cnt), cs.n_clouds, _ptr(pair), pair_host.ctypes.data_as(C.c_void_p), B, _ptr(t),
-        _ptr(rot), tol, _ptr(records), _ptr(rows), stride, _ptr(ws), 0 if ws is None else ws.numel(), _stream()), "grid_check")
+    check(_lib.lib().icpmi_grid_check_batch(*head, tol, _ptr(records), _ptr(rows), stride, *tail), "grid_check")
     return records, rows
 
 
@@ -345,14 +359,8 @@ def beam_pairs(field_or_planes, threshold, min_x, min_y, resolution, cloud_set, 
     0, -1], and what lies at or behind a cloud's count is not written.  ``out``: a records tensor, or the triple (records,
     hist, rows) with None for what is not asked for, to write into.  The rows are the caller's own float64 (arrays or device
     tensors).  Enqueues and does not synchronise."""
-    field, planes, ws, ny, nx, thr, dev = _cast_source(field_or_planes, threshold)
-    cs = cloud_set
-    if cs.dim != 2:
-        raise ValueError("the beam model is 2-D")
-    if cs.pts.device != dev:
-        raise ValueError(f"the clouds live on {cs.pts.device}, the map on {dev}")
-    if not (np.isfinite(resolution) and resolution > 0.0) or not (np.isfinite(min_x) and np.isfinite(min_y)):
-        raise ValueError(f"resolution must be positive and finite and the map's corner finite, got {resolution}, ({min_x}, {min_y})")
+    head, tail, _keep, B, stride, dev = _map_pairs(field_or_planes, threshold, min_x, min_y, resolution, cloud_set, pair_clouds, translations,
+                                                   cos_sin)       # (_keep: what head and tail point into)
     H = int(half_width)
     if H != half_width or not 0 <= H <= _lib.GB_MAX_HALF_WIDTH:
         raise ValueError(f"half_width must be a whole number in [0, {_lib.GB_MAX_HALF_WIDTH}], got {half_width}")
@@ -366,27 +374,12 @@ def beam_pairs(field_or_planes, threshold, min_x, min_y, resolution, cloud_set, 
     if table.dtype != torch.int32 or tuple(table.shape) != (2 * H + 3,):
         raise ValueError(f"table must be int32 [{2 * H + 3}] for a half width of {H}, got {table.dtype} {tuple(table.shape)}")
     table = table.to(dev).contiguous()
-    pair_host = np.ascontiguousarray(pair_clouds, dtype=np.int32).reshape(-1)
-    B = len(pair_host)
-    if B and (pair_host.min() < 0 or pair_host.max() >= cs.n_clouds):
-        raise ValueError("pair_clouds must index the cloud set")
-    named = np.diff(cs.off_host).astype(np.int64)[pair_host]
-    if B and int(named.max()) > MAX_ROWS:
-        raise ValueError(f"a cloud above {MAX_ROWS} rows cannot be scored: filter it first")
-    if int(named.sum()) >= 2 ** 29:
-        raise ValueError(f"{int(named.sum())} rows: fewer than 2^29 fit one call")
-    stride = int(named.max()) if B else 0
-    t, rot = _rows_f64(translations, 2, "translations", dev, B), _rows_f64(cos_sin, 2, "cos_sin", dev, B)
     rec_out, hist_out, rows_out = (out, None, None) if out is None or isinstance(out, torch.Tensor) else out
     records = _cast_out(rec_out, (B, _lib.GB_INTS), dev)
     hist = _cast_out(hist_out, (B, 2 * H + 3), dev) if want_hist else None
     rows = _cast_out(rows_out, (B, stride, _lib.GB_ROW_INTS), dev) if want_rows else None
-    pair = torch.from_numpy(pair_host).to(dev)
-    check(_lib.lib().icpmi_grid_beam_batch(
-        _ptr(field), _ptr(planes), ny, nx, thr, float(min_x), float(min_y), float(resolution), _ptr(cs.pts), _ptr(cs.off),
-        cs.off_host.ctypes.data_as(C.c_void_p), _ptr(cs.cnt), cs.n_clouds, _ptr(pair), pair_host.ctypes.data_as(C.c_void_p), B, _ptr(t),
-        _ptr(rot), float(beyond), H, _ptr(table), _ptr(records), _ptr(hist), _ptr(rows), stride, _ptr(ws), 0 if ws is None else ws.numel(),
-        _stream()), "grid_beam")
+    check(_lib.lib().icpmi_grid_beam_batch(*head, float(beyond), H, _ptr(table), _ptr(records), _ptr(hist), _ptr(rows), stride, *tail),
+          "grid_beam")
     return records, hist, rows
 
 
@@ -528,11 +521,9 @@ class GridMatchBatch:
     def _setup(self, grid, cloud_set, pair_clouds, translations, angle_rows, window, centre_angle, field, max_window, max_angles):
         """The pairs, their angles and the refusals the two searches share; everything but the outputs and the workspace."""
         require_gpu()
-        if cloud_set.dim != 2:
-            raise ValueError("grid matching is 2-D")
         self.grid, self.cs, self.field = grid, cloud_set, field
         dev = cloud_set.pts.device
-        self.pair_host = np.ascontiguousarray(pair_clouds, dtype=np.int32).reshape(-1)
+        self.pair_host, _, self.pair = _pair_list(cloud_set, pair_clouds)
         self.B = B = len(self.pair_host)
         self.t_host = np.ascontiguousarray(np.asarray(translations, dtype=np.float64).reshape(B, 2))
         self.angles = np.ascontiguousarray(np.asarray(angle_rows, dtype=np.float64).reshape(B, -1))
@@ -544,12 +535,7 @@ class GridMatchBatch:
             raise ValueError(f"between 1 and {max_angles} angles per pair, got {self.A}")
         if self.centre_angle >= self.A:
             raise ValueError("centre_angle must be negative (none) or an index into the angle rows")
-        if B and (self.pair_host.min() < 0 or self.pair_host.max() >= cloud_set.n_clouds):
-            raise ValueError("pair_clouds must index the cloud set")
-        if B and int(np.diff(cloud_set.off_host)[self.pair_host].max()) > MAX_ROWS:
-            raise ValueError(f"a cloud above {MAX_ROWS} rows cannot be scored (int32 sums): filter it first")
         self.cos_sin_host = np.ascontiguousarray(np.stack([np.cos(self.angles), np.sin(self.angles)], axis=2))
-        self.pair = torch.from_numpy(self.pair_host).to(dev)
         self.t = torch.from_numpy(self.t_host).to(dev)
         self.cos_sin = torch.from_numpy(self.cos_sin_host).to(dev)
         self.k = shift_bits(grid.log_odds_min, grid.log_odds_max) if field is None else int(field[1])
@@ -566,16 +552,18 @@ class GridMatchBatch:
         self._field_buf = score_field(lo, self.k, self._field_buf)
         return self._field_buf
 
+    def _pair_args(self):
+        """The arguments the two searches' C entries share: the world, the cloud set and the pairs (``min_x`` ... ``n_angles``)."""
+        g, cs = self.grid, self.cs
+        return (float(g.min_x), float(g.min_y), float(g.resolution), _ptr(cs.pts), _ptr(cs.off), cs.off_host.ctypes.data_as(C.c_void_p),
+                _ptr(cs.cnt), cs.n_clouds, _ptr(self.pair), self.pair_host.ctypes.data_as(C.c_void_p), self.B, _ptr(self.t),
+                _ptr(self.cos_sin), self.A)
+
     def run(self):
-        g = self.grid
         fld = self._field()
         ny, nx = fld.shape
-        cs = self.cs
-        check(_lib.lib().icpmi_grid_match_batch(
-            _ptr(fld), ny, nx, float(g.min_x), float(g.min_y), float(g.resolution), _ptr(cs.pts), _ptr(cs.off),
-            cs.off_host.ctypes.data_as(C.c_void_p), _ptr(cs.cnt), cs.n_clouds, _ptr(self.pair),
-            self.pair_host.ctypes.data_as(C.c_void_p), self.B, _ptr(self.t), _ptr(self.cos_sin), self.A, self.W,
-            self.centre_angle, _ptr(self.records), _ptr(self.scores), _ptr(self.ws), self.ws.numel(), _stream()), "grid_match")
+        check(_lib.lib().icpmi_grid_match_batch(_ptr(fld), ny, nx, *self._pair_args(), self.W, self.centre_angle, _ptr(self.records),
+                                                _ptr(self.scores), _ptr(self.ws), self.ws.numel(), _stream()), "grid_match")
         if self.moments is not None:
             match_moments(self.scores, self.records, self.B, self.A, self.W, self.half_step, out=self.moments)
         return self.records
@@ -644,19 +632,15 @@ class GridSearchBatch(GridMatchBatch):
         self._bound_buf = None
 
     def run(self):
-        g = self.grid
         fld = self._field()
         if self.bounds is not None:
             bnd = self.bounds
         else:
             bnd = self._bound_buf = bound_field(fld, self.block, self._bound_buf)
         ny, nx = fld.shape
-        cs = self.cs
-        check(_lib.lib().icpmi_grid_search_batch(
-            _ptr(fld), _ptr(bnd), ny, nx, float(g.min_x), float(g.min_y), float(g.resolution), _ptr(cs.pts), _ptr(cs.off),
-            cs.off_host.ctypes.data_as(C.c_void_p), _ptr(cs.cnt), cs.n_clouds, _ptr(self.pair),
-            self.pair_host.ctypes.data_as(C.c_void_p), self.B, _ptr(self.t), _ptr(self.cos_sin), self.A, self.W, self.block,
-            self.centre_angle, _ptr(self.records), _ptr(self.bounds_volume), _ptr(self.ws), self.ws.numel(), _stream()), "grid_search")
+        check(_lib.lib().icpmi_grid_search_batch(_ptr(fld), _ptr(bnd), ny, nx, *self._pair_args(), self.W, self.block, self.centre_angle,
+                                                 _ptr(self.records), _ptr(self.bounds_volume), _ptr(self.ws), self.ws.numel(), _stream()),
+              "grid_search")
         return self.records
 
     def unpack(self, records=None):

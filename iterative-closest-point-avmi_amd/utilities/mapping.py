@@ -359,11 +359,46 @@ class OccupancyGrid2D:
             raise ValueError(f"{n} scans but {len(p)} predicted poses")
         return p
 
-    def _match_set(self, cs, pair_clouds, poses, linear_window, angular_window, angular_step, field, want_scores=False, half_log_odds=None):
-        from icpmi import gridmatch
+    @staticmethod
+    def _one_pose(pose):
+        """One pose ([x, y, theta] or a 3 x 3 matrix) as the stack of one the batched methods take."""
+        p = np.asarray(pose, dtype=np.float64)
+        return p[None] if p.ndim == 2 else p.reshape(1, 3)
+
+    @staticmethod
+    def _first(info):
+        """The ``info`` of a batch of one as the single-scan methods return it: entry 0 of every array and list."""
+        return {k: (v[0] if isinstance(v, (np.ndarray, list)) else v) for k, v in info.items()}
+
+    def _named(self, clouds=None, voxel_size=None, scan=None, poses=None, history=None, ids=None):
+        """-> (cloud set, pair_clouds) of the three ways the pair methods name their scans: ``clouds``, one pair each (through
+        the voxel filter when a size is given); one ``scan``, uploaded once, at every pose of ``poses``; scans resident in a
+        ``history`` by ``ids``, read where they are (``_history_rows`` chooses the rows)."""
+        from icpmi import gridmatch, history as _h
+        if history is not None:
+            ids = _h._scan_ids(ids, ("ids", "scan ids"), history.n_scans)
+            return self._history_rows(history, voxel_size), ids
+        if scan is not None:
+            return gridmatch.cloud_set_of([scan]), np.zeros(len(self._xytheta(poses)), dtype=np.int32)
+        cs = gridmatch.cloud_set_of(clouds, voxel_size)
+        return cs, np.arange(cs.n_clouds)
+
+    def _pairs(self, cs, pair_clouds, poses):
+        """What every pair method starts with -> (pair_clouds int32 [B], the poses as (B, 3) rows [x, y, theta]): the clouds
+        on this grid's device, a pose per pair."""
         if cs.pts.device != self._dev:
             raise ValueError(f"the clouds live on {cs.pts.device}, the grid on {self._dev}")
-        xyt = self._xytheta(poses, len(pair_clouds))
+        pair_clouds = np.ascontiguousarray(pair_clouds, dtype=np.int32).reshape(-1)
+        return pair_clouds, self._xytheta(poses, len(pair_clouds))
+
+    @staticmethod
+    def _cos_sin(theta):
+        """(cos, sin) rows of the headings ``theta``, by NumPy on the host: the rotations the cast, the check and the beam model take."""
+        return np.stack([np.cos(theta), np.sin(theta)], axis=1)
+
+    def _match_set(self, cs, pair_clouds, poses, linear_window, angular_window, angular_step, field, want_scores=False, half_log_odds=None):
+        from icpmi import gridmatch
+        pair_clouds, xyt = self._pairs(cs, pair_clouds, poses)
         if angular_step is None:                                   # score_poses: the pose itself and nothing around it
             angles, centre, W = xyt[:, 2:3], 0, 0
         else:
@@ -385,9 +420,7 @@ class OccupancyGrid2D:
         then carries the moments of the score volume about the winner, the sub-cell pose (``t_refined``, ``angle_refined``,
         ``R_refined``) and its ``covariance``, with ``edge_weight`` to show a distribution the window cut off.
         -> (R [B,2,2], t [B,2], score [B], info) as ``icpmi.gridmatch.GridMatchBatch.unpack`` forms them."""
-        from icpmi import gridmatch
-        cs = gridmatch.cloud_set_of(clouds, voxel_size)
-        return self._match_set(cs, np.arange(cs.n_clouds), predicted_poses, linear_window, angular_window, angular_step, field,
+        return self._match_set(*self._named(clouds, voxel_size), predicted_poses, linear_window, angular_window, angular_step, field,
                                half_log_odds=half_log_odds).unpack()
 
     def match_scan(self, points_local, predicted_pose, linear_window=0.6, angular_window=12.0, angular_step=1.0, voxel_size=None,
@@ -395,16 +428,13 @@ class OccupancyGrid2D:
         """``match_scans`` of one scan -> (R (2,2), t (2,), score, info) with scalar entries in ``info``."""
         R, t, score, info = self.match_scans([points_local], [predicted_pose], linear_window, angular_window, angular_step,
                                              voxel_size, field, half_log_odds)
-        return R[0], t[0], int(score[0]), {k: (v[0] if isinstance(v, np.ndarray) else v) for k, v in info.items()}
+        return R[0], t[0], int(score[0]), self._first(info)
 
     def score_poses(self, points_local, poses, field=None):
         """The score of one scan at every pose of ``poses`` ((P, 3) rows [x, y, theta] or 3 x 3 matrices): the same kernel
         with one angle and no shifts per pose (pass one matrix as a stack of one) — weights for a particle filter, or a check of a loop closure before its edge
         goes into the graph -> (score [P], info)."""
-        from icpmi import gridmatch
-        cs = gridmatch.cloud_set_of([points_local])
-        xyt = self._xytheta(poses)
-        _, _, score, info = self._match_set(cs, np.zeros(len(xyt), dtype=np.int32), xyt, 0.0, 0.0, None, field).unpack()
+        _, _, score, info = self._match_set(*self._named(scan=points_local, poses=poses), poses, 0.0, 0.0, None, field).unpack()
         return score, info
 
     # ── the map read back as ranges (icpmi.gridmatch.cast_rays; no counterpart in the reference) ─────────────────────
@@ -448,8 +478,7 @@ class OccupancyGrid2D:
         src, k, threshold = self._cast_map(occupied_log_odds, field, planes)
         xyt = self._xytheta(poses)
         ang = np.asarray(angles, dtype=np.float64).reshape(-1)
-        pose_cs = np.stack([np.cos(xyt[:, 2]), np.sin(xyt[:, 2])], axis=1)
-        beam_cs = np.stack([np.cos(ang), np.sin(ang)], axis=1)
+        pose_cs, beam_cs = self._cos_sin(xyt[:, 2]), self._cos_sin(ang)
         rec = gridmatch.cast_rays(src, threshold, self.min_x, self.min_y, self.resolution, xyt[:, :2], pose_cs, beam_cs, max_range)
         rec = rec.cpu().numpy().astype(np.int64)
         k_hit, k_unknown = rec[..., _lib.GC_K_HIT], rec[..., _lib.GC_K_UNKNOWN]
@@ -465,19 +494,15 @@ class OccupancyGrid2D:
 
     def cast_scan(self, pose, angles, max_range, occupied_log_odds=0.5, field=None, planes=None):
         """``cast_scans`` from one pose ([x, y, theta] or a 3 x 3 matrix) -> (ranges (A,), info) with (A, ...) entries."""
-        p = np.asarray(pose, dtype=np.float64)
-        ranges, info = self.cast_scans(p[None] if p.ndim == 2 else p.reshape(1, 3), angles, max_range, occupied_log_odds, field, planes)
-        return ranges[0], {k: (v[0] if isinstance(v, np.ndarray) else v) for k, v in info.items()}
+        ranges, info = self.cast_scans(self._one_pose(pose), angles, max_range, occupied_log_odds, field, planes)
+        return ranges[0], self._first(info)
 
     # ── measured scans held against the map along their beams (icpmi.gridmatch.check_pairs; no counterpart in the reference) ──
     def _check_set(self, cs, pair_clouds, poses, tolerance, occupied_log_odds, field, planes, want_rows):
         from icpmi import gridmatch
         src, k, threshold = self._cast_map(occupied_log_odds, field, planes)
-        if cs.pts.device != self._dev:
-            raise ValueError(f"the clouds live on {cs.pts.device}, the grid on {self._dev}")
-        pair_clouds = np.ascontiguousarray(pair_clouds, dtype=np.int32).reshape(-1)
-        xyt = self._xytheta(poses, len(pair_clouds))
-        cos_sin = np.stack([np.cos(xyt[:, 2]), np.sin(xyt[:, 2])], axis=1)
+        pair_clouds, xyt = self._pairs(cs, pair_clouds, poses)
+        cos_sin = self._cos_sin(xyt[:, 2])
         records, rows = gridmatch.check_pairs(src, threshold, self.min_x, self.min_y, self.resolution, cs, pair_clouds, xyt[:, :2], cos_sin,
                                               tolerance, want_rows=want_rows)
         rec = records.cpu().numpy().astype(np.int64)
@@ -525,47 +550,33 @@ class OccupancyGrid2D:
         ``status`` (``icpmi._lib.GK_ST_*``); ``violated_share`` and ``in_free_share`` (count / rows, 0.0 where rows is 0);
         ``shift_bits``.  With ``want_rows``, ``classes``: per scan an (n, 4) int32 array [class, k_hit, K, k_unknown] per row
         (``icpmi._lib.GK_CLASS_*``; ``GK_NO_CELLS`` for a row without cells)."""
-        from icpmi import gridmatch
-        cs = gridmatch.cloud_set_of(clouds, voxel_size)
-        return self._check_set(cs, np.arange(cs.n_clouds), poses, tolerance, occupied_log_odds, field, planes, want_rows)
+        return self._check_set(*self._named(clouds, voxel_size), poses, tolerance, occupied_log_odds, field, planes, want_rows)
 
     def check_scan(self, points_local, pose, tolerance=2, occupied_log_odds=0.5, voxel_size=None, field=None, planes=None, want_rows=False):
         """``check_scans`` of one scan at one pose ([x, y, theta] or a 3 x 3 matrix) -> info with scalar entries (``classes``:
-        the one (n, 4) array).  Planes packed from a ``likelihood_field`` with a lower ``occupied_log_odds`` thicken the walls:
-        the remedy for returns just in front of a thin wall."""
-        p = np.asarray(pose, dtype=np.float64)
-        info = self.check_scans([points_local], p[None] if p.ndim == 2 else p.reshape(1, 3), tolerance, occupied_log_odds, voxel_size,
-                                field, planes, want_rows)
-        return {k: (v[0] if isinstance(v, (np.ndarray, list)) else v) for k, v in info.items()}
+        the one (n, 4) array)."""
+        return self._first(self.check_scans([points_local], self._one_pose(pose), tolerance, occupied_log_odds, voxel_size, field, planes,
+                                            want_rows))
 
     def check_poses(self, points_local, poses, tolerance=2, occupied_log_odds=0.5, field=None, planes=None, want_rows=False):
         """``check_scans`` of ONE scan at every pose of ``poses`` ((P, 3) rows [x, y, theta] or 3 x 3 matrices), as
         ``score_poses`` scores one: the scan is uploaded once and every hypothesis names it — a particle filter's free-space
-        test, or a gate on loop-closure candidates -> info with (P,) entries.  Planes packed from a ``likelihood_field`` with a
-        lower ``occupied_log_odds`` thicken the walls: the remedy for returns just in front of a thin wall."""
-        from icpmi import gridmatch
-        cs = gridmatch.cloud_set_of([points_local])
-        xyt = self._xytheta(poses)
-        return self._check_set(cs, np.zeros(len(xyt), dtype=np.int32), xyt, tolerance, occupied_log_odds, field, planes, want_rows)
+        test, or a gate on loop-closure candidates -> info with (P,) entries."""
+        return self._check_set(*self._named(scan=points_local, poses=poses), poses, tolerance, occupied_log_odds, field, planes, want_rows)
 
     def check_history(self, history, ids, poses, tolerance=2, occupied_log_odds=0.5, voxel_size=None, field=None, planes=None,
                       want_rows=False):
         """``check_scans`` of scans resident in an ``icpmi.ScanHistory``, by id: the rows are read where they are and no scan
-        is uploaded; ``voxel_size`` chooses them as in ``match_history``.  Planes packed from a ``likelihood_field`` with a
-        lower ``occupied_log_odds`` thicken the walls: the remedy for returns just in front of a thin wall."""
-        from icpmi import history as _h
-        ids = _h._scan_ids(ids, ("ids", "scan ids"), history.n_scans)
-        return self._check_set(self._history_rows(history, voxel_size), ids, poses, tolerance, occupied_log_odds, field, planes, want_rows)
+        is uploaded; ``voxel_size`` chooses them as in ``match_history``."""
+        return self._check_set(*self._named(history=history, ids=ids, voxel_size=voxel_size), poses, tolerance, occupied_log_odds, field,
+                               planes, want_rows)
 
     # ── the beam model: measured scans scored against the ranges the map expects (icpmi.gridmatch.beam_pairs) ───────────
     def _beam_set(self, cs, pair_clouds, poses, sigma, half_width, beyond, table, occupied_log_odds, field, planes, want_histogram, want_rows):
         from icpmi import gridmatch
         src, k, threshold = self._cast_map(occupied_log_odds, field, planes)
-        if cs.pts.device != self._dev:
-            raise ValueError(f"the clouds live on {cs.pts.device}, the grid on {self._dev}")
-        pair_clouds = np.ascontiguousarray(pair_clouds, dtype=np.int32).reshape(-1)
-        xyt = self._xytheta(poses, len(pair_clouds))
-        cos_sin = np.stack([np.cos(xyt[:, 2]), np.sin(xyt[:, 2])], axis=1)
+        pair_clouds, xyt = self._pairs(cs, pair_clouds, poses)
+        cos_sin = self._cos_sin(xyt[:, 2])
         if table is None:
             table = gridmatch.beam_table(self.resolution, self.resolution if sigma is None else sigma, half_width)
         if beyond is None:
@@ -606,39 +617,30 @@ class OccupancyGrid2D:
         ``rows``); ``mean_score`` (score / rows, 0.0 where rows is 0); ``shift_bits``.  With ``want_histogram``,
         ``histogram`` (B, 2H + 3): the rows per index.  With ``want_rows``, ``classes``: per scan an (n, 4) int32 array [index,
         k_hit, k_z, k_unknown] per row (``GB_NO_CELLS`` for a row without cells)."""
-        from icpmi import gridmatch
-        cs = gridmatch.cloud_set_of(clouds, voxel_size)
-        return self._beam_set(cs, np.arange(cs.n_clouds), poses, sigma, half_width, beyond, table, occupied_log_odds, field, planes,
+        return self._beam_set(*self._named(clouds, voxel_size), poses, sigma, half_width, beyond, table, occupied_log_odds, field, planes,
                               want_histogram, want_rows)
 
     def beam_scan(self, points_local, pose, sigma=None, half_width=8, beyond=None, table=None, occupied_log_odds=0.5, voxel_size=None,
                   field=None, planes=None, want_histogram=False, want_rows=False):
         """``beam_scans`` of one scan at one pose ([x, y, theta] or a 3 x 3 matrix) -> info with scalar entries (``histogram``:
         the one (2H + 3,) array; ``classes``: the one (n, 4) array)."""
-        p = np.asarray(pose, dtype=np.float64)
-        info = self.beam_scans([points_local], p[None] if p.ndim == 2 else p.reshape(1, 3), sigma, half_width, beyond, table,
-                               occupied_log_odds, voxel_size, field, planes, want_histogram, want_rows)
-        return {k: (v[0] if isinstance(v, (np.ndarray, list)) else v) for k, v in info.items()}
+        return self._first(self.beam_scans([points_local], self._one_pose(pose), sigma, half_width, beyond, table, occupied_log_odds,
+                                           voxel_size, field, planes, want_histogram, want_rows))
 
     def beam_poses(self, points_local, poses, sigma=None, half_width=8, beyond=None, table=None, occupied_log_odds=0.5, field=None,
                    planes=None, want_histogram=False, want_rows=False):
         """``beam_scans`` of ONE scan at every pose of ``poses`` ((P, 3) rows [x, y, theta] or 3 x 3 matrices): the scan is
         uploaded once and every hypothesis names it — a particle filter's measurement update (``icpmi.gridmatch.pose_weights``
         of ``score`` and ``status``), or a ranking of loop-closure candidates -> info with (P,) entries."""
-        from icpmi import gridmatch
-        cs = gridmatch.cloud_set_of([points_local])
-        xyt = self._xytheta(poses)
-        return self._beam_set(cs, np.zeros(len(xyt), dtype=np.int32), xyt, sigma, half_width, beyond, table, occupied_log_odds, field,
-                              planes, want_histogram, want_rows)
+        return self._beam_set(*self._named(scan=points_local, poses=poses), poses, sigma, half_width, beyond, table, occupied_log_odds,
+                              field, planes, want_histogram, want_rows)
 
     def beam_history(self, history, ids, poses, sigma=None, half_width=8, beyond=None, table=None, occupied_log_odds=0.5, voxel_size=None,
                      field=None, planes=None, want_histogram=False, want_rows=False):
         """``beam_scans`` of scans resident in an ``icpmi.ScanHistory``, by id: the rows are read where they are and no scan
         is uploaded; ``voxel_size`` chooses them as in ``match_history``."""
-        from icpmi import history as _h
-        ids = _h._scan_ids(ids, ("ids", "scan ids"), history.n_scans)
-        return self._beam_set(self._history_rows(history, voxel_size), ids, poses, sigma, half_width, beyond, table, occupied_log_odds,
-                              field, planes, want_histogram, want_rows)
+        return self._beam_set(*self._named(history=history, ids=ids, voxel_size=voxel_size), poses, sigma, half_width, beyond, table,
+                              occupied_log_odds, field, planes, want_histogram, want_rows)
 
     @staticmethod
     def _history_rows(history, voxel_size):
@@ -658,11 +660,8 @@ class OccupancyGrid2D:
         """``match_scans`` of scans resident in an ``icpmi.ScanHistory``, by id: the raw rows are read where they are and no
         scan is uploaded.  ``voxel_size``: the history's own filtered copies where it is one of the history's voxel sizes;
         any other size filters every resident scan first."""
-        from icpmi import history as _h
-        ids = _h._scan_ids(ids, ("ids", "scan ids"), history.n_scans)
-        cs = self._history_rows(history, voxel_size)
-        return self._match_set(cs, ids, predicted_poses, linear_window, angular_window, angular_step, field,
-                               half_log_odds=half_log_odds).unpack()
+        return self._match_set(*self._named(history=history, ids=ids, voxel_size=voxel_size), predicted_poses, linear_window, angular_window,
+                               angular_step, field, half_log_odds=half_log_odds).unpack()
 
     # ── the same search over a wide window (icpmi.gridmatch.GridSearchBatch): metres and the full circle ─────────────
     def bound_field(self, field=None, block=8):
@@ -674,11 +673,9 @@ class OccupancyGrid2D:
 
     def _search_set(self, cs, pair_clouds, poses, linear_window, angular_window, angular_step, block, field, bounds):
         from icpmi import gridmatch
-        if cs.pts.device != self._dev:
-            raise ValueError(f"the clouds live on {cs.pts.device}, the grid on {self._dev}")
         if bounds is not None and field is None:
             raise ValueError("bounds= belongs to the field it was made from: pass that field= too")
-        xyt = self._xytheta(poses, len(pair_clouds))
+        pair_clouds, xyt = self._pairs(cs, pair_clouds, poses)
         angles, centre = gridmatch.angle_grid(xyt[:, 2], angular_window, angular_step)
         W = int(round(linear_window / self.resolution))
         job = gridmatch.GridSearchBatch(self, cs, pair_clouds, xyt[:, :2], angles, W, centre, block=block, field=field, bounds=bounds)
@@ -693,9 +690,7 @@ class OccupancyGrid2D:
         ``block`` x ``block`` (4, 8 or 16); only blocks whose upper bound reaches a seed score are scored.  ``info`` adds
         ``blocks``, ``survivors``, ``seed_score`` and ``max_bound``.  ``bounds``: a ``bound_field(field, block)`` kept by the
         caller, with the ``field`` it was made from."""
-        from icpmi import gridmatch
-        cs = gridmatch.cloud_set_of(clouds, voxel_size)
-        return self._search_set(cs, np.arange(cs.n_clouds), predicted_poses, linear_window, angular_window, angular_step, block, field,
+        return self._search_set(*self._named(clouds, voxel_size), predicted_poses, linear_window, angular_window, angular_step, block, field,
                                 bounds).unpack()
 
     def search_scan(self, points_local, predicted_pose, linear_window=5.0, angular_window=180.0, angular_step=1.0, voxel_size=None,
@@ -703,15 +698,13 @@ class OccupancyGrid2D:
         """``search_scans`` of one scan -> (R (2,2), t (2,), score, info) with scalar entries in ``info``."""
         R, t, score, info = self.search_scans([points_local], [predicted_pose], linear_window, angular_window, angular_step,
                                               voxel_size, block, field, bounds)
-        return R[0], t[0], int(score[0]), {k: (v[0] if isinstance(v, np.ndarray) else v) for k, v in info.items()}
+        return R[0], t[0], int(score[0]), self._first(info)
 
     def search_history(self, history, ids, predicted_poses, linear_window=5.0, angular_window=180.0, angular_step=1.0, voxel_size=None,
                        block=8, field=None, bounds=None):
         """``search_scans`` of scans resident in an ``icpmi.ScanHistory``, by id, with ``match_history``'s choice of rows."""
-        from icpmi import history as _h
-        ids = _h._scan_ids(ids, ("ids", "scan ids"), history.n_scans)
-        cs = self._history_rows(history, voxel_size)
-        return self._search_set(cs, ids, predicted_poses, linear_window, angular_window, angular_step, block, field, bounds).unpack()
+        return self._search_set(*self._named(history=history, ids=ids, voxel_size=voxel_size), predicted_poses, linear_window, angular_window,
+                                angular_step, block, field, bounds).unpack()
 
     # ── probability / display, mapping.py:150-166 (NumPy on the host copy) ───
     def to_probability(self):

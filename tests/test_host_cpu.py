@@ -728,3 +728,28 @@ def test_grid_update_plan_rows():
     for kw, want in rows:
         code, got = call(**kw)
         assert code == 0 and got == want, (kw, got)
+
+
+def test_the_four_pair_entries_judge_a_bad_pair_list_alike():
+    """The exhaustive match, the wide search, the check and the beam model take one pair list (cloud set offsets on the host,
+    a cloud index per pair) and refuse a bad one with the same code, decided on the host before anything is enqueued: the
+    device pointers are fakes that are never dereferenced, and everything else about each call is in order."""
+    import icpmi
+    L = icpmi.lib()
+    FAKE, BIG, ERR_ARG, ERR_UNSUPPORTED = 4096, 1 << 40, -1, -4
+
+    def codes(off=(0, 100, 100, 360), pair=(0, 2, 1, 2), n_clouds=None, off_host=True):
+        off_a, pair_a = np.array(off, dtype=np.int32), np.array(pair, dtype=np.int32)
+        lst = (FAKE, FAKE, off_a.ctypes.data if off_host else None, None, len(off_a) - 1 if n_clouds is None else n_clouds, FAKE,
+               pair_a.ctypes.data, len(pair_a), FAKE, FAKE)                  # pts ... cos_sin, as all four take them
+        world = (-14.0, -10.0, 0.1)
+        return (L.icpmi_grid_match_batch(FAKE, 400, 560, *world, *lst, 1, 0, -1, FAKE, None, FAKE, BIG, None),
+                L.icpmi_grid_search_batch(FAKE, FAKE, 400, 560, *world, *lst, 1, 0, 4, -1, FAKE, None, FAKE, BIG, None),
+                L.icpmi_grid_check_batch(None, FAKE, 400, 560, 2048, *world, *lst, 2, FAKE, None, 0, None, 0, None),
+                L.icpmi_grid_beam_batch(None, FAKE, 400, 560, 2048, *world, *lst, 0.5, 8, FAKE, FAKE, None, None, 0, None, 0, None))
+
+    assert codes(pair=(0, 3)) == (ERR_ARG,) * 4                              # an index beyond the set
+    assert codes(off=(0, 100, 90, 360)) == (ERR_ARG,) * 4                    # a negative row count
+    assert codes(n_clouds=-1) == (ERR_ARG,) * 4
+    assert codes(off_host=False) == (ERR_ARG,) * 4
+    assert codes(off=(0, 65536), pair=(0,)) == (ERR_UNSUPPORTED,) * 4        # a cloud above ICPMI_GM_MAX_ROWS
