@@ -9,6 +9,10 @@
 // (FtSide): the batch passes one set of tables twice, the resident chain of a scan history (icpmi_history_feature_align,
 // at the end of this file) takes its targets — and without a start per pair its sources — from the history's feature store.
 //
+// The host side, after the kernels, has each thing once: the cloud-side limits (ft_cfg_check), the workspace of both chains
+// (FtWs), the per-cloud half of both chains and of a history's feature store (ft_cloud_stages, in features.hpp for
+// history.hip), the work set of a call with a start per pair (ft_build_work_set), the pair half (ft_pair_stages).
+//
 // What is pinned to the reference's numbers, stage by stage ("feature alignment"):
 //   curvature     to the reference's own sensitivity to summation order: np.cov sums the neighbours in per-point distance
 //                 order; here they are summed in ASCENDING ROW order, so rows with the same neighbour set get the same bits
@@ -16,6 +20,7 @@
 //   descriptors   bit for bit (exact neighbour distances, IEEE sqrt, as KDTree.query)
 //   matches       identical lists when the ratio test is not within rounding of equality (the fixtures check their margins)
 //   RANSAC        the hypotheses are an input; inlier counts equal when no error is within rounding of the threshold
+#include "features.hpp"
 #include "linalg.hpp"
 #include "prep_common.hpp"
 #include "sort.hpp"
@@ -35,15 +40,21 @@ constexpr int FT_THREADS = 256;
 struct FtCloud {
     int c, n, first;          // cloud, valid rows (0: nothing to do), first row in the set
 };
+// valid rows of cloud c of a set: its count (nullptr: every cloud is full), at most the rows its offsets give it
+__device__ __forceinline__ int ft_rows(const int32_t* __restrict__ off, const int32_t* __restrict__ cnt, int c) {
+    const int cap = off[c + 1] - off[c];
+    return min(cnt ? cnt[c] : cap, cap);
+}
+// keypoints of a cloud, matches of a pair: a stored count never reaches past its slots
+__device__ __forceinline__ int ft_clamp_kp(int n, int kp_stride) { return min(min(n, kp_stride), FT_MAX_KP); }
+
 __device__ __forceinline__ FtCloud ft_stage_cloud(const double* __restrict__ pts, const int32_t* __restrict__ off,
                                                   const int32_t* __restrict__ cnt, const int32_t* __restrict__ cloud_ids,
                                                   double2* P, int32_t* ident) {
     FtCloud f;
     f.c = cloud_ids ? cloud_ids[blockIdx.x] : (int)blockIdx.x;
     f.first = off[f.c];
-    const int cap = off[f.c + 1] - f.first;
-    int n = cnt ? cnt[f.c] : cap;
-    n = n > cap ? cap : n;
+    const int n = ft_rows(off, cnt, f.c);
     f.n = (n < 0 || n > FT_MAX_ROWS) ? 0 : n;               // beyond the capacity: left alone (the chain reports status 2)
     const double2* g = reinterpret_cast<const double2*>(pts) + f.first;
     for (int i = threadIdx.x; i < f.n; i += blockDim.x) {
@@ -149,7 +160,7 @@ __global__ __launch_bounds__(ICPMI_WAVE) void ft_keypoints_kernel(const double* 
         __syncthreads();
         bitonic_sort_pairs(keys, rows, npad);
     }
-    const int limit = min(min(top_n, kp_stride), FT_MAX_KP);
+    const int limit = ft_clamp_kp(top_n, kp_stride);
     int nk = 0;                                                     // the same in every lane
     for (int c = 0; c < n && nk < limit; ++c) {
         const uint32_t idx = rows[c];
@@ -201,7 +212,7 @@ __global__ __launch_bounds__(FT_THREADS) void ft_descriptors_kernel(const double
     const FtCloud f = ft_stage_cloud(pts, off, cnt, cloud_ids, P, ident);
     if (f.n <= 0) { if (threadIdx.x == 0) out_desc_len[f.c] = 0; return; }
     const int kk = min(k, f.n - 1) + 1;                            // features.py:82, 85
-    const int n_kp = min(min(kp_cnt[f.c], kp_stride), FT_MAX_KP);
+    const int n_kp = ft_clamp_kp(kp_cnt[f.c], kp_stride);
     const int32_t* my_kp = kp + (size_t)f.c * kp_stride;
     double* desc = out_desc + (size_t)f.c * kp_stride * FT_DESC_STRIDE;
     if (kk <= 8) ft_descriptor_rows<8>(P, ident, f.n, kk, my_kp, n_kp, desc);
@@ -235,7 +246,7 @@ __global__ __launch_bounds__(FT_MAX_KP) void ft_match_kernel(const FtSide src, c
     __shared__ int wave_tot[FT_MAX_KP / ICPMI_WAVE];
     const int b = blockIdx.x, i = threadIdx.x;
     const int sc = pair_src[b], tc = pair_tgt[b];
-    const int ns = min(min(src.kp_cnt[sc], kp_stride), FT_MAX_KP), nt = min(min(tgt.kp_cnt[tc], kp_stride), FT_MAX_KP);
+    const int ns = ft_clamp_kp(src.kp_cnt[sc], kp_stride), nt = ft_clamp_kp(tgt.kp_cnt[tc], kp_stride);
     const int len = src.desc_len[sc];
     // features.py:97; descriptors of different lengths cannot be compared (NumPy raises; the chain reports status 5)
     const bool any = ns > 0 && nt >= 2 && len == tgt.desc_len[tc] && len > 0 && len <= FT_MAX_K;
@@ -296,6 +307,14 @@ __device__ __forceinline__ double ft_err(const FtRigid& g, const double2 s, cons
     return sqrt(ex * ex + ey * ey);                                 // np.linalg.norm(src @ R.T + t - dst, axis=1)
 }
 
+// "no alignment" in a pair's record: identity, zeros, 0 inliers, no winning hypothesis
+__device__ __forceinline__ void ft_write_no_alignment(double* __restrict__ rec) {
+    rec[ICPMI_FTREC_INLIERS] = 0.0;
+    rec[ICPMI_FTREC_R] = 1.0; rec[ICPMI_FTREC_R + 1] = 0.0; rec[ICPMI_FTREC_R + 2] = 0.0; rec[ICPMI_FTREC_R + 3] = 1.0;
+    rec[ICPMI_FTREC_T] = 0.0; rec[ICPMI_FTREC_T + 1] = 0.0;
+    rec[ICPMI_FTREC_BEST] = -1.0;
+}
+
 // hypothesis h of a pair with n matches: the index pair, from the int32 table or from two uniform doubles in [0, 1):
 // i = floor(u0 * n), j = floor(u1 * (n - 1)), j += (j >= i) — two distinct indices, each pair equally likely
 __device__ __forceinline__ bool ft_hypothesis(const int32_t* __restrict__ hyp_idx, const double* __restrict__ hyp_u, size_t h, int n,
@@ -321,14 +340,13 @@ __global__ __launch_bounds__(FT_THREADS) void ft_ransac_kernel(const FtSide src,
     const int sc = pair_src[b], tc = pair_tgt[b];
     double* rec = records + (size_t)b * ICPMI_FTREC_DOUBLES;
     int32_t* counts = out_counts ? out_counts + (size_t)b * n_iter : nullptr;
-    int n = min(min(match_cnt[b], kp_stride), FT_MAX_KP);
+    int n = ft_clamp_kp(match_cnt[b], kp_stride);
     if (tid == 0) bad = 0;
     __syncthreads();
     {   // the matched keypoints' coordinates, features.py:133-134
+        // (bounded by the slots alone, without ft_clamp_kp's FT_MAX_KP: the single-stage entry admits any kp_stride and any count)
         const int ns_kp = min(src.kp_cnt[sc], kp_stride), nt_kp = min(tgt.kp_cnt[tc], kp_stride);
-        const int cap_s = src.off[sc + 1] - src.off[sc], cap_t = tgt.off[tc + 1] - tgt.off[tc];
-        const int rows_s = min(src.cnt ? src.cnt[sc] : cap_s, cap_s);
-        const int rows_t = min(tgt.cnt ? tgt.cnt[tc] : cap_t, cap_t);
+        const int rows_s = ft_rows(src.off, src.cnt, sc), rows_t = ft_rows(tgt.off, tgt.cnt, tc);
         const double2* Ps = reinterpret_cast<const double2*>(src.pts) + src.off[sc];
         const double2* Pt = reinterpret_cast<const double2*>(tgt.pts) + tgt.off[tc];
         for (int m = tid; m < n; m += FT_THREADS) {
@@ -346,8 +364,8 @@ __global__ __launch_bounds__(FT_THREADS) void ft_ransac_kernel(const FtSide src,
         for (int h = tid; counts && h < n_iter; h += FT_THREADS) counts[h] = 0;
         if (tid == 0) {
             for (int q = 0; q < ICPMI_FTREC_DOUBLES; ++q) rec[q] = 0.0;
-            rec[ICPMI_FTREC_MATCHES] = (double)n; rec[ICPMI_FTREC_R] = 1.0; rec[ICPMI_FTREC_R + 3] = 1.0;
-            rec[ICPMI_FTREC_STATUS] = (double)ICPMI_FT_ST_FEW_MATCHES; rec[ICPMI_FTREC_BEST] = -1.0;
+            ft_write_no_alignment(rec);
+            rec[ICPMI_FTREC_MATCHES] = (double)n; rec[ICPMI_FTREC_STATUS] = (double)ICPMI_FT_ST_FEW_MATCHES;
         }
         return;
     }
@@ -473,10 +491,9 @@ __global__ void ft_finish_kernel(const FtSide src, const FtSide tgt, const int32
     rec[ICPMI_FTREC_NS] = (double)ns; rec[ICPMI_FTREC_NT] = (double)nt;
     const bool looked = status != ICPMI_FT_ST_CAPACITY && status != ICPMI_FT_ST_FEW_ROWS;      // else the reference never extracts keypoints
     rec[ICPMI_FTREC_KPS] = looked ? (double)src.kp_cnt[sc] : 0.0; rec[ICPMI_FTREC_KPT] = looked ? (double)tgt.kp_cnt[tc] : 0.0;
-    if (status != ICPMI_FT_ST_OK) {                                       // identity, zeros, 0 inliers
+    if (status != ICPMI_FT_ST_OK) {
         if (status != ICPMI_FT_ST_FEW_MATCHES) rec[ICPMI_FTREC_MATCHES] = 0.0;
-        rec[ICPMI_FTREC_INLIERS] = 0.0; rec[ICPMI_FTREC_R] = 1.0; rec[ICPMI_FTREC_R + 1] = 0.0; rec[ICPMI_FTREC_R + 2] = 0.0; rec[ICPMI_FTREC_R + 3] = 1.0;
-        rec[ICPMI_FTREC_T] = 0.0; rec[ICPMI_FTREC_T + 1] = 0.0; rec[ICPMI_FTREC_BEST] = -1.0;
+        ft_write_no_alignment(rec);
     }
     rec[ICPMI_FTREC_STATUS] = (double)status;
     if (!init_out) return;
@@ -496,56 +513,132 @@ __global__ void ft_finish_kernel(const FtSide src, const FtSide tgt, const int32
     for (int q = 0; q < 6; ++q) init_out[(size_t)b * 6 + q] = o[q];
 }
 
-// ── the chain's workspace, described once ──
-// work clouds (the caller's, then a transformed source per pair when a start is given) | their filtered copies | offsets
-// of the work set | counts | source cloud of every pair in the work set | curvature | keypoints | their counts |
-// descriptors | their lengths | matches | their counts | voxel scratch
+// ── what the two chains share on the host ────────────────────────────────────────────────────────────────────────
+// keypoint slots per cloud: top_n rounded up to 8
+static int ft_kp_stride(int top_n) { return top_n <= 0 ? 8 : (top_n + 7) / 8 * 8; }
+
+static FtSide ft_side(const FtTables& t) { return FtSide{t.pts, t.off, t.cnt, t.kp, t.kp_cnt, t.desc, t.desc_len}; }
+
+// The cloud-side limits, stated once: the batch chain checks its arguments with it, a store its own configuration, a
+// single-stage entry its subset (the fields it does not have take values that pass).
+static int ft_cfg_check(const FtCloudCfg& c, int kp_stride) {
+    if (!(c.voxel_size > 0.0) || c.k_curvature < 0 || c.k_descriptor < 0 || kp_stride <= 0) return ICPMI_ERR_ARG;
+    if (c.k_curvature > FT_MAX_K || c.k_descriptor > FT_MAX_K || c.top_n > FT_MAX_KP || c.top_n > kp_stride) return ICPMI_ERR_UNSUPPORTED;
+    return ICPMI_OK;
+}
+int ft_store_check(const icpmi_feature_store* s) {
+    if (!s || !s->vox || !s->curv || !s->cnt || !s->kp || !s->kp_cnt || !s->desc || !s->desc_len) return ICPMI_ERR_ARG;
+    return ft_cfg_check(ft_store_cfg(s), s->kp_stride);
+}
+
+// The workspace of a chain call, described once.  The work set — the clouds the per-cloud stages run on — is `front` clouds
+// of the caller's (the batch chain: all of them, the resident chain: none, its targets are in the store) followed, with a
+// start per pair, by one transformed copy of its source per pair (room for max_n rows each).
+// matches | their counts | the work set's raw rows, its offsets, the source of every pair in it (with a start only: without
+// one the caller's arrays are the work set) | its tables: filtered rows, counts, curvature, keypoints, their counts,
+// descriptors, their lengths | voxel scratch.  A work set of no clouds has none of the last two.
 struct FtWs {
     Carve c;
-    int32_t total_rows, n_clouds, max_n, n_pairs, kp_stride, with_init;
-    size_t work_rows = (size_t)total_rows + (with_init ? (size_t)n_pairs * (size_t)max_n : 0);
-    size_t work_clouds = (size_t)n_clouds + (with_init ? (size_t)n_pairs : 0);
-    double* work_pts = c.take<double>(with_init ? work_rows * 16 : 0);
-    double* vox = c.take<double>(work_rows * 16);
-    int32_t* work_off = c.take<int32_t>((work_clouds + 1) * 4);
-    int32_t* cnt = c.take<int32_t>(work_clouds * 4);
-    int32_t* work_src = c.take<int32_t>((size_t)n_pairs * 4);
-    double* curv = c.take<double>(work_rows * 8);
-    int32_t* kp = c.take<int32_t>(work_clouds * kp_stride * 4);
-    int32_t* kp_cnt = c.take<int32_t>(work_clouds * 4);
-    double* desc = c.take<double>(work_clouds * kp_stride * FT_DESC_STRIDE * 8);
-    int32_t* desc_len = c.take<int32_t>(work_clouds * 4);
+    int32_t front_rows, front_clouds, max_n, n_pairs, kp_stride, with_init;
+    size_t work_clouds = (size_t)front_clouds + (with_init ? (size_t)n_pairs : 0);
+    size_t work_rows = (size_t)front_rows + (with_init ? (size_t)n_pairs * (size_t)max_n : 0);
     int32_t* matches = c.take<int32_t>((size_t)n_pairs * kp_stride * 8);
     int32_t* match_cnt = c.take<int32_t>((size_t)n_pairs * 4);
-    size_t vws_bytes = icpmi_voxel_workspace_bytes(max_n);
+    double* raw = c.take<double>(with_init ? work_rows * 16 : 0);
+    int32_t* off = c.take<int32_t>(with_init ? (work_clouds + 1) * 4 : 0);
+    int32_t* pair_work = c.take<int32_t>(with_init ? (size_t)n_pairs * 4 : 0);
+    FtTables work{c.take<double>(work_rows * 16), off, c.take<int32_t>(work_clouds * 4), c.take<double>(work_rows * 8),
+                  c.take<int32_t>(work_clouds * kp_stride * 4), c.take<int32_t>(work_clouds * 4),
+                  c.take<double>(work_clouds * kp_stride * FT_DESC_STRIDE * 8), c.take<int32_t>(work_clouds * 4), kp_stride};
+    size_t vws_bytes = work_clouds ? icpmi_voxel_workspace_bytes(max_n) : 0;
     void* vws = c.take<void>(vws_bytes);
     size_t bytes = c.off + 256;
 };
 
-// keypoint slots per cloud: top_n rounded up to 8
-static int ft_kp_stride(int top_n) { return top_n <= 0 ? 8 : (top_n + 7) / 8 * 8; }
-
-// What a chain call starts, decided as a whole from its arguments (no HIP call): the work set and the grid of every stage.
+// What a chain call starts, read off its workspace description (no HIP call): the grid of every stage.
 struct FtPlan {
-    bool with_init;
-    int work_clouds;          // clouds of the work set: one workgroup each in the per-cloud stages
+    int work_clouds;          // clouds of the work set: one workgroup each in the per-cloud stages (0: those do not run)
     int kp_stride;
     int pair_grid;            // one workgroup per pair: transform, matching, RANSAC
     int finish_grid;          // a thread per pair
 };
-static FtPlan plan_features(int n_clouds, int n_pairs, int top_n, bool with_init) {
-    FtPlan p;
-    p.with_init = with_init;
-    p.work_clouds = n_clouds + (with_init ? n_pairs : 0);
-    p.kp_stride = ft_kp_stride(top_n);
-    p.pair_grid = n_pairs;
-    p.finish_grid = (n_pairs + FT_THREADS - 1) / FT_THREADS;
-    return p;
+static FtPlan plan_features(const FtWs& w) {
+    return FtPlan{(int)w.work_clouds, w.kp_stride, w.n_pairs, (w.n_pairs + FT_THREADS - 1) / FT_THREADS};
 }
 
 static bool ft_stage_args_ok(const void* pts, const void* off, int n_sel) { return pts && off && n_sel >= 0; }
 
-// the pair stages over two sides (the callers have checked their arguments; n_pairs > 0)
+// the per-cloud stages on the clouds cloud_ids[0 .. n_sel) of a set (the callers have checked their arguments; n_sel > 0)
+static int ft_launch_curvature(const double* pts, const int32_t* off, const int32_t* cnt, const int32_t* cloud_ids, int n_sel, int k,
+                               double* out_curv, hipStream_t st) {
+    ft_curvature_kernel<<<n_sel, FT_THREADS, 0, st>>>(pts, off, cnt, cloud_ids, k, out_curv);
+    ICPMI_LAUNCH_CHECK();
+    return ICPMI_OK;
+}
+static int ft_launch_keypoints(const double* pts, const int32_t* off, const int32_t* cnt, const int32_t* cloud_ids, int n_sel,
+                               const double* curv, const int32_t* order, int top_n, double min_dist, int32_t* out_kp, int32_t* out_kp_cnt,
+                               int kp_stride, hipStream_t st) {
+    ft_keypoints_kernel<<<n_sel, ICPMI_WAVE, 0, st>>>(pts, off, cnt, cloud_ids, curv, order, top_n, min_dist, out_kp, out_kp_cnt, kp_stride);
+    ICPMI_LAUNCH_CHECK();
+    return ICPMI_OK;
+}
+static int ft_launch_descriptors(const double* pts, const int32_t* off, const int32_t* cnt, const int32_t* cloud_ids, int n_sel,
+                                 const int32_t* kp, const int32_t* kp_cnt, int kp_stride, int k, double* out_desc, int32_t* out_desc_len,
+                                 hipStream_t st) {
+    ft_descriptors_kernel<<<n_sel, FT_THREADS, 0, st>>>(pts, off, cnt, cloud_ids, kp, kp_cnt, kp_stride, k, out_desc, out_desc_len);
+    ICPMI_LAUNCH_CHECK();
+    return ICPMI_OK;
+}
+
+// the per-cloud half of both chains and of a history's feature store (features.hpp)
+int ft_cloud_stages(const FtTables& t, const double* raw, const int32_t* off_host, int first, int n, const int32_t* cloud_ids,
+                    const FtCloudCfg& cfg, void* vws, size_t vws_bytes, hipStream_t st) {
+    int rc = icpmi_voxel_downsample_batch(raw, t.off + first, off_host + first, n, 2, cfg.voxel_size, t.pts, t.cnt + first, vws, vws_bytes, st);
+    if (rc != ICPMI_OK) return rc;
+    rc = ft_launch_curvature(t.pts, t.off, t.cnt, cloud_ids, n, cfg.k_curvature, t.curv, st);
+    if (rc != ICPMI_OK) return rc;
+    rc = ft_launch_keypoints(t.pts, t.off, t.cnt, cloud_ids, n, t.curv, nullptr, cfg.top_n, cfg.min_kp_dist, t.kp, t.kp_cnt, t.kp_stride, st);
+    if (rc != ICPMI_OK) return rc;
+    return ft_launch_descriptors(t.pts, t.off, t.cnt, cloud_ids, n, t.kp, t.kp_cnt, t.kp_stride, cfg.k_descriptor, t.desc, t.desc_len, st);
+}
+
+// ── the work set ─────────────────────────────────────────────────────────────────────────────────────────────────
+// The clouds the per-cloud stages of a chain call run on: raw rows, the host mirror of t.off, the source of every pair in
+// the set, and the set's tables.  Without a start it is the caller's own set on the workspace's tables.
+struct FtWorkSet {
+    const double* raw;
+    const int32_t* off_host;
+    const int32_t* pair_src;
+    FtTables t;
+};
+// With a start per pair, `set` — the raw set on entry — becomes `front` of its clouds as they are (copied) followed by
+// `source @ R_init.T + t_init` of every pair's source, laid out by ft_work_offsets_kernel's rule; off_host receives the host
+// mirror of its offsets.  A source must be a cloud below n_sources with at most max_rows rows that end at or before row
+// max_end; with nothing in front the set starts at the raw set's first offset, which must be 0.  Every refusal comes before
+// the first HIP call.
+static int ft_build_work_set(const FtPlan& plan, const FtWs& w, int front, int n_sources, int max_rows, int max_end,
+                             const int32_t* pair_src_host, const double* init, std::vector<int32_t>& off_host, FtWorkSet& set,
+                             hipStream_t st) {
+    if (front == 0 && set.off_host[0] != 0) return ICPMI_ERR_ARG;
+    off_host.assign(set.off_host, set.off_host + front + 1);
+    for (int b = 0; b < plan.pair_grid; ++b) {
+        const int sc = pair_src_host[b];
+        if (sc < 0 || sc >= n_sources) return ICPMI_ERR_ARG;
+        const int rows = set.off_host[sc + 1] - set.off_host[sc];
+        if (rows < 0 || rows > max_rows || set.off_host[sc + 1] > max_end) return ICPMI_ERR_ARG;
+        off_host.push_back(off_host.back() + rows);
+    }
+    if (front && hipMemcpyAsync(w.raw, set.raw, (size_t)set.off_host[front] * 16, hipMemcpyDeviceToDevice, st) != hipSuccess)
+        return ICPMI_ERR_HIP;
+    ft_work_offsets_kernel<<<1, 1024, 0, st>>>(set.t.off, front, set.pair_src, plan.pair_grid, w.off, w.pair_work);
+    ft_transform_kernel<<<plan.pair_grid, FT_THREADS, 0, st>>>(set.raw, set.t.off, w.raw, w.off, front, set.pair_src, init);
+    ICPMI_LAUNCH_CHECK();
+    set = FtWorkSet{w.raw, off_host.data(), w.pair_work, w.work};
+    return ICPMI_OK;
+}
+
+// ── the pair stages ──────────────────────────────────────────────────────────────────────────────────────────────
+// over two sides (the callers have checked their arguments; n_pairs > 0)
 static int ft_launch_match(const FtSide& src, const FtSide& tgt, int kp_stride, const int32_t* pair_src, const int32_t* pair_tgt, int n_pairs,
                            double ratio_sq, int32_t* out_matches, int32_t* out_match_cnt, hipStream_t st) {
     ft_match_kernel<<<n_pairs, FT_MAX_KP, 0, st>>>(src, tgt, kp_stride, pair_src, pair_tgt, ratio_sq, out_matches, out_match_cnt);
@@ -589,49 +682,17 @@ static int ft_pair_stages(const FtPlan& plan, const FtSide& src, const FtSide& t
     return ICPMI_OK;
 }
 
-// ── the resident chain's workspace (icpmi_history_feature_align), described once ──
-// matches | their counts — and, with a start per pair, the work set: one transformed copy of its source per pair (capacity
-// max_n rows each), their filtered copies, offsets, counts, the identity pair list into the set, curvature, keypoints,
-// descriptors, voxel scratch.  Without a start the sources are clouds of the store and only the first two exist.
-struct FtHistWs {
-    Carve c;
-    int32_t n_pairs, max_n, kp_stride, with_init;
-    size_t work_clouds = with_init ? (size_t)n_pairs : 0;
-    size_t work_rows = work_clouds * (size_t)max_n;
-    int32_t* matches = c.take<int32_t>((size_t)n_pairs * kp_stride * 8);
-    int32_t* match_cnt = c.take<int32_t>((size_t)n_pairs * 4);
-    double* work_pts = c.take<double>(work_rows * 16);
-    double* vox = c.take<double>(work_rows * 16);
-    int32_t* work_off = c.take<int32_t>(with_init ? (work_clouds + 1) * 4 : 0);
-    int32_t* cnt = c.take<int32_t>(work_clouds * 4);
-    int32_t* work_src = c.take<int32_t>(work_clouds * 4);
-    double* curv = c.take<double>(work_rows * 8);
-    int32_t* kp = c.take<int32_t>(work_clouds * kp_stride * 4);
-    int32_t* kp_cnt = c.take<int32_t>(work_clouds * 4);
-    double* desc = c.take<double>(work_clouds * kp_stride * FT_DESC_STRIDE * 8);
-    int32_t* desc_len = c.take<int32_t>(work_clouds * 4);
-    size_t vws_bytes = with_init ? icpmi_voxel_workspace_bytes(max_n) : 0;
-    void* vws = c.take<void>(vws_bytes);
-    size_t bytes = c.off + 256;
-};
-
-static bool ft_store_complete(const icpmi_feature_store* s) {
-    return s && s->vox && s->curv && s->cnt && s->kp && s->kp_cnt && s->desc && s->desc_len && s->voxel_size > 0.0 && s->kp_stride > 0 &&
-           s->k_curvature >= 0 && s->k_descriptor >= 0;
-}
-
 }  // namespace icpmi
 
+// ── the single-stage entry points: argument check, then the chain's launcher ─────────────────────────────────────────
 extern "C" int icpmi_feature_curvature_batch(const double* pts, const int32_t* off_dev, const int32_t* cnt_dev,
                                              const int32_t* cloud_ids, int32_t n_sel, int32_t k, double* out_curvature,
                                              void* stream) {
     using namespace icpmi;
-    if (!ft_stage_args_ok(pts, off_dev, n_sel) || !out_curvature || k < 0) return ICPMI_ERR_ARG;
-    if (k > FT_MAX_K) return ICPMI_ERR_UNSUPPORTED;
-    if (n_sel == 0) return ICPMI_OK;
-    ft_curvature_kernel<<<n_sel, FT_THREADS, 0, (hipStream_t)stream>>>(pts, off_dev, cnt_dev, cloud_ids, k, out_curvature);
-    ICPMI_LAUNCH_CHECK();
-    return ICPMI_OK;
+    if (!ft_stage_args_ok(pts, off_dev, n_sel) || !out_curvature) return ICPMI_ERR_ARG;
+    const int rc = ft_cfg_check(FtCloudCfg{1.0, k, 0, 0.0, 0}, 1);
+    if (rc != ICPMI_OK || n_sel == 0) return rc;
+    return ft_launch_curvature(pts, off_dev, cnt_dev, cloud_ids, n_sel, k, out_curvature, (hipStream_t)stream);
 }
 
 extern "C" int icpmi_feature_keypoints_batch(const double* pts, const int32_t* off_dev, const int32_t* cnt_dev,
@@ -639,26 +700,22 @@ extern "C" int icpmi_feature_keypoints_batch(const double* pts, const int32_t* o
                                              const int32_t* order, int32_t top_n, double min_dist, int32_t* out_kp,
                                              int32_t* out_kp_cnt, int32_t kp_stride, void* stream) {
     using namespace icpmi;
-    if (!ft_stage_args_ok(pts, off_dev, n_sel) || (!curvature && !order) || !out_kp || !out_kp_cnt || kp_stride <= 0) return ICPMI_ERR_ARG;
-    if (top_n > FT_MAX_KP || top_n > kp_stride) return ICPMI_ERR_UNSUPPORTED;
-    if (n_sel == 0) return ICPMI_OK;
-    ft_keypoints_kernel<<<n_sel, ICPMI_WAVE, 0, (hipStream_t)stream>>>(pts, off_dev, cnt_dev, cloud_ids, curvature, order, top_n, min_dist,
-                                                                       out_kp, out_kp_cnt, kp_stride);
-    ICPMI_LAUNCH_CHECK();
-    return ICPMI_OK;
+    if (!ft_stage_args_ok(pts, off_dev, n_sel) || (!curvature && !order) || !out_kp || !out_kp_cnt) return ICPMI_ERR_ARG;
+    const int rc = ft_cfg_check(FtCloudCfg{1.0, 0, top_n, min_dist, 0}, kp_stride);
+    if (rc != ICPMI_OK || n_sel == 0) return rc;
+    return ft_launch_keypoints(pts, off_dev, cnt_dev, cloud_ids, n_sel, curvature, order, top_n, min_dist, out_kp, out_kp_cnt, kp_stride,
+                               (hipStream_t)stream);
 }
 
 extern "C" int icpmi_feature_descriptors_batch(const double* pts, const int32_t* off_dev, const int32_t* cnt_dev,
                                                const int32_t* cloud_ids, int32_t n_sel, const int32_t* kp, const int32_t* kp_cnt,
                                                int32_t kp_stride, int32_t k, double* out_desc, int32_t* out_desc_len, void* stream) {
     using namespace icpmi;
-    if (!ft_stage_args_ok(pts, off_dev, n_sel) || !kp || !kp_cnt || !out_desc || !out_desc_len || kp_stride <= 0 || k < 0) return ICPMI_ERR_ARG;
-    if (k > FT_MAX_K) return ICPMI_ERR_UNSUPPORTED;
-    if (n_sel == 0) return ICPMI_OK;
-    ft_descriptors_kernel<<<n_sel, FT_THREADS, 0, (hipStream_t)stream>>>(pts, off_dev, cnt_dev, cloud_ids, kp, kp_cnt, kp_stride, k, out_desc,
-                                                                         out_desc_len);
-    ICPMI_LAUNCH_CHECK();
-    return ICPMI_OK;
+    if (!ft_stage_args_ok(pts, off_dev, n_sel) || !kp || !kp_cnt || !out_desc || !out_desc_len) return ICPMI_ERR_ARG;
+    const int rc = ft_cfg_check(FtCloudCfg{1.0, 0, 0, 0.0, k}, kp_stride);
+    if (rc != ICPMI_OK || n_sel == 0) return rc;
+    return ft_launch_descriptors(pts, off_dev, cnt_dev, cloud_ids, n_sel, kp, kp_cnt, kp_stride, k, out_desc, out_desc_len,
+                                 (hipStream_t)stream);
 }
 
 extern "C" int icpmi_feature_match_batch(const double* desc, const int32_t* desc_len, const int32_t* kp_cnt, int32_t kp_stride,
@@ -686,6 +743,7 @@ extern "C" int icpmi_feature_ransac_batch(const double* pts, const int32_t* off_
                             inlier_thresh, out_records, out_counts, (hipStream_t)stream);
 }
 
+// ── the chain: feature_based_alignment for every pair (features.py:247-315 inside slam.py:68-88) ─────────────────
 extern "C" size_t icpmi_feature_align_batch_workspace_bytes(int32_t total_rows, int32_t n_clouds, int32_t max_n, int32_t n_pairs,
                                                             int32_t top_n, int32_t with_init) {
     if (total_rows < 0 || n_clouds < 0 || max_n < 0 || n_pairs < 0) return 0;
@@ -701,59 +759,38 @@ extern "C" int icpmi_feature_align_batch(const double* pts, const int32_t* off_d
                                          void* workspace, size_t workspace_bytes, void* stream) {
     using namespace icpmi;
     if (!pts || !off_dev || !off_host || !pair_src || !pair_tgt || !out_records || !workspace) return ICPMI_ERR_ARG;
-    if (n_clouds <= 0 || n_pairs < 0 || n_iter < 0 || hyp_pair_stride < 0 || k_curvature < 0 || k_descriptor < 0) return ICPMI_ERR_ARG;
+    if (n_clouds <= 0 || n_pairs < 0 || n_iter < 0 || hyp_pair_stride < 0) return ICPMI_ERR_ARG;
     if (n_iter > 0 && !hyp_idx == !hyp_u) return ICPMI_ERR_ARG;
     if (init_in && !pair_src_host) return ICPMI_ERR_ARG;
-    if (!(voxel_size > 0.0)) return ICPMI_ERR_ARG;
-    if (k_curvature > FT_MAX_K || k_descriptor > FT_MAX_K || top_n > FT_MAX_KP) return ICPMI_ERR_UNSUPPORTED;
-    if (n_pairs == 0) return ICPMI_OK;
+    const FtCloudCfg cfg{voxel_size, k_curvature, top_n, min_kp_dist, k_descriptor};
+    int rc = ft_cfg_check(cfg, ft_kp_stride(top_n));
+    if (rc != ICPMI_OK || n_pairs == 0) return rc;
     int max_n, total_rows;
     if (!cloud_rows(off_host, n_clouds, max_n, total_rows)) return ICPMI_ERR_ARG;
-    const FtPlan plan = plan_features(n_clouds, n_pairs, top_n, init_in != nullptr);
-    const FtWs w{workspace, total_rows, n_clouds, max_n, n_pairs, plan.kp_stride, plan.with_init ? 1 : 0};
+    const FtWs w{workspace, total_rows, n_clouds, max_n, n_pairs, ft_kp_stride(top_n), init_in ? 1 : 0};
     if (workspace_bytes < w.bytes) return ICPMI_ERR_WORKSPACE;
+    const FtPlan plan = plan_features(w);
     hipStream_t st = (hipStream_t)stream;
     // the work set: the caller's clouds as they are, or followed by a transformed source per pair
-    const double* work_pts = pts;
-    const int32_t* work_off = off_dev;
-    const int32_t* work_src = pair_src;
+    FtWorkSet set{pts, off_host, pair_src, w.work};
+    set.t.off = off_dev;
     std::vector<int32_t> work_off_host;
-    const int32_t* work_off_host_p = off_host;
-    if (plan.with_init) {
-        work_off_host.assign(off_host, off_host + n_clouds + 1);
-        for (int b = 0; b < n_pairs; ++b) {
-            const int sc = pair_src_host[b];
-            if (sc < 0 || sc >= n_clouds) return ICPMI_ERR_ARG;
-            work_off_host.push_back(work_off_host.back() + (off_host[sc + 1] - off_host[sc]));
-        }
-        work_off_host_p = work_off_host.data();
-        if (hipMemcpyAsync(w.work_pts, pts, (size_t)total_rows * 16, hipMemcpyDeviceToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
-        ft_work_offsets_kernel<<<1, 1024, 0, st>>>(off_dev, n_clouds, pair_src, n_pairs, w.work_off, w.work_src);
-        ft_transform_kernel<<<plan.pair_grid, FT_THREADS, 0, st>>>(pts, off_dev, w.work_pts, w.work_off, n_clouds, pair_src, init_in);
-        ICPMI_LAUNCH_CHECK();
-        work_pts = w.work_pts; work_off = w.work_off; work_src = w.work_src;
-    }
-    int rc = icpmi_voxel_downsample_batch(work_pts, work_off, work_off_host_p, plan.work_clouds, 2, voxel_size, w.vox, w.cnt, w.vws,
-                                          w.vws_bytes, stream);
+    if (init_in) rc = ft_build_work_set(plan, w, n_clouds, n_clouds, max_n, total_rows, pair_src_host, init_in, work_off_host, set, st);
     if (rc != ICPMI_OK) return rc;
-    rc = icpmi_feature_curvature_batch(w.vox, work_off, w.cnt, nullptr, plan.work_clouds, k_curvature, w.curv, stream);
+    rc = ft_cloud_stages(set.t, set.raw, set.off_host, 0, plan.work_clouds, nullptr, cfg, w.vws, w.vws_bytes, st);
     if (rc != ICPMI_OK) return rc;
-    rc = icpmi_feature_keypoints_batch(w.vox, work_off, w.cnt, nullptr, plan.work_clouds, w.curv, nullptr, top_n, min_kp_dist, w.kp, w.kp_cnt,
-                                       plan.kp_stride, stream);
-    if (rc != ICPMI_OK) return rc;
-    rc = icpmi_feature_descriptors_batch(w.vox, work_off, w.cnt, nullptr, plan.work_clouds, w.kp, w.kp_cnt, plan.kp_stride, k_descriptor, w.desc,
-                                         w.desc_len, stream);
-    if (rc != ICPMI_OK) return rc;
-    const FtSide side{w.vox, work_off, w.cnt, w.kp, w.kp_cnt, w.desc, w.desc_len};      // sources and targets: clouds of the one work set
-    const FtPairArgs a{work_src, pair_tgt, n_pairs, ratio_sq, hyp_idx, hyp_u, n_iter, hyp_pair_stride, inlier_thresh, min_inliers,
+    const FtSide side = ft_side(set.t);                             // sources and targets: clouds of the one work set
+    const FtPairArgs a{set.pair_src, pair_tgt, n_pairs, ratio_sq, hyp_idx, hyp_u, n_iter, hyp_pair_stride, inlier_thresh, min_inliers,
                        init_in, init_out, out_records};
     return ft_pair_stages(plan, side, side, a, w.matches, w.match_cnt, st);
 }
 
 // ── the resident chain: the pair half of icpmi_feature_align_batch on a history's feature store ──────────────────────
+// Without a start the sources are clouds of the store as the targets are; with one they are a work set with no clouds in
+// front, which goes through the per-cloud half here, with the store's configuration.
 extern "C" size_t icpmi_history_feature_align_workspace_bytes(int32_t n_pairs, int32_t max_n, int32_t top_n, int32_t with_init) {
     if (n_pairs < 0 || max_n < 0) return 0;
-    return icpmi::FtHistWs{nullptr, n_pairs, max_n, icpmi::ft_kp_stride(top_n), with_init ? 1 : 0}.bytes;
+    return icpmi::FtWs{nullptr, 0, 0, max_n, n_pairs, icpmi::ft_kp_stride(top_n), with_init ? 1 : 0}.bytes;
 }
 
 extern "C" int icpmi_history_feature_align(const icpmi_history* h, const icpmi_feature_store* s, const int32_t* off_host,
@@ -763,48 +800,29 @@ extern "C" int icpmi_history_feature_align(const icpmi_history* h, const icpmi_f
                                            const double* init_in, double* init_out, double* out_records, void* workspace,
                                            size_t workspace_bytes, void* stream) {
     using namespace icpmi;
-    if (!h || !h->pts || !h->off_dev || !h->ids || h->scan_capacity <= 0 || h->row_capacity <= 0 || !ft_store_complete(s)) return ICPMI_ERR_ARG;
+    if (!h || !h->pts || !h->off_dev || !h->ids || h->scan_capacity <= 0 || h->row_capacity <= 0) return ICPMI_ERR_ARG;
     if (n_pairs < 0 || max_n < 0 || n_iter < 0 || hyp_pair_stride < 0) return ICPMI_ERR_ARG;
-    if (s->k_curvature > FT_MAX_K || s->k_descriptor > FT_MAX_K || s->top_n > FT_MAX_KP || s->top_n > s->kp_stride) return ICPMI_ERR_UNSUPPORTED;
-    if (n_pairs == 0) return ICPMI_OK;
+    int rc = ft_store_check(s);
+    if (rc != ICPMI_OK || n_pairs == 0) return rc;
     if (!pair_src || !pair_tgt || !out_records || !workspace) return ICPMI_ERR_ARG;
     if (n_iter > 0 && !hyp_idx == !hyp_u) return ICPMI_ERR_ARG;
     if (init_in && (!pair_src_host || !off_host)) return ICPMI_ERR_ARG;
     if (s->kp_stride != ft_kp_stride(s->top_n)) return ICPMI_ERR_ARG;              // the work set's tables share the store's stride
-    const FtPlan plan = plan_features(0, n_pairs, s->top_n, init_in != nullptr);
-    const FtHistWs w{workspace, n_pairs, max_n, plan.kp_stride, plan.with_init ? 1 : 0};
+    const FtWs w{workspace, 0, 0, max_n, n_pairs, s->kp_stride, init_in ? 1 : 0};
     if (workspace_bytes < w.bytes) return ICPMI_ERR_WORKSPACE;
+    const FtPlan plan = plan_features(w);
     hipStream_t st = (hipStream_t)stream;
-    const FtSide store{s->vox, h->off_dev, s->cnt, s->kp, s->kp_cnt, s->desc, s->desc_len};
+    const FtTables store_tables = ft_store_tables(h, s);
+    const FtSide store = ft_side(store_tables);
     FtPairArgs a{pair_src, pair_tgt, n_pairs, ratio_sq, hyp_idx, hyp_u, n_iter, hyp_pair_stride, inlier_thresh, min_inliers,
                  init_in, init_out, out_records};
-    if (!plan.with_init) return ft_pair_stages(plan, store, store, a, w.matches, w.match_cnt, st);
-    // a start per pair: the work set is one transformed copy of its source per pair, laid out by ft_work_offsets_kernel's
-    // rule with no clouds in front (the history's first offset is 0), and goes through the four per-cloud stages here
-    if (off_host[0] != 0) return ICPMI_ERR_ARG;
-    std::vector<int32_t> work_off_host(1, 0);
-    for (int b = 0; b < n_pairs; ++b) {
-        const int sc = pair_src_host[b];
-        if (sc < 0 || sc >= h->scan_capacity) return ICPMI_ERR_ARG;
-        const int rows = off_host[sc + 1] - off_host[sc];
-        if (rows < 0 || rows > max_n || off_host[sc + 1] > h->row_capacity) return ICPMI_ERR_ARG;
-        work_off_host.push_back(work_off_host.back() + rows);
-    }
-    ft_work_offsets_kernel<<<1, 1024, 0, st>>>(h->off_dev, 0, pair_src, n_pairs, w.work_off, w.work_src);
-    ft_transform_kernel<<<plan.pair_grid, FT_THREADS, 0, st>>>(h->pts, h->off_dev, w.work_pts, w.work_off, 0, pair_src, init_in);
-    ICPMI_LAUNCH_CHECK();
-    int rc = icpmi_voxel_downsample_batch(w.work_pts, w.work_off, work_off_host.data(), plan.work_clouds, 2, s->voxel_size, w.vox, w.cnt,
-                                          w.vws, w.vws_bytes, stream);
+    if (!init_in) return ft_pair_stages(plan, store, store, a, w.matches, w.match_cnt, st);
+    FtWorkSet set{h->pts, off_host, pair_src, store_tables};                        // the history's raw set, before it is built
+    std::vector<int32_t> work_off_host;
+    rc = ft_build_work_set(plan, w, 0, h->scan_capacity, max_n, h->row_capacity, pair_src_host, init_in, work_off_host, set, st);
     if (rc != ICPMI_OK) return rc;
-    rc = icpmi_feature_curvature_batch(w.vox, w.work_off, w.cnt, nullptr, plan.work_clouds, s->k_curvature, w.curv, stream);
+    rc = ft_cloud_stages(set.t, set.raw, set.off_host, 0, plan.work_clouds, nullptr, ft_store_cfg(s), w.vws, w.vws_bytes, st);
     if (rc != ICPMI_OK) return rc;
-    rc = icpmi_feature_keypoints_batch(w.vox, w.work_off, w.cnt, nullptr, plan.work_clouds, w.curv, nullptr, s->top_n, s->min_kp_dist, w.kp,
-                                       w.kp_cnt, plan.kp_stride, stream);
-    if (rc != ICPMI_OK) return rc;
-    rc = icpmi_feature_descriptors_batch(w.vox, w.work_off, w.cnt, nullptr, plan.work_clouds, w.kp, w.kp_cnt, plan.kp_stride, s->k_descriptor,
-                                         w.desc, w.desc_len, stream);
-    if (rc != ICPMI_OK) return rc;
-    const FtSide work{w.vox, w.work_off, w.cnt, w.kp, w.kp_cnt, w.desc, w.desc_len};
-    a.pair_src = w.work_src;
-    return ft_pair_stages(plan, work, store, a, w.matches, w.match_cnt, st);
+    a.pair_src = set.pair_src;
+    return ft_pair_stages(plan, ft_side(set.t), store, a, w.matches, w.match_cnt, st);
 }

@@ -7,9 +7,9 @@
 // scan is added, and a query is the search kernel and the ICP kernels on the state they left.
 //
 // Adding and matching have no kernel of their own: the filter (voxel.hip), the prepare kernels (prep.hip), both halves
-// of the rotation search (rotsearch.hip) and the per-cloud feature stages (features.hip; icpmi_history_features_add fills a
-// feature store with them, icpmi_history_feature_align of features.hip runs the pair stages on it) are the batch path's,
-// run on a range of clouds; growing is device-to-device copies.
+// of the rotation search (rotsearch.hip, through rotsearch.hpp) and the per-cloud half of the feature alignment (features.hip,
+// through features.hpp: icpmi_history_features_add is ft_cloud_stages into a feature store, icpmi_history_feature_align of
+// features.hip runs the pair stages on it) are the batch path's, run on a range of clouds; growing is device-to-device copies.
 //
 // One kernel lives here: history_world_rows_kernel, transform_points_2d (slam.py:46-50) of resident raw rows.  After an
 // accepted closure the reference moves every pose (slam.py:606-607), transforms every past scan again on the host and
@@ -22,6 +22,7 @@
 //    fixed until a relayout — with the rows in use, every array would move at every add;
 //  - the filter takes a cloud's rows from off[c + 1] - off[c], so the raw clouds lie back to back and the clouds not
 //    added yet have zero rows (off[c] = rows in use).
+#include "features.hpp"
 #include "prep_common.hpp"
 #include "rotsearch.hpp"
 
@@ -121,28 +122,16 @@ extern "C" int icpmi_history_features_add(const icpmi_history* h, const icpmi_fe
                                           int32_t n_new, void* stream) {
     using namespace icpmi;
     if (!h || !h->pts || !h->off_dev || !h->ids || !h->voxel_ws || h->scan_capacity <= 0 || h->row_capacity <= 0) return ICPMI_ERR_ARG;
-    if (!s || !s->vox || !s->curv || !s->cnt || !s->kp || !s->kp_cnt || !s->desc || !s->desc_len) return ICPMI_ERR_ARG;
     if (!off_host || first < 0 || n_new < 0 || first > h->scan_capacity - n_new) return ICPMI_ERR_ARG;
-    if (!(s->voxel_size > 0.0) || s->kp_stride <= 0 || s->k_curvature < 0 || s->k_descriptor < 0) return ICPMI_ERR_ARG;
-    if (s->k_curvature > 31 || s->k_descriptor > 31 || s->top_n > ICPMI_FT_MAX_KP || s->top_n > s->kp_stride) return ICPMI_ERR_UNSUPPORTED;
-    if (n_new == 0) return ICPMI_OK;
+    const int rc = ft_store_check(s);
+    if (rc != ICPMI_OK || n_new == 0) return rc;
     int max_n, end_row;
     if (off_host[first] < 0 || !cloud_rows(off_host + first, n_new, max_n, end_row)) return ICPMI_ERR_ARG;
     if (end_row > h->row_capacity) return ICPMI_ERR_ARG;
     if (max_n > HISTORY_MAX_ROWS) return ICPMI_ERR_UNSUPPORTED;
-    const int32_t* ids = h->ids + first;
-    // the first half of icpmi_feature_align_batch for this range: the filter on the tail of the offsets, the three feature
-    // kernels on the clouds ids[0 .. n_new)
-    int rc = icpmi_voxel_downsample_batch(h->pts, h->off_dev + first, off_host + first, n_new, 2, s->voxel_size, s->vox, s->cnt + first,
-                                          h->voxel_ws, h->voxel_ws_bytes, stream);
-    if (rc != ICPMI_OK) return rc;
-    rc = icpmi_feature_curvature_batch(s->vox, h->off_dev, s->cnt, ids, n_new, s->k_curvature, s->curv, stream);
-    if (rc != ICPMI_OK) return rc;
-    rc = icpmi_feature_keypoints_batch(s->vox, h->off_dev, s->cnt, ids, n_new, s->curv, nullptr, s->top_n, s->min_kp_dist, s->kp, s->kp_cnt,
-                                       s->kp_stride, stream);
-    if (rc != ICPMI_OK) return rc;
-    return icpmi_feature_descriptors_batch(s->vox, h->off_dev, s->cnt, ids, n_new, s->kp, s->kp_cnt, s->kp_stride, s->k_descriptor, s->desc,
-                                           s->desc_len, stream);
+    // the first half of icpmi_feature_align_batch for this range, into the store
+    return ft_cloud_stages(ft_store_tables(h, s), h->pts, off_host, first, n_new, h->ids + first, ft_store_cfg(s), h->voxel_ws,
+                           h->voxel_ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int icpmi_history_search(const icpmi_history* h, const int32_t* pair_src, const int32_t* pair_tgt, int32_t n_pairs,

@@ -57,10 +57,88 @@ def test_library_exports_the_feature_entry_points():
     for s in NEW_SYMBOLS:
         assert hasattr(L, s), s
         assert s in _lib.EXPORTS, s
-    # the chain's workspace: described once (csrc/features.hip, FtWs); a start per pair adds a source copy per pair
+    # the workspace of both chains: described once (csrc/features.hip, FtWs); a start per pair adds a source copy per pair
     q = lib.icpmi_feature_align_batch_workspace_bytes
     assert q(-1, 1, 1, 1, 100, 0) == 0 and q(1000, 3, 500, 2, 100, 0) > 1000 * 24
     assert q(1000, 3, 500, 2, 100, 1) >= q(1000, 3, 500, 2, 100, 0) + 2 * 500 * 40
+
+
+FAKE = 4096                                                    # a non-null address that is never dereferenced
+ERR_ARG, ERR_WORKSPACE, ERR_UNSUPPORTED = -1, -2, -4
+
+
+def test_align_batch_refuses_bad_arguments_on_the_host():
+    """Every refusal icpmi_feature_align_batch decides on the host, before any launch (the device pointers are fakes that
+    are never dereferenced), and the order in which it decides when two faults coincide: a bad argument before an
+    unsupported one, both before "no pairs: nothing to do", that before the host offsets, those before the workspace, and
+    the workspace before the host sources of a start per pair."""
+    import icpmi
+    L = icpmi.lib()
+    align = L.icpmi_feature_align_batch
+    off = np.array([0, 300, 600], dtype=np.int32)
+    src = np.array([0, 1], dtype=np.int32)
+    offp, srcp = off.ctypes.data_as(ctypes.c_void_p), src.ctypes.data_as(ctypes.c_void_p)
+    need = {w: L.icpmi_feature_align_batch_workspace_bytes(600, 2, 300, 2, 100, w) for w in (0, 1)}
+
+    def call(pts=FAKE, off_dev=FAKE, off_host=offp, n_clouds=2, pair_src=FAKE, pair_src_host=srcp, pair_tgt=FAKE, n_pairs=2,
+             voxel_size=0.2, k_curvature=10, top_n=100, k_descriptor=30, hyp_idx=None, hyp_u=FAKE, n_iter=10, init_in=FAKE,
+             records=FAKE, ws=FAKE, ws_bytes=need[1]):
+        return align(pts, off_dev, off_host, n_clouds, pair_src, pair_src_host, pair_tgt, n_pairs, voxel_size, k_curvature, top_n,
+                     0.3, k_descriptor, 0.64, hyp_idx, hyp_u, n_iter, 0, 0.5, 3, init_in, FAKE, records, ws, ws_bytes, None)
+
+    for kw in (dict(pts=None), dict(off_dev=None), dict(off_host=None), dict(pair_src=None), dict(pair_tgt=None), dict(records=None),
+               dict(ws=None)):
+        assert call(**kw) == ERR_ARG, kw
+    for kw in (dict(n_clouds=0), dict(n_clouds=-1), dict(n_pairs=-1), dict(n_iter=-1), dict(k_curvature=-1), dict(k_descriptor=-1)):
+        assert call(**kw) == ERR_ARG, kw
+    assert call(hyp_idx=FAKE) == ERR_ARG and call(hyp_u=None) == ERR_ARG                # exactly one hypothesis table
+    assert call(pair_src_host=None) == ERR_ARG                                          # a start per pair needs the host mirror
+    assert call(voxel_size=0.0) == ERR_ARG and call(voxel_size=float("nan")) == ERR_ARG
+    assert call(k_curvature=32) == ERR_UNSUPPORTED and call(k_descriptor=32) == ERR_UNSUPPORTED
+    assert call(top_n=257) == ERR_UNSUPPORTED
+    assert call(n_pairs=0) == 0                                                         # nothing to do
+    assert call(n_pairs=0, n_iter=0, hyp_u=None, init_in=None, pair_src_host=None) == 0
+    assert call(ws_bytes=need[1] - 1) == ERR_WORKSPACE
+    assert call(init_in=None, ws_bytes=need[0] - 1) == ERR_WORKSPACE
+    assert call(init_in=None, pair_src_host=None, ws_bytes=need[0] - 1) == ERR_WORKSPACE
+    # two faults at once
+    assert call(k_curvature=32, voxel_size=0.0) == ERR_ARG and call(top_n=257, n_iter=-1) == ERR_ARG
+    assert call(k_descriptor=32, pts=None) == ERR_ARG and call(k_curvature=32, pair_src_host=None) == ERR_ARG
+    assert call(n_pairs=0, pts=None) == ERR_ARG and call(n_pairs=0, voxel_size=0.0) == ERR_ARG
+    assert call(n_pairs=0, k_curvature=32) == ERR_UNSUPPORTED and call(n_pairs=0, top_n=257) == ERR_UNSUPPORTED
+    assert call(n_pairs=0, ws_bytes=0) == 0
+    assert call(k_curvature=32, ws_bytes=0) == ERR_UNSUPPORTED
+    src[:] = (0, 2)
+    assert call() == ERR_ARG                                                            # a source that is no cloud of the set
+    assert call(ws_bytes=need[1] - 1) == ERR_WORKSPACE                                  # the workspace is looked at first
+    assert call(top_n=257) == ERR_UNSUPPORTED
+    src[:] = (-1, 0)
+    assert call() == ERR_ARG
+    src[:] = (0, 1)
+    off[:] = (0, 300, 200)
+    assert call() == ERR_ARG and call(init_in=None) == ERR_ARG                          # decreasing host offsets
+    assert call(ws_bytes=0) == ERR_ARG and call(n_pairs=0) == 0                         # before the workspace, after "no pairs"
+
+
+def test_align_batch_workspace_bytes_against_literal_values():
+    """csrc/features.hip, FtWs: every array rounded up to 256 bytes, 256 at the end.  Two clouds of 300 rows, 2 pairs, top_n
+    100 (stride 104); V is the voxel scratch of a 300-row cloud, icpmi_voxel_workspace_bytes(300) rounded up to 256.
+    Without a start the work set is the caller's clouds, on the caller's offsets and pair list: filtered rows 600 * 16 =
+    9600 -> 9728, counts 256, curvature 4800 -> 4864, keypoints 2 * 104 * 4 = 832 -> 1024, their counts 256, descriptors
+    2 * 104 * 256 = 53248, their lengths 256, matches 2 * 104 * 8 = 1664 -> 1792, their counts 256.
+    With a start per pair it is 4 clouds of 1200 rows: two row arrays of 19200 each, offsets, counts and the pair list 256
+    each, curvature 9600 -> 9728, keypoints 1664 -> 1792, their counts 256, descriptors 106496, their lengths 256, matches
+    1792, their counts 256."""
+    import icpmi
+    L = icpmi.lib()
+    q = L.icpmi_feature_align_batch_workspace_bytes
+    V = -(-L.icpmi_voxel_workspace_bytes(300) // 256) * 256
+    assert q(600, 2, 300, 2, 100, 0) == 9728 + 256 + 4864 + 1024 + 256 + 53248 + 256 + 1792 + 256 + V + 256 == 71936 + V
+    assert q(600, 2, 300, 2, 100, 1) == 2 * 19200 + 3 * 256 + 9728 + 1792 + 256 + 106496 + 256 + 1792 + 256 + V + 256 == 160000 + V
+    assert q(600, 2, 300, 2, 100, 7) == q(600, 2, 300, 2, 100, 1)                      # with_init is a flag
+    assert q(-1, 2, 300, 2, 100, 0) == 0 and q(600, -1, 300, 2, 100, 0) == 0 and q(600, 2, -1, 2, 100, 0) == 0
+    assert q(600, 2, 300, -1, 100, 1) == 0
+    assert q(600, 2, 300, 2, 3, 0) == q(600, 2, 300, 2, 8, 0) == q(600, 2, 300, 2, 0, 0)   # top_n <= 0 or below 8: a stride of 8
 
 
 def test_ransac_draws_are_the_references(monkeypatch):

@@ -59,7 +59,7 @@ def test_new_entries_are_declared_exported_and_bound():
 
 
 def test_workspace_bytes_against_literal_values():
-    """csrc/features.hip, FtHistWs: every array rounded up to 256 bytes, 256 at the end.  5 pairs, top_n 100 (stride 104):
+    """csrc/features.hip, FtWs with no clouds in front: every array rounded up to 256 bytes, 256 at the end.  5 pairs, top_n 100 (stride 104):
     matches 5 * 104 * 8 = 4160 -> 4352, counts 256; with a start per pair and sources of up to 300 rows the work set adds two
     row arrays of 1500 * 16 -> 24064 each, four small arrays of 256, curvature 12000 -> 12032, keypoints 2080 -> 2304,
     descriptors 133120, and 256 of voxel scratch."""
