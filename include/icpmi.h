@@ -1148,6 +1148,105 @@ int icpmi_grid_beam_batch(const int16_t* field, const void* planes, int32_t ny, 
                           double beyond, int32_t half_width, const int32_t* table, int32_t* out_records, int32_t* out_hist,
                           int32_t* out_rows, int32_t row_stride, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the particle filter on the occupancy grid: predict, weigh, resample (no counterpart in the reference) ---------------
+ * Localisation in a finished map, with the particles resident on the device.  N particles, 1 <= N <=
+ * ICPMI_PF_MAX_PARTICLES, are three float64 device arrays: pair_t [N][2] (x, y), theta [N] and cos_sin [N][2] (cos theta,
+ * sin theta) — pair_t and cos_sin in exactly the layout icpmi_grid_beam_batch takes under those names, so the beam model
+ * reads the particles where they are.  A step is icpmi_pf_predict, icpmi_grid_beam_batch (every pair naming the one scan),
+ * icpmi_pf_weights, icpmi_pf_resample when the caller decides so, and icpmi_pf_estimate.  After the beam model's integer
+ * score everything but the estimate is integer, and the estimate is summed in a fixed order: a step is a function of
+ * (inputs, seed, step) to the bit.  No entry synchronises.
+ *
+ * Random numbers: Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; the Random123
+ * constants M0 = 0xD2511F53, M1 = 0xCD9E8D57, W0 = 0x9E3779B9, W1 = 0xBB67AE85), counter-based, no state.  The key is
+ * (seed & 0xffffffff, seed >> 32); the counter is [particle, block, step, purpose], purpose ICPMI_PF_PURPOSE_PREDICT or
+ * ICPMI_PF_PURPOSE_RESAMPLE.  A round maps the counter (c0, c1, c2, c3) under the key (k0, k1) to (hi(M1 c2) ^ c1 ^ k0,
+ * lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)); ten rounds, the key raised by (W0, W1) between them.
+ * Normal deviates without a transcendental function: particle i takes blocks 0 .. ICPMI_PF_PREDICT_BLOCKS - 1, 20 words in
+ * order, each word as two 16-bit halves, the low one first: 40 halves.  Deviate m (m = 0, 1, 2) is z_m = (S_m - 393210) *
+ * 2^-16 with S_m the sum of halves 12 m .. 12 m + 11, an integer in [0, 786420]: the sum of twelve uniforms, exact in float64,
+ * of standard deviation 1 to within 2^-33 and tails to +-6.
+ *
+ * icpmi_pf_predict — the motion model, in place, a lane per particle.  The control (dx, dy, dtheta) is in the robot's
+ * frame.  In float64, every operation rounded on its own:
+ *   ux = dx + sigma_x * z0,  uy = dy + sigma_y * z1,  ut = dtheta + sigma_theta * z2,
+ *   x' = x + (c * ux - s * uy),  y' = y + (s * ux + c * uy),  theta' = theta + ut   (c, s: the particle's cos_sin),
+ *   (c', s') = (cos theta', sin theta') by the device library's sincos (OCML: within 4 ulp).  theta is not wrapped.
+ * Refusals, on the host before anything is enqueued, in this order: n < 0: ICPMI_ERR_ARG; n > ICPMI_PF_MAX_PARTICLES:
+ * ICPMI_ERR_UNSUPPORTED; n == 0: ICPMI_OK, nothing done, whatever else is passed; a null pointer, pair_t or cos_sin not
+ * 16-byte aligned, theta not 8-byte aligned; a control or a deviation that is not finite; a deviation below zero: ICPMI_ERR_ARG.
+ * Launches: pf_predict_kernel, workgroups of ICPMI_PF_THREADS lanes.
+ *
+ * icpmi_pf_weights — beam records to integer weights.  records: device, 16-byte aligned, int32 [n][ICPMI_GB_INTS] as
+ * icpmi_grid_beam_batch left them.  s_max is the largest SCORE among the records with status ICPMI_GB_ST_OK.  An OK record
+ * has d = s_max - score (int64: int32 extremes do not overflow) and the weight min(wtable[d >> shift], ICPMI_PF_MAX_WEIGHT)
+ * where d >> shift < entries, else 0; a record that is not OK has 0.  wtable: device, uint32 [entries], 1 <= entries <=
+ * ICPMI_PF_MAX_ENTRIES, staged (and clipped) into LDS; 0 <= shift <= ICPMI_PF_MAX_SHIFT.  w: device, uint32 [n].  sums:
+ * device, int64 [ICPMI_PF_SUMS] = [W = sum w, sum w^2, OK records, s_max], by integer atomics — the order does not matter;
+ * w <= 2^20 and n <= 2^20 keep W <= 2^40 and sum w^2 <= 2^60.  No OK record: W = 0, and s_max is the least int64.
+ * Refusals, in this order: n as for icpmi_pf_predict; a null pointer, records not 16-byte aligned, sums not 8-byte aligned,
+ * entries or shift outside their ranges: ICPMI_ERR_ARG.
+ * Launches: pf_sums_init_kernel (one wave), pf_max_kernel and pf_weights_kernel (a lane per record; one atomic per
+ * workgroup and slot).
+ *
+ * icpmi_pf_resample — systematic resampling in integers.  C_i: the inclusive prefix sum of w (uint64), W = C_{n-1}.
+ * rho = (r1 * 2^32 + r0) mod W, r0 and r1 the first two words of Philox at counter [0, 0, step, ICPMI_PF_PURPOSE_RESAMPLE].
+ * E_i = floor((n * C_i + rho) / W) in uint64 (n * C_i + rho < 2^61), E_{-1} = 0: particle i has E_i - E_{i-1} offspring,
+ * which sum to n exactly, and new particle j has the ancestor i with E_{i-1} <= j < E_i.  ancestors: device, int32 [n]; the
+ * state is gathered by ancestor from (pair_t, theta, cos_sin) into (out_pair_t, out_theta, out_cos_sin), bit copies; info:
+ * device, int32 [ICPMI_PF_INFO_INTS] = [status, 0, 0, 0], status ICPMI_PF_ST_OK or, where W = 0, ICPMI_PF_ST_DEGENERATE:
+ * the ancestors are then the identity and the state is copied unchanged.
+ * Refusals, in this order: n as for icpmi_pf_predict; a null pointer, a pair_t or cos_sin (in or out) not 16-byte aligned, a
+ * theta not 8-byte aligned, an output that is its own input: ICPMI_ERR_ARG; a workspace that is NULL, not 16-byte aligned or
+ * below icpmi_pf_workspace_bytes(n): ICPMI_ERR_WORKSPACE.
+ * Launches, none of which waits on another workgroup: pf_block_sums_kernel (a workgroup per ICPMI_PF_SCAN_BLOCK weights:
+ * their sum), pf_scan_sums_kernel (ONE workgroup: the exclusive scan of up to ICPMI_PF_MAX_PARTICLES / ICPMI_PF_SCAN_BLOCK
+ * block sums, ICPMI_PF_SUMS_PER_LANE consecutive sums per lane; W, rho, info), pf_offspring_kernel (a workgroup per block
+ * scans it again from its offset and stores E_i as uint32) and pf_gather_kernel (a lane per new particle: a bisection of E,
+ * the ancestor, the copy).
+ *
+ * icpmi_pf_estimate — weighted moments: out, device, float64 [ICPMI_PF_EST_DOUBLES] = [sum w, sum w x, sum w y, sum w c,
+ * sum w s, sum (w x) x, sum (w x) y, sum (w y) y], every product rounded on its own.  Added in a fixed order: a workgroup
+ * per ICPMI_PF_EST_CHUNK particles, lane t adding particles base + t + ICPMI_PF_THREADS k in the order of k, the lanes by
+ * the library's fixed tree; the workgroups' partials in index order by one lane per sum.  No floating-point atomics: the
+ * same inputs give the same bits on every run.
+ * Refusals: n as above (n == 0: ICPMI_OK, nothing written); a null pointer or misaligned pair_t / cos_sin / out (16, 16, 8
+ * bytes): ICPMI_ERR_ARG; the workspace as for icpmi_pf_resample.
+ * Launches: pf_moments_kernel, pf_moments_sum_kernel (one wave).
+ *
+ * icpmi_pf_workspace_bytes(n): what icpmi_pf_resample and icpmi_pf_estimate need for n particles (one buffer serves both,
+ * one call at a time); 0 for n outside [1, ICPMI_PF_MAX_PARTICLES]. */
+#define ICPMI_PF_MAX_PARTICLES 1048576
+#define ICPMI_PF_THREADS 256
+#define ICPMI_PF_PREDICT_BLOCKS 5
+#define ICPMI_PF_PURPOSE_PREDICT 0
+#define ICPMI_PF_PURPOSE_RESAMPLE 1
+#define ICPMI_PF_MAX_ENTRIES 4096
+#define ICPMI_PF_MAX_SHIFT 32
+#define ICPMI_PF_MAX_WEIGHT 1048576
+#define ICPMI_PF_SUMS 4
+#define ICPMI_PF_SUM_W 0
+#define ICPMI_PF_SUM_WW 1
+#define ICPMI_PF_SUM_OK 2
+#define ICPMI_PF_SUM_SMAX 3
+#define ICPMI_PF_SCAN_BLOCK 1024
+#define ICPMI_PF_SUMS_PER_LANE 4
+#define ICPMI_PF_INFO_INTS 4
+#define ICPMI_PF_ST_OK 0
+#define ICPMI_PF_ST_DEGENERATE 1
+#define ICPMI_PF_EST_CHUNK 1024
+#define ICPMI_PF_EST_DOUBLES 8
+int icpmi_pf_predict(int32_t n, double* pair_t, double* theta, double* cos_sin, double dx, double dy, double dtheta,
+                     double sigma_x, double sigma_y, double sigma_theta, uint64_t seed, uint32_t step, void* stream);
+int icpmi_pf_weights(int32_t n, const int32_t* records, const uint32_t* wtable, int32_t entries, int32_t shift, uint32_t* w,
+                     int64_t* sums, void* stream);
+int icpmi_pf_resample(int32_t n, const uint32_t* w, const double* pair_t, const double* theta, const double* cos_sin,
+                      double* out_pair_t, double* out_theta, double* out_cos_sin, int32_t* ancestors, int32_t* info,
+                      uint64_t seed, uint32_t step, void* workspace, size_t workspace_bytes, void* stream);
+int icpmi_pf_estimate(int32_t n, const uint32_t* w, const double* pair_t, const double* cos_sin, double* out, void* workspace,
+                      size_t workspace_bytes, void* stream);
+size_t icpmi_pf_workspace_bytes(int32_t n);
+
 /* ── pose graph: PoseGraph2D.optimize, utilities/pose_graph.py:83-134 ──────────
  * Gauss-Newton on SE(2) over n_nodes poses [x, y, theta] (nodes: device, updated
  * in place) and n_edges constraints (i, j, z_ij [3], Omega [3][3] row-major).

@@ -4,7 +4,8 @@ Host side of libicpmi.so: ``icpmi.batch`` (batched scan-pair ICP on one GPU),
 ``icpmi.dist`` (the same batch sharded over the GPUs of a node), ``icpmi.synth``
 (synthetic scans), ``icpmi.history`` (``ScanHistory``: past scans kept prepared on the
 device for loop-closure matching), ``icpmi.information`` (the information matrix of an ICP result and the pose-graph
-edge it gives), ``icpmi.gridmatch`` (correlative scan-to-map matching against the occupancy grid).  The drop-in modules with the reference's own names live in
+edge it gives), ``icpmi.gridmatch`` (correlative scan-to-map matching against the occupancy grid), ``icpmi.particles``
+(``ParticleFilter``: localisation in the finished map, the particles resident on the device).  The drop-in modules with the reference's own names live in
 the sibling package ``utilities`` (``utilities.icp``, ``utilities.mapping``).
 """
 from ._lib import IcpmiError, build, lib  # noqa: F401
@@ -28,4 +29,9 @@ def __getattr__(name):
         import importlib
         information = importlib.import_module(".information", __name__)
         return information if name == "information" else getattr(information, name)
+    # icpmi.particles, icpmi.ParticleFilter and icpmi.weight_table, the same way
+    if name in ("particles", "ParticleFilter", "weight_table"):
+        import importlib
+        particles = importlib.import_module(".particles", __name__)
+        return particles if name == "particles" else getattr(particles, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -61,6 +61,12 @@ GB_THREADS, GB_CHUNK_ROWS, GB_MAX_HALF_WIDTH, GB_TABLE_CLIP = 256, 256, 127, 327
 GB_INTS, GB_REC_STATUS, GB_REC_ROWS, GB_REC_SCORE, GB_REC_EXPECTED, GB_REC_NOVEL, GB_REC_UNEXPLORED = 8, 0, 1, 2, 3, 4, 5
 GB_ST_OK, GB_ST_EMPTY, GB_ST_CAPACITY, GB_NO_CELLS = 0, 1, 2, -2
 GB_ROW_INTS, GB_ROW_INDEX, GB_ROW_K_HIT, GB_ROW_K_Z, GB_ROW_K_UNKNOWN = 4, 0, 1, 2, 3
+# icpmi_pf_* (PF_*: the particle filter's capacities, the sizes its kernels are built on, the generator's purposes, the slots
+# of the weights' int64 sums, the resampling's info record and statuses, the doubles of the estimate)
+PF_MAX_PARTICLES, PF_THREADS, PF_PREDICT_BLOCKS, PF_PURPOSE_PREDICT, PF_PURPOSE_RESAMPLE = 2 ** 20, 256, 5, 0, 1
+PF_MAX_ENTRIES, PF_MAX_SHIFT, PF_MAX_WEIGHT = 4096, 32, 2 ** 20
+PF_SUMS, PF_SUM_W, PF_SUM_WW, PF_SUM_OK, PF_SUM_SMAX = 4, 0, 1, 2, 3
+PF_SCAN_BLOCK, PF_SUMS_PER_LANE, PF_INFO_INTS, PF_ST_OK, PF_ST_DEGENERATE, PF_EST_CHUNK, PF_EST_DOUBLES = 1024, 4, 4, 0, 1, 1024, 8
 # icpmi_pose_graph_optimize: its statuses (PG_ST_*) and the slots of its info record (PGINFO_*: three values, then PHASES clocks)
 PG_ST_NOTHING, PG_ST_CONVERGED, PG_ST_MAXITER, PG_ST_SINGULAR, PG_ST_REFUSED = 0, 1, 2, 3, 4
 PGINFO_DOUBLES, PGINFO_ITERATIONS, PGINFO_STATUS, PGINFO_STEP, PGINFO_PHASE_US, PGINFO_PHASES = 10, 0, 1, 2, 3, 7
@@ -229,6 +235,11 @@ _SIGS = {
     "icpmi_grid_beam_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double] +
                               [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_int32] +
                               [C.c_void_p] * 4 + [C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "icpmi_pf_predict": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_double] * 6 + [C.c_uint64, C.c_uint32, C.c_void_p]),
+    "icpmi_pf_weights": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "icpmi_pf_resample": (C.c_int, [C.c_int32] + [C.c_void_p] * 9 + [C.c_uint64, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "icpmi_pf_estimate": (C.c_int, [C.c_int32] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
+    "icpmi_pf_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "icpmi_pose_graph_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32]),
     "icpmi_pose_graph_optimize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                             C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_size_t,

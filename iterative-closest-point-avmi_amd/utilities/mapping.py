@@ -642,6 +642,13 @@ class OccupancyGrid2D:
         return self._beam_set(*self._named(history=history, ids=ids, voxel_size=voxel_size), poses, sigma, half_width, beyond, table,
                               occupied_log_odds, field, planes, want_histogram, want_rows)
 
+    def particle_filter(self, n, **kw):
+        """An ``icpmi.particles.ParticleFilter`` of ``n`` particles bound to this grid: localisation in the map as it is now
+        (its bit planes are packed once; ``refresh_map()`` after the grid has changed).  ``kw``: ``seed``, ``temperature`` and
+        the beam model's ``sigma``, ``half_width``, ``beyond``, ``table``, ``occupied_log_odds``, ``field``, ``planes``."""
+        from icpmi.particles import ParticleFilter
+        return ParticleFilter(self, n, **kw)
+
     @staticmethod
     def _history_rows(history, voxel_size):
         """The cloud set of a history's scans at ``voxel_size``: the raw rows (None), the history's own filtered copies where

@@ -1,0 +1,164 @@
+#!/usr/bin/env python3
+"""The resident particle filter (icpmi.particles.ParticleFilter: icpmi_pf_predict, icpmi_grid_beam_batch, icpmi_pf_weights,
+icpmi_pf_resample, icpmi_pf_estimate) beside the path a caller had without it, in the same run: bench.py's config-4 grid
+(2 242 x 2 402 cells at 0.05 m, 32 scans applied) with kept planes, one 360-row scan, N = 512, 4 096 and 65 536 particles,
+one process on one GPU, device events, the variants alternating.  Per N:
+
+  (predict, beam, weights, resample, estimate)
+            each stage's C entry alone on the filter's own tensors, arguments prepared once; `beam` is the beam model's
+            launch on the resident particles — the yardstick the step is held against;
+  (step)    the five stages enqueued back to back, resampling every time, nothing read back: what the device does per scan;
+  (filter)  ParticleFilter.predict / weigh / maybe_resample / estimate with their read-backs (the four sums, the eight
+            moments) and the scan's upload: what a caller waits for per scan;
+  (host)    the path of a caller without the filter: OccupancyGrid2D.beam_poses (poses up, records back), pose_weights,
+            systematic resampling and the motion model in NumPy, and the poses with their cos / sin uploaded again.
+
+A sample is BLOCK runs back to back between two events, divided by BLOCK (2 for the variants that synchronise per run);
+SAMPLES samples per variant after a warm-up of each.  `beam_again` samples the yardstick twice: |median(beam) -
+median(beam_again)| is the run-to-run spread a difference has to exceed.  No hardware counters are collected.
+
+usage: time_particles.py [samples] [block]   (prints one JSON line)"""
+import ctypes as C
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "iterative-closest-point-avmi_amd"))
+sys.path.insert(0, REPO)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from icpmi import _lib, gridmatch, synth  # noqa: E402
+from icpmi.batch import _ptr, _stream  # noqa: E402
+
+SAMPLES = int(sys.argv[1]) if len(sys.argv) > 1 else 21
+BLOCK = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+SIZES, ROWS, HALF_WIDTH, TEMPERATURE = (4096, 512, 65536), 360, 8, 8.0
+CONTROL, MOTION = (0.02, 0.0, 0.005), (0.01, 0.01, 0.002)
+
+
+def sample(fn, block):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(block):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / block
+
+
+def stats(v):
+    q1, med, q3 = np.percentile(v, [25, 50, 75])
+    return {"median_ms": round(float(med), 4), "q1_ms": round(float(q1), 4), "q3_ms": round(float(q3), 4),
+            "min_ms": round(float(np.min(v)), 4), "max_ms": round(float(np.max(v)), 4), "samples": len(v)}
+
+
+assert torch.cuda.is_available(), "time_particles.py measures on the GPU: there is nothing to time without one"
+import bench  # noqa: E402
+grid, org, hits, _ = bench.raycast_workload(synth, 32)
+grid.update_scans(org, hits)
+planes = grid.occupancy_planes()
+L = _lib.lib()
+full = synth.scan((0.5, -0.1, np.deg2rad(14.0)), 4242)           # tools/time_beam.py's scan
+scan = full[np.linspace(0, len(full) - 1, ROWS).astype(np.int64)]
+one = gridmatch.cloud_set_of([scan])
+start = np.array([0.5, -0.1, np.deg2rad(14.0)])
+
+
+def variants_of(n):
+    """-> {name: (run, runs per sample)} for n particles, started as a cloud about the scan's pose"""
+    pf = grid.particle_filter(n, seed=n, temperature=TEMPERATURE, half_width=HALF_WIDTH, planes=planes)
+    pf.init_gaussian(start, (0.2, 0.2, 0.05))
+    pf.weigh(scan)                                                 # makes the pair list and leaves real weights
+    pair_host, pair = pf._pair[0]
+    p, st = pf.planes, _stream()
+    spare = pf._spare
+
+    def call(fn, *args):
+        def run():
+            rc = fn(*args)
+            assert rc == 0, rc
+        return run
+
+    state = (_ptr(pf.pair_t), _ptr(pf.theta), _ptr(pf.cos_sin))
+    predict = call(L.icpmi_pf_predict, n, *state, *CONTROL, *MOTION, pf.seed, 1, st)
+    beam = call(L.icpmi_grid_beam_batch, None, _ptr(p.buf), p.ny, p.nx, p.threshold, float(grid.min_x), float(grid.min_y), float(grid.resolution),
+                _ptr(one.pts), _ptr(one.off), one.off_host.ctypes.data_as(C.c_void_p), _ptr(one.cnt), one.n_clouds, _ptr(pair),
+                pair_host.ctypes.data_as(C.c_void_p), n, state[0], state[2], pf.beyond, HALF_WIDTH, _ptr(pf._beam_table), _ptr(pf.records), None, None,
+                0, None, 0, st)
+    weights = call(L.icpmi_pf_weights, n, _ptr(pf.records), _ptr(pf._weight_table), len(pf.weight_table_host), pf.weight_shift, _ptr(pf.w),
+                   _ptr(pf.sums), st)
+    # (the resampled generation goes to the spare buffers and is not swapped in: every run reads the same particles)
+    resample = call(L.icpmi_pf_resample, n, _ptr(pf.w), *state, _ptr(spare[0]), _ptr(spare[1]), _ptr(spare[2]), _ptr(pf.ancestors), _ptr(pf.info),
+                    pf.seed, 2, _ptr(pf._ws), pf._ws.numel(), st)
+    estimate = call(L.icpmi_pf_estimate, n, _ptr(pf.w), state[0], state[2], _ptr(pf.moments), _ptr(pf._ws), pf._ws.numel(), st)
+    # the motion noise is small and the control is undone every other run, so the cloud stays where the map is
+    back = call(L.icpmi_pf_predict, n, *state, *(-v for v in CONTROL), *MOTION, pf.seed, 3, st)
+    flip = [0]
+
+    def move():
+        flip[0] ^= 1
+        (predict if flip[0] else back)()
+
+    def step():
+        move()
+        beam()
+        weights()
+        resample()
+        estimate()
+
+    own = grid.particle_filter(n, seed=n + 1, temperature=TEMPERATURE, half_width=HALF_WIDTH, planes=planes)
+    own.init_gaussian(start, (0.2, 0.2, 0.05))
+
+    def filter_step():
+        flip[0] ^= 1
+        own.predict(CONTROL if flip[0] else tuple(-v for v in CONTROL), MOTION)
+        own.weigh(scan)
+        own.maybe_resample(0.5)
+        return own.estimate()
+
+    rng = np.random.default_rng(n)
+    host_poses = [start + rng.normal(size=(n, 3)) * (0.2, 0.2, 0.05)]
+    up = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(p.buf.device)            # noqa: E731
+
+    def host_step():
+        poses = host_poses[0]
+        flip[0] ^= 1
+        u = np.array(CONTROL if flip[0] else tuple(-v for v in CONTROL)) + rng.normal(size=(n, 3)) * MOTION
+        c, s = np.cos(poses[:, 2]), np.sin(poses[:, 2])
+        poses = poses + np.stack([c * u[:, 0] - s * u[:, 1], s * u[:, 0] + c * u[:, 1], u[:, 2]], axis=1)
+        info = grid.beam_poses(scan, poses, half_width=HALF_WIDTH, planes=planes)
+        w, ess = gridmatch.pose_weights(info["score"], temperature=TEMPERATURE, status=info["status"])
+        if ess < 0.5 * n:
+            anc = np.minimum(np.searchsorted(np.cumsum(w), (rng.random() + np.arange(n)) / n), n - 1)
+            poses = poses[anc]
+        host_poses[0] = poses
+        mean = (w[:, None] * poses[:, :2]).sum(axis=0)
+        keep = (up(poses[:, :2]), up(np.stack([np.cos(poses[:, 2]), np.sin(poses[:, 2])], axis=1)))      # the next step's upload
+        return mean, keep
+
+    return {"predict": (move, BLOCK), "beam": (beam, BLOCK), "weights": (weights, BLOCK), "resample": (resample, BLOCK), "estimate": (estimate, BLOCK),
+            "step": (step, BLOCK), "filter": (filter_step, 2), "host": (host_step, 2), "beam_again": (beam, BLOCK)}, (pf, own)
+
+
+out = {"grid": [grid.ny, grid.nx], "resolution": grid.resolution, "rows": ROWS, "block": BLOCK, "half_width": HALF_WIDTH, "temperature": TEMPERATURE,
+       "counters": "none collected"}
+for n in SIZES:
+    variants, keep = variants_of(n)
+    for fn, _ in variants.values():
+        sample(fn, 2)
+    times = {name: [] for name in variants}
+    for _ in range(SAMPLES):
+        for name, (fn, block) in variants.items():
+            times[name].append(sample(fn, block))
+    med = lambda name: float(np.median(times[name]))                                              # noqa: E731
+    res = {name: stats(times[name]) for name in variants}
+    res["stages_sum_ms"] = round(sum(med(s) for s in ("predict", "beam", "weights", "resample", "estimate")), 4)
+    res["step_over_beam"] = round(med("step") / med("beam"), 3)
+    res["filter_over_beam"] = round(med("filter") / med("beam"), 3)
+    res["host_over_filter"] = round(med("host") / med("filter"), 3)
+    res["beam_spread_ms"] = round(abs(med("beam") - med("beam_again")), 4)
+    res["ess_of_the_last_filter_step"] = round(float(keep[1].ess), 1)
+    out[f"n{n}"] = res
+print(json.dumps(out))
