@@ -1285,6 +1285,12 @@ size_t icpmi_pf_workspace_bytes(int32_t n);
  * four clocks between assembly and dx stay 0 and the whole elimination is in dx.
  * icpmi_pose_graph_optimize_dense: the same call with the dense path forced;
  * it never returns ICPMI_PG_ST_REFUSED.
+ * Refused on the host before anything is enqueued: null nodes or info,
+ * negative sizes, null edge arrays with n_edges > 0, fix_node or an edge index
+ * outside the graph (ICPMI_ERR_ARG); a null workspace, or one below the plain
+ * size query's value (ICPMI_ERR_WORKSPACE: also where the graph has weak chain
+ * edges; ICPMI_PG_ST_REFUSED is for a workspace that holds the graph without
+ * its twins).
  * workspace: icpmi_pose_graph_workspace_bytes(edges_ij_host, n_nodes, n_edges),
  * icpmi_pose_graph_dense_workspace_bytes(...) for the dense call. */
 #define ICPMI_PG_ST_NOTHING 0

@@ -44,8 +44,18 @@
 // plain kernel loads Omega_q.  The two kernels share every phase's one copy; the plain one keeps the registers, scratch
 // and LDS it had (DESIGN.md has both resource reports).
 //
-// PoseGraph2D.marginals (blocks of H^-1 on the same plan, its own kernels and layout) follows pg_optimize below.
+// Where things are, in this order.  PgPlanWs, the plan's device arrays, listed once as the base of every layout; the
+// optimiser's layouts (PgWs, and PgRobWs = PgWs + two arrays) and kernel arguments (layout + PgCaller, the caller's fields,
+// once for both); the 3 x 3 helpers and pg_linearise; the phases, the two kernels and total_error's kernel; the host plan;
+// pg_stage, the ONE host front of every entry that runs on a plan — it checks the arguments, refuses what the host can
+// refuse before the first HIP call, reads Omega back, finds the weak chain edges, makes the twins' rows, uploads and
+// synchronises — and per entry a host function that hands it a PgCall, fills the kernel's argument and launches; then
+// PoseGraph2D.marginals (blocks of H^-1 on the same plan and front, its own layout MgWs and kernels marg_*).  One file: as
+// a translation unit of their own the marginals left both Gauss-Newton kernels their instructions and 0.3 % more time
+// (DESIGN.md).
 #include "common.hpp"
+#include <optional>
+#include <type_traits>
 #include <vector>
 
 namespace icpmi {
@@ -54,14 +64,17 @@ constexpr int PG_THREADS = 512;                    // one workgroup, 2 waves per
 constexpr double PG_PI = 3.141592653589793;        // np.pi
 constexpr double PG_2PI = 6.283185307179586;       // 2 * np.pi
 
-// The device arrays, listed ONCE: the plan's index arrays, then what the kernel works in (m: edges with the twins,
-// w: twins).  Over a null base it only counts (the *_workspace_bytes queries); over the caller's workspace it is the
-// pointer block the kernel gets by value, inside PgArgs.  The + 1 keep zero-sized arrays distinct.
-struct PgWs {
+// The plan's device arrays, listed ONCE for every layout that runs on a plan (PgWs, PgRobWs, MgWs): a layout derives from
+// this, so the index arrays are carved first, lists its own arrays, and ends with the twins' rows and its size.  Over a
+// null base a layout only counts (the *_workspace_bytes queries); over the caller's workspace it is the pointer block
+// its kernels get by value.  n nodes, m edges with the twins, k closures, w twins.  The + 1 keep zero-sized arrays distinct.
+struct PgPlanWs {
     Carve c;
     int n, m, k, dense, w;
-    // rows of the system, closure unknowns, columns of X: int like the kernel's indices (the workspace of a graph
-    // near 2^31 / 3 rows would not fit any device); every product of two of them is taken in size_t
+    // rows of the system, closure unknowns, columns of the optimiser's X, bytes of [n][9]: int like the kernels' indices
+    // (the workspace of a graph near 2^31 / 3 rows would not fit any device); every product of two of them is taken in
+    // size_t.  The last two are the optimiser's alone and stand here, in front of the pointers, because that is where
+    // pose_graph_kernel's argument had them: behind the index arrays its SGPR spills rose from 120 to 137.
     int N3 = 3 * n, K = 3 * k, ncols = 1 + K;
     size_t blocks = 9 * (size_t)n * 8;
     int32_t* ei = c.take<int32_t>((size_t)m * 2 * 4);            // [m] ei, then [m] ej
@@ -70,6 +83,11 @@ struct PgWs {
     int32_t* csr_edge = c.take<int32_t>(((size_t)2 * m + 1) * 4);        // ... in edge order
     int32_t* loop_slot = c.take<int32_t>((size_t)(m + 1) * 4);   // [m] index among the non-chain edges, -1 for a chain edge
     int32_t* loop_edge = c.take<int32_t>((size_t)(k + 1) * 4);   // [k] edge ids of the non-chain edges
+};
+
+// The optimiser's layout: what pose_graph_kernel works in, inside PgArgs.
+struct PgWs : PgPlanWs {
+    using Base = PgPlanWs;
     // block tridiagonal T per node: D[v] = H[v][v], U[v] = H[v][v+s], L[v] = H[v][v-s] (s = level stride)
     double *D = c.take<double>(blocks), *U = c.take<double>(blocks), *L = c.take<double>(blocks);
     // per even node of a level: L[e] * inv(D[e-s]) and U[e] * inv(D[e+s])
@@ -84,29 +102,26 @@ struct PgWs {
     size_t bytes = c.off + 256;
 };
 
-struct PgArgs : PgWs {
+// what the caller of either optimiser passes: its arrays and settings
+struct PgCaller {
     double* nodes;                 // [n][3] x, y, theta — updated in place
     const double* z;               // [m][3]    the caller's arrays, or tw_z / tw_omega
     const double* omega;           // [m][9]
     int n_iter, fix;
     double eps;
-    double* info;                  // [ICPMI_PGINFO_DOUBLES]
+    double* info;                  // [ICPMI_PGINFO_DOUBLES], the robust kernel's [ICPMI_ROB_DOUBLES]
 };
+struct PgArgs : PgWs, PgCaller {};
 
 // The robust optimiser's device arrays: PgWs, then per edge of the plan (m: with the twins) its weight and its mask.
 struct PgRobWs : PgWs {
+    using Base = PgWs;
     double* wgt = c.take<double>(((size_t)m + 1) * 8);           // [m] w_q of this iteration: 1.0 for an unmasked edge and for a twin
     uint8_t* rob = c.take<uint8_t>((size_t)m + 1);               // [m] the caller's mask, 0 for the twins
     size_t bytes = c.off + 256;                                  // of the whole layout (PgWs::bytes ends before wgt)
 };
 
-struct PgRobArgs : PgRobWs {
-    double* nodes;                 // as PgArgs
-    const double* z;
-    const double* omega;
-    int n_iter, fix;
-    double eps;
-    double* info;                  // [ICPMI_ROB_DOUBLES]
+struct PgRobArgs : PgRobWs, PgCaller {
     const double* omega0;          // [m0][9] the caller's Omega: chi2 is taken of the edge as given, also where it has a twin
     int m0, kernel;                // the caller's edges; ICPMI_ROB_KERNEL_*
     double delta;
@@ -671,10 +686,26 @@ static void pg_sym_eigenvalues(const double* o, double* e) {                 // 
     e[1] = 3.0 * q - e[0] - e[2];
 }
 
+static bool pg_chained(const int32_t* ij, int q) { return ij[2 * q] - ij[2 * q + 1] == 1 || ij[2 * q + 1] - ij[2 * q] == 1; }
+// the weak chain edges of a graph that is split (above): p.stiff, p.weak, or p.refused
+static void pg_find_weak(PgPlan& p, const int32_t* ij, const double* omega, int n, int m) {
+    for (size_t t = 0; t < 9 * (size_t)m; t += 3) p.stiff = fmax(p.stiff, (fabs(omega[t]) + fabs(omega[t + 1])) + fabs(omega[t + 2]));
+    for (int q = 0; q < m; ++q) {
+        if (!pg_chained(ij, q)) continue;
+        double e[3];
+        pg_sym_eigenvalues(omega + 9 * (size_t)q, e);
+        const double lo = fmin(fmin(e[0], e[1]), e[2]);
+        const double amin = fmin(fmin(fabs(e[0]), fabs(e[1])), fabs(e[2])), amax = fmax(fmax(fabs(e[0]), fabs(e[1])), fabs(e[2]));
+        if (!(amin > 64 * 0x1p-53 * amax)) p.refused = true;             // all zero and NaN included
+        else if (!(lo >= p.stiff / (3.0 * n))) p.weak.push_back(q);
+    }
+    if (p.refused) p.weak.clear();
+}
+
 static PgPlan pg_plan(const int32_t* ij, const double* omega, int n, int m, bool force_dense) {
     PgPlan p;
     p.dense = force_dense;
-    const auto chained = [&](int q) { return ij[2 * q] - ij[2 * q + 1] == 1 || ij[2 * q + 1] - ij[2 * q] == 1; };
+    const auto chained = [&](int q) { return pg_chained(ij, q); };
     std::vector<char> linked(n > 1 ? n - 1 : 0, 0);
     for (int q = 0; q < m; ++q) {
         const int i = ij[2 * q], j = ij[2 * q + 1];
@@ -682,19 +713,7 @@ static PgPlan pg_plan(const int32_t* ij, const double* omega, int n, int m, bool
         if (chained(q)) linked[i < j ? i : j] = 1;
     }
     for (char c : linked) if (!c) p.dense = 1;               // a gap in the chain: T would be singular
-    if (!p.dense && omega) {
-        for (size_t t = 0; t < 9 * (size_t)m; t += 3) p.stiff = fmax(p.stiff, (fabs(omega[t]) + fabs(omega[t + 1])) + fabs(omega[t + 2]));
-        for (int q = 0; q < m; ++q) {
-            if (!chained(q)) continue;
-            double e[3];
-            pg_sym_eigenvalues(omega + 9 * (size_t)q, e);
-            const double lo = fmin(fmin(e[0], e[1]), e[2]);
-            const double amin = fmin(fmin(fabs(e[0]), fabs(e[1])), fabs(e[2])), amax = fmax(fmax(fabs(e[0]), fabs(e[1])), fabs(e[2]));
-            if (!(amin > 64 * 0x1p-53 * amax)) p.refused = true;             // all zero and NaN included
-            else if (!(lo >= p.stiff / (3.0 * n))) p.weak.push_back(q);
-        }
-        if (p.refused) p.weak.clear();
-    }
+    if (!p.dense && omega) pg_find_weak(p, ij, omega, n, m);
     p.twins = (int)p.weak.size();
     const int m2 = p.m2 = m + p.twins;
     p.ei_ej.resize(2 * (size_t)m2);
@@ -715,19 +734,20 @@ static PgPlan pg_plan(const int32_t* ij, const double* omega, int n, int m, bool
     }
     return p;
 }
-static size_t pg_workspace_bytes(const int32_t* edges_ij_host, const double* omega_host, int32_t n_nodes, int32_t n_edges, bool force_dense) {
+
+// the layout W of a plan over `base`, built base by base (W::Base) down to PgPlanWs; tail: what W lists after its base (MgWs: s, diag)
+template <class W, class... Tail> static W pg_layout(void* base, int n, const PgPlan& p, Tail... tail) {
+    if constexpr (std::is_same_v<W, PgPlanWs>) return PgPlanWs{base, n, p.m2, p.k, p.dense, p.twins};
+    else return W{pg_layout<typename W::Base>(base, n, p), tail...};
+}
+// a size query: the layout W of the graph's plan, counted over a null base (0: sizes below zero, no edge list, a bad index)
+template <class W, class... Tail> static size_t pg_layout_bytes(const int32_t* edges_ij_host, const double* omega_host, int32_t n_nodes,
+                                                                int32_t n_edges, bool force_dense, Tail... tail) {
     if (n_nodes < 0 || n_edges < 0 || (n_edges > 0 && !edges_ij_host)) return 0;
     const PgPlan p = pg_plan(edges_ij_host, omega_host, n_nodes, n_edges, force_dense);
-    return p.rc == ICPMI_OK ? PgWs{nullptr, n_nodes, p.m2, p.k, p.dense, p.twins}.bytes : 0;
+    return p.rc == ICPMI_OK ? pg_layout<W>(nullptr, n_nodes, p, tail...).bytes : 0;
 }
 
-// an info record without a launch: nothing to do, or the split refused before its first iteration
-static int pg_write_info(double* info, int status, hipStream_t st) {
-    double rec[ICPMI_PGINFO_DOUBLES] = {};
-    rec[ICPMI_PGINFO_STATUS] = (double)status;
-    if (hipMemcpyAsync(info, rec, sizeof(rec), hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
-    return hipStreamSynchronize(st) == hipSuccess ? ICPMI_OK : ICPMI_ERR_HIP;          // `rec` is on this stack frame
-}
 // host <-> device copies of whole vectors (nothing for an empty one); the caller synchronises
 template <class T> static bool pg_upload(T* dst, const std::vector<T>& v, hipStream_t st) {
     return v.empty() || hipMemcpyAsync(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st) == hipSuccess;
@@ -736,41 +756,92 @@ static bool pg_read_back(std::vector<double>& v, const double* src, size_t count
     v.resize(count);
     return hipMemcpyAsync(v.data(), src, count * 8, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
 }
+// pageable host memory: the runtime stages these copies before returning; the plan lives until the synchronise anyway
+static bool pg_upload_plan(const PgPlanWs& w, const PgPlan& p, hipStream_t st) {
+    return pg_upload(w.ei, p.ei_ej, st) && pg_upload(w.csr_ptr, p.csr_ptr, st) && pg_upload(w.csr_edge, p.csr_edge, st) &&
+           pg_upload(w.loop_slot, p.loop_slot, st) && pg_upload(w.loop_edge, p.loop_edge, st);
+}
+// the info record of a call that launches nothing, written from the host
+static int pg_write_info(double* info, const double* record, int doubles, hipStream_t st) {
+    if (hipMemcpyAsync(info, record, (size_t)doubles * 8, hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
+    return hipStreamSynchronize(st) == hipSuccess ? ICPMI_OK : ICPMI_ERR_HIP;          // `record` is on the caller's stack frame
+}
+
+// ── the host front of every entry that runs on a plan: optimize / optimize_dense, optimize_robust, marginals ──
+// What an entry hands it: the caller's arguments that all of them have, and what differs between their info records.
+struct PgCall {
+    const void* nodes;             // only tested for null here
+    const int32_t* ij;             // [m][2] on the host
+    const double *z, *omega;       // [m][3], [m][9] on the device
+    int n, m, n_iter, fix;
+    bool dense;                    // the entry's path rule: forced by the caller, or pg_robust_dense
+    bool evaluates;                // n_iter == 0 still launches (the robust entry's evaluation-only call); else: a MAXITER record
+    double* info;                  // device
+    int info_doubles, status_slot, path_slot;      // of a record written here: its length, where its status goes and (or -1) its path
+    void* workspace;
+    size_t workspace_bytes;
+    hipStream_t st;
+};
+// What it hands back.  Nothing to launch (an error, or a record written here): rc alone.  Else the layout over the
+// caller's workspace, the plan uploaded into it, and z / Omega as the kernels are to read them: the caller's, or the rows
+// with the twins in the workspace.
+template <class W> struct PgStaged {
+    int rc;
+    std::optional<W> w;
+    const double *z, *omega;
+};
+// extras(w, st): the entry's own uploads and memsets, enqueued in front of the one synchronise (what they read on the
+// host lives in the entry's frame); tail: what the layout W lists after its base.  Everything down to the workspace
+// check is decided without a HIP call: a refusal of the host costs no round trip and touches no pointer.
+template <class W, class Extras, class... Tail> static PgStaged<W> pg_stage(const PgCall& c, Extras extras, Tail... tail) {
+    const auto done = [](int rc) { return PgStaged<W>{rc, std::nullopt, nullptr, nullptr}; };
+    const auto record = [&](int status) {
+        double rec[ICPMI_ROB_DOUBLES] = {};                      // the longest of the three
+        static_assert(ICPMI_ROB_DOUBLES >= ICPMI_PGINFO_DOUBLES && ICPMI_ROB_DOUBLES >= ICPMI_MARG_DOUBLES, "info records");
+        rec[c.status_slot] = (double)status;
+        if (c.path_slot >= 0) rec[c.path_slot] = (double)(c.dense ? ICPMI_MARG_PATH_DENSE : ICPMI_MARG_PATH_SPLIT);
+        return done(pg_write_info(c.info, rec, c.info_doubles, c.st));
+    };
+    if (!c.nodes || !c.info || c.n < 0 || c.m < 0 || c.n_iter < 0) return done(ICPMI_ERR_ARG);
+    if (c.m > 0 && (!c.ij || !c.z || !c.omega)) return done(ICPMI_ERR_ARG);
+    if (c.n < 2 || c.m == 0) return record(ICPMI_PG_ST_NOTHING);                       // pose_graph.py:89-91
+    if (c.n_iter == 0 && !c.evaluates) return record(ICPMI_PG_ST_MAXITER);
+    if (c.fix < 0 || c.fix >= c.n) return done(ICPMI_ERR_ARG);
+    const int n = c.n, m = c.m;
+    PgPlan p = pg_plan(c.ij, nullptr, n, m, c.dense);            // without the matrices: every index and the path, no twins
+    if (p.rc != ICPMI_OK) return done(p.rc);
+    if (!c.workspace || c.workspace_bytes < pg_layout<W>(nullptr, n, p, tail...).bytes) return done(ICPMI_ERR_WORKSPACE);
+    std::vector<double> om, zz;
+    if (!p.dense) {                                              // the information matrices, to find the weak chain edges
+        if (!pg_read_back(om, c.omega, 9 * (size_t)m, c.st)) return done(ICPMI_ERR_HIP);
+        pg_find_weak(p, c.ij, om.data(), n, m);
+        if (!p.weak.empty()) p = pg_plan(c.ij, om.data(), n, m, false);      // the lists again, with the twins
+    }
+    PgStaged<W> s{ICPMI_OK, pg_layout<W>(c.workspace, n, p, tail...), c.z, c.omega};
+    const W& w = *s.w;
+    // a chain edge with a null direction, or a workspace sized without the information matrices and so without room for
+    // the twins: the split is refused before anything is launched and the caller continues on the dense path
+    if (p.refused || c.workspace_bytes < w.bytes) return record(ICPMI_PG_ST_REFUSED);
+    if (p.twins) {                                               // the twins' rows are made of the caller's z
+        if (!pg_read_back(zz, c.z, 3 * (size_t)m, c.st)) return done(ICPMI_ERR_HIP);
+        p.add_twin_rows(om.data(), zz.data(), m);
+        if (!pg_upload(w.tw_omega, p.omega, c.st) || !pg_upload(w.tw_z, p.z, c.st)) return done(ICPMI_ERR_HIP);
+        s.z = w.tw_z; s.omega = w.tw_omega;
+    }
+    if (!pg_upload_plan(w, p, c.st) || !extras(w, c.st)) return done(ICPMI_ERR_HIP);
+    if (hipStreamSynchronize(c.st) != hipSuccess) return done(ICPMI_ERR_HIP);          // the plan's vectors are on this stack frame
+    return s;
+}
 
 static int pg_optimize(double* nodes, const int32_t* edges_ij_host, const double* edges_z, const double* edges_omega,
                        int32_t n_nodes, int32_t n_edges, int32_t n_iterations, int32_t fix_node, double convergence_eps,
                        double* info, void* workspace, size_t workspace_bytes, void* stream, bool force_dense) {
-    if (!nodes || !info || n_nodes < 0 || n_edges < 0 || n_iterations < 0) return ICPMI_ERR_ARG;
-    if (n_edges > 0 && (!edges_ij_host || !edges_z || !edges_omega)) return ICPMI_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (n_nodes < 2 || n_edges == 0) return pg_write_info(info, ICPMI_PG_ST_NOTHING, st);          // pose_graph.py:89-91
-    if (n_iterations == 0) return pg_write_info(info, ICPMI_PG_ST_MAXITER, st);
-    if (fix_node < 0 || fix_node >= n_nodes) return ICPMI_ERR_ARG;
-    const int n = n_nodes, m = n_edges;
-    std::vector<double> om, zz;                              // the information matrices, to find the weak chain edges
-    if (!force_dense && !pg_read_back(om, edges_omega, 9 * (size_t)m, st)) return ICPMI_ERR_HIP;
-    PgPlan p = pg_plan(edges_ij_host, force_dense ? nullptr : om.data(), n, m, force_dense);
-    if (p.rc != ICPMI_OK) return p.rc;
-    const PgWs w{workspace, n, p.m2, p.k, p.dense, p.twins};
-    if (!workspace || workspace_bytes < w.bytes || p.refused) {
-        if (!workspace || (!p.twins && !p.refused)) return ICPMI_ERR_WORKSPACE;
-        // a chain edge with a null direction, or a workspace sized without the information matrices
-        // (icpmi_pose_graph_workspace_bytes) and so without room for the twins: the split is refused before its
-        // first iteration and the caller continues on the dense path
-        return pg_write_info(info, ICPMI_PG_ST_REFUSED, st);
-    }
-    PgArgs a{w, nodes, edges_z, edges_omega, n_iterations, fix_node, convergence_eps, info};
-    if (p.twins) {                                           // the twins' rows are made of the caller's z
-        if (!pg_read_back(zz, edges_z, 3 * (size_t)m, st)) return ICPMI_ERR_HIP;
-        p.add_twin_rows(om.data(), zz.data(), m);
-        if (!pg_upload(w.tw_omega, p.omega, st) || !pg_upload(w.tw_z, p.z, st)) return ICPMI_ERR_HIP;
-        a.z = w.tw_z; a.omega = w.tw_omega;
-    }
-    // pageable host memory: the runtime stages these copies before returning; the plan lives until the synchronise anyway
-    if (!pg_upload(w.ei, p.ei_ej, st) || !pg_upload(w.csr_ptr, p.csr_ptr, st) || !pg_upload(w.csr_edge, p.csr_edge, st) ||
-        !pg_upload(w.loop_slot, p.loop_slot, st) || !pg_upload(w.loop_edge, p.loop_edge, st))
-        return ICPMI_ERR_HIP;
-    if (hipStreamSynchronize(st) != hipSuccess) return ICPMI_ERR_HIP;
+    const PgCall c{nodes, edges_ij_host, edges_z, edges_omega, n_nodes, n_edges, n_iterations, fix_node, force_dense, false,
+                   info, ICPMI_PGINFO_DOUBLES, ICPMI_PGINFO_STATUS, -1, workspace, workspace_bytes, st};
+    const PgStaged<PgWs> s = pg_stage<PgWs>(c, [](const PgWs&, hipStream_t) { return true; });
+    if (!s.w) return s.rc;
+    const PgArgs a{*s.w, {nodes, s.z, s.omega, n_iterations, fix_node, convergence_eps, info}};
     pose_graph_kernel<<<1, PG_THREADS, 0, st>>>(a);
     ICPMI_LAUNCH_CHECK();
     return ICPMI_OK;
@@ -788,58 +859,31 @@ static bool pg_robust_dense(const int32_t* ij, const uint8_t* mask, int m, bool 
 }
 static size_t pg_robust_workspace_bytes(const int32_t* edges_ij_host, const double* omega_host, const uint8_t* mask_host,
                                         int32_t n_nodes, int32_t n_edges, bool force_dense) {
-    if (n_nodes < 0 || n_edges < 0 || (n_edges > 0 && (!edges_ij_host || !mask_host))) return 0;
-    const PgPlan p = pg_plan(edges_ij_host, omega_host, n_nodes, n_edges, pg_robust_dense(edges_ij_host, mask_host, n_edges, force_dense));
-    return p.rc == ICPMI_OK ? PgRobWs{{nullptr, n_nodes, p.m2, p.k, p.dense, p.twins}}.bytes : 0;
-}
-static int pg_robust_write_info(double* info, int status, hipStream_t st) {
-    double rec[ICPMI_ROB_DOUBLES] = {};
-    rec[ICPMI_PGINFO_STATUS] = (double)status;
-    if (hipMemcpyAsync(info, rec, sizeof(rec), hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
-    return hipStreamSynchronize(st) == hipSuccess ? ICPMI_OK : ICPMI_ERR_HIP;
+    if (n_edges > 0 && (!edges_ij_host || !mask_host)) return 0;
+    return pg_layout_bytes<PgRobWs>(edges_ij_host, omega_host, n_nodes, n_edges,
+                                    pg_robust_dense(edges_ij_host, mask_host, n_edges, force_dense));
 }
 
 static int pg_optimize_robust(double* nodes, const int32_t* edges_ij_host, const double* edges_z, const double* edges_omega,
                               const uint8_t* mask_host, int32_t n_nodes, int32_t n_edges, int32_t n_iterations, int32_t fix_node,
                               double convergence_eps, int32_t kernel, double delta, bool force_dense, double* edge_chi2,
                               double* edge_weight, double* info, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!nodes || !info || !edge_chi2 || !edge_weight || n_nodes < 0 || n_edges < 0 || n_iterations < 0) return ICPMI_ERR_ARG;
-    if (n_edges > 0 && (!edges_ij_host || !edges_z || !edges_omega || !mask_host)) return ICPMI_ERR_ARG;
+    if (!edge_chi2 || !edge_weight || (n_edges > 0 && (!edges_ij_host || !mask_host))) return ICPMI_ERR_ARG;
     if (kernel != ICPMI_ROB_KERNEL_HUBER && kernel != ICPMI_ROB_KERNEL_CAUCHY && kernel != ICPMI_ROB_KERNEL_GEMAN_MCCLURE) return ICPMI_ERR_ARG;
     if (!(delta > 0.0)) return ICPMI_ERR_ARG;                // NaN included
     hipStream_t st = (hipStream_t)stream;
-    const int n = n_nodes, m = n_edges;
-    if (n >= 2 && m > 0) {
-        // everything the host can refuse comes before the first HIP call: the anchor, the edge indices, and a workspace
-        // below what the graph needs even without twins
-        if (fix_node < 0 || fix_node >= n) return ICPMI_ERR_ARG;
-        const size_t least = pg_robust_workspace_bytes(edges_ij_host, nullptr, mask_host, n, m, force_dense);
-        if (least == 0) return ICPMI_ERR_ARG;
-        if (!workspace || workspace_bytes < least) return ICPMI_ERR_WORKSPACE;
-    }
-    if (n < 2 || m == 0) return pg_robust_write_info(info, ICPMI_PG_ST_NOTHING, st);
-    force_dense = pg_robust_dense(edges_ij_host, mask_host, m, force_dense);
-    std::vector<double> om, zz;
-    if (!force_dense && !pg_read_back(om, edges_omega, 9 * (size_t)m, st)) return ICPMI_ERR_HIP;
-    PgPlan p = pg_plan(edges_ij_host, force_dense ? nullptr : om.data(), n, m, force_dense);
-    if (p.rc != ICPMI_OK) return p.rc;
-    const PgRobWs w{{workspace, n, p.m2, p.k, p.dense, p.twins}};
-    // as pg_optimize: a chain edge with a null direction, or twins without room: the caller continues on the dense path
-    if (p.refused || workspace_bytes < w.bytes) return pg_robust_write_info(info, ICPMI_PG_ST_REFUSED, st);
-    PgRobArgs a{w, nodes, edges_z, edges_omega, n_iterations, fix_node, convergence_eps, info, edges_omega, m, kernel, delta,
-                edge_chi2, edge_weight};
-    if (p.twins) {
-        if (!pg_read_back(zz, edges_z, 3 * (size_t)m, st)) return ICPMI_ERR_HIP;
-        p.add_twin_rows(om.data(), zz.data(), m);
-        if (!pg_upload(w.tw_omega, p.omega, st) || !pg_upload(w.tw_z, p.z, st)) return ICPMI_ERR_HIP;
-        a.z = w.tw_z; a.omega = w.tw_omega;
-    }
-    std::vector<uint8_t> rob(mask_host, mask_host + m);
-    rob.resize(p.m2, 0);                                     // a twin is unmasked by construction
-    if (!pg_upload(w.ei, p.ei_ej, st) || !pg_upload(w.csr_ptr, p.csr_ptr, st) || !pg_upload(w.csr_edge, p.csr_edge, st) ||
-        !pg_upload(w.loop_slot, p.loop_slot, st) || !pg_upload(w.loop_edge, p.loop_edge, st) || !pg_upload(w.rob, rob, st))
-        return ICPMI_ERR_HIP;
-    if (hipStreamSynchronize(st) != hipSuccess) return ICPMI_ERR_HIP;          // the plan's vectors are on this stack frame
+    const PgCall c{nodes, edges_ij_host, edges_z, edges_omega, n_nodes, n_edges, n_iterations, fix_node,
+                   pg_robust_dense(edges_ij_host, mask_host, n_edges, force_dense), true,
+                   info, ICPMI_ROB_DOUBLES, ICPMI_PGINFO_STATUS, -1, workspace, workspace_bytes, st};
+    std::vector<uint8_t> rob;                                // [m2] the caller's mask, then the twins: unmasked by construction
+    const PgStaged<PgRobWs> s = pg_stage<PgRobWs>(c, [&](const PgRobWs& w, hipStream_t st) {
+        rob.assign(mask_host, mask_host + n_edges);
+        rob.resize(w.m, 0);
+        return pg_upload(w.rob, rob, st);
+    });
+    if (!s.w) return s.rc;
+    const PgRobArgs a{*s.w, {nodes, s.z, s.omega, n_iterations, fix_node, convergence_eps, info}, edges_omega, n_edges, kernel, delta,
+                      edge_chi2, edge_weight};
     pose_graph_robust_kernel<<<1, PG_THREADS, 0, st>>>(a);
     ICPMI_LAUNCH_CHECK();
     return ICPMI_OK;
@@ -875,33 +919,26 @@ static int pg_optimize_robust(double* nodes, const int32_t* edges_ij_host, const
 constexpr int MG_THREADS = 256;                    // the grid-wide kernels
 enum MgFlag { MG_REFUSED, MG_SINGULAR, MG_FLAGS };
 
-// The device arrays of a marginals call, listed ONCE (as PgWs: counts over a null base, hands out pointers otherwise).
-// n nodes, m edges with the twins, k closures, w twins, s selected nodes, diag: the diagonal is wanted.
-struct MgWs {
-    Carve c;
-    int n, m, k, dense, w, s, diag;
-    int N3 = 3 * n, K = 3 * k;
-    int ncols = dense ? 0 : K + 3 * s + (diag ? K : 0);          // columns of X: Y = T^-1 W | V = T^-1 E_S | Z = T^-T W
+// The device arrays of a marginals call: the plan's (PgPlanWs), then its own.  s selected nodes, diag: the diagonal is
+// wanted.  Its X has other columns than the optimiser's, and no T on the dense path: xcols and tblocks, not the base's.
+struct MgWs : PgPlanWs {
+    using Base = PgPlanWs;
+    int s, diag;
+    int xcols = dense ? 0 : K + 3 * s + (diag ? K : 0);          // columns of X: Y = T^-1 W | V = T^-1 E_S | Z = T^-T W
     int NL = dense ? N3 : K;                                     // order of the pivoted system: H, or M
     int nrhs = 3 * s + (diag ? N3 : 0);                          // its right-hand sides: 3 per selected node, then (diagonal) 3 per node
-    size_t blocks = dense ? 0 : 9 * (size_t)n * 8;
-    int32_t* ei = c.take<int32_t>((size_t)m * 2 * 4);            // the plan's index arrays, as in PgWs
-    int32_t* ej = ei ? ei + m : nullptr;
-    int32_t* csr_ptr = c.take<int32_t>(((size_t)n + 1) * 4);
-    int32_t* csr_edge = c.take<int32_t>(((size_t)2 * m + 1) * 4);
-    int32_t* loop_slot = c.take<int32_t>((size_t)(m + 1) * 4);
-    int32_t* loop_edge = c.take<int32_t>((size_t)(k + 1) * 4);
+    size_t tblocks = dense ? 0 : blocks;
     int32_t* sel = c.take<int32_t>((size_t)(s + 1) * 4);         // [s] the selected nodes
     int32_t* piv = c.take<int32_t>((size_t)(NL + 1) * 4);        // [NL] pivot rows of the elimination
     int32_t* flag = c.take<int32_t>(MG_FLAGS * 4);               // MgFlag
-    double *D = c.take<double>(blocks), *U = c.take<double>(blocks), *L = c.take<double>(blocks);   // T, as in PgWs
-    double* Sl = c.take<double>(blocks);                         // [n][9] the left Schur complements, inverted
-    double* Td = c.take<double>(diag ? blocks : 0);              // [n][9] the diagonal blocks of T^-1
-    double* X = c.take<double>((size_t)N3 * ncols * 8);          // [3n][ncols] right-hand sides -> solutions
+    double *D = c.take<double>(tblocks), *U = c.take<double>(tblocks), *L = c.take<double>(tblocks);   // T, as in PgWs
+    double* Sl = c.take<double>(tblocks);                        // [n][9] the left Schur complements, inverted
+    double* Td = c.take<double>(diag ? tblocks : 0);             // [n][9] the diagonal blocks of T^-1
+    double* X = c.take<double>((size_t)N3 * xcols * 8);          // [3n][xcols] right-hand sides -> solutions
     double* AB = c.take<double>(18 * (size_t)(k + 1) * 8);       // [k][18] Jacobians of the closures
     double* A = c.take<double>(((size_t)NL * NL + 1) * 8);       // [NL][NL] M or H -> its LU factors
     double* R = c.take<double>(((size_t)NL * nrhs + 1) * 8);     // [NL][nrhs] right-hand sides -> solutions
-    double* tw_omega = w ? c.take<double>((size_t)m * 9 * 8) : nullptr;
+    double* tw_omega = w ? c.take<double>((size_t)m * 9 * 8) : nullptr;      // as in PgWs
     double* tw_z = w ? c.take<double>((size_t)m * 3 * 8) : nullptr;
     size_t bytes = c.off + 256;
 };
@@ -975,8 +1012,8 @@ __global__ __launch_bounds__(MG_THREADS) void marg_closure_jacobians_kernel(MgAr
 // of B_q at node j (both for a self-edge), nothing at the anchor; columns [K, K + 3s): the unit columns of the selection.
 __global__ __launch_bounds__(MG_THREADS) void marg_chain_rhs_kernel(MgArgs g) {
     const size_t t = (size_t)blockIdx.x * MG_THREADS + threadIdx.x;
-    if (t >= (size_t)g.N3 * g.ncols) return;
-    const int row = (int)(t / g.ncols), col = (int)(t % g.ncols), v = row / 3, c = row % 3, K = g.K;
+    if (t >= (size_t)g.N3 * g.xcols) return;
+    const int row = (int)(t / g.xcols), col = (int)(t % g.xcols), v = row / 3, c = row % 3, K = g.K;
     double x = 0.0;
     if (col >= K && col < K + 3 * g.s) x = (g.sel[(col - K) / 3] == v && (col - K) % 3 == c) ? 1.0 : 0.0;
     else if (v != g.fix) {
@@ -1017,7 +1054,7 @@ __global__ void marg_chain_factor_kernel(MgArgs g) {
 
 // T^-1 (columns below K + 3s) or T^-T (the others) on the columns of X: one column per lane, serial along the chain.
 __global__ __launch_bounds__(ICPMI_WAVE) void marg_chain_solve_kernel(MgArgs g) {
-    const int col = blockIdx.x * ICPMI_WAVE + threadIdx.x, n = g.n, ncols = g.ncols;
+    const int col = blockIdx.x * ICPMI_WAVE + threadIdx.x, n = g.n, ncols = g.xcols;
     if (col >= ncols || g.flag[MG_REFUSED]) return;
     const bool tr = col >= g.K + 3 * g.s;
     double y[3] = {0.0, 0.0, 0.0}, t1[3], t2[3];
@@ -1056,7 +1093,7 @@ __global__ __launch_bounds__(MG_THREADS) void marg_closure_system_kernel(MgArgs 
     const int eq = g.loop_edge[q];
     const double* Om = g.omega + 9 * (size_t)eq;
     if (c >= K + s3) {                                           // row r of C Z_v^T, column c - K - s3 = 3v + component
-        const double* Zr = g.X + (size_t)(c - K - s3) * g.ncols + K + s3 + 3 * q;
+        const double* Zr = g.X + (size_t)(c - K - s3) * g.xcols + K + s3 + 3 * q;
         g.R[(size_t)r * g.nrhs + (c - K)] = (Om[3 * a] * Zr[0] + Om[3 * a + 1] * Zr[1]) + Om[3 * a + 2] * Zr[2];
         return;
     }
@@ -1066,8 +1103,8 @@ __global__ __launch_bounds__(MG_THREADS) void marg_closure_system_kernel(MgArgs 
     for (int bb = 0; bb < 3; ++bb) {
         double sum = 0.0;
         for (int cc = 0; cc < 3; ++cc) {
-            if (i != f) sum += AB[3 * bb + cc] * g.X[(size_t)(3 * i + cc) * g.ncols + c];
-            if (j != f) sum += AB[9 + 3 * bb + cc] * g.X[(size_t)(3 * j + cc) * g.ncols + c];
+            if (i != f) sum += AB[3 * bb + cc] * g.X[(size_t)(3 * i + cc) * g.xcols + c];
+            if (j != f) sum += AB[9 + 3 * bb + cc] * g.X[(size_t)(3 * j + cc) * g.xcols + c];
         }
         acc += Om[3 * a + bb] * sum;
     }
@@ -1155,7 +1192,7 @@ __global__ __launch_bounds__(MG_THREADS) void marg_split_out_kernel(MgArgs g) {
     const size_t d = t < nc ? t : t - nc;
     const int e = (int)(d % 9), v = (int)(d / 9 % g.n), K = g.K;
     const int rhs = t < nc ? 3 * (int)(d / 9 / g.n) + e % 3 : 3 * g.s + 3 * v + e % 3;     // column of R
-    const double* Xr = g.X + (size_t)(3 * v + e / 3) * g.ncols;
+    const double* Xr = g.X + (size_t)(3 * v + e / 3) * g.xcols;
     double acc = 0.0;
     for (int q = 0; q < K; ++q) acc += Xr[q] * g.R[(size_t)q * g.nrhs + rhs];
     if (t < nc) g.out_columns[t] = Xr[K + rhs] - acc;
@@ -1187,20 +1224,12 @@ __global__ void marg_info_kernel(MgArgs g) {
     g.info[ICPMI_MARG_TWINS] = (double)g.w;
 }
 
-static int mg_write_info(double* info, int status, int dense, hipStream_t st) {
-    double rec[ICPMI_MARG_DOUBLES] = {};
-    rec[ICPMI_MARG_STATUS] = (double)status;
-    rec[ICPMI_MARG_PATH] = (double)(dense ? ICPMI_MARG_PATH_DENSE : ICPMI_MARG_PATH_SPLIT);
-    if (hipMemcpyAsync(info, rec, sizeof(rec), hipMemcpyHostToDevice, st) != hipSuccess) return ICPMI_ERR_HIP;
-    return hipStreamSynchronize(st) == hipSuccess ? ICPMI_OK : ICPMI_ERR_HIP;
-}
-
+// the kernels index [n][9] and [s][9] in int
+static bool mg_indexable(int32_t n_nodes, int32_t n_selected) { return (size_t)n_nodes <= 0x7fffffffu / 9 && (size_t)n_selected <= 0x7fffffffu / 9; }
 static size_t mg_workspace_bytes(const int32_t* edges_ij_host, const double* omega_host, int32_t n_nodes, int32_t n_edges,
                                  int32_t n_selected, bool diag, bool force_dense) {
-    if (n_nodes < 0 || n_edges < 0 || n_selected < 0 || (n_edges > 0 && !edges_ij_host)) return 0;
-    if ((size_t)n_nodes > 0x7fffffffu / 9 || (size_t)n_selected > 0x7fffffffu / 9) return 0;      // int indices of the kernels
-    const PgPlan p = pg_plan(edges_ij_host, omega_host, n_nodes, n_edges, force_dense);
-    return p.rc == ICPMI_OK ? MgWs{nullptr, n_nodes, p.m2, p.k, p.dense, p.twins, n_selected, diag}.bytes : 0;
+    if (n_selected < 0 || !mg_indexable(n_nodes, n_selected)) return 0;
+    return pg_layout_bytes<MgWs>(edges_ij_host, omega_host, n_nodes, n_edges, force_dense, (int)n_selected, (int)diag);
 }
 
 static inline unsigned mg_grid(size_t items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
@@ -1209,40 +1238,23 @@ static int mg_marginals(const double* nodes, const int32_t* edges_ij_host, const
                         int32_t n_nodes, int32_t n_edges, int32_t fix_node, const int32_t* selected_host, int32_t n_selected,
                         double* out_diagonal, double* out_columns, bool force_dense, double* info, void* workspace,
                         size_t workspace_bytes, void* stream) {
-    if (!nodes || !info || (!out_diagonal && !out_columns) || n_nodes < 0 || n_edges < 0 || n_selected < 0) return ICPMI_ERR_ARG;
-    if (n_edges > 0 && (!edges_ij_host || !edges_z || !edges_omega)) return ICPMI_ERR_ARG;
-    if (n_selected > 0 && !selected_host) return ICPMI_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (n_nodes < 2 || n_edges == 0) return mg_write_info(info, ICPMI_PG_ST_NOTHING, force_dense, st);      // as optimize
-    if (fix_node < 0 || fix_node >= n_nodes) return ICPMI_ERR_ARG;
-    for (int a = 0; a < n_selected; ++a) if (selected_host[a] < 0 || selected_host[a] >= n_nodes) return ICPMI_ERR_ARG;
-    const int n = n_nodes, m = n_edges, s = out_columns ? n_selected : 0, diag = out_diagonal != nullptr;
-    // everything the host can refuse comes before the first HIP call: the edge indices, and a workspace below what
-    // the graph needs even without twins
-    const size_t least = mg_workspace_bytes(edges_ij_host, nullptr, n, m, s, diag, force_dense);
-    if (least == 0) return ICPMI_ERR_ARG;
-    if (!workspace || workspace_bytes < least) return ICPMI_ERR_WORKSPACE;
-    std::vector<double> om, zz;
-    if (!force_dense && !pg_read_back(om, edges_omega, 9 * (size_t)m, st)) return ICPMI_ERR_HIP;
-    PgPlan p = pg_plan(edges_ij_host, force_dense ? nullptr : om.data(), n, m, force_dense);
-    if (p.rc != ICPMI_OK) return p.rc;
-    const MgWs w{workspace, n, p.m2, p.k, p.dense, p.twins, s, diag};
-    // a chain edge with a null direction, or a workspace sized without the information matrices: the caller repeats densely
-    if (p.refused || workspace_bytes < w.bytes) return mg_write_info(info, ICPMI_PG_ST_REFUSED, 0, st);
-    MgArgs a{w, nodes, edges_z, edges_omega, fix_node, out_diagonal, out_columns, info};
-    if (p.twins) {
-        if (!pg_read_back(zz, edges_z, 3 * (size_t)m, st)) return ICPMI_ERR_HIP;
-        p.add_twin_rows(om.data(), zz.data(), m);
-        if (!pg_upload(w.tw_omega, p.omega, st) || !pg_upload(w.tw_z, p.z, st)) return ICPMI_ERR_HIP;
-        a.z = w.tw_z; a.omega = w.tw_omega;
+    if ((!out_diagonal && !out_columns) || n_selected < 0 || (n_selected > 0 && !selected_host)) return ICPMI_ERR_ARG;
+    const int n = n_nodes, s = out_columns ? n_selected : 0, diag = out_diagonal != nullptr;
+    if (n >= 2 && n_edges > 0) {                                 // not where there is nothing to do: that is no error
+        for (int a = 0; a < n_selected; ++a) if (selected_host[a] < 0 || selected_host[a] >= n) return ICPMI_ERR_ARG;
+        if (!mg_indexable(n, s)) return ICPMI_ERR_ARG;
     }
+    hipStream_t st = (hipStream_t)stream;
+    const PgCall c{nodes, edges_ij_host, edges_z, edges_omega, n_nodes, n_edges, 0, fix_node, force_dense, true,
+                   info, ICPMI_MARG_DOUBLES, ICPMI_MARG_STATUS, ICPMI_MARG_PATH, workspace, workspace_bytes, st};
     const std::vector<int32_t> sel(selected_host, selected_host + s);
-    if (!pg_upload(w.ei, p.ei_ej, st) || !pg_upload(w.csr_ptr, p.csr_ptr, st) || !pg_upload(w.csr_edge, p.csr_edge, st) ||
-        !pg_upload(w.loop_slot, p.loop_slot, st) || !pg_upload(w.loop_edge, p.loop_edge, st) || !pg_upload(w.sel, sel, st))
-        return ICPMI_ERR_HIP;
-    if (hipMemsetAsync(w.flag, 0, MG_FLAGS * 4, st) != hipSuccess) return ICPMI_ERR_HIP;
-    if (w.dense && hipMemsetAsync(w.A, 0, (size_t)w.NL * w.NL * 8, st) != hipSuccess) return ICPMI_ERR_HIP;
-    if (hipStreamSynchronize(st) != hipSuccess) return ICPMI_ERR_HIP;          // the plan's vectors are on this stack frame
+    const PgStaged<MgWs> staged = pg_stage<MgWs>(c, [&](const MgWs& w, hipStream_t st) {
+        return pg_upload(w.sel, sel, st) && hipMemsetAsync(w.flag, 0, MG_FLAGS * 4, st) == hipSuccess &&
+               (!w.dense || hipMemsetAsync(w.A, 0, (size_t)w.NL * w.NL * 8, st) == hipSuccess);
+    }, s, diag);
+    if (!staged.w) return staged.rc;
+    const MgWs& w = *staged.w;
+    const MgArgs a{w, nodes, staged.z, staged.omega, fix_node, out_diagonal, out_columns, info};
     const size_t outs = (size_t)s * n * 9;
     marg_assemble_kernel<<<mg_grid(n, MG_THREADS), MG_THREADS, 0, st>>>(a);
     if (w.dense) {
@@ -1254,9 +1266,9 @@ static int mg_marginals(const double* nodes, const int32_t* edges_ij_host, const
         }
     } else {
         if (w.k > 0) marg_closure_jacobians_kernel<<<mg_grid(w.k, MG_THREADS), MG_THREADS, 0, st>>>(a);
-        if (w.ncols > 0) marg_chain_rhs_kernel<<<mg_grid((size_t)w.N3 * w.ncols, MG_THREADS), MG_THREADS, 0, st>>>(a);
+        if (w.xcols > 0) marg_chain_rhs_kernel<<<mg_grid((size_t)w.N3 * w.xcols, MG_THREADS), MG_THREADS, 0, st>>>(a);
         marg_chain_factor_kernel<<<1, ICPMI_WAVE, 0, st>>>(a);
-        if (w.ncols > 0) marg_chain_solve_kernel<<<mg_grid(w.ncols, ICPMI_WAVE), ICPMI_WAVE, 0, st>>>(a);
+        if (w.xcols > 0) marg_chain_solve_kernel<<<mg_grid(w.xcols, ICPMI_WAVE), ICPMI_WAVE, 0, st>>>(a);
         if (w.k > 0) {
             marg_closure_system_kernel<<<mg_grid((size_t)w.K * (w.K + w.nrhs), MG_THREADS), MG_THREADS, 0, st>>>(a);
             marg_lu_factor_kernel<<<1, PG_THREADS, 0, st>>>(w.A, w.NL, w.piv, w.flag, MG_REFUSED);
@@ -1286,14 +1298,14 @@ extern "C" int icpmi_pose_graph_marginals(const double* nodes, const int32_t* ed
 }
 
 extern "C" size_t icpmi_pose_graph_workspace_bytes(const int32_t* edges_ij_host, int32_t n_nodes, int32_t n_edges) {
-    return icpmi::pg_workspace_bytes(edges_ij_host, nullptr, n_nodes, n_edges, false);
+    return icpmi::pg_layout_bytes<icpmi::PgWs>(edges_ij_host, nullptr, n_nodes, n_edges, false);
 }
 extern "C" size_t icpmi_pose_graph_weighted_workspace_bytes(const int32_t* edges_ij_host, const double* edges_omega_host,
                                                             int32_t n_nodes, int32_t n_edges) {
-    return icpmi::pg_workspace_bytes(edges_ij_host, edges_omega_host, n_nodes, n_edges, false);
+    return icpmi::pg_layout_bytes<icpmi::PgWs>(edges_ij_host, edges_omega_host, n_nodes, n_edges, false);
 }
 extern "C" size_t icpmi_pose_graph_dense_workspace_bytes(const int32_t* edges_ij_host, int32_t n_nodes, int32_t n_edges) {
-    return icpmi::pg_workspace_bytes(edges_ij_host, nullptr, n_nodes, n_edges, true);
+    return icpmi::pg_layout_bytes<icpmi::PgWs>(edges_ij_host, nullptr, n_nodes, n_edges, true);
 }
 
 extern "C" int icpmi_pose_graph_optimize(double* nodes, const int32_t* edges_ij_host, const double* edges_z,

@@ -16,6 +16,7 @@ per-edge helper ``_error_and_jacobians`` (pose_graph.py:138-182) has no host
 counterpart here: edges are linearised inside the kernels.
 """
 import ctypes as C
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -53,6 +54,47 @@ def pose_vec_to_matrix(v):
 def relative_transform_vec(T_i, T_j):
     """pose_graph.py:34-37: z_ij = T_i^-1 T_j as [dx, dy, dtheta]."""
     return pose_matrix_to_vec(np.linalg.inv(T_i) @ T_j)
+
+
+def _print_outcome(status, iters, step, n_iterations):
+    """The reference's one line per optimisation (pose_graph.py:118, 131-134)."""
+    if status == SINGULAR:
+        print(f"  PoseGraph: singular H at iter {iters}, stopping")
+    elif status == CONVERGED:
+        print(f"  PoseGraph converged: iter={iters - 1}, ||Δx||={step:.2e}")
+    elif status == MAX_ITERATIONS:
+        print(f"  PoseGraph max iterations: iter={n_iterations}, ||Δx||={step:.2e}")
+
+
+def _continued(launch, n_iterations=None, dense=False, status_slot=_STATUS):
+    """``launch(dense, iterations)`` -> info record, run with the continuation every plan entry has: a split that is
+    refused (``_SPLIT_REFUSED``: before its first iteration by the plan, or in one where a block turns out exactly singular)
+    leaves the poses of the iteration before, and the remaining iterations take the dense matrix.  Returns (record, the
+    refused launch's record or None); the two records of an optimiser (``n_iterations`` given) are merged here:
+    iterations and clocks add up, the step is the split's where the dense run is singular at once, and a robust record
+    keeps the cost of the poses given unless the split was refused at once, where the dense launch has it."""
+    info = launch(dense, n_iterations)
+    if int(info[status_slot]) != _SPLIT_REFUSED:
+        return info, None
+    if n_iterations is None:
+        return launch(True, None), info
+    first, info = info, launch(True, n_iterations - int(info[_ITERATIONS]))
+    info[_ITERATIONS] += first[_ITERATIONS]
+    info[_PHASES] += first[_PHASES]
+    if int(info[_ITERATIONS]) == int(first[_ITERATIONS]):
+        info[_STEP] = first[_STEP]
+    if len(info) == _lib.ROB_DOUBLES:
+        info[_lib.ROB_WEIGHTS_US] += first[_lib.ROB_WEIGHTS_US]
+        if int(first[_ITERATIONS]) > 0:
+            info[_lib.ROB_COST_BEFORE] = first[_lib.ROB_COST_BEFORE]
+    return info, first
+
+
+def _info_dict(info, first):
+    """``last_info`` of an optimiser's (merged) record."""
+    return dict(iterations=int(info[_ITERATIONS]), status=int(info[_STATUS]), step_norm=float(info[_STEP]),
+                split_refused_at=None if first is None else int(first[_ITERATIONS]),
+                phase_us=dict(zip(PHASE_KEYS, info[_PHASES].tolist())))
 
 
 class Marginals:
@@ -141,55 +183,58 @@ class PoseGraph2D:
             om[q] = o
         return ij, z, om
 
+    def _stage(self, fix_node=0, edge_weights=None):
+        """What every device entry takes, staged once: the sizes, the anchor (a negative index counts from the end), the
+        device, the poses / z / Omega on the host and on the device, and the host pointers of the edge list and of Omega
+        (``edge_weights``: Omega times one weight per edge)."""
+        _b.require_gpu()
+        t = SimpleNamespace(n=len(self.nodes), dev=torch.device("cuda", torch.cuda.current_device()))
+        t.ij, t.z, t.om = self._edge_arrays()
+        t.m = len(t.ij)
+        if edge_weights is not None:
+            w = np.asarray(edge_weights, dtype=np.float64)
+            if w.shape != (t.m,):
+                raise ValueError(f"edge_weights needs one weight per edge ({t.m}), got shape {w.shape}")
+            t.om = np.ascontiguousarray(t.om * w[:, None, None])
+        t.fix = int(fix_node + t.n if fix_node < 0 else fix_node)
+        t.poses = np.ascontiguousarray(np.array(self.nodes, dtype=np.float64).reshape(t.n, 3))
+        t.d_nodes, t.d_z, t.d_om = (torch.from_numpy(a).to(t.dev) for a in (t.poses, t.z, t.om))
+        t.ijp, t.omp = t.ij.ctypes.data_as(C.c_void_p), t.om.ctypes.data_as(C.c_void_p)
+        return t
+
+    @staticmethod
+    def _launch(t, what, entry, size, d_info, *args):
+        """One call of a plan entry — ``entry(nodes, edges, z, Omega, *args, info, workspace, its size, stream)`` — in a
+        workspace of ``size`` bytes.  Returns the info record."""
+        ws = torch.empty(max(int(size), 256), dtype=torch.uint8, device=t.dev)
+        _lib.check(entry(_b._ptr(t.d_nodes), t.ijp, _b._ptr(t.d_z), _b._ptr(t.d_om), *args, _b._ptr(d_info), _b._ptr(ws), ws.numel(),
+                         _b._stream()), what)
+        return d_info.cpu().numpy()
+
+    def _take(self, t):
+        out = t.d_nodes.cpu().numpy()
+        for k in range(t.n):                                 # in place, like pose_graph.py:122-125
+            self.nodes[k][:] = out[k]
+
     def optimize(self, n_iterations=20, fix_node=0, convergence_eps=1e-6):
         """pose_graph.py:83-134: Gauss-Newton with the pose at ``fix_node`` held constant."""
-        n = len(self.nodes)
-        if n < 2 or len(self.edges) == 0:
+        if len(self.nodes) < 2 or len(self.edges) == 0:
             return
-        _b.require_gpu()
-        L = _lib.lib()
-        dev = torch.device("cuda", torch.cuda.current_device())
-        ij, z, om = self._edge_arrays()
-        m = len(ij)
-        fix = fix_node + n if fix_node < 0 else fix_node
-        d_nodes = torch.from_numpy(np.ascontiguousarray(np.array(self.nodes, dtype=np.float64).reshape(n, 3))).to(dev)
-        d_z, d_om = torch.from_numpy(z).to(dev), torch.from_numpy(om).to(dev)
-        d_info = torch.zeros(_lib.PGINFO_DOUBLES, dtype=torch.float64, device=dev)
-        ijp = ij.ctypes.data_as(C.c_void_p)
+        t, L = self._stage(fix_node), _lib.lib()
+        d_info = torch.zeros(_lib.PGINFO_DOUBLES, dtype=torch.float64, device=t.dev)
 
-        def launch(size_query, entry, iterations):
-            ws = torch.empty(max(int(size_query(ijp, n, m)), 256), dtype=torch.uint8, device=dev)
-            _lib.check(entry(_b._ptr(d_nodes), ijp, _b._ptr(d_z), _b._ptr(d_om), n, m, iterations, int(fix),
-                             float(convergence_eps), _b._ptr(d_info), _b._ptr(ws), ws.numel(), _b._stream()),
-                       "PoseGraph2D.optimize")
-            return d_info.cpu().numpy()
+        def launch(dense, iterations):
+            # sized with the information matrices: room for the twins of weak chain edges
+            size = (L.icpmi_pose_graph_dense_workspace_bytes(t.ijp, t.n, t.m) if dense
+                    else L.icpmi_pose_graph_weighted_workspace_bytes(t.ijp, t.omp, t.n, t.m))
+            return self._launch(t, "PoseGraph2D.optimize", L.icpmi_pose_graph_optimize_dense if dense else L.icpmi_pose_graph_optimize,
+                                size, d_info, t.n, t.m, iterations, t.fix, float(convergence_eps))
 
-        omp = om.ctypes.data_as(C.c_void_p)                 # with the information matrices: room for the twins of weak chain edges
-        info = launch(lambda *a: L.icpmi_pose_graph_weighted_workspace_bytes(a[0], omp, *a[1:]),
-                      L.icpmi_pose_graph_optimize, int(n_iterations))
-        split_refused_at = None
-        if int(info[_STATUS]) == _SPLIT_REFUSED:
-            # the chain part of the split turned out exactly singular: the remaining iterations take the dense matrix
-            split_refused_at, first = int(info[_ITERATIONS]), info
-            info = launch(L.icpmi_pose_graph_dense_workspace_bytes, L.icpmi_pose_graph_optimize_dense,
-                          int(n_iterations) - split_refused_at)
-            info[_ITERATIONS] += first[_ITERATIONS]
-            info[_PHASES] += first[_PHASES]
-            if int(info[_ITERATIONS]) == split_refused_at:
-                info[_STEP] = first[_STEP]                         # singular at once: the last step applied is the split's
-        out = d_nodes.cpu().numpy()
-        iters, status, step = int(info[_ITERATIONS]), int(info[_STATUS]), info[_STEP]
-        for k in range(n):                                   # in place, like pose_graph.py:122-125
-            self.nodes[k][:] = out[k]
-        self.last_info = dict(iterations=iters, status=status, step_norm=float(step), split_refused_at=split_refused_at,
-                              phase_us=dict(zip(PHASE_KEYS, info[_PHASES].tolist())))
+        info, first = _continued(launch, int(n_iterations))
+        self._take(t)
+        self.last_info = _info_dict(info, first)
         if VERBOSE:
-            if status == SINGULAR:
-                print(f"  PoseGraph: singular H at iter {iters}, stopping")
-            elif status == CONVERGED:
-                print(f"  PoseGraph converged: iter={iters - 1}, ||Δx||={step:.2e}")
-            elif status == MAX_ITERATIONS:
-                print(f"  PoseGraph max iterations: iter={n_iterations}, ||Δx||={step:.2e}")
+            _print_outcome(int(info[_STATUS]), int(info[_ITERATIONS]), info[_STEP], n_iterations)
 
     # ── robust edges (no counterpart in the reference) ────────────────────
     def _robust_mask(self, ij, edges):
@@ -212,40 +257,26 @@ class PoseGraph2D:
         return mask
 
     def _run_robust(self, what, n_iterations, fix_node, convergence_eps, kernel, delta, edges):
-        """The robust entry on the current graph, with the REFUSED -> dense continuation of ``optimize``.
-        -> (nodes (n, 3), info record, the first launch's record or None, chi2, weights, mask)."""
+        """The robust entry on the current graph.  -> (the staging, merged info record, the refused launch's record or
+        None, chi2, weights, mask)."""
         if kernel not in ROBUST_KERNELS:
             raise ValueError(f"unknown robust kernel {kernel!r}: one of {sorted(ROBUST_KERNELS)}")
         if not float(delta) > 0.0:
             raise ValueError(f"delta must be > 0, got {delta!r}")
-        n = len(self.nodes)
-        _b.require_gpu()
-        L = _lib.lib()
-        dev = torch.device("cuda", torch.cuda.current_device())
-        ij, z, om = self._edge_arrays()
-        m = len(ij)
-        mask = self._robust_mask(ij, edges)
-        fix = fix_node + n if fix_node < 0 else fix_node
-        d_nodes = torch.from_numpy(np.ascontiguousarray(np.array(self.nodes, dtype=np.float64).reshape(n, 3))).to(dev)
-        d_z, d_om = torch.from_numpy(z).to(dev), torch.from_numpy(om).to(dev)
-        d_info = torch.zeros(_lib.ROB_DOUBLES, dtype=torch.float64, device=dev)
-        d_chi2, d_wgt = (torch.zeros(m, dtype=torch.float64, device=dev) for _ in range(2))
-        ijp, omp, maskp = (a.ctypes.data_as(C.c_void_p) for a in (ij, om, mask))
+        t, L = self._stage(fix_node), _lib.lib()
+        mask = self._robust_mask(t.ij, edges)
+        maskp = mask.ctypes.data_as(C.c_void_p)
+        d_info = torch.zeros(_lib.ROB_DOUBLES, dtype=torch.float64, device=t.dev)
+        d_chi2, d_wgt = (torch.zeros(t.m, dtype=torch.float64, device=t.dev) for _ in range(2))
 
         def launch(dense, iterations):
-            size = L.icpmi_pose_graph_robust_workspace_bytes(ijp, omp, maskp, n, m, int(dense))
-            ws = torch.empty(max(int(size), 256), dtype=torch.uint8, device=dev)
-            _lib.check(L.icpmi_pose_graph_optimize_robust(
-                _b._ptr(d_nodes), ijp, _b._ptr(d_z), _b._ptr(d_om), maskp, n, m, int(iterations), int(fix), float(convergence_eps),
-                ROBUST_KERNELS[kernel], float(delta), int(dense), _b._ptr(d_chi2), _b._ptr(d_wgt), _b._ptr(d_info), _b._ptr(ws),
-                ws.numel(), _b._stream()), what)
-            return d_info.cpu().numpy()
+            return self._launch(t, what, L.icpmi_pose_graph_optimize_robust,
+                                L.icpmi_pose_graph_robust_workspace_bytes(t.ijp, t.omp, maskp, t.n, t.m, int(dense)), d_info,
+                                maskp, t.n, t.m, iterations, t.fix, float(convergence_eps), ROBUST_KERNELS[kernel], float(delta),
+                                int(dense), _b._ptr(d_chi2), _b._ptr(d_wgt))
 
-        info, first = launch(False, n_iterations), None
-        if int(info[_STATUS]) == _SPLIT_REFUSED:                  # as optimize: the remaining iterations take the dense matrix
-            first = info
-            info = launch(True, int(n_iterations) - int(first[_ITERATIONS]))
-        return d_nodes.cpu().numpy(), info, first, d_chi2.cpu().numpy(), d_wgt.cpu().numpy(), mask.astype(bool)
+        info, first = _continued(launch, int(n_iterations))
+        return t, info, first, d_chi2.cpu().numpy(), d_wgt.cpu().numpy(), mask.astype(bool)
 
     def optimize_robust(self, n_iterations=20, fix_node=0, convergence_eps=1e-6, kernel="huber", delta=2.7955, edges=None):
         """``optimize`` with a robust loss on some edges: Gauss-Newton on sum of chi2 over the plain edges plus sum of
@@ -260,39 +291,20 @@ class PoseGraph2D:
         n = len(self.nodes)
         if n < 2 or len(self.edges) == 0:
             return
-        out, info, first, chi2, weights, mask = self._run_robust("PoseGraph2D.optimize_robust", int(n_iterations), fix_node,
-                                                                 convergence_eps, kernel, delta, edges)
-        split_refused_at = None
-        if first is not None:
-            split_refused_at = int(first[_ITERATIONS])
-            info[_ITERATIONS] += first[_ITERATIONS]
-            info[_PHASES] += first[_PHASES]
-            info[_lib.ROB_WEIGHTS_US] += first[_lib.ROB_WEIGHTS_US]
-            if split_refused_at > 0:
-                info[_lib.ROB_COST_BEFORE] = first[_lib.ROB_COST_BEFORE]     # of the poses given; refused at once, the dense launch has it
-            if int(info[_ITERATIONS]) == split_refused_at:
-                info[_STEP] = first[_STEP]
-        iters, status, step = int(info[_ITERATIONS]), int(info[_STATUS]), info[_STEP]
-        for k in range(n):
-            self.nodes[k][:] = out[k]
+        t, info, first, chi2, weights, mask = self._run_robust("PoseGraph2D.optimize_robust", n_iterations, fix_node,
+                                                               convergence_eps, kernel, delta, edges)
+        self._take(t)
         # the plan's path rule (pg_plan, csrc/posegraph.hip) restated: the split needs every pair of consecutive nodes joined
         # by an edge, none of those edges robust; a refused split went on densely
-        ij = self._edge_arrays()[0]
-        chained = np.abs(ij[:, 0] - ij[:, 1]) == 1
+        chained = np.abs(t.ij[:, 0] - t.ij[:, 1]) == 1
         dense = (first is not None or bool(mask[chained].any())
-                 or len(set(np.minimum(ij[chained, 0], ij[chained, 1]).tolist())) < n - 1)
-        self.last_info = dict(iterations=iters, status=status, step_norm=float(step), split_refused_at=split_refused_at,
-                              phase_us=dict(zip(PHASE_KEYS, info[_PHASES].tolist())),
+                 or len(set(np.minimum(t.ij[chained, 0], t.ij[chained, 1]).tolist())) < n - 1)
+        self.last_info = dict(_info_dict(info, first),
                               cost_before=float(info[_lib.ROB_COST_BEFORE]), cost_after=float(info[_lib.ROB_COST_AFTER]),
                               weights_us=float(info[_lib.ROB_WEIGHTS_US]), path="dense" if dense else "split")
         self.last_robust = dict(chi2=chi2, weights=weights, mask=mask, kernel=kernel, delta=float(delta))
         if VERBOSE:
-            if status == SINGULAR:
-                print(f"  PoseGraph: singular H at iter {iters}, stopping")
-            elif status == CONVERGED:
-                print(f"  PoseGraph converged: iter={iters - 1}, ||Δx||={step:.2e}")
-            elif status == MAX_ITERATIONS:
-                print(f"  PoseGraph max iterations: iter={n_iterations}, ||Δx||={step:.2e}")
+            _print_outcome(int(info[_STATUS]), int(info[_ITERATIONS]), info[_STEP], n_iterations)
 
     def robust_cost(self, kernel, delta, edges=None):
         """(cost, chi2, weights) of the robust loss at the current poses (``optimize_robust`` names the arguments): the
@@ -324,42 +336,23 @@ class PoseGraph2D:
             sel.append(v)
         if not sel and not diagonal:
             raise ValueError("marginals: nothing asked for (diagonal=False and no nodes)")
-        _b.require_gpu()
-        L = _lib.lib()
-        dev = torch.device("cuda", torch.cuda.current_device())
-        ij, z, om = self._edge_arrays()
-        m, s = len(ij), len(sel)
-        if edge_weights is not None:
-            w = np.asarray(edge_weights, dtype=np.float64)
-            if w.shape != (m,):
-                raise ValueError(f"edge_weights needs one weight per edge ({m}), got shape {w.shape}")
-            om = np.ascontiguousarray(om * w[:, None, None])
-        fix = fix_node + n if fix_node < 0 else fix_node
-        poses = np.ascontiguousarray(np.array(self.nodes, dtype=np.float64).reshape(n, 3))
-        d_nodes = torch.from_numpy(poses).to(dev)
-        d_z, d_om = torch.from_numpy(z).to(dev), torch.from_numpy(om).to(dev)
-        d_info = torch.zeros(_lib.MARG_DOUBLES, dtype=torch.float64, device=dev)
-        d_diag = torch.empty((n, 3, 3), dtype=torch.float64, device=dev) if diagonal else None
-        d_cols = torch.empty((s, n, 3, 3), dtype=torch.float64, device=dev) if s else None
+        t, L, s = self._stage(fix_node, edge_weights), _lib.lib(), len(sel)
+        d_info = torch.zeros(_lib.MARG_DOUBLES, dtype=torch.float64, device=t.dev)
+        d_diag = torch.empty((n, 3, 3), dtype=torch.float64, device=t.dev) if diagonal else None
+        d_cols = torch.empty((s, n, 3, 3), dtype=torch.float64, device=t.dev) if s else None
         sel_host = np.ascontiguousarray(np.array(sel, dtype=np.int32))
-        ijp, omp, selp = (a.ctypes.data_as(C.c_void_p) for a in (ij, om, sel_host))
 
-        def launch(dense):
-            size = L.icpmi_pose_graph_marginals_workspace_bytes(ijp, omp, n, m, s, int(bool(diagonal)), int(dense))
-            ws = torch.empty(max(int(size), 256), dtype=torch.uint8, device=dev)
-            _lib.check(L.icpmi_pose_graph_marginals(_b._ptr(d_nodes), ijp, _b._ptr(d_z), _b._ptr(d_om), n, m, int(fix), selp, s,
-                                                    _b._ptr(d_diag) if diagonal else None, _b._ptr(d_cols) if s else None,
-                                                    int(dense), _b._ptr(d_info), _b._ptr(ws), ws.numel(), _b._stream()),
-                       "PoseGraph2D.marginals")
-            return d_info.cpu().numpy()
+        def launch(dense, _):
+            return self._launch(t, "PoseGraph2D.marginals", L.icpmi_pose_graph_marginals,
+                                L.icpmi_pose_graph_marginals_workspace_bytes(t.ijp, t.omp, n, t.m, s, int(bool(diagonal)), int(dense)),
+                                d_info, n, t.m, t.fix, sel_host.ctypes.data_as(C.c_void_p), s, _b._ptr(d_diag) if diagonal else None,
+                                _b._ptr(d_cols) if s else None, int(dense))
 
-        info = launch(bool(force_dense))
-        if int(info[_lib.MARG_STATUS]) == _SPLIT_REFUSED:          # as optimize: go on with the dense matrix
-            info = launch(True)
+        info, _ = _continued(launch, dense=bool(force_dense), status_slot=_lib.MARG_STATUS)
         status = int(info[_lib.MARG_STATUS])
         if status == SINGULAR:
             raise np.linalg.LinAlgError("Singular matrix")
-        return Marginals(poses, fix, sel, d_diag.cpu().numpy() if diagonal else None, d_cols.cpu().numpy() if s else None,
+        return Marginals(t.poses, t.fix, sel, d_diag.cpu().numpy() if diagonal else None, d_cols.cpu().numpy() if s else None,
                          status, "dense" if int(info[_lib.MARG_PATH]) == _lib.MARG_PATH_DENSE else "split")
 
     def get_poses_as_matrices(self):
@@ -369,17 +362,10 @@ class PoseGraph2D:
         """pose_graph.py:189-194: sum of e^T Omega e over the edges."""
         if not self.edges:
             return 0.0
-        _b.require_gpu()
-        dev = torch.device("cuda", torch.cuda.current_device())
-        n = len(self.nodes)
-        ij, z, om = self._edge_arrays()
-        m = len(ij)
-        d_nodes = torch.from_numpy(np.ascontiguousarray(np.array(self.nodes, dtype=np.float64).reshape(n, 3))).to(dev)
-        d_i = torch.from_numpy(np.ascontiguousarray(ij[:, 0])).to(dev)
-        d_j = torch.from_numpy(np.ascontiguousarray(ij[:, 1])).to(dev)
-        d_z, d_om = torch.from_numpy(z).to(dev), torch.from_numpy(om).to(dev)
-        scratch = torch.empty(m + 1, dtype=torch.float64, device=dev)
-        _lib.check(_lib.lib().icpmi_pose_graph_error(_b._ptr(d_nodes), _b._ptr(d_i), _b._ptr(d_j), _b._ptr(d_z), _b._ptr(d_om),
-                                                     m, _b._ptr(scratch), _b._ptr(scratch[m:]), _b._stream()),
+        t = self._stage()
+        d_i, d_j = (torch.from_numpy(np.ascontiguousarray(t.ij[:, c])).to(t.dev) for c in (0, 1))
+        scratch = torch.empty(t.m + 1, dtype=torch.float64, device=t.dev)
+        _lib.check(_lib.lib().icpmi_pose_graph_error(_b._ptr(t.d_nodes), _b._ptr(d_i), _b._ptr(d_j), _b._ptr(t.d_z), _b._ptr(t.d_om),
+                                                     t.m, _b._ptr(scratch), _b._ptr(scratch[t.m:]), _b._stream()),
                    "PoseGraph2D.total_error")
-        return float(scratch[m].item())
+        return float(scratch[t.m].item())

@@ -7,8 +7,6 @@ levels of the chain, more nodes than threads, a closure system wider than 512, b
 indefinite information, the branch cut, the 1e5 offset and every weak-chain case.
 tests/test_pose_graph_marginals_cpu.py holds LAPACK's float64 inverse to the same bound on the same cases.
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -112,41 +110,3 @@ def test_each_output_alone_and_the_accessors(upg):
     empty = upg.PoseGraph2D()
     empty.add_node([0.0, 0.0, 0.0])
     assert empty.marginals() is None                                              # as optimize: nothing to do
-
-
-def test_refused_without_room_for_the_twins_writes_nothing(upg):
-    """A workspace sized without the information matrices has no room for the twins of weak chain edges: the call ends with
-    REFUSED before any kernel and the outputs keep what they held; with fewer than two nodes the status is NOTHING."""
-    import torch
-    from icpmi import _lib
-    from icpmi import batch as _b
-    L = _lib.lib()
-    c = ref.cases()["weak_eps1e-08"]
-    g = c["graph"]
-    n, m = len(g["nodes"]), len(g["ei"])
-    dev = torch.device("cuda", torch.cuda.current_device())
-    ij = np.ascontiguousarray(np.stack([g["ei"], g["ej"]], axis=1).astype(np.int32))
-    d_nodes, d_z, d_om = (torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev) for a in (g["nodes"], g["z"], g["omega"]))
-    d_info = torch.full((_lib.MARG_DOUBLES,), -1.0, dtype=torch.float64, device=dev)
-    d_diag = torch.full((n, 9), 7.0, dtype=torch.float64, device=dev)
-    ijp = ij.ctypes.data_as(C.c_void_p)
-    om_host = np.ascontiguousarray(g["omega"], dtype=np.float64)
-    small = L.icpmi_pose_graph_marginals_workspace_bytes(ijp, None, n, m, 0, 1, 0)
-    full = L.icpmi_pose_graph_marginals_workspace_bytes(ijp, om_host.ctypes.data_as(C.c_void_p), n, m, 0, 1, 0)
-    assert 0 < small < full
-    ws = torch.empty(full, dtype=torch.uint8, device=dev)
-
-    def call(n_nodes, ws_bytes):
-        rc = L.icpmi_pose_graph_marginals(_b._ptr(d_nodes), ijp, _b._ptr(d_z), _b._ptr(d_om), n_nodes, m, c["fix"], None, 0,
-                                          _b._ptr(d_diag), None, 0, _b._ptr(d_info), _b._ptr(ws), ws_bytes, _b._stream())
-        torch.cuda.synchronize()
-        return rc, int(d_info.cpu()[_lib.MARG_STATUS])
-
-    assert call(n, small) == (_lib.OK, _lib.PG_ST_REFUSED)
-    assert bool((d_diag == 7.0).all())
-    assert call(1, full) == (_lib.OK, _lib.PG_ST_NOTHING)
-    assert bool((d_diag == 7.0).all())
-    assert call(n, full) == (_lib.OK, _lib.PG_ST_CONVERGED)
-    r = mref.reference("weak_eps1e-08")
-    got = d_diag.cpu().numpy().reshape(n, 3, 3)
-    assert max(mref.worst_ratio(r, got, [v], v) for v in range(n)) <= 1.0

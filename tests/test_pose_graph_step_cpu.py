@@ -144,3 +144,39 @@ def test_weak_chain_edges_get_room_in_the_workspace():
     for name in ("weak_eps1e-12", "weak_eps0", "weak_zero_matrix", "weak_last_node", "singular_chain"):
         plain, weighted = sizes(ref.cases()[name]["graph"])
         assert weighted == plain > 0, name
+
+
+@pytest.mark.parametrize("entry, size_query", [("icpmi_pose_graph_optimize", "icpmi_pose_graph_workspace_bytes"),
+                                               ("icpmi_pose_graph_optimize_dense", "icpmi_pose_graph_dense_workspace_bytes")])
+def test_host_refusals_come_before_any_launch(entry, size_query):
+    """Fake device pointers on a 6-node chain with one closure: every refusal below is decided on the host before the first
+    HIP call, so none of the pointers is ever touched."""
+    import ctypes as C
+    import os
+    import re
+    import icpmi
+    from conftest import REPO
+    header = open(os.path.join(REPO, "include", "icpmi.h")).read()
+    ERR_ARG, ERR_WORKSPACE = (int(re.search(r"^#define ICPMI_ERR_%s \((-\d+)\)" % k, header, flags=re.M).group(1)) for k in ("ARG", "WORKSPACE"))
+    L = icpmi.lib()
+    ij = np.ascontiguousarray(np.array([(0, 1), (1, 2), (2, 3), (3, 4), (4, 5), (5, 0)], dtype=np.int32))
+    n, m = 6, len(ij)
+    ijp = ij.ctypes.data_as(C.c_void_p)
+    nodes, z, omega, info, ws = [C.c_void_p(0x1000 * (k + 1)) for k in range(5)]
+    least = getattr(L, size_query)(ijp, n, m)
+    assert least > 0
+
+    def call(nodes=nodes, ijp=ijp, z=z, omega=omega, n=n, m=m, iters=5, fix=0, info=info, ws=ws, ws_bytes=least):
+        return getattr(L, entry)(nodes, ijp, z, omega, n, m, iters, fix, 1e-6, info, ws, ws_bytes, None)
+
+    assert call(nodes=None) == ERR_ARG and call(info=None) == ERR_ARG
+    assert call(n=-1) == ERR_ARG and call(m=-1) == ERR_ARG and call(iters=-1) == ERR_ARG
+    assert call(ijp=None) == ERR_ARG and call(z=None) == ERR_ARG and call(omega=None) == ERR_ARG
+    assert call(fix=6) == ERR_ARG and call(fix=-1) == ERR_ARG
+    for bad in ((0, 6), (-1, 2)):
+        bad_ij = ij.copy()
+        bad_ij[2] = bad
+        assert call(ijp=bad_ij.ctypes.data_as(C.c_void_p)) == ERR_ARG
+        assert getattr(L, size_query)(bad_ij.ctypes.data_as(C.c_void_p), n, m) == 0
+    assert call(ws=None) == ERR_WORKSPACE
+    assert call(ws_bytes=least - 1) == ERR_WORKSPACE and call(ws_bytes=0) == ERR_WORKSPACE

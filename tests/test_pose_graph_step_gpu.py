@@ -92,3 +92,68 @@ def test_total_error_against_extended_precision(upg):
         got = _graph(upg, g).total_error()
         print(f"total_error {label}: m {len(g['ei'])} reference {tot!r} device {got!r} error/bound {abs(got - tot) / bound:.3e}")
         assert abs(got - tot) <= bound, (label, got, tot, bound)
+
+
+@pytest.mark.parametrize("entry", ["optimize", "optimize_robust", "marginals"])
+def test_refused_without_room_for_the_twins_writes_nothing(upg, entry):
+    """The three entries that run on a plan share one host front.  On the smallest graph with a twin and a closure — a
+    6-node chain, the closure (5, 0), chain edge 2 with Omega = diag(1e-8, 1e4, 1e4), every other Omega = 1e4 I — a
+    workspace sized without the information matrices has no room for the twin: ICPMI_OK, status REFUSED, and the nodes and
+    every output keep the bytes they held.  Sized with the matrices the call proceeds.  With fewer than two nodes the
+    status is NOTHING and again nothing is written."""
+    import ctypes as C
+    import torch
+    from icpmi import _lib
+    from icpmi import batch as _b
+    L = _lib.lib()
+    n, dev = 6, torch.device("cuda", torch.cuda.current_device())
+    ij = np.ascontiguousarray(np.array([(0, 1), (1, 2), (2, 3), (3, 4), (4, 5), (5, 0)], dtype=np.int32))
+    m = len(ij)
+    t = 2.0 * np.pi * np.arange(n) / n
+    nodes = np.ascontiguousarray(np.stack([np.cos(t), np.sin(t), t + np.pi / 2], axis=1))
+    nodes[1:] += 0.01 * np.array([[1.0, -2.0, 0.5], [-1.5, 0.5, 1.0], [0.5, 1.0, -1.0], [2.0, -0.5, 0.5], [-1.0, 1.5, -0.5]])
+    c, s = np.cos(np.pi / 3), np.sin(np.pi / 3)                                     # consecutive poses of the regular hexagon
+    z = np.ascontiguousarray(np.tile([s, 1.0 - c, np.pi / 3], (m, 1)))
+    om = np.ascontiguousarray(np.tile(1e4 * np.eye(3), (m, 1, 1)))
+    om[2] = np.diag([1e-8, 1e4, 1e4])
+    mask = np.ascontiguousarray(np.array([0, 0, 0, 0, 0, 1], dtype=np.uint8))
+    ijp, omp, maskp = (a.ctypes.data_as(C.c_void_p) for a in (ij, om, mask))
+    d_nodes, d_z, d_om = (torch.from_numpy(a).to(dev) for a in (nodes, z, om))
+    doubles, status_slot = {"optimize": (_lib.PGINFO_DOUBLES, _lib.PGINFO_STATUS), "optimize_robust": (_lib.ROB_DOUBLES, _lib.PGINFO_STATUS),
+                            "marginals": (_lib.MARG_DOUBLES, _lib.MARG_STATUS)}[entry]
+    d_info = torch.full((doubles,), -1.0, dtype=torch.float64, device=dev)
+    # what the entry writes besides nodes and info: nothing; chi2 and weights per edge; the diagonal blocks
+    outs = [torch.full((k,), 7.0, dtype=torch.float64, device=dev) for k in {"optimize": (), "optimize_robust": (m, m), "marginals": (n * 9,)}[entry]]
+    if entry == "optimize":
+        small, full = L.icpmi_pose_graph_workspace_bytes(ijp, n, m), L.icpmi_pose_graph_weighted_workspace_bytes(ijp, omp, n, m)
+    elif entry == "optimize_robust":
+        small, full = (L.icpmi_pose_graph_robust_workspace_bytes(ijp, o, maskp, n, m, 0) for o in (None, omp))
+    else:
+        small, full = (L.icpmi_pose_graph_marginals_workspace_bytes(ijp, o, n, m, 0, 1, 0) for o in (None, omp))
+    assert 0 < small < full
+    ws = torch.empty(full, dtype=torch.uint8, device=dev)
+
+    def call(n_nodes, ws_bytes):
+        common = (_b._ptr(d_nodes), ijp, _b._ptr(d_z), _b._ptr(d_om))
+        tail = (_b._ptr(d_info), _b._ptr(ws), ws_bytes, _b._stream())
+        if entry == "optimize":
+            rc = L.icpmi_pose_graph_optimize(*common, n_nodes, m, 5, 0, 1e-6, *tail)
+        elif entry == "optimize_robust":
+            rc = L.icpmi_pose_graph_optimize_robust(*common, maskp, n_nodes, m, 5, 0, 1e-6, _lib.ROB_KERNEL_HUBER, 2.0, 0,
+                                                    _b._ptr(outs[0]), _b._ptr(outs[1]), *tail)
+        else:
+            rc = L.icpmi_pose_graph_marginals(*common, n_nodes, m, 0, None, 0, _b._ptr(outs[0]), None, 0, *tail)
+        torch.cuda.synchronize()
+        return rc, int(d_info.cpu()[status_slot])
+
+    def untouched():
+        return d_nodes.cpu().numpy().tobytes() == nodes.tobytes() and all(bool((o == 7.0).all()) for o in outs)
+
+    assert call(n, small) == (_lib.OK, _lib.PG_ST_REFUSED)
+    assert untouched()
+    assert call(1, full) == (_lib.OK, _lib.PG_ST_NOTHING)
+    assert untouched()
+    rc, status = call(n, full)
+    assert rc == _lib.OK and status in (_lib.PG_ST_CONVERGED, _lib.PG_ST_MAXITER), (rc, status)
+    assert all(bool(torch.isfinite(o).all()) and not bool((o == 7.0).all()) for o in outs)
+    assert entry == "marginals" or d_nodes.cpu().numpy().tobytes() != nodes.tobytes()
