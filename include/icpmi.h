@@ -26,6 +26,18 @@
  *    `cnt[c]` the number of valid rows (device side, so that voxel filtering,
  *    normals and ICP chain without a host round trip).  cnt == NULL means full
  *    capacity (off[c+1]-off[c]).
+ *
+ * The shape of the declarations
+ *  The Python binding is not written beside this file, it is read from it (icpmi/_header.py, at import): the constants,
+ *  the struct classes and the restype / argtypes of every entry.  So the declarations keep a shape a small reader can
+ *  follow, and the reader refuses the file when a line falls outside it:
+ *  - one `#define ICPMI_<NAME> <integer>` per line, the integer decimal or hex, bare or in parentheses — no expressions;
+ *  - a prototype starts in column 0, `<type> icpmi_<name>(<type> <name>, ...);` over any number of lines, `(void)` for
+ *    no parameters; types are the <stdint.h> names, int, size_t, float, double, and pointers to those, to void, to char
+ *    and to a struct declared above;
+ *  - a struct is `typedef struct icpmi_x { ... } icpmi_x;`, its fields of the same types, declared before its first use.
+ *  Comments may hold anything.  Nothing else stands outside them but the include guard, the two includes and the
+ *  extern "C" guard.
  */
 #ifndef ICPMI_H
 #define ICPMI_H

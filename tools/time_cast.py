@@ -24,7 +24,6 @@ in TB/s).  The walk's rate is rays x mean steps looked at (to the hit, or all th
 hardware counters are collected.  There is no earlier capability to compare a time against.
 
 usage: time_cast.py [samples] [block] [libicpmi_variant.so ...]   (prints one JSON line)"""
-import ctypes as C
 import json
 import os
 import sys
@@ -43,7 +42,6 @@ BLOCK = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 EXTRA = sys.argv[3:]
 HBM_TBS = float(os.environ.get("ICPMI_HBM_TBS", "8.0"))
 REACH, POSES, BEAMS, ROWS = 30.0, 4096, 360, 1430
-ENTRIES = ("icpmi_grid_occupancy_planes_bytes", "icpmi_grid_occupancy_planes", "icpmi_grid_cast_rays")
 
 
 def sample(fn, block=BLOCK):
@@ -63,12 +61,8 @@ def stats(v):
 
 
 def library(name):
-    """A variant library of lib/, with the shipped loader's signatures on the entries timed here."""
-    L = C.CDLL(os.path.join(os.path.dirname(_lib.LIB_PATH), name))
-    for entry in ENTRIES:
-        fn = getattr(L, entry)
-        fn.restype, fn.argtypes = _lib._SIGS[entry]
-    return L
+    """A variant library of lib/ (every object but one is the shipped library's), with the shipped loader's signatures."""
+    return _lib.bind(os.path.join(os.path.dirname(_lib.LIB_PATH), name))
 
 
 assert torch.cuda.is_available(), "time_cast.py measures on the GPU: there is nothing to time without one"

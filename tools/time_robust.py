@@ -66,10 +66,7 @@ def stats(v):
 
 assert torch.cuda.is_available(), "time_robust.py measures on the GPU: there is nothing to time without one"
 if len(sys.argv) > 2:                           # another build: bind what it exports (torch, and with it the HIP runtime, is loaded)
-    L = C.CDLL(os.path.abspath(sys.argv[2]))
-    for name, (res, args) in _lib._SIGS.items():
-        if hasattr(L, name):
-            getattr(L, name).restype, getattr(L, name).argtypes = res, args
+    L = _lib.bind(os.path.abspath(sys.argv[2]), exported_only=True)
 else:
     L = _lib.lib()
 robust = hasattr(L, "icpmi_pose_graph_optimize_robust")
