@@ -22,6 +22,7 @@ The angles' cos / sin are computed here on the host with NumPy (as ``prealign.An
 winner is formed on the host from the record: R from that cos / sin, t = predicted + whole cells.
 """
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -237,39 +238,118 @@ def cast_rays(field_or_planes, threshold, min_x, min_y, resolution, poses_xy, po
     return out
 
 
-def _pair_list(cs, pair_clouds):
-    """The pair list every pair entry takes -> (pair_host int32 [B], the rows of each pair's cloud int64 [B], the device copy):
-    a 2-D cloud set, every pair naming one of its clouds, none of them above ``MAX_ROWS`` rows."""
-    if cs.dim != 2:
-        raise ValueError("pairs against the grid are 2-D")
-    pair_host = np.ascontiguousarray(pair_clouds, dtype=np.int32).reshape(-1)
-    if len(pair_host) and (pair_host.min() < 0 or pair_host.max() >= cs.n_clouds):
-        raise ValueError("pair_clouds must index the cloud set")
-    named = np.diff(cs.off_host).astype(np.int64)[pair_host]
-    if len(named) and int(named.max()) > MAX_ROWS:
-        raise ValueError(f"a cloud above {MAX_ROWS} rows cannot be scored (int32 sums): filter it first")
-    return pair_host, named, torch.from_numpy(pair_host).to(cs.pts.device)
+class GridPairs:
+    """The pair list every pair entry takes: ``host`` (int32 [B], the cloud of each pair), ``dev`` (its device copy, made
+    here, once) and what the checks need of it: ``clouds``, the different clouds it names in rising order, and ``times``, the
+    pairs that name each.  ``on(cloud_set)`` judges the list against a cloud set from those two alone — no pass over the B
+    entries, no upload — so one list serves every cloud set that has the clouds it names."""
+
+    def __init__(self, pair_clouds, device):
+        self.host = np.ascontiguousarray(pair_clouds, dtype=np.int32).reshape(-1)
+        self.B = len(self.host)
+        self.clouds, self.times = np.unique(self.host, return_counts=True)
+        self._ends = self.clouds + 1                               # (the named clouds' entries of a set's offsets, for ``on``)
+        self._host_ptr = C.c_void_p(self.host.ctypes.data)
+        self.dev = torch.from_numpy(self.host).to(device)
+
+    @classmethod
+    def of(cls, pair_clouds, device):
+        """``pair_clouds`` itself when it is a GridPairs already, else a new one on ``device``."""
+        return pair_clouds if isinstance(pair_clouds, cls) else cls(pair_clouds, device)
+
+    def on(self, cs):
+        """The refusals of a pair list against the grid — a 2-D cloud set on the list's device, every pair naming one of its
+        clouds, none of them above ``MAX_ROWS`` rows -> (the rows of the largest named cloud, the rows of all pairs)."""
+        if cs.dim != 2:
+            raise ValueError("pairs against the grid are 2-D")
+        if cs.pts.device != self.dev.device:
+            raise ValueError(f"the clouds live on {cs.pts.device}, the pair list on {self.dev.device}")
+        if not self.B:
+            return 0, 0
+        if self.clouds[0] < 0 or self.clouds[-1] >= cs.n_clouds:
+            raise ValueError("pair_clouds must index the cloud set")
+        named = cs.off_host[self._ends] - cs.off_host[self.clouds]
+        stride = int(named.max())
+        if stride > MAX_ROWS:
+            raise ValueError(f"a cloud above {MAX_ROWS} rows cannot be scored (int32 sums): filter it first")
+        return stride, int(named @ self.times)                      # (int32 rows by int64 times: an int64 sum)
+
+    def args(self, cs):
+        """The pair-list arguments of the four C entries (``pts`` ... ``n_pairs``) for this list on ``cs``."""
+        return (_ptr(cs.pts), _ptr(cs.off), C.c_void_p(cs.off_host.ctypes.data), _ptr(cs.cnt), cs.n_clouds, _ptr(self.dev),
+                self._host_ptr, self.B)
 
 
-def _map_pairs(field_or_planes, threshold, min_x, min_y, resolution, cs, pair_clouds, translations, cos_sin):
-    """Pairs of a cloud set against a map, as ``check_pairs`` and ``beam_pairs`` take them -> (head, tail, keep, B, stride,
-    dev): the arguments their C entries begin with (``field`` ... ``cos_sin``) and end with (workspace, bytes, stream), the
-    arrays and tensors those point into (to be held until the call has returned), the pairs, the rows of the largest named
-    cloud and the map's device."""
-    field, planes, ws, ny, nx, thr, dev = _cast_source(field_or_planes, threshold)
-    if cs.pts.device != dev:
-        raise ValueError(f"the clouds live on {cs.pts.device}, the map on {dev}")
-    if not (np.isfinite(resolution) and resolution > 0.0) or not (np.isfinite(min_x) and np.isfinite(min_y)):
-        raise ValueError(f"resolution must be positive and finite and the map's corner finite, got {resolution}, ({min_x}, {min_y})")
-    pair_host, named, pair = _pair_list(cs, pair_clouds)
-    B = len(pair_host)
-    if int(named.sum()) >= 2 ** 29:
-        raise ValueError(f"{int(named.sum())} rows: fewer than 2^29 fit one call")
-    t, rot = _rows_f64(translations, 2, "translations", dev, B), _rows_f64(cos_sin, 2, "cos_sin", dev, B)
-    head = (_ptr(field), _ptr(planes), ny, nx, thr, float(min_x), float(min_y), float(resolution), _ptr(cs.pts), _ptr(cs.off),
-            cs.off_host.ctypes.data_as(C.c_void_p), _ptr(cs.cnt), cs.n_clouds, _ptr(pair), pair_host.ctypes.data_as(C.c_void_p), B, _ptr(t),
-            _ptr(rot))
-    return head, (_ptr(ws), 0 if ws is None else ws.numel(), _stream()), (pair_host, pair, t, rot, ws), B, int(named.max()) if B else 0, dev
+class MapPairs:
+    """Pairs of a cloud set against a map, checked and uploaded once and then run many times: what ``check_pairs`` and
+    ``beam_pairs`` prepare on every call.  The arguments are theirs.  The object holds what its C calls point into — the
+    planes, or the field with the workspace it is packed into; the cloud set's tensors; the pair list (``pairs``, a
+    ``GridPairs``; one given as ``pair_clouds`` is used as it is); the pose tensors ``t`` and ``rot`` — with ``B``, ``stride``
+    (the rows of the largest named cloud) and ``dev``.  float64 contiguous pose tensors on the map's device are used in place,
+    and ``point_at`` aims the same object at another pair of them.  ``head`` is what the two C entries begin with (``field`` ...
+    ``cos_sin``), ``tail()`` what they end with (workspace, bytes, stream): the stream is the current one of every call."""
+
+    def __init__(self, field_or_planes, threshold, min_x, min_y, resolution, cloud_set, pair_clouds, translations, cos_sin):
+        self.field, self.planes, self.ws, self.ny, self.nx, self.threshold, self.dev = _cast_source(field_or_planes, threshold)
+        cs = self.cs = cloud_set
+        if cs.pts.device != self.dev:
+            raise ValueError(f"the clouds live on {cs.pts.device}, the map on {self.dev}")
+        self.world = (float(min_x), float(min_y), float(resolution))
+        if not (all(map(math.isfinite, self.world)) and resolution > 0.0):
+            raise ValueError(f"resolution must be positive and finite and the map's corner finite, got {resolution}, ({min_x}, {min_y})")
+        self.pairs = GridPairs.of(pair_clouds, self.dev)
+        self.stride, rows = self.pairs.on(cs)
+        if rows >= 2 ** 29:
+            raise ValueError(f"{rows} rows: fewer than 2^29 fit one call")
+        self.B = self.pairs.B
+        self._clouds = (cs.pts, cs.off, cs.off_host, cs.cnt)       # head points into these, whatever becomes of the set
+        self.point_at(translations, cos_sin)
+
+    def point_at(self, translations, cos_sin):
+        """Aim the calls at these poses (B rows of 2 each, as the constructor takes them) -> self.  Nothing else is looked at
+        again: the pair list is neither checked nor uploaded."""
+        self.t, self.rot = _rows_f64(translations, 2, "translations", self.dev, self.B), _rows_f64(cos_sin, 2, "cos_sin", self.dev, self.B)
+        self.head = (_ptr(self.field), _ptr(self.planes), self.ny, self.nx, self.threshold, *self.world, *self.pairs.args(self.cs),
+                     _ptr(self.t), _ptr(self.rot))
+        return self
+
+    def tail(self):
+        return _ptr(self.ws), 0 if self.ws is None else self.ws.numel(), _stream()
+
+    def check(self, tolerance, want_rows=False, out=None):
+        """``check_pairs`` of the prepared pairs -> (records, rows).  With ``out`` given, nothing is allocated."""
+        tol = int(tolerance)
+        if tol != tolerance or not 0 <= tol <= _lib.GK_MAX_TOLERANCE:
+            raise ValueError(f"tolerance must be a whole number of steps in [0, 2^30], got {tolerance}")
+        rec_out, rows_out = (out if want_rows else (out, None)) if out is not None else (None, None)
+        records = _cast_out(rec_out, (self.B, _lib.GK_INTS), self.dev)
+        rows = _cast_out(rows_out, (self.B, self.stride, _lib.GK_ROW_INTS), self.dev) if want_rows else None
+        check(_lib.lib().icpmi_grid_check_batch(*self.head, tol, _ptr(records), _ptr(rows), self.stride, *self.tail()), "grid_check")
+        return records, rows
+
+    def beam(self, table, half_width, beyond, want_hist=False, want_rows=False, out=None):
+        """``beam_pairs`` of the prepared pairs -> (records, hist, rows).  An int32 [2H + 3] ``table`` on the map's device is
+        read where it is; with ``out`` given as well, nothing is allocated."""
+        H = int(half_width)
+        if H != half_width or not 0 <= H <= _lib.GB_MAX_HALF_WIDTH:
+            raise ValueError(f"half_width must be a whole number in [0, {_lib.GB_MAX_HALF_WIDTH}], got {half_width}")
+        if not (math.isfinite(beyond) and beyond >= 0.0):
+            raise ValueError(f"beyond must be finite and not negative, got {beyond}")
+        if not isinstance(table, torch.Tensor):
+            host = np.asarray(table)
+            if host.dtype.kind not in "iu" or host.size and np.abs(host.astype(np.int64)).max() >= 2 ** 31:
+                raise ValueError("table must hold int32 entries")
+            table = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32))
+        if table.dtype != torch.int32 or tuple(table.shape) != (2 * H + 3,):
+            raise ValueError(f"table must be int32 [{2 * H + 3}] for a half width of {H}, got {table.dtype} {tuple(table.shape)}")
+        table = table.to(self.dev).contiguous()
+        rec_out, hist_out, rows_out = (out, None, None) if out is None or isinstance(out, torch.Tensor) else out
+        records = _cast_out(rec_out, (self.B, _lib.GB_INTS), self.dev)
+        hist = _cast_out(hist_out, (self.B, 2 * H + 3), self.dev) if want_hist else None
+        rows = _cast_out(rows_out, (self.B, self.stride, _lib.GB_ROW_INTS), self.dev) if want_rows else None
+        check(_lib.lib().icpmi_grid_beam_batch(*self.head, float(beyond), H, _ptr(table), _ptr(records), _ptr(hist), _ptr(rows), self.stride,
+                                               *self.tail()), "grid_beam")
+        return records, hist, rows
 
 
 def check_pairs(field_or_planes, threshold, min_x, min_y, resolution, cloud_set, pair_clouds, translations, cos_sin, tolerance,
@@ -284,16 +364,8 @@ def check_pairs(field_or_planes, threshold, min_x, min_y, resolution, cloud_set,
     cloud; what lies at or behind a cloud's count is not written.  ``out``: a records tensor, or with ``want_rows`` the pair
     (records, rows), to write into.  The rows are the caller's own float64 (arrays or device tensors).  Enqueues and does not
     synchronise."""
-    head, tail, _keep, B, stride, dev = _map_pairs(field_or_planes, threshold, min_x, min_y, resolution, cloud_set, pair_clouds, translations,
-                                                   cos_sin)       # (_keep: what head and tail point into)
-    tol = int(tolerance)
-    if tol != tolerance or not 0 <= tol <= _lib.GK_MAX_TOLERANCE:
-        raise ValueError(f"tolerance must be a whole number of steps in [0, 2^30], got {tolerance}")
-    rec_out, rows_out = (out if want_rows else (out, None)) if out is not None else (None, None)
-    records = _cast_out(rec_out, (B, _lib.GK_INTS), dev)
-    rows = _cast_out(rows_out, (B, stride, _lib.GK_ROW_INTS), dev) if want_rows else None
-    check(_lib.lib().icpmi_grid_check_batch(*head, tol, _ptr(records), _ptr(rows), stride, *tail), "grid_check")
-    return records, rows
+    return MapPairs(field_or_planes, threshold, min_x, min_y, resolution, cloud_set, pair_clouds, translations, cos_sin).check(
+        tolerance, want_rows, out)
 
 
 def beam_table(resolution, sigma, half_width, z_hit=0.8, z_short=0.1, z_rand=0.1, unexplored=None, scale=1024):
@@ -359,28 +431,8 @@ def beam_pairs(field_or_planes, threshold, min_x, min_y, resolution, cloud_set, 
     0, -1], and what lies at or behind a cloud's count is not written.  ``out``: a records tensor, or the triple (records,
     hist, rows) with None for what is not asked for, to write into.  The rows are the caller's own float64 (arrays or device
     tensors).  Enqueues and does not synchronise."""
-    head, tail, _keep, B, stride, dev = _map_pairs(field_or_planes, threshold, min_x, min_y, resolution, cloud_set, pair_clouds, translations,
-                                                   cos_sin)       # (_keep: what head and tail point into)
-    H = int(half_width)
-    if H != half_width or not 0 <= H <= _lib.GB_MAX_HALF_WIDTH:
-        raise ValueError(f"half_width must be a whole number in [0, {_lib.GB_MAX_HALF_WIDTH}], got {half_width}")
-    if not (np.isfinite(beyond) and beyond >= 0.0):
-        raise ValueError(f"beyond must be finite and not negative, got {beyond}")
-    if not isinstance(table, torch.Tensor):
-        host = np.asarray(table)
-        if host.dtype.kind not in "iu" or host.size and np.abs(host.astype(np.int64)).max() >= 2 ** 31:
-            raise ValueError("table must hold int32 entries")
-        table = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32))
-    if table.dtype != torch.int32 or tuple(table.shape) != (2 * H + 3,):
-        raise ValueError(f"table must be int32 [{2 * H + 3}] for a half width of {H}, got {table.dtype} {tuple(table.shape)}")
-    table = table.to(dev).contiguous()
-    rec_out, hist_out, rows_out = (out, None, None) if out is None or isinstance(out, torch.Tensor) else out
-    records = _cast_out(rec_out, (B, _lib.GB_INTS), dev)
-    hist = _cast_out(hist_out, (B, 2 * H + 3), dev) if want_hist else None
-    rows = _cast_out(rows_out, (B, stride, _lib.GB_ROW_INTS), dev) if want_rows else None
-    check(_lib.lib().icpmi_grid_beam_batch(*head, float(beyond), H, _ptr(table), _ptr(records), _ptr(hist), _ptr(rows), stride, *tail),
-          "grid_beam")
-    return records, hist, rows
+    return MapPairs(field_or_planes, threshold, min_x, min_y, resolution, cloud_set, pair_clouds, translations, cos_sin).beam(
+        table, half_width, beyond, want_hist, want_rows, out)
 
 
 def ray_end_cells(min_x, min_y, resolution, poses_xy, pose_cs, beam_cs, reach):
@@ -523,8 +575,9 @@ class GridMatchBatch:
         require_gpu()
         self.grid, self.cs, self.field = grid, cloud_set, field
         dev = cloud_set.pts.device
-        self.pair_host, _, self.pair = _pair_list(cloud_set, pair_clouds)
-        self.B = B = len(self.pair_host)
+        self.pairs = GridPairs.of(pair_clouds, dev)
+        self.pairs.on(cloud_set)
+        self.B = B = self.pairs.B
         self.t_host = np.ascontiguousarray(np.asarray(translations, dtype=np.float64).reshape(B, 2))
         self.angles = np.ascontiguousarray(np.asarray(angle_rows, dtype=np.float64).reshape(B, -1))
         self.A, self.W, self.centre_angle = self.angles.shape[1], int(window), int(centre_angle)
@@ -554,10 +607,8 @@ class GridMatchBatch:
 
     def _pair_args(self):
         """The arguments the two searches' C entries share: the world, the cloud set and the pairs (``min_x`` ... ``n_angles``)."""
-        g, cs = self.grid, self.cs
-        return (float(g.min_x), float(g.min_y), float(g.resolution), _ptr(cs.pts), _ptr(cs.off), cs.off_host.ctypes.data_as(C.c_void_p),
-                _ptr(cs.cnt), cs.n_clouds, _ptr(self.pair), self.pair_host.ctypes.data_as(C.c_void_p), self.B, _ptr(self.t),
-                _ptr(self.cos_sin), self.A)
+        g = self.grid
+        return (float(g.min_x), float(g.min_y), float(g.resolution), *self.pairs.args(self.cs), _ptr(self.t), _ptr(self.cos_sin), self.A)
 
     def run(self):
         fld = self._field()

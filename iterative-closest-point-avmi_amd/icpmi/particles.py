@@ -6,8 +6,6 @@ scores one scan at every particle where the particles are; its integer scores be
 counter [particle, block, step, purpose]: a step is a function of (inputs, seed, step) to the bit.  A step reads four sums
 back (``weigh``) and, when the caller asks for it, eight more (``estimate``); nothing else crosses to the host.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -101,7 +99,7 @@ class ParticleFilter:
         self.info = torch.zeros(_lib.PF_INFO_INTS, dtype=torch.int32, device=dev)
         self.moments = torch.zeros(_lib.PF_EST_DOUBLES, dtype=torch.float64, device=dev)
         self._ws = torch.empty(max(_lib.lib().icpmi_pf_workspace_bytes(N), 256), dtype=torch.uint8, device=dev)
-        self._pair = {}                                            # cloud index -> (host int32 [N], its device copy)
+        self._pairs = None                                         # the GridPairs of the last scan index: N entries, all that index
         self.last_sums = None
 
     # ── the map ──────────────────────────────────────────────────────────────
@@ -157,29 +155,25 @@ class ParticleFilter:
         return self
 
     # ── the measurement ──────────────────────────────────────────────────────
-    def _weigh(self, cs, cloud):
-        """The beam model (the entry ``gridmatch.beam_pairs`` calls) with every particle naming cloud ``cloud`` of ``cs``, on
-        the filter's own tensors, then the weights -> (ess, OK records)."""
-        g, p = self.grid, self.planes
-        if cs.dim != 2 or cs.pts.device != p.buf.device:
-            raise ValueError("the scan must be 2-D and on the map's device")
+    def scan_pairs(self, cs, cloud):
+        """Every particle of the present generation paired with cloud ``cloud`` of ``cs`` against the filter's planes -> the
+        prepared ``gridmatch.MapPairs``, on the filter's own pose tensors.  The pair list is made once per scan index and
+        kept: a fresh cloud set costs neither an upload nor a pass over the particles."""
         cloud = int(cloud)
-        if not 0 <= cloud < cs.n_clouds:
-            raise ValueError(f"scan {cloud} is not among the {cs.n_clouds} clouds of the set")
-        rows = int(cs.off_host[cloud + 1] - cs.off_host[cloud])
-        if rows > gridmatch.MAX_ROWS or self.n * rows >= 2 ** 29:
-            raise ValueError(f"{self.n} particles x {rows} rows: at most {gridmatch.MAX_ROWS} rows and fewer than 2^29 beams fit one call")
-        if cloud not in self._pair:
-            host = np.full(self.n, cloud, dtype=np.int32)
-            self._pair = {cloud: (host, torch.from_numpy(host).to(p.buf.device))}
-        pair_host, pair = self._pair[cloud]
-        L = _lib.lib()
-        check(L.icpmi_grid_beam_batch(None, _ptr(p.buf), p.ny, p.nx, p.threshold, float(g.min_x), float(g.min_y), float(g.resolution), _ptr(cs.pts),
-                                      _ptr(cs.off), cs.off_host.ctypes.data_as(C.c_void_p), _ptr(cs.cnt), cs.n_clouds, _ptr(pair),
-                                      pair_host.ctypes.data_as(C.c_void_p), self.n, _ptr(self.pair_t), _ptr(self.cos_sin), self.beyond,
-                                      self.half_width, _ptr(self._beam_table), _ptr(self.records), None, None, 0, None, 0, _stream()), "grid_beam")
-        check(L.icpmi_pf_weights(self.n, _ptr(self.records), _ptr(self._weight_table), len(self.weight_table_host), self.weight_shift,
-                                 _ptr(self.w), _ptr(self.sums), _stream()), "pf_weights")
+        if self._pairs is None or int(self._pairs.clouds[0]) != cloud:
+            self._pairs = gridmatch.GridPairs(np.full(self.n, cloud, dtype=np.int32), self.planes.buf.device)
+        g = self.grid
+        return gridmatch.MapPairs(self.planes, None, g.min_x, g.min_y, g.resolution, cs, self._pairs, self.pair_t, self.cos_sin)
+
+    def beam(self, pairs):
+        """Enqueue the beam model of ``scan_pairs``' call into ``records``, with the filter's table, half width and beyond."""
+        return pairs.beam(self._beam_table, self.half_width, self.beyond, out=self.records)[0]
+
+    def _weigh(self, cs, cloud):
+        """The beam model with every particle naming cloud ``cloud`` of ``cs``, then the weights -> (ess, OK records)."""
+        self.beam(self.scan_pairs(cs, cloud))
+        check(_lib.lib().icpmi_pf_weights(self.n, _ptr(self.records), _ptr(self._weight_table), len(self.weight_table_host), self.weight_shift,
+                                          _ptr(self.w), _ptr(self.sums), _stream()), "pf_weights")
         self.last_sums = [int(v) for v in self.sums.cpu().numpy()]         # the step's one synchronisation
         W, WW, ok = self.last_sums[_lib.PF_SUM_W], self.last_sums[_lib.PF_SUM_WW], self.last_sums[_lib.PF_SUM_OK]
         self.ess = W * W / WW if WW else 0.0

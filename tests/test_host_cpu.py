@@ -753,3 +753,111 @@ def test_the_four_pair_entries_judge_a_bad_pair_list_alike():
     assert codes(n_clouds=-1) == (ERR_ARG,) * 4
     assert codes(off_host=False) == (ERR_ARG,) * 4
     assert codes(off=(0, 65536), pair=(0,)) == (ERR_UNSUPPORTED,) * 4        # a cloud above ICPMI_GM_MAX_ROWS
+
+
+def test_map_pairs_forms_the_head_of_the_check_and_the_beam_model_once(monkeypatch):
+    """icpmi.gridmatch.MapPairs over CPU tensors (nothing dereferences them) and a stand-in for the library that records
+    its arguments: the head (``field`` ... ``cos_sin``) and the tail (workspace, bytes, stream) of both C calls equal a tuple
+    written out here in include/icpmi.h's order; GridMatchBatch's pair part is the same GridPairs' output; the stream is
+    asked for at every call and not at construction; re-pointing and a second cloud set leave the pair list alone; and every
+    refusal ``_map_pairs`` raised is raised with its text."""
+    import types
+    import torch
+    from icpmi import _lib, gridmatch
+    from icpmi.batch import CloudSet
+    from test_grid_pairs_gpu import CAPS, COUNTS, K, MIN_X, MIN_Y, NX, NY, PAIRS, RES, THRESHOLD
+    value = lambda args: [getattr(a, "value", a) for a in args]                 # noqa: E731  (c_void_p -> its address, None for null)
+    rng = np.random.default_rng(58)
+    off = np.concatenate([[0], np.cumsum(CAPS)]).astype(np.int32)
+    cs = CloudSet(torch.from_numpy(rng.normal(size=(sum(CAPS), 2))), off, cnt=torch.tensor(COUNTS, dtype=torch.int32))
+    B = len(PAIRS)
+    t, rot, t2, rot2 = (torch.from_numpy(rng.normal(size=(B, 2))) for _ in range(4))
+    planes = gridmatch.OccupancyPlanes(torch.zeros(2 * NY * ((NX + 31) // 32) * 4, dtype=torch.uint8), NY, NX, THRESHOLD)
+    asked, calls = [], []
+    monkeypatch.setattr(gridmatch, "_stream", lambda: asked.append(1) or 1000 + len(asked))
+    record = lambda name: lambda *a: calls.append((name, value(a))) or 0         # noqa: E731
+    fake = types.SimpleNamespace(icpmi_grid_check_batch=record("check"), icpmi_grid_beam_batch=record("beam"),
+                                 icpmi_grid_occupancy_planes_bytes=_lib.lib().icpmi_grid_occupancy_planes_bytes)
+
+    mp = gridmatch.MapPairs(planes, None, MIN_X, MIN_Y, RES, cs, PAIRS, t, rot)
+    assert asked == [] and (mp.B, mp.stride, mp.dev) == (B, 300, torch.device("cpu"))
+    assert mp.t is t and mp.rot is rot                                           # float64, contiguous, on the map's device: in place
+    assert mp.pairs.host.dtype == np.int32 and mp.pairs.host.tolist() == list(PAIRS) and mp.pairs.dev.tolist() == list(PAIRS)
+    assert mp.pairs.clouds.tolist() == [0, 1, 2, 3] and mp.pairs.times.tolist() == [1, 1, 3, 3]
+    pair_part = [cs.pts.data_ptr(), cs.off.data_ptr(), cs.off_host.ctypes.data, cs.cnt.data_ptr(), 4, mp.pairs.dev.data_ptr(),
+                 mp.pairs.host.ctypes.data, B]
+    head = [None, planes.buf.data_ptr(), NY, NX, THRESHOLD, MIN_X, MIN_Y, RES] + pair_part + [t.data_ptr(), rot.data_ptr()]
+    assert value(mp.head) == head and value(mp.pairs.args(cs)) == pair_part
+    rec, rows = torch.zeros((B, _lib.GK_INTS), dtype=torch.int32), torch.zeros((B, 300, _lib.GK_ROW_INTS), dtype=torch.int32)
+    hist, table = torch.zeros((B, 19), dtype=torch.int32), torch.zeros(19, dtype=torch.int32)
+    monkeypatch.setattr(_lib, "lib", lambda: fake)
+    assert mp.check(2, want_rows=True, out=(rec, rows)) == (rec, rows)
+    assert mp.beam(table, 8, 1.5, want_hist=True, out=(rec, hist, None)) == (rec, hist, None)
+    assert calls[0] == ("check", head + [2, rec.data_ptr(), rows.data_ptr(), 300, None, 0, 1001])
+    assert calls[1] == ("beam", head + [1.5, 8, table.data_ptr(), rec.data_ptr(), hist.data_ptr(), None, 300, None, 0, 1002])
+    assert len(asked) == 2                                                       # once per call
+
+    # through a field: the workspace the entry packs the planes into is made at construction and is the tail's
+    fld = torch.zeros((NY, NX), dtype=torch.int16)
+    mf = gridmatch.MapPairs(fld, THRESHOLD, MIN_X, MIN_Y, RES, cs, mp.pairs, t, rot)
+    assert mf.pairs is mp.pairs and value(mf.head)[:5] == [fld.data_ptr(), None, NY, NX, THRESHOLD] and value(mf.head)[5:] == head[5:]
+    assert value(mf.tail()) == [mf.ws.data_ptr(), mf.ws.numel(), 1003] and mf.ws.numel() > 0
+
+    # re-pointed: the two pose pointers change, nothing else; pointed back, the head is the first one
+    dev_before = mp.pairs.dev
+    assert value(mp.point_at(t2, rot2).head) == head[:16] + [t2.data_ptr(), rot2.data_ptr()] and mp.pairs.dev is dev_before
+    assert value(mp.point_at(t, rot).head) == head
+
+    # an existing pair list against a second cloud set — the filter's pattern, all pairs naming cloud 0: judged from the clouds
+    # it names; the B entries are not read (the host array is swapped for something that has an address and nothing else) and
+    # nothing is uploaded
+    zeros = gridmatch.GridPairs(np.zeros(B, dtype=np.int32), torch.device("cpu"))
+    assert zeros.clouds.tolist() == [0] and zeros.times.tolist() == [B]
+    zeros_dev, zeros.host = zeros.dev, types.SimpleNamespace(ctypes=zeros.host.ctypes)
+    uploads = []
+    monkeypatch.setattr(torch, "from_numpy", lambda a: uploads.append(a))
+    for rows_of_scan in (5, 7):
+        scan = CloudSet(torch.zeros((rows_of_scan, 2), dtype=torch.float64), np.array([0, rows_of_scan], dtype=np.int32),
+                        off=torch.tensor([0, rows_of_scan], dtype=torch.int32))
+        one = gridmatch.MapPairs(planes, None, MIN_X, MIN_Y, RES, scan, zeros, t, rot)
+        assert one.pairs is zeros and zeros.dev is zeros_dev and (one.B, one.stride) == (B, rows_of_scan)
+        assert value(one.head)[8:16] == [scan.pts.data_ptr(), scan.off.data_ptr(), scan.off_host.ctypes.data, None, 1, zeros_dev.data_ptr(),
+                                         zeros.host.ctypes.data, B]
+    assert uploads == []
+    monkeypatch.undo()
+
+    # GridMatchBatch hands the same object's output to the two searches
+    monkeypatch.setattr(gridmatch, "require_gpu", lambda: None)
+    grid = types.SimpleNamespace(device_log_odds=torch.zeros((NY, NX), dtype=torch.float32), min_x=MIN_X, min_y=MIN_Y, resolution=RES,
+                                 log_odds_min=-5.0, log_odds_max=5.0)
+    match = gridmatch.GridMatchBatch(grid, cs, mp.pairs, t.numpy(), np.zeros((B, 3)), 0, field=(fld, K))
+    assert match.pairs is mp.pairs and match.B == B
+    assert value(match._pair_args()) == [MIN_X, MIN_Y, RES] + pair_part + [match.t.data_ptr(), match.cos_sin.data_ptr(), 3]
+
+    # the refusals, each with the text it had
+    def refused(text, source=planes, min_x=MIN_X, cloud_set=cs, pair=PAIRS, tr=t):
+        with pytest.raises(ValueError) as e:
+            gridmatch.MapPairs(source, None, min_x, MIN_Y, RES, cloud_set, pair, tr, rot)
+        assert str(e.value) == text
+    set_of = lambda rows, dim=2: CloudSet(torch.zeros((4, dim), dtype=torch.float64), np.array([0, rows], dtype=np.int32),   # noqa: E731
+                                          off=torch.zeros(2, dtype=torch.int32))
+    refused("pairs against the grid are 2-D", cloud_set=set_of(4, 3), pair=[0] * B)
+    refused("pair_clouds must index the cloud set", pair=(2, 3, 0, 1, 2, 4, 2, 3))
+    refused("pair_clouds must index the cloud set", pair=(2, 3, 0, -1, 2, 3, 2, 3))
+    refused("a cloud above 65535 rows cannot be scored (int32 sums): filter it first", cloud_set=set_of(65536), pair=[0] * B)
+    assert gridmatch.MAX_ROWS == 65535 and 65535 * 8193 >= 2 ** 29 > 65535 * 8192
+    many = torch.zeros((8193, 2), dtype=torch.float64)
+    with pytest.raises(ValueError) as e:
+        gridmatch.MapPairs(planes, None, MIN_X, MIN_Y, RES, set_of(65535), np.zeros(8193, dtype=np.int32), many, many)
+    assert str(e.value) == f"{65535 * 8193} rows: fewer than 2^29 fit one call"
+    assert gridmatch.MapPairs(planes, None, MIN_X, MIN_Y, RES, set_of(65535), np.zeros(8192, dtype=np.int32), many[:8192], many[:8192]).B == 8192
+    refused(f"resolution must be positive and finite and the map's corner finite, got {RES}, (nan, {MIN_Y})", min_x=float("nan"))
+    refused(f"translations must be float64 rows of 2, {B} of them", tr=t[:B - 1])
+    refused(f"translations must be float64 rows of 2, {B} of them", tr=torch.zeros((B, 3), dtype=torch.float64))
+    refused("the map must be a contiguous int16 (ny, nx) device field or the OccupancyPlanes of one", source=fld.float())
+    with pytest.raises(ValueError) as e:
+        mp.check(2.5)
+    assert str(e.value) == "tolerance must be a whole number of steps in [0, 2^30], got 2.5"
+    with pytest.raises(ValueError) as e:
+        mp.point_at(t, rot[:3])
+    assert str(e.value) == f"cos_sin must be float64 rows of 2, {B} of them" and mp.t is t and mp.rot is rot

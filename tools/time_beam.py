@@ -3,8 +3,8 @@
 (check_pairs) on the same inputs in the same run: bench.py's config-4 grid (2 242 x 2 402 cells at 0.05 m, 32 scans applied),
 one process on one GPU, device events, the variants alternating:
 
-  (k4k)   the check: 4 096 poses x one 360-row scan over kept planes, the entry called with arguments prepared once — the
-          yardstick; sampled twice (k4k_again);
+  (k4k)   the check: 4 096 poses x one 360-row scan over kept planes, the library's prepared call (gridmatch.MapPairs.check
+          and .beam, outputs given): checked and uploaded once, then run — the yardstick; sampled twice (k4k_again);
   (b4k)   the beam model on those pairs: half width 8, the default table, beyond = 1.5 * (8 + 2) cells;
   (b4h)   (b4k) with the histograms written as well;
   (b4r)   (b4k) with the rows' records written as well;
@@ -21,50 +21,27 @@ is the check's time plus the extra steps of `beyond`: `walked` gives the mean st
 hardware counters are collected.
 
 usage: time_beam.py [samples] [block]   (prints one JSON line)"""
-import ctypes as C
 import json
-import os
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "iterative-closest-point-avmi_amd"))
-sys.path.insert(0, REPO)
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from timing import alternate, stats  # (first: it puts the repository on sys.path)
+import numpy as np
+import torch
 
-from icpmi import ScanHistory, _lib, gridmatch, synth  # noqa: E402
-from icpmi.batch import _ptr, _stream  # noqa: E402
+from icpmi import ScanHistory, _lib, gridmatch, synth
 
 SAMPLES = int(sys.argv[1]) if len(sys.argv) > 1 else 21
 BLOCK = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 POSES, ROWS, RESIDENT, TOLERANCE, HALF_WIDTH = 4096, 360, 512, 2, 8
 
-
-def sample(fn, block=BLOCK):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(block):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / block
-
-
-def stats(v):
-    q1, med, q3 = np.percentile(v, [25, 50, 75])
-    return {"median_ms": round(float(med), 4), "q1_ms": round(float(q1), 4), "q3_ms": round(float(q3), 4),
-            "min_ms": round(float(np.min(v)), 4), "max_ms": round(float(np.max(v)), 4), "samples": len(v)}
-
-
 assert torch.cuda.is_available(), "time_beam.py measures on the GPU: there is nothing to time without one"
-import bench  # noqa: E402
+import bench
 grid, org, hits, _ = bench.raycast_workload(synth, 32)
 grid.update_scans(org, hits)
 raw, k = grid.score_field()
 ny, nx = raw.shape
 threshold = int(np.rint(0.5 * 2.0 ** k))
 dev = raw.device
-L = _lib.lib()
 planes = grid.occupancy_planes(field=(raw, k))
 up = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)                                    # noqa: E731
 BEYOND = 1.5 * (HALF_WIDTH + 2) * grid.resolution
@@ -84,27 +61,17 @@ drive = np.array(drive)
 
 
 def entry_of(cs, pair_host, xyt, beyond=None, want_hist=False, want_rows=False):
-    """One entry over one set of pairs over the kept planes, arguments made once: the check (beyond None) or the beam model
-    -> (run, records, hist, rows)"""
-    B = len(pair_host)
-    pair_host = np.ascontiguousarray(pair_host, dtype=np.int32)
-    pair, t, rot = up(pair_host), up(xyt[:, :2]), up(np.stack([np.cos(xyt[:, 2]), np.sin(xyt[:, 2])], axis=1))
-    stride = int(np.diff(cs.off_host)[pair_host].max())
-    rec = torch.empty((B, _lib.GB_INTS), dtype=torch.int32, device=dev)
-    bins = torch.empty((B, 2 * HALF_WIDTH + 3), dtype=torch.int32, device=dev) if want_hist else None
-    rows = torch.empty((B, stride, _lib.GB_ROW_INTS), dtype=torch.int32, device=dev) if want_rows else None
-    head = (None, _ptr(planes[0].buf), ny, nx, threshold, grid.min_x, grid.min_y, grid.resolution, _ptr(cs.pts), _ptr(cs.off),
-            cs.off_host.ctypes.data_as(C.c_void_p), _ptr(cs.cnt), cs.n_clouds, _ptr(pair), pair_host.ctypes.data_as(C.c_void_p), B, _ptr(t), _ptr(rot))
+    """The library's prepared call over one set of pairs over the kept planes, its outputs made once: the check (beyond None)
+    or the beam model -> (run, records, hist, rows)"""
+    pairs = gridmatch.MapPairs(planes[0], threshold, grid.min_x, grid.min_y, grid.resolution, cs, pair_host, up(xyt[:, :2]),
+                               up(np.stack([np.cos(xyt[:, 2]), np.sin(xyt[:, 2])], axis=1)))
+    rec = torch.empty((pairs.B, _lib.GB_INTS), dtype=torch.int32, device=dev)
+    bins = torch.empty((pairs.B, 2 * HALF_WIDTH + 3), dtype=torch.int32, device=dev) if want_hist else None
+    rows = torch.empty((pairs.B, pairs.stride, _lib.GB_ROW_INTS), dtype=torch.int32, device=dev) if want_rows else None
     if beyond is None:
-        fn, args = L.icpmi_grid_check_batch, head + (TOLERANCE, _ptr(rec), _ptr(rows), stride, None, 0, _stream())
-    else:
-        fn, args = L.icpmi_grid_beam_batch, head + (float(beyond), HALF_WIDTH, _ptr(table), _ptr(rec), _ptr(bins), _ptr(rows), stride, None, 0, _stream())
-
-    def run():
-        rc = fn(*args)
-        assert rc == 0, rc
-    run.keep = (pair, t, rot, pair_host, rec, bins, rows)          # the arguments point into these, the outputs included: a caller
-    return run, rec, bins, rows                                    # that drops an output must not hand its memory to the next entry
+        out = (rec, rows) if want_rows else rec
+        return (lambda: pairs.check(TOLERANCE, want_rows, out)), rec, bins, rows
+    return (lambda: pairs.beam(table, HALF_WIDTH, beyond, want_hist, want_rows, (rec, bins, rows))), rec, bins, rows
 
 
 assert _lib.GB_INTS == _lib.GK_INTS and _lib.GB_ROW_INTS == _lib.GK_ROW_INTS
@@ -129,12 +96,7 @@ variants = {"k4k": k4k, "b4k": b4k, "b4h": b4h, "b4r": b4r, "b4z": b4z, "kh": kh
             "p4k": lambda: grid.beam_poses(scan, poses, half_width=HALF_WIDTH, planes=planes),
             "k4k_again": k4k}
 host_bound = {"p4k"}                                            # synchronises per call: a shorter block is enough
-for fn in variants.values():
-    sample(fn, 2)
-times = {name: [] for name in variants}
-for _ in range(SAMPLES):
-    for name, fn in variants.items():
-        times[name].append(sample(fn, 2 if name in host_bound else BLOCK))
+times = alternate({name: (fn, 2 if name in host_bound else BLOCK) for name, fn in variants.items()}, SAMPLES, 2)
 
 
 def looked_at(rows, counts, k_end):

@@ -28,14 +28,12 @@ import json
 import os
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "iterative-closest-point-avmi_amd"))
-sys.path.insert(0, REPO)
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from timing import alternate, stats  # (first: it puts the repository on sys.path)
+import numpy as np
+import torch
 
-from icpmi import _lib, gridmatch, synth  # noqa: E402
-from icpmi.batch import _ptr, _stream  # noqa: E402
+from icpmi import _lib, gridmatch, synth
+from icpmi.batch import _ptr, _stream
 
 SAMPLES = int(sys.argv[1]) if len(sys.argv) > 1 else 15
 BLOCK = int(sys.argv[2]) if len(sys.argv) > 2 else 20
@@ -44,29 +42,13 @@ HBM_TBS = float(os.environ.get("ICPMI_HBM_TBS", "8.0"))
 REACH, POSES, BEAMS, ROWS = 30.0, 4096, 360, 1430
 
 
-def sample(fn, block=BLOCK):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(block):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / block
-
-
-def stats(v):
-    q1, med, q3 = np.percentile(v, [25, 50, 75])
-    return {"median_ms": round(float(med), 4), "q1_ms": round(float(q1), 4), "q3_ms": round(float(q3), 4),
-            "min_ms": round(float(np.min(v)), 4), "max_ms": round(float(np.max(v)), 4), "samples": len(v)}
-
-
 def library(name):
     """A variant library of lib/ (every object but one is the shipped library's), with the shipped loader's signatures."""
     return _lib.bind(os.path.join(os.path.dirname(_lib.LIB_PATH), name))
 
 
 assert torch.cuda.is_available(), "time_cast.py measures on the GPU: there is nothing to time without one"
-import bench  # noqa: E402
+import bench
 grid, org, hits, _ = bench.raycast_workload(synth, 32)
 grid.update_scans(org, hits)
 raw, k = grid.score_field()
@@ -137,12 +119,7 @@ variants["f"] = grid.score_field
 variants["sp"] = lambda: grid.score_poses(scan, poses, field=(raw, k))
 variants["r4k_again"] = kept["4k"]
 host_bound = {"s1", "s4k", "s4f", "sp"}                          # these synchronise per call: a shorter block is enough
-for fn in variants.values():
-    sample(fn, 2)
-times = {name: [] for name in variants}
-for _ in range(SAMPLES):
-    for name, fn in variants.items():
-        times[name].append(sample(fn, 2 if name in host_bound else BLOCK))
+times = alternate({name: (fn, 2 if name in host_bound else BLOCK) for name, fn in variants.items()}, SAMPLES, 2)
 
 # what the walks looked at: the steps to the hit, or every step inside the grid (the origins are inside it)
 steps = {}

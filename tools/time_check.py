@@ -3,8 +3,8 @@
 config-4 grid (2 242 x 2 402 cells at 0.05 m, 32 scans applied), one process on one GPU, device events, the variants
 alternating:
 
-  (k4k)   4 096 poses x one 360-row scan over kept planes, the entry called with arguments prepared once; sampled twice
-          (k4k_again);
+  (k4k)   4 096 poses x one 360-row scan over kept planes, the library's prepared call (gridmatch.MapPairs.check, outputs
+          given): checked and uploaded once, then run; sampled twice (k4k_again);
   (k4f)   the same through the field: the call packs the planes first;
   (k4r)   (k4k) with the rows' records written as well;
   (kh)    512 scans of 2 048 rows resident in a ScanHistory, checked by id at the poses they were taken from, kept planes;
@@ -20,43 +20,22 @@ scan's own returns, the cast's at its reach, so the check looks at fewer steps p
 There is no earlier capability to compare a time against.
 
 usage: time_check.py [samples] [block]   (prints one JSON line)"""
-import ctypes as C
 import json
-import os
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "iterative-closest-point-avmi_amd"))
-sys.path.insert(0, REPO)
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from timing import alternate, stats  # (first: it puts the repository on sys.path)
+import numpy as np
+import torch
 
-from icpmi import ScanHistory, _lib, gridmatch, synth  # noqa: E402
-from icpmi.batch import _ptr, _stream  # noqa: E402
+from icpmi import ScanHistory, _lib, gridmatch, synth
+from icpmi.batch import _ptr, _stream
 
 SAMPLES = int(sys.argv[1]) if len(sys.argv) > 1 else 21
 BLOCK = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 REACH, POSES, ROWS, RESIDENT, TOLERANCE = 30.0, 4096, 360, 512, 2
 
-
-def sample(fn, block=BLOCK):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(block):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / block
-
-
-def stats(v):
-    q1, med, q3 = np.percentile(v, [25, 50, 75])
-    return {"median_ms": round(float(med), 4), "q1_ms": round(float(q1), 4), "q3_ms": round(float(q3), 4),
-            "min_ms": round(float(np.min(v)), 4), "max_ms": round(float(np.max(v)), 4), "samples": len(v)}
-
-
 assert torch.cuda.is_available(), "time_check.py measures on the GPU: there is nothing to time without one"
-import bench  # noqa: E402
+import bench
 grid, org, hits, _ = bench.raycast_workload(synth, 32)
 grid.update_scans(org, hits)
 raw, k = grid.score_field()
@@ -80,29 +59,20 @@ hist.add_many([synth.scan(p, 7000 + i) for i, p in enumerate(drive)])
 drive = np.array(drive)
 
 
-def check_of(cs, pair_host, xyt, field, kept, want_rows):
-    """The entry over one set of pairs, arguments made once -> (run, records, rows)"""
-    B = len(pair_host)
-    pair_host = np.ascontiguousarray(pair_host, dtype=np.int32)
-    pair, t, rot = up(pair_host), up(xyt[:, :2]), up(np.stack([np.cos(xyt[:, 2]), np.sin(xyt[:, 2])], axis=1))
-    stride = int(np.diff(cs.off_host)[pair_host].max())
-    rec = torch.empty((B, _lib.GK_INTS), dtype=torch.int32, device=dev)
-    rows = torch.empty((B, stride, _lib.GK_ROW_INTS), dtype=torch.int32, device=dev) if want_rows else None
-    args = (_ptr(field), _ptr(kept), ny, nx, threshold, grid.min_x, grid.min_y, grid.resolution, _ptr(cs.pts), _ptr(cs.off),
-            cs.off_host.ctypes.data_as(C.c_void_p), _ptr(cs.cnt), cs.n_clouds, _ptr(pair), pair_host.ctypes.data_as(C.c_void_p), B, _ptr(t), _ptr(rot),
-            TOLERANCE, _ptr(rec), _ptr(rows), stride, _ptr(ws), ws.numel(), _stream())
-
-    def run():
-        rc = L.icpmi_grid_check_batch(*args)
-        assert rc == 0, rc
-    run.keep = (pair, t, rot, pair_host)                           # the arguments point into these
-    return run, rec, rows
+def check_of(cs, pair_host, xyt, source, want_rows):
+    """The library's prepared call over one set of pairs, its outputs made once -> (run, records, rows)"""
+    pairs = gridmatch.MapPairs(source, threshold, grid.min_x, grid.min_y, grid.resolution, cs, pair_host, up(xyt[:, :2]),
+                               up(np.stack([np.cos(xyt[:, 2]), np.sin(xyt[:, 2])], axis=1)))
+    rec = torch.empty((pairs.B, _lib.GK_INTS), dtype=torch.int32, device=dev)
+    rows = torch.empty((pairs.B, pairs.stride, _lib.GK_ROW_INTS), dtype=torch.int32, device=dev) if want_rows else None
+    out = (rec, rows) if want_rows else rec
+    return (lambda: pairs.check(TOLERANCE, want_rows, out)), rec, rows
 
 
-k4k, rec4k, _ = check_of(one, np.zeros(POSES, dtype=np.int32), poses, None, planes[0].buf, False)
-k4f, rec4f, _ = check_of(one, np.zeros(POSES, dtype=np.int32), poses, raw, None, False)
-k4r, rec4r, rows4r = check_of(one, np.zeros(POSES, dtype=np.int32), poses, None, planes[0].buf, True)
-kh, rech, rowsh = check_of(hist.raw, np.arange(RESIDENT), drive, None, planes[0].buf, True)
+k4k, rec4k, _ = check_of(one, np.zeros(POSES, dtype=np.int32), poses, planes[0], False)
+k4f, rec4f, _ = check_of(one, np.zeros(POSES, dtype=np.int32), poses, raw, False)
+k4r, rec4r, rows4r = check_of(one, np.zeros(POSES, dtype=np.int32), poses, planes[0], True)
+kh, rech, rowsh = check_of(hist.raw, np.arange(RESIDENT), drive, planes[0], True)
 for fn in (k4k, k4f, k4r, kh):
     fn()
 want = rec4k.cpu().numpy()
@@ -123,17 +93,12 @@ def r4k():
     assert rc == 0, rc
 
 
+host_bound = {"sp", "c4k"}                                      # these synchronise per call: a shorter block is enough
 variants = {"k4k": k4k, "k4f": k4f, "k4r": k4r, "kh": kh, "r4k": r4k,
             "sp": lambda: grid.score_poses(scan, poses, field=(raw, k)),
             "c4k": lambda: grid.check_poses(scan, poses, tolerance=TOLERANCE, planes=planes),
             "k4k_again": k4k}
-host_bound = {"sp", "c4k"}                                      # these synchronise per call: a shorter block is enough
-for fn in variants.values():
-    sample(fn, 2)
-times = {name: [] for name in variants}
-for _ in range(SAMPLES):
-    for name, fn in variants.items():
-        times[name].append(sample(fn, 2 if name in host_bound else BLOCK))
+times = alternate({name: (fn, 2 if name in host_bound else BLOCK) for name, fn in variants.items()}, SAMPLES, 2)
 
 
 def looked_at(rows, counts):

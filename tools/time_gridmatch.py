@@ -17,42 +17,23 @@ difference has to exceed.  There is no earlier capability to compare a time agai
 
 usage: time_gridmatch.py [samples] [block]   (prints one JSON line)"""
 import json
-import os
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "iterative-closest-point-avmi_amd"))
-sys.path.insert(0, REPO)
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from timing import alternate, stats  # (first: it puts the repository on sys.path)
+import numpy as np
+import torch
 
-from icpmi import ScanHistory, synth  # noqa: E402
-from icpmi.batch import CloudSet  # noqa: E402
-from icpmi.gridmatch import GridMatchBatch, angle_grid  # noqa: E402
+from icpmi import ScanHistory, synth
+from icpmi.batch import CloudSet
+from icpmi.gridmatch import GridMatchBatch, angle_grid
 
 SAMPLES = int(sys.argv[1]) if len(sys.argv) > 1 else 15
 BLOCK = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 N_HIST, N_POSES, ROWS, W = 512, 4096, 1430, 6
 
 
-def sample(fn, block=BLOCK):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(block):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / block
-
-
-def stats(v):
-    q1, med, q3 = np.percentile(v, [25, 50, 75])
-    return {"median_ms": round(float(med), 4), "q1_ms": round(float(q1), 4), "q3_ms": round(float(q3), 4),
-            "min_ms": round(float(np.min(v)), 4), "max_ms": round(float(np.max(v)), 4), "samples": len(v)}
-
-
 assert torch.cuda.is_available(), "time_gridmatch.py measures on the GPU: there is nothing to time without one"
-import bench  # noqa: E402
+import bench
 grid, org, hits, _ = bench.raycast_workload(synth, 32)
 grid.update_scans(org, hits)
 field = grid.score_field()
@@ -80,8 +61,7 @@ hyp = np.array(true) + rng.uniform(-1.0, 1.0, size=(N_POSES, 3)) * np.array([0.5
 c = GridMatchBatch(grid, one, np.zeros(N_POSES, dtype=np.int32), hyp[:, :2], hyp[:, 2:3], 0, 0, field=field)
 
 variants = {"a1": a.run, "k": k.run, "m": m.run, "f": grid.score_field, "b": b.run, "c": c.run, "a2": a.run}
-for fn in variants.values():
-    sample(fn, 3)
+times = alternate({name: (fn, BLOCK) for name, fn in variants.items()}, SAMPLES, 3)
 # what the runs found, once: the single scan's error against its true pose, the batch's statuses
 _, t, score, info = a.unpack()
 minfo = m.unpack()[3]
@@ -91,10 +71,6 @@ found = {"err_m": [round(float(abs(t[0, i] - true[i])), 4) for i in (0, 1)], "er
          "refined_err_deg": round(float(np.rad2deg(abs(minfo["angle_refined"][0] - true[2]))), 3),
          "support": int(minfo["support"][0]), "edge_weight": round(float(minfo["edge_weight"][0]), 5),
          "history_status_ok": int((b.unpack()[3]["status"] == 0).sum()), "poses_status_ok": int((c.unpack()[3]["status"] == 0).sum())}
-times = {name: [] for name in variants}
-for _ in range(SAMPLES):
-    for name, fn in variants.items():
-        times[name].append(sample(fn))
 both = np.array(times["a1"] + times["a2"])
 out = {"grid": [grid.ny, grid.nx], "resolution": grid.resolution, "block": BLOCK, "found": found,
        "a_one_scan_25x13x13_field_rebuilt": stats(both), "a1": stats(times["a1"]), "a2": stats(times["a2"]),

@@ -18,42 +18,23 @@ difference has to exceed.  The survivor fraction is what the records report (slo
 
 usage: time_gridmatch_wide.py [samples] [block]   (prints one JSON line)"""
 import json
-import os
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "iterative-closest-point-avmi_amd"))
-sys.path.insert(0, REPO)
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from timing import alternate, stats  # (first: it puts the repository on sys.path)
+import numpy as np
+import torch
 
-from icpmi import synth  # noqa: E402
-from icpmi.batch import CloudSet  # noqa: E402
-from icpmi.gridmatch import GridMatchBatch, GridSearchBatch, angle_grid, bound_field  # noqa: E402
+from icpmi import synth
+from icpmi.batch import CloudSet
+from icpmi.gridmatch import GridMatchBatch, GridSearchBatch, angle_grid, bound_field
 
 SAMPLES = int(sys.argv[1]) if len(sys.argv) > 1 else 15
 BLOCK = int(sys.argv[2]) if len(sys.argv) > 2 else 10
 ROWS, W_NEAR, W_WIDE = 1430, 31, 100
 
 
-def sample(fn, block=BLOCK):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(block):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / block
-
-
-def stats(v):
-    q1, med, q3 = np.percentile(v, [25, 50, 75])
-    return {"median_ms": round(float(med), 4), "q1_ms": round(float(q1), 4), "q3_ms": round(float(q3), 4),
-            "min_ms": round(float(np.min(v)), 4), "max_ms": round(float(np.max(v)), 4), "samples": len(v)}
-
-
 assert torch.cuda.is_available(), "time_gridmatch_wide.py measures on the GPU: there is nothing to time without one"
-import bench  # noqa: E402
+import bench
 grid, org, hits, _ = bench.raycast_workload(synth, 32)
 grid.update_scans(org, hits)
 field = grid.score_field()
@@ -75,8 +56,7 @@ w = {D: GridSearchBatch(grid, one, [0], [far[:2]], circle, W_WIDE, ccentre, bloc
 
 variants = {"s8": s[8].run, "e": e.run, "s4": s[4].run, "s16": s[16].run, "r8": r8.run, "w8": w[8].run, "w4": w[4].run, "w16": w[16].run,
             "m": lambda: bound_field(field[0], 8, kept[8]), "s8b": s[8].run}
-for fn in variants.values():
-    sample(fn, 2)
+times = alternate({name: (fn, BLOCK) for name, fn in variants.items()}, SAMPLES, 2)
 
 
 def found(job, pred):
@@ -92,10 +72,6 @@ def found(job, pred):
 what = {"e": found(e, near), **{f"s{D}": found(s[D], near) for D in s}, **{f"w{D}": found(w[D], far) for D in w}}
 what["near_equal_to_exhaustive"] = bool(all(np.array_equal(s[D].records.cpu().numpy()[:, :8], e.records.cpu().numpy()) for D in s))
 what["wide_blocks_agree"] = bool(all(np.array_equal(w[D].records.cpu().numpy()[:, :8], w[8].records.cpu().numpy()[:, :8]) for D in w))
-times = {name: [] for name in variants}
-for _ in range(SAMPLES):
-    for name, fn in variants.items():
-        times[name].append(sample(fn))
 out = {"grid": [grid.ny, grid.nx], "resolution": grid.resolution, "block": BLOCK, "rows": ROWS,
        "near": {"W": W_NEAR, "angles": int(angles.shape[1]), "candidates": int(angles.shape[1]) * (2 * W_NEAR + 1) ** 2},
        "wide": {"W": W_WIDE, "angles": int(circle.shape[1]), "candidates": int(circle.shape[1]) * (2 * W_WIDE + 1) ** 2},

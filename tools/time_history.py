@@ -19,16 +19,14 @@ rotation_search, is the measurement described above, unchanged.
 
 usage: time_history.py [samples] [block] [--alignment {rotation_search,features,both}]   (prints one JSON line)"""
 import json
-import os
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "iterative-closest-point-avmi_amd"))
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from timing import alternate, sample, stats  # (first: it puts the repository on sys.path)
+import numpy as np
+import torch
 
-from icpmi import ScanHistory, synth  # noqa: E402
-from icpmi.prealign import RunIcpPairBatch  # noqa: E402
+from icpmi import ScanHistory, synth
+from icpmi.prealign import RunIcpPairBatch
 
 ICP = dict(error_threshold=1e-10, max_iterations=150, method="point_to_line")
 VOXEL, NORMAL_K, RS_VOXEL = 0.04, 12, 0.15
@@ -42,22 +40,6 @@ if "--alignment" in sys.argv:
 SAMPLES = int(sys.argv[1]) if len(sys.argv) > 1 else 15
 BLOCK = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 N, BIG = 512, 4096
-
-
-def sample(fn, block=BLOCK):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(block):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / block
-
-
-def stats(v):
-    q1, med, q3 = np.percentile(v, [25, 50, 75])
-    return {"median_ms": round(float(med), 4), "q1_ms": round(float(q1), 4), "q3_ms": round(float(q3), 4),
-            "min_ms": round(float(np.min(v)), 4), "max_ms": round(float(np.max(v)), 4), "samples": len(v)}
 
 
 def records(b):
@@ -100,12 +82,7 @@ def feature_alignment(method):
     equal = all(np.array_equal(x.cpu().numpy()[:N], y.cpu().numpy()[:N], equal_nan=True) for x, y in zip(parts(m), parts(batch)))
     rec = batch.features.records.cpu().numpy()[:N]
     variants = {"a1": batch.run, "b": m.run, "a2": batch.run}
-    for fn in variants.values():
-        sample(fn, 3)
-    times = {k: [] for k in variants}
-    for _ in range(SAMPLES):
-        for k, fn in variants.items():
-            times[k].append(sample(fn))
+    times = alternate({k: (fn, BLOCK) for k, fn in variants.items()}, SAMPLES, 3)
     t_add = time_add(hist, SAMPLES, BLOCK)
     a = np.array(times["a1"] + times["a2"])
     return {"alignment": method, "shape": f"{N} candidates of 2048-beam scans, one source", "block": BLOCK,
@@ -141,12 +118,7 @@ equal = {name: bool(np.array_equal(records(m)[0], want[0], equal_nan=True) and n
          for name, m in (("b", m_small), ("c", m_big))}
 
 variants = {"a1": batch.run, "b": m_small.run, "c": m_big.run, "a2": batch.run}
-for fn in variants.values():
-    sample(fn, 3)
-times = {k: [] for k in variants}
-for _ in range(SAMPLES):
-    for k, fn in variants.items():
-        times[k].append(sample(fn))
+times = alternate({k: (fn, BLOCK) for k, fn in variants.items()}, SAMPLES, 3)
 
 t_add = time_add(small, SAMPLES, BLOCK)
 

@@ -22,17 +22,15 @@ import json
 import os
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "iterative-closest-point-avmi_amd"))
-sys.path.insert(0, REPO)
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from timing import alternate, stats  # (first: it puts the repository on sys.path)
+import numpy as np
+import torch
 
-import ctypes as C  # noqa: E402
+import ctypes as C
 
-from icpmi import _lib, gridmatch, synth  # noqa: E402
-from icpmi.batch import CloudSet, _ptr, _stream  # noqa: E402
-from icpmi.gridmatch import GridMatchBatch, GridSearchBatch, angle_grid  # noqa: E402
+from icpmi import _lib, gridmatch, synth
+from icpmi.batch import CloudSet, _ptr, _stream
+from icpmi.gridmatch import GridMatchBatch, GridSearchBatch, angle_grid
 
 SAMPLES = int(sys.argv[1]) if len(sys.argv) > 1 else 15
 BLOCK = int(sys.argv[2]) if len(sys.argv) > 2 else 20
@@ -40,24 +38,8 @@ RADII, ROWS, W, W_WIDE = (3, 6, 20, 64), 1430, 6, 31
 HBM_TBS = float(os.environ.get("ICPMI_HBM_TBS", "8.0"))
 
 
-def sample(fn, block=BLOCK):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(block):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / block
-
-
-def stats(v):
-    q1, med, q3 = np.percentile(v, [25, 50, 75])
-    return {"median_ms": round(float(med), 4), "q1_ms": round(float(q1), 4), "q3_ms": round(float(q3), 4),
-            "min_ms": round(float(np.min(v)), 4), "max_ms": round(float(np.max(v)), 4), "samples": len(v)}
-
-
 assert torch.cuda.is_available(), "time_likelihood.py measures on the GPU: there is nothing to time without one"
-import bench  # noqa: E402
+import bench
 grid, org, hits, _ = bench.raycast_workload(synth, 32)
 grid.update_scans(org, hits)
 raw, k = grid.score_field()
@@ -105,8 +87,7 @@ variants["d6"] = build(6, d2_only=True)
 variants.update({n: j.run for n, j in match.items()})
 variants.update({n: j.run for n, j in search.items()})
 variants["l6_again"] = build(6)
-for fn in variants.values():
-    sample(fn, 3)
+times = alternate({name: (fn, BLOCK) for name, fn in variants.items()}, SAMPLES, 3)
 found = {}
 for n, job in list(match.items()) + list(search.items()):
     _, t, score, info = job.unpack()
@@ -115,10 +96,6 @@ for n, job in list(match.items()) + list(search.items()):
 d2 = gridmatch.distance_field(raw, threshold, 6).cpu().numpy()
 found["occupied_cells"] = int((d2 == 0).sum())
 found["cells_within_6"] = int((d2 <= 36).sum())
-times = {name: [] for name in variants}
-for _ in range(SAMPLES):
-    for name, fn in variants.items():
-        times[name].append(sample(fn))
 cells = grid.ny * grid.nx
 floor_ms = 4.0 * cells / (HBM_TBS * 1e12) * 1e3
 out = {"grid": [grid.ny, grid.nx], "resolution": grid.resolution, "block": BLOCK, "found": found, "hbm_tbs": HBM_TBS,

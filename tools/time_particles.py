@@ -6,7 +6,8 @@ one process on one GPU, device events, the variants alternating.  Per N:
 
   (predict, beam, weights, resample, estimate)
             each stage's C entry alone on the filter's own tensors, arguments prepared once; `beam` is the beam model's
-            launch on the resident particles — the yardstick the step is held against;
+            launch on the resident particles as the filter makes it (ParticleFilter.scan_pairs once, .beam per run) — the
+            yardstick the step is held against;
   (step)    the five stages enqueued back to back, resampling every time, nothing read back: what the device does per scan;
   (filter)  ParticleFilter.predict / weigh / maybe_resample / estimate with their read-backs (the four sums, the eight
             moments) and the scan's upload: what a caller waits for per scan;
@@ -18,44 +19,23 @@ SAMPLES samples per variant after a warm-up of each.  `beam_again` samples the y
 median(beam_again)| is the run-to-run spread a difference has to exceed.  No hardware counters are collected.
 
 usage: time_particles.py [samples] [block]   (prints one JSON line)"""
-import ctypes as C
 import json
-import os
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "iterative-closest-point-avmi_amd"))
-sys.path.insert(0, REPO)
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from timing import alternate, stats  # (first: it puts the repository on sys.path)
+import numpy as np
+import torch
 
-from icpmi import _lib, gridmatch, synth  # noqa: E402
-from icpmi.batch import _ptr, _stream  # noqa: E402
+from icpmi import _lib, gridmatch, synth
+from icpmi.batch import _ptr, _stream
 
 SAMPLES = int(sys.argv[1]) if len(sys.argv) > 1 else 21
 BLOCK = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 SIZES, ROWS, HALF_WIDTH, TEMPERATURE = (4096, 512, 65536), 360, 8, 8.0
 CONTROL, MOTION = (0.02, 0.0, 0.005), (0.01, 0.01, 0.002)
 
-
-def sample(fn, block):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(block):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / block
-
-
-def stats(v):
-    q1, med, q3 = np.percentile(v, [25, 50, 75])
-    return {"median_ms": round(float(med), 4), "q1_ms": round(float(q1), 4), "q3_ms": round(float(q3), 4),
-            "min_ms": round(float(np.min(v)), 4), "max_ms": round(float(np.max(v)), 4), "samples": len(v)}
-
-
 assert torch.cuda.is_available(), "time_particles.py measures on the GPU: there is nothing to time without one"
-import bench  # noqa: E402
+import bench
 grid, org, hits, _ = bench.raycast_workload(synth, 32)
 grid.update_scans(org, hits)
 planes = grid.occupancy_planes()
@@ -70,8 +50,8 @@ def variants_of(n):
     """-> {name: (run, runs per sample)} for n particles, started as a cloud about the scan's pose"""
     pf = grid.particle_filter(n, seed=n, temperature=TEMPERATURE, half_width=HALF_WIDTH, planes=planes)
     pf.init_gaussian(start, (0.2, 0.2, 0.05))
-    pf.weigh(scan)                                                 # makes the pair list and leaves real weights
-    pair_host, pair = pf._pair[0]
+    pf.weigh(scan)                                                 # leaves real weights
+    pairs = pf.scan_pairs(one, 0)                                  # the prepared call weigh() makes, on the present generation
     p, st = pf.planes, _stream()
     spare = pf._spare
 
@@ -83,10 +63,7 @@ def variants_of(n):
 
     state = (_ptr(pf.pair_t), _ptr(pf.theta), _ptr(pf.cos_sin))
     predict = call(L.icpmi_pf_predict, n, *state, *CONTROL, *MOTION, pf.seed, 1, st)
-    beam = call(L.icpmi_grid_beam_batch, None, _ptr(p.buf), p.ny, p.nx, p.threshold, float(grid.min_x), float(grid.min_y), float(grid.resolution),
-                _ptr(one.pts), _ptr(one.off), one.off_host.ctypes.data_as(C.c_void_p), _ptr(one.cnt), one.n_clouds, _ptr(pair),
-                pair_host.ctypes.data_as(C.c_void_p), n, state[0], state[2], pf.beyond, HALF_WIDTH, _ptr(pf._beam_table), _ptr(pf.records), None, None,
-                0, None, 0, st)
+    beam = lambda: pf.beam(pairs)                                  # noqa: E731
     weights = call(L.icpmi_pf_weights, n, _ptr(pf.records), _ptr(pf._weight_table), len(pf.weight_table_host), pf.weight_shift, _ptr(pf.w),
                    _ptr(pf.sums), st)
     # (the resampled generation goes to the spare buffers and is not swapped in: every run reads the same particles)
@@ -146,12 +123,7 @@ out = {"grid": [grid.ny, grid.nx], "resolution": grid.resolution, "rows": ROWS, 
        "counters": "none collected"}
 for n in SIZES:
     variants, keep = variants_of(n)
-    for fn, _ in variants.values():
-        sample(fn, 2)
-    times = {name: [] for name in variants}
-    for _ in range(SAMPLES):
-        for name, (fn, block) in variants.items():
-            times[name].append(sample(fn, block))
+    times = alternate(variants, SAMPLES, 2)
     med = lambda name: float(np.median(times[name]))                                              # noqa: E731
     res = {name: stats(times[name]) for name in variants}
     res["stages_sum_ms"] = round(sum(med(s) for s in ("predict", "beam", "weights", "resample", "estimate")), 4)

@@ -15,16 +15,14 @@ has to exceed.  Before any timing the two grids are compared bit for bit.
 
 usage: time_rebuild.py [samples] [scans]   (prints one JSON line)"""
 import json
-import os
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "iterative-closest-point-avmi_amd"))
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from timing import alternate, sample, stats  # (first: it puts the repository on sys.path)
+import numpy as np
+import torch
 
-from icpmi import ScanHistory, synth  # noqa: E402
-from utilities.mapping import OccupancyGrid2D  # noqa: E402
+from icpmi import ScanHistory, synth
+from utilities.mapping import OccupancyGrid2D
 
 SAMPLES = int(sys.argv[1]) if len(sys.argv) > 1 else 15
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 512
@@ -34,22 +32,6 @@ BLOCK = 20
 def pose_matrix(x, y, th):
     c, s = np.cos(th), np.sin(th)
     return np.array([[c, -s, x], [s, c, y], [0.0, 0.0, 1.0]])
-
-
-def sample(fn, block=1):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(block):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / block
-
-
-def stats(v):
-    q1, med, q3 = np.percentile(v, [25, 50, 75])
-    return {"median_ms": round(float(med), 4), "q1_ms": round(float(q1), 4), "q3_ms": round(float(q3), 4),
-            "min_ms": round(float(np.min(v)), 4), "max_ms": round(float(np.max(v)), 4), "samples": len(v)}
 
 
 assert torch.cuda.is_available(), "time_rebuild.py measures on the GPU: there is nothing to time without one"
@@ -95,12 +77,7 @@ equal = bool(torch.equal(grid_a.device_log_odds, grid_b.device_log_odds))
 rows_equal = bool(np.array_equal(rows.cpu().numpy(), np.concatenate([pts @ T[:2, :2].T + T[:2, 2] for pts, T in history])))
 
 variants = {"a1": host_path, "b": resident_path, "a2": host_path}
-for fn in variants.values():
-    sample(fn)
-times = {k: [] for k in variants}
-for _ in range(SAMPLES):
-    for k, fn in variants.items():
-        times[k].append(sample(fn))
+times = alternate({k: (fn, 1) for k, fn in variants.items()}, SAMPLES, 1)
 sample(transform_alone, 3)
 t_rows = [sample(transform_alone, BLOCK) for _ in range(SAMPLES)]
 
