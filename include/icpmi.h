@@ -131,11 +131,29 @@ int icpmi_voxel_downsample_batch(const double* pts, const int32_t* off_dev, cons
  * Pair b matches every valid row of cloud pair_src[b] against cloud
  * pair_tgt[b] (exhaustive, LDS-tiled, float64 direct differences, lowest index
  * on ties).  out_idx/out_dist are [n_pairs][out_stride]; dist is the Euclidean
- * distance (sqrt), index is relative to the target cloud. */
+ * distance (sqrt), index is relative to the target cloud.
+ * max_src_n bounds the rows written per pair: rows [0, min(N, max_src_n)) of pair b's out rows are written and nothing
+ * else is, so a source cloud with more valid rows than max_src_n is truncated to it (out_stride >= max_src_n keeps
+ * every write inside pair b's rows).  A pair with an empty target gets index -1 and distance +inf. */
 int icpmi_nn_batch(const double* pts, const int32_t* off_dev, const int32_t* cnt_dev,
                    const int32_t* pair_src, const int32_t* pair_tgt, int32_t n_pairs,
                    int32_t max_src_n, int32_t dim,
                    int32_t* out_idx, double* out_dist, int32_t out_stride, void* stream);
+
+/* What icpmi_nn_batch starts for these three arguments — no HIP call, no launch, no device pointer; the entry takes
+ * its launch shape from this function.  The refusals are that entry's for them (ICPMI_ERR_ARG: a null out, n_pairs or
+ * max_src_n < 0, dim outside {2, 3}).  A call that launches nothing (n_pairs == 0 or max_src_n == 0): ICPMI_OK and a
+ * plan of zeros.
+ *   rows_per_lane  S: source rows a lane holds in registers (1, 2 or 4, by the number of workgroups the call makes)
+ *   threads        lanes of a workgroup;  rows_per_wg = threads * S consecutive source rows of one pair
+ *   tile_points    target rows staged in LDS at a time;  chunk: target rows per running minimum (tile_points is a
+ *                  multiple of it)
+ *   grid_x         workgroups per pair, ceil(max_src_n / rows_per_wg);  launches: slices of at most 65 535 pairs
+ * A workgroup whose rows reach past its cloud's count runs the body for min(S, ceil(rows left / threads)) rows. */
+typedef struct icpmi_nn_plan {
+    int32_t rows_per_lane, threads, rows_per_wg, tile_points, chunk, grid_x, launches;
+} icpmi_nn_plan;
+int icpmi_nn_batch_plan(int32_t n_pairs, int32_t max_src_n, int32_t dim, icpmi_nn_plan* out);
 
 /* ---- estimate_normals_2d, icp.py:51-76 ------------------------------------
  * k+1 nearest neighbours (self included, k clamped to n-1), 2x2 covariance,
@@ -292,7 +310,8 @@ int icpmi_prepare_targets_ex(const double* pts, const int32_t* off_dev, const in
  * answers bit for bit, icp.py:179): binary search + outward sweep on the sorted
  * copy instead of the exhaustive scan.  Target clouds of the pairs must have
  * been prepared (<= 4096 rows).  out_second_sq (optional) receives the squared
- * distance of the second nearest target point. */
+ * distance of the second nearest target point.  As there, max_src_n bounds the
+ * rows written per pair: a longer source cloud is truncated to it. */
 int icpmi_nn_prepared_batch(const double* pts, const int32_t* off_dev, const int32_t* cnt_dev,
                             const void* prepared, const int32_t* pair_src, const int32_t* pair_tgt,
                             int32_t n_pairs, int32_t max_src_n, int32_t max_tgt_n, int32_t total_rows,

@@ -50,11 +50,11 @@ template <int DIM, int S>
 __global__ __launch_bounds__(NN_THREADS) void nn_batch_kernel(
     const double* __restrict__ pts, const int32_t* __restrict__ off, const int32_t* __restrict__ cnt,
     const int32_t* __restrict__ pair_src, const int32_t* __restrict__ pair_tgt,
-    int32_t* __restrict__ out_idx, double* __restrict__ out_dist, int out_stride) {
+    int32_t* __restrict__ out_idx, double* __restrict__ out_dist, int out_stride, int max_src_n) {
     __shared__ __attribute__((aligned(16))) double tile[NN_TILE_DOUBLES];
     const int b = blockIdx.y;
     const int sc = pair_src[b], tc = pair_tgt[b];
-    const int N = cnt ? cnt[sc] : off[sc + 1] - off[sc];
+    const int N = min(cnt ? cnt[sc] : off[sc + 1] - off[sc], max_src_n);   // a longer cloud is truncated: the out rows hold max_src_n
     const int M = cnt ? cnt[tc] : off[tc + 1] - off[tc];
     const int first = blockIdx.x * (NN_THREADS * S);
     if (first >= N) return;                                    // uniform per workgroup
@@ -69,16 +69,38 @@ __global__ __launch_bounds__(NN_THREADS) void nn_batch_kernel(
     else nn_rows<DIM, 1>(src, tgt, N, M, first, tile, oi, od);
 }
 
+constexpr int NN_SLICE = 65535;         // the pair index is the grid's y: at most 65 535 per launch, so a larger batch goes down in slices
+
+// The launch shape of icpmi_nn_batch, for a call that launches (n_pairs, max_src_n > 0; dim 2 or 3).
+// Rows per thread: enough workgroups to cover the chip first, then register
+// blocking (one LDS broadcast read feeds S evaluations per lane).
+// The loop is FP64-VALU bound at every S (one broadcast ds_read_b128 per S evaluations is far
+// from the LDS limit already at S = 2), so tiles stay small: more, equal-sized workgroups
+// balance better over 256 CUs than fewer large ones with a ragged last tile.  S = 4 only when
+// even that leaves tens of workgroups per CU.
+static icpmi_nn_plan plan_nn(int n_pairs, int max_src_n, int dim) {
+    auto tiles = [&](int s) { return (max_src_n + NN_THREADS * s - 1) / (NN_THREADS * s); };
+    const long wg4 = (long)n_pairs * tiles(4), wg2 = (long)n_pairs * tiles(2);
+    icpmi_nn_plan p{};
+    p.rows_per_lane = wg4 >= 16384 ? 4 : (wg2 >= 512 ? 2 : 1);
+    p.threads = NN_THREADS;
+    p.rows_per_wg = NN_THREADS * p.rows_per_lane;
+    p.tile_points = dim == 2 ? nn_tile_points<2>() : nn_tile_points<3>();
+    p.chunk = NN_CHUNK;
+    p.grid_x = tiles(p.rows_per_lane);
+    p.launches = (n_pairs + NN_SLICE - 1) / NN_SLICE;
+    return p;
+}
+
 template <int DIM, int S>
-static int launch_nn(const double* pts, const int32_t* off, const int32_t* cnt, const int32_t* ps,
+static int launch_nn(const icpmi_nn_plan& plan, const double* pts, const int32_t* off, const int32_t* cnt, const int32_t* ps,
                      const int32_t* pt, int n_pairs, int max_src_n, int32_t* out_idx, double* out_dist,
                      int out_stride, hipStream_t st) {
-    // the pair index is the grid's y: at most 65 535 per launch, so a larger batch goes down in slices
-    for (int p0 = 0; p0 < n_pairs; p0 += 65535) {
-        const int np = n_pairs - p0 < 65535 ? n_pairs - p0 : 65535;
-        dim3 grid((max_src_n + NN_THREADS * S - 1) / (NN_THREADS * S), np);
+    for (int p0 = 0; p0 < n_pairs; p0 += NN_SLICE) {
+        const int np = n_pairs - p0 < NN_SLICE ? n_pairs - p0 : NN_SLICE;
+        dim3 grid(plan.grid_x, np);
         nn_batch_kernel<DIM, S><<<grid, NN_THREADS, 0, st>>>(pts, off, cnt, ps + p0, pt + p0, out_idx + (size_t)p0 * out_stride,
-                                                             out_dist + (size_t)p0 * out_stride, out_stride);
+                                                             out_dist + (size_t)p0 * out_stride, out_stride, max_src_n);
         ICPMI_LAUNCH_CHECK();
     }
     return ICPMI_OK;
@@ -86,26 +108,27 @@ static int launch_nn(const double* pts, const int32_t* off, const int32_t* cnt, 
 
 }  // namespace icpmi
 
+// What icpmi_nn_batch starts for these arguments: its refusals for them, then plan_nn.  No HIP call.
+extern "C" int icpmi_nn_batch_plan(int32_t n_pairs, int32_t max_src_n, int32_t dim, icpmi_nn_plan* out) {
+    using namespace icpmi;
+    if (!out || n_pairs < 0 || max_src_n < 0 || (dim != 2 && dim != 3)) return ICPMI_ERR_ARG;
+    *out = n_pairs == 0 || max_src_n == 0 ? icpmi_nn_plan{} : plan_nn(n_pairs, max_src_n, dim);
+    return ICPMI_OK;
+}
+
 extern "C" int icpmi_nn_batch(const double* pts, const int32_t* off_dev, const int32_t* cnt_dev,
                               const int32_t* pair_src, const int32_t* pair_tgt, int32_t n_pairs,
                               int32_t max_src_n, int32_t dim, int32_t* out_idx, double* out_dist,
                               int32_t out_stride, void* stream) {
     using namespace icpmi;
     if (!pts || !off_dev || !pair_src || !pair_tgt || !out_idx || !out_dist) return ICPMI_ERR_ARG;
-    if (n_pairs < 0 || max_src_n < 0 || out_stride < max_src_n || (dim != 2 && dim != 3)) return ICPMI_ERR_ARG;
-    if (n_pairs == 0 || max_src_n == 0) return ICPMI_OK;
+    icpmi_nn_plan plan;
+    if (icpmi_nn_batch_plan(n_pairs, max_src_n, dim, &plan) != ICPMI_OK || out_stride < max_src_n) return ICPMI_ERR_ARG;
+    if (plan.launches == 0) return ICPMI_OK;
     hipStream_t st = (hipStream_t)stream;
-    // Rows per thread: enough workgroups to cover the chip first, then register
-    // blocking (one LDS broadcast read feeds S evaluations per lane).
-    // The loop is FP64-VALU bound at every S (one broadcast ds_read_b128 per S evaluations is far
-    // from the LDS limit already at S = 2), so tiles stay small: more, equal-sized workgroups
-    // balance better over 256 CUs than fewer large ones with a ragged last tile.  S = 4 only when
-    // even that leaves tens of workgroups per CU.
-    const long wg4 = (long)n_pairs * ((max_src_n + NN_THREADS * 4 - 1) / (NN_THREADS * 4));
-    const long wg2 = (long)n_pairs * ((max_src_n + NN_THREADS * 2 - 1) / (NN_THREADS * 2));
-    const int S = wg4 >= 16384 ? 4 : (wg2 >= 512 ? 2 : 1);
+    const int S = plan.rows_per_lane;
 #define ICPMI_NN_GO(D, SS) \
-    return launch_nn<D, SS>(pts, off_dev, cnt_dev, pair_src, pair_tgt, n_pairs, max_src_n, out_idx, out_dist, out_stride, st)
+    return launch_nn<D, SS>(plan, pts, off_dev, cnt_dev, pair_src, pair_tgt, n_pairs, max_src_n, out_idx, out_dist, out_stride, st)
     if (dim == 2) {
         if (S == 4) ICPMI_NN_GO(2, 4);
         if (S == 2) ICPMI_NN_GO(2, 2);

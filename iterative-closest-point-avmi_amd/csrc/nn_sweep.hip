@@ -20,13 +20,13 @@ __global__ __launch_bounds__(NNS_THREADS) void nn_sweep_kernel(
     const int32_t* __restrict__ pair_src, const int32_t* __restrict__ pair_tgt,
     const double2* __restrict__ g_sxy, const int32_t* __restrict__ g_sorig, const int32_t* __restrict__ g_dir,
     int32_t* __restrict__ out_idx, double* __restrict__ out_dist, double* __restrict__ out_second2,
-    int out_stride, int lds_points) {
+    int out_stride, int lds_points, int max_src_n) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     double2* sxy = reinterpret_cast<double2*>(dyn);
     int32_t* sorig = reinterpret_cast<int32_t*>(dyn + (size_t)lds_points * 16);
     const int b = blockIdx.y;
     const int sc = pair_src[b], tc = pair_tgt[b];
-    const int N = cnt ? cnt[sc] : off[sc + 1] - off[sc];
+    const int N = min(cnt ? cnt[sc] : off[sc + 1] - off[sc], max_src_n);   // a longer cloud is truncated: the out rows hold max_src_n
     const int M = cnt ? cnt[tc] : off[tc + 1] - off[tc];
     const int first = blockIdx.x * NNS_THREADS;
     if (first >= N) return;                                    // uniform per workgroup
@@ -75,7 +75,8 @@ extern "C" int icpmi_nn_prepared_batch(const double* pts, const int32_t* off_dev
         dim3 grid((max_src_n + NNS_THREADS - 1) / NNS_THREADS, np);
         nn_sweep_kernel<<<grid, NNS_THREADS, lds, (hipStream_t)stream>>>(
             pts, off_dev, cnt_dev, pair_src + p0, pair_tgt + p0, v.sxy, v.sorig, v.dir, out_idx + (size_t)p0 * out_stride,
-            out_dist + (size_t)p0 * out_stride, out_second_sq ? out_second_sq + (size_t)p0 * out_stride : nullptr, out_stride, cap);
+            out_dist + (size_t)p0 * out_stride, out_second_sq ? out_second_sq + (size_t)p0 * out_stride : nullptr, out_stride, cap,
+            max_src_n);
         ICPMI_LAUNCH_CHECK();
     }
     return ICPMI_OK;

@@ -107,7 +107,7 @@ def _read_header():
 
 
 # Last, so that every name this module owns is there to be refused to a constant of the header.  Published: OK, ERR_*,
-# ST_*, RES_*, GM_*, ...; IcpParams, History, FeatureStore, GridPlan; _SIGS, {name: (restype, argtypes)}, and EXPORTS.
+# ST_*, RES_*, GM_*, ...; IcpParams, NnPlan, History, FeatureStore, GridPlan; _SIGS, {name: (restype, argtypes)}, and EXPORTS.
 OWN_NAMES = frozenset(globals()) | {"OWN_NAMES", "EXPORTS", "_SIGS"}
 _constants, _structs, _SIGS = _header.read(_read_header(), reserved=OWN_NAMES)
 EXPORTS = tuple(_SIGS)

@@ -83,7 +83,7 @@ def test_real_header_is_fully_accounted_for(tmp_path, monkeypatch):
     assert spelled(_lib._SIGS) == spelled(h.functions)                     # (a second reading makes its own struct classes)
     assert h.constants and all(getattr(_lib, n) == v for n, v in h.constants.items())
     assert (_lib.OK, _lib.ERR_ARG, _lib.ERR_WORKSPACE, _lib.ERR_HIP, _lib.ERR_UNSUPPORTED) == (0, -1, -2, -3, -4)
-    assert [c.__name__ for c in h.structs.values()] == ["IcpParams", "History", "FeatureStore", "GridPlan"]
+    assert [c.__name__ for c in h.structs.values()] == ["IcpParams", "NnPlan", "History", "FeatureStore", "GridPlan"]
     assert all(issubclass(getattr(_lib, c.__name__), C.Structure) and getattr(_lib, c.__name__)._fields_ == c._fields_
                for c in h.structs.values())
     # a missing header is an error with the path, as a missing library is: there is no table to fall back on
@@ -98,7 +98,7 @@ def test_struct_layout_against_the_c_compiler(tmp_path):
     table = _header.read(open(HEADER).read()).structs                          # C name -> class; checked: the classes _lib uses
     c_name = {getattr(_lib, cls.__name__): name for name, cls in table.items()}
     structs = list(c_name)
-    assert len(structs) == 4
+    assert len(structs) == 5
     c_field = lambda f: f[:-1] if f.endswith("_") and keyword.iskeyword(f[:-1]) else f          # noqa: E731
     lines = ["#include <stdio.h>", '#include "icpmi.h"', "int main(void) {"]
     for cls in structs:
