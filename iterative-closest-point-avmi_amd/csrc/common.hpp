@@ -100,11 +100,22 @@ __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
 // ── cross-lane moves on the VALU (DPP), no LDS crossbar ─────────────────────
 // dpp_ctrl: quad_perm [1,0,3,2] = 0xB1, quad_perm [2,3,0,1] = 0x4E,
 // row_half_mirror = 0x141, row_mirror = 0x140 (rows are 16 lanes).
+// These four only permute lanes inside a row, so with full row and bank masks every lane reads a lane that exists: the
+// destination needs no old value.  mov_dpp with bound_ctrl on says so (an undefined old value); update_dpp(0, ...) made
+// the compiler write a zero into the destination in front of every move.  (An INACTIVE source lane reads as 0, as it
+// did: the reductions below are for whole waves.)
+template <int CTRL>
+__device__ __forceinline__ int dpp_b32(int v) {
+    static_assert(CTRL == 0xB1 || CTRL == 0x4E || CTRL == 0x141 || CTRL == 0x140, "a permutation inside the row");
+    return __builtin_amdgcn_mov_dpp(v, CTRL, 0xf, 0xf, true);
+}
+template <int CTRL>
+__device__ __forceinline__ float dpp_f32(float v) { return __int_as_float(dpp_b32<CTRL>(__float_as_int(v))); }
 template <int CTRL>
 __device__ __forceinline__ double dpp_f64(double v) {
     const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffll), CTRL, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, false);
+    const int lo = dpp_b32<CTRL>((int)(b & 0xffffffffll));
+    const int hi = dpp_b32<CTRL>((int)(b >> 32));
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 __device__ __forceinline__ double readlane_f64(double v, int lane) {
@@ -139,14 +150,65 @@ __device__ __forceinline__ long long wave_sum(long long v) {     // the two halv
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, ICPMI_WAVE);
     return v;
 }
+// Wave-wide min / max, identical in every lane: the same four DPP steps inside the rows, then two steps across the rows
+// on the VALU (no LDS crossbar, no scalar registers).  v_permlane16_swap of a register with a copy of itself leaves rows
+// (0, 0, 2, 2) in one and (1, 1, 3, 3) in the other, v_permlane32_swap the lower half twice and the upper half twice.
+// min and max are exact, so the tree does not matter to the result.
+template <bool ROWS16>
+__device__ __forceinline__ void swap_self(unsigned v, unsigned& x, unsigned& y) {
+    if constexpr (ROWS16) { const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false); x = r[0]; y = r[1]; }
+    else { const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false); x = r[0]; y = r[1]; }
+}
+template <bool ROWS16>
+__device__ __forceinline__ void swap_self(double v, double& x, double& y) {
+    const long long b = __double_as_longlong(v);
+    unsigned xl, yl, xh, yh;
+    swap_self<ROWS16>((unsigned)b, xl, yl);
+    swap_self<ROWS16>((unsigned)(b >> 32), xh, yh);
+    x = __longlong_as_double(((long long)xh << 32) | xl);
+    y = __longlong_as_double(((long long)yh << 32) | yl);
+}
 __device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, ICPMI_WAVE));
-    return v;
+    v = fmin(v, dpp_f64<0xB1>(v));
+    v = fmin(v, dpp_f64<0x4E>(v));
+    v = fmin(v, dpp_f64<0x141>(v));
+    v = fmin(v, dpp_f64<0x140>(v));
+    double x, y;
+    swap_self<true>(v, x, y);
+    swap_self<false>(fmin(x, y), x, y);
+    return fmin(x, y);
 }
 __device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, ICPMI_WAVE));
+    v = fmax(v, dpp_f64<0xB1>(v));
+    v = fmax(v, dpp_f64<0x4E>(v));
+    v = fmax(v, dpp_f64<0x141>(v));
+    v = fmax(v, dpp_f64<0x140>(v));
+    double x, y;
+    swap_self<true>(v, x, y);
+    swap_self<false>(fmax(x, y), x, y);
+    return fmax(x, y);
+}
+__device__ __forceinline__ float wave_max(float v) {
+    v = fmaxf(v, dpp_f32<0xB1>(v));
+    v = fmaxf(v, dpp_f32<0x4E>(v));
+    v = fmaxf(v, dpp_f32<0x141>(v));
+    v = fmaxf(v, dpp_f32<0x140>(v));
+    unsigned x, y;
+    swap_self<true>((unsigned)__float_as_int(v), x, y);
+    swap_self<false>((unsigned)__float_as_int(fmaxf(__int_as_float((int)x), __int_as_float((int)y))), x, y);
+    return fmaxf(__int_as_float((int)x), __int_as_float((int)y));
+}
+
+// Inclusive prefix sum over the wave (integer adds: any tree is exact).  Four shifts inside the rows (row_shr:1, 2, 4, 8;
+// a lane the shift leaves without a source adds 0), then the running totals across the rows: lane 15 of rows 0 and 2 into
+// rows 1 and 3 (row_bcast:15, row mask 0xa), lane 31 into rows 2 and 3 (row_bcast:31, row mask 0xc).  Whole waves only.
+__device__ __forceinline__ int wave_incscan(int v) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
     return v;
 }
 

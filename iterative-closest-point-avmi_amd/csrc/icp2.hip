@@ -127,7 +127,9 @@ __device__ __forceinline__ void wave_totals(double* scratch, const double (&v)[N
         const double q = row_sum(swap_add(h[2 * k], h[2 * k + 1], true));
         const int row = l >> 4;
         const int idx = 4 * k + ((row & 1) << 1) + (row >> 1);
-        if ((l & 15) == 0 && idx < NV) scratch[idx * RED_MAXW + w] = q;
+        // every lane of a row holds the row's total; the LAST lane stores it: with the store in lane 0 the second stage
+        // (icp2_resume_kernel<768, 2, true, true>, at its 80-register cap) spills four registers in the lead wave's solve
+        if ((l & 15) == 15 && idx < NV) scratch[idx * RED_MAXW + w] = q;
     }
 }
 
@@ -419,7 +421,8 @@ __device__ __forceinline__ void icp2_pair(const Icp2Args& a, const int b) {
             }
             if (tid == 0) { lds_sq[-1] = make_float4(0.f, 0.f, 0.f, 0.f); lds_sq[M] = make_float4(0.f, 0.f, 0.f, 0.f); }
             __syncthreads();                                     // rt_bits = 0 is visible, the images are complete
-            atomicMax(&rt_bits, __float_as_int(rmax));           // non-negative floats order like their bits
+            rmax = wave_max(rmax);                               // one atomic per wave, not one per thread, on the one word
+            if (lane_id() == 0) atomicMax(&rt_bits, __float_as_int(rmax));      // non-negative floats order like their bits
         }
         // moving source rows in registers: row n = s*RT + tid
         double px[ICP2_SMAX], py[ICP2_SMAX];

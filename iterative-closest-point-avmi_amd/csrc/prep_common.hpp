@@ -418,12 +418,7 @@ __device__ __forceinline__ PrepGrid prep_grid_build(const double2* sxy, int M, c
         const int lo = min(nc, (int)threadIdx.x * per), hi = min(nc, lo + per);
         uint32_t sum = 0;
         for (int c = lo; c < hi; ++c) sum += cell_end[c];
-        uint32_t inc = sum;
-#pragma unroll
-        for (int o = 1; o < ICPMI_WAVE; o <<= 1) {
-            const uint32_t t = (uint32_t)__shfl_up((int)inc, o, ICPMI_WAVE);
-            if (lane_id() >= o) inc += t;
-        }
+        const uint32_t inc = (uint32_t)wave_incscan((int)sum);
         if (lane_id() == ICPMI_WAVE - 1) wave_tot[wave_id()] = (int)inc;
         __syncthreads();
         uint32_t run = inc - sum;

@@ -71,7 +71,8 @@ __device__ __forceinline__ void bitonic_sort_packed(T* v, int npad) {
 // elements (the packed values are distinct: the row is part of them).
 template <int CTRL>
 __device__ __forceinline__ uint32_t sort_dpp(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
+    // a permutation inside the row (quad_perm, row mirrors, row_ror): every lane has a source, so no old value (common.hpp, dpp_b32)
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xf, 0xf, true);
 }
 template <int PATTERN>
 __device__ __forceinline__ uint32_t sort_swz(uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, PATTERN); }

@@ -104,12 +104,7 @@ __device__ __forceinline__ double vox_packed_range(const double (&ext)[3], int n
 // the grand total.  scratch: VOX_MAXW ints of LDS.
 __device__ __forceinline__ int block_exscan(int v, int* scratch, int& total) {
     const int l = lane_id(), w = wave_id(), nw = blockDim.x / ICPMI_WAVE;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < ICPMI_WAVE; o <<= 1) {
-        const int t = __shfl_up(inc, o, ICPMI_WAVE);
-        if (l >= o) inc += t;
-    }
+    const int inc = wave_incscan(v);
     __syncthreads();
     if (l == ICPMI_WAVE - 1) scratch[w] = inc;
     __syncthreads();
