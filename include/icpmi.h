@@ -16,7 +16,12 @@
  *    ICPMI_* option switches (read from the environment once, at first use) and
  *    up to three side streams per device that launchers use to overlap the
  *    independent launches of one call (made on first use, destroyed by
- *    icpmi_shutdown).  Calls may come from several host threads.
+ *    icpmi_shutdown).  Calls may come from several host threads.  Every caller
+ *    stream of a device shares these side streams and their events: a launcher
+ *    holds one lock over its fork / launch / join sequence, so calls from
+ *    different streams never interleave their event records; their side work
+ *    runs one after the other on the side stream, and a caller's stream waits
+ *    for the side stream up to its own launch, never for a later caller's.
  *  - Every call is asynchronous on `stream` (a hipStream_t passed as void*).
  *  - Return value: ICPMI_OK (0) or a negative ICPMI_ERR_* code; no exceptions
  *    cross the boundary.  Launch-time HIP errors are reported as ICPMI_ERR_HIP.

@@ -812,7 +812,7 @@ __global__ __launch_bounds__(ICP2_FAR_THREADS, 4) void icp2_far_kernel(Icp2Args 
 
 // The parked state of the stages (see Icp2Args), in the caller's workspace: transformed rows | sweep positions (max_src_n of
 // each per pair) | the three lists of pairs (second stage, wide, far) | their three counters, no gap between them.
-struct Icp2Ws {                 // (tests/test_icp2_layout_gpu.py reads the far counter at its offset here: keep the two together)
+struct Icp2Ws {                 // (tests/test_icp2_layout_gpu.py and tests/stream_cases.py read the counters at their offset here: keep them together)
     Carve c;
     int n_pairs, max_src_n;
     size_t st_rows = (size_t)n_pairs * (size_t)max_src_n;

@@ -198,8 +198,11 @@ def voxel_downsample_set(cs, voxel_size, out=None, workspace=None):
     return out
 
 
-def normals_set(cs, k, cloud_ids=None, out=None, workspace=None):
-    """estimate_normals_2d (reference icp.py:51-76) for the selected clouds of a 2-D set."""
+def normals_set(cs, k, cloud_ids=None, out=None, workspace=None, cloud_ids_dev=None, return_workspace=False):
+    """estimate_normals_2d (reference icp.py:51-76) for the selected clouds of a 2-D set.  ``cloud_ids_dev``: the int32 device
+    copy of ``cloud_ids`` when the caller keeps one (else it is uploaded here, and the host waits for the stream);
+    ``return_workspace``: -> (normals, the workspace used), to hand back at the next call.  With ``out``, a workspace and
+    device ids (or every cloud) the call only enqueues."""
     L = _lib.lib()
     if cs.dim != 2:
         raise ValueError("normals are defined for 2-D clouds only")
@@ -211,7 +214,9 @@ def normals_set(cs, k, cloud_ids=None, out=None, workspace=None):
         ids = np.ascontiguousarray(cloud_ids, dtype=np.int32)
         n_sel = len(ids)
         max_n = int(np.diff(cs.off_host)[ids].max()) if n_sel else 0
-        ids_t = torch.from_numpy(ids).to(cs.pts.device)
+        ids_t = cloud_ids_dev if cloud_ids_dev is not None else torch.from_numpy(ids).to(cs.pts.device)
+        if ids_t.dtype != torch.int32 or ids_t.numel() != n_sel or ids_t.device != cs.pts.device:
+            raise ValueError("cloud_ids_dev must be the int32 device copy of cloud_ids")
     if max_n <= PREP_MAX_POINTS or k > 31:
         # sweep search on the axis-sorted copy (prep.hip; clouds above 4096 rows through global memory); the sorted copy
         # is a by-product.  Any k (the exhaustive kernel below holds its lists in registers: k <= 31).
@@ -223,57 +228,78 @@ def normals_set(cs, k, cloud_ids=None, out=None, workspace=None):
                                          _ptr(ids_t), None if ids_host is None else ids_host.ctypes.data_as(C.c_void_p), n_sel,
                                          cs.n_clouds, cs.total_rows, max_n, int(k), _ptr(out), _ptr(workspace),
                                          workspace.numel(), 1, _stream()), "estimate_normals_2d")
-        return out
+        return (out, workspace) if return_workspace else out
     need = L.icpmi_normals_workspace_bytes(cs.total_rows, max_n)
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(need, dtype=torch.uint8, device=cs.pts.device)
     check(L.icpmi_normals_2d_batch(_ptr(cs.pts), _ptr(cs.off), _ptr(cs.cnt), _ptr(ids_t), n_sel, cs.total_rows,
                                    max_n, int(k), _ptr(out), _ptr(workspace), workspace.numel(), _stream()),
           "estimate_normals_2d")
-    return out
+    return (out, workspace) if return_workspace else out
 
 
-def nn_set(cs, pair_src, pair_tgt):
-    """1-NN of every row of cloud pair_src[b] in cloud pair_tgt[b] -> (dist, idx) device tensors [B, stride]."""
+def nn_set(cs, pair_src, pair_tgt=None, out=None):
+    """1-NN of every row of cloud pair_src[b] in cloud pair_tgt[b] -> (dist, idx) device tensors [B, stride].  With a
+    ``PairList`` already on the device as ``pair_src`` and ``out`` = the (dist, idx) of an earlier call, the call allocates
+    and uploads nothing: one launch on the current stream."""
     L = _lib.lib()
-    p = PairList(pair_src, pair_tgt).to(cs.pts.device)
+    p = PairList.of(pair_src, pair_tgt).to(cs.pts.device)
     B = p.B
     stride = max(int(np.diff(cs.off_host)[p.src_host].max()) if B else 0, 1)
-    idx = torch.empty((max(B, 1), stride), dtype=torch.int32, device=cs.pts.device)
-    dist = torch.empty((max(B, 1), stride), dtype=torch.float64, device=cs.pts.device)
+    if out is None:
+        out = (torch.empty((max(B, 1), stride), dtype=torch.float64, device=cs.pts.device),
+               torch.empty((max(B, 1), stride), dtype=torch.int32, device=cs.pts.device))
+    dist, idx = out
+    if tuple(dist.shape) != (max(B, 1), stride) or tuple(idx.shape) != (max(B, 1), stride):
+        raise ValueError(f"out must be (dist, idx) of shape {(max(B, 1), stride)}")
     check(L.icpmi_nn_batch(_ptr(cs.pts), _ptr(cs.off), _ptr(cs.cnt), _ptr(p.src), _ptr(p.tgt), B, stride, cs.dim,
                            _ptr(idx), _ptr(dist), stride, _stream()), "nn")
     return dist, idx
 
 
-def nn_set_sweep(cs, pair_src, pair_tgt, return_second=False):
+class SweepWorkspace:
+    """What ``nn_set_sweep`` allocates for a cloud set and a pair list — the prepared targets, the target ids on the device
+    and the outputs — kept, so that a repeated call only enqueues its two launches."""
+
+    def __init__(self, cs, p, return_second):
+        dev = cs.pts.device
+        B = p.B
+        sizes = np.diff(cs.off_host)
+        self.tgt_ids = np.unique(p.tgt_host)
+        self.max_tgt = int(sizes[self.tgt_ids].max()) if B else 0
+        if self.max_tgt > PREP_MAX_POINTS:
+            raise ValueError(f"target clouds above {PREP_MAX_POINTS} rows need the exhaustive search (nn_set)")
+        self.stride = max(int(sizes[p.src_host].max()) if B else 0, 1)
+        self.prepared = torch.empty(_lib.lib().icpmi_prepared_bytes(cs.total_rows, cs.n_clouds, self.max_tgt),
+                                    dtype=torch.uint8, device=dev)
+        self.ids = torch.from_numpy(self.tgt_ids.astype(np.int32)).to(dev)
+        self.idx = torch.empty((max(B, 1), self.stride), dtype=torch.int32, device=dev)
+        self.dist = torch.empty((max(B, 1), self.stride), dtype=torch.float64, device=dev)
+        self.second = torch.empty((max(B, 1), self.stride), dtype=torch.float64, device=dev) if return_second else None
+
+
+def nn_set_sweep(cs, pair_src, pair_tgt=None, return_second=False, workspace=None):
     """Same result as ``nn_set`` by the sorted-sweep search (2-D, target clouds of at most 4096 rows):
-    prepares the target clouds (axis choice + sort), then binary search + outward sweep per query."""
+    prepares the target clouds (axis choice + sort), then binary search + outward sweep per query.  ``workspace``: the
+    ``SweepWorkspace`` of the same set and (device-resident ``PairList``) pairs — the call then allocates and uploads nothing."""
     L = _lib.lib()
     if cs.dim != 2:
         raise ValueError("the sweep search is 2-D only")
     dev = cs.pts.device
-    p = PairList(pair_src, pair_tgt)
+    p = PairList.of(pair_src, pair_tgt)
     B = p.B
-    sizes = np.diff(cs.off_host)
-    tgt_ids = np.unique(p.tgt_host)
-    max_tgt = int(sizes[tgt_ids].max()) if B else 0
-    if max_tgt > PREP_MAX_POINTS:
-        raise ValueError(f"target clouds above {PREP_MAX_POINTS} rows need the exhaustive search (nn_set)")
-    stride = max(int(sizes[p.src_host].max()) if B else 0, 1)
-    prepared = torch.empty(L.icpmi_prepared_bytes(cs.total_rows, cs.n_clouds, max_tgt), dtype=torch.uint8, device=dev)
-    ids = torch.from_numpy(tgt_ids.astype(np.int32)).to(dev)
-    check(L.icpmi_prepare_targets(_ptr(cs.pts), _ptr(cs.off), None, _ptr(cs.cnt), _ptr(ids), None, len(tgt_ids),
-                                  cs.n_clouds, cs.total_rows, max_tgt, -1, None, _ptr(prepared), prepared.numel(),
+    w = workspace if workspace is not None else SweepWorkspace(cs, p, return_second)
+    if return_second and w.second is None:
+        raise ValueError("this workspace holds no tensor for the second distances")
+    check(L.icpmi_prepare_targets(_ptr(cs.pts), _ptr(cs.off), None, _ptr(cs.cnt), _ptr(w.ids), None, len(w.tgt_ids),
+                                  cs.n_clouds, cs.total_rows, w.max_tgt, -1, None, _ptr(w.prepared), w.prepared.numel(),
                                   _stream()), "prepare_targets")
     p.to(dev)
-    idx = torch.empty((max(B, 1), stride), dtype=torch.int32, device=dev)
-    dist = torch.empty((max(B, 1), stride), dtype=torch.float64, device=dev)
-    second = torch.empty((max(B, 1), stride), dtype=torch.float64, device=dev) if return_second else None
-    check(L.icpmi_nn_prepared_batch(_ptr(cs.pts), _ptr(cs.off), _ptr(cs.cnt), _ptr(prepared), _ptr(p.src), _ptr(p.tgt), B,
-                                    stride, max_tgt, cs.total_rows, _ptr(idx), _ptr(dist), _ptr(second), stride,
+    second = w.second if return_second else None
+    check(L.icpmi_nn_prepared_batch(_ptr(cs.pts), _ptr(cs.off), _ptr(cs.cnt), _ptr(w.prepared), _ptr(p.src), _ptr(p.tgt), B,
+                                    w.stride, w.max_tgt, cs.total_rows, _ptr(w.idx), _ptr(w.dist), _ptr(second), w.stride,
                                     _stream()), "nn (sweep)")
-    return (dist, idx, second) if return_second else (dist, idx)
+    return (w.dist, w.idx, second) if return_second else (w.dist, w.idx)
 
 
 class IcpBatch(_Paired):

@@ -110,11 +110,12 @@ def likelihood_table(peak, sigma_cells, radius):
     return np.clip(np.rint(peak * np.exp(-np.arange(R * R + 1) / (2 * sigma_cells**2))), -32767, 32767).astype(np.int16)
 
 
-def likelihood_field(field, threshold, radius, table, keep_free=True, out=None, d2_out=None):
+def likelihood_field(field, threshold, radius, table, keep_free=True, out=None, d2_out=None, workspace=None):
     """``icpmi_grid_likelihood_field``: ``table[d2]`` wherever ``distance_field``'s d2 is within the radius; beyond it
     min(field, 0) — the raw field's penalty for a hit in observed free space — with ``keep_free``, else 0.  ``table``: radius^2
     + 1 int16 on the host (``likelihood_table``), none of them -32768.  ``d2_out``: an int16 tensor that receives the distance
-    field of the same launch.  -> the int16 (ny, nx) field (``out`` when given), which every matcher takes as
+    field of the same launch; ``workspace``: a uint8 tensor of ``icpmi_grid_likelihood_workspace_bytes`` to use instead of
+    a fresh one.  -> the int16 (ny, nx) field (``out`` when given), which every matcher takes as
     ``field=(tensor, k)`` and ``bound_field`` as its input."""
     R = _radius(radius)
     table = np.ascontiguousarray(table)
@@ -127,7 +128,10 @@ def likelihood_field(field, threshold, radius, table, keep_free=True, out=None, 
         d2_out = _int16_field(field, d2_out, "d2_out")
     ny, nx = field.shape
     L = _lib.lib()
-    ws = torch.empty(L.icpmi_grid_likelihood_workspace_bytes(ny, nx, R), dtype=torch.uint8, device=field.device)
+    need = L.icpmi_grid_likelihood_workspace_bytes(ny, nx, R)
+    ws = workspace if workspace is not None else torch.empty(need, dtype=torch.uint8, device=field.device)
+    if ws.dtype != torch.uint8 or ws.numel() < need or ws.device != field.device:
+        raise ValueError(f"workspace must be a uint8 tensor of at least {need} bytes on the field's device")
     check(L.icpmi_grid_likelihood_field(_ptr(field), ny, nx, int(threshold), R, table.ctypes.data_as(C.c_void_p), int(bool(keep_free)),
                                         None if d2_out is None else _ptr(d2_out), _ptr(out), _ptr(ws), ws.numel(), _stream()),
           "grid_likelihood_field")

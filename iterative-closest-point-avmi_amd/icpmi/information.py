@@ -37,12 +37,14 @@ def _method_code(method):
     raise ValueError(f"method must be one of {ICP_METHODS}, got {method!r}")
 
 
-def information_set(cs, normals, pair_src, pair_tgt, transforms, method, max_corr_dist=None):
+def information_set(cs, normals, pair_src, pair_tgt, transforms, method, max_corr_dist=None, out=None):
     """``icpmi_icp_information_batch`` for the pairs (pair_src[b], pair_tgt[b]) of a 2-D cloud set — filtered or not: the
     valid rows are ``cs.cnt``'s — at ``transforms`` ([B, 6]: R row major, t; a device tensor, or an array that is
     uploaded) -> a device (B, INFO_DOUBLES) float64 tensor of records (slots ``_lib.INFO_*``; ``unpack_information``).
     ``normals``: row layout of ``cs.pts`` (``normals_set``), needed for point_to_line only.  ``max_corr_dist=None`` keeps
-    every correspondence.  Enqueued on the current stream; does not synchronise."""
+    every correspondence.  Enqueued on the current stream.  With a ``PairList`` already on the device as ``pair_src``, a
+    device tensor of transforms and ``out`` (a (B, INFO_DOUBLES) float64 tensor to write into) the call uploads and
+    allocates nothing and does not synchronise; an upload from an array makes the host wait for the stream."""
     L = _lib.lib()
     if cs.dim != 2:
         raise IcpmiError("the information matrix is 2-D only (ICPMI_ERR_UNSUPPORTED)")
@@ -64,7 +66,10 @@ def information_set(cs, normals, pair_src, pair_tgt, transforms, method, max_cor
     if normals is not None and (normals.dtype != torch.float64 or normals.shape[0] < cs.total_rows or normals.device != dev):
         raise ValueError("normals must be float64, on the set's device, one row per row of the set")
     max_src_n = int(np.diff(cs.off_host)[p.src_host].max()) if B else 0
-    out = torch.empty((B, _lib.INFO_DOUBLES), dtype=torch.float64, device=dev)
+    if out is None:
+        out = torch.empty((B, _lib.INFO_DOUBLES), dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (B, _lib.INFO_DOUBLES) or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous ({B}, {_lib.INFO_DOUBLES}) float64 tensor on {dev}")
     check(L.icpmi_icp_information_batch(_ptr(cs.pts), _ptr(cs.off), _ptr(cs.cnt), _ptr(normals), _ptr(p.src), _ptr(p.tgt), B,
                                         max_src_n, _ptr(transforms), code, -1.0 if max_corr_dist is None else float(max_corr_dist),
                                         _ptr(out), _stream()), "icp_information")
@@ -75,7 +80,10 @@ def batch_information(batch, pairs=None, results=None):
     """``IcpBatch.information``: the records of the pairs ``pairs`` (indices into the batch's pair list; None: all) at the
     transforms held in ``results`` (None: the batch's own result tensor, as the last ``run()`` left it), with the batch's
     method and ``max_corr_dist``, on its filtered clouds.  The transforms are gathered on the device (slots RES_R..RES_R + 3
-    and RES_T, RES_T + 1 of each record), so nothing synchronises.
+    and RES_T, RES_T + 1 of each record).  For ``pairs=None`` the call keeps the target ids and the normals' workspace on
+    the device (an ``IcpBatch`` has the ids there already; a resident batch uploads them at its first call) and only
+    enqueues, without a synchronisation.  A selection of pairs is uploaded at every call, and the host waits for the stream
+    while it is.
 
     Row-order normals of the targets: on the sorted-sweep path they exist only inside the prepared buffer, in sorted order,
     so they are computed here — ``normals_set`` on the filtered clouds, for the targets of the listed pairs, into a buffer
@@ -88,19 +96,34 @@ def batch_information(batch, pairs=None, results=None):
     vox = batch.vox
     dev = vox.pts.device
     res = batch.results if results is None else results
-    cols = torch.tensor([_lib.RES_R, _lib.RES_R + 1, _lib.RES_R + 2, _lib.RES_R + 3, _lib.RES_T, _lib.RES_T + 1], device=dev)
-    transforms = res[torch.from_numpy(idx).to(dev)][:, cols].contiguous()
+    if batch.use_p2l and (batch.info_normals is None or batch.info_normals.shape[0] < vox.pts.shape[0]):
+        batch.info_normals = torch.zeros((max(vox.pts.shape[0], 1), 2), dtype=torch.float64, device=dev)
+    mcd = batch.params.max_corr_dist
+    mcd = None if mcd < 0 else mcd
+    if pairs is None and batch.B:
+        # every pair: the batch's own pair list, and buffers kept from the first call on
+        kept = getattr(batch, "_info_all", None)
+        if kept is None:
+            ids, ids_dev = getattr(batch, "tgt_ids", None), getattr(batch, "tgt_ids_dev", None)
+            if ids_dev is None:                                    # a resident batch keeps no list of its targets: one upload, once
+                ids = np.unique(batch.pair_tgt_host)
+                ids_dev = torch.from_numpy(ids).to(dev)
+            kept = batch._info_all = dict(ids=ids, ids_dev=ids_dev, ws=None)
+        T = torch.cat([res[:batch.B, _lib.RES_R:_lib.RES_R + 4], res[:batch.B, _lib.RES_T:_lib.RES_T + 2]], dim=1)
+        normals = None
+        if batch.use_p2l:
+            normals, kept["ws"] = normals_set(vox, batch.normal_k, cloud_ids=kept["ids"], out=batch.info_normals,
+                                              workspace=kept["ws"], cloud_ids_dev=kept["ids_dev"], return_workspace=True)
+        return information_set(vox, normals, batch.pairs, None, T, batch.params.method, mcd)
+    transforms = torch.cat([res[:, _lib.RES_R:_lib.RES_R + 4], res[:, _lib.RES_T:_lib.RES_T + 2]], dim=1)[torch.from_numpy(idx).to(dev)]
     src, tgt = batch.pair_src_host[idx], batch.pair_tgt_host[idx]
     normals = None
     if batch.use_p2l:
-        if batch.info_normals is None or batch.info_normals.shape[0] < vox.pts.shape[0]:
-            batch.info_normals = torch.zeros((max(vox.pts.shape[0], 1), 2), dtype=torch.float64, device=dev)
         if len(idx):
             normals = normals_set(vox, batch.normal_k, cloud_ids=np.unique(tgt), out=batch.info_normals)
         else:
             normals = batch.info_normals
-    mcd = batch.params.max_corr_dist
-    return information_set(vox, normals, src, tgt, transforms, batch.params.method, None if mcd < 0 else mcd)
+    return information_set(vox, normals, src, tgt, transforms.contiguous(), batch.params.method, mcd)
 
 
 def unpack_information(rec):

@@ -169,11 +169,16 @@ class ParticleFilter:
         """Enqueue the beam model of ``scan_pairs``' call into ``records``, with the filter's table, half width and beyond."""
         return pairs.beam(self._beam_table, self.half_width, self.beyond, out=self.records)[0]
 
-    def _weigh(self, cs, cloud):
-        """The beam model with every particle naming cloud ``cloud`` of ``cs``, then the weights -> (ess, OK records)."""
-        self.beam(self.scan_pairs(cs, cloud))
+    def enqueue_weights(self, pairs):
+        """The two launches of a measurement update on the current stream, nothing read back: the beam model of
+        ``scan_pairs``' call into ``records``, then ``icpmi_pf_weights`` into ``w`` and ``sums``."""
+        self.beam(pairs)
         check(_lib.lib().icpmi_pf_weights(self.n, _ptr(self.records), _ptr(self._weight_table), len(self.weight_table_host), self.weight_shift,
                                           _ptr(self.w), _ptr(self.sums), _stream()), "pf_weights")
+
+    def _weigh(self, cs, cloud):
+        """The beam model with every particle naming cloud ``cloud`` of ``cs``, then the weights -> (ess, OK records)."""
+        self.enqueue_weights(self.scan_pairs(cs, cloud))
         self.last_sums = [int(v) for v in self.sums.cpu().numpy()]         # the step's one synchronisation
         W, WW, ok = self.last_sums[_lib.PF_SUM_W], self.last_sums[_lib.PF_SUM_WW], self.last_sums[_lib.PF_SUM_OK]
         self.ess = W * W / WW if WW else 0.0
@@ -220,14 +225,18 @@ class ParticleFilter:
         return True
 
     # ── reading the filter ───────────────────────────────────────────────────
+    def enqueue_estimate(self):
+        """``icpmi_pf_estimate`` on the current stream, nothing read back -> ``moments``, the device tensor of the eight sums."""
+        check(_lib.lib().icpmi_pf_estimate(self.n, _ptr(self.w), _ptr(self.pair_t), _ptr(self.cos_sin), _ptr(self.moments), _ptr(self._ws),
+                                           self._ws.numel(), _stream()), "pf_estimate")
+        return self.moments
+
     def estimate(self):
         """``icpmi_pf_estimate`` of the present particles and weights (synchronises) -> a dict: ``mean`` [x, y, theta] — the
         weighted means of x and y, theta = atan2(sum w sin, sum w cos) —, ``covariance`` (2, 2) of (x, y), ``resultant`` in
         [0, 1] (1: every heading equal) and ``sums``, the eight float64 sums themselves.  Every entry NaN but ``sums`` when no
         particle has a weight."""
-        check(_lib.lib().icpmi_pf_estimate(self.n, _ptr(self.w), _ptr(self.pair_t), _ptr(self.cos_sin), _ptr(self.moments), _ptr(self._ws),
-                                           self._ws.numel(), _stream()), "pf_estimate")
-        S = self.moments.cpu().numpy().copy()
+        S = self.enqueue_estimate().cpu().numpy().copy()
         if not S[0] > 0.0:
             return {"mean": np.full(3, np.nan), "covariance": np.full((2, 2), np.nan), "resultant": float("nan"), "sums": S}
         W = S[0]

@@ -145,6 +145,38 @@ def _voxel_rows(points_dev, voxel_size):
     return out.pts[: _b.filtered_rows(out)]
 
 
+def enqueue_submap_search(ctx, src_in, tgt_in, dtab, n_coarse, max_fine, pred_t, voxel_size):
+    """The device half of ``submap_rotation_search``, enqueued on the current stream with nothing read back: the two device
+    clouds copied behind one another into the context's rows, ``icpmi_rotation_search`` into ``ctx.rec`` and — for a scan
+    the refinement holds on chip — ``icpmi_rotation_refine`` into ``ctx.ref_out``.  ``dtab``: the angle tables on the device
+    (``ctx.device_table``).  -> whether the refinement ran on the device.  Allocates only when the context has to grow."""
+    ns, nt = int(src_in.shape[0]), int(tgt_in.shape[0])
+    if ns + nt > ctx.cap:
+        ctx.cap = max(2 * (ns + nt), 8192)
+        ctx.stage = torch.empty((ctx.cap, 2), dtype=torch.float64).pin_memory()
+        ctx.pts = torch.empty((ctx.cap, 2), dtype=torch.float64, device=ctx.dev)
+    ctx.pts[:ns].copy_(src_in)                                                    # device to device: the submap never visits the host
+    ctx.pts[ns:ns + nt].copy_(tgt_in)
+    ws = ctx.workspace(ns, nt, n_coarse, max_fine)
+    L = _lib.lib()
+    _lib.check(L.icpmi_rotation_search(_b._ptr(ctx.pts), ns, nt, float(voxel_size), _b._ptr(dtab[0]), n_coarse,
+                                       _b._ptr(dtab[1]) if max_fine else None, _b._ptr(dtab[2]) if max_fine else None,
+                                       max_fine, 0, float(pred_t[0]), float(pred_t[1]), _b._ptr(ctx.rec), _b._ptr(ws),
+                                       ws.numel(), _b._stream()), "submap_rotation_search")
+    on_device = ns <= _lib.RSR_MAX_ROWS                                       # the refinement's finishing workgroup holds the rows in LDS
+    if on_device:
+        # translation: one nearest-neighbour centroid step over the closest 80 %, slam.py:161-181, still on the device
+        need = L.icpmi_rotation_refine_workspace_bytes(ns)
+        if getattr(ctx, "ref_ws", None) is None or ctx.ref_ws.numel() < need:
+            ctx.ref_ws = torch.empty(2 * need, dtype=torch.uint8, device=ctx.dev)
+            ctx.ref_out = torch.zeros(4, dtype=torch.float64, device=ctx.dev)
+        _lib.check(L.icpmi_rotation_refine(_b._ptr(ws), ns, nt, _b._ptr(ctx.rec), _b._ptr(dtab[0]),
+                                           _b._ptr(dtab[1]) if max_fine else None, max_fine, float(pred_t[0]), float(pred_t[1]),
+                                           _b._ptr(ctx.ref_out), _b._ptr(ctx.ref_ws), ctx.ref_ws.numel(), _b._stream()),
+                   "submap_rotation_search (refinement)")
+    return on_device
+
+
 def submap_rotation_search(source_local, submap_global, predicted_pose, angle_range=60.0, angle_step=2.0,
                            fine_step=0.5, voxel_size=0.3):
     """slam.py:111-183 -> (R (2,2), t (2,)).
@@ -171,31 +203,10 @@ def submap_rotation_search(source_local, submap_global, predicted_pose, angle_ra
                                np.deg2rad(fine_step))                            # slam.py:154-156, for every possible winner
     ctx = _SearchContext.get()
     ns, nt = int(src_in.shape[0]), int(tgt_in.shape[0])
-    if ns + nt > ctx.cap:
-        ctx.cap = max(2 * (ns + nt), 8192)
-        ctx.stage = torch.empty((ctx.cap, 2), dtype=torch.float64).pin_memory()
-        ctx.pts = torch.empty((ctx.cap, 2), dtype=torch.float64, device=ctx.dev)
-    ctx.pts[:ns].copy_(src_in)                                                    # device to device: the submap never visits the host
-    ctx.pts[ns:ns + nt].copy_(tgt_in)
     dtab = ctx.device_table(angles, fine, fine_n)
     max_fine = int(fine.shape[1])
-    ws = ctx.workspace(ns, nt, len(angles), max_fine)
-    L = _lib.lib()
-    _lib.check(L.icpmi_rotation_search(_b._ptr(ctx.pts), ns, nt, float(voxel_size), _b._ptr(dtab[0]), len(angles),
-                                       _b._ptr(dtab[1]) if max_fine else None, _b._ptr(dtab[2]) if max_fine else None,
-                                       max_fine, 0, float(pred_t[0]), float(pred_t[1]), _b._ptr(ctx.rec), _b._ptr(ws),
-                                       ws.numel(), _b._stream()), "submap_rotation_search")
-    on_device = ns <= _lib.RSR_MAX_ROWS                                       # the refinement's finishing workgroup holds the rows in LDS
+    on_device = enqueue_submap_search(ctx, src_in, tgt_in, dtab, len(angles), max_fine, pred_t, voxel_size)
     if on_device:
-        # translation: one nearest-neighbour centroid step over the closest 80 %, slam.py:161-181, still on the device
-        need = L.icpmi_rotation_refine_workspace_bytes(ns)
-        if getattr(ctx, "ref_ws", None) is None or ctx.ref_ws.numel() < need:
-            ctx.ref_ws = torch.empty(2 * need, dtype=torch.uint8, device=ctx.dev)
-            ctx.ref_out = torch.zeros(4, dtype=torch.float64, device=ctx.dev)
-        _lib.check(L.icpmi_rotation_refine(_b._ptr(ws), ns, nt, _b._ptr(ctx.rec), _b._ptr(dtab[0]),
-                                           _b._ptr(dtab[1]) if max_fine else None, max_fine, float(pred_t[0]), float(pred_t[1]),
-                                           _b._ptr(ctx.ref_out), _b._ptr(ctx.ref_ws), ctx.ref_ws.numel(), _b._stream()),
-                   "submap_rotation_search (refinement)")
         both = torch.cat([ctx.rec, ctx.ref_out]).cpu().numpy()                # one read-back
         rec, ref = both[:_lib.RSREC_DOUBLES], both[_lib.RSREC_DOUBLES:]
     else:
