@@ -680,7 +680,8 @@ int icpmi_bresenham_cells(const int32_t* segs, const int64_t* cell_off, int32_t 
  * shares its launch with the finalise pass of the previous group (the other set of regions).  A region covers the
  * box the rays stay in (icpmi_grid_update_scans_box; the whole grid otherwise), so a group holds up to 32 scans
  * when the box is at most 1/16 of the grid and at least 2 always: a replay of S scans is about S/32 + 1 launches.
- * Every call leaves the workspace all zero again.
+ * Every call leaves the workspace all zero again; a call that is refused (icpmi_grid_update_plan lists the reasons) is
+ * refused before anything is started.
  * scan_seq: ignored (kept for binary compatibility; calls are independent).
  * full_clip != 0 clips every cell of the grid on the first scan (needed only
  * when cells may lie outside [lo, hi] beforehand).
@@ -730,23 +731,29 @@ int icpmi_grid_update_scans_box(float* log_odds, void* counts, int32_t ny, int32
                                 const int32_t* box_host, void* stream);
 
 /* What icpmi_grid_update_scans_box starts for its HOST arguments (have_hits: whether `hits` is non-null), under the
- * RAYCAST option as it stands — no HIP call, no launch, no device pointer.  The refusals are that entry's, in its
- * order (ICPMI_ERR_ARG: a null out or hit_off_host, ny, nx <= 0 or > 2^29, n_scans < 0, a band outside [0, ny], a
- * resolution that is not > 0, a negative beam count, beams without hits).  An empty band starts nothing: ICPMI_OK and
- * a plan of zeros (ICPMI_RC_PASS_NONE).
+ * RAYCAST option as it stands — no HIP call, no launch, no device pointer.  The refusals are that entry's: both ask
+ * one check, which that entry makes before its first launch, so a refused call has touched neither the grid nor the
+ * workspace (ICPMI_ERR_ARG: a null out or hit_off_host, ny, nx <= 0 or > 2^29, n_scans < 0, a band outside [0, ny], a
+ * resolution that is not > 0, a negative beam count in any scan, beams without hits).  An empty band starts nothing:
+ * ICPMI_OK and a plan of zeros (ICPMI_RC_PASS_NONE).
  *   pass        the counting pass of the scans that fit a 16-bit counter: one launch in which a workgroup owns a
  *               rectangle of cells (OWNER), counters of a 64 x 64 tile in LDS (TILES), an atomic per (wave, cell) on
  *               the scan's counter region (ATOMIC)
  *   group_max   scans counted per launch at most;  tiles_x, tiles_y: 64 x 64 tiles of the window (grid or band cut to
  *               the box);  live_scans: scans with beams
  *   wide        1: a scan has more than 65 535 beams and goes through the two-round route (hits, then misses, on the
- *               atomic counters) whatever `pass` says about the others */
+ *               atomic counters) whatever `pass` says about the others
+ *   rounds      what the call issues one after the other: groups of up to group_max scans, and wide scans one each
+ *               (the owner pass: 1; no scan with beams: 0)
+ *   launches    kernel launches of those rounds (the memset of the box slots is none): a group is one launch that also
+ *               finalises the group before it, plus one for its scan boxes (TILES, live_scans > 1) when no group went
+ *               before and one to finalise it when no group follows; a wide scan is four */
 #define ICPMI_RC_PASS_NONE 0
 #define ICPMI_RC_PASS_OWNER 1
 #define ICPMI_RC_PASS_TILES 2
 #define ICPMI_RC_PASS_ATOMIC 3
 typedef struct icpmi_grid_plan {
-    int32_t pass, group_max, tiles_x, tiles_y, live_scans, wide;
+    int32_t pass, group_max, tiles_x, tiles_y, live_scans, wide, rounds, launches;
 } icpmi_grid_plan;
 int icpmi_grid_update_plan(int32_t ny, int32_t nx, double resolution, const int32_t* hit_off_host, int32_t n_scans,
                            int32_t have_hits, int32_t full_clip, int32_t row_begin, int32_t row_end,

@@ -21,6 +21,7 @@
 // incrementally, and equal cells in adjacent lanes are merged into one atomic
 // (all 2 048 beams start in the origin cell).
 #include "raywalk.hpp"
+#include <vector>
 
 namespace icpmi {
 
@@ -718,8 +719,8 @@ struct GridWs {
     size_t bytes = c.off;
 };
 
-// ── host side of update_scan: what a call starts is decided first and as a whole (plan_raycast: a function of its
-// arguments, no HIP call), then issued (icpmi_grid_update_scans_box) ──────────────────────────────────────────────
+// ── host side of update_scan: a call is checked (check_update), then what it starts is decided as a whole (plan_raycast
+// and plan_rounds: functions of its host arguments, no HIP call), then issued (icpmi_grid_update_scans_box) ──────────
 // The RAYCAST option by its first letter; `other` (any other value) only keeps the owner pass off.
 enum class RcOption { unset, atomic, tiles, owner, other };
 static RcOption parse_rc_option(const char* v) {
@@ -785,23 +786,57 @@ static int count_blocks(int nb) {
     return (int)((waves * ICPMI_WAVE + RC_THREADS - 1) / RC_THREADS);
 }
 
+// Every refusal of an update that its host arguments decide; the launcher and icpmi_grid_update_plan both ask here and
+// nowhere else, so a call is refused before it starts anything or not at all.  An empty band starts nothing and passes.
+static int check_update(int ny, int nx, double resolution, const int32_t* hit_off, int n_scans, bool have_hits,
+                        int row_begin, int row_end) {
+    if (!hit_off || ny <= 0 || nx <= 0 || n_scans < 0) return ICPMI_ERR_ARG;
+    if (row_begin < 0 || row_end > ny || row_begin > row_end) return ICPMI_ERR_ARG;
+    if (row_begin == row_end) return ICPMI_OK;
+    if (ny > RC_COORD_MAX || nx > RC_COORD_MAX || !(resolution > 0.0)) return ICPMI_ERR_ARG;
+    for (int t = 0; t < n_scans; ++t) {
+        const int nb = hit_off[t + 1] - hit_off[t];
+        if (nb < 0 || (nb > 0 && !have_hits)) return ICPMI_ERR_ARG;
+    }
+    return ICPMI_OK;
+}
+
 // The group that starts at the first scan with beams at or after `from`, and goes on while the scans fit a 16-bit counter
-// (scans without beams are skipped: mapping.py:113-114, a silent no-op without a clip).  BUILT: end = one past its last
-// scan; NONE: the replay ends (end = n_scans) or scan `end` is too wide for a group; BAD: a negative beam count.
-enum { RC_GROUP_BAD = -1, RC_GROUP_NONE = 0, RC_GROUP_BUILT = 1 };
-static int build_group(const int32_t* hit_off, int n_scans, int group_max, int from, ScanGroup& gq, int& end) {
+// (scans without beams are skipped: mapping.py:113-114, a silent no-op without a clip; check_update has seen to it that
+// no count is negative).  True: end = one past its last scan; false: the replay ends (end = n_scans) or scan `end` is
+// too wide for a group.
+static bool build_group(const int32_t* hit_off, int n_scans, int group_max, int from, ScanGroup& gq, int& end) {
     gq = ScanGroup{};
     for (end = from; end < n_scans && gq.n < group_max; ++end) {
         const int nb = hit_off[end + 1] - hit_off[end];
-        if (nb < 0) return RC_GROUP_BAD;
         if (nb == 0) continue;
         if (nb > RC_WIDE) break;
         gq.nb[gq.n] = nb; gq.origin_row[gq.n] = end; gq.hit_row[gq.n] = hit_off[end];
         gq.first_block[gq.n + 1] = gq.first_block[gq.n] + count_blocks(nb);
         ++gq.n;
     }
-    return gq.n > 0 ? RC_GROUP_BUILT : RC_GROUP_NONE;
+    return gq.n > 0;
 }
+
+// A round of a replay: a group (grp.n > 0) or one scan of more beams than a group takes (grp.n == 0, scan `wide_scan`).
+struct RcRound { ScanGroup grp; int wide_scan; };
+// The rounds of a checked call in the order they are issued: every scan with beams is in exactly one.
+static std::vector<RcRound> plan_rounds(const int32_t* hit_off, int n_scans, const RaycastPlan& p) {
+    std::vector<RcRound> rounds;
+    for (int s = 0; s < n_scans;) {
+        RcRound r{};
+        int end;
+        const bool built = build_group(hit_off, n_scans, p.group_max, s, r.grp, end);
+        if (!built && end >= n_scans) break;                    // only scans without beams were left
+        r.wide_scan = built ? -1 : end;
+        s = built ? end : end + 1;
+        rounds.push_back(r);
+    }
+    return rounds;
+}
+static bool is_group(const std::vector<RcRound>& rounds, int q) { return q >= 0 && q < (int)rounds.size() && rounds[q].grp.n > 0; }
+// The tile pass with several live scans in the window works on each scan's own cell box, found on the device.
+static bool own_boxes(const RaycastPlan& p) { return p.pass == RcPass::tiles && p.live_scans > 1; }
 
 // What the q-th group (or wide scan) of a call works on: counter grids and scan boxes alternate between two sets, the
 // bounding-box slots between three (a finalise pass frees the slot two groups ahead).
@@ -877,29 +912,29 @@ extern "C" int icpmi_grid_update_scans_band(float* log_odds, void* counts_ws, in
                                        l_hit, l_miss, lo, hi, scan_seq, full_clip, row_begin, row_end, nullptr, stream);
 }
 
-// What icpmi_grid_update_scans_box would start for these host arguments, under the RAYCAST option as it stands: the same
-// refusals in the same order, then plan_raycast and build_group's checks of the beam counts.  No HIP call.
+// What icpmi_grid_update_scans_box would start for these host arguments, under the RAYCAST option as it stands: that
+// entry's check, plan and rounds, and the launches its walk over the rounds issues, counted.  No HIP call.
 extern "C" int icpmi_grid_update_plan(int32_t ny, int32_t nx, double resolution, const int32_t* hit_off_host, int32_t n_scans,
                                       int32_t have_hits, int32_t full_clip, int32_t row_begin, int32_t row_end,
                                       const int32_t* box_host, icpmi_grid_plan* out) {
     using namespace icpmi;
-    if (!out || !hit_off_host || ny <= 0 || nx <= 0 || n_scans < 0) return ICPMI_ERR_ARG;
-    if (row_begin < 0 || row_end > ny || row_begin > row_end) return ICPMI_ERR_ARG;
-    if (ny > RC_COORD_MAX || nx > RC_COORD_MAX || !(resolution > 0.0)) return ICPMI_ERR_ARG;
+    const int rc = out ? check_update(ny, nx, resolution, hit_off_host, n_scans, have_hits != 0, row_begin, row_end) : ICPMI_ERR_ARG;
+    if (rc != ICPMI_OK) return rc;
     *out = icpmi_grid_plan{};
     if (row_begin == row_end) return ICPMI_OK;                  // an empty band: nothing is started (pass ICPMI_RC_PASS_NONE)
     const RaycastPlan plan = plan_raycast(ny, nx, row_begin, row_end, box_host, hit_off_host, n_scans, full_clip != 0,
                                           have_hits != 0, parse_rc_option(option("RAYCAST")));
-    int wide = 0;
-    for (int t = 0; t < n_scans; ++t) {
-        const int nb = hit_off_host[t + 1] - hit_off_host[t];
-        if (nb < 0) return ICPMI_ERR_ARG;
-        if (nb > 0 && !have_hits) return ICPMI_ERR_ARG;
-        wide |= nb > RC_WIDE ? 1 : 0;
-    }
     out->pass = plan.pass == RcPass::owner ? ICPMI_RC_PASS_OWNER : plan.pass == RcPass::tiles ? ICPMI_RC_PASS_TILES : ICPMI_RC_PASS_ATOMIC;
     out->group_max = plan.group_max; out->tiles_x = plan.tiles_x; out->tiles_y = plan.tiles_y;
-    out->live_scans = plan.live_scans; out->wide = wide;
+    if (plan.pass == RcPass::owner) { out->live_scans = out->rounds = out->launches = 1; return ICPMI_OK; }
+    const std::vector<RcRound> rounds = plan_rounds(hit_off_host, n_scans, plan);
+    out->rounds = (int32_t)rounds.size();
+    for (int q = 0; q < (int)rounds.size(); ++q) {              // the launches of the launcher's walk, round by round
+        const bool group = is_group(rounds, q), after_group = is_group(rounds, q - 1);
+        out->live_scans += group ? rounds[q].grp.n : 1; out->wide |= group ? 0 : 1;
+        if (group) out->launches += (own_boxes(plan) && !after_group ? 1 : 0) + 1 + (is_group(rounds, q + 1) ? 0 : 1);
+        else out->launches += 4;
+    }
     return ICPMI_OK;
 }
 
@@ -910,10 +945,9 @@ extern "C" int icpmi_grid_update_scans_box(float* log_odds, void* counts_ws, int
                                            int64_t scan_seq, int32_t full_clip, int32_t row_begin, int32_t row_end,
                                            const int32_t* box_host, void* stream) {
     using namespace icpmi;
-    if (!log_odds || !counts_ws || !origins || !hit_off_host || ny <= 0 || nx <= 0 || n_scans < 0) return ICPMI_ERR_ARG;
-    if (row_begin < 0 || row_end > ny || row_begin > row_end) return ICPMI_ERR_ARG;
-    if (row_begin == row_end) return ICPMI_OK;                  // an empty band: nothing to write
-    if (ny > RC_COORD_MAX || nx > RC_COORD_MAX || !(resolution > 0.0)) return ICPMI_ERR_ARG;
+    if (!log_odds || !counts_ws || !origins) return ICPMI_ERR_ARG;
+    const int rc = check_update(ny, nx, resolution, hit_off_host, n_scans, hits != nullptr, row_begin, row_end);
+    if (rc != ICPMI_OK || row_begin == row_end) return rc;      // refused, or an empty band: nothing to write
     hipStream_t st = (hipStream_t)stream;
     (void)scan_seq;   // ignored: a call starts with empty boxes and ends with empty counter grids (a finalise pass zeroes what it reads)
     const RaycastPlan plan = plan_raycast(ny, nx, row_begin, row_end, box_host, hit_off_host, n_scans, full_clip != 0,
@@ -933,53 +967,41 @@ extern "C" int icpmi_grid_update_scans_box(float* log_odds, void* counts_ws, int
         ICPMI_LAUNCH_CHECK();
         return ICPMI_OK;
     }
-    // The replay: the launch that counts group q also finalises group q - 1 (`fin`, from the other set of counter grids)
-    // and, on the tile pass, finds the scan boxes of group q + 1 (`nxt`, built one round ahead for that).
+    // The replay, round by round.  The launch that counts group q also finalises group q - 1 when that was a group (from the
+    // other set of counter grids) and, with scan boxes, finds those of group q + 1 for it; a group that no group follows is
+    // finalised by a launch of its own, and so are its boxes found when no group went before.
     constexpr int rt_wgs = 1536;     // resident workgroups of the tile pass (6 per CU)
-    ScanGroup grp{}, nxt{};
-    int end = 0, nxt_end = 0;
-    bool have_nxt = false, pending = false;   // pending: a counted group whose finalisation rides on the next launch
-    FinArgs fin = base;
-    int clip_all = full_clip, s = 0;
-    for (int64_t q = 0;; ++q) {
-        const bool boxes_ready = have_nxt;
-        int r = RC_GROUP_BUILT;
-        if (have_nxt) { grp = nxt; end = nxt_end; have_nxt = false; }
-        else r = build_group(hit_off_host, n_scans, plan.group_max, s, grp, end);
-        if (r == RC_GROUP_BAD) return ICPMI_ERR_ARG;
-        if (r == RC_GROUP_NONE && end >= n_scans) break;
-        if (!hits) return ICPMI_ERR_ARG;
+    static const ScanGroup no_group{};
+    const std::vector<RcRound> rounds = plan_rounds(hit_off_host, n_scans, plan);
+    const auto fin_of = [&](int q) {                            // only round 0 clips the whole band: every cell is inside [lo, hi] after it
+        return fin_args(base, rc_slots(ws, plan, q), rounds[q].grp.n, 0, true, q == 0 ? full_clip : 0);
+    };
+    for (int q = 0; q < (int)rounds.size(); ++q) {
         const RcSlots at = rc_slots(ws, plan, q);
-        if (r == RC_GROUP_NONE) {                               // scan `end` is too wide for a group
-            if (pending) { ray_finalize_kernel<<<RC_FIN_BLOCKS, RC_THREADS, 0, st>>>(g, fin); pending = false; }
-            launch_wide_scan(g, origins + 2 * (size_t)end, hits + 2 * (size_t)hit_off_host[end],
-                             hit_off_host[end + 1] - hit_off_host[end], at, base, clip_all, st);
-            s = end + 1;
-        } else {
-            const int blocks = grp.first_block[grp.n];
-            if (plan.pass == RcPass::tiles) {
-                TileArgs ta{nullptr, plan.tiles_x, plan.tiles_y};
-                if (plan.live_scans > 1) {                      // several scans share the window: each one's own box
-                    if (!boxes_ready) ray_scan_boxes_kernel<<<grp.n, RT_THREADS, 0, st>>>(g, origins, hits, grp, at.boxes);
-                    ta.boxes = at.boxes;
-                    const int rn = build_group(hit_off_host, n_scans, plan.group_max, end, nxt, nxt_end);
-                    if (rn == RC_GROUP_BAD) return ICPMI_ERR_ARG;
-                    have_nxt = rn == RC_GROUP_BUILT;            // (nxt.n is 0 otherwise)
-                }
-                const int n_items = grp.n * rt_blocks_per_scan(plan.tiles_x * plan.tiles_y);
-                const int n_count = n_items < rt_wgs ? n_items : rt_wgs, n_fin = pending ? RC_FIN_BLOCKS : 0;
-                ray_tile_step_kernel<<<n_count + n_fin + nxt.n, RT_THREADS, 0, st>>>(g, origins, hits, grp, at.counts, plan.cells, at.box, ta,
-                                                                                     n_items, n_count, n_fin, fin, nxt, at.next_boxes);
-            } else if (pending) ray_step_kernel<<<blocks + RC_FIN_BLOCKS, RC_THREADS, 0, st>>>(g, origins, hits, grp, at.counts, plan.cells,
-                                                                                               at.box, blocks, fin);
-            else ray_count_group_kernel<<<blocks, RC_THREADS, 0, st>>>(g, origins, hits, grp, at.counts, plan.cells, at.box);
-            fin = fin_args(base, at, grp.n, 0, true, clip_all);
-            pending = true; s = end;
+        const ScanGroup& grp = rounds[q].grp;
+        if (!is_group(rounds, q)) {
+            const int w = rounds[q].wide_scan;
+            launch_wide_scan(g, origins + 2 * (size_t)w, hits + 2 * (size_t)hit_off_host[w], hit_off_host[w + 1] - hit_off_host[w],
+                             at, base, q == 0 ? full_clip : 0, st);
+            ICPMI_LAUNCH_CHECK();
+            continue;
         }
-        clip_all = 0;                                           // every cell is inside [lo, hi] after one clipped scan
+        const bool after_group = is_group(rounds, q - 1), before_group = is_group(rounds, q + 1);
+        const FinArgs fin = after_group ? fin_of(q - 1) : base;
+        const int blocks = grp.first_block[grp.n];
+        if (plan.pass == RcPass::tiles) {
+            const TileArgs ta{own_boxes(plan) ? at.boxes : nullptr, plan.tiles_x, plan.tiles_y};
+            if (own_boxes(plan) && !after_group) ray_scan_boxes_kernel<<<grp.n, RT_THREADS, 0, st>>>(g, origins, hits, grp, at.boxes);
+            const ScanGroup& nxt = own_boxes(plan) && before_group ? rounds[q + 1].grp : no_group;
+            const int n_items = grp.n * rt_blocks_per_scan(plan.tiles_x * plan.tiles_y);
+            const int n_count = n_items < rt_wgs ? n_items : rt_wgs, n_fin = after_group ? RC_FIN_BLOCKS : 0;
+            ray_tile_step_kernel<<<n_count + n_fin + nxt.n, RT_THREADS, 0, st>>>(g, origins, hits, grp, at.counts, plan.cells, at.box, ta,
+                                                                                 n_items, n_count, n_fin, fin, nxt, at.next_boxes);
+        } else if (after_group) ray_step_kernel<<<blocks + RC_FIN_BLOCKS, RC_THREADS, 0, st>>>(g, origins, hits, grp, at.counts, plan.cells,
+                                                                                                at.box, blocks, fin);
+        else ray_count_group_kernel<<<blocks, RC_THREADS, 0, st>>>(g, origins, hits, grp, at.counts, plan.cells, at.box);
+        if (!before_group) ray_finalize_kernel<<<RC_FIN_BLOCKS, RC_THREADS, 0, st>>>(g, fin_of(q));
         ICPMI_LAUNCH_CHECK();
     }
-    if (pending) ray_finalize_kernel<<<RC_FIN_BLOCKS, RC_THREADS, 0, st>>>(g, fin);
-    ICPMI_LAUNCH_CHECK();
     return ICPMI_OK;
 }

@@ -686,48 +686,56 @@ def test_cell_box_holds_a_coordinate_whose_quotient_overflows():
 
 def test_grid_update_plan_rows():
     """icpmi_grid_update_plan: the host-only view of what icpmi_grid_update_scans_box starts — its refusals, and the pass, group
-    size, tiles, live scans and wide flag for the default RAYCAST option, against literal values."""
+    size, tiles, live scans and wide flag for the default RAYCAST option, and the rounds and kernel launches of the call
+    (counted by hand from the launcher's rules), against literal values."""
     import ctypes
     import icpmi
     from icpmi import _lib
     icpmi.build()
     lib = icpmi.lib()
     ERR_ARG, NONE, OWNER, TILES, ATOMIC = -1, _lib.RC_PASS_NONE, _lib.RC_PASS_OWNER, _lib.RC_PASS_TILES, _lib.RC_PASS_ATOMIC
-    assert ctypes.sizeof(_lib.GridPlan) == 24 and _lib.GridPlan.wide.offset == 20
+    assert ctypes.sizeof(_lib.GridPlan) == 32 and _lib.GridPlan.wide.offset == 20
 
     def call(ny=150, nx=200, res=0.05, off=(0, 2048), have_hits=1, full_clip=0, rows=None, box=(0, 0, 199, 149), out=True, n_scans=None):
         o = np.array(off, dtype=np.int32) if off is not None else None
         b = np.array(box, dtype=np.int32) if box is not None else None
-        plan = _lib.GridPlan(-7, -7, -7, -7, -7, -7)
+        plan = _lib.GridPlan(-7, -7, -7, -7, -7, -7, -7, -7)
         r0, r1 = (0, ny) if rows is None else rows
         code = lib.icpmi_grid_update_plan(ny, nx, res, o.ctypes.data if o is not None else None, len(off) - 1 if n_scans is None else n_scans,
                                           have_hits, full_clip, r0, r1, b.ctypes.data if b is not None else None,
                                           ctypes.byref(plan) if out else None)
-        return code, (plan.pass_, plan.group_max, plan.tiles_x, plan.tiles_y, plan.live_scans, plan.wide)
+        return code, (plan.pass_, plan.group_max, plan.tiles_x, plan.tiles_y, plan.live_scans, plan.wide), (plan.rounds, plan.launches)
 
     # refusals, in the order of icpmi_grid_update_scans_box
     for kw in (dict(out=False), dict(off=None, n_scans=1), dict(ny=0), dict(nx=-1), dict(n_scans=-1), dict(rows=(-1, 10)), dict(rows=(0, 151)),
                dict(rows=(9, 8)), dict(ny=2 ** 29 + 1, rows=(0, 1)), dict(res=0.0), dict(res=float("nan")), dict(off=(0, 10, 5)),
-               dict(have_hits=0)):
+               dict(have_hits=0), dict(off=(0, 2, 4, 6, 5), box=None)):            # the last: a bad count beyond the first group
         assert call(**kw)[0] == ERR_ARG, kw
-    # (pass, group_max, tiles_x, tiles_y, live_scans, wide)
-    rows = [(dict(), (OWNER, 2, 4, 3, 1, 0)),                                          # the live update
-            (dict(rows=(7, 7)), (NONE, 0, 0, 0, 0, 0)),                                 # an empty band starts nothing
-            (dict(full_clip=1), (ATOMIC, 2, 4, 3, 1, 0)),                               # the owner pass does no whole-grid clip
-            (dict(box=None), (ATOMIC, 2, 4, 3, 1, 0)),                                  # no promise about the rays
-            (dict(off=(0, 65535)), (OWNER, 2, 4, 3, 1, 0)), (dict(off=(0, 65536)), (ATOMIC, 2, 4, 3, 1, 1)),
-            (dict(off=(0, 100, 100, 300)), (TILES, 2, 4, 3, 2, 0)),                     # a replay with a box
-            (dict(off=(0, 100, 70000, 70100)), (TILES, 2, 4, 3, 3, 1)),
-            (dict(off=(0, 100, 300), box=(10, 20, 70, 40)), (TILES, 32, 1, 1, 2, 0)),   # a small box: 32 scans a group
-            (dict(off=(0, 100, 300), rows=(40, 97)), (TILES, 5, 4, 1, 2, 0)),           # a band: 200 x 57 cells
-            (dict(off=(0, 100, 300), box=(300, 0, 400, 10)), (ATOMIC, 32, 1, 1, 2, 0)),  # a box beside the grid: an empty window
-            (dict(off=(0, 0, 0)), (ATOMIC, 2, 4, 3, 0, 0)), (dict(off=(0, 0), have_hits=0), (ATOMIC, 2, 4, 3, 0, 0)),
-            (dict(ny=4000, nx=4000, box=(0, 0, 3999, 3999)), (ATOMIC, 2, 63, 63, 1, 0)),   # 3 969 tiles: too many for the owner pass
-            (dict(ny=1200, nx=1200, box=(0, 0, 1199, 1199)), (ATOMIC, 2, 19, 19, 1, 0)),   # 361 > 320
-            (dict(ny=1088, nx=1088, box=(0, 0, 1087, 1087)), (OWNER, 2, 17, 17, 1, 0))]    # 289 tiles
-    for kw, want in rows:
-        code, got = call(**kw)
-        assert code == 0 and got == want, (kw, got)
+    # (pass, group_max, tiles_x, tiles_y, live_scans, wide), (rounds, launches).  A group: the launch that counts it (and finalises
+    # the group before it), one before it for its scan boxes (TILES, several live scans) unless a group went before, one after it to
+    # finalise it unless a group follows; a wide scan: four.
+    five = (0, 10, 20, 30, 40, 50)
+    rows = [(dict(), (OWNER, 2, 4, 3, 1, 0), (1, 1)),                                  # the live update
+            (dict(rows=(7, 7)), (NONE, 0, 0, 0, 0, 0), (0, 0)),                         # an empty band starts nothing
+            (dict(full_clip=1), (ATOMIC, 2, 4, 3, 1, 0), (1, 2)),                       # the owner pass does no whole-grid clip: count + finalise
+            (dict(box=None), (ATOMIC, 2, 4, 3, 1, 0), (1, 2)),                          # no promise about the rays
+            (dict(off=(0, 65535)), (OWNER, 2, 4, 3, 1, 0), (1, 1)), (dict(off=(0, 65536)), (ATOMIC, 2, 4, 3, 1, 1), (1, 4)),
+            (dict(off=(0, 100, 100, 300)), (TILES, 2, 4, 3, 2, 0), (1, 3)),             # a replay with a box: boxes + step + finalise
+            (dict(off=(0, 100, 70000, 70100)), (TILES, 2, 4, 3, 3, 1), (3, 10)),        # a wide scan in the middle: 3 + 4 + 3
+            (dict(off=(0, 70000, 70000, 70010)), (TILES, 2, 4, 3, 2, 1), (2, 7)),       # a wide scan first, a scan without beams: 4 + 3
+            (dict(off=(0, 10, 20, 30, 100000), box=None), (ATOMIC, 2, 4, 3, 4, 1), (3, 7)),   # a wide scan last: 1 + 2 + 4
+            (dict(off=(0, 100, 300), box=(10, 20, 70, 40)), (TILES, 32, 1, 1, 2, 0), (1, 3)),   # a small box: 32 scans a group
+            (dict(off=(0, 100, 300), rows=(40, 97)), (TILES, 5, 4, 1, 2, 0), (1, 3)),   # a band: 200 x 57 cells
+            (dict(off=(0, 100, 300), box=(300, 0, 400, 10)), (ATOMIC, 32, 1, 1, 2, 0), (1, 2)),  # a box beside the grid: an empty window
+            (dict(off=(0, 0, 0)), (ATOMIC, 2, 4, 3, 0, 0), (0, 0)), (dict(off=(0, 0), have_hits=0), (ATOMIC, 2, 4, 3, 0, 0), (0, 0)),
+            (dict(off=five, box=None), (ATOMIC, 2, 4, 3, 5, 0), (3, 4)),                # groups of 2: count + 2 steps + finalise
+            (dict(off=five), (TILES, 2, 4, 3, 5, 0), (3, 5)),                           # boxes once + 3 steps + finalise
+            (dict(ny=4000, nx=4000, box=(0, 0, 3999, 3999)), (ATOMIC, 2, 63, 63, 1, 0), (1, 2)),   # 3 969 tiles: too many for the owner pass
+            (dict(ny=1200, nx=1200, box=(0, 0, 1199, 1199)), (ATOMIC, 2, 19, 19, 1, 0), (1, 2)),   # 361 > 320
+            (dict(ny=1088, nx=1088, box=(0, 0, 1087, 1087)), (OWNER, 2, 17, 17, 1, 0), (1, 1))]    # 289 tiles
+    for kw, want, issued in rows:
+        code, got, got_issued = call(**kw)
+        assert code == 0 and got == want and got_issued == issued, (kw, got, got_issued)
 
 
 def test_the_four_pair_entries_judge_a_bad_pair_list_alike():

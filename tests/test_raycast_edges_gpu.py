@@ -146,6 +146,31 @@ def test_replay_arithmetic(umap, raypath, case, start):
     _note("arith", case.name, raypath, g.log_odds)
 
 
+# ── a refusal comes before the first launch ─────────────────────────────────────────────────────────────────────────────
+def test_a_bad_last_scan_is_refused_before_anything_is_started(umap, raypath):
+    """Four scans of two beams inside an 8 x 8 grid, no box (groups of two), and offsets whose LAST count is negative: the
+    entry refuses the call as a whole, so the grid keeps its start values bit for bit and the workspace stays all zero (a
+    refusal met after the first group was counted left its counters and a box slot behind).  All 8 rows of `hits` exist, so
+    whatever reads them reads inside the allocation."""
+    import torch
+    import icpmi
+    L = icpmi.lib()
+    rng = np.random.default_rng(23)
+    start = torch.from_numpy(rng.uniform(-4.0, 4.0, size=(8, 8)).astype(np.float32)).cuda()
+    grid = start.clone()
+    ws = torch.zeros(L.icpmi_grid_workspace_bytes(8, 8), dtype=torch.uint8, device="cuda")
+    origins = torch.from_numpy(rng.uniform(1.0, 7.0, size=(4, 2))).cuda()
+    hits = torch.from_numpy(rng.uniform(1.0, 7.0, size=(8, 2))).cuda()
+    off = np.array([0, 2, 4, 6, 5], dtype=np.int32)
+    code = L.icpmi_grid_update_scans_box(grid.data_ptr(), ws.data_ptr(), 8, 8, 0.0, 0.0, 1.0, origins.data_ptr(), hits.data_ptr(),
+                                         off.ctypes.data, 4, 0.9, -0.4, -8.0, 8.0, 0, 0, 0, 8, None,
+                                         torch._C._cuda_getCurrentRawStream(grid.device.index))
+    torch.cuda.synchronize()
+    assert code == -1                                                    # ICPMI_ERR_ARG
+    assert torch.equal(grid.view(torch.int32), start.view(torch.int32)), "a refused call wrote the grid"
+    assert int(ws.count_nonzero()) == 0, "a refused call left counts or a box in the workspace"
+
+
 # ── the three passes agree: a failure above names the pass, this one names the family ───────────────────────────────────
 @pytest.mark.parametrize("family", ["live", "band", "replay", "counter", "arith"])
 def test_the_three_passes_wrote_the_same_bytes(family):
