@@ -1203,7 +1203,7 @@ int icpmi_grid_beam_batch(const int16_t* field, const void* planes, int32_t ny, 
  * Random numbers: Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; the Random123
  * constants M0 = 0xD2511F53, M1 = 0xCD9E8D57, W0 = 0x9E3779B9, W1 = 0xBB67AE85), counter-based, no state.  The key is
  * (seed & 0xffffffff, seed >> 32); the counter is [particle, block, step, purpose], purpose ICPMI_PF_PURPOSE_PREDICT or
- * ICPMI_PF_PURPOSE_RESAMPLE.  A round maps the counter (c0, c1, c2, c3) under the key (k0, k1) to (hi(M1 c2) ^ c1 ^ k0,
+ * ICPMI_PF_PURPOSE_RESAMPLE (or ICPMI_PFG_PURPOSE_UNIFORM, below).  A round maps the counter (c0, c1, c2, c3) under the key (k0, k1) to (hi(M1 c2) ^ c1 ^ k0,
  * lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)); ten rounds, the key raised by (W0, W1) between them.
  * Normal deviates without a transcendental function: particle i takes blocks 0 .. ICPMI_PF_PREDICT_BLOCKS - 1, 20 words in
  * order, each word as two 16-bit halves, the low one first: 40 halves.  Deviate m (m = 0, 1, 2) is z_m = (S_m - 393210) *
@@ -1289,6 +1289,66 @@ int icpmi_pf_resample(int32_t n, const uint32_t* w, const double* pair_t, const 
 int icpmi_pf_estimate(int32_t n, const uint32_t* w, const double* pair_t, const double* cos_sin, double* out, void* workspace,
                       size_t workspace_bytes, void* stream);
 size_t icpmi_pf_workspace_bytes(int32_t n);
+
+/* ---- the particle filter: a start over the map's free cells, recovery by injection (ICPMI_PFG_*: "global") ---------------
+ * Poses drawn uniformly from the map's free space, on the device: once for the whole population (a start without a prior)
+ * and after a resampling for a share of it (random injection, the recovery of augmented MCL).  A draw is a function of
+ * (planes, box, seed, step) to the bit.  No entry synchronises.
+ *
+ * Free cell: a cell inside the grid whose bit is clear in BOTH planes of icpmi_grid_occupancy_planes — neither occupied nor
+ * unknown — and that lies inside the cell box [x0, x1) x [y0, y1).  The box is clipped to the grid; a box that is empty
+ * after clipping is legal and has no free cell.  The pad bits of a row's last word are never free.
+ *
+ * Free index: with words = ny * wpr in the planes' row-major word order, the index buffer (device, 16-byte aligned,
+ * icpmi_pf_free_index_bytes(ny, nx) bytes) holds uint32 header [ICPMI_PFG_FREE_HEADER] = [F, words, wpr, 0 ...]; then, each
+ * from the next multiple of 256 bytes on, free [words]: the masked free word of every plane word; rank [words]: the
+ * exclusive prefix sum of popcount(free[.]); and the ceil(words / ICPMI_PFG_FREE_BLOCK) block sums the build scans (its
+ * scratch).  F is the total, below 2^31.  The index is a function of (planes, box) to the bit.
+ *
+ * icpmi_pf_free_index — builds the index of `planes` (what icpmi_grid_occupancy_planes wrote for this ny, nx).
+ * Refusals, on the host before anything is enqueued, in this order: the grid as icpmi_grid_occupancy_planes refuses it (ny
+ * or nx negative or above 2^29, ny * nx >= 2^31): ICPMI_ERR_ARG; words > ICPMI_PFG_FREE_MAX_WORDS: ICPMI_ERR_UNSUPPORTED;
+ * planes NULL or not 16-byte aligned where words > 0: ICPMI_ERR_ARG; an index that is NULL, not 16-byte aligned or below
+ * icpmi_pf_free_index_bytes(ny, nx): ICPMI_ERR_WORKSPACE.  x0, y0, x1, y1 are any int32: each is clipped into
+ * [0, nx] or [0, ny] on the host, and the kernels see no other value.
+ * Launches, none of which waits on another workgroup: pf_free_sums_kernel (a workgroup per ICPMI_PFG_FREE_BLOCK words: the
+ * free cells among them), pf_free_scan_kernel (ONE workgroup: the exclusive scan of up to ICPMI_PFG_FREE_MAX_WORDS /
+ * ICPMI_PFG_FREE_BLOCK block sums, ICPMI_PF_SUMS_PER_LANE consecutive sums per lane; the header) and pf_free_write_kernel (a
+ * workgroup per block scans it again from its offset and stores free and rank).  words == 0: the header alone.
+ *
+ * icpmi_pf_draw_uniform — of n slots, m are drawn, 0 <= m <= n: slot j iff ((j + 1) * m) div n > (j * m) div n in 64-bit
+ * integers, which is exactly m slots, spread evenly (m == n: every slot).  The other slots are not touched.  Slot j at
+ * (seed, step): r = Philox4x32-10 at the counter [j, 0, step, ICPMI_PFG_PURPOSE_UNIFORM] under the filter's key;
+ *   k = (uint64(r0) * F) >> 32;  J = the largest word index with rank[J] <= k;  bit = the (k - rank[J])-th set bit of
+ *   free[J], counted from bit 0;  cx = 32 * (J mod wpr) + bit,  cy = J div wpr;
+ *   ux = (double(r1 >> 8) + 0.5) * 2^-24,  uy the same from r2;
+ *   x = min_x + (double(cx) + ux) * resolution,  y = min_y + (double(cy) + uy) * resolution;
+ *   theta = theta0 + ((double(r3) + 0.5) * 2^-32 - 0.5) * theta_span, not wrapped;
+ * float64, every operation rounded on its own (no fused multiply-add); cos_sin by the device library's sincos of theta.
+ * pair_t, theta, cos_sin: the filter's state arrays.  ancestors: device, int32 [n], or NULL; a drawn slot gets
+ * ICPMI_PFG_INJECTED.  info: device, int32 [ICPMI_PF_INFO_INTS] = [status, F, 0, 0]; with F == 0 the status is
+ * ICPMI_PFG_ST_NO_FREE and nothing else is written.
+ * Refusals, in this order: n as for icpmi_pf_predict (n == 0: ICPMI_OK, nothing done); m outside [0, n]; index, pair_t,
+ * theta, cos_sin or info NULL, index, pair_t or cos_sin not 16-byte aligned, theta not 8-byte aligned; a resolution that is
+ * not positive and finite, a theta_span outside [0, 2 pi], a theta0, min_x or min_y that is not finite: ICPMI_ERR_ARG.
+ * Launches: pf_draw_uniform_kernel, a lane per slot.  The search over rank is a bisection of at most 23 steps over
+ * [0, words), words read from the header and clamped to [1, ICPMI_PFG_FREE_MAX_WORDS]; the bit select takes at most 32
+ * steps: an index of stale or zero bytes yields wrong particles or ICPMI_PFG_ST_NO_FREE, never an address outside the
+ * buffers of an index that was once built there.
+ *
+ * icpmi_pf_free_index_bytes(ny, nx): the index buffer's size; 0 for a grid icpmi_pf_free_index refuses. */
+#define ICPMI_PFG_PURPOSE_UNIFORM 2
+#define ICPMI_PFG_FREE_HEADER 64
+#define ICPMI_PFG_FREE_BLOCK 4096
+#define ICPMI_PFG_FREE_MAX_WORDS 4194304
+#define ICPMI_PFG_INJECTED (-1)
+#define ICPMI_PFG_ST_NO_FREE 2
+size_t icpmi_pf_free_index_bytes(int32_t ny, int32_t nx);
+int icpmi_pf_free_index(const void* planes, int32_t ny, int32_t nx, int32_t x0, int32_t y0, int32_t x1, int32_t y1, void* index,
+                        size_t index_bytes, void* stream);
+int icpmi_pf_draw_uniform(int32_t n, int32_t m, const void* index, double min_x, double min_y, double resolution, double theta0,
+                          double theta_span, double* pair_t, double* theta, double* cos_sin, int32_t* ancestors, int32_t* info,
+                          uint64_t seed, uint32_t step, void* stream);
 
 /* ── pose graph: PoseGraph2D.optimize, utilities/pose_graph.py:83-134 ──────────
  * Gauss-Newton on SE(2) over n_nodes poses [x, y, theta] (nodes: device, updated

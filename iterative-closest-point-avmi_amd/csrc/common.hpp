@@ -59,7 +59,7 @@ int launch_icp2(const double* pts, const int32_t* off, const int32_t* cnt, const
                 hipStream_t st);
 
 // ── carving a caller's buffer (host) ─────────────────────────────────────────
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+__host__ __device__ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Rows of the clouds of a set, from the host mirror of its offsets: false when a cloud has a negative row count.  With a
 // `limit` (and a counter), max_n is the largest cloud at or below it and *n_above counts the clouds above it.
@@ -81,17 +81,18 @@ inline bool cloud_rows(const int32_t* off_host, int n_clouds, int& max_n, int& t
 // 256; packed<T>(bytes) moves on by exactly `bytes` (the layouts that keep no gaps).  Every layout is described ONCE, by a
 // struct whose first member is a Carve and whose pointers are initialised from it, in the order they are declared (which
 // is the order of the layout).  Over a null base it only counts (every pointer is nullptr): that is the layout's *_bytes
-// query; over the caller's buffer it yields the pointers the launcher uses.
+// query; over the caller's buffer it yields the pointers the launcher uses.  (Host and device: a kernel that is handed a
+// buffer alone — the free index of particles.hpp — finds its parts by the same description.)
 struct Carve {
     unsigned char* base;
     size_t off = 0;
-    Carve(void* b) : base((unsigned char*)b) {}
-    template <class T> T* packed(size_t bytes) {
+    __host__ __device__ Carve(void* b) : base((unsigned char*)b) {}
+    template <class T> __host__ __device__ T* packed(size_t bytes) {
         T* p = base ? (T*)(base + off) : nullptr;
         off += bytes;
         return p;
     }
-    template <class T> T* take(size_t bytes) { return packed<T>(align256(bytes)); }
+    template <class T> __host__ __device__ T* take(size_t bytes) { return packed<T>(align256(bytes)); }
 };
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (ICPMI_WAVE - 1); }

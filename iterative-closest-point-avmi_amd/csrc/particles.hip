@@ -1,5 +1,5 @@
 // particles.hip — the particle filter on the occupancy grid (include/icpmi.h: icpmi_pf_predict, icpmi_pf_weights,
-// icpmi_pf_resample, icpmi_pf_estimate, icpmi_pf_workspace_bytes).  The particles stay on the device in the layout the
+// icpmi_pf_resample, icpmi_pf_estimate, icpmi_pf_workspace_bytes, icpmi_pf_free_index, icpmi_pf_draw_uniform).  The particles stay on the device in the layout the
 // beam model takes its poses in (gridbeam.hip reads them where they are); this file moves them, turns the beam model's
 // records into integer weights, resamples by an integer prefix sum and adds the weighted moments in a fixed order.
 //   pf_predict_kernel       a lane per particle: three deviates from Philox (particles.hpp), the motion model, sincos;
@@ -11,7 +11,12 @@
 //                           again from their offsets — so no workgroup waits on another inside a launch; E_i per particle,
 //                           then a lane per new particle bisects E for its ancestor and copies the state;
 //   pf_moments_kernel, pf_moments_sum_kernel
-//                           per-workgroup partial sums by the fixed tree of common.hpp, combined in index order.
+//                           per-workgroup partial sums by the fixed tree of common.hpp, combined in index order;
+//   pf_free_sums_kernel, pf_free_scan_kernel, pf_free_write_kernel
+//                           icpmi_pf_free_index: the map's free cells as masked words and their ranks — the same chain of
+//                           launches as the resampling's prefix sum, over the words of the bit planes;
+//   pf_draw_uniform_kernel  icpmi_pf_draw_uniform: a lane per slot draws a free cell by its rank (a bounded bisection, a
+//                           bounded bit select), a point inside it and a heading.
 #include "particles.hpp"
 
 namespace icpmi {
@@ -254,7 +259,200 @@ __global__ __launch_bounds__(ICPMI_WAVE) void pf_moments_sum_kernel(int chunks, 
     out[threadIdx.x] = s;
 }
 
+// ── the free index ───────────────────────────────────────────────────────────
+struct PfFreeArgs {
+    const uint32_t* occ;      // the two planes (gridcast.hpp: GcPlanes)
+    const uint32_t* unk;
+    unsigned words;
+    int wpr;
+    int x0, y0, x1, y1;       // the box, every end clipped into the grid by plan_free_index: 0 <= x0, x1 <= nx (which keeps a
+                              // row's pad bits out, and x - 32 wx inside int), 0 <= y0, y1 <= ny
+};
+
+// the bits of word wx of row y that lie inside the box
+__device__ __forceinline__ uint32_t pf_box_mask(const PfFreeArgs& a, int y, int wx) {
+    if (y < a.y0 || y >= a.y1) return 0u;
+    const int lo = min(max(a.x0 - 32 * wx, 0), 32), hi = min(max(a.x1 - 32 * wx, 0), 32);
+    if (hi <= lo) return 0u;                                   // (so lo < 32)
+    return (hi == 32 ? ~0u : (1u << hi) - 1u) & ~((1u << lo) - 1u);
+}
+
+// The lane's PF_FREE_LANE_WORDS consecutive free words of scan block `block` (0 behind the last word).  Four words are one
+// 16-byte load of each plane; the last group of a plane may reach past `words`, into the plane's padding to 256 bytes,
+// and what it finds there is dropped.
+__device__ __forceinline__ void pf_lane_free(const PfFreeArgs& a, unsigned block, uint32_t (&v)[PF_FREE_LANE_WORDS], unsigned& first) {
+    first = block * ICPMI_PFG_FREE_BLOCK + threadIdx.x * PF_FREE_LANE_WORDS;
+    int y = (int)(first / (unsigned)a.wpr), wx = (int)(first - (unsigned)y * (unsigned)a.wpr);
+#pragma unroll
+    for (int g = 0; g < PF_FREE_LANE_WORDS / 4; ++g) {
+        const unsigned t = first + 4 * g;
+        uint4 o = make_uint4(~0u, ~0u, ~0u, ~0u), u = o;
+        if (t < a.words) {
+            o = *reinterpret_cast<const uint4*>(a.occ + t);
+            u = *reinterpret_cast<const uint4*>(a.unk + t);
+        }
+        const uint32_t f[4] = {~(o.x | u.x), ~(o.y | u.y), ~(o.z | u.z), ~(o.w | u.w)};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            v[4 * g + q] = t + q < a.words ? f[q] & pf_box_mask(a, y, wx) : 0u;
+            if (++wx == a.wpr) {
+                wx = 0;
+                ++y;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(PF_THREADS) void pf_free_sums_kernel(PfFreeArgs a, uint32_t* block_sums) {
+    __shared__ unsigned long long wave_tot[PF_WAVES];
+    uint32_t v[PF_FREE_LANE_WORDS];
+    unsigned first;
+    pf_lane_free(a, blockIdx.x, v, first);
+    unsigned long long mine = 0, all;
+#pragma unroll
+    for (int k = 0; k < PF_FREE_LANE_WORDS; ++k) mine += (unsigned)__popc(v[k]);
+    block_exclusive(mine, wave_tot, all);
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = (uint32_t)all;             // at most 32 * ICPMI_PFG_FREE_BLOCK
+}
+
+// ONE workgroup, as pf_scan_sums_kernel: lane t owns sums ICPMI_PF_SUMS_PER_LANE t ... (at most PF_FREE_MAX_BLOCKS in all)
+__global__ __launch_bounds__(PF_THREADS) void pf_free_scan_kernel(int blocks, uint32_t* block_sums, uint32_t* header, unsigned words, int wpr) {
+    __shared__ unsigned long long wave_tot[PF_WAVES];
+    unsigned long long v[ICPMI_PF_SUMS_PER_LANE], mine = 0, all;
+    const int first = threadIdx.x * ICPMI_PF_SUMS_PER_LANE;
+#pragma unroll
+    for (int k = 0; k < ICPMI_PF_SUMS_PER_LANE; ++k) {
+        v[k] = first + k < blocks ? block_sums[first + k] : 0ull;
+        mine += v[k];
+    }
+    unsigned long long run = block_exclusive(mine, wave_tot, all);
+#pragma unroll
+    for (int k = 0; k < ICPMI_PF_SUMS_PER_LANE; ++k) {
+        if (first + k < blocks) block_sums[first + k] = (uint32_t)run;
+        run += v[k];
+    }
+    if (threadIdx.x < ICPMI_PFG_FREE_HEADER)                     // F = all < 2^31: a grid has fewer cells
+        header[threadIdx.x] = threadIdx.x == 0 ? (uint32_t)all : threadIdx.x == 1 ? words : threadIdx.x == 2 ? (uint32_t)wpr : 0u;
+}
+
+__global__ __launch_bounds__(PF_THREADS) void pf_free_write_kernel(PfFreeArgs a, const uint32_t* block_sums, uint32_t* free, uint32_t* rank) {
+    __shared__ unsigned long long wave_tot[PF_WAVES];
+    uint32_t v[PF_FREE_LANE_WORDS];
+    unsigned first;
+    pf_lane_free(a, blockIdx.x, v, first);
+    unsigned long long mine = 0, all;
+#pragma unroll
+    for (int k = 0; k < PF_FREE_LANE_WORDS; ++k) mine += (unsigned)__popc(v[k]);
+    uint32_t C = block_sums[blockIdx.x] + (uint32_t)block_exclusive(mine, wave_tot, all);
+    // groups of four again: the last one may reach past `words`, into the padding of free and rank to 256 bytes
+#pragma unroll
+    for (int g = 0; g < PF_FREE_LANE_WORDS / 4; ++g) {
+        uint32_t r[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            r[q] = C;
+            C += (uint32_t)__popc(v[4 * g + q]);
+        }
+        const unsigned t = first + 4 * g;
+        if (t < a.words) {
+            *reinterpret_cast<uint4*>(free + t) = make_uint4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
+            *reinterpret_cast<uint4*>(rank + t) = make_uint4(r[0], r[1], r[2], r[3]);
+        }
+    }
+}
+
+// ── the draw ─────────────────────────────────────────────────────────────────
+// A lane per slot.  Everything read from the index is bounded: words to [1, ICPMI_PFG_FREE_MAX_WORDS], the bisection to 23
+// steps inside [0, words), the bit select to 32 steps and a bit below 32 — an index of stale or zero bytes gives wrong
+// particles or NO_FREE, and no address outside the index.
+__global__ __launch_bounds__(PF_THREADS) void pf_draw_uniform_kernel(int n, int m, const void* index, double min_x, double min_y, double res,
+                                                                     double theta0, double span, double2* pair_t, double* theta, double2* cos_sin,
+                                                                     int32_t* ancestors, int32_t* info, uint64_t seed, uint32_t step) {
+    const unsigned j = blockIdx.x * PF_THREADS + threadIdx.x;
+    const uint32_t* header = reinterpret_cast<const uint32_t*>(index);
+    const uint32_t F = header[0];
+    const unsigned words = min(max(header[1], 1u), (unsigned)ICPMI_PFG_FREE_MAX_WORDS), wpr = max(header[2], 1u);
+    if (j < ICPMI_PF_INFO_INTS) info[j] = j == 0 ? (F ? ICPMI_PF_ST_OK : ICPMI_PFG_ST_NO_FREE) : j == 1 ? (int32_t)F : 0;
+    if (j >= (unsigned)n || F == 0u) return;
+    const unsigned long long jm = (unsigned long long)j * (unsigned)m;
+    if ((jm + (unsigned)m) / (unsigned)n == jm / (unsigned)n) return;          // not one of the m slots
+    const PfFreeIndex ix(const_cast<void*>(index), words);
+    const Philox r = pf_draw(seed, j, 0u, step, ICPMI_PFG_PURPOSE_UNIFORM);
+    const uint32_t k = (uint32_t)(((unsigned long long)r.v[0] * F) >> 32);     // < F
+    unsigned lo = 0, hi = words - 1;                           // the largest J with rank[J] <= k lies in [lo, hi] (rank[0] = 0)
+    for (int it = 0; it < 23 && lo < hi; ++it) {
+        const unsigned mid = lo + ((hi - lo + 1) >> 1);
+        if (ix.rank[mid] <= k) lo = mid;
+        else hi = mid - 1;
+    }
+    uint32_t fw = ix.free[lo];
+    const uint32_t skip = k - ix.rank[lo];
+    for (uint32_t s = 0; s < 32u && s < skip; ++s) fw &= fw - 1u;              // drop the set bits below the one drawn
+    const int bit = fw ? __ffs((int)fw) - 1 : 31;
+    const unsigned cy = lo / wpr, cx = 32u * (lo - cy * wpr) + (unsigned)bit;
+    const double ux = ((double)(r.v[1] >> 8) + 0.5) * (1.0 / 16777216.0), uy = ((double)(r.v[2] >> 8) + 0.5) * (1.0 / 16777216.0);
+    const double th = theta0 + (((double)r.v[3] + 0.5) * (1.0 / 4294967296.0) - 0.5) * span;
+    double s, c;
+    sincos(th, &s, &c);
+    pair_t[j] = make_double2(min_x + ((double)cx + ux) * res, min_y + ((double)cy + uy) * res);
+    theta[j] = th;
+    cos_sin[j] = make_double2(c, s);
+    if (ancestors) ancestors[j] = ICPMI_PFG_INJECTED;
+}
+
 }  // namespace icpmi
+
+extern "C" size_t icpmi_pf_free_index_bytes(int32_t ny, int32_t nx) {
+    const icpmi::PfFreePlan plan = icpmi::plan_free_index(ny, nx, 0, 0, nx, ny);
+    return plan.rc == ICPMI_OK ? plan.index_bytes : 0;
+}
+
+extern "C" int icpmi_pf_free_index(const void* planes, int32_t ny, int32_t nx, int32_t x0, int32_t y0, int32_t x1, int32_t y1, void* index,
+                                   size_t index_bytes, void* stream) {
+    using namespace icpmi;
+    const PfFreePlan plan = plan_free_index(ny, nx, x0, y0, x1, y1);
+    if (plan.rc != ICPMI_OK) return plan.rc;
+    if (plan.words && (!planes || misaligned16(planes))) return ICPMI_ERR_ARG;
+    if (!index || misaligned16(index) || index_bytes < plan.index_bytes) return ICPMI_ERR_WORKSPACE;
+    const PfFreeIndex ix(index, plan.words);
+    const GcPlanes L(ny, nx);
+    const unsigned char* base = reinterpret_cast<const unsigned char*>(planes);
+    const PfFreeArgs a{reinterpret_cast<const uint32_t*>(base + L.occ), reinterpret_cast<const uint32_t*>(base + L.unk), plan.words, plan.wpr,
+                       plan.x0, plan.y0, plan.x1, plan.y1};
+    const hipStream_t st = (hipStream_t)stream;
+    if (plan.blocks) {
+        pf_free_sums_kernel<<<plan.blocks, PF_THREADS, 0, st>>>(a, ix.block_sums);
+        ICPMI_LAUNCH_CHECK();
+    }
+    pf_free_scan_kernel<<<1, PF_THREADS, 0, st>>>((int)plan.blocks, ix.block_sums, ix.header, plan.words, plan.wpr);
+    ICPMI_LAUNCH_CHECK();
+    if (plan.blocks) {
+        pf_free_write_kernel<<<plan.blocks, PF_THREADS, 0, st>>>(a, ix.block_sums, ix.free, ix.rank);
+        ICPMI_LAUNCH_CHECK();
+    }
+    return ICPMI_OK;
+}
+
+extern "C" int icpmi_pf_draw_uniform(int32_t n, int32_t m, const void* index, double min_x, double min_y, double resolution, double theta0,
+                                     double theta_span, double* pair_t, double* theta, double* cos_sin, int32_t* ancestors, int32_t* info,
+                                     uint64_t seed, uint32_t step, void* stream) {
+    using namespace icpmi;
+    const PfPlan plan = plan_particles(n);
+    if (plan.rc != ICPMI_OK || plan.nothing) return plan.rc;
+    if (m < 0 || m > n) return ICPMI_ERR_ARG;
+    if (!index || !pair_t || !theta || !cos_sin || !info || misaligned16(index) || misaligned16(pair_t) || misaligned16(cos_sin) ||
+        misaligned8(theta))
+        return ICPMI_ERR_ARG;
+    const double inf = __builtin_inf();
+    for (double v : {min_x, min_y, resolution, theta0, theta_span})
+        if (!(fabs(v) < inf)) return ICPMI_ERR_ARG;
+    if (!(resolution > 0.0) || theta_span < 0.0 || theta_span > 6.283185307179586) return ICPMI_ERR_ARG;
+    pf_draw_uniform_kernel<<<plan.lanes_grid, PF_THREADS, 0, (hipStream_t)stream>>>(
+        n, m, index, min_x, min_y, resolution, theta0, theta_span, reinterpret_cast<double2*>(pair_t), theta, reinterpret_cast<double2*>(cos_sin),
+        ancestors, info, seed, step);
+    ICPMI_LAUNCH_CHECK();
+    return ICPMI_OK;
+}
 
 extern "C" size_t icpmi_pf_workspace_bytes(int32_t n) {
     const icpmi::PfPlan plan = icpmi::plan_particles(n);

@@ -1,6 +1,7 @@
 // particles.hpp — what the particle filter's kernels and its host entries share (particles.hip; include/icpmi.h: icpmi_pf_*):
-// the counter-based generator and the deviates made of its halves, for the host and the device alike; the workspace, once;
-// and the host plan: what each entry starts, decided as a whole and without a HIP call (the idiom of gridpairs.hpp).
+// the counter-based generator and the deviates made of its halves, for the host and the device alike; the workspace and the
+// free index, each once; and the host plans: what each entry starts, decided as a whole and without a HIP call (the idiom
+// of gridpairs.hpp).
 #pragma once
 #include "gridcast.hpp"
 
@@ -88,6 +89,57 @@ inline PfPlan plan_particles(int n) {
     p.ws_bytes = PfWs(nullptr, (int)p.blocks, (int)p.chunks, n).bytes();
     return p;
 }
+// ── the free index of icpmi_pf_free_index, described once: the host sizes and carves it, the draw finds its parts from the
+// header's `words` alone ─────────────────────────────────────────────────────
+constexpr int PF_FREE_LANE_WORDS = ICPMI_PFG_FREE_BLOCK / PF_THREADS;         // consecutive words of a lane in a scan block
+constexpr int PF_FREE_MAX_BLOCKS = ICPMI_PFG_FREE_MAX_WORDS / ICPMI_PFG_FREE_BLOCK;
+static_assert(ICPMI_PFG_FREE_BLOCK % (4 * PF_THREADS) == 0, "a lane's words are whole groups of four");
+static_assert(PF_FREE_MAX_BLOCKS == PF_THREADS * ICPMI_PF_SUMS_PER_LANE, "one workgroup scans every block sum of the largest index");
+static_assert(ICPMI_PFG_FREE_MAX_WORDS == (1 << 22), "the draw's bisection: 22 halvings, at most 23 steps");
+static_assert(ICPMI_PFG_FREE_HEADER >= 3 && ICPMI_PFG_FREE_HEADER <= ICPMI_WAVE, "one wave writes the header");
+
+struct PfFreeIndex {
+    Carve c;
+    uint32_t* header;         // [ICPMI_PFG_FREE_HEADER]: F, words, wpr, 0 ...
+    uint32_t* free;           // [words]: the masked free word of every plane word
+    uint32_t* rank;           // [words]: the free cells in the words before it
+    uint32_t* block_sums;     // [blocks]: the build's scratch — the free cells of each scan block, then of the blocks before it
+    __host__ __device__ static unsigned blocks_of(size_t words) { return (unsigned)((words + ICPMI_PFG_FREE_BLOCK - 1) / ICPMI_PFG_FREE_BLOCK); }
+    __host__ __device__ PfFreeIndex(void* base, size_t words)
+        : c(base), header(c.take<uint32_t>(ICPMI_PFG_FREE_HEADER * sizeof(uint32_t))), free(c.take<uint32_t>(words * sizeof(uint32_t))),
+          rank(c.take<uint32_t>(words * sizeof(uint32_t))), block_sums(c.take<uint32_t>(blocks_of(words) * sizeof(uint32_t))) {}
+    __host__ __device__ size_t bytes() const { return c.off; }
+};
+
+// What icpmi_pf_free_index starts, decided as a whole and without a HIP call
+struct PfFreePlan {
+    int rc;                   // ICPMI_OK, or why nothing is launched
+    int wpr;
+    unsigned words, blocks;   // blocks == 0 (an empty grid): the header alone
+    int x0, y0, x1, y1;       // the box clipped to the grid; x1 <= x0 or y1 <= y0: empty
+    size_t plane_bytes, index_bytes;
+};
+inline PfFreePlan plan_free_index(int ny, int nx, int x0, int y0, int x1, int y1) {
+    PfFreePlan p{ICPMI_OK, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const GcPlan grid = plan_cast(ny, nx, 0, 0);
+    if (grid.rc != ICPMI_OK) { p.rc = grid.rc; return p; }
+    const GcPlanes L(ny, nx);
+    if (L.words > (size_t)ICPMI_PFG_FREE_MAX_WORDS) { p.rc = ICPMI_ERR_UNSUPPORTED; return p; }
+    p.wpr = L.wpr;
+    p.words = (unsigned)L.words;
+    p.blocks = PfFreeIndex::blocks_of(L.words);
+    // both ends of both axes into the grid: the kernels only ever see 0 <= x0, x1 <= nx and 0 <= y0, y1 <= ny, so their
+    // mask arithmetic stays far from the ends of int whatever int32 the caller passed
+    const auto into = [](int v, int n) { return v < 0 ? 0 : (v > n ? n : v); };
+    p.x0 = into(x0, nx);
+    p.y0 = into(y0, ny);
+    p.x1 = into(x1, nx);
+    p.y1 = into(y1, ny);
+    p.plane_bytes = L.bytes;
+    p.index_bytes = PfFreeIndex(nullptr, L.words).bytes();
+    return p;
+}
+
 inline bool misaligned8(const void* p) { return ((uintptr_t)p & 7) != 0; }
 inline int pf_workspace_rc(const PfPlan& plan, const void* workspace, size_t workspace_bytes) {
     return !workspace || misaligned16(workspace) || workspace_bytes < plan.ws_bytes ? ICPMI_ERR_WORKSPACE : ICPMI_OK;

@@ -29,8 +29,8 @@ def __getattr__(name):
         import importlib
         information = importlib.import_module(".information", __name__)
         return information if name == "information" else getattr(information, name)
-    # icpmi.particles, icpmi.ParticleFilter and icpmi.weight_table, the same way
-    if name in ("particles", "ParticleFilter", "weight_table"):
+    # icpmi.particles, icpmi.ParticleFilter, icpmi.Recovery and icpmi.weight_table, the same way
+    if name in ("particles", "ParticleFilter", "Recovery", "weight_table"):
         import importlib
         particles = importlib.import_module(".particles", __name__)
         return particles if name == "particles" else getattr(particles, name)

@@ -645,7 +645,9 @@ class OccupancyGrid2D:
     def particle_filter(self, n, **kw):
         """An ``icpmi.particles.ParticleFilter`` of ``n`` particles bound to this grid: localisation in the map as it is now
         (its bit planes are packed once; ``refresh_map()`` after the grid has changed).  ``kw``: ``seed``, ``temperature`` and
-        the beam model's ``sigma``, ``half_width``, ``beyond``, ``table``, ``occupied_log_odds``, ``field``, ``planes``."""
+        the beam model's ``sigma``, ``half_width``, ``beyond``, ``table``, ``occupied_log_odds``, ``field``, ``planes``.  The
+        filter starts about a known pose (``init_gaussian``) or over the free cells of this map (``init_uniform``, ``free_cells``)
+        and recovers by injection (``resample(inject=)``, ``maybe_resample(recovery=)``)."""
         from icpmi.particles import ParticleFilter
         return ParticleFilter(self, n, **kw)
 

@@ -18,7 +18,22 @@ A sample is BLOCK runs back to back between two events, divided by BLOCK (2 for 
 SAMPLES samples per variant after a warm-up of each.  `beam_again` samples the yardstick twice: |median(beam) -
 median(beam_again)| is the run-to-run spread a difference has to exceed.  No hardware counters are collected.
 
-usage: time_particles.py [samples] [block]   (prints one JSON line)"""
+With --global the same grid serves the start over the free cells and the recovery by injection instead (icpmi_pf_free_index,
+icpmi_pf_draw_uniform):
+
+  (index)   the free index of the whole grid, built again into its buffer (FreeCells.build: three launches);
+  (draw_n)  every one of n = 4 096, 65 536 and 2^20 slots drawn from it;
+  (step, step_inject)
+            per N = 4 096 and 65 536, the five-stage step above and the same step with n / 4 slots of the resampled
+            generation drawn anew, ancestors marked;
+  (host_start)
+            what the parent of this feature could offer for a start: the field read back, np.nonzero of its free cells,
+            NumPy draws and ParticleFilter.set_poses, at n = 4 096;
+
+and, once and without a clock, a whole-map start in the room map of the test suite (200 x 280 cells at 0.1 m, twelve scans
+of 64 rows) at 2^18 particles over the full circle: the error of the estimate at every scan.
+
+usage: time_particles.py [--global] [samples] [block]   (prints one JSON line)"""
 import json
 import sys
 
@@ -29,8 +44,10 @@ import torch
 from icpmi import _lib, gridmatch, synth
 from icpmi.batch import _ptr, _stream
 
-SAMPLES = int(sys.argv[1]) if len(sys.argv) > 1 else 21
-BLOCK = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+GLOBAL = "--global" in sys.argv[1:]
+ARGS = [a for a in sys.argv[1:] if a != "--global"]
+SAMPLES = int(ARGS[0]) if len(ARGS) > 0 else 21
+BLOCK = int(ARGS[1]) if len(ARGS) > 1 else 20
 SIZES, ROWS, HALF_WIDTH, TEMPERATURE = (4096, 512, 65536), 360, 8, 8.0
 CONTROL, MOTION = (0.02, 0.0, 0.005), (0.01, 0.01, 0.002)
 
@@ -85,6 +102,17 @@ def variants_of(n):
         resample()
         estimate()
 
+    if GLOBAL:
+        # (as the resampled generation, the injected slots go to the spare buffers)
+        inject = call(L.icpmi_pf_draw_uniform, n, n // 4, _ptr(pf.free_cells().index), grid.min_x, grid.min_y, grid.resolution, 0.0, 2.0 * np.pi,
+                      _ptr(spare[0]), _ptr(spare[1]), _ptr(spare[2]), _ptr(pf.ancestors), _ptr(pf.draw_info), pf.seed, 2, st)
+
+        def step_inject():
+            step()
+            inject()
+
+        return {"step": (step, BLOCK), "step_inject": (step_inject, BLOCK), "step_again": (step, BLOCK)}, (pf,)
+
     own = grid.particle_filter(n, seed=n + 1, temperature=TEMPERATURE, half_width=HALF_WIDTH, planes=planes)
     own.init_gaussian(start, (0.2, 0.2, 0.05))
 
@@ -119,8 +147,77 @@ def variants_of(n):
             "step": (step, BLOCK), "filter": (filter_step, 2), "host": (host_step, 2), "beam_again": (beam, BLOCK)}, (pf, own)
 
 
+def room_start(n):
+    """A start over every free cell of the suite's room map and the full circle, n particles, the twelve scans of the track
+    thinned to 64 rows -> what the filter settles on, scan by scan (run once: nothing is timed)."""
+    from utilities.mapping import OccupancyGrid2D
+    poses = np.array([(-1.0 + 0.25 * k, -0.5 + 0.02 * k, 0.05 * k) for k in range(12)])             # tests/gridmatch_ref.py: SCENE_POSES
+    room = OccupancyGrid2D(min_x=-14.0, max_x=14.0, min_y=-10.0, max_y=10.0, resolution=0.1)
+    for k, p in enumerate(poses):
+        room.update_scan(p[:2].copy(), synth.to_world(synth.scan(tuple(p), 50 + k), tuple(p)))
+    pf = room.particle_filter(n, seed=1, temperature=TEMPERATURE, half_width=HALF_WIDTH)
+    free = pf.free_cells().count()
+    pf.init_uniform()
+    track = []
+    for k, p in enumerate(poses):
+        if k:
+            a, d = poses[k - 1], p[:2] - poses[k - 1, :2]
+            c, s = np.cos(a[2]), np.sin(a[2])
+            pf.predict((c * d[0] + s * d[1], -s * d[0] + c * d[1], p[2] - a[2]), (0.05, 0.05, np.deg2rad(1.0)))
+        ess, ok = pf.weigh(synth.scan(tuple(p), 50 + k)[::32])
+        did = pf.maybe_resample(0.5)
+        est = pf.estimate()
+        track.append({"scan": k, "ess": round(ess, 1), "ok": ok, "resampled": did, "best_score": pf.last_sums[_lib.PF_SUM_SMAX],
+                      "error_m": round(float(np.hypot(*(est["mean"][:2] - p[:2]))), 3),
+                      "error_deg": round(float(np.degrees(abs((est["mean"][2] - p[2] + np.pi) % (2 * np.pi) - np.pi))), 2),
+                      "resultant": round(est["resultant"], 4)})
+    return {"particles": n, "free_cells": free, "track": track}
+
+
+def global_report():
+    pf = grid.particle_filter(2 ** 20, seed=5, planes=planes)
+    free = pf.free_cells()
+    frame = (grid.min_x, grid.min_y, grid.resolution, 0.0, 2.0 * np.pi)
+
+    def draw(n):
+        def run():
+            rc = L.icpmi_pf_draw_uniform(n, n, _ptr(free.index), *frame, _ptr(pf.pair_t), _ptr(pf.theta), _ptr(pf.cos_sin), None, _ptr(pf.draw_info),
+                                         pf.seed, 1, _stream())
+            assert rc == 0, rc
+        return run
+
+    small = grid.particle_filter(4096, seed=6, planes=planes)
+    rng = np.random.default_rng(6)
+    threshold = planes[0].threshold
+
+    def host_start():
+        f = grid.score_field()[0].cpu().numpy()                    # the field read back
+        ys, xs = np.nonzero((f != 0) & (f < threshold))
+        pick = rng.integers(0, len(xs), size=small.n)
+        small.set_poses(np.stack([grid.min_x + (xs[pick] + rng.random(small.n)) * grid.resolution,
+                                  grid.min_y + (ys[pick] + rng.random(small.n)) * grid.resolution, rng.uniform(-np.pi, np.pi, small.n)], axis=1))
+
+    variants = {"index": (free.build, BLOCK), "draw_4096": (draw(4096), BLOCK), "draw_65536": (draw(65536), BLOCK), "draw_1048576": (draw(2 ** 20), BLOCK),
+                "host_start": (host_start, 2), "index_again": (free.build, BLOCK)}
+    times = alternate(variants, SAMPLES, 2)
+    res = {name: stats(times[name]) for name in variants}
+    res["free_cells"] = free.count()
+    for n in (4096, 65536):
+        steps, _ = variants_of(n)
+        times = alternate(steps, SAMPLES, 2)
+        res[f"n{n}"] = {name: stats(times[name]) for name in steps}
+        res[f"n{n}"]["inject_adds_ms"] = round(float(np.median(times["step_inject"]) - np.median(times["step"])), 4)
+        res[f"n{n}"]["step_spread_ms"] = round(abs(float(np.median(times["step"]) - np.median(times["step_again"]))), 4)
+    res["room_start"] = room_start(2 ** 18)
+    return res
+
+
 out = {"grid": [grid.ny, grid.nx], "resolution": grid.resolution, "rows": ROWS, "block": BLOCK, "half_width": HALF_WIDTH, "temperature": TEMPERATURE,
        "counters": "none collected"}
+if GLOBAL:
+    out.update(global_report())
+    print(json.dumps(out))
+    sys.exit(0)
 for n in SIZES:
     variants, keep = variants_of(n)
     times = alternate(variants, SAMPLES, 2)
