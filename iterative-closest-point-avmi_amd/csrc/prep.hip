@@ -69,7 +69,13 @@ __device__ __forceinline__ uint32_t prep_polar_key21(double x, double y) {
 }
 __device__ __forceinline__ float prep_polar_image(uint32_t k21) { return (float)k21 * PREP_POLAR_Q - 3.14159265f; }
 
-template <int E>
+// MED3: the network's exchange is one median (sort.hpp).  It costs six registers through the sort, which the leanest
+// instantiations do not have below their occupancy step: prep_targets_kernel<0, *> (62 -> 68 VGPRs, 8 -> 7 waves a SIMD)
+// and <6, true> (70 -> 76, 7 -> 6) keep min / max / select; every other one is unchanged in registers, scratch and
+// occupancy and takes the median.
+constexpr bool prep_sort_med3(int kk, bool grid) { return !(kk == 0 || (kk == 6 && grid)); }
+
+template <int E, bool MED3>
 __device__ __forceinline__ void prep_sort_polar32(const double* __restrict__ P, int M, uint64_t* keys, uint32_t* rows) {
     uint32_t v[E];
 #pragma unroll
@@ -77,7 +83,7 @@ __device__ __forceinline__ void prep_sort_polar32(const double* __restrict__ P, 
         const int i = e * PREP_THREADS + (int)threadIdx.x;            // coalesced; any start order sorts the same
         v[e] = i < M ? (prep_polar_key21(P[2 * i], P[2 * i + 1]) << 11) | (uint32_t)i : 0xffffffffu;
     }
-    bitonic_sort_regs_fixed<uint32_t, E, PREP_THREADS>(v, reinterpret_cast<uint32_t*>(keys));
+    bitonic_sort_regs_fixed<uint32_t, E, PREP_THREADS, MED3>(v, reinterpret_cast<uint32_t*>(keys));
     __syncthreads();                                                   // the network's scratch is the key array written next
 #pragma unroll
     for (int e = 0; e < E; ++e) {
@@ -88,10 +94,10 @@ __device__ __forceinline__ void prep_sort_polar32(const double* __restrict__ P, 
     __syncthreads();
 }
 
-template <int E>
+template <int E, bool MED3>
 __device__ __forceinline__ void prep_sort_regs(const double* __restrict__ P, int M, int dir, uint64_t* by_row, uint64_t* keys,
                                                uint32_t* rows) {
-    if (dir == SWEEP_POLAR) { prep_sort_polar32<E>(P, M, keys, rows); return; }
+    if (dir == SWEEP_POLAR) { prep_sort_polar32<E, MED3>(P, M, keys, rows); return; }
     constexpr uint64_t ROW_MASK = 0x7ff;                               // rows below 2 048
     uint64_t v[E];
 #pragma unroll
@@ -162,9 +168,9 @@ __global__ __launch_bounds__(PREP_THREADS, (KK <= 13 ? ICPMI_PREP_WPS : (KK <= 1
         // (key, row) as ONE 64-bit element: the key's low 11 bits give way to the row, the network runs on registers
         // (sort.hpp: thread t owns slots t E .. t E + E - 1), and the rare neighbours whose keys agree in the 53 bits
         // that are left are put right afterwards from the full keys — the order is exactly the pair sort's.
-        if (lds.nsort == PREP_THREADS) prep_sort_regs<1>(P, M, dir, by_row, keys, rows);
-        else if (lds.nsort == 2 * PREP_THREADS) prep_sort_regs<2>(P, M, dir, by_row, keys, rows);
-        else prep_sort_regs<4>(P, M, dir, by_row, keys, rows);
+        if (lds.nsort == PREP_THREADS) prep_sort_regs<1, prep_sort_med3(KK, GRID)>(P, M, dir, by_row, keys, rows);
+        else if (lds.nsort == 2 * PREP_THREADS) prep_sort_regs<2, prep_sort_med3(KK, GRID)>(P, M, dir, by_row, keys, rows);
+        else prep_sort_regs<4, prep_sort_med3(KK, GRID)>(P, M, dir, by_row, keys, rows);
     } else {
         for (int i = threadIdx.x; i < npad; i += PREP_THREADS) {
             keys[i] = i < M ? f64_sortable(dir == SWEEP_POLAR ? polar_key(P[2 * i], P[2 * i + 1]) : proj(dir, P[2 * i], P[2 * i + 1])) : ~0ull;

@@ -66,7 +66,7 @@ __device__ __forceinline__ void bitonic_sort_packed(T* v, int npad) {
 // it took ~18 vector instructions per element and stage, DESIGN K5), so that each stage is: its partner through the
 // cheapest cross-lane move that reaches it — a DPP quad permutation or row (half) mirror / rotation, ds_swizzle inside 32
 // lanes, ds_bpermute across the halves of the wave (addresses computed once) —, one v_min, one v_max, one select on a lane
-// mask that is a constant of the stage.  Strides inside a thread are plain min / max pairs; the strides that cross waves
+// mask that is a constant of the stage (round 6: one median for 32-bit words, below).  Strides inside a thread are plain min / max pairs; the strides that cross waves
 // (6 of the 66 stages of 2 048 elements on 512 threads) go through LDS.  Same result as any sorting network on distinct
 // elements (the packed values are distinct: the row is part of them).
 template <int CTRL>
@@ -104,16 +104,50 @@ template <int L> __device__ __forceinline__ uint64_t sort_flip_lane(uint64_t v, 
     return ((uint64_t)sort_flip_lane<L>((uint32_t)(v >> 32), a63) << 32) | sort_flip_lane<L>((uint32_t)v, a63);
 }
 
-template <typename T, int E>
+// 32-bit words, one instruction per compare-exchange with a partner in another lane (round 6): for unsigned words
+// med3(a, b, 0) = min(a, b) and med3(a, b, ~0) = max(a, b) — for every pair, the pad word included —, so the median of
+// the lane's word, the partner's and a SELECT word (0 in the lane that keeps the minimum, all ones in the other) is the
+// whole exchange: v_med3_u32 instead of v_min, v_max and a select.  Which lane keeps the minimum is one bit of the lane id
+// in every stage inside a wave (bit log2 of the stride, or of half the flip block, in lanes), so six select words, made
+// once in front of the first stage, serve all of them; the stages across waves read one bit of the WAVE's number: their
+// word is a scalar.  Written as max(min(a, b), min(max(a, b), c)), the form the compiler's median pattern matches: no
+// inline assembly, so the hazard recogniser sees the instruction (a DPP move may not read a register a vector instruction
+// wrote within the last two slots).  There is no 64-bit median: the 64-bit network keeps its compare and two selects.
+__device__ __forceinline__ uint32_t sort_med3(uint32_t a, uint32_t b, uint32_t c) {
+    const uint32_t lo = a < b ? a : b, hi = a < b ? b : a, t = hi < c ? hi : c;
+    uint32_t r = lo < t ? t : lo;
+    // An empty statement the optimiser cannot look through (it emits nothing).  Without it every word after the network is
+    // a min / max expression 66 stages deep in which each level uses both its inputs twice, and the value analyses behind
+    // the callers' comparisons with the pad word walk all 2^66 paths: the compilation does not end.
+    // (It relies on the pattern being matched in front of it: `v_med3_u32` in the assembly of voxel.hip and prep.hip, and no
+    // v_min_u32 / v_max_u32 with a DPP operand, is the check after a compiler update.)
+    asm("" : "+v"(r));
+    return r;
+}
+constexpr int sort_log2(int x) { return x <= 1 ? 0 : 1 + sort_log2(x / 2); }
+
+// MED3 (32-bit words only; the default for them): the exchange above.  Without it the v_min, v_max and select of round 4,
+// every statement as it was — the 64-bit network, and the 32-bit one of the callers that opt out: the median needs six more
+// registers through the sort, whether the select words are held or made stage by stage, which costs the leanest
+// instantiations of the prepare kernel an occupancy step (prep.hip, prep_sort_med3; DESIGN K5).
+template <typename T, int E, bool MED3>
 struct SortNetRegs {
+    static_assert(!MED3 || sizeof(T) == 4, "there is no 64-bit median");
     T (&v)[E];
     T* lds;
     int base, lane, a32, a63;
+    uint32_t sel[6];                                                   // MED3: select word of lane bit b = 0 .. 5:
+    int wave;                                                          //   0 where the bit is clear (the lane keeps the minimum), else all ones; the wave's number, a scalar
     __device__ __forceinline__ SortNetRegs(T (&v_)[E], T* lds_) : v(v_), lds(lds_) {
         base = (int)threadIdx.x * E;
         lane = lane_id();
         a32 = (lane ^ 32) << 2;
         a63 = (63 - lane) << 2;
+        if constexpr (MED3) {
+#pragma unroll
+            for (int b = 0; b < 6; ++b) sel[b] = (uint32_t)((int)((uint32_t)lane << (31 - b)) >> 31);
+            wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x) / ICPMI_WAVE;
+        }
     }
     static __device__ __forceinline__ T mn(T a, T b) { return a < b ? a : b; }
     static __device__ __forceinline__ T mx(T a, T b) { return a < b ? b : a; }
@@ -128,30 +162,43 @@ struct SortNetRegs {
             }
         } else if constexpr (FLIP ? S <= E * ICPMI_WAVE : S < E * ICPMI_WAVE) {     // inside the wave
             constexpr int LB = FLIP ? S / E : S / E;                   // block (flip) or stride (xor) in lanes
-            const bool lower = FLIP ? (lane & (LB / 2)) == 0 : (lane & LB) == 0;
+            [[maybe_unused]] const bool lower = FLIP ? (lane & (LB / 2)) == 0 : (lane & LB) == 0;
             T o[E];
 #pragma unroll
             for (int e = 0; e < E; ++e) {
                 if constexpr (FLIP) o[e] = sort_flip_lane<LB>(v[E - 1 - e], a63);   // the mirror image: the partner's elements in reverse
                 else o[e] = sort_xor_lane<LB>(v[e], a32);
             }
-            // the lower lane of a pair keeps the minimum (the lane mask is a constant of the stage)
+            // the lower lane of a pair keeps the minimum (the lane bit is a constant of the stage)
 #pragma unroll
             for (int e = 0; e < E; ++e) {
-                if constexpr (sizeof(T) == 4) v[e] = lower ? mn(v[e], o[e]) : mx(v[e], o[e]);      // v_min, v_max, select: measured faster for 32 bits
+                if constexpr (MED3) v[e] = sort_med3(v[e], o[e], sel[sort_log2(FLIP ? LB / 2 : LB)]);      // one median
+                else if constexpr (sizeof(T) == 4) v[e] = lower ? mn(v[e], o[e]) : mx(v[e], o[e]);         // v_min, v_max, select
                 else v[e] = ((o[e] < v[e]) == lower) ? o[e] : v[e];                              // 64 bits: one compare, two selects
             }
         } else {                                                       // across waves: through LDS
 #pragma unroll
             for (int e = 0; e < E; ++e) lds[base + e] = v[e];
             __syncthreads();
+            // the partner lies above (x > i) where bit S (flip: S / 2) of i is clear: a bit of the wave's number
+            [[maybe_unused]] constexpr int WB = sort_log2((FLIP ? S / 2 : S) / (E * ICPMI_WAVE));
+            if constexpr (MED3) {
+                // all partners first, then the medians: interleaved with them (each ends in an asm statement) the loads of
+                // a mirror-image stage are no longer merged into one 128-bit access
+                uint32_t o[E];
 #pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const int i = base + e;
-                const int x = FLIP ? (i ^ (S - 1)) : (i ^ S);
-                const T o = lds[x];
-                if constexpr (sizeof(T) == 4) v[e] = x > i ? mn(v[e], o) : mx(v[e], o);
-                else v[e] = ((o < v[e]) == (x > i)) ? o : v[e];
+                for (int e = 0; e < E; ++e) o[e] = lds[FLIP ? ((base + e) ^ (S - 1)) : ((base + e) ^ S)];
+#pragma unroll
+                for (int e = 0; e < E; ++e) v[e] = sort_med3(v[e], o[e], 0u - (uint32_t)((wave >> WB) & 1));
+            } else {
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    const int i = base + e;
+                    const int x = FLIP ? (i ^ (S - 1)) : (i ^ S);
+                    const T o = lds[x];
+                    if constexpr (sizeof(T) == 4) v[e] = x > i ? mn(v[e], o) : mx(v[e], o);
+                    else v[e] = ((o < v[e]) == (x > i)) ? o : v[e];
+                }
             }
             __syncthreads();
         }
@@ -168,9 +215,9 @@ struct SortNetRegs {
 
 // Sorts NPAD = E * THREADS packed values ascending; thread t owns elements t*E .. t*E + E-1 on entry and on return.
 // lds: NPAD elements of scratch; ends with a barrier after its last LDS stage (callers that reuse `lds` at once add theirs).
-template <typename T, int E, int THREADS>
+template <typename T, int E, int THREADS, bool MED3 = sizeof(T) == 4>
 __device__ __forceinline__ void bitonic_sort_regs_fixed(T (&v)[E], T* lds) {
-    SortNetRegs<T, E> net(v, lds);
+    SortNetRegs<T, E, MED3> net(v, lds);
     net.template levels<2, E * THREADS>();
 }
 
