@@ -327,7 +327,8 @@ int icpmi_nn_prepared_batch(const double* pts, const int32_t* off_dev, const int
  * For every angle a (given as cos, sin pairs — computed by the caller with the
  * reference's own NumPy calls): mean over the rows of src_c of the squared
  * nearest-neighbour distance of (src_c @ R(a).T + shift) in tgt, R = [[c,-s],[s,c]].
- * One launch for a whole sweep.  src_c: (n_src, 2), tgt: (n_tgt, 2), row-major. */
+ * One launch for a whole sweep.  src_c: (n_src, 2), tgt: (n_tgt, 2), row-major.  An angle whose cos / sin is NaN (or a
+ * source row that is) scores NaN, as the mean of NumPy's distances would — not the +inf a scan that skips NaN leaves. */
 int icpmi_rotation_scores(const double* src_c, int32_t n_src, const double* tgt, int32_t n_tgt,
                           const double* cos_sin, int32_t n_angles, double shift_x, double shift_y,
                           double* out_scores, void* stream);

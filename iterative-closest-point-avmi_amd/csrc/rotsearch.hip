@@ -49,6 +49,9 @@ __device__ __forceinline__ double rs_score_angle(const double* __restrict__ src,
         double best[1];
         int bestj[1];
         rs_nearest_tiled(tgt, m, tile, p, best, bestj);
+        // A row that is not a number (a NaN angle in the caller's table) has no nearest target: the scan's fmin drops every
+        // NaN distance and would leave +inf, a score no arg-min ever names.  NaN instead, which np.argmin names first.
+        if (p[0][0] != p[0][0] || p[0][1] != p[0][1]) best[0] = __builtin_nan("");
         if (i < n) {
             const double d = sqrt(best[0]);                   // KDTree distance ...
             acc[0] += d * d;                                  // ... squared, features.py:218
