@@ -681,8 +681,10 @@ int icpmi_bresenham_cells(const int32_t* segs, const int64_t* cell_off, int32_t 
  * shares its launch with the finalise pass of the previous group (the other set of regions).  A region covers the
  * box the rays stay in (icpmi_grid_update_scans_box; the whole grid otherwise), so a group holds up to 32 scans
  * when the box is at most 1/16 of the grid and at least 2 always: a replay of S scans is about S/32 + 1 launches.
- * Every call leaves the workspace all zero again; a call that is refused (icpmi_grid_update_plan lists the reasons) is
- * refused before anything is started.
+ * Every call leaves the four counter grids — the first 16 * ny * nx bytes — all zero again; the bounding-box slots and the
+ * scans' cell boxes behind them keep what the call's last group left there.  No call depends on them: a call clears the
+ * slots unless it is the one-scan call with a box, which does not read them, and writes the boxes before it reads them.
+ * A call that is refused (icpmi_grid_update_plan lists the reasons) is refused before anything is started.
  * scan_seq: ignored (kept for binary compatibility; calls are independent).
  * full_clip != 0 clips every cell of the grid on the first scan (needed only
  * when cells may lie outside [lo, hi] beforehand).
