@@ -648,6 +648,68 @@ int icpmi_history_feature_align(const icpmi_history* h, const icpmi_feature_stor
                                 const double* init_in, double* init_out, double* out_records, void* workspace,
                                 size_t workspace_bytes, void* stream);
 
+/* ---- appearance signatures: loop-closure candidates by what a scan looks like, not by where the pose graph puts it ------
+ * _find_loop_candidates (slam.py:230-268) keeps the past scans whose position ESTIMATE lies near the current one, so a
+ * revisit drift has carried beyond its threshold is never matched.  A history can keep, per scan, a binary polar occupancy
+ * image about the sensor (a 2-D Scan Context): ICPMI_SIG_RINGS rings of ring_width from min_range outwards by
+ * ICPMI_SIG_SECTORS sectors of 2 pi / 64 from the x axis counter-clockwise, 260 bytes a scan, and rank its scans against
+ * one by the overlap of the images under the best of the 64 rotations.  Integers end to end and no transcendental
+ * function on the device: every result is bit-equal to a NumPy restatement (tests/signatures_ref.py).
+ * The store is the caller's device memory, addressed by the history's scan_capacity:
+ *   sig      [scan_capacity][ICPMI_SIG_RINGS] uint64: bit s of word r — ring r, sector s holds at least one raw row;
+ *   sig_bits [scan_capacity] int32: the set bits of the scan's 32 words;
+ *   tables   [ICPMI_SIG_TABLE_DOUBLES] double, made on the host: edge2[33], edge2[j] = (min_range + j * ring_width)^2,
+ *            ascending; then bc[k] = cos(k pi / 32) and bs[k] = sin(k pi / 32) for k = 1 .. 15 (15 and 15).
+ * (The store is three pointers in the argument lists, not a struct: ring_width and min_range reach the device through
+ * edge2 alone.)
+ * The rule of a RAW row (x, y) of the sensor frame (h->pts; no voxel size plays a part), each product and sum rounded:
+ *   d2 = x * x + y * y;  ring = #{ j in 0 .. 32 : d2 >= edge2[j] } - 1;  the row is skipped unless 0 <= ring < 32 (NaN: every
+ *   comparison false; inf: ring 32; a return below min_range; a row beyond the reach);
+ *   q = (y >= 0) ? (x > 0 ? 0 : 1) : (x < 0 ? 2 : 3);  (u, v) = (x, y), (y, -x), (-x, -y), (-y, x) for q = 0 .. 3 (exact);
+ *   sector = 16 q + #{ k in 1 .. 15 : v * bc[k] >= u * bs[k] }. */
+#define ICPMI_SIG_RINGS 32
+#define ICPMI_SIG_SECTORS 64
+#define ICPMI_SIG_TABLE_DOUBLES 63
+#define ICPMI_SIG_MAX_TOP 64
+#define ICPMI_SIG_REC_INTS 4
+#define ICPMI_SIG_REC_ID 0
+#define ICPMI_SIG_REC_SCORE 1
+#define ICPMI_SIG_REC_SHIFT 2
+#define ICPMI_SIG_REC_BEST 3
+#define ICPMI_SIG_TILE 64         /* candidates a workgroup of the pair kernel takes */
+
+/* Writes sig and sig_bits of the clouds [first, first + n_new) of the history and leaves every other cloud's alone.  Uses
+ * pts, off_dev and the capacities of h; off_host mirrors off_dev.  A cloud of zero rows gets 32 zero words and 0 bits;
+ * nothing caps a cloud's rows (they are streamed).  One launch; n_new == 0: none, ICPMI_OK.  Refused on the host, before
+ * the launch: a null pointer, a range beyond the scan capacity, a negative row count or rows beyond the row capacity
+ * (ICPMI_ERR_ARG). */
+int icpmi_history_signatures_add(const icpmi_history* h, uint64_t* sig, int32_t* sig_bits, const double* tables,
+                                 const int32_t* off_host, int32_t first, int32_t n_new, void* stream);
+
+/* Ranks scans against scans by their signatures.  query_ids [n_queries], lo, hi [n_queries] (device): the candidates of
+ * query i are the scans c with lo[i] <= c < hi[i], clipped to [0, n_scans); an empty range is fine.  A query id is a
+ * cloud of the store, n_scans (a source staged behind the last scan) included; one outside [0, scan_capacity) has no
+ * candidates.  For a candidate with words B against the query's A:
+ *   inter(s) = sum over r of popcount(A[r] & rotl64(B[r], s)), s = 0 .. 63;  best = the largest, shift = the LOWEST s with it;
+ *   union = bits(A) + bits(B) - best;  score = union ? (best * 65535) / union : 0 (unsigned integer division: 0 .. 65535).
+ * rotl by s turns the candidate's image counter-clockwise by s sectors, so the query's heading is the candidate's minus
+ * s * 2 pi / 64.
+ * out_records [n_queries][top_k][ICPMI_SIG_REC_INTS] int32 {id, score, shift, best}: the top_k candidates by descending
+ * score, equal scores by ascending id; slots without a candidate {-1, 0, 0, 0}.  1 <= top_k <= ICPMI_SIG_MAX_TOP.
+ * out_all (optional) [n_queries][n_scans] int32: (score << 8) | shift of every candidate, -1 outside the query's range.
+ * workspace: icpmi_history_similar_workspace_bytes(n_queries, n_scans, top_k) bytes, 16-byte aligned (the rows of
+ * out_all for a call without one; 0 for arguments the entry refuses; at least 256).  Only scan_capacity of h is used.
+ * At most two launches (every pair; the selection), nothing returns to the host; n_queries == 0: none, ICPMI_OK.
+ * Refused on the host, before any launch: n_queries or n_scans negative, n_scans above the scan capacity, top_k outside
+ * [1, ICPMI_SIG_MAX_TOP], a null pointer other than out_all, a misaligned workspace (ICPMI_ERR_ARG); more than 65 535
+ * queries or n_queries * n_scans reaching 2^31 (ICPMI_ERR_UNSUPPORTED); a workspace below its size (ICPMI_ERR_WORKSPACE).
+ * A row exactly on the negative x axis (y = +0 or -0, x < 0) belongs to the second quadrant by the rule above and lands
+ * in sector 31, not 32: the one place where a quarter turn of a cloud is not a rotation of its image by 16 sectors. */
+size_t icpmi_history_similar_workspace_bytes(int32_t n_queries, int32_t n_scans, int32_t top_k);
+int icpmi_history_similar(const icpmi_history* h, const uint64_t* sig, const int32_t* sig_bits, const int32_t* query_ids,
+                          int32_t n_queries, const int32_t* lo, const int32_t* hi, int32_t n_scans, int32_t top_k,
+                          int32_t* out_records, int32_t* out_all, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- OccupancyGrid2D, utilities/mapping.py ---------------------------------
  * world -> cell index, mapping.py:57-60,94-98: floor((w - min) / res), float64
  * IEEE division, result as int64. */

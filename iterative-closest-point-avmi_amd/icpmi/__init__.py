@@ -20,7 +20,7 @@ _INFORMATION = ("information_set", "icp_information", "unpack_information", "edg
 def __getattr__(name):
     # icpmi.ScanHistory / icpmi.find_loop_candidates: icpmi.history's, imported on first use (that module needs torch;
     # `import icpmi` alone — the build, the scan generator in spawned processes — must not)
-    if name in ("ScanHistory", "find_loop_candidates", "history"):
+    if name in ("ScanHistory", "find_loop_candidates", "similar_loop_candidates", "history"):
         import importlib
         history = importlib.import_module(".history", __name__)
         return history if name == "history" else getattr(history, name)

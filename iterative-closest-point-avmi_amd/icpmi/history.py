@@ -17,6 +17,17 @@ the map and the submap buffer (slam.py:271-277, 612-615).  The raw rows are here
 launch of ``icpmi_history_world_rows`` — NumPy's ``points @ T[:2, :2].T + T[:2, 2]`` bit for bit — and
 ``OccupancyGrid2D.rebuild_from_history`` / ``RollingSubmap.reset_from_history`` take the history and the poses.
 
+``find_loop_candidates`` trusts the pose estimates: a revisit that drift has carried beyond its threshold is never tried.
+A history built with ``signature={}`` also keeps a polar occupancy image of every scan (260 bytes) and finds candidates by
+appearance, on the device, whatever the headings and the estimates:
+
+    hist = ScanHistory(..., signature={"ring_width": 0.5})
+    cands = similar_loop_candidates(hist, sid, min_interval=50, max_candidates=5, min_score=0.3)   # [(idx, score), ...]
+    m = hist.match(sid, [k for k, _ in cands], ...)
+
+``hist.similar(sources, top_k=...)`` is the query behind it (``SimilarScans``: ids, scores, a heading estimate per
+candidate, optionally the whole similarity row).
+
 ``match`` returns a ``RunIcpPairBatch`` whose clouds are the resident ones: ``run()`` / ``unpack()`` / ``first_accepted()``
 are that class's own code, and its records are the batch path's bit for bit (same kernels on the same filtered rows).
 
@@ -62,6 +73,72 @@ def find_loop_candidates(current_pose, poses, current_idx, distance_threshold, m
     idx = np.flatnonzero(keep)
     idx = idx[np.argsort(dist[idx], kind="stable")][:max_candidates]
     return [(int(k), float(dist[k])) for k in idx]
+
+
+SIG_DEFAULTS = {"ring_width": 0.5, "min_range": 0.1}
+
+
+def signature_config(signature):
+    """The ``signature`` argument of ``ScanHistory`` over ``SIG_DEFAULTS``, checked -> {ring_width, min_range} as floats."""
+    unknown = set(signature) - set(SIG_DEFAULTS)
+    if unknown:
+        raise ValueError(f"signature takes {sorted(SIG_DEFAULTS)}: got {sorted(unknown)}")
+    cfg = {k: float(signature.get(k, v)) for k, v in SIG_DEFAULTS.items()}
+    for k, v in cfg.items():
+        if not (v > 0 and np.isfinite(v)):
+            raise ValueError(f"signature[{k!r}] must be positive and finite: got {v!r}")
+    return cfg
+
+
+def signature_tables(ring_width, min_range):
+    """The 63 doubles of a signature store (include/icpmi.h): edge2[33] = (min_range + j * ring_width) ** 2, then cos and
+    sin of k pi / 32 for k = 1 .. 15.  The device only compares against them: no libm of its own has to agree with NumPy's."""
+    edge = min_range + np.arange(_lib.SIG_RINGS + 1, dtype=np.float64) * ring_width
+    a = np.arange(1, 16, dtype=np.float64) * np.pi / 32
+    return np.ascontiguousarray(np.concatenate([edge * edge, np.cos(a), np.sin(a)]))
+
+
+def shift_yaw(shift):
+    """The heading of a source relative to a candidate that a record's ``shift`` implies, in (-pi, pi]: rotating the
+    candidate's image by ``shift`` sectors counter-clockwise gives the source's, and a scene seen turned counter-clockwise
+    is a sensor turned clockwise — source yaw - candidate yaw = -shift * 2 pi / 64 (to within a sector, and to within the
+    symmetries of the place)."""
+    yaw = -(np.asarray(shift, dtype=np.float64) % _lib.SIG_SECTORS) * (2.0 * np.pi / _lib.SIG_SECTORS)
+    return np.where(yaw <= -np.pi, yaw + 2.0 * np.pi, yaw)
+
+
+def similar_args(ids, n_scans, top_k=10, min_interval=0, lo=None, hi=None):
+    """The host side of ``ScanHistory.similar``, checked: (ids, lo, hi) as int32 arrays, one entry per source.  ids: scan ids
+    in [0, n_scans] — n_scans is a staged source.  Without ``lo`` / ``hi`` the candidates of source id are the scans
+    [0, id - min_interval + 1): the reference's ``current_idx - i < min_interval -> continue`` (slam.py:255).  ``lo`` /
+    ``hi``: one integer for all sources or one per source; the device clips them to [0, n_scans)."""
+    if not 1 <= int(top_k) <= _lib.SIG_MAX_TOP:
+        raise ValueError(f"top_k must lie in [1, {_lib.SIG_MAX_TOP}]: got {top_k}")
+    if int(min_interval) < 0:
+        raise ValueError(f"min_interval must not be negative: got {min_interval}")
+    ids = _scan_ids(ids, ("sources", "source ids"), n_scans + 1)
+
+    def bound(v, default, name):
+        if v is None:
+            return default
+        a = np.asarray(v)
+        if a.ndim > 1 or not np.issubdtype(a.dtype, np.integer) or (a.ndim == 1 and len(a) != len(ids)):
+            raise ValueError(f"{name} must be one integer or one per source ({len(ids)})")
+        return np.ascontiguousarray(np.broadcast_to(np.clip(a, -2 ** 31, 2 ** 31 - 1), ids.shape), dtype=np.int32)
+    return ids, bound(lo, np.zeros(len(ids), dtype=np.int32), "lo"), bound(hi, ids - np.int32(min_interval) + 1, "hi")
+
+
+def similar_loop_candidates(hist, source, *, min_interval, max_candidates, min_score):
+    """Loop-closure candidates by appearance -> [(idx, score), ...], the shape of ``find_loop_candidates``' return (its
+    second entry a similarity in [0, 1], best first, where that one's is a distance, nearest first): the at most
+    ``max_candidates`` scans at least ``min_interval`` scans older than ``source`` (a scan id, or an (n, 2) array taken as the
+    scan after the last) that look most like it, those scoring below ``min_score`` dropped.  ``[k for k, _ in cands]``
+    goes into ``hist.match``.  One query of ``hist.similar``; synchronises."""
+    if not (isinstance(source, (int, np.integer)) or np.ndim(source) == 2):
+        raise ValueError("source must be one scan id or one (n, 2) array")
+    found = hist.similar(source, top_k=max_candidates, min_interval=min_interval)
+    found.run()
+    return [(k, score) for k, score, _ in found.unpack()[0] if score >= min_score]
 
 
 def scan_reach(points):
@@ -201,6 +278,50 @@ class HistoryMatch(RunIcpPairBatch):
         return super().run(events)
 
 
+class SimilarScans:
+    """What ``ScanHistory.similar`` returns: one ``icpmi_history_similar`` query, its buffers allocated and its arguments
+    uploaded.  ``run()`` enqueues it on the current stream (two launches, nothing returns to the host) and may be repeated;
+    ``unpack()`` synchronises.  Valid while the history keeps its buffers and its staged source, as a ``HistoryMatch`` is."""
+
+    def __init__(self, hist, ids, lo, hi, top_k, all_scores, staged):
+        self.history, self.top_k, self.n_queries, self.n_scans = hist, int(top_k), len(ids), hist.n_scans
+        self.layout_generation = hist.layout_generation
+        self.stage_generation = hist.stage_generation if staged else None
+        dev = hist.device
+        self.ids_host = ids
+        self.query_ids, self.lo, self.hi = (torch.from_numpy(a).to(dev) for a in (ids, lo, hi))
+        self.records_dev = torch.zeros((self.n_queries, self.top_k, _lib.SIG_REC_INTS), dtype=torch.int32, device=dev)
+        self.all_dev = torch.zeros((self.n_queries, self.n_scans), dtype=torch.int32, device=dev) if all_scores else None
+        need = _lib.lib().icpmi_history_similar_workspace_bytes(self.n_queries, self.n_scans, self.top_k)
+        if need == 0:
+            raise ValueError(f"{self.n_queries} sources against {self.n_scans} scans: too many pairs for one query (2^31 - 1 at most, "
+                             "65 535 sources at most)")
+        self.ws = torch.zeros(need, dtype=torch.uint8, device=dev)
+        self.records = self.all = None                             # NumPy arrays, from unpack()
+
+    def run(self):
+        h = self.history
+        if h.layout_generation != self.layout_generation:
+            raise _lib.IcpmiError("the history has grown since this query was made: call similar() again")
+        if self.stage_generation is not None and h.stage_generation != self.stage_generation:
+            raise _lib.IcpmiError("the staged source of this query has been overwritten: call similar() again")
+        check(_lib.lib().icpmi_history_similar(C.byref(h.state), _ptr(h.sig), _ptr(h.sig_bits), _ptr(self.query_ids), self.n_queries,
+                                               _ptr(self.lo), _ptr(self.hi), self.n_scans, self.top_k, _ptr(self.records_dev),
+                                               _ptr(self.all_dev), _ptr(self.ws), self.ws.numel(), _stream()), "history_similar")
+        return self.records_dev
+
+    def unpack(self):
+        """-> per source, the list of its (id, score in [0, 1], yaw) best first — yaw: ``shift_yaw`` of the record's shift,
+        the heading of the source relative to that candidate.  Leaves ``records`` (n_sources, top_k, 4) int32 {id, score,
+        shift, best} and ``all`` (n_sources, n_scans) int32 (score << 8) | shift, -1 outside a source's range (None without
+        ``all_scores``) as NumPy arrays.  Synchronises."""
+        self.records = self.records_dev.cpu().numpy()
+        self.all = None if self.all_dev is None else self.all_dev.cpu().numpy()
+        yaw = shift_yaw(self.records[:, :, _lib.SIG_REC_SHIFT])
+        return [[(int(r[_lib.SIG_REC_ID]), r[_lib.SIG_REC_SCORE] / 65535.0, float(y)) for r, y in zip(recs, yaws) if r[_lib.SIG_REC_ID] >= 0]
+                for recs, yaws in zip(self.records, yaw)]
+
+
 class ScanHistory:
     """An append-only set of 2-D scans (at most 4096 rows each: the on-chip kernels) resident on one device, each filtered
     at the ICP voxel size and at the rotation search's, with its mean and both search orders (and normals from ``normal_k``
@@ -214,13 +335,20 @@ class ScanHistory:
     derives from a cloud alone — the filter at the feature voxel size, curvature, keypoints, descriptors — so that
     ``match(alignment_method="features" / "both")`` is resident too.  Its cloud-side keys (``FEAT_CLOUD_KEYS``) over
     ``FEAT_DEFAULTS`` fix that store: 24 more bytes per row and 12 + 260 * kp_stride bytes per scan (27 052 at the
-    reference's ``top_n`` of 100).  ``None``: no store, and ``match`` refuses those two methods."""
+    reference's ``top_n`` of 100).  ``None``: no store, and ``match`` refuses those two methods.
+
+    ``signature`` (a dict, possibly empty: ``ring_width`` 0.5 and ``min_range`` 0.1 unless given, in the scans' unit): the
+    history also keeps an appearance signature of every scan — a binary polar occupancy image of its raw rows about the
+    sensor, 32 rings by 64 sectors, 260 bytes a scan (include/icpmi.h) — and ``similar`` ranks scans against a scan by
+    it, whatever their headings and wherever the pose graph believes them to be.  ``None``: no signatures, nothing
+    allocated, and ``similar`` refuses."""
 
     def __init__(self, voxel_size=0.06, normal_k=10, rotation_voxel_size=0.3, scan_capacity=256, row_capacity=None, device=None,
-                 feat_cfg=None):
+                 feat_cfg=None, signature=None):
         require_gpu()
         if not voxel_size > 0 or not rotation_voxel_size > 0:
             raise ValueError("voxel sizes must be positive")
+        self.sig_cfg = None if signature is None else signature_config(signature)
         self.feat_cfg = self.store = None
         if feat_cfg is not None:
             self.feat_cfg = {k: feat_cfg.get(k, FEAT_DEFAULTS[k]) for k in FEAT_CLOUD_KEYS}
@@ -238,6 +366,8 @@ class ScanHistory:
         self.allow_polar = True            # until a scan above 2048 rows arrives (the ICP kernels for such targets walk projections)
         self.layout_generation = self.stage_generation = 0
         self.scan_capacity = self.row_capacity = 0
+        if self.sig_cfg is not None:
+            self.sig_tables = torch.from_numpy(signature_tables(**self.sig_cfg)).to(self.device)
         scan_capacity = max(int(scan_capacity), 1)
         self._allocate(scan_capacity, max(int(row_capacity), 1) if row_capacity is not None else 1024 * scan_capacity)
 
@@ -275,6 +405,10 @@ class ScanHistory:
             self.ft_desc, self.ft_desc_len = torch.zeros((S, K, _lib.FT_DESC_STRIDE), **f64), torch.zeros(S, **i32)
             per_row += [("ft_vox", None)]
             per_scan += [("ft_vox", "cnt"), ("ft_kp", None), ("ft_kp_cnt", None), ("ft_desc", None), ("ft_desc_len", None)]
+        if self.sig_cfg is not None:
+            # the signature store: 32 words and their bit count per scan (int64 holds the uint64 words: the bits are what matters)
+            self.sig, self.sig_bits = torch.zeros((S, _lib.SIG_RINGS), dtype=torch.int64, device=dev), torch.zeros(S, **i32)
+            per_scan += [("sig", None), ("sig_bits", None)]
         if old:
             pick = lambda d, name, part: getattr(d[name], part or "pts") if isinstance(d[name], CloudSet) else d[name]   # noqa: E731
             for name, part in per_row:
@@ -325,12 +459,15 @@ class ScanHistory:
         self.stage_generation += 1
         return int(ends[-1])
 
-    def _process(self, first, n, prepare, features=True):
+    def _process(self, first, n, prepare, features=True, signatures=True):
         off_host = self.raw.off_host.ctypes.data_as(C.c_void_p)
         check(_lib.lib().icpmi_history_add(C.byref(self.state), off_host, first, n, 1 if prepare else 0, _stream()), "history_add")
         if features and self.store is not None:
             check(_lib.lib().icpmi_history_features_add(C.byref(self.state), C.byref(self.store), off_host, first, n, _stream()),
                   "history_features_add")
+        if signatures and self.sig_cfg is not None:
+            check(_lib.lib().icpmi_history_signatures_add(C.byref(self.state), _ptr(self.sig), _ptr(self.sig_bits), _ptr(self.sig_tables),
+                                                          off_host, first, n, _stream()), "history_signatures_add")
 
     @staticmethod
     def _clouds(clouds):
@@ -365,6 +502,41 @@ class ScanHistory:
             raise ValueError("this history keeps no features (feat_cfg=None)")
         return self.ft_vox.cnt[:self.n_scans].cpu().numpy(), self.ft_kp_cnt[:self.n_scans].cpu().numpy()
 
+    def signatures(self, ids=None):
+        """(words (n, 32) uint64, bits (n,) int32) of the scans ``ids`` (every scan in order without) on the host: bit s of
+        word r — ring r, sector s of the scan's polar image holds a raw row (synchronises); needs ``signature``."""
+        if self.sig_cfg is None:
+            raise ValueError("this history keeps no signatures (signature=None)")
+        if ids is None:
+            words, bits = self.sig[:self.n_scans], self.sig_bits[:self.n_scans]
+        else:
+            at = torch.from_numpy(_scan_ids(ids, ("ids", "scan ids"), self.n_scans).astype(np.int64)).to(self.device)
+            words, bits = self.sig[at], self.sig_bits[at]
+        return words.cpu().numpy().view(np.uint64), bits.cpu().numpy()
+
+    def similar(self, sources, *, top_k=10, min_interval=0, lo=None, hi=None, all_scores=False):
+        """The scans that look most like each source, whatever the headings -> a ``SimilarScans`` (``run()``, then
+        ``unpack()``).  ``sources``: a scan id, a sequence of ids, or ONE (n, 2) array, which is staged behind the last scan as
+        ``match`` stages its source, given a signature for this query and not added — it counts as scan id ``len(self)``.
+        The candidates of source id are the scans [0, id - min_interval + 1) (slam.py:255: at least ``min_interval`` scans
+        older; 0: the source itself included, with score 1), or [lo, hi) where given (one integer or one per source).  Per
+        source the ``top_k`` (1 .. 64) best by score — the overlap of the two polar images over their union under the best
+        of the 64 rotations, 0 .. 65535 — equal scores by lower id.  ``all_scores``: every candidate's score and shift as
+        well, an (n_sources, n_scans) array (all scans as sources: the similarity matrix of the run)."""
+        if self.sig_cfg is None:
+            raise ValueError("this history keeps no signatures (signature=None)")
+        staged = not isinstance(sources, (int, np.integer)) and np.ndim(sources) == 2
+        if staged:
+            ids = [self.n_scans]
+        else:
+            ids = [int(sources)] if isinstance(sources, (int, np.integer)) else sources
+            ids = _scan_ids(ids, ("sources", "source ids"), self.n_scans)          # (a staged source is named by passing it)
+        args = similar_args(ids, self.n_scans, top_k, min_interval, lo, hi)
+        if staged:
+            # cloud n_scans, for this query: rows_used stays; filtered too, so that a match of the same array finds its state
+            self._place(self._clouds([sources]), self.n_scans, prepare=False, features=False)
+        return SimilarScans(self, *args, top_k, all_scores, staged)
+
     def add(self, points):
         """Append one scan (slam.py:554) -> its id."""
         return self.add_many([points])[0]
@@ -385,8 +557,8 @@ class ScanHistory:
         if redo:
             # a target above 2048 rows makes the ICP launch walk projections for every target of its batch: the earlier
             # scans, in bearing order until now, are put in order again (once in a history's life; their raw rows are here)
-            # (their features do not depend on the search order: the store is left alone)
-            self._process(0, first, True, features=False)
+            # (their features and signatures do not depend on the search order: those stores are left alone)
+            self._process(0, first, True, features=False, signatures=False)
         return list(range(first, self.n_scans))
 
     def match(self, source, candidates, *, error_threshold=1e-7, max_iterations=100, method="point_to_line", max_corr_dist=None,
